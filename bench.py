@@ -1,6 +1,7 @@
 """Headline benchmark: images/sec forward+backward of the ASY-VRNet fusion hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--phi l|nano|...] [--batch 8] [--size 512]
+                    [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 (one rank per GPU, RCCL).  A "step" is one forward+backward pass of EfficientVRNet over one
@@ -8,7 +9,11 @@ synthetic batch (BASELINE.json configs[1]: bs=8/GPU, 512x512 image + 4x512x512 r
 heads), driven by the fixed scalar sum_k mean(det_k^2) + mean(seg^2).  Inputs are resident in HBM
 before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step when --dump-outputs is given
+(dump_outputs(): loss, parameter gradients, BatchNorm running statistics, as DIR/<name>.npy) and prints the line, whose
+`roofline` and `cpu_baseline` are then null.
+
+Extra objects in the line, measured only with --full (separate runs after the timed steps):
   roofline      dominant kernel class (implicit-GEMM conv fwd/dgrad on the fp32 MFMA): algorithmic FLOPs per
                 launch / average launch duration, measured with HIP events on the launch stream in an
                 instrumented, serialised replay of the timed steps (the timed region itself runs as one captured
@@ -128,14 +133,55 @@ def loss_of(det, seg):
     return sum((d * d).mean() for d in det) + (seg * seg).mean()
 
 
+INPUT_POOL = 8          # distinct synthetic batches; step i uses batch i % INPUT_POOL
+
+
 def make_batches(n, batch, size, rank, device):
+    """min(n, INPUT_POOL) seeded batches on `device`.  The pool keeps set-up time and memory independent of the step count
+    (drawing one batch of the headline config on the host takes ~0.1 s, longer than a step); every step still copies its
+    batch into the captured graph's static inputs."""
     out = []
-    for s in range(n):
+    for s in range(min(n, INPUT_POOL)):
         g = torch.Generator().manual_seed(1234 + 1000 * rank + s)
         x = torch.randn((batch, 3, size, size), generator=g)
         r = torch.rand((batch, 4, size, size), generator=g)
         out.append((x.to(device), r.to(device)))
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def seeded_sample(flat, cap, seed):
+    """`flat` (1-D) itself when it has at most `cap` elements, else its values at a fixed, seeded, sorted index set of at
+    most `cap` elements (the same set in every run for the same length)."""
+    if flat.numel() <= cap:
+        return flat
+    idx = torch.randint(0, flat.numel(), (cap,), generator=torch.Generator().manual_seed(seed)).unique()
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, model, loss, grad_cap=1 << 23, buffer_cap=1 << 21):
+    """What a caller of the timed step receives from its last replay, as float32 .npy files under `path`:
+      loss.npy          the scalar that drove the backward pass
+      param_grads.npy   every parameter's gradient, flattened and concatenated in named_parameters() order (zeros for a
+                        parameter without one); a seeded sample of grad_cap elements when larger (phi = l: 49.8 M)
+      bn_buffers.npy    the floating-point buffers (BatchNorm running statistics after the W + K steps), same rule
+    At most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    with torch.no_grad():
+        grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float()
+                           for p in model.parameters()])
+        bufs = torch.cat([b.reshape(-1).float() for b in model.buffers() if b.dtype.is_floating_point])
+        arrays = {"loss": loss.detach().float().reshape(()), "param_grads": seeded_sample(grads, grad_cap, 1),
+                  "bn_buffers": seeded_sample(bufs, buffer_cap, 2)}
+    total = 0
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= DUMP_LIMIT_BYTES, total
 
 
 class ConvTimer:
@@ -292,14 +338,17 @@ def cpu_model():
 def cpu_baseline(phi, size, batch, seed_sd):
     """the CPU oracle (the build's restatement of the reference, kind "port") forward+backward on the host
     cores at the benchmark's own batch (bs 8 by default), 1 warm-up + 2 timed iterations (a bounded sample: ~10 s per
-    iteration for phi=l at bs 8), plus a bs=1 eval forward; threads = cores this process may use, capped at 32
-    (measured in round 1: more threads make the oracle slower)."""
+    iteration for phi=l at bs 8), plus a bs=1 eval forward; threads = cores this process may use (its affinity mask, and
+    OMP_NUM_THREADS where set: a shared host may grant fewer cores than it shows), capped at 32 (measured in round 1: more
+    threads make the oracle slower)."""
     from oracle import vrnet_oracle as O
     import asy_vrnet_amd as A
     try:
         avail = len(os.sched_getaffinity(0))
     except AttributeError:
         avail = os.cpu_count() or 1
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        avail = min(avail, int(os.environ["OMP_NUM_THREADS"]))
     torch.set_num_threads(max(1, min(avail, 32)))
     m = A.EfficientVRNet(4, 9, phi, img_size=size)
     A.randomize_state_dict(m.state_dict(), seed=seed_sd)
@@ -375,7 +424,13 @@ def main():
     ap.add_argument("--plane-gemms", default=None, help="ClusterBlock GEMMs on bf16-plane operands (csrc/pgemm.hip): off, fwd, wgrad, fwd+wgrad "
                     "(default: off in fp32, fwd+wgrad in bf16 mode) (A/B aid)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one captured hipGraph per step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (dump_outputs())")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline (instrumented replay) and the CPU baseline")
     args = ap.parse_args()
+    if args.detail and not args.full:
+        ap.error("--detail prints from the instrumented replay of --full")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # Started directly (not by torchrun): start the N ranks ourselves, as a CHILD process, before anything in this
@@ -434,11 +489,13 @@ def main():
     batches = make_batches(args.warmup + args.steps, args.batch, args.size, rank, dev)
 
     def eager_step(i):
-        x, r = batches[i]
+        x, r = batches[i % len(batches)]
         if net is model:
             model.zero_grad(set_to_none=True)
         det, seg = net(x, r)
-        loss_of(det, seg).backward()
+        loss = loss_of(det, seg)
+        loss.backward()
+        return loss.detach()
 
     launch = "eager"
     step = eager_step
@@ -449,7 +506,7 @@ def main():
             launch = "hipgraph"
 
             def step(i):
-                gs(*batches[i])
+                return gs(*batches[i % len(batches)])
         except Exception as e:                      # capture unsupported: fall back to eager launches
             if dist.is_initialized():
                 # data parallel: a per-rank fallback would pair one rank's bucket collectives with another rank's segment
@@ -468,7 +525,7 @@ def main():
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        loss = step(args.warmup + i)
     fence()
     el = time.perf_counter() - t0
     if dist.is_initialized():
@@ -477,9 +534,11 @@ def main():
         el = float(t.item())
     ms_per_step = 1e3 * el / args.steps
     value = world * args.batch * args.steps / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         model.concurrent = False      # serial launches: an event pair then brackets exactly one kernel
         # An event pair around a HOST call times GPU work only while the stream is still busy when the host records the
         # first event; on a drained stream the pair also spans the host's launch latency (round 3: the driver's line read
@@ -568,7 +627,7 @@ def main():
                                 "launches_per_step": (ncf + ncb) // args.steps,
                                 "avg_launch_mbytes": round((bcf + bcb) / (ncf + ncb) / 1e6, 1)}}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.phi, args.size, args.cpu_batch or args.batch, 0)
 
     if rank == 0:

@@ -150,3 +150,62 @@ def test_roofline_families_follow_the_rocprof_summary_of_the_same_round():
         assert abs(rate - v["achieved"]) < 0.10 * rate, (fam, "rocprofv3", round(rate, 1), "line", v["achieved"])
         checked += 1
     assert checked >= 2
+
+
+def test_dump_outputs_is_seeded_float32_and_bounded(tmp_path):
+    """--dump-outputs: float32 files, the same bytes for the same model and loss, and a seeded sample of the gradients once
+    they exceed the cap (the headline model has 49.8 M parameters); the default caps stay under the 64 MB limit."""
+    import numpy as np
+    import torch
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Conv2d(3, 16, 3), torch.nn.BatchNorm2d(16), torch.nn.Linear(40, 7, bias=False))
+    m[0].weight.grad = torch.randn_like(m[0].weight)             # m[0].bias and m[1]'s parameters keep no gradient
+    m[2].weight.grad = torch.randn_like(m[2].weight)
+    loss = torch.tensor(1.25, dtype=torch.float64)
+    n = sum(p.numel() for p in m.parameters())
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), m, loss, grad_cap=100, buffer_cap=10)
+    for name in ("loss", "param_grads", "bn_buffers"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 1.25
+    g = np.load(tmp_path / "a" / "param_grads.npy")
+    assert n > 100 and 90 <= g.size <= 100
+    full = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in m.parameters()])
+    assert np.isin(g, full.numpy()).all()
+    bench.dump_outputs(str(tmp_path / "c"), m, loss)                 # under the default caps: everything
+    assert np.array_equal(np.load(tmp_path / "c" / "param_grads.npy"), full.numpy())
+    assert np.load(tmp_path / "c" / "bn_buffers.npy").size == 2 * 16        # num_batches_tracked is an integer
+    assert 4 * ((1 << 23) + (1 << 21) + 1) + 3 * 128 <= bench.DUMP_LIMIT_BYTES
+
+
+def test_bench_inputs_are_seeded_and_pooled():
+    import torch
+    import bench
+    a = bench.make_batches(12, 1, 16, 0, "cpu")
+    b = bench.make_batches(3, 1, 16, 0, "cpu")
+    assert len(a) == bench.INPUT_POOL and len(b) == 3
+    assert all(torch.equal(x, y) for p, q in zip(a, b) for x, y in zip(p, q))
+    assert not torch.equal(a[0][0], a[1][0])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields with roofline / cpu_baseline null, reports exactly --steps timed
+    steps, and --dump-outputs writes the last step's loss, gradients and BatchNorm statistics."""
+    import subprocess
+    import sys
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--phi", "nano", "--batch", "2", "--size", "128",
+                          "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["config"]["launch"] == "hipgraph"
+    assert abs(d["value"] - 2 / d["ms_per_step"] * 1e3) < 0.01 * d["value"]
+    loss, g, b = (np.load(tmp_path / f"{n}.npy") for n in ("loss", "param_grads", "bn_buffers"))
+    assert loss.shape == () and np.isfinite(loss) and loss > 0
+    assert g.dtype == np.float32 and g.size == 4137016 and np.isfinite(g).all() and np.abs(g).max() > 0
+    assert b.dtype == np.float32 and np.isfinite(b).all()

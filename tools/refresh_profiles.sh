@@ -7,14 +7,14 @@ R=${1:?round prefix, e.g. r04}
 out=gpurun_out/refresh
 rm -rf $out; mkdir -p $out
 # ---- the other BASELINE configurations and comparison runs (one call, one box)
-python3 bench.py --phi nano --no-cpu-baseline > $out/bench_phi-nano_bs8_512.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --dtype f32-mfma > $out/bench_phi-l_bs8_512_f32-mfma.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --dtype bf16 > $out/bench_phi-l_bs8_512_bf16.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --dtype bf16 --batch 16 > $out/bench_phi-l_bs16_512_bf16.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --dtype bf16 --batch 4 --size 1024 > $out/bench_phi-l_bs4_1024_bf16.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --batch 4 --size 1024 > $out/bench_phi-l_bs4_1024.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --detail 2> $out/per_shape_detail_phi-l_bs8_512.txt > /dev/null
-python3 bench.py --no-cpu-baseline --detail --dtype bf16 --batch 16 2> $out/per_shape_detail_phi-l_bs16_512_bf16.txt > /dev/null
+python3 bench.py --full --phi nano --no-cpu-baseline > $out/bench_phi-nano_bs8_512.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --dtype f32-mfma > $out/bench_phi-l_bs8_512_f32-mfma.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --dtype bf16 > $out/bench_phi-l_bs8_512_bf16.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --dtype bf16 --batch 16 > $out/bench_phi-l_bs16_512_bf16.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --dtype bf16 --batch 4 --size 1024 > $out/bench_phi-l_bs4_1024_bf16.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --batch 4 --size 1024 > $out/bench_phi-l_bs4_1024.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --detail 2> $out/per_shape_detail_phi-l_bs8_512.txt > /dev/null
+python3 bench.py --full --no-cpu-baseline --detail --dtype bf16 --batch 16 2> $out/per_shape_detail_phi-l_bs16_512_bf16.txt > /dev/null
 VRNET_BENCH_FORCE_DP=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 \
     bench.py --gpus 1 --no-cpu-baseline --no-roofline 2>/dev/null | grep metric > $out/line_dp1_rccl_3segments_phi-l_bs8_512.json
 # ---- the issue ceiling of the x6 loop on THIS round's boxes (bench.py reads the newest round's file only; round-4 ADVICE: r04 had
@@ -61,10 +61,10 @@ python3 tools/join_hbm_rate.py $out/hbm_traffic_pmc_phi-l_bs8_512.csv $out/kerne
 (echo "# python tools/debug/section_stamps.py   (phi = l, bs 8, 512 px, fp32; device clock, us)"; python3 tools/debug/section_stamps.py 2>&1 | grep -v amdgpu.ids) > $out/section_timeline_untraced_phi-l_bs8_512.txt
 (echo "# python tools/debug/section_stamps.py --bf16 --batch 16"; python3 tools/debug/section_stamps.py --bf16 --batch 16 2>&1 | grep -v amdgpu.ids) > $out/section_timeline_untraced_phi-l_bs16_512_bf16.txt
 # ---- the headline line LAST, with the PMC traffic of THIS kernel source in place (bench.py checks the source hash), by the
-# driver's exact command
+# driver's command with --full (the roofline and the CPU baseline of the line)
 cp $out/hbm_traffic_pmc_phi-l_bs8_512.csv profiles/${R}_hbm_traffic_pmc_phi-l_bs8_512.csv
 cp $out/hbm_traffic_pmc_phi-l_bs8_512.csv.meta.json profiles/${R}_hbm_traffic_pmc_phi-l_bs8_512.csv.meta.json
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_phi-l_bs8_512.json 2> $out/bench_l.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_phi-l_bs8_512.json 2> $out/bench_l.err
 # the serial rocprofv3 summary of the SAME command line's instrumented replay conditions, for the roofline cross-check
 # (tests/test_bench_contract.py: per-family FLOPs / rocprof duration within 5 % of the line's per-family rate)
 ls -la $out
