@@ -8,7 +8,7 @@
 //   mode 1 (data gradient) dx[m, c] = sum_{t, n} dy[src'(m, t), n] * w[t][n][c]    m over input pixels
 // Three kernels, chosen per shape by vrnet_conv2d_f32 (measured table: profiles/*per_shape_detail*):
 //   igemm_kernel      register-staged (global -> registers -> k-major LDS images, ds_read_b32 fragments), 64 x 64 x 16
-//                     tiles at 8 workgroups per CU (128 x {32,64,128} variants for narrow outputs / non-vector shapes);
+//                     tiles at 8 workgroups per CU (128 x 64 / 128 x 32 variants for narrow outputs);
 //   igemm_dma_kernel  LDS-DMA ring (global_load_lds_dwordx4, 3 stages, XOR-swizzled ds_read_b128 fragments) for the
 //                     layers whose grid cannot fill the chip at 8 workgroups per CU, and for long contractions;
 //   igemm_bf16_kernel (igemm_bf16.hip) bf16-rounded operands on v_mfma_f32_32x32x16_bf16 (precision = 1).
@@ -18,17 +18,6 @@
 #include "x6.h"
 
 #include <cstdlib>
-
-// default variants of igemm_planes_reg_kernel for the 128 x 64 / 128 x 128 tile classes (0: igemm_planes_kernel; -1: per-shape rule)
-#ifndef VR_PLANES_REG21
-#define VR_PLANES_REG21 0
-#endif
-#ifndef VR_PLANES_STREAM_MIN_ROWS
-#define VR_PLANES_STREAM_MIN_ROWS 0      // 0: never
-#endif
-#ifndef VR_PLANES_REG22
-#define VR_PLANES_REG22 0
-#endif
 
 namespace {
 
@@ -329,17 +318,6 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
   if (mt >= MT) return;
   const int m0 = mt * BM, n0 = nt * BN;
   const IgemmArgs p = igemm_select_stream(p_in, m0);
-#ifdef VR_IGEMM_STAMP2
-  // diagnostic build: per-workgroup timeline [start, first stage landed, main loop done, epilogue done, HW id]
-  unsigned long long* wg_stamp = reinterpret_cast<unsigned long long*>(p_in.stats) + 8 * (long)blockIdx.x;
-  if (tid == 0) {
-    wg_stamp[0] = __builtin_amdgcn_s_memtime();
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    wg_stamp[4] = hw;
-    wg_stamp[5] = __builtin_readcyclecounter();
-  }
-#endif
   const int nkb = (p.CK + BK - 1) / BK;
   const int TAPS = p.kh * p.kw;
 
@@ -515,13 +493,7 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
   for (int st = 0; st < NST - 1; ++st)
     if (st < nsteps) issue();
   int cur = 0, kb = s_begin - (s_begin / nkb) * nkb;
-#ifdef VR_IGEMM_STAMP
-  unsigned long long* stamp = reinterpret_cast<unsigned long long*>(p.stats);     // diagnostic build: 64 x 4 stamps
-#endif
   for (int s = 0; s < nsteps; ++s) {
-#ifdef VR_IGEMM_STAMP
-    if (blockIdx.x == 8 && tid == 0 && s < 64) stamp[4 * s + 3] = __builtin_amdgcn_s_memtime();
-#endif
     // stage s has landed once at most the min(NST - 2, stages left) younger stages (4 DMAs each) are still outstanding
     {
       const int younger = nsteps - 1 - s < NST - 2 ? nsteps - 1 - s : NST - 2;      // block-uniform
@@ -536,12 +508,6 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#ifdef VR_IGEMM_STAMP2
-    if (tid == 0 && s == 0) wg_stamp[1] = __builtin_amdgcn_s_memtime();
-#endif
-#ifdef VR_IGEMM_STAMP
-    if (blockIdx.x == 8 && tid == 0 && s < 64) stamp[4 * s + 0] = __builtin_amdgcn_s_memtime();
-#endif
     const bool more = s + NST - 1 < nsteps;   // next stage goes into the slot every wave finished reading before this barrier
     if (more) issue_begin();
     const float* As = smem + cur * ST_FLOATS;
@@ -573,9 +539,6 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
           for (int i = 0; i < TN; ++i) bq[i][j] *= ks[j];
       }
     }
-#ifdef VR_IGEMM_STAMP
-    if (blockIdx.x == 8 && tid == 0 && s < 64) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); stamp[4 * s + 1] = __builtin_amdgcn_s_memtime(); }
-#endif
     constexpr int GROUPS = KQ >= 4 ? 4 : KQ;          // MFMA groups that each carry DMA pieces behind them
     if constexpr (PROD == 1) {
       constexpr int NK16 = KQ / 2;
@@ -609,18 +572,6 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
         vr_bf16x8 a3[TM][3], b3[TN][3];
 #pragma unroll
         for (int i = 0; i < TM; ++i) vr_split3(af[i][2 * ks], af[i][2 * ks + 1], a3[i]);
-#ifdef VR_TUNING
-        // timing experiment (results garbage): what would weights that arrive pre-split into bf16 planes be worth?
-        // VRNET_X6_FAKE_PRESPLIT=1 takes the B fragments' bits as they are instead of splitting them.
-        if (p.dbg_fake_presplit) {
-#pragma unroll
-          for (int i = 0; i < TN; ++i) {
-            b3[i][0] = __builtin_bit_cast(vr_bf16x8, bq[i][2 * ks]);
-            b3[i][1] = __builtin_bit_cast(vr_bf16x8, bq[i][2 * ks + 1]);
-            b3[i][2] = b3[i][0];
-          }
-        } else
-#endif
 #pragma unroll
         for (int i = 0; i < TN; ++i) vr_split3(bq[i][2 * ks], bq[i][2 * ks + 1], b3[i]);
 #pragma unroll
@@ -654,32 +605,12 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
       }
     }
     if (more) issue_end();
-#ifdef VR_IGEMM_STAMP
-    if (blockIdx.x == 8 && tid == 0 && s < 64) stamp[4 * s + 2] = __builtin_amdgcn_s_memtime();
-#endif
     if (++cur == NST) cur = 0;
     if (++kb == nkb) kb = 0;
   }
   __syncthreads();
-#ifdef VR_IGEMM_STAMP2
-  if (tid == 0) wg_stamp[2] = __builtin_amdgcn_s_memtime();
-  {
-    IgemmArgs q = p;
-    q.stats = nullptr;
-    igemm_epilogue<TM, TN, 2, 2>(q, acc, smem, m0, n0);
-  }
-  __syncthreads();
-  if (tid == 0) wg_stamp[3] = __builtin_amdgcn_s_memtime();
-  return;
-#endif
-#ifdef VR_IGEMM_STAMP
-  IgemmArgs q = p;            // the stats pointer carries the stamps in this build
-  q.stats = nullptr;
-  igemm_epilogue<TM, TN, 2, 2>(q, acc, smem, m0, n0);
-#else
   if (p.ksplit > 1) igemm_splitk_store<TM, TN>(p, acc, GT, L, split);
   else igemm_epilogue<TM, TN, 2, 2>(p, acc, smem, m0, n0);
-#endif
 }
 
 
@@ -1491,10 +1422,6 @@ __global__ void pack_weight_kernel(const float* w, float* out, int Cout, int Cin
 
 // igemm_bf16.hip
 int vr_igemm_bf16_launch(const void* args, int mode, hipStream_t st);
-// igemm_planes.hip: x6 with pre-split weights, A fragments from global memory; returns 1 when the shape has no such kernel
-int vr_igemm_planes_reg_launch(const void* args, const void* planes, int variant, long M, int S, hipStream_t st);
-// igemm_planes.hip: K = 64 / 128 over big maps, B resident in LDS, barrier-free A streams; returns 1 when the shape has no such kernel
-int vr_igemm_planes_stream_launch(const void* args, const void* planes, long M, hipStream_t st);
 int vr_wgrad_bf16_launch(const void* args, int ident, int blocks_x, int splits, int streams, hipStream_t st);
 
 // narrowconv.hip
@@ -1654,7 +1581,6 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
             (!aux || ((ldaux % 4 == 0) && vr_aligned16(aux)));
   p.stats = stats;
   p.stats_nb = (int)vr_cdiv(p.CN, 32);
-  p.dbg_fake_presplit = vr_tune("VRNET_X6_FAKE_PRESPLIT", 0);
   if (colstats) {
     VR_CHECK_ARG(colstats->partial && (!colstats->tile_totals || colstats->gamma), "conv2d: column statistics need `partial` (and gamma "
                                                                                  "with tile_totals)");
@@ -1674,11 +1600,9 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
   VR_CHECK_ARG(!colstats || (p.e_vec && !p.perm2 && p.CN > 32 && (!colstats->x2 || (colstats->ldx2 % 4 == 0 && vr_aligned16(colstats->x2)))),
                "conv2d: column statistics need the vector epilogue (NHWC, channel counts %% 4 == 0, 16-byte rows), > 32 output "
                "channels and no stride-2 data gradient");
-#ifndef VR_IGEMM_STAMP2
   VR_CHECK_ARG(!stats || (p.e_vec && !p.perm2 && mode == 0 && ((long)p.MH * p.MW) % 32 == 0 && p.CN > 32),
                "conv2d: output statistics need the vector epilogue, a forward conv, > 32 output channels and a map of a "
                "multiple of 32 pixels");
-#endif
   dim3 block(256);
   hipStream_t st = vr_stream(stream);
   // bf16-rounded operands: the forward launches whose grid fills the chip run on the LDS-DMA tile kernels below (as do
@@ -1698,40 +1622,10 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
     VR_LAUNCH_CHECK("conv2d(bf16)");
     return VR_OK;
   }
-  // Tile choice: 128-row tiles while they fill the chip (256 CUs x >= 2 workgroups); otherwise 64 x 64 tiles,
-  // which quadruple the workgroup count of the small-M layers (M = 2048 / 8192 at the 16x16 / 32x32 stages).
-  const long mt128 = vr_cdiv(M, 128);
-  const int bn128 = p.CN > 64 ? 128 : (p.CN > 32 ? 64 : 32);
-  const long blocks128 = mt128 * vr_cdiv(p.CN, bn128);
   const bool vec = p.a_vec && p.b_vec;
-  static const int force_cfg = vr_tune("VRNET_IGEMM_CFG", -1);   // tuning aid
-  static const int force_bk = vr_tune("VRNET_IGEMM_BK", 0);   // tuning aid
-  const bool bk32 = force_bk == 32;        // BK = 32 measured 3 % slower over the net's shapes (tools/tune_igemm.py --bk)
-#define VR_IGEMM_(BM_, BN_, BK_, TM_, TN_, WM_, WN_, GRID)                                                              \
-  do {                                                                                                                  \
-    if (mode == 0) {                                                                                                    \
-      if (vec) hipLaunchKernelGGL((igemm_kernel<BM_, BN_, BK_, TM_, TN_, WM_, WN_, 0, true>), GRID, block, 0, st, p);   \
-      else hipLaunchKernelGGL((igemm_kernel<BM_, BN_, BK_, TM_, TN_, WM_, WN_, 0, false>), GRID, block, 0, st, p);      \
-    } else {                                                                                                            \
-      if (vec) hipLaunchKernelGGL((igemm_kernel<BM_, BN_, BK_, TM_, TN_, WM_, WN_, 1, true>), GRID, block, 0, st, p);   \
-      else hipLaunchKernelGGL((igemm_kernel<BM_, BN_, BK_, TM_, TN_, WM_, WN_, 1, false>), GRID, block, 0, st, p);      \
-    }                                                                                                                   \
-  } while (0)
-#define VR_IGEMM(BM_, BN_, TM_, TN_, WM_, WN_, GRID)                     \
-  do {                                                                   \
-    if (bk32) VR_IGEMM_(BM_, BN_, 32, TM_, TN_, WM_, WN_, GRID);         \
-    else VR_IGEMM_(BM_, BN_, 16, TM_, TN_, WM_, WN_, GRID);              \
-  } while (0)
-  // Measured on MI355X over every conv shape of the net (tools/tune_igemm.py, phi = l, bs 8, 512 px): 64 x 64 tiles
-  // (7 workgroups per CU) beat 128 x 128 (2 per CU) and 128 x 64 on 90 % of the shapes -- 21.4 vs 30.7 / 25.9 ms
-  // per step over all forward + data-gradient launches; the exceptions are within 10 %.
-  (void)blocks128;
   static const int use_dma = vr_tune("VRNET_IGEMM_DMA", 1);   // tuning aid
-  // Measured per shape (bench.py --detail): the DMA ring wins where the grid cannot fill the chip with 8 workgroups
-  // per CU (M <= 8192 pixels: +5..40 %) and on long contractions; the register-staged kernel keeps the large-M,
-  // short-K layers (2048 row tiles x few K steps: its 8 workgroups per CU hide the store-heavy epilogues better).
   const long ktot = (long)p.CK * kh * kw;
-  const bool dma_ok = use_dma && force_cfg < 0 && vec && p.CN > 32 && (!kscale || p.CK <= 1024);
+  const bool dma_ok = use_dma && vec && p.CN > 32 && (!kscale || p.CK <= 1024);
   // 64 x 64 ring tiles where the grid cannot fill the chip with 8 workgroups per CU (M <= 8192 pixels: +5..40 %) and
   // on long contractions; the register-staged kernel keeps the large-M, short-K layers (2048 row tiles x few K steps:
   // its 8 workgroups per CU hide the store-heavy epilogues better).  128 x 128 ring tiles (T = 2) were measured on the
@@ -1791,50 +1685,13 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
       IgemmArgs q = p;
       q.kscale = nullptr;
       const int JB = (int)(((p.CN + 127) >> 7) << 1);
-      // round 6: A fragments straight from global memory (igemm_planes.hip); variant = 100 NW + 10 TN + workgroups per CU.
-      // Measured alone, warm / operands rotated through > 256 MB (profiles/r06_planes_reg_probe.txt): the 256 x 64 tile with
-      // eight waves on one B stage takes 10-17 % less time where the 128 x 64 grid leaves the chip under-filled and the
-      // contraction is long (8 192 rows x 320 columns, K >= 512: 70.5 -> 58.8 us warm, 75.5 -> 68.2 cold); elsewhere the
-      // variants are within +-5 % of igemm_planes_kernel cold and the step does not move (24.33 vs 24.26-24.31 ms, same call),
-      // so only that class is dispatched (-1 = this rule; the diagnostic build can force a variant for every launch).
-      // Round 6: two more forms of this GEMM (igemm_planes.hip), both measured and NEITHER dispatched by the product build (the
-      // diagnostic build can force them: VRNET_PLANES_STREAM_MIN_ROWS / VRNET_PLANES_REG21 / _REG22; tests/test_planes_reg.py runs
-      // the parity cases on them).  Alone they are faster -- profiles/r06_planes_reg_probe.txt, r06_planes_stream_probe.txt:
-      // A fragments from global memory 5-17 % on the under-filled 8 192-row grids with long contractions (70.5 -> 58.8 us on
-      // 256 x 64 tiles of eight waves), resident B + barrier-free A streams 5-15 % at 131 072 rows x <= 128 columns -- but with
-      // operands rotated through > 256 MB (as inside the step) the gains shrink to 0-10 %, and IN the step they are not there:
-      // same call, ms per step: round-5 head 25.09-25.15, the 256 x 64 rule on 25.27-25.38, rule off 25.16-25.26, streaming rule on
-      // or off 25.38-25.47 vs 25.39-25.46; every 128 x 64 variant 24.17-24.35 against 24.14-24.50 (profiles/r06_planes_reg_step.txt).
-      static const int stream_min = vr_tune("VRNET_PLANES_STREAM_MIN_ROWS", VR_PLANES_STREAM_MIN_ROWS);
-      static const int stream_max_n = vr_tune("VRNET_PLANES_STREAM_MAX_COLS", 128);
-      if (stream_min > 0 && S == 1 && M >= stream_min && p.CN <= stream_max_n && !p.perm2 &&
-          vr_igemm_planes_stream_launch(&q, w_planes, M, st) == 0) {
-        vr_note_kernel(9);
-        VR_LAUNCH_CHECK("conv2d(x6, pre-split weights, resident B)");
-        return VR_OK;
-      }
-      // variant = 100 NW + 10 TN + workgroups per CU; -1 = 256 x 64 tiles where the 128 x 64 grid under-fills the chip and the
-      // contraction is long (the rule that measured +0.2 ms in the step)
-      static const int reg21 = vr_tune("VRNET_PLANES_REG21", VR_PLANES_REG21), reg22 = vr_tune("VRNET_PLANES_REG22", VR_PLANES_REG22);
-      int reg_variant = tile == 22 ? reg22 : reg21;
-      if (reg_variant < 0) reg_variant = (tile == 21 && S == 1 && M <= 8192 && p.CK >= 512 && p.CN <= 512) ? 812 : 0;
-      if (reg_variant && vr_igemm_planes_reg_launch(&q, w_planes, reg_variant, M, S, st) == 0) {
-        if (S > 1)
-          hipLaunchKernelGGL((igemm_splitk_finish_kernel<1, 2, 4, 1>), dim3((unsigned)(8 * vr_cdiv(mt, 8) * nt21)), block, 0, st, q,
-                             (int)mt, (int)nt21);
-        vr_note_kernel(9);
-        VR_LAUNCH_CHECK("conv2d(x6, pre-split weights, A from global memory)");
-        return VR_OK;
-      }
+      // (two further forms of this GEMM -- A fragments from global memory, B resident in LDS -- were faster alone and neutral to
+      // +0.2 ms in the step: DESIGN 3.1)
       if (tile == 22) {
         dim3 grid((unsigned)(8 * vr_cdiv(mt, 8) * nt22));
         // 128 x 128 tile: two stages (40 KB, 3 workgroups per CU) measured 0.2 ms per step ahead of three (60 KB, 2 per CU)
-        if (vr_tune("VRNET_PLANES_NST2", 1))
-          hipLaunchKernelGGL((igemm_planes_kernel<2, 2>), grid, block, 0, st, q, reinterpret_cast<const unsigned char*>(w_planes), JB,
-                             (int)mt, (int)nt22);
-        else
-          hipLaunchKernelGGL((igemm_planes_kernel<2, 3>), grid, block, 0, st, q, reinterpret_cast<const unsigned char*>(w_planes), JB,
-                             (int)mt, (int)nt22);
+        hipLaunchKernelGGL((igemm_planes_kernel<2, 2>), grid, block, 0, st, q, reinterpret_cast<const unsigned char*>(w_planes), JB,
+                           (int)mt, (int)nt22);
       } else {
         dim3 grid((unsigned)(8 * vr_cdiv(mt, 8) * nt21 * S));
         hipLaunchKernelGGL((igemm_planes_kernel<1, 3>), grid, block, 0, st, q, reinterpret_cast<const unsigned char*>(w_planes), JB,
@@ -1869,28 +1726,29 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
     VR_LAUNCH_CHECK("conv2d");
     return VR_OK;
   }
-  int cfg = p.CN > 32 ? 2 : 3;
+  // Register-staged tiles: 64 x 64 by default; 128 x 64 for narrow outputs over long contractions; 128 x 32 for <= 32 columns.
+  // Measured on MI355X over every conv shape of the net (phi = l, bs 8, 512 px; profiles/r01_igemm_tile_sweep.txt): 64 x 64
+  // tiles (7 workgroups per CU) beat 128 x 128 (2 per CU) and 128 x 64 on 90 % of the shapes -- 21.4 vs 30.7 / 25.9 ms per
+  // step over all forward + data-gradient launches; the exceptions are within 10 %.  BK = 32 measured 3 % slower.
+#define VR_IGEMM(BM_, BN_, TM_, TN_, WM_, WN_, GRID)                                                                   \
+  do {                                                                                                                  \
+    if (mode == 0) {                                                                                                    \
+      if (vec) hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 0, true>), GRID, block, 0, st, p);    \
+      else hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 0, false>), GRID, block, 0, st, p);       \
+    } else {                                                                                                            \
+      if (vec) hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 1, true>), GRID, block, 0, st, p);    \
+      else hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 1, false>), GRID, block, 0, st, p);       \
+    }                                                                                                                   \
+  } while (0)
   static const int narrow = vr_tune("VRNET_IGEMM_NARROW", 1);   // tuning aid
-  if (narrow && vec && p.CN > 32 && p.CN <= 192 && ktot >= 512) cfg = 1;      // 128 x 64 tiles for narrow outputs
-  if (force_cfg >= 0 && p.CN > 32) cfg = (force_cfg == 0 && p.CN <= 64) ? 1 : force_cfg;
-  if (cfg == 2) {
-    dim3 grid(vr_cdiv(M, 64), vr_cdiv(p.CN, 64));
-    VR_IGEMM(64, 64, 1, 1, 2, 2, grid);
-  } else if (cfg == 1) {
-    dim3 grid(mt128, vr_cdiv(p.CN, 64));
-    VR_IGEMM(128, 64, 2, 1, 2, 2, grid);
-  } else if (bn128 == 128) {
-    dim3 grid(mt128, vr_cdiv(p.CN, 128));
-    VR_IGEMM(128, 128, 2, 2, 2, 2, grid);
-  } else if (bn128 == 64) {
-    dim3 grid(mt128, 1);
-    VR_IGEMM(128, 64, 2, 1, 2, 2, grid);
+  if (p.CN <= 32) {
+    VR_IGEMM(128, 32, 1, 1, 4, 1, dim3(vr_cdiv(M, 128), 1));
+  } else if (narrow && vec && p.CN <= 192 && ktot >= 512) {
+    VR_IGEMM(128, 64, 2, 1, 2, 2, dim3(vr_cdiv(M, 128), vr_cdiv(p.CN, 64)));
   } else {
-    dim3 grid(mt128, 1);
-    VR_IGEMM(128, 32, 1, 1, 4, 1, grid);
+    VR_IGEMM(64, 64, 1, 1, 2, 2, dim3(vr_cdiv(M, 64), vr_cdiv(p.CN, 64)));
   }
 #undef VR_IGEMM
-#undef VR_IGEMM_
   vr_note_kernel(1);
   VR_LAUNCH_CHECK("conv2d");
   return VR_OK;

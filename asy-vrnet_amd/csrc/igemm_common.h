@@ -43,7 +43,8 @@ struct IgemmArgs {
   // of GroupNorm's backward moments, which otherwise cost a pass over the tensor each; col_tot[mb][n / 32] = the same two
   // sums weighted by col_gamma[n] and added over the tile's 32 columns (GroupNorm backward: per-sample coefficients).
   double* col_part; const float* col_x2; long ld_col_x2; const float* col_gamma; double* col_tot;
-  int dbg_fake_presplit;   // diagnostic build only (timing experiment, igemm.hip)
+  int reserved0;   // unused: without it the fields below move and hipcc emits different code (register allocation,
+                   // scheduling) for every kernel taking IgemmArgs; kept so that those kernels stay as measured
   // Output as bf16 planes (pgemm.hip; vector epilogue only): plane q of element (m, n) at yp[q * yp_plane + m * ldyp + n].
   // yp_np = 3: the stored fp32 value split exactly into three bf16 values (v = p0 + p1 + p2, round-to-nearest-even splits) --
   // the operand format of the next x6 GEMM, which then splits nothing; yp_np = 1: the value rounded to bf16.  `y` may be

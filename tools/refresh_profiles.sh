@@ -32,8 +32,8 @@ if [ -d .ab/base ]; then
      ms=$(python3 bench.py --no-cpu-baseline --no-roofline $f 2>/dev/null | python3 -c "import sys,json; print(json.loads(sys.stdin.readline())['ms_per_step'])"); echo "[$f] $ms"; done) > $out/ab_schedule_switches.txt
 fi
 # ---- diagnostic build: launch-skipping ablations of the step
+make -C asy-vrnet_amd/csrc -j16 tuning || exit 1
 export VRNET_HIP_LIB=$PWD/asy-vrnet_amd/csrc/libvrnet_hip_tuning.so
-[ asy-vrnet_amd/csrc/libvrnet_hip_tuning.so -nt asy-vrnet_amd/csrc/libvrnet_hip.so ] || echo "STALE diagnostic build (run make tuning after make)" >&2
 tools/sweep_env.sh "" "VRNET_ABLATE=igemm" "VRNET_ABLATE=wgrad" "VRNET_ABLATE=igemm,wgrad" "VRNET_ABLATE=moments,affine" \
     "VRNET_ABLATE=cluster" "VRNET_ABLATE=misc,dwconv" "VRNET_ABLATE=igemm,wgrad,moments,affine,cluster,misc,dwconv" \
     "VRNET_ABLATE=igemm_small,wgrad_small" "VRNET_ABLATE=igemm_mid,wgrad_mid" "VRNET_ABLATE=igemm_big,wgrad_big" \
