@@ -1,7 +1,7 @@
-"""Box decode of the det maps, mirroring utils/utils_bbox.py: `decode_outputs` runs as one HIP kernel
-(no concat / grid / stride tensors); `yolo_correct_boxes` is the reference's host-side letterbox un-map (numpy, on
-the handful of boxes that survive NMS).  NMS itself is torchvision's `batched_nms` in the reference
-(utils_bbox.py:124) and is out of scope (parity unpinned)."""
+"""Box decode and NMS of the det maps, mirroring utils/utils_bbox.py: `decode_outputs` runs as one HIP
+kernel (no concat / grid / stride tensors); `non_max_suppression` as the HIP select + NMS kernels of csrc/nms.hip, in
+place of the torchvision `batched_nms` the reference calls (utils_bbox.py:124); `yolo_correct_boxes` is the reference's
+host-side letterbox un-map (numpy, on the handful of boxes that survive NMS)."""
 import numpy as np
 import torch
 
@@ -37,3 +37,70 @@ def yolo_correct_boxes(box_xy, box_wh, input_shape, image_shape, letterbox_image
         size = size * (net_hw / inner)
     top_left, bottom_right = centre - 0.5 * size, centre + 0.5 * size
     return np.concatenate([top_left * img_hw, bottom_right * img_hw], axis=-1)
+
+
+def _nms_workspace(segments, n_max, device):
+    return torch.empty(hip.nms_workspace_bytes(segments, n_max), dtype=torch.uint8, device=device)
+
+
+def non_max_suppression(prediction, num_classes, input_shape, image_shape, letterbox_image, conf_thres=0.5, nms_thres=0.4):
+    """utils_bbox.py:86-135 on the (B, A, 5+nc) GPU tensor `decode_outputs` returns.  A list of B float32 numpy arrays
+    (N_b, 7): (top, left, bottom, right) in pixels of the original image, obj, class_conf, class_pred, rows in
+    descending score = obj * class_conf order (ties: lower anchor first); (0, 7) when no anchor passes conf_thres.
+    Only channels 5 .. 5+num_classes-1 are read.  Unlike the reference, `prediction` is left unchanged (it overwrites
+    prediction[..., :4] with corner boxes), and boxes of one class are compared as they are rather than after
+    batched_nms' per-class coordinate offset (which only perturbs the rounding of the IoU).
+
+    One device -> host read of the B candidate counts sizes the suppression mask from the largest of them (rather than
+    from A: 21 504 anchors at 1024 px would need 58 MB per image); the kept rows come back in a second copy."""
+    if not (torch.is_tensor(prediction) and prediction.is_cuda and prediction.dim() == 3):
+        raise RuntimeError("non_max_suppression: expects the (B, A, 5+nc) GPU tensor of decode_outputs")
+    B, A, C = prediction.shape
+    if A == 0:
+        return [None] * B                    # the reference skips an image without anchors (utils_bbox.py:112-113)
+    pred = prediction.detach().float().contiguous()
+    dev = pred.device
+    rows = torch.empty((B, A, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, A), dtype=torch.float32, device=dev)
+    cls = torch.empty((B, A), dtype=torch.int64, device=dev)
+    ids = torch.empty((B, A), dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    hip.detect_select(pred, num_classes, conf_thres, rows, scores, cls, ids, counts)
+    n_max = int(counts.max())
+    out = [np.zeros((0, 7), dtype=np.float32) for _ in range(B)]
+    if n_max == 0:
+        return out
+    keep = torch.empty((B, n_max), dtype=torch.int32, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    rows_out = torch.empty((B, n_max, 7), dtype=torch.float32, device=dev)
+    hip.nms_segmented(rows, scores, cls, ids, counts, B, A, n_max, nms_thres, _nms_workspace(B, n_max, dev), keep, kept,
+                      rows_out)
+    kept = kept.cpu().numpy()
+    host = rows_out[:, :int(kept.max())].cpu().numpy()
+    for b in range(B):
+        det = host[b, :kept[b]].copy()
+        if len(det):
+            box_xy, box_wh = (det[:, 0:2] + det[:, 2:4]) / 2, det[:, 2:4] - det[:, 0:2]
+            det[:, :4] = yolo_correct_boxes(box_xy, box_wh, input_shape, image_shape, letterbox_image)
+        out[b] = det
+    return out
+
+
+def batched_nms(boxes, scores, idxs, iou_threshold):
+    """torchvision.ops.boxes.batched_nms on the GPU: boxes (N, 4) as (x1, y1, x2, y2), scores (N,), idxs (N,) class ids.
+    Returns the int64 indices of the kept boxes on the boxes' device, by decreasing score (ties: lower index first).
+    Boxes of different classes never suppress each other; boxes and scores are computed in fp32."""
+    if not (torch.is_tensor(boxes) and boxes.is_cuda and boxes.dim() == 2 and boxes.shape[1] == 4):
+        raise RuntimeError("batched_nms: expects (N, 4) boxes on a GPU")
+    n = boxes.shape[0]
+    if scores.shape != (n,) or idxs.shape != (n,):
+        raise RuntimeError(f"batched_nms: scores / idxs must be ({n},), got {tuple(scores.shape)} / {tuple(idxs.shape)}")
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=boxes.device)
+    dev = boxes.device
+    keep = torch.empty(n, dtype=torch.int32, device=dev)
+    kept = torch.empty(1, dtype=torch.int32, device=dev)
+    hip.nms_segmented(boxes.detach().float().contiguous(), scores.detach().float().contiguous(),
+                      idxs.detach().to(dev, torch.int64).contiguous(), None, None, 1, n, n, iou_threshold,
+                      _nms_workspace(1, n, dev), keep, kept)
+    return keep[:int(kept)].long()

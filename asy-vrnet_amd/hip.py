@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VRNET_HIP_LIB") or os.path.join(_HERE, "csrc", "libvrnet_hip.so")   # override: diagnostic builds only
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -123,6 +123,9 @@ _SIGS = {
     "vrnet_sa_apply_f32": ([P, L, P, P, P, P, L, I, L, I, P], I),
     "vrnet_sa_bwd_workspace": ([I, L, I], L),
     "vrnet_decode_outputs_f32": ([P, P, P, I, I, I, F, F, P, P], I),
+    "vrnet_detect_select_f32": ([P, I, I, I, I, F, P, P, P, P, P, P], I),
+    "vrnet_nms_workspace_bytes": ([I, I], L),
+    "vrnet_nms_segmented_f32": ([P, I, P, P, P, P, I, L, I, D, P, L, P, P, P, P], I),
     "vrnet_batch_formats_u8": ([P, P, I, I, I, I, P, P, P, P], I),
     "vrnet_yolo_loss_workspace": ([I, L, I, I], L),
     "vrnet_yolo_loss_f32": ([P, P, P, P, P, I, I, I, P, P, I, F, P, P, P, P, P, L, P], I),
@@ -783,6 +786,26 @@ def decode_outputs(levels, input_h, input_w, out):
     ws = (ctypes.c_int * n)(*[t.shape[3] for t in levels])
     _check(_lib.vrnet_decode_outputs_f32(ptrs, hs, ws, n, levels[0].shape[0], levels[0].shape[1], float(input_h),
                                          float(input_w), ptr(out), stream()), "decode_outputs")
+
+
+def detect_select(pred, num_classes, conf_thres, rows, scores, cls, ids, counts):
+    """pred (B, A, C) fp32 -> the per-image candidate lists of non_max_suppression (vrnet_detect_select_f32)."""
+    B, A, C = pred.shape
+    _check(_lib.vrnet_detect_select_f32(ptr(pred), B, A, C, num_classes, float(conf_thres), ptr(rows), ptr(scores), ptr(cls),
+                                        ptr(ids), ptr(counts), stream()), "detect_select")
+
+
+def nms_workspace_bytes(segments, n_max):
+    return _lib.vrnet_nms_workspace_bytes(segments, n_max)
+
+
+def nms_segmented(rows, scores, classes, ids, counts, segments, stride, n_max, iou_thres, workspace, keep, kept,
+                  rows_out=None):
+    """Class-aware greedy NMS over `segments` segments (vrnet_nms_segmented_f32); rows (..., ld) holds the boxes in
+    columns 0-3, ids / counts may be None."""
+    _check(_lib.vrnet_nms_segmented_f32(ptr(rows), rows.shape[-1], ptr(scores), ptr(classes), ptr(ids), ptr(counts),
+                                        segments, stride, n_max, float(iou_thres), ptr(workspace), workspace.numel(),
+                                        ptr(keep), ptr(kept), ptr(rows_out), stream()), "nms_segmented")
 
 
 def batch_formats(img_u8, png_u8, num_classes_seg, images=None, png_out=None, onehot=None):

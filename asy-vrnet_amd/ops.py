@@ -7,10 +7,11 @@ The CUDA dispatch key is the HIP device on ROCm.  There is no CPU kernel: callin
 
     out, idx = torch.ops.vrnet.cluster(f, v, alpha, beta, heads, fold)     # Cluster core, vr_coc.py:158-190
     y = torch.ops.vrnet.conv2d_nhwc(x, w, bias, stride, pad, dil)           # NHWC implicit-GEMM conv (fp32-accurate x6 / MFMA)
+    keep = torch.ops.vrnet.batched_nms(boxes, scores, idxs, iou_threshold)  # torchvision.ops.boxes.batched_nms
 """
 import torch
 
-from . import hip
+from . import decode, hip
 
 
 @torch.library.custom_op("vrnet::cluster", mutates_args=(), device_types="cuda")
@@ -666,6 +667,16 @@ def _re_bwd(ctx, g, *unused):
 
 
 radar_enhance.register_autograd(_re_bwd, setup_context=_re_setup)
+
+
+@torch.library.custom_op("vrnet::batched_nms", mutates_args=(), device_types="cuda")
+def batched_nms(boxes: torch.Tensor, scores: torch.Tensor, idxs: torch.Tensor, iou_threshold: float) -> torch.Tensor:
+    return decode.batched_nms(boxes, scores, idxs, iou_threshold)
+
+
+@batched_nms.register_fake
+def _(boxes, scores, idxs, iou_threshold):
+    return boxes.new_empty((torch.library.get_ctx().new_dynamic_size(),), dtype=torch.int64)
 
 
 # Autocast policy (the reference trains under torch.cuda.amp.autocast, utils/utils_fit.py:86-88): these ops compute in fp32

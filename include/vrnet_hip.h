@@ -22,7 +22,7 @@ extern "C" {
 #endif
 
 /* ---- library ------------------------------------------------------------------------------------- */
-int vrnet_abi_version(void);                 /* == 10 */
+int vrnet_abi_version(void);                 /* == 11 */
 /* Kernel family the last vrnet_conv2d_f32 / vrnet_conv2d_wgrad_f32 call of this thread dispatched to: 1 fp32 MFMA
  * (register-staged), 2 fp32 MFMA (LDS-DMA ring), 3 bf16-rounded operands, 4 direct kernels for tiny channel counts,
  * 5 direct HBM-streaming kernels for 1x1 convs with <= 16 output channels over wide inputs (head predictions, seg logits),
@@ -559,6 +559,28 @@ int vrnet_mt_copy_f32(const long long* addrs, const long* sizes, const int* chun
  * anchors level-major then row-major, stride_l = input_h / hs[l].  `levels`, `hs`, `ws` are HOST arrays. */
 int vrnet_decode_outputs_f32(const float* const* levels, const int* hs, const int* ws, int n_levels, int B, int C,
                              float input_h, float input_w, float* out, void* stream);
+
+/* ---- detection NMS (csrc/nms.hip, ABI 11) --------------------------------------------------------------------
+ * vrnet_detect_select_f32, utils/utils_bbox.py:90-121 (non_max_suppression up to the batched_nms call): pred (B, A, C) =
+ *   decode_outputs' result; per anchor class_conf / class_pred = max / first arg-max over channels 5 .. 5+num_classes-1,
+ *   score = obj * class_conf (fp32), kept iff score >= conf_thres (a NaN fails).  The candidates of image b go to element
+ *   k < counts[b] of rows (B, A, 7) = (x1, y1, x2, y2 = cx -+ w/2, cy -+ h/2, obj, class_conf, class_pred), scores (B, A),
+ *   cls (B, A) and ids (B, A) = anchor index, in no particular order.  counts (B) is zeroed on `stream` first.
+ * vrnet_nms_segmented_f32, torchvision.ops.boxes.batched_nms (called at utils_bbox.py:124) over `segments` independent
+ *   segments: element k < counts[s] (counts NULL: all n_max) of segment s has the box (x1, y1, x2, y2) at
+ *   rows[(s * stride + k) * ld], score scores[s * stride + k], class classes[s * stride + k] and tie-break id
+ *   ids[s * stride + k] (ids NULL: k; the ids of a segment must be distinct).  Greedy NMS in the order (score descending,
+ *   id ascending), suppressing a box of the same class whose IoU with a kept one is > iou_thres (torchvision's CPU
+ *   expression in fp32, compared in double).  keep (segments, n_max) receives the k of the kept boxes in that order,
+ *   kept (segments) their count; rows_out (segments, n_max, ld), if not NULL, the kept rows (all ld values).
+ *   n_max <= 262 144; workspace: vrnet_nms_workspace_bytes(segments, n_max) bytes (the n_max^2 / 8-byte suppression
+ *   mask of each segment dominates). */
+int vrnet_detect_select_f32(const float* pred, int B, int A, int C, int num_classes, float conf_thres, float* rows,
+                            float* scores, long long* cls, int* ids, int* counts, void* stream);
+long vrnet_nms_workspace_bytes(int segments, int n_max);
+int vrnet_nms_segmented_f32(const float* rows, int ld, const float* scores, const long long* classes, const int* ids,
+                            const int* counts, int segments, long stride, int n_max, double iou_thres, void* workspace,
+                            long workspace_bytes, int* keep, int* kept, float* rows_out, void* stream);
 
 /* ---- input formats -----------------------------------------------------------------------------
  * What YoloDataset.__getitem__ / yolo_dataset_collate (utils/dataloader.py:88-107, 440-457) do to a letterboxed batch,

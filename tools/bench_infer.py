@@ -1,11 +1,14 @@
 """Inference-side timing of the hot path on one GPU (not the BASELINE metric): eval-mode forward of EfficientVRNet +
-the box decode (decode_outputs), captured in one hipGraph per batch size.
+the box decode (decode_outputs), captured in one hipGraph per batch size.  With --nms CONF/IOU[,CONF/IOU...] the timed
+loop also runs non_max_suppression on the decoded boxes (outside the graph: its output size depends on the data), once
+per threshold pair, and reports the NMS step alone as well.
 
-    python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16]
+    python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
 """
 import argparse
 import os
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
@@ -18,9 +21,11 @@ def main():
     ap.add_argument("--batches", default="1,8,32")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--nms", default="", help="comma list of conf/iou threshold pairs (e.g. 0.05/0.5,0.001/0.5)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
-    from asy_vrnet_amd.decode import decode_outputs
+    from asy_vrnet_amd.decode import decode_outputs, non_max_suppression
+    pairs = [tuple(float(v) for v in p.split("/")) for p in args.nms.split(",") if p]
     dev = torch.device("cuda")
     model = A.EfficientVRNet(4, 9, args.phi, img_size=args.size).to(dev).eval()
     A.randomize_state_dict(model.state_dict(), seed=0)
@@ -55,6 +60,28 @@ def main():
         ms = e0.elapsed_time(e1) / args.steps
         print(f"phi={args.phi} {args.size}x{args.size} {args.dtype} eval forward + decode, bs={bs}: {ms:.3f} ms/batch, "
               f"{bs / ms * 1e3:.1f} img/s; boxes {tuple(out[0].shape)}, seg {tuple(out[1].shape)}")
+        S = (args.size, args.size)
+        for conf, iou in pairs:
+            def post():
+                return non_max_suppression(out[0], model.num_classes, S, S, True, conf_thres=conf, nms_thres=iou)
+
+            def timed(fn):
+                for _ in range(3):
+                    fn()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    fn()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / args.steps * 1e3
+
+            g.replay()
+            dets = post()
+            nms_ms = timed(post)
+            full_ms = timed(lambda: (g.replay(), post()))
+            cand = int(((out[0][..., 4:5] * out[0][..., 5:5 + model.num_classes]).amax(-1) >= conf).sum())
+            print(f"  + non_max_suppression conf {conf} iou {iou}, bs={bs}: {full_ms:.3f} ms/batch "
+                  f"(NMS alone {nms_ms:.3f} ms); candidates {cand}, kept {sum(len(d) for d in dets)}")
 
 
 if __name__ == "__main__":
