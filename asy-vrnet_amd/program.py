@@ -9,7 +9,6 @@ flags) and parameter gradients are written once per parameter.  A single autogra
 exposes the whole network to torch.autograd, so `loss.backward()`, optimizers, EMA deep-copies
 and state_dict work exactly as with the reference module.
 """
-import os
 import weakref
 
 import torch
@@ -68,10 +67,10 @@ class Act:
         return self.B * self.H * self.W
 
 
-ASIDE_LAG = int(os.environ.get("VRNET_ASIDE_LAG", "1"))           # tape closures a main-chain weight gradient may trail by
-_SERIAL_SITES = int(os.environ.get("VRNET_SERIAL_SITES", "0"), 0)   # diagnostic: parallel sections (bit = site id) run serially
-FUSED_MLP_MIN_ROWS = int(os.environ.get("VRNET_FUSED_MLP_MIN_ROWS", "16384"))      # (diagnostic override)
-WGRAD_STREAMS = int(os.environ.get("VRNET_WGRAD_STREAMS", "2"))   # side streams for weight gradients (measured: 2 < 1 < 4 ms/step)
+# settled by sweeps in the step: profiles/r06_program_knob_sweep.txt, profiles/r06_fused_mlp_min_rows.txt
+ASIDE_LAG = 1               # tape closures a main-chain weight gradient may trail by
+FUSED_MLP_MIN_ROWS = 16384  # fewest GEMM rows of a fused Mlp launch (prec_mlp)
+WGRAD_STREAMS = 2           # side streams for weight gradients
 
 
 class RT:
@@ -86,12 +85,12 @@ class RT:
         self.bf16 = False           # dense convs with bf16-rounded operands on the bf16 MFMA (model.compute_dtype)
         self.fp32_precision = 2     # fp32 layers: 2 = six-bf16-product kernels where available, 0 = fp32 MFMA only
         self.fused_mlp = True       # Mlp of a ClusterBlock as one kernel per direction where the library has one
-        self.wplanes = None         # WeightPlanes: pre-split weights for the x6 kernels (model.weight_planes, default on)
+        self.wplanes = None         # X6WeightPlanes: pre-split weights for the x6 kernels (model.weight_planes, default on)
         self.bn_colstats = True     # BatchNorm batch statistics from the producing conv's epilogue (no pass over z)
         self.pnp = 0                # plane GEMMs (csrc/pgemm.hip) in the ClusterBlocks: 0 off, 3 fp32 values as three bf16 planes,
                                     # 1 bf16 tensors (compute_dtype "bf16"); pg_fwd / pg_wgrad: which GEMM kinds take them
         self.pg_fwd, self.pg_wgrad = True, True
-        self.pweights = None        # PlaneWeights: the weights of the plane GEMMs, split once per forward
+        self.pweights = None        # PlaneGemmWeights: the weights of the plane GEMMs, split once per forward
         self.forced_idx = None      # {block name: (B,H,W,E) uint8}: Cluster assignments to replay instead of the arg-max (model.forced_idx_maps)
         self.sync_bn = None         # parallel.SyncBatchNormStats: BatchNorm statistics over all ranks (model._sync_bn)
         self.consts = {}
@@ -263,8 +262,6 @@ class RT:
         (wait_stream) on both sides.  Under hipGraph capture the fork / join become graph edges."""
         if not self.concurrent or len(fns) < 2 or self._depth > 0:      # no nested forks (star topology only)
             return [fn() for fn in fns]
-        if _SERIAL_SITES and site is not None and (_SERIAL_SITES >> site) & 1:      # diagnostic: VRNET_SERIAL_SITES bit mask
-            return [fn() for fn in fns]
         cur = torch.cuda.current_stream(self.device)
         streams = self._streams(len(fns))
         main_tape, outs, subtapes = self.tape, [], []
@@ -420,8 +417,7 @@ class RT:
         an x6 tile kernel, or the planes are switched off).  mode 0: w is [J = Cout][K = Cin]; mode 1: [K = Cout][J = Cin]."""
         if self.wplanes is None or self.bf16 or self.fp32_precision != 2 or K % 16 or not hip.conv2d_dma_plan(rows, J, K)[0]:
             return None
-        sj, sk = (K, 1) if mode == 0 else (1, J)
-        return self.wplanes.get((id(w), mode), w, J, K, sj, sk, kscale)
+        return self.wplanes.dgrad(w, kscale) if mode else self.wplanes.fwd(w)
 
     def prec_wgrad(self, ldx, lddy, ci, co):
         if self.bf16 and hip.bf16_wgrad_ok(ldx, lddy, ci, co):
@@ -772,7 +768,7 @@ def bn_backward(rt, bn, z, ms, dy, lddy, mask=None, dz_out=None):
         hip.bn_coef_bwd(tot2, ms, bn.weight, True, 1, rt.sync_bn.count(B, HW, rt.sync_batch_total), C, A, E, D, S, rt.buf(C), rt.buf(C), 0)
         hip.bn_coef_bwd(mom2, ms, bn.weight, True, B, HW, C, rt.buf(C), rt.buf(C), rt.buf(C), rt.buf(C), gw, gb, accw)
     else:
-        fwd = getattr(ms, "fwd_coef", None) if (mask is not None and BN_ZMASK) else None
+        fwd = getattr(ms, "fwd_coef", None) if mask is not None else None
         if fwd is not None:
             # y = ReLU(BN(z)): neither pass reads y -- two tensor reads each where there were three
             hip.bn_stats_bwd_zmask(dy, lddy, z.t, z.ld, fwd, ms, bn.weight, rt.training, B, HW, C, A, E, D, S, gw, gb, accw)
@@ -1060,10 +1056,10 @@ def _planes_plan(rt, M, C, ED, hid, fused_mlp):
     conv in fcfv / proj / fc1 / fc2 (rows x columns x contraction of each product; the Mlp convs only when the block has no
     fused Mlp kernel)."""
     def gemm(cols, K):
-        return rt.pg_fwd and M <= PG_MAX_ROWS and hip.gemm_planes_ok(M, cols, K)
+        return rt.pg_fwd and hip.gemm_planes_ok(M, cols, K)
 
     def wg(ci, co):
-        return rt.pg_wgrad and M <= PG_MAX_ROWS and hip.wgrad_planes_ok(M, ci, co)
+        return rt.pg_wgrad and hip.wgrad_planes_ok(M, ci, co)
     plan = {"fcfv": (gemm(2 * ED, C), gemm(C, 2 * ED), wg(C, 2 * ED)),
             "proj": (gemm(C, ED), gemm(ED, C), wg(ED, C))}
     if not fused_mlp:
@@ -1453,7 +1449,7 @@ def image_enhance(rt, x, r, m, out=None):
             dxb, acc = rt.buf(B, H, W, C), 0
         dp = rt.buf(B, H, W, C)
         fwd = getattr(ms1, "fwd_coef", None)
-        if nch and BN_ZMASK and fwd is not None and g.is_contiguous():
+        if nch and fwd is not None and g.is_contiguous():
             A2, E2, D2, S2 = bn_bwd_coef(rt, m.norm, t, ms2, g, C)
             dt = rt.buf(B, H, W, C)
             nf = hip.fusion_fold_chunks(n, C)
@@ -1598,7 +1594,7 @@ def radar_enhance(rt, x, r, m, out=None):
     z = rt.new(B, H, W, C)
     conv_call(rt, u, conv, z, bias=False, bn_stats=True)
     nch = _fusion_chunks(rt, r, z)
-    if BN_ZMASK and rt.relu_masks is None and rt.sync_bn is None:      # (synchronised BatchNorm reads the ReLU output as its mask)
+    if rt.relu_masks is None and rt.sync_bn is None:      # (synchronised BatchNorm reads the ReLU output as its mask)
         # s = ReLU(BN(z)) + r in ONE apply launch; the ReLU output itself is never stored: the backward pass recomputes its
         # mask from z with the forward coefficients (bn_backward, zmask form).  (round 5: -1 launch, -2 tensor passes per level)
         if nch and rt.training:
@@ -1622,7 +1618,7 @@ def radar_enhance(rt, x, r, m, out=None):
         if g is None:
             return
         fwd = getattr(ms1, "fwd_coef", None)
-        if nch and BN_ZMASK and fwd is not None and q is s and g.is_contiguous():
+        if nch and fwd is not None and q is s and g.is_contiguous():
             # the backward apply of `norm` also leaves the moments of bn1's backward (csrc/fusion.hip): one pass over ds less
             A2, E2, D2, S2 = bn_bwd_coef(rt, m.norm, s, ms2, g, C)
             ds = rt.buf(B, H, W, C)
@@ -1650,7 +1646,7 @@ def coc_upsample(rt, x, m, nchw_out=None):
     """CoCUpsample.forward (coc_fpn_dual.py:24-26): BaseConv 1x1 -> bilinear, align_corners=True."""
     bc = m.upsample[0]
     s = m.scale
-    if rt.fused_upsample and not bc.ds_conv and BN_ZMASK and rt.relu_masks is None and rt.sync_bn is None:
+    if rt.fused_upsample and not bc.ds_conv and rt.relu_masks is None and rt.sync_bn is None:
         # (round 5, K11) conv -> [BatchNorm + ReLU on the taps of the bilinear gather]: the low-resolution activation is never
         # stored (the backward needs z and the forward coefficients only: the ReLU mask is recomputed from them)
         conv, bn = bc.conv, bc.bn
@@ -1828,10 +1824,10 @@ def backbone_forward(rt, bb, x, r):
         return y
     xe, re_ = x, r
     dims = [bb.network[3 * i][0].norm1.weight.shape[0] for i in range(4)]
-    # Two-stream mode (default): the image and the radar chain of every stage run as ONE batch of 2B samples in one
-    # (2B,H,W,C) buffer, image samples first -- one launch per layer with twice the tiles and per-half parameters
-    # instead of two half-filled launches on two streams (vr_coc.py:589-600 calls network[idx] / network_radar[idx]
-    # back to back on equal shapes).  model.pair_streams = False keeps the two chains on two forked streams.
+    # Two-stream mode (model.pair_streams, off by default): the image and the radar chain of every stage run as ONE batch of
+    # 2B samples in one (2B,H,W,C) buffer, image samples first -- one launch per layer with twice the tiles and per-half
+    # parameters instead of two half-filled launches on two streams (vr_coc.py:589-600 calls network[idx] / network_radar[idx]
+    # back to back on equal shapes).  The default keeps the two chains on two forked streams.
     outs, outs_r = [], []
 
     def chain(act, blocks, prefix):
@@ -1841,17 +1837,15 @@ def backbone_forward(rt, bb, x, r):
 
     if overlapped:
         return _backbone_overlapped(rt, bb, x, r, embed, chain)
-    mask = os.environ.get("VRNET_PAIR_MASK")      # diagnostic: which stages (bits 0-3) / reducers (bits 4-6) run two-stream
 
-    def can_pair(h, w, bit=None):    # rows of one stream must be whole 128-row tiles (true for every stage from 256 px at bs 2)
-        on = rt.pair_streams if (mask is None or bit is None) else bool(int(mask, 0) >> bit & 1)
-        return on and (B * h * w) % 128 == 0
+    def can_pair(h, w):    # rows of one stream must be whole 128-row tiles (true for every stage from 256 px at bs 2)
+        return rt.pair_streams and (B * h * w) % 128 == 0
     xr = rt.new_pair(2 * B, H // 4, W // 4, dims[0])             # stage-0 input: both patch embeddings
     xh, rh = xr.halves()
     rt.parallel([lambda: embed(xe, bb.patch_embed, out=xh), lambda: embed(re_, bb.patch_embed_radar, out=rh)], site=1)
     for i in range(4):
         pi, pr = f"backbone.backbone.network.{3 * i}", f"backbone.backbone.network_radar.{3 * i}"
-        if can_pair(xr.H, xr.W, i):
+        if can_pair(xr.H, xr.W):
             for j, (bi, br) in enumerate(zip(bb.network[3 * i], bb.network_radar[3 * i])):
                 xr = cluster_block(rt, xr, (bi, br), (f"{pi}.{j}.token_mixer", f"{pr}.{j}.token_mixer"))
             xs, rs = xr.halves()
@@ -1870,7 +1864,7 @@ def backbone_forward(rt, bb, x, r):
             outs_r.append(r)
         if i < 3:
             ci, cr = bb.network[3 * i + 2].proj, bb.network_radar[3 * i + 2].proj
-            if can_pair(fused.H // 2, fused.W // 2, 4 + i):
+            if can_pair(fused.H // 2, fused.W // 2):
                 xr = simple_conv(rt, fused, (ci, cr))
             else:
                 xr = rt.new_pair(2 * B, fused.H // 2, fused.W // 2, dims[i + 1])
@@ -1998,37 +1992,36 @@ def head_forward(rt, hd, feats, det_outs):
     rt.parallel([(lambda k=k, x=x: level(k, x)) for k, x in enumerate(feats)], site=5)
 
 
-class WeightPlanes:
-    """Pre-split weights for the x6 kernels (hip.conv2d `w_planes`): the six-product scheme spends its VALU time on
-    splitting fragments into bf16 planes, and a weight tile is the same for every row tile of a step -- so every 1x1 weight
-    whose launch runs on an x6 tile kernel is split ONCE per forward, all of them in ONE launch (hip.conv_planes_pack), into
-    the kernel's LDS stage image.  Derived caches like FusedQKV: the first forward that needs a pack builds it on the spot
-    and registers it; from then on `refresh()` re-splits the whole table at the start of every forward (the parameters may
-    have been updated in place)."""
+class SplitWeights:
+    """1x1 weights split into bf16 planes ONCE per forward, all of them in ONE launch: a weight tile is the same for every
+    row tile of a step, so the GEMM kernels need not split it themselves.  Derived caches like FusedQKV: the first forward
+    that needs an entry splits it on the spot and registers it; from then on `refresh()` re-splits the whole table at the
+    start of every forward (the parameters may have been updated in place).  An entry is the source as a J x K matrix
+    (element strides sj, sk) with kscale[K] folded in; a subclass supplies what the two uses differ in: an entry's destination
+    (`alloc`), its fields of the int64 table row (`dest_row`), its blocks in the split launch (`blocks`) and the launch (`split`)."""
 
-    def __init__(self, model, device):
-        self.owner, self.device = id(model), device
-        self.entries = {}          # key -> [source tensor, J, K, sj, sk, kscale tensor or None, planes buffer]
-        self.table, self.nblocks, self.dirty = None, 0, False
+    def __init__(self, device):
+        self.device = device
+        self.entries = {}          # key -> [source, J, K, sj, sk, kscale or None, destination, (source pointers)]
+        self.table, self.nblocks, self.dirty, self.ents = None, 0, False, []
 
-    def get(self, key, w, J, K, sj, sk, kscale):
+    def get(self, key, w, J, K, sj, sk, kscale=None):
         ent = self.entries.get(key)
         ids = (w.data_ptr(), None if kscale is None else kscale.data_ptr())
         if ent is not None and ent[7] == ids:
             return ent[6]
-        buf = torch.empty((hip.conv_planes_bytes(J, K),), dtype=torch.uint8, device=self.device)
-        ent = [w, J, K, sj, sk, kscale, buf, ids]
+        ent = [w, J, K, sj, sk, kscale, self.alloc(J, K), ids]
         self.entries[key] = ent
         self.dirty = True
         tab, nb = self._table([ent])
-        hip.conv_planes_pack(tab, 1, nb)          # first use: split now (later forwards: refresh())
-        return buf
+        self.split(tab, 1, nb)          # first use: split now (later forwards: refresh())
+        return ent[6]
 
     def _table(self, ents):
         rows, first = [], 0
-        for w, J, K, sj, sk, kscale, buf, _ in ents:
-            rows += [w.data_ptr(), J, K, sj, sk, 0 if kscale is None else kscale.data_ptr(), buf.data_ptr(), first]
-            first += (K // 16) * 2 * ((J + 127) // 128)
+        for w, J, K, sj, sk, kscale, dst, _ in ents:
+            rows += [w.data_ptr(), J, K, sj, sk, 0 if kscale is None else kscale.data_ptr(), *self.dest_row(dst), first]
+            first += self.blocks(J, K)
         return torch.tensor(rows, dtype=torch.int64, device=self.device), first
 
     def refresh(self):
@@ -2045,60 +2038,7 @@ class WeightPlanes:
             self.ents = list(self.entries.values())
             self.table, self.nblocks = self._table(self.ents)
             self.dirty = False
-        hip.conv_planes_pack(self.table, len(self.ents), self.nblocks)
-
-
-BN_ZMASK = os.environ.get("VRNET_BN_ZMASK", "1") != "0"      # (diagnostic A/B switch)
-PG_MAX_ROWS = int(os.environ.get("VRNET_PG_MAX_ROWS", "1000000000"))      # plane GEMMs only for maps of at most this many pixels (diagnostic override)
-# which GEMM kinds of the ClusterBlocks run on plane operands by default, per compute_dtype (measured: DESIGN 3.6)
-PLANE_GEMMS_DEFAULT = {"f32": False, "bf16": "fwd+wgrad", "off": False}
-
-
-class PlaneWeights:
-    """Weights of the plane GEMMs (hip.gemm_planes): every 1x1 weight a ClusterBlock multiplies with is split into bf16 planes
-    ONCE per forward, all of them in one launch (hip.planes_split) -- forward form w[Cout][Cin] as it is, data-gradient form
-    the transpose with the layer scale folded in.  Same life cycle as WeightPlanes: the first forward that needs a pack
-    builds it on the spot and registers it, `refresh()` re-splits the whole table at the start of every later forward."""
-
-    def __init__(self, model, device, np_):
-        self.owner, self.device, self.np = id(model), device, np_
-        self.entries = {}          # key -> [source, R, K, sr, sk, kscale or None, Planes, (pointers)]
-        self.table, self.nblocks, self.dirty, self.ents = None, 0, False, []
-
-    def get(self, key, w, R, K, sr, sk, kscale=None):
-        ent = self.entries.get(key)
-        ids = (w.data_ptr(), None if kscale is None else kscale.data_ptr())
-        if ent is not None and ent[7] == ids:
-            return ent[6]
-        ent = [w, R, K, sr, sk, kscale, hip.Planes.empty(self.np, (R, K), self.device), ids]
-        self.entries[key] = ent
-        self.dirty = True
-        tab, nb = self._table([ent])
-        hip.planes_split(tab, 1, nb, self.np)          # first use: split now (later forwards: refresh())
-        return ent[6]
-
-    def _table(self, ents):
-        rows, first = [], 0
-        for w, R, K, sr, sk, kscale, pl, _ in ents:
-            rows += [w.data_ptr(), R, K, sr, sk, 0 if kscale is None else kscale.data_ptr(), pl.t.data_ptr(), pl.ld, pl.plane, first]
-            first += hip.planes_split_blocks(R, K)
-        return torch.tensor(rows, dtype=torch.int64, device=self.device), first
-
-    def refresh(self):
-        # entries whose source storage has been replaced since they were registered (model.to, load_state_dict(assign=True),
-        # p.data = ...) are dropped: their next use re-registers them
-        stale = [k for k, e in self.entries.items()
-                 if e[7] != (e[0].data_ptr(), None if e[5] is None else e[5].data_ptr())]
-        for k in stale:
-            del self.entries[k]
-            self.dirty = True
-        if not self.entries:
-            return
-        if self.dirty:
-            self.ents = list(self.entries.values())
-            self.table, self.nblocks = self._table(self.ents)
-            self.dirty = False
-        hip.planes_split(self.table, len(self.ents), self.nblocks, self.np)
+        self.split(self.table, len(self.ents), self.nblocks)
 
     def fwd(self, w):
         """planes of w[Cout][Cin] (a 1x1 conv weight or a 2-D matrix): the B operand of the forward GEMM."""
@@ -2111,6 +2051,48 @@ class PlaneWeights:
         return self.get((id(w), 1), w, ci, co, 1, ci, kscale)
 
 
+class X6WeightPlanes(SplitWeights):
+    """Pre-split weights for the x6 kernels (hip.conv2d `w_planes`), whose six-product scheme spends its VALU time on splitting
+    fragments: every 1x1 weight whose launch runs on an x6 tile kernel, split into that kernel's LDS stage image."""
+
+    def alloc(self, J, K):
+        return torch.empty((hip.conv_planes_bytes(J, K),), dtype=torch.uint8, device=self.device)
+
+    def dest_row(self, buf):
+        return [buf.data_ptr()]
+
+    def blocks(self, J, K):
+        return (K // 16) * 2 * ((J + 127) // 128)
+
+    def split(self, table, n, nblocks):
+        hip.conv_planes_pack(table, n, nblocks)
+
+
+class PlaneGemmWeights(SplitWeights):
+    """Weights of the plane GEMMs (hip.gemm_planes): every 1x1 weight a ClusterBlock multiplies with, as hip.Planes of `np`
+    planes -- forward form w[Cout][Cin] as it is, data-gradient form the transpose with the layer scale folded in."""
+
+    def __init__(self, device, np_):
+        super().__init__(device)
+        self.np = np_
+
+    def alloc(self, R, K):
+        return hip.Planes.empty(self.np, (R, K), self.device)
+
+    def dest_row(self, pl):
+        return [pl.t.data_ptr(), pl.ld, pl.plane]
+
+    def blocks(self, R, K):
+        return hip.planes_split_blocks(R, K)
+
+    def split(self, table, n, nblocks):
+        hip.planes_split(table, n, nblocks, self.np)
+
+
+# which GEMM kinds of the ClusterBlocks run on plane operands by default, per compute_dtype (measured: DESIGN 3.6)
+PLANE_GEMMS_DEFAULT = {"f32": False, "bf16": "fwd+wgrad", "off": False}
+
+
 class FusedQKV:
     """Concatenated [fc1 ; fc_v] weights and biases of every Cluster module (vr_coc.py:145-147): both 1x1 convs read
     the same normalised input, so each block runs them as ONE GEMM with 2*E*D output channels (twice the tiles of the
@@ -2120,9 +2102,6 @@ class FusedQKV:
     CHUNK = 4096
 
     def __init__(self, model, device):
-        # bound to THIS module tree: copy.deepcopy (ModelEMA) and nn.DataParallel replicas carry a stale copy of the
-        # object along (views lose their aliasing under deepcopy), so the owner id is checked on every forward
-        self.owner = id(model)
         dst, src = [], []
         for mod in model.modules():
             tm = getattr(mod, "token_mixer", None)
@@ -2152,6 +2131,19 @@ class FusedQKV:
             self.ci = torch.tensor(ci, dtype=torch.int32, device=dev)
             self.n, self.nc, self.key = len(sizes), len(ct), key
         hip.mt_copy(self.addrs, self.sizes, self.ct, self.ci, self.n, self.nc, self.CHUNK)
+
+
+def _derived_cache(model, attr, make, *spec):
+    """model.<attr>, a cache derived from the parameters, rebuilt by make() unless it was built for THIS module tree and the
+    same `spec` (device, plane count): copy.deepcopy (ModelEMA) and nn.DataParallel replicas carry a stale copy of the object
+    along (views lose their aliasing under deepcopy), so the owner is checked on every forward."""
+    key = (id(model),) + spec
+    cache = getattr(model, attr, None)
+    if cache is None or cache.built_for != key:
+        cache = make()
+        cache.built_for = key
+        setattr(model, attr, cache)
+    return cache
 
 
 def forward_pass(model, x, x_radar, record, need_dx=False, need_dr=False):
@@ -2196,7 +2188,7 @@ def forward_pass(model, x, x_radar, record, need_dx=False, need_dr=False):
             if model.training:
                 rt.sync_bn.begin_forward(B, x.device)
                 rt.sync_batch_total = rt.sync_bn.batch_total      # this pass's count, also for ITS backward (bn_backward)
-        cd = str(os.environ.get("VRNET_COMPUTE_DTYPE") or getattr(model, "compute_dtype", "f32")).lower()   # env: diagnostics
+        cd = str(getattr(model, "compute_dtype", "f32")).lower()
         if cd not in ("f32", "fp32", "float32", "torch.float32", "f32-mfma", "bf16", "bfloat16", "torch.bfloat16"):
             raise RuntimeError(f"compute_dtype {cd!r}: expected 'f32', 'f32-mfma' or 'bf16'")
         rt.bf16 = cd in ("bf16", "bfloat16", "torch.bfloat16")
@@ -2213,16 +2205,11 @@ def forward_pass(model, x, x_radar, record, need_dx=False, need_dr=False):
         rt.on_param_grad = rt.ready.append if rt.bucketer is not None else None
         if getattr(model, "record_relu_masks", False):
             rt.relu_masks = {}
-        fq = getattr(model, "_fused_qkv", None)
-        if fq is None or fq.owner != id(model) or fq.dst[0].device != x.device:
-            fq = model._fused_qkv = FusedQKV(model, x.device)
+        fq = _derived_cache(model, "_fused_qkv", lambda: FusedQKV(model, x.device), x.device)
         refreshes = [fq.refresh]
         if getattr(model, "weight_planes", True) and not rt.bf16 and rt.fp32_precision == 2:
-            wp = getattr(model, "_weight_planes", None)
-            if wp is None or wp.owner != id(model) or wp.device != x.device:
-                wp = model._weight_planes = WeightPlanes(model, x.device)
-            refreshes.append(wp.refresh)       # after fq.refresh(): the concatenated fc1 | fc_v weights are sources too
-            rt.wplanes = wp
+            rt.wplanes = _derived_cache(model, "_weight_planes", lambda: X6WeightPlanes(x.device), x.device)
+            refreshes.append(rt.wplanes.refresh)       # after fq.refresh(): the concatenated fc1 | fc_v weights are sources too
         # plane GEMMs in the ClusterBlocks (csrc/pgemm.hip): model.plane_gemms = None (default: see below), False, True or a
         # string of GEMM kinds "fwd", "wgrad", "fwd+wgrad"
         pg = getattr(model, "plane_gemms", None)
@@ -2232,11 +2219,8 @@ def forward_pass(model, x, x_radar, record, need_dx=False, need_dr=False):
             kinds = pg if isinstance(pg, str) else "fwd+wgrad"
             rt.pg_fwd, rt.pg_wgrad = "fwd" in kinds, "wgrad" in kinds
             rt.pnp = 1 if rt.bf16 else 3
-            pwts = getattr(model, "_plane_weights", None)
-            if pwts is None or pwts.owner != id(model) or pwts.device != x.device or pwts.np != rt.pnp:
-                pwts = model._plane_weights = PlaneWeights(model, x.device, rt.pnp)
-            refreshes.append(pwts.refresh)
-            rt.pweights = pwts
+            rt.pweights = _derived_cache(model, "_plane_weights", lambda: PlaneGemmWeights(x.device, rt.pnp), x.device, rt.pnp)
+            refreshes.append(rt.pweights.refresh)
 
         def refresh_all():
             for fn in refreshes:

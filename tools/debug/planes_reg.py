@@ -6,8 +6,8 @@ import asy_vrnet_amd as A
 from asy_vrnet_amd import hip, program
 step = [0]
 log = collections.Counter()
-orig = program.WeightPlanes.get
-def get(self, key, w, J, K, sj, sk, kscale):
+orig = program.SplitWeights.get
+def get(self, key, w, J, K, sj, sk, kscale=None):
     ent = self.entries.get(key)
     ids = (w.data_ptr(), None if kscale is None else kscale.data_ptr())
     if step[0] >= 1 and not (ent is not None and ent[7] == ids):
@@ -15,7 +15,7 @@ def get(self, key, w, J, K, sj, sk, kscale):
         site = [f"{fr.name}:{fr.lineno}" for fr in traceback.extract_stack()[:-1] if fr.filename.endswith("program.py")][-2:]
         log[(step[0], why, J, K, tuple(site))] += 1
     return orig(self, key, w, J, K, sj, sk, kscale)
-program.WeightPlanes.get = get
+program.SplitWeights.get = get
 packs = collections.Counter()
 for n in ("conv_planes_pack", "pack_weight_t", "planes_split", "mlp_pack"):
     if hasattr(hip, n):

@@ -37,7 +37,7 @@ export VRNET_HIP_LIB=$PWD/asy-vrnet_amd/csrc/libvrnet_hip_tuning.so
 tools/sweep_env.sh "" "VRNET_ABLATE=igemm" "VRNET_ABLATE=wgrad" "VRNET_ABLATE=igemm,wgrad" "VRNET_ABLATE=moments,affine" \
     "VRNET_ABLATE=cluster" "VRNET_ABLATE=misc,dwconv" "VRNET_ABLATE=igemm,wgrad,moments,affine,cluster,misc,dwconv" \
     "VRNET_ABLATE=igemm_small,wgrad_small" "VRNET_ABLATE=igemm_mid,wgrad_mid" "VRNET_ABLATE=igemm_big,wgrad_big" \
-    "VRNET_SPLITK=0" "VRNET_BN_ZMASK=0" "" > $out/ablation_ms_per_step.txt 2>&1
+    "VRNET_SPLITK=0" "" > $out/ablation_ms_per_step.txt 2>&1
 FLAGS="--dtype bf16 --batch 16" tools/sweep_env.sh "" "VRNET_ABLATE=igemm" "VRNET_ABLATE=wgrad" "VRNET_ABLATE=igemm,wgrad" \
     "VRNET_ABLATE=moments,affine" "VRNET_ABLATE=cluster" "VRNET_ABLATE=misc,dwconv" > $out/ablation_ms_per_step_bf16_bs16.txt 2>&1
 unset VRNET_HIP_LIB
