@@ -4,6 +4,7 @@
 //   * vrnet_yolo_loss_f32: YOLOLoss.forward / get_losses / get_assignments / dynamic_k_matching (SimOTA),
 //     nets/yolo_training.py:60-427, IOUloss :13-57.
 //   * vrnet_seg_loss_f32: CE_Loss / Focal_Loss (+ Dice_loss), nets/deeplabv3_training.py:9-59.
+//   * vrnet_seg_fscore_f32: the f_score metric, utils_seg/utils_metrics.py:12-31.
 // Every reduction has a fixed order (fp64 block partials, integer atomics only): results are reproducible.
 #include "common.h"
 
@@ -342,7 +343,8 @@ struct SegArgs {
   int B, C, ignore; long HW;
   int focal, dice;
   float alpha, gamma, beta, smooth, grad_scale;
-  double* partial;     // [blocks][3 + 3C]: ce_num, ce_den, focal_sum, tp[C], sp[C], st[C]
+  float thr;           // f_score only: probability threshold
+  double* partial;     // [blocks][3 + 3C]: ce_num, ce_den, focal_sum, tp[C], sp[C], st[C]  (f_score: [blocks][3C])
   double* coef;        // [3 + 2C]: 1/ce_den, 1/N, (unused), dtp[C], dsp[C]
   float* out;          // [3]: main, dice, total
   float* dx;
@@ -472,6 +474,95 @@ long seg_blocks(long n) {
   return b > 2048 ? 2048 : (b < 1 ? 1 : b);
 }
 
+// f_score (utils_seg/utils_metrics.py:12-31): per class c, over every pixel, tp = sum t_c [p_c > thr], sp = sum [p_c > thr],
+// st = sum t_c, with t the one-hot target without its last channel.  A wave takes 64 pixels at a time: each lane forms
+// the bit mask of its pixel's classes above the threshold while the wave stages the 64 target rows (contiguous) in LDS with
+// coalesced loads, then lane c < C walks the 64 pixels (mask by readlane, t_c from LDS) and accumulates class c alone, so
+// no per-thread array of class sums is needed.  fp64 partials per workgroup; the final sum runs in a fixed order.
+constexpr int FS_THREADS = 256;
+
+__global__ __launch_bounds__(FS_THREADS) void fscore_reduce_kernel(const SegArgs p) {
+  __shared__ double sred[FS_THREADS / 64][3 * SMAXC];
+  __shared__ float stg[FS_THREADS / 64][64 * (SMAXC + 1)];     // a tile's target rows, staged by coalesced loads
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long total = (long)p.B * p.HW;
+  const int ld = p.C + 1;
+  double tp = 0.0, sp = 0.0, st = 0.0;
+  // the workgroup's 4 waves take 4 consecutive 64-pixel tiles per step (a trip count shared by the workgroup: barriers)
+  for (long t0 = (long)blockIdx.x * (FS_THREADS / 64); t0 * 64 < total; t0 += (long)gridDim.x * (FS_THREADS / 64)) {
+    const long tile = t0 + wave, e = tile * 64 + lane;
+    const int rows = tile * 64 >= total ? 0 : (total - tile * 64 < 64 ? (int)(total - tile * 64) : 64);
+    const float* oh = p.onehot + tile * 64 * ld;
+    __syncthreads();                                          // the previous step's rows have been read
+#pragma unroll 11
+    for (int j = lane; j < rows * ld; j += 64) stg[wave][j] = oh[j];
+    unsigned int mask = 0u;
+    if (e < total) {
+      const long b = e / p.HW, pix = e - b * p.HW;
+      float v[SMAXC], lse;
+      seg_softmax(p, b, pix, v, lse);
+      for (int c = 0; c < p.C; ++c) mask |= (expf(v[c] - lse) > p.thr ? 1u : 0u) << c;
+    }
+    __syncthreads();
+    // lane c < C accumulates class c over the tile's rows; rows past the end have mask 0 and are not read
+    for (int r = 0; r < rows; ++r) {
+      const unsigned int mr = (unsigned int)__builtin_amdgcn_readlane((int)mask, r);
+      if (lane < p.C) {
+        const double tc = (double)stg[wave][r * ld + lane];
+        const bool hit = (mr >> lane) & 1u;
+        tp += hit ? tc : 0.0;
+        sp += hit ? 1.0 : 0.0;
+        st += tc;
+      }
+    }
+  }
+  if (lane < p.C) {
+    sred[wave][lane] = tp;
+    sred[wave][p.C + lane] = sp;
+    sred[wave][2 * p.C + lane] = st;
+  }
+  __syncthreads();
+  const int K = 3 * p.C;
+  if (threadIdx.x < K) {
+    double s = 0.0;
+    for (int w = 0; w < FS_THREADS / 64; ++w) s += sred[w][threadIdx.x];
+    p.partial[(long)blockIdx.x * K + threadIdx.x] = s;
+  }
+}
+
+// Thread t sums entry t % K over the partial rows t / K, t / K + G, ... (G = 256 / K groups), then thread i < K adds the
+// G group sums in order: a fixed order, independent of timing.
+__global__ __launch_bounds__(FS_THREADS) void fscore_final_kernel(const SegArgs p, double* counts) {
+  __shared__ double grp[FS_THREADS];
+  __shared__ double tot[3 * SMAXC];
+  const int K = 3 * p.C, G = FS_THREADS / K;
+  const int i = threadIdx.x % K, g = threadIdx.x / K;
+  if (g < G) {
+    double s = 0.0;
+#pragma unroll 8
+    for (int k = g; k < p.nblocks; k += G) s += p.partial[(long)k * K + i];
+    grp[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    double s = 0.0;
+    for (int q = 0; q < G; ++q) s += grp[q * K + threadIdx.x];
+    tot[threadIdx.x] = s;
+    if (counts) counts[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double b2 = (double)p.beta * p.beta, sm = p.smooth;
+    double mean = 0.0;
+    for (int c = 0; c < p.C; ++c) {
+      const double tpc = tot[c], spc = tot[p.C + c], stc = tot[2 * p.C + c];
+      const double fn = stc - tpc, fp = spc - tpc;
+      mean += ((1.0 + b2) * tpc + sm) / ((1.0 + b2) * tpc + b2 * fn + fp + sm);
+    }
+    p.out[0] = (float)(mean / p.C);
+  }
+}
+
 }  // namespace
 
 extern "C" long vrnet_yolo_loss_workspace(int B, long n_anchors, int max_gt, int num_classes) {
@@ -559,6 +650,27 @@ extern "C" int vrnet_seg_loss_f32(const float* x, const long long* png, const fl
   hipLaunchKernelGGL(seg_final_kernel, dim3(1), dim3(128), K * sizeof(double), st, p);
   if (dx) hipLaunchKernelGGL(seg_grad_kernel, dim3(p.nblocks), dim3(256), 0, st, p);
   VR_LAUNCH_CHECK("seg_loss");
+  return VR_OK;
+}
+
+extern "C" int vrnet_seg_fscore_f32(const float* x, const float* onehot, int B, int C, long HW, float beta, float smooth,
+                                    float threshold, float* out, double* counts, void* workspace, long workspace_bytes,
+                                    void* stream) {
+  VR_CHECK_ARG(x && onehot && out && workspace && B > 0 && C > 0 && C <= SMAXC && HW > 0,
+               "seg_fscore: bad arguments (1..%d classes, one-hot target required)", SMAXC);
+  if (workspace_bytes < vrnet_seg_loss_workspace(B, C, HW)) {
+    vr_set_error("seg_fscore: workspace too small");
+    return VR_ERR_WORKSPACE;
+  }
+  SegArgs p{};
+  p.x = x; p.onehot = onehot; p.B = B; p.C = C; p.HW = HW; p.beta = beta; p.smooth = smooth; p.thr = threshold;
+  p.out = out;
+  p.nblocks = (int)seg_blocks((long)B * HW);
+  p.partial = reinterpret_cast<double*>(workspace);
+  hipStream_t st = vr_stream(stream);
+  hipLaunchKernelGGL(fscore_reduce_kernel, dim3(p.nblocks), dim3(FS_THREADS), 0, st, p);
+  hipLaunchKernelGGL(fscore_final_kernel, dim3(1), dim3(FS_THREADS), 0, st, p, counts);
+  VR_LAUNCH_CHECK("seg_fscore");
   return VR_OK;
 }
 

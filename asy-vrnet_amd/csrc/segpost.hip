@@ -1,0 +1,159 @@
+// Segmentation post-processing of the seg logits: the class map of utils_seg/callbacks.py:113-160 `get_miou_png` /
+// deeplab.py:141-167 `detect_image`, and the confusion matrix of utils_seg/utils_metrics.py:35-44 `fast_hist`.
+//   softmax   one thread per pixel of the letterbox window: softmax over the C channels of the NCHW logits, written to
+//             the workspace as planes (B, C, nh, nw) fp32, computed once per window pixel rather than once per tap
+//   resize    one thread per output pixel: OpenCV INTER_LINEAR coordinates per axis, the 4 taps blended horizontally then
+//             vertically, class by class, arg-max with the lower class first on equal values (numpy argmax); one byte out.
+//             Planes, not pixel-major rows: neighbouring output pixels share or neighbour their taps, so one class's tap
+//             loads of a wave fall in one or two cache lines (pixel-major rows of C floats spread them over C times as many)
+//   hist      (label, pred) pair counts in a per-workgroup LDS histogram (n <= 32: 4 KiB), then one 64-bit atomic per
+//             non-empty bin; integer atomics only, so the result does not depend on the order in which workgroups run
+// The f_score metric (utils_metrics.py:12-31) sits next to the seg loss in loss.hip.
+#include "common.h"
+
+// The source coordinate is computed in fp32 with one rounding per operation, as the rule it implements states; a fused
+// multiply-add could move floor() across an integer and pick another tap.
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int SEGP_MAXC = 32;        // the seg loss's class cap (SMAXC in loss.hip)
+constexpr int HIST_MAXN = 32;
+
+struct SegPredArgs {
+  const float* x;                    // (B, C, H, W)
+  int B, C, H, W, top, left, nh, nw, oh, ow;
+  float sy, sx;                      // nh / oh, nw / ow
+  float* prob;                       // (B, C, nh, nw)
+  unsigned char* out;                // (B, oh, ow)
+};
+
+__global__ __launch_bounds__(256) void segp_softmax_kernel(const SegPredArgs p) {
+  const long total = (long)p.B * p.nh * p.nw;
+  const long plane = (long)p.H * p.W;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const long b = e / ((long)p.nh * p.nw);
+    const int r = (int)(e - b * p.nh * p.nw), y = r / p.nw, xx = r - y * p.nw;
+    const float* src = p.x + b * p.C * plane + (long)(p.top + y) * p.W + (p.left + xx);
+    float m = -INFINITY;
+    for (int c = 0; c < p.C; ++c) m = fmaxf(m, src[c * plane]);
+    float s = 0.f;
+    for (int c = 0; c < p.C; ++c) s += expf(src[c * plane] - m);
+    float* dst = p.prob + b * p.C * p.nh * p.nw + r;
+    for (int c = 0; c < p.C; ++c) dst[(long)c * p.nh * p.nw] = expf(src[c * plane] - m) / s;
+  }
+}
+
+// OpenCV resize INTER_LINEAR source coordinate along one axis: f = (d + 0.5) * scale - 0.5, s = floor(f), f -= s, clamped
+// to the first / last source pixel with weight 0 on the second tap.
+__device__ __forceinline__ void linear_tap(int d, float scale, int src, int& s0, int& s1, float& f) {
+  f = ((float)d + 0.5f) * scale - 0.5f;
+  const float fl = floorf(f);
+  int s = (int)fl;
+  f = f - fl;
+  if (s < 0) { s = 0; f = 0.f; }
+  if (s >= src - 1) { s = src - 1; f = 0.f; }
+  s0 = s;
+  s1 = s + 1 < src ? s + 1 : s;
+}
+
+__global__ __launch_bounds__(256) void segp_resize_argmax_kernel(const SegPredArgs p) {
+  const long total = (long)p.B * p.oh * p.ow;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const long b = e / ((long)p.oh * p.ow);
+  const int r = (int)(e - b * p.oh * p.ow), oy = r / p.ow, ox = r - oy * p.ow;
+  int y0, y1, x0, x1;
+  float fy, fx;
+  linear_tap(oy, p.sy, p.nh, y0, y1, fy);
+  linear_tap(ox, p.sx, p.nw, x0, x1, fx);
+  const float ax0 = 1.f - fx, ay0 = 1.f - fy;
+  const long pl = (long)p.nh * p.nw;
+  const float* r0 = p.prob + b * p.C * pl + (long)y0 * p.nw;
+  const float* r1 = p.prob + b * p.C * pl + (long)y1 * p.nw;
+  float best = 0.f;
+  int arg = 0;
+  for (int c = 0; c < p.C; ++c) {
+    const float top = r0[c * pl + x0] * ax0 + r0[c * pl + x1] * fx;
+    const float bot = r1[c * pl + x0] * ax0 + r1[c * pl + x1] * fx;
+    const float v = top * ay0 + bot * fy;
+    if (c == 0 || v > best) { best = v; arg = c; }
+  }
+  p.out[e] = (unsigned char)arg;
+}
+
+template <typename TL, typename TP>
+__global__ __launch_bounds__(256) void confusion_hist_kernel(const TL* label, const TP* pred, long N, int n,
+                                                             unsigned long long* hist) {
+  __shared__ unsigned int bins[HIST_MAXN * HIST_MAXN];
+  for (int i = threadIdx.x; i < n * n; i += 256) bins[i] = 0u;
+  __syncthreads();
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < N; e += (long)gridDim.x * 256) {
+    const long long a = (long long)label[e], b = (long long)pred[e];
+    if (a >= 0 && a < n && b >= 0 && b < n) atomicAdd(&bins[a * n + b], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n * n; i += 256)
+    if (bins[i]) atomicAdd(&hist[i], (unsigned long long)bins[i]);
+}
+
+template <typename TL>
+void launch_hist(const TL* label, const void* pred, int pred_bytes, long N, int n, long long* hist, int grid,
+                 hipStream_t st) {
+  auto* h = reinterpret_cast<unsigned long long*>(hist);
+  if (pred_bytes == 1)
+    hipLaunchKernelGGL((confusion_hist_kernel<TL, unsigned char>), dim3(grid), dim3(256), 0, st, label,
+                       static_cast<const unsigned char*>(pred), N, n, h);
+  else
+    hipLaunchKernelGGL((confusion_hist_kernel<TL, long long>), dim3(grid), dim3(256), 0, st, label,
+                       static_cast<const long long*>(pred), N, n, h);
+}
+
+}  // namespace
+
+extern "C" long vrnet_seg_predict_workspace(int B, int C, int nh, int nw) {
+  return (long)B * nh * nw * C * (long)sizeof(float) + 256;
+}
+
+extern "C" int vrnet_seg_predict_f32(const float* x, int B, int C, int H, int W, int top, int left, int nh, int nw, int oh,
+                                     int ow, unsigned char* out, void* workspace, long workspace_bytes, void* stream) {
+  VR_CHECK_ARG(x && out && workspace && B > 0 && C > 0 && C <= SEGP_MAXC && H > 0 && W > 0 && nh > 0 && nw > 0 && top >= 0 &&
+                   left >= 0 && (long)top + nh <= H && (long)left + nw <= W && oh > 0 && ow > 0,
+               "seg_predict: bad arguments (1..%d classes; the window top %d left %d %d x %d must lie inside %d x %d; "
+               "output %d x %d)", SEGP_MAXC, top, left, nh, nw, H, W, oh, ow);
+  if (workspace_bytes < vrnet_seg_predict_workspace(B, C, nh, nw)) {
+    vr_set_error("seg_predict: workspace %ld < %ld bytes", workspace_bytes, vrnet_seg_predict_workspace(B, C, nh, nw));
+    return VR_ERR_WORKSPACE;
+  }
+  SegPredArgs p{};
+  p.x = x; p.B = B; p.C = C; p.H = H; p.W = W; p.top = top; p.left = left; p.nh = nh; p.nw = nw; p.oh = oh; p.ow = ow;
+  p.sy = (float)nh / (float)oh;
+  p.sx = (float)nw / (float)ow;
+  p.prob = reinterpret_cast<float*>(workspace);
+  p.out = out;
+  hipStream_t st = vr_stream(stream);
+  const long nwin = (long)B * nh * nw, nout = (long)B * oh * ow;
+  long g1 = vr_cdiv(nwin, 256);
+  if (g1 > 4096) g1 = 4096;
+  hipLaunchKernelGGL(segp_softmax_kernel, dim3((unsigned)g1), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(segp_resize_argmax_kernel, dim3((unsigned)vr_cdiv(nout, 256)), dim3(256), 0, st, p);
+  VR_LAUNCH_CHECK("seg_predict");
+  return VR_OK;
+}
+
+extern "C" int vrnet_confusion_hist(const void* label, int label_bytes, const void* pred, int pred_bytes, long N, int n,
+                                    long long* hist, void* stream) {
+  VR_CHECK_ARG(hist && N >= 0 && n > 0 && n <= HIST_MAXN && (label_bytes == 1 || label_bytes == 8) &&
+                   (pred_bytes == 1 || pred_bytes == 8) && (N == 0 || (label && pred)),
+               "confusion_hist: bad arguments (1..%d classes; labels and predictions of 1 or 8 bytes)", HIST_MAXN);
+  if (N == 0) return VR_OK;
+  long grid = vr_cdiv(N, 256 * 8);
+  if (grid > 1024) grid = 1024;
+  hipStream_t st = vr_stream(stream);
+  if (label_bytes == 1)
+    launch_hist(static_cast<const unsigned char*>(label), pred, pred_bytes, N, n, hist, (int)grid, st);
+  else
+    launch_hist(static_cast<const long long*>(label), pred, pred_bytes, N, n, hist, (int)grid, st);
+  VR_LAUNCH_CHECK("confusion_hist");
+  return VR_OK;
+}

@@ -1,11 +1,13 @@
 """Box decode and NMS of the det maps, mirroring utils/utils_bbox.py: `decode_outputs` runs as one HIP
 kernel (no concat / grid / stride tensors); `non_max_suppression` as the HIP select + NMS kernels of csrc/nms.hip, in
 place of the torchvision `batched_nms` the reference calls (utils_bbox.py:124); `yolo_correct_boxes` is the reference's
-host-side letterbox un-map (numpy, on the handful of boxes that survive NMS)."""
+host-side letterbox un-map (numpy, on the handful of boxes that survive NMS).  `seg_predict` is the class map of the seg
+logits (utils_seg/callbacks.py:113-160, deeplab.py:141-167) as the two HIP kernels of csrc/segpost.hip."""
 import numpy as np
 import torch
 
 from . import hip
+from .metrics import MAX_CLASSES as SEG_MAX_CLASSES
 
 
 def decode_outputs(outputs, input_shape, local_rank=None):
@@ -104,3 +106,46 @@ def batched_nms(boxes, scores, idxs, iou_threshold):
                       idxs.detach().to(dev, torch.int64).contiguous(), None, None, 1, n, n, iou_threshold,
                       _nms_workspace(1, n, dev), keep, kept)
     return keep[:int(kept)].long()
+
+
+def seg_window(input_shape, image_shape):
+    """The letterbox window (top, left, nh, nw) that utils_seg/utils.py:19-31 `resize_image` pastes an image of
+    image_shape = (ih, iw) into, in a network input of input_shape = (H, W).  nw / nh truncate (int(), not the np.round of
+    yolo_correct_boxes: the reference's two letterboxes differ)."""
+    H, W = int(input_shape[0]), int(input_shape[1])
+    ih, iw = int(image_shape[0]), int(image_shape[1])
+    scale = min(W / iw, H / ih)
+    nw, nh = int(iw * scale), int(ih * scale)
+    return (H - nh) // 2, (W - nw) // 2, nh, nw
+
+
+def seg_predict(outputs_seg, input_shape, image_shape):
+    """get_miou_png / detect_image (utils_seg/callbacks.py:140-157, deeplab.py:141-167) for a batch of images of one
+    original size: outputs_seg (B, C, H, W) seg logits of a letterboxed input of input_shape = (H, W), image_shape =
+    (ih, iw).  Returns the (B, ih, iw) uint8 class map on the logits' device: per output pixel the arg-max over classes of
+    the OpenCV INTER_LINEAR resize of the letterbox window's softmax (softmax, crop, resize, arg-max: the reference's
+    order), equal values going to the lower class as numpy argmax.  No host synchronisation; fp16 / bf16 logits are
+    computed in fp32."""
+    if not (torch.is_tensor(outputs_seg) and outputs_seg.dim() == 4):
+        raise RuntimeError("seg_predict: expects (B, C, H, W) seg logits")
+    B, C, H, W = outputs_seg.shape
+    if not 0 < C <= SEG_MAX_CLASSES:
+        raise RuntimeError(f"seg_predict: {C} classes (1..{SEG_MAX_CLASSES} supported)")
+    if (H, W) != (int(input_shape[0]), int(input_shape[1])):
+        raise RuntimeError(f"seg_predict: logits are {H} x {W}, input_shape is {tuple(input_shape)}")
+    ih, iw = int(image_shape[0]), int(image_shape[1])
+    if ih <= 0 or iw <= 0:
+        raise RuntimeError(f"seg_predict: bad image_shape {tuple(image_shape)}")
+    top, left, nh, nw = seg_window(input_shape, image_shape)
+    if nh <= 0 or nw <= 0:
+        raise RuntimeError(f"seg_predict: image {ih} x {iw} leaves an empty window in {H} x {W}")
+    if not outputs_seg.is_cuda:
+        raise RuntimeError("seg_predict: the logits must be on a GPU (there is no CPU fallback)")
+    x = outputs_seg.detach()
+    x = x if (x.is_contiguous() and x.dtype == torch.float32) else x.contiguous().float()
+    out = torch.empty((B, ih, iw), dtype=torch.uint8, device=x.device)
+    if B == 0:
+        return out
+    ws = torch.empty(hip.seg_predict_workspace_bytes(B, C, nh, nw), dtype=torch.uint8, device=x.device)
+    hip.seg_predict(x, top, left, nh, nw, out, ws)
+    return out

@@ -131,6 +131,10 @@ _SIGS = {
     "vrnet_yolo_loss_f32": ([P, P, P, P, P, I, I, I, P, P, I, F, P, P, P, P, P, L, P], I),
     "vrnet_seg_loss_workspace": ([I, I, L], L),
     "vrnet_seg_loss_f32": ([P, P, P, P, I, I, L, I, I, F, F, F, F, F, P, P, P, L, P], I),
+    "vrnet_seg_fscore_f32": ([P, P, I, I, L, F, F, F, P, P, P, L, P], I),
+    "vrnet_seg_predict_workspace": ([I, I, I, I], L),
+    "vrnet_seg_predict_f32": ([P, I, I, I, I, I, I, I, I, I, I, P, P, L, P], I),
+    "vrnet_confusion_hist": ([P, I, P, I, L, I, P, P], I),
     "vrnet_mean_square_workspace": ([I, P], L),
     "vrnet_mean_square_f32": ([I, P, P, P, P, L, P], I),
     "vrnet_mean_square_bwd_f32": ([I, P, P, P, P, P], I),
@@ -849,6 +853,34 @@ def seg_loss(x, png, onehot, weights, focal, dice, alpha, gamma, beta, smooth, g
     _check(_lib.vrnet_seg_loss_f32(ptr(x), ptr(png), ptr(onehot), ptr(weights), B, C, H * W, int(focal), int(bool(dice)),
                                    float(alpha), float(gamma), float(beta), float(smooth), float(grad_scale), ptr(out),
                                    ptr(dx), ptr(ws), ws.numel(), stream()), "seg_loss")
+
+
+def seg_fscore(x, onehot, beta, smooth, threshold, out, counts=None):
+    """x (B, C, H, W) fp32, onehot (B, H, W, C+1) fp32 -> out[0] = f_score (vrnet_seg_fscore_f32); counts (3C) fp64, if
+    given, receives the totals tp[C], sp[C], st[C]."""
+    B, C, H, W = x.shape
+    ws = _ws.get(_lib.vrnet_seg_loss_workspace(B, C, H * W), x.device)
+    _check(_lib.vrnet_seg_fscore_f32(ptr(x), ptr(onehot), B, C, H * W, float(beta), float(smooth), float(threshold),
+                                     ptr(out), ptr(counts), ptr(ws), ws.numel(), stream()), "seg_fscore")
+
+
+def seg_predict_workspace_bytes(B, C, nh, nw):
+    return _lib.vrnet_seg_predict_workspace(B, C, nh, nw)
+
+
+def seg_predict(x, top, left, nh, nw, out, ws):
+    """x (B, C, H, W) fp32 -> out (B, oh, ow) uint8: arg-max of the bilinear resize of the window's softmax
+    (vrnet_seg_predict_f32); ws: seg_predict_workspace_bytes(B, C, nh, nw) bytes."""
+    B, C, H, W = x.shape
+    _check(_lib.vrnet_seg_predict_f32(ptr(x), B, C, H, W, top, left, nh, nw, out.shape[1], out.shape[2], ptr(out), ptr(ws),
+                                      ws.numel(), stream()), "seg_predict")
+
+
+def confusion_hist(label, pred, n, hist):
+    """hist (n, n) int64 += counts of (label, pred) pairs with both in [0, n) (vrnet_confusion_hist); label / pred are
+    contiguous uint8 or int64 tensors of one size."""
+    _check(_lib.vrnet_confusion_hist(ptr(label), label.element_size(), ptr(pred), pred.element_size(), label.numel(), n,
+                                     ptr(hist), stream()), "confusion_hist")
 
 
 def mean_square(tensors):

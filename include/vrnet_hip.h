@@ -582,6 +582,34 @@ int vrnet_nms_segmented_f32(const float* rows, int ld, const float* scores, cons
                             const int* counts, int segments, long stride, int n_max, double iou_thres, void* workspace,
                             long workspace_bytes, int* keep, int* kept, float* rows_out, void* stream);
 
+/* ---- segmentation post-processing (csrc/segpost.hip, loss.hip) ------------------------------------------------
+ * Added within ABI 11: new symbols only, no existing signature or layout changed; hip.py binds every declared symbol at
+ * load time, so a library without them fails the import.
+ * vrnet_seg_predict_f32, utils_seg/callbacks.py:140-157 (EvalCallback.get_miou_png) and deeplab.py:141-167 (detect_image):
+ *   x (B, C, H, W) fp32 seg logits, C <= 32; the letterbox window rows top .. top+nh-1, columns left .. left+nw-1 (inside
+ *   H x W) -> out (B, oh, ow) uint8 = per output pixel the arg-max over c of the bilinear resize of the window's softmax
+ *   (softmax over C, crop, resize, arg-max: the reference's order; equal values -> the lower c, as numpy argmax).  The
+ *   resize is OpenCV's INTER_LINEAR (cv2.resize at callbacks.py:153): per axis scale = src / dst, f = (d + 0.5) * scale - 0.5
+ *   in fp32, s = floor(f), f -= s, s < 0 -> (0, 0), s >= src - 1 -> (src - 1, 0); horizontal taps blended first.
+ *   workspace: vrnet_seg_predict_workspace(B, C, nh, nw) bytes (the window's softmax, (B, C, nh, nw) fp32).
+ * vrnet_confusion_hist, utils_seg/utils_metrics.py:35-44 (fast_hist, called per image at :102): hist (n, n) int64 +=
+ *   counts of the pairs (label[i], pred[i]), i < N, row = label, column = pred; label / pred of label_bytes / pred_bytes
+ *   = 1 (uint8) or 8 (int64) each; n <= 32.  A pair whose label or prediction is outside [0, n) is skipped (the reference
+ *   skips such labels and would bin such a prediction into another cell).  Integer atomics: the same result on every run.
+ * vrnet_seg_fscore_f32, utils_seg/utils_metrics.py:12-31 (f_score, utils/utils_fit.py:78,109,177): x (B, C, HW) fp32
+ *   logits, onehot (B, HW, C+1) fp32, C <= 32; per class c < C over every pixel tp = sum t_c [p_c > threshold],
+ *   sp = sum [p_c > threshold], st = sum t_c (p = softmax over C, t = onehot without its last channel; fp64 sums in a
+ *   fixed order), fn = st - tp, fp = sp - tp; out[0] = mean over c of ((1+b^2) tp + smooth) / ((1+b^2) tp + b^2 fn + fp +
+ *   smooth), b = beta.  counts (3C) fp64, if not NULL, receives tp[C], sp[C], st[C].  workspace:
+ *   vrnet_seg_loss_workspace(B, C, HW) bytes. */
+long vrnet_seg_predict_workspace(int B, int C, int nh, int nw);
+int vrnet_seg_predict_f32(const float* x, int B, int C, int H, int W, int top, int left, int nh, int nw, int oh, int ow,
+                          unsigned char* out, void* workspace, long workspace_bytes, void* stream);
+int vrnet_confusion_hist(const void* label, int label_bytes, const void* pred, int pred_bytes, long N, int n,
+                         long long* hist, void* stream);
+int vrnet_seg_fscore_f32(const float* x, const float* onehot, int B, int C, long HW, float beta, float smooth,
+                         float threshold, float* out, double* counts, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- input formats -----------------------------------------------------------------------------
  * What YoloDataset.__getitem__ / yolo_dataset_collate (utils/dataloader.py:88-107, 440-457) do to a letterboxed batch,
  * from BYTES: img (B, H, W, 3) u8 RGB -> images (B, 3, H, W) f32 = ((v / 255) - mean) / std evaluated in double and rounded

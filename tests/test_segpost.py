@@ -1,0 +1,458 @@
+"""Segmentation post-processing (csrc/segpost.hip, the f_score of csrc/loss.hip): float64 numpy restatements of
+utils_seg/utils_metrics.py `f_score` / `fast_hist`, of the letterbox window of utils_seg/utils.py `resize_image` and of the
+class map of get_miou_png / detect_image (softmax, crop, OpenCV INTER_LINEAR resize, arg-max), pinned on the reference's
+own values (tests/golden/segmetrics_small.npz, tools/make_golden_segmetrics.py) and on hand-built cases, then the HIP path
+(decode.seg_predict, metrics.f_score, metrics.fast_hist) against them."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from asy_vrnet_amd import decode, metrics
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "segmetrics_small.npz")
+F32 = np.float32
+NEAR_TIE = 1e-5          # top-two probability gap below which a pixel's class may differ from the restatement
+MAX_NEAR_TIES = 1e-3     # ... and the largest fraction of a case's pixels that may be such pixels
+THR_MARGIN = 1e-4        # no probability of an f_score input lies this close to a threshold
+
+
+# ---- the restatements -----------------------------------------------------------------------------------------------
+
+def softmax64(x):
+    """Softmax over axis 1 of (B, C, ...) logits, in float64."""
+    x = np.asarray(x, np.float64)
+    e = np.exp(x - x.max(axis=1, keepdims=True))
+    return e / e.sum(axis=1, keepdims=True)
+
+
+def f_score_restated(x, onehot, beta, smooth, thr):
+    """utils_metrics.py:12-31 on (B, C, H, W) logits and a (B, H, W, C+1) one-hot target: (score, (tp, sp, st))."""
+    hit = softmax64(x) > thr
+    t = np.moveaxis(np.asarray(onehot, np.float64)[..., :-1], -1, 1)
+    axes = (0,) + tuple(range(2, hit.ndim))
+    tp, sp, st = (t * hit).sum(axes), hit.sum(axes).astype(np.float64), t.sum(axes)
+    fn, fp = st - tp, sp - tp
+    b2 = float(beta) ** 2
+    score = ((1 + b2) * tp + smooth) / ((1 + b2) * tp + b2 * fn + fp + smooth)
+    return score.mean(), (tp, sp, st)
+
+
+def fast_hist_restated(a, b, n):
+    """Pair counts, row = label, column = prediction, of the pairs with both in [0, n)."""
+    a, b = np.asarray(a).reshape(-1).astype(np.int64), np.asarray(b).reshape(-1).astype(np.int64)
+    k = (a >= 0) & (a < n) & (b >= 0) & (b < n)
+    h = np.zeros((n, n), np.int64)
+    np.add.at(h, (a[k], b[k]), 1)
+    return h
+
+
+def fast_hist_reference_form(a, b, n):
+    """The reference's own expression (utils_metrics.py:39-44), for inputs whose predictions lie in [0, n)."""
+    a, b = np.asarray(a).reshape(-1), np.asarray(b).reshape(-1)
+    k = (a >= 0) & (a < n)
+    return np.bincount(n * a[k].astype(int) + b[k], minlength=n ** 2).reshape(n, n)
+
+
+def window_restated(input_shape, image_shape):
+    """utils_seg/utils.py:19-31 with size = (W, H), then the crop of callbacks.py:148-149: (top, left, nh, nw)."""
+    h, w = input_shape
+    ih, iw = image_shape
+    scale = min(w / iw, h / ih)
+    nw, nh = int(iw * scale), int(ih * scale)
+    return (h - nh) // 2, (w - nw) // 2, nh, nw
+
+
+def linear_coords(src, dst):
+    """OpenCV INTER_LINEAR source taps along one axis: scale = src / dst, f = (d + 0.5) * scale - 0.5 in float32,
+    s = floor(f), f -= s; s < 0 -> (0, 0); s >= src - 1 -> (src - 1, 0).  Returns (s0, s1, f)."""
+    scale = F32(src) / F32(dst)
+    f = (np.arange(dst, dtype=F32) + F32(0.5)) * scale - F32(0.5)
+    fl = np.floor(f)
+    f = f - fl
+    s = fl.astype(np.int64)
+    low = s < 0
+    s[low], f[low] = 0, 0
+    high = s >= src - 1
+    s[high], f[high] = src - 1, 0
+    assert f.dtype == F32
+    return s, np.minimum(s + 1, src - 1), f.astype(np.float64)
+
+
+def resize_linear(img, oh, ow, rows=None):
+    """(h, w, C) float64 -> (len(rows), ow, C): horizontal taps blended first, then vertical (output rows `rows`)."""
+    h, w = img.shape[:2]
+    y0, y1, fy = linear_coords(h, oh)
+    x0, x1, fx = linear_coords(w, ow)
+    if rows is not None:
+        y0, y1, fy = y0[rows], y1[rows], fy[rows]
+    ax = fx[None, :, None]
+    top = img[y0][:, x0] * (1 - ax) + img[y0][:, x1] * ax
+    bot = img[y1][:, x0] * (1 - ax) + img[y1][:, x1] * ax
+    ay = fy[:, None, None]
+    return top * (1 - ay) + bot * ay
+
+
+def seg_predict_restated(x, input_shape, image_shape, distinct=None, chunk=96):
+    """get_miou_png for each image of (B, C, H, W) logits: (class map (B, ih, iw) uint8, top-two gap (B, ih, iw)).  The gap
+    is taken over the channels `distinct` (default: all)."""
+    ih, iw = image_shape
+    top, left, nh, nw = window_restated(input_shape, image_shape)
+    p = softmax64(x)[:, :, top:top + nh, left:left + nw]
+    B, C = p.shape[:2]
+    cls = np.empty((B, ih, iw), np.uint8)
+    gap = np.empty((B, ih, iw), np.float64)
+    sel = list(range(C)) if distinct is None else list(distinct)
+    for b in range(B):
+        img = np.ascontiguousarray(np.moveaxis(p[b], 0, -1))
+        for r0 in range(0, ih, chunk):
+            v = resize_linear(img, ih, iw, rows=np.arange(r0, min(r0 + chunk, ih)))
+            cls[b, r0:r0 + len(v)] = v.argmax(axis=-1)
+            vs = v[..., sel]
+            if len(sel) > 1:
+                two = np.partition(vs, -2, axis=-1)[..., -2:]
+                gap[b, r0:r0 + len(v)] = two[..., 1] - two[..., 0]
+            else:
+                gap[b, r0:r0 + len(v)] = np.inf
+    return cls, gap
+
+
+def onehot_of(labels, C):
+    return np.eye(C + 1, dtype=F32)[labels]
+
+
+def draw_logits(rng, shape, thresholds=(0.5, 0.3)):
+    """N(0, 3^2) logits, redrawing every pixel with a float64 probability within THR_MARGIN of a threshold."""
+    x = (3.0 * rng.standard_normal(shape)).astype(F32)
+    while True:
+        p = softmax64(x)
+        close = np.zeros((shape[0],) + shape[2:], bool)
+        for t in thresholds:
+            close |= (np.abs(p - t) < THR_MARGIN).any(axis=1)
+        if not close.any():
+            return x
+        idx = np.nonzero(close)
+        x[idx[0], :, idx[1], idx[2]] = (3.0 * rng.standard_normal((len(idx[0]), shape[1]))).astype(F32)
+
+
+# ---- the restatements pinned on the reference's values and on hand-built cases --------------------------------------
+
+@pytest.fixture(scope="module")
+def golden():
+    return np.load(GOLDEN)
+
+
+@pytest.mark.parametrize("C", [9, 21])
+def test_restated_f_score_matches_reference(golden, C):
+    x, labels = golden[f"fscore_c{C}_logits"], golden[f"fscore_c{C}_labels"]
+    p = softmax64(x)
+    for t in golden["thresholds"]:
+        assert np.abs(p - t).min() >= THR_MARGIN          # every threshold decision of the fixture is unambiguous
+    for i, beta in enumerate(golden["betas"]):
+        for j, thr in enumerate(golden["thresholds"]):
+            score, _ = f_score_restated(x, onehot_of(labels, C), beta, float(golden["smooth"]), thr)
+            want = float(golden[f"fscore_c{C}_scores"][i, j])
+            print(f"C={C} beta={beta} thr={thr}: restated {score:.9f} reference {want:.9f}")
+            assert abs(score - want) <= 1e-6
+
+
+def test_restated_fast_hist_matches_reference(golden):
+    n, a, b = int(golden["hist_n"]), golden["hist_label"], golden["hist_pred"]
+    assert (a == n).any() and (a == 255).any()
+    assert np.array_equal(fast_hist_restated(a, b, n), golden["hist"])
+    assert np.array_equal(fast_hist_reference_form(a, b, n), golden["hist"])
+
+
+def test_restated_window_matches_reference(golden):
+    H, W = golden["win_input"]
+    got = [window_restated((H, W), tuple(s)) for s in golden["win_sizes"]]
+    assert [(nw, nh) for _, _, nh, nw in got] == [tuple(v) for v in golden["win_nwnh"]]
+    assert [decode.seg_window((H, W), tuple(s)) for s in golden["win_sizes"]] == got
+    # the issue's worked example: 333 x 517 at 512 -> a window 329 wide at left 91 (np.round would give 330)
+    assert window_restated((512, 512), (517, 333)) == (0, 91, 512, 329)
+
+
+def test_restated_linear_identity():
+    img = np.random.default_rng(0).random((5, 7, 3))
+    assert np.array_equal(resize_linear(img, 5, 7), img)
+
+
+def test_restated_linear_row_upscale_and_edge_clamps():
+    a, b = 0.2, 1.0
+    img = np.array([[[a], [b]]])
+    got = resize_linear(img, 1, 4)[0, :, 0]
+    assert np.allclose(got, [a, 0.75 * a + 0.25 * b, 0.25 * a + 0.75 * b, b], rtol=0, atol=1e-15)
+    # edge clamps: the first output column takes the first source column alone (s < 0 -> 0, f = 0), the last the last
+    s0, s1, f = linear_coords(3, 7)
+    assert (s0[0], f[0]) == (0, 0.0) and (s0[-1], f[-1]) == (2, 0.0)
+    img = np.random.default_rng(1).random((2, 3, 2))
+    out = resize_linear(img, 2, 7)
+    assert np.array_equal(out[:, 0], img[:, 0]) and np.array_equal(out[:, -1], img[:, -1])
+
+
+def test_restated_linear_exact_2x_downscale_is_block_mean():
+    img = np.random.default_rng(2).random((6, 8, 3))
+    want = img.reshape(3, 2, 4, 2, 3).mean(axis=(1, 3))
+    assert np.allclose(resize_linear(img, 3, 4), want, rtol=0, atol=1e-15)
+
+
+def test_restated_linear_one_pixel_wide_source():
+    img = np.random.default_rng(3).random((4, 1, 2))
+    out = resize_linear(img, 4, 5)
+    for d in range(5):
+        assert np.array_equal(out[:, d], img[:, 0])
+
+
+def test_restated_linear_against_cv2_when_available():
+    cv2 = pytest.importorskip("cv2")
+    rng = np.random.default_rng(4)
+    for (h, w), (oh, ow) in [((288, 512), (1080, 1920)), ((512, 329), (517, 333)), ((64, 64), (32, 32)), ((7, 1), (9, 5))]:
+        img = rng.random((h, w, 3)).astype(F32)
+        want = cv2.resize(img, (ow, oh), interpolation=cv2.INTER_LINEAR)
+        assert np.abs(resize_linear(img.astype(np.float64), oh, ow) - want).max() <= 1e-5
+
+
+def test_restated_argmax_lower_index_on_ties():
+    x = np.zeros((1, 4, 8, 8), F32)
+    x[:, 2] = x[:, 1] = 1.0
+    cls, gap = seg_predict_restated(x, (8, 8), (5, 9))
+    assert (cls == 1).all() and (gap == 0).all()
+
+
+# ---- argument errors that need no GPU -------------------------------------------------------------------------------
+
+def test_seg_predict_argument_errors():
+    with pytest.raises(RuntimeError, match="GPU"):
+        decode.seg_predict(torch.zeros(1, 9, 16, 16), (16, 16), (20, 30))
+    with pytest.raises(RuntimeError, match="classes"):
+        decode.seg_predict(torch.zeros(1, 33, 16, 16), (16, 16), (20, 30))
+    with pytest.raises(RuntimeError, match="input_shape"):
+        decode.seg_predict(torch.zeros(1, 9, 16, 16), (16, 32), (20, 30))
+    with pytest.raises(RuntimeError):
+        decode.seg_predict(torch.zeros(9, 16, 16), (16, 16), (20, 30))
+
+
+def test_f_score_argument_errors():
+    x = torch.zeros(2, 9, 16, 16)
+    with pytest.raises(RuntimeError, match="GPU"):
+        metrics.f_score(x, torch.zeros(2, 16, 16, 10))
+    with pytest.raises(RuntimeError, match="target"):
+        metrics.f_score(x, torch.zeros(2, 32, 32, 10))           # the reference's resize branch: not supported
+    with pytest.raises(RuntimeError, match="target"):
+        metrics.f_score(x, torch.zeros(2, 16, 16, 9))
+    with pytest.raises(RuntimeError, match="classes"):
+        metrics.f_score(torch.zeros(2, 33, 16, 16), torch.zeros(2, 16, 16, 34))
+
+
+def test_fast_hist_argument_errors():
+    a = torch.zeros(100, dtype=torch.uint8)
+    with pytest.raises(RuntimeError, match="GPU"):
+        metrics.fast_hist(a, a, 9)
+    with pytest.raises(RuntimeError, match="n = 33"):
+        metrics.fast_hist(a, a, 33)
+    with pytest.raises(RuntimeError, match="n = 0"):
+        metrics.fast_hist(a, a, 0)
+    with pytest.raises(RuntimeError, match="uint8 or int64"):
+        metrics.fast_hist(a.int(), a, 9)
+    with pytest.raises(RuntimeError, match="predictions"):
+        metrics.fast_hist(a, a[:99], 9)
+    with pytest.raises(RuntimeError, match="out"):
+        metrics.fast_hist(a, a, 9, out=torch.zeros(9, 9, dtype=torch.int32))
+
+
+def test_exports():
+    import asy_vrnet_amd.hip as hip
+    assert {"vrnet_seg_predict_workspace", "vrnet_seg_predict_f32", "vrnet_confusion_hist",
+            "vrnet_seg_fscore_f32"} <= set(hip.EXPORTED)
+    assert hip.seg_predict_workspace_bytes(2, 9, 288, 512) >= 2 * 288 * 512 * 9 * 4
+
+
+# ---- the HIP path against the restatements --------------------------------------------------------------------------
+
+def check_predict(x, input_shape, image_shape, distinct=None):
+    before = x.clone()
+    got = decode.seg_predict(x, input_shape, image_shape)
+    assert torch.equal(x, before), "the logits were modified"
+    B = x.shape[0]
+    assert got.is_cuda and got.dtype == torch.uint8 and tuple(got.shape) == (B,) + tuple(image_shape)
+    want, gap = seg_predict_restated(x.float().cpu().numpy(), input_shape, image_shape, distinct)
+    got = got.cpu().numpy()
+    near = gap < NEAR_TIE
+    wrong = (got != want) & ~near
+    print(f"seg_predict {tuple(x.shape)} -> {tuple(image_shape)}: {int(near.sum())} of {near.size} pixels near a tie, "
+          f"{int((got != want).sum())} differ, {int(wrong.sum())} of them outside a near tie")
+    assert not wrong.any()
+    assert near.sum() <= MAX_NEAR_TIES * near.size
+    return got, want
+
+
+PREDICT_CASES = [  # (B, C, input (H, W), image (ih, iw)): every size, B in {1, 3}, C in {2, 9, 21, 32}
+    (1, 9, (512, 512), (1080, 1920)), (3, 2, (512, 512), (480, 640)), (1, 21, (512, 512), (517, 333)),
+    (3, 32, (512, 512), (60, 100)), (3, 9, (512, 512), (512, 512)), (1, 32, (512, 512), (256, 256)),
+    (3, 21, (128, 192), (360, 640)), (1, 2, (128, 192), (360, 640)), (1, 32, (512, 512), (480, 640)),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,C,input_shape,image_shape", PREDICT_CASES)
+def test_seg_predict_matches_restatement(B, C, input_shape, image_shape):
+    rng = np.random.default_rng(B * 1000 + C + image_shape[0])
+    x = torch.from_numpy((3.0 * rng.standard_normal((B, C) + input_shape)).astype(F32)).cuda()
+    check_predict(x, input_shape, image_shape)
+
+
+@pytest.mark.gpu
+def test_seg_predict_duplicated_channels_pick_lower_index():
+    rng = np.random.default_rng(12)
+    x = (3.0 * rng.standard_normal((2, 6, 512, 512))).astype(F32)
+    x[:, 3], x[:, 5] = x[:, 1], x[:, 0]
+    got, want = check_predict(torch.from_numpy(x).cuda(), (512, 512), (480, 640), distinct=(0, 1, 2, 4))
+    assert not np.isin(got, (3, 5)).any()
+    assert (got == 1).any() and (got == 0).any()
+    same = decode.seg_predict(torch.zeros(2, 5, 64, 64, device="cuda"), (64, 64), (100, 37))
+    assert (same == 0).all()
+
+
+@pytest.mark.gpu
+def test_seg_predict_half_precision_logits():
+    rng = np.random.default_rng(13)
+    x = torch.from_numpy((3.0 * rng.standard_normal((2, 9, 128, 128))).astype(F32)).cuda()
+    for dt in (torch.float16, torch.bfloat16):
+        xl = x.to(dt)
+        assert torch.equal(decode.seg_predict(xl, (128, 128), (360, 640)), decode.seg_predict(xl.float(), (128, 128), (360, 640)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("C", [9, 21])
+def test_f_score_matches_reference(golden, C):
+    x = torch.from_numpy(golden[f"fscore_c{C}_logits"]).cuda()
+    t = torch.from_numpy(onehot_of(golden[f"fscore_c{C}_labels"], C)).cuda()
+    for i, beta in enumerate(golden["betas"]):
+        for j, thr in enumerate(golden["thresholds"]):
+            got = metrics.f_score(x, t, beta=int(beta), smooth=float(golden["smooth"]), threhold=float(thr))
+            assert got.is_cuda and got.dtype == torch.float32 and got.dim() == 0
+            want = float(golden[f"fscore_c{C}_scores"][i, j])
+            print(f"C={C} beta={beta} thr={thr}: HIP {float(got):.9f} reference {want:.9f}")
+            assert abs(float(got) - want) <= 1e-6
+
+
+@pytest.mark.gpu
+def test_f_score_counts_match_restatement_at_training_size():
+    import asy_vrnet_amd.hip as hip
+    rng = np.random.default_rng(14)
+    B, C, H, W = 8, 9, 512, 512
+    x = draw_logits(rng, (B, C, H, W))
+    labels = rng.integers(0, C + 1, size=(B, H, W)).astype(np.uint8)
+    agree = rng.random((B, H, W)) < 0.6
+    labels[agree] = x.argmax(axis=1).astype(np.uint8)[agree]
+    onehot = onehot_of(labels, C)
+    xg, tg = torch.from_numpy(x).cuda(), torch.from_numpy(onehot).cuda()
+    for beta, thr in ((1, 0.5), (2, 0.3)):
+        score, counts = f_score_restated(x, onehot, beta, 1e-5, thr)
+        out = torch.empty(1, device="cuda")
+        got_counts = torch.empty(3 * C, dtype=torch.float64, device="cuda")
+        hip.seg_fscore(xg, tg, beta, 1e-5, thr, out, got_counts)
+        got_counts = got_counts.cpu().numpy().reshape(3, C)
+        print(f"beta={beta} thr={thr}: HIP {float(out):.9f} restated {score:.9f}; tp {got_counts[0].astype(int)}")
+        assert np.array_equal(got_counts, np.stack(counts))
+        assert abs(float(out) - score) <= 1e-6
+        assert torch.equal(metrics.f_score(xg, tg, beta=beta, threhold=thr).reshape(1), out)
+
+
+@pytest.mark.gpu
+def test_f_score_half_precision_input(golden):
+    x = torch.from_numpy(golden["fscore_c9_logits"]).cuda()
+    t = torch.from_numpy(onehot_of(golden["fscore_c9_labels"], 9)).cuda()
+    for dt in (torch.float16, torch.bfloat16):
+        xl = x.to(dt)
+        got = metrics.f_score(xl, t)
+        assert got.dtype == torch.float32
+        assert torch.equal(got, metrics.f_score(xl.float(), t))
+        xr = xl.float().cpu().numpy()
+        print(f"{dt}: closest probability to the threshold {np.abs(softmax64(xr) - 0.5).min():.3g}")
+        want, _ = f_score_restated(xr, onehot_of(golden["fscore_c9_labels"], 9), 1, 1e-5, 0.5)
+        assert abs(float(got) - want) <= 1e-6
+
+
+@pytest.mark.gpu
+def test_post_processing_is_deterministic_and_does_not_sync():
+    rng = np.random.default_rng(15)
+    x = torch.from_numpy(draw_logits(rng, (4, 9, 128, 128))).cuda()
+    t = torch.from_numpy(onehot_of(rng.integers(0, 10, size=(4, 128, 128)), 9)).cuda()
+    labels = torch.from_numpy(rng.integers(0, 10, size=(4, 360, 640)).astype(np.uint8)).cuda()
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        a = metrics.f_score(x, t)
+        b = metrics.f_score(x, t)
+        pa = decode.seg_predict(x, (128, 128), (360, 640))
+        pb = decode.seg_predict(x, (128, 128), (360, 640))
+        ha = metrics.fast_hist(labels, pa, 9)
+        hb = metrics.fast_hist(labels, pb, 9)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert torch.equal(pa, pb) and torch.equal(ha, hb)
+
+
+def random_pairs(rng, N, n, label_dtype, pred_dtype, out_of_range_preds):
+    a = rng.integers(0, n + 1, size=N)
+    a[rng.random(N) < 0.05] = 255
+    b = rng.integers(0, n, size=N)
+    if out_of_range_preds:
+        b[rng.random(N) < 0.05] = n
+        if pred_dtype == np.int64:
+            b[rng.random(N) < 0.02] = -1
+        if label_dtype == np.int64:
+            a[rng.random(N) < 0.02] = -3
+    return a.astype(label_dtype), b.astype(pred_dtype)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("label_dtype", [np.uint8, np.int64])
+@pytest.mark.parametrize("pred_dtype", [np.uint8, np.int64])
+def test_fast_hist_matches_bincount(label_dtype, pred_dtype):
+    rng = np.random.default_rng(16)
+    for N, n in ((1000003, 9), (777, 21), (4096, 32), (300, 1)):
+        a, b = random_pairs(rng, N, n, label_dtype, pred_dtype, out_of_range_preds=False)
+        got = metrics.fast_hist(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), n)
+        assert got.is_cuda and got.dtype == torch.int64 and got.shape == (n, n)
+        assert np.array_equal(got.cpu().numpy(), fast_hist_reference_form(a, b, n))
+        a, b = random_pairs(rng, N, n, label_dtype, pred_dtype, out_of_range_preds=True)
+        got = metrics.fast_hist(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), n)
+        assert np.array_equal(got.cpu().numpy(), fast_hist_restated(a, b, n))
+
+
+@pytest.mark.gpu
+def test_fast_hist_full_hd_batch_and_accumulation():
+    rng = np.random.default_rng(17)
+    a, b = random_pairs(rng, 8 * 1080 * 1920, 9, np.uint8, np.uint8, out_of_range_preds=False)
+    a, b = a.reshape(8, 1080, 1920), b.reshape(8, 1080, 1920)
+    ag, bg = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    want = fast_hist_reference_form(a, b, 9)
+    assert np.array_equal(metrics.fast_hist(ag, bg, 9).cpu().numpy(), want)
+    out = torch.zeros(9, 9, dtype=torch.int64, device="cuda")
+    total = np.zeros((9, 9), np.int64)
+    for k in range(3):
+        assert metrics.fast_hist(ag[k], bg[k].long(), 9, out=out) is out
+        total += fast_hist_reference_form(a[k], b[k], 9)
+    assert np.array_equal(out.cpu().numpy(), total)
+
+
+@pytest.mark.gpu
+def test_end_to_end_nano():
+    import asy_vrnet_amd as A
+    model = A.EfficientVRNet(4, 9, "nano", img_size=128).cuda().eval()
+    A.randomize_state_dict(model.state_dict(), seed=2)
+    x, r = A.synthetic_inputs(2, 128, 1, "cuda")
+    with torch.no_grad():
+        _, seg = model(x, r)
+    assert tuple(seg.shape) == (2, 9, 128, 128)
+    print("seg logits std", float(seg.std()))
+    pred = decode.seg_predict(seg, (128, 128), (360, 640))
+    labels = np.random.default_rng(18).integers(0, 10, size=(2, 360, 640)).astype(np.uint8)
+    labels[:, :20] = 255
+    hist = metrics.fast_hist(torch.from_numpy(labels).cuda(), pred, 9)
+    got, _ = check_predict(seg, (128, 128), (360, 640))
+    assert np.array_equal(hist.cpu().numpy(), fast_hist_reference_form(labels, got, 9))

@@ -1,9 +1,13 @@
 """Inference-side timing of the hot path on one GPU (not the BASELINE metric): eval-mode forward of EfficientVRNet +
 the box decode (decode_outputs), captured in one hipGraph per batch size.  With --nms CONF/IOU[,CONF/IOU...] the timed
 loop also runs non_max_suppression on the decoded boxes (outside the graph: its output size depends on the data), once
-per threshold pair, and reports the NMS step alone as well.
+per threshold pair, and reports the NMS step alone as well.  With --seg HxW[,HxW...] it times the seg side after the
+forward: decode.seg_predict into each original size H x W, metrics.fast_hist of that class map against random labels,
+and, once per batch size, metrics.f_score of the seg logits against a random one-hot target next to an eager torch
+expression of the same metric.
 
     python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
+                                [--seg 1080x1920,480x640]
 """
 import argparse
 import os
@@ -22,10 +26,23 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--nms", default="", help="comma list of conf/iou threshold pairs (e.g. 0.05/0.5,0.001/0.5)")
+    ap.add_argument("--seg", default="", help="comma list of original image sizes HxW (e.g. 1080x1920,480x640)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
-    from asy_vrnet_amd.decode import decode_outputs, non_max_suppression
+    from asy_vrnet_amd.decode import decode_outputs, non_max_suppression, seg_predict
+    from asy_vrnet_amd.metrics import f_score, fast_hist
     pairs = [tuple(float(v) for v in p.split("/")) for p in args.nms.split(",") if p]
+    seg_sizes = [tuple(int(v) for v in p.split("x")) for p in args.seg.split(",") if p]
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3
     dev = torch.device("cuda")
     model = A.EfficientVRNet(4, 9, args.phi, img_size=args.size).to(dev).eval()
     A.randomize_state_dict(model.state_dict(), seed=0)
@@ -65,16 +82,6 @@ def main():
             def post():
                 return non_max_suppression(out[0], model.num_classes, S, S, True, conf_thres=conf, nms_thres=iou)
 
-            def timed(fn):
-                for _ in range(3):
-                    fn()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(args.steps):
-                    fn()
-                torch.cuda.synchronize()
-                return (time.perf_counter() - t0) / args.steps * 1e3
-
             g.replay()
             dets = post()
             nms_ms = timed(post)
@@ -82,6 +89,41 @@ def main():
             cand = int(((out[0][..., 4:5] * out[0][..., 5:5 + model.num_classes]).amax(-1) >= conf).sum())
             print(f"  + non_max_suppression conf {conf} iou {iou}, bs={bs}: {full_ms:.3f} ms/batch "
                   f"(NMS alone {nms_ms:.3f} ms); candidates {cand}, kept {sum(len(d) for d in dets)}")
+
+        if seg_sizes:
+            g.replay()
+            seg = out[1]
+            ns = seg.shape[1]
+            gen = torch.Generator(device=dev).manual_seed(bs)
+            for ih, iw in seg_sizes:
+                pred_ms = timed(lambda: seg_predict(seg, S, (ih, iw)))
+                full_ms = timed(lambda: (g.replay(), seg_predict(seg, S, (ih, iw))))
+                pred = seg_predict(seg, S, (ih, iw))
+                labels = torch.randint(0, ns + 1, (bs, ih, iw), generator=gen, device=dev, dtype=torch.uint8)
+                hist_ms = timed(lambda: fast_hist(labels, pred, ns))
+                print(f"  + seg_predict to {ih}x{iw}, bs={bs}: {full_ms:.3f} ms/batch (seg_predict alone {pred_ms:.3f} ms); "
+                      f"fast_hist of the {bs}x{ih}x{iw} map {hist_ms:.3f} ms")
+            target = torch.nn.functional.one_hot(
+                torch.randint(0, ns + 1, (bs,) + S, generator=gen, device=dev), ns + 1).float()
+            f_ms = timed(lambda: f_score(seg, target))
+            e_ms = timed(lambda: f_score_eager(seg, target))
+            a, b = float(f_score(seg, target)), float(f_score_eager(seg, target))
+            print(f"  + f_score {bs}x{ns}x{S[0]}x{S[1]}: {f_ms:.3f} ms (eager torch {e_ms:.3f} ms); value {a:.6f} "
+                  f"(eager {b:.6f})")
+
+
+def f_score_eager(x, target, beta=1, smooth=1e-5, threshold=0.5):
+    """The f_score metric as plain torch operations, for comparison: softmax over the channels, threshold, per-class
+    true-positive / predicted / target sums over every pixel, the F-beta mean."""
+    n, c = x.shape[:2]
+    p = torch.softmax(x.float().permute(0, 2, 3, 1).reshape(n, -1, c), dim=-1)
+    hit = (p > threshold).float()
+    t = target.reshape(n, -1, c + 1)[..., :c]
+    tp = (t * hit).sum(dim=(0, 1))
+    fp = hit.sum(dim=(0, 1)) - tp
+    fn = t.sum(dim=(0, 1)) - tp
+    b2 = beta * beta
+    return (((1 + b2) * tp + smooth) / ((1 + b2) * tp + b2 * fn + fp + smooth)).mean()
 
 
 if __name__ == "__main__":
