@@ -1,9 +1,11 @@
 """Input formats of the training pipeline, restated from the reference's dataloader (utils/dataloader.py is
 not importable here: cv2 / albumentations).  Only the deterministic evaluation path (`random=False`) and the format
 conversions are covered; the random augmentations (mosaic, mixup, HSV jitter, :217-437) are a training-recipe concern
-outside the hot path.  Host side (numpy / PIL): parsing, letterbox, box mapping.  Device side (`device_batch`,
-csrc/formats.hip): the per-pixel conversions of a letterboxed batch -- image normalisation + CHW, label clamp, one-hot --
-from bytes.  Pins: the functions the reference keeps in importable modules (`preprocess_input`, `preprocess_input_radar`,
+outside the hot path.  Host side (numpy / PIL): parsing, box mapping, and the PIL letterbox (`letterbox_sample`,
+`resize_image`) kept as the restated reference.  Device side: `device_letterbox` (csrc/letterbox.hip) -- the letterbox
+itself from RAW frame bytes, Pillow's bicubic / nearest resize reproduced bit for bit, with the paste, the padding and
+the normalisation in the same call -- and `device_batch` (csrc/formats.hip): the per-pixel conversions of a letterboxed
+batch -- image normalisation + CHW, label clamp, one-hot -- from bytes.  Pins: the functions the reference keeps in importable modules (`preprocess_input`, `preprocess_input_radar`,
 `resize_image`) produced tests/golden/formats_small.npz (tools/make_golden_formats.py); round 5: the reference's own
 `YoloDataset.__getitem__` (train=False) + `yolo_dataset_collate`, importable once cv2 / albumentations are stubbed (the
 evaluation path touches neither), produced tests/golden/dataset_small.npz (tools/make_golden_dataset.py) -- parsing,
@@ -142,6 +144,42 @@ def device_batch(images_u8, pngs_u8, num_classes_seg, device="cuda"):
             raise RuntimeError(f"device_batch: expected uint8 bytes, got {t.dtype}")
         return t.to(device, non_blocking=True).contiguous()
     return hip.batch_formats(dev(images_u8), dev(pngs_u8), num_classes_seg)
+
+
+def device_letterbox(images_u8, input_shape, labels_u8=None, letterbox_image=True, normalise=True, device="cuda"):
+    """`resize_image` (utils/utils.py:19-32, utils_seg/utils.py:19-31) and the image / label half of `letterbox_sample`, ON
+    THE DEVICE from raw bytes (vrnet_letterbox_u8): images_u8 (B,ih,iw,3) uint8 RGB frames of ONE original size (a single
+    (ih,iw,3) frame counts as B = 1), labels_u8 (B,ih,iw) uint8 or None; input_shape = (H, W).  Returns (images, labels):
+    images (B,3,H,W) float32, normalised as `device_batch` does it, or the uint8 (B,H,W,3) canvas when normalise=False;
+    labels (B,H,W) uint8 -- what `device_batch(None, labels, ns)` takes -- or None.  The bytes are Pillow's BICUBIC /
+    NEAREST bytes, bit for bit.  letterbox_image=False stretches to the whole canvas (utils/utils.py:30-31).  numpy arrays
+    or tensors.  The boxes stay with `adjust_boxes`, on the host."""
+    from . import hip
+
+    def host(a, what, batched):
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        if t.dtype != torch.uint8:
+            raise RuntimeError(f"device_letterbox: expected uint8 {what}, got {t.dtype}")
+        return t[None] if t.dim() == batched - 1 else t
+    img = host(images_u8, "frames", 4)
+    if img.dim() != 4 or img.shape[-1] != 3:
+        raise RuntimeError(f"device_letterbox: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    B, ih, iw = img.shape[:3]
+    lab = None if labels_u8 is None else host(labels_u8, "labels", 3)
+    if lab is not None and tuple(lab.shape) != (B, ih, iw):
+        raise RuntimeError(f"device_letterbox: the labels {tuple(lab.shape)} do not match the frames {(B, ih, iw)}")
+    H, W = (int(v) for v in input_shape)
+    nw, nh, dx, dy = letterbox_geometry(max(iw, 1), max(ih, 1), W, H) if letterbox_image else (W, H, 0, 0)
+    if min(B, ih, iw) <= 0 or nw <= 0 or nh <= 0:
+        raise RuntimeError(f"device_letterbox: {B} frames of {ih} x {iw} leave an empty window ({nh} x {nw}) in a {H} x {W} input")
+    img = img.to(device, non_blocking=True).contiguous()
+    lab = None if lab is None else lab.to(device, non_blocking=True).contiguous()
+    with torch.cuda.device(img.device):
+        canvas = None if normalise else torch.empty((B, H, W, 3), dtype=torch.uint8, device=img.device)
+        images = torch.empty((B, 3, H, W), dtype=torch.float32, device=img.device) if normalise else None
+        labels = None if lab is None else torch.empty((B, H, W), dtype=torch.uint8, device=img.device)
+        hip.letterbox(img, lab, H, W, nw, nh, dx, dy, canvas=canvas, images=images, label_out=labels)
+    return (images if normalise else canvas), labels
 
 
 def make_sample(image, box, radar, png, num_classes_seg):

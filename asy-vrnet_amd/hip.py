@@ -127,6 +127,8 @@ _SIGS = {
     "vrnet_nms_workspace_bytes": ([I, I], L),
     "vrnet_nms_segmented_f32": ([P, I, P, P, P, P, I, L, I, D, P, L, P, P, P, P], I),
     "vrnet_batch_formats_u8": ([P, P, I, I, I, I, P, P, P, P], I),
+    "vrnet_letterbox_workspace": ([I, I, I, I, I], L),
+    "vrnet_letterbox_u8": ([P, P] + [I] * 9 + [P, P, P, P, L, P], I),
     "vrnet_yolo_loss_workspace": ([I, L, I, I], L),
     "vrnet_yolo_loss_f32": ([P, P, P, P, P, I, I, I, P, P, I, F, P, P, P, P, P, L, P], I),
     "vrnet_seg_loss_workspace": ([I, I, L], L),
@@ -830,6 +832,32 @@ def batch_formats(img_u8, png_u8, num_classes_seg, images=None, png_out=None, on
     _check(_lib.vrnet_batch_formats_u8(ptr(img_u8), ptr(png_u8), B, H, W, int(num_classes_seg), ptr(images), ptr(png_out),
                                        ptr(onehot), stream()), "batch_formats")
     return images, png_out, onehot
+
+
+def letterbox_workspace_bytes(B, ih, iw, nh, nw):
+    return _lib.vrnet_letterbox_workspace(B, ih, iw, nh, nw)
+
+
+def letterbox(img_u8, label_u8, H, W, nw, nh, dx, dy, canvas=None, images=None, label_out=None, ws=None):
+    """Raw frames -> the letterboxed batch, Pillow's bytes (vrnet_letterbox_u8): img_u8 (B,ih,iw,3) uint8 RGB, label_u8
+    (B,ih,iw) uint8 or None; the window nw x nh at column dx, row dy of the W x H canvas.  Outputs (None = not wanted):
+    canvas (B,H,W,3) uint8, images (B,3,H,W) f32 normalised as batch_formats does, label_out (B,H,W) uint8.  ws: a uint8
+    tensor of letterbox_workspace_bytes(B, ih, iw, nh, nw) bytes (default: this stream's scratch arena)."""
+    src = img_u8 if img_u8 is not None else label_u8
+    if src is None or src.dim() < 3:
+        raise RuntimeError("letterbox: expected frames (B, ih, iw, 3) and / or label maps (B, ih, iw)")
+    B, ih, iw = src.shape[:3]
+    for t, sh, dt in ((img_u8, (B, ih, iw, 3), torch.uint8), (label_u8, (B, ih, iw), torch.uint8),
+                      (canvas, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
+                      (label_out, (B, H, W), torch.uint8)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or not t.is_cuda):
+            raise RuntimeError(f"letterbox: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+    if ws is None:
+        ws = _ws.get(_lib.vrnet_letterbox_workspace(B, ih, iw, nh, nw), src.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"letterbox: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    _check(_lib.vrnet_letterbox_u8(ptr(img_u8), ptr(label_u8), B, ih, iw, int(H), int(W), int(nw), int(nh), int(dx), int(dy),
+                                   ptr(canvas), ptr(images), ptr(label_out), ptr(ws), ws.numel(), stream()), "letterbox")
 
 
 def yolo_loss(levels, grads, strides, labels, counts, max_gt, grad_scale, out, fg=None, matched=None, piou=None):

@@ -8,10 +8,11 @@ The CUDA dispatch key is the HIP device on ROCm.  There is no CPU kernel: callin
     out, idx = torch.ops.vrnet.cluster(f, v, alpha, beta, heads, fold)     # Cluster core, vr_coc.py:158-190
     y = torch.ops.vrnet.conv2d_nhwc(x, w, bias, stride, pad, dil)           # NHWC implicit-GEMM conv (fp32-accurate x6 / MFMA)
     keep = torch.ops.vrnet.batched_nms(boxes, scores, idxs, iou_threshold)  # torchvision.ops.boxes.batched_nms
+    images, labels = torch.ops.vrnet.letterbox(frames_u8, labels_u8, H, W, True)  # Pillow's letterbox from raw bytes
 """
 import torch
 
-from . import decode, hip
+from . import data, decode, hip
 
 
 @torch.library.custom_op("vrnet::cluster", mutates_args=(), device_types="cuda")
@@ -452,6 +453,21 @@ def _(images_u8, pngs_u8, num_classes_seg):
     B, H, W, _ = images_u8.shape
     return (images_u8.new_empty((B, 3, H, W), dtype=torch.float32), pngs_u8.new_empty((B, H, W), dtype=torch.int64),
             pngs_u8.new_empty((B, H, W, num_classes_seg + 1), dtype=torch.float32))
+
+
+@torch.library.custom_op("vrnet::letterbox", mutates_args=(), device_types="cuda")
+def letterbox(images_u8: torch.Tensor, labels_u8: torch.Tensor, input_h: int, input_w: int, letterbox_image: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """Raw frames (B,ih,iw,3) uint8 and label maps (B,ih,iw) uint8 of one original size -> the letterboxed batch
+    (utils/dataloader.py:131-146, utils/utils.py:19-32): images (B,3,H,W) float32 normalised as preprocess_input does,
+    labels (B,H,W) uint8; Pillow's BICUBIC / NEAREST bytes, bit for bit."""
+    return data.device_letterbox(images_u8, (input_h, input_w), labels_u8, letterbox_image, device=images_u8.device)
+
+
+@letterbox.register_fake
+def _(images_u8, labels_u8, input_h, input_w, letterbox_image):
+    B = images_u8.shape[0]
+    return (images_u8.new_empty((B, 3, input_h, input_w), dtype=torch.float32),
+            labels_u8.new_empty((B, input_h, input_w), dtype=torch.uint8))
 
 
 # ---- ShuffleAttention (backbone/attention_modules/shuffle_attention.py:48-72) --------------------------------------------

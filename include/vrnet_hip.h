@@ -620,6 +620,31 @@ int vrnet_seg_fscore_f32(const float* x, const float* onehot, int B, int C, long
 int vrnet_batch_formats_u8(const unsigned char* img, const unsigned char* png, int B, int H, int W, int num_classes_seg,
                            float* images, long long* png_out, float* onehot, void* stream);
 
+/* ---- letterbox from raw bytes (csrc/letterbox.hip) --------------------------------------------------------------
+ * Added within ABI 11: new symbols only, no existing signature or layout changed.
+ * vrnet_letterbox_u8, utils/utils.py:19-32 and utils_seg/utils.py:19-31 (resize_image: detect_image, get_FPS, get_map_txt,
+ *   both EvalCallbacks) and the random=False branch of get_random_data (utils/dataloader.py:131-146): img (B, ih, iw, 3) u8
+ *   RGB frames of ONE original size and, optionally, label (B, ih, iw) u8 maps -> the frames resized to nw x nh with
+ *   Pillow's Image.BICUBIC and pasted at column dx, row dy of a W x H canvas of 128, the labels resized with Image.NEAREST
+ *   and pasted on a canvas of 0.  The caller computes (nw, nh, dx, dy): scale = min(W / iw, H / ih), nw = int(iw * scale),
+ *   nh = int(ih * scale), dx = (W - nw) / 2, dy = (H - nh) / 2 (floor), or (W, H, 0, 0) for letterbox_image=False; required:
+ *   0 < nw <= W, 0 < nh <= H and the window inside the canvas.  Outputs, any non-empty subset (NULL = not wanted):
+ *   canvas (B, H, W, 3) u8; images (B, 3, H, W) f32 = the canvas normalised exactly as vrnet_batch_formats_u8 does it;
+ *   label_out (B, H, W) u8 (needs label).
+ *   EXACTNESS: the bytes are Pillow's, bit for bit (checked against Pillow 12.2).  Bicubic: Resample.c ImagingResample --
+ *   per axis in -> out: scale = in / out, fs = max(scale, 1), support = 2 fs; per output index xx: center = (xx + 0.5) scale,
+ *   xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), in), weights
+ *   bicubic((x + xmin - center + 0.5) / fs) (a = -0.5) normalised by their sum, k = (int)(w 2^22 +- 0.5); out = clamp((2^21 +
+ *   sum k v) >> 22, 0, 255) in int32; the horizontal pass first, its uint8 result feeding the vertical pass; a pass whose
+ *   axis keeps its size is skipped.  Nearest: Geometry.c ImagingScaleAffine -- per axis a0 = in / out, xo = a0 / 2,
+ *   idx[x] = (int)xo, xo += a0 (a running sum).  The tables are built on the device in double, one rounding per operation:
+ *   no host table, no copy, no synchronisation; the call can be captured in a graph.
+ *   workspace: vrnet_letterbox_workspace(B, ih, iw, nh, nw) bytes (the tables plus the horizontal pass's uint8 result). */
+long vrnet_letterbox_workspace(int B, int ih, int iw, int nh, int nw);
+int vrnet_letterbox_u8(const unsigned char* img, const unsigned char* label, int B, int ih, int iw, int H, int W, int nw,
+                       int nh, int dx, int dy, unsigned char* canvas, float* images, unsigned char* label_out,
+                       void* workspace, long workspace_bytes, void* stream);
+
 /* ---- training losses on the path's outputs: value + gradient w.r.t. the head outputs ------------
  * vrnet_yolo_loss_f32: YOLOLoss (nets/yolo_training.py:60-427): decode (:99-111), SimOTA assignment per image
  *   (get_assignments :200-264, get_in_boxes_info :291-368, dynamic_k_matching :370-427), IoU / objectness / class

@@ -4,10 +4,13 @@ loop also runs non_max_suppression on the decoded boxes (outside the graph: its 
 per threshold pair, and reports the NMS step alone as well.  With --seg HxW[,HxW...] it times the seg side after the
 forward: decode.seg_predict into each original size H x W, metrics.fast_hist of that class map against random labels,
 and, once per batch size, metrics.f_score of the seg logits against a random one-hot target next to an eager torch
-expression of the same metric.
+expression of the same metric.  With --letterbox HxW[,HxW...] it times the input side: data.device_letterbox of a batch of
+raw uint8 frames of each original size H x W into the network input -- on frames already resident on the device, and
+including the host-to-device copy from pinned memory -- next to Pillow's data.resize_image of the same frames on one
+core (where Pillow is installed), with the bytes per image that cross PCIe either way.
 
     python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
-                                [--seg 1080x1920,480x640]
+                                [--seg 1080x1920,480x640] [--letterbox 1080x1920,480x640]
 """
 import argparse
 import os
@@ -27,12 +30,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--nms", default="", help="comma list of conf/iou threshold pairs (e.g. 0.05/0.5,0.001/0.5)")
     ap.add_argument("--seg", default="", help="comma list of original image sizes HxW (e.g. 1080x1920,480x640)")
+    ap.add_argument("--letterbox", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
+    from asy_vrnet_amd.data import device_letterbox, resize_image
     from asy_vrnet_amd.decode import decode_outputs, non_max_suppression, seg_predict
     from asy_vrnet_amd.metrics import f_score, fast_hist
     pairs = [tuple(float(v) for v in p.split("/")) for p in args.nms.split(",") if p]
     seg_sizes = [tuple(int(v) for v in p.split("x")) for p in args.seg.split(",") if p]
+    frame_sizes = [tuple(int(v) for v in p.split("x")) for p in args.letterbox.split(",") if p]
 
     def timed(fn):
         for _ in range(3):
@@ -110,6 +116,29 @@ def main():
             a, b = float(f_score(seg, target)), float(f_score_eager(seg, target))
             print(f"  + f_score {bs}x{ns}x{S[0]}x{S[1]}: {f_ms:.3f} ms (eager torch {e_ms:.3f} ms); value {a:.6f} "
                   f"(eager {b:.6f})")
+
+        for ih, iw in frame_sizes:
+            gen = torch.Generator().manual_seed(bs)
+            pinned = torch.randint(0, 256, (bs, ih, iw, 3), generator=gen, dtype=torch.uint8).pin_memory()
+            resident = pinned.to(dev)
+            dev_ms = timed(lambda: device_letterbox(resident, S))
+            copy_ms = timed(lambda: device_letterbox(pinned, S))
+            line = (f"  + device_letterbox {ih}x{iw} -> {S[0]}x{S[1]}, bs={bs}: {dev_ms:.3f} ms/batch on resident frames, "
+                    f"{copy_ms:.3f} ms/batch with the copy from pinned memory ({copy_ms / bs:.3f} ms/image; "
+                    f"{ih * iw * 3 / 1e6:.2f} MB/image over PCIe, against {S[0] * S[1] * 3 / 1e6:.2f} MB letterboxed)")
+            try:
+                from PIL import Image
+            except ImportError:
+                print(line + "; Pillow not installed")
+                continue
+            pil = [Image.fromarray(f) for f in pinned.numpy()]
+            resize_image(pil[0], (S[1], S[0]))
+            t0 = time.perf_counter()
+            for _ in range(3):
+                for im in pil:
+                    resize_image(im, (S[1], S[0]))
+            pil_ms = (time.perf_counter() - t0) / (3 * bs) * 1e3
+            print(line + f"; Pillow resize_image on one core {pil_ms:.3f} ms/image")
 
 
 def f_score_eager(x, target, beta=1, smooth=1e-5, threshold=0.5):
