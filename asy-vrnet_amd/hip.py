@@ -137,6 +137,8 @@ _SIGS = {
     "vrnet_seg_predict_workspace": ([I, I, I, I], L),
     "vrnet_seg_predict_f32": ([P, I, I, I, I, I, I, I, I, I, I, P, P, L, P], I),
     "vrnet_confusion_hist": ([P, I, P, I, L, I, P, P], I),
+    "vrnet_det_map_workspace_bytes": ([I, I, I], L),
+    "vrnet_det_map_f64": ([P, P, P, P, P, P, I, P, P, P, P, I, I, I, P, I, D] + [P] * 15 + [P, L, P], I),
     "vrnet_mean_square_workspace": ([I, P], L),
     "vrnet_mean_square_f32": ([I, P, P, P, P, L, P], I),
     "vrnet_mean_square_bwd_f32": ([I, P, P, P, P, P], I),
@@ -909,6 +911,22 @@ def confusion_hist(label, pred, n, hist):
     contiguous uint8 or int64 tensors of one size."""
     _check(_lib.vrnet_confusion_hist(ptr(label), label.element_size(), ptr(pred), pred.element_size(), label.numel(), n,
                                      ptr(hist), stream()), "confusion_hist")
+
+
+def det_map(det_image, det_label, det_score, det_box, order, det_offsets, gt_box, gt_difficult, gt_perm, gt_offsets,
+            n_images, num_classes, min_overlap, score_threhold, out, ws=None):
+    """VOC AP matching and curves for len(min_overlap) IoU thresholds (vrnet_det_map_f64, which documents every array).
+    out: dict of the output tensors by the header's names; out["rec"] / out["prec"] may be None."""
+    D, G, T = det_score.numel(), gt_difficult.numel(), len(min_overlap)
+    if ws is None:
+        ws = _ws.get(_lib.vrnet_det_map_workspace_bytes(D, G, T), det_offsets.device)
+    thr = (ctypes.c_double * T)(*[float(v) for v in min_overlap])
+    _check(_lib.vrnet_det_map_f64(ptr(det_image), ptr(det_label), ptr(det_score), ptr(det_box), ptr(order), ptr(det_offsets), D,
+                                  ptr(gt_box), ptr(gt_difficult), ptr(gt_perm), ptr(gt_offsets), G, int(n_images),
+                                  int(num_classes), thr, T, float(score_threhold),
+                                  *[ptr(out[k]) for k in ("match", "ovmax", "tp", "fp", "rec", "prec", "n_gt", "n_img", "n_tp",
+                                                          "ap", "f1", "recall", "precision", "lamr", "map")],
+                                  ptr(ws), ws.numel(), stream()), "det_map")
 
 
 def mean_square(tensors):

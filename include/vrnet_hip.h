@@ -610,6 +610,43 @@ int vrnet_confusion_hist(const void* label, int label_bytes, const void* pred, i
 int vrnet_seg_fscore_f32(const float* x, const float* onehot, int B, int C, long HW, float beta, float smooth,
                          float threshold, float* out, double* counts, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- detection mAP (csrc/detmap.hip) ---------------------------------------------------------------------------
+ * Added within ABI 11: new symbols only, no existing signature or layout changed; hip.py binds every declared symbol at
+ * load time, so a library without them fails the import.
+ * vrnet_det_map_f64, utils/utils_map.py:276-798 (get_map, called at utils/callbacks.py:226; voc_ap :95-136,
+ *   log_average_miss_rate :31-67) for T <= 16 IoU thresholds min_overlap (a HOST array) in the same launches.
+ *   Detections, in input order (the reference's: files by sorted name, then lines): det_image / det_label (D) int,
+ *   det_score (D) fp64 without NaN, det_box (D, 4) fp64 = left, top, right, bottom.  order (D): rank -> input index, ranks
+ *   grouped by class ascending, inside a class by score descending with ties in input order (:416, a stable sort);
+ *   det_offsets (num_classes + 1): the ranks of class c are det_offsets[c] .. det_offsets[c + 1] - 1.
+ *   Ground truths, in input order: gt_box (G, 4) fp64, gt_difficult (G) bytes.  gt_perm (G): slot -> input index, slots
+ *   grouped by image * num_classes + class with the input order kept inside a group; gt_offsets (n_images * num_classes
+ *   + 1): the slots of a group.  Images and classes are indices in [0, n_images) and [0, num_classes).
+ *   Match (:462-477): over the ground truths of the detection's image and class in input order, difficult ones included,
+ *   iw = min(r) - max(l) + 1, ih likewise, and only if both > 0 ov = iw ih / (area_det + area_gt - iw ih), every extent
+ *   with the + 1; the first strict maximum from ovmax = -1.  Per threshold (:482-498): ovmax >= min_overlap[t] on a
+ *   difficult ground truth -> neither tp nor fp; on another one the lowest rank matched to it at t is the tp, every later
+ *   one an fp; below the threshold an fp.  Per (t, class) (:554-599): ctp / cfp inclusive cumulative sums by rank,
+ *   rec = ctp / max(n_gt, 1) (n_gt: non-difficult ground truths of the class), prec = ctp / max(ctp + cfp, 1); ap = voc_ap;
+ *   recall, precision and f1 = 2 rec prec / (rec + prec, 1 where 0) at the last rank whose score >= score_threhold (0 if
+ *   none); lamr = log_average_miss_rate(rec, cfp, n_img) (n_img: images with a non-difficult ground truth of the class) --
+ *   the reference passes RECALL there.  All five are 0 for a class without detections and NaN for a class without a
+ *   non-difficult ground truth, which the reference does not evaluate; map[t] = mean ap over the other classes in class
+ *   order, 0 if there is none (:380-382, 652-656).  IEEE fp64, one rounding per operation, the reference's operand order.
+ *   Outputs by rank: match (D) = input index of the matched ground truth or -1, ovmax (D), tp / fp (T, D) bytes, rec /
+ *   prec (T, D) (both NULL = not wanted); per class: n_gt, n_img (num_classes) int, n_tp, ap, f1, recall, precision, lamr
+ *   (T, num_classes); map (T).  D = 0 and G = 0 are valid.  Limits: D, G <= 2^24, num_classes <= 65535, n_images x
+ *   num_classes <= 2^27.  Integer atomics and fixed-order fp64 sums: the same bits on every run.
+ *   workspace: vrnet_det_map_workspace_bytes(D, G, T) bytes (first-claim ranks (T, G), cumulative counts 2 x (T, D)). */
+long vrnet_det_map_workspace_bytes(int D, int G, int T);
+int vrnet_det_map_f64(const int* det_image, const int* det_label, const double* det_score, const double* det_box,
+                      const int* order, const int* det_offsets, int D, const double* gt_box,
+                      const unsigned char* gt_difficult, const int* gt_perm, const int* gt_offsets, int G, int n_images,
+                      int num_classes, const double* min_overlap, int T, double score_threhold, int* match, double* ovmax,
+                      unsigned char* tp, unsigned char* fp, double* rec, double* prec, int* n_gt, int* n_img, int* n_tp,
+                      double* ap, double* f1, double* recall, double* precision, double* lamr, double* map,
+                      void* workspace, long workspace_bytes, void* stream);
+
 /* ---- input formats -----------------------------------------------------------------------------
  * What YoloDataset.__getitem__ / yolo_dataset_collate (utils/dataloader.py:88-107, 440-457) do to a letterboxed batch,
  * from BYTES: img (B, H, W, 3) u8 RGB -> images (B, 3, H, W) f32 = ((v / 255) - mean) / std evaluated in double and rounded
