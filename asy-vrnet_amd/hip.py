@@ -129,6 +129,7 @@ _SIGS = {
     "vrnet_batch_formats_u8": ([P, P, I, I, I, I, P, P, P, P], I),
     "vrnet_letterbox_workspace": ([I, I, I, I, I], L),
     "vrnet_letterbox_u8": ([P, P] + [I] * 9 + [P, P, P, P, L, P], I),
+    "vrnet_render_u8": ([P, P, I, I, I, P, I, I, F, P, P, I, P, I, I, P, P, P, P], I),
     "vrnet_yolo_loss_workspace": ([I, L, I, I], L),
     "vrnet_yolo_loss_f32": ([P, P, P, P, P, I, I, I, P, P, I, F, P, P, P, P, P, L, P], I),
     "vrnet_seg_loss_workspace": ([I, I, L], L),
@@ -860,6 +861,31 @@ def letterbox(img_u8, label_u8, H, W, nw, nh, dx, dy, canvas=None, images=None, 
         raise RuntimeError(f"letterbox: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
     _check(_lib.vrnet_letterbox_u8(ptr(img_u8), ptr(label_u8), B, ih, iw, int(H), int(W), int(nw), int(nh), int(dx), int(dy),
                                    ptr(canvas), ptr(images), ptr(label_out), ptr(ws), ws.numel(), stream()), "letterbox")
+
+
+def render(frames, class_map, out, palette=None, mix_type=0, alpha=0.7, boxes=None, box_offsets=None, box_palette=None,
+           thickness=1, counts=None, flag=None):
+    """The rendered frames (vrnet_render_u8): frames / out (B,ih,iw,3) uint8, class_map (B,ih,iw) uint8 or None, palette
+    (n,3) uint8, boxes (N,5) int32 with box_offsets (B+1) int32 and box_palette (m,3) uint8, counts (B,n) int64 (overwritten;
+    n = counts.shape[1] when there is no palette), flag (1) int32 (data-error bits, OR-ed in).  out may be frames when there
+    is no class map."""
+    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8 or not frames.is_contiguous():
+        raise RuntimeError("render: expected contiguous uint8 frames of shape (B, ih, iw, 3)")
+    B, ih, iw = frames.shape[:3]
+    n_colors = palette.shape[0] if palette is not None else (counts.shape[1] if counts is not None else 0)
+    n_rows = 0 if boxes is None else boxes.shape[0]
+    for t, sh, dt in ((out, (B, ih, iw, 3), torch.uint8), (class_map, (B, ih, iw), torch.uint8), (palette, (n_colors, 3), torch.uint8),
+                      (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32), (counts, (B, n_colors), torch.int64),
+                      (flag, (1,), torch.int32),
+                      (box_palette, (0 if box_palette is None else box_palette.shape[0], 3), torch.uint8)):
+        if t is not None and (tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous()):
+            raise RuntimeError(f"render: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+    if out is None or (n_rows and (box_offsets is None or box_palette is None)):
+        raise RuntimeError("render: out is required, and box rows need box_offsets and a box_palette")
+    _check(_lib.vrnet_render_u8(ptr(frames), ptr(class_map), B, ih, iw, ptr(palette), n_colors, int(mix_type), float(alpha),
+                                ptr(boxes) if n_rows else None, ptr(box_offsets), n_rows, ptr(box_palette),
+                                0 if box_palette is None else box_palette.shape[0], int(thickness), ptr(out), ptr(counts),
+                                ptr(flag), stream()), "render")
 
 
 def yolo_loss(levels, grads, strides, labels, counts, max_gt, grad_scale, out, fg=None, matched=None, piou=None):

@@ -9,10 +9,11 @@ The CUDA dispatch key is the HIP device on ROCm.  There is no CPU kernel: callin
     y = torch.ops.vrnet.conv2d_nhwc(x, w, bias, stride, pad, dil)           # NHWC implicit-GEMM conv (fp32-accurate x6 / MFMA)
     keep = torch.ops.vrnet.batched_nms(boxes, scores, idxs, iou_threshold)  # torchvision.ops.boxes.batched_nms
     images, labels = torch.ops.vrnet.letterbox(frames_u8, labels_u8, H, W, True)  # Pillow's letterbox from raw bytes
+    out, counts = torch.ops.vrnet.render(frames_u8, class_map, palette, 0, 0.7, rows, offsets, box_palette, 5)  # overlay + boxes
 """
 import torch
 
-from . import data, decode, hip
+from . import data, decode, hip, render as _render
 
 
 @torch.library.custom_op("vrnet::cluster", mutates_args=(), device_types="cuda")
@@ -468,6 +469,22 @@ def _(images_u8, labels_u8, input_h, input_w, letterbox_image):
     B = images_u8.shape[0]
     return (images_u8.new_empty((B, 3, input_h, input_w), dtype=torch.float32),
             labels_u8.new_empty((B, input_h, input_w), dtype=torch.uint8))
+
+
+@torch.library.custom_op("vrnet::render", mutates_args=(), device_types="cuda")
+def render(frames_u8: torch.Tensor, class_map: torch.Tensor, palette: torch.Tensor, mix_type: int, alpha: float,
+           boxes: torch.Tensor, box_offsets: torch.Tensor, box_palette: torch.Tensor, thickness: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """Frames (B,ih,iw,3) uint8 and their class map (B,ih,iw) uint8 -> the overlay of deeplab.py:169-222 (mix_type 0 / 1 / 2
+    with palette (n,3) uint8) with the box outlines of yolo.py:221-222 on top (boxes (N,5) int32 left, top, right, bottom,
+    colour; box_offsets (B+1) int32; box_palette (m,3) uint8; N may be 0), and the (B,n) int64 pixels of each class."""
+    return _render.render_frame(frames_u8, class_map, (boxes, box_offsets), None, palette, mix_type, alpha, True,
+                                box_palette, thickness, device=frames_u8.device)
+
+
+@render.register_fake
+def _(frames_u8, class_map, palette, mix_type, alpha, boxes, box_offsets, box_palette, thickness):
+    return (torch.empty_like(frames_u8, memory_format=torch.contiguous_format),
+            frames_u8.new_empty((frames_u8.shape[0], palette.shape[0]), dtype=torch.int64))
 
 
 # ---- ShuffleAttention (backbone/attention_modules/shuffle_attention.py:48-72) --------------------------------------------

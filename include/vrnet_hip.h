@@ -682,6 +682,43 @@ int vrnet_letterbox_u8(const unsigned char* img, const unsigned char* label, int
                        int nh, int dx, int dy, unsigned char* canvas, float* images, unsigned char* label_out,
                        void* workspace, long workspace_bytes, void* stream);
 
+/* ---- result rendering (csrc/render.hip) -------------------------------------------------------------------------
+ * Added within ABI 11: new symbols only, no existing signature or layout changed; hip.py binds every declared symbol at
+ * load time, so a library without them fails the import.
+ * vrnet_render_u8, deeplab.py:169-222 (detect_image: the three mix_types and the pixel counts of :172-185) and yolo.py:221-222
+ *   (the box outlines), in one launch: frames (B, ih, iw, 3) u8 RGB original frames -> out (B, ih, iw, 3) u8.  Every pointer
+ *   but frames and out may be NULL.  Every output byte is exact.
+ *   class_map (B, ih, iw) u8 (what vrnet_seg_predict_f32 writes) with palette (n_colors, 3) u8, 1 <= n_colors <= 256:
+ *     mix_type 1 (deeplab.py:209)  out = palette[class];
+ *     mix_type 2 (deeplab.py:216)  out = frame where class != 0, else 0 (a bool times float32, cast back); no palette needed;
+ *     mix_type 0 (deeplab.py:193-201)  Image.blend(frame, palette[class], alpha), Pillow's ImagingBlend per byte:
+ *       out = (uint8)((float)a + alpha * (float)((int)b - (int)a)), a the frame byte, b the palette byte, alpha a C float
+ *       in [0, 1] (0.7f, not 0.7), each operation rounded to fp32 (no fused multiply-add), truncated towards zero;
+ *       byte-identical to Pillow 12.2 on all 256 x 256 (a, b) pairs.
+ *     No class_map: out = frame.  A class id >= n_colors (the reference raises IndexError) takes the last colour, is not
+ *     counted, and sets bit 0 of *flag.
+ *   counts (B, n_colors) int64, if not NULL (needs class_map; n_colors > 0 even without a palette): OVERWRITTEN with the
+ *     pixels of each class per image (deeplab.py:172-185).  Integer atomics: the same result on every run.
+ *   boxes (n_rows, 5) int32 rows left, top, right, bottom, colour index; box_offsets (B + 1) int32: the rows of image b
+ *     are box_offsets[b] .. box_offsets[b + 1] - 1 (clamped into [0, n_rows]); box_palette (n_box_colors, 3) u8,
+ *     1 <= n_box_colors <= 256; thickness >= 1.  Painted after the mix (yolo.py:221-222): for i = 0 .. thickness - 1 the
+ *     ring [left+i, top+i, right-i, bottom-i] paints the perimeter pixels of that inclusive rectangle, clipped to the
+ *     image, while left+i <= right-i and top+i <= bottom-i; where several rows of an image paint a pixel the LAST row
+ *     wins (sequential drawing) -- decided per pixel, independent of scheduling.  Two differences from Pillow 12.2's
+ *     ImageDraw.rectangle(outline=): Pillow paints a ring of one row (y0 == y1) two rows high ([5,5,5,5] paints (5,5) and
+ *     (5,6)) and raises ValueError for x1 < x0; here a ring is its geometric perimeter and an empty ring paints nothing.
+ *     At most 1024 rows per image: later rows of an image are ignored and set bit 2 of *flag; a colour index outside
+ *     [0, n_box_colors) is clamped and sets bit 1.
+ *   flag: one int32, if not NULL: the bits above are OR-ed into it (never cleared here), so a caller can read it when it
+ *     next synchronises.
+ *   out may BE frames when class_map is NULL (boxes drawn in place: only painted pixels are written); any other overlap of
+ *   out with frames or class_map is rejected.  ih, iw <= 2^24, B ih iw < 2^31.  No workspace, no allocation, no host
+ *   synchronisation; the call (a memset of counts, one kernel) can be captured in a graph. */
+int vrnet_render_u8(const unsigned char* frames, const unsigned char* class_map, int B, int ih, int iw,
+                    const unsigned char* palette, int n_colors, int mix_type, float alpha, const int* boxes,
+                    const int* box_offsets, int n_rows, const unsigned char* box_palette, int n_box_colors, int thickness,
+                    unsigned char* out, long long* counts, int* flag, void* stream);
+
 /* ---- training losses on the path's outputs: value + gradient w.r.t. the head outputs ------------
  * vrnet_yolo_loss_f32: YOLOLoss (nets/yolo_training.py:60-427): decode (:99-111), SimOTA assignment per image
  *   (get_assignments :200-264, get_in_boxes_info :291-368, dynamic_k_matching :370-427), IoU / objectness / class

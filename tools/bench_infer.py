@@ -7,10 +7,15 @@ and, once per batch size, metrics.f_score of the seg logits against a random one
 expression of the same metric.  With --letterbox HxW[,HxW...] it times the input side: data.device_letterbox of a batch of
 raw uint8 frames of each original size H x W into the network input -- on frames already resident on the device, and
 including the host-to-device copy from pinned memory -- next to Pillow's data.resize_image of the same frames on one
-core (where Pillow is installed), with the bytes per image that cross PCIe either way.
+core (where Pillow is installed), with the bytes per image that cross PCIe either way.  With --render HxW[,HxW...] it times
+the output side after the forward: render.seg_render (mix_type 0, with the pixel counts) of the class map seg_predict makes
+at each original size H x W, and render.render_frame of the same map with 100 boxes per image, on frames resident on the
+device -- next to a plain device copy of the same frame bytes (out.copy_(frames): the bound of a byte-bound pass) and to the
+host path on one core (numpy palette lookup + Image.blend, where Pillow is installed), with the bytes per image that
+would otherwise cross PCIe.
 
     python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
-                                [--seg 1080x1920,480x640] [--letterbox 1080x1920,480x640]
+                                [--seg 1080x1920,480x640] [--letterbox 1080x1920,480x640] [--render 1080x1920,480x640]
 """
 import argparse
 import os
@@ -31,14 +36,17 @@ def main():
     ap.add_argument("--nms", default="", help="comma list of conf/iou threshold pairs (e.g. 0.05/0.5,0.001/0.5)")
     ap.add_argument("--seg", default="", help="comma list of original image sizes HxW (e.g. 1080x1920,480x640)")
     ap.add_argument("--letterbox", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
+    ap.add_argument("--render", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
     from asy_vrnet_amd.data import device_letterbox, resize_image
     from asy_vrnet_amd.decode import decode_outputs, non_max_suppression, seg_predict
     from asy_vrnet_amd.metrics import f_score, fast_hist
+    from asy_vrnet_amd.render import det_palette, render_frame, seg_palette, seg_render
     pairs = [tuple(float(v) for v in p.split("/")) for p in args.nms.split(",") if p]
     seg_sizes = [tuple(int(v) for v in p.split("x")) for p in args.seg.split(",") if p]
     frame_sizes = [tuple(int(v) for v in p.split("x")) for p in args.letterbox.split(",") if p]
+    render_sizes = [tuple(int(v) for v in p.split("x")) for p in args.render.split(",") if p]
 
     def timed(fn):
         for _ in range(3):
@@ -139,6 +147,49 @@ def main():
                     resize_image(im, (S[1], S[0]))
             pil_ms = (time.perf_counter() - t0) / (3 * bs) * 1e3
             print(line + f"; Pillow resize_image on one core {pil_ms:.3f} ms/image")
+
+        for ih, iw in render_sizes:
+            import numpy as np
+            g.replay()
+            gen = torch.Generator(device=dev).manual_seed(bs)
+            frames = torch.randint(0, 256, (bs, ih, iw, 3), generator=gen, device=dev, dtype=torch.uint8)
+            cmap = seg_predict(out[1], S, (ih, iw))
+            pal, bpal = torch.from_numpy(seg_palette(9)).to(dev), torch.from_numpy(det_palette(4)).to(dev)
+            rng = np.random.default_rng(bs)
+            left, top = rng.integers(0, iw - 8, (bs * 100)), rng.integers(0, ih - 8, (bs * 100))
+            rows = np.stack([left, top, np.minimum(left + rng.integers(8, iw // 3, bs * 100), iw),
+                             np.minimum(top + rng.integers(8, ih // 3, bs * 100), ih), rng.integers(0, 4, bs * 100)], axis=1)
+            boxes = (torch.from_numpy(rows.astype(np.int32)).to(dev), torch.arange(0, bs * 100 + 1, 100, dtype=torch.int32, device=dev))
+            thick = max((ih + iw) // args.size, 1)
+            dst = torch.empty_like(frames)
+            inplace = frames.clone()
+            # alternating rounds of the four device variants, so that a drift of the clock hits them alike
+            variants = {"copy": lambda: dst.copy_(frames),
+                        "seg_render": lambda: seg_render(frames, cmap, pal, 0, 0.7, count=True, out=dst),
+                        "render_frame": lambda: render_frame(frames, cmap, boxes, palette=pal, box_palette=bpal, thickness=thick,
+                                                             count=True, out=dst),
+                        "boxes_in_place": lambda: render_frame(inplace, None, boxes, box_palette=bpal, thickness=thick, out=inplace)}
+            ms = {k: min(timed(fn) for _ in range(3)) for k, fn in variants.items()}
+            mb = bs * ih * iw * 3 / 1e6
+            line = (f"  + render {ih}x{iw}, bs={bs}: device copy of the frames {ms['copy']:.4f} ms ({2 * mb / ms['copy']:.0f} GB/s read + "
+                    f"written); seg_render mix 0 + counts {ms['seg_render']:.4f} ms ({7 * mb / 3 / ms['seg_render']:.0f} GB/s "
+                    f"of its 7 B/pixel: {7 / 6 * ms['copy'] / ms['seg_render']:.2f} of the copy's rate); render_frame with 100 boxes/image, thickness {thick}, {ms['render_frame']:.4f} ms "
+                    f"({ms['render_frame'] / ms['seg_render']:.2f} x the no-box call); the boxes alone in place "
+                    f"{ms['boxes_in_place']:.4f} ms; {mb / bs:.2f} MB/image rendered on the device instead of "
+                    f"{ih * iw / 1e6:.2f} MB of class map down and back")
+            try:
+                from PIL import Image
+            except ImportError:
+                print(line + "; Pillow not installed")
+                continue
+            host_frames, host_map, host_pal = frames.cpu().numpy(), cmap.cpu().numpy(), seg_palette(9)
+            t0 = time.perf_counter()
+            for b in range(min(bs, 2)):
+                seg_img = np.reshape(host_pal[np.reshape(host_map[b], [-1])], [ih, iw, -1])
+                Image.blend(Image.fromarray(host_frames[b]), Image.fromarray(np.uint8(seg_img)), 0.7)
+                np.bincount(host_map[b].reshape(-1), minlength=9)
+            host_ms = (time.perf_counter() - t0) / min(bs, 2) * 1e3
+            print(line + f"; host path on one core (numpy palette lookup + Image.blend + bincount) {host_ms:.3f} ms/image")
 
 
 def f_score_eager(x, target, beta=1, smooth=1e-5, threshold=0.5):
