@@ -11,6 +11,11 @@
 //   scan    one workgroup per segment, `removed` bit mask in LDS; per 64-row block wave 0 resolves the block serially
 //           against its diagonal words (registers), then all waves OR the rows of the kept boxes into the later words;
 //           the kept boxes are written out in one parallel pass at the end
+// A captured graph needs a fixed candidate capacity: vrnet_nms_capped_f32 runs `order_capped` in place of `order` -- every
+// candidate of a segment is ranked, only ranks < cap are scattered, and mask / scan see min(count, cap) boxes.  Greedy NMS
+// decides a box from higher-ranked boxes only, so the result is the prefix of the uncapped result: its kept rows of rank
+// < cap.  `finish` (vrnet_detect_finish_f32) then restates the host tail of decode.non_max_suppression and render.box_rows
+// per kept row: the letterbox un-map in fp64, the integer draw rows with their prefix-sum offsets, the class counts.
 // IoU is the torchvision CPU kernel's expression in IEEE fp32 with no contraction (pragma below), compared in
 // double: bit-reproducible by a float32 numpy restatement (tests/test_nms.py).
 #include "common.h"
@@ -22,6 +27,8 @@
 namespace {
 
 constexpr int NMS_MAX_WORDS = 4096;          // LDS of the scan: 48 KiB, n_max <= 262 144 per segment
+constexpr int NMS_FLAG_CANDIDATES = 8;       // bits of the flag word, above render.hip's 1, 2, 4: more candidates than cap
+constexpr int NMS_FLAG_DET_CLASS = 16;       // a kept row whose class id lies outside [0, num_classes)
 
 // A 64-bit key whose unsigned order is (score descending, id ascending): the score's bits mapped to an order-preserving
 // unsigned integer (-0 folded onto +0 and every NaN onto one value, so equal scores give equal high words), then the id
@@ -122,6 +129,7 @@ struct SegArgs {
   int* keep;                   // (S, n_max): k of the kept boxes in score order
   int* kept;                   // (S)
   float* rows_out;             // (S, n_max, ld) or NULL
+  int* flag;                   // order_capped only
 };
 
 __device__ __forceinline__ int seg_count(const SegArgs& p, int s) { return p.counts ? min(p.counts[s], p.n_max) : p.n_max; }
@@ -143,6 +151,34 @@ __global__ __launch_bounds__(256) void order_kernel(const SegArgs p) {
     for (int t = 0; t < 256; ++t) rank += tile[t] > ki;
   }
   if (i >= n) return;
+  const float* r = p.rows + (off + i) * p.ld;
+  const long d = (long)s * p.n_max + rank;
+  p.sbox[d] = make_float4(r[0], r[1], r[2], r[3]);
+  p.scls[d] = p.cls[off + i];
+  p.spos[d] = i;
+}
+
+// `order` for a fixed capacity n_max = cap: ALL min(counts[s], stride) candidates are ranked, ranks >= cap are dropped (which
+// candidates survive does not depend on the arbitrary list order of `select`), and the flag word tells when any were
+__global__ __launch_bounds__(256) void order_capped_kernel(const SegArgs p) {
+  __shared__ unsigned long long tile[256];
+  const int s = blockIdx.y, count = p.counts[s];
+  const int n = (int)min((long)max(count, 0), p.stride);
+  if ((int)blockIdx.x * 256 >= n) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && count > p.n_max) atomicOr(p.flag, NMS_FLAG_CANDIDATES);
+  const long off = (long)s * p.stride;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long ki = i < n ? nms_key(p.scores[off + i], p.ids ? p.ids[off + i] : i) : 0;
+  int rank = 0;
+  for (int j0 = 0; j0 < n; j0 += 256) {
+    const int j = j0 + threadIdx.x;
+    __syncthreads();
+    tile[threadIdx.x] = j < n ? nms_key(p.scores[off + j], p.ids ? p.ids[off + j] : j) : 0;
+    __syncthreads();
+#pragma unroll 16
+    for (int t = 0; t < 256; ++t) rank += tile[t] > ki;
+  }
+  if (i >= n || rank >= p.n_max) return;
   const float* r = p.rows + (off + i) * p.ld;
   const long d = (long)s * p.n_max + rank;
   p.sbox[d] = make_float4(r[0], r[1], r[2], r[3]);
@@ -240,6 +276,73 @@ __global__ __launch_bounds__(256) void scan_kernel(const SegArgs p) {
   if (threadIdx.x == 0) p.kept[s] = base;
 }
 
+struct FinishArgs {
+  const float* rows;           // (B, cap, 7) kept rows: x1, y1, x2, y2 of the network input, obj, class_conf, class
+  const int* kept;             // (B)
+  int B, cap, nc, ih, iw;
+  double off_y, off_x, sc_y, sc_x, img_h, img_w;
+  float* out;                  // (B, cap, 7): top, left, bottom, right in pixels of the original image, obj, class_conf, class
+  int* draw;                   // (B * cap, 5) zeroed by the caller: left, top, right, bottom, class, the images back to back
+  int* offsets;                // (B + 1)
+  unsigned long long* counts;  // (B, nc) zeroed by the caller
+  int* flag;
+};
+
+// np.clip(np.floor(float64(v)), -2^31, 2^31 - 1).astype(int64) of render.box_rows
+__device__ __forceinline__ int floor_clip(float v) {
+  double f = floor((double)v);
+  f = f < -2147483648.0 ? -2147483648.0 : (f > 2147483647.0 ? 2147483647.0 : f);
+  return (int)f;
+}
+
+// One thread per (image, row slot).  The fp32 centre / size of decode.non_max_suppression, then decode.yolo_correct_boxes
+// in fp64 operation by operation (no contraction: the pragma above), one rounding to fp32 as the assignment into the
+// float32 array does; without a letterbox the caller passes offset 0 and scale 1, which change no bit.
+__global__ __launch_bounds__(256) void detect_finish_kernel(const FinishArgs p) {
+  __shared__ int part[256];
+  const int b = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+  int before = 0;                                     // kept rows of the images in front of this one
+  for (int j = threadIdx.x; j < b; j += 256) before += min(max(p.kept[j], 0), p.cap);
+  part[threadIdx.x] = before;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  const int base = part[0], n = min(max(p.kept[b], 0), p.cap);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (b == 0) p.offsets[0] = 0;
+    p.offsets[b + 1] = base + n;
+  }
+  if (k >= p.cap) return;
+  const float* r = p.rows + ((long)b * p.cap + k) * 7;
+  float* o = p.out + ((long)b * p.cap + k) * 7;
+  if (k >= n) {
+    for (int c = 0; c < 7; ++c) o[c] = 0.0f;
+    return;
+  }
+  const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
+  const float cx = (x1 + x2) / 2.0f, cy = (y1 + y2) / 2.0f, w = x2 - x1, h = y2 - y1;
+  double c_y = (double)cy, c_x = (double)cx, s_y = (double)h, s_x = (double)w;
+  c_y = (c_y - p.off_y) * p.sc_y;
+  c_x = (c_x - p.off_x) * p.sc_x;
+  s_y = s_y * p.sc_y;
+  s_x = s_x * p.sc_x;
+  const double hy = 0.5 * s_y, hx = 0.5 * s_x;
+  const float top = (float)((c_y - hy) * p.img_h), left = (float)((c_x - hx) * p.img_w);
+  const float bottom = (float)((c_y + hy) * p.img_h), right = (float)((c_x + hx) * p.img_w);
+  o[0] = top; o[1] = left; o[2] = bottom; o[3] = right; o[4] = r[4]; o[5] = r[5]; o[6] = r[6];
+  const int label = (int)r[6];
+  int* d = p.draw + 5L * (base + k);
+  d[0] = max(0, floor_clip(left));
+  d[1] = max(0, floor_clip(top));
+  d[2] = min(p.iw, floor_clip(right));
+  d[3] = min(p.ih, floor_clip(bottom));
+  d[4] = label;
+  if (label >= 0 && label < p.nc) atomicAdd(p.counts + (long)b * p.nc + label, 1ull);
+  else atomicOr(p.flag, NMS_FLAG_DET_CLASS);
+}
+
 long seg_mask_words(long n_max) { return n_max * vr_cdiv(n_max, 64); }
 
 }  // namespace
@@ -265,14 +368,14 @@ extern "C" long vrnet_nms_workspace_bytes(int segments, int n_max) {
   return segments * per + 256;
 }
 
-extern "C" int vrnet_nms_segmented_f32(const float* rows, int ld, const float* scores, const long long* classes,
-                                       const int* ids, const int* counts, int segments, long stride, int n_max,
-                                       double iou_thres, void* workspace, long workspace_bytes, int* keep, int* kept,
-                                       float* rows_out, void* stream) {
+// the three launches of both NMS entry points; `flag` non-NULL selects the capped order
+static int nms_run(const char* fn, const float* rows, int ld, const float* scores, const long long* classes, const int* ids,
+                   const int* counts, int segments, long stride, int n_max, double iou_thres, void* workspace,
+                   long workspace_bytes, int* keep, int* kept, float* rows_out, int* flag, void* stream) {
   VR_CHECK_ARG(rows && scores && classes && keep && kept && segments > 0 && segments < 65536 && n_max > 0 && ld >= 4 &&
-                   stride >= n_max, "nms_segmented: bad arguments");
-  VR_CHECK_ARG(vr_cdiv(n_max, 64) <= NMS_MAX_WORDS, "nms_segmented: n_max %d above %d", n_max, NMS_MAX_WORDS * 64);
-  VR_CHECK_ARG(workspace && workspace_bytes >= vrnet_nms_workspace_bytes(segments, n_max), "nms_segmented: workspace %ld < %ld",
+                   stride >= n_max, "%s: bad arguments", fn);
+  VR_CHECK_ARG(vr_cdiv(n_max, 64) <= NMS_MAX_WORDS, "%s: n_max %d above %d", fn, n_max, NMS_MAX_WORDS * 64);
+  VR_CHECK_ARG(workspace && workspace_bytes >= vrnet_nms_workspace_bytes(segments, n_max), "%s: workspace %ld < %ld", fn,
                workspace_bytes, vrnet_nms_workspace_bytes(segments, n_max));
   const long SN = (long)segments * n_max;
   SegArgs p{};
@@ -283,13 +386,56 @@ extern "C" int vrnet_nms_segmented_f32(const float* rows, int ld, const float* s
   p.mask = reinterpret_cast<unsigned long long*>(w);   w += segments * seg_mask_words(n_max) * 8;
   p.scls = reinterpret_cast<long long*>(w);            w += SN * sizeof(long long);
   p.spos = reinterpret_cast<int*>(w);
-  p.keep = keep; p.kept = kept; p.rows_out = rows_out;
+  p.keep = keep; p.kept = kept; p.rows_out = rows_out; p.flag = flag;
   const hipStream_t st = vr_stream(stream);
-  hipLaunchKernelGGL(order_kernel, dim3(vr_cdiv(n_max, 256), segments), dim3(256), 0, st, p);
+  if (flag)
+    hipLaunchKernelGGL(order_capped_kernel, dim3(vr_cdiv(stride, 256), segments), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL(order_kernel, dim3(vr_cdiv(n_max, 256), segments), dim3(256), 0, st, p);
   VR_LAUNCH_CHECK("nms order");
   hipLaunchKernelGGL(mask_kernel, dim3(p.nb, p.nb, segments), dim3(64), 0, st, p);
   VR_LAUNCH_CHECK("nms mask");
   hipLaunchKernelGGL(scan_kernel, dim3(segments), dim3(256), p.nb * (sizeof(unsigned long long) + sizeof(int)), st, p);
   VR_LAUNCH_CHECK("nms scan");
+  return VR_OK;
+}
+
+extern "C" int vrnet_nms_segmented_f32(const float* rows, int ld, const float* scores, const long long* classes,
+                                       const int* ids, const int* counts, int segments, long stride, int n_max,
+                                       double iou_thres, void* workspace, long workspace_bytes, int* keep, int* kept,
+                                       float* rows_out, void* stream) {
+  return nms_run("nms_segmented", rows, ld, scores, classes, ids, counts, segments, stride, n_max, iou_thres, workspace,
+                 workspace_bytes, keep, kept, rows_out, nullptr, stream);
+}
+
+extern "C" int vrnet_nms_capped_f32(const float* rows, int ld, const float* scores, const long long* classes, const int* ids,
+                                    const int* counts, int segments, long stride, int cap, double iou_thres, void* workspace,
+                                    long workspace_bytes, int* keep, int* kept, float* rows_out, int* flag, void* stream) {
+  VR_CHECK_ARG(counts && flag && stride > 0 && stride < (1L << 31), "nms_capped: needs device counts, a flag word and stride < 2^31");
+  return nms_run("nms_capped", rows, ld, scores, classes, ids, counts, segments, stride, cap, iou_thres, workspace,
+                 workspace_bytes, keep, kept, rows_out, flag, stream);
+}
+
+extern "C" int vrnet_detect_finish_f32(const float* rows, const int* kept, int B, int cap, int num_classes, int image_h,
+                                       int image_w, double offset_y, double offset_x, double scale_y, double scale_x,
+                                       float* rows_out, int* draw_rows, int* offsets, long long* det_counts, int* flag,
+                                       void* stream) {
+  VR_CHECK_ARG(rows && kept && rows_out && draw_rows && offsets && det_counts && flag && rows != rows_out,
+               "detect_finish: every array is required, rows_out apart from rows");
+  VR_CHECK_ARG(B > 0 && B < 65536 && cap > 0 && (long)B * cap < (1L << 27) && num_classes >= 1 && image_h > 0 && image_w > 0,
+               "detect_finish: bad shape (B %d, cap %d, %d classes, image %d x %d)", B, cap, num_classes, image_h, image_w);
+  const hipStream_t st = vr_stream(stream);
+  if (hipMemsetAsync(draw_rows, 0, sizeof(int) * 5 * (size_t)B * cap, st) != hipSuccess ||
+      hipMemsetAsync(det_counts, 0, sizeof(long long) * (size_t)B * num_classes, st) != hipSuccess) {
+    vr_set_error("detect_finish: memset failed");
+    return VR_ERR_LAUNCH;
+  }
+  FinishArgs p{};
+  p.rows = rows; p.kept = kept; p.B = B; p.cap = cap; p.nc = num_classes; p.ih = image_h; p.iw = image_w;
+  p.off_y = offset_y; p.off_x = offset_x; p.sc_y = scale_y; p.sc_x = scale_x; p.img_h = (double)image_h; p.img_w = (double)image_w;
+  p.out = rows_out; p.draw = draw_rows; p.offsets = offsets; p.counts = reinterpret_cast<unsigned long long*>(det_counts);
+  p.flag = flag;
+  hipLaunchKernelGGL(detect_finish_kernel, dim3(vr_cdiv(cap, 256), B), dim3(256), 0, st, p);
+  VR_LAUNCH_CHECK("detect_finish");
   return VR_OK;
 }

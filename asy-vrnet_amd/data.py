@@ -182,6 +182,28 @@ def device_letterbox(images_u8, input_shape, labels_u8=None, letterbox_image=Tru
     return (images if normalise else canvas), labels
 
 
+def device_radar(radar, normalise=True, device="cuda", out=None):
+    """The radar half of the prediction scripts ON THE DEVICE (vrnet_radar_normalise): radar (B, 4, H, W) float32 or
+    float64 maps (a single (4, H, W) frame counts as B = 1), numpy array or tensor -> (B, 4, H, W) float32 on the device.
+    normalise=True: each frame through `preprocess_input_radar` (its global min and max over all four channels, as
+    yolo.py:134 calls it per frame), bit-identical to `preprocess_input_radar(frame).astype(float32)` -- the arithmetic
+    runs in the maps' own type, as numpy's does; a constant frame is NaN in both.  normalise=False: the plain cast
+    (deeplab.py and the dataloader feed the maps raw).  Two launches, no host synchronisation."""
+    from . import hip
+    t = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
+    if t.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"device_radar: expected float32 or float64 maps, got {t.dtype}")
+    t = t[None] if t.dim() == 3 else t
+    if t.dim() != 4 or t.numel() == 0:
+        raise RuntimeError(f"device_radar: expected maps of shape (B, 4, H, W) or (4, H, W), got {tuple(t.shape)}")
+    t = t.to(device, non_blocking=True).contiguous()
+    with torch.cuda.device(t.device):
+        if out is None:
+            out = torch.empty(t.shape, dtype=torch.float32, device=t.device)
+        hip.radar_normalise(t, out, normalise)
+    return out
+
+
 def make_sample(image, box, radar, png, num_classes_seg):
     """YoloDataset.__getitem__ after augmentation (dataloader.py:88-107): (image CHW float64, boxes cxcywh, radar,
     png, one-hot)."""

@@ -126,7 +126,11 @@ _SIGS = {
     "vrnet_detect_select_f32": ([P, I, I, I, I, F, P, P, P, P, P, P], I),
     "vrnet_nms_workspace_bytes": ([I, I], L),
     "vrnet_nms_segmented_f32": ([P, I, P, P, P, P, I, L, I, D, P, L, P, P, P, P], I),
+    "vrnet_nms_capped_f32": ([P, I, P, P, P, P, I, L, I, D, P, L, P, P, P, P, P], I),
+    "vrnet_detect_finish_f32": ([P, P, I, I, I, I, I, D, D, D, D, P, P, P, P, P, P], I),
     "vrnet_batch_formats_u8": ([P, P, I, I, I, I, P, P, P, P], I),
+    "vrnet_radar_workspace_bytes": ([I], L),
+    "vrnet_radar_normalise": ([P, I, I, L, I, P, P, L, P], I),
     "vrnet_letterbox_workspace": ([I, I, I, I, I], L),
     "vrnet_letterbox_u8": ([P, P] + [I] * 9 + [P, P, P, P, L, P], I),
     "vrnet_render_u8": ([P, P, I, I, I, P, I, I, F, P, P, I, P, I, I, P, P, P, P], I),
@@ -815,6 +819,44 @@ def nms_segmented(rows, scores, classes, ids, counts, segments, stride, n_max, i
     _check(_lib.vrnet_nms_segmented_f32(ptr(rows), rows.shape[-1], ptr(scores), ptr(classes), ptr(ids), ptr(counts),
                                         segments, stride, n_max, float(iou_thres), ptr(workspace), workspace.numel(),
                                         ptr(keep), ptr(kept), ptr(rows_out), stream()), "nms_segmented")
+
+
+def nms_capped(rows, scores, classes, ids, counts, segments, stride, cap, iou_thres, workspace, keep, kept, rows_out, flag):
+    """nms_segmented with a fixed capacity (vrnet_nms_capped_f32): every candidate is ranked, ranks < cap enter the NMS;
+    counts (segments) int32 is required, flag (1) int32 receives bit 8 when a segment has more candidates than cap."""
+    _check(_lib.vrnet_nms_capped_f32(ptr(rows), rows.shape[-1], ptr(scores), ptr(classes), ptr(ids), ptr(counts), segments,
+                                     stride, cap, float(iou_thres), ptr(workspace), workspace.numel(), ptr(keep), ptr(kept),
+                                     ptr(rows_out), ptr(flag), stream()), "nms_capped")
+
+
+def detect_finish(rows, kept, num_classes, image_shape, offset, scale, rows_out, draw_rows, offsets, det_counts, flag):
+    """The kept rows (B, cap, 7) of nms_capped -> rows in pixels of the original image, the renderer's box rows with
+    their offsets and the class counts (vrnet_detect_finish_f32).  offset / scale: the (y, x) float64 pairs of
+    yolo_correct_boxes; image_shape = (ih, iw)."""
+    B, cap = rows.shape[:2]
+    for t, sh, dt in ((rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32), (rows_out, (B, cap, 7), torch.float32),
+                      (draw_rows, (B * cap, 5), torch.int32), (offsets, (B + 1,), torch.int32),
+                      (det_counts, (B, num_classes), torch.int64), (flag, (1,), torch.int32)):
+        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"detect_finish: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+    _check(_lib.vrnet_detect_finish_f32(ptr(rows), ptr(kept), B, cap, int(num_classes), int(image_shape[0]), int(image_shape[1]),
+                                        float(offset[0]), float(offset[1]), float(scale[0]), float(scale[1]), ptr(rows_out),
+                                        ptr(draw_rows), ptr(offsets), ptr(det_counts), ptr(flag), stream()), "detect_finish")
+
+
+def radar_normalise(radar, out, normalise=True, ws=None):
+    """radar (B, ...) float32 / float64 -> out, the same shape in float32: each frame min-max normalised as
+    preprocess_input_radar does it, or (normalise=False) cast (vrnet_radar_normalise)."""
+    if radar.dtype not in (torch.float32, torch.float64) or not radar.is_contiguous() or radar.dim() < 2 or radar.numel() == 0:
+        raise RuntimeError(f"radar_normalise: expected contiguous float32 / float64 maps (B, ...), got {radar.dtype} {tuple(radar.shape)}")
+    if out.dtype != torch.float32 or out.shape != radar.shape or not out.is_contiguous():
+        raise RuntimeError(f"radar_normalise: out must be a contiguous float32 tensor of shape {tuple(radar.shape)}")
+    B = radar.shape[0]
+    if normalise and ws is None:
+        ws = torch.empty(_lib.vrnet_radar_workspace_bytes(B) // 8, dtype=torch.float64, device=radar.device)
+    _check(_lib.vrnet_radar_normalise(ptr(radar), int(radar.dtype == torch.float64), B, radar.numel() // B, int(bool(normalise)),
+                                      ptr(out), ptr(ws), 0 if ws is None else ws.numel() * ws.element_size(), stream()),
+           "radar_normalise")
 
 
 def batch_formats(img_u8, png_u8, num_classes_seg, images=None, png_out=None, onehot=None):

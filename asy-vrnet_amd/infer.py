@@ -1,0 +1,239 @@
+"""Frame-to-result inference as ONE replayed hipGraph: the joint detection + segmentation of a camera-plus-radar stream
+that the reference runs frame by frame (predict.py modes `video` and `fps`; `detect_image` / `get_FPS` of yolo.py and
+deeplab.py), from raw frame bytes and radar maps to detections, class map, counts and the rendered frame, all on the
+device and without a host synchronisation until the caller reads a result.
+
+The chain inside `FramePipeline` is data.device_letterbox -> (data.device_radar) -> the eval-mode forward ->
+decode.decode_outputs -> hip.detect_select -> hip.nms_capped -> hip.detect_finish -> decode.seg_predict ->
+render.render_frame on the device (draw_rows, offsets) pair.  `decode.non_max_suppression` sizes its buffers from a
+read-back of the candidate counts and maps the kept rows on the host; here the candidate capacity is fixed
+(`max_candidates`), every candidate is ranked and the best `cap` enter the NMS (the exact prefix of the uncapped result),
+and the letterbox un-map, the renderer's integer rows and the class counts are made by one kernel from the kept rows.
+
+Bits of `FrameResult.flag` (an int32 word, zeroed by every run; read it when you read a result): render.FLAG_CLASS,
+FLAG_BOX_COLOUR, FLAG_BOX_ROWS (see render.render_frame), FLAG_CANDIDATES -- an image had more candidates than the
+capacity, so only its `cap` best-scored ones were considered -- and FLAG_DET_CLASS -- a kept row with a class id
+outside [0, num_classes), which is not counted."""
+import numpy as np
+import torch
+
+from . import data
+from . import render as rendering
+
+FLAG_CANDIDATES, FLAG_DET_CLASS = 8, 16          # NMS_FLAG_* of csrc/nms.hip, above render.FLAG_*
+
+
+def validate_config(model, frame_shape, input_shape, batch, max_candidates):
+    """The constructor's checks that need no device; returns ((ih, iw), (H, W), batch, max_candidates) as ints."""
+    if getattr(model, "training", True):
+        raise RuntimeError("FramePipeline: the model must be in eval mode (model.eval()): a training-mode forward updates the "
+                           "BatchNorm statistics with every frame")
+    try:
+        (ih, iw), (H, W) = (int(v) for v in frame_shape), (int(v) for v in input_shape)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"FramePipeline: frame_shape and input_shape are (height, width) pairs, got {frame_shape!r} and "
+                           f"{input_shape!r}") from None
+    if min(ih, iw, H, W) <= 0 or int(batch) < 1:
+        raise RuntimeError(f"FramePipeline: bad shapes (batch {batch}, frames {ih} x {iw}, input {H} x {W})")
+    if isinstance(max_candidates, bool) or int(max_candidates) != max_candidates or \
+            not 1 <= int(max_candidates) <= rendering.MAX_BOXES:
+        raise RuntimeError(f"FramePipeline: max_candidates must be an integer in 1..{rendering.MAX_BOXES} (the renderer's box rows "
+                           f"per image), got {max_candidates!r}")
+    return (ih, iw), (H, W), int(batch), int(max_candidates)
+
+
+def validate_inputs(frames_u8, radar, batch, frame_shape, input_shape):
+    """frames (B, ih, iw, 3) uint8 and radar (B, 4, H, W) float32 / float64, numpy arrays or tensors, of exactly the
+    shapes the pipeline was built for (with batch 1 the leading axis may be missing); returns them as tensors."""
+    f = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
+    r = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
+    if f.dtype != torch.uint8:
+        raise RuntimeError(f"FramePipeline: expected uint8 frames, got {f.dtype}")
+    if r.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"FramePipeline: expected float32 or float64 radar maps, got {r.dtype}")
+    f = f[None] if batch == 1 and f.dim() == 3 else f
+    r = r[None] if batch == 1 and r.dim() == 3 else r
+    want_f, want_r = (batch,) + tuple(frame_shape) + (3,), (batch, 4) + tuple(input_shape)
+    if tuple(f.shape) != want_f:
+        raise RuntimeError(f"FramePipeline: built for frames of shape {want_f}, got {tuple(f.shape)} (a pipeline is tied to its "
+                           "shapes: build another one for another frame size or batch)")
+    if tuple(r.shape) != want_r:
+        raise RuntimeError(f"FramePipeline: built for radar maps of shape {want_r}, got {tuple(r.shape)}")
+    return f, r
+
+
+def unmap_scalars(input_shape, image_shape, letterbox_image):
+    """(offset, scale): the (y, x) float64 pairs with which decode.yolo_correct_boxes maps a centre, (c - offset) * scale, and a
+    size, s * scale -- its own expressions, np.round included; (0, 0), (1, 1) without a letterbox."""
+    if not letterbox_image:
+        return (0.0, 0.0), (1.0, 1.0)
+    net_hw = np.asarray(input_shape, dtype=np.float64)
+    img_hw = np.asarray(image_shape, dtype=np.float64)
+    inner = np.round(img_hw * (net_hw / img_hw).min())
+    return tuple(0.5 * (net_hw - inner) / net_hw), tuple(net_hw / inner)
+
+
+class FrameResult:
+    """What one `FramePipeline.run` leaves on the device.  The tensors are the pipeline's own buffers: the next `run`
+    overwrites them, so read (or clone) what you need first.
+    rows (B, cap, 7) float32: top, left, bottom, right in pixels of the original frame, obj, class_conf, class, in descending
+    score order, zero from row kept[b] on; kept (B) int32; det_counts (B, num_classes) int64; class_map (B, ih, iw) uint8;
+    seg_counts (B, len(seg palette)) int64 pixels per class and rendered (B, ih, iw, 3) uint8, both None with render=False;
+    flag (1) int32, the data-error bits of the module docstring."""
+    __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag")
+
+    def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag):
+        self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
+        self.seg_counts, self.rendered, self.flag = seg_counts, rendered, flag
+
+    def detections(self):
+        """The list `decode.non_max_suppression` returns: per image an (N_b, 7) float32 numpy array in the same order,
+        (0, 7) for an image without detections.  One device-to-host copy (rows and counts packed into one tensor), which
+        waits for the frame."""
+        B = self.kept.shape[0]
+        packed = torch.cat([self.rows.reshape(-1), self.kept.view(torch.float32)]).cpu().numpy()
+        kept = packed[-B:].view(np.int32)
+        rows = packed[:-B].reshape(B, -1, 7)
+        return [rows[b, :kept[b]].copy() for b in range(B)]
+
+
+class FramePipeline:
+    """One object from raw frames to results: run(frames_u8, radar) -> FrameResult.
+
+    model: an EfficientVRNet in eval mode on a HIP device.  frame_shape = (ih, iw) of the raw frames, input_shape = (H, W)
+    of the network, batch = frames per call; all frames of a call share one size.  conf_thres / nms_thres /
+    letterbox_image: as `decode.non_max_suppression` (with letterbox_image=False the frame is stretched to the input and
+    the class map is the resize of the whole seg output).  max_candidates (1..render.MAX_BOXES): the fixed capacity of the
+    captured NMS; the effective capacity is min(max_candidates, anchors).  An image with more candidates keeps its best-
+    scored `cap` (score descending, anchor ascending) -- the result is then the prefix of `non_max_suppression`'s, and
+    FLAG_CANDIDATES is set.  normalise_radar: False (the default) feeds the radar maps RAW, as deeplab.py and the training
+    dataloader do; True min-max normalises every frame's maps on the device (`data.device_radar`), as yolo.py:134 does on
+    the host.  radar_dtype: the type of the static radar buffer; float64 maps are normalised in float64, as the reference
+    normalises a float64 .npz, only in a float64 buffer.  render / mix_type / alpha / seg_palette / box_palette: the
+    `render.render_frame` picture (seg overlay, box outlines of thickness yolo.py:164) and the per-class pixel counts;
+    default palettes `render.seg_palette(num_seg_classes)` and `render.det_palette(num_classes)`.
+
+    graph=True warms the chain up (twice, on a side stream: workspaces and caches exist before the capture; the model's
+    buffers are restored afterwards) and captures it as one hipGraph; run() then copies the inputs into the static
+    buffers `frames_u8` (B, ih, iw, 3) / `radar` (B, 4, H, W) and replays.  graph=False runs the same calls eagerly, after one
+    warm-up pass in the constructor (so `cap` and the buffers exist, and no run builds a cache).  Neither run synchronises
+    with the host."""
+
+    def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
+                 max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
+                 box_palette=None, graph=True, radar_dtype=torch.float32):
+        self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
+            model, frame_shape, input_shape, batch, max_candidates)
+        if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
+            raise RuntimeError(f"FramePipeline: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
+        if radar_dtype not in (torch.float32, torch.float64) or (radar_dtype == torch.float64 and not normalise_radar):
+            raise RuntimeError("FramePipeline: radar_dtype is float32, or float64 together with normalise_radar")
+        self.model = model
+        self.conf_thres, self.nms_thres, self.letterbox_image = float(conf_thres), float(nms_thres), bool(letterbox_image)
+        self.normalise_radar, self.render, self.mix_type, self.alpha = bool(normalise_radar), bool(render), mix_type, float(alpha)
+        p = next(model.parameters(), None)
+        if p is None or not p.is_cuda:
+            raise RuntimeError("FramePipeline: the model must be on a HIP device (there is no CPU fallback)")
+        self.device = dev = p.device
+        (ih, iw), (H, W), B = self.frame_shape, self.input_shape, self.batch
+        self.num_classes = int(model.num_classes)
+        self.thickness = int(max((iw + ih) // np.mean(self.input_shape), 1))                    # yolo.py:164
+        self.offset, self.scale = unmap_scalars(self.input_shape, self.frame_shape, self.letterbox_image)
+        pal = rendering.seg_palette(int(model.num_seg_classes)) if seg_palette is None else seg_palette
+        bpal = rendering.det_palette(self.num_classes) if box_palette is None else box_palette
+        self.seg_palette, self.box_palette = (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+                                              for t in (pal, bpal))
+        self.seg_palette, self.box_palette = self.seg_palette.to(dev), self.box_palette.to(dev)
+        self.frames_u8 = torch.zeros((B, ih, iw, 3), dtype=torch.uint8, device=dev)
+        self.radar = torch.zeros((B, 4, H, W), dtype=radar_dtype, device=dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.cap = None                       # the NMS buffers follow the anchor count of the first (warm-up) pass
+        self.graph = self.result = None
+        if graph:
+            self._capture()
+        else:
+            self._warm_up(1)
+
+    def _allocate(self, anchors):
+        from . import hip
+        B, dev = self.batch, self.device
+        self.cap = cap = min(self.max_candidates, anchors)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self._cand = (torch.empty((B, anchors, 7), device=dev), torch.empty((B, anchors), device=dev),
+                      torch.empty((B, anchors), dtype=torch.int64, device=dev), torch.empty((B, anchors), **i32),
+                      torch.empty(B, **i32))                                    # rows, scores, classes, ids, counts
+        self._nms_ws = torch.empty(hip.nms_workspace_bytes(B, cap), dtype=torch.uint8, device=dev)
+        self._keep, self._kept = torch.empty((B, cap), **i32), torch.empty(B, **i32)
+        self._kept_rows, self._rows = torch.empty((B, cap, 7), device=dev), torch.empty((B, cap, 7), device=dev)
+        self._draw_rows, self._offsets = torch.empty((B * cap, 5), **i32), torch.empty(B + 1, **i32)
+        self._det_counts = torch.empty((B, self.num_classes), dtype=torch.int64, device=dev)
+
+    def _chain(self):
+        from . import decode, hip            # the library loads with the first pass, not with the package
+        S, F = self.input_shape, self.frame_shape
+        images, _ = data.device_letterbox(self.frames_u8, S, letterbox_image=self.letterbox_image, device=self.device)
+        radar = data.device_radar(self.radar, True, self.device) if self.normalise_radar else self.radar
+        det, seg = self.model(images, radar)
+        pred = decode.decode_outputs(det, S)
+        if self.cap is None:
+            self._allocate(pred.shape[1])
+        rows, scores, classes, ids, counts = self._cand
+        self.flag.zero_()
+        hip.detect_select(pred, self.num_classes, self.conf_thres, rows, scores, classes, ids, counts)
+        hip.nms_capped(rows, scores, classes, ids, counts, self.batch, pred.shape[1], self.cap, self.nms_thres, self._nms_ws,
+                       self._keep, self._kept, self._kept_rows, self.flag)
+        hip.detect_finish(self._kept_rows, self._kept, self.num_classes, F, self.offset, self.scale, self._rows,
+                          self._draw_rows, self._offsets, self._det_counts, self.flag)
+        if self.letterbox_image:
+            class_map = decode.seg_predict(seg, S, F)
+        else:                                 # the frame was stretched over the whole input: the window is the input
+            class_map = torch.empty((self.batch,) + F, dtype=torch.uint8, device=self.device)
+            ws = torch.empty(hip.seg_predict_workspace_bytes(self.batch, seg.shape[1], S[0], S[1]), dtype=torch.uint8,
+                             device=self.device)
+            hip.seg_predict(seg.contiguous().float(), 0, 0, S[0], S[1], class_map, ws)
+        rendered = seg_counts = None
+        if self.render:
+            rendered, seg_counts = rendering.render_frame(
+                self.frames_u8, class_map, (self._draw_rows, self._offsets), palette=self.seg_palette, mix_type=self.mix_type,
+                alpha=self.alpha, count=True, box_palette=self.box_palette, thickness=self.thickness, flag=self.flag,
+                device=self.device)
+        return FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
+
+    def _warm_up(self, passes, stream=None):
+        """Runs the chain on the zeroed static buffers, on `stream` or the current one: the first pass sizes the NMS buffers
+        from the anchor count (`cap`) and builds the caches with their host-to-device copies, so that no later run does."""
+        dev = self.device
+        saved = [(b, b.detach().clone()) for b in self.model.buffers() if b.numel()]
+        cur = torch.cuda.current_stream(dev)
+        stream = cur if stream is None else stream
+        stream.wait_stream(cur)
+        with torch.no_grad(), torch.cuda.stream(stream):
+            for _ in range(passes):
+                self._chain()
+        cur.wait_stream(stream)
+        torch.cuda.synchronize(dev)
+        with torch.no_grad():
+            for b, old in saved:                    # the warm-up's zero-input passes must leave the model as it was
+                b.copy_(old)
+
+    def _capture(self):
+        self.stream = torch.cuda.Stream(self.device)    # warm-up AND capture run here: the scratch arenas of hip.Workspace are
+        self._warm_up(2, self.stream)                   # keyed by stream, so they exist before the capture, in no graph pool
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
+            self.result = self._chain()
+
+    def run(self, frames_u8, radar):
+        """frames_u8 (B, ih, iw, 3) uint8 RGB and radar (B, 4, H, W) float32 / float64: numpy arrays or tensors, pageable,
+        pinned or on the device -> FrameResult.  The inputs are copied into the static buffers (non_blocking), then the graph
+        is replayed (graph=False: the chain is run); no host synchronisation."""
+        f, r = validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape)
+        with torch.cuda.device(self.device):
+            self.frames_u8.copy_(f, non_blocking=True)
+            self.radar.copy_(r, non_blocking=True)
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                with torch.no_grad():
+                    self.result = self._chain()
+        return self.result

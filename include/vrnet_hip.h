@@ -581,6 +581,31 @@ long vrnet_nms_workspace_bytes(int segments, int n_max);
 int vrnet_nms_segmented_f32(const float* rows, int ld, const float* scores, const long long* classes, const int* ids,
                             const int* counts, int segments, long stride, int n_max, double iou_thres, void* workspace,
                             long workspace_bytes, int* keep, int* kept, float* rows_out, void* stream);
+/* The same NMS with a FIXED capacity, for a captured graph (added within ABI 11: new symbols only; yolo.py:149 non_max_suppression inside predict.py's
+ * `video` / `fps` loops, yolo.py:229-291 get_FPS):
+ * vrnet_nms_capped_f32: vrnet_nms_segmented_f32 with device `counts` (required) and n_max = cap.  ALL min(counts[s],
+ *   stride) candidates of a segment are ranked by (score descending, id ascending); only ranks < cap enter the NMS, so the
+ *   result is the exact prefix of the uncapped result -- its kept boxes of rank < cap -- whatever order the candidate list
+ *   has.  Bit 8 of *flag (int32, OR-ed in) is set when counts[s] > cap for some segment.  keep / kept / rows_out
+ *   (segments, cap[, ld]); workspace: vrnet_nms_workspace_bytes(segments, cap).  stride < 2^31.
+ * vrnet_detect_finish_f32, utils/utils_bbox.py:126-134 + 5-30 (yolo_correct_boxes) and yolo.py:164-208 (the box corners and
+ *   class counts of detect_image): rows (B, cap, 7) / kept (B) = rows_out / kept of vrnet_nms_capped_f32 on
+ *   vrnet_detect_select_f32's rows.  Per kept row: box_xy = (r[0:2] + r[2:4]) / 2, box_wh = r[2:4] - r[0:2] in fp32; then in
+ *   fp64, per axis, centre = (centre - offset) * scale, size = size * scale, (centre -+ 0.5 size) * image size, rounded once
+ *   to fp32.  The caller computes the shape-only scalars in float64: with a letterbox inner = round(image * min(input /
+ *   image)), offset = 0.5 * (input - inner) / input, scale = input / inner; without one offset = 0, scale = 1 (exact
+ *   identities).  rows_out (B, cap, 7) = top, left, bottom, right in pixels of the original image, obj, class_conf, class;
+ *   rows k >= kept[b] are zero.  draw_rows (B * cap, 5) int32 = left, top, right, bottom, class with left = max(0,
+ *   floor(left)), top = max(0, floor(top)), right = min(image_w, floor(right)), bottom = min(image_h, floor(bottom)), the
+ *   images back to back (the rest zero); offsets (B + 1) int32 their prefix sums: what vrnet_render_u8 takes as boxes /
+ *   box_offsets.  det_counts (B, num_classes) int64 = kept rows per class; a class id outside [0, num_classes) is not
+ *   counted and sets bit 16 of *flag. */
+int vrnet_nms_capped_f32(const float* rows, int ld, const float* scores, const long long* classes, const int* ids,
+                         const int* counts, int segments, long stride, int cap, double iou_thres, void* workspace,
+                         long workspace_bytes, int* keep, int* kept, float* rows_out, int* flag, void* stream);
+int vrnet_detect_finish_f32(const float* rows, const int* kept, int B, int cap, int num_classes, int image_h, int image_w,
+                            double offset_y, double offset_x, double scale_y, double scale_x, float* rows_out,
+                            int* draw_rows, int* offsets, long long* det_counts, int* flag, void* stream);
 
 /* ---- segmentation post-processing (csrc/segpost.hip, loss.hip) ------------------------------------------------
  * Added within ABI 11: new symbols only, no existing signature or layout changed; hip.py binds every declared symbol at
@@ -656,6 +681,15 @@ int vrnet_det_map_f64(const int* det_image, const int* det_label, const double* 
  * onehot. */
 int vrnet_batch_formats_u8(const unsigned char* img, const unsigned char* png, int B, int H, int W, int num_classes_seg,
                            float* images, long long* png_out, float* onehot, void* stream);
+/* vrnet_radar_normalise (added within ABI 11: a new symbol only), utils/utils.py:50-53 preprocess_input_radar as yolo.py:134 applies it to one frame's maps:
+ * radar (B, frame_elems) float32 (is_f64 = 0) or float64 (1), frame_elems = 4 H W -> out (B, frame_elems) f32 =
+ * (x - lo) / (hi - lo) + 1e-13 with lo / hi the frame's minimum / maximum over all its values, evaluated in the input's
+ * type as numpy does and rounded to float32 (bit-identical; a constant frame gives NaN, as the reference's 0 / 0; a NaN in a
+ * frame makes the whole frame NaN).  normalise = 0: the cast alone (deeplab.py and the dataloader feed the maps raw).  Two
+ * launches (partials, apply), no atomics.  workspace (8-byte aligned): vrnet_radar_workspace_bytes(B) bytes. */
+long vrnet_radar_workspace_bytes(int B);
+int vrnet_radar_normalise(const void* radar, int is_f64, int B, long frame_elems, int normalise, float* out, void* workspace,
+                          long workspace_bytes, void* stream);
 
 /* ---- letterbox from raw bytes (csrc/letterbox.hip) --------------------------------------------------------------
  * Added within ABI 11: new symbols only, no existing signature or layout changed.

@@ -1,0 +1,331 @@
+"""The captured frame-to-result pipeline (asy-vrnet_amd/infer.py) and the three device pieces under it: the capped NMS
+(vrnet_nms_capped_f32), the detection tail on the device (vrnet_detect_finish_f32) and the radar normalisation
+(vrnet_radar_normalise).  Each is specified as an exact restatement of a host function of this package that golden vectors
+already pin -- decode.non_max_suppression, decode.yolo_correct_boxes, render.box_rows, data.preprocess_input_radar -- so every
+comparison is bitwise."""
+import numpy as np
+import pytest
+import torch
+
+import asy_vrnet_amd as A
+from asy_vrnet_amd import data, decode, infer, render
+
+NC = 4
+
+
+def cuda(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def capped_detect(pred, cap, conf, nms, input_shape, image_shape, letterbox, nc=NC):
+    """The detection tail of FramePipeline on a (B, A, 5+nc) device tensor: (list of (N_b, 7) rows, flag word, tensors)."""
+    import asy_vrnet_amd.hip as hip
+    B, A_, _ = pred.shape
+    dev = pred.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    rows, scores = torch.empty((B, A_, 7), device=dev), torch.empty((B, A_), device=dev)
+    cls, ids, counts = torch.empty((B, A_), dtype=torch.int64, device=dev), torch.empty((B, A_), **i32), torch.empty(B, **i32)
+    flag = torch.zeros(1, **i32)
+    keep, kept, kept_rows = torch.empty((B, cap), **i32), torch.empty(B, **i32), torch.empty((B, cap, 7), device=dev)
+    ws = torch.empty(hip.nms_workspace_bytes(B, cap), dtype=torch.uint8, device=dev)
+    hip.detect_select(pred, nc, conf, rows, scores, cls, ids, counts)
+    hip.nms_capped(rows, scores, cls, ids, counts, B, A_, cap, nms, ws, keep, kept, kept_rows, flag)
+    out = finish(kept_rows, kept, nc, input_shape, image_shape, letterbox, flag)
+    res = infer.FrameResult(out["rows"], kept, out["det_counts"], None, None, None, flag)
+    return res.detections(), int(flag), dict(out, counts=counts, kept=kept)
+
+
+def finish(kept_rows, kept, nc, input_shape, image_shape, letterbox, flag=None):
+    import asy_vrnet_amd.hip as hip
+    B, cap = kept_rows.shape[:2]
+    dev = kept_rows.device
+    out = dict(rows=torch.full((B, cap, 7), 7.0, device=dev), draw_rows=torch.full((B * cap, 5), -3, dtype=torch.int32, device=dev),
+               offsets=torch.full((B + 1,), -3, dtype=torch.int32, device=dev),
+               det_counts=torch.full((B, nc), -3, dtype=torch.int64, device=dev),
+               flag=torch.zeros(1, dtype=torch.int32, device=dev) if flag is None else flag)
+    offset, scale = infer.unmap_scalars(input_shape, image_shape, letterbox)
+    hip.detect_finish(kept_rows, kept, nc, image_shape, offset, scale, out["rows"], out["draw_rows"], out["offsets"],
+                      out["det_counts"], out["flag"])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- 1. capped NMS
+def synthetic_prediction():
+    """(4, 336, 5 + 4): image 0 every anchor above 0.3, image 1 exactly 100, image 2 none, image 3 37 with groups of equal
+    scores and heavily overlapping boxes of the same and of different classes."""
+    rng = np.random.default_rng(71)
+    B, A_ = 4, 336
+    p = np.zeros((B, A_, 5 + NC), np.float32)
+    p[..., 0:2] = rng.uniform(0.1, 0.9, (B, A_, 2))
+    p[..., 2:4] = rng.uniform(0.02, 0.12, (B, A_, 2))
+    p[..., 4] = rng.uniform(0.7, 1.0, (B, A_))
+    p[..., 5:] = rng.uniform(0.0, 0.5, (B, A_, NC))
+    best = rng.integers(0, NC, (B, A_))
+    np.put_along_axis(p[..., 5:], best[..., None], rng.uniform(0.7, 1.0, (B, A_, 1)).astype(np.float32), axis=-1)
+    passing = np.zeros((B, A_), bool)
+    passing[0] = True
+    passing[1, rng.permutation(A_)[:100]] = True
+    sel = rng.permutation(A_)[:37]
+    passing[3, sel] = True
+    p[..., 4][~passing] = 0.05
+    # image 3: equal scores in groups of 5 (same obj and class_conf), boxes jittered around three centres
+    for g, a in enumerate(sel):
+        p[3, a, 4] = np.float32(0.75 + 0.03 * (g // 5))
+        p[3, a, 5:] = 0.1
+        p[3, a, 5 + g % NC if g % 3 else 5] = np.float32(0.9)
+        p[3, a, 0:2] = np.float32([0.3, 0.5, 0.7][g % 3]) + rng.uniform(-0.01, 0.01, 2)
+        p[3, a, 2:4] = 0.2 + rng.uniform(-0.01, 0.01, 2)
+    return p
+
+
+def zero_outside_top(p, cap, conf):
+    """A copy of p with the objectness of every candidate outside the `cap` best keys (score descending, anchor ascending)
+    of its image set to 0; also the candidate counts."""
+    q = p.copy()
+    score = p[..., 4] * p[..., 5:5 + NC].max(-1)                       # fp32, as the select kernel
+    counts = []
+    for b in range(len(p)):
+        cand = np.flatnonzero(score[b] >= np.float32(conf))
+        order = cand[np.lexsort((cand, -score[b, cand].astype(np.float64)))]
+        q[b, order[cap:], 4] = 0.0
+        counts.append(len(cand))
+    return q, counts
+
+
+@pytest.mark.gpu
+def test_capped_nms_is_the_exact_prefix():
+    cap, conf, nms, S, F = 100, 0.3, 0.4, (128, 128), (90, 160)
+    p = synthetic_prediction()
+    q, counts = zero_outside_top(p, cap, conf)
+    assert counts == [336, 100, 0, 37]
+    uncapped = decode.non_max_suppression(cuda(p), NC, S, F, True, conf_thres=conf, nms_thres=nms)
+    want = decode.non_max_suppression(cuda(q), NC, S, F, True, conf_thres=conf, nms_thres=nms)
+    got, flag, t = capped_detect(cuda(p), cap, conf, nms, S, F, True)
+    print("candidates", t["counts"].tolist(), "kept capped", [len(g) for g in got], "uncapped", [len(u) for u in uncapped])
+    assert t["counts"].tolist() == counts
+    assert len(uncapped[0]) > len(want[0]) > 0                     # the cap was exercised
+    assert len(want[3]) < 37 and len(want[3]) > 3                   # image 3 suppresses, and keeps boxes of several classes
+    for b in range(4):
+        assert got[b].dtype == np.float32 and got[b].shape == want[b].shape, b
+        assert np.array_equal(got[b], want[b]), b
+        assert np.array_equal(got[b], uncapped[b][:len(got[b])]), b                 # the prefix of the uncapped result
+    assert flag & infer.FLAG_CANDIDATES
+    # the overflow bit comes from image 0 alone
+    assert capped_detect(cuda(p[1:]), cap, conf, nms, S, F, True)[1] == 0
+    assert capped_detect(cuda(p[:1]), cap, conf, nms, S, F, True)[1] == infer.FLAG_CANDIDATES
+
+
+# ---------------------------------------------------------------------------------------------- 2. detect_finish
+@pytest.mark.gpu
+@pytest.mark.parametrize("letterbox", [True, False])
+@pytest.mark.parametrize("image_shape", [(37, 53), (1080, 1920)])
+@pytest.mark.parametrize("input_shape", [(64, 64), (128, 192)])
+def test_detect_finish_equals_the_host_path(letterbox, image_shape, input_shape):
+    cap = 70
+    kept = [0, 1, 17, cap]
+    rng = np.random.default_rng(72)
+    rows = np.zeros((4, cap, 7), np.float32)
+    lo = rng.uniform(-0.3, 0.9, (4, cap, 2))
+    rows[..., 0:2] = lo
+    rows[..., 2:4] = lo + rng.uniform(0.0, 0.6, (4, cap, 2))          # reaches below 0 and above 1 on every side
+    rows[..., 4:6] = rng.uniform(0.5, 1.0, (4, cap, 2))
+    rows[..., 6] = rng.integers(0, NC, (4, cap))
+    assert rows[..., 0].min() < 0 and rows[..., 1].min() < 0 and rows[..., 2].max() > 1 and rows[..., 3].max() > 1
+    out = finish(cuda(rows), torch.tensor(kept, dtype=torch.int32, device="cuda"), NC, input_shape, image_shape, letterbox)
+    want = []
+    for b in range(4):                                                  # decode.non_max_suppression's host tail
+        det = rows[b, :kept[b]].copy()
+        if len(det):
+            box_xy, box_wh = (det[:, 0:2] + det[:, 2:4]) / 2, det[:, 2:4] - det[:, 0:2]
+            det[:, :4] = decode.yolo_correct_boxes(box_xy, box_wh, input_shape, image_shape, letterbox)
+        want.append(det)
+    got = out["rows"].cpu().numpy()
+    for b in range(4):
+        assert np.array_equal(got[b, :kept[b]], want[b]), b
+        assert not got[b, kept[b]:].any(), b
+    draw, offsets, _, counts = render.box_rows(want, image_shape, NC, input_shape)
+    assert np.array_equal(out["offsets"].cpu().numpy(), offsets)
+    assert np.array_equal(out["draw_rows"].cpu().numpy()[:len(draw)], draw)
+    assert not out["draw_rows"].cpu().numpy()[len(draw):].any()
+    assert np.array_equal(out["det_counts"].cpu().numpy(), counts)
+    assert int(out["flag"]) == 0
+
+
+@pytest.mark.gpu
+def test_detect_finish_flags_a_class_outside_the_range():
+    rows = np.zeros((1, 3, 7), np.float32)
+    rows[0, :, 0:4] = [0.2, 0.2, 0.6, 0.6]
+    rows[0, :, 6] = [1, 7, -1]
+    out = finish(cuda(rows), torch.tensor([3], dtype=torch.int32, device="cuda"), NC, (64, 64), (64, 64), True)
+    assert int(out["flag"]) == infer.FLAG_DET_CLASS
+    draw, _, _, counts = render.box_rows([rows[0]], (64, 64), NC)       # box_rows counts classes 0 .. n-1 only, too
+    assert np.array_equal(out["det_counts"].cpu().numpy(), counts) and counts.sum() == 1
+    assert out["draw_rows"].cpu().numpy()[:, 4].tolist() == [1, 7, -1]
+
+
+# ---------------------------------------------------------------------------------------------- 3. device_radar
+def radar_frames(shape, dtype):
+    rng = np.random.default_rng(73)
+    x = rng.standard_normal(shape)
+    x[0] = x[0] * 40.0 + 100.0
+    if shape[0] > 1:
+        x[1] = -np.abs(x[1]) * 3.0 - 1.0              # negative values only
+    if shape[0] > 2:
+        x[2] = 0.375                                   # constant: 0 / 0 in the reference
+    return x.astype(dtype)
+
+
+def radar_restated(x):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.stack([data.preprocess_input_radar(f).astype(np.float32) for f in x])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,dtype", [((3, 4, 33, 47), np.float32), ((3, 4, 33, 47), np.float64),
+                                         ((2, 4, 80, 96), np.float64),      # more than 64 x 256 values: every partial is used
+                                         ((1, 4, 260, 260), np.float32)])   # more than 1024 x 256: the apply loops
+def test_device_radar_equals_preprocess_input_radar(shape, dtype):
+    x = radar_frames(shape, dtype)
+    want = radar_restated(x)
+    assert np.isfinite(want[:2]).all() and (shape[0] < 3 or np.isnan(want[2]).all())
+    for src in (x, cuda(x)):
+        got = data.device_radar(src)
+        assert got.dtype == torch.float32 and tuple(got.shape) == shape
+        assert np.array_equal(got.cpu().numpy(), want, equal_nan=True)
+    assert np.array_equal(data.device_radar(x, normalise=False).cpu().numpy(), x.astype(np.float32))
+    assert np.array_equal(data.device_radar(x[0]).cpu().numpy(), want[:1], equal_nan=True)      # one frame counts as B = 1
+
+
+# ---------------------------------------------------------------------------------------------- 4-6. the pipeline
+S, F, CAP, NMS_THRES = (64, 64), (40, 56), 64, 0.4
+
+
+def make_inputs(seed):
+    rng = np.random.default_rng(seed)
+    frames = rng.integers(0, 256, (2,) + F + (3,), dtype=np.uint8)
+    radar = (rng.standard_normal((2, 4) + S) * 2.0 + 1.0).astype(np.float32)
+    return frames, radar
+
+
+def compose(model, frames, radar, conf):
+    """The eager composition of the public calls, as INTEGRATION.md writes yolo.py's and deeplab.py's detect_image."""
+    fr = cuda(frames)
+    images, _ = data.device_letterbox(fr, S)
+    rd = torch.from_numpy(np.stack([data.preprocess_input_radar(f) for f in radar])).float().cuda()
+    with torch.no_grad():
+        det, seg = model(images, rd)
+    pred = decode.decode_outputs(det, S)
+    results = decode.non_max_suppression(pred, NC, S, F, True, conf_thres=conf, nms_thres=NMS_THRES)
+    cmap = decode.seg_predict(seg, S, F)
+    out, seg_counts = render.render_frame(fr, cmap, results, S, palette=render.seg_palette(9), box_palette=render.det_palette(NC),
+                                          count=True)
+    return dict(detections=results, det_counts=render.box_rows(results, F, NC, S)[3], class_map=cmap.cpu().numpy(),
+                seg_counts=seg_counts.cpu().numpy(), rendered=out.cpu().numpy(), pred=pred)
+
+
+@pytest.fixture(scope="module")
+def setup():
+    model = A.EfficientVRNet(NC, 9, "nano", img_size=S[0]).cuda().eval()
+    A.randomize_state_dict(model.state_dict(), seed=4)
+    first, second = make_inputs(74), make_inputs(75)
+    pred = compose(model, *first, 0.5)["pred"]
+    score = (pred[..., 4] * pred[..., 5:5 + NC].amax(-1)).flatten().sort(descending=True).values
+    conf = float(score[11])                                # the 12th-largest score of the batch
+    buffers = [b.detach().clone() for b in model.buffers()]
+    pipes = {g: A.FramePipeline(model, F, S, batch=2, conf_thres=conf, nms_thres=NMS_THRES, max_candidates=CAP,
+                                normalise_radar=True, graph=g) for g in (False, True)}
+    assert all(torch.equal(a, b) for a, b in zip(buffers, model.buffers()))        # the warm-up left the model alone
+    return dict(model=model, conf=conf, first=first, second=second, pipes=pipes,
+                want=[compose(model, *first, conf), compose(model, *second, conf)])
+
+
+def snapshot(res):
+    return dict(detections=res.detections(), det_counts=res.det_counts.cpu().numpy(), class_map=res.class_map.cpu().numpy(),
+                seg_counts=res.seg_counts.cpu().numpy(), rendered=res.rendered.cpu().numpy(), kept=res.kept.cpu().numpy(),
+                flag=int(res.flag))
+
+
+def assert_same(got, want):
+    assert len(got["detections"]) == len(want["detections"])
+    for g, w in zip(got["detections"], want["detections"]):
+        assert g.dtype == np.float32 and g.shape == w.shape and np.array_equal(g, w)
+    for k in ("det_counts", "class_map", "seg_counts", "rendered"):
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+    assert got["flag"] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("graph", [False, True])
+def test_pipeline_equals_the_eager_composition(setup, graph):
+    want = setup["want"][0]
+    n = [len(d) for d in want["detections"]]
+    print("conf_thres", setup["conf"], "kept per image", n)
+    assert sum(n) > 0 and want["det_counts"].sum() == sum(n)                       # not vacuous
+    pipe = setup["pipes"][graph]
+    assert (pipe.graph is not None) == graph and pipe.cap == CAP
+    got = snapshot(pipe.run(*setup["first"]))
+    assert 0 < got["kept"].max() < CAP                                                 # and no image reaches the cap
+    assert_same(got, want)
+    assert tuple(pipe.result.class_map.shape) == (2,) + F and pipe.result.class_map.dtype == torch.uint8
+    assert tuple(pipe.result.rendered.shape) == (2,) + F + (3,)
+
+
+@pytest.mark.gpu
+def test_replay_follows_its_inputs(setup):
+    pipe = setup["pipes"][True]
+    a = snapshot(pipe.run(*setup["first"]))
+    b = snapshot(pipe.run(*setup["second"]))
+    assert_same(a, setup["want"][0])
+    assert_same(b, setup["want"][1])
+    assert not np.array_equal(a["rendered"], b["rendered"])
+    assert any(x.shape != y.shape or not np.array_equal(x, y) for x, y in zip(a["detections"], b["detections"]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("graph", [False, True])
+def test_run_does_not_synchronise(setup, graph):
+    pipe = setup["pipes"][graph]
+    frames, radar = (cuda(a) for a in setup["second"])
+    pipe.run(frames, radar)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        res = pipe.run(frames, radar)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert_same(snapshot(res), setup["want"][1])
+
+
+# ---------------------------------------------------------------------------------------------- 7. argument errors (no GPU)
+def test_pipeline_argument_errors():
+    model = A.EfficientVRNet(NC, 9, "nano", img_size=S[0])
+    with pytest.raises(RuntimeError, match="eval mode"):
+        A.FramePipeline(model, F, S)
+    model.eval()
+    for bad in (0, render.MAX_BOXES + 1, -5, 2.5):
+        with pytest.raises(RuntimeError, match="max_candidates"):
+            A.FramePipeline(model, F, S, max_candidates=bad)
+    assert infer.validate_config(model, F, S, 2, render.MAX_BOXES) == (F, S, 2, render.MAX_BOXES)
+    frames, radar = make_inputs(76)
+    f, r = infer.validate_inputs(frames, radar, 2, F, S)
+    assert tuple(f.shape) == (2,) + F + (3,) and tuple(r.shape) == (2, 4) + S
+    with pytest.raises(RuntimeError, match="built for frames"):
+        infer.validate_inputs(frames[:, :-1], radar, 2, F, S)
+    with pytest.raises(RuntimeError, match="built for frames"):
+        infer.validate_inputs(frames[:1], radar, 2, F, S)
+    with pytest.raises(RuntimeError, match="built for radar"):
+        infer.validate_inputs(frames, radar[:, :3], 2, F, S)
+    with pytest.raises(RuntimeError, match="uint8"):
+        infer.validate_inputs(frames.astype(np.float32), radar, 2, F, S)
+
+
+def test_unmap_scalars_are_those_of_yolo_correct_boxes():
+    """(c - offset) * scale and s * scale with the scalars of unmap_scalars are yolo_correct_boxes' own operations."""
+    rng = np.random.default_rng(77)
+    xy, wh = rng.uniform(0, 1, (50, 2)).astype(np.float32), rng.uniform(0, 0.5, (50, 2)).astype(np.float32)
+    for inp, img, lb in (((64, 64), (37, 53), True), ((128, 192), (1080, 1920), True), ((64, 64), (37, 53), False)):
+        off, sc = infer.unmap_scalars(inp, img, lb)
+        c = (xy[:, ::-1].astype(np.float64) - np.array(off)) * np.array(sc)
+        s = wh[:, ::-1].astype(np.float64) * np.array(sc)
+        mine = np.concatenate([(c - 0.5 * s) * np.array(img, np.float64), (c + 0.5 * s) * np.array(img, np.float64)], axis=-1)
+        assert np.array_equal(mine, decode.yolo_correct_boxes(xy, wh, inp, img, lb))

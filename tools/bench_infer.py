@@ -12,10 +12,16 @@ the output side after the forward: render.seg_render (mix_type 0, with the pixel
 at each original size H x W, and render.render_frame of the same map with 100 boxes per image, on frames resident on the
 device -- next to a plain device copy of the same frame bytes (out.copy_(frames): the bound of a byte-bound pass) and to the
 host path on one core (numpy palette lookup + Image.blend, where Pillow is installed), with the bytes per image that
-would otherwise cross PCIe.
+would otherwise cross PCIe.  With --pipeline HxW[,HxW...] it times frame-in to rendered-frame-out for frames of each original
+size H x W resident on the device, three ways in alternating rounds (the minimum of three rounds each, on the same seeded
+frames): the eager composition of the public calls (device_letterbox, the forward, decode_outputs, non_max_suppression with
+its two read-backs, seg_predict, render_frame with its upload of the box rows), infer.FramePipeline(graph=False) and
+infer.FramePipeline(graph=True), at the thresholds of the first --nms pair (default 0.5/0.4), with the candidate and kept
+counts of the frames.
 
     python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
                                 [--seg 1080x1920,480x640] [--letterbox 1080x1920,480x640] [--render 1080x1920,480x640]
+                                [--pipeline 1080x1920]
 """
 import argparse
 import os
@@ -37,16 +43,19 @@ def main():
     ap.add_argument("--seg", default="", help="comma list of original image sizes HxW (e.g. 1080x1920,480x640)")
     ap.add_argument("--letterbox", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
     ap.add_argument("--render", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
+    ap.add_argument("--pipeline", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
     from asy_vrnet_amd.data import device_letterbox, resize_image
     from asy_vrnet_amd.decode import decode_outputs, non_max_suppression, seg_predict
     from asy_vrnet_amd.metrics import f_score, fast_hist
-    from asy_vrnet_amd.render import det_palette, render_frame, seg_palette, seg_render
+    from asy_vrnet_amd.infer import FramePipeline
+    from asy_vrnet_amd.render import MAX_BOXES, det_palette, render_frame, seg_palette, seg_render
     pairs = [tuple(float(v) for v in p.split("/")) for p in args.nms.split(",") if p]
     seg_sizes = [tuple(int(v) for v in p.split("x")) for p in args.seg.split(",") if p]
     frame_sizes = [tuple(int(v) for v in p.split("x")) for p in args.letterbox.split(",") if p]
     render_sizes = [tuple(int(v) for v in p.split("x")) for p in args.render.split(",") if p]
+    pipeline_sizes = [tuple(int(v) for v in p.split("x")) for p in args.pipeline.split(",") if p]
 
     def timed(fn):
         for _ in range(3):
@@ -190,6 +199,38 @@ def main():
                 np.bincount(host_map[b].reshape(-1), minlength=9)
             host_ms = (time.perf_counter() - t0) / min(bs, 2) * 1e3
             print(line + f"; host path on one core (numpy palette lookup + Image.blend + bincount) {host_ms:.3f} ms/image")
+
+        for ih, iw in pipeline_sizes:
+            conf, iou = pairs[0] if pairs else (0.5, 0.4)
+            gen = torch.Generator().manual_seed(bs)
+            frames = torch.randint(0, 256, (bs, ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
+            pal, bpal = torch.from_numpy(seg_palette(9)).to(dev), torch.from_numpy(det_palette(model.num_classes)).to(dev)
+
+            def composed():
+                images, _ = device_letterbox(frames, S)
+                with torch.no_grad():
+                    det, seg = model(images, r)
+                results = non_max_suppression(decode_outputs(det, S), model.num_classes, S, (ih, iw), True, conf_thres=conf,
+                                              nms_thres=iou)
+                cmap = seg_predict(seg, S, (ih, iw))
+                return render_frame(frames, cmap, [d[:MAX_BOXES] for d in results], S, palette=pal, box_palette=bpal, count=True)
+
+            pipes = {g: FramePipeline(model, (ih, iw), S, batch=bs, conf_thres=conf, nms_thres=iou, seg_palette=pal,
+                                      box_palette=bpal, graph=g) for g in (False, True)}
+            variants = {"composition": composed, "pipeline_eager": lambda: pipes[False].run(frames, r),
+                        "pipeline_captured": lambda: pipes[True].run(frames, r)}
+            rounds = {k: [] for k in variants}
+            for _ in range(3):                       # alternating rounds, so that a drift of the clock hits them alike
+                for k, fn in variants.items():
+                    rounds[k].append(timed(fn))
+            ms = {k: min(v) for k, v in rounds.items()}
+            res = pipes[True].run(frames, r)
+            same = torch.equal(res.rendered, composed()[0])
+            print(f"  + pipeline {ih}x{iw} -> rendered frame, conf {conf} iou {iou}, bs={bs}: eager composition of the public calls "
+                  f"{ms['composition']:.3f} ms/batch, FramePipeline eager {ms['pipeline_eager']:.3f} ms, captured "
+                  f"{ms['pipeline_captured']:.3f} ms ({ms['composition'] / ms['pipeline_captured']:.2f} x the composition, "
+                  f"{bs / ms['pipeline_captured'] * 1e3:.1f} frames/s); candidates {pipes[True]._cand[4].tolist()} of capacity "
+                  f"{pipes[True].cap}, kept {res.kept.tolist()}, flag {int(res.flag)}; rendered frames equal the composition's: {same}")
 
 
 def f_score_eager(x, target, beta=1, smooth=1e-5, threshold=0.5):
