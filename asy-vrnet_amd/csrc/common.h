@@ -46,6 +46,12 @@ static inline hipStream_t vr_stream(void* s) { return reinterpret_cast<hipStream
 static inline long vr_cdiv(long a, long b) { return (a + b - 1) / b; }
 static inline bool vr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// stream_ops.hip: the work split of the moments kernel on 16-byte accesses (C % 4 == 0), and the launch that finishes its
+// chunk partials [B][nchunks][C][2] into out [B][C][2]
+void vr_moments_plan4(int B, long HW, int C, int* TPR, int* ncb, int* nchunks, long* rows);
+int vr_moments_reduce(const double* partial, double* out, int B, int nchunks, int C, hipStream_t st);
+extern "C" long vrnet_moments_workspace(int B, long HW, int C);
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -347,27 +347,64 @@ __global__ void ohwi_kernel(const float* src, float* dst, int Cout, int Cin, int
 }
 
 // ------------------------------------------------------------------------------------------ bilinear upsample
+// The arithmetic helpers of this family switch fp contraction off and write every fused multiply-add out (round 7): left to
+// the compiler, WHICH products it fuses depends on the code around the expression -- the same source line gave
+// fma(scale, o, -a) for the weight in one kernel and fl(scale * o) - a in its neighbour -- and kernels that are meant to agree
+// bit for bit would do so by luck.  The forms below are the ones the compiler had chosen for the kernels of rounds 1-6, so
+// their results are unchanged: FUSED_L (the weight as one fma) in the adjoints, two roundings in the forward gathers.
+template <bool FUSED_L = false>
 __device__ __forceinline__ void src_index(float scale, int o, int in_size, int* i0, int* i1, float* l1) {
+#pragma clang fp contract(off)
   const float r = scale * (float)o;
   int a = (int)r;
   if (a > in_size - 1) a = in_size - 1;
   *i0 = a;
   *i1 = a + ((a < in_size - 1) ? 1 : 0);
-  *l1 = r - (float)a;
+  *l1 = FUSED_L ? __builtin_fmaf(scale, (float)o, -(float)a) : r - (float)a;
 }
 
 // bnA != nullptr (round 5, K11): the taps are ReLU(BatchNorm(z)) of the pre-normalisation map x = z, evaluated on the fly as
 // fmaxf(fma(A[c], z - S[c], D[c]), 0) -- the expression of the apply kernel (stream_ops.hip bn_pre), so the result has the bits of
 // affine + upsample while the low-resolution activation is never stored.
+__device__ __forceinline__ float up_tap(float v, bool bn, float a, float d, float s) {
+  return bn ? fmaxf(__builtin_fmaf(a, v - s, d), 0.f) : v;
+}
 __device__ __forceinline__ float up_tap(float v, const float* bnA, const float* bnD, const float* bnS, int c) {
-  return bnA ? fmaxf(__builtin_fmaf(bnA[c], v - bnS[c], bnD[c]), 0.f) : v;
+  return bnA ? up_tap(v, true, bnA[c], bnD[c], bnS[c]) : v;
 }
 
+// One output value of the gather: THE expression of the family.  Every forward kernel below (and the fused gather + concat
+// kernel) evaluates a component through these two helpers and nothing else, so that they agree bit for bit.
+// (1 - ly) ((1 - lx) v00 + lx v01) + ly ((1 - lx) v10 + lx v11), the first product of every sum fused into the addition
+__device__ __forceinline__ float up_lerp(float v00, float v01, float v10, float v11, float lx, float ly) {
+#pragma clang fp contract(off)
+  const float ax = 1.f - lx, ay = 1.f - ly;
+  const float top = __builtin_fmaf(ax, v00, lx * v01), bot = __builtin_fmaf(ax, v10, lx * v11);
+  return __builtin_fmaf(ay, top, ly * bot);
+}
+__device__ __forceinline__ float up_blend(float t00, float t01, float t10, float t11, float lx, float ly, const float* bnA,
+                                          const float* bnD, const float* bnS, int c) {
+  return up_lerp(up_tap(t00, bnA, bnD, bnS, c), up_tap(t01, bnA, bnD, bnS, c), up_tap(t10, bnA, bnD, bnS, c),
+                 up_tap(t11, bnA, bnD, bnS, c), lx, ly);
+}
+// ... with the channel's coefficients already in registers (a kernel that keeps its channels for many pixels)
+__device__ __forceinline__ float up_blend(float t00, float t01, float t10, float t11, float lx, float ly, bool bn, float a,
+                                          float d, float s) {
+  return up_lerp(up_tap(t00, bn, a, d, s), up_tap(t01, bn, a, d, s), up_tap(t10, bn, a, d, s), up_tap(t11, bn, a, d, s), lx, ly);
+}
+// Index arithmetic of the family (round 7): a workgroup belongs to ONE line of the tensor -- an output row (b, oy) of an NHWC
+// map, a plane (b, c) of an NCHW one -- which it finds from blockIdx.x with two uniform 32-bit divisions; a thread then splits
+// its position inside the line with ONE 32-bit division.  (Before: three 64-bit `/` and three 64-bit `%` per element -- some
+// 600 VALU instructions in front of four loads and one store; upsample_vec ran at 0.55 TB/s.)
+__device__ __forceinline__ float up_ratio(int in_size, int out_size) {
+  return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
+}
+
+// scalar fallback (any C, either output layout)
 __global__ __launch_bounds__(256) void upsample_kernel(const float* x, long ldx, float* y, long ldy, int B, int H,
                                                        int W, int C, int OH, int OW, int out_nchw, const float* bnA,
                                                        const float* bnD, const float* bnS) {
-  const float ry = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-  const float rx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
+  const float ry = up_ratio(H, OH), rx = up_ratio(W, OW);
   const long total = (long)B * OH * OW * C;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     int c, ox, oy;
@@ -382,212 +419,375 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* x, long ldx,
     src_index(ry, oy, H, &y0, &y1, &ly);
     src_index(rx, ox, W, &x0, &x1, &lx);
     const float* base = x + (b * H * W) * ldx + c;
-    const float v00 = up_tap(base[((long)y0 * W + x0) * ldx], bnA, bnD, bnS, c), v01 = up_tap(base[((long)y0 * W + x1) * ldx], bnA, bnD, bnS, c);
-    const float v10 = up_tap(base[((long)y1 * W + x0) * ldx], bnA, bnD, bnS, c), v11 = up_tap(base[((long)y1 * W + x1) * ldx], bnA, bnD, bnS, c);
-    const float v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+    const float v = up_blend(base[((long)y0 * W + x0) * ldx], base[((long)y0 * W + x1) * ldx], base[((long)y1 * W + x0) * ldx],
+                             base[((long)y1 * W + x1) * ldx], lx, ly, bnA, bnD, bnS, c);
     if (out_nchw) y[e] = v;
     else y[((b * OH + oy) * OW + ox) * ldy + c] = v;
   }
 }
 
-// NHWC output on 16-byte accesses: a thread interpolates four consecutive channels of one output pixel (index arithmetic
-// once per quad; the same expression per component as the scalar kernel).
-__global__ __launch_bounds__(256) void upsample_vec_kernel(const float* x, long ldx, float* y, long ldy, int B, int H, int W,
-                                                           int C, int OH, int OW, const float* bnA, const float* bnD,
+// NHWC output on 16-byte accesses: a thread interpolates four consecutive channels of one output pixel.  Grid: `segs`
+// workgroups per output row (b, oy), 256 (ox, channel quad) positions each.
+__global__ __launch_bounds__(256) void upsample_vec_kernel(const float* x, long ldx, float* y, long ldy, int H, int W, int C,
+                                                           int OH, int OW, int segs, const float* bnA, const float* bnD,
                                                            const float* bnS) {
-  const float ry = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-  const float rx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-  const int CQ = C >> 2;
-  const long total = (long)B * OH * OW * CQ;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    const int cq = e % CQ;
-    long q = e / CQ;
-    const int ox = q % OW; q /= OW;
-    const int oy = q % OH;
-    const long b = q / OH;
-    int y0, y1, x0, x1;
-    float ly, lx;
-    src_index(ry, oy, H, &y0, &y1, &ly);
-    src_index(rx, ox, W, &x0, &x1, &lx);
-    const float* base = x + (b * H * W) * ldx + 4 * cq;
-    f32x4 v00 = *reinterpret_cast<const f32x4*>(base + ((long)y0 * W + x0) * ldx);
-    f32x4 v01 = *reinterpret_cast<const f32x4*>(base + ((long)y0 * W + x1) * ldx);
-    f32x4 v10 = *reinterpret_cast<const f32x4*>(base + ((long)y1 * W + x0) * ldx);
-    f32x4 v11 = *reinterpret_cast<const f32x4*>(base + ((long)y1 * W + x1) * ldx);
-    if (bnA) {
+  const float ry = up_ratio(H, OH), rx = up_ratio(W, OW);
+  const unsigned CQ = (unsigned)C >> 2;
+  const unsigned row = blockIdx.x / (unsigned)segs;                        // b * OH + oy
+  const unsigned e = (blockIdx.x - row * (unsigned)segs) * 256u + threadIdx.x;
+  if (e >= (unsigned)OW * CQ) return;
+  const unsigned b = row / (unsigned)OH, oy = row - b * (unsigned)OH;
+  const unsigned ox = e / CQ, cq = e - ox * CQ;
+  int y0, y1, x0, x1;
+  float ly, lx;
+  src_index(ry, (int)oy, H, &y0, &y1, &ly);
+  src_index(rx, (int)ox, W, &x0, &x1, &lx);
+  const float* r0 = x + ((long)b * H + y0) * W * ldx + 4 * cq;
+  const float* r1 = x + ((long)b * H + y1) * W * ldx + 4 * cq;
+  const f32x4 v00 = *reinterpret_cast<const f32x4*>(r0 + (long)x0 * ldx), v01 = *reinterpret_cast<const f32x4*>(r0 + (long)x1 * ldx);
+  const f32x4 v10 = *reinterpret_cast<const f32x4*>(r1 + (long)x0 * ldx), v11 = *reinterpret_cast<const f32x4*>(r1 + (long)x1 * ldx);
+  f32x4 v;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = 4 * cq + j;
-        v00[j] = up_tap(v00[j], bnA, bnD, bnS, c);
-        v01[j] = up_tap(v01[j], bnA, bnD, bnS, c);
-        v10[j] = up_tap(v10[j], bnA, bnD, bnS, c);
-        v11[j] = up_tap(v11[j], bnA, bnD, bnS, c);
-      }
-    }
-    f32x4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (1.f - ly) * ((1.f - lx) * v00[j] + lx * v01[j]) + ly * ((1.f - lx) * v10[j] + lx * v11[j]);
-    *reinterpret_cast<f32x4*>(y + ((b * OH + oy) * OW + ox) * ldy + 4 * cq) = v;
-  }
-}
-
-// The adjoint for NHWC dy on 16-byte accesses (same gather, four channels per thread).
-__global__ __launch_bounds__(256) void upsample_bwd_vec_kernel(const float* dy, long lddy, float* dx, long lddx, int B, int H,
-                                                               int W, int C, int OH, int OW, int accumulate) {
-  const float ry = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-  const float rx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-  const int CQ = C >> 2;
-  const long total = (long)B * H * W * CQ;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    const int cq = e % CQ;
-    long q = e / CQ;
-    const int ix = q % W; q /= W;
-    const int iy = q % H;
-    const long b = q / H;
-    int oy_lo = 0, oy_hi = OH - 1, ox_lo = 0, ox_hi = OW - 1;
-    if (ry > 0.f) {
-      oy_lo = max(0, (int)floorf((float)(iy - 1) / ry) - 1);
-      oy_hi = min(OH - 1, (int)ceilf((float)(iy + 1) / ry) + 1);
-    }
-    if (rx > 0.f) {
-      ox_lo = max(0, (int)floorf((float)(ix - 1) / rx) - 1);
-      ox_hi = min(OW - 1, (int)ceilf((float)(ix + 1) / rx) + 1);
-    }
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1;
-      float ly;
-      src_index(ry, oy, H, &y0, &y1, &ly);
-      const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
-      if (wy == 0.f) continue;
-      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-        int x0, x1;
-        float lx;
-        src_index(rx, ox, W, &x0, &x1, &lx);
-        const float wx = (x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f);
-        if (wx == 0.f) continue;
-        const f32x4 g = *reinterpret_cast<const f32x4*>(dy + ((b * OH + oy) * (long)OW + ox) * lddy + 4 * cq);
-        const float w = wy * wx;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[j] += w * g[j];
-      }
-    }
-    f32x4* d = reinterpret_cast<f32x4*>(dx + ((b * H + iy) * (long)W + ix) * lddx + 4 * cq);
-    if (accumulate) s += *d;
-    *d = s;
-  }
+  for (int j = 0; j < 4; ++j) v[j] = up_blend(v00[j], v01[j], v10[j], v11[j], lx, ly, bnA, bnD, bnS, (int)(4 * cq) + j);
+  *reinterpret_cast<f32x4*>(y + ((long)row * OW + ox) * ldy + 4 * cq) = v;
 }
 
 // NCHW output (the seg logits, C = num_seg_classes): a thread writes four consecutive ox of one (b, c, oy) row as one 16-byte
-// store; the row pair and its weight are found once per thread.  Same expression per output as upsample_kernel.
-__global__ __launch_bounds__(256) void upsample_nchw4_kernel(const float* x, long ldx, float* y, int B, int H, int W, int C,
-                                                             int OH, int OW, const float* bnA, const float* bnD,
+// store.  Grid: `segs` workgroups per plane (b, c), 256 (oy, ox quad) positions each.  From scale 2 on, the four outputs of a
+// thread read at most four neighbouring source columns (3 rx < 1.5): their eight taps are loaded -- and put through the
+// BatchNorm + ReLU -- once, not sixteen times (`near`).  Same expression per output as upsample_kernel.
+__global__ __launch_bounds__(256) void upsample_nchw4_kernel(const float* x, long ldx, float* y, int H, int W, int C, int OH,
+                                                             int OW, int segs, int near, const float* bnA, const float* bnD,
                                                              const float* bnS) {
-  const float ry = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-  const float rx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-  const int OQ = OW >> 2;
-  const long total = (long)B * C * OH * OQ;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    const int oq = e % OQ;
-    long q = e / OQ;
-    const int oy = q % OH; q /= OH;
-    const int c = q % C;
-    const long b = q / C;
-    int y0, y1;
-    float ly;
-    src_index(ry, oy, H, &y0, &y1, &ly);
-    const float* r0 = x + ((b * H + y0) * (long)W) * ldx + c;
-    const float* r1 = x + ((b * H + y1) * (long)W) * ldx + c;
-    f32x4 v;
+  const float ry = up_ratio(H, OH), rx = up_ratio(W, OW);
+  const unsigned OQ = (unsigned)OW >> 2;
+  const unsigned plane = blockIdx.x / (unsigned)segs;                      // b * C + c
+  const unsigned e = (blockIdx.x - plane * (unsigned)segs) * 256u + threadIdx.x;
+  if (e >= (unsigned)OH * OQ) return;
+  const unsigned b = plane / (unsigned)C;
+  const int c = (int)(plane - b * (unsigned)C);
+  const unsigned oy = e / OQ, oq = e - oy * OQ;
+  int y0, y1;
+  float ly;
+  src_index(ry, (int)oy, H, &y0, &y1, &ly);
+  const float* r0 = x + ((long)b * H + y0) * W * ldx + c;
+  const float* r1 = x + ((long)b * H + y1) * W * ldx + c;
+  f32x4 v;
+  if (near) {
+    int xa, xb;
+    float l0;
+    src_index(rx, (int)(4 * oq), W, &xa, &xb, &l0);
+    float t0[4], t1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long col = min(xa + k, W - 1);
+      t0[k] = up_tap(r0[col * ldx], bnA, bnD, bnS, c);
+      t1[k] = up_tap(r1[col * ldx], bnA, bnD, bnS, c);
+    }
+    auto pick = [](const float (&t)[4], int k) { return k == 0 ? t[0] : (k == 1 ? t[1] : (k == 2 ? t[2] : t[3])); };
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       int x0, x1;
       float lx;
-      src_index(rx, 4 * oq + j, W, &x0, &x1, &lx);
-      const float v00 = up_tap(r0[(long)x0 * ldx], bnA, bnD, bnS, c), v01 = up_tap(r0[(long)x1 * ldx], bnA, bnD, bnS, c);
-      const float v10 = up_tap(r1[(long)x0 * ldx], bnA, bnD, bnS, c), v11 = up_tap(r1[(long)x1 * ldx], bnA, bnD, bnS, c);
-      v[j] = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+      src_index(rx, (int)(4 * oq) + j, W, &x0, &x1, &lx);
+      v[j] = up_lerp(pick(t0, x0 - xa), pick(t0, x1 - xa), pick(t1, x0 - xa), pick(t1, x1 - xa), lx, ly);
     }
-    *reinterpret_cast<f32x4*>(y + ((b * C + c) * OH + oy) * (long)OW + 4 * oq) = v;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int x0, x1;
+      float lx;
+      src_index(rx, (int)(4 * oq) + j, W, &x0, &x1, &lx);
+      v[j] = up_blend(r0[(long)x0 * ldx], r0[(long)x1 * ldx], r1[(long)x0 * ldx], r1[(long)x1 * ldx], lx, ly, bnA, bnD, bnS, c);
+    }
   }
+  *reinterpret_cast<f32x4*>(y + ((long)plane * OH + oy) * OW + 4 * oq) = v;
 }
 
-// gather form of the adjoint: deterministic, no atomics
-__global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* dy, long lddy, int dy_nchw, float* dx, long lddx,
-                                                           int B, int H, int W, int C, int OH, int OW, int accumulate) {
-  const float ry = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
-  const float rx = OW > 1 ? (float)(W - 1) / (float)(OW - 1) : 0.f;
-  const long total = (long)B * H * W * C;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    int c, ix, iy;
-    long b;
-    if (dy_nchw) {      // neighbouring threads = neighbouring ix of one channel plane: their dy reads share lines (round 4: with
-      ix = e % W;       // c fastest they came from planes megabytes apart -- 0.56 TB/s on the seg logits' gradient)
-      long q = e / W;
-      iy = q % H; q /= H;
-      c = q % C;
-      b = q / C;
+// ---- the adjoint: gather form, deterministic, no atomics ------------------------------------------------------------------
+// The output window (oy_lo .. oy_hi, ox_lo .. ox_hi) that can reach input pixel (iy, ix), and the column weights inside it.
+__device__ __forceinline__ void up_bwd_window(float r, int i, int out_size, int* lo, int* hi) {
+  *lo = 0;
+  *hi = out_size - 1;
+  if (r > 0.f) {
+    *lo = max(0, (int)floorf((float)(i - 1) / r) - 1);
+    *hi = min(out_size - 1, (int)ceilf((float)(i + 1) / r) + 1);
+  }
+}
+template <bool FUSED_L = false>
+__device__ __forceinline__ float up_bwd_weight(float r, int o, int in_size, int i) {
+  int i0, i1;
+  float l;
+  src_index<FUSED_L>(r, o, in_size, &i0, &i1, &l);
+  return (i0 == i ? 1.f - l : 0.f) + (i1 == i ? l : 0.f);
+}
+// one term of the adjoint: s + (wy wx) g, the product with g fused into the addition
+__device__ __forceinline__ float up_bwd_term(float wy, float wx, float g, float s) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(wy * wx, g, s);
+}
+constexpr int UP_MAXR = 16;      // widest window whose column weights a thread keeps in registers
+
+// NHWC dy on 16-byte accesses, four channels per thread.  Grid: `segs` workgroups per input row (b, iy), 256 (ix, channel
+// quad) positions each.  The column weights do not depend on oy: found once per thread (they were re-derived for every
+// (oy, ox) pair); the terms and their order are unchanged.
+// cs / coff: dy is the gradient of a concatenation that holds this map's channel j at column coff + cs * j (cs = 1: a block of
+// torch.cat; cs = 2, coff = 0 / 1: one half of the 2-group channel shuffle) -- read in place, the half is never copied out.
+__global__ __launch_bounds__(256) void upsample_bwd_vec_kernel(const float* dy, long lddy, int cs, int coff, float* dx,
+                                                               long lddx, int H, int W, int C, int OH, int OW, int segs,
+                                                               int accumulate) {
+  const float ry = up_ratio(H, OH), rx = up_ratio(W, OW);
+  const unsigned CQ = (unsigned)C >> 2;
+  const unsigned row = blockIdx.x / (unsigned)segs;                        // b * H + iy
+  const unsigned e = (blockIdx.x - row * (unsigned)segs) * 256u + threadIdx.x;
+  if (e >= (unsigned)W * CQ) return;
+  const unsigned b = row / (unsigned)H;
+  const int iy = (int)(row - b * (unsigned)H);
+  const unsigned uix = e / CQ, cq = e - uix * CQ;
+  const int ix = (int)uix;
+  int oy_lo, oy_hi, ox_lo, ox_hi;
+  up_bwd_window(ry, iy, OH, &oy_lo, &oy_hi);
+  up_bwd_window(rx, ix, OW, &ox_lo, &ox_hi);
+  const int nx = ox_hi - ox_lo + 1;
+  float wxs[UP_MAXR];
+  if (nx <= UP_MAXR) {
+#pragma unroll
+    for (int t = 0; t < UP_MAXR; ++t) wxs[t] = t < nx ? up_bwd_weight<true>(rx, min(ox_lo + t, OW - 1), W, ix) : 0.f;
+  }
+  // the thread's four columns: cs == 1 one aligned quad; cs == 2 every second one of two aligned quads
+  const float* gbase = dy + (long)b * OH * OW * lddy + (cs == 1 ? coff + 4 * cq : 8 * cq);
+  auto load = [&](const float* p) {
+    const f32x4 u = *reinterpret_cast<const f32x4*>(p);
+    if (cs == 1) return u;
+    const f32x4 w = *reinterpret_cast<const f32x4*>(p + 4);
+    const f32x4 ev = {u[0], u[2], w[0], w[2]}, od = {u[1], u[3], w[1], w[3]};
+    return coff ? od : ev;
+  };
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+    const float wy = up_bwd_weight<true>(ry, oy, H, iy);
+    if (wy == 0.f) continue;
+    const float* grow = gbase + ((long)oy * OW + ox_lo) * lddy;
+    if (nx <= UP_MAXR) {
+#pragma unroll
+      for (int t = 0; t < UP_MAXR; ++t) {
+        const float wx = wxs[t];
+        if (wx == 0.f) continue;
+        const f32x4 g = load(grow + t * lddy);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = up_bwd_term(wy, wx, g[j], s[j]);
+      }
+      continue;
+    }
+    for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+      const float wx = up_bwd_weight<true>(rx, ox, W, ix);
+      if (wx == 0.f) continue;
+      const f32x4 g = load(grow + (long)(ox - ox_lo) * lddy);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = up_bwd_term(wy, wx, g[j], s[j]);
+    }
+  }
+  f32x4* d = reinterpret_cast<f32x4*>(dx + ((long)row * W + ix) * lddx + 4 * cq);
+  if (accumulate) s += *d;
+  *d = s;
+}
+
+// One element per thread: NCHW dy (the seg logits' gradient) -- `segs` workgroups per plane (b, c), 256 (iy, ix) positions
+// each, so that neighbouring threads read neighbouring dy of one plane (round 4: with c fastest they came from planes
+// megabytes apart) -- or NHWC dy of any channel count: `segs` workgroups per input row (b, iy), 256 (ix, c) positions each.
+// cs / coff as above (NHWC only).
+__global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* dy, long lddy, int dy_nchw, int cs, int coff, float* dx,
+                                                           long lddx, int H, int W, int C, int OH, int OW, int segs,
+                                                           int accumulate) {
+  const float ry = up_ratio(H, OH), rx = up_ratio(W, OW);
+  const unsigned line = blockIdx.x / (unsigned)segs;
+  const unsigned e = (blockIdx.x - line * (unsigned)segs) * 256u + threadIdx.x;
+  unsigned b;
+  int c, ix, iy;
+  if (dy_nchw) {        // line = b * C + c
+    if (e >= (unsigned)H * (unsigned)W) return;
+    b = line / (unsigned)C;
+    c = (int)(line - b * (unsigned)C);
+    iy = (int)(e / (unsigned)W);
+    ix = (int)(e - (unsigned)iy * (unsigned)W);
+  } else {              // line = b * H + iy
+    if (e >= (unsigned)W * (unsigned)C) return;
+    b = line / (unsigned)H;
+    iy = (int)(line - b * (unsigned)H);
+    ix = (int)(e / (unsigned)C);
+    c = (int)(e - (unsigned)ix * (unsigned)C);
+  }
+  int oy_lo, oy_hi, ox_lo, ox_hi;
+  up_bwd_window(ry, iy, OH, &oy_lo, &oy_hi);
+  up_bwd_window(rx, ix, OW, &ox_lo, &ox_hi);
+  float s = 0.f;
+  // the column weights do not depend on oy: found once (round 4; they were re-derived for every (oy, ox) pair -- 121 times
+  // per element at scale 4); the terms and their order are unchanged
+  const int nx = ox_hi - ox_lo + 1;
+  float wxs[UP_MAXR];
+  if (nx <= UP_MAXR) {
+#pragma unroll
+    for (int t = 0; t < UP_MAXR; ++t) wxs[t] = t < nx ? up_bwd_weight<true>(rx, min(ox_lo + t, OW - 1), W, ix) : 0.f;
+  }
+  const float* gbase = dy_nchw ? dy + ((long)b * C + c) * OH * OW + ox_lo
+                               : dy + ((long)b * OH * OW + ox_lo) * lddy + coff + (long)cs * c;
+  const long gstep = dy_nchw ? 1 : lddy, grow_step = dy_nchw ? OW : (long)OW * lddy;
+  for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+    const float wy = up_bwd_weight<true>(ry, oy, H, iy);
+    if (wy == 0.f) continue;
+    const float* grow = gbase + oy * grow_step;
+    if (nx <= UP_MAXR) {
+#pragma unroll
+      for (int t = 0; t < UP_MAXR; ++t) {
+        const float wx = wxs[t];
+        if (wx == 0.f) continue;
+        s = up_bwd_term(wy, wx, grow[t * gstep], s);
+      }
+      continue;
+    }
+    for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+      const float wx = up_bwd_weight<true>(rx, ox, W, ix);
+      if (wx == 0.f) continue;
+      s = up_bwd_term(wy, wx, grow[(ox - ox_lo) * gstep], s);
+    }
+  }
+  float* d = dx + (((long)b * H + iy) * W + ix) * lddx + c;
+  *d = accumulate ? *d + s : s;
+}
+
+// ---- CoCUpsample + torch.cat with the skip map (+ 2-group channel shuffle) + the statistics of the result, ONE launch ------
+// (round 7; coc_fpn_dual.py:193-221: every up-path level of the neck).  cat (B, OH, OW, C + Cs) is written once and the
+// interpolated map is never stored: a thread owns one output quad cv of the concatenation and walks the pixels of its chunk.
+//   plain:      cat = [up | skip] (up_first) or [skip | up]: the quad lies in one of the halves (C % 4 == Cs % 4 == 0);
+//   interleave: channel 2 j = first_j, 2 j + 1 = second_j (C == Cs), as cat2_vec_kernel: the quad takes TWO channels of
+//               each half (8-byte loads).
+// Work split and summation order are those of moments_kernel<4> over the written tensor (moments_plan: chunk x sample x
+// channel block; thread (tx = quad, ty = row phase) adds its rows in ascending order in fp64, ty = 0 adds the phases in
+// ascending order), so the statistics have the bits of a moments pass over `cat`:
+//   stats 1: per-(sample, channel) (sum, sum of squares) chunk partials in the moments layout (moments_reduce finishes them);
+//   stats 2: one (sum, sum of squares) pair per workgroup, the moments kernel's total_only form, as gn_apply_fwd consumes.
+// (oy, ox) of a thread's pixel advance incrementally: one 32-bit division per thread, none per element.
+template <int IL>
+__global__ __launch_bounds__(256) void bn_relu_upsample_cat_kernel(const float* __restrict__ z, long ldz, const float* bnA,
+                                                                   const float* bnD, const float* bnS,
+                                                                   const float* __restrict__ skip, long lds,
+                                                                   float* __restrict__ cat, long ldc, int H, int W, int C,
+                                                                   int Cs, int OH, int OW, int up_first, int stats, int TPR,
+                                                                   int rows_per_chunk, int nchunks, double* partial) {
+  extern __shared__ double sm[];   // [256][8]
+  const float ry = up_ratio(H, OH), rx = up_ratio(W, OW);
+  const int tid = threadIdx.x;
+  const int tx = tid % TPR, ty = tid / TPR, RP = 256 / TPR;
+  const int chunk = blockIdx.x, b = blockIdx.y;
+  const int Ct = C + Cs, CV = Ct >> 2;
+  const int cv = blockIdx.z * TPR + tx;
+  const int HW = OH * OW;
+  const int r0 = chunk * rows_per_chunk, r1 = min(HW, r0 + rows_per_chunk);
+  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+  if (cv < CV && r0 + ty < r1) {
+    // first channel of this thread in the interpolated map (-1: none) and in the skip map (-1: none)
+    int uc, sc;
+    if (IL) {
+      uc = sc = 2 * cv;
     } else {
-      c = e % C;
-      long q = e / C;
-      ix = q % W; q /= W;
-      iy = q % H;
-      b = q / H;
+      const int first = up_first ? C : Cs;
+      const bool in_first = 4 * cv < first;
+      const bool is_up = in_first == (up_first != 0);
+      uc = is_up ? 4 * cv - (in_first ? 0 : first) : -1;
+      sc = is_up ? -1 : 4 * cv - (in_first ? 0 : first);
     }
-    int oy_lo = 0, oy_hi = OH - 1, ox_lo = 0, ox_hi = OW - 1;
-    if (ry > 0.f) {
-      oy_lo = max(0, (int)floorf((float)(iy - 1) / ry) - 1);
-      oy_hi = min(OH - 1, (int)ceilf((float)(iy + 1) / ry) + 1);
-    }
-    if (rx > 0.f) {
-      ox_lo = max(0, (int)floorf((float)(ix - 1) / rx) - 1);
-      ox_hi = min(OW - 1, (int)ceilf((float)(ix + 1) / rx) + 1);
-    }
-    float s = 0.f;
-    // the column weights do not depend on oy: found once (round 4; they were re-derived for every (oy, ox) pair -- 121 times
-    // per element at scale 4); the terms and their order are unchanged
-    constexpr int MAXR = 16;
-    const int nx = ox_hi - ox_lo + 1;
-    float wxs[MAXR];
-    if (nx <= MAXR) {
+    const bool bn = bnA != nullptr;
+    float fa[4], fd[4], fs[4];
 #pragma unroll
-      for (int t = 0; t < MAXR; ++t) {
-        int x0, x1;
-        float lx;
-        src_index(rx, min(ox_lo + t, OW - 1), W, &x0, &x1, &lx);
-        wxs[t] = t < nx ? (x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f) : 0.f;
-      }
+    for (int j = 0; j < 4; ++j) {
+      const bool has = bn && uc >= 0 && j < (IL ? 2 : 4);
+      fa[j] = has ? bnA[uc + j] : 0.f;
+      fd[j] = has ? bnD[uc + j] : 0.f;
+      fs[j] = has ? bnS[uc + j] : 0.f;
     }
-    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-      int y0, y1;
-      float ly;
-      src_index(ry, oy, H, &y0, &y1, &ly);
-      const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
-      if (wy == 0.f) continue;
-      if (nx <= MAXR) {
-        const float* grow = dy_nchw ? dy + ((b * C + c) * OH + oy) * (long)OW + ox_lo : dy + ((b * OH + oy) * (long)OW + ox_lo) * lddy + c;
-        const long gstep = dy_nchw ? 1 : lddy;
-#pragma unroll
-        for (int t = 0; t < MAXR; ++t) {
-          const float wx = wxs[t];
-          if (wx == 0.f) continue;
-          s += wy * wx * grow[t * gstep];
-        }
-        continue;
+    const float* zb = z + (long)b * H * W * ldz + max(uc, 0);
+    const float* sb = skip + (long)b * HW * lds + max(sc, 0);
+    float* cb = cat + (long)b * HW * ldc + 4 * cv;
+    int r = r0 + ty;
+    int oy = r / OW, ox = r - oy * OW;
+    const int dqy = RP / OW, dqx = RP - dqy * OW;         // a step of RP pixels
+    int yrow = -1, y0 = 0, y1 = 0;
+    float ly = 0.f;
+    for (; r < r1; r += RP) {
+      if (oy != yrow) {
+        src_index(ry, oy, H, &y0, &y1, &ly);
+        yrow = oy;
       }
-      for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+      f32x4 o;
+      if (IL || uc >= 0) {
         int x0, x1;
         float lx;
         src_index(rx, ox, W, &x0, &x1, &lx);
-        const float wx = (x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f);
-        if (wx == 0.f) continue;
-        const float g = dy_nchw ? dy[((b * C + c) * OH + oy) * (long)OW + ox]
-                                : dy[((b * OH + oy) * (long)OW + ox) * lddy + c];
-        s += wy * wx * g;
+        const float* p0 = zb + (long)y0 * W * ldz;
+        const float* p1 = zb + (long)y1 * W * ldz;
+        if (IL) {
+          const float2 t00 = *reinterpret_cast<const float2*>(p0 + (long)x0 * ldz), t01 = *reinterpret_cast<const float2*>(p0 + (long)x1 * ldz);
+          const float2 t10 = *reinterpret_cast<const float2*>(p1 + (long)x0 * ldz), t11 = *reinterpret_cast<const float2*>(p1 + (long)x1 * ldz);
+          const float2 sk = *reinterpret_cast<const float2*>(sb + (long)r * lds);
+          const float u0 = up_blend(t00.x, t01.x, t10.x, t11.x, lx, ly, bn, fa[0], fd[0], fs[0]);
+          const float u1 = up_blend(t00.y, t01.y, t10.y, t11.y, lx, ly, bn, fa[1], fd[1], fs[1]);
+          if (up_first) { o[0] = u0; o[1] = sk.x; o[2] = u1; o[3] = sk.y; }
+          else { o[0] = sk.x; o[1] = u0; o[2] = sk.y; o[3] = u1; }
+        } else {
+          const f32x4 t00 = *reinterpret_cast<const f32x4*>(p0 + (long)x0 * ldz), t01 = *reinterpret_cast<const f32x4*>(p0 + (long)x1 * ldz);
+          const f32x4 t10 = *reinterpret_cast<const f32x4*>(p1 + (long)x0 * ldz), t11 = *reinterpret_cast<const f32x4*>(p1 + (long)x1 * ldz);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) o[j] = up_blend(t00[j], t01[j], t10[j], t11[j], lx, ly, bn, fa[j], fd[j], fs[j]);
+        }
+      } else {
+        o = *reinterpret_cast<const f32x4*>(sb + (long)r * lds);
+      }
+      *reinterpret_cast<f32x4*>(cb + (long)r * ldc) = o;
+      if (stats) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          s1[j] += (double)o[j];
+          s2[j] += (double)o[j] * (double)o[j];
+        }
+      }
+      ox += dqx;
+      oy += dqy;
+      if (ox >= OW) { ox -= OW; ++oy; }
+    }
+  }
+  if (stats == 0) return;
+  if (stats == 2) {       // as moments_kernel, total_only
+    double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { t1 += s1[j]; t2 += s2[j]; }
+    t1 = wave_sum(t1);
+    t2 = wave_sum(t2);
+    if ((tid & 63) == 0) { sm[2 * (tid >> 6)] = t1; sm[2 * (tid >> 6) + 1] = t2; }
+    __syncthreads();
+    if (tid < 2)
+      partial[(((long)b * nchunks + chunk) * gridDim.z + blockIdx.z) * 2 + tid] = sm[tid] + sm[2 + tid] + sm[4 + tid] + sm[6 + tid];
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    sm[(long)tid * 8 + j] = s1[j];
+    sm[(long)tid * 8 + 4 + j] = s2[j];
+  }
+  __syncthreads();
+  if (ty == 0 && cv < CV) {
+    for (int q = 1; q < RP; ++q) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        s1[j] += sm[(long)(q * TPR + tx) * 8 + j];
+        s2[j] += sm[(long)(q * TPR + tx) * 8 + 4 + j];
       }
     }
-    float* d = dx + ((b * H + iy) * (long)W + ix) * lddx + c;
-    *d = accumulate ? *d + s : s;
+    double* out = partial + (((long)b * nchunks + chunk) * Ct + (long)cv * 4) * 2;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      out[2 * j] = s1[j];
+      out[2 * j + 1] = s2[j];
+    }
   }
 }
 
@@ -1028,17 +1228,30 @@ extern "C" int vrnet_dwconv3x3_wgrad_f32(const float* x, long ldx, const float* 
   return VR_OK;
 }
 
+// grid of the line-per-workgroup kernels above: `segs` workgroups of 256 positions for each of `lines` lines of `per` positions
+static bool up_grid(long lines, long per, int* segs, unsigned* blocks) {
+  const long sg = vr_cdiv(per, 256), nb = lines * sg;
+  if (per >= (1L << 31) || nb >= (1L << 31)) return false;
+  *segs = (int)sg;
+  *blocks = (unsigned)nb;
+  return true;
+}
+
 static int upsample_launch(const float* x, long ldx, float* y, long ldy, int B, int H, int W, int C, int scale, int out_nchw,
                            const float* bnA, const float* bnD, const float* bnS, void* stream) {
-  if (!out_nchw && C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && vr_aligned16(x) && vr_aligned16(y))
-    hipLaunchKernelGGL(upsample_vec_kernel, dim3(grid_for((long)B * H * W * scale * scale * (C / 4))), dim3(256), 0,
-                       vr_stream(stream), x, ldx, y, ldy, B, H, W, C, H * scale, W * scale, bnA, bnD, bnS);
-  else if (out_nchw && (W * scale) % 4 == 0 && vr_aligned16(y))
-    hipLaunchKernelGGL(upsample_nchw4_kernel, dim3(grid_for((long)B * H * W * scale * scale * C / 4)), dim3(256), 0,
-                       vr_stream(stream), x, ldx, y, B, H, W, C, H * scale, W * scale, bnA, bnD, bnS);
+  const int OH = H * scale, OW = W * scale;
+  int segs;
+  unsigned blocks;
+  if (!out_nchw && C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && vr_aligned16(x) && vr_aligned16(y) &&
+      up_grid((long)B * OH, (long)OW * (C / 4), &segs, &blocks))
+    hipLaunchKernelGGL(upsample_vec_kernel, dim3(blocks), dim3(256), 0, vr_stream(stream), x, ldx, y, ldy, H, W, C, OH, OW, segs,
+                       bnA, bnD, bnS);
+  else if (out_nchw && OW % 4 == 0 && vr_aligned16(y) && up_grid((long)B * C, (long)OH * (OW / 4), &segs, &blocks))
+    hipLaunchKernelGGL(upsample_nchw4_kernel, dim3(blocks), dim3(256), 0, vr_stream(stream), x, ldx, y, H, W, C, OH, OW, segs,
+                       scale >= 2 ? 1 : 0, bnA, bnD, bnS);
   else
     hipLaunchKernelGGL(upsample_kernel, dim3(grid_for((long)B * H * W * scale * scale * C)), dim3(256), 0,
-                       vr_stream(stream), x, ldx, y, ldy, B, H, W, C, H * scale, W * scale, out_nchw, bnA, bnD, bnS);
+                       vr_stream(stream), x, ldx, y, ldy, B, H, W, C, OH, OW, out_nchw, bnA, bnD, bnS);
   VR_LAUNCH_CHECK("upsample");
   return VR_OK;
 }
@@ -1061,17 +1274,89 @@ extern "C" int vrnet_bn_relu_upsample_bilinear_f32(const float* z, long ldz, con
   return upsample_launch(z, ldz, y, ldy, B, H, W, C, scale, out_nchw, A, D, S, stream);
 }
 
+static int upsample_bwd_launch(const float* dy, long lddy, int dy_nchw, int cs, int coff, float* dx, long lddx, int B, int H,
+                               int W, int C, int scale, int accumulate, void* stream) {
+  const int OH = H * scale, OW = W * scale;
+  int segs;
+  unsigned blocks;
+  // (cs == 2: the quads of the interleaved halves start at column 0 of the wide row; cs == 1: at coff)
+  if (!dy_nchw && C % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && vr_aligned16(dy) && vr_aligned16(dx) &&
+      (cs == 2 || coff % 4 == 0) && up_grid((long)B * H, (long)W * (C / 4), &segs, &blocks)) {
+    hipLaunchKernelGGL(upsample_bwd_vec_kernel, dim3(blocks), dim3(256), 0, vr_stream(stream), dy, lddy, cs, coff, dx, lddx, H, W,
+                       C, OH, OW, segs, accumulate);
+  } else {
+    const bool ok = dy_nchw ? up_grid((long)B * C, (long)H * W, &segs, &blocks) : up_grid((long)B * H, (long)W * C, &segs, &blocks);
+    VR_CHECK_ARG(ok, "upsample_bwd: map too large");
+    hipLaunchKernelGGL(upsample_bwd_kernel, dim3(blocks), dim3(256), 0, vr_stream(stream), dy, lddy, dy_nchw, cs, coff, dx, lddx,
+                       H, W, C, OH, OW, segs, accumulate);
+  }
+  VR_LAUNCH_CHECK("upsample_bwd");
+  return VR_OK;
+}
+
 extern "C" int vrnet_upsample_bilinear_bwd_f32(const float* dy, long lddy, int dy_nchw, float* dx, long lddx, int B,
                                                int H, int W, int C, int scale, int accumulate, void* stream) {
   if (vr_ablated("misc")) return VR_OK;
-  VR_CHECK_ARG(dy && dx && scale >= 1, "upsample_bwd: bad arguments");
-  if (!dy_nchw && C % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && vr_aligned16(dy) && vr_aligned16(dx))
-    hipLaunchKernelGGL(upsample_bwd_vec_kernel, dim3(grid_for((long)B * H * W * (C / 4), 256)), dim3(256), 0, vr_stream(stream),
-                       dy, lddy, dx, lddx, B, H, W, C, H * scale, W * scale, accumulate);
+  VR_CHECK_ARG(dy && dx && scale >= 1 && B > 0 && H > 0 && W > 0 && C > 0, "upsample_bwd: bad arguments");
+  return upsample_bwd_launch(dy, lddy, dy_nchw, 1, 0, dx, lddx, B, H, W, C, scale, accumulate, stream);
+}
+
+/* The adjoint read IN PLACE from the gradient of a concatenation (NHWC, row stride lddy): channel j of the upsampled map is
+ * column coff + cstride * j of dy -- cstride 1: a block of torch.cat; cstride 2, coff 0 / 1: a half of the 2-group channel
+ * shuffle.  Same terms in the same order as vrnet_upsample_bilinear_bwd_f32 on the half copied out. */
+extern "C" int vrnet_upsample_bilinear_bwd_cat_f32(const float* dy, long lddy, int coff, int cstride, float* dx, long lddx,
+                                                   int B, int H, int W, int C, int scale, int accumulate, void* stream) {
+  if (vr_ablated("misc")) return VR_OK;
+  VR_CHECK_ARG(dy && dx && scale >= 1 && B > 0 && H > 0 && W > 0 && C > 0, "upsample_bwd_cat: bad arguments");
+  VR_CHECK_ARG((cstride == 1 && coff >= 0) || (cstride == 2 && (coff == 0 || coff == 1)), "upsample_bwd_cat: channel map");
+  VR_CHECK_ARG(lddy >= coff + (long)cstride * (C - 1) + 1 && lddx >= C, "upsample_bwd_cat: row strides");
+  return upsample_bwd_launch(dy, lddy, 0, cstride, coff, dx, lddx, B, H, W, C, scale, accumulate, stream);
+}
+
+/* CoCUpsample's gather + torch.cat with `skip` (+ the 2-group channel shuffle) + the statistics of the result in one launch
+ * (bn_relu_upsample_cat_kernel).  vrnet_up_cat_ok: the shapes it takes; vrnet_up_cat_pairs: pairs per sample of stats = 2. */
+extern "C" int vrnet_up_cat_ok(int C, int Cs, long ldz, long lds, long ldc, int interleave) {
+  return C > 0 && Cs > 0 && C % 4 == 0 && Cs % 4 == 0 && ldz % 4 == 0 && lds % 4 == 0 && ldc % 4 == 0 && ldz >= C && lds >= Cs &&
+         ldc >= C + Cs && (!interleave || C == Cs);
+}
+extern "C" long vrnet_up_cat_pairs(int B, long HW, int Ct) {
+  int TPR, ncb, nchunks;
+  long rows;
+  vr_moments_plan4(B, HW, Ct, &TPR, &ncb, &nchunks, &rows);
+  return (long)nchunks * ncb;
+}
+extern "C" int vrnet_bn_relu_upsample_cat_f32(const float* z, long ldz, const float* A, const float* D, const float* S,
+                                              const float* skip, long lds, float* cat, long ldc, int B, int H, int W, int C,
+                                              int Cs, int scale, int up_first, int interleave, int stats, double* out,
+                                              void* workspace, long workspace_bytes, void* stream) {
+  VR_CHECK_ARG(z && skip && cat && scale >= 1 && B > 0 && H > 0 && W > 0, "bn_relu_upsample_cat: bad arguments");
+  VR_CHECK_ARG((!A && !D && !S) || (A && D && S), "bn_relu_upsample_cat: the BatchNorm coefficients come as three or not at all");
+  VR_CHECK_ARG(vrnet_up_cat_ok(C, Cs, ldz, lds, ldc, interleave) && vr_aligned16(z) && vr_aligned16(skip) && vr_aligned16(cat),
+               "bn_relu_upsample_cat: needs C %% 4 == Cs %% 4 == 0 (C == Cs with the shuffle) and 16-byte aligned rows");
+  VR_CHECK_ARG(stats >= 0 && stats <= 2 && (stats == 0 || out) && (stats != 1 || workspace), "bn_relu_upsample_cat: statistics");
+  const long HW = (long)H * scale * W * scale;
+  VR_CHECK_ARG(HW < (1L << 31), "bn_relu_upsample_cat: map too large");
+  const int Ct = C + Cs;
+  if (stats == 1 && workspace_bytes < vrnet_moments_workspace(B, HW, Ct)) {
+    vr_set_error("bn_relu_upsample_cat: workspace too small");
+    return VR_ERR_WORKSPACE;
+  }
+  if (vr_ablated("misc")) return VR_OK;
+  int TPR, ncb, nchunks;
+  long rows;
+  vr_moments_plan4(B, HW, Ct, &TPR, &ncb, &nchunks, &rows);
+  hipStream_t st = vr_stream(stream);
+  double* partial = stats == 1 ? reinterpret_cast<double*>(workspace) : out;
+  const dim3 grid(nchunks, B, ncb), block(256);
+  const size_t lds_bytes = 256 * 8 * sizeof(double);
+  if (interleave)
+    hipLaunchKernelGGL((bn_relu_upsample_cat_kernel<1>), grid, block, lds_bytes, st, z, ldz, A, D, S, skip, lds, cat, ldc, H, W, C,
+                       Cs, H * scale, W * scale, up_first, stats, TPR, (int)rows, nchunks, partial);
   else
-    hipLaunchKernelGGL(upsample_bwd_kernel, dim3(grid_for((long)B * H * W * C, 256)), dim3(256), 0, vr_stream(stream), dy,
-                       lddy, dy_nchw, dx, lddx, B, H, W, C, H * scale, W * scale, accumulate);
-  VR_LAUNCH_CHECK("upsample_bwd");
+    hipLaunchKernelGGL((bn_relu_upsample_cat_kernel<0>), grid, block, lds_bytes, st, z, ldz, A, D, S, skip, lds, cat, ldc, H, W, C,
+                       Cs, H * scale, W * scale, up_first, stats, TPR, (int)rows, nchunks, partial);
+  VR_LAUNCH_CHECK("bn_relu_upsample_cat");
+  if (stats == 1) return vr_moments_reduce(partial, out, B, nchunks, Ct, st);
   return VR_OK;
 }
 

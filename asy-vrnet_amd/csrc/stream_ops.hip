@@ -1007,6 +1007,17 @@ static int moments_plan(int B, long HW, int C, int vec, int* TPR, int* ncb, int*
 
 }  // namespace
 
+// for the kernels of other files that leave statistics in the moments kernel's layout and order (spatial.hip)
+void vr_moments_plan4(int B, long HW, int C, int* TPR, int* ncb, int* nchunks, long* rows) {
+  moments_plan(B, HW, C, 4, TPR, ncb, nchunks, rows);
+}
+int vr_moments_reduce(const double* partial, double* out, int B, int nchunks, int C, hipStream_t st) {
+  const long n = (long)B * C * 2;
+  hipLaunchKernelGGL(moments_reduce_kernel, dim3(vr_cdiv(n, 16)), dim3(256), 0, st, partial, out, B, nchunks, C);
+  VR_LAUNCH_CHECK("moments_reduce");
+  return VR_OK;
+}
+
 extern "C" long vrnet_moments_workspace(int B, long HW, int C) {
   int TPR, ncb, nchunks;
   long rows;

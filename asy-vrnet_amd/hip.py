@@ -103,6 +103,10 @@ _SIGS = {
     "vrnet_upsample_bilinear_f32": ([P, L, P, L, I, I, I, I, I, I, P], I),
     "vrnet_bn_relu_upsample_bilinear_f32": ([P, L, P, P, P, P, L, I, I, I, I, I, I, P], I),
     "vrnet_upsample_bilinear_bwd_f32": ([P, L, I, P, L, I, I, I, I, I, I, P], I),
+    "vrnet_up_cat_ok": ([I, I, L, L, L, I], I),
+    "vrnet_up_cat_pairs": ([I, L, I], L),
+    "vrnet_bn_relu_upsample_cat_f32": ([P, L, P, P, P, P, L, P, L, I, I, I, I, I, I, I, I, I, P, P, L, P], I),
+    "vrnet_upsample_bilinear_bwd_cat_f32": ([P, L, I, I, P, L, I, I, I, I, I, I, P], I),
     "vrnet_reduce_workspace": ([], L),
     "vrnet_minmax_f32": ([P, L, P, P, L, P], I),
     "vrnet_enhance_mul_f32": ([P, P, P, P, L, P], I),
@@ -718,6 +722,41 @@ def bn_relu_upsample(z, ldz, A, Dc, S, y, ldy, B, H, W, C, scale, out_nchw=0):
 def upsample_bwd(dy, lddy, dy_nchw, dx, lddx, B, H, W, C, scale, accumulate=0):
     _check(_lib.vrnet_upsample_bilinear_bwd_f32(ptr(dy), lddy, dy_nchw, ptr(dx), lddx, B, H, W, C, scale, accumulate,
                                                 stream()), "upsample_bwd")
+
+
+def upsample_bwd_cat(dy, lddy, coff, cstride, dx, lddx, B, H, W, C, scale, accumulate=0):
+    """upsample_bwd with its NHWC dy read in place from a concatenation's gradient: channel j at column coff + cstride * j."""
+    _check(_lib.vrnet_upsample_bilinear_bwd_cat_f32(ptr(dy), lddy, coff, cstride, ptr(dx), lddx, B, H, W, C, scale, accumulate,
+                                                    stream()), "upsample_bwd_cat")
+
+
+def up_cat_ok(C, Cs, ldz, lds, ldc, interleave, *tensors):
+    """Shapes bn_relu_upsample_cat takes: channel counts and row strides % 4 (equal widths with the shuffle), 16-byte aligned bases."""
+    return bool(_lib.vrnet_up_cat_ok(C, Cs, ldz, lds, ldc, int(interleave))) and all(t.data_ptr() % 16 == 0 for t in tensors)
+
+
+UP_CAT_NONE, UP_CAT_SA_SUMS, UP_CAT_GN_PAIRS = 0, 1, 2
+
+
+def bn_relu_upsample_cat(z, ldz, A, Dc, S, skip, lds, cat, ldc, B, H, W, C, Cs, scale, up_first, interleave, stats=UP_CAT_NONE):
+    """cat = torch.cat of upsample(ReLU(A (z - S) + Dc)) (A None: of upsample(z)) and skip, [up | skip] if up_first else
+    [skip | up], + the 2-group channel shuffle when interleave -- one launch, the interpolated map is never stored.
+    Returns None, the (B, C + Cs, 2) channel sums of cat (UP_CAT_SA_SUMS: what moments(cat) returns) or its per-sample
+    (pairs, pairs per sample) for gn_apply_fwd (UP_CAT_GN_PAIRS)."""
+    Ct, HW = C + Cs, H * scale * W * scale
+    out, res, ws, nws = None, None, None, 0
+    if stats == UP_CAT_SA_SUMS:
+        out = res = torch.empty((B, Ct, 2), dtype=torch.float64, device=z.device)
+        ws = _ws.get(_lib.vrnet_moments_workspace(B, HW, Ct), z.device)
+        nws = ws.numel()
+    elif stats == UP_CAT_GN_PAIRS:
+        per = _lib.vrnet_up_cat_pairs(B, HW, Ct)
+        out = torch.empty((B, per, 2), dtype=torch.float64, device=z.device)
+        res = (out, per)
+    _check(_lib.vrnet_bn_relu_upsample_cat_f32(ptr(z), ldz, ptr(A), ptr(Dc), ptr(S), ptr(skip), lds, ptr(cat), ldc, B, H, W, C, Cs,
+                                               scale, int(up_first), int(interleave), stats, ptr(out), ptr(ws), nws, stream()),
+           "bn_relu_upsample_cat")
+    return res
 
 
 def minmax(p, n, mm):

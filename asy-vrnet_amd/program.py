@@ -115,6 +115,7 @@ class RT:
         self.mlp_recompute = "auto"  # fused Mlp backward recomputes the pre-activation instead of reading a stored one
         self.fused_fusion = True    # the fused passes of csrc/fusion.hip in the fusion blocks
         self.fused_upsample = True  # CoCUpsample: BatchNorm + ReLU applied on the taps of the bilinear gather (K11)
+        self.fused_up_cat = True    # ... which also writes the neck's concatenation with the skip map and leaves its statistics
         self.early_wgrads = 2       # 1 = behind every section: measured (round 5, same call): 25.87-26.06 ms with it against 25.75-25.92 without -- the weight
                                     # gradients then contend with the small kernels of the critical chain they were meant to fill
         self.stamps = None          # diagnostic: (int64 buffer, [names]) -- rt.stamp(name) writes the device clock in stream order
@@ -1474,14 +1475,16 @@ def image_enhance(rt, x, r, m, out=None):
     return y
 
 
-def shuffle_attention(rt, x, m, defer_apply=False):
+def shuffle_attention(rt, x, m, defer_apply=False, mom=None):
     """ShuffleAttention.forward (shuffle_attention.py:48-72) on a contiguous map.
+    mom: the (B, C, 2) channel sums of x when a fused producer already has them (as in eca).
     defer_apply: only the gate coefficients are computed; the returned Act has NO tensor (a shape and a gradient slot) and
     carries the coefficients as `.sa = (P, Q, Mn)` -- the caller's fused kernel (hip.sa_cat_sums) applies the gate while it
     writes the consumer's tensor.  The backward closure is the same either way (it never reads the output)."""
     B, HW, C, G = x.B, x.HW, x.C, m.G
     params = [t.reshape(-1) for t in (m.cweight, m.cbias, m.sweight, m.sbias, m.gn.weight, m.gn.bias)]
-    mom = hip.moments(x.t, x.ld, B, HW, C)
+    if mom is None:
+        mom = hip.moments(x.t, x.ld, B, HW, C)
     P, Q, Mn = rt.buf(B, C), rt.buf(B, C), rt.buf(B, C)
     hip.sa_coef_fwd(mom, *params, B, HW, C, G, P, Q, Mn)
     if defer_apply:
@@ -1642,11 +1645,18 @@ def radar_enhance(rt, x, r, m, out=None):
 
 
 # ----------------------------------------------------------------------------------------- neck pieces
-def coc_upsample(rt, x, m, nchw_out=None):
-    """CoCUpsample.forward (coc_fpn_dual.py:24-26): BaseConv 1x1 -> bilinear, align_corners=True."""
+def _fused_upsample_ok(rt, bc):
+    """CoCUpsample with BatchNorm + ReLU on the taps of the gather: the one condition coc_upsample and up_cat both go by."""
+    return rt.fused_upsample and not bc.ds_conv and rt.relu_masks is None and rt.sync_bn is None
+
+
+def coc_upsample(rt, x, m, nchw_out=None, cat_with=None):
+    """CoCUpsample.forward (coc_fpn_dual.py:24-26): BaseConv 1x1 -> bilinear, align_corners=True.
+    cat_with = (skip, up_first, interleave, stats) (up_cat below, on the fused path only): the gather writes the concatenation
+    with `skip` itself; returns (the concatenated Act, the statistics hip.bn_relu_upsample_cat left)."""
     bc = m.upsample[0]
     s = m.scale
-    if rt.fused_upsample and not bc.ds_conv and rt.relu_masks is None and rt.sync_bn is None:
+    if _fused_upsample_ok(rt, bc):
         # (round 5, K11) conv -> [BatchNorm + ReLU on the taps of the bilinear gather]: the low-resolution activation is never
         # stored (the backward needs z and the forward coefficients only: the ReLU mask is recomputed from them)
         conv, bn = bc.conv, bc.bn
@@ -1656,6 +1666,8 @@ def coc_upsample(rt, x, m, nchw_out=None):
         cA, cD, cS, ms = bn_fwd_coef(rt, z, bn)
         ms.fwd_coef = (cA, cD, cS)
         B, H, W, C = z.B, z.H, z.W, co
+        if cat_with is not None:
+            return _up_cat_fused(rt, x, conv, bn, z, ms, (cA, cD, cS), s, *cat_with)
         to_nchw = nchw_out is not None      # (the closure below must not capture the output tensor itself: output -> autograd
         hi = None if to_nchw else rt.new(B, H * s, W * s, C)      #  node -> tape -> closure -> output would be a cycle)
         if to_nchw:
@@ -1676,6 +1688,7 @@ def coc_upsample(rt, x, m, nchw_out=None):
             conv_backward(rt, x, conv, dz, co)
         rt.push(bwd_fused)
         return z if to_nchw else hi
+    assert cat_with is None      # (up_cat asks for the concatenation only under _fused_upsample_ok)
     lo = base_conv(rt, x, bc)
     B, H, W, C = lo.B, lo.H, lo.W, lo.C
     if nchw_out is not None:
@@ -1700,6 +1713,61 @@ def coc_upsample(rt, x, m, nchw_out=None):
         hip.upsample_bwd(g, C, 0, buf, C, B, H, W, C, s, accumulate=acc)
     rt.push(bwd)
     return hi
+
+
+def _up_cat_ok(rt, m, skip, interleave):
+    """The fused CoCUpsample's condition, and shapes the gather + concat kernel takes (its conv output and the concatenation are
+    fresh contiguous buffers of C and C + Cs columns: with C % 4 == Cs % 4 == 0 their rows are 16-byte aligned)."""
+    bc = m.upsample[0]
+    C, Cs = bc.conv.out_channels, skip.C
+    return rt.fused_up_cat and _fused_upsample_ok(rt, bc) and hip.up_cat_ok(C, Cs, C, skip.ld, C + Cs, interleave, skip.t)
+
+
+def _up_cat_fused(rt, x, conv, bn, z, ms, coef, s, skip, up_first, interleave, stats):
+    """conv -> [BatchNorm + ReLU on the taps, bilinear gather, torch.cat with `skip` (+ channel shuffle), statistics of the
+    result]: ONE launch behind the conv (csrc/spatial.hip, bn_relu_upsample_cat_kernel) where bn_relu_upsample, cat2 and the
+    consumer's statistics pass were three to five; the interpolated map is never stored, and its gradient neither: the adjoint
+    gather reads its half of the concatenation's gradient in place."""
+    B, H, W, C, Cs = z.B, z.H, z.W, z.C, skip.C
+    Ct = C + Cs
+    il = bool(interleave)
+    cat = rt.new(B, H * s, W * s, Ct)
+    res = hip.bn_relu_upsample_cat(z.t, C, *coef, skip.t, skip.ld, cat.t, Ct, B, H, W, C, Cs, s, up_first, il, stats)
+    if il:
+        coff, cs = (0 if up_first else 1), 2
+    else:
+        coff, cs = (0 if up_first else Cs), 1
+
+    def bwd_up_cat():
+        g = take_grad(cat)
+        if g is None:
+            return
+        if skip.need_grad:                                      # the skip half: cat2's adjoint with the other half absent
+            bs, accs = rt.grad_target(skip)
+            if up_first:
+                hip.cat2(None, C, C, bs, Cs, Cs, g, Ct, cat.rows, il, dir=1, accumulate_b=accs)
+            else:
+                hip.cat2(bs, Cs, Cs, None, C, C, g, Ct, cat.rows, il, dir=1, accumulate_a=accs)
+        dlo = rt.buf(B, H, W, C)
+        hip.upsample_bwd_cat(g, Ct, coff, cs, dlo, C, B, H, W, C, s)
+        dz = bn_backward(rt, bn, z, ms, dlo, C, mask=z)      # (mask: only "there is a ReLU" on this path)
+        conv_backward(rt, x, conv, dz, C)
+    rt.push(bwd_up_cat)
+    return cat, res
+
+
+def up_cat(rt, x, m, skip, up_first, interleave, stats=hip.UP_CAT_NONE):
+    """cat2 of CoCUpsample(x) and `skip` ([up | skip] if up_first), as the up-path levels of the neck use it.  Returns (the
+    concatenated Act, statistics): hip.UP_CAT_SA_SUMS -> its channel sums for the ShuffleAttention behind it;
+    hip.UP_CAT_GN_PAIRS -> set as `.pairs` for the GroupNorm behind it (both None when the fused kernel does not apply: the
+    consumer then makes its own pass, as before)."""
+    if _up_cat_ok(rt, m, skip, interleave):
+        cat, res = coc_upsample(rt, x, m, cat_with=(skip, up_first, interleave, stats))
+        if stats == hip.UP_CAT_GN_PAIRS:
+            cat.pairs, res = res, None
+        return cat, res
+    up = coc_upsample(rt, x, m)
+    return (cat2(rt, up, skip, interleave) if up_first else cat2(rt, skip, up, interleave)), None
 
 
 def coc_conv(rt, x, m, name=None):
@@ -1945,17 +2013,20 @@ def neck_forward(rt, nk, x, r, seg_out):
 
     def seg_branch():        # image-stream features only (coc_fpn_dual.py:193-209)
         a5 = aspp(rt, x5, nk.aspp)
-        t = shuffle_attention(rt, cat2(rt, x4, coc_upsample(rt, a5, nk.upsample5_4), True), nk.sc_attn_seg4)
-        t = shuffle_attention(rt, cat2(rt, coc_upsample(rt, t, nk.upsample4_3), x3, True), nk.sc_attn_seg3)
-        t = shuffle_attention(rt, cat2(rt, coc_upsample(rt, t, nk.upsample3_2), x2, True), nk.sc_attn_seg2)
+        def level(lo, up, skip, up_first, attn):      # (the gather leaves the channel sums the attention starts from)
+            cat, mom = up_cat(rt, lo, up, skip, up_first, True, hip.UP_CAT_SA_SUMS)
+            return shuffle_attention(rt, cat, attn, mom=mom)
+        t = level(a5, nk.upsample5_4, x4, False, nk.sc_attn_seg4)
+        t = level(t, nk.upsample4_3, x3, True, nk.sc_attn_seg3)
+        t = level(t, nk.upsample3_2, x2, True, nk.sc_attn_seg2)
         return coc_upsample(rt, t, nk.upsample2_0, nchw_out=seg_out)
 
     def det_branch():        # radar-stream features only (coc_fpn_dual.py:213-221)
         r5_ = radar_enhance(rt, *r5) if isinstance(r5, tuple) else r5      # (deferred by _backbone_overlapped)
         p5 = coc_conv(rt, r5_, nk.p5_out_det, "backbone.p5_out_det.coc.token_mixer")
-        p4 = coc_conv(rt, cat2(rt, r4, coc_upsample(rt, p5, nk.p5_4_det), False), nk.p4_out_det,
+        p4 = coc_conv(rt, up_cat(rt, p5, nk.p5_4_det, r4, False, False, hip.UP_CAT_GN_PAIRS)[0], nk.p4_out_det,
                       "backbone.p4_out_det.coc.token_mixer")
-        p3 = coc_conv(rt, cat2(rt, r3, coc_upsample(rt, p4, nk.p4_3_det), False), nk.p3_out_det,
+        p3 = coc_conv(rt, up_cat(rt, p4, nk.p4_3_det, r3, False, False, hip.UP_CAT_GN_PAIRS)[0], nk.p3_out_det,
                       "backbone.p3_out_det.coc.token_mixer")
         return (p3, p4, p5)
     seg_lo, feats = rt.parallel([seg_branch, det_branch], site=4)
@@ -2177,6 +2248,7 @@ def forward_pass(model, x, x_radar, record, need_dx=False, need_dr=False):
         rt.early_wgrads = int(getattr(model, "early_wgrads", 2))
         rt.fused_fusion = bool(getattr(model, "fused_fusion", True))
         rt.fused_upsample = bool(getattr(model, "fused_upsample", True))
+        rt.fused_up_cat = bool(getattr(model, "fused_up_cat", True))
         rt.mlp_recompute = getattr(model, "mlp_recompute", "auto")
         rt.overlap_fusion = bool(getattr(model, "overlap_fusion", True))     # RadarEnhanceByImage beside the image chain (round 5)
         rt.fused_mlp = bool(getattr(model, "fused_mlp", True))

@@ -460,6 +460,25 @@ int vrnet_bn_relu_upsample_bilinear_f32(const float* z, long ldz, const float* A
                                         long ldy, int B, int H, int W, int C, int scale, int out_nchw, void* stream);
 int vrnet_upsample_bilinear_bwd_f32(const float* dy, long lddy, int dy_nchw, float* dx, long lddx, int B, int H, int W,
                                     int C, int scale, int accumulate, void* stream);
+/* ---- the neck's up-path levels in one gather (csrc/spatial.hip) -- added within ABI 11: new symbols only.
+ * vrnet_bn_relu_upsample_cat_f32, coc_fpn_dual.py:193-221: cat (B, sH, sW, C + Cs; row stride ldc) = torch.cat of the map
+ *   vrnet_bn_relu_upsample_bilinear_f32 would write (A == D == S == NULL: of vrnet_upsample_bilinear_f32) and skip (B, sH, sW, Cs;
+ *   row stride lds): [up | skip] if up_first, else [skip | up]; interleave (C == Cs): + the 2-group channel shuffle (column 2 j =
+ *   first half's channel j, 2 j + 1 = second half's), the order of vrnet_cat2_f32.  The interpolated map is never stored; cat has
+ *   the bits of the two calls.  Needs vrnet_up_cat_ok (C % 4 == Cs % 4 == 0, row strides % 4 == 0) and 16-byte aligned bases.
+ *   stats 0: none.  stats 1: out (B, C + Cs, 2) fp64 = per-(sample, channel) (sum, sum of squares) of cat with the bits of
+ *   vrnet_moments_f32 on it; workspace: vrnet_moments_workspace(B, sH sW, C + Cs).  stats 2: out (B, per, 2) fp64 = per-sample
+ *   (sum, sum of squares) pairs, per = vrnet_up_cat_pairs(B, sH sW, C + Cs), the `pairs` of vrnet_gn_apply_fwd.  Fixed
+ *   summation order, no atomics.
+ * vrnet_upsample_bilinear_bwd_cat_f32: vrnet_upsample_bilinear_bwd_f32 reading its NHWC dy in place from the gradient of such a
+ *   concatenation (row stride lddy): channel j at column coff + cstride j (cstride 1, or 2 with coff 0 / 1 for the shuffle). */
+int vrnet_up_cat_ok(int C, int Cs, long ldz, long lds, long ldc, int interleave);
+long vrnet_up_cat_pairs(int B, long HW, int Ct);
+int vrnet_bn_relu_upsample_cat_f32(const float* z, long ldz, const float* A, const float* D, const float* S, const float* skip,
+                                   long lds, float* cat, long ldc, int B, int H, int W, int C, int Cs, int scale, int up_first,
+                                   int interleave, int stats, double* out, void* workspace, long workspace_bytes, void* stream);
+int vrnet_upsample_bilinear_bwd_cat_f32(const float* dy, long lddy, int coff, int cstride, float* dx, long lddx, int B, int H,
+                                        int W, int C, int scale, int accumulate, void* stream);
 
 /* ---- ImageEnhanceByRadar gain (vr_coc.py:312-316) with data_normal (:59-67): batch-global min/max of the
  * ReLU'd radar projection p (contiguous, n elements), out = (1 + (p-min)/(max-min)) * x, and the backward
