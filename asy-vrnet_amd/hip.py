@@ -132,7 +132,8 @@ _SIGS = {
     "vrnet_nms_segmented_f32": ([P, I, P, P, P, P, I, L, I, D, P, L, P, P, P, P], I),
     "vrnet_nms_capped_f32": ([P, I, P, P, P, P, I, L, I, D, P, L, P, P, P, P, P], I),
     "vrnet_detect_finish_f32": ([P, P, I, I, I, I, I, D, D, D, D, P, P, P, P, P, P], I),
-    "vrnet_batch_formats_u8": ([P, P, I, I, I, I, P, P, P, P], I),
+    "vrnet_eval_append_f32": ([P, P, I, I, P, P, I, P, I, I, P, P, P, P, P, P, P, P, P], I),
+    "vrnet_batch_formats_u8":([P, P, I, I, I, I, P, P, P, P], I),
     "vrnet_radar_workspace_bytes": ([I], L),
     "vrnet_radar_normalise": ([P, I, I, L, I, P, P, L, P], I),
     "vrnet_letterbox_workspace": ([I, I, I, I, I], L),
@@ -881,6 +882,33 @@ def detect_finish(rows, kept, num_classes, image_shape, offset, scale, rows_out,
     _check(_lib.vrnet_detect_finish_f32(ptr(rows), ptr(kept), B, cap, int(num_classes), int(image_shape[0]), int(image_shape[1]),
                                         float(offset[0]), float(offset[1]), float(scale[0]), float(scale[1]), ptr(rows_out),
                                         ptr(draw_rows), ptr(offsets), ptr(det_counts), ptr(flag), stream()), "detect_finish")
+
+
+def eval_append(rows, kept, gt, gt_count, cursor, arena, flag):
+    """One batch of kept rows and ground truths -> the record arena of a validation pass, at the image slots cursor ..
+    cursor + B - 1 (vrnet_eval_append_f32).  rows (B, cap, 7) / kept (B): `detect_finish`'s rows_out / kept; gt (B, max_gt, 5)
+    int32 with gt_count (B); cursor (1) int32; arena: a dict of det_label (N, max_boxes) int32, det_score (N, max_boxes)
+    float64, det_box (N, max_boxes, 4) float64, det_count (N) int32, gt_label (N, max_gt) int32, gt_box (N, max_gt, 4)
+    float64, gt_n (N) int32; flag (1) int32 receives bits 32 (no room: nothing written), 64 (gt_count > max_gt), 128 (a
+    value int() cannot take)."""
+    B, cap = rows.shape[:2]
+    max_gt = gt.shape[1] if gt.dim() == 3 else -1
+    N, max_boxes = arena["det_label"].shape if arena["det_label"].dim() == 2 else (-1, -1)
+    i32, f64 = torch.int32, torch.float64
+    for name, t, sh, dt in (("rows", rows, (B, cap, 7), torch.float32), ("kept", kept, (B,), i32), ("gt", gt, (B, max_gt, 5), i32),
+                            ("gt_count", gt_count, (B,), i32), ("cursor", cursor, (1,), i32), ("flag", flag, (1,), i32),
+                            ("det_label", arena["det_label"], (N, max_boxes), i32),
+                            ("det_score", arena["det_score"], (N, max_boxes), f64),
+                            ("det_box", arena["det_box"], (N, max_boxes, 4), f64), ("det_count", arena["det_count"], (N,), i32),
+                            ("gt_label", arena["gt_label"], (N, max_gt), i32), ("gt_box", arena["gt_box"], (N, max_gt, 4), f64),
+                            ("gt_n", arena["gt_n"], (N,), i32)):
+        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"eval_append: {name} must be a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} "
+                               f"{tuple(t.shape)}")
+    _check(_lib.vrnet_eval_append_f32(ptr(rows), ptr(kept), B, cap, ptr(gt), ptr(gt_count), max_gt, ptr(cursor), N, max_boxes,
+                                      ptr(arena["det_label"]), ptr(arena["det_score"]), ptr(arena["det_box"]),
+                                      ptr(arena["det_count"]), ptr(arena["gt_label"]), ptr(arena["gt_box"]), ptr(arena["gt_n"]),
+                                      ptr(flag), stream()), "eval_append")
 
 
 def radar_normalise(radar, out, normalise=True, ws=None):

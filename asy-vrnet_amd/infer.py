@@ -197,7 +197,13 @@ class FramePipeline:
                 self.frames_u8, class_map, (self._draw_rows, self._offsets), palette=self.seg_palette, mix_type=self.mix_type,
                 alpha=self.alpha, count=True, box_palette=self.box_palette, thickness=self.thickness, flag=self.flag,
                 device=self.device)
-        return FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
+        result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
+        self._tail(result)
+        return result
+
+    def _tail(self, result):
+        """Called last in the chain, inside the capture: nothing here; a subclass appends device work on the result
+        (evaluate.EvalPipeline)."""
 
     def _warm_up(self, passes, stream=None):
         """Runs the chain on the zeroed static buffers, on `stream` or the current one: the first pass sizes the NMS buffers

@@ -772,6 +772,30 @@ int vrnet_render_u8(const unsigned char* frames, const unsigned char* class_map,
                     const int* box_offsets, int n_rows, const unsigned char* box_palette, int n_box_colors, int thickness,
                     unsigned char* out, long long* counts, int* flag, void* stream);
 
+/* ---- the record arena of a validation pass (csrc/evalacc.hip) --------------------------------------------------------
+ * Added within ABI 11: a new symbol only.
+ * vrnet_eval_append_f32, utils/callbacks.py:151-170 (get_map_txt: the rows, scores and coordinates it writes per image)
+ *   and :207-220 (the ground-truth file of on_epoch_end), for the B images of one batch, appended at the image slots
+ *   *cursor .. *cursor + B - 1 of an arena of N slots; no host argument changes between the launches of a validation pass.
+ *   rows (B, cap, 7) fp32 / kept (B) int32 = rows_out / kept of vrnet_detect_finish_f32 (top, left, bottom, right, obj,
+ *   class_conf, class, in descending score order); gt (B, max_gt, 5) int32 = x1, y1, x2, y2, class with gt_count (B).
+ *   Image b, slot s = *cursor + b, rows k < n = min(kept[b], max_boxes, cap):
+ *     det_score (N, max_boxes) fp64 = float(str(score)[:6]) of score = obj * class_conf (one fp32 multiply): with
+ *       x = (double)score, k4 = rint(x * 1e4), it is k4 / 1e4 if (float)(k4 / 1e4) == score, else floor(x * 1e4) / 1e4
+ *       (exact for 1e-4 <= score <= 1, where numpy prints positionally);
+ *     det_box (N, max_boxes, 4) fp64 = left, top, right, bottom, each (double)(int)value, truncated toward zero; a
+ *       non-finite value or one outside int32 (Python raises there) is written as 0 and sets bit 128 of *flag;
+ *     det_label (N, max_boxes) int32 = (int)class, under the same rule; det_count (N) int32 = n.
+ *     Elements k >= n of a slot are not written.
+ *   gt_label (N, max_gt) int32, gt_box (N, max_gt, 4) fp64, gt_n (N) int32: the first min(gt_count[b], max_gt) ground
+ *   truths; gt_count[b] > max_gt sets bit 64.  If *cursor + B > N nothing is written, bit 32 is set and *cursor stays;
+ *   otherwise a one-thread launch behind the append adds B to *cursor.  No atomics on the records: every element has one
+ *   writer, the arena is bitwise the same on every run. */
+int vrnet_eval_append_f32(const float* rows, const int* kept, int B, int cap, const int* gt, const int* gt_count,
+                          int max_gt, int* cursor, int N, int max_boxes, int* det_label, double* det_score,
+                          double* det_box, int* det_count, int* gt_label, double* gt_box, int* gt_n, int* flag,
+                          void* stream);
+
 /* ---- training losses on the path's outputs: value + gradient w.r.t. the head outputs ------------
  * vrnet_yolo_loss_f32: YOLOLoss (nets/yolo_training.py:60-427): decode (:99-111), SimOTA assignment per image
  *   (get_assignments :200-264, get_in_boxes_info :291-368, dynamic_k_matching :370-427), IoU / objectness / class

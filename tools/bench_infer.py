@@ -17,11 +17,16 @@ size H x W resident on the device, three ways in alternating rounds (the minimum
 frames): the eager composition of the public calls (device_letterbox, the forward, decode_outputs, non_max_suppression with
 its two read-backs, seg_predict, render_frame with its upload of the box rows), infer.FramePipeline(graph=False) and
 infer.FramePipeline(graph=True), at the thresholds of the first --nms pair (default 0.5/0.4), with the candidate and kept
-counts of the frames.
+counts of the frames.  With --evaluate HxW[,HxW...] it times a validation pass of --steps batches of frames of each
+original size H x W resident on the device, two ways in alternating rounds (the minimum of three rounds each, on the same
+seeded frames, label maps and ground truths): evaluate.EvalPipeline.add per batch, and the per-image path that existed
+before it -- infer.FramePipeline(batch=1).run + metrics.DetectionEvaluator.add (one device-to-host copy per image) +
+metrics.fast_hist -- in images/s, at the thresholds of the first --nms pair (default 0.05/0.5, EvalCallback's), with the mAP
+and mIoU of both.
 
     python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
                                 [--seg 1080x1920,480x640] [--letterbox 1080x1920,480x640] [--render 1080x1920,480x640]
-                                [--pipeline 1080x1920]
+                                [--pipeline 1080x1920] [--evaluate 1080x1920]
 """
 import argparse
 import os
@@ -44,6 +49,7 @@ def main():
     ap.add_argument("--letterbox", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
     ap.add_argument("--render", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
     ap.add_argument("--pipeline", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920)")
+    ap.add_argument("--evaluate", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
     from asy_vrnet_amd.data import device_letterbox, resize_image
@@ -56,6 +62,7 @@ def main():
     frame_sizes = [tuple(int(v) for v in p.split("x")) for p in args.letterbox.split(",") if p]
     render_sizes = [tuple(int(v) for v in p.split("x")) for p in args.render.split(",") if p]
     pipeline_sizes = [tuple(int(v) for v in p.split("x")) for p in args.pipeline.split(",") if p]
+    evaluate_sizes = [tuple(int(v) for v in p.split("x")) for p in args.evaluate.split(",") if p]
 
     def timed(fn):
         for _ in range(3):
@@ -231,6 +238,57 @@ def main():
                   f"{ms['pipeline_captured']:.3f} ms ({ms['composition'] / ms['pipeline_captured']:.2f} x the composition, "
                   f"{bs / ms['pipeline_captured'] * 1e3:.1f} frames/s); candidates {pipes[True]._cand[4].tolist()} of capacity "
                   f"{pipes[True].cap}, kept {res.kept.tolist()}, flag {int(res.flag)}; rendered frames equal the composition's: {same}")
+
+        for ih, iw in evaluate_sizes:
+            import numpy as np
+            from asy_vrnet_amd.evaluate import EvalPipeline
+            from asy_vrnet_amd.metrics import DetectionEvaluator
+            conf, iou = pairs[0] if pairs else (0.05, 0.5)
+            ns, names, n_batches = model.num_seg_classes, [str(c) for c in range(model.num_classes)], args.steps
+            gen = torch.Generator().manual_seed(bs)
+            frames = torch.randint(0, 256, (bs, ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
+            labels = torch.randint(0, ns + 1, (bs, ih, iw), generator=gen, dtype=torch.uint8).to(dev)
+            rng = np.random.default_rng(bs)
+            x1, y1 = rng.integers(0, iw // 2, (bs, 4)), rng.integers(0, ih // 2, (bs, 4))
+            gts = [np.stack([x1[b], y1[b], x1[b] + iw // 4, y1[b] + ih // 4, rng.integers(0, model.num_classes, 4)], axis=1)
+                   for b in range(bs)]
+            batched = EvalPipeline(model, (ih, iw), S, names, ns, batch=bs, capacity=bs * n_batches, conf_thres=conf, nms_thres=iou)
+            single = FramePipeline(model, (ih, iw), S, batch=1, conf_thres=conf, nms_thres=iou, render=False)
+            ev, hist = DetectionEvaluator(names), torch.zeros((ns, ns), dtype=torch.int64, device=dev)
+
+            def captured_pass():
+                batched.reset()
+                for k in range(n_batches):
+                    batched.add([f"{k}_{b}" for b in range(bs)], frames, r, labels, gts)
+
+            def per_image_pass():                 # the path before EvalPipeline: one device-to-host copy per image
+                ev.reset()
+                hist.zero_()
+                for k in range(n_batches):
+                    for b in range(bs):
+                        res = single.run(frames[b:b + 1], r[b:b + 1])
+                        ev.add(f"{k}_{b}", res.detections()[0], gts[b])
+                        fast_hist(labels[b], res.class_map, ns, out=hist)
+
+            def seconds(fn):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
+
+            variants = {"captured": captured_pass, "per_image": per_image_pass}
+            rounds = {k: [] for k in variants}
+            for _ in range(3):                       # alternating rounds, so that a drift of the clock hits them alike
+                for k, fn in variants.items():
+                    rounds[k].append(seconds(fn))
+            sec, n_img = {k: min(v) for k, v in rounds.items()}, bs * n_batches
+            res = batched.compute(strict=False)
+            print(f"  + evaluate {ih}x{iw}, conf {conf} iou {iou}, bs={bs}, {n_img} images: EvalPipeline.add {n_img / sec['captured']:.1f} "
+                  f"images/s; per image (FramePipeline.run + DetectionEvaluator.add + fast_hist) {n_img / sec['per_image']:.1f} "
+                  f"images/s ({sec['per_image'] / sec['captured']:.2f} x); mAP {float(res.det.map):.6f} (per image "
+                  f"{float(ev.compute().map):.6f}), mIoU {res.miou:.6f}, flag {res.flag}; confusion matrices equal: "
+                  f"{bool((torch.from_numpy(res.hist).to(dev) == hist).all())}")
 
 
 def f_score_eager(x, target, beta=1, smooth=1e-5, threshold=0.5):
