@@ -919,8 +919,9 @@ static int cluster_fwd_impl(const float* f, const float* v, long ld, const float
   int T, npt;
   int rc = cluster_check("cluster_fwd", f, v, ld, B, H, W, E, D, fold, &T, &npt, 0);
   if (rc) return rc;
-  VR_CHECK_ARG((out || outp) && idx && alpha && beta && (!out || (ldo % 4 == 0 && vr_aligned16(out))) && vr_planes_out_ok(outp, E * D),
+  VR_CHECK_ARG((out || outp) && idx && alpha && beta && vr_planes_out_ok(outp, E * D),
                "cluster_fwd: bad output (the fp32 output may be NULL only with a plane output)");
+  VR_CHECK_ARG(!out || (ldo % 4 == 0 && vr_aligned16(out)), "cluster_fwd: rows must be 16-byte aligned");
   VR_CHECK_ARG(T != 0 || wgt, "cluster_fwd: regions of more than 256 points need the similarity map `wgt` (B,H,W,E)");
   VR_CHECK_ARG((!alpha2 == !beta2) && (!alpha2 || B % 2 == 0), "cluster_fwd: a two-stream launch needs alpha2, beta2 and an even batch");
   ClusterArgs p{};

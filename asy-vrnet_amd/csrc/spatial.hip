@@ -1154,6 +1154,7 @@ extern "C" int vrnet_dwconv3x3_f32(const float* x, long ldx, const float* w, flo
   if (vr_ablated("dwconv")) return VR_OK;
   VR_CHECK_ARG(x && w && y && B > 0 && H > 0 && W > 0 && C > 0, "dwconv3x3: bad arguments");
   VR_CHECK_ARG((long)B * H * W * C < (1L << 31), "dwconv3x3: tensor too large");
+  VR_CHECK_ARG(ldx >= C && ldy >= C, "dwconv3x3: row stride smaller than channel count");
   const bool vec = C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && ldx % 4 == 0 && ldy % 4 == 0 && vr_aligned16(x) &&
                    vr_aligned16(y) && vr_aligned16(w);
   static const int slide = vr_tune("VRNET_DW_SLIDE", 1);     // tuning aid

@@ -1141,6 +1141,8 @@ static int affine_impl(const float* x1, long ld1, const float* A, const float* D
   VR_CHECK_ARG(pre != 2 || masky, "affine: mask mode without mask tensor");
   VR_CHECK_ARG(pre != 3 || (mA && mD && mS && x2), "affine: recomputed-mask mode needs z (x2) and the forward coefficients");
   VR_CHECK_ARG(!(accumulate && add), "affine: accumulate (in place) and add (out of place) are exclusive");
+  VR_CHECK_ARG(ldo >= C && (!x1 || ld1 >= C) && (!x2 || ld2 >= C) && (pre != 2 || ldm >= C) && (!add || ldadd >= C),
+               "affine: row stride smaller than channel count");
   if (accumulate) { add = out; ldadd = ldo; }
   AffineArgs p{x1, ld1, A, D1, S1, masky, ldm, x2, ld2, E, D2, S2, out, ldo, HW, C, coef_bstride, pre, accumulate, add, ldadd,
                mA, mD, mS};

@@ -283,7 +283,10 @@ int vrnet_moments_f32(const float* x, long ldx, const float* x2, long ldx2, cons
  * indexed [b*coef_bstride + c] (0 = per channel, C = per sample and channel); NULL A/E = 1, NULL D1/D2/S1/S2 = 0,
  * NULL x1/x2 = term absent.  The shifts keep normalisation in torch's (x - mean) * scale order: the algebraically
  * equal A*x + (beta - mean*A) cancels catastrophically when |mean| >> std.  The apply step of GroupNorm / BatchNorm(+ReLU, + residual) forward AND backward,
- * ECA gating (eca.py:22), global-feature broadcast (coc_fpn_dual.py:96). */
+ * ECA gating (eca.py:22), global-feature broadcast (coc_fpn_dual.py:96).
+ * Every tensor that is read or written (out; x1, x2 if given; masky when pre == 2; add if given) needs a row stride >= C:
+ * a smaller one is refused ("affine: row stride smaller than channel count").  16-byte kernel when C % 4 == 0 and all of
+ * them have strides % 4 == 0 and 16-byte aligned bases, one float per access otherwise. */
 int vrnet_affine_f32(const float* x1, long ld1, const float* A, const float* D1, const float* S1, int pre,
                      const float* masky, long ldm, const float* x2, long ld2, const float* E, const float* D2,
                      const float* S2, long coef_bstride, float* out, long ldo, int B, long HW, int C, int accumulate,
@@ -414,7 +417,9 @@ int vrnet_fill_f32(float* dst, float value, long n, void* stream);
  * stage at 512 px) stay in registers; larger ones (neck p3 at 512 px, everything at 1024 px) use a streaming kernel.
  * idx: (B,H,W,E) u8 hard assignment (first maximum, as torch.max(dim)); wgt: (B,H,W,E) similarity of the
  * assigned centre (optional for regions of <= 256 points, required above).  alpha, beta: device scalars (sim_alpha, sim_beta, :148-149).
- * alpha2 / beta2 (NULL = none): two-stream launch, samples [B/2, B) belong to a second Cluster module. */
+ * alpha2 / beta2 (NULL = none): two-stream launch, samples [B/2, B) belong to a second Cluster module.
+ * There are 16-byte kernels only: ld, ldo (backward: lddo, lddf) % 4 == 0 and 16-byte aligned f, v, out (dout, df, dv), else
+ * the call is refused ("cluster_fwd: rows must be 16-byte aligned" / "cluster_bwd: ..."). */
 int vrnet_cluster_fwd_f32(const float* f, const float* v, long ld, const float* alpha, const float* beta,
                           float* out, long ldo, unsigned char* idx, float* wgt, int B, int H, int W, int E, int D,
                           int fold, const float* alpha2, const float* beta2, void* stream);
@@ -442,7 +447,8 @@ int vrnet_cluster_ab_reduce_multi(int n, const void* const* partial, const long*
                                   float* const* dbeta, const int* accumulate, void* stream);
 
 /* ---- depthwise 3x3, stride 1, pad 1 (DWConv.dconv, normal_conv.py:26-27; head towers decouplehead.py:23-34)
- * w: [C][3][3] (the OIHW tensor of a groups=C conv).  flip = 1 gives the input gradient. */
+ * w: [C][3][3] (the OIHW tensor of a groups=C conv).  flip = 1 gives the input gradient.  ldx, ldy >= C, else the call is
+ * refused ("dwconv3x3: row stride smaller than channel count"). */
 int vrnet_dwconv3x3_f32(const float* x, long ldx, const float* w, float* y, long ldy, int B, int H, int W, int C,
                         int flip, int accumulate, void* stream);
 long vrnet_dwconv3x3_wgrad_workspace(int B, int H, int W, int C);
