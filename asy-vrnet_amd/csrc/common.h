@@ -63,6 +63,48 @@ typedef struct vrnet_planes_out {
   int np;           /* 3: the fp32 value split exactly into three planes; 1: rounded to bf16 */
 } vrnet_planes_out;
 }
+extern "C" {
+/* include/vrnet_hip.h: the per-image geometry record of the ragged (mixed-size) entry points. */
+typedef struct vrnet_frame_geom {
+  int ih, iw;                                   /* the image's own size inside its (ihm, iwm) slot */
+  int nw, nh, dx, dy;                           /* data.letterbox_geometry: the letterbox window in the (H, W) canvas */
+  int seg_top, seg_left, seg_nh, seg_nw;        /* decode.seg_window */
+  int thickness;                                /* yolo.py:164 */
+  int reserved;                                 /* 0 */
+  double offset_y, offset_x, scale_y, scale_x;  /* infer.unmap_scalars */
+} vrnet_frame_geom;
+}
+#define VR_FLAG_GEOMETRY 256                    /* a record that had to be clamped; bits 1..128: render / nms / evalacc */
+
+__device__ __forceinline__ int vr_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Record b of the table, clamped so that no access derived from it leaves the image's slot (ihm x iwm) or the canvas
+// (H x W; H == 0: the entry point has no canvas and its window fields stay as they are).  bad: something was clamped.
+// b is the block's image index, so the loads are wave-uniform.
+__device__ __forceinline__ vrnet_frame_geom vr_geom_load(const vrnet_frame_geom* tab, int b, int ihm, int iwm, int H, int W,
+                                                          bool& bad) {
+  const vrnet_frame_geom t = tab[b];
+  vrnet_frame_geom g = t;
+  g.ih = vr_clampi(t.ih, 0, ihm);
+  g.iw = vr_clampi(t.iw, 0, iwm);
+  g.thickness = vr_clampi(t.thickness, 1, 1 << 24);
+  // an image without pixels is no legal record either: it stays empty (its slot is all padding) and is reported
+  bad = g.ih != t.ih || g.iw != t.iw || g.thickness != t.thickness || t.ih <= 0 || t.iw <= 0;
+  if (H > 0) {
+    g.nw = vr_clampi(t.nw, 0, W);
+    g.nh = vr_clampi(t.nh, 0, H);
+    g.dx = vr_clampi(t.dx, 0, W - g.nw);
+    g.dy = vr_clampi(t.dy, 0, H - g.nh);
+    g.seg_nw = vr_clampi(t.seg_nw, 0, W);
+    g.seg_nh = vr_clampi(t.seg_nh, 0, H);
+    g.seg_left = vr_clampi(t.seg_left, 0, W - g.seg_nw);
+    g.seg_top = vr_clampi(t.seg_top, 0, H - g.seg_nh);
+    bad = bad || g.nw != t.nw || g.nh != t.nh || g.dx != t.dx || g.dy != t.dy || g.seg_nw != t.seg_nw || g.seg_nh != t.seg_nh ||
+          g.seg_left != t.seg_left || g.seg_top != t.seg_top;
+  }
+  return g;
+}
+
 static inline bool vr_planes_out_ok(const vrnet_planes_out* o, int C) {
   return !o || (o->p && (o->np == 1 || o->np == 3) && o->ld >= C && o->ld % 4 == 0 && (o->np == 1 || o->plane % 4 == 0) &&
                 (reinterpret_cast<uintptr_t>(o->p) & 7) == 0);

@@ -57,7 +57,10 @@ __device__ void bicubic_taps(int xx, int in, int out, int cap, int* bounds, int*
   int xmax = (int)(center + support + 0.5);
   if (xmax > in) xmax = in;
   int n = xmax - xmin;
-  if (n > cap) n = cap;              // never taken: n <= 2 * support + 1 <= cap; keeps the stores inside the table
+  // keeps the stores inside the table.  Never taken from vrnet_letterbox_u8, whose cap is this axis's own ksize >= n; the
+  // ragged caller's cap is the pipeline's max_taps, which a wrong table can exceed: the taps are then truncated and the
+  // tables kernel reports FLAG_GEOMETRY
+  if (n > cap) n = cap;
   double ww = 0.0;
   for (int x = 0; x < n; ++x) ww += bicubic((x + xmin - center + 0.5) * ss);
   for (int x = 0; x < n; ++x) {
@@ -95,6 +98,19 @@ __global__ __launch_bounds__(256) void letterbox_tables_kernel(const LetterboxAr
 __device__ __forceinline__ unsigned char clip8(int acc) {
   acc >>= LB_PRECISION_BITS;
   return (unsigned char)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
+}
+
+// batch_formats_kernel's arithmetic: ((v / 255) - mean) / std in double, rounded once; pixel r of image b's CHW planes
+__device__ __forceinline__ void normalise_store(float* images, long b, long HW, long r, const unsigned char* v) {
+  const double mean[3] = {0.485, 0.456, 0.406}, sd[3] = {0.229, 0.224, 0.225};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double d = (double)v[c];
+    d /= 255.0;
+    d -= mean[c];
+    d /= sd[c];
+    images[(b * 3 + c) * HW + r] = (float)d;
+  }
 }
 
 __global__ __launch_bounds__(256) void letterbox_horizontal_kernel(const LetterboxArgs p) {
@@ -158,17 +174,7 @@ __global__ __launch_bounds__(256) void letterbox_vertical_paste_kernel(const Let
     p.canvas[e * 3 + 1] = v[1];
     p.canvas[e * 3 + 2] = v[2];
   }
-  if (p.images) {                    // batch_formats_kernel's arithmetic: ((v / 255) - mean) / std in double, rounded once
-    const double mean[3] = {0.485, 0.456, 0.406}, sd[3] = {0.229, 0.224, 0.225};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      double d = (double)v[c];
-      d /= 255.0;
-      d -= mean[c];
-      d /= sd[c];
-      p.images[(b * 3 + c) * HW + r] = (float)d;
-    }
-  }
+  if (p.images) normalise_store(p.images, b, HW, r, v);
   if (p.label_out) {
     unsigned char lab = 0;
     if (inside) {
@@ -180,7 +186,7 @@ __global__ __launch_bounds__(256) void letterbox_vertical_paste_kernel(const Let
 }
 
 // Resample.c precompute_coeffs: ksize, the tap capacity of one output index
-int lb_ksize(int in, int out) {
+__host__ __device__ int lb_ksize(int in, int out) {
   double fs = (double)in / out;
   if (fs < 1.0) fs = 1.0;
   return (int)ceil(2.0 * fs) * 2 + 1;
@@ -191,6 +197,150 @@ long lb_table_ints(int ih, int iw, int nh, int nw) {
 }
 
 long lb_align(long n) { return (n + 255) / 256 * 256; }
+
+// ---- the ragged form: frames of their own sizes in the corners of (ihm, iwm) slots, the geometry of image b in tab[b].
+// The same arithmetic (bicubic_taps, nearest_indices, clip8, normalise_store); the tables of image b live in slot b of the
+// workspace, sized by the canvas and the caller's tap capacity; blockIdx.y is the image, so a block reads one record.
+struct RaggedLetterboxArgs {
+  const unsigned char* img;          // (B, ihm, iwm, 3)
+  const unsigned char* label;        // (B, ihm, iwm) or null
+  const vrnet_frame_geom* tab;       // (B)
+  int B, ihm, iwm, H, W, cap;        // cap: taps per table entry
+  long slot;                         // ints of one image's tables
+  int* tables;
+  unsigned char* mid;                // (B, ihm, W, 3): the horizontal pass's result, rows of W pixels
+  unsigned char* canvas;             // (B, H, W, 3) or null
+  float* images;                     // (B, 3, H, W) or null
+  unsigned char* label_out;          // (B, H, W) or null
+  int* flag;                         // or null
+};
+
+struct RaggedTables {
+  int *hb, *hk, *vb, *vk, *xi, *yi;
+};
+
+__host__ __device__ inline long lb_ragged_slot_ints(int H, int W, int cap) { return ((long)W + H) * (3 + cap); }
+
+__device__ __forceinline__ RaggedTables ragged_tables(const RaggedLetterboxArgs& p, int b) {
+  RaggedTables s;
+  int* t = p.tables + b * p.slot;
+  s.hb = t; t += 2L * p.W;
+  s.hk = t; t += (long)p.W * p.cap;
+  s.vb = t; t += 2L * p.H;
+  s.vk = t; t += (long)p.H * p.cap;
+  s.xi = t; t += p.W;
+  s.yi = t;
+  return s;
+}
+
+// the record of this block's image; an image or window without pixels is `empty`: its canvas is all padding
+__device__ __forceinline__ vrnet_frame_geom ragged_geom(const RaggedLetterboxArgs& p, int b, bool& empty, bool& bad) {
+  const vrnet_frame_geom g = vr_geom_load(p.tab, b, p.ihm, p.iwm, p.H, p.W, bad);
+  empty = g.ih <= 0 || g.iw <= 0 || g.nw <= 0 || g.nh <= 0;
+  return g;
+}
+
+__global__ __launch_bounds__(256) void letterbox_ragged_tables_kernel(const RaggedLetterboxArgs p) {
+  const int b = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+  bool empty, bad;
+  const vrnet_frame_geom g = ragged_geom(p, b, empty, bad);
+  const bool pixels = p.canvas || p.images;
+  if (e == 0 && p.flag) {            // a clamped record, or taps beyond the slot's capacity (bicubic_taps then truncates them)
+    if (!empty && pixels)
+      bad = bad || (g.nw != g.iw && lb_ksize(g.iw, g.nw) > p.cap) || (g.nh != g.ih && lb_ksize(g.ih, g.nh) > p.cap);
+    if (bad) atomicOr(p.flag, VR_FLAG_GEOMETRY);
+  }
+  if (empty) return;
+  const RaggedTables s = ragged_tables(p, b);
+  if (e < p.W) {
+    if (e < g.nw && pixels && g.nw != g.iw) bicubic_taps(e, g.iw, g.nw, p.cap, s.hb, s.hk);
+  } else if (e < p.W + p.H) {
+    const int y = e - p.W;
+    if (y < g.nh && pixels && g.nh != g.ih) bicubic_taps(y, g.ih, g.nh, p.cap, s.vb, s.vk);
+  } else if (p.label_out) {
+    if (e == p.W + p.H) nearest_indices(g.iw, g.nw, s.xi);
+    if (e == p.W + p.H + 1) nearest_indices(g.ih, g.nh, s.yi);
+  }
+}
+
+__global__ __launch_bounds__(256) void letterbox_ragged_horizontal_kernel(const RaggedLetterboxArgs p) {
+  const int b = blockIdx.y;
+  bool empty, bad;
+  const vrnet_frame_geom g = ragged_geom(p, b, empty, bad);
+  if (empty || g.nw == g.iw) return;             // this image skips the pass, as Pillow does
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  const int row = (int)(e / p.W), xx = (int)(e - (long)row * p.W);
+  if (row >= g.ih || xx >= g.nw) return;
+  const RaggedTables s = ragged_tables(p, b);
+  const int xmin = s.hb[2 * xx], n = s.hb[2 * xx + 1];
+  const unsigned char* src = p.img + (((long)b * p.ihm + row) * p.iwm + xmin) * 3;
+  const int* k = s.hk + xx;
+  int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
+  for (int t = 0; t < n; ++t) {
+    const int w = k[(long)t * g.nw];
+    a0 += w * src[3 * t];
+    a1 += w * src[3 * t + 1];
+    a2 += w * src[3 * t + 2];
+  }
+  unsigned char* dst = p.mid + (((long)b * p.ihm + row) * p.W + xx) * 3;
+  dst[0] = clip8(a0);
+  dst[1] = clip8(a1);
+  dst[2] = clip8(a2);
+}
+
+__global__ __launch_bounds__(256) void letterbox_ragged_vertical_paste_kernel(const RaggedLetterboxArgs p) {
+  const long HW = (long)p.H * p.W;
+  const long b = blockIdx.y, r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= HW) return;
+  bool empty, bad;
+  const vrnet_frame_geom g = ragged_geom(p, (int)b, empty, bad);
+  const RaggedTables s = ragged_tables(p, (int)b);
+  const long e = b * HW + r;
+  const int y = (int)(r / p.W), x = (int)(r - (long)y * p.W);
+  const int wx = x - g.dx, wy = y - g.dy;
+  const bool inside = !empty && wx >= 0 && wx < g.nw && wy >= 0 && wy < g.nh;
+  unsigned char v[3] = {128, 128, 128};
+  if (inside && (p.canvas || p.images)) {
+    // the horizontal result: the workspace (rows of W pixels), or the frame's own slot when that pass was skipped
+    const bool resized = g.nw != g.iw;
+    const unsigned char* src = resized ? p.mid + (b * p.ihm * p.W + wx) * 3 : p.img + (b * p.ihm * p.iwm + wx) * 3;
+    const long rs = (resized ? (long)p.W : (long)p.iwm) * 3;
+    if (g.nh != g.ih) {
+      const int ymin = s.vb[2 * wy], n = s.vb[2 * wy + 1];
+      const int* k = s.vk + wy;
+      src += ymin * rs;
+      int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
+      for (int t = 0; t < n; ++t) {
+        const int w = k[(long)t * g.nh];
+        a0 += w * src[t * rs];
+        a1 += w * src[t * rs + 1];
+        a2 += w * src[t * rs + 2];
+      }
+      v[0] = clip8(a0);
+      v[1] = clip8(a1);
+      v[2] = clip8(a2);
+    } else {
+      src += wy * rs;
+      v[0] = src[0];
+      v[1] = src[1];
+      v[2] = src[2];
+    }
+  }
+  if (p.canvas) {
+    p.canvas[e * 3] = v[0];
+    p.canvas[e * 3 + 1] = v[1];
+    p.canvas[e * 3 + 2] = v[2];
+  }
+  if (p.images) normalise_store(p.images, b, HW, r, v);
+  if (p.label_out) {
+    unsigned char lab = 0;
+    if (inside) {
+      const int sx = s.xi[wx], sy = s.yi[wy];
+      if (sx >= 0 && sx < g.iw && sy >= 0 && sy < g.ih) lab = p.label[(b * p.ihm + sy) * p.iwm + sx];
+    }
+    p.label_out[e] = lab;
+  }
+}
 
 }  // namespace
 
@@ -238,5 +388,43 @@ extern "C" int vrnet_letterbox_u8(const unsigned char* img, const unsigned char*
     hipLaunchKernelGGL(letterbox_horizontal_kernel, dim3((unsigned)vr_cdiv((long)B * ih * nw, 256)), dim3(256), 0, st, p);
   hipLaunchKernelGGL(letterbox_vertical_paste_kernel, dim3((unsigned)vr_cdiv((long)B * H * W, 256)), dim3(256), 0, st, p);
   VR_LAUNCH_CHECK("letterbox");
+  return VR_OK;
+}
+
+extern "C" long vrnet_letterbox_ragged_workspace(int B, int ihm, int iwm, int H, int W, int max_taps) {
+  if (B <= 0 || ihm <= 0 || iwm <= 0 || H <= 0 || W <= 0 || max_taps <= 0) return 0;
+  return lb_align(B * lb_ragged_slot_ints(H, W, max_taps) * (long)sizeof(int)) + lb_align((long)B * ihm * W * 3);
+}
+
+extern "C" int vrnet_letterbox_ragged_u8(const unsigned char* img, const unsigned char* label, const vrnet_frame_geom* geom,
+                                         int B, int ihm, int iwm, int H, int W, int max_taps, unsigned char* canvas,
+                                         float* images, unsigned char* label_out, int* flag, void* workspace,
+                                         long workspace_bytes, void* stream) {
+  VR_CHECK_ARG(geom && B > 0 && B < 65536 && ihm > 0 && iwm > 0 && H > 0 && W > 0 && max_taps >= 5 && max_taps <= 4096,
+               "letterbox_ragged: bad shape (B %d, slots %d x %d, canvas %d x %d, max_taps %d)", B, ihm, iwm, H, W, max_taps);
+  VR_CHECK_ARG(canvas || images || label_out, "letterbox_ragged: no output requested");
+  VR_CHECK_ARG(img || !(canvas || images), "letterbox_ragged: an image output needs the frames");
+  VR_CHECK_ARG(label || !label_out, "letterbox_ragged: a label output needs the label maps");
+  VR_CHECK_ARG((long)B * ihm * iwm < (1L << 31) && (long)B * H * W < (1L << 31) && (long)B * ihm * W < (1L << 31) &&
+                   (long)B * lb_ragged_slot_ints(H, W, max_taps) < (1L << 31),
+               "letterbox_ragged: batch too large");
+  const long need = vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, max_taps);
+  if (!workspace || workspace_bytes < need) {
+    vr_set_error("letterbox_ragged: workspace %ld < %ld bytes", workspace ? workspace_bytes : 0L, need);
+    return VR_ERR_WORKSPACE;
+  }
+  RaggedLetterboxArgs p{};
+  p.img = img; p.label = label; p.tab = geom;
+  p.B = B; p.ihm = ihm; p.iwm = iwm; p.H = H; p.W = W; p.cap = max_taps;
+  p.slot = lb_ragged_slot_ints(H, W, max_taps);
+  p.tables = static_cast<int*>(workspace);
+  p.mid = static_cast<unsigned char*>(workspace) + lb_align(B * p.slot * (long)sizeof(int));
+  p.canvas = canvas; p.images = images; p.label_out = label_out; p.flag = flag;
+  hipStream_t st = vr_stream(stream);
+  hipLaunchKernelGGL(letterbox_ragged_tables_kernel, dim3((unsigned)vr_cdiv((long)W + H + 2, 256), B), dim3(256), 0, st, p);
+  if (canvas || images)
+    hipLaunchKernelGGL(letterbox_ragged_horizontal_kernel, dim3((unsigned)vr_cdiv((long)ihm * W, 256), B), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(letterbox_ragged_vertical_paste_kernel, dim3((unsigned)vr_cdiv((long)H * W, 256), B), dim3(256), 0, st, p);
+  VR_LAUNCH_CHECK("letterbox_ragged");
   return VR_OK;
 }

@@ -286,6 +286,8 @@ struct FinishArgs {
   int* offsets;                // (B + 1)
   unsigned long long* counts;  // (B, nc) zeroed by the caller
   int* flag;
+  const vrnet_frame_geom* tab; // RAGGED only: (B) records; ih, iw and the four scalars of image b come from tab[b],
+  int ihm, iwm;                // clamped to the slot ihm x iwm
 };
 
 // np.clip(np.floor(float64(v)), -2^31, 2^31 - 1).astype(int64) of render.box_rows
@@ -298,9 +300,20 @@ __device__ __forceinline__ int floor_clip(float v) {
 // One thread per (image, row slot).  The fp32 centre / size of decode.non_max_suppression, then decode.yolo_correct_boxes
 // in fp64 operation by operation (no contraction: the pragma above), one rounding to fp32 as the assignment into the
 // float32 array does; without a letterbox the caller passes offset 0 and scale 1, which change no bit.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void detect_finish_kernel(const FinishArgs p) {
   __shared__ int part[256];
   const int b = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+  int ih = p.ih, iw = p.iw;
+  double off_y = p.off_y, off_x = p.off_x, sc_y = p.sc_y, sc_x = p.sc_x, img_h = p.img_h, img_w = p.img_w;
+  if constexpr (RAGGED) {                             // the image's own record: the block's, so wave-uniform
+    bool bad;
+    const vrnet_frame_geom g = vr_geom_load(p.tab, b, p.ihm, p.iwm, 0, 0, bad);
+    if (bad && k == 0) atomicOr(p.flag, VR_FLAG_GEOMETRY);
+    ih = g.ih; iw = g.iw;
+    off_y = g.offset_y; off_x = g.offset_x; sc_y = g.scale_y; sc_x = g.scale_x;
+    img_h = (double)g.ih; img_w = (double)g.iw;
+  }
   int before = 0;                                     // kept rows of the images in front of this one
   for (int j = threadIdx.x; j < b; j += 256) before += min(max(p.kept[j], 0), p.cap);
   part[threadIdx.x] = before;
@@ -324,20 +337,20 @@ __global__ __launch_bounds__(256) void detect_finish_kernel(const FinishArgs p) 
   const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3];
   const float cx = (x1 + x2) / 2.0f, cy = (y1 + y2) / 2.0f, w = x2 - x1, h = y2 - y1;
   double c_y = (double)cy, c_x = (double)cx, s_y = (double)h, s_x = (double)w;
-  c_y = (c_y - p.off_y) * p.sc_y;
-  c_x = (c_x - p.off_x) * p.sc_x;
-  s_y = s_y * p.sc_y;
-  s_x = s_x * p.sc_x;
+  c_y = (c_y - off_y) * sc_y;
+  c_x = (c_x - off_x) * sc_x;
+  s_y = s_y * sc_y;
+  s_x = s_x * sc_x;
   const double hy = 0.5 * s_y, hx = 0.5 * s_x;
-  const float top = (float)((c_y - hy) * p.img_h), left = (float)((c_x - hx) * p.img_w);
-  const float bottom = (float)((c_y + hy) * p.img_h), right = (float)((c_x + hx) * p.img_w);
+  const float top = (float)((c_y - hy) * img_h), left = (float)((c_x - hx) * img_w);
+  const float bottom = (float)((c_y + hy) * img_h), right = (float)((c_x + hx) * img_w);
   o[0] = top; o[1] = left; o[2] = bottom; o[3] = right; o[4] = r[4]; o[5] = r[5]; o[6] = r[6];
   const int label = (int)r[6];
   int* d = p.draw + 5L * (base + k);
   d[0] = max(0, floor_clip(left));
   d[1] = max(0, floor_clip(top));
-  d[2] = min(p.iw, floor_clip(right));
-  d[3] = min(p.ih, floor_clip(bottom));
+  d[2] = min(iw, floor_clip(right));
+  d[3] = min(ih, floor_clip(bottom));
   d[4] = label;
   if (label >= 0 && label < p.nc) atomicAdd(p.counts + (long)b * p.nc + label, 1ull);
   else atomicOr(p.flag, NMS_FLAG_DET_CLASS);
@@ -435,7 +448,29 @@ extern "C" int vrnet_detect_finish_f32(const float* rows, const int* kept, int B
   p.off_y = offset_y; p.off_x = offset_x; p.sc_y = scale_y; p.sc_x = scale_x; p.img_h = (double)image_h; p.img_w = (double)image_w;
   p.out = rows_out; p.draw = draw_rows; p.offsets = offsets; p.counts = reinterpret_cast<unsigned long long*>(det_counts);
   p.flag = flag;
-  hipLaunchKernelGGL(detect_finish_kernel, dim3(vr_cdiv(cap, 256), B), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(detect_finish_kernel<false>, dim3(vr_cdiv(cap, 256), B), dim3(256), 0, st, p);
   VR_LAUNCH_CHECK("detect_finish");
+  return VR_OK;
+}
+
+extern "C" int vrnet_detect_finish_ragged_f32(const float* rows, const int* kept, const vrnet_frame_geom* geom, int B, int cap,
+                                              int num_classes, int ihm, int iwm, float* rows_out, int* draw_rows, int* offsets,
+                                              long long* det_counts, int* flag, void* stream) {
+  VR_CHECK_ARG(rows && kept && geom && rows_out && draw_rows && offsets && det_counts && flag && rows != rows_out,
+               "detect_finish_ragged: every array is required, rows_out apart from rows");
+  VR_CHECK_ARG(B > 0 && B < 65536 && cap > 0 && (long)B * cap < (1L << 27) && num_classes >= 1 && ihm > 0 && iwm > 0,
+               "detect_finish_ragged: bad shape (B %d, cap %d, %d classes, slots %d x %d)", B, cap, num_classes, ihm, iwm);
+  const hipStream_t st = vr_stream(stream);
+  if (hipMemsetAsync(draw_rows, 0, sizeof(int) * 5 * (size_t)B * cap, st) != hipSuccess ||
+      hipMemsetAsync(det_counts, 0, sizeof(long long) * (size_t)B * num_classes, st) != hipSuccess) {
+    vr_set_error("detect_finish_ragged: memset failed");
+    return VR_ERR_LAUNCH;
+  }
+  FinishArgs p{};
+  p.rows = rows; p.kept = kept; p.B = B; p.cap = cap; p.nc = num_classes; p.tab = geom; p.ihm = ihm; p.iwm = iwm;
+  p.out = rows_out; p.draw = draw_rows; p.offsets = offsets; p.counts = reinterpret_cast<unsigned long long*>(det_counts);
+  p.flag = flag;
+  hipLaunchKernelGGL(detect_finish_kernel<true>, dim3(vr_cdiv(cap, 256), B), dim3(256), 0, st, p);
+  VR_LAUNCH_CHECK("detect_finish_ragged");
   return VR_OK;
 }

@@ -292,6 +292,145 @@ __global__ __launch_bounds__(256) void render_kernel(const RenderArgs p) {
   }
 }
 
+// ---- the ragged form: frames, class map and out are (B, ihm, iwm[, 3]) slots with image b in the top-left ih_b x iw_b
+// corner; ih_b, iw_b and the outline thickness come from tab[b].  blockIdx.y is the image, so a workgroup keeps one
+// image's box rows and one histogram in LDS for its whole life.  Four consecutive pixels of the slot per thread (dword
+// accesses when the slots allow it), each with its own (x, y): a group may wrap a row.  Every pixel of the slot outside
+// the image is written 0 and counts nowhere.
+struct RaggedRenderArgs {
+  RenderArgs r;                      // ih, iw = the slot ihm, iwm; thickness, head, ngroups, total, inplace unused
+  const vrnet_frame_geom* tab;       // (B)
+};
+
+__global__ __launch_bounds__(256) void render_ragged_kernel(const RaggedRenderArgs a) {
+  __shared__ int4 s_rows[RN_MAXBOX];
+  __shared__ unsigned char s_rcol[RN_MAXBOX];
+  __shared__ unsigned int s_pal[RN_MAXCOL], s_bpal[RN_MAXCOL], s_bins[RN_MAXCOL];
+  const RenderArgs& p = a.r;
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const bool has_map = p.cmap != nullptr, first = blockIdx.x == 0 && tid == 0;
+  bool bad;
+  const vrnet_frame_geom g = vr_geom_load(a.tab, b, p.ih, p.iw, 0, 0, bad);
+  if (bad && first) raise_flag(p, VR_FLAG_GEOMETRY);
+  for (int i = tid; i < RN_MAXCOL; i += 256) {
+    s_pal[i] = (p.palette && i < p.n_colors) ? pack_rgb(p.palette + 3 * i) : 0u;
+    s_bpal[i] = (p.box_palette && i < p.n_box_colors) ? pack_rgb(p.box_palette + 3 * i) : 0u;
+    s_bins[i] = 0u;
+  }
+  int start, nrows;
+  row_range(p, b, start, nrows);
+  if (nrows > RN_MAXBOX) {
+    if (first) raise_flag(p, RN_FLAG_BOX_ROWS);
+    nrows = RN_MAXBOX;
+  }
+  for (int k = tid; k < nrows; k += 256) {
+    int ci;
+    s_rows[k] = load_row(p.boxes + 5L * (start + k), ci);
+    if (ci < 0 || ci >= p.n_box_colors) raise_flag(p, RN_FLAG_BOX_COLOUR);
+    s_rcol[k] = (unsigned char)clampi(ci, 0, p.n_box_colors - 1);
+  }
+  __syncthreads();
+  const int slot = p.ih * p.iw, ngroups = (slot + 3) / 4;
+  const long base = (long)b * slot;
+  const bool need_frame = has_map ? p.mix != 1 : true;
+  for (int grp = blockIdx.x * 256 + tid; grp < ngroups; grp += gridDim.x * 256) {
+    const int p0 = 4 * grp, npx = min(4, slot - p0);
+    const bool dwords = p.vec && npx == 4;
+    unsigned int cls4 = 0;
+    if (has_map) {
+      const unsigned char* c = p.cmap + base + p0;
+      if (dwords) cls4 = *reinterpret_cast<const unsigned int*>(c);
+      else
+        for (int j = 0; j < npx; ++j) cls4 |= (unsigned int)c[j] << (8 * j);
+    }
+    unsigned int f[3] = {0u, 0u, 0u};
+    if (need_frame) {
+      const unsigned char* s = p.frames + 3L * (base + p0);
+      if (dwords) {
+        const unsigned int* s4 = reinterpret_cast<const unsigned int*>(s);
+        f[0] = s4[0];
+        f[1] = s4[1];
+        f[2] = s4[2];
+      } else {
+        for (int j = 0; j < 3 * npx; ++j) f[j >> 2] |= (unsigned int)s[j] << (8 * (j & 3));
+      }
+    }
+    unsigned int px[4] = {f[0] & 0xFFFFFFu, (f[0] >> 24) | ((f[1] & 0xFFFFu) << 8), (f[1] >> 16) | ((f[2] & 0xFFu) << 16), f[2] >> 8};
+    int xs[4], ys[4];
+    unsigned int in = 0;                               // bit j: pixel j lies inside the image
+    {
+      int y = p0 / p.iw, x = p0 - y * p.iw;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        xs[j] = x;
+        ys[j] = y;
+        if (j < npx && y < g.ih && x < g.iw) in |= 1u << j;
+        if (++x == p.iw) { x = 0; ++y; }
+      }
+    }
+    if (has_map) {
+      int cls[4];
+      bool badcls = false;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        cls[j] = (cls4 >> (8 * j)) & 255;
+        int c = cls[j];
+        if (p.n_colors > 0 && c >= p.n_colors) {
+          if (in & (1u << j)) badcls = true;
+          c = p.n_colors - 1;
+        }
+        px[j] = shade(p, true, cls[j], px[j], s_pal[c]);
+      }
+      if (badcls) raise_flag(p, RN_FLAG_CLASS);
+      if (p.counts) {
+        // a wave inside one region of the map adds once; otherwise a thread whose four pixels agree adds once
+        const bool same4 = in == 15u && cls[0] == cls[1] && cls[0] == cls[2] && cls[0] == cls[3] && !badcls;
+        const int lead = __builtin_amdgcn_readfirstlane(cls[0]);
+        if (__all(same4 && cls[0] == lead)) {
+          const unsigned long long active = __ballot(1);
+          if (__lane_id() == __ffsll((long long)active) - 1) atomicAdd(&s_bins[lead], 4u * (unsigned int)__popcll(active));
+        } else if (same4) {
+          atomicAdd(&s_bins[cls[0]], 4u);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if ((in & (1u << j)) && cls[j] < p.n_colors) atomicAdd(&s_bins[cls[j]], 1u);
+        }
+      }
+    }
+    unsigned int hit = ~in & 15u;                      // bit j: pixel j is settled (painted, or padding)
+    for (int k = nrows - 1; k >= 0 && hit != 15u; --k) {
+      const int4 q = s_rows[k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (!(hit & (1u << j)) && on_rings(xs[j], ys[j], q, g.thickness)) {
+          px[j] = s_bpal[s_rcol[k]];
+          hit |= 1u << j;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (!(in & (1u << j))) px[j] = 0u;
+    unsigned char* o = p.out + 3L * (base + p0);
+    const unsigned int o0 = px[0] | (px[1] << 24), o1 = (px[1] >> 8) | (px[2] << 16), o2 = (px[2] >> 16) | (px[3] << 8);
+    if (dwords) {
+      unsigned int* o4 = reinterpret_cast<unsigned int*>(o);
+      o4[0] = o0;
+      o4[1] = o1;
+      o4[2] = o2;
+    } else {
+      const unsigned int w[3] = {o0, o1, o2};
+      for (int j = 0; j < 3 * npx; ++j) o[j] = (unsigned char)(w[j >> 2] >> (8 * (j & 3)));
+    }
+  }
+  __syncthreads();
+  if (p.counts)
+    for (int i = tid; i < p.n_colors; i += 256) {
+      const unsigned int v = s_bins[i];
+      if (v) atomicAdd(&p.counts[(long)b * p.n_colors + i], (unsigned long long)v);
+    }
+}
+
 bool overlap(const void* a, long a_bytes, const void* b, long b_bytes) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   return x < y + (uintptr_t)b_bytes && y < x + (uintptr_t)a_bytes;
@@ -345,5 +484,51 @@ extern "C" int vrnet_render_u8(const unsigned char* frames, const unsigned char*
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(render_kernel, dim3((unsigned)grid), dim3(256), 0, st, p);
   VR_LAUNCH_CHECK("render");
+  return VR_OK;
+}
+
+extern "C" int vrnet_render_ragged_u8(const unsigned char* frames, const unsigned char* class_map,
+                                      const vrnet_frame_geom* geom, int B, int ihm, int iwm, const unsigned char* palette,
+                                      int n_colors, int mix_type, float alpha, const int* boxes, const int* box_offsets,
+                                      int n_rows, const unsigned char* box_palette, int n_box_colors, unsigned char* out,
+                                      long long* counts, int* flag, void* stream) {
+  VR_CHECK_ARG(frames && out && geom && B > 0 && B < 65536 && ihm > 0 && iwm > 0 && ihm <= (1 << 24) && iwm <= (1 << 24) &&
+                   (long)B * ihm * iwm < (1L << 31),
+               "render_ragged: bad shape (B %d, slots %d x %d; at most 2^31 - 1 pixels in all)", B, ihm, iwm);
+  VR_CHECK_ARG(mix_type >= 0 && mix_type <= 2, "render_ragged: mix_type %d is not 0, 1 or 2", mix_type);
+  VR_CHECK_ARG(alpha >= 0.f && alpha <= 1.f, "render_ragged: alpha %g outside [0, 1]", (double)alpha);
+  VR_CHECK_ARG(n_colors >= 0 && n_colors <= RN_MAXCOL && (n_colors > 0) == (palette != nullptr || counts != nullptr) &&
+                   (!palette || n_colors > 0),
+               "render_ragged: a palette or counts need 1..%d colours, got %d", RN_MAXCOL, n_colors);
+  VR_CHECK_ARG(!class_map || mix_type == 2 || palette, "render_ragged: mix_type %d of a class map needs a palette", mix_type);
+  VR_CHECK_ARG(class_map || !counts, "render_ragged: counts need a class map");
+  VR_CHECK_ARG(n_rows >= 0 && (n_rows == 0 || (boxes && box_offsets && box_palette && n_box_colors > 0 &&
+                                                n_box_colors <= RN_MAXCOL)),
+               "render_ragged: %d box rows need offsets and a box palette of 1..%d colours", n_rows, RN_MAXCOL);
+  const long total = (long)B * ihm * iwm;
+  VR_CHECK_ARG(!overlap(out, 3 * total, frames, 3 * total), "render_ragged: out overlaps the frames (the padding is written)");
+  VR_CHECK_ARG(!class_map || !overlap(out, 3 * total, class_map, total), "render_ragged: out overlaps the class map");
+  hipStream_t st = vr_stream(stream);
+  if (counts && hipMemsetAsync(counts, 0, (size_t)B * n_colors * sizeof(long long), st) != hipSuccess) {
+    vr_set_error("render_ragged: clearing the counts failed");
+    return VR_ERR_LAUNCH;
+  }
+  RaggedRenderArgs a{};
+  RenderArgs& p = a.r;
+  a.tab = geom;
+  p.frames = frames; p.cmap = class_map; p.palette = palette; p.out = out;
+  p.boxes = n_rows > 0 ? boxes : nullptr; p.offsets = box_offsets; p.box_palette = box_palette;
+  p.counts = reinterpret_cast<unsigned long long*>(counts); p.flag = flag;
+  p.B = B; p.ih = ihm; p.iw = iwm; p.n_colors = n_colors; p.n_box_colors = n_box_colors; p.n_rows = n_rows;
+  p.mix = mix_type; p.alpha = alpha;
+  // dword accesses: every slot starts on a 4-byte boundary in all three tensors
+  const long slot = (long)ihm * iwm;
+  p.vec = ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(class_map)) & 3) == 0 &&
+          (slot % 4 == 0 || B == 1);
+  long grid = vr_cdiv(vr_cdiv(slot, 4), 256);
+  const long per_image = vr_cdiv(2048, B);
+  if (grid > per_image) grid = per_image;
+  hipLaunchKernelGGL(render_ragged_kernel, dim3((unsigned)grid, B), dim3(256), 0, st, a);
+  VR_LAUNCH_CHECK("render_ragged");
   return VR_OK;
 }

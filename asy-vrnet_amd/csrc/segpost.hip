@@ -28,19 +28,23 @@ struct SegPredArgs {
   unsigned char* out;                // (B, oh, ow)
 };
 
+// softmax over the C channels of one pixel: src / dst step by a plane per channel
+__device__ __forceinline__ void softmax_pixel(const float* src, long plane, int C, float* dst, long dplane) {
+  float m = -INFINITY;
+  for (int c = 0; c < C; ++c) m = fmaxf(m, src[c * plane]);
+  float s = 0.f;
+  for (int c = 0; c < C; ++c) s += expf(src[c * plane] - m);
+  for (int c = 0; c < C; ++c) dst[c * dplane] = expf(src[c * plane] - m) / s;
+}
+
 __global__ __launch_bounds__(256) void segp_softmax_kernel(const SegPredArgs p) {
   const long total = (long)p.B * p.nh * p.nw;
   const long plane = (long)p.H * p.W;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const long b = e / ((long)p.nh * p.nw);
     const int r = (int)(e - b * p.nh * p.nw), y = r / p.nw, xx = r - y * p.nw;
-    const float* src = p.x + b * p.C * plane + (long)(p.top + y) * p.W + (p.left + xx);
-    float m = -INFINITY;
-    for (int c = 0; c < p.C; ++c) m = fmaxf(m, src[c * plane]);
-    float s = 0.f;
-    for (int c = 0; c < p.C; ++c) s += expf(src[c * plane] - m);
-    float* dst = p.prob + b * p.C * p.nh * p.nw + r;
-    for (int c = 0; c < p.C; ++c) dst[(long)c * p.nh * p.nw] = expf(src[c * plane] - m) / s;
+    softmax_pixel(p.x + b * p.C * plane + (long)(p.top + y) * p.W + (p.left + xx), plane, p.C,
+                  p.prob + b * p.C * p.nh * p.nw + r, (long)p.nh * p.nw);
   }
 }
 
@@ -57,29 +61,74 @@ __device__ __forceinline__ void linear_tap(int d, float scale, int src, int& s0,
   s1 = s + 1 < src ? s + 1 : s;
 }
 
+// output pixel (oy, ox) of one image: the arg-max over the classes of the bilinear blend of prob (C, nh, nw)
+__device__ __forceinline__ unsigned char resize_argmax_pixel(const float* prob, int C, int nh, int nw, float sy, float sx,
+                                                             int oy, int ox) {
+  int y0, y1, x0, x1;
+  float fy, fx;
+  linear_tap(oy, sy, nh, y0, y1, fy);
+  linear_tap(ox, sx, nw, x0, x1, fx);
+  const float ax0 = 1.f - fx, ay0 = 1.f - fy;
+  const long pl = (long)nh * nw;
+  const float* r0 = prob + (long)y0 * nw;
+  const float* r1 = prob + (long)y1 * nw;
+  float best = 0.f;
+  int arg = 0;
+  for (int c = 0; c < C; ++c) {
+    const float top = r0[c * pl + x0] * ax0 + r0[c * pl + x1] * fx;
+    const float bot = r1[c * pl + x0] * ax0 + r1[c * pl + x1] * fx;
+    const float v = top * ay0 + bot * fy;
+    if (c == 0 || v > best) { best = v; arg = c; }
+  }
+  return (unsigned char)arg;
+}
+
 __global__ __launch_bounds__(256) void segp_resize_argmax_kernel(const SegPredArgs p) {
   const long total = (long)p.B * p.oh * p.ow;
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e >= total) return;
   const long b = e / ((long)p.oh * p.ow);
   const int r = (int)(e - b * p.oh * p.ow), oy = r / p.ow, ox = r - oy * p.ow;
-  int y0, y1, x0, x1;
-  float fy, fx;
-  linear_tap(oy, p.sy, p.nh, y0, y1, fy);
-  linear_tap(ox, p.sx, p.nw, x0, x1, fx);
-  const float ax0 = 1.f - fx, ay0 = 1.f - fy;
-  const long pl = (long)p.nh * p.nw;
-  const float* r0 = p.prob + b * p.C * pl + (long)y0 * p.nw;
-  const float* r1 = p.prob + b * p.C * pl + (long)y1 * p.nw;
-  float best = 0.f;
-  int arg = 0;
-  for (int c = 0; c < p.C; ++c) {
-    const float top = r0[c * pl + x0] * ax0 + r0[c * pl + x1] * fx;
-    const float bot = r1[c * pl + x0] * ax0 + r1[c * pl + x1] * fx;
-    const float v = top * ay0 + bot * fy;
-    if (c == 0 || v > best) { best = v; arg = c; }
-  }
-  p.out[e] = (unsigned char)arg;
+  p.out[e] = resize_argmax_pixel(p.prob + b * p.C * p.nh * p.nw, p.C, p.nh, p.nw, p.sy, p.sx, oy, ox);
+}
+
+// ---- the ragged form: the window and the output size of image b come from tab[b]; the class map is the padded
+// (B, ihm, iwm) buffer with image b in the top-left corner of its slot and 0 outside it.  blockIdx.y is the image.
+struct RaggedSegArgs {
+  const float* x;                    // (B, C, H, W)
+  const vrnet_frame_geom* tab;       // (B)
+  int B, C, H, W, ihm, iwm;
+  float* prob;                       // image b: (C, seg_nh, seg_nw) at b * C * H * W
+  unsigned char* out;                // (B, ihm, iwm)
+  int* flag;                         // or null
+};
+
+__global__ __launch_bounds__(256) void segp_ragged_softmax_kernel(const RaggedSegArgs p) {
+  const int b = blockIdx.y;
+  bool bad;
+  const vrnet_frame_geom g = vr_geom_load(p.tab, b, p.ihm, p.iwm, p.H, p.W, bad);
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r == 0 && bad && p.flag) atomicOr(p.flag, VR_FLAG_GEOMETRY);
+  const int nh = g.seg_nh, nw = g.seg_nw;
+  if (r >= nh * nw) return;
+  const int y = r / nw, xx = r - y * nw;
+  const long plane = (long)p.H * p.W;
+  softmax_pixel(p.x + (long)b * p.C * plane + (long)(g.seg_top + y) * p.W + (g.seg_left + xx), plane, p.C,
+                p.prob + (long)b * p.C * plane + r, (long)nh * nw);
+}
+
+__global__ __launch_bounds__(256) void segp_ragged_resize_argmax_kernel(const RaggedSegArgs p) {
+  const int b = blockIdx.y;
+  bool bad;
+  const vrnet_frame_geom g = vr_geom_load(p.tab, b, p.ihm, p.iwm, p.H, p.W, bad);
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= p.ihm * p.iwm) return;
+  const int oy = e / p.iwm, ox = e - oy * p.iwm;
+  unsigned char cls = 0;                           // the padding of the slot, and an image without a window
+  if (oy < g.ih && ox < g.iw && g.seg_nh > 0 && g.seg_nw > 0)
+    cls = resize_argmax_pixel(p.prob + (long)b * p.C * p.H * p.W, p.C, g.seg_nh, g.seg_nw, (float)g.seg_nh / (float)g.ih,
+                              (float)g.seg_nw / (float)g.iw, oy, ox);
+  p.out[(long)b * p.ihm * p.iwm + e] = cls;
 }
 
 template <typename TL, typename TP>
@@ -155,5 +204,31 @@ extern "C" int vrnet_confusion_hist(const void* label, int label_bytes, const vo
   else
     launch_hist(static_cast<const long long*>(label), pred, pred_bytes, N, n, hist, (int)grid, st);
   VR_LAUNCH_CHECK("confusion_hist");
+  return VR_OK;
+}
+
+extern "C" long vrnet_seg_predict_ragged_workspace(int B, int C, int H, int W) {
+  return (long)B * H * W * C * (long)sizeof(float) + 256;
+}
+
+extern "C" int vrnet_seg_predict_ragged_f32(const float* x, const vrnet_frame_geom* geom, int B, int C, int H, int W, int ihm,
+                                            int iwm, unsigned char* out, int* flag, void* workspace, long workspace_bytes,
+                                            void* stream) {
+  VR_CHECK_ARG(x && geom && out && workspace && B > 0 && B < 65536 && C > 0 && C <= SEGP_MAXC && H > 0 && W > 0 && ihm > 0 &&
+                   iwm > 0 && (long)H * W < (1L << 31) && (long)ihm * iwm < (1L << 31),
+               "seg_predict_ragged: bad arguments (B %d, 1..%d classes, got %d; logits %d x %d; slots %d x %d)", B, SEGP_MAXC, C,
+               H, W, ihm, iwm);
+  if (workspace_bytes < vrnet_seg_predict_ragged_workspace(B, C, H, W)) {
+    vr_set_error("seg_predict_ragged: workspace %ld < %ld bytes", workspace_bytes, vrnet_seg_predict_ragged_workspace(B, C, H, W));
+    return VR_ERR_WORKSPACE;
+  }
+  RaggedSegArgs p{};
+  p.x = x; p.tab = geom; p.B = B; p.C = C; p.H = H; p.W = W; p.ihm = ihm; p.iwm = iwm;
+  p.prob = reinterpret_cast<float*>(workspace);
+  p.out = out; p.flag = flag;
+  hipStream_t st = vr_stream(stream);
+  hipLaunchKernelGGL(segp_ragged_softmax_kernel, dim3((unsigned)vr_cdiv((long)H * W, 256), B), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(segp_ragged_resize_argmax_kernel, dim3((unsigned)vr_cdiv((long)ihm * iwm, 256), B), dim3(256), 0, st, p);
+  VR_LAUNCH_CHECK("seg_predict_ragged");
   return VR_OK;
 }

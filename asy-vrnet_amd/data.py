@@ -182,6 +182,171 @@ def device_letterbox(images_u8, input_shape, labels_u8=None, letterbox_image=Tru
     return (images if normalise else canvas), labels
 
 
+# ---- ragged batches: frames of their own sizes in the corners of padded (B, ihm, iwm[, 3]) slots ------------------------
+# vrnet_frame_geom of include/vrnet_hip.h, one record per image (80 bytes)
+GEOM_DTYPE = np.dtype([(n, "<i4") for n in ("ih", "iw", "nw", "nh", "dx", "dy", "seg_top", "seg_left", "seg_nh", "seg_nw",
+                                            "thickness", "reserved")] +
+                      [(n, "<f8") for n in ("offset_y", "offset_x", "scale_y", "scale_x")])
+
+
+def resample_ksize(n_in, n_out):
+    """Pillow's Resample.c precompute_coeffs: the taps one output index of an axis resized n_in -> n_out can take."""
+    return int(np.ceil(2.0 * max(n_in / n_out, 1.0))) * 2 + 1
+
+
+def default_max_taps(capacity, input_shape):
+    """The tap capacity a ragged pipeline reserves per table entry.  Both axes of a letterboxed frame share one scale s, and
+    1 / s <= R = max(iwm / W, ihm / H, 1) for a frame inside the capacity; an axis in -> out = int(in * s) has
+    in / out = (1 / s) * (1 + f / out) with 0 <= f < 1 the part int() cut off, so its support 2 * in / out exceeds 2 / s by less
+    than 2 / (s * out) <= 1 once out >= 2 R: ceil() then grows by at most one and ksize by at most two.  Hence
+    ksize(R) + 2 = 2 * ceil(2 R) + 3 serves every frame whose window is at least 2 R pixels on both axes; only thinner
+    slivers can need more, and `frame_geometry` rejects those."""
+    (ihm, iwm), (H, W) = capacity, input_shape
+    return int(np.ceil(2.0 * max(iwm / W, ihm / H, 1.0))) * 2 + 3
+
+
+def frame_sizes(sizes, batch=None, fn="frame_geometry"):
+    """sizes as a (B, 2) int64 array of (ih, iw) rows.  Sizes are HOST integers (a list, an array or a CPU tensor): they
+    size the copies and are validated before anything is launched, so a device tensor, whose read-back would synchronise,
+    is rejected."""
+    if torch.is_tensor(sizes) and sizes.is_cuda:
+        raise RuntimeError(f"{fn}: sizes are host integers, got a tensor on {sizes.device} (reading it back would synchronise)")
+    try:
+        arr = np.asarray(sizes)
+        ok = arr.ndim == 2 and arr.shape[1] == 2 and np.array_equal(arr, arr.astype(np.int64))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise RuntimeError(f"{fn}: sizes are B integer (height, width) pairs, got {sizes!r}")
+    if batch is not None and len(arr) != batch:
+        raise RuntimeError(f"{fn}: {len(arr)} sizes for a batch of {batch} frames")
+    return arr.astype(np.int64)
+
+
+def frame_geometry(sizes, input_shape, letterbox_image=True, capacity=None, max_taps=None, fn="frame_geometry"):
+    """The packed per-image table of the ragged entry points: sizes (B, 2) = (ih, iw) per image -> a (B,) GEOM_DTYPE array
+    (`.view(np.uint8).reshape(B, -1)` is what the device takes).  Every value is what the fixed-size path computes for that
+    image alone: `letterbox_geometry`, `decode.seg_window`, `infer.unmap_scalars` and the thickness of yolo.py:164; with
+    letterbox_image=False the window is the whole input.  Host only.  Raises RuntimeError naming the image index for a
+    size that is not positive or above capacity = (ihm, iwm), for an empty window, and for a frame whose resize needs more
+    taps than max_taps (see `default_max_taps`)."""
+    from . import decode, infer
+    arr = frame_sizes(sizes, fn=fn)
+    H, W = (int(v) for v in input_shape)
+    tab = np.zeros(len(arr), GEOM_DTYPE)
+    for b, (ih, iw) in enumerate(arr.tolist()):
+        if ih <= 0 or iw <= 0:
+            raise RuntimeError(f"{fn}: image {b}: bad size {ih} x {iw}")
+        if capacity is not None and (ih > capacity[0] or iw > capacity[1]):
+            raise RuntimeError(f"{fn}: image {b}: {ih} x {iw} is above the capacity {capacity[0]} x {capacity[1]}")
+        if letterbox_image:
+            nw, nh, dx, dy = letterbox_geometry(iw, ih, W, H)
+            top, left, snh, snw = decode.seg_window((H, W), (ih, iw))
+        else:
+            (nw, nh, dx, dy), (top, left, snh, snw) = (W, H, 0, 0), (0, 0, H, W)
+        if min(nw, nh, snw, snh) <= 0:
+            raise RuntimeError(f"{fn}: image {b}: {ih} x {iw} leaves an empty window ({nh} x {nw}) in a {H} x {W} input")
+        need = max(resample_ksize(iw, nw) if nw != iw else 0, resample_ksize(ih, nh) if nh != ih else 0)
+        if max_taps is not None and need > max_taps:
+            raise RuntimeError(f"{fn}: image {b}: resizing {ih} x {iw} to {nh} x {nw} takes {need} taps, above the tap capacity "
+                               f"{max_taps} (a sliver: raise max_taps)")
+        offset, scale = infer.unmap_scalars((H, W), (ih, iw), letterbox_image)
+        tab[b] = (ih, iw, nw, nh, dx, dy, top, left, snh, snw, int(max((iw + ih) // np.mean((H, W)), 1)), 0,
+                  offset[0], offset[1], scale[0], scale[1])
+    return tab
+
+
+def ragged_items(items, sizes, batch, trailing, what, fn):
+    """The two forms a ragged batch comes in -> (list of B uint8 tensors or one padded uint8 tensor, sizes (B, 2) int64):
+    a list of B arrays (ih_b, iw_b) + trailing of their own sizes (sizes optional, checked when given), or a padded buffer
+    (B, ihp, iwp) + trailing with the images in the top-left corners, which needs sizes.  batch=None: B follows the input."""
+    def u8(a, k):
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        if t.dtype != torch.uint8:
+            raise RuntimeError(f"{fn}: expected uint8 {what}, got {t.dtype}" + ("" if k is None else f" for image {k}"))
+        return t
+    if isinstance(items, (list, tuple)):
+        if batch is not None and len(items) != batch:
+            raise RuntimeError(f"{fn}: {len(items)} {what} for a batch of {batch}")
+        ts = [u8(a, k) for k, a in enumerate(items)]
+        for k, t in enumerate(ts):
+            if t.dim() != 2 + len(trailing) or tuple(t.shape[2:]) != trailing:
+                raise RuntimeError(f"{fn}: image {k}: expected {what} of shape (ih, iw{''.join(', %d' % v for v in trailing)}), "
+                                   f"got {tuple(t.shape)}")
+        own = np.array([t.shape[:2] for t in ts], np.int64).reshape(-1, 2)
+        if sizes is not None:
+            given = frame_sizes(sizes, len(ts), fn)
+            for k in range(len(ts)):
+                if tuple(given[k]) != tuple(own[k]):
+                    raise RuntimeError(f"{fn}: image {k}: sizes says {tuple(given[k].tolist())}, the array is "
+                                       f"{tuple(own[k].tolist())}")
+        return ts, own
+    t = u8(items, None)
+    if t.dim() != 3 + len(trailing) or tuple(t.shape[3:]) != trailing:
+        raise RuntimeError(f"{fn}: expected a list of {what} or a padded buffer (B, ihm, iwm{''.join(', %d' % v for v in trailing)}), "
+                           f"got {tuple(t.shape)}")
+    if batch is not None and t.shape[0] != batch:
+        raise RuntimeError(f"{fn}: {t.shape[0]} {what} for a batch of {batch}")
+    if sizes is None:
+        raise RuntimeError(f"{fn}: a padded buffer of {what} needs sizes, the (height, width) of every image in it")
+    given = frame_sizes(sizes, t.shape[0], fn)
+    for k, (ih, iw) in enumerate(given.tolist()):
+        if ih > t.shape[1] or iw > t.shape[2]:
+            raise RuntimeError(f"{fn}: image {k}: sizes says {ih} x {iw}, the padded buffer is {t.shape[1]} x {t.shape[2]}")
+    return t, given
+
+
+def fill_slots(dst, items, sizes, corners_only=False):
+    """Copies a ragged batch (`ragged_items`) into the corners of the slots of the device buffer dst (B, ihm, iwm, ...), all
+    non_blocking.  A padded buffer is copied whole, its padding included: the ragged kernels read no input padding into a
+    result.  corners_only=True copies only the `[:ih_b, :iw_b]` corner of every slot of a padded buffer too and leaves the
+    rest of dst as it is -- for a buffer whose padding means something, as the 255 of `EvalPipeline.labels_u8`."""
+    if torch.is_tensor(items) and not corners_only:
+        dst[:, :items.shape[1], :items.shape[2]].copy_(items, non_blocking=True)
+    else:
+        for b, t in enumerate(items):
+            ih, iw = int(sizes[b][0]), int(sizes[b][1])
+            dst[b, :ih, :iw].copy_(t[:ih, :iw], non_blocking=True)
+
+
+def device_letterbox_ragged(frames, sizes, input_shape, labels=None, letterbox_image=True, normalise=True, capacity=None,
+                            max_taps=None, flag=None, device="cuda"):
+    """`device_letterbox` for frames of DIFFERENT original sizes in one call (vrnet_letterbox_ragged_u8).  frames: a list of
+    B uint8 arrays (ih_b, iw_b, 3) (sizes may be None), or a padded (B, ihm, iwm, 3) buffer with image b in its top-left
+    corner and sizes (B, 2) = (ih_b, iw_b); labels: the same two forms of (ih_b, iw_b) maps, or None.  capacity = (ihm, iwm)
+    of the device slots (default: the padded buffer's, or the largest frame's); max_taps: `default_max_taps`.  Returns
+    (images, labels) exactly as `device_letterbox` would for every frame alone: the same Pillow bytes.  flag: an int32
+    device word that receives hip.FLAG_GEOMETRY (never, for a table this function built).  numpy arrays or tensors."""
+    from . import hip
+    fn = "device_letterbox_ragged"
+    items, own = ragged_items(frames, sizes, None, (3,), "frames", fn)
+    B = len(own)
+    labs = None if labels is None else ragged_items(labels, own, B, (), "label maps", fn)[0]
+    if capacity is None:
+        capacity = tuple(items.shape[1:3]) if torch.is_tensor(items) else (int(own[:, 0].max()), int(own[:, 1].max()))
+    ihm, iwm = (int(v) for v in capacity)
+    for t in (items, labs):
+        if torch.is_tensor(t) and (t.shape[1] > ihm or t.shape[2] > iwm):
+            raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {(ihm, iwm)}")
+    H, W = (int(v) for v in input_shape)
+    max_taps = default_max_taps((ihm, iwm), (H, W)) if max_taps is None else int(max_taps)
+    tab = frame_geometry(own, (H, W), letterbox_image, (ihm, iwm), max_taps, fn)
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        geom = torch.from_numpy(tab.view(np.uint8).reshape(B, -1)).to(dev, non_blocking=True)
+        img = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
+        fill_slots(img, items, own)
+        lab = None
+        if labs is not None:
+            lab = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
+            fill_slots(lab, labs, own)
+        canvas = None if normalise else torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+        images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if normalise else None
+        out_lab = None if lab is None else torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        hip.letterbox_ragged(img, lab, geom, H, W, max_taps, canvas=canvas, images=images, label_out=out_lab, flag=flag)
+    return (images if normalise else canvas), out_lab
+
+
 def device_radar(radar, normalise=True, device="cuda", out=None):
     """The radar half of the prediction scripts ON THE DEVICE (vrnet_radar_normalise): radar (B, 4, H, W) float32 or
     float64 maps (a single (4, H, W) frame counts as B = 1), numpy array or tensor -> (B, 4, H, W) float32 on the device.

@@ -149,3 +149,28 @@ def seg_predict(outputs_seg, input_shape, image_shape):
     ws = torch.empty(hip.seg_predict_workspace_bytes(B, C, nh, nw), dtype=torch.uint8, device=x.device)
     hip.seg_predict(x, top, left, nh, nw, out, ws)
     return out
+
+
+def seg_predict_ragged(outputs_seg, geom, capacity, flag=None):
+    """`seg_predict` for a batch of images of their own sizes (vrnet_seg_predict_ragged_f32): outputs_seg (B, C, H, W) seg
+    logits, geom the (B, hip.GEOM_BYTES) device table of `data.frame_geometry` (window and size of image b), capacity =
+    (ihm, iwm).  Returns the padded (B, ihm, iwm) uint8 class map: image b is `[b, :ih_b, :iw_b]`, equal to `seg_predict` on
+    that image alone, and every pixel outside it is 0.  flag: an int32 device word for hip.FLAG_GEOMETRY, or None.  No host
+    synchronisation."""
+    if not (torch.is_tensor(outputs_seg) and outputs_seg.dim() == 4):
+        raise RuntimeError("seg_predict_ragged: expects (B, C, H, W) seg logits")
+    B, C, H, W = outputs_seg.shape
+    if not 0 < C <= SEG_MAX_CLASSES:
+        raise RuntimeError(f"seg_predict_ragged: {C} classes (1..{SEG_MAX_CLASSES} supported)")
+    if not outputs_seg.is_cuda:
+        raise RuntimeError("seg_predict_ragged: the logits must be on a GPU (there is no CPU fallback)")
+    ihm, iwm = int(capacity[0]), int(capacity[1])
+    if ihm <= 0 or iwm <= 0 or B == 0:
+        raise RuntimeError(f"seg_predict_ragged: bad capacity {tuple(capacity)} or an empty batch")
+    x = outputs_seg.detach()
+    x = x if (x.is_contiguous() and x.dtype == torch.float32) else x.contiguous().float()
+    with torch.cuda.device(x.device):
+        out = torch.empty((B, ihm, iwm), dtype=torch.uint8, device=x.device)
+        ws = torch.empty(hip.seg_predict_ragged_workspace_bytes(B, C, H, W), dtype=torch.uint8, device=x.device)
+        hip.seg_predict_ragged(x, geom, out, ws, flag)
+    return out

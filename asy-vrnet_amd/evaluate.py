@@ -93,23 +93,28 @@ def validate_eval_config(class_names, num_seg_classes, batch, capacity, max_boxe
     return names, int(num_seg_classes), int(capacity), int(max_boxes), int(max_gt)
 
 
-def validate_add(image_ids, seen, label_maps, gt_boxes, batch, frame_shape, num_classes, max_gt):
+def validate_add(image_ids, seen, label_maps, gt_boxes, batch, frame_shape, num_classes, max_gt, sizes=None):
     """The host checks of `EvalPipeline.add` beside `infer.validate_inputs`: B distinct new ids, label maps (B, ih, iw)
     uint8, B integer (n, 5) ground-truth arrays with n <= max_gt and classes in [0, num_classes).  Returns (ids, labels as a
-    tensor, the ground truths packed as one int32 array: (B, max_gt, 5) rows x1, y1, x2, y2, class, then the B counts)."""
+    tensor, the ground truths packed as one int32 array: (B, max_gt, 5) rows x1, y1, x2, y2, class, then the B counts).
+    sizes (B, 2), from a ragged pipeline: the label maps come as the frames do (`data.ragged_items`: a list of maps of
+    their images' sizes, or a padded buffer) and are returned in that form."""
     if isinstance(image_ids, str) or len(image_ids) != batch:
         raise RuntimeError(f"EvalPipeline: add takes exactly batch = {batch} image ids, got {image_ids!r}")
     ids = [str(i) for i in image_ids]
     for k, i in enumerate(ids):
         if i in seen or i in ids[:k]:
             raise RuntimeError(f"EvalPipeline: image {i!r} was added twice")
-    lab = label_maps if torch.is_tensor(label_maps) else torch.from_numpy(np.ascontiguousarray(label_maps))
-    if lab.dtype != torch.uint8:
-        raise RuntimeError(f"EvalPipeline: expected uint8 label maps, got {lab.dtype}")
-    lab = lab[None] if batch == 1 and lab.dim() == 2 else lab
-    if tuple(lab.shape) != (batch,) + tuple(frame_shape):
-        raise RuntimeError(f"EvalPipeline: built for label maps of shape {(batch,) + tuple(frame_shape)} (the frames' size), "
-                           f"got {tuple(lab.shape)}")
+    if sizes is not None:
+        lab = data.ragged_items(label_maps, sizes, batch, (), "label maps", "EvalPipeline")[0]
+    else:
+        lab = label_maps if torch.is_tensor(label_maps) else torch.from_numpy(np.ascontiguousarray(label_maps))
+        if lab.dtype != torch.uint8:
+            raise RuntimeError(f"EvalPipeline: expected uint8 label maps, got {lab.dtype}")
+        lab = lab[None] if batch == 1 and lab.dim() == 2 else lab
+        if tuple(lab.shape) != (batch,) + tuple(frame_shape):
+            raise RuntimeError(f"EvalPipeline: built for label maps of shape {(batch,) + tuple(frame_shape)} (the frames' size), "
+                               f"got {tuple(lab.shape)}")
     if len(gt_boxes) != batch:
         raise RuntimeError(f"EvalPipeline: add takes exactly batch = {batch} ground-truth arrays, got {len(gt_boxes)}")
     packed = np.zeros(batch * max_gt * 5 + batch, dtype=np.int32)
@@ -159,11 +164,15 @@ class EvalPipeline(infer.FramePipeline):
     they were.
 
     `add` takes exactly `batch` images: for a validation set whose length is no multiple of batch, evaluate the rest with
-    a second pipeline of batch 1 (or build this one with batch=1)."""
+    a second pipeline of batch 1 (or build this one with batch=1).
+
+    ragged=True (with max_taps, as `infer.FramePipeline`): frame_shape is the capacity, every image has its own size, and
+    `add` takes frames and label maps as lists of arrays (or padded buffers with sizes).  labels_u8 is filled with 255
+    outside each image, which the confusion matrix skips, so only an image's own pixels are counted."""
 
     def __init__(self, model, frame_shape, input_shape, class_names, num_seg_classes, batch=1, capacity=None, max_boxes=100,
                  max_gt=64, conf_thres=0.05, nms_thres=0.5, letterbox_image=True, max_candidates=1024, normalise_radar=False,
-                 graph=True):
+                 graph=True, ragged=False, max_taps=None):
         infer.validate_config(model, frame_shape, input_shape, batch, max_candidates)
         self.class_names, self.num_seg_classes, self.capacity, self.max_boxes, self.max_gt = validate_eval_config(
             class_names, num_seg_classes, batch, capacity, max_boxes, max_gt, conf_thres)
@@ -184,7 +193,7 @@ class EvalPipeline(infer.FramePipeline):
         self.hist = torch.zeros((self.num_seg_classes, self.num_seg_classes), dtype=torch.int64, device=dev)
         super().__init__(model, frame_shape, input_shape, batch=batch, conf_thres=conf_thres, nms_thres=nms_thres,
                          letterbox_image=letterbox_image, max_candidates=max_candidates, normalise_radar=normalise_radar,
-                         render=False, graph=graph)
+                         render=False, graph=graph, ragged=ragged, max_taps=max_taps)
 
     def _tail(self, result):
         from . import hip, metrics
@@ -206,21 +215,33 @@ class EvalPipeline(infer.FramePipeline):
             t.zero_()
         self.image_ids = []
 
-    def add(self, image_ids, frames_u8, radar, label_maps, gt_boxes):
+    def add(self, image_ids, frames_u8, radar, label_maps, gt_boxes, sizes=None):
         """One batch: image_ids, a list of B strings (a duplicate raises); frames_u8 (B, ih, iw, 3) uint8 RGB and radar
         (B, 4, H, W), as `FramePipeline.run`; label_maps (B, ih, iw) uint8; gt_boxes, a list of B integer (n, 5) arrays x1,
         y1, x2, y2, class as `data.parse_annotation_line` returns.  Validates on the host, copies into the static buffers
         (non_blocking) and replays the graph (graph=False: runs the chain); no host synchronisation.  Returns the
-        `infer.FrameResult` of the batch."""
-        f, r = infer.validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape)
+        `infer.FrameResult` of the batch.  A ragged pipeline takes frames_u8 and label_maps as `FramePipeline.run` takes its
+        frames (lists of arrays of their own sizes, or padded buffers with sizes)."""
+        table = None
+        if self.ragged:
+            f, r, sizes, table = infer.validate_ragged_inputs(frames_u8, radar, sizes, self.batch, self.frame_shape,
+                                                              self.input_shape, self.letterbox_image, self.max_taps)
+        else:
+            if sizes is not None:
+                raise RuntimeError("EvalPipeline: sizes belong to a ragged pipeline (ragged=True)")
+            f, r = infer.validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape)
         ids, labels, packed = validate_add(image_ids, set(self.image_ids), label_maps, gt_boxes, self.batch, self.frame_shape,
-                                           len(self.class_names), self.max_gt)
+                                           len(self.class_names), self.max_gt, sizes)
         if len(self.image_ids) + self.batch > self.capacity:
             raise RuntimeError(f"EvalPipeline: the arena holds {self.capacity} images and is full (capacity=...)")
         with torch.cuda.device(self.device):
-            self.labels_u8.copy_(labels, non_blocking=True)
+            if self.ragged:
+                self.labels_u8.fill_(255)
+                data.fill_slots(self.labels_u8, labels, sizes, corners_only=True)     # a padded buffer's own padding stays out
+            else:
+                self.labels_u8.copy_(labels, non_blocking=True)
             self._gt_packed.copy_(torch.from_numpy(packed), non_blocking=True)
-        result = self.run(f, r)
+        result = self._launch(f, r, sizes, table)
         self.image_ids.extend(ids)
         return result
 
@@ -289,7 +310,8 @@ def evaluate_lines(pipeline, val_lines, radar_root, seg_root, batch_loader=None)
     resets `pipeline`, adds the annotation lines `val_lines` in batches of pipeline.batch and returns pipeline.compute().
     batch_loader(line, radar_root, seg_root) -> (image id, frame, radar, label map, ground truths), default `load_line`.
     len(val_lines) must be a multiple of pipeline.batch (see `EvalPipeline`); a frame or label map whose size differs from
-    the pipeline's raises with the file's name."""
+    the pipeline's raises with the file's name.  A ragged pipeline accepts mixed sizes up to its capacity (a label map
+    must still have its frame's size)."""
     load = load_line if batch_loader is None else batch_loader
     lines = [l for l in val_lines if l.strip()]
     B, (ih, iw) = pipeline.batch, pipeline.frame_shape
@@ -299,6 +321,14 @@ def evaluate_lines(pipeline, val_lines, radar_root, seg_root, batch_loader=None)
     pipeline.reset()
     for k in range(0, len(lines), B):
         items = [load(l, radar_root, seg_root) for l in lines[k:k + B]]
+        if getattr(pipeline, "ragged", False):
+            for l, (_, frame, _, label, _) in zip(lines[k:k + B], items):
+                if np.ndim(frame) != 3 or tuple(np.shape(label)) != tuple(np.shape(frame)[:2]) or np.asarray(label).dtype != np.uint8:
+                    raise RuntimeError(f"evaluate_lines: {l.split()[0]}: frame {tuple(np.shape(frame))}, but its label map is "
+                                       f"{tuple(np.shape(label))} {np.asarray(label).dtype} (a uint8 map of the frame's size is needed)")
+            pipeline.add([i[0] for i in items], [np.asarray(i[1], dtype=np.uint8) for i in items], np.stack([i[2] for i in items]),
+                         [np.asarray(i[3]) for i in items], [i[4] for i in items])
+            continue
         for l, (_, frame, _, label, _) in zip(lines[k:k + B], items):
             if tuple(np.shape(frame)) != (ih, iw, 3) or tuple(np.shape(label)) != (ih, iw):
                 raise RuntimeError(f"evaluate_lines: {l.split()[0]}: frame {tuple(np.shape(frame))} / label map "

@@ -139,6 +139,12 @@ _SIGS = {
     "vrnet_letterbox_workspace": ([I, I, I, I, I], L),
     "vrnet_letterbox_u8": ([P, P] + [I] * 9 + [P, P, P, P, L, P], I),
     "vrnet_render_u8": ([P, P, I, I, I, P, I, I, F, P, P, I, P, I, I, P, P, P, P], I),
+    "vrnet_letterbox_ragged_workspace": ([I] * 6, L),
+    "vrnet_letterbox_ragged_u8": ([P, P, P] + [I] * 6 + [P, P, P, P, P, L, P], I),
+    "vrnet_detect_finish_ragged_f32": ([P, P, P, I, I, I, I, I, P, P, P, P, P, P], I),
+    "vrnet_seg_predict_ragged_workspace": ([I, I, I, I], L),
+    "vrnet_seg_predict_ragged_f32": ([P, P, I, I, I, I, I, I, P, P, P, L, P], I),
+    "vrnet_render_ragged_u8": ([P, P, P, I, I, I, P, I, I, F, P, P, I, P, I, P, P, P, P], I),
     "vrnet_yolo_loss_workspace": ([I, L, I, I], L),
     "vrnet_yolo_loss_f32": ([P, P, P, P, P, I, I, I, P, P, I, F, P, P, P, P, P, L, P], I),
     "vrnet_seg_loss_workspace": ([I, I, L], L),
@@ -1132,3 +1138,96 @@ def bn_coef_bwd_from_chunks(partial, nchunks, count, mean_rstd, gamma, training,
     _check(_lib.vrnet_bn_coef_bwd_from_chunks(ptr(partial), nchunks, count, ptr(mean_rstd), ptr(gamma), 1 if training else 0, C, ptr(A),
                                               ptr(E), ptr(Dc), ptr(S), ptr(dgamma), ptr(dbeta), accumulate, stream()),
            "bn_coef_bwd_from_chunks")
+
+
+# ---- ragged batches (include/vrnet_hip.h "ragged batches"): per-image geometry from a device table -------------------
+GEOM_BYTES = 80          # sizeof(vrnet_frame_geom)
+FLAG_GEOMETRY = 256      # VR_FLAG_GEOMETRY of csrc/common.h
+
+
+def _geom(geom, B, fn):
+    """The table: a contiguous uint8 GPU tensor (B, GEOM_BYTES), 8-byte aligned (`data.frame_geometry` packs it)."""
+    if geom is None or geom.dtype != torch.uint8 or tuple(geom.shape) != (B, GEOM_BYTES) or not geom.is_contiguous() or \
+            not geom.is_cuda or geom.data_ptr() % 8:
+        raise RuntimeError(f"{fn}: the geometry table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape ({B}, {GEOM_BYTES})")
+    return ptr(geom)
+
+
+def _ragged_check(fn, specs):
+    for t, sh, dt in specs:
+        if t is not None and (t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or not t.is_cuda):
+            raise RuntimeError(f"{fn}: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+
+
+def letterbox_ragged_workspace_bytes(B, ihm, iwm, H, W, max_taps):
+    return _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, max_taps)
+
+
+def letterbox_ragged(img_u8, label_u8, geom, H, W, max_taps, canvas=None, images=None, label_out=None, flag=None, ws=None):
+    """`letterbox` for frames of their own sizes (vrnet_letterbox_ragged_u8): img_u8 (B,ihm,iwm,3) / label_u8 (B,ihm,iwm)
+    padded slots, geom the (B, GEOM_BYTES) table; max_taps: the tap capacity of a table entry; flag (1) int32 or None."""
+    src = img_u8 if img_u8 is not None else label_u8
+    if src is None or src.dim() < 3:
+        raise RuntimeError("letterbox_ragged: expected frames (B, ihm, iwm, 3) and / or label maps (B, ihm, iwm)")
+    B, ihm, iwm = src.shape[:3]
+    _ragged_check("letterbox_ragged", ((img_u8, (B, ihm, iwm, 3), torch.uint8), (label_u8, (B, ihm, iwm), torch.uint8),
+                                       (canvas, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
+                                       (label_out, (B, H, W), torch.uint8), (flag, (1,), torch.int32)))
+    need = _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, int(H), int(W), int(max_taps))
+    if ws is None:
+        ws = _ws.get(need, src.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"letterbox_ragged: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    _check(_lib.vrnet_letterbox_ragged_u8(ptr(img_u8), ptr(label_u8), _geom(geom, B, "letterbox_ragged"), B, ihm, iwm, int(H),
+                                          int(W), int(max_taps), ptr(canvas), ptr(images), ptr(label_out), ptr(flag), ptr(ws),
+                                          ws.numel(), stream()), "letterbox_ragged")
+
+
+def detect_finish_ragged(rows, kept, geom, num_classes, capacity, rows_out, draw_rows, offsets, det_counts, flag):
+    """`detect_finish` with the image shape and the un-map scalars of image b from geom[b]
+    (vrnet_detect_finish_ragged_f32); capacity = (ihm, iwm)."""
+    B, cap = rows.shape[:2]
+    _ragged_check("detect_finish_ragged", (
+        (rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32), (rows_out, (B, cap, 7), torch.float32),
+        (draw_rows, (B * cap, 5), torch.int32), (offsets, (B + 1,), torch.int32), (det_counts, (B, num_classes), torch.int64),
+        (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_detect_finish_ragged_f32(ptr(rows), ptr(kept), _geom(geom, B, "detect_finish_ragged"), B, cap,
+                                               int(num_classes), int(capacity[0]), int(capacity[1]), ptr(rows_out),
+                                               ptr(draw_rows), ptr(offsets), ptr(det_counts), ptr(flag), stream()),
+           "detect_finish_ragged")
+
+
+def seg_predict_ragged_workspace_bytes(B, C, H, W):
+    return _lib.vrnet_seg_predict_ragged_workspace(B, C, H, W)
+
+
+def seg_predict_ragged(x, geom, out, ws, flag=None):
+    """x (B, C, H, W) fp32 -> out (B, ihm, iwm) uint8, the window and size of image b from geom[b], 0 outside the image
+    (vrnet_seg_predict_ragged_f32); ws: seg_predict_ragged_workspace_bytes(B, C, H, W) bytes."""
+    B, C, H, W = x.shape
+    _ragged_check("seg_predict_ragged", ((x, (B, C, H, W), torch.float32), (out, (B,) + tuple(out.shape[1:3]), torch.uint8),
+                                         (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_seg_predict_ragged_f32(ptr(x), _geom(geom, B, "seg_predict_ragged"), B, C, H, W, out.shape[1], out.shape[2],
+                                             ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), "seg_predict_ragged")
+
+
+def render_ragged(frames, class_map, geom, out, palette=None, mix_type=0, alpha=0.7, boxes=None, box_offsets=None,
+                  box_palette=None, counts=None, flag=None):
+    """`render` on padded slots (vrnet_render_ragged_u8): frames / out (B,ihm,iwm,3), class_map (B,ihm,iwm); ih, iw and the
+    thickness of image b from geom[b]; out must not be the frames."""
+    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError("render_ragged: expected contiguous uint8 frames of shape (B, ihm, iwm, 3)")
+    B, ih, iw = frames.shape[:3]
+    n_colors = palette.shape[0] if palette is not None else (counts.shape[1] if counts is not None else 0)
+    n_rows = 0 if boxes is None else boxes.shape[0]
+    _ragged_check("render_ragged", (
+        (frames, (B, ih, iw, 3), torch.uint8), (out, (B, ih, iw, 3), torch.uint8), (class_map, (B, ih, iw), torch.uint8),
+        (palette, (n_colors, 3), torch.uint8), (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32),
+        (counts, (B, n_colors), torch.int64), (flag, (1,), torch.int32),
+        (box_palette, (0 if box_palette is None else box_palette.shape[0], 3), torch.uint8)))
+    if out is None or (n_rows and (box_offsets is None or box_palette is None)):
+        raise RuntimeError("render_ragged: out is required, and box rows need box_offsets and a box_palette")
+    _check(_lib.vrnet_render_ragged_u8(ptr(frames), ptr(class_map), _geom(geom, B, "render_ragged"), B, ih, iw, ptr(palette),
+                                       n_colors, int(mix_type), float(alpha), ptr(boxes) if n_rows else None, ptr(box_offsets),
+                                       n_rows, ptr(box_palette), 0 if box_palette is None else box_palette.shape[0], ptr(out),
+                                       ptr(counts), ptr(flag), stream()), "render_ragged")

@@ -13,7 +13,14 @@ and the letterbox un-map, the renderer's integer rows and the class counts are m
 Bits of `FrameResult.flag` (an int32 word, zeroed by every run; read it when you read a result): render.FLAG_CLASS,
 FLAG_BOX_COLOUR, FLAG_BOX_ROWS (see render.render_frame), FLAG_CANDIDATES -- an image had more candidates than the
 capacity, so only its `cap` best-scored ones were considered -- and FLAG_DET_CLASS -- a kept row with a class id
-outside [0, num_classes), which is not counted."""
+outside [0, num_classes), which is not counted -- and, in a ragged pipeline, FLAG_GEOMETRY -- a record of the geometry
+table had to be clamped by a kernel, which the host checks of `run` rule out.
+
+ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
+size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
+arguments, so ONE captured graph serves any mix of sizes.  `predict_dir` is predict.py's `dir_predict` mode on top of it."""
+import os
+
 import numpy as np
 import torch
 
@@ -21,6 +28,9 @@ from . import data
 from . import render as rendering
 
 FLAG_CANDIDATES, FLAG_DET_CLASS = 8, 16          # NMS_FLAG_* of csrc/nms.hip, above render.FLAG_*
+FLAG_GEOMETRY = 256                              # VR_FLAG_GEOMETRY of csrc/common.h, above evaluate.FLAG_EVAL_*
+# the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
+IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
 
 def validate_config(model, frame_shape, input_shape, batch, max_candidates):
@@ -62,6 +72,32 @@ def validate_inputs(frames_u8, radar, batch, frame_shape, input_shape):
     return f, r
 
 
+def validate_radar(radar, batch, input_shape):
+    """The radar half of `validate_inputs`: (B, 4, H, W) float32 / float64 as a tensor."""
+    r = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
+    if r.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"FramePipeline: expected float32 or float64 radar maps, got {r.dtype}")
+    r = r[None] if batch == 1 and r.dim() == 3 else r
+    if tuple(r.shape) != (batch, 4) + tuple(input_shape):
+        raise RuntimeError(f"FramePipeline: built for radar maps of shape {(batch, 4) + tuple(input_shape)}, got {tuple(r.shape)}")
+    return r
+
+
+def validate_ragged_inputs(frames, radar, sizes, batch, capacity, input_shape, letterbox_image=True, max_taps=None):
+    """The host checks of a ragged `run`, which need no device: frames as a list of `batch` uint8 arrays (ih_b, iw_b, 3) of
+    their own sizes (sizes optional, checked when given) or a padded (batch, ihp, iwp, 3) buffer with sizes (batch, 2);
+    every size inside the capacity, with a non-empty window and within the tap capacity (`data.frame_geometry`: each
+    error names the image index).  Returns (frames as `data.ragged_items` gives them, radar tensor, sizes (B, 2) int64,
+    the geometry table)."""
+    fn = "FramePipeline"
+    items, own = data.ragged_items(frames, sizes, batch, (3,), "frames", fn)
+    if torch.is_tensor(items) and (items.shape[1] > capacity[0] or items.shape[2] > capacity[1]):
+        raise RuntimeError(f"{fn}: the padded buffer {tuple(items.shape[1:3])} is above the capacity {tuple(capacity)}")
+    max_taps = data.default_max_taps(capacity, input_shape) if max_taps is None else max_taps
+    table = data.frame_geometry(own, input_shape, letterbox_image, capacity, max_taps, fn)
+    return items, validate_radar(radar, batch, input_shape), own, table
+
+
 def unmap_scalars(input_shape, image_shape, letterbox_image):
     """(offset, scale): the (y, x) float64 pairs with which decode.yolo_correct_boxes maps a centre, (c - offset) * scale, and a
     size, s * scale -- its own expressions, np.round included; (0, 0), (1, 1) without a letterbox."""
@@ -79,12 +115,16 @@ class FrameResult:
     rows (B, cap, 7) float32: top, left, bottom, right in pixels of the original frame, obj, class_conf, class, in descending
     score order, zero from row kept[b] on; kept (B) int32; det_counts (B, num_classes) int64; class_map (B, ih, iw) uint8;
     seg_counts (B, len(seg palette)) int64 pixels per class and rendered (B, ih, iw, 3) uint8, both None with render=False;
-    flag (1) int32, the data-error bits of the module docstring."""
-    __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag")
+    flag (1) int32, the data-error bits of the module docstring.
+    From a ragged pipeline class_map (B, ihm, iwm) and rendered (B, ihm, iwm, 3) are PADDED tensors of the capacity: image b
+    is `class_map[b, :ih_b, :iw_b]` / `rendered[b, :ih_b, :iw_b]` with (ih_b, iw_b) = sizes[b], everything outside it is 0,
+    and seg_counts[b] counts the image's own pixels only.  sizes: the (B, 2) host integers of that run (None from a
+    fixed-size pipeline)."""
+    __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes")
 
-    def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag):
+    def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None):
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
-        self.seg_counts, self.rendered, self.flag = seg_counts, rendered, flag
+        self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
 
     def detections(self):
         """The list `decode.non_max_suppression` returns: per image an (N_b, 7) float32 numpy array in the same order,
@@ -117,11 +157,18 @@ class FramePipeline:
     buffers are restored afterwards) and captures it as one hipGraph; run() then copies the inputs into the static
     buffers `frames_u8` (B, ih, iw, 3) / `radar` (B, 4, H, W) and replays.  graph=False runs the same calls eagerly, after one
     warm-up pass in the constructor (so `cap` and the buffers exist, and no run builds a cache).  Neither run synchronises
-    with the host."""
+    with the host.
+
+    ragged=True: frame_shape is the CAPACITY (ihm, iwm) and run(frames, radar, sizes=None) takes frames of their own sizes
+    -- a list of B arrays, or a padded (B, ihp, iwp, 3) buffer plus sizes (B, 2).  Every size is validated on the host
+    (inside the capacity, non-empty window, taps within max_taps: `data.default_max_taps`), each frame is copied into the
+    corner of its slot of `frames_u8` and the geometry table into `geom`, all non_blocking, and the ONE graph is replayed:
+    no recapture, no host synchronisation, no per-size cache.  The results are padded (see `FrameResult`).  The radar stays
+    (B, 4, H, W)."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
-                 box_palette=None, graph=True, radar_dtype=torch.float32):
+                 box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
         if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
@@ -147,6 +194,12 @@ class FramePipeline:
         self.frames_u8 = torch.zeros((B, ih, iw, 3), dtype=torch.uint8, device=dev)
         self.radar = torch.zeros((B, 4, H, W), dtype=radar_dtype, device=dev)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ragged, self.sizes = bool(ragged), None
+        if self.ragged:                       # the warm-up and the capture run on a table of frames that fill their slots
+            self.max_taps = data.default_max_taps(self.frame_shape, self.input_shape) if max_taps is None else int(max_taps)
+            table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, self.frame_shape,
+                                        self.max_taps, "FramePipeline")
+            self.geom = torch.from_numpy(table.view(np.uint8).reshape(B, -1).copy()).to(dev)
         self.cap = None                       # the NMS buffers follow the anchor count of the first (warm-up) pass
         self.graph = self.result = None
         if graph:
@@ -171,6 +224,8 @@ class FramePipeline:
     def _chain(self):
         from . import decode, hip            # the library loads with the first pass, not with the package
         S, F = self.input_shape, self.frame_shape
+        if self.ragged:
+            return self._ragged_chain()
         images, _ = data.device_letterbox(self.frames_u8, S, letterbox_image=self.letterbox_image, device=self.device)
         radar = data.device_radar(self.radar, True, self.device) if self.normalise_radar else self.radar
         det, seg = self.model(images, radar)
@@ -197,6 +252,34 @@ class FramePipeline:
                 self.frames_u8, class_map, (self._draw_rows, self._offsets), palette=self.seg_palette, mix_type=self.mix_type,
                 alpha=self.alpha, count=True, box_palette=self.box_palette, thickness=self.thickness, flag=self.flag,
                 device=self.device)
+        result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
+        self._tail(result)
+        return result
+
+    def _ragged_chain(self):
+        """`_chain` with the geometry of every image read from `self.geom` on the device."""
+        from . import decode, hip
+        (H, W), F, B, dev = self.input_shape, self.frame_shape, self.batch, self.device
+        self.flag.zero_()
+        images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        hip.letterbox_ragged(self.frames_u8, None, self.geom, H, W, self.max_taps, images=images, flag=self.flag)
+        radar = data.device_radar(self.radar, True, dev) if self.normalise_radar else self.radar
+        det, seg = self.model(images, radar)
+        pred = decode.decode_outputs(det, (H, W))
+        if self.cap is None:
+            self._allocate(pred.shape[1])
+        rows, scores, classes, ids, counts = self._cand
+        hip.detect_select(pred, self.num_classes, self.conf_thres, rows, scores, classes, ids, counts)
+        hip.nms_capped(rows, scores, classes, ids, counts, B, pred.shape[1], self.cap, self.nms_thres, self._nms_ws,
+                       self._keep, self._kept, self._kept_rows, self.flag)
+        hip.detect_finish_ragged(self._kept_rows, self._kept, self.geom, self.num_classes, F, self._rows, self._draw_rows,
+                                 self._offsets, self._det_counts, self.flag)
+        class_map = decode.seg_predict_ragged(seg, self.geom, F, self.flag)
+        rendered = seg_counts = None
+        if self.render:
+            rendered, seg_counts = rendering.render_frame_ragged(
+                self.frames_u8, self.geom, class_map, (self._draw_rows, self._offsets), palette=self.seg_palette,
+                mix_type=self.mix_type, alpha=self.alpha, count=True, box_palette=self.box_palette, flag=self.flag)
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
         self._tail(result)
         return result
@@ -229,17 +312,72 @@ class FramePipeline:
         with torch.no_grad(), torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
             self.result = self._chain()
 
-    def run(self, frames_u8, radar):
+    def run(self, frames_u8, radar, sizes=None):
         """frames_u8 (B, ih, iw, 3) uint8 RGB and radar (B, 4, H, W) float32 / float64: numpy arrays or tensors, pageable,
         pinned or on the device -> FrameResult.  The inputs are copied into the static buffers (non_blocking), then the graph
-        is replayed (graph=False: the chain is run); no host synchronisation."""
-        f, r = validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape)
+        is replayed (graph=False: the chain is run); no host synchronisation.  A ragged pipeline takes frames_u8 as a list
+        of B arrays of their own sizes, or as a padded buffer with sizes (B, 2) = (ih_b, iw_b); the result carries `sizes`."""
+        if not self.ragged:
+            if sizes is not None:
+                raise RuntimeError("FramePipeline: sizes belong to a ragged pipeline (ragged=True); this one is tied to frames of "
+                                   f"{self.frame_shape[0]} x {self.frame_shape[1]}")
+            f, r = validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape)
+            return self._launch(f, r)
+        return self._launch(*validate_ragged_inputs(frames_u8, radar, sizes, self.batch, self.frame_shape, self.input_shape,
+                                                    self.letterbox_image, self.max_taps))
+
+    def _launch(self, f, r, sizes=None, table=None):
+        """The copies and the replay of `run`, on inputs that `validate_inputs` / `validate_ragged_inputs` returned."""
         with torch.cuda.device(self.device):
-            self.frames_u8.copy_(f, non_blocking=True)
+            if self.ragged:
+                data.fill_slots(self.frames_u8, f, sizes)
+                self.geom.copy_(torch.from_numpy(table.view(np.uint8).reshape(self.batch, -1)), non_blocking=True)
+                self.sizes = sizes
+            else:
+                self.frames_u8.copy_(f, non_blocking=True)
             self.radar.copy_(r, non_blocking=True)
             if self.graph is not None:
                 self.graph.replay()
             else:
                 with torch.no_grad():
                     self.result = self._chain()
+        self.result.sizes = self.sizes
         return self.result
+
+
+def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
+    """predict.py's `dir_predict` mode on a ragged pipeline: every picture of the folder dir_origin_path whose name ends in
+    one of IMAGE_EXTENSIONS (the reference's filter, lower case), in sorted order, with its radar maps
+    radar_root/<frame id>.npz (`data.load_radar` by `data.frame_id` of the file name), in batches of pipeline.batch.  A
+    final partial batch is filled by repeating the last picture; the repeats are dropped here.  Returns a list of
+    (file name, (N, 7) detections) in that order; with dir_save_path the rendered frame of every picture, sliced to its own
+    size, is saved there as <stem>.png through Pillow (the reference renames .jpg to .png; here every picture is a PNG).  Two
+    pictures that differ only in their extension would then share one output file: with dir_save_path that raises before
+    anything runs."""
+    from PIL import Image
+    if not getattr(pipeline, "ragged", False):
+        raise RuntimeError("predict_dir: needs a ragged pipeline (FramePipeline(..., ragged=True)): a folder holds pictures of any size")
+    names = sorted(n for n in os.listdir(dir_origin_path) if n.lower().endswith(IMAGE_EXTENSIONS))
+    if dir_save_path is not None:
+        stems = {}
+        for n in names:
+            other = stems.setdefault(os.path.splitext(n)[0], n)
+            if other != n:
+                raise RuntimeError(f"predict_dir: {other} and {n} would both be saved as {os.path.splitext(n)[0]}.png")
+    B, out = pipeline.batch, []
+    if dir_save_path is not None:
+        os.makedirs(dir_save_path, exist_ok=True)
+    for k in range(0, len(names), B):
+        chunk = names[k:k + B]
+        frames = [np.array(Image.open(os.path.join(dir_origin_path, n)).convert("RGB"), dtype=np.uint8) for n in chunk]
+        radar = [np.asarray(data.load_radar(radar_root, data.frame_id(n)), dtype=np.float32) for n in chunk]
+        fill = B - len(chunk)
+        result = pipeline.run(frames + frames[-1:] * fill, np.stack(radar + radar[-1:] * fill))
+        dets = result.detections()
+        rendered = None if dir_save_path is None or result.rendered is None else result.rendered.cpu().numpy()
+        for b, n in enumerate(chunk):
+            out.append((n, dets[b]))
+            if rendered is not None:
+                ih, iw = (int(v) for v in result.sizes[b])
+                Image.fromarray(rendered[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + ".png"))
+    return out

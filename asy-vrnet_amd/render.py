@@ -212,6 +212,45 @@ def render_frame(frames_u8, class_map=None, results=None, input_shape=None, pale
     return (out, counts) if count else out
 
 
+def render_frame_ragged(frames_u8, geom, class_map=None, results=None, palette=None, mix_type=0, alpha=0.7, count=False,
+                        box_palette=None, out=None, flag=None):
+    """`render_frame` for a batch of images of their own sizes (vrnet_render_ragged_u8).  frames_u8 (B, ihm, iwm, 3) and
+    class_map (B, ihm, iwm) (or None) are padded uint8 DEVICE tensors with image b in the top-left corner of slot b; geom is
+    the (B, hip.GEOM_BYTES) device table of `data.frame_geometry`, which gives every image its size and its outline
+    thickness.  results: None or a pair (rows (N, 5) int32, offsets (B + 1) int32) of device tensors, as
+    `hip.detect_finish_ragged` leaves them.  Returns out (B, ihm, iwm, 3), or (out, counts) with count=True: image b is
+    `out[b, :ih_b, :iw_b]`, equal to `render_frame` on that image alone; every pixel outside it is 0 and is not counted.
+    out must not be the frames.  flag also receives hip.FLAG_GEOMETRY.  No host synchronisation."""
+    from . import hip
+    fn = "render_ragged"
+    img = frames_u8
+    if not (torch.is_tensor(img) and img.is_cuda and img.dtype == torch.uint8 and img.dim() == 4 and img.shape[-1] == 3):
+        raise RuntimeError(f"{fn}: expected padded uint8 frames (B, ihm, iwm, 3) on a GPU")
+    B, ih, iw = img.shape[:3]
+    if class_map is not None and not (torch.is_tensor(class_map) and class_map.dtype == torch.uint8 and
+                                      tuple(class_map.shape) == (B, ih, iw)):
+        raise RuntimeError(f"{fn}: the class map must be a uint8 tensor of shape {(B, ih, iw)}")
+    if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
+        raise RuntimeError(f"{fn}: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
+    if count and class_map is None:
+        raise RuntimeError(f"{fn}: count=True needs a class map")
+    pal = None if class_map is None else _palette(palette, seg_palette(21), fn)
+    rows = offsets = bpal = None
+    if results is not None:
+        rows, offsets = results
+        bpal = _palette(box_palette, det_palette(4), fn)
+    dev = img.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((B, ih, iw, 3), dtype=torch.uint8, device=dev)
+        counts = torch.empty((B, pal.shape[0]), dtype=torch.int64, device=dev) if count else None
+        hip.render_ragged(img.contiguous(), None if class_map is None else class_map.contiguous(), geom, out,
+                          palette=None if pal is None else _palette_on(pal, dev), mix_type=mix_type, alpha=alpha, boxes=rows,
+                          box_offsets=offsets, box_palette=None if bpal is None else _palette_on(bpal, dev), counts=counts,
+                          flag=flag)
+    return (out, counts) if count else out
+
+
 def seg_render(frames_u8, class_map, palette=None, mix_type=0, alpha=0.7, count=False, out=None, flag=None, device="cuda"):
     """deeplab.py:169-222 on the device: frames_u8 (B,ih,iw,3) uint8 original frames and class_map (B,ih,iw) uint8 (what
     `decode.seg_predict` returns) -> the (B,ih,iw,3) uint8 picture of mix_type 0 (Image.blend(frame, palette[class], alpha),

@@ -778,6 +778,64 @@ int vrnet_render_u8(const unsigned char* frames, const unsigned char* class_map,
                     const int* box_offsets, int n_rows, const unsigned char* box_palette, int n_box_colors, int thickness,
                     unsigned char* out, long long* counts, int* flag, void* stream);
 
+/* ---- ragged batches: frames of mixed sizes through the four size-dependent entry points -----------------------------
+ * Added within ABI 11: new symbols only, no existing signature, layout or kernel behaviour changed; hip.py binds every
+ * declared symbol at load time, so a library without them fails the import.
+ * LAYOUT.  Frames, label maps, class maps and rendered frames are padded buffers (B, ihm, iwm[, 3]); (ihm, iwm) is the
+ *   capacity.  Image b occupies the top-left ih_b x iw_b corner of slot b, with row stride iwm.  Every OUTPUT pixel of a
+ *   slot outside its image (class map, rendered frame) is written 0 on every call; input padding is never read into a
+ *   result.
+ * TABLE.  geom (B) records in DEVICE memory, one per image, built on the host per image by the same helpers that compute
+ *   the launch scalars of the fixed entry points, and only read here:
+ *     ih, iw                       the image's own size, 1 <= ih <= ihm, 1 <= iw <= iwm
+ *     nw, nh, dx, dy               the letterbox window (vrnet_letterbox_u8's scalars)
+ *     seg_top, seg_left, seg_nh, seg_nw   the window vrnet_seg_predict_f32 takes (utils_seg/utils.py:19-31; kept apart
+ *                                  from the four above because yolo_correct_boxes rounds where resize_image truncates)
+ *     thickness                    the outline thickness of yolo.py:164
+ *     reserved                     0
+ *     offset_y, offset_x, scale_y, scale_x   the float64 un-map scalars of vrnet_detect_finish_f32
+ *   80 bytes, 8-byte aligned.  The kernels do not trust it: ih / iw are clamped to [0, ihm] / [0, iwm], a window to the
+ *   canvas (sizes to [0, H] / [0, W], then the corner so that it fits), thickness to [1, 2^24], so no access leaves a slot;
+ *   a record that had to be clamped, one with ih <= 0 or iw <= 0 -- or, in the letterbox, whose taps exceed max_taps and
+ *   are truncated -- sets bit 256 (FLAG_GEOMETRY) of *flag (OR-ed in; flag may be NULL except in detect_finish).  An image
+ *   or window clamped to nothing is all padding.
+ * GRIDS are sized by the capacities with the image as grid dimension y: a workgroup lies inside one image and reads one
+ *   record.  All calls: no allocation, no host synchronisation, capturable in a graph.
+ * vrnet_letterbox_ragged_u8: vrnet_letterbox_u8 per image -- img (B, ihm, iwm, 3), label (B, ihm, iwm) -> canvas (B, H, W, 3)
+ *   / images (B, 3, H, W) / label_out (B, H, W), the same Pillow-exact bytes.  The tables of image b are built on the
+ *   device in slot b of the workspace ((W + H) * (3 + max_taps) ints); the horizontal pass writes a (B, ihm, W, 3)
+ *   intermediate; a pass whose axis keeps its size is skipped per image.  max_taps (>= 5): the tap capacity of a table
+ *   entry; image b needs ksize = 2 * ceil(2 * max(in / out, 1)) + 1 per resized axis.
+ *   workspace: vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, max_taps) bytes.
+ * vrnet_detect_finish_ragged_f32: vrnet_detect_finish_f32 with image_h, image_w and the four scalars of image b from geom[b].
+ * vrnet_seg_predict_ragged_f32: vrnet_seg_predict_f32 with the window and the output size of image b from geom[b]; out is
+ *   the padded (B, ihm, iwm) map.  workspace: vrnet_seg_predict_ragged_workspace(B, C, H, W) bytes.
+ * vrnet_render_ragged_u8: vrnet_render_u8 on the padded frames / class_map / out with ih, iw, thickness of image b from
+ *   geom[b]; boxes are clipped to the image's own size and counts cover its own pixels only.  out must not overlap frames
+ *   (the padding is written): there is no in-place form. */
+typedef struct vrnet_frame_geom {
+  int ih, iw;
+  int nw, nh, dx, dy;
+  int seg_top, seg_left, seg_nh, seg_nw;
+  int thickness;
+  int reserved;
+  double offset_y, offset_x, scale_y, scale_x;
+} vrnet_frame_geom;
+long vrnet_letterbox_ragged_workspace(int B, int ihm, int iwm, int H, int W, int max_taps);
+int vrnet_letterbox_ragged_u8(const unsigned char* img, const unsigned char* label, const vrnet_frame_geom* geom, int B,
+                              int ihm, int iwm, int H, int W, int max_taps, unsigned char* canvas, float* images,
+                              unsigned char* label_out, int* flag, void* workspace, long workspace_bytes, void* stream);
+int vrnet_detect_finish_ragged_f32(const float* rows, const int* kept, const vrnet_frame_geom* geom, int B, int cap,
+                                   int num_classes, int ihm, int iwm, float* rows_out, int* draw_rows, int* offsets,
+                                   long long* det_counts, int* flag, void* stream);
+long vrnet_seg_predict_ragged_workspace(int B, int C, int H, int W);
+int vrnet_seg_predict_ragged_f32(const float* x, const vrnet_frame_geom* geom, int B, int C, int H, int W, int ihm, int iwm,
+                                 unsigned char* out, int* flag, void* workspace, long workspace_bytes, void* stream);
+int vrnet_render_ragged_u8(const unsigned char* frames, const unsigned char* class_map, const vrnet_frame_geom* geom, int B,
+                           int ihm, int iwm, const unsigned char* palette, int n_colors, int mix_type, float alpha,
+                           const int* boxes, const int* box_offsets, int n_rows, const unsigned char* box_palette,
+                           int n_box_colors, unsigned char* out, long long* counts, int* flag, void* stream);
+
 /* ---- the record arena of a validation pass (csrc/evalacc.hip) --------------------------------------------------------
  * Added within ABI 11: a new symbol only.
  * vrnet_eval_append_f32, utils/callbacks.py:151-170 (get_map_txt: the rows, scores and coordinates it writes per image)

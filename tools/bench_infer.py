@@ -22,11 +22,15 @@ original size H x W resident on the device, two ways in alternating rounds (the 
 seeded frames, label maps and ground truths): evaluate.EvalPipeline.add per batch, and the per-image path that existed
 before it -- infer.FramePipeline(batch=1).run + metrics.DetectionEvaluator.add (one device-to-host copy per image) +
 metrics.fast_hist -- in images/s, at the thresholds of the first --nms pair (default 0.05/0.5, EvalCallback's), with the mAP
-and mIoU of both.
+and mIoU of both.  With --ragged HxW[,HxW...] it compares infer.FramePipeline(ragged=True) of capacity H x W, every frame AT
+the capacity (the ragged kernels then move the fixed ones' bytes plus the geometry table), with the fixed-size captured
+pipeline at the same shapes on the same frames resident on the device: seven alternating rounds of --steps runs each, frames
+per second from the median round of each, the fixed pipeline's own run-to-run spread beside the ratio, and whether the
+results are equal.
 
     python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
                                 [--seg 1080x1920,480x640] [--letterbox 1080x1920,480x640] [--render 1080x1920,480x640]
-                                [--pipeline 1080x1920] [--evaluate 1080x1920]
+                                [--pipeline 1080x1920] [--evaluate 1080x1920] [--ragged 1080x1920]
 """
 import argparse
 import os
@@ -50,6 +54,7 @@ def main():
     ap.add_argument("--render", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
     ap.add_argument("--pipeline", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920)")
     ap.add_argument("--evaluate", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920)")
+    ap.add_argument("--ragged", default="", help="comma list of capacities HxW (e.g. 1080x1920)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
     from asy_vrnet_amd.data import device_letterbox, resize_image
@@ -63,6 +68,7 @@ def main():
     render_sizes = [tuple(int(v) for v in p.split("x")) for p in args.render.split(",") if p]
     pipeline_sizes = [tuple(int(v) for v in p.split("x")) for p in args.pipeline.split(",") if p]
     evaluate_sizes = [tuple(int(v) for v in p.split("x")) for p in args.evaluate.split(",") if p]
+    ragged_sizes = [tuple(int(v) for v in p.split("x")) for p in args.ragged.split(",") if p]
 
     def timed(fn):
         for _ in range(3):
@@ -238,6 +244,29 @@ def main():
                   f"{ms['pipeline_captured']:.3f} ms ({ms['composition'] / ms['pipeline_captured']:.2f} x the composition, "
                   f"{bs / ms['pipeline_captured'] * 1e3:.1f} frames/s); candidates {pipes[True]._cand[4].tolist()} of capacity "
                   f"{pipes[True].cap}, kept {res.kept.tolist()}, flag {int(res.flag)}; rendered frames equal the composition's: {same}")
+
+        for ih, iw in ragged_sizes:
+            import statistics
+            conf, iou = pairs[0] if pairs else (0.5, 0.4)
+            gen = torch.Generator().manual_seed(bs)
+            frames = torch.randint(0, 256, (bs, ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
+            sizes = [(ih, iw)] * bs
+            pipes = {k: FramePipeline(model, (ih, iw), S, batch=bs, conf_thres=conf, nms_thres=iou, ragged=(k == "ragged"))
+                     for k in ("fixed", "ragged")}
+            variants = {"fixed": lambda: pipes["fixed"].run(frames, r), "ragged": lambda: pipes["ragged"].run(frames, r, sizes)}
+            rounds = {k: [] for k in variants}
+            for _ in range(7):                       # alternating rounds, so that a drift of the clock hits them alike
+                for k, fn in variants.items():
+                    rounds[k].append(timed(fn))
+            med = {k: statistics.median(v) for k, v in rounds.items()}
+            a, b = pipes["fixed"].run(frames, r), pipes["ragged"].run(frames, r, sizes)
+            same = all(torch.equal(getattr(a, k), getattr(b, k)) for k in ("rows", "kept", "det_counts", "class_map", "seg_counts",
+                                                                           "rendered"))
+            for k in ("fixed", "ragged"):
+                print(f"  + ragged {ih}x{iw}, conf {conf} iou {iou}, bs={bs}: {k} captured pipeline median {med[k]:.3f} ms/batch "
+                      f"({bs / med[k] * 1e3:.1f} frames/s), rounds min {min(rounds[k]):.3f} max {max(rounds[k]):.3f} ms")
+            print(f"  + ragged {ih}x{iw}, bs={bs}: ragged / fixed time {med['ragged'] / med['fixed']:.4f} (the fixed pipeline's own rounds "
+                  f"span {max(rounds['fixed']) / min(rounds['fixed']):.4f}); flags {int(a.flag)} {int(b.flag)}; results equal: {same}")
 
         for ih, iw in evaluate_sizes:
             import numpy as np
