@@ -12,10 +12,14 @@ all-reduce of the gradient-arena slice it completed is issued (RCCL's stream wai
 enqueued so far) and overlaps the replay of segment k+1.  Collectives stay outside the captured
 graphs.  Any change of shape (last batch of an epoch, validation loop) needs its own GraphedStep;
 the plain `model(x, r)` path stays available for those.
+
+`TrainStep` is the whole training step on top of that: the real loss on targets in static buffers, the optimizer step and
+the EMA update as one more graph, and the epoch's loss statistics, without a host synchronisation.
 """
+import numpy as np
 import torch
 
-from . import program
+from . import hip, losses, metrics, program
 
 
 def replay_segments(graphs, bucketer):
@@ -84,7 +88,11 @@ class GraphedStep:
             with self.bucketer.deferring():
                 self._capture(cuts)
 
+    def _prologue(self):
+        """Work a subclass puts in front of the forward pass: the first nodes of graph 0 (and of every warm-up pass)."""
+
     def _eager(self):
+        self._prologue()
         det, seg = self.net(self.x, self.r)
         loss = self.loss_fn(det, seg)
         loss.backward()
@@ -97,6 +105,7 @@ class GraphedStep:
         state = {}
 
         def seg0():
+            self._prologue()
             rt, inputs, dets, seg = program.forward_pass(model, self.x, self.r, record=True)
             leaves = [d.requires_grad_(True) for d in dets] + [seg.requires_grad_(True)]
             loss = self.loss_fn(leaves[:3], leaves[3])
@@ -135,3 +144,191 @@ class GraphedStep:
             self.net.sync_buffers()
         replay_segments(self.graphs, self.bucketer)
         return self.loss
+
+
+class TrainStep(GraphedStep):
+    """One captured training step: forward, the reference's loss (`losses.training_loss`: SimOTA YOLO loss, focal or CE,
+    dice, det + 5 seg; utils_fit.py:96-106), backward, optimizer step and EMA update, replayed without a host sync.
+
+        step = TrainStep(net, yolo_loss, optimizer, ema, batch, size, num_seg_classes, max_gt=64)
+        res = step(images, radar, targets, pngs, seg_labels)      # device tensors, valid until the next call
+
+    net: EfficientVRNet or parallel.DataParallelVRNet; optimizer: optim.SGD / optim.Adam; ema: optim.ModelEMA or None.
+    images (B,3,H,W) float32, radar (B,4,H,W) float32, targets: B tensors of (n_i, 5) rows [cx, cy, w, h, cls] (None or
+    empty: no boxes; n_i <= max_gt), pngs (B,H,W) integer labels, seg_labels (B,H,W,ns+1) one-hot (needed for the dice
+    loss and the f-score).  With from_bytes=True images are the letterboxed canvas bytes (B,H,W,3) uint8 and pngs the label
+    bytes (B,H,W) uint8, as `data.device_letterbox(..., normalise=False)` or a dataloader produces them: 4 B per pixel
+    cross PCIe and vrnet_batch_formats_u8, the first node of graph 0, writes the float images, the int64 labels and the
+    one-hot labels straight into the buffers the forward pass and the losses read; seg_labels stays None.
+    Host or device inputs; numpy arrays are taken too.
+
+    Two kinds of graph.  The forward / backward graph(s) are GraphedStep's (three segments under data parallelism, the
+    all-reduces between them); the loss closure is `losses.training_loss_packed` on the static buffers, followed by the
+    f-score (f_score=True) and the addition of the step's values to a running fp64 sum.  The UPDATE graph is always its own:
+    optimizer.step(scalars=rec), then ema.update(model, scalars=rec); it replays behind the last segment, i.e. behind
+    bucketer.wait() under data parallelism.  What changes from step to step -- the learning rate, the EMA decay, Adam's
+    bias corrections -- is read by those kernels from `rec`, a hip.StepScalars record in device memory that every call
+    writes in stream order through a fresh pinned staging tensor: a graph bakes launch scalars in.
+
+    Counters.  Every call reads lr from optimizer.param_groups (so `optim.set_optimizer_lr` works as before), advances
+    Adam's per-parameter `step` and `ema.updates` on the host (`Adam.advance`, `ModelEMA.advance`) and writes their values
+    into the record.  optimizer.state_dict(), ema.updates, the EMA weights and the model's buffers are therefore what the
+    eager loop would have left: checkpoints work, and so does an eager step (zero_grad, model, loss, backward, step,
+    update) for an odd last batch in between.
+
+    Statistics.  res holds total, loss_det, loss_seg (and f_score) of this step; `stats()` returns their means since the
+    last `reset_stats()` with ONE read-back (utils_fit.py reads three values back per iteration).
+
+    Rebuild rule.  The parameters' .grad tensors belong to the step, the momentum, betas, eps, nesterov and the set of
+    updated parameters are baked into the update graph.  Un-freezing parameters (train.py:584), changing the momentum or
+    any shape (batch, size, max_gt) needs a NEW TrainStep.
+
+    Raises at construction: synchronised BatchNorm (inherited), an optimizer whose groups disagree on lr."""
+
+    def __init__(self, net, yolo_loss, optimizer, ema, batch, size, num_seg_classes, max_gt=64, cls_weights=None,
+                 focal_loss=True, dice_loss=True, f_score=False, from_bytes=False, device="cuda", warmup=2, segments=None):
+        optimizer._uniform("lr")
+        dev = torch.device(device)
+        h, w = (size, size) if isinstance(size, int) else size
+        ns = int(num_seg_classes)
+        self.yolo_loss, self.optimizer, self.ema = yolo_loss, optimizer, ema
+        self.batch, self.hw, self.ns, self.max_gt = int(batch), (h, w), ns, int(max_gt)
+        self.focal_loss, self.dice_loss, self.f_score, self.from_bytes = bool(focal_loss), bool(dice_loss), bool(f_score), bool(from_bytes)
+        self.names = ("total", "loss_det", "loss_seg") + (("f_score",) if self.f_score else ())
+        with torch.cuda.device(dev):
+            self.labels = torch.zeros((batch, max(self.max_gt, 1), 5), dtype=torch.float32, device=dev)
+            self.counts = torch.zeros(batch, dtype=torch.int32, device=dev)
+            self.png = torch.zeros((batch, h, w), dtype=torch.int64, device=dev)
+            self.onehot = torch.zeros((batch, h, w, ns + 1), dtype=torch.float32, device=dev)
+            self.images_u8 = torch.zeros((batch, h, w, 3), dtype=torch.uint8, device=dev) if self.from_bytes else None
+            self.labels_u8 = torch.zeros((batch, h, w), dtype=torch.uint8, device=dev) if self.from_bytes else None
+            self.weights = torch.ones(ns, dtype=torch.float32, device=dev)
+            if cls_weights is not None:
+                self.weights.copy_(torch.as_tensor(cls_weights, dtype=torch.float32).reshape(ns))
+            self.rec = torch.zeros(4, dtype=torch.float32, device=dev)            # hip.StepScalars
+            self._acc = torch.zeros(len(self.names) + 1, dtype=torch.float64, device=dev)     # running sums, step count
+        self._vals = None
+        super().__init__(net, self._loss, batch, size, dev, warmup=warmup, segments=segments)
+        self._capture_update()
+        self._acc.zero_()                                # the warm-up passes on zero inputs counted themselves
+        torch.cuda.synchronize(dev)
+
+    def _prologue(self):
+        if self.from_bytes:
+            hip.batch_formats(self.images_u8, self.labels_u8, self.ns, images=self.x, png_out=self.png, onehot=self.onehot)
+
+    def _loss(self, det, seg):
+        total, ldet, lseg = losses.training_loss_packed(self.yolo_loss, det, seg, self.labels, self.counts, self.max_gt, self.png,
+                                                        self.onehot, self.weights, self.ns, self.focal_loss, self.dice_loss)
+        vals = [total.detach(), ldet.detach(), lseg.detach()]
+        if self.f_score:
+            vals.append(metrics.f_score(seg.detach(), self.onehot))
+        self._vals = torch.stack(vals)
+        n = len(vals)
+        self._acc[:n].add_(self._vals)
+        self._acc[n:].add_(1.0)
+        return total
+
+    def _capture_update(self):
+        """The update graph.  The address tables are laid out and uploaded BEFORE the capture (host-to-device copies); inside
+        it the front ends find nothing changed and issue their one launch each."""
+        model, opt = self.model, self.optimizer
+        self._grads = [(p, p.grad) for p in model.parameters() if p.grad is not None]
+        with torch.cuda.device(self.device):
+            tab = opt._live()
+            if tab is None:
+                raise RuntimeError("TrainStep: no parameter of the optimizer received a gradient")
+            self._opt_addrs = tab.addrs
+            if self.ema is not None:
+                self.ema._tensor_table(model)
+            torch.cuda.synchronize(self.device)
+            cur = torch.cuda.current_stream(self.device)
+            self.stream.wait_stream(cur)
+            self.update_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.update_graph, pool=self.graphs[-1].pool(), stream=self.stream,
+                                  capture_error_mode="thread_local"):
+                opt.step(scalars=self.rec)
+                if self.ema is not None:
+                    self.ema.update(model, scalars=self.rec)
+
+    # ---- one step ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _tensor(a):
+        return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+
+    def _validate(self, images, radar, targets, pngs, seg_labels):
+        B, (h, w), ns = self.batch, self.hw, self.ns
+        images, radar, pngs = self._tensor(images), self._tensor(radar), self._tensor(pngs)
+
+        def need(t, what, shape, dtypes):
+            if tuple(t.shape) != shape or t.dtype not in dtypes:
+                raise RuntimeError(f"TrainStep: {what} must be {' / '.join(str(d) for d in dtypes)} of shape {shape}, got "
+                                   f"{t.dtype} {tuple(t.shape)}")
+        ints = (torch.int64, torch.int32, torch.uint8)
+        if self.from_bytes:
+            need(images, "images (from_bytes=True: the letterboxed canvas bytes)", (B, h, w, 3), (torch.uint8,))
+            need(pngs, "pngs (from_bytes=True: the label bytes)", (B, h, w), (torch.uint8,))
+            if seg_labels is not None:
+                raise RuntimeError("TrainStep: from_bytes=True makes the one-hot labels on the device; seg_labels must be None")
+        else:
+            need(images, "images", (B, 3, h, w), (torch.float32,))
+            need(pngs, "pngs", (B, h, w), ints)
+            if seg_labels is None:
+                if self.dice_loss or self.f_score:
+                    raise RuntimeError("TrainStep: the dice loss and the f-score need the one-hot seg_labels (B, H, W, ns + 1)")
+            else:
+                seg_labels = self._tensor(seg_labels)
+                need(seg_labels, "seg_labels", (B, h, w, ns + 1), (torch.float32,))
+        need(radar, "radar", (B, 4, h, w), (torch.float32,))
+        if len(targets) != B:
+            raise RuntimeError(f"TrainStep: {len(targets)} target lists for a batch of {B}")
+        packed, counts = losses.pack_targets(targets, self.max_gt)        # raises, naming the image, above max_gt
+        return images, radar, pngs, seg_labels, packed, counts
+
+    def __call__(self, images, radar, targets, pngs, seg_labels=None):
+        images, radar, pngs, seg_labels, packed, counts = self._validate(images, radar, targets, pngs, seg_labels)
+        opt, ema = self.optimizer, self.ema
+        lr = float(opt._uniform("lr"))
+        with torch.cuda.device(self.device):
+            if any(p.grad is not g for p, g in self._grads):          # an eager step in between took the .grad tensors
+                for p, g in self._grads:
+                    p.grad = g
+                opt._live()                                           # ... and pointed the table's gradient row at its own
+            if opt._table.addrs is not self._opt_addrs:
+                raise RuntimeError("TrainStep: the optimizer's tensor table was laid out anew (parameters un-frozen or groups "
+                                   "changed): build a new TrainStep")
+            if self.from_bytes:
+                self.images_u8.copy_(images, non_blocking=True)
+                self.labels_u8.copy_(pngs, non_blocking=True)
+            else:
+                self.x.copy_(images, non_blocking=True)
+                self.png.copy_(pngs, non_blocking=True)
+                if seg_labels is not None:
+                    self.onehot.copy_(seg_labels, non_blocking=True)
+            self.r.copy_(radar, non_blocking=True)
+            self.labels.copy_(packed, non_blocking=True)
+            self.counts.copy_(counts, non_blocking=True)
+            bc = opt.advance() if hasattr(opt, "advance") else None
+            decay = ema.advance() if ema is not None else 0.0
+            # a FRESH pinned staging tensor per step (as optim._Table.set_row): a host that runs ahead never overwrites a
+            # record a queued copy has yet to read
+            staged = torch.tensor([lr, decay] + list(bc or (1.0, 1.0)), dtype=torch.float32).pin_memory()
+            self.rec.copy_(staged, non_blocking=True)
+            if getattr(self.net, "broadcast_buffers", False) and self.model.training:
+                self.net.sync_buffers()
+            replay_segments(self.graphs, self.bucketer)
+            self.update_graph.replay()
+        return {k: self._vals[i] for i, k in enumerate(self.names)}
+
+    def stats(self):
+        """{"steps": n, "total": mean, "loss_det": mean, "loss_seg": mean[, "f_score": mean]} over the calls since the last
+        `reset_stats()`, accumulated in fp64 on the device: one read-back (and the only synchronisation of an epoch)."""
+        a = self._acc.cpu()
+        n = int(a[-1])
+        out = {"steps": n}
+        for i, k in enumerate(self.names):
+            out[k] = float(a[i]) / n if n else float("nan")
+        return out
+
+    def reset_stats(self):
+        self._acc.zero_()

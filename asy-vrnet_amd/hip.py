@@ -161,6 +161,10 @@ _SIGS = {
     "vrnet_mt_sgd_f32": ([P, P, P, P, P, I, I, I, F, F, I, I, P], I),
     "vrnet_mt_adam_f32": ([P, P, P, P, P, I, I, I, F, F, F, F, I, P], I),
     "vrnet_mt_ema_f32": ([P, P, P, P, I, I, I, F, P], I),
+    "vrnet_mt_sgd_dev_f32": ([P, P, P, P, P, I, I, I, P, F, I, P], I),
+    "vrnet_mt_adam_dev_f32": ([P, P, P, P, P, I, I, I, P, F, F, F, P], I),
+    "vrnet_mt_ema_dev_f32": ([P, P, P, P, I, I, I, P, P], I),
+    "vrnet_adam_bias_correction": ([F, F, I, ctypes.POINTER(F), ctypes.POINTER(F)], I),
     "vrnet_clock_stamp": ([P, P], I),
     "vrnet_mt_copy_f32": ([P, P, P, P, I, I, I, P], I),
     "vrnet_sa_bwd_f32": ([P, L, P, L, P, P, P, P] + [P] * 6 + [P, L] + [P] * 6 + [P, I, L, I, I, I, I, P, L, P], I),
@@ -830,6 +834,49 @@ def mt_adam(addrs, sizes, chunk_tensor, chunk_index, weight_decay, n_tensors, n_
 def mt_ema(addrs, sizes, chunk_tensor, chunk_index, n_tensors, n_chunks, chunk_elems, decay):
     _check(_lib.vrnet_mt_ema_f32(ptr(addrs), ptr(sizes), ptr(chunk_tensor), ptr(chunk_index), n_tensors, n_chunks,
                                  chunk_elems, decay, stream()), "mt_ema")
+
+
+class StepScalars(ctypes.Structure):
+    """vrnet_step_scalars (include/vrnet_hip.h): the 16-byte record the `_dev` updates read from device memory."""
+    _fields_ = [("lr", F), ("ema_decay", F), ("adam_bc1", F), ("adam_bc2_sqrt", F)]
+
+
+def _scalars(s, name):
+    if s.dtype != torch.float32 or s.numel() != 4 or not s.is_contiguous():
+        raise RuntimeError(f"{name}: the step-scalar record is a contiguous float32 GPU tensor of 4 elements "
+                           "(lr, ema_decay, adam_bc1, adam_bc2_sqrt)")
+    return ptr(s)
+
+
+def mt_sgd_dev(addrs, sizes, chunk_tensor, chunk_index, weight_decay, n_tensors, n_chunks, chunk_elems, scalars, momentum,
+               nesterov):
+    """mt_sgd with lr read from the record `scalars` in device memory (vrnet_mt_sgd_dev_f32)."""
+    _check(_lib.vrnet_mt_sgd_dev_f32(ptr(addrs), ptr(sizes), ptr(chunk_tensor), ptr(chunk_index), ptr(weight_decay),
+                                     n_tensors, n_chunks, chunk_elems, _scalars(scalars, "mt_sgd_dev"), momentum,
+                                     int(nesterov), stream()), "mt_sgd_dev")
+
+
+def mt_adam_dev(addrs, sizes, chunk_tensor, chunk_index, weight_decay, n_tensors, n_chunks, chunk_elems, scalars, beta1,
+                beta2, eps):
+    """mt_adam with lr and the bias corrections read from the record (vrnet_mt_adam_dev_f32)."""
+    _check(_lib.vrnet_mt_adam_dev_f32(ptr(addrs), ptr(sizes), ptr(chunk_tensor), ptr(chunk_index), ptr(weight_decay),
+                                      n_tensors, n_chunks, chunk_elems, _scalars(scalars, "mt_adam_dev"), beta1, beta2, eps,
+                                      stream()), "mt_adam_dev")
+
+
+def mt_ema_dev(addrs, sizes, chunk_tensor, chunk_index, n_tensors, n_chunks, chunk_elems, scalars):
+    """mt_ema with the decay read from the record (vrnet_mt_ema_dev_f32)."""
+    _check(_lib.vrnet_mt_ema_dev_f32(ptr(addrs), ptr(sizes), ptr(chunk_tensor), ptr(chunk_index), n_tensors, n_chunks,
+                                     chunk_elems, _scalars(scalars, "mt_ema_dev"), stream()), "mt_ema_dev")
+
+
+def adam_bias_correction(beta1, beta2, step):
+    """(bc1, bc2_sqrt) as vrnet_mt_adam_f32 derives them from `step`: C's double-precision pow / sqrt, rounded to float
+    (host only, no GPU needed)."""
+    bc1, bc2 = F(), F()
+    _check(_lib.vrnet_adam_bias_correction(float(beta1), float(beta2), int(step), ctypes.byref(bc1), ctypes.byref(bc2)),
+           "adam_bias_correction")
+    return bc1.value, bc2.value
 
 
 def mt_copy(addrs, sizes, chunk_tensor, chunk_index, n_tensors, n_chunks, chunk_elems):

@@ -35,6 +35,37 @@ def _pack_labels(labels, device):
     return packed, cnt, G
 
 
+def pack_targets(labels, max_gt, out=None, counts_out=None):
+    """list of (n_i, 5) [cx, cy, w, h, cls] (None or empty: no boxes) -> the pinned host pair (B, max_gt, 5) float32 and
+    (B,) int32 of FIXED shape that `YOLOLoss.forward_packed` takes after one non-blocking copy each; unused rows are zero.
+    With `out` / `counts_out` the pair is filled in place.  n_i > max_gt raises RuntimeError naming the image, before
+    anything is written."""
+    B, max_gt = len(labels), int(max_gt)
+    rows = []
+    for b, l in enumerate(labels):
+        n = int(l.shape[0]) if l is not None and l.numel() else 0
+        if n > max_gt:
+            raise RuntimeError(f"pack_targets: image {b} has {n} boxes, above max_gt = {max_gt}")
+        if n and (l.dim() != 2 or l.shape[1] != 5):
+            raise RuntimeError(f"pack_targets: image {b}: expected (n, 5) rows [cx, cy, w, h, cls], got {tuple(l.shape)}")
+        rows.append(n)
+    if out is None:
+        out = torch.zeros((B, max(max_gt, 1), 5), dtype=torch.float32)
+        out = out.pin_memory() if torch.cuda.is_available() else out
+    if counts_out is None:
+        counts_out = torch.zeros(B, dtype=torch.int32)
+        counts_out = counts_out.pin_memory() if torch.cuda.is_available() else counts_out
+    if tuple(out.shape) != (B, max(max_gt, 1), 5) or out.dtype != torch.float32 or tuple(counts_out.shape) != (B,) \
+            or counts_out.dtype != torch.int32 or out.is_cuda or counts_out.is_cuda:
+        raise RuntimeError(f"pack_targets: the buffers must be host tensors ({B}, {max(max_gt, 1)}, 5) float32 and ({B},) int32")
+    out.zero_()
+    for b, l in enumerate(labels):
+        if rows[b]:
+            out[b, :rows[b]] = l.detach().to("cpu", torch.float32)
+        counts_out[b] = rows[b]
+    return out, counts_out
+
+
 def _gpu_maps(inputs):
     outs = [t if (t.is_contiguous() and t.dtype == torch.float32) else t.contiguous().float() for t in inputs]
     if not outs or not all(o.is_cuda and o.dim() == 4 and o.shape[:2] == outs[0].shape[:2] for o in outs):
@@ -80,13 +111,28 @@ class YOLOLoss(nn.Module):
         self.strides = list(strides)
         self.fp16 = fp16
         self.log_vars = nn.Parameter(torch.zeros(3))
-        self.last_stats = None          # device tensor [loss, num_fg, sum iou, sum obj, sum cls] of the last call
+        self.last_stats = None          # device tensor [loss, num_fg, sum iou, sum obj, sum cls] of the last call that took gradients
 
     def forward(self, inputs, labels=None, _scale=1.0):
         if len(inputs) != len(self.strides) or inputs[0].shape[1] != 5 + self.num_classes:
             raise RuntimeError(f"YOLOLoss: expects {len(self.strides)} maps with {5 + self.num_classes} channels")
         packed, counts, G = _pack_labels(labels, inputs[0].device)
         loss = _YoloLossFn.apply(self.strides, packed, counts, G, float(_scale), *inputs)
+        self.last_stats = getattr(loss.grad_fn, "stats", None)
+        return loss
+
+    def forward_packed(self, inputs, packed, counts, max_gt, _scale=1.0):
+        """`forward` on targets that already sit on the device in a FIXED shape: packed (B, max_gt, 5) float32 and counts
+        (B,) int32, `pack_targets`' pair after its copy.  Nothing is allocated from or copied off the host, so the call
+        can be captured in a hipGraph; slots at and above counts[b] are never read."""
+        if len(inputs) != len(self.strides) or inputs[0].shape[1] != 5 + self.num_classes:
+            raise RuntimeError(f"YOLOLoss: expects {len(self.strides)} maps with {5 + self.num_classes} channels")
+        B, G = inputs[0].shape[0], max(int(max_gt), 1)
+        if not (packed.is_cuda and packed.dtype == torch.float32 and tuple(packed.shape) == (B, G, 5) and packed.is_contiguous()
+                and counts.is_cuda and counts.dtype == torch.int32 and tuple(counts.shape) == (B,)):
+            raise RuntimeError(f"YOLOLoss.forward_packed: expects GPU targets ({B}, {G}, 5) float32 and counts ({B},) int32")
+        loss = _YoloLossFn.apply(self.strides, packed, counts, int(max_gt), float(_scale), *inputs)
+        self.last_stats = getattr(loss.grad_fn, "stats", None)
         return loss
 
     @torch.no_grad()
@@ -169,6 +215,16 @@ def training_loss(yolo_loss, outputs, outputs_seg, targets, pngs, seg_labels, we
     """utils/utils_fit.py:96-106 (the active fp16 branch): loss_seg = Focal|CE (+ Dice); total = loss_det + 5 * loss_seg.
     The factor 5 is folded into the seg kernel's gradient.  Returns (total, loss_det, loss_seg)."""
     loss_det = yolo_loss(outputs, targets)
+    seg5 = _seg(outputs_seg, pngs, seg_labels if dice_loss else None, weights, focal=focal_loss, dice=dice_loss, scale=5.0)
+    return loss_det + seg5, loss_det, seg5 / 5.0
+
+
+def training_loss_packed(yolo_loss, outputs, outputs_seg, packed, counts, max_gt, pngs, seg_labels, weights, num_class_seg,
+                         focal_loss=True, dice_loss=True):
+    """`training_loss` on `pack_targets`' device pair instead of a list of label rows, and on pngs (int64), seg_labels and
+    weights (float32) that already live on the device: no allocation from and no copy off the host, so a hipGraph can
+    capture it (graph.TrainStep).  Returns (total, loss_det, loss_seg)."""
+    loss_det = yolo_loss.forward_packed(outputs, packed, counts, max_gt)
     seg5 = _seg(outputs_seg, pngs, seg_labels if dice_loss else None, weights, focal=focal_loss, dice=dice_loss, scale=5.0)
     return loss_det + seg5, loss_det, seg5 / 5.0
 

@@ -197,11 +197,16 @@ class SGD(_FusedOptimizer):
                                   "dampening": 0})
 
     @torch.no_grad()
-    def step(self):
+    def step(self, scalars=None):
+        """scalars: a device tensor holding hip.StepScalars; lr is then read from it on the device (capturable)."""
         tab = self._live()
         if tab is None:
             return
         lr, mu, nest = self._uniform("lr"), self._uniform("momentum"), self._uniform("nesterov")
+        if scalars is not None:
+            hip.mt_sgd_dev(tab.addrs, tab.sizes, tab.chunk_tensor, tab.chunk_index, tab.wd, tab.n, tab.n_chunks, CHUNK, scalars,
+                           float(mu), bool(nest))
+            return
         hip.mt_sgd(tab.addrs, tab.sizes, tab.chunk_tensor, tab.chunk_index, tab.wd, tab.n, tab.n_chunks, CHUNK, float(lr),
                    float(mu), bool(nest), False)
 
@@ -215,16 +220,38 @@ class Adam(_FusedOptimizer):
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         super().__init__(params, {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay})
 
-    @torch.no_grad()
-    def step(self):
-        tab = self._live()
-        if tab is None:
-            return
-        lr, (b1, b2), eps = self._uniform("lr"), self._uniform("betas"), self._uniform("eps")
+    def _next_step(self, tab):
         nxt = [int(st.get("step", 0)) + 1 for st in tab.states]
         if len(set(nxt)) != 1:               # validated BEFORE any counter moves: an error leaves the state untouched
             raise RuntimeError("fused Adam: parameters with different step counts in one table (un-freeze with a new "
                                "optimizer, as train.py:575-590 does)")
+        return nxt[0]
+
+    def advance(self):
+        """Moves the per-parameter step counters on by one, as `step()` does, and returns (bc1, bc2_sqrt) of the new count for
+        the record of `step(scalars=...)`, which leaves the counters alone.  (None when no parameter has a gradient.)"""
+        tab = self._live()
+        if tab is None:
+            return None
+        b1, b2 = self._uniform("betas")
+        nxt = self._next_step(tab)
+        for st in tab.states:
+            st["step"] = nxt
+        return hip.adam_bias_correction(b1, b2, nxt)
+
+    @torch.no_grad()
+    def step(self, scalars=None):
+        """scalars: a device tensor holding hip.StepScalars; lr and the bias corrections are then read from it on the device
+        (capturable) and the step counters stay with the caller (`advance`)."""
+        tab = self._live()
+        if tab is None:
+            return
+        lr, (b1, b2), eps = self._uniform("lr"), self._uniform("betas"), self._uniform("eps")
+        if scalars is not None:
+            hip.mt_adam_dev(tab.addrs, tab.sizes, tab.chunk_tensor, tab.chunk_index, tab.wd, tab.n, tab.n_chunks, CHUNK, scalars,
+                            float(b1), float(b2), float(eps))
+            return
+        nxt = [self._next_step(tab)]
         for st in tab.states:
             st["step"] = nxt[0]
         hip.mt_adam(tab.addrs, tab.sizes, tab.chunk_tensor, tab.chunk_index, tab.wd, tab.n, tab.n_chunks, CHUNK, float(lr),
@@ -293,27 +320,44 @@ class ModelEMA:
     def refresh(self):
         self._pairs = None
 
-    def update(self, model):
+    def advance(self):
+        """Counts one update, as `update()` does, and returns its decay rounded to float for the record of
+        `update(model, scalars=...)`, which leaves the counter alone."""
+        self.updates += 1
+        return hip.F(self.decay(self.updates)).value
+
+    def _tensor_table(self, model):
+        """The (ema, model) address table for `model`, resolved once per model object."""
+        model = de_parallel(model)
+        if self._pairs is None or self._pairs[0] is not model:
+            msd = model.state_dict()
+            es, ms = [], []
+            for k, v in self.ema.state_dict().items():
+                if v.dtype.is_floating_point and v.numel() > 0:
+                    es.append(v)
+                    ms.append(msd[k].detach())
+            _check_tensors(es)
+            _check_tensors(ms, es)
+            self._pairs = (model, es, ms)
+        _, es, ms = self._pairs
+        t = self._table
+        t.layout((id(model), len(es)), [e.numel() for e in es], 2, es[0].device)
+        t.set_row(0, es)
+        t.set_row(1, ms)
+        return t
+
+    def update(self, model, scalars=None):
+        """scalars: a device tensor holding hip.StepScalars; the decay is then read from it on the device (capturable) and
+        the update counter stays with the caller (`advance`)."""
         with torch.no_grad():
-            self.updates += 1
-            d = self.decay(self.updates)
-            model = de_parallel(model)
-            if self._pairs is None or self._pairs[0] is not model:
-                msd = model.state_dict()
-                es, ms = [], []
-                for k, v in self.ema.state_dict().items():
-                    if v.dtype.is_floating_point and v.numel() > 0:
-                        es.append(v)
-                        ms.append(msd[k].detach())
-                _check_tensors(es)
-                _check_tensors(ms, es)
-                self._pairs = (model, es, ms)
-            _, es, ms = self._pairs
-            t = self._table
-            t.layout((id(model), len(es)), [e.numel() for e in es], 2, es[0].device)
-            t.set_row(0, es)
-            t.set_row(1, ms)
-            hip.mt_ema(t.addrs, t.sizes, t.chunk_tensor, t.chunk_index, t.n, t.n_chunks, CHUNK, float(d))
+            if scalars is None:
+                self.updates += 1
+                d = self.decay(self.updates)
+            t = self._tensor_table(model)
+            if scalars is not None:
+                hip.mt_ema_dev(t.addrs, t.sizes, t.chunk_tensor, t.chunk_index, t.n, t.n_chunks, CHUNK, scalars)
+            else:
+                hip.mt_ema(t.addrs, t.sizes, t.chunk_tensor, t.chunk_index, t.n, t.n_chunks, CHUNK, float(d))
 
     def update_attr(self, model, include=(), exclude=("process_group", "reducer")):
         copy_attr(self.ema, model, include, exclude)

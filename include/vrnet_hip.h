@@ -578,6 +578,32 @@ int vrnet_mt_ema_f32(const long long* addrs, const long* sizes, const int* chunk
 int vrnet_mt_copy_f32(const long long* addrs, const long* sizes, const int* chunk_tensor, const int* chunk_index,
                       int n_tensors, int n_chunks, int chunk_elems, void* stream);
 
+/* The same three updates with the values that change from step to step read from DEVICE memory, for a captured hipGraph
+ * (graph.TrainStep): a graph bakes launch scalars in, and lr (reset every epoch, nets/yolo_training.py:544-548), the EMA
+ * decay ramp (yolo_training.py:466-468) and Adam's bias corrections change during a run.  The host writes one 16-byte
+ * record per step, in stream order before the graph; momentum, betas, eps and nesterov stay launch constants.  The
+ * per-element arithmetic is the scalar forms' own (shared device functions), so for the same values the results are the
+ * same bits; vrnet_mt_sgd_dev_f32 is the first_step = 0 form (buffers exist and start at zero).
+ * Added within ABI 11: new symbols only, no existing signature, layout or kernel behaviour changed; hip.py binds every
+ * declared symbol at import, so a library older than this header fails to load there. */
+typedef struct vrnet_step_scalars {
+  float lr;             /* learning rate of this step */
+  float ema_decay;      /* ModelEMA: decay * (1 - exp(-updates / tau)), rounded to float */
+  float adam_bc1;       /* 1 - beta1^step           } as vrnet_adam_bias_correction returns them */
+  float adam_bc2_sqrt;  /* sqrt(1 - beta2^step)     } */
+} vrnet_step_scalars;
+int vrnet_mt_sgd_dev_f32(const long long* addrs, const long* sizes, const int* chunk_tensor, const int* chunk_index,
+                         const float* weight_decay, int n_tensors, int n_chunks, int chunk_elems,
+                         const vrnet_step_scalars* s, float momentum, int nesterov, void* stream);
+int vrnet_mt_adam_dev_f32(const long long* addrs, const long* sizes, const int* chunk_tensor, const int* chunk_index,
+                          const float* weight_decay, int n_tensors, int n_chunks, int chunk_elems,
+                          const vrnet_step_scalars* s, float beta1, float beta2, float eps, void* stream);
+int vrnet_mt_ema_dev_f32(const long long* addrs, const long* sizes, const int* chunk_tensor, const int* chunk_index,
+                         int n_tensors, int n_chunks, int chunk_elems, const vrnet_step_scalars* s, void* stream);
+/* HOST helper, no launch: the bias corrections vrnet_mt_adam_f32 derives from `step` (>= 1) in double precision and
+ * rounds to float -- bc1 = 1 - beta1^step, bc2_sqrt = sqrt(1 - beta2^step); bc1 and bc2_sqrt are HOST pointers. */
+int vrnet_adam_bias_correction(float beta1, float beta2, int step, float* bc1, float* bc2_sqrt);
+
 /* ---- box decode ----------------------------------------------------------------------------
  * decode_outputs, utils/utils_bbox.py:32-84: levels[l] = raw head map (B, C = 5+num_classes, hs[l], ws[l]) NCHW (the
  * hot path's det outputs); out (B, sum_l hs*ws, C): [cx/in_w, cy/in_h, w/in_w, h/in_h, sigmoid(obj), sigmoid(cls)...],
