@@ -75,6 +75,7 @@ typedef struct vrnet_frame_geom {
 } vrnet_frame_geom;
 }
 #define VR_FLAG_GEOMETRY 256                    /* a record that had to be clamped; bits 1..128: render / nms / evalacc */
+#define VR_FLAG_BOX_COUNT 512                   /* traintargets.hip: a box count outside [0, max_gt], clamped */
 
 __device__ __forceinline__ int vr_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -103,6 +104,18 @@ __device__ __forceinline__ vrnet_frame_geom vr_geom_load(const vrnet_frame_geom*
           g.seg_left != t.seg_left || g.seg_top != t.seg_top;
   }
   return g;
+}
+
+// Pillow's nearest resize of an axis in -> out (Geometry.c ImagingScaleAffine): the source index of each output index, a
+// running double sum (not x * a0), so it is sequential: one thread runs it.  Shared by the label half of the letterbox
+// (csrc/letterbox.hip) and the segmentation targets of the training step (csrc/traintargets.hip).
+__device__ inline void vr_nearest_indices(int in, int out, int* idx) {
+  const double a0 = (double)in / out;
+  double xo = a0 * 0.5;
+  for (int x = 0; x < out; ++x) {
+    idx[x] = (int)xo;
+    xo += a0;
+  }
 }
 
 static inline bool vr_planes_out_ok(const vrnet_planes_out* o, int C) {

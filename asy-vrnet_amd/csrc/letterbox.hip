@@ -72,16 +72,6 @@ __device__ void bicubic_taps(int xx, int in, int out, int cap, int* bounds, int*
   bounds[2 * xx + 1] = n;
 }
 
-// Geometry.c ImagingScaleAffine: the source index of each output index, a running sum (not x * a0)
-__device__ void nearest_indices(int in, int out, int* idx) {
-  const double a0 = (double)in / out;
-  double xo = a0 * 0.5;
-  for (int x = 0; x < out; ++x) {
-    idx[x] = (int)xo;
-    xo += a0;
-  }
-}
-
 __global__ __launch_bounds__(256) void letterbox_tables_kernel(const LetterboxArgs p) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   const bool pixels = p.canvas || p.images;
@@ -90,8 +80,8 @@ __global__ __launch_bounds__(256) void letterbox_tables_kernel(const LetterboxAr
   } else if (e < p.nw + p.nh) {
     if (pixels && p.nh != p.ih) bicubic_taps(e - p.nw, p.ih, p.nh, p.ksv, p.vb, p.vk);
   } else if (p.label_out) {
-    if (e == p.nw + p.nh) nearest_indices(p.iw, p.nw, p.xi);
-    if (e == p.nw + p.nh + 1) nearest_indices(p.ih, p.nh, p.yi);
+    if (e == p.nw + p.nh) vr_nearest_indices(p.iw, p.nw, p.xi);
+    if (e == p.nw + p.nh + 1) vr_nearest_indices(p.ih, p.nh, p.yi);
   }
 }
 
@@ -258,8 +248,8 @@ __global__ __launch_bounds__(256) void letterbox_ragged_tables_kernel(const Ragg
     const int y = e - p.W;
     if (y < g.nh && pixels && g.nh != g.ih) bicubic_taps(y, g.ih, g.nh, p.cap, s.vb, s.vk);
   } else if (p.label_out) {
-    if (e == p.W + p.H) nearest_indices(g.iw, g.nw, s.xi);
-    if (e == p.W + p.H + 1) nearest_indices(g.ih, g.nh, s.yi);
+    if (e == p.W + p.H) vr_nearest_indices(g.iw, g.nw, s.xi);
+    if (e == p.W + p.H + 1) vr_nearest_indices(g.ih, g.nh, s.yi);
   }
 }
 

@@ -347,6 +347,125 @@ def device_letterbox_ragged(frames, sizes, input_shape, labels=None, letterbox_i
     return (images if normalise else canvas), out_lab
 
 
+def pack_boxes(boxes, max_gt):
+    """B arrays of (n_i, 5) INTEGER rows x1, y1, x2, y2, cls in pixels of the original image (`parse_annotation_line`'s;
+    None or empty: no boxes) -> the pinned host pair (B, max_gt, 5) int32 and (B,) int32 that `hip.box_targets_ragged` takes
+    after one non-blocking copy each, as `losses.pack_targets` packs float targets; unused rows are zero.  Raises
+    RuntimeError naming the image for more than max_gt rows, for values that are not integers (the reference parses the
+    annotation with int()) or outside int32, and for a wrong shape -- before anything is written."""
+    B, max_gt = len(boxes), int(max_gt)
+    rows = []
+    for b, a in enumerate(boxes):
+        if a is None:
+            rows.append(None)
+            continue
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.size == 0:
+            rows.append(None)
+            continue
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise RuntimeError(f"pack_boxes: image {b}: boxes are integer pixel rows x1, y1, x2, y2, cls, got {a.dtype}")
+        if a.ndim != 2 or a.shape[1] != 5:
+            raise RuntimeError(f"pack_boxes: image {b}: expected (n, 5) rows x1, y1, x2, y2, cls, got {a.shape}")
+        if a.shape[0] > max_gt:
+            raise RuntimeError(f"pack_boxes: image {b} has {a.shape[0]} boxes, above max_gt = {max_gt}")
+        if a.min() < -2 ** 31 or a.max() >= 2 ** 31:
+            raise RuntimeError(f"pack_boxes: image {b}: a value outside int32")
+        rows.append(a.astype(np.int32))
+    out = torch.zeros((B, max(max_gt, 1), 5), dtype=torch.int32)
+    counts = torch.zeros(B, dtype=torch.int32)
+    if torch.cuda.is_available():
+        out, counts = out.pin_memory(), counts.pin_memory()
+    for b, a in enumerate(rows):
+        if a is not None:
+            out[b, :len(a)] = torch.from_numpy(a)
+            counts[b] = len(a)
+    return out, counts
+
+
+def device_train_batch_ragged(frames, sizes, input_shape, labels, boxes, num_classes_seg, max_gt=64, letterbox_image=True,
+                              capacity=None, max_taps=None, flag=None, device="cuda"):
+    """The dataset item of the reference's training path (`random=False`: `letterbox_sample`, `boxes_xyxy_to_cxcywh`,
+    `seg_targets`, the image half of `make_sample`) for a batch of RAW frames of different sizes, ON THE DEVICE: one call of
+    vrnet_letterbox_ragged_u8 (the float images), one of vrnet_seg_targets_ragged_u8 and one of
+    vrnet_box_targets_ragged_f32.  frames / labels / sizes / capacity / max_taps: as `device_letterbox_ragged` takes them
+    (labels are required); boxes: B arrays of (n_i, 5) integer rows in original pixels (`pack_boxes`).  Returns (images
+    (B,3,H,W) f32, png (B,H,W) int64, onehot (B,H,W,ns+1) f32, targets (B,max_gt,5) f32 rows [cx, cy, w, h, cls], counts (B)
+    int32): what `losses.training_loss_packed` reads, bit for bit what the host functions give per image."""
+    from . import hip
+    fn = "device_train_batch_ragged"
+    items, own = ragged_items(frames, sizes, None, (3,), "frames", fn)
+    B = len(own)
+    if labels is None:
+        raise RuntimeError(f"{fn}: the label maps are required")
+    labs = ragged_items(labels, own, B, (), "label maps", fn)[0]
+    if len(boxes) != B:
+        raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
+    if capacity is None:
+        capacity = tuple(items.shape[1:3]) if torch.is_tensor(items) else (int(own[:, 0].max()), int(own[:, 1].max()))
+    ihm, iwm = (int(v) for v in capacity)
+    for t in (items, labs):
+        if torch.is_tensor(t) and (t.shape[1] > ihm or t.shape[2] > iwm):
+            raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {(ihm, iwm)}")
+    H, W = (int(v) for v in input_shape)
+    ns = int(num_classes_seg)
+    max_taps = default_max_taps((ihm, iwm), (H, W)) if max_taps is None else int(max_taps)
+    tab = frame_geometry(own, (H, W), letterbox_image, (ihm, iwm), max_taps, fn)
+    packed, counts = pack_boxes(boxes, max_gt)
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        geom = torch.from_numpy(tab.view(np.uint8).reshape(B, -1)).to(dev, non_blocking=True)
+        img = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
+        fill_slots(img, items, own)
+        lab = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
+        fill_slots(lab, labs, own)
+        images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        hip.letterbox_ragged(img, None, geom, H, W, max_taps, images=images, flag=flag)
+        png, onehot = hip.seg_targets_ragged(lab, geom, H, W, ns, flag=flag)
+        targets, counts_out = hip.box_targets_ragged(packed.to(dev, non_blocking=True), counts.to(dev, non_blocking=True), geom,
+                                                     (ihm, iwm), H, W, flag=flag)
+    return images, png, onehot, targets, counts_out
+
+
+class FrameDataset(torch.utils.data.Dataset):
+    """The decode-only dataset in front of `graph.TrainStep(from_frames=True)`: item i is what YoloDataset reads from disk
+    for annotation line i (dataloader.py:73-80, 111-129) and nothing more -- no resize, no box mapping, no one-hot:
+    (frame (ih, iw, 3) uint8 RGB, radar (4, H, W) float32 as stored, boxes (n, 5) int64 in original pixels, label (ih, iw)
+    uint8, (ih, iw)).  The JPEG is the first field of the line; its frame id (`frame_id`) names
+    seg_dataset_path/VOC2007/SegmentationClass/<id>.png and radar_root/<id>.npz.  A label map of another size than its
+    frame raises: the device letterbox resizes both by one geometry record."""
+
+    def __init__(self, annotation_lines, seg_dataset_path, radar_root):
+        self.annotation_lines = list(annotation_lines)
+        self.seg_dataset_path, self.radar_root = seg_dataset_path, radar_root
+
+    def __len__(self):
+        return len(self.annotation_lines)
+
+    def __getitem__(self, index):
+        from PIL import Image
+        line = self.annotation_lines[index % len(self.annotation_lines)]
+        fid = frame_id(line)
+        path, boxes = parse_annotation_line(line)
+        frame = np.array(Image.open(path).convert("RGB"), dtype=np.uint8)
+        label = np.array(Image.open(os.path.join(self.seg_dataset_path, "VOC2007/SegmentationClass", fid + ".png")))
+        if label.ndim != 2 or label.dtype != np.uint8:
+            raise RuntimeError(f"FrameDataset: {fid}.png: expected a single-channel 8-bit label map, got {label.dtype} {label.shape}")
+        if label.shape != frame.shape[:2]:
+            raise RuntimeError(f"FrameDataset: {fid}: the label map is {label.shape}, the frame {frame.shape[:2]}")
+        radar = np.asarray(load_radar(self.radar_root, fid), dtype=np.float32)
+        return frame, radar, boxes.astype(np.int64), label, frame.shape[:2]
+
+
+def frames_collate(batch):
+    """Items of `FrameDataset` -> the arguments of `TrainStep(from_frames=True)`'s call: (frames: list of (ih_b, iw_b, 3)
+    uint8 tensors, radar (B, 4, H, W) float32, boxes: list of (n_b, 5) int64 arrays, labels: list of (ih_b, iw_b) uint8
+    tensors, sizes (B, 2) int64 array).  Host only."""
+    frames, radars, boxes, labels, sizes = zip(*batch)
+    return ([torch.from_numpy(np.ascontiguousarray(f)) for f in frames], torch.from_numpy(np.stack(radars)).float(),
+            list(boxes), [torch.from_numpy(np.ascontiguousarray(l)) for l in labels], np.array(sizes, np.int64).reshape(-1, 2))
+
+
 def device_radar(radar, normalise=True, device="cuda", out=None):
     """The radar half of the prediction scripts ON THE DEVICE (vrnet_radar_normalise): radar (B, 4, H, W) float32 or
     float64 maps (a single (4, H, W) frame counts as B = 1), numpy array or tensor -> (B, 4, H, W) float32 on the device.

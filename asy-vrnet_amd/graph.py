@@ -19,7 +19,7 @@ the EMA update as one more graph, and the epoch's loss statistics, without a hos
 import numpy as np
 import torch
 
-from . import hip, losses, metrics, program
+from . import data, hip, losses, metrics, program
 
 
 def replay_segments(graphs, bucketer):
@@ -162,6 +162,23 @@ class TrainStep(GraphedStep):
     one-hot labels straight into the buffers the forward pass and the losses read; seg_labels stays None.
     Host or device inputs; numpy arrays are taken too.
 
+    With from_frames=True (not together with from_bytes) the step takes RAW frames of mixed sizes and does the reference's
+    `random=False` dataset item inside graph 0 as well:
+
+        step = TrainStep(net, yolo_loss, optimizer, ema, batch, size, ns, from_frames=True, capacity=(ihm, iwm))
+        res = step(frames, radar, boxes, labels, sizes=None)
+
+    frames / labels: a list of B uint8 arrays (ih_b, iw_b, 3) / (ih_b, iw_b) of their own sizes, or padded buffers (B, ihp,
+    iwp[, 3]) plus sizes (B, 2) host integers, as `FramePipeline(ragged=True)` takes them; radar (B,4,H,W) float32, taken as
+    it is; boxes: B arrays of (n_i, 5) INTEGER rows x1, y1, x2, y2, cls in pixels of the original image
+    (`data.parse_annotation_line`; None or empty: no boxes).  One host validation per call, before anything is enqueued:
+    capacity, empty window, tap capacity (`data.frame_geometry`), box counts and dtypes (`data.pack_boxes`).  Then the
+    frames and label maps are copied into the corners of their slots, the geometry table and the boxes go up through fresh
+    pinned staging tensors, and the first nodes of graph 0 -- vrnet_letterbox_ragged_u8, vrnet_seg_targets_ragged_u8,
+    vrnet_box_targets_ragged_f32 -- write the float images, the labels, the one-hot labels, the packed targets and their
+    counts in place.  `stats()` then carries "flag": the flag word of those kernels (hip.FLAG_GEOMETRY, hip.FLAG_BOX_COUNT;
+    0 for inputs that passed the host validation), read back in the same single read-back; `reset_stats()` clears it.
+
     Two kinds of graph.  The forward / backward graph(s) are GraphedStep's (three segments under data parallelism, the
     all-reduces between them); the loss closure is `losses.training_loss_packed` on the static buffers, followed by the
     f-score (f_score=True) and the addition of the step's values to a running fp64 sum.  The UPDATE graph is always its own:
@@ -186,14 +203,20 @@ class TrainStep(GraphedStep):
     Raises at construction: synchronised BatchNorm (inherited), an optimizer whose groups disagree on lr."""
 
     def __init__(self, net, yolo_loss, optimizer, ema, batch, size, num_seg_classes, max_gt=64, cls_weights=None,
-                 focal_loss=True, dice_loss=True, f_score=False, from_bytes=False, device="cuda", warmup=2, segments=None):
+                 focal_loss=True, dice_loss=True, f_score=False, from_bytes=False, device="cuda", warmup=2, segments=None,
+                 from_frames=False, capacity=None, max_taps=None, letterbox_image=True):
         optimizer._uniform("lr")
+        if from_frames and from_bytes:
+            raise RuntimeError("TrainStep: from_frames and from_bytes exclude each other (raw frames, or a letterboxed batch)")
+        if from_frames and capacity is None:
+            raise RuntimeError("TrainStep: from_frames=True needs capacity = (ihm, iwm), the largest frame a call may bring")
         dev = torch.device(device)
         h, w = (size, size) if isinstance(size, int) else size
         ns = int(num_seg_classes)
         self.yolo_loss, self.optimizer, self.ema = yolo_loss, optimizer, ema
         self.batch, self.hw, self.ns, self.max_gt = int(batch), (h, w), ns, int(max_gt)
         self.focal_loss, self.dice_loss, self.f_score, self.from_bytes = bool(focal_loss), bool(dice_loss), bool(f_score), bool(from_bytes)
+        self.from_frames = bool(from_frames)
         self.names = ("total", "loss_det", "loss_seg") + (("f_score",) if self.f_score else ())
         with torch.cuda.device(dev):
             self.labels = torch.zeros((batch, max(self.max_gt, 1), 5), dtype=torch.float32, device=dev)
@@ -206,16 +229,44 @@ class TrainStep(GraphedStep):
             if cls_weights is not None:
                 self.weights.copy_(torch.as_tensor(cls_weights, dtype=torch.float32).reshape(ns))
             self.rec = torch.zeros(4, dtype=torch.float32, device=dev)            # hip.StepScalars
-            self._acc = torch.zeros(len(self.names) + 1, dtype=torch.float64, device=dev)     # running sums, step count
+            # running sums, step count; from_frames: the flag word too, so that stats() stays one read-back
+            self._acc = torch.zeros(len(self.names) + 1 + int(self.from_frames), dtype=torch.float64, device=dev)
+            if self.from_frames:
+                self._frame_buffers(batch, capacity, max_taps, letterbox_image, dev)
         self._vals = None
         super().__init__(net, self._loss, batch, size, dev, warmup=warmup, segments=segments)
         self._capture_update()
-        self._acc.zero_()                                # the warm-up passes on zero inputs counted themselves
+        self.reset_stats()                               # the warm-up passes on zero inputs counted themselves
         torch.cuda.synchronize(dev)
+
+    def _frame_buffers(self, batch, capacity, max_taps, letterbox_image, dev):
+        """The static inputs of from_frames=True.  The warm-up and the capture run on a table of frames that fill their
+        slots (as FramePipeline's do) and on no boxes."""
+        (h, w), B = self.hw, batch
+        self.capacity = ihm, iwm = tuple(int(v) for v in capacity)
+        self.letterbox_image = bool(letterbox_image)
+        self.max_taps = data.default_max_taps(self.capacity, self.hw) if max_taps is None else int(max_taps)
+        table = data.frame_geometry([self.capacity] * B, self.hw, self.letterbox_image, self.capacity, self.max_taps, "TrainStep")
+        self.geom = torch.from_numpy(table.view(np.uint8).reshape(B, -1).copy()).to(dev)
+        self.frames_u8 = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
+        self.frame_labels_u8 = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
+        self.boxes = torch.zeros((B, max(self.max_gt, 1), 5), dtype=torch.int32, device=dev)
+        self.box_counts = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._lb_ws = torch.empty(hip.letterbox_ragged_workspace_bytes(B, ihm, iwm, h, w, self.max_taps), dtype=torch.uint8,
+                                  device=dev)
 
     def _prologue(self):
         if self.from_bytes:
             hip.batch_formats(self.images_u8, self.labels_u8, self.ns, images=self.x, png_out=self.png, onehot=self.onehot)
+        elif self.from_frames:
+            h, w = self.hw
+            hip.letterbox_ragged(self.frames_u8, None, self.geom, h, w, self.max_taps, images=self.x, flag=self.flag,
+                                 ws=self._lb_ws)
+            hip.seg_targets_ragged(self.frame_labels_u8, self.geom, h, w, self.ns, png_out=self.png, onehot=self.onehot,
+                                   flag=self.flag)
+            hip.box_targets_ragged(self.boxes, self.box_counts, self.geom, self.capacity, h, w, targets=self.labels,
+                                   counts_out=self.counts, flag=self.flag)
 
     def _loss(self, det, seg):
         total, ldet, lseg = losses.training_loss_packed(self.yolo_loss, det, seg, self.labels, self.counts, self.max_gt, self.png,
@@ -226,7 +277,9 @@ class TrainStep(GraphedStep):
         self._vals = torch.stack(vals)
         n = len(vals)
         self._acc[:n].add_(self._vals)
-        self._acc[n:].add_(1.0)
+        self._acc[n:n + 1].add_(1.0)
+        if self.from_frames:
+            self._acc[n + 1:].copy_(self.flag)
         return total
 
     def _capture_update(self):
@@ -285,8 +338,34 @@ class TrainStep(GraphedStep):
         packed, counts = losses.pack_targets(targets, self.max_gt)        # raises, naming the image, above max_gt
         return images, radar, pngs, seg_labels, packed, counts
 
-    def __call__(self, images, radar, targets, pngs, seg_labels=None):
-        images, radar, pngs, seg_labels, packed, counts = self._validate(images, radar, targets, pngs, seg_labels)
+    def _validate_frames(self, frames, radar, boxes, labels, sizes):
+        """The host checks of a from_frames call, which need no device; returns what the copies take, the geometry table
+        among it."""
+        B, (h, w), fn = self.batch, self.hw, "TrainStep"
+        items, own = data.ragged_items(frames, sizes, B, (3,), "frames", fn)
+        labs = data.ragged_items(labels, own, B, (), "label maps", fn)[0]
+        for t in (items, labs):
+            if torch.is_tensor(t) and (t.shape[1] > self.capacity[0] or t.shape[2] > self.capacity[1]):
+                raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {self.capacity}")
+        table = data.frame_geometry(own, self.hw, self.letterbox_image, self.capacity, self.max_taps, fn)
+        radar = self._tensor(radar)
+        if tuple(radar.shape) != (B, 4, h, w) or radar.dtype != torch.float32:
+            raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(B, 4, h, w)}, got {radar.dtype} {tuple(radar.shape)}")
+        if len(boxes) != B:
+            raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
+        packed, counts = data.pack_boxes(boxes, self.max_gt)              # raises, naming the image
+        return items, labs, own, table, radar, packed, counts
+
+    def __call__(self, images, radar, targets, pngs, seg_labels=None, sizes=None):
+        if self.from_frames:                 # step(frames, radar, boxes, labels, sizes=None)
+            if seg_labels is not None and sizes is not None:
+                raise RuntimeError("TrainStep: from_frames=True takes (frames, radar, boxes, labels, sizes)")
+            items, labs, own, table, radar, packed, counts = self._validate_frames(
+                images, radar, targets, pngs, seg_labels if sizes is None else sizes)
+        else:
+            if sizes is not None:
+                raise RuntimeError("TrainStep: sizes belong to from_frames=True")
+            images, radar, pngs, seg_labels, packed, counts = self._validate(images, radar, targets, pngs, seg_labels)
         opt, ema = self.optimizer, self.ema
         lr = float(opt._uniform("lr"))
         with torch.cuda.device(self.device):
@@ -297,7 +376,16 @@ class TrainStep(GraphedStep):
             if opt._table.addrs is not self._opt_addrs:
                 raise RuntimeError("TrainStep: the optimizer's tensor table was laid out anew (parameters un-frozen or groups "
                                    "changed): build a new TrainStep")
-            if self.from_bytes:
+            if self.from_frames:
+                # the kernels read no input padding into a result: what an earlier call left in a slot is harmless
+                data.fill_slots(self.frames_u8, items, own)
+                data.fill_slots(self.frame_labels_u8, labs, own)
+                # fresh pinned staging tensors (`pack_boxes` makes its own), as for the step record below
+                self.geom.copy_(torch.from_numpy(table.view(np.uint8).reshape(self.batch, -1).copy()).pin_memory(),
+                                non_blocking=True)
+                self.boxes.copy_(packed, non_blocking=True)
+                self.box_counts.copy_(counts, non_blocking=True)
+            elif self.from_bytes:
                 self.images_u8.copy_(images, non_blocking=True)
                 self.labels_u8.copy_(pngs, non_blocking=True)
             else:
@@ -306,8 +394,9 @@ class TrainStep(GraphedStep):
                 if seg_labels is not None:
                     self.onehot.copy_(seg_labels, non_blocking=True)
             self.r.copy_(radar, non_blocking=True)
-            self.labels.copy_(packed, non_blocking=True)
-            self.counts.copy_(counts, non_blocking=True)
+            if not self.from_frames:
+                self.labels.copy_(packed, non_blocking=True)
+                self.counts.copy_(counts, non_blocking=True)
             bc = opt.advance() if hasattr(opt, "advance") else None
             decay = ema.advance() if ema is not None else 0.0
             # a FRESH pinned staging tensor per step (as optim._Table.set_row): a host that runs ahead never overwrites a
@@ -324,11 +413,15 @@ class TrainStep(GraphedStep):
         """{"steps": n, "total": mean, "loss_det": mean, "loss_seg": mean[, "f_score": mean]} over the calls since the last
         `reset_stats()`, accumulated in fp64 on the device: one read-back (and the only synchronisation of an epoch)."""
         a = self._acc.cpu()
-        n = int(a[-1])
+        n = int(a[len(self.names)])
         out = {"steps": n}
         for i, k in enumerate(self.names):
             out[k] = float(a[i]) / n if n else float("nan")
+        if self.from_frames:
+            out["flag"] = int(a[-1])
         return out
 
     def reset_stats(self):
         self._acc.zero_()
+        if self.from_frames:
+            self.flag.zero_()

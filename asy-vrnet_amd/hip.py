@@ -145,6 +145,8 @@ _SIGS = {
     "vrnet_seg_predict_ragged_workspace": ([I, I, I, I], L),
     "vrnet_seg_predict_ragged_f32": ([P, P, I, I, I, I, I, I, P, P, P, L, P], I),
     "vrnet_render_ragged_u8": ([P, P, P, I, I, I, P, I, I, F, P, P, I, P, I, P, P, P, P], I),
+    "vrnet_seg_targets_ragged_u8": ([P, P, I, I, I, I, I, I, P, P, P, P], I),
+    "vrnet_box_targets_ragged_f32": ([P, P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_yolo_loss_workspace": ([I, L, I, I], L),
     "vrnet_yolo_loss_f32": ([P, P, P, P, P, I, I, I, P, P, I, F, P, P, P, P, P, L, P], I),
     "vrnet_seg_loss_workspace": ([I, I, L], L),
@@ -1190,6 +1192,7 @@ def bn_coef_bwd_from_chunks(partial, nchunks, count, mean_rstd, gamma, training,
 # ---- ragged batches (include/vrnet_hip.h "ragged batches"): per-image geometry from a device table -------------------
 GEOM_BYTES = 80          # sizeof(vrnet_frame_geom)
 FLAG_GEOMETRY = 256      # VR_FLAG_GEOMETRY of csrc/common.h
+FLAG_BOX_COUNT = 512     # VR_FLAG_BOX_COUNT of csrc/common.h: box_targets_ragged clamped a count outside [0, max_gt]
 
 
 def _geom(geom, B, fn):
@@ -1278,3 +1281,45 @@ def render_ragged(frames, class_map, geom, out, palette=None, mix_type=0, alpha=
                                        n_colors, int(mix_type), float(alpha), ptr(boxes) if n_rows else None, ptr(box_offsets),
                                        n_rows, ptr(box_palette), 0 if box_palette is None else box_palette.shape[0], ptr(out),
                                        ptr(counts), ptr(flag), stream()), "render_ragged")
+
+
+def seg_targets_ragged(label_u8, geom, H, W, num_classes_seg, png_out=None, onehot=None, flag=None):
+    """Raw label maps of their own sizes -> the segmentation targets of the letterboxed batch (vrnet_seg_targets_ragged_u8):
+    label_u8 (B,ihm,iwm) padded slots, geom the (B, GEOM_BYTES) table -> png_out (B,H,W) int64 (Pillow's NEAREST pick in the
+    window, 0 outside, labels >= ns clamped to ns) and onehot (B,H,W,ns+1) f32, as `batch_formats` writes them; flag (1)
+    int32 or None.  Returns (png_out, onehot)."""
+    if label_u8 is None or label_u8.dim() != 3:
+        raise RuntimeError("seg_targets_ragged: expected label maps (B, ihm, iwm)")
+    B, ihm, iwm = label_u8.shape
+    H, W, ns = int(H), int(W), int(num_classes_seg)
+    if png_out is None:
+        png_out = torch.empty((B, H, W), dtype=torch.int64, device=label_u8.device)
+    if onehot is None:
+        onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=label_u8.device)
+    _ragged_check("seg_targets_ragged", ((label_u8, (B, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
+                                         (onehot, (B, H, W, ns + 1), torch.float32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_seg_targets_ragged_u8(ptr(label_u8), _geom(geom, B, "seg_targets_ragged"), B, ihm, iwm, H, W, ns,
+                                            ptr(png_out), ptr(onehot), ptr(flag), stream()), "seg_targets_ragged")
+    return png_out, onehot
+
+
+def box_targets_ragged(boxes, counts, geom, capacity, H, W, targets=None, counts_out=None, flag=None):
+    """Boxes in pixels of the original images -> the packed targets of the letterboxed batch (vrnet_box_targets_ragged_f32):
+    boxes (B,max_gt,5) int32 rows x1, y1, x2, y2, cls with counts (B) int32, geom the (B, GEOM_BYTES) table, capacity =
+    (ihm, iwm) -> targets (B,max_gt,5) f32 rows [cx, cy, w, h, cls] and counts_out (B) int32, what `data.adjust_boxes` and
+    `data.boxes_xyxy_to_cxcywh` give per image, kept rows in input order, the rows behind them 0.  flag (1) int32 or None:
+    receives FLAG_BOX_COUNT for a count outside [0, max_gt] (clamped).  Returns (targets, counts_out)."""
+    if boxes is None or boxes.dim() != 3:
+        raise RuntimeError("box_targets_ragged: expected boxes (B, max_gt, 5)")
+    B, max_gt = boxes.shape[:2]
+    if targets is None:
+        targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
+    if counts_out is None:
+        counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
+    _ragged_check("box_targets_ragged", ((boxes, (B, max_gt, 5), torch.int32), (counts, (B,), torch.int32),
+                                         (targets, (B, max_gt, 5), torch.float32), (counts_out, (B,), torch.int32),
+                                         (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_box_targets_ragged_f32(ptr(boxes), ptr(counts), _geom(geom, B, "box_targets_ragged"), B, max_gt,
+                                             int(capacity[0]), int(capacity[1]), int(H), int(W), ptr(targets), ptr(counts_out),
+                                             ptr(flag), stream()), "box_targets_ragged")
+    return targets, counts_out

@@ -862,6 +862,28 @@ int vrnet_render_ragged_u8(const unsigned char* frames, const unsigned char* cla
                            const int* boxes, const int* box_offsets, int n_rows, const unsigned char* box_palette,
                            int n_box_colors, unsigned char* out, long long* counts, int* flag, void* stream);
 
+/* ---- the targets of a training batch from raw label maps and boxes (csrc/traintargets.hip) ---------------------------
+ * Added within ABI 11: new symbols only.  Both follow the ragged rules above: padded (B, ihm, iwm) slots, the geometry of
+ * image b from geom[b], clamped on the device (bit 256 of *flag for a clamped record; flag may be NULL), grid y the image,
+ * no workspace, no allocation, no host synchronisation, capturable in a graph.  Every output element is written on every
+ * call.  With vrnet_letterbox_ragged_u8 (images only) they are the `random=False` dataset item of utils/dataloader.py
+ * (:88-105, :129-183) for a batch of frames of mixed sizes, bit for bit.
+ * vrnet_seg_targets_ragged_u8: label (B, ihm, iwm) -> png_out (B, H, W) int64 and onehot (B, H, W, ns + 1) fp32.  Inside the
+ *   window (dx, dy, nw, nh) the source pixel is Pillow's Image.NEAREST pick (the index recurrence of the letterbox's
+ *   label_out), outside it the label is 0; labels >= num_classes_seg become num_classes_seg, and the one-hot row is that of
+ *   vrnet_batch_formats_u8.  0 < num_classes_seg < 255; (W + H) * 4 + 16 * W bytes of LDS must fit 64 KiB.
+ * vrnet_box_targets_ragged_f32: boxes (B, max_gt, 5) int32 rows x1, y1, x2, y2, cls in pixels of the original image, counts
+ *   (B) -> targets (B, max_gt, 5) fp32 rows cx, cy, w, h, cls on the canvas and counts_out (B): the buffers
+ *   vrnet_yolo_loss_f32 reads.  Per coordinate, in fp64 as numpy evaluates dataloader.py:170-171: the 64-bit integer product
+ *   x * nw, converted to double, / iw (IEEE division), + dx, truncated toward zero (y: nh, ih, dy); then x1, y1 < 0 -> 0,
+ *   x2 > W -> W, y2 > H -> H; rows with x2 - x1 > 1 and y2 - y1 > 1 are kept and compacted IN INPUT ORDER (the reference's
+ *   shuffle is omitted); w = x2 - x1, h = y2 - y1, cx = x1 + w / 2, cy = y1 + h / 2.  Rows at and beyond counts_out[b] are
+ *   written 0.  A counts[b] outside [0, max_gt] is clamped and sets bit 512 of *flag.  One workgroup per image. */
+int vrnet_seg_targets_ragged_u8(const unsigned char* label, const vrnet_frame_geom* geom, int B, int ihm, int iwm, int H,
+                                int W, int num_classes_seg, long long* png_out, float* onehot, int* flag, void* stream);
+int vrnet_box_targets_ragged_f32(const int* boxes, const int* counts, const vrnet_frame_geom* geom, int B, int max_gt,
+                                 int ihm, int iwm, int H, int W, float* targets, int* counts_out, int* flag, void* stream);
+
 /* ---- the record arena of a validation pass (csrc/evalacc.hip) --------------------------------------------------------
  * Added within ABI 11: a new symbol only.
  * vrnet_eval_append_f32, utils/callbacks.py:151-170 (get_map_txt: the rows, scores and coordinates it writes per image)

@@ -13,6 +13,15 @@ tensors, non-blocking copies).  A round is `--steps` steps (more when a step is 
 inside a host clock that ends in a device synchronise; the line gives the median round and the spread between rounds.
 
     python tools/bench_train_step.py --captured [--phi nano] [--rounds 5]
+
+--frames IHxIW (with --captured) starts from RAW frames of that size instead: the batch of every contender is the host
+letterbox (data.letterbox_sample) of one seeded set of frames, label maps and pixel boxes, and two contenders join
+  host letterbox   data.letterbox_sample + boxes_xyxy_to_cxcywh per image on the host INSIDE the timed loop, then the
+                   from_bytes step: what a single-process loop pays without the device path (decoding is in no mode)
+  from_frames      graph.TrainStep(from_frames=True): the raw bytes over PCIe, letterbox and targets inside graph 0
+so that from_bytes, fed pre-letterboxed bytes, is the device-only floor of the three.
+
+    python tools/bench_train_step.py --captured --frames 1080x1920 [--phi nano]
 """
 import argparse
 import math
@@ -39,12 +48,44 @@ def synthetic_batch(B, S, NC, NS, seed=0):
     return labels, torch.from_numpy(png), torch.from_numpy(img_u8)
 
 
+def synthetic_frames(B, ih, iw, S, NC, NS, seed=0):
+    """The seeded RAW batch of --frames: frames, label maps and integer pixel boxes of one size, and their host letterbox
+    in the form `synthetic_batch` returns."""
+    from PIL import Image
+    from asy_vrnet_amd import data
+    rng = np.random.default_rng(seed)
+    frames = rng.integers(0, 256, (B, ih, iw, 3), dtype=np.uint8)
+    maps = np.kron(rng.integers(0, NS + 1, (B, -(-ih // 16), -(-iw // 16))), np.ones((16, 16), dtype=np.int64))[:, :ih, :iw]
+    maps = np.ascontiguousarray(maps).astype(np.uint8)
+    boxes = []
+    for n in rng.integers(3, 25, B):
+        c = np.stack([rng.integers(iw // 8, iw - iw // 8, n), rng.integers(ih // 8, ih - ih // 8, n)], 1)
+        half = np.stack([rng.integers(iw // 64 + 2, iw // 5, n), rng.integers(ih // 64 + 2, ih // 5, n)], 1)
+        boxes.append(np.concatenate([c - half, c + half, rng.integers(0, NC, (n, 1))], 1).astype(np.int64))
+    pil = [(Image.fromarray(f), Image.fromarray(m)) for f, m in zip(frames, maps)]
+
+    def host_letterbox():
+        imgs, labs, targets = [], [], []
+        for (f, m), bx in zip(pil, boxes):
+            image, box, label = data.letterbox_sample(f, m, bx, (S, S))
+            imgs.append(np.array(image))
+            labs.append(np.array(label))
+            targets.append(torch.from_numpy(data.boxes_xyxy_to_cxcywh(box).astype(np.float32)))
+        return torch.from_numpy(np.stack(imgs)), torch.from_numpy(np.stack(labs)), targets
+    return torch.from_numpy(frames), torch.from_numpy(maps), boxes, host_letterbox
+
+
 def captured(a):
     from asy_vrnet_amd import data
     from asy_vrnet_amd.graph import TrainStep
     dev = torch.device("cuda:0")
     B, S, NC, NS = a.batch, a.size, 4, 9
-    labels, png, img_u8 = synthetic_batch(B, S, NC, NS)
+    if a.frames:
+        ih, iw = (int(v) for v in a.frames.lower().split("x"))
+        raw_frames, raw_maps, boxes, host_letterbox = synthetic_frames(B, ih, iw, S, NC, NS)
+        img_u8, png, labels = host_letterbox()
+    else:
+        labels, png, img_u8 = synthetic_batch(B, S, NC, NS)
     # every contender sees the same numbers: the float forms are the device's own conversion of the bytes
     x, png_d, onehot = data.device_batch(img_u8, png.to(torch.uint8), NS, device=dev)
     _, r = A.synthetic_inputs(B, S, 1, dev)
@@ -77,6 +118,16 @@ def captured(a):
     runs = [("eager", eager_step),
             ("TrainStep", lambda: step_f(hx, hr, labels, hpng, honehot)["total"]),
             ("TrainStep(from_bytes)", lambda: step_b(hu8, hr, labels, hlab8)["total"])]
+    if a.frames:
+        t3 = trainer()
+        step_r = TrainStep(t3[0], t3[1], t3[2], t3[3], B, S, NS, max_gt=32, from_frames=True, capacity=(ih, iw), device=dev)
+        hraw, hmaps, sizes = pin(raw_frames), pin(raw_maps), [(ih, iw)] * B
+
+        def host_letterbox_step():
+            u8, lab8, targets = host_letterbox()
+            return step_b(u8, hr, targets, lab8)["total"]
+        runs += [("host letterbox + from_bytes", host_letterbox_step),
+                 ("TrainStep(from_frames)", lambda: step_r(hraw, hr, boxes, hmaps, sizes)["total"])]
 
     def window(fn, n):
         torch.cuda.synchronize()
@@ -105,6 +156,13 @@ def captured(a):
               f"{last[name]:.4f}")
     for name in ("TrainStep", "TrainStep(from_bytes)"):
         print(f"  eager / {name:22s} {med['eager'] / med[name]:6.2f} x")
+    if a.frames:
+        fb, hl, fr = med["TrainStep(from_bytes)"], med["host letterbox + from_bytes"], med["TrainStep(from_frames)"]
+        px = B * S * S
+        print(f"  frames {ih} x {iw}: from_frames - from_bytes = {fr - fb:.3f} ms (the prologue and its copies: "
+              f"{B * ih * iw * 4 / 1e6:.1f} MB of frames and label maps in instead of {px * 4 / 1e6:.1f} MB of letterboxed bytes, "
+              f"{px * 12 / 1e6:.1f} MB of float images and {px * (8 + 4 * (NS + 1)) / 1e6:.1f} MB of targets out); "
+              f"host letterbox / from_frames = {hl / fr:.2f} x; flag {step_r.stats()['flag']}")
 
 
 def main():
@@ -115,6 +173,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--captured", action="store_true", help="eager loop against graph.TrainStep, alternating rounds")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--frames", default=None, metavar="IHxIW",
+                    help="with --captured: raw frames of this size; adds the host-letterbox and the from_frames contenders")
     a = ap.parse_args()
     if a.captured:
         return captured(a)
