@@ -429,48 +429,43 @@ extern "C" int vrnet_nms_capped_f32(const float* rows, int ld, const float* scor
                  workspace_bytes, keep, kept, rows_out, flag, stream);
 }
 
+// the checks, the clears and the launch of both detect_finish entry points, on `p` as the entry point filled it; `what`
+// names the size h x w in the message
+static int finish_run(const char* fn, bool ragged, const char* what, int h, int w, const FinishArgs& p, void* stream) {
+  VR_CHECK_ARG(p.rows && p.kept && (p.tab || !ragged) && p.out && p.draw && p.offsets && p.counts && p.flag && p.rows != p.out,
+               "%s: every array is required, rows_out apart from rows", fn);
+  VR_CHECK_ARG(p.B > 0 && p.B < 65536 && p.cap > 0 && (long)p.B * p.cap < (1L << 27) && p.nc >= 1 && h > 0 && w > 0,
+               "%s: bad shape (B %d, cap %d, %d classes, %s %d x %d)", fn, p.B, p.cap, p.nc, what, h, w);
+  const hipStream_t st = vr_stream(stream);
+  if (hipMemsetAsync(p.draw, 0, sizeof(int) * 5 * (size_t)p.B * p.cap, st) != hipSuccess ||
+      hipMemsetAsync(p.counts, 0, sizeof(long long) * (size_t)p.B * p.nc, st) != hipSuccess) {
+    vr_set_error("%s: memset failed", fn);
+    return VR_ERR_LAUNCH;
+  }
+  if (ragged) hipLaunchKernelGGL(detect_finish_kernel<true>, dim3(vr_cdiv(p.cap, 256), p.B), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL(detect_finish_kernel<false>, dim3(vr_cdiv(p.cap, 256), p.B), dim3(256), 0, st, p);
+  VR_LAUNCH_CHECK(fn);
+  return VR_OK;
+}
+
 extern "C" int vrnet_detect_finish_f32(const float* rows, const int* kept, int B, int cap, int num_classes, int image_h,
                                        int image_w, double offset_y, double offset_x, double scale_y, double scale_x,
                                        float* rows_out, int* draw_rows, int* offsets, long long* det_counts, int* flag,
                                        void* stream) {
-  VR_CHECK_ARG(rows && kept && rows_out && draw_rows && offsets && det_counts && flag && rows != rows_out,
-               "detect_finish: every array is required, rows_out apart from rows");
-  VR_CHECK_ARG(B > 0 && B < 65536 && cap > 0 && (long)B * cap < (1L << 27) && num_classes >= 1 && image_h > 0 && image_w > 0,
-               "detect_finish: bad shape (B %d, cap %d, %d classes, image %d x %d)", B, cap, num_classes, image_h, image_w);
-  const hipStream_t st = vr_stream(stream);
-  if (hipMemsetAsync(draw_rows, 0, sizeof(int) * 5 * (size_t)B * cap, st) != hipSuccess ||
-      hipMemsetAsync(det_counts, 0, sizeof(long long) * (size_t)B * num_classes, st) != hipSuccess) {
-    vr_set_error("detect_finish: memset failed");
-    return VR_ERR_LAUNCH;
-  }
   FinishArgs p{};
   p.rows = rows; p.kept = kept; p.B = B; p.cap = cap; p.nc = num_classes; p.ih = image_h; p.iw = image_w;
   p.off_y = offset_y; p.off_x = offset_x; p.sc_y = scale_y; p.sc_x = scale_x; p.img_h = (double)image_h; p.img_w = (double)image_w;
   p.out = rows_out; p.draw = draw_rows; p.offsets = offsets; p.counts = reinterpret_cast<unsigned long long*>(det_counts);
   p.flag = flag;
-  hipLaunchKernelGGL(detect_finish_kernel<false>, dim3(vr_cdiv(cap, 256), B), dim3(256), 0, st, p);
-  VR_LAUNCH_CHECK("detect_finish");
-  return VR_OK;
+  return finish_run("detect_finish", false, "image", image_h, image_w, p, stream);
 }
 
 extern "C" int vrnet_detect_finish_ragged_f32(const float* rows, const int* kept, const vrnet_frame_geom* geom, int B, int cap,
                                               int num_classes, int ihm, int iwm, float* rows_out, int* draw_rows, int* offsets,
                                               long long* det_counts, int* flag, void* stream) {
-  VR_CHECK_ARG(rows && kept && geom && rows_out && draw_rows && offsets && det_counts && flag && rows != rows_out,
-               "detect_finish_ragged: every array is required, rows_out apart from rows");
-  VR_CHECK_ARG(B > 0 && B < 65536 && cap > 0 && (long)B * cap < (1L << 27) && num_classes >= 1 && ihm > 0 && iwm > 0,
-               "detect_finish_ragged: bad shape (B %d, cap %d, %d classes, slots %d x %d)", B, cap, num_classes, ihm, iwm);
-  const hipStream_t st = vr_stream(stream);
-  if (hipMemsetAsync(draw_rows, 0, sizeof(int) * 5 * (size_t)B * cap, st) != hipSuccess ||
-      hipMemsetAsync(det_counts, 0, sizeof(long long) * (size_t)B * num_classes, st) != hipSuccess) {
-    vr_set_error("detect_finish_ragged: memset failed");
-    return VR_ERR_LAUNCH;
-  }
   FinishArgs p{};
   p.rows = rows; p.kept = kept; p.B = B; p.cap = cap; p.nc = num_classes; p.tab = geom; p.ihm = ihm; p.iwm = iwm;
   p.out = rows_out; p.draw = draw_rows; p.offsets = offsets; p.counts = reinterpret_cast<unsigned long long*>(det_counts);
   p.flag = flag;
-  hipLaunchKernelGGL(detect_finish_kernel<true>, dim3(vr_cdiv(cap, 256), B), dim3(256), 0, st, p);
-  VR_LAUNCH_CHECK("detect_finish_ragged");
-  return VR_OK;
+  return finish_run("detect_finish_ragged", true, "slots", ihm, iwm, p, stream);
 }

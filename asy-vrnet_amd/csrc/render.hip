@@ -297,6 +297,9 @@ __global__ __launch_bounds__(256) void render_kernel(const RenderArgs p) {
 // image's box rows and one histogram in LDS for its whole life.  Four consecutive pixels of the slot per thread (dword
 // accesses when the slots allow it), each with its own (x, y): a group may wrap a row.  Every pixel of the slot outside
 // the image is written 0 and counts nowhere.
+// A kernel of its own, unlike the letterbox and seg_predict: render_kernel draws in place, keeps dword accesses for any
+// base alignment through a head of 0-3 pixels and has a one-row shortcut in the ring scan; this one falls back to byte
+// accesses when ihm * iwm % 4 != 0 and B > 1.  Each is better on some input.
 struct RaggedRenderArgs {
   RenderArgs r;                      // ih, iw = the slot ihm, iwm; thickness, head, ngroups, total, inplace unused
   const vrnet_frame_geom* tab;       // (B)
@@ -436,22 +439,31 @@ bool overlap(const void* a, long a_bytes, const void* b, long b_bytes) {
   return x < y + (uintptr_t)b_bytes && y < x + (uintptr_t)a_bytes;
 }
 
+// the argument checks that both entry points share; `ok`: the entry point's own pointer and batch conditions, `what`
+// names the size h x w in the message
+int render_check(const char* fn, bool ok, const char* what, int B, int h, int w, const unsigned char* class_map,
+                 const unsigned char* palette, int n_colors, int mix_type, float alpha, const long long* counts) {
+  VR_CHECK_ARG(ok && B > 0 && h > 0 && w > 0 && h <= (1 << 24) && w <= (1 << 24) && (long)B * h * w < (1L << 31),
+               "%s: bad shape (B %d, %s %d x %d; at most 2^31 - 1 pixels in all)", fn, B, what, h, w);
+  VR_CHECK_ARG(mix_type >= 0 && mix_type <= 2, "%s: mix_type %d is not 0, 1 or 2", fn, mix_type);
+  VR_CHECK_ARG(alpha >= 0.f && alpha <= 1.f, "%s: alpha %g outside [0, 1]", fn, (double)alpha);
+  VR_CHECK_ARG(n_colors >= 0 && n_colors <= RN_MAXCOL && (n_colors > 0) == (palette != nullptr || counts != nullptr) &&
+                   (!palette || n_colors > 0),
+               "%s: a palette or counts need 1..%d colours, got %d", fn, RN_MAXCOL, n_colors);
+  VR_CHECK_ARG(!class_map || mix_type == 2 || palette, "%s: mix_type %d of a class map needs a palette", fn, mix_type);
+  VR_CHECK_ARG(class_map || !counts, "%s: counts need a class map", fn);
+  return VR_OK;
+}
+
 }  // namespace
 
 extern "C" int vrnet_render_u8(const unsigned char* frames, const unsigned char* class_map, int B, int ih, int iw,
                                const unsigned char* palette, int n_colors, int mix_type, float alpha, const int* boxes,
                                const int* box_offsets, int n_rows, const unsigned char* box_palette, int n_box_colors,
                                int thickness, unsigned char* out, long long* counts, int* flag, void* stream) {
-  VR_CHECK_ARG(frames && out && B > 0 && ih > 0 && iw > 0 && ih <= (1 << 24) && iw <= (1 << 24) &&
-                   (long)B * ih * iw < (1L << 31),
-               "render: bad shape (B %d, frames %d x %d; at most 2^31 - 1 pixels in all)", B, ih, iw);
-  VR_CHECK_ARG(mix_type >= 0 && mix_type <= 2, "render: mix_type %d is not 0, 1 or 2", mix_type);
-  VR_CHECK_ARG(alpha >= 0.f && alpha <= 1.f, "render: alpha %g outside [0, 1]", (double)alpha);
-  VR_CHECK_ARG(n_colors >= 0 && n_colors <= RN_MAXCOL && (n_colors > 0) == (palette != nullptr || counts != nullptr) &&
-                   (!palette || n_colors > 0),
-               "render: a palette or counts need 1..%d colours, got %d", RN_MAXCOL, n_colors);
-  VR_CHECK_ARG(!class_map || mix_type == 2 || palette, "render: mix_type %d of a class map needs a palette", mix_type);
-  VR_CHECK_ARG(class_map || !counts, "render: counts need a class map");
+  if (const int rc = render_check("render", frames && out, "frames", B, ih, iw, class_map, palette, n_colors, mix_type, alpha,
+                                  counts))
+    return rc;
   VR_CHECK_ARG(n_rows >= 0 && (n_rows == 0 || (boxes && box_offsets && box_palette && n_box_colors > 0 &&
                                                 n_box_colors <= RN_MAXCOL && thickness > 0 && thickness <= (1 << 24))),
                "render: %d box rows need offsets, a box palette of 1..%d colours and 0 < thickness <= 2^24", n_rows, RN_MAXCOL);
@@ -492,16 +504,9 @@ extern "C" int vrnet_render_ragged_u8(const unsigned char* frames, const unsigne
                                       int n_colors, int mix_type, float alpha, const int* boxes, const int* box_offsets,
                                       int n_rows, const unsigned char* box_palette, int n_box_colors, unsigned char* out,
                                       long long* counts, int* flag, void* stream) {
-  VR_CHECK_ARG(frames && out && geom && B > 0 && B < 65536 && ihm > 0 && iwm > 0 && ihm <= (1 << 24) && iwm <= (1 << 24) &&
-                   (long)B * ihm * iwm < (1L << 31),
-               "render_ragged: bad shape (B %d, slots %d x %d; at most 2^31 - 1 pixels in all)", B, ihm, iwm);
-  VR_CHECK_ARG(mix_type >= 0 && mix_type <= 2, "render_ragged: mix_type %d is not 0, 1 or 2", mix_type);
-  VR_CHECK_ARG(alpha >= 0.f && alpha <= 1.f, "render_ragged: alpha %g outside [0, 1]", (double)alpha);
-  VR_CHECK_ARG(n_colors >= 0 && n_colors <= RN_MAXCOL && (n_colors > 0) == (palette != nullptr || counts != nullptr) &&
-                   (!palette || n_colors > 0),
-               "render_ragged: a palette or counts need 1..%d colours, got %d", RN_MAXCOL, n_colors);
-  VR_CHECK_ARG(!class_map || mix_type == 2 || palette, "render_ragged: mix_type %d of a class map needs a palette", mix_type);
-  VR_CHECK_ARG(class_map || !counts, "render_ragged: counts need a class map");
+  if (const int rc = render_check("render_ragged", frames && out && geom && B < 65536, "slots", B, ihm, iwm, class_map, palette,
+                                  n_colors, mix_type, alpha, counts))
+    return rc;
   VR_CHECK_ARG(n_rows >= 0 && (n_rows == 0 || (boxes && box_offsets && box_palette && n_box_colors > 0 &&
                                                 n_box_colors <= RN_MAXCOL)),
                "render_ragged: %d box rows need offsets and a box palette of 1..%d colours", n_rows, RN_MAXCOL);

@@ -20,13 +20,28 @@ namespace {
 constexpr int SEGP_MAXC = 32;        // the seg loss's class cap (SMAXC in loss.hip)
 constexpr int HIST_MAXN = 32;
 
+// One body for both entry points.  The window and the size of image b are `geom` (vrnet_seg_predict_f32: one record for
+// every image, ih, iw = ihm, iwm) or tab[b] clamped by vr_geom_load (vrnet_seg_predict_ragged_f32: RAGGED); the class map
+// is (B, ihm, iwm) with image b in the top-left corner of its slot and 0 outside it.  The image is blockIdx.x / bpi, so a
+// block reads one record and its loads are wave-uniform.
 struct SegPredArgs {
   const float* x;                    // (B, C, H, W)
-  int B, C, H, W, top, left, nh, nw, oh, ow;
-  float sy, sx;                      // nh / oh, nw / ow
-  float* prob;                       // (B, C, nh, nw)
-  unsigned char* out;                // (B, oh, ow)
+  const vrnet_frame_geom* tab;       // RAGGED: (B) records
+  vrnet_frame_geom geom;             // otherwise: the record of every image
+  int B, C, H, W, ihm, iwm;
+  long pslot;                        // floats from one image's planes to the next: C * nh * nw (tight), or C * H * W
+  int bpi;                           // blocks per image of this launch
+  float* prob;                       // image b: (C, seg_nh, seg_nw) at b * pslot
+  unsigned char* out;                // (B, ihm, iwm)
+  int* flag;                         // or null
 };
+
+template <bool RAGGED>
+__device__ __forceinline__ vrnet_frame_geom segp_geom(const SegPredArgs& p, int b, bool& bad) {
+  bad = false;
+  if constexpr (RAGGED) return vr_geom_load(p.tab, b, p.ihm, p.iwm, p.H, p.W, bad);
+  return p.geom;
+}
 
 // softmax over the C channels of one pixel: src / dst step by a plane per channel
 __device__ __forceinline__ void softmax_pixel(const float* src, long plane, int C, float* dst, long dplane) {
@@ -37,15 +52,18 @@ __device__ __forceinline__ void softmax_pixel(const float* src, long plane, int 
   for (int c = 0; c < C; ++c) dst[c * dplane] = expf(src[c * plane] - m) / s;
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void segp_softmax_kernel(const SegPredArgs p) {
-  const long total = (long)p.B * p.nh * p.nw;
+  const long b = blockIdx.x / p.bpi, r = (long)(blockIdx.x - b * p.bpi) * 256 + threadIdx.x;
+  bool bad;
+  const vrnet_frame_geom g = segp_geom<RAGGED>(p, (int)b, bad);
+  if (r == 0 && bad && p.flag) atomicOr(p.flag, VR_FLAG_GEOMETRY);
+  const long n = (long)g.seg_nh * g.seg_nw;
+  if (r >= n) return;
+  const int y = (int)(r / g.seg_nw), xx = (int)(r - (long)y * g.seg_nw);
   const long plane = (long)p.H * p.W;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    const long b = e / ((long)p.nh * p.nw);
-    const int r = (int)(e - b * p.nh * p.nw), y = r / p.nw, xx = r - y * p.nw;
-    softmax_pixel(p.x + b * p.C * plane + (long)(p.top + y) * p.W + (p.left + xx), plane, p.C,
-                  p.prob + b * p.C * p.nh * p.nw + r, (long)p.nh * p.nw);
-  }
+  softmax_pixel(p.x + b * p.C * plane + (long)(g.seg_top + y) * p.W + (g.seg_left + xx), plane, p.C,
+                p.prob + b * p.pslot + r, n);
 }
 
 // OpenCV resize INTER_LINEAR source coordinate along one axis: f = (d + 0.5) * scale - 0.5, s = floor(f), f -= s, clamped
@@ -83,52 +101,28 @@ __device__ __forceinline__ unsigned char resize_argmax_pixel(const float* prob, 
   return (unsigned char)arg;
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void segp_resize_argmax_kernel(const SegPredArgs p) {
-  const long total = (long)p.B * p.oh * p.ow;
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= total) return;
-  const long b = e / ((long)p.oh * p.ow);
-  const int r = (int)(e - b * p.oh * p.ow), oy = r / p.ow, ox = r - oy * p.ow;
-  p.out[e] = resize_argmax_pixel(p.prob + b * p.C * p.nh * p.nw, p.C, p.nh, p.nw, p.sy, p.sx, oy, ox);
-}
-
-// ---- the ragged form: the window and the output size of image b come from tab[b]; the class map is the padded
-// (B, ihm, iwm) buffer with image b in the top-left corner of its slot and 0 outside it.  blockIdx.y is the image.
-struct RaggedSegArgs {
-  const float* x;                    // (B, C, H, W)
-  const vrnet_frame_geom* tab;       // (B)
-  int B, C, H, W, ihm, iwm;
-  float* prob;                       // image b: (C, seg_nh, seg_nw) at b * C * H * W
-  unsigned char* out;                // (B, ihm, iwm)
-  int* flag;                         // or null
-};
-
-__global__ __launch_bounds__(256) void segp_ragged_softmax_kernel(const RaggedSegArgs p) {
-  const int b = blockIdx.y;
+  const long b = blockIdx.x / p.bpi, e = (long)(blockIdx.x - b * p.bpi) * 256 + threadIdx.x;
   bool bad;
-  const vrnet_frame_geom g = vr_geom_load(p.tab, b, p.ihm, p.iwm, p.H, p.W, bad);
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r == 0 && bad && p.flag) atomicOr(p.flag, VR_FLAG_GEOMETRY);
-  const int nh = g.seg_nh, nw = g.seg_nw;
-  if (r >= nh * nw) return;
-  const int y = r / nw, xx = r - y * nw;
-  const long plane = (long)p.H * p.W;
-  softmax_pixel(p.x + (long)b * p.C * plane + (long)(g.seg_top + y) * p.W + (g.seg_left + xx), plane, p.C,
-                p.prob + (long)b * p.C * plane + r, (long)nh * nw);
-}
-
-__global__ __launch_bounds__(256) void segp_ragged_resize_argmax_kernel(const RaggedSegArgs p) {
-  const int b = blockIdx.y;
-  bool bad;
-  const vrnet_frame_geom g = vr_geom_load(p.tab, b, p.ihm, p.iwm, p.H, p.W, bad);
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= p.ihm * p.iwm) return;
-  const int oy = e / p.iwm, ox = e - oy * p.iwm;
+  const vrnet_frame_geom g = segp_geom<RAGGED>(p, (int)b, bad);
+  const long slot = (long)p.ihm * p.iwm;
+  if (e >= slot) return;
+  const int oy = (int)(e / p.iwm), ox = (int)(e - (long)oy * p.iwm);
   unsigned char cls = 0;                           // the padding of the slot, and an image without a window
   if (oy < g.ih && ox < g.iw && g.seg_nh > 0 && g.seg_nw > 0)
-    cls = resize_argmax_pixel(p.prob + (long)b * p.C * p.H * p.W, p.C, g.seg_nh, g.seg_nw, (float)g.seg_nh / (float)g.ih,
+    cls = resize_argmax_pixel(p.prob + b * p.pslot, p.C, g.seg_nh, g.seg_nw, (float)g.seg_nh / (float)g.ih,
                               (float)g.seg_nw / (float)g.iw, oy, ox);
-  p.out[(long)b * p.ihm * p.iwm + e] = cls;
+  p.out[b * slot + e] = cls;
+}
+
+// the two launches of both entry points; `win`: the largest window of an image, in pixels
+template <bool RAGGED>
+void segp_launch(SegPredArgs p, long win, hipStream_t st) {
+  p.bpi = (int)vr_cdiv(win, 256);
+  hipLaunchKernelGGL(segp_softmax_kernel<RAGGED>, dim3((unsigned)((long)p.B * p.bpi)), dim3(256), 0, st, p);
+  p.bpi = (int)vr_cdiv((long)p.ihm * p.iwm, 256);
+  hipLaunchKernelGGL(segp_resize_argmax_kernel<RAGGED>, dim3((unsigned)((long)p.B * p.bpi)), dim3(256), 0, st, p);
 }
 
 template <typename TL, typename TP>
@@ -175,17 +169,12 @@ extern "C" int vrnet_seg_predict_f32(const float* x, int B, int C, int H, int W,
     return VR_ERR_WORKSPACE;
   }
   SegPredArgs p{};
-  p.x = x; p.B = B; p.C = C; p.H = H; p.W = W; p.top = top; p.left = left; p.nh = nh; p.nw = nw; p.oh = oh; p.ow = ow;
-  p.sy = (float)nh / (float)oh;
-  p.sx = (float)nw / (float)ow;
+  p.x = x; p.B = B; p.C = C; p.H = H; p.W = W; p.ihm = oh; p.iwm = ow;
+  p.geom.ih = oh; p.geom.iw = ow; p.geom.seg_top = top; p.geom.seg_left = left; p.geom.seg_nh = nh; p.geom.seg_nw = nw;
+  p.pslot = (long)C * nh * nw;
   p.prob = reinterpret_cast<float*>(workspace);
   p.out = out;
-  hipStream_t st = vr_stream(stream);
-  const long nwin = (long)B * nh * nw, nout = (long)B * oh * ow;
-  long g1 = vr_cdiv(nwin, 256);
-  if (g1 > 4096) g1 = 4096;
-  hipLaunchKernelGGL(segp_softmax_kernel, dim3((unsigned)g1), dim3(256), 0, st, p);
-  hipLaunchKernelGGL(segp_resize_argmax_kernel, dim3((unsigned)vr_cdiv(nout, 256)), dim3(256), 0, st, p);
+  segp_launch<false>(p, (long)nh * nw, vr_stream(stream));
   VR_LAUNCH_CHECK("seg_predict");
   return VR_OK;
 }
@@ -222,13 +211,12 @@ extern "C" int vrnet_seg_predict_ragged_f32(const float* x, const vrnet_frame_ge
     vr_set_error("seg_predict_ragged: workspace %ld < %ld bytes", workspace_bytes, vrnet_seg_predict_ragged_workspace(B, C, H, W));
     return VR_ERR_WORKSPACE;
   }
-  RaggedSegArgs p{};
+  SegPredArgs p{};
   p.x = x; p.tab = geom; p.B = B; p.C = C; p.H = H; p.W = W; p.ihm = ihm; p.iwm = iwm;
+  p.pslot = (long)C * H * W;
   p.prob = reinterpret_cast<float*>(workspace);
   p.out = out; p.flag = flag;
-  hipStream_t st = vr_stream(stream);
-  hipLaunchKernelGGL(segp_ragged_softmax_kernel, dim3((unsigned)vr_cdiv((long)H * W, 256), B), dim3(256), 0, st, p);
-  hipLaunchKernelGGL(segp_ragged_resize_argmax_kernel, dim3((unsigned)vr_cdiv((long)ihm * iwm, 256), B), dim3(256), 0, st, p);
+  segp_launch<true>(p, (long)H * W, vr_stream(stream));
   VR_LAUNCH_CHECK("seg_predict_ragged");
   return VR_OK;
 }

@@ -225,7 +225,7 @@ def frame_sizes(sizes, batch=None, fn="frame_geometry"):
 
 def frame_geometry(sizes, input_shape, letterbox_image=True, capacity=None, max_taps=None, fn="frame_geometry"):
     """The packed per-image table of the ragged entry points: sizes (B, 2) = (ih, iw) per image -> a (B,) GEOM_DTYPE array
-    (`.view(np.uint8).reshape(B, -1)` is what the device takes).  Every value is what the fixed-size path computes for that
+    (`geometry_bytes` of it is what the device takes).  Every value is what the fixed-size path computes for that
     image alone: `letterbox_geometry`, `decode.seg_window`, `infer.unmap_scalars` and the thickness of yolo.py:164; with
     letterbox_image=False the window is the whole input.  Host only.  Raises RuntimeError naming the image index for a
     size that is not positive or above capacity = (ihm, iwm), for an empty window, and for a frame whose resize needs more
@@ -254,6 +254,11 @@ def frame_geometry(sizes, input_shape, letterbox_image=True, capacity=None, max_
         tab[b] = (ih, iw, nw, nh, dx, dy, top, left, snh, snw, int(max((iw + ih) // np.mean((H, W)), 1)), 0,
                   offset[0], offset[1], scale[0], scale[1])
     return tab
+
+
+def geometry_bytes(table):
+    """A `frame_geometry` table as the (B, hip.GEOM_BYTES) uint8 host tensor the device takes; it shares the table's memory."""
+    return torch.from_numpy(table.view(np.uint8).reshape(len(table), -1))
 
 
 def ragged_items(items, sizes, batch, trailing, what, fn):
@@ -333,7 +338,7 @@ def device_letterbox_ragged(frames, sizes, input_shape, labels=None, letterbox_i
     tab = frame_geometry(own, (H, W), letterbox_image, (ihm, iwm), max_taps, fn)
     dev = torch.device(device)
     with torch.cuda.device(dev):
-        geom = torch.from_numpy(tab.view(np.uint8).reshape(B, -1)).to(dev, non_blocking=True)
+        geom = geometry_bytes(tab).to(dev, non_blocking=True)
         img = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
         fill_slots(img, items, own)
         lab = None
@@ -414,7 +419,7 @@ def device_train_batch_ragged(frames, sizes, input_shape, labels, boxes, num_cla
     packed, counts = pack_boxes(boxes, max_gt)
     dev = torch.device(device)
     with torch.cuda.device(dev):
-        geom = torch.from_numpy(tab.view(np.uint8).reshape(B, -1)).to(dev, non_blocking=True)
+        geom = geometry_bytes(tab).to(dev, non_blocking=True)
         img = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
         fill_slots(img, items, own)
         lab = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)

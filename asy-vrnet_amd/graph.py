@@ -247,7 +247,7 @@ class TrainStep(GraphedStep):
         self.letterbox_image = bool(letterbox_image)
         self.max_taps = data.default_max_taps(self.capacity, self.hw) if max_taps is None else int(max_taps)
         table = data.frame_geometry([self.capacity] * B, self.hw, self.letterbox_image, self.capacity, self.max_taps, "TrainStep")
-        self.geom = torch.from_numpy(table.view(np.uint8).reshape(B, -1).copy()).to(dev)
+        self.geom = data.geometry_bytes(table).to(dev)
         self.frames_u8 = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
         self.frame_labels_u8 = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
         self.boxes = torch.zeros((B, max(self.max_gt, 1), 5), dtype=torch.int32, device=dev)
@@ -381,8 +381,7 @@ class TrainStep(GraphedStep):
                 data.fill_slots(self.frames_u8, items, own)
                 data.fill_slots(self.frame_labels_u8, labs, own)
                 # fresh pinned staging tensors (`pack_boxes` makes its own), as for the step record below
-                self.geom.copy_(torch.from_numpy(table.view(np.uint8).reshape(self.batch, -1).copy()).pin_memory(),
-                                non_blocking=True)
+                self.geom.copy_(data.geometry_bytes(table).pin_memory(), non_blocking=True)
                 self.boxes.copy_(packed, non_blocking=True)
                 self.box_counts.copy_(counts, non_blocking=True)
             elif self.from_bytes:

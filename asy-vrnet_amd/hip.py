@@ -235,6 +235,14 @@ def ptr(t):
     return t.data_ptr()
 
 
+def _tensors(fn, specs):
+    """The (tensor or None, shape, dtype) triples of a wrapper's arguments: each tensor contiguous, on the device, of
+    exactly that shape and type."""
+    for t, sh, dt in specs:
+        if t is not None and (t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or not t.is_cuda):
+            raise RuntimeError(f"{fn}: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+
+
 def stream():
     return torch.cuda.current_stream().cuda_stream
 
@@ -929,11 +937,10 @@ def detect_finish(rows, kept, num_classes, image_shape, offset, scale, rows_out,
     their offsets and the class counts (vrnet_detect_finish_f32).  offset / scale: the (y, x) float64 pairs of
     yolo_correct_boxes; image_shape = (ih, iw)."""
     B, cap = rows.shape[:2]
-    for t, sh, dt in ((rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32), (rows_out, (B, cap, 7), torch.float32),
-                      (draw_rows, (B * cap, 5), torch.int32), (offsets, (B + 1,), torch.int32),
-                      (det_counts, (B, num_classes), torch.int64), (flag, (1,), torch.int32)):
-        if tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous():
-            raise RuntimeError(f"detect_finish: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+    _tensors("detect_finish", ((rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32),
+                               (rows_out, (B, cap, 7), torch.float32), (draw_rows, (B * cap, 5), torch.int32),
+                               (offsets, (B + 1,), torch.int32), (det_counts, (B, num_classes), torch.int64),
+                               (flag, (1,), torch.int32)))
     _check(_lib.vrnet_detect_finish_f32(ptr(rows), ptr(kept), B, cap, int(num_classes), int(image_shape[0]), int(image_shape[1]),
                                         float(offset[0]), float(offset[1]), float(scale[0]), float(scale[1]), ptr(rows_out),
                                         ptr(draw_rows), ptr(offsets), ptr(det_counts), ptr(flag), stream()), "detect_finish")
@@ -986,9 +993,7 @@ def batch_formats(img_u8, png_u8, num_classes_seg, images=None, png_out=None, on
     img_u8 (B,H,W,3) uint8 -> images (B,3,H,W) f32; png_u8 (B,H,W) uint8 -> png (B,H,W) int64, onehot (B,H,W,ns+1) f32."""
     src = img_u8 if img_u8 is not None else png_u8
     B, H, W = src.shape[:3]
-    for t, sh in ((img_u8, (B, H, W, 3)), (png_u8, (B, H, W))):
-        if t is not None and (t.dtype != torch.uint8 or tuple(t.shape) != sh or not t.is_contiguous() or not t.is_cuda):
-            raise RuntimeError(f"batch_formats: expected a contiguous uint8 GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+    _tensors("batch_formats", ((img_u8, (B, H, W, 3), torch.uint8), (png_u8, (B, H, W), torch.uint8)))
     if img_u8 is not None and images is None:
         images = torch.empty((B, 3, H, W), dtype=torch.float32, device=src.device)
     if png_u8 is not None:
@@ -1014,11 +1019,9 @@ def letterbox(img_u8, label_u8, H, W, nw, nh, dx, dy, canvas=None, images=None, 
     if src is None or src.dim() < 3:
         raise RuntimeError("letterbox: expected frames (B, ih, iw, 3) and / or label maps (B, ih, iw)")
     B, ih, iw = src.shape[:3]
-    for t, sh, dt in ((img_u8, (B, ih, iw, 3), torch.uint8), (label_u8, (B, ih, iw), torch.uint8),
-                      (canvas, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
-                      (label_out, (B, H, W), torch.uint8)):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or not t.is_cuda):
-            raise RuntimeError(f"letterbox: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+    _tensors("letterbox", ((img_u8, (B, ih, iw, 3), torch.uint8), (label_u8, (B, ih, iw), torch.uint8),
+                           (canvas, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
+                           (label_out, (B, H, W), torch.uint8)))
     if ws is None:
         ws = _ws.get(_lib.vrnet_letterbox_workspace(B, ih, iw, nh, nw), src.device)
     elif ws.dtype != torch.uint8 or not ws.is_contiguous():
@@ -1038,12 +1041,10 @@ def render(frames, class_map, out, palette=None, mix_type=0, alpha=0.7, boxes=No
     B, ih, iw = frames.shape[:3]
     n_colors = palette.shape[0] if palette is not None else (counts.shape[1] if counts is not None else 0)
     n_rows = 0 if boxes is None else boxes.shape[0]
-    for t, sh, dt in ((out, (B, ih, iw, 3), torch.uint8), (class_map, (B, ih, iw), torch.uint8), (palette, (n_colors, 3), torch.uint8),
-                      (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32), (counts, (B, n_colors), torch.int64),
-                      (flag, (1,), torch.int32),
-                      (box_palette, (0 if box_palette is None else box_palette.shape[0], 3), torch.uint8)):
-        if t is not None and (tuple(t.shape) != sh or t.dtype != dt or not t.is_contiguous()):
-            raise RuntimeError(f"render: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
+    _tensors("render", (
+        (out, (B, ih, iw, 3), torch.uint8), (class_map, (B, ih, iw), torch.uint8), (palette, (n_colors, 3), torch.uint8),
+        (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32), (counts, (B, n_colors), torch.int64),
+        (flag, (1,), torch.int32), (box_palette, (0 if box_palette is None else box_palette.shape[0], 3), torch.uint8)))
     if out is None or (n_rows and (box_offsets is None or box_palette is None)):
         raise RuntimeError("render: out is required, and box rows need box_offsets and a box_palette")
     _check(_lib.vrnet_render_u8(ptr(frames), ptr(class_map), B, ih, iw, ptr(palette), n_colors, int(mix_type), float(alpha),
@@ -1203,12 +1204,6 @@ def _geom(geom, B, fn):
     return ptr(geom)
 
 
-def _ragged_check(fn, specs):
-    for t, sh, dt in specs:
-        if t is not None and (t.dtype != dt or tuple(t.shape) != sh or not t.is_contiguous() or not t.is_cuda):
-            raise RuntimeError(f"{fn}: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
-
-
 def letterbox_ragged_workspace_bytes(B, ihm, iwm, H, W, max_taps):
     return _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, max_taps)
 
@@ -1220,7 +1215,7 @@ def letterbox_ragged(img_u8, label_u8, geom, H, W, max_taps, canvas=None, images
     if src is None or src.dim() < 3:
         raise RuntimeError("letterbox_ragged: expected frames (B, ihm, iwm, 3) and / or label maps (B, ihm, iwm)")
     B, ihm, iwm = src.shape[:3]
-    _ragged_check("letterbox_ragged", ((img_u8, (B, ihm, iwm, 3), torch.uint8), (label_u8, (B, ihm, iwm), torch.uint8),
+    _tensors("letterbox_ragged", ((img_u8, (B, ihm, iwm, 3), torch.uint8), (label_u8, (B, ihm, iwm), torch.uint8),
                                        (canvas, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
                                        (label_out, (B, H, W), torch.uint8), (flag, (1,), torch.int32)))
     need = _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, int(H), int(W), int(max_taps))
@@ -1237,7 +1232,7 @@ def detect_finish_ragged(rows, kept, geom, num_classes, capacity, rows_out, draw
     """`detect_finish` with the image shape and the un-map scalars of image b from geom[b]
     (vrnet_detect_finish_ragged_f32); capacity = (ihm, iwm)."""
     B, cap = rows.shape[:2]
-    _ragged_check("detect_finish_ragged", (
+    _tensors("detect_finish_ragged", (
         (rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32), (rows_out, (B, cap, 7), torch.float32),
         (draw_rows, (B * cap, 5), torch.int32), (offsets, (B + 1,), torch.int32), (det_counts, (B, num_classes), torch.int64),
         (flag, (1,), torch.int32)))
@@ -1255,7 +1250,7 @@ def seg_predict_ragged(x, geom, out, ws, flag=None):
     """x (B, C, H, W) fp32 -> out (B, ihm, iwm) uint8, the window and size of image b from geom[b], 0 outside the image
     (vrnet_seg_predict_ragged_f32); ws: seg_predict_ragged_workspace_bytes(B, C, H, W) bytes."""
     B, C, H, W = x.shape
-    _ragged_check("seg_predict_ragged", ((x, (B, C, H, W), torch.float32), (out, (B,) + tuple(out.shape[1:3]), torch.uint8),
+    _tensors("seg_predict_ragged", ((x, (B, C, H, W), torch.float32), (out, (B,) + tuple(out.shape[1:3]), torch.uint8),
                                          (flag, (1,), torch.int32)))
     _check(_lib.vrnet_seg_predict_ragged_f32(ptr(x), _geom(geom, B, "seg_predict_ragged"), B, C, H, W, out.shape[1], out.shape[2],
                                              ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), "seg_predict_ragged")
@@ -1270,7 +1265,7 @@ def render_ragged(frames, class_map, geom, out, palette=None, mix_type=0, alpha=
     B, ih, iw = frames.shape[:3]
     n_colors = palette.shape[0] if palette is not None else (counts.shape[1] if counts is not None else 0)
     n_rows = 0 if boxes is None else boxes.shape[0]
-    _ragged_check("render_ragged", (
+    _tensors("render_ragged", (
         (frames, (B, ih, iw, 3), torch.uint8), (out, (B, ih, iw, 3), torch.uint8), (class_map, (B, ih, iw), torch.uint8),
         (palette, (n_colors, 3), torch.uint8), (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32),
         (counts, (B, n_colors), torch.int64), (flag, (1,), torch.int32),
@@ -1296,7 +1291,7 @@ def seg_targets_ragged(label_u8, geom, H, W, num_classes_seg, png_out=None, oneh
         png_out = torch.empty((B, H, W), dtype=torch.int64, device=label_u8.device)
     if onehot is None:
         onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=label_u8.device)
-    _ragged_check("seg_targets_ragged", ((label_u8, (B, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
+    _tensors("seg_targets_ragged", ((label_u8, (B, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
                                          (onehot, (B, H, W, ns + 1), torch.float32), (flag, (1,), torch.int32)))
     _check(_lib.vrnet_seg_targets_ragged_u8(ptr(label_u8), _geom(geom, B, "seg_targets_ragged"), B, ihm, iwm, H, W, ns,
                                             ptr(png_out), ptr(onehot), ptr(flag), stream()), "seg_targets_ragged")
@@ -1316,7 +1311,7 @@ def box_targets_ragged(boxes, counts, geom, capacity, H, W, targets=None, counts
         targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
     if counts_out is None:
         counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
-    _ragged_check("box_targets_ragged", ((boxes, (B, max_gt, 5), torch.int32), (counts, (B,), torch.int32),
+    _tensors("box_targets_ragged", ((boxes, (B, max_gt, 5), torch.int32), (counts, (B,), torch.int32),
                                          (targets, (B, max_gt, 5), torch.float32), (counts_out, (B,), torch.int32),
                                          (flag, (1,), torch.int32)))
     _check(_lib.vrnet_box_targets_ragged_f32(ptr(boxes), ptr(counts), _geom(geom, B, "box_targets_ragged"), B, max_gt,

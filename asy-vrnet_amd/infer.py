@@ -56,19 +56,14 @@ def validate_inputs(frames_u8, radar, batch, frame_shape, input_shape):
     """frames (B, ih, iw, 3) uint8 and radar (B, 4, H, W) float32 / float64, numpy arrays or tensors, of exactly the
     shapes the pipeline was built for (with batch 1 the leading axis may be missing); returns them as tensors."""
     f = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
-    r = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
     if f.dtype != torch.uint8:
         raise RuntimeError(f"FramePipeline: expected uint8 frames, got {f.dtype}")
-    if r.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError(f"FramePipeline: expected float32 or float64 radar maps, got {r.dtype}")
+    r = validate_radar(radar, batch, input_shape)
     f = f[None] if batch == 1 and f.dim() == 3 else f
-    r = r[None] if batch == 1 and r.dim() == 3 else r
-    want_f, want_r = (batch,) + tuple(frame_shape) + (3,), (batch, 4) + tuple(input_shape)
+    want_f = (batch,) + tuple(frame_shape) + (3,)
     if tuple(f.shape) != want_f:
         raise RuntimeError(f"FramePipeline: built for frames of shape {want_f}, got {tuple(f.shape)} (a pipeline is tied to its "
                            "shapes: build another one for another frame size or batch)")
-    if tuple(r.shape) != want_r:
-        raise RuntimeError(f"FramePipeline: built for radar maps of shape {want_r}, got {tuple(r.shape)}")
     return f, r
 
 
@@ -199,7 +194,7 @@ class FramePipeline:
             self.max_taps = data.default_max_taps(self.frame_shape, self.input_shape) if max_taps is None else int(max_taps)
             table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, self.frame_shape,
                                         self.max_taps, "FramePipeline")
-            self.geom = torch.from_numpy(table.view(np.uint8).reshape(B, -1).copy()).to(dev)
+            self.geom = data.geometry_bytes(table).to(dev)
         self.cap = None                       # the NMS buffers follow the anchor count of the first (warm-up) pass
         self.graph = self.result = None
         if graph:
@@ -222,47 +217,16 @@ class FramePipeline:
         self._det_counts = torch.empty((B, self.num_classes), dtype=torch.int64, device=dev)
 
     def _chain(self):
+        """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
+        device where a fixed one passes it in the launch arguments: the four frame ops differ, nothing else."""
         from . import decode, hip            # the library loads with the first pass, not with the package
-        S, F = self.input_shape, self.frame_shape
-        if self.ragged:
-            return self._ragged_chain()
-        images, _ = data.device_letterbox(self.frames_u8, S, letterbox_image=self.letterbox_image, device=self.device)
-        radar = data.device_radar(self.radar, True, self.device) if self.normalise_radar else self.radar
-        det, seg = self.model(images, radar)
-        pred = decode.decode_outputs(det, S)
-        if self.cap is None:
-            self._allocate(pred.shape[1])
-        rows, scores, classes, ids, counts = self._cand
-        self.flag.zero_()
-        hip.detect_select(pred, self.num_classes, self.conf_thres, rows, scores, classes, ids, counts)
-        hip.nms_capped(rows, scores, classes, ids, counts, self.batch, pred.shape[1], self.cap, self.nms_thres, self._nms_ws,
-                       self._keep, self._kept, self._kept_rows, self.flag)
-        hip.detect_finish(self._kept_rows, self._kept, self.num_classes, F, self.offset, self.scale, self._rows,
-                          self._draw_rows, self._offsets, self._det_counts, self.flag)
-        if self.letterbox_image:
-            class_map = decode.seg_predict(seg, S, F)
-        else:                                 # the frame was stretched over the whole input: the window is the input
-            class_map = torch.empty((self.batch,) + F, dtype=torch.uint8, device=self.device)
-            ws = torch.empty(hip.seg_predict_workspace_bytes(self.batch, seg.shape[1], S[0], S[1]), dtype=torch.uint8,
-                             device=self.device)
-            hip.seg_predict(seg.contiguous().float(), 0, 0, S[0], S[1], class_map, ws)
-        rendered = seg_counts = None
-        if self.render:
-            rendered, seg_counts = rendering.render_frame(
-                self.frames_u8, class_map, (self._draw_rows, self._offsets), palette=self.seg_palette, mix_type=self.mix_type,
-                alpha=self.alpha, count=True, box_palette=self.box_palette, thickness=self.thickness, flag=self.flag,
-                device=self.device)
-        result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
-        self._tail(result)
-        return result
-
-    def _ragged_chain(self):
-        """`_chain` with the geometry of every image read from `self.geom` on the device."""
-        from . import decode, hip
         (H, W), F, B, dev = self.input_shape, self.frame_shape, self.batch, self.device
-        self.flag.zero_()
-        images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        hip.letterbox_ragged(self.frames_u8, None, self.geom, H, W, self.max_taps, images=images, flag=self.flag)
+        self.flag.zero_()                     # first: the ragged letterbox may raise FLAG_GEOMETRY
+        if self.ragged:
+            images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+            hip.letterbox_ragged(self.frames_u8, None, self.geom, H, W, self.max_taps, images=images, flag=self.flag)
+        else:
+            images, _ = data.device_letterbox(self.frames_u8, (H, W), letterbox_image=self.letterbox_image, device=dev)
         radar = data.device_radar(self.radar, True, dev) if self.normalise_radar else self.radar
         det, seg = self.model(images, radar)
         pred = decode.decode_outputs(det, (H, W))
@@ -272,14 +236,28 @@ class FramePipeline:
         hip.detect_select(pred, self.num_classes, self.conf_thres, rows, scores, classes, ids, counts)
         hip.nms_capped(rows, scores, classes, ids, counts, B, pred.shape[1], self.cap, self.nms_thres, self._nms_ws,
                        self._keep, self._kept, self._kept_rows, self.flag)
-        hip.detect_finish_ragged(self._kept_rows, self._kept, self.geom, self.num_classes, F, self._rows, self._draw_rows,
-                                 self._offsets, self._det_counts, self.flag)
-        class_map = decode.seg_predict_ragged(seg, self.geom, F, self.flag)
+        finished = (self._rows, self._draw_rows, self._offsets, self._det_counts, self.flag)
+        if self.ragged:
+            hip.detect_finish_ragged(self._kept_rows, self._kept, self.geom, self.num_classes, F, *finished)
+            class_map = decode.seg_predict_ragged(seg, self.geom, F, self.flag)
+        else:
+            hip.detect_finish(self._kept_rows, self._kept, self.num_classes, F, self.offset, self.scale, *finished)
+            if self.letterbox_image:
+                class_map = decode.seg_predict(seg, (H, W), F)
+            else:                             # the frame was stretched over the whole input: the window is the input
+                class_map = torch.empty((B,) + F, dtype=torch.uint8, device=dev)
+                ws = torch.empty(hip.seg_predict_workspace_bytes(B, seg.shape[1], H, W), dtype=torch.uint8, device=dev)
+                hip.seg_predict(seg.contiguous().float(), 0, 0, H, W, class_map, ws)
         rendered = seg_counts = None
         if self.render:
-            rendered, seg_counts = rendering.render_frame_ragged(
-                self.frames_u8, self.geom, class_map, (self._draw_rows, self._offsets), palette=self.seg_palette,
-                mix_type=self.mix_type, alpha=self.alpha, count=True, box_palette=self.box_palette, flag=self.flag)
+            picture = dict(palette=self.seg_palette, mix_type=self.mix_type, alpha=self.alpha, count=True,
+                           box_palette=self.box_palette, flag=self.flag)
+            boxes = (self._draw_rows, self._offsets)
+            if self.ragged:
+                rendered, seg_counts = rendering.render_frame_ragged(self.frames_u8, self.geom, class_map, boxes, **picture)
+            else:
+                rendered, seg_counts = rendering.render_frame(self.frames_u8, class_map, boxes, thickness=self.thickness,
+                                                              device=dev, **picture)
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
         self._tail(result)
         return result
@@ -331,7 +309,7 @@ class FramePipeline:
         with torch.cuda.device(self.device):
             if self.ragged:
                 data.fill_slots(self.frames_u8, f, sizes)
-                self.geom.copy_(torch.from_numpy(table.view(np.uint8).reshape(self.batch, -1)), non_blocking=True)
+                self.geom.copy_(data.geometry_bytes(table), non_blocking=True)
                 self.sizes = sizes
             else:
                 self.frames_u8.copy_(f, non_blocking=True)

@@ -668,6 +668,7 @@ int vrnet_detect_finish_f32(const float* rows, const int* kept, int B, int cap, 
  *   resize is OpenCV's INTER_LINEAR (cv2.resize at callbacks.py:153): per axis scale = src / dst, f = (d + 0.5) * scale - 0.5
  *   in fp32, s = floor(f), f -= s, s < 0 -> (0, 0), s >= src - 1 -> (src - 1, 0); horizontal taps blended first.
  *   workspace: vrnet_seg_predict_workspace(B, C, nh, nw) bytes (the window's softmax, (B, C, nh, nw) fp32).
+ *   The kernels are those of vrnet_seg_predict_ragged_f32, given one record for every image in their arguments.
  * vrnet_confusion_hist, utils_seg/utils_metrics.py:35-44 (fast_hist, called per image at :102): hist (n, n) int64 +=
  *   counts of the pairs (label[i], pred[i]), i < N, row = label, column = pred; label / pred of label_bytes / pred_bytes
  *   = 1 (uint8) or 8 (int64) each; n <= 32.  A pair whose label or prediction is outside [0, n) is skipped (the reference
@@ -825,8 +826,8 @@ int vrnet_render_u8(const unsigned char* frames, const unsigned char* class_map,
  *   a record that had to be clamped, one with ih <= 0 or iw <= 0 -- or, in the letterbox, whose taps exceed max_taps and
  *   are truncated -- sets bit 256 (FLAG_GEOMETRY) of *flag (OR-ed in; flag may be NULL except in detect_finish).  An image
  *   or window clamped to nothing is all padding.
- * GRIDS are sized by the capacities with the image as grid dimension y: a workgroup lies inside one image and reads one
- *   record.  All calls: no allocation, no host synchronisation, capturable in a graph.
+ * GRIDS are sized by the capacities, a whole number of workgroups per image (the image is grid dimension y, or
+ *   blockIdx.x / blocks-per-image in seg_predict): a workgroup lies inside one image and reads one record.  All calls: no allocation, no host synchronisation, capturable in a graph.
  * vrnet_letterbox_ragged_u8: vrnet_letterbox_u8 per image -- img (B, ihm, iwm, 3), label (B, ihm, iwm) -> canvas (B, H, W, 3)
  *   / images (B, 3, H, W) / label_out (B, H, W), the same Pillow-exact bytes.  The tables of image b are built on the
  *   device in slot b of the workspace ((W + H) * (3 + max_taps) ints); the horizontal pass writes a (B, ihm, W, 3)
@@ -835,7 +836,7 @@ int vrnet_render_u8(const unsigned char* frames, const unsigned char* class_map,
  *   workspace: vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, max_taps) bytes.
  * vrnet_detect_finish_ragged_f32: vrnet_detect_finish_f32 with image_h, image_w and the four scalars of image b from geom[b].
  * vrnet_seg_predict_ragged_f32: vrnet_seg_predict_f32 with the window and the output size of image b from geom[b]; out is
- *   the padded (B, ihm, iwm) map.  workspace: vrnet_seg_predict_ragged_workspace(B, C, H, W) bytes.
+ *   the padded (B, ihm, iwm) map, written by the same kernels.  workspace: vrnet_seg_predict_ragged_workspace(B, C, H, W) bytes.
  * vrnet_render_ragged_u8: vrnet_render_u8 on the padded frames / class_map / out with ih, iw, thickness of image b from
  *   geom[b]; boxes are clipped to the image's own size and counts cover its own pixels only.  out must not overlap frames
  *   (the padding is written): there is no in-place form. */

@@ -346,6 +346,32 @@ def test_each_output_alone_and_a_dirty_workspace():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("ih,iw", [(37, 53), (150, 70), (64, 53)])   # both passes up-scale, both down-scale, neither runs
+def test_the_workspace_is_all_the_call_writes(ih, iw):
+    """A workspace of exactly letterbox_workspace_bytes, carved from the front of a larger 0xA5 tensor: the bytes behind it
+    stay 0xA5 (the tables and the horizontal result of the kernels fit the size the library reports) and the outputs
+    equal the restatement."""
+    import asy_vrnet_amd.hip as hip
+    B, H, W = 3, 64, 96
+    img, lab = frames(np.random.default_rng(ih * 1000 + iw), B, ih, iw)
+    want_canvas, want_label, (nw, nh) = letterbox_restated(img, lab, H, W)
+    nw2, nh2, dx, dy = data.letterbox_geometry(iw, ih, W, H)
+    assert (nw2, nh2) == (nw, nh) and ((nw, nh) == (iw, ih)) == ((ih, iw) == (64, 53))
+    need = hip.letterbox_workspace_bytes(B, ih, iw, nh, nw)
+    big = torch.full((need + (1 << 20),), 0xA5, dtype=torch.uint8, device="cuda")
+    new = lambda *s, dtype=torch.uint8: torch.full(s, 77, dtype=dtype, device="cuda")
+    canvas, images, label = new(B, H, W, 3), new(B, 3, H, W, dtype=torch.float32), new(B, H, W)
+    hip.letterbox(torch.from_numpy(img).cuda(), torch.from_numpy(lab).cuda(), H, W, nw, nh, dx, dy, canvas=canvas, images=images,
+                  label_out=label, ws=big[:need])
+    touched = int((big[need:] != 0xA5).sum())
+    print(f"letterbox {ih} x {iw} -> window {nh} x {nw}: workspace {need} bytes, {touched} bytes behind it written")
+    assert touched == 0
+    assert np.array_equal(canvas.cpu().numpy(), want_canvas)
+    assert np.array_equal(label.cpu().numpy(), want_label)
+    assert np.array_equal(images.cpu().numpy(), normalise_restated(want_canvas))
+
+
+@pytest.mark.gpu
 def test_letterbox_in_a_captured_graph():
     rng = np.random.default_rng(22)
     first, first_lab = frames(rng, 2, 270, 480)

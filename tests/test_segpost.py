@@ -303,6 +303,34 @@ def test_seg_predict_matches_restatement(B, C, input_shape, image_shape):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("image_shape", [(37, 53), (150, 70)])
+def test_seg_predict_workspace_is_all_the_call_writes(image_shape):
+    """A workspace of exactly seg_predict_workspace_bytes, carved from the front of a larger 0xA5 tensor: the bytes behind
+    it stay 0xA5 (the probability planes of the kernels fit the size the library reports) and the class map equals the
+    restatement as in `check_predict`."""
+    import asy_vrnet_amd.hip as hip
+    B, C, input_shape = 3, 9, (64, 96)
+    rng = np.random.default_rng(image_shape[0])
+    x = torch.from_numpy((3.0 * rng.standard_normal((B, C) + input_shape)).astype(F32)).cuda()
+    top, left, nh, nw = window_restated(input_shape, image_shape)
+    assert (top, left, nh, nw) == tuple(decode.seg_window(input_shape, image_shape))
+    need = hip.seg_predict_workspace_bytes(B, C, nh, nw)
+    big = torch.full((need + (1 << 20),), 0xA5, dtype=torch.uint8, device="cuda")
+    got = torch.full((B,) + image_shape, 77, dtype=torch.uint8, device="cuda")
+    hip.seg_predict(x, top, left, nh, nw, got, big[:need])
+    touched = int((big[need:] != 0xA5).sum())
+    want, gap = seg_predict_restated(x.cpu().numpy(), input_shape, image_shape)
+    got = got.cpu().numpy()
+    near = gap < NEAR_TIE
+    wrong = (got != want) & ~near
+    print(f"seg_predict -> {image_shape}: workspace {need} bytes, {touched} bytes behind it written; {int(near.sum())} of "
+          f"{near.size} pixels near a tie, {int(wrong.sum())} differ outside a near tie")
+    assert touched == 0
+    assert not wrong.any()
+    assert near.sum() <= MAX_NEAR_TIES * near.size
+
+
+@pytest.mark.gpu
 def test_seg_predict_duplicated_channels_pick_lower_index():
     rng = np.random.default_rng(12)
     x = (3.0 * rng.standard_normal((2, 6, 512, 512))).astype(F32)
