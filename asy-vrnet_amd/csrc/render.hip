@@ -27,6 +27,7 @@
 // Data errors do not stop the launch: a class id >= n_colors takes the last colour and is not counted, a colour index
 // outside [0, n_box_colors) is clamped, rows past RN_MAXBOX of one image are ignored, and each sets its bit in *flag.
 #include "common.h"
+#include "pixel.h"                   // blend_byte: ImagingBlend on one byte, shared with heatmap.hip
 
 #pragma clang fp contract(off)
 
@@ -78,14 +79,6 @@ __device__ __forceinline__ void raise_flag(const RenderArgs& p, int bit) {
 
 __device__ __forceinline__ unsigned int pack_rgb(const unsigned char* c) {
   return (unsigned int)c[0] | ((unsigned int)c[1] << 8) | ((unsigned int)c[2] << 16);
-}
-
-// ImagingBlend (Blend.c) on one byte
-__device__ __forceinline__ unsigned int blend_byte(unsigned int a, unsigned int b, float alpha) {
-  const float d = (float)((int)b - (int)a);
-  const float t = alpha * d;
-  const float v = (float)a + t;
-  return (unsigned int)(int)v & 255u;
 }
 
 // the pixel before the boxes: frame and colour as packed r | g << 8 | b << 16

@@ -10,6 +10,7 @@
 //             non-empty bin; integer atomics only, so the result does not depend on the order in which workgroups run
 // The f_score metric (utils_metrics.py:12-31) sits next to the seg loss in loss.hip.
 #include "common.h"
+#include "pixel.h"                   // linear_tap: the OpenCV INTER_LINEAR tap of one axis, shared with heatmap.hip
 
 // The source coordinate is computed in fp32 with one rounding per operation, as the rule it implements states; a fused
 // multiply-add could move floor() across an integer and pick another tap.
@@ -64,19 +65,6 @@ __global__ __launch_bounds__(256) void segp_softmax_kernel(const SegPredArgs p) 
   const long plane = (long)p.H * p.W;
   softmax_pixel(p.x + b * p.C * plane + (long)(g.seg_top + y) * p.W + (g.seg_left + xx), plane, p.C,
                 p.prob + b * p.pslot + r, n);
-}
-
-// OpenCV resize INTER_LINEAR source coordinate along one axis: f = (d + 0.5) * scale - 0.5, s = floor(f), f -= s, clamped
-// to the first / last source pixel with weight 0 on the second tap.
-__device__ __forceinline__ void linear_tap(int d, float scale, int src, int& s0, int& s1, float& f) {
-  f = ((float)d + 0.5f) * scale - 0.5f;
-  const float fl = floorf(f);
-  int s = (int)fl;
-  f = f - fl;
-  if (s < 0) { s = 0; f = 0.f; }
-  if (s >= src - 1) { s = src - 1; f = 0.f; }
-  s0 = s;
-  s1 = s + 1 < src ? s + 1 : s;
 }
 
 // output pixel (oy, ox) of one image: the arg-max over the classes of the bilinear blend of prob (C, nh, nw)

@@ -147,6 +147,10 @@ _SIGS = {
     "vrnet_render_ragged_u8": ([P, P, P, I, I, I, P, I, I, F, P, P, I, P, I, P, P, P, P], I),
     "vrnet_seg_targets_ragged_u8": ([P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_box_targets_ragged_f32": ([P, P, P, I, I, I, I, I, I, P, P, P, P], I),
+    "vrnet_heatmap_workspace": ([I, I, I], L),
+    "vrnet_heatmap_f32": ([P, P, P] + [I] * 11 + [P, P, F, P, P, P, P, L, P], I),
+    "vrnet_heatmap_ragged_workspace": ([I, I, I], L),
+    "vrnet_heatmap_ragged_f32": ([P, P, P, P] + [I] * 7 + [P, P, F, P, P, P, P, P, L, P], I),
     "vrnet_yolo_loss_workspace": ([I, L, I, I], L),
     "vrnet_yolo_loss_f32": ([P, P, P, P, P, I, I, I, P, P, I, F, P, P, P, P, P, L, P], I),
     "vrnet_seg_loss_workspace": ([I, I, L], L),
@@ -1053,6 +1057,35 @@ def render(frames, class_map, out, palette=None, mix_type=0, alpha=0.7, boxes=No
                                 ptr(flag), stream()), "render")
 
 
+def _heat_levels(fn, levels, H, W):
+    """The three raw detection maps of an (H, W) input: (B, 5 + nc, H/8, W/8), (.., H/16, W/16), (.., H/32, W/32) fp32."""
+    if len(levels) != 3 or levels[0] is None or levels[0].dim() != 4 or levels[0].shape[1] < 6:
+        raise RuntimeError(f"{fn}: expected three detection maps (B, 5 + nc, h, w) with nc >= 1")
+    B, C = levels[0].shape[:2]
+    _tensors(fn, tuple((t, (B, C, H // s, W // s), torch.float32) for t, s in zip(levels, (8, 16, 32))))
+    return B, C - 5
+
+
+def heatmap_workspace_bytes(B, H, W):
+    return _lib.vrnet_heatmap_workspace(B, H, W)
+
+
+def heatmap(levels, H, W, mask, minmax, ws, window=0, dx=0, dy=0, nw=0, nh=0, frames=None, cmap=None, alpha=0.5, out=None):
+    """yolo.py:288-351 on the device (vrnet_heatmap_f32): levels the three raw detection maps of an (H, W) input -> mask
+    (B, ih, iw) uint8 and minmax (B, 2) int32; with out (B, ih, iw, 3) uint8 also the blend of cmap (256, 3) uint8 over
+    frames (B, ih, iw, 3) uint8.  window = 1 maps the pixels through the letterbox window (dx, dy, nw, nh).  ws:
+    heatmap_workspace_bytes(B, H, W) bytes."""
+    B, nc = _heat_levels("heatmap", levels, int(H), int(W))
+    if mask is None or mask.dim() != 3:
+        raise RuntimeError("heatmap: mask (B, ih, iw) is required")
+    ih, iw = mask.shape[1:]
+    _tensors("heatmap", ((mask, (B, ih, iw), torch.uint8), (minmax, (B, 2), torch.int32), (frames, (B, ih, iw, 3), torch.uint8),
+                         (out, (B, ih, iw, 3), torch.uint8), (cmap, (256, 3), torch.uint8)))
+    _check(_lib.vrnet_heatmap_f32(ptr(levels[0]), ptr(levels[1]), ptr(levels[2]), B, nc, int(H), int(W), ih, iw, int(window),
+                                  int(dx), int(dy), int(nw), int(nh), ptr(frames), ptr(cmap), float(alpha), ptr(mask), ptr(out),
+                                  ptr(minmax), ptr(ws), ws.numel(), stream()), "heatmap")
+
+
 def yolo_loss(levels, grads, strides, labels, counts, max_gt, grad_scale, out, fg=None, matched=None, piou=None):
     """levels / grads: lists of contiguous (B, C, h, w) fp32 GPU tensors (grads None = value only)."""
     n = len(levels)
@@ -1318,3 +1351,22 @@ def box_targets_ragged(boxes, counts, geom, capacity, H, W, targets=None, counts
                                              int(capacity[0]), int(capacity[1]), int(H), int(W), ptr(targets), ptr(counts_out),
                                              ptr(flag), stream()), "box_targets_ragged")
     return targets, counts_out
+
+
+def heatmap_ragged_workspace_bytes(B, H, W):
+    return _lib.vrnet_heatmap_ragged_workspace(B, H, W)
+
+
+def heatmap_ragged(levels, geom, H, W, mask, minmax, ws, window=1, frames=None, cmap=None, alpha=0.5, out=None, flag=None):
+    """`heatmap` on padded slots (vrnet_heatmap_ragged_f32): mask (B, ihm, iwm), frames / out (B, ihm, iwm, 3); ih, iw and
+    the window of image b from geom[b]; 0 outside the image.  ws: heatmap_ragged_workspace_bytes(B, H, W) bytes."""
+    B, nc = _heat_levels("heatmap_ragged", levels, int(H), int(W))
+    if mask is None or mask.dim() != 3:
+        raise RuntimeError("heatmap_ragged: mask (B, ihm, iwm) is required")
+    ihm, iwm = mask.shape[1:]
+    _tensors("heatmap_ragged", ((mask, (B, ihm, iwm), torch.uint8), (minmax, (B, 2), torch.int32),
+                                (frames, (B, ihm, iwm, 3), torch.uint8), (out, (B, ihm, iwm, 3), torch.uint8),
+                                (cmap, (256, 3), torch.uint8), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_heatmap_ragged_f32(ptr(levels[0]), ptr(levels[1]), ptr(levels[2]), _geom(geom, B, "heatmap_ragged"), B, nc,
+                                         int(H), int(W), ihm, iwm, int(window), ptr(frames), ptr(cmap), float(alpha), ptr(mask),
+                                         ptr(out), ptr(minmax), ptr(flag), ptr(ws), ws.numel(), stream()), "heatmap_ragged")

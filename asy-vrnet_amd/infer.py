@@ -114,12 +114,18 @@ class FrameResult:
     From a ragged pipeline class_map (B, ihm, iwm) and rendered (B, ihm, iwm, 3) are PADDED tensors of the capacity: image b
     is `class_map[b, :ih_b, :iw_b]` / `rendered[b, :ih_b, :iw_b]` with (ih_b, iw_b) = sizes[b], everything outside it is 0,
     and seg_counts[b] counts the image's own pixels only.  sizes: the (B, 2) host integers of that run (None from a
-    fixed-size pipeline)."""
-    __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes")
+    fixed-size pipeline).
+    From a pipeline with heatmap=True (None otherwise): heat_mask (B, ih, iw) uint8, heat_picture (B, ih, iw, 3) uint8 and
+    heat_range (B, 2) int32 = each mask's (min, max), what `render.heatmap` returns for the frames and the raw detection
+    maps of the run; padded like class_map / rendered from a ragged pipeline."""
+    __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
+                 "heat_picture", "heat_range")
 
-    def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None):
+    def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
+                 heat_picture=None, heat_range=None):
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
+        self.heat_mask, self.heat_picture, self.heat_range = heat_mask, heat_picture, heat_range
 
     def detections(self):
         """The list `decode.non_max_suppression` returns: per image an (N_b, 7) float32 numpy array in the same order,
@@ -146,7 +152,10 @@ class FramePipeline:
     the host.  radar_dtype: the type of the static radar buffer; float64 maps are normalised in float64, as the reference
     normalises a float64 .npz, only in a float64 buffer.  render / mix_type / alpha / seg_palette / box_palette: the
     `render.render_frame` picture (seg overlay, box outlines of thickness yolo.py:164) and the per-class pixel counts;
-    default palettes `render.seg_palette(num_seg_classes)` and `render.det_palette(num_classes)`.
+    default palettes `render.seg_palette(num_seg_classes)` and `render.det_palette(num_classes)`.  heatmap=True adds the
+    detection heat map of yolo.py:288-351 (`render.heatmap` on the raw detection maps and the frames, jet blended at
+    heat_alpha; aligned through the letterbox window when letterbox_image is set) to the chain and the result; with the
+    default nothing about the chain, the result or the graph changes.
 
     graph=True warms the chain up (twice, on a side stream: workspaces and caches exist before the capture; the model's
     buffers are restored afterwards) and captures it as one hipGraph; run() then copies the inputs into the static
@@ -163,11 +172,15 @@ class FramePipeline:
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
-                 box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None):
+                 box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
+                 heat_alpha=0.5):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
         if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
             raise RuntimeError(f"FramePipeline: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
+        if not 0.0 <= float(heat_alpha) <= 1.0:
+            raise RuntimeError(f"FramePipeline: heat_alpha must lie in [0, 1], got {heat_alpha!r}")
+        self.heatmap, self.heat_alpha = bool(heatmap), float(heat_alpha)
         if radar_dtype not in (torch.float32, torch.float64) or (radar_dtype == torch.float64 and not normalise_radar):
             raise RuntimeError("FramePipeline: radar_dtype is float32, or float64 together with normalise_radar")
         self.model = model
@@ -259,6 +272,13 @@ class FramePipeline:
                 rendered, seg_counts = rendering.render_frame(self.frames_u8, class_map, boxes, thickness=self.thickness,
                                                               device=dev, **picture)
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
+        if self.heatmap:
+            if self.ragged:
+                heat = rendering.heatmap_ragged(self.frames_u8, det, self.geom, (H, W), window=self.letterbox_image,
+                                                alpha=self.heat_alpha, flag=self.flag)
+            else:
+                heat = rendering.heatmap(self.frames_u8, det, (H, W), letterbox_image=self.letterbox_image, alpha=self.heat_alpha)
+            result.heat_picture, result.heat_mask, result.heat_range = heat
         self._tail(result)
         return result
 
@@ -329,9 +349,10 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     radar_root/<frame id>.npz (`data.load_radar` by `data.frame_id` of the file name), in batches of pipeline.batch.  A
     final partial batch is filled by repeating the last picture; the repeats are dropped here.  Returns a list of
     (file name, (N, 7) detections) in that order; with dir_save_path the rendered frame of every picture, sliced to its own
-    size, is saved there as <stem>.png through Pillow (the reference renames .jpg to .png; here every picture is a PNG).  Two
-    pictures that differ only in their extension would then share one output file: with dir_save_path that raises before
-    anything runs."""
+    size, is saved there as <stem>.png through Pillow (the reference renames .jpg to .png; here every picture is a PNG), and
+    from a pipeline with heatmap=True its heat picture as <stem>_heat.png beside it.  Two pictures that would share one
+    output file (names that differ only in their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on): with
+    dir_save_path that raises before anything runs."""
     from PIL import Image
     if not getattr(pipeline, "ragged", False):
         raise RuntimeError("predict_dir: needs a ragged pipeline (FramePipeline(..., ragged=True)): a folder holds pictures of any size")
@@ -339,9 +360,11 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     if dir_save_path is not None:
         stems = {}
         for n in names:
-            other = stems.setdefault(os.path.splitext(n)[0], n)
-            if other != n:
-                raise RuntimeError(f"predict_dir: {other} and {n} would both be saved as {os.path.splitext(n)[0]}.png")
+            stem = os.path.splitext(n)[0]
+            for target in (stem, stem + "_heat") if getattr(pipeline, "heatmap", False) else (stem,):
+                other = stems.setdefault(target, n)
+                if other != n:
+                    raise RuntimeError(f"predict_dir: {other} and {n} would both be saved as {target}.png")
     B, out = pipeline.batch, []
     if dir_save_path is not None:
         os.makedirs(dir_save_path, exist_ok=True)
@@ -353,9 +376,13 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         result = pipeline.run(frames + frames[-1:] * fill, np.stack(radar + radar[-1:] * fill))
         dets = result.detections()
         rendered = None if dir_save_path is None or result.rendered is None else result.rendered.cpu().numpy()
+        heat = None if dir_save_path is None else getattr(result, "heat_picture", None)
+        heat = None if heat is None else heat.cpu().numpy()
         for b, n in enumerate(chunk):
             out.append((n, dets[b]))
+            ih, iw = (int(v) for v in result.sizes[b])
             if rendered is not None:
-                ih, iw = (int(v) for v in result.sizes[b])
                 Image.fromarray(rendered[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + ".png"))
+            if heat is not None:
+                Image.fromarray(heat[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_heat.png"))
     return out

@@ -14,8 +14,18 @@ while left+i <= right-i and top+i <= bottom-i.  It equals `ImageDraw.rectangle(o
 cases: Pillow paints a ring of ONE row (y0 == y1) two rows high ([5,5,5,5] paints (5,5) and (5,6)), and it raises
 ValueError for x1 < x0 where this module paints nothing.
 
-Out of scope: the label text and its filled background (they need the reference's font file), crop saving,
-`detect_heatmap` (cv2) and video I/O."""
+* `heatmap_mask` / `heatmap` / `heatmap_ragged`: yolo.py:288-351 `detect_heatmap` (csrc/heatmap.hip) -- per level
+  sigmoid(max class logit) * sigmoid(objectness), OpenCV's INTER_LINEAR resize to the frame, times 255 truncated to a byte,
+  the max over the three levels; then matplotlib's `imshow(mask, alpha, cmap="jet")` colour rule (default normalisation:
+  vmin / vmax are the mask's own min / max) blended over the frame.  Two things are NOT reproduced.  The reference saves
+  matplotlib's FIGURE, a 200-dpi canvas with margins onto which both images are resampled; here the picture has the
+  frame's own resolution and is `Image.blend(frame, jet[index], alpha)` per byte.  And under a letterbox the reference
+  still stretches the whole level map, grey bars included, over the picture, so the heat is misaligned: letterbox_image=False
+  is that faithful form (valid for any frame), letterbox_image=True maps every pixel through the letterbox window first,
+  which is this project's own definition (see csrc/heatmap.hip).
+* `jet_lut`: matplotlib's "jet" as 256 x 3 bytes, from its segment data; matplotlib itself is not imported.
+
+Out of scope: the label text and its filled background (they need the reference's font file), crop saving and video I/O."""
 import colorsys
 
 import numpy as np
@@ -249,6 +259,175 @@ def render_frame_ragged(frames_u8, geom, class_map=None, results=None, palette=N
                           box_offsets=offsets, box_palette=None if bpal is None else _palette_on(bpal, dev), counts=counts,
                           flag=flag)
     return (out, counts) if count else out
+
+
+# matplotlib's "jet" (_cm.py `_jet_data`): per channel the (x, y) break points of a piecewise-linear map
+_JET_SEGMENTS = (
+    ((0.00, 0.0), (0.35, 0.0), (0.66, 1.0), (0.89, 1.0), (1.00, 0.5)),
+    ((0.000, 0.0), (0.125, 0.0), (0.375, 1.0), (0.640, 1.0), (0.910, 0.0), (1.000, 0.0)),
+    ((0.00, 0.5), (0.11, 1.0), (0.34, 1.0), (0.65, 0.0), (1.00, 0.0)),
+)
+
+
+def jet_lut():
+    """`matplotlib.colormaps["jet"](np.arange(256), bytes=True)[:, :3]` as a (256, 3) uint8 array: the lookup table
+    matplotlib builds from the segment data (colors.py `_create_lookup_table`, N = 256, gamma 1), then (lut * 255)
+    truncated to bytes."""
+    N = 256
+    lut = np.empty((N, 3), np.float64)
+    xind = (N - 1) * np.linspace(0, 1, N)
+    for ch, seg in enumerate(_JET_SEGMENTS):
+        x, y = np.array(seg, np.float64).T
+        x = x * (N - 1)
+        ind = np.searchsorted(x, xind)[1:-1]
+        distance = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+        lut[:, ch] = np.concatenate([[y[0]], distance * (y[ind] - y[ind - 1]) + y[ind - 1], [y[-1]]])
+    return (np.clip(lut, 0.0, 1.0) * 255).astype(np.uint8)
+
+
+def _heat_levels(outputs, input_shape, fn):
+    """The checks of the three raw detection maps that need no device; returns (levels as fp32 tensors, B, (H, W))."""
+    try:
+        H, W = (int(v) for v in input_shape)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{fn}: input_shape is a (height, width) pair, got {input_shape!r}") from None
+    if H <= 0 or W <= 0 or H % 32 or W % 32:
+        raise RuntimeError(f"{fn}: input_shape must be positive multiples of 32, got {(H, W)}")
+    if not isinstance(outputs, (list, tuple)) or len(outputs) != 3 or not all(torch.is_tensor(t) and t.dim() == 4 for t in outputs):
+        raise RuntimeError(f"{fn}: outputs must be the three detection maps (B, 5 + nc, h, w) of strides 8, 16 and 32")
+    B, C = outputs[0].shape[:2]
+    if C < 6:
+        raise RuntimeError(f"{fn}: outputs have {C} channels; 4 box values, the objectness and at least one class are needed")
+    for t, s in zip(outputs, (8, 16, 32)):
+        if tuple(t.shape) != (B, C, H // s, W // s):
+            raise RuntimeError(f"{fn}: the outputs of stride {s} must have shape {(B, C, H // s, W // s)} for input_shape "
+                               f"{(H, W)}, got {tuple(t.shape)}")
+        if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise RuntimeError(f"{fn}: expected float32 (or half precision) outputs, got dtype {t.dtype}")
+    if B == 0:
+        raise RuntimeError(f"{fn}: outputs of an empty batch")
+    return B, (H, W)
+
+
+def _heat_common(alpha, cmap, fn):
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise RuntimeError(f"{fn}: alpha must lie in [0, 1], got {alpha!r}")
+    if cmap is None:
+        return jet_lut()
+    shape, dtype = tuple(cmap.shape), (cmap.dtype if torch.is_tensor(cmap) else np.asarray(cmap).dtype)
+    if shape != (256, 3) or dtype not in (torch.uint8, np.uint8):
+        raise RuntimeError(f"{fn}: cmap must be a uint8 table of shape (256, 3), got {dtype} {shape}")
+    return cmap if torch.is_tensor(cmap) else np.asarray(cmap)
+
+
+def _heat_device(outputs, fn):
+    if not all(t.is_cuda for t in outputs) or len({t.device for t in outputs}) != 1:
+        raise RuntimeError(f"{fn}: the outputs must be on one GPU device (there is no CPU fallback)")
+    return [t.detach() if (t.is_contiguous() and t.dtype == torch.float32) else t.detach().contiguous().float() for t in outputs]
+
+
+def _heat_window(input_shape, image_shape, letterbox_image):
+    """(window, dx, dy, nw, nh) of the fixed-size call."""
+    if not letterbox_image:
+        return 0, 0, 0, 0, 0
+    from . import decode
+    top, left, nh, nw = decode.seg_window(input_shape, image_shape)
+    if nh <= 0 or nw <= 0:
+        raise RuntimeError(f"heatmap: image {tuple(image_shape)} leaves an empty window in {tuple(input_shape)}")
+    return 1, left, top, nw, nh
+
+
+def heatmap_mask(outputs, image_shape, input_shape, letterbox_image=False):
+    """Steps :336-342 of yolo.py `detect_heatmap` for a batch: outputs = the three raw detection maps (B, 5 + nc, H/8, W/8),
+    (.., H/16, W/16), (.., H/32, W/32) of a network input of input_shape = (H, W), image_shape = (ih, iw) of the original
+    frames.  Returns the (B, ih, iw) uint8 mask on the outputs' device.  letterbox_image=False: the reference's resize of the
+    whole level map; True: through the window of `decode.seg_window` (module docstring).  No host synchronisation."""
+    from . import hip
+    fn = "heatmap"
+    B, (H, W) = _heat_levels(outputs, input_shape, fn)
+    ih, iw = int(image_shape[0]), int(image_shape[1])
+    if ih <= 0 or iw <= 0:
+        raise RuntimeError(f"{fn}: bad image_shape {tuple(image_shape)}")
+    window = _heat_window((H, W), (ih, iw), letterbox_image)
+    levels = _heat_device(outputs, fn)
+    dev = levels[0].device
+    with torch.cuda.device(dev):
+        mask = torch.empty((B, ih, iw), dtype=torch.uint8, device=dev)
+        minmax = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        ws = torch.empty(hip.heatmap_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
+        hip.heatmap(levels, H, W, mask, minmax, ws, *window)
+    return mask
+
+
+def _heat_frames(frames_u8, batched, out, fn):
+    img = _as_u8(frames_u8, "frames", 4, fn) if batched else frames_u8
+    if not torch.is_tensor(img) or img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
+        raise RuntimeError(f"{fn}: expected uint8 frames of shape (B, ih, iw, 3), got "
+                           f"{tuple(img.shape) if torch.is_tensor(img) else type(img).__name__}")
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(img.shape) or not out.is_contiguous():
+            raise RuntimeError(f"{fn}: out must be a contiguous uint8 tensor of shape {tuple(img.shape)}")
+        if _overlap(out, img):
+            raise RuntimeError(f"{fn}: out must not alias the frames")
+    return img
+
+
+def heatmap(frames_u8, outputs, input_shape, letterbox_image=False, alpha=0.5, cmap=None, out=None):
+    """yolo.py:288-351 `detect_heatmap` on the device: frames_u8 (B, ih, iw, 3) uint8 RGB original frames (numpy or tensor; a
+    single (ih, iw, 3) frame counts as B = 1) and outputs as in `heatmap_mask`.  Returns (picture, mask, minmax): picture
+    (B, ih, iw, 3) uint8 = Image.blend(frame, cmap[index(mask)], alpha) with matplotlib's default normalisation per image
+    (module docstring), mask (B, ih, iw) uint8, minmax (B, 2) int32 = each mask's (min, max).  cmap: a (256, 3) uint8 table,
+    default `jet_lut()`.  out: the device tensor to write the picture into; it must not alias the frames.  No host
+    synchronisation."""
+    from . import hip
+    fn = "heatmap"
+    B, (H, W) = _heat_levels(outputs, input_shape, fn)
+    img = _heat_frames(frames_u8, True, out, fn)
+    if img.shape[0] != B:
+        raise RuntimeError(f"{fn}: {img.shape[0]} frames for outputs of {B} images")
+    ih, iw = img.shape[1:3]
+    lut = _heat_common(alpha, cmap, fn)
+    window = _heat_window((H, W), (ih, iw), letterbox_image)
+    levels = _heat_device(outputs, fn)
+    dev = levels[0].device
+    img = img.to(dev, non_blocking=True).contiguous()
+    with torch.cuda.device(dev):
+        picture = torch.empty((B, ih, iw, 3), dtype=torch.uint8, device=dev) if out is None else out
+        mask = torch.empty((B, ih, iw), dtype=torch.uint8, device=dev)
+        minmax = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        ws = torch.empty(hip.heatmap_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
+        hip.heatmap(levels, H, W, mask, minmax, ws, *window, frames=img, cmap=_palette_on(lut, dev), alpha=alpha, out=picture)
+    return picture, mask, minmax
+
+
+def heatmap_ragged(frames_u8, outputs, geom, input_shape, window=True, alpha=0.5, cmap=None, out=None, flag=None):
+    """`heatmap` for a batch of images of their own sizes (vrnet_heatmap_ragged_f32): frames_u8 (B, ihm, iwm, 3) padded uint8
+    DEVICE slots with image b in the top-left corner, geom the (B, hip.GEOM_BYTES) device table of `data.frame_geometry`.
+    window=True maps the pixels of image b through its letterbox window (dx, dy, nw, nh) of the table (the whole input for
+    a table made with letterbox_image=False); window=False is the reference's whole-map resize.  Returns (picture
+    (B, ihm, iwm, 3), mask (B, ihm, iwm), minmax (B, 2)): image b is `[b, :ih_b, :iw_b]`, equal to `heatmap` on that image
+    alone; every pixel outside it is 0 and minmax[b] covers the image's own pixels.  flag: an int32 device word for
+    hip.FLAG_GEOMETRY, or None.  No host synchronisation."""
+    from . import hip
+    fn = "heatmap_ragged"
+    B, (H, W) = _heat_levels(outputs, input_shape, fn)
+    img = _heat_frames(frames_u8, False, out, fn)
+    if img.shape[0] != B:
+        raise RuntimeError(f"{fn}: {img.shape[0]} frame slots for outputs of {B} images")
+    lut = _heat_common(alpha, cmap, fn)
+    levels = _heat_device(outputs, fn)
+    dev = levels[0].device
+    if img.device != dev:
+        raise RuntimeError(f"{fn}: the frames must be on the outputs' device {dev}")
+    ihm, iwm = img.shape[1:3]
+    with torch.cuda.device(dev):
+        picture = torch.empty((B, ihm, iwm, 3), dtype=torch.uint8, device=dev) if out is None else out
+        mask = torch.empty((B, ihm, iwm), dtype=torch.uint8, device=dev)
+        minmax = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        ws = torch.empty(hip.heatmap_ragged_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
+        hip.heatmap_ragged(levels, geom, H, W, mask, minmax, ws, window=1 if window else 0, frames=img.contiguous(),
+                           cmap=_palette_on(lut, dev), alpha=alpha, out=picture, flag=flag)
+    return picture, mask, minmax
 
 
 def seg_render(frames_u8, class_map, palette=None, mix_type=0, alpha=0.7, count=False, out=None, flag=None, device="cuda"):

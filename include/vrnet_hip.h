@@ -885,6 +885,42 @@ int vrnet_seg_targets_ragged_u8(const unsigned char* label, const vrnet_frame_ge
 int vrnet_box_targets_ragged_f32(const int* boxes, const int* counts, const vrnet_frame_geom* geom, int B, int max_gt,
                                  int ihm, int iwm, int H, int W, float* targets, int* counts_out, int* flag, void* stream);
 
+/* ---- detection heat maps (csrc/heatmap.hip) ---------------------------------------------------------------------------
+ * Added within ABI 11: new symbols only, no existing signature, layout or kernel behaviour changed.
+ * vrnet_heatmap_f32, yolo.py:288-351 (detect_heatmap; predict.py's `heatmap` mode) for B images of one size ih x iw:
+ *   p3, p4, p5: the raw detection maps (B, 5 + nc, H/8, W/8), (.., H/16, W/16), (.., H/32, W/32) fp32 NCHW of an H x W input
+ *   (multiples of 32), nc >= 1.  Per level score = sigmoid(max_c cls_c) * sigmoid(obj) in fp32 (:339), resized to ih x iw
+ *   with OpenCV's INTER_LINEAR rule (:340: the taps of vrnet_seg_predict_f32, horizontal blend first), times 255 and
+ *   truncated to a byte (:341); mask (B, ih, iw) u8 = the max over the levels (:342).  minmax (B, 2) int32 = the (min, max)
+ *   of each image's mask, the vmin / vmax of matplotlib's default normalisation (:344).
+ *   window = 0: the reference's resize of the WHOLE level map, whatever letterbox made the input (dx, dy, nw, nh unused).
+ *   window = 1: this project's aligned form: pixel x is mapped through the letterbox window (dx, dy, nw, nh) of the canvas,
+ *     f = ((dx + ((x + 0.5) * nw) / iw) * w_l) / W - 0.5 in fp64, one rounding per operation, then the same floor and clamps,
+ *     the fraction rounded to fp32; likewise in y.  The window must lie inside the canvas.
+ *   out (B, ih, iw, 3) u8 or NULL (the mask only; frames and cmap may then be NULL): Image.blend(frame, cmap[index], alpha) per byte
+ *     in the arithmetic of vrnet_render_u8's mix_type 0, with frames (B, ih, iw, 3) u8, cmap (256, 3) u8 (matplotlib's jet
+ *     as bytes for the reference's picture) and index(m) = trunc(((m - vmin) / (vmax - vmin)) * 256) in fp64, one rounding
+ *     per operation, 256 -> 255, and 0 for every m when vmax == vmin.  The picture has the frame's resolution: matplotlib's
+ *     200-dpi figure with its margins is not reproduced.  out must not overlap frames or mask.  0 <= alpha <= 1.
+ *   workspace: vrnet_heatmap_workspace(B, H, W) bytes (the score planes), 4-byte aligned.
+ *   Three launches (two without out), no memset, integer atomics only (the same bytes on every run), no allocation, no
+ *   host synchronisation, capturable in a graph.
+ * vrnet_heatmap_ragged_f32: the same kernels on padded slots mask (B, ihm, iwm) / frames, out (B, ihm, iwm, 3), with ih, iw
+ *   and the window (dx, dy, nw, nh) of image b from geom[b] (the ragged rules above: clamped on the device, bit 256 of *flag
+ *   for a clamped record, flag may be NULL).  Every pixel of a slot outside its image is written 0; minmax[b] covers the
+ *   image's own pixels and is (255, 0) for an image without pixels.  Image b equals vrnet_heatmap_f32 on that image alone.
+ *   workspace: vrnet_heatmap_ragged_workspace(B, H, W) bytes. */
+long vrnet_heatmap_workspace(int B, int H, int W);
+int vrnet_heatmap_f32(const float* p3, const float* p4, const float* p5, int B, int nc, int H, int W, int ih, int iw,
+                      int window, int dx, int dy, int nw, int nh, const unsigned char* frames, const unsigned char* cmap,
+                      float alpha, unsigned char* mask, unsigned char* out, int* minmax, void* workspace,
+                      long workspace_bytes, void* stream);
+long vrnet_heatmap_ragged_workspace(int B, int H, int W);
+int vrnet_heatmap_ragged_f32(const float* p3, const float* p4, const float* p5, const vrnet_frame_geom* geom, int B, int nc,
+                             int H, int W, int ihm, int iwm, int window, const unsigned char* frames,
+                             const unsigned char* cmap, float alpha, unsigned char* mask, unsigned char* out, int* minmax,
+                             int* flag, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- the record arena of a validation pass (csrc/evalacc.hip) --------------------------------------------------------
  * Added within ABI 11: a new symbol only.
  * vrnet_eval_append_f32, utils/callbacks.py:151-170 (get_map_txt: the rows, scores and coordinates it writes per image)

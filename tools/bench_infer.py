@@ -26,11 +26,17 @@ and mIoU of both.  With --ragged HxW[,HxW...] it compares infer.FramePipeline(ra
 the capacity (the ragged kernels then move the fixed ones' bytes plus the geometry table), with the fixed-size captured
 pipeline at the same shapes on the same frames resident on the device: seven alternating rounds of --steps runs each, frames
 per second from the median round of each, the fixed pipeline's own run-to-run spread beside the ratio, and whether the
-results are equal.
+results are equal.  With --heatmap HxW[,HxW...] it times the detection heat map of the raw detection maps of the forward at each
+original size H x W, on frames resident on the device: render.heatmap_mask, render.heatmap and its aligned form, each captured
+in a hipGraph of its own and replayed --steps times between two device events (device time: no launch gaps of the host), in
+alternating rounds, next to a plain device copy of the same frame bytes measured the same way (the bound of a byte-bound
+pass: the heat map reads 3 and writes 1 + 3 bytes per pixel, the copy reads 3 and writes 3); and the replay of
+infer.FramePipeline with and without heatmap=True (without it: the chain as it was before the option existed).
 
     python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
                                 [--seg 1080x1920,480x640] [--letterbox 1080x1920,480x640] [--render 1080x1920,480x640]
                                 [--pipeline 1080x1920] [--evaluate 1080x1920] [--ragged 1080x1920]
+                                [--heatmap 1080x1920,480x640]
 """
 import argparse
 import os
@@ -55,6 +61,7 @@ def main():
     ap.add_argument("--pipeline", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920)")
     ap.add_argument("--evaluate", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920)")
     ap.add_argument("--ragged", default="", help="comma list of capacities HxW (e.g. 1080x1920)")
+    ap.add_argument("--heatmap", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
     from asy_vrnet_amd.data import device_letterbox, resize_image
@@ -69,6 +76,7 @@ def main():
     pipeline_sizes = [tuple(int(v) for v in p.split("x")) for p in args.pipeline.split(",") if p]
     evaluate_sizes = [tuple(int(v) for v in p.split("x")) for p in args.evaluate.split(",") if p]
     ragged_sizes = [tuple(int(v) for v in p.split("x")) for p in args.ragged.split(",") if p]
+    heat_sizes = [tuple(int(v) for v in p.split("x")) for p in args.heatmap.split(",") if p]
 
     def timed(fn):
         for _ in range(3):
@@ -79,6 +87,33 @@ def main():
             fn()
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / args.steps * 1e3
+
+    def replayed(fn):
+        """fn captured in a graph of its own (after two passes on the capture stream): a function that replays it --steps
+        times and returns the device time per replay in ms, from two events on the stream."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.no_grad(), torch.cuda.stream(side):
+            for _ in range(2):
+                fn()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(graph, stream=side):
+            keep = fn()
+
+        def measure():
+            for _ in range(3):
+                graph.replay()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(args.steps):
+                graph.replay()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / args.steps
+        measure.keep = keep
+        return measure
     dev = torch.device("cuda")
     model = A.EfficientVRNet(4, 9, args.phi, img_size=args.size).to(dev).eval()
     A.randomize_state_dict(model.state_dict(), seed=0)
@@ -244,6 +279,44 @@ def main():
                   f"{ms['pipeline_captured']:.3f} ms ({ms['composition'] / ms['pipeline_captured']:.2f} x the composition, "
                   f"{bs / ms['pipeline_captured'] * 1e3:.1f} frames/s); candidates {pipes[True]._cand[4].tolist()} of capacity "
                   f"{pipes[True].cap}, kept {res.kept.tolist()}, flag {int(res.flag)}; rendered frames equal the composition's: {same}")
+
+        for ih, iw in heat_sizes:
+            import statistics
+            from asy_vrnet_amd.render import heatmap, heatmap_mask
+            with torch.no_grad():
+                det = [d.detach().float().contiguous() for d in model(x, r)[0]]
+            gen = torch.Generator(device=dev).manual_seed(bs)
+            frames = torch.randint(0, 256, (bs, ih, iw, 3), generator=gen, device=dev, dtype=torch.uint8)
+            dst = torch.empty_like(frames)
+            variants = {"copy": replayed(lambda: dst.copy_(frames)),
+                        "mask": replayed(lambda: heatmap_mask(det, (ih, iw), S)),
+                        "heatmap": replayed(lambda: heatmap(frames, det, S, out=dst)),
+                        "aligned": replayed(lambda: heatmap(frames, det, S, letterbox_image=True, out=dst))}
+            rounds = {k: [] for k in variants}
+            for _ in range(5):                       # alternating rounds, so that a drift of the clock hits them alike
+                for k, fn in variants.items():
+                    rounds[k].append(fn())
+            ms = {k: statistics.median(v) for k, v in rounds.items()}
+            mb = bs * ih * iw / 1e6
+            print(f"  + heatmap {ih}x{iw} from {S[0]}x{S[1]}, bs={bs}, device time per captured replay (median of 5 rounds of "
+                  f"{args.steps}): device copy of the frames {ms['copy']:.4f} ms ({6 * mb / ms['copy']:.0f} GB/s read + written); "
+                  f"heatmap_mask {ms['mask']:.4f} ms ({ms['mask'] / ms['copy']:.2f} x the copy, 1 B/pixel written); heatmap "
+                  f"{ms['heatmap']:.4f} ms ({ms['heatmap'] / ms['copy']:.2f} x the copy; {8 * mb / ms['heatmap']:.0f} GB/s of its "
+                  f"1 + 1 + 3 + 3 B/pixel); aligned form {ms['aligned']:.4f} ms; rounds of heatmap min {min(rounds['heatmap']):.4f} "
+                  f"max {max(rounds['heatmap']):.4f} ms")
+            pipes = {h: FramePipeline(model, (ih, iw), S, batch=bs, heatmap=h) for h in (False, True)}
+            rounds = {h: [] for h in pipes}
+            for _ in range(5):
+                for h, pipe in pipes.items():
+                    rounds[h].append(timed(lambda: pipe.run(frames, r)))
+            med = {h: statistics.median(v) for h, v in rounds.items()}
+            a, b = pipes[False].run(frames, r), pipes[True].run(frames, r)
+            same = all(torch.equal(getattr(a, k), getattr(b, k)) for k in ("rows", "kept", "det_counts", "class_map", "seg_counts",
+                                                                           "rendered"))
+            print(f"  + heatmap {ih}x{iw}, bs={bs}: FramePipeline replay without heatmap {med[False]:.3f} ms/batch (rounds "
+                  f"{min(rounds[False]):.3f}..{max(rounds[False]):.3f}), with heatmap=True {med[True]:.3f} ms/batch (rounds "
+                  f"{min(rounds[True]):.3f}..{max(rounds[True]):.3f}): +{med[True] - med[False]:.3f} ms; heat range "
+                  f"{b.heat_range.tolist()}; other fields equal: {same}")
 
         for ih, iw in ragged_sizes:
             import statistics
