@@ -103,7 +103,10 @@ class _YoloLossFn(torch.autograd.Function):
 
 class YOLOLoss(nn.Module):
     """nets/yolo_training.py:60-72.  `log_vars` is kept (it is in the reference's parameter list, :72) although the
-    reference's active code never uses it (:184-194 are commented out there)."""
+    reference's active code never uses it (:184-194 are commented out there).
+    Defined where the reference is not: equal costs go to the lower anchor index and, for an anchor claimed by several
+    boxes, to the lower box index; the boxes of an image without any candidate anchor (the reference's topk raises
+    there) match nothing and contribute nothing (pinned by tests/test_loss_edges.py)."""
 
     def __init__(self, num_classes, fp16=False, strides=(8, 16, 32)):
         super().__init__()
