@@ -1537,16 +1537,18 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
                stride, pad, dil);
   const bool plain = !ypre && !res && !kscale && !aux && !out_nchw && act == 0 && !stats && precision != 1 && !pair_rows &&
                      !colstats;
-  if (plain && tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride)) vr_note_kernel(4);
-  if (plain && tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride))
+  // one check for every path below: a row of a holds the contracted channels, a row of y the produced ones
+  VR_CHECK_ARG(lda >= (mode == 0 ? Cin : Cout) && (out_nchw || ldy >= (mode == 0 ? Cout : Cin)),
+               "conv2d: row stride smaller than channel count");
+  if (plain && tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride)) {
+    vr_note_kernel(4);
     return vr_tiny_conv(mode, a, lda, w, mode == 0 ? bias : nullptr, y, ldy, B, H, W, Cin, Cout, kh, pad, dil, accumulate,
                         vr_stream(stream));
+  }
   // narrow outputs over wide inputs (head predictions, seg logits): direct HBM-streaming kernels (narrowconv.hip)
   if ((vr_tune("VRNET_NARROW", 3) >> mode & 1) && !colstats && !ypre && !res && !kscale && !aux && act == 0 && !stats && !pair_rows && precision != 1 &&
       precision != 3 && vr_narrow_conv_ok(Cin, Cout, kh, kw, stride, pad) && !tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride) && vr_aligned16(w) &&
       (mode == 0 ? (lda % 4 == 0 && vr_aligned16(a)) : (!out_nchw && ldy % 4 == 0 && vr_aligned16(y)))) {
-    VR_CHECK_ARG(lda >= (mode == 0 ? Cin : Cout) && (out_nchw || ldy >= (mode == 0 ? Cout : Cin)),
-                 "conv2d: row stride smaller than channel count");
     vr_note_kernel(5);
     return vr_narrow_conv(mode, a, lda, w, mode == 0 ? bias : nullptr, y, ldy, (long)B * H * W, (long)H * W, Cin, Cout,
                           mode == 0 ? out_nchw : 0, out_ctot, out_coff, accumulate, vr_stream(stream));
@@ -1572,7 +1574,6 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
   VR_CHECK_ARG(M < (1L << 31) && (long)B * p.SH * p.SW < (1L << 31), "conv2d: too many pixels");
   p.M = (int)M;
   p.perm2 = (mode == 1 && stride == 2 && p.MH % 2 == 0 && p.MW % 2 == 0 && (M / 4) % 128 == 0) ? 1 : 0;
-  VR_CHECK_ARG(lda >= p.CK && (out_nchw || ldy >= p.CN), "conv2d: row stride smaller than channel count");
   p.a_vec = (p.CK % 4 == 0) && (lda % 4 == 0) && vr_aligned16(a);
   p.b_vec = (Cin % 4 == 0) && vr_aligned16(w);
   p.e_vec = !out_nchw && (p.CN % 4 == 0) && (ldy % 4 == 0) && vr_aligned16(y) &&
@@ -1940,6 +1941,7 @@ extern "C" int vrnet_conv2d_wgrad_f32(const float* x, long ldx, const float* dy,
   }
   const long M = (long)B * OH * OW;
   VR_CHECK_ARG(M < (1L << 31) && (long)B * H * W < (1L << 31), "conv2d_wgrad: too many pixels");
+  VR_CHECK_ARG(ldx >= Cin && lddy >= Cout, "conv2d_wgrad: row stride smaller than channel count");
   const int streams = dw2 ? 2 : 1;
   VR_CHECK_ARG(streams == 1 || (B % 2 == 0 && (!dbias == !dbias2) && (!row_scale == !row_scale2)),
                "conv2d_wgrad: a two-stream launch needs an even batch and the second set of outputs");
@@ -1963,10 +1965,11 @@ extern "C" int vrnet_conv2d_wgrad_f32(const float* x, long ldx, const float* dy,
   }
   VR_CHECK_ARG(streams == 1 || !tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride),
                "conv2d_wgrad: two-stream launch of a tiny-channel layer");
-  if (tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride)) vr_note_kernel(4);
-  if (tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride))
+  if (tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride)) {
+    vr_note_kernel(4);
     return vr_tiny_wgrad(x, ldx, dy, lddy, dw, dbias, row_scale, B, H, W, Cin, Cout, kh, pad, dil, accumulate, workspace,
                          vr_stream(stream));
+  }
   if (vr_tune("VRNET_NARROW_WGRAD", 1) && streams == 1 && !dls && vr_narrow_wgrad_ok(Cin, Cout, kh, kw, stride, pad) && ldx % 4 == 0 && vr_aligned16(x)) {
     float *nslab, *nbslab;
     int nS;

@@ -199,6 +199,8 @@ int vrnet_wgrad_planes_f32(const void* x, long ldx, long x_plane, const void* dy
 /* Weight (+ bias) gradient of the same convolutions (autograd of nn.Conv2d): dw in OIHW layout
  * [Cout][Cin][kh][kw], dbias[Cout] (NULL = none), both scaled by row_scale[Cout] when given (layer scale).
  * Deterministic split over output pixels into fp32 slabs in `workspace` (size from ..._workspace).
+ * ldx < Cin or lddy < Cout is refused ("conv2d_wgrad: row stride smaller than channel count"), as vrnet_conv2d_f32 refuses
+ * lda / ldy below the contracted / produced channel count ("conv2d: row stride ..."), whichever kernel would serve the shape.
  * precision 1: dy and x rounded to bf16 while staged, v_mfma_f32_32x32x16_bf16 with transposing LDS reads, fp32
  * accumulate / slabs / bias sums (needs 16-byte rows, Cin, Cout multiples of 4 and > 32).
  * Two-stream launch (dw2 != NULL; workspace with pair = 1): samples [0, B/2) contribute to (dw, dbias, row_scale),
