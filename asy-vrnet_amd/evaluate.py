@@ -137,7 +137,8 @@ def validate_add(image_ids, seen, label_maps, gt_boxes, batch, frame_shape, num_
 
 class EvalResult:
     """What `EvalPipeline.compute` returns.  det: the `metrics.DetMapResult` of the detections (device tensors: map, ap, f1,
-    recall, precision, lamr, n_gt, n_det, n_tp); hist (n, n) int64, rows = labels, columns = predictions; iou, pa_recall,
+    recall, precision, lamr, n_gt, n_det, n_tp); coco: the `metrics.CocoMapResult` of the same detections with
+    compute(coco=True), else None; hist (n, n) int64, rows = labels, columns = predictions; iou, pa_recall,
     precision (n,) float64 and accuracy, miou floats: per_class_iu, per_class_PA_Recall, per_class_Precision, per_Accuracy
     and nanmean(iou) of utils_seg/utils_metrics.py:47-60,131 on that matrix (numpy, on the host); flag: the int word of
     the module docstring; images: the number of images evaluated."""
@@ -245,10 +246,12 @@ class EvalPipeline(infer.FramePipeline):
         self.image_ids.extend(ids)
         return result
 
-    def compute(self, min_overlap=0.5, score_threhold=0.5, strict=True):
+    def compute(self, min_overlap=0.5, score_threhold=0.5, strict=True, coco=False):
         """The one read-back of a validation pass (`voc_map` then makes its own range check) -> `EvalResult`.  strict: raise
         if any flag bit is set -- FLAG_CANDIDATES included, since a capped candidate set changes the mAP; strict=False
-        returns the result with the bits in `flag`.  May be called repeatedly: the same bits every time."""
+        returns the result with the bits in `flag`.  coco=True: `coco` of the result is the `metrics.CocoMapResult` of the
+        same arrays (no ground truth is a crowd, annotation ids from 1), at the price of `coco_map`'s own range check.  May
+        be called repeatedly: the same bits every time."""
         from . import metrics
         n, N, dev = self.num_seg_classes, len(self.image_ids), self.device
         with torch.cuda.device(dev), torch.no_grad():
@@ -277,11 +280,13 @@ class EvalPipeline(infer.FramePipeline):
             image = torch.arange(N, device=dev)[:, None]
             dmask = torch.arange(self.max_boxes, device=dev)[None, :] < a["det_count"][perm][:, None]
             gmask = torch.arange(self.max_gt, device=dev)[None, :] < a["gt_n"][perm][:, None]
-            det = metrics.voc_map(image.expand(N, self.max_boxes)[dmask], a["det_label"][perm][dmask], a["det_score"][perm][dmask],
-                                  a["det_box"][perm][dmask], image.expand(N, self.max_gt)[gmask], a["gt_label"][perm][gmask],
-                                  a["gt_box"][perm][gmask], num_classes=len(self.class_names), min_overlap=min_overlap,
+            arrays = (image.expand(N, self.max_boxes)[dmask], a["det_label"][perm][dmask], a["det_score"][perm][dmask],
+                      a["det_box"][perm][dmask], image.expand(N, self.max_gt)[gmask], a["gt_label"][perm][gmask],
+                      a["gt_box"][perm][gmask])
+            det = metrics.voc_map(*arrays, num_classes=len(self.class_names), min_overlap=min_overlap,
                                   score_threhold=score_threhold, device=dev)
-        return EvalResult(det=det, hist=host[:n * n].view(np.int64).reshape(n, n).copy(), iou=iou, pa_recall=pa_recall,
+            coco_res = metrics.coco_map(*arrays, num_classes=len(self.class_names), device=dev) if coco else None
+        return EvalResult(det=det, coco=coco_res, hist=host[:n * n].view(np.int64).reshape(n, n).copy(), iou=iou, pa_recall=pa_recall,
                           precision=precision, accuracy=float(host[n * n + 3 * n]), miou=float(np.nanmean(iou)), flag=flag,
                           images=N)
 

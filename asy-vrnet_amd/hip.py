@@ -161,6 +161,9 @@ _SIGS = {
     "vrnet_confusion_hist": ([P, I, P, I, L, I, P, P], I),
     "vrnet_det_map_workspace_bytes": ([I, I, I], L),
     "vrnet_det_map_f64": ([P, P, P, P, P, P, I, P, P, P, P, I, I, I, P, I, D] + [P] * 15 + [P, L, P], I),
+    "vrnet_coco_map_group_bytes": ([I, I], L),
+    "vrnet_coco_map_workspace_bytes": ([I, L], L),
+    "vrnet_coco_map_f64": ([P, P, P, P, P, I, P, P, P, I, I, L, P, P, P, P, P, I, I, I] + [P] * 9 + [L, P], I),
     "vrnet_mean_square_workspace": ([I, P], L),
     "vrnet_mean_square_f32": ([I, P, P, P, P, L, P], I),
     "vrnet_mean_square_bwd_f32": ([I, P, P, P, P, P], I),
@@ -1151,6 +1154,21 @@ def det_map(det_image, det_label, det_score, det_box, order, det_offsets, gt_box
                                   *[ptr(out[k]) for k in ("match", "ovmax", "tp", "fp", "rec", "prec", "n_gt", "n_img", "n_tp",
                                                           "ap", "f1", "recall", "precision", "lamr", "map")],
                                   ptr(ws), ws.numel(), stream()), "det_map")
+
+
+def coco_map(det_box, order, rank, class_slot, det_offsets, group_start, group_gt, group_ws, lds_bytes, slice_bytes, gt_box,
+             gt_area, gt_crowd, gt_label, gt_perm, num_classes, zero_id_gt, iou_thrs, rec_thrs, out, ws=None):
+    """COCO bbox evaluation (vrnet_coco_map_f64, which documents every array).  out: dict of the output tensors by the
+    header's names."""
+    D, G, NG = rank.numel(), gt_label.numel(), group_ws.numel()
+    if ws is None:
+        ws = _ws.get(_lib.vrnet_coco_map_workspace_bytes(D, int(slice_bytes)), det_offsets.device)
+    _check(_lib.vrnet_coco_map_f64(ptr(det_box), ptr(order), ptr(rank), ptr(class_slot), ptr(det_offsets), D, ptr(group_start),
+                                   ptr(group_gt), ptr(group_ws), NG, int(lds_bytes), int(slice_bytes), ptr(gt_box),
+                                   ptr(gt_area), ptr(gt_crowd), ptr(gt_label), ptr(gt_perm), G, int(num_classes),
+                                   int(zero_id_gt), ptr(iou_thrs), ptr(rec_thrs),
+                                   *[ptr(out[k]) for k in ("dt_match", "dt_code", "n_gt", "precision", "recall", "stats")],
+                                   ptr(ws), ws.numel(), stream()), "coco_map")
 
 
 def mean_square(tensors):

@@ -8,7 +8,11 @@ The detection metric of utils/utils_map.py (`get_map`, :276-798: VOC AP matching
 `voc_map` on flat arrays, `DetectionEvaluator` for an evaluation loop that feeds it image by image in place of the two
 text files per image of utils/callbacks.py:175-248, and `read_map_dir` / `get_map` for directories in the reference's
 format.  Matching, flags, curves and AP are HIP kernels (csrc/detmap.hip); the global sort and the grouping of the ground
-truths by (image, class) are torch ops on the device."""
+truths by (image, class) are torch ops on the device.
+
+The COCO numbers the same callback logs where pycocotools is installed (`get_coco_map`, utils_map.py:894-923, called at
+utils/callbacks.py:224) are `coco_map` on the same flat arrays, `DetectionEvaluator.compute_coco`, and `get_coco_map` for
+directories: COCOeval's bbox evaluation restated in csrc/cocomap.hip, without pycocotools."""
 import glob
 import os
 
@@ -266,6 +270,10 @@ class DetectionEvaluator:
         return voc_map(**self.arrays(), num_classes=len(self.class_names), min_overlap=min_overlap,
                        score_threhold=score_threhold, return_curves=return_curves, device=device)
 
+    def compute_coco(self, device="cuda"):
+        """One upload and one `coco_map` call over everything added since the last reset (annotation ids from 1)."""
+        return coco_map(**self.arrays(), num_classes=len(self.class_names), device=device)
+
 
 def _map_line(line, n_numbers):
     tok = line.split()
@@ -327,3 +335,195 @@ def get_map(MINOVERLAP, draw_plot, score_threhold=0.5, path='./map_out'):
     names = data.pop("class_names")
     data.pop("image_ids")
     return float(voc_map(**data, num_classes=len(names), min_overlap=float(MINOVERLAP), score_threhold=score_threhold).map)
+
+
+# ---- COCO detection metrics (utils/utils_map.py:800-923, COCOeval) ------------------------------------------------------
+
+COCO_IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)      # cocoeval.py Params.setDetParams
+COCO_REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+COCO_MAX_DETS = (1, 10, 100)
+COCO_AREA_RNG = ((0.0, 1e10), (0.0, 1024.0), (1024.0, 9216.0), (9216.0, 1e10))                  # all, small, medium, large
+COCO_LDS_BYTES = 65536        # a group's IoUs and state stay in LDS up to here (CM_LDS in csrc/cocomap.hip)
+_coco_consts = {}
+
+
+class CocoMapResult:
+    """What `coco_map` returns: device tensors, read back only when the caller asks.  K = num_classes; the axes are
+    COCOeval's: T = 10 IoU thresholds, R = 101 recall points, A = 4 area ranges (all, small, medium, large), M = 3 caps on
+    the detections per image (1, 10, 100).
+      stats      (12,) fp64   COCOeval.stats: AP, AP50, AP75, AP small / medium / large, AR at 1 / 10 / 100 detections, AR
+                              small / medium / large; -1 where no class has a ground truth that counts
+      precision  (10, 101, K, 4, 3) fp64;  recall (10, K, 4, 3) fp64: -1 for a class without a counted ground truth
+      n_gt       (K, 4) int32 ground truths that are neither crowd nor outside the area range
+    and, with return_matches=True, in the detections' input order:
+      dt_match   (10, 4, D) int32 the input index of the matched ground truth, -1 for none
+      dt_ignore  (10, 4, D) uint8 the detection is ignored at that threshold and range
+      kept       (D,) uint8       0: cut by the 100 detections per (image, class); such a detection has dt_match -1"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def keys(self):
+        return self.__dict__.keys()
+
+    def __getitem__(self, k):
+        return self.__dict__[k]
+
+
+def coco_map(det_image, det_label, det_score, det_box, gt_image, gt_label, gt_box, gt_difficult=None, num_classes=None,
+             gt_area=None, zero_id_gt=None, return_matches=False, device="cuda"):
+    """COCOeval(cocoGt, cocoDt, 'bbox') with evaluate(), accumulate(), summarize() -- what utils_map.py:894-923
+    `get_coco_map` runs -- on the flat arrays `voc_map` takes (same conventions and checks: numpy arrays or tensors, moved
+    to `device`, which must be a GPU; boxes left, top, right, bottom; D = 0 and G = 0 valid; NaN scores refused).  A box
+    becomes x, y, w, h = l, t, r - l, b - t; gt_difficult is COCO's iscrowd (and ignore); gt_area (G,) defaults to the
+    reference's w * h - 10.0 (utils_map.py:842).  Images are evaluated in index order, so equal scores order by image
+    index and then by input order.  zero_id_gt: the index of the ground truth carrying annotation id 0, which COCOeval
+    cannot tell from "unmatched" (the reference numbers from 0, :865); None: ids from 1, the COCO convention.  The
+    parameters are COCOeval's defaults and fixed.  Returns a `CocoMapResult`.  All arithmetic is fp64 in COCOeval's
+    operand order; the result is bitwise the same on every run.  One read-back (the range check, which also fetches the
+    number of (image, class) groups and the workspace size)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("coco_map: the device must be a GPU (there is no CPU fallback)")
+    d_img, d_lab = _flat(det_image, torch.int64, dev), _flat(det_label, torch.int64, dev)
+    d_score = _flat(det_score, torch.float64, dev) + 0.0
+    d_box = _flat(det_box, torch.float64, dev, 4)
+    g_img, g_lab = _flat(gt_image, torch.int64, dev), _flat(gt_label, torch.int64, dev)
+    g_box = _flat(gt_box, torch.float64, dev, 4)
+    D, G = d_score.numel(), g_img.numel()
+    g_crowd = torch.zeros(G, dtype=torch.uint8, device=dev) if gt_difficult is None else \
+        (_flat(gt_difficult, torch.int64, dev) != 0).to(torch.uint8)
+    g_area = (g_box[:, 2] - g_box[:, 0]) * (g_box[:, 3] - g_box[:, 1]) - 10.0 if gt_area is None else \
+        _flat(gt_area, torch.float64, dev)
+    if not (d_img.numel() == d_lab.numel() == d_box.shape[0] == D and
+            g_lab.numel() == g_box.shape[0] == g_crowd.numel() == g_area.numel() == G):
+        raise RuntimeError("coco_map: the detection arrays (and the ground-truth arrays) must have one length each")
+    if D > MAX_BOXES or G > MAX_BOXES:
+        raise RuntimeError(f"coco_map: {D} detections, {G} ground truths (0..{MAX_BOXES} each supported)")
+    zero_id = -1 if zero_id_gt is None else int(zero_id_gt)
+    if zero_id_gt is not None and not 0 <= zero_id < G:
+        raise RuntimeError(f"coco_map: zero_id_gt = {zero_id} is no index into the {G} ground truths")
+    i64 = dict(dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        img_all, lab_all = torch.cat([d_img, g_img]), torch.cat([d_lab, g_lab])
+        zero = torch.zeros((), **i64)
+        # the (image, class) key: with num_classes=None the multiplier is the largest id + 1, still on the device
+        if num_classes is not None:
+            mult = int(num_classes)
+        else:
+            mult = lab_all.max().clamp(min=0) + 1 if D + G else 1
+        dkey, gkey = d_img * mult + d_lab, g_img * mult + g_lab
+        # slots: grouped by (image, class), score descending inside a group, ties in input order
+        by_score = torch.sort(d_score, descending=True, stable=True).indices
+        order = by_score[torch.sort(dkey[by_score], stable=True).indices]
+        skey = dkey[order]
+        is_start = torch.ones(D, dtype=torch.bool, device=dev)
+        is_start[1:] = skey[1:] != skey[:-1]
+        gid = torch.cumsum(is_start, 0) - 1
+        # at most D groups: the tables have D rows, of which the first n_groups are used
+        grp_cnt = torch.zeros(D, **i64).scatter_add_(0, gid, torch.ones(D, **i64))
+        grp_start = torch.zeros(D + 1, **i64)
+        grp_start[1:] = torch.cumsum(grp_cnt, 0)
+        rank = torch.arange(D, **i64) - grp_start[gid]
+        g_sorted = torch.sort(gkey, stable=True)
+        gt_perm = g_sorted.indices
+        gk = skey[grp_start[:D].clamp(max=max(D - 1, 0))]
+        glo = torch.searchsorted(g_sorted.values, gk)
+        ghi = torch.searchsorted(g_sorted.values, gk, right=True)
+        n_g = ghi - glo
+        need = 8 * grp_cnt.clamp(max=COCO_MAX_DETS[-1]) * n_g + 160 * ((n_g + 31) // 32) + (n_g + 7) // 8 * 8
+        used = grp_cnt > 0
+        big = used & (need > COCO_LDS_BYTES)
+        slice_need = torch.where(big, need, zero)
+        grp_ws = torch.cumsum(slice_need, 0) - slice_need
+        lds_need = torch.where(used & ~big, need, zero)
+        # ranges, in one read-back: [min image, max image, min label, max label, NaN scores, groups, slice bytes, LDS bytes]
+        if D + G:
+            words = [img_all.min(), img_all.max(), lab_all.min(), lab_all.max(), torch.isnan(d_score).sum()]
+            words += [is_start.sum(), slice_need.sum(), lds_need.max()] if D else [zero, zero, zero]
+            lo_i, hi_i, lo_l, hi_l, bad, NG, slice_bytes, lds_bytes = torch.stack(words).tolist()
+        else:
+            lo_i, hi_i, lo_l, hi_l, bad, NG, slice_bytes, lds_bytes = 0, -1, 0, -1, 0, 0, 0, 0
+    if bad:
+        raise RuntimeError("coco_map: NaN scores cannot be ranked")
+    C = max(hi_l + 1, 1) if num_classes is None else int(num_classes)
+    if not 1 <= C <= MAX_MAP_CLASSES:
+        raise RuntimeError(f"coco_map: {C} classes (1..{MAX_MAP_CLASSES} supported)")
+    if lo_i < 0 or lo_l < 0 or hi_l >= C:
+        raise RuntimeError(f"coco_map: image indices must be >= 0 and class ids in [0, {C}) "
+                           f"(got images {lo_i}..{hi_i}, classes {lo_l}..{hi_l})")
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        # class order -> slot: classes ascending, score descending, ties by image index, then by input order -- two stable
+        # sorts of the slot sequence, which already runs by image, then by rank inside a group
+        by_score = torch.sort(d_score[order], descending=True, stable=True).indices
+        class_slot = by_score[torch.sort(d_lab[order][by_score], stable=True).indices]
+        det_off = torch.zeros(C + 1, **i32)
+        det_off[1:] = torch.cumsum(torch.bincount(d_lab, minlength=C), 0)
+        if dev not in _coco_consts:
+            _coco_consts[dev] = (torch.from_numpy(COCO_IOU_THRS).to(dev), torch.from_numpy(COCO_REC_THRS).to(dev))
+        iou_thrs, rec_thrs = _coco_consts[dev]
+        T, R, A, M = len(COCO_IOU_THRS), len(COCO_REC_THRS), len(COCO_AREA_RNG), len(COCO_MAX_DETS)
+        out = {"dt_match": torch.empty((T * A, D), **i32), "dt_code": torch.empty((T * A, D), dtype=torch.uint8, device=dev),
+               "n_gt": torch.empty((C, A), **i32), "precision": torch.empty((T, R, C, A, M), **f64),
+               "recall": torch.empty((T, C, A, M), **f64), "stats": torch.empty(12, **f64)}
+        arg = lambda t, dt=None: (t.to(dt) if dt else t).contiguous() if t.numel() else \
+            torch.empty(t.shape, dtype=dt or t.dtype, device=dev)
+        hip.coco_map(arg(d_box), arg(order, torch.int32), arg(rank, torch.int32), arg(class_slot, torch.int32), det_off,
+                     arg(grp_start[:NG + 1], torch.int32), arg(torch.stack([glo, ghi], 1)[:NG], torch.int32), arg(grp_ws[:NG]),
+                     lds_bytes, slice_bytes, arg(g_box), arg(g_area), arg(g_crowd), arg(g_lab, torch.int32),
+                     arg(gt_perm, torch.int32), C, zero_id, iou_thrs, rec_thrs, out)
+        res = {k: out[k] for k in ("stats", "precision", "recall", "n_gt")}
+        if return_matches:
+            dt_match = torch.empty((T * A, D), **i32)
+            dt_ignore = torch.empty((T * A, D), dtype=torch.uint8, device=dev)
+            kept = torch.empty(D, dtype=torch.uint8, device=dev)
+            dt_match[:, order] = out["dt_match"]
+            dt_ignore[:, order] = (out["dt_code"] == 2).to(torch.uint8)
+            kept[order] = (rank < COCO_MAX_DETS[-1]).to(torch.uint8)
+            res.update(dt_match=dt_match.view(T, A, D), dt_ignore=dt_ignore.view(T, A, D), kept=kept)
+    return CocoMapResult(**res)
+
+
+def get_coco_map(class_names, path):
+    """utils_map.py:894-923 with the reference's signature: COCOeval.stats, the 12 COCO summary numbers, of the directory
+    `path` (format: `read_map_dir`) as a numpy array; utils/callbacks.py:224 logs element 1, the AP at IoU 0.5.  The two
+    directories are parsed on the host as preprocess_gt / preprocess_dr do (:800-892): a line whose class is not in
+    class_names is dropped, a ground-truth line containing `difficult` is a crowd, the area of a ground truth is w * h -
+    10.0.  Images are numbered by sorted file stem (COCOeval sorts the image ids).  The reference numbers its annotations
+    from 0 in os.listdir order of ground-truth/, and COCOeval cannot tell annotation id 0 from "unmatched": the first kept
+    box in that order is handed to `coco_map` as zero_id_gt.  Without any kept detection the result is twelve zeros
+    (:912-914).  A detection file without a ground-truth file raises RuntimeError: pycocotools asserts there ("Results do
+    not correspond to current coco set") and the callback's `except` then falls back to `get_map`.  Only the return value is
+    reproduced: nothing is written (no coco_eval/ directory), nothing is printed."""
+    class_names = list(class_names)
+    gt_path, dr_path = os.path.join(path, "ground-truth"), os.path.join(path, "detection-results")
+    stem = lambda f: os.path.splitext(f)[0]
+    gt_files, dr_files = os.listdir(gt_path), os.listdir(dr_path)
+    index = {s: i for i, s in enumerate(sorted({stem(f) for f in gt_files}))}
+    odd = sorted({stem(f) for f in dr_files} - set(index))
+    if odd:
+        raise RuntimeError(f"get_coco_map: detection-results files without a ground-truth file: {odd[:5]}")
+    lines = lambda f: [l.strip() for l in open(f).read().splitlines() if l.strip()]
+    gts, dets = [], []
+    for f in gt_files:                                               # os.listdir order: the first kept box gets id 0
+        for line in lines(os.path.join(gt_path, f)):
+            diff = "difficult" in line
+            tok = line.split()
+            name, box = " ".join(tok[:-5] if diff else tok[:-4]), [float(v) for v in (tok[-5:-1] if diff else tok[-4:])]
+            if name in class_names:
+                gts.append((index[stem(f)], class_names.index(name), box, diff))
+    for f in dr_files:
+        for line in lines(os.path.join(dr_path, f)):
+            tok = line.split()
+            name, num = " ".join(tok[:-5]), [float(v) for v in tok[-5:]]
+            if name in class_names:
+                dets.append((index[stem(f)], class_names.index(name), num[0], num[1:]))
+    if not dets:
+        return np.zeros(12, dtype=np.float64)
+    res = coco_map(np.array([d[0] for d in dets], dtype=np.int64), np.array([d[1] for d in dets], dtype=np.int64),
+                   np.array([d[2] for d in dets], dtype=np.float64), np.array([d[3] for d in dets], dtype=np.float64).reshape(-1, 4),
+                   np.array([g[0] for g in gts], dtype=np.int64), np.array([g[1] for g in gts], dtype=np.int64),
+                   np.array([g[2] for g in gts], dtype=np.float64).reshape(-1, 4), np.array([g[3] for g in gts], dtype=np.uint8),
+                   num_classes=max(len(class_names), 1), zero_id_gt=0 if gts else None)
+    return res.stats.cpu().numpy()

@@ -726,6 +726,51 @@ int vrnet_det_map_f64(const int* det_image, const int* det_label, const double* 
                       double* ap, double* f1, double* recall, double* precision, double* lamr, double* map,
                       void* workspace, long workspace_bytes, void* stream);
 
+/* ---- COCO detection metrics (csrc/cocomap.hip) -----------------------------------------------------------------
+ * Added within ABI 11: new symbols only, no existing signature or layout changed; hip.py binds every declared symbol at
+ * load time, so a library without them fails the import.
+ * vrnet_coco_map_f64, utils/utils_map.py:894-923 (get_coco_map, called at utils/callbacks.py:224, fed by preprocess_gt /
+ *   preprocess_dr :800-892): COCOeval(cocoGt, cocoDt, 'bbox') evaluate(), accumulate(), summarize() with its default
+ *   parameters -- iou_thrs (10) = np.linspace(.5, .95, 10) and rec_thrs (101) = np.linspace(0, 1, 101) as DEVICE arrays of
+ *   the doubles numpy gives, maxDets 1 / 10 / 100, area ranges [0, 1e10], [0, 1024], [1024, 9216], [9216, 1e10].
+ *   Detections: det_box (D, 4) fp64 = left, top, right, bottom in input order.  order (D): slot -> input index, slots
+ *   grouped by (image, class), inside a group by score descending with ties in input order; rank (D): a slot's position
+ *   inside its group (slots of rank >= 100 are cut); group_start (n_groups + 1): the slots of group k, one group per
+ *   (image, class) pair that has a detection; group_gt (n_groups, 2): the group's range lo, hi in gt_perm; class_slot (D):
+ *   class order -> slot, classes ascending, inside a class score descending with ties by image index, then rank;
+ *   det_offsets (num_classes + 1): the class-order positions of class c.  Ground truths in input order: gt_box (G, 4),
+ *   gt_area (G) fp64, gt_crowd (G) bytes (ignore = iscrowd), gt_label (G); gt_perm (G): input indices grouped by (image,
+ *   class), input order inside a group.  zero_id_gt: the input index of the ground truth that carries annotation id 0 (the
+ *   reference numbers from 0, :865; COCOeval reads dtm == 0 as "unmatched": a detection matched to it consumes it and
+ *   counts as a false positive, or as ignored if the ground truth is ignored or its own area is outside the range), -1:
+ *   ids from 1.
+ *   A box is x, y, w, h = l, t, r - l, b - t (no + 1); IoU: w = min(dx + dw, gx + gw) - max(dx, gx), h likewise, 0 unless
+ *   both > 0, else w h / (dw dh [crowd] or dw dh + gw gh - w h).  Per group, threshold t and range: a ground truth is
+ *   ignored if crowd or area outside the range; detections in slot order, each starting from iou = min(t, 1 - 1e-10) and
+ *   taking, over the non-ignored ground truths in input order and then (only if none was taken) the ignored ones, the last
+ *   one with IoU >= the running best that is not yet matched (a crowd may be matched again); an unmatched detection whose
+ *   area w h is outside the range is ignored.  Per (class, range, maxDet M): the first M slots of every group in class
+ *   order; tp / fp cumulative sums, rc = tp / npig, pr = tp / ((fp + tp) + 2^-52), the envelope from the back, precision[r]
+ *   = pr at the first index with rc >= rec_thrs[r] (0: none), recall = rc[-1] (0: no detections); -1 where npig = 0.
+ *   Outputs: dt_match (40, D) by slot, plane t * 4 + range: the matched ground truth's input index or -1; dt_code (40, D)
+ *   bytes: 0 fp, 1 tp, 2 ignored, 3 cut; n_gt (num_classes, 4) int = npig; precision (10, 101, num_classes, 4, 3), recall
+ *   (10, num_classes, 4, 3), stats (12) in COCOeval.stats order (-1: no entry > -1).  IEEE fp64, one rounding per
+ *   operation; integer atomics only and fixed-order sums: the same bits on every run.  D = 0 and G = 0 are valid.
+ *   A group keeps its IoUs (8 x min(n_det, 100) x n_gt bytes), 40 matched bit sets and a flag byte per ground truth --
+ *   vrnet_coco_map_group_bytes(n_det, n_gt) bytes -- in LDS; lds_bytes (<= 65536) is the largest such figure over the
+ *   groups that stay at or below 65536, and every other group k has group_ws[k] (a multiple of 8) as the offset of its
+ *   slice in slice_bytes bytes of the workspace.
+ *   workspace: vrnet_coco_map_workspace_bytes(D, slice_bytes) bytes.  Limits: D, G <= 2^24, num_classes <= 65535. */
+long vrnet_coco_map_group_bytes(int n_det, int n_gt);
+long vrnet_coco_map_workspace_bytes(int D, long slice_bytes);
+int vrnet_coco_map_f64(const double* det_box, const int* order, const int* rank, const int* class_slot,
+                       const int* det_offsets, int D, const int* group_start, const int* group_gt, const long* group_ws,
+                       int n_groups, int lds_bytes, long slice_bytes, const double* gt_box, const double* gt_area,
+                       const unsigned char* gt_crowd, const int* gt_label, const int* gt_perm, int G, int num_classes,
+                       int zero_id_gt, const double* iou_thrs, const double* rec_thrs, int* dt_match,
+                       unsigned char* dt_code, int* n_gt, double* precision, double* recall, double* stats,
+                       void* workspace, long workspace_bytes, void* stream);
+
 /* ---- input formats -----------------------------------------------------------------------------
  * What YoloDataset.__getitem__ / yolo_dataset_collate (utils/dataloader.py:88-107, 440-457) do to a letterboxed batch,
  * from BYTES: img (B, H, W, 3) u8 RGB -> images (B, 3, H, W) f32 = ((v / 255) - mean) / std evaluated in double and rounded
