@@ -16,13 +16,11 @@
 //               stores -- canvas rows, CHW planes and the label canvas, each coalesced over a wave's consecutive x
 // The accumulator is int32 as Pillow's: the taps of a row are normalised to sum 1 with negative lobes, sum |k| < 1.4 * 2^22
 // for the bicubic kernel at any scale, so |2^21 + sum k * v| < 2^21 + 255 * 1.4 * 2^22 < 1.5e9 < 2^31.
-#include "common.h"
+#include "resample.h"               // bicubic_taps, clip8, normalise_store, lb_ksize: shared with csrc/augment.hip
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int LB_PRECISION_BITS = 32 - 8 - 2;      // Resample.c PRECISION_BITS
 
 struct LetterboxArgs {
   const unsigned char* img;          // (B, ih, iw, 3)
@@ -37,41 +35,6 @@ struct LetterboxArgs {
   unsigned char* label_out;          // (B, H, W) or null
 };
 
-// Resample.c bicubic_filter, a = -0.5
-__device__ __forceinline__ double bicubic(double x) {
-  const double a = -0.5;
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-  return 0.0;
-}
-
-// Resample.c precompute_coeffs + normalize_coeffs_8bpc for output index xx of an axis resized in -> out
-__device__ void bicubic_taps(int xx, int in, int out, int cap, int* bounds, int* k) {
-  const double scale = (double)in / out;
-  const double fs = scale < 1.0 ? 1.0 : scale;
-  const double support = 2.0 * fs, ss = 1.0 / fs;
-  const double center = (xx + 0.5) * scale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in) xmax = in;
-  int n = xmax - xmin;
-  // keeps the stores inside the table.  Never taken from vrnet_letterbox_u8, whose cap is this axis's own ksize >= n; the
-  // ragged caller's cap is the pipeline's max_taps, which a wrong table can exceed: the taps are then truncated and the
-  // tables kernel reports FLAG_GEOMETRY
-  if (n > cap) n = cap;
-  double ww = 0.0;
-  for (int x = 0; x < n; ++x) ww += bicubic((x + xmin - center + 0.5) * ss);
-  for (int x = 0; x < n; ++x) {
-    double w = bicubic((x + xmin - center + 0.5) * ss);
-    if (ww != 0.0) w /= ww;
-    k[(long)x * out + xx] = w < 0 ? (int)(-0.5 + w * (1 << LB_PRECISION_BITS)) : (int)(0.5 + w * (1 << LB_PRECISION_BITS));
-  }
-  bounds[2 * xx] = xmin;
-  bounds[2 * xx + 1] = n;
-}
-
 __global__ __launch_bounds__(256) void letterbox_tables_kernel(const LetterboxArgs p) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   const bool pixels = p.canvas || p.images;
@@ -82,24 +45,6 @@ __global__ __launch_bounds__(256) void letterbox_tables_kernel(const LetterboxAr
   } else if (p.label_out) {
     if (e == p.nw + p.nh) vr_nearest_indices(p.iw, p.nw, p.xi);
     if (e == p.nw + p.nh + 1) vr_nearest_indices(p.ih, p.nh, p.yi);
-  }
-}
-
-__device__ __forceinline__ unsigned char clip8(int acc) {
-  acc >>= LB_PRECISION_BITS;
-  return (unsigned char)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
-}
-
-// batch_formats_kernel's arithmetic: ((v / 255) - mean) / std in double, rounded once; pixel r of image b's CHW planes
-__device__ __forceinline__ void normalise_store(float* images, long b, long HW, long r, const unsigned char* v) {
-  const double mean[3] = {0.485, 0.456, 0.406}, sd[3] = {0.229, 0.224, 0.225};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double d = (double)v[c];
-    d /= 255.0;
-    d -= mean[c];
-    d /= sd[c];
-    images[(b * 3 + c) * HW + r] = (float)d;
   }
 }
 
@@ -175,18 +120,9 @@ __global__ __launch_bounds__(256) void letterbox_vertical_paste_kernel(const Let
   }
 }
 
-// Resample.c precompute_coeffs: ksize, the tap capacity of one output index
-__host__ __device__ int lb_ksize(int in, int out) {
-  double fs = (double)in / out;
-  if (fs < 1.0) fs = 1.0;
-  return (int)ceil(2.0 * fs) * 2 + 1;
-}
-
 long lb_table_ints(int ih, int iw, int nh, int nw) {
   return (long)nw * (2 + lb_ksize(iw, nw) + 1) + (long)nh * (2 + lb_ksize(ih, nh) + 1);
 }
-
-long lb_align(long n) { return (n + 255) / 256 * 256; }
 
 // ---- the ragged form: frames of their own sizes in the corners of (ihm, iwm) slots, the geometry of image b in tab[b].
 // The same arithmetic (bicubic_taps, nearest_indices, clip8, normalise_store); the tables of image b live in slot b of the
@@ -208,8 +144,6 @@ struct RaggedLetterboxArgs {
 struct RaggedTables {
   int *hb, *hk, *vb, *vk, *xi, *yi;
 };
-
-__host__ __device__ inline long lb_ragged_slot_ints(int H, int W, int cap) { return ((long)W + H) * (3 + cap); }
 
 __device__ __forceinline__ RaggedTables ragged_tables(const RaggedLetterboxArgs& p, int b) {
   RaggedTables s;

@@ -1,7 +1,8 @@
 """Input formats of the training pipeline, restated from the reference's dataloader (utils/dataloader.py is
-not importable here: cv2 / albumentations).  Only the deterministic evaluation path (`random=False`) and the format
-conversions are covered; the random augmentations (mosaic, mixup, HSV jitter, :217-437) are a training-recipe concern
-outside the hot path.  Host side (numpy / PIL): parsing, box mapping, and the PIL letterbox (`letterbox_sample`,
+not importable here: cv2 / albumentations).  The deterministic evaluation path (`random=False`) and the format
+conversions came first; the random resize / placement / flip / HSV jitter of :187-247 followed (`augment_params`,
+`augment_sample`, `device_augment_batch_ragged`; csrc/augment.hip); mosaic and mixup (:251-437) stay out.
+Host side (numpy / PIL): parsing, box mapping, and the PIL letterbox (`letterbox_sample`,
 `resize_image`) kept as the restated reference.  Device side: `device_letterbox` (csrc/letterbox.hip) -- the letterbox
 itself from RAW frame bytes, Pillow's bicubic / nearest resize reproduced bit for bit, with the paste, the padding and
 the normalisation in the same call -- and `device_batch` (csrc/formats.hip): the per-pixel conversions of a letterboxed
@@ -430,6 +431,303 @@ def device_train_batch_ragged(frames, sizes, input_shape, labels, boxes, num_cla
         targets, counts_out = hip.box_targets_ragged(packed.to(dev, non_blocking=True), counts.to(dev, non_blocking=True), geom,
                                                      (ihm, iwm), H, W, flag=flag)
     return images, png, onehot, targets, counts_out
+
+
+# ---- the random training augmentation (utils/dataloader.py:187-247, utils_seg/dataloader.py:79-111), host side ----------
+# The host functions below are the truth the kernels of csrc/augment.hip are held to, as `letterbox_sample`, `adjust_boxes`
+# and `seg_targets` are for the frame path.  The reference's joint loader returns before its augmentation (:182) and never
+# moves the radar map; here one record per image drives the frame, the label map, the boxes and the radar map alike.
+# vrnet_aug_rec of include/vrnet_hip.h, one record per image (816 bytes)
+AUG_DTYPE = np.dtype([(n, "<i4") for n in ("ih", "iw", "nw", "nh", "dx", "dy", "flip", "color", "lb_nw", "lb_nh", "lb_dx",
+                                           "lb_dy")] + [("lut", "u1", (3, 256))])
+
+
+def default_aug_max_taps(capacity, input_shape, jitter=.3, scale=(.25, 2)):
+    """The tap capacity an augmented pipeline reserves per table entry.  The sampler fixes one axis of the window first --
+    nw = int(s W) when new_ar >= 1, nh = int(s H) otherwise, s >= scale[0] -- so that axis has in / out <= R0 =
+    max(iwm / int(scale[0] W), ihm / int(scale[0] H)) for a frame inside the capacity.  The other axis follows through
+    new_ar = iw / ih * u / v with u, v in [1 - jitter, 1 + jitter]: its in / out is the first axis's times v / u or u / v, at
+    most J = (1 + jitter) / (1 - jitter), times (1 + f / out) with 0 <= f < 1 the part int() cut off.  With R = max(R0 J, 1) the
+    support 2 in / out then exceeds 2 R by less than 2 R / out <= 1 once out >= 2 R, so ceil() grows by at most one and ksize
+    by at most two, as in `default_max_taps`: 2 * ceil(2 R) + 3 serves every window of at least 2 R pixels on both axes.
+    Only thinner slivers can need more, and `augment_params` rejects those by name."""
+    (ihm, iwm), (H, W) = capacity, input_shape
+    lo = max(int(scale[0] * W), 1), max(int(scale[0] * H), 1)
+    R = max(max(iwm / lo[0], ihm / lo[1]) * (1 + jitter) / (1 - jitter), 1.0)
+    return int(np.ceil(2.0 * R)) * 2 + 3
+
+
+def aug_luts(r):
+    """The three 256-byte tables of the colour stage from the gains r = (hue, sat, val) (dataloader.py:226-229)."""
+    r = np.asarray(r, np.float64)
+    x = np.arange(0, 256, dtype=r.dtype)
+    return np.stack([((x * r[0]) % 180).astype(np.uint8), np.clip(x * r[1], 0, 255).astype(np.uint8),
+                     np.clip(x * r[2], 0, 255).astype(np.uint8)])
+
+
+def aug_record(size, input_shape, nw, nh, dx, dy, flip=False, color=False, gains=(1.0, 1.0, 1.0)):
+    """One AUG_DTYPE record for an image of size = (ih, iw) written out by hand: the window, the flip, and the tables of
+    `aug_luts(gains)`; the letterbox window of the image is filled in.  Not validated: `check_aug_table` does that."""
+    H, W = (int(v) for v in input_shape)
+    ih, iw = (int(v) for v in size)
+    rec = np.zeros((), AUG_DTYPE)
+    lb = letterbox_geometry(max(iw, 1), max(ih, 1), W, H)
+    for k, v in zip(AUG_DTYPE.names[:12], (ih, iw, nw, nh, dx, dy, int(bool(flip)), int(bool(color))) + lb):
+        rec[k] = v
+    rec["lut"] = aug_luts(gains)
+    return rec
+
+
+def check_aug_table(table, input_shape, capacity=None, max_taps=None, fn="augment_params"):
+    """Raises RuntimeError naming the image index for a record the kernels would have to clamp: a size that is not positive
+    or above capacity = (ihm, iwm), an empty window or one above twice the canvas's larger side, a stale letterbox window,
+    and a resize that needs more taps than max_taps.  Host only.  Returns the table."""
+    H, W = (int(v) for v in input_shape)
+    table = np.asarray(table)
+    if table.dtype != AUG_DTYPE or table.ndim != 1:
+        raise RuntimeError(f"{fn}: the augmentation table is a (B,) array of data.AUG_DTYPE records")
+    for b, t in enumerate(table):
+        ih, iw, nw, nh, dx, dy = (int(t[k]) for k in ("ih", "iw", "nw", "nh", "dx", "dy"))
+        if ih <= 0 or iw <= 0:
+            raise RuntimeError(f"{fn}: image {b}: bad size {ih} x {iw}")
+        if capacity is not None and (ih > capacity[0] or iw > capacity[1]):
+            raise RuntimeError(f"{fn}: image {b}: {ih} x {iw} is above the capacity {capacity[0]} x {capacity[1]}")
+        if nw <= 0 or nh <= 0:
+            raise RuntimeError(f"{fn}: image {b}: the draw leaves an empty window ({nh} x {nw}) for {ih} x {iw} in a {H} x {W} input")
+        if max(nw, nh) > 2 * max(W, H) or not (-nw <= dx <= W and -nh <= dy <= H):
+            raise RuntimeError(f"{fn}: image {b}: the window {nh} x {nw} at ({dy}, {dx}) is out of range for a {H} x {W} input "
+                               f"(at most {2 * max(W, H)} pixels, touching the canvas)")
+        if tuple(int(t[k]) for k in ("lb_nw", "lb_nh", "lb_dx", "lb_dy")) != letterbox_geometry(iw, ih, W, H) or \
+                min(int(t["lb_nw"]), int(t["lb_nh"])) <= 0:
+            raise RuntimeError(f"{fn}: image {b}: the record's letterbox window is not that of {ih} x {iw} in a {H} x {W} input")
+        need = max(resample_ksize(iw, nw) if nw != iw else 0, resample_ksize(ih, nh) if nh != ih else 0)
+        if max_taps is not None and need > max_taps:
+            raise RuntimeError(f"{fn}: image {b}: resizing {ih} x {iw} to {nh} x {nw} takes {need} taps, above the tap capacity "
+                               f"{max_taps} (a sliver: raise max_taps)")
+    return table
+
+
+def augment_params(sizes, input_shape, rng, jitter=.3, hue=.1, sat=.7, val=.4, scale=(.25, 2), flip=.5, color=True,
+                   capacity=None, max_taps=None, fn="augment_params"):
+    """The random draw of the training augmentation, one AUG_DTYPE record per image (`augment_bytes` of the table is what
+    the device takes): sizes (B, 2) = (ih, iw) per image, rng a numpy.random.RandomState or a seed.  Per image, in the order
+    of utils/dataloader.py:187-217: two rand() for new_ar = iw / ih * rand(1 - jitter, 1 + jitter) / rand(1 - jitter, 1 + jitter),
+    one for scale, then nh = int(scale * h), nw = int(nh * new_ar) when new_ar < 1, else nw = int(scale * w), nh =
+    int(nw / new_ar); one rand() each for dx = int(rand(0, w - nw)) and dy (negative when the window is larger than the
+    canvas; int() truncates toward zero); one for the flip (rand() < flip); uniform(-1, 1, 3) * [hue, sat, val] + 1 for the
+    gains, from which `aug_luts` builds the three tables (drawn with color=False too, so the stream does not depend on it).
+    The record also carries the image's letterbox window, which the stored radar map is aligned with.  Host only.  Raises
+    RuntimeError naming the image index (`check_aug_table`) for an empty window, a size above capacity = (ihm, iwm) and a
+    resize that needs more taps than max_taps (see `default_aug_max_taps`)."""
+    arr = frame_sizes(sizes, fn=fn)
+    H, W = (int(v) for v in input_shape)
+    rs = rng if isinstance(rng, np.random.RandomState) else np.random.RandomState(rng)
+
+    def rand(a=0.0, b=1.0):
+        return rs.rand() * (b - a) + a
+    tab = np.zeros(len(arr), AUG_DTYPE)
+    for b, (ih, iw) in enumerate(arr.tolist()):            # what no draw can mend is raised before the generator moves
+        if ih <= 0 or iw <= 0:
+            raise RuntimeError(f"{fn}: image {b}: bad size {ih} x {iw}")
+        if capacity is not None and (ih > capacity[0] or iw > capacity[1]):
+            raise RuntimeError(f"{fn}: image {b}: {ih} x {iw} is above the capacity {capacity[0]} x {capacity[1]}")
+    for b, (ih, iw) in enumerate(arr.tolist()):
+        new_ar = iw / ih * rand(1 - jitter, 1 + jitter) / rand(1 - jitter, 1 + jitter)
+        sc = rand(scale[0], scale[1])
+        if new_ar < 1:
+            nh = int(sc * H)
+            nw = int(nh * new_ar)
+        else:
+            nw = int(sc * W)
+            nh = int(nw / new_ar)
+        dx = int(rand(0, W - nw))
+        dy = int(rand(0, H - nh))
+        flipped = rand() < flip
+        gains = rs.uniform(-1, 1, 3) * [hue, sat, val] + 1
+        tab[b] = aug_record((ih, iw), (H, W), nw, nh, dx, dy, flipped, color, gains)
+    return check_aug_table(tab, (H, W), capacity, max_taps, fn)
+
+
+def augment_bytes(table):
+    """An AUG_DTYPE table as the (B, hip.AUG_BYTES) uint8 host tensor the device takes; it shares the table's memory."""
+    return torch.from_numpy(table.view(np.uint8).reshape(len(table), -1))
+
+
+def rgb_to_hsv_u8(rgb):
+    """OpenCV's 8-bit COLOR_RGB2HSV restated, integers only: (..., 3) uint8 -> (..., 3) uint8 with h in [0, 180).
+    v = max, d = max - min; s = (d * sdiv[v] + 2048) >> 12 with sdiv[i] = rint((255 << 12) / i); h0 = g - b if v == r, else
+    b - r + 2 d if v == g, else r - g + 4 d; h = (h0 * hdiv[d] + 2048) >> 12 (arithmetic shift) with hdiv[i] =
+    rint((180 << 12) / (6 i)), plus 180 when negative; both tables are 0 at i = 0."""
+    a = np.asarray(rgb).astype(np.int64)
+    r, g, b = a[..., 0], a[..., 1], a[..., 2]
+    i = np.arange(1, 256, dtype=np.float64)
+    sdiv = np.concatenate([[0], np.rint((255 << 12) / i)]).astype(np.int64)
+    hdiv = np.concatenate([[0], np.rint((180 << 12) / (6 * i))]).astype(np.int64)
+    v = np.maximum(np.maximum(r, g), b)
+    d = v - np.minimum(np.minimum(r, g), b)
+    s = (d * sdiv[v] + 2048) >> 12
+    h0 = np.where(v == r, g - b, np.where(v == g, b - r + 2 * d, r - g + 4 * d))
+    h = (h0 * hdiv[d] + 2048) >> 12
+    h = np.where(h < 0, h + 180, h)
+    return np.stack([h, np.minimum(s, 255), v], -1).astype(np.uint8)
+
+
+def hsv_to_rgb_u8(hsv):
+    """OpenCV's COLOR_HSV2RGB for 8-bit input restated in float32, one rounding per operation: s, v times 1 / 255f, h times
+    6f / 180 (minus 6 when a hue byte of 180 or more brings it to 6 or above); sector = floor(h), f = h - sector; tab = {v,
+    v (1 - s), v (1 - s f), v (1 - s (1 - f))}; (b, g, r) = tab[{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}][sector]; s == 0
+    gives v in all three; each channel times 255f, rounded half to even, clipped to a byte."""
+    f32 = np.float32
+    a = np.asarray(hsv)
+    h, s, v = (a[..., k].astype(f32) for k in range(3))
+    s = s * (f32(1) / f32(255))
+    v = v * (f32(1) / f32(255))
+    h = h * (f32(6) / f32(180))
+    h = np.where(h >= f32(6), h - f32(6), h).astype(f32)
+    fl = np.floor(h)
+    sector = fl.astype(np.int64)
+    f = h - fl
+    one = f32(1)
+    tab = np.stack([v, v * (one - s), v * (one - s * f), v * (one - s * (one - f))], -1)
+    assert tab.dtype == np.float32
+    pick = np.array([[1, 3, 0], [1, 0, 2], [3, 0, 1], [0, 2, 1], [0, 1, 3], [2, 1, 0]])[sector]          # (..., 3): b, g, r
+    bgr = np.take_along_axis(tab, pick, -1)
+    bgr = np.where((a[..., 1] == 0)[..., None], v[..., None], bgr).astype(f32)
+    out = np.clip(np.rint(bgr * f32(255)), 0, 255).astype(np.uint8)
+    return out[..., ::-1]
+
+
+def hsv_jitter(canvas_u8, luts):
+    """The colour stage (dataloader.py:221-232) on a (..., 3) uint8 RGB array: `rgb_to_hsv_u8`, the three table lookups
+    (luts (3, 256) uint8: hue, sat, val), `hsv_to_rgb_u8`.  The conversions restate OpenCV's 8-bit paths from its public
+    sources; cv2 is not a dependency of this project and agreement with cv2's own bytes is UNMEASURED.  The round trip alone
+    moves a byte by up to 5 levels on random input, so identity gains are not the identity; `color=False` skips the stage."""
+    luts = np.asarray(luts, np.uint8).reshape(3, 256)
+    hsv = rgb_to_hsv_u8(canvas_u8)
+    return hsv_to_rgb_u8(np.stack([luts[k][hsv[..., k]] for k in range(3)], -1))
+
+
+def augment_boxes(box, iw, ih, w, h, rec):
+    """`adjust_boxes` with the window of the record instead of the letterbox's, and box[:, [0, 2]] = w - box[:, [2, 0]] when
+    the record flips, before the clip (dataloader.py:237-247, minus its in-place shuffle): integer storage, so every
+    mapped coordinate is truncated toward zero.  With the letterbox window and no flip it equals `adjust_boxes`."""
+    nw, nh, dx, dy = (int(rec[k]) for k in ("nw", "nh", "dx", "dy"))
+    out = np.array(box, dtype=np.int64).reshape(-1, 5)
+    if out.shape[0] == 0:
+        return out.astype(np.float64)
+    out[:, [0, 2]] = out[:, [0, 2]] * nw / iw + dx
+    out[:, [1, 3]] = out[:, [1, 3]] * nh / ih + dy
+    if int(rec["flip"]):
+        out[:, [0, 2]] = w - out[:, [2, 0]]
+    out[:, 0:2][out[:, 0:2] < 0] = 0
+    out[:, 2][out[:, 2] > w] = w
+    out[:, 3][out[:, 3] > h] = h
+    keep = ((out[:, 2] - out[:, 0]) > 1) & ((out[:, 3] - out[:, 1]) > 1)
+    return out[keep].astype(np.float64)
+
+
+def augment_radar(radar, input_shape, rec):
+    """The radar map under an augmentation record -- this project's own definition, the reference has none.  radar (4, H, W)
+    belongs to the LETTERBOXED frame (window lb_nw x lb_nh at (lb_dx, lb_dy)).  Canvas pixel (x, y): x' = W - 1 - x when the
+    record flips, else x; wx = x' - dx, wy = y - dy; outside 0 <= wx < nw, 0 <= wy < nh the value is 0; inside it is
+    radar[c, lb_dy + ((2 wy + 1) * lb_nh) // (2 nh), lb_dx + ((2 wx + 1) * lb_nw) // (2 nw)]: the nearest stored pixel under
+    the pixel-centre map, integers only.  Values stored outside the letterbox window are never read.  With the letterbox
+    window and no flip it returns the window's values bit for bit.  Nearest sampling duplicates (enlarging) or drops
+    (shrinking) the sparse radar points; that is a choice, and its effect on accuracy has not been measured."""
+    H, W = (int(v) for v in input_shape)
+    radar = np.asarray(radar)
+    nw, nh, dx, dy, lnw, lnh, ldx, ldy = (int(rec[k]) for k in ("nw", "nh", "dx", "dy", "lb_nw", "lb_nh", "lb_dx", "lb_dy"))
+    x = np.arange(W, dtype=np.int64)
+    wx = (W - 1 - x if int(rec["flip"]) else x) - dx
+    wy = np.arange(H, dtype=np.int64) - dy
+    okx, oky = (wx >= 0) & (wx < nw), (wy >= 0) & (wy < nh)
+    sx = ldx + ((2 * np.where(okx, wx, 0) + 1) * lnw) // (2 * nw)
+    sy = ldy + ((2 * np.where(oky, wy, 0) + 1) * lnh) // (2 * nh)
+    out = radar[:, sy[:, None], sx[None, :]]
+    return np.where((oky[:, None] & okx[None, :])[None], out, np.zeros((), radar.dtype)).astype(radar.dtype)
+
+
+def augment_sample(image, seg_label, box, radar, input_shape, rec):
+    """One dataset item under the augmentation record rec (`augment_params`), on PIL images and numpy arrays; returns
+    (canvas, boxes, label canvas, radar).  Image: resize((nw, nh), BICUBIC) pasted at (dx, dy) on a grey (128) canvas --
+    Pillow crops what falls outside -- then FLIP_LEFT_RIGHT of the whole canvas when the record flips, then `hsv_jitter`
+    when its colour stage is on (the order of dataloader.py:195-232).  Label: resize((nw, nh), NEAREST) pasted on a 0 canvas
+    and flipped with it (utils_seg/dataloader.py:91-111), no colour stage.  Boxes: `augment_boxes`.  Radar: `augment_radar`."""
+    from PIL import Image
+    iw, ih = image.size
+    h, w = input_shape
+    nw, nh, dx, dy = (int(rec[k]) for k in ("nw", "nh", "dx", "dy"))
+    new_image = Image.new("RGB", [w, h], (128, 128, 128))
+    new_image.paste(image.convert("RGB").resize((nw, nh), Image.BICUBIC), (dx, dy))
+    new_label = Image.new("L", [w, h], (0))
+    new_label.paste(Image.fromarray(np.array(seg_label)).resize((nw, nh), Image.NEAREST), (dx, dy))
+    if int(rec["flip"]):
+        new_image = new_image.transpose(Image.FLIP_LEFT_RIGHT)
+        new_label = new_label.transpose(Image.FLIP_LEFT_RIGHT)
+    if int(rec["color"]):
+        new_image = Image.fromarray(hsv_jitter(np.array(new_image, np.uint8), rec["lut"]))
+    return new_image, augment_boxes(box, iw, ih, w, h, rec), new_label, augment_radar(radar, input_shape, rec)
+
+
+def device_augment_batch_ragged(frames, sizes, input_shape, labels, boxes, radar, num_classes_seg, params, max_gt=64,
+                                capacity=None, max_taps=None, flag=None, device="cuda"):
+    """`device_train_batch_ragged` under the training augmentation: the dataset item `augment_sample` builds per image, for a
+    batch of RAW frames of different sizes, ON THE DEVICE -- vrnet_augment_frames_u8 (three launches: the float images),
+    vrnet_augment_seg_targets_u8, vrnet_augment_box_targets_f32 and vrnet_augment_radar_f32.  frames / labels / sizes / boxes /
+    capacity: as `device_train_batch_ragged` takes them; radar (B, 4, H, W) float32, each map aligned with the letterbox window
+    of its frame; params: an AUG_DTYPE table (`augment_params`, or `aug_record`s written by hand), validated here
+    (`check_aug_table`); max_taps: `default_aug_max_taps`.  Returns (images (B,3,H,W) f32, png (B,H,W) int64, onehot
+    (B,H,W,ns+1) f32, targets (B,max_gt,5) f32, counts (B) int32, radar (B,4,H,W) f32), bit for bit what the host functions
+    give per image."""
+    from . import hip
+    fn = "device_augment_batch_ragged"
+    items, own = ragged_items(frames, sizes, None, (3,), "frames", fn)
+    B = len(own)
+    if labels is None:
+        raise RuntimeError(f"{fn}: the label maps are required")
+    labs = ragged_items(labels, own, B, (), "label maps", fn)[0]
+    if len(boxes) != B:
+        raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
+    if capacity is None:
+        capacity = tuple(items.shape[1:3]) if torch.is_tensor(items) else (int(own[:, 0].max()), int(own[:, 1].max()))
+    ihm, iwm = (int(v) for v in capacity)
+    for t in (items, labs):
+        if torch.is_tensor(t) and (t.shape[1] > ihm or t.shape[2] > iwm):
+            raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {(ihm, iwm)}")
+    H, W = (int(v) for v in input_shape)
+    ns = int(num_classes_seg)
+    max_taps = default_aug_max_taps((ihm, iwm), (H, W)) if max_taps is None else int(max_taps)
+    tab = check_aug_params(params, own, (H, W), (ihm, iwm), max_taps, fn)
+    rad = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
+    if tuple(rad.shape) != (B, 4, H, W) or rad.dtype != torch.float32:
+        raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(B, 4, H, W)}, got {rad.dtype} {tuple(rad.shape)}")
+    packed, counts = pack_boxes(boxes, max_gt)
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        aug = augment_bytes(tab).to(dev, non_blocking=True)
+        img = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
+        fill_slots(img, items, own)
+        lab = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
+        fill_slots(lab, labs, own)
+        images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        hip.augment_frames(img, aug, H, W, max_taps, images=images, flag=flag)
+        png, onehot = hip.augment_seg_targets(lab, aug, H, W, ns, flag=flag)
+        targets, counts_out = hip.augment_box_targets(packed.to(dev, non_blocking=True), counts.to(dev, non_blocking=True), aug,
+                                                      (ihm, iwm), H, W, flag=flag)
+        radar_out = hip.augment_radar(rad.to(dev, non_blocking=True).contiguous(), aug, (ihm, iwm), flag=flag)
+    return images, png, onehot, targets, counts_out, radar_out
+
+
+def check_aug_params(params, sizes, input_shape, capacity, max_taps, fn):
+    """An explicit augmentation table against the batch it is for: B records whose (ih, iw) are the frames' own, then
+    `check_aug_table`.  Returns the table as a contiguous array."""
+    tab = np.ascontiguousarray(params)
+    if tab.dtype != AUG_DTYPE or tab.ndim != 1 or len(tab) != len(sizes):
+        raise RuntimeError(f"{fn}: the augmentation table is a ({len(sizes)},) array of data.AUG_DTYPE records")
+    for b, (ih, iw) in enumerate(np.asarray(sizes).tolist()):
+        if (int(tab[b]["ih"]), int(tab[b]["iw"])) != (ih, iw):
+            raise RuntimeError(f"{fn}: image {b}: the record is for {int(tab[b]['ih'])} x {int(tab[b]['iw'])}, the frame is {ih} x {iw}")
+    return check_aug_table(tab, input_shape, capacity, max_taps, fn)
 
 
 class FrameDataset(torch.utils.data.Dataset):

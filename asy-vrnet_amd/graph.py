@@ -179,6 +179,22 @@ class TrainStep(GraphedStep):
     counts in place.  `stats()` then carries "flag": the flag word of those kernels (hip.FLAG_GEOMETRY, hip.FLAG_BOX_COUNT;
     0 for inputs that passed the host validation), read back in the same single read-back; `reset_stats()` clears it.
 
+    With from_frames=True and augment set -- True, or a dict of `data.augment_params`' keywords (jitter, hue, sat, val,
+    scale, flip, color) -- the prologue is the training augmentation instead of the letterbox: the random resize, placement,
+    flip and colour jitter of utils/dataloader.py:187-247, applied by one record per image to the frame, the label map, the
+    boxes AND the radar map (each radar map is aligned with the letterbox window of its frame, as the dataset stores it):
+
+        step = TrainStep(..., from_frames=True, capacity=(ihm, iwm), augment=True, aug_seed=0)
+        res = step(frames, radar, boxes, labels, sizes=None, aug=None)
+
+    Six launches -- vrnet_augment_frames_u8 (tables, horizontal, vertical + paste + flip + colour), vrnet_augment_seg_targets_u8,
+    vrnet_augment_box_targets_f32, vrnet_augment_radar_f32 -- write the float images, the radar input, the labels, the one-hot
+    labels, the packed targets and their counts.  Every call draws its table on the host from the step's own
+    numpy RandomState(aug_seed) (`data.augment_params`; `aug_table` keeps the last one) and copies it into the static device
+    table before the replay, as the geometry table is copied; aug= hands in an explicit `data.AUG_DTYPE` table instead (a
+    caller's own sampler; the step's generator is then not advanced).  The table is validated on the host with the rest,
+    before anything is enqueued.  max_taps defaults to `data.default_aug_max_taps`.  augment without from_frames raises.
+
     Two kinds of graph.  The forward / backward graph(s) are GraphedStep's (three segments under data parallelism, the
     all-reduces between them); the loss closure is `losses.training_loss_packed` on the static buffers, followed by the
     f-score (f_score=True) and the addition of the step's values to a running fp64 sum.  The UPDATE graph is always its own:
@@ -204,8 +220,12 @@ class TrainStep(GraphedStep):
 
     def __init__(self, net, yolo_loss, optimizer, ema, batch, size, num_seg_classes, max_gt=64, cls_weights=None,
                  focal_loss=True, dice_loss=True, f_score=False, from_bytes=False, device="cuda", warmup=2, segments=None,
-                 from_frames=False, capacity=None, max_taps=None, letterbox_image=True):
+                 from_frames=False, capacity=None, max_taps=None, letterbox_image=True, augment=None, aug_seed=None):
         optimizer._uniform("lr")
+        if augment is not None and augment is not False and not from_frames:
+            raise RuntimeError("TrainStep: augment needs from_frames=True (the augmentation starts from the raw frames)")
+        if augment is not None and augment is not False and not letterbox_image:
+            raise RuntimeError("TrainStep: augment places the frame itself; letterbox_image=False does not apply")
         if from_frames and from_bytes:
             raise RuntimeError("TrainStep: from_frames and from_bytes exclude each other (raw frames, or a letterboxed batch)")
         if from_frames and capacity is None:
@@ -217,6 +237,7 @@ class TrainStep(GraphedStep):
         self.batch, self.hw, self.ns, self.max_gt = int(batch), (h, w), ns, int(max_gt)
         self.focal_loss, self.dice_loss, self.f_score, self.from_bytes = bool(focal_loss), bool(dice_loss), bool(f_score), bool(from_bytes)
         self.from_frames = bool(from_frames)
+        self.augment = None if augment is None or augment is False else ({} if augment is True else dict(augment))
         self.names = ("total", "loss_det", "loss_seg") + (("f_score",) if self.f_score else ())
         with torch.cuda.device(dev):
             self.labels = torch.zeros((batch, max(self.max_gt, 1), 5), dtype=torch.float32, device=dev)
@@ -232,22 +253,31 @@ class TrainStep(GraphedStep):
             # running sums, step count; from_frames: the flag word too, so that stats() stays one read-back
             self._acc = torch.zeros(len(self.names) + 1 + int(self.from_frames), dtype=torch.float64, device=dev)
             if self.from_frames:
-                self._frame_buffers(batch, capacity, max_taps, letterbox_image, dev)
+                self._frame_buffers(batch, capacity, max_taps, letterbox_image, dev, aug_seed)
         self._vals = None
         super().__init__(net, self._loss, batch, size, dev, warmup=warmup, segments=segments)
         self._capture_update()
         self.reset_stats()                               # the warm-up passes on zero inputs counted themselves
         torch.cuda.synchronize(dev)
 
-    def _frame_buffers(self, batch, capacity, max_taps, letterbox_image, dev):
+    def _frame_buffers(self, batch, capacity, max_taps, letterbox_image, dev, aug_seed=None):
         """The static inputs of from_frames=True.  The warm-up and the capture run on a table of frames that fill their
-        slots (as FramePipeline's do) and on no boxes."""
+        slots (as FramePipeline's do) and on no boxes; with augment, on the letterbox window of such a frame."""
         (h, w), B = self.hw, batch
         self.capacity = ihm, iwm = tuple(int(v) for v in capacity)
         self.letterbox_image = bool(letterbox_image)
-        self.max_taps = data.default_max_taps(self.capacity, self.hw) if max_taps is None else int(max_taps)
-        table = data.frame_geometry([self.capacity] * B, self.hw, self.letterbox_image, self.capacity, self.max_taps, "TrainStep")
-        self.geom = data.geometry_bytes(table).to(dev)
+        if self.augment is None:
+            self.max_taps = data.default_max_taps(self.capacity, self.hw) if max_taps is None else int(max_taps)
+            table = data.frame_geometry([self.capacity] * B, self.hw, self.letterbox_image, self.capacity, self.max_taps, "TrainStep")
+            self.geom = data.geometry_bytes(table).to(dev)
+        else:
+            kw = {k: self.augment[k] for k in ("jitter", "scale") if k in self.augment}
+            self.max_taps = data.default_aug_max_taps(self.capacity, self.hw, **kw) if max_taps is None else int(max_taps)
+            self._aug_rng = np.random.RandomState(aug_seed)
+            rec = data.aug_record(self.capacity, self.hw, *data.letterbox_geometry(iwm, ihm, w, h))
+            self.aug_table = data.check_aug_table(np.stack([rec] * B), self.hw, self.capacity, self.max_taps, "TrainStep")
+            self.aug = data.augment_bytes(self.aug_table).to(dev)
+            self.radar_in = torch.zeros((B, 4, h, w), dtype=torch.float32, device=dev)
         self.frames_u8 = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
         self.frame_labels_u8 = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
         self.boxes = torch.zeros((B, max(self.max_gt, 1), 5), dtype=torch.int32, device=dev)
@@ -259,6 +289,14 @@ class TrainStep(GraphedStep):
     def _prologue(self):
         if self.from_bytes:
             hip.batch_formats(self.images_u8, self.labels_u8, self.ns, images=self.x, png_out=self.png, onehot=self.onehot)
+        elif self.from_frames and self.augment is not None:
+            h, w = self.hw
+            hip.augment_frames(self.frames_u8, self.aug, h, w, self.max_taps, images=self.x, flag=self.flag, ws=self._lb_ws)
+            hip.augment_seg_targets(self.frame_labels_u8, self.aug, h, w, self.ns, png_out=self.png, onehot=self.onehot,
+                                    flag=self.flag)
+            hip.augment_box_targets(self.boxes, self.box_counts, self.aug, self.capacity, h, w, targets=self.labels,
+                                    counts_out=self.counts, flag=self.flag)
+            hip.augment_radar(self.radar_in, self.aug, self.capacity, out=self.r, flag=self.flag)
         elif self.from_frames:
             h, w = self.hw
             hip.letterbox_ragged(self.frames_u8, None, self.geom, h, w, self.max_taps, images=self.x, flag=self.flag,
@@ -338,33 +376,45 @@ class TrainStep(GraphedStep):
         packed, counts = losses.pack_targets(targets, self.max_gt)        # raises, naming the image, above max_gt
         return images, radar, pngs, seg_labels, packed, counts
 
-    def _validate_frames(self, frames, radar, boxes, labels, sizes):
+    def _validate_frames(self, frames, radar, boxes, labels, sizes, aug=None):
         """The host checks of a from_frames call, which need no device; returns what the copies take, the geometry table
-        among it."""
+        (with augment: the augmentation table, drawn here unless the caller brought one) among it."""
         B, (h, w), fn = self.batch, self.hw, "TrainStep"
         items, own = data.ragged_items(frames, sizes, B, (3,), "frames", fn)
         labs = data.ragged_items(labels, own, B, (), "label maps", fn)[0]
         for t in (items, labs):
             if torch.is_tensor(t) and (t.shape[1] > self.capacity[0] or t.shape[2] > self.capacity[1]):
                 raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {self.capacity}")
-        table = data.frame_geometry(own, self.hw, self.letterbox_image, self.capacity, self.max_taps, fn)
+        if self.augment is None:
+            if aug is not None:
+                raise RuntimeError(f"{fn}: an aug table belongs to a step built with augment")
+            table = data.frame_geometry(own, self.hw, self.letterbox_image, self.capacity, self.max_taps, fn)
+        elif aug is not None:
+            table = data.check_aug_params(aug, own, self.hw, self.capacity, self.max_taps, fn)
+        else:
+            table = None                     # drawn last, below: a call that raises for another reason draws nothing
         radar = self._tensor(radar)
         if tuple(radar.shape) != (B, 4, h, w) or radar.dtype != torch.float32:
             raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(B, 4, h, w)}, got {radar.dtype} {tuple(radar.shape)}")
         if len(boxes) != B:
             raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
         packed, counts = data.pack_boxes(boxes, self.max_gt)              # raises, naming the image
+        if table is None:
+            # a draw that fails its own checks (an empty window, a sliver's taps) has advanced the generator: the next call
+            # draws anew
+            table = data.augment_params(own, self.hw, self._aug_rng, capacity=self.capacity, max_taps=self.max_taps, fn=fn,
+                                        **self.augment)
         return items, labs, own, table, radar, packed, counts
 
-    def __call__(self, images, radar, targets, pngs, seg_labels=None, sizes=None):
-        if self.from_frames:                 # step(frames, radar, boxes, labels, sizes=None)
+    def __call__(self, images, radar, targets, pngs, seg_labels=None, sizes=None, aug=None):
+        if self.from_frames:                 # step(frames, radar, boxes, labels, sizes=None, aug=None)
             if seg_labels is not None and sizes is not None:
                 raise RuntimeError("TrainStep: from_frames=True takes (frames, radar, boxes, labels, sizes)")
             items, labs, own, table, radar, packed, counts = self._validate_frames(
-                images, radar, targets, pngs, seg_labels if sizes is None else sizes)
+                images, radar, targets, pngs, seg_labels if sizes is None else sizes, aug)
         else:
-            if sizes is not None:
-                raise RuntimeError("TrainStep: sizes belong to from_frames=True")
+            if sizes is not None or aug is not None:
+                raise RuntimeError("TrainStep: sizes and aug belong to from_frames=True")
             images, radar, pngs, seg_labels, packed, counts = self._validate(images, radar, targets, pngs, seg_labels)
         opt, ema = self.optimizer, self.ema
         lr = float(opt._uniform("lr"))
@@ -381,7 +431,11 @@ class TrainStep(GraphedStep):
                 data.fill_slots(self.frames_u8, items, own)
                 data.fill_slots(self.frame_labels_u8, labs, own)
                 # fresh pinned staging tensors (`pack_boxes` makes its own), as for the step record below
-                self.geom.copy_(data.geometry_bytes(table).pin_memory(), non_blocking=True)
+                if self.augment is None:
+                    self.geom.copy_(data.geometry_bytes(table).pin_memory(), non_blocking=True)
+                else:
+                    self.aug_table = table
+                    self.aug.copy_(data.augment_bytes(table).pin_memory(), non_blocking=True)
                 self.boxes.copy_(packed, non_blocking=True)
                 self.box_counts.copy_(counts, non_blocking=True)
             elif self.from_bytes:
@@ -392,7 +446,8 @@ class TrainStep(GraphedStep):
                 self.png.copy_(pngs, non_blocking=True)
                 if seg_labels is not None:
                     self.onehot.copy_(seg_labels, non_blocking=True)
-            self.r.copy_(radar, non_blocking=True)
+            # with augment the radar maps go through vrnet_augment_radar_f32, which writes self.r inside graph 0
+            (self.r if self.augment is None else self.radar_in).copy_(radar, non_blocking=True)
             if not self.from_frames:
                 self.labels.copy_(packed, non_blocking=True)
                 self.counts.copy_(counts, non_blocking=True)

@@ -147,6 +147,10 @@ _SIGS = {
     "vrnet_render_ragged_u8": ([P, P, P, I, I, I, P, I, I, F, P, P, I, P, I, P, P, P, P], I),
     "vrnet_seg_targets_ragged_u8": ([P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_box_targets_ragged_f32": ([P, P, P, I, I, I, I, I, I, P, P, P, P], I),
+    "vrnet_augment_frames_u8": ([P, P] + [I] * 6 + [P, P, P, P, L, P], I),
+    "vrnet_augment_seg_targets_u8": ([P, P, I, I, I, I, I, I, P, P, P, P], I),
+    "vrnet_augment_box_targets_f32": ([P, P, P, I, I, I, I, I, I, P, P, P, P], I),
+    "vrnet_augment_radar_f32": ([P, P, I, I, I, I, I, P, P, P], I),
     "vrnet_heatmap_workspace": ([I, I, I], L),
     "vrnet_heatmap_f32": ([P, P, P] + [I] * 11 + [P, P, F, P, P, P, P, L, P], I),
     "vrnet_heatmap_ragged_workspace": ([I, I, I], L),
@@ -1388,3 +1392,87 @@ def heatmap_ragged(levels, geom, H, W, mask, minmax, ws, window=1, frames=None, 
     _check(_lib.vrnet_heatmap_ragged_f32(ptr(levels[0]), ptr(levels[1]), ptr(levels[2]), _geom(geom, B, "heatmap_ragged"), B, nc,
                                          int(H), int(W), ihm, iwm, int(window), ptr(frames), ptr(cmap), float(alpha), ptr(mask),
                                          ptr(out), ptr(minmax), ptr(flag), ptr(ws), ws.numel(), stream()), "heatmap_ragged")
+
+
+# ---- training augmentation (include/vrnet_hip.h "training augmentation"): per-image records from a device table ----------
+AUG_BYTES = 816          # sizeof(vrnet_aug_rec)
+
+
+def _aug(aug, B, fn):
+    """The table: a contiguous uint8 GPU tensor (B, AUG_BYTES), 8-byte aligned (`data.augment_params` packs it)."""
+    if aug is None or aug.dtype != torch.uint8 or tuple(aug.shape) != (B, AUG_BYTES) or not aug.is_contiguous() or \
+            not aug.is_cuda or aug.data_ptr() % 8:
+        raise RuntimeError(f"{fn}: the augmentation table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape ({B}, {AUG_BYTES})")
+    return ptr(aug)
+
+
+def augment_frames(img_u8, aug, H, W, max_taps, canvas=None, images=None, flag=None, ws=None):
+    """Raw frames of their own sizes -> the augmented canvas (vrnet_augment_frames_u8): img_u8 (B,ihm,iwm,3) padded slots, aug
+    the (B, AUG_BYTES) table -> canvas (B,H,W,3) uint8 and / or images (B,3,H,W) f32, what `data.augment_sample` and
+    `device_batch` give per image; max_taps: the tap capacity of a table entry; flag (1) int32 or None; ws:
+    letterbox_ragged_workspace_bytes(B, ihm, iwm, H, W, max_taps) bytes."""
+    if img_u8 is None or img_u8.dim() != 4:
+        raise RuntimeError("augment_frames: expected frames (B, ihm, iwm, 3)")
+    B, ihm, iwm = img_u8.shape[:3]
+    H, W = int(H), int(W)
+    _tensors("augment_frames", ((img_u8, (B, ihm, iwm, 3), torch.uint8), (canvas, (B, H, W, 3), torch.uint8),
+                                (images, (B, 3, H, W), torch.float32), (flag, (1,), torch.int32)))
+    need = _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, int(max_taps))
+    if ws is None:
+        ws = _ws.get(need, img_u8.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"augment_frames: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    _check(_lib.vrnet_augment_frames_u8(ptr(img_u8), _aug(aug, B, "augment_frames"), B, ihm, iwm, H, W, int(max_taps), ptr(canvas),
+                                        ptr(images), ptr(flag), ptr(ws), ws.numel(), stream()), "augment_frames")
+
+
+def augment_seg_targets(label_u8, aug, H, W, num_classes_seg, png_out=None, onehot=None, flag=None):
+    """`seg_targets_ragged` under the augmentation records (vrnet_augment_seg_targets_u8): label_u8 (B,ihm,iwm) padded slots
+    -> png_out (B,H,W) int64 and onehot (B,H,W,ns+1) f32 of the augmented label canvas.  Returns (png_out, onehot)."""
+    if label_u8 is None or label_u8.dim() != 3:
+        raise RuntimeError("augment_seg_targets: expected label maps (B, ihm, iwm)")
+    B, ihm, iwm = label_u8.shape
+    H, W, ns = int(H), int(W), int(num_classes_seg)
+    if png_out is None:
+        png_out = torch.empty((B, H, W), dtype=torch.int64, device=label_u8.device)
+    if onehot is None:
+        onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=label_u8.device)
+    _tensors("augment_seg_targets", ((label_u8, (B, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
+                                     (onehot, (B, H, W, ns + 1), torch.float32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_augment_seg_targets_u8(ptr(label_u8), _aug(aug, B, "augment_seg_targets"), B, ihm, iwm, H, W, ns,
+                                             ptr(png_out), ptr(onehot), ptr(flag), stream()), "augment_seg_targets")
+    return png_out, onehot
+
+
+def augment_box_targets(boxes, counts, aug, capacity, H, W, targets=None, counts_out=None, flag=None):
+    """`box_targets_ragged` under the augmentation records (vrnet_augment_box_targets_f32): what `data.augment_boxes` and
+    `data.boxes_xyxy_to_cxcywh` give per image.  Returns (targets, counts_out)."""
+    if boxes is None or boxes.dim() != 3:
+        raise RuntimeError("augment_box_targets: expected boxes (B, max_gt, 5)")
+    B, max_gt = boxes.shape[:2]
+    if targets is None:
+        targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
+    if counts_out is None:
+        counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
+    _tensors("augment_box_targets", ((boxes, (B, max_gt, 5), torch.int32), (counts, (B,), torch.int32),
+                                     (targets, (B, max_gt, 5), torch.float32), (counts_out, (B,), torch.int32),
+                                     (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_augment_box_targets_f32(ptr(boxes), ptr(counts), _aug(aug, B, "augment_box_targets"), B, max_gt,
+                                              int(capacity[0]), int(capacity[1]), int(H), int(W), ptr(targets), ptr(counts_out),
+                                              ptr(flag), stream()), "augment_box_targets")
+    return targets, counts_out
+
+
+def augment_radar(radar, aug, capacity, out=None, flag=None):
+    """The radar maps under the augmentation records (vrnet_augment_radar_f32): radar (B,4,H,W) f32, aligned with the
+    letterbox window of its frame -> out (B,4,H,W) f32, the integer gather of `data.augment_radar`; out is not radar;
+    capacity = (ihm, iwm) of the frames' slots, by which the records are judged."""
+    if radar is None or radar.dim() != 4 or radar.shape[1] != 4:
+        raise RuntimeError("augment_radar: expected radar maps (B, 4, H, W)")
+    B, _, H, W = radar.shape
+    if out is None:
+        out = torch.empty((B, 4, H, W), dtype=torch.float32, device=radar.device)
+    _tensors("augment_radar", ((radar, (B, 4, H, W), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_augment_radar_f32(ptr(radar), _aug(aug, B, "augment_radar"), B, int(capacity[0]), int(capacity[1]), H, W,
+                                        ptr(out), ptr(flag), stream()), "augment_radar")
+    return out

@@ -1023,6 +1023,51 @@ int vrnet_mean_square_f32(int k, const void* const* t, const long* n, float* los
                           void* stream);
 int vrnet_mean_square_bwd_f32(int k, const void* const* t, const long* n, const float* g, void* const* grad, void* stream);
 
+/* ---- training augmentation on the device (csrc/augment.hip) -------------------------------------------------------------
+ * Added within ABI 11: new symbols and one new record layout (vrnet_aug_rec) only, no existing signature, layout or kernel
+ * behaviour changed; hip.py binds every declared symbol at import.
+ * The random resize, placement, left-right flip and HSV jitter of utils/dataloader.py:187-247, applied consistently to the
+ * frame, the label map (as utils_seg/dataloader.py:91-111), the boxes and the radar map of an image.  Nothing here draws a
+ * random number: the host draws one record per image (data.augment_params) and the kernels apply it; they equal the host
+ * functions data.augment_sample / augment_boxes / hsv_jitter bit for bit.  All four entry points follow the ragged rules
+ * above: padded (B, ihm, iwm) slots, image index on grid y, the record of image b read and clamped on the device -- 0 <= ih
+ * <= ihm, 0 <= iw <= iwm, 0 <= nw, nh <= 2 max(W, H), -nw <= dx <= W, -nh <= dy <= H, the letterbox window inside the canvas --
+ * and bit 256 of *flag (VR_FLAG_GEOMETRY; flag may be NULL) set when something had to be clamped, when a size or window is
+ * not positive, or when a resize needs more taps than max_taps.  An image whose record had to be clamped gets padding in
+ * every output (grey canvas without the colour stage, label 0, no boxes, radar 0); the other images are unaffected.  No host
+ * synchronisation; capturable.
+ * The window (nw x nh pasted at (dx, dy)) may be larger than the canvas and start at negative offsets; what falls outside
+ * is cropped, as Pillow's paste does.  flip mirrors the finished canvas (labels, boxes and radar alike).
+ * vrnet_augment_frames_u8: img (B, ihm, iwm, 3) -> canvas (B, H, W, 3) uint8 and / or images (B, 3, H, W) fp32 normalised as
+ *   vrnet_batch_formats_u8 does: Pillow's BICUBIC bytes (a pass whose size does not change is skipped), grey (128) padding,
+ *   the flip, then -- color != 0 -- RGB -> HSV in OpenCV's 8-bit integer arithmetic, lut[0..2] on H, S, V, and HSV -> RGB in
+ *   float32, over the whole canvas.  Three launches.  workspace: vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W,
+ *   max_taps) bytes (tables and the horizontal result are indexed by visible column / row).
+ * vrnet_augment_seg_targets_u8: label (B, ihm, iwm) -> png_out (B, H, W) int64 and onehot (B, H, W, ns + 1) fp32 as
+ *   vrnet_seg_targets_ragged_u8 writes them: Pillow's NEAREST pick inside the window, 0 outside.
+ * vrnet_augment_box_targets_f32: vrnet_box_targets_ragged_f32's arithmetic with the record's window, and x1, x2 = W - x2,
+ *   W - x1 before the clip when flip is set; the same compaction, count clamp and VR_FLAG_BOX_COUNT.
+ * vrnet_augment_radar_f32: radar (B, 4, H, W), aligned with the letterbox window (lb_*) of its frame -> out (B, 4, H, W): for
+ *   canvas pixel (x, y), x' = flip ? W - 1 - x : x, wx = x' - dx, wy = y - dy; 0 outside 0 <= wx < nw, 0 <= wy < nh, else
+ *   radar[c][lb_dy + ((2 wy + 1) lb_nh) / (2 nh)][lb_dx + ((2 wx + 1) lb_nw) / (2 nw)] (integer division).  out != radar; ihm,
+ *   iwm only judge the record as the other three entry points do. */
+typedef struct vrnet_aug_rec {
+  int ih, iw;                        /* the image's own size inside its (ihm, iwm) slot */
+  int nw, nh, dx, dy;                /* the resized frame and where it is pasted; may leave the canvas on every side */
+  int flip, color;                   /* != 0: mirror the canvas left-right; run the colour stage */
+  int lb_nw, lb_nh, lb_dx, lb_dy;    /* data.letterbox_geometry: the window the stored radar map is aligned with */
+  unsigned char lut[3][256];         /* hue, saturation, value tables of the colour stage */
+} vrnet_aug_rec;                     /* 816 bytes; the table must be 8-byte aligned */
+int vrnet_augment_frames_u8(const unsigned char* img, const vrnet_aug_rec* aug, int B, int ihm, int iwm, int H, int W,
+                            int max_taps, unsigned char* canvas, float* images, int* flag, void* workspace,
+                            long workspace_bytes, void* stream);
+int vrnet_augment_seg_targets_u8(const unsigned char* label, const vrnet_aug_rec* aug, int B, int ihm, int iwm, int H, int W,
+                                 int num_classes_seg, long long* png_out, float* onehot, int* flag, void* stream);
+int vrnet_augment_box_targets_f32(const int* boxes, const int* counts, const vrnet_aug_rec* aug, int B, int max_gt, int ihm,
+                                  int iwm, int H, int W, float* targets, int* counts_out, int* flag, void* stream);
+int vrnet_augment_radar_f32(const float* radar, const vrnet_aug_rec* aug, int B, int ihm, int iwm, int H, int W, float* out,
+                            int* flag, void* stream);
+
 
 #ifdef __cplusplus
 }
