@@ -1835,6 +1835,32 @@ static void wgrad_plan(long M, int Cin, int Cout, int T, int* cfg, int* bn, int*
   }
 }
 
+// Which reduction follows a weight gradient of S slabs: kind 0 = wgrad_reduce_kernel<vec, sl> over `total` outputs (followed by
+// wgrad_rowdot_kernel when a layer-scale gradient is wanted), kind 1 = wgrad_reduce_rows_kernel<sl> (16-byte accesses: vec 4).
+// rows_ok: a layer-scale gradient is wanted and dw / w are 16-byte aligned.
+struct WgradReduceChoice {
+  int kind, vec, sl;
+  long total;
+};
+static WgradReduceChoice wgrad_reduce_choose(int S, int T, int Cout, int Cin, bool has_dbias, bool rows_ok) {
+  WgradReduceChoice c{};
+  const bool rvec = (Cin % 4 == 0);                 // slabs are 16-byte aligned (workspace arena), rows of Cin floats
+  c.vec = rvec ? 4 : 1;
+  c.total = (long)T * Cout * Cin / (rvec ? 4 : 1) + (has_dbias ? Cout : 0);
+  if (rows_ok && T == 1 && rvec) {
+    const int Q = Cin / 4;
+    int sl = 1;
+    while (sl < 16 && sl * 2 * Q <= 256) sl *= 2;
+    c.kind = 1; c.sl = sl;
+    return c;
+  }
+  // lanes per output: enough of them to cover the serial slab loop of the small matrices, one thread per output
+  // once the matrix alone yields >= 64K threads (a 16-lane block there is 6 K workgroups of 256 B of output each)
+  c.kind = 0;
+  c.sl = (c.total >= 65536 || S <= 2) ? 1 : ((c.total >= 16384 || S <= 8) ? 4 : 16);
+  return c;
+}
+
 // Slab reduction shared by every weight-gradient kernel: dw / dbias (+ layer-scale partials) from S slabs per stream.
 // (also called from pgemm.hip: the plane weight gradient writes the same slabs)
 int vr_wgrad_reduce_launch(float* slab, float* bslab, float* ls_part, long ls_stride, int S, int T, int Cout, int Cin,
@@ -1852,17 +1878,15 @@ int vr_wgrad_reduce_launch(float* slab, float* bslab, float* ls_part, long ls_st
                                int streams, const float* row_scale, float* dw, float* dbias, int accumulate,
                                const float* row_scale2, float* dw2, float* dbias2, const float* w, const float* w2,
                                const float* bias, const float* bias2, float* dls, float* dls2, hipStream_t st) {
-  const bool rvec = (Cin % 4 == 0);                 // slabs are 16-byte aligned (workspace arena), rows of Cin floats
-  if (dls && T == 1 && rvec && vr_aligned16(dw) && (!dw2 || vr_aligned16(dw2)) && vr_aligned16(w) && (!w2 || vr_aligned16(w2)) &&
-      (!bias || dbias)) {
+  const bool rows_ok = dls && vr_aligned16(dw) && (!dw2 || vr_aligned16(dw2)) && vr_aligned16(w) && (!w2 || vr_aligned16(w2)) &&
+                       (!bias || dbias);
+  const WgradReduceChoice c = wgrad_reduce_choose(S, T, Cout, Cin, dbias != nullptr, rows_ok);
+  if (c.kind == 1) {
     // slab sums, row scale AND the layer-scale gradient in one launch: one workgroup per output row
-    const int Q = Cin / 4;
-    int sl = 1;
-    while (sl < 16 && sl * 2 * Q <= 256) sl *= 2;
 #define VR_WROWS(SL_)                                                                                                     \
   hipLaunchKernelGGL((wgrad_reduce_rows_kernel<SL_>), dim3(Cout, streams), dim3(256), 0, st, slab, bslab, row_scale, dw,  \
                      dbias, S, Cout, Cin, accumulate, row_scale2, dw2, dbias2, w, w2, bias, bias2, dls, dls2)
-    switch (sl) {
+    switch (c.sl) {
       case 16: VR_WROWS(16); break;
       case 8: VR_WROWS(8); break;
       case 4: VR_WROWS(4); break;
@@ -1873,20 +1897,17 @@ int vr_wgrad_reduce_launch(float* slab, float* bslab, float* ls_part, long ls_st
     VR_LAUNCH_CHECK("conv2d_wgrad_reduce_rows");
     return VR_OK;
   }
-  const long total = (long)T * Cout * Cin / (rvec ? 4 : 1) + (dbias ? Cout : 0);
+  const long total = c.total;
 #define VR_WREDUCE(VEC_, SL_)                                                                                        \
   hipLaunchKernelGGL((wgrad_reduce_kernel<VEC_, SL_>), dim3(vr_cdiv(total, 256 / SL_), streams), dim3(256), 0, st, slab, \
                      bslab, row_scale, dw, dbias, S, T, Cout, Cin, accumulate, row_scale2, dw2, dbias2, w, w2, ls_part)
-  // lanes per output: enough of them to cover the serial slab loop of the small matrices, one thread per output
-  // once the matrix alone yields >= 64K threads (a 16-lane block there is 6 K workgroups of 256 B of output each)
-  const int sl = (total >= 65536 || S <= 2) ? 1 : ((total >= 16384 || S <= 8) ? 4 : 16);
-  if (rvec) {
-    if (sl == 16) VR_WREDUCE(4, 16);
-    else if (sl == 4) VR_WREDUCE(4, 4);
+  if (c.vec == 4) {
+    if (c.sl == 16) VR_WREDUCE(4, 16);
+    else if (c.sl == 4) VR_WREDUCE(4, 4);
     else VR_WREDUCE(4, 1);
   } else {
-    if (sl == 16) VR_WREDUCE(1, 16);
-    else if (sl == 4) VR_WREDUCE(1, 4);
+    if (c.sl == 16) VR_WREDUCE(1, 16);
+    else if (c.sl == 4) VR_WREDUCE(1, 4);
     else VR_WREDUCE(1, 1);
   }
 #undef VR_WREDUCE
@@ -1896,6 +1917,58 @@ int vr_wgrad_reduce_launch(float* slab, float* bslab, float* ls_part, long ls_st
                        (int)((ls_stride - Cout) / Cout), ls_stride, accumulate, bias2, dls2);
     VR_LAUNCH_CHECK("conv2d_wgrad_rowdot");
   }
+  return VR_OK;
+}
+
+// Which kernel vrnet_conv2d_wgrad_f32 launches on the MFMA path (after the tiny / narrow early exits) for Ms contraction rows per
+// stream, and on which row split.  kind 0 wgrad_kernel, 1 wgrad_dma_kernel, 2 wgrad_x6_kernel, 3 the bf16 kernel
+// (igemm_bf16.hip); tile = 64064 / 128128 / 128064 / 128032 (BM BN of wgrad_kernel), or the x6 cfg 22 / 21 / 12.  precision is
+// what the kernel runs at: 2 falls back to 0 where no tile kernel serves the shape.  vec: 16-byte rows on both operands
+// (channel counts and row strides % 4, aligned bases).  Returns 0, 1 (precision out of range) or 2 (precision 1 without a
+// kernel for the shape).
+struct WgradChoice {
+  int kind, tile, precision, S, rows, nt, ct, xcd_group;
+};
+static int wgrad_choose(long Ms, int Cin, int Cout, int T, bool ident, bool vec, int precision, WgradChoice* c) {
+  (void)ident;          // every kernel has an ident and a gather instantiation: the flag selects the template argument only
+  int cfg = 0, bn = 0, x6cfg = 0;
+  *c = WgradChoice{};
+  if (precision == 2 || precision == 1) {      // the tile kernels: x6, or (precision 1) bf16-rounded operands
+    if (vec) wgrad_plan(Ms, Cin, Cout, T, &x6cfg, &bn, &c->nt, &c->ct, &c->S, &c->rows, 2);
+    if (!x6cfg && precision == 2) precision = 0;       // no tile kernel for this shape: the fp32 MFMA path
+  }
+  if (!x6cfg) wgrad_plan(Ms, Cin, Cout, T, &cfg, &bn, &c->nt, &c->ct, &c->S, &c->rows, precision == 1);
+  c->precision = precision;
+  if (precision < 0 || precision > 2) return 1;
+  const long tiles = (long)c->nt * c->ct * T;
+  if (x6cfg) {
+    c->kind = 2; c->tile = x6cfg;
+    c->xcd_group = (c->S % 8 == 0 && tiles * (c->S / 8) <= 96) ? 1 : 0;      // see wgrad_plan / wgrad_rows_xcd
+  } else if (precision == 1) {
+    if (!(vec && cfg == 1 && c->rows % 64 == 0)) return 2;
+    c->kind = 3; c->tile = 64064;
+  } else {
+    static const int use_dma = vr_tune("VRNET_WGRAD_DMA", 1);   // tuning aid
+    // measured (bench.py --detail): the ring wins only for the smallest weight matrices (<= 4 tiles: +5..19 %); with
+    // more tiles the row-split grid already fills the chip and the 8-workgroups-per-CU kernel is 5-15 % faster
+    if (cfg == 1 && vec && (use_dma == 2 || (use_dma && tiles <= 4))) { c->kind = 1; c->tile = 64064; }
+    else c->tile = cfg == 1 ? 64064 : (bn == 128 ? 128128 : (bn == 64 ? 128064 : 128032));
+  }
+  return 0;
+}
+
+/* The plan of vrnet_conv2d_wgrad_f32's MFMA path (host only; include/vrnet_hip.h). */
+extern "C" int vrnet_conv2d_wgrad_plan(long rows, int Cin, int Cout, int taps, int ident, int vec, int precision, int has_bias,
+                                       int has_dls, int* out) {
+  VR_CHECK_ARG(out && rows > 0 && Cin > 0 && Cout > 0 && taps > 0, "conv2d_wgrad_plan: bad arguments");
+  WgradChoice c;
+  const int rc = wgrad_choose(rows, Cin, Cout, taps, ident != 0, vec != 0, precision, &c);
+  VR_CHECK_ARG(rc != 1, "conv2d_wgrad: precision 0 (fp32 MFMA), 1 (bf16 operands) or 2 (x6)");
+  VR_CHECK_ARG(rc != 2, "conv2d_wgrad: the bf16 path needs 16-byte aligned rows, channel counts that "
+                        "are multiples of 4 and more than 32 channels on both sides");
+  const WgradReduceChoice r = wgrad_reduce_choose(c.S, taps, Cout, Cin, has_bias != 0, has_dls != 0);
+  out[0] = c.kind; out[1] = c.tile; out[2] = c.S; out[3] = c.rows; out[4] = c.xcd_group;
+  out[5] = r.kind; out[6] = r.vec; out[7] = r.sl;
   return VR_OK;
 }
 
@@ -1949,15 +2022,13 @@ extern "C" int vrnet_conv2d_wgrad_f32(const float* x, long ldx, const float* dy,
   VR_CHECK_ARG(!dls || (w && T == 1 && (!bias || dbias) && (streams == 1 || (w2 && dls2 && (!bias == !bias2)))),
                "conv2d_wgrad: the layer-scale gradient needs a 1x1 conv, its weights, (with a bias) the bias gradient, "
                "and in a two-stream launch the second set");
-  int cfg, bn, nt, ct, S, rows;
-  const bool vec_all = (Cin % 4 == 0) && (ldx % 4 == 0) && vr_aligned16(x) && (Cout % 4 == 0) && (lddy % 4 == 0) &&
-                       vr_aligned16(dy);
-  int x6cfg = 0;
-  if (precision == 2 || precision == 1) {      // the tile kernels: x6, or (precision 1) bf16-rounded operands
-    if (vec_all) wgrad_plan(M / streams, Cin, Cout, T, &x6cfg, &bn, &nt, &ct, &S, &rows, 2);
-    if (!x6cfg && precision == 2) precision = 0;       // no tile kernel for this shape: the fp32 MFMA path
-  }
-  if (!x6cfg) wgrad_plan(M / streams, Cin, Cout, T, &cfg, &bn, &nt, &ct, &S, &rows, precision == 1);
+  const bool vec = (Cin % 4 == 0) && (ldx % 4 == 0) && vr_aligned16(x) && (Cout % 4 == 0) && (lddy % 4 == 0) &&
+                   vr_aligned16(dy);
+  const bool ident = kh == 1 && kw == 1 && stride == 1 && pad == 0;
+  WgradChoice c;
+  const int choice_rc = wgrad_choose(M / streams, Cin, Cout, T, ident, vec, precision, &c);
+  precision = c.precision;
+  const int S = c.S, rows = c.rows, nt = c.nt, ct = c.ct;
   const long need = vrnet_conv2d_wgrad_workspace(B, OH, OW, Cin, Cout, kh, kw, streams == 2);
   if (workspace_bytes < need) {
     vr_set_error("conv2d_wgrad: workspace %ld < %ld bytes", workspace_bytes, need);
@@ -1991,9 +2062,6 @@ extern "C" int vrnet_conv2d_wgrad_f32(const float* x, long ldx, const float* dy,
   p.M = (int)M; p.OH = OH; p.OW = OW; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
   p.kh = kh; p.kw = kw; p.stride = stride; p.pad = pad; p.dil = dil;
   p.rows_per_split = rows; p.n_tiles = nt; p.c_tiles = ct; p.splits = S;
-  const bool vec = (Cin % 4 == 0) && (ldx % 4 == 0) && vr_aligned16(x) && (Cout % 4 == 0) && (lddy % 4 == 0) &&
-                   vr_aligned16(dy);
-  const bool ident = kh == 1 && kw == 1 && stride == 1 && pad == 0;
   hipStream_t st = vr_stream(stream);
   dim3 grid(nt * ct * T, S, streams), block(256);
 #define VR_WGRAD(BM_, BN_, TM_, TN_, WM_, WN_)                                                                      \
@@ -2002,9 +2070,11 @@ extern "C" int vrnet_conv2d_wgrad_f32(const float* x, long ldx, const float* dy,
     else if (vec) hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, TM_, TN_, WM_, WN_, false, true>), grid, block, 0, st, p);     \
     else hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, TM_, TN_, WM_, WN_, false, false>), grid, block, 0, st, p);             \
   } while (0)
-  VR_CHECK_ARG(precision >= 0 && precision <= 2, "conv2d_wgrad: precision 0 (fp32 MFMA), 1 (bf16 operands) or 2 (x6)");
-  if (x6cfg) {
-    p.xcd_group = (S % 8 == 0 && (long)nt * ct * T * (S / 8) <= 96) ? 1 : 0;      // see wgrad_plan / wgrad_rows_xcd
+  VR_CHECK_ARG(choice_rc != 1, "conv2d_wgrad: precision 0 (fp32 MFMA), 1 (bf16 operands) or 2 (x6)");
+  VR_CHECK_ARG(choice_rc != 2, "conv2d_wgrad: the bf16 path needs 16-byte aligned rows, channel counts that "
+                               "are multiples of 4 and more than 32 channels on both sides");
+  if (c.kind == 2) {
+    p.xcd_group = c.xcd_group;
     const dim3 grid8 = grid;
 #define VR_WX6(TN_, TC_)                                                                                            \
   do {                                                                                                              \
@@ -2016,28 +2086,21 @@ extern "C" int vrnet_conv2d_wgrad_f32(const float* x, long ldx, const float* dy,
       else hipLaunchKernelGGL((wgrad_x6_kernel<TN_, TC_, false, 1>), grid8, block, 0, st, p);                        \
     }                                                                                                               \
   } while (0)
-    if (x6cfg == 22) VR_WX6(2, 2);
-    else if (x6cfg == 21) VR_WX6(2, 1);
+    if (c.tile == 22) VR_WX6(2, 2);
+    else if (c.tile == 21) VR_WX6(2, 1);
     else VR_WX6(1, 2);
 #undef VR_WX6
-  } else if (precision == 1) {
-    VR_CHECK_ARG(vec && cfg == 1 && rows % 64 == 0, "conv2d_wgrad: the bf16 path needs 16-byte aligned rows, channel counts that "
-                                                    "are multiples of 4 and more than 32 channels on both sides");
+  } else if (c.kind == 3) {
     vr_wgrad_bf16_launch(&p, ident ? 1 : 0, nt * ct * T, S, streams, st);
-  } else {
-  static const int use_dma = vr_tune("VRNET_WGRAD_DMA", 1);   // tuning aid
-  // measured (bench.py --detail): the ring wins only for the smallest weight matrices (<= 4 tiles: +5..19 %); with
-  // more tiles the row-split grid already fills the chip and the 8-workgroups-per-CU kernel is 5-15 % faster
-  if (cfg == 1 && vec && (use_dma == 2 || (use_dma && nt * ct * T <= 4))) {
+  } else if (c.kind == 1) {
     if (ident) hipLaunchKernelGGL((wgrad_dma_kernel<true>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((wgrad_dma_kernel<false>), grid, block, 0, st, p);
-  } else if (cfg == 1) VR_WGRAD(64, 64, 1, 1, 2, 2);
-  else if (bn == 128) VR_WGRAD(128, 128, 2, 2, 2, 2);
-  else if (bn == 64) VR_WGRAD(128, 64, 2, 1, 2, 2);
+  } else if (c.tile == 64064) VR_WGRAD(64, 64, 1, 1, 2, 2);
+  else if (c.tile == 128128) VR_WGRAD(128, 128, 2, 2, 2, 2);
+  else if (c.tile == 128064) VR_WGRAD(128, 64, 2, 1, 2, 2);
   else VR_WGRAD(128, 32, 1, 1, 4, 1);
-  }
 #undef VR_WGRAD
-  vr_note_kernel(x6cfg ? (precision == 2 ? 6 : 3) : (precision == 1 ? 3 : 1));
+  vr_note_kernel(c.kind == 2 ? (precision == 2 ? 6 : 3) : (precision == 1 ? 3 : 1));
   VR_LAUNCH_CHECK("conv2d_wgrad");
   return wgrad_reduce_launch(p.slab, p.bslab, ls_part, ls_stride, S, T, Cout, Cin, streams, row_scale, dw, dbias, accumulate,
                              row_scale2, dw2, dbias2, w, w2, bias, bias2, dls, dls2, st);

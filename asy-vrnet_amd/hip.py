@@ -44,6 +44,7 @@ _SIGS = {
     "vrnet_wgrad_planes_f32": ([P, L, L, P, L, L, I, L, I, I, P, P, P, I, P, P, P, P, L, P], I),
     "vrnet_conv2d_dma_tile": ([L, I], I),
     "vrnet_conv2d_wgrad_workspace": ([I] * 8, L),
+    "vrnet_conv2d_wgrad_plan": ([L] + [I] * 8 + [P], I),
     "vrnet_conv2d_wgrad_f32": ([P, L, P, L, P, P, P] + [I] * 14 + [P, P, P, P, P, P, P, P, P, P, L, P], I),
     "vrnet_pack_weight_f32": ([P, P, I, I, I, I, P], I),
     "vrnet_mlp_fused_ok": ([I, I, L], I),
@@ -434,6 +435,15 @@ def conv2d_wgrad(x, ldx, dy, lddy, dw, dbias, row_scale, B, H, W, Cin, OH, OW, C
                                        OH, OW, Cout, kh, kw, stride, pad, dil, accumulate, precision, ptr(dw2),
                                        ptr(dbias2), ptr(row_scale2), ptr(w), ptr(bias), ptr(dls), ptr(w2), ptr(bias2),
                                        ptr(dls2), ptr(ws), ws.numel(), stream()), "conv2d_wgrad")
+
+
+def conv2d_wgrad_plan(rows, Cin, Cout, taps, ident, vec, precision=0, has_bias=True, has_dls=False):
+    """(kernel, tile, S, rows_per_split, xcd_group, reduce, VEC, SL) of conv2d_wgrad's MFMA path for `rows` output pixels per
+    stream (vrnet_conv2d_wgrad_plan in include/vrnet_hip.h; a host call).  Raises where conv2d_wgrad refuses the call."""
+    out = (ctypes.c_int * 8)()
+    _check(_lib.vrnet_conv2d_wgrad_plan(rows, Cin, Cout, taps, int(ident), int(vec), precision, int(has_bias), int(has_dls), out),
+           "conv2d_wgrad_plan")
+    return tuple(out)
 
 
 def bf16_wgrad_ok(ldx, lddy, Cin, Cout):

@@ -209,6 +209,20 @@ int vrnet_wgrad_planes_f32(const void* x, long ldx, long x_plane, const void* dy
  *   dls[n] (+)= sum_c w[n][c] * dw_raw[n][c] + bias[n] * db_raw[n]  (raw = before row_scale), which equals
  *   sum_m dy[m,n] * conv(h)[m,n] -- so the branch output is neither stored in the forward pass nor re-read. */
 long vrnet_conv2d_wgrad_workspace(int B, int OH, int OW, int Cin, int Cout, int kh, int kw, int pair);
+/* What vrnet_conv2d_wgrad_f32 launches on its MFMA path (the shapes that the tiny- and narrow-channel kernels, families 4
+ * and 5, do not take) for `rows` = B*OH*OW output pixels PER STREAM and taps = kh * kw; a host-only query, taken from the
+ * functions the launcher itself dispatches on.  ident: 1x1, stride 1, pad 0; vec: both operands have 16-byte rows (Cin, Cout,
+ * ldx, lddy % 4 == 0, aligned bases); has_bias: dbias given; has_dls: dls given (dw and w 16-byte aligned).  out[8]:
+ *   0 kernel   0 wgrad_kernel, 1 wgrad_dma_kernel, 2 wgrad_x6_kernel (precision 2: x6, 1: bf16-rounded operands), 3 the bf16
+ *              kernel of igemm_bf16.hip.  0 / 1 at precision 2: no tile kernel for the shape, the fp32 path serves it.
+ *   1 tile     64064 / 128128 / 128064 / 128032 (rows x columns of dW per workgroup), or the x6 cfg 22 / 21 / 12
+ *   2 S        row splits = slabs per stream            3 rows_per_split (the last split may be shorter)
+ *   4 xcd_group  1: all tiles of a row split run on one XCD (x6 kernels)
+ *   5 reduce   0 wgrad_reduce_kernel<VEC, SL> (with has_dls followed by wgrad_rowdot_kernel), 1 wgrad_reduce_rows_kernel<SL>
+ *   6 VEC      7 SL
+ * Returns non-zero where vrnet_conv2d_wgrad_f32 refuses the call (precision 1 without a kernel, precision outside 0..2). */
+int vrnet_conv2d_wgrad_plan(long rows, int Cin, int Cout, int taps, int ident, int vec, int precision, int has_bias,
+                            int has_dls, int* out);
 int vrnet_conv2d_wgrad_f32(const float* x, long ldx, const float* dy, long lddy, float* dw, float* dbias,
                            const float* row_scale, int B, int H, int W, int Cin, int OH, int OW, int Cout, int kh,
                            int kw, int stride, int pad, int dil, int accumulate, int precision, float* dw2,
