@@ -1509,6 +1509,216 @@ extern "C" long vrnet_conv2d_splitk_workspace(long rows, int cols, long ktot) {
  * back to the fp32 MFMA).  Alignment requirements (16-byte rows, channel counts % 4) are the caller's, as for precision 1. */
 extern "C" int vrnet_conv2d_dma_tile(long rows, int cols) { return vr_dma_tile(rows, cols); }
 
+// What vrnet_conv2d_f32 launches for a call, decided in ONE place: conv_choose fills a ConvChoice from the call's geometry, row
+// strides, pointer alignments and option flags (a ConvQuery), the launcher switches on it and the host-only query
+// vrnet_conv2d_plan (include/vrnet_hip.h) answers from it.
+enum ConvKernel {
+  CONV_IGEMM = 0,       // igemm_kernel<BM, BN, ..., mode, vec>, tile = 128032 / 128064 / 64064          family 1
+  CONV_RING = 1,        // igemm_dma_kernel<mode, 3, 1, 1>: the fp32 LDS-DMA ring, 64 x 64              family 2
+  CONV_X6 = 2,          // igemm_dma_kernel<mode, 3, 2, 2 / 1, 6>, tile 22 / 21 (+ the split finish)      family 6
+  CONV_BF16_TILE = 3,   // igemm_dma_kernel<mode, 3, 2, 2 / 1, 1>: bf16-rounded operands, tile 22 / 21   family 3
+  CONV_PLANES = 4,      // igemm_planes_kernel<2, 2> / <1, 3> on pre-split weights (+ the split finish)   family 9
+  CONV_BF16 = 5,        // igemm_bf16_kernel<mode> (igemm_bf16.hip), 64 x 64                              family 3
+  CONV_TINY = 6,        // tinyconv.hip                                                                   family 4
+  CONV_NARROW = 7,      // narrowconv.hip                                                                 family 5
+  CONV_PATCH = 8,       // patch data gradient (tinyconv.hip)                                             family 4
+};
+struct ConvQuery {
+  int B, H, W, Cin, OH, OW, Cout, kh, kw, stride, pad, dil, mode, precision;
+  long lda, ldy;
+  // 16-byte alignment of a, w, (two-stream launches) w2 and y; of the epilogue operands: absent, or an aligned base and (where
+  // it has one) a row stride % 4 == 0
+  bool a_al, w_al, w2_al, y_al, bias_al, ypre_al, res_al, res_scale_al, aux_al;
+  bool kscale, plain, epilogue, out_nchw, stats, colstats, colstats_al, planes;      // epilogue: ypre, res, kscale, aux or act
+  long ws_bytes;                 // bytes of split workspace (0: none given)
+  int pair_rows;
+};
+struct ConvChoice {
+  int kernel, family, tile, S, perm2, a_vec, b_vec, e_vec, pair_rows;
+  long k_live;
+  unsigned grid_x, grid_y, finish_grid;      // finish_grid: workgroups of igemm_splitk_finish_kernel (S > 1)
+  int mt, nt;                                // row / column tiles of the ring and tile kernels
+};
+
+static int conv_choose(const ConvQuery& q, ConvChoice* c) {
+  *c = ConvChoice{};
+  c->S = 1;
+  const int mode = q.mode, precision = q.precision, Cin = q.Cin, Cout = q.Cout, kh = q.kh, kw = q.kw, stride = q.stride;
+  const int pair_rows = q.pair_rows;
+  if (q.plain && tiny_shape(q.H, q.W, Cin, q.OH, q.OW, Cout, kh, kw, stride)) {
+    c->kernel = CONV_TINY; c->family = 4;
+    return VR_OK;
+  }
+  // narrow outputs over wide inputs (head predictions, seg logits): direct HBM-streaming kernels (narrowconv.hip)
+  if ((vr_tune("VRNET_NARROW", 3) >> mode & 1) && !q.colstats && !q.epilogue && !q.stats && !pair_rows && precision != 1 &&
+      precision != 3 && vr_narrow_conv_ok(Cin, Cout, kh, kw, stride, q.pad) && !tiny_shape(q.H, q.W, Cin, q.OH, q.OW, Cout, kh, kw, stride) && q.w_al &&
+      (mode == 0 ? (q.lda % 4 == 0 && q.a_al) : (!q.out_nchw && q.ldy % 4 == 0 && q.y_al))) {
+    c->kernel = CONV_NARROW; c->family = 5;
+    return VR_OK;
+  }
+  if (q.plain && mode == 1 && Cin <= 8 && kh == kw && kh == stride && q.pad == 0 && q.dil == 1 && q.H == q.OH * kh &&
+      q.W == q.OW * kw && (size_t)kh * kw * Cout * Cin * 4 <= 60000) {
+    c->kernel = CONV_PATCH; c->family = 4;
+    return VR_OK;
+  }
+  const int MH = mode == 0 ? q.OH : q.H, MW = mode == 0 ? q.OW : q.W, SH = mode == 0 ? q.H : q.OH, SW = mode == 0 ? q.W : q.OW;
+  const int CK = mode == 0 ? Cin : Cout, CN = mode == 0 ? Cout : Cin;
+  const long M = (long)q.B * MH * MW;
+  VR_CHECK_ARG(M < (1L << 31) && (long)q.B * SH * SW < (1L << 31), "conv2d: too many pixels");
+  c->perm2 = (mode == 1 && stride == 2 && MH % 2 == 0 && MW % 2 == 0 && (M / 4) % 128 == 0) ? 1 : 0;
+  c->a_vec = (CK % 4 == 0) && (q.lda % 4 == 0) && q.a_al;
+  c->b_vec = (Cin % 4 == 0) && q.w_al;
+  c->e_vec = !q.out_nchw && (CN % 4 == 0) && (q.ldy % 4 == 0) && q.y_al && q.bias_al && q.ypre_al && q.res_al && q.res_scale_al &&
+             q.aux_al;
+  c->pair_rows = pair_rows;
+  VR_CHECK_ARG(!pair_rows || (pair_rows < M && 2L * pair_rows == M), "conv2d: the two streams must have equal row counts");
+  if (pair_rows && c->perm2) {
+    if ((M / 8) % 128 == 0) c->pair_rows = (int)(M / 8);      // parity-major rows: the streams split every parity class
+    else c->perm2 = 0;
+  }
+  if (pair_rows) c->b_vec = c->b_vec && q.w2_al;      // (bias2 / res_scale2: the caller folds them into bias_al / res_scale_al)
+  VR_CHECK_ARG(!q.colstats || (c->e_vec && !c->perm2 && CN > 32 && q.colstats_al),
+               "conv2d: column statistics need the vector epilogue (NHWC, channel counts %% 4 == 0, 16-byte rows), > 32 output "
+               "channels and no stride-2 data gradient");
+  VR_CHECK_ARG(!q.stats || (c->e_vec && !c->perm2 && mode == 0 && ((long)MH * MW) % 32 == 0 && CN > 32),
+               "conv2d: output statistics need the vector epilogue, a forward conv, > 32 output channels and a map of a "
+               "multiple of 32 pixels");
+  // bf16-rounded operands: the forward launches whose grid fills the chip run on the LDS-DMA tile kernels below (as do
+  // data gradients at precision 3, standard weight layout); everything else on the register-staged bf16 kernel
+  const bool bf16_tile_fwd = precision == 1 && mode == 0 && c->a_vec && c->b_vec && CN > 32 && vr_dma_tile(M, CN) != 0 &&
+                             (!pair_rows || pair_rows % 128 == 0);
+  if (precision == 1 && !bf16_tile_fwd) {
+    // bf16 operands: both operands must be contraction-contiguous 16-byte rows; in mode 1 `w` is the TRANSPOSED pack
+    // (vrnet_pack_weight_t_f32, which also folds kscale in), so kscale must not be passed again
+    VR_CHECK_ARG(c->a_vec && CK % 4 == 0 && q.w_al && CN > 32 && !q.kscale,
+                 "conv2d: the bf16 path needs 16-byte aligned rows, a contraction that is a multiple of 4, more than 32 "
+                 "output channels and (mode 1) the transposed weight pack with kscale folded in");
+    c->perm2 = 0;
+    c->pair_rows = pair_rows;
+    c->kernel = CONV_BF16; c->family = 3; c->tile = 64064; c->k_live = (long)CK * kh * kw;
+    c->grid_x = (unsigned)vr_cdiv(M, 64); c->grid_y = (unsigned)vr_cdiv(CN, 64);
+    return VR_OK;
+  }
+  const bool vec = c->a_vec && c->b_vec;
+  static const int use_dma = vr_tune("VRNET_IGEMM_DMA", 1);   // tuning aid
+  const long ktot = (long)CK * kh * kw;
+  c->k_live = ktot;
+  const bool dma_ok = use_dma && vec && CN > 32 && (!q.kscale || CK <= 1024);
+  // 64 x 64 ring tiles where the grid cannot fill the chip with 8 workgroups per CU (M <= 8192 pixels: +5..40 %) and
+  // on long contractions; the register-staged kernel keeps the large-M, short-K layers (2048 row tiles x few K steps:
+  // its 8 workgroups per CU hide the store-heavy epilogues better).  128 x 128 ring tiles (T = 2) were measured on the
+  // large-M layers with >= 768 such tiles: 4-11 % slower than either (K <= 256 there: prologue / epilogue bound), so
+  // they are not dispatched.  All measured with bench.py --detail.
+  const bool dma_shape = use_dma == 2 || M <= 8192 || (M <= 32768 && ktot >= 1024);
+  // precision 2 (x6): 128 x 128 x 16 ring tiles with 2 x 2 accumulators per wave -- each split fragment feeds two
+  // MFMA groups, which is what pays for the split (on 64 x 64 tiles the conversions cost what the faster MFMA saves)
+  const bool bf16_tiles = precision == 3 || (precision == 1 && mode == 0);   // (mode 1 at precision 1 brings the transposed pack)
+  if ((precision == 2 || bf16_tiles) && dma_ok && (!pair_rows || c->pair_rows % 128 == 0)) {
+    const long mt = vr_cdiv(M, 128), nt22 = vr_cdiv(CN, 128), nt21 = vr_cdiv(CN, 64);
+    int S = 1;
+    // (the bf16-rounded tiles of precision 1 / 3 keep the unsplit rule: their callers asked vrnet_conv2d_dma_tile)
+    // contraction length that counts for the split: only taps that reach the image for at least one row (a 3 x 3 conv with
+    // dilation 18 on a 16 x 16 map is its centre tap)
+    long k_live = ktot;
+    if (kh * kw > 1) {
+      auto live = [&](int k, int n_m, int n_s) {
+        int n = 0;
+        for (int t = 0; t < k; ++t) {
+          bool any = false;
+          for (int o = 0; o < n_m && !any; ++o) {
+            if (mode == 0) {
+              const int sidx = o * stride - q.pad + t * q.dil;
+              any = sidx >= 0 && sidx < n_s;
+            } else {
+              const int tt = o + q.pad - t * q.dil;
+              any = tt >= 0 && tt % stride == 0 && tt / stride < n_s;
+            }
+          }
+          n += any;
+        }
+        return n;
+      };
+      k_live = (long)CK * live(kh, MH, SH) * live(kw, MW, SW);
+    }
+    c->k_live = k_live;
+    const int tile = precision == 2 ? vr_dma_plan(M, CN, k_live, q.ws_bytes, &S) : vr_dma_tile(M, CN);
+    if (tile) {
+      const long nt = tile == 22 ? nt22 : nt21;
+      c->tile = tile; c->S = S; c->mt = (int)mt; c->nt = (int)nt;
+      c->grid_x = (unsigned)(8 * vr_cdiv(mt, 8) * nt * S); c->grid_y = 1;
+      c->finish_grid = S > 1 ? (unsigned)(8 * vr_cdiv(mt, 8) * nt) : 0;
+      // pre-split weights (vrnet_conv_planes_pack_f32; in mode 1 the pack holds the transposed weights with kscale folded in)
+      if (precision == 2 && q.planes && kh == 1 && kw == 1 && stride == 1 && q.pad == 0 && !pair_rows && CK % 16 == 0 &&
+          vr_tune("VRNET_X6_PLANES", 1)) {
+        c->kernel = CONV_PLANES; c->family = 9;
+      } else {
+        c->kernel = precision == 2 ? CONV_X6 : CONV_BF16_TILE; c->family = precision == 2 ? 6 : 3;
+      }
+      return VR_OK;
+    }
+  }
+  VR_CHECK_ARG(precision != 3, "conv2d: precision 3 (bf16-rounded operands on the LDS-DMA tiles, standard weight layout) has "
+                               "no kernel for this shape / alignment: ask vrnet_conv2d_dma_tile first");
+  if (dma_ok && dma_shape) {
+    c->kernel = CONV_RING; c->family = 2; c->tile = 64064;
+    c->mt = (int)vr_cdiv(M, 64); c->nt = (int)vr_cdiv(CN, 64);
+    c->grid_x = (unsigned)(8 * vr_cdiv(c->mt, 8) * c->nt); c->grid_y = 1;
+    return VR_OK;
+  }
+  // Register-staged tiles: 64 x 64 by default; 128 x 64 for narrow outputs over long contractions; 128 x 32 for <= 32 columns.
+  // Measured on MI355X over every conv shape of the net (phi = l, bs 8, 512 px; profiles/r01_igemm_tile_sweep.txt): 64 x 64
+  // tiles (7 workgroups per CU) beat 128 x 128 (2 per CU) and 128 x 64 on 90 % of the shapes -- 21.4 vs 30.7 / 25.9 ms per
+  // step over all forward + data-gradient launches; the exceptions are within 10 %.  BK = 32 measured 3 % slower.
+  static const int narrow = vr_tune("VRNET_IGEMM_NARROW", 1);   // tuning aid
+  c->kernel = CONV_IGEMM; c->family = 1;
+  if (CN <= 32) {
+    c->tile = 128032; c->grid_x = (unsigned)vr_cdiv(M, 128); c->grid_y = 1;
+  } else if (narrow && vec && CN <= 192 && ktot >= 512) {
+    c->tile = 128064; c->grid_x = (unsigned)vr_cdiv(M, 128); c->grid_y = (unsigned)vr_cdiv(CN, 64);
+  } else {
+    c->tile = 64064; c->grid_x = (unsigned)vr_cdiv(M, 64); c->grid_y = (unsigned)vr_cdiv(CN, 64);
+  }
+  return VR_OK;
+}
+
+// The argument checks of vrnet_conv2d_f32 that depend on the geometry alone (shared with vrnet_conv2d_plan).
+static int conv_check_geometry(const ConvQuery& q) {
+  VR_CHECK_ARG(q.precision >= 0 && q.precision <= 3, "conv2d: precision 0 (fp32 MFMA), 1 / 3 (bf16 operands, fp32 accumulate) "
+                                                     "or 2 (fp32 products as six bf16 x bf16 products, fp32 accumulate)");
+  VR_CHECK_ARG(q.B > 0 && q.H > 0 && q.W > 0 && q.Cin > 0 && q.OH > 0 && q.OW > 0 && q.Cout > 0, "conv2d: bad shape");
+  VR_CHECK_ARG(q.kh > 0 && q.kw > 0 && q.stride > 0 && q.dil > 0 && q.pad >= 0, "conv2d: bad geometry");
+  VR_CHECK_ARG((q.H + 2 * q.pad - q.dil * (q.kh - 1) - 1) / q.stride + 1 == q.OH &&
+                   (q.W + 2 * q.pad - q.dil * (q.kw - 1) - 1) / q.stride + 1 == q.OW,
+               "conv2d: output size %dx%d inconsistent with input %dx%d k%d s%d p%d d%d", q.OH, q.OW, q.H, q.W, q.kh,
+               q.stride, q.pad, q.dil);
+  // one check for every path: a row of a holds the contracted channels, a row of y the produced ones
+  VR_CHECK_ARG(q.lda >= (q.mode == 0 ? q.Cin : q.Cout) && (q.out_nchw || q.ldy >= (q.mode == 0 ? q.Cout : q.Cin)),
+               "conv2d: row stride smaller than channel count");
+  return VR_OK;
+}
+
+/* The plan of vrnet_conv2d_f32 (host only; include/vrnet_hip.h). */
+extern "C" int vrnet_conv2d_plan(int B, int H, int W, int Cin, int OH, int OW, int Cout, int kh, int kw, int stride, int pad,
+                                 int dil, int mode, int precision, long lda, long ldy, int flags, long workspace_bytes, int* out) {
+  VR_CHECK_ARG(out && (mode == 0 || mode == 1) && workspace_bytes >= 0, "conv2d_plan: bad arguments");
+  ConvQuery q{};
+  q.B = B; q.H = H; q.W = W; q.Cin = Cin; q.OH = OH; q.OW = OW; q.Cout = Cout; q.kh = kh; q.kw = kw; q.stride = stride;
+  q.pad = pad; q.dil = dil; q.mode = mode; q.precision = precision; q.lda = lda; q.ldy = ldy;
+  q.a_al = flags & 1; q.w_al = flags & 2; q.y_al = flags & 4; q.bias_al = flags & 8; q.ypre_al = flags & 16;
+  q.res_al = flags & 32; q.res_scale_al = flags & 64; q.aux_al = flags & 128; q.w2_al = true;
+  q.kscale = flags & 256; q.epilogue = !(flags & 512); q.out_nchw = flags & 1024; q.stats = flags & 2048;
+  q.colstats = flags & 4096; q.planes = flags & 8192; q.colstats_al = true;
+  VR_CHECK_ARG(q.epilogue || !q.kscale, "conv2d_plan: kscale is a fused epilogue operand");
+  q.plain = !q.epilogue && !q.out_nchw && !q.stats && precision != 1 && !q.colstats;
+  q.ws_bytes = workspace_bytes;
+  if (int rc = conv_check_geometry(q)) return rc;
+  ConvChoice c;
+  if (int rc = conv_choose(q, &c)) return rc;
+  out[0] = c.family; out[1] = c.kernel; out[2] = c.tile; out[3] = c.S; out[4] = (int)c.k_live; out[5] = c.perm2;
+  out[6] = c.a_vec; out[7] = c.b_vec; out[8] = c.e_vec; out[9] = (int)c.grid_x; out[10] = (int)c.grid_y; out[11] = (int)c.finish_grid;
+  return VR_OK;
+}
+
 extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const float* bias, float* y, long ldy,
                                 int B, int H, int W, int Cin, int OH, int OW, int Cout, int kh, int kw, int stride,
                                 int pad, int dil, int mode, int act, float* ypre, long ldypre, const float* res,
@@ -1527,37 +1737,36 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
                                                      (!res_scale == !res_scale2) && (!kscale == !kscale2))),
                "conv2d: a two-stream launch needs the second parameter set and a first-stream row count that is a "
                "multiple of 128");
-  VR_CHECK_ARG(precision >= 0 && precision <= 3, "conv2d: precision 0 (fp32 MFMA), 1 / 3 (bf16 operands, fp32 accumulate) "
-                                                 "or 2 (fp32 products as six bf16 x bf16 products, fp32 accumulate)");
-  VR_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && OH > 0 && OW > 0 && Cout > 0, "conv2d: bad shape");
-  VR_CHECK_ARG(kh > 0 && kw > 0 && stride > 0 && dil > 0 && pad >= 0, "conv2d: bad geometry");
-  VR_CHECK_ARG((H + 2 * pad - dil * (kh - 1) - 1) / stride + 1 == OH &&
-                   (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1 == OW,
-               "conv2d: output size %dx%d inconsistent with input %dx%d k%d s%d p%d d%d", OH, OW, H, W, kh,
-               stride, pad, dil);
-  const bool plain = !ypre && !res && !kscale && !aux && !out_nchw && act == 0 && !stats && precision != 1 && !pair_rows &&
-                     !colstats;
-  // one check for every path below: a row of a holds the contracted channels, a row of y the produced ones
-  VR_CHECK_ARG(lda >= (mode == 0 ? Cin : Cout) && (out_nchw || ldy >= (mode == 0 ? Cout : Cin)),
-               "conv2d: row stride smaller than channel count");
-  if (plain && tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride)) {
-    vr_note_kernel(4);
-    return vr_tiny_conv(mode, a, lda, w, mode == 0 ? bias : nullptr, y, ldy, B, H, W, Cin, Cout, kh, pad, dil, accumulate,
-                        vr_stream(stream));
-  }
-  // narrow outputs over wide inputs (head predictions, seg logits): direct HBM-streaming kernels (narrowconv.hip)
-  if ((vr_tune("VRNET_NARROW", 3) >> mode & 1) && !colstats && !ypre && !res && !kscale && !aux && act == 0 && !stats && !pair_rows && precision != 1 &&
-      precision != 3 && vr_narrow_conv_ok(Cin, Cout, kh, kw, stride, pad) && !tiny_shape(H, W, Cin, OH, OW, Cout, kh, kw, stride) && vr_aligned16(w) &&
-      (mode == 0 ? (lda % 4 == 0 && vr_aligned16(a)) : (!out_nchw && ldy % 4 == 0 && vr_aligned16(y)))) {
-    vr_note_kernel(5);
+  ConvQuery q{};
+  q.B = B; q.H = H; q.W = W; q.Cin = Cin; q.OH = OH; q.OW = OW; q.Cout = Cout; q.kh = kh; q.kw = kw; q.stride = stride;
+  q.pad = pad; q.dil = dil; q.mode = mode; q.precision = precision; q.lda = lda; q.ldy = ldy;
+  q.a_al = vr_aligned16(a); q.w_al = vr_aligned16(w); q.w2_al = !pair_rows || vr_aligned16(w2); q.y_al = vr_aligned16(y);
+  q.bias_al = (!bias || vr_aligned16(bias)) && (!pair_rows || !bias2 || vr_aligned16(bias2));
+  q.ypre_al = !ypre || ((ldypre % 4 == 0) && vr_aligned16(ypre));
+  q.res_al = !res || ((ldres % 4 == 0) && vr_aligned16(res));
+  q.res_scale_al = (!res_scale || vr_aligned16(res_scale)) && (!pair_rows || !res_scale2 || vr_aligned16(res_scale2));
+  q.aux_al = !aux || ((ldaux % 4 == 0) && vr_aligned16(aux));
+  q.kscale = kscale != nullptr;
+  q.epilogue = ypre || res || kscale || aux || act != 0;
+  q.plain = !q.epilogue && !out_nchw && !stats && precision != 1 && !pair_rows && !colstats;
+  q.out_nchw = out_nchw != 0; q.stats = stats != nullptr; q.colstats = colstats != nullptr;
+  q.colstats_al = !colstats || !colstats->x2 || (colstats->ldx2 % 4 == 0 && vr_aligned16(colstats->x2));
+  q.planes = w_planes != nullptr;
+  q.ws_bytes = workspace ? workspace_bytes : 0;
+  q.pair_rows = pair_rows;
+  if (int rc = conv_check_geometry(q)) return rc;
+  VR_CHECK_ARG(!colstats || (colstats->partial && (!colstats->tile_totals || colstats->gamma)),
+               "conv2d: column statistics need `partial` (and gamma with tile_totals)");
+  ConvChoice c;
+  if (int rc = conv_choose(q, &c)) return rc;
+  hipStream_t st = vr_stream(stream);
+  vr_note_kernel(c.family);
+  if (c.kernel == CONV_TINY)
+    return vr_tiny_conv(mode, a, lda, w, mode == 0 ? bias : nullptr, y, ldy, B, H, W, Cin, Cout, kh, pad, dil, accumulate, st);
+  if (c.kernel == CONV_NARROW)
     return vr_narrow_conv(mode, a, lda, w, mode == 0 ? bias : nullptr, y, ldy, (long)B * H * W, (long)H * W, Cin, Cout,
-                          mode == 0 ? out_nchw : 0, out_ctot, out_coff, accumulate, vr_stream(stream));
-  }
-  if (plain && mode == 1 && Cin <= 8 && kh == kw && kh == stride && pad == 0 && dil == 1 && H == OH * kh &&
-      W == OW * kw && (size_t)kh * kw * Cout * Cin * 4 <= 60000) {
-    vr_note_kernel(4);
-    return vr_patch_dgrad(a, lda, w, y, ldy, B, H, W, Cin, Cout, kh, accumulate, vr_stream(stream));
-  }
+                          mode == 0 ? out_nchw : 0, out_ctot, out_coff, accumulate, st);
+  if (c.kernel == CONV_PATCH) return vr_patch_dgrad(a, lda, w, y, ldy, B, H, W, Cin, Cout, kh, accumulate, st);
   IgemmArgs p{};
   p.a = a; p.lda = lda; p.w = w; p.bias = bias; p.y = y; p.ldy = ldy;
   p.ypre = ypre; p.ldypre = ldypre; p.res = res; p.ldres = ldres; p.res_scale = res_scale;
@@ -1570,187 +1779,84 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
   } else {
     p.MH = H; p.MW = W; p.SH = OH; p.SW = OW; p.CK = Cout; p.CN = Cin;
   }
-  const long M = (long)B * p.MH * p.MW;
-  VR_CHECK_ARG(M < (1L << 31) && (long)B * p.SH * p.SW < (1L << 31), "conv2d: too many pixels");
-  p.M = (int)M;
-  p.perm2 = (mode == 1 && stride == 2 && p.MH % 2 == 0 && p.MW % 2 == 0 && (M / 4) % 128 == 0) ? 1 : 0;
-  p.a_vec = (p.CK % 4 == 0) && (lda % 4 == 0) && vr_aligned16(a);
-  p.b_vec = (Cin % 4 == 0) && vr_aligned16(w);
-  p.e_vec = !out_nchw && (p.CN % 4 == 0) && (ldy % 4 == 0) && vr_aligned16(y) &&
-            (!bias || vr_aligned16(bias)) && (!ypre || ((ldypre % 4 == 0) && vr_aligned16(ypre))) &&
-            (!res || ((ldres % 4 == 0) && vr_aligned16(res))) && (!res_scale || vr_aligned16(res_scale)) &&
-            (!aux || ((ldaux % 4 == 0) && vr_aligned16(aux)));
+  p.M = (int)((long)B * p.MH * p.MW);
+  p.perm2 = c.perm2; p.a_vec = c.a_vec; p.b_vec = c.b_vec; p.e_vec = c.e_vec;
   p.stats = stats;
   p.stats_nb = (int)vr_cdiv(p.CN, 32);
   if (colstats) {
-    VR_CHECK_ARG(colstats->partial && (!colstats->tile_totals || colstats->gamma), "conv2d: column statistics need `partial` (and gamma "
-                                                                                 "with tile_totals)");
     p.col_part = colstats->partial; p.col_x2 = colstats->x2; p.ld_col_x2 = colstats->ldx2;
     p.col_gamma = colstats->gamma; p.col_tot = colstats->tile_totals;
   }
-  p.pair_rows = pair_rows; p.w2 = w2; p.bias2 = bias2; p.res_scale2 = res_scale2; p.kscale2 = kscale2;
-  VR_CHECK_ARG(!pair_rows || (pair_rows < M && 2L * pair_rows == M), "conv2d: the two streams must have equal row counts");
-  if (pair_rows && p.perm2) {
-    if ((M / 8) % 128 == 0) p.pair_rows = (int)(M / 8);      // parity-major rows: the streams split every parity class
-    else p.perm2 = 0;
-  }
-  if (pair_rows) {
-    p.b_vec = p.b_vec && vr_aligned16(w2);
-    p.e_vec = p.e_vec && (!bias2 || vr_aligned16(bias2)) && (!res_scale2 || vr_aligned16(res_scale2));
-  }
-  VR_CHECK_ARG(!colstats || (p.e_vec && !p.perm2 && p.CN > 32 && (!colstats->x2 || (colstats->ldx2 % 4 == 0 && vr_aligned16(colstats->x2)))),
-               "conv2d: column statistics need the vector epilogue (NHWC, channel counts %% 4 == 0, 16-byte rows), > 32 output "
-               "channels and no stride-2 data gradient");
-  VR_CHECK_ARG(!stats || (p.e_vec && !p.perm2 && mode == 0 && ((long)p.MH * p.MW) % 32 == 0 && p.CN > 32),
-               "conv2d: output statistics need the vector epilogue, a forward conv, > 32 output channels and a map of a "
-               "multiple of 32 pixels");
-  dim3 block(256);
-  hipStream_t st = vr_stream(stream);
-  // bf16-rounded operands: the forward launches whose grid fills the chip run on the LDS-DMA tile kernels below (as do
-  // data gradients at precision 3, standard weight layout); everything else on the register-staged bf16 kernel
-  const bool bf16_tile_fwd = precision == 1 && mode == 0 && p.a_vec && p.b_vec && p.CN > 32 && vr_dma_tile(M, p.CN) != 0 &&
-                             (!pair_rows || pair_rows % 128 == 0);
-  if (precision == 1 && !bf16_tile_fwd) {
-    // bf16 operands: both operands must be contraction-contiguous 16-byte rows; in mode 1 `w` is the TRANSPOSED pack
-    // (vrnet_pack_weight_t_f32, which also folds kscale in), so kscale must not be passed again
-    VR_CHECK_ARG(p.a_vec && p.CK % 4 == 0 && vr_aligned16(w) && p.CN > 32 && !kscale,
-                 "conv2d: the bf16 path needs 16-byte aligned rows, a contraction that is a multiple of 4, more than 32 "
-                 "output channels and (mode 1) the transposed weight pack with kscale folded in");
-    p.perm2 = 0;
-    p.pair_rows = pair_rows;
-    vr_igemm_bf16_launch(&p, mode, st);
-    vr_note_kernel(3);
-    VR_LAUNCH_CHECK("conv2d(bf16)");
-    return VR_OK;
-  }
-  const bool vec = p.a_vec && p.b_vec;
-  static const int use_dma = vr_tune("VRNET_IGEMM_DMA", 1);   // tuning aid
-  const long ktot = (long)p.CK * kh * kw;
-  const bool dma_ok = use_dma && vec && p.CN > 32 && (!kscale || p.CK <= 1024);
-  // 64 x 64 ring tiles where the grid cannot fill the chip with 8 workgroups per CU (M <= 8192 pixels: +5..40 %) and
-  // on long contractions; the register-staged kernel keeps the large-M, short-K layers (2048 row tiles x few K steps:
-  // its 8 workgroups per CU hide the store-heavy epilogues better).  128 x 128 ring tiles (T = 2) were measured on the
-  // large-M layers with >= 768 such tiles: 4-11 % slower than either (K <= 256 there: prologue / epilogue bound), so
-  // they are not dispatched.  All measured with bench.py --detail.
-  const bool dma_shape = use_dma == 2 || M <= 8192 || (M <= 32768 && ktot >= 1024);
-  // precision 2 (x6): 128 x 128 x 16 ring tiles with 2 x 2 accumulators per wave -- each split fragment feeds two
-  // MFMA groups, which is what pays for the split (on 64 x 64 tiles the conversions cost what the faster MFMA saves)
-  const bool bf16_tiles = precision == 3 || (precision == 1 && mode == 0);   // (mode 1 at precision 1 brings the transposed pack)
-  if ((precision == 2 || bf16_tiles) && dma_ok && (!pair_rows || p.pair_rows % 128 == 0)) {
-    const long mt = vr_cdiv(M, 128), nt22 = vr_cdiv(p.CN, 128), nt21 = vr_cdiv(p.CN, 64);
-    int S = 1;
-    // (the bf16-rounded tiles of precision 1 / 3 keep the unsplit rule: their callers asked vrnet_conv2d_dma_tile)
-    // contraction length that counts for the split: only taps that reach the image for at least one row (a 3 x 3 conv with
-    // dilation 18 on a 16 x 16 map is its centre tap)
-    long k_live = ktot;
-    if (kh * kw > 1) {
-      auto live = [&](int k, int n_m, int n_s) {
-        int c = 0;
-        for (int t = 0; t < k; ++t) {
-          bool any = false;
-          for (int o = 0; o < n_m && !any; ++o) {
-            if (mode == 0) {
-              const int sidx = o * stride - pad + t * dil;
-              any = sidx >= 0 && sidx < n_s;
-            } else {
-              const int tt = o + pad - t * dil;
-              any = tt >= 0 && tt % stride == 0 && tt / stride < n_s;
-            }
-          }
-          c += any;
-        }
-        return c;
-      };
-      k_live = (long)p.CK * live(kh, p.MH, p.SH) * live(kw, p.MW, p.SW);
-    }
-    const int tile = precision == 2 ? vr_dma_plan(M, p.CN, k_live, workspace ? workspace_bytes : 0, &S) : vr_dma_tile(M, p.CN);
-    if (S > 1) { p.ksplit = S; p.kslab = reinterpret_cast<float*>(workspace); }
-#define VR_TILE_LAUNCH(PR)                                                                                              \
-  do {                                                                                                                  \
-    if (tile == 22) {                                                                                                   \
-      dim3 grid((unsigned)(8 * vr_cdiv(mt, 8) * nt22));                                                                 \
-      if (mode == 0) hipLaunchKernelGGL((igemm_dma_kernel<0, 3, 2, 2, PR>), grid, block, 0, st, p, (int)mt, (int)nt22); \
-      else hipLaunchKernelGGL((igemm_dma_kernel<1, 3, 2, 2, PR>), grid, block, 0, st, p, (int)mt, (int)nt22);           \
-    } else {                                                                                                            \
-      dim3 grid((unsigned)(8 * vr_cdiv(mt, 8) * nt21 * S));                                                             \
-      if (mode == 0) hipLaunchKernelGGL((igemm_dma_kernel<0, 3, 2, 1, PR>), grid, block, 0, st, p, (int)mt, (int)nt21); \
-      else hipLaunchKernelGGL((igemm_dma_kernel<1, 3, 2, 1, PR>), grid, block, 0, st, p, (int)mt, (int)nt21);           \
-      if (S > 1)                                                                                                        \
-        hipLaunchKernelGGL((igemm_splitk_finish_kernel<2, 1, 2, 2>), dim3((unsigned)(8 * vr_cdiv(mt, 8) * nt21)), block, 0, st, \
-                           p, (int)mt, (int)nt21);                                                                      \
-    }                                                                                                                   \
-  } while (0)
-    if (tile && precision == 2 && w_planes && kh == 1 && kw == 1 && stride == 1 && pad == 0 && !pair_rows && p.CK % 16 == 0 &&
-        vr_tune("VRNET_X6_PLANES", 1)) {
-      // pre-split weights (vrnet_conv_planes_pack_f32; in mode 1 the pack holds the transposed weights with kscale folded in)
-      IgemmArgs q = p;
-      q.kscale = nullptr;
+  p.pair_rows = c.pair_rows; p.w2 = w2; p.bias2 = bias2; p.res_scale2 = res_scale2; p.kscale2 = kscale2;
+  if (c.S > 1) { p.ksplit = c.S; p.kslab = reinterpret_cast<float*>(workspace); }
+  const dim3 block(256), grid(c.grid_x, c.grid_y), finish(c.finish_grid ? c.finish_grid : 1);
+  const bool vec = c.a_vec && c.b_vec;
+  switch (c.kernel) {
+    case CONV_BF16:
+      vr_igemm_bf16_launch(&p, mode, st);
+      VR_LAUNCH_CHECK("conv2d(bf16)");
+      return VR_OK;
+    case CONV_PLANES: {
+      IgemmArgs pq = p;
+      pq.kscale = nullptr;
       const int JB = (int)(((p.CN + 127) >> 7) << 1);
+      const unsigned char* planes = reinterpret_cast<const unsigned char*>(w_planes);
       // (two further forms of this GEMM -- A fragments from global memory, B resident in LDS -- were faster alone and neutral to
       // +0.2 ms in the step: DESIGN 3.1)
-      if (tile == 22) {
-        dim3 grid((unsigned)(8 * vr_cdiv(mt, 8) * nt22));
+      if (c.tile == 22) {
         // 128 x 128 tile: two stages (40 KB, 3 workgroups per CU) measured 0.2 ms per step ahead of three (60 KB, 2 per CU)
-        hipLaunchKernelGGL((igemm_planes_kernel<2, 2>), grid, block, 0, st, q, reinterpret_cast<const unsigned char*>(w_planes), JB,
-                           (int)mt, (int)nt22);
+        hipLaunchKernelGGL((igemm_planes_kernel<2, 2>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
       } else {
-        dim3 grid((unsigned)(8 * vr_cdiv(mt, 8) * nt21 * S));
-        hipLaunchKernelGGL((igemm_planes_kernel<1, 3>), grid, block, 0, st, q, reinterpret_cast<const unsigned char*>(w_planes), JB,
-                           (int)mt, (int)nt21);
-        if (S > 1)
-          hipLaunchKernelGGL((igemm_splitk_finish_kernel<1, 2, 4, 1>), dim3((unsigned)(8 * vr_cdiv(mt, 8) * nt21)), block, 0, st, q,
-                             (int)mt, (int)nt21);
+        hipLaunchKernelGGL((igemm_planes_kernel<1, 3>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
+        if (c.S > 1) hipLaunchKernelGGL((igemm_splitk_finish_kernel<1, 2, 4, 1>), finish, block, 0, st, pq, c.mt, c.nt);
       }
-      vr_note_kernel(9);
       VR_LAUNCH_CHECK("conv2d(x6, pre-split weights)");
       return VR_OK;
     }
-    if (tile) {
-      if (precision == 2) VR_TILE_LAUNCH(6);
-      else VR_TILE_LAUNCH(1);
-      vr_note_kernel(precision == 2 ? 6 : 3);
+#define VR_TILE_LAUNCH(PR)                                                                                          \
+  do {                                                                                                              \
+    if (c.tile == 22) {                                                                                             \
+      if (mode == 0) hipLaunchKernelGGL((igemm_dma_kernel<0, 3, 2, 2, PR>), grid, block, 0, st, p, c.mt, c.nt);     \
+      else hipLaunchKernelGGL((igemm_dma_kernel<1, 3, 2, 2, PR>), grid, block, 0, st, p, c.mt, c.nt);               \
+    } else {                                                                                                        \
+      if (mode == 0) hipLaunchKernelGGL((igemm_dma_kernel<0, 3, 2, 1, PR>), grid, block, 0, st, p, c.mt, c.nt);     \
+      else hipLaunchKernelGGL((igemm_dma_kernel<1, 3, 2, 1, PR>), grid, block, 0, st, p, c.mt, c.nt);               \
+      if (c.S > 1) hipLaunchKernelGGL((igemm_splitk_finish_kernel<2, 1, 2, 2>), finish, block, 0, st, p, c.mt, c.nt); \
+    }                                                                                                               \
+  } while (0)
+    case CONV_X6:
+      VR_TILE_LAUNCH(6);
       VR_LAUNCH_CHECK("conv2d(dma tiles)");
       return VR_OK;
-    }
+    case CONV_BF16_TILE:
+      VR_TILE_LAUNCH(1);
+      VR_LAUNCH_CHECK("conv2d(dma tiles)");
+      return VR_OK;
 #undef VR_TILE_LAUNCH
+    case CONV_RING:
+      // (rings of 4 / 6 stages for launches with <= 2 / 1 workgroups per CU were measured: 3-10 % slower -- the stage
+      // time there is not DMA latency but per-stage issue overhead, see the interleaved issue in the kernel)
+      if (mode == 0) hipLaunchKernelGGL((igemm_dma_kernel<0, 3, 1, 1>), grid, block, 0, st, p, c.mt, c.nt);
+      else hipLaunchKernelGGL((igemm_dma_kernel<1, 3, 1, 1>), grid, block, 0, st, p, c.mt, c.nt);
+      VR_LAUNCH_CHECK("conv2d");
+      return VR_OK;
+    default:
+      break;
   }
-  VR_CHECK_ARG(precision != 3, "conv2d: precision 3 (bf16-rounded operands on the LDS-DMA tiles, standard weight layout) has "
-                               "no kernel for this shape / alignment: ask vrnet_conv2d_dma_tile first");
-  if (dma_ok && dma_shape) {
-    const int MT = (int)vr_cdiv(M, 64), NT = (int)vr_cdiv(p.CN, 64);
-    dim3 grid((unsigned)(8 * vr_cdiv(MT, 8) * NT));
-    // (rings of 4 / 6 stages for launches with <= 2 / 1 workgroups per CU were measured: 3-10 % slower -- the stage
-    // time there is not DMA latency but per-stage issue overhead, see the interleaved issue in the kernel)
-    if (mode == 0) hipLaunchKernelGGL((igemm_dma_kernel<0, 3, 1, 1>), grid, block, 0, st, p, MT, NT);
-    else hipLaunchKernelGGL((igemm_dma_kernel<1, 3, 1, 1>), grid, block, 0, st, p, MT, NT);
-    vr_note_kernel(2);
-    VR_LAUNCH_CHECK("conv2d");
-    return VR_OK;
-  }
-  // Register-staged tiles: 64 x 64 by default; 128 x 64 for narrow outputs over long contractions; 128 x 32 for <= 32 columns.
-  // Measured on MI355X over every conv shape of the net (phi = l, bs 8, 512 px; profiles/r01_igemm_tile_sweep.txt): 64 x 64
-  // tiles (7 workgroups per CU) beat 128 x 128 (2 per CU) and 128 x 64 on 90 % of the shapes -- 21.4 vs 30.7 / 25.9 ms per
-  // step over all forward + data-gradient launches; the exceptions are within 10 %.  BK = 32 measured 3 % slower.
-#define VR_IGEMM(BM_, BN_, TM_, TN_, WM_, WN_, GRID)                                                                   \
+#define VR_IGEMM(BM_, BN_, TM_, TN_, WM_, WN_)                                                                         \
   do {                                                                                                                  \
     if (mode == 0) {                                                                                                    \
-      if (vec) hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 0, true>), GRID, block, 0, st, p);    \
-      else hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 0, false>), GRID, block, 0, st, p);       \
+      if (vec) hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 0, true>), grid, block, 0, st, p);    \
+      else hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 0, false>), grid, block, 0, st, p);       \
     } else {                                                                                                            \
-      if (vec) hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 1, true>), GRID, block, 0, st, p);    \
-      else hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 1, false>), GRID, block, 0, st, p);       \
+      if (vec) hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 1, true>), grid, block, 0, st, p);    \
+      else hipLaunchKernelGGL((igemm_kernel<BM_, BN_, 16, TM_, TN_, WM_, WN_, 1, false>), grid, block, 0, st, p);       \
     }                                                                                                                   \
   } while (0)
-  static const int narrow = vr_tune("VRNET_IGEMM_NARROW", 1);   // tuning aid
-  if (p.CN <= 32) {
-    VR_IGEMM(128, 32, 1, 1, 4, 1, dim3(vr_cdiv(M, 128), 1));
-  } else if (narrow && vec && p.CN <= 192 && ktot >= 512) {
-    VR_IGEMM(128, 64, 2, 1, 2, 2, dim3(vr_cdiv(M, 128), vr_cdiv(p.CN, 64)));
-  } else {
-    VR_IGEMM(64, 64, 1, 1, 2, 2, dim3(vr_cdiv(M, 64), vr_cdiv(p.CN, 64)));
-  }
+  if (c.tile == 128032) VR_IGEMM(128, 32, 1, 1, 4, 1);
+  else if (c.tile == 128064) VR_IGEMM(128, 64, 2, 1, 2, 2);
+  else VR_IGEMM(64, 64, 1, 1, 2, 2);
 #undef VR_IGEMM
-  vr_note_kernel(1);
   VR_LAUNCH_CHECK("conv2d");
   return VR_OK;
 }

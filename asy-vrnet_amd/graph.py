@@ -16,10 +16,31 @@ the plain `model(x, r)` path stays available for those.
 `TrainStep` is the whole training step on top of that: the real loss on targets in static buffers, the optimizer step and
 the EMA update as one more graph, and the epoch's loss statistics, without a host synchronisation.
 """
+import contextlib
+import gc
+
 import numpy as np
 import torch
 
 from . import data, hip, losses, metrics, program
+
+
+@contextlib.contextmanager
+def collector_held_off():
+    """Around a stream capture: no run of Python's cycle collector inside it.  A dead reference cycle that holds GPU objects of
+    an EARLIER capture (a CUDAGraph, tensors of its pool) is otherwise destroyed at whatever allocation trips the collector's
+    counter -- between two captured launches, and the process was seen to abort there (GraphedStep._capture, under
+    program.backward_range, when the suite ran in another order).  torch.cuda.graph once collected before every capture and
+    now does so only with torch.compiler.config.force_cudagraph_gc: collect here, once, and hold the collector off until the
+    capture has ended."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def replay_segments(graphs, bucketer):
@@ -115,27 +136,28 @@ class GraphedStep:
             self.loss = loss.detach()
 
         bounds = None
-        for k in range(len(cuts) + 1):
-            g = torch.cuda.CUDAGraph()
-            # thread_local: with a process group alive, RCCL's watchdog thread polls its work events (hipEventQuery) at any
-            # moment; under the default "global" capture mode such a call from ANOTHER thread invalidates the capture
-            # (hipErrorStreamCaptureInvalidated) and raises in the watchdog, which aborts the process at exit
-            with torch.cuda.graph(g, pool=pool, stream=self.stream, capture_error_mode="thread_local"):
-                if k == 0:
-                    seg0()
-                    n = state["n"]
-                    bounds = [n] + [c for c in cuts if 0 < c < n] + [0]
-                rt = state["rt"]
-                if k + 1 < len(bounds):
-                    program.backward_range(rt, bounds[k + 1], bounds[k])
-                if k + 2 == len(bounds):
-                    program.backward_end(rt, model, state["inputs"], (False, False))
-                else:
-                    program.backward_cut(rt, final=False)
-            pool = g.pool()
-            self.graphs.append(g)
-            if k + 2 >= len(bounds):
-                break
+        with collector_held_off():
+            for k in range(len(cuts) + 1):
+                g = torch.cuda.CUDAGraph()
+                # thread_local: with a process group alive, RCCL's watchdog thread polls its work events (hipEventQuery) at any
+                # moment; under the default "global" capture mode such a call from ANOTHER thread invalidates the capture
+                # (hipErrorStreamCaptureInvalidated) and raises in the watchdog, which aborts the process at exit
+                with torch.cuda.graph(g, pool=pool, stream=self.stream, capture_error_mode="thread_local"):
+                    if k == 0:
+                        seg0()
+                        n = state["n"]
+                        bounds = [n] + [c for c in cuts if 0 < c < n] + [0]
+                    rt = state["rt"]
+                    if k + 1 < len(bounds):
+                        program.backward_range(rt, bounds[k + 1], bounds[k])
+                    if k + 2 == len(bounds):
+                        program.backward_end(rt, model, state["inputs"], (False, False))
+                    else:
+                        program.backward_cut(rt, final=False)
+                pool = g.pool()
+                self.graphs.append(g)
+                if k + 2 >= len(bounds):
+                    break
 
     def __call__(self, x, x_radar):
         self.x.copy_(x, non_blocking=True)
@@ -336,8 +358,8 @@ class TrainStep(GraphedStep):
             cur = torch.cuda.current_stream(self.device)
             self.stream.wait_stream(cur)
             self.update_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.update_graph, pool=self.graphs[-1].pool(), stream=self.stream,
-                                  capture_error_mode="thread_local"):
+            with collector_held_off(), torch.cuda.graph(self.update_graph, pool=self.graphs[-1].pool(), stream=self.stream,
+                                                        capture_error_mode="thread_local"):
                 opt.step(scalars=self.rec)
                 if self.ema is not None:
                     self.ema.update(model, scalars=self.rec)

@@ -45,6 +45,7 @@ _SIGS = {
     "vrnet_conv2d_dma_tile": ([L, I], I),
     "vrnet_conv2d_wgrad_workspace": ([I] * 8, L),
     "vrnet_conv2d_wgrad_plan": ([L] + [I] * 8 + [P], I),
+    "vrnet_conv2d_plan": ([I] * 14 + [L, L, I, L, P], I),
     "vrnet_conv2d_wgrad_f32": ([P, L, P, L, P, P, P] + [I] * 14 + [P, P, P, P, P, P, P, P, P, P, L, P], I),
     "vrnet_pack_weight_f32": ([P, P, I, I, I, I, P], I),
     "vrnet_mlp_fused_ok": ([I, I, L], I),
@@ -290,9 +291,10 @@ _ws = Workspace()
 def conv2d(a, lda, w, bias, y, ldy, B, H, W, Cin, OH, OW, Cout, kh, kw, stride, pad, dil, mode=0, act=0,
            ypre=None, ldypre=0, res=None, ldres=0, res_scale=None, kscale=None, aux=None, ldaux=0,
            out_nchw=0, out_ctot=0, out_coff=0, accumulate=0, stats=None, precision=0, pair_rows=0, w2=None, bias2=None,
-           res_scale2=None, kscale2=None, colstats=None, w_planes=None):
+           res_scale2=None, kscale2=None, colstats=None, w_planes=None, workspace=None):
     """pair_rows > 0: two-stream launch, GEMM rows >= pair_rows use (w2, bias2, res_scale2, kscale2).
-    colstats = (partial, x2, ldx2, gamma, tile_totals) (None entries allowed): column statistics of the stored outputs."""
+    colstats = (partial, x2, ldx2, gamma, tile_totals) (None entries allowed): column statistics of the stored outputs.
+    workspace (a uint8 tensor): the split workspace of the call, all of it, instead of this stream's scratch arena."""
     cs = None
     if colstats is not None:
         part, x2, ldx2, gam, tot = colstats
@@ -304,6 +306,8 @@ def conv2d(a, lda, w, bias, y, ldy, B, H, W, Cin, OH, OW, Cout, kh, kw, stride, 
         wsb = _lib.vrnet_conv2d_splitk_workspace(rows, cols, ktot)
         if wsb:
             ws = _ws.get(wsb, a.device)
+    if workspace is not None:
+        ws, wsb = workspace, workspace.numel() * workspace.element_size()
     _check(_lib.vrnet_conv2d_f32(ptr(a), lda, ptr(w), ptr(bias), ptr(y), ldy, B, H, W, Cin, OH, OW, Cout, kh, kw,
                                  stride, pad, dil, mode, act, ptr(ypre), ldypre, ptr(res), ldres, ptr(res_scale),
                                  ptr(kscale), ptr(aux), ldaux, out_nchw, out_ctot, out_coff, accumulate, ptr(stats),
@@ -443,6 +447,24 @@ def conv2d_wgrad_plan(rows, Cin, Cout, taps, ident, vec, precision=0, has_bias=T
     out = (ctypes.c_int * 8)()
     _check(_lib.vrnet_conv2d_wgrad_plan(rows, Cin, Cout, taps, int(ident), int(vec), precision, int(has_bias), int(has_dls), out),
            "conv2d_wgrad_plan")
+    return tuple(out)
+
+
+CONV_PLAN_FLAGS = dict(a=1, w=2, y=4, bias=8, ypre=16, res=32, res_scale=64, aux=128)
+
+
+def conv2d_plan(B, H, W, Cin, OH, OW, Cout, kh, kw, stride, pad, dil, mode=0, precision=0, lda=None, ldy=None, misaligned=(),
+                kscale=False, plain=False, out_nchw=False, stats=False, colstats=False, w_planes=False, workspace_bytes=0):
+    """(family, kernel, tile, S, k_live, perm2, a_vec, b_vec, e_vec, grid x, grid y, finish grid) of a single-stream conv2d call
+    (vrnet_conv2d_plan in include/vrnet_hip.h; a host call).  lda, ldy default to the channel counts; misaligned: names of
+    CONV_PLAN_FLAGS whose operand is given and not on 16-byte rows; plain: no fused epilogue operand (ypre, res, kscale, aux,
+    act).  Raises where conv2d refuses the call."""
+    ck, cn = (Cin, Cout) if mode == 0 else (Cout, Cin)
+    flags = sum(v for k, v in CONV_PLAN_FLAGS.items() if k not in misaligned)
+    flags |= 256 * bool(kscale) | 512 * bool(plain) | 1024 * bool(out_nchw) | 2048 * bool(stats) | 4096 * bool(colstats) | 8192 * bool(w_planes)
+    out = (ctypes.c_int * 12)()
+    _check(_lib.vrnet_conv2d_plan(B, H, W, Cin, OH, OW, Cout, kh, kw, stride, pad, dil, mode, precision, ck if lda is None else lda,
+                                  cn if ldy is None else ldy, flags, workspace_bytes, out), "conv2d_plan")
     return tuple(out)
 
 

@@ -307,7 +307,8 @@ class FramePipeline:
         self.stream = torch.cuda.Stream(self.device)    # warm-up AND capture run here: the scratch arenas of hip.Workspace are
         self._warm_up(2, self.stream)                   # keyed by stream, so they exist before the capture, in no graph pool
         self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
+        from .graph import collector_held_off
+        with collector_held_off(), torch.no_grad(), torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
             self.result = self._chain()
 
     def run(self, frames_u8, radar, sizes=None):

@@ -107,6 +107,28 @@ int vrnet_conv2d_f32(const float* a, long lda, const float* w, const float* bias
  * vrnet_conv2d_dma_plan: the tile (as vrnet_conv2d_dma_tile, or 21 for a split launch) and *splits. */
 long vrnet_conv2d_splitk_workspace(long rows, int cols, long ktot);
 int vrnet_conv2d_dma_plan(long rows, int cols, long ktot, int* splits);
+/* What vrnet_conv2d_f32 launches for a single-stream call (pair_rows = 0): a host-only query, answered by the function the
+ * launcher itself dispatches on.  Geometry, mode, precision and the row strides lda, ldy as in vrnet_conv2d_f32;
+ * workspace_bytes: the split workspace the call would be given (0: none).  flags, one bit per condition the dispatch reads:
+ *      1 a      2 w      4 y        16-byte aligned bases
+ *      8 bias  16 ypre  32 res  64 res_scale  128 aux    absent, or an aligned base and (ypre, res, aux) a row stride % 4 == 0
+ *    256 kscale given           512 no fused epilogue operand: no ypre, res, kscale, aux, act
+ *   1024 out_nchw              2048 stats given          4096 colstats given          8192 w_planes given
+ * out[12]:
+ *   0 family   what vrnet_last_kernel reports after the call
+ *   1 kernel   0 igemm_kernel (tile 128032 / 128064 / 64064 = rows x columns per workgroup), 1 the fp32 LDS-DMA ring
+ *              igemm_dma_kernel<mode, 3, 1, 1> (64064), 2 the x6 tile kernels (tile 22 = 128 x 128, 21 = 128 x 64), 3 the same
+ *              tiles on bf16-rounded operands, 4 igemm_planes_kernel on pre-split weights (22 / 21), 5 igemm_bf16_kernel
+ *              (64064), 6 the tiny-channel kernels, 7 the narrow-output kernels, 8 the patch data gradient (6-8: the rest is 0)
+ *   2 tile     3 S   splits of the contraction (> 1: igemm_splitk_finish_kernel follows)
+ *   4 k_live   the contraction length that counts for the split: taps that reach the image for at least one row
+ *   5 perm2    parity-major rows of a stride-2 data gradient
+ *   6 a_vec    7 b_vec   16-byte loaders of the activation / weight operand      8 e_vec   vector epilogue
+ *   9 grid x  10 grid y  11 workgroups of the finish kernel (0: none)
+ * Returns non-zero where vrnet_conv2d_f32 refuses the call (precision 1 / 3 without a kernel for the shape or alignment,
+ * statistics without the vector epilogue, bad geometry), with the launcher's message. */
+int vrnet_conv2d_plan(int B, int H, int W, int Cin, int OH, int OW, int Cout, int kh, int kw, int stride, int pad, int dil,
+                      int mode, int precision, long lda, long ldy, int flags, long workspace_bytes, int* out);
 /* Pre-split weights for the x6 kernels (precision 2, 1x1 convs, contraction % 16 == 0): the six-product scheme spends its
  * VALU time on splitting fragments into bf16 planes; weights are the same for every row tile of a step, so they can be
  * split ONCE per step.  vrnet_conv_planes_pack_f32 does that for a whole table of weights in one launch (round-to-nearest-
