@@ -17,6 +17,7 @@
 #include "igemm_common.h"
 #include "x6.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -757,9 +758,207 @@ __global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) v
   else igemm_epilogue<TM, TNW, 4, 1>(p, acc, reinterpret_cast<float*>(smem), m0, n0);
 }
 
+// The same GEMM for k x k convs (stride, padding, dilation; both directions) on pre-split weights: the pack holds one 1x1-style
+// image per tap, tap t at K16 steps [t * CK / 16, (t + 1) * CK / 16) of one buffer, so the contraction order is (tap, channel) as
+// in igemm_dma_kernel and a stage's B tile is still one contiguous 6 KB (x TN) block.  The A loader is the implicit-GEMM gather
+// of igemm_dma_kernel: a slot's source row is recomputed when the K loop crosses a tap, rows whose tap lies in the padding (or,
+// in a strided data gradient, between the output pixels) read the zero page, and taps that no row of the tile reaches are
+// skipped.  The live taps are a block-uniform 32-bit mask, reduced once through the first word of the (still empty) ring and
+// walked with scalar bit operations: no LDS beyond the ring.  Ring, waits, MFMA loop, split contraction and epilogue are those
+// of igemm_planes_kernel.
+template <int TN, int NST>
+__global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) void igemm_planes_kxk_kernel(const IgemmArgs p,
+                                                                                                          const unsigned char* planes,
+                                                                                                          int JB, int MT, int NT) {
+  constexpr int TM = 1, TNW = 2 * TN, BM = 128, BN = 64 * TN, BK = 16;
+  constexpr int A_BYTES = BM * BK * 4, B_BYTES = TN * 6144, ST_BYTES = A_BYTES + B_BYTES;
+  constexpr int NA = A_BYTES / 1024 / 4;
+  static_assert(NST * ST_BYTES >= 4 * 32 * STAGE_LD * 4, "epilogue staging must fit the ring");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[NST * ST_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const float* zero_page = vr_zero_page;
+  asm volatile("" : "+s"(zero_page));
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int GT = 8 * ((MT + 7) >> 3) * NT;
+  const int split = __builtin_amdgcn_readfirstlane(p.ksplit > 1 ? (int)blockIdx.x / GT : 0);
+  const int L = blockIdx.x - split * GT, jj = L >> 3;
+  const int nt = jj % NT, mt = (jj / NT) * 8 + (L & 7);
+  if (mt >= MT) return;
+  const int m0 = mt * BM, n0 = nt * BN;
+  const int nkb = p.CK / BK, TAPS = p.kh * p.kw;
+  const int NBW = TN == 2 ? 3 : (wave < 2 ? 2 : 1);
+
+  // ---- A loader roles: slot (row, quad) of the 128 x 16 fp32 image; per row the sample's first source row and the
+  // tap-independent part of the source coordinates (a row beyond M gets a y no tap brings into the image)
+  int a_c[NA], a_base[NA], a_py[NA], a_px[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const int sl = (wave * NA + i) * 64 + lane, r = sl >> 2;
+    a_c[i] = 4 * ((sl & 3) ^ ((r >> 2) & 3));
+    const int m = m0 + r;
+    int b, y, x;
+    igemm_row_to_pixel(p, m < p.M ? m : 0, b, y, x);
+    a_base[i] = b * p.SH * p.SW;
+    a_py[i] = m < p.M ? (p.mode == 0 ? y * p.stride - p.pad : y + p.pad) : -(1 << 24);
+    a_px[i] = p.mode == 0 ? x * p.stride - p.pad : x + p.pad;
+  }
+  auto src_row = [&](int i, int ky, int kx) -> int {      // source row of slot i under tap (ky, kx), -1: none
+    int sy, sx;
+    if (p.mode == 0) {
+      sy = a_py[i] + ky * p.dil;
+      sx = a_px[i] + kx * p.dil;
+    } else {
+      const int ty = a_py[i] - ky * p.dil, tx = a_px[i] - kx * p.dil;
+      if (ty < 0 || tx < 0 || (ty % p.stride) != 0 || (tx % p.stride) != 0) return -1;
+      sy = ty / p.stride;
+      sx = tx / p.stride;
+    }
+    if (sy < 0 || sy >= p.SH || sx < 0 || sx >= p.SW) return -1;
+    return a_base[i] + sy * p.SW + sx;
+  };
+  unsigned live;      // taps that reach the image for at least one row of this tile (TAPS <= 32)
+  {
+    unsigned mine = 0u;
+    for (int t = 0; t < TAPS; ++t) {
+      const int ky = t / p.kw, kx = t - ky * p.kw;
+#pragma unroll
+      for (int i = 0; i < NA; ++i)
+        if (src_row(i, ky, kx) >= 0) mine |= 1u << t;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine |= (unsigned)__shfl_xor((int)mine, o, 64);
+    unsigned* mask_s = reinterpret_cast<unsigned*>(smem);
+    if (tid == 0) *mask_s = 0u;
+    __syncthreads();
+    if (lane == 0 && mine) atomicOr(mask_s, mine);
+    __syncthreads();
+    live = (unsigned)__builtin_amdgcn_readfirstlane((int)*mask_s);
+    __syncthreads();      // the word belongs to the ring: every wave has read it before the first DMA is issued
+  }
+  const int nsteps_all = __popc(live) * nkb;
+  const int s_begin = p.ksplit > 1 ? (int)((long)split * nsteps_all / p.ksplit) : 0;
+  const int nsteps = (p.ksplit > 1 ? (int)((long)(split + 1) * nsteps_all / p.ksplit) : nsteps_all) - s_begin;
+
+  const float* a_run[NA];
+  int a_inc[NA];
+  const long b_step = (long)JB * 6144;
+  const unsigned char* b_base = planes + ((long)(n0 >> 6)) * 6144 + (long)lane * 16;
+  const unsigned char* b_src = b_base;
+  unsigned rem = live;      // live taps not yet set up
+  auto setup_tap = [&]() {
+    const int t = rem ? __builtin_ctz(rem) : 0;
+    rem &= rem - 1;
+    const int ky = t / p.kw, kx = t - ky * p.kw;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int row = src_row(i, ky, kx);
+      a_run[i] = row >= 0 ? p.a + (long)row * p.lda + a_c[i] : zero_page;
+      a_inc[i] = row >= 0 ? BK : 0;
+    }
+    b_src = b_base + (long)t * nkb * b_step;
+  };
+  int ld_kb = s_begin - (s_begin / nkb) * nkb, ld_buf = 0;      // (k block, ring slot) of the NEXT stage to issue
+  for (int i = 0; i < s_begin / nkb; ++i) rem &= rem - 1;
+  if (ld_kb != 0 && nsteps > 0) {      // a split that starts inside a tap
+    setup_tap();
+#pragma unroll
+    for (int i = 0; i < NA; ++i) a_run[i] += (long)ld_kb * a_inc[i];
+    b_src += ld_kb * b_step;
+  }
+  auto issue_begin = [&]() {
+    if (ld_kb == 0) setup_tap();
+  };
+  auto issue_piece = [&](int i) {
+    unsigned char* stage = smem + ld_buf * ST_BYTES;
+    if (i < NA) {
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a_run[i],
+                                       (__attribute__((address_space(3))) void*)(stage + (wave * NA + i) * 1024), 16, 0, 0);
+      a_run[i] += a_inc[i];
+    } else if (i - NA < NBW) {
+      const int j = i - NA;
+      const int piece = TN == 2 ? wave * 3 + j : (wave < 2 ? wave * 2 + j : 2 + wave);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src + piece * 1024),
+                                       (__attribute__((address_space(3))) void*)(stage + A_BYTES + piece * 1024), 16, 0, 0);
+    }
+  };
+  auto issue_end = [&]() {
+    b_src += b_step;
+    if (++ld_kb == nkb) ld_kb = 0;
+    if (++ld_buf == NST) ld_buf = 0;
+  };
+  constexpr int NPMAX = NA + (TN == 2 ? 3 : 2);
+  auto issue = [&]() {
+    issue_begin();
+#pragma unroll
+    for (int i = 0; i < NPMAX; ++i) issue_piece(i);
+    issue_end();
+  };
+
+  f32x16 acc[TM][TNW];
+#pragma unroll
+  for (int j = 0; j < TNW; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
+  const int h = lane >> 5;
+  const int ra = wave * 32 + (lane & 31);
+  const int a_off = ra * BK * 4, a_swz = (ra >> 2) & 3;
+  int b_off[TNW];
+#pragma unroll
+  for (int i = 0; i < TNW; ++i) {
+    const int rb = 32 * i + (lane & 31);
+    b_off[i] = ((rb >> 6) * 6 + h) * 1024 + (rb & 63) * 16;       // + plane * 2048
+  }
+
+#pragma unroll
+  for (int st = 0; st < NST - 1; ++st)
+    if (st < nsteps) issue();
+  int cur = 0;
+  for (int s = 0; s < nsteps; ++s) {
+    if (NST >= 3 && nsteps - 1 - s >= 1) {       // one younger stage stays in flight
+      if (TN == 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      else if (wave < 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    const bool more = s + NST - 1 < nsteps;      // the next stage goes into the slot every wave finished reading before this barrier
+    if (more) issue_begin();
+    const unsigned char* As = smem + cur * ST_BYTES;
+    const unsigned char* Bs = As + A_BYTES;
+    vr_bf16x8 a3[3], b3[TNW][3];
+#pragma unroll
+    for (int i = 0; i < TNW; ++i)
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) b3[i][pl] = *reinterpret_cast<const vr_bf16x8*>(Bs + b_off[i] + pl * 2048);
+    {
+      f32x4 lo = *reinterpret_cast<const f32x4*>(As + a_off + 16 * ((2 * h) ^ a_swz));
+      f32x4 hi = *reinterpret_cast<const f32x4*>(As + a_off + 16 * ((2 * h + 1) ^ a_swz));
+      vr_split3(lo, hi, a3);
+    }
+#pragma unroll
+    for (int jn = 0; jn < TNW; ++jn) {
+      acc[0][jn] = vr_mfma_x6(a3, b3[jn], acc[0][jn]);
+      if (more) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < NPMAX; ++q)
+          if (q % TNW == jn) issue_piece(q);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (more) issue_end();
+    if (++cur == NST) cur = 0;
+  }
+  __syncthreads();
+  if (p.ksplit > 1) igemm_splitk_store<TM, TNW>(p, acc, GT, L, split);
+  else igemm_epilogue<TM, TNW, 4, 1>(p, acc, reinterpret_cast<float*>(smem), m0, n0);
+}
+
 // Multi-tensor weight split: one launch for every eligible weight of a step.  Table entry e (8 longs): source address,
-// columns J, contraction K, element strides (column, contraction), contraction-scale address or 0, destination address,
-// first block.  Block = (entry, k16 step, 64-column block); thread = (lane half, column): 8 values -> 3 x 8 bf16.
+// columns J (+ 2^32: split by truncation instead of round-to-nearest-even), contraction K, element strides (column,
+// contraction), contraction-scale address or 0, destination address, first block.  Block = (entry, k16 step, 64-column block); thread = (lane half, column): 8 values -> 3 x 8 bf16.
 __global__ __launch_bounds__(128) void planes_pack_kernel(const long* table, int nentries) {
   int e = 0;
   {   // the entry this block belongs to: first-block offsets ascend
@@ -773,6 +972,7 @@ __global__ __launch_bounds__(128) void planes_pack_kernel(const long* table, int
   const long* t = table + 8 * e;
   const float* src = reinterpret_cast<const float*>(t[0]);
   const int J = (int)t[1], K = (int)t[2];
+  const bool trunc = (t[1] >> 32) & 1;      // bit 32 of the columns field: split by truncation, the planes vr_split3 makes
   const long sj = t[3], sk = t[4];
   const float* ksc = reinterpret_cast<const float*>(t[5]);
   unsigned short* dst = reinterpret_cast<unsigned short*>(t[6]);
@@ -790,6 +990,21 @@ __global__ __launch_bounds__(128) void planes_pack_kernel(const long* table, int
     v[i] = x;
   }
   unsigned short* d = dst + ((long)(kb * JB + jb) * 6144 + hh * 1024 + col * 16) / 2;      // plane stride 2048 B
+  if (trunc) {
+    // The k x k launches split their weight fragments by truncation in igemm_dma_kernel (vr_split3) before they ran on planes:
+    // the same three planes here keep every product, and so every result of those launches, bit for bit what it was.
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const unsigned b0 = __builtin_bit_cast(unsigned, v[i]);
+      const float r1 = v[i] - __builtin_bit_cast(float, b0 & 0xffff0000u);
+      const unsigned b1 = __builtin_bit_cast(unsigned, r1);
+      const float r2 = r1 - __builtin_bit_cast(float, b1 & 0xffff0000u);
+      d[i] = (unsigned short)(b0 >> 16);
+      d[1024 + i] = (unsigned short)(b1 >> 16);
+      d[2048 + i] = (unsigned short)(__builtin_bit_cast(unsigned, r2) >> 16);
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const __bf16 p0 = (__bf16)v[i];
@@ -1517,7 +1732,7 @@ enum ConvKernel {
   CONV_RING = 1,        // igemm_dma_kernel<mode, 3, 1, 1>: the fp32 LDS-DMA ring, 64 x 64              family 2
   CONV_X6 = 2,          // igemm_dma_kernel<mode, 3, 2, 2 / 1, 6>, tile 22 / 21 (+ the split finish)      family 6
   CONV_BF16_TILE = 3,   // igemm_dma_kernel<mode, 3, 2, 2 / 1, 1>: bf16-rounded operands, tile 22 / 21   family 3
-  CONV_PLANES = 4,      // igemm_planes_kernel<2, 2> / <1, 3> on pre-split weights (+ the split finish)   family 9
+  CONV_PLANES = 4,      // igemm_planes_kernel<2, 2> / <1, 3>, igemm_planes_kxk_kernel<1, 3> on pre-split weights (+ the split finish)   family 9
   CONV_BF16 = 5,        // igemm_bf16_kernel<mode> (igemm_bf16.hip), 64 x 64                              family 3
   CONV_TINY = 6,        // tinyconv.hip                                                                   family 4
   CONV_NARROW = 7,      // narrowconv.hip                                                                 family 5
@@ -1539,6 +1754,29 @@ struct ConvChoice {
   unsigned grid_x, grid_y, finish_grid;      // finish_grid: workgroups of igemm_splitk_finish_kernel (S > 1)
   int mt, nt;                                // row / column tiles of the ring and tile kernels
 };
+
+// Contraction length that counts for the split: CK times the taps that reach the image for at least one row.
+static long conv_k_live(const ConvQuery& q, int MH, int MW, int SH, int SW, int CK) {
+  if (q.kh * q.kw <= 1) return CK;
+  auto live = [&](int k, int n_m, int n_s) {
+    int n = 0;
+    for (int t = 0; t < k; ++t) {
+      bool any = false;
+      for (int o = 0; o < n_m && !any; ++o) {
+        if (q.mode == 0) {
+          const int sidx = o * q.stride - q.pad + t * q.dil;
+          any = sidx >= 0 && sidx < n_s;
+        } else {
+          const int tt = o + q.pad - t * q.dil;
+          any = tt >= 0 && tt % q.stride == 0 && tt / q.stride < n_s;
+        }
+      }
+      n += any;
+    }
+    return n;
+  };
+  return (long)CK * live(q.kh, MH, SH) * live(q.kw, MW, SW);
+}
 
 static int conv_choose(const ConvQuery& q, ConvChoice* c) {
   *c = ConvChoice{};
@@ -1613,33 +1851,37 @@ static int conv_choose(const ConvQuery& q, ConvChoice* c) {
   // precision 2 (x6): 128 x 128 x 16 ring tiles with 2 x 2 accumulators per wave -- each split fragment feeds two
   // MFMA groups, which is what pays for the split (on 64 x 64 tiles the conversions cost what the faster MFMA saves)
   const bool bf16_tiles = precision == 3 || (precision == 1 && mode == 0);   // (mode 1 at precision 1 brings the transposed pack)
+  // A k x k conv whose caller brings pre-split weights (one pack image per tap) runs on igemm_planes_kxk_kernel, 128 x 64 tiles,
+  // whatever the tile count: the caller has paid for the split and asks for this kernel, the rule that sends a launch with few
+  // tiles elsewhere is the caller's to apply (Runtime.planes_kxk of program.py brings planes only where this launch would have
+  // run on the x6 tiles anyway).  Not taken: contractions that are no multiple of 16, more than 32 taps (the kernel's tap mask),
+  // scalar loaders, two-stream launches, and the shapes vr_dma_plan gives the 128 x 128 tile (the gather's row state would cost
+  // 18 VGPRs over igemm_planes_kernel<2, 2>; no k x k launch of the net has the >= 512 such tiles) -- those run as without planes.
+  if (precision == 2 && q.planes && kh * kw > 1 && kh * kw <= 32 && use_dma && vec && !pair_rows && CK % 16 == 0 &&
+      vr_tune("VRNET_X6_PLANES", 1)) {
+    const long k_live = conv_k_live(q, MH, MW, SH, SW, CK);
+    int S = 1;
+    const int tile = vr_dma_plan(M, CN, k_live, q.ws_bytes, &S);
+    if (tile != 22) {
+      const long mt = vr_cdiv(M, 128), nt = vr_cdiv(CN, 64), gt = 8 * vr_cdiv(mt, 8) * nt;
+      if (!tile && q.ws_bytes > 0) {      // no tile by the rule: the split of vr_dma_plan without its floor of 192 workgroups
+        S = (int)std::min<long>(std::min<long>(vr_cdiv(512, mt * nt), k_live / 16 / 32), 8);
+        if (S < 2 || S * gt * 8192 * 4 > q.ws_bytes) S = 1;
+      }
+      c->k_live = k_live; c->tile = 21; c->S = S; c->mt = (int)mt; c->nt = (int)nt;
+      c->grid_x = (unsigned)(gt * S); c->grid_y = 1;
+      c->finish_grid = S > 1 ? (unsigned)gt : 0;
+      c->kernel = CONV_PLANES; c->family = 9;
+      return VR_OK;
+    }
+  }
   if ((precision == 2 || bf16_tiles) && dma_ok && (!pair_rows || c->pair_rows % 128 == 0)) {
     const long mt = vr_cdiv(M, 128), nt22 = vr_cdiv(CN, 128), nt21 = vr_cdiv(CN, 64);
     int S = 1;
     // (the bf16-rounded tiles of precision 1 / 3 keep the unsplit rule: their callers asked vrnet_conv2d_dma_tile)
     // contraction length that counts for the split: only taps that reach the image for at least one row (a 3 x 3 conv with
     // dilation 18 on a 16 x 16 map is its centre tap)
-    long k_live = ktot;
-    if (kh * kw > 1) {
-      auto live = [&](int k, int n_m, int n_s) {
-        int n = 0;
-        for (int t = 0; t < k; ++t) {
-          bool any = false;
-          for (int o = 0; o < n_m && !any; ++o) {
-            if (mode == 0) {
-              const int sidx = o * stride - q.pad + t * q.dil;
-              any = sidx >= 0 && sidx < n_s;
-            } else {
-              const int tt = o + q.pad - t * q.dil;
-              any = tt >= 0 && tt % stride == 0 && tt / stride < n_s;
-            }
-          }
-          n += any;
-        }
-        return n;
-      };
-      k_live = (long)CK * live(kh, MH, SH) * live(kw, MW, SW);
-    }
+    const long k_live = conv_k_live(q, MH, MW, SH, SW, CK);
     c->k_live = k_live;
     const int tile = precision == 2 ? vr_dma_plan(M, CN, k_live, q.ws_bytes, &S) : vr_dma_tile(M, CN);
     if (tile) {
@@ -1807,7 +2049,9 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
         // 128 x 128 tile: two stages (40 KB, 3 workgroups per CU) measured 0.2 ms per step ahead of three (60 KB, 2 per CU)
         hipLaunchKernelGGL((igemm_planes_kernel<2, 2>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
       } else {
-        hipLaunchKernelGGL((igemm_planes_kernel<1, 3>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
+        // k x k: the gathering sibling; its pack holds kh * kw images of JB x CK / 16 blocks
+        if (kh * kw > 1) hipLaunchKernelGGL((igemm_planes_kxk_kernel<1, 3>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
+        else hipLaunchKernelGGL((igemm_planes_kernel<1, 3>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
         if (c.S > 1) hipLaunchKernelGGL((igemm_splitk_finish_kernel<1, 2, 4, 1>), finish, block, 0, st, pq, c.mt, c.nt);
       }
       VR_LAUNCH_CHECK("conv2d(x6, pre-split weights)");
@@ -2217,7 +2461,8 @@ extern "C" long vrnet_conv_planes_bytes(int J, int K) { return (long)(K / 16) * 
 
 /* One launch that splits every weight of `table` (device array, 8 longs per entry: source address, J, K, element stride
  * between columns, element stride along the contraction, address of a per-contraction-index scale or 0, destination
- * address, index of the entry's first block; an entry has (K / 16) * 2 * ceil(J / 128) blocks) into three bf16 planes in the
+ * address, index of the entry's first block; columns + 2^32: the entry is split by truncation (the planes the x6 kernels make
+ * of a fragment they split themselves) instead of round-to-nearest-even; an entry has (K / 16) * 2 * ceil(J / 128) blocks) into three bf16 planes in the
  * stage-image order of igemm_planes_kernel.  total_blocks = sum of the entries' blocks. */
 extern "C" int vrnet_conv_planes_pack_f32(const long* table, int nentries, long total_blocks, void* stream) {
   VR_CHECK_ARG(table && nentries > 0 && total_blocks > 0 && total_blocks < (1L << 31), "conv_planes_pack: bad table");

@@ -12,8 +12,9 @@ namespace {
 // |a1| < 2^-7 |a| and |a2| < 2^-14 |a|: the dropped products a1b2 and a2b1 are each below 2^-21 |ab| (a2b2 below 2^-28)
 // and, the planes of a truncated operand all having its sign, carry the sign of ab -- a bias towards zero of at most
 // 2^-20 |ab| per product, about 2^-23 typically (the planes' leading bits are spread evenly), not zero-mean rounding noise.
-// The weights that are split once per step (planes_pack_kernel, mlp_pack_kernel) are split round-to-nearest-even, which
-// halves their side of it and makes it zero-mean; the activations are truncated in the kernels (2 VALU operations per
+// The 1x1 weights that are split once per step (planes_pack_kernel, mlp_pack_kernel) are split round-to-nearest-even, which
+// halves their side of it and makes it zero-mean (the k x k weights, which went onto planes later, keep the truncation of the
+// kernel that split them before: their launches give the bits they gave); the activations are truncated in the kernels (2 VALU operations per
 // plane instead of the 5 of an RNE split).  Measured against an fp64 matmul over the net's GEMM shapes the result is as
 // close as the fp32 MFMA's (profiles/r03_x6_vs_fp32_mfma_gemm_probe.txt), at 6 x 32 instead of 8 x 64 matrix-pipe cycles
 // per 32 x 32 x 16 block (v_mfma_f32_32x32x16_bf16 vs eight v_mfma_f32_32x32x2_f32).

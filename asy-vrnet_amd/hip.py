@@ -315,6 +315,11 @@ def conv2d(a, lda, w, bias, y, ldy, B, H, W, Cin, OH, OW, Cout, kh, kw, stride, 
            "conv2d")
 
 
+def conv2d_splitk_workspace(rows, cols, ktot):
+    """Bytes of split workspace conv2d gives a precision-2 call of rows x cols over a contraction of ktot (0: no split)."""
+    return _lib.vrnet_conv2d_splitk_workspace(rows, cols, ktot)
+
+
 def conv_planes_bytes(J, K):
     return _lib.vrnet_conv_planes_bytes(J, K)
 

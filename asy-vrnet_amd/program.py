@@ -420,6 +420,34 @@ class RT:
             return None
         return self.wplanes.dgrad(w, kscale) if mode else self.wplanes.fwd(w)
 
+    def planes_kxk(self, conv, mode, x, OH, OW, a, lda, y, ldy, kscale=None, plain=False):
+        """bf16 planes of a k x k conv's weight, one pack image per tap, for the single-stream hip.conv2d launch with activation
+        operand `a` (row stride lda) and NHWC output `y` (ldy) -- or None: the planes are switched off, or the launch's own plan
+        (hip.conv2d_plan on the same geometry, strides, alignments and workspace) answers neither the x6 tiles (family 6) without
+        planes nor the planes kernel (family 9) with them.  A launch that gets planes reads nothing else of the weight, so its
+        caller passes the OIHW tensor and skips the [T][Cout][Cin] pack."""
+        co, ci, kh, kw = conv.weight.shape
+        K = co if mode else ci
+        if self.wplanes is None or self.bf16 or self.fp32_precision != 2 or K % 16 or not 1 < kh * kw <= 32:
+            return None
+        if kscale is not None:       # (no k x k conv of the net has a layer scale behind it: such a launch keeps the kernel it had,
+            return None              # whose product with the scale is not known to round as the pack's does)
+        s, p, d = conv.stride[0], conv.padding[0], conv.dilation[0]
+        mis = tuple(n for n, t in (("a", a), ("y", y), ("w", conv.weight)) if t.data_ptr() % 16)
+        key = (conv, mode, x.B, x.H, x.W, lda, ldy, mis, kscale is not None, plain)
+        on = self.wplanes.plans.get(key)
+        if on is None:
+            rows, cols = (x.B * x.H * x.W, ci) if mode else (x.B * OH * OW, co)
+            plan = lambda w_planes: hip.conv2d_plan(x.B, x.H, x.W, ci, OH, OW, co, kh, kw, s, p, d, mode=mode, precision=2, lda=lda,
+                                                    ldy=ldy, misaligned=mis, kscale=kscale is not None, plain=plain, w_planes=w_planes,
+                                                    workspace_bytes=hip.conv2d_splitk_workspace(rows, cols, K * kh * kw))[0]
+            # (the library runs a k x k launch that brings planes on its planes kernel whatever the tile count; the rule that keeps
+            # launches with few tiles off the x6 tiles stays in force here: planes only where family 6 would have run)
+            on = self.wplanes.plans[key] = plan(False) == 6 and plan(True) == 9
+        if not on:
+            return None
+        return self.wplanes.dgrad(conv.weight, kscale) if mode else self.wplanes.fwd(conv.weight)
+
     def prec_wgrad(self, ldx, lddy, ci, co):
         if self.bf16 and hip.bf16_wgrad_ok(ldx, lddy, ci, co):
             return 1
@@ -586,9 +614,14 @@ def conv_call(rt, x, conv, out, act=0, ypre=None, res=None, res_scale=None, nchw
         if c1 is not None:
             kw2 = _pair_kw(rt, x, conv, rt.weight, bias, res_scale)
             kw2["pair_rows"] = (x.B // 2) * OH * OW
+        kxk = False
         if c1 is None and kh == 1 and kw == 1 and s == 1 and p == 0:
             kw2["w_planes"] = rt.planes(c0.weight, 0, co, ci, x.B * OH * OW)
-        hip.conv2d(x.t, x.ld, rt.weight(c0), b, out.t, out.ld, x.B, x.H, x.W, ci, OH, OW, co, kh, kw, s, p, d,
+        elif c1 is None:
+            kw2["w_planes"] = rt.planes_kxk(c0, 0, x, OH, OW, x.t, x.ld, out.t, out.ld,
+                                            plain=not (act or ypre is not None or res is not None or stats or "colstats" in kw2))
+            kxk = kw2["w_planes"] is not None      # every tap's weights come from the planes: no [T][Cout][Cin] pack
+        hip.conv2d(x.t, x.ld, c0.weight if kxk else rt.weight(c0), b, out.t, out.ld, x.B, x.H, x.W, ci, OH, OW, co, kh, kw, s, p, d,
                    mode=0, act=act, ypre=None if ypre is None else ypre.t, ldypre=0 if ypre is None else ypre.ld,
                    res=None if res is None else res.t, ldres=0 if res is None else res.ld,
                    res_scale=_pair(res_scale)[0] if res_scale is not None else None,
@@ -661,8 +694,15 @@ def conv_backward(rt, x, conv, dy, lddy, kscale=None, aux=None, row_scale=None, 
             ld = x.C
         ks0, ks1 = _pair(kscale) if kscale is not None else (None, None)
         rows = x.B * x.H * x.W if not isinstance(conv, tuple) or (x.B // 2) * x.H * x.W % 128 == 0 else None
-        wd, ks, prec = rt.dgrad_operands(c0, c0.weight, rt.weight(c0), co, ci, kh, kw, ks0, lddy, rows)
         kw2 = {}
+        wp = None
+        if c1 is None and kh * kw > 1:
+            wp = rt.planes_kxk(c0, 1, x, OH, OW, dy, lddy, buf, ld, kscale=ks0, plain=ks0 is None and aux is None)
+        if wp is not None:       # every tap's weights come from the planes: no [T][Cout][Cin] pack for this launch
+            wd, ks, prec = c0.weight, ks0, 2
+            kw2["w_planes"] = wp
+        else:
+            wd, ks, prec = rt.dgrad_operands(c0, c0.weight, rt.weight(c0), co, ci, kh, kw, ks0, lddy, rows)
         if c1 is not None:
             wd1, ks1, prec1 = rt.dgrad_operands(c1, c1.weight, rt.weight(c1), co, ci, kh, kw, ks1, lddy, rows)
             assert prec1 == prec
@@ -2076,23 +2116,28 @@ class SplitWeights:
         self.entries = {}          # key -> [source, J, K, sj, sk, kscale or None, destination, (source pointers)]
         self.table, self.nblocks, self.dirty, self.ents = None, 0, False, []
 
-    def get(self, key, w, J, K, sj, sk, kscale=None):
+    def get(self, key, w, J, K, sj, sk, kscale=None, taps=1):
+        """taps > 1: `taps` matrices of the same J x K shape and strides, matrix t at source element t and -- one table row each --
+        at destination `dest_row(dst, t, J, K)` (the per-tap images of a k x k conv weight), split by truncation as
+        igemm_dma_kernel splits the fragments of such a weight: the launch keeps its bits when it moves onto planes."""
         ent = self.entries.get(key)
         ids = (w.data_ptr(), None if kscale is None else kscale.data_ptr())
         if ent is not None and ent[7] == ids:
             return ent[6]
-        ent = [w, J, K, sj, sk, kscale, self.alloc(J, K), ids]
+        ent = [w, J, K, sj, sk, kscale, self.alloc(J, K * taps), ids, taps]      # (taps > 1: split by truncation, bit 32 of J)
         self.entries[key] = ent
         self.dirty = True
         tab, nb = self._table([ent])
-        self.split(tab, 1, nb)          # first use: split now (later forwards: refresh())
+        self.split(tab, taps, nb)          # first use: split now (later forwards: refresh())
         return ent[6]
 
     def _table(self, ents):
         rows, first = [], 0
-        for w, J, K, sj, sk, kscale, dst, _ in ents:
-            rows += [w.data_ptr(), J, K, sj, sk, 0 if kscale is None else kscale.data_ptr(), *self.dest_row(dst), first]
-            first += self.blocks(J, K)
+        for w, J, K, sj, sk, kscale, dst, _, taps in ents:
+            for t in range(taps):
+                rows += [w.data_ptr() + t * w.element_size(), J | (taps > 1) << 32, K, sj, sk, 0 if kscale is None else kscale.data_ptr(),
+                         *self.dest_row(dst, t, J, K), first]
+                first += self.blocks(J, K)
         return torch.tensor(rows, dtype=torch.int64, device=self.device), first
 
     def refresh(self):
@@ -2109,28 +2154,36 @@ class SplitWeights:
             self.ents = list(self.entries.values())
             self.table, self.nblocks = self._table(self.ents)
             self.dirty = False
-        self.split(self.table, len(self.ents), self.nblocks)
+        self.split(self.table, sum(e[8] for e in self.ents), self.nblocks)
 
     def fwd(self, w):
-        """planes of w[Cout][Cin] (a 1x1 conv weight or a 2-D matrix): the B operand of the forward GEMM."""
+        """planes of w[Cout][Cin] (a 1x1 conv weight or a 2-D matrix): the B operand of the forward GEMM.  A k x k weight
+        [Cout][Cin][kh][kw] is T = kh * kw such matrices, tap t = ky * kw + kx at element t with strides (Cin T, T)."""
         co, ci = w.shape[0], w.shape[1]
-        return self.get((id(w), 0), w, co, ci, ci, 1)
+        T = w.numel() // (co * ci)
+        return self.get((id(w), 0), w, co, ci, ci * T, T, taps=T)
 
     def dgrad(self, w, kscale=None):
         """planes of w^T [Cin][Cout] with kscale[Cout] folded in: the B operand of the data-gradient GEMM."""
         co, ci = w.shape[0], w.shape[1]
-        return self.get((id(w), 1), w, ci, co, 1, ci, kscale)
+        T = w.numel() // (co * ci)
+        return self.get((id(w), 1), w, ci, co, T, ci * T, kscale, taps=T)
 
 
 class X6WeightPlanes(SplitWeights):
     """Pre-split weights for the x6 kernels (hip.conv2d `w_planes`), whose six-product scheme spends its VALU time on splitting
-    fragments: every 1x1 weight whose launch runs on an x6 tile kernel, split into that kernel's LDS stage image."""
+    fragments: every 1x1 weight whose launch runs on an x6 tile kernel, split into that kernel's LDS stage image, and every k x k
+    weight whose launch does, as one such image per tap.  plans: Runtime.planes_kxk's answers, kept from step to step."""
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.plans = {}
 
     def alloc(self, J, K):
         return torch.empty((hip.conv_planes_bytes(J, K),), dtype=torch.uint8, device=self.device)
 
-    def dest_row(self, buf):
-        return [buf.data_ptr()]
+    def dest_row(self, buf, t=0, J=0, K=0):
+        return [buf.data_ptr() + t * hip.conv_planes_bytes(J, K)]      # tap t: K16 steps [t K / 16, (t + 1) K / 16) of the buffer
 
     def blocks(self, J, K):
         return (K // 16) * 2 * ((J + 127) // 128)
@@ -2150,7 +2203,7 @@ class PlaneGemmWeights(SplitWeights):
     def alloc(self, R, K):
         return hip.Planes.empty(self.np, (R, K), self.device)
 
-    def dest_row(self, pl):
+    def dest_row(self, pl, t=0, J=0, K=0):
         return [pl.t.data_ptr(), pl.ld, pl.plane]
 
     def blocks(self, R, K):

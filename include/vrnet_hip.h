@@ -136,7 +136,15 @@ int vrnet_conv2d_plan(int B, int H, int W, int Cin, int OH, int OW, int Cout, in
  * [lane half][64 columns] x 8 bf16); `w_planes` of vrnet_conv2d_f32 passes one such pack (NULL = split in the kernel).
  * mode 0: columns J = Cout, contraction K = Cin (source strides Cin, 1 for an OIHW 1x1 weight); mode 1: J = Cin, K = Cout
  * (strides 1, Cin) with kscale folded in through the table's scale address (the kscale argument is then ignored).
- * `w` is still required: shapes without a tile kernel (vrnet_conv2d_dma_tile == 0) use it.  Kernel family 9. */
+ * `w` is still required: shapes without a tile kernel (vrnet_conv2d_dma_tile == 0) use it.  Kernel family 9.
+ * k x k convs (2 .. 32 taps, any stride / padding / dilation; the 128 x 64 tile, split or not): the pack is kh * kw such images
+ * in ONE buffer of vrnet_conv_planes_bytes(J, kh * kw * K) bytes, tap t = ky * kw + kx at K16 steps [t * K / 16, (t + 1) * K / 16),
+ * i.e. one table entry per tap on the OIHW weight: source w + t, destination + t * vrnet_conv_planes_bytes(J, K), and 2^32 added
+ * to the entry's J: such an entry is split by truncation, into the planes igemm_dma_kernel makes of the weight fragments it
+ * splits itself, so a k x k launch gives the same bits with planes as without (a 1x1 entry stays round-to-nearest-even); mode 0 strides
+ * (Cin * kh * kw, kh * kw), mode 1 (kh * kw, Cin * kh * kw) with kscale as for 1x1.  A call whose plan (vrnet_conv2d_plan with
+ * flag 8192) does not answer family 9 -- no tile, the 128 x 128 tile, K % 16 != 0, more than 32 taps -- runs as without
+ * `w_planes` and reads `w`; a call that does answer 9 reads only the pack. */
 long vrnet_conv_planes_bytes(int J, int K);
 int vrnet_conv_planes_pack_f32(const long* table, int nentries, long total_blocks, void* stream);
 
