@@ -44,6 +44,8 @@ static inline bool vr_ablated(const char*) { return false; }
 
 static inline hipStream_t vr_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline long vr_cdiv(long a, long b) { return (a + b - 1) / b; }
+// Workgroups of the XCD-aware tile map for mt x nt tiles: the row tiles are padded to whole eights (one per XCD).
+static inline long vr_xcd_tiles(long mt, long nt) { return 8 * vr_cdiv(mt, 8) * nt; }
 static inline bool vr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // stream_ops.hip: the work split of the moments kernel on 16-byte accesses (C % 4 == 0), and the launch that finishes its

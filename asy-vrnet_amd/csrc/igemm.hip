@@ -312,10 +312,8 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
   asm volatile("" : "+s"(zero_page));
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int GT = 8 * ((MT + 7) >> 3) * NT;            // workgroups per split (the tile map pads row tiles to eights)
-  const int split = __builtin_amdgcn_readfirstlane(p_in.ksplit > 1 ? (int)blockIdx.x / GT : 0);
-  const int L = blockIdx.x - split * GT, jj = L >> 3;
-  const int nt = jj % NT, mt = (jj / NT) * 8 + (L & 7);
+  int GT, split, L, mt, nt;                           // GT: workgroups per split (the tile map pads row tiles to eights)
+  igemm_tile_map(MT, NT, p_in.ksplit, GT, split, L, mt, nt);
   if (mt >= MT) return;
   const int m0 = mt * BM, n0 = nt * BN;
   const IgemmArgs p = igemm_select_stream(p_in, m0);
@@ -379,9 +377,8 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
     __syncthreads();     // ordinary loads retire here, before the first DMA is issued
   }
   // split contraction: this workgroup runs steps [s_begin, s_begin + nsteps) of the tile's ntaps * nkb
-  const int nsteps_all = ntaps * nkb;
-  const int s_begin = p.ksplit > 1 ? (int)((long)split * nsteps_all / p.ksplit) : 0;
-  const int nsteps = (p.ksplit > 1 ? (int)((long)(split + 1) * nsteps_all / p.ksplit) : nsteps_all) - s_begin;
+  int s_begin, nsteps;
+  igemm_split_range(p, split, ntaps * nkb, s_begin, nsteps);
 
   // Per tap: a running source pointer and a per-stage advance for each of the thread's four DMA slots.  Slots that
   // are masked for the whole tap (row outside the tile / image, padded tap, channel quad beyond CK or CN) point at
@@ -616,10 +613,10 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
 
 
 // ------------------------------------------------------------------------------------------------
-// x6 implicit GEMM for 1x1 convs with PRE-SPLIT weights (round 3).  The six-product scheme spends its VALU time on splitting
-// fragments into bf16 planes, and the matrix pipe and the VALU do not overlap on gfx950 -- but the B operand is the same
-// weight tile for every row tile of every launch of a step.  vrnet_conv_planes_pack_f32 splits every eligible weight ONCE
-// per step into three bf16 planes laid out as the LDS image of a stage: [k16 step][64-column block][plane][lane half][64
+// x6 implicit GEMM for convs with PRE-SPLIT weights (1x1: round 3; k x k: the KXK arm below).  The six-product scheme spends its VALU
+// time on splitting fragments into bf16 planes, and the matrix pipe and the VALU do not overlap on gfx950 -- but the B operand
+// is the same weight tile for every row tile of every launch of a step.  vrnet_conv_planes_pack_f32 splits every eligible weight
+// ONCE per step into three bf16 planes laid out as the LDS image of a stage: [k16 step][64-column block][plane][lane half][64
 // columns] x 8 bf16, so a stage's B tile is one contiguous 6 KB (x TN) block that goes global -> LDS by DMA as it is and
 // every B fragment is one conflict-free ds_read_b128 per plane; only the A (activation) fragments are split in the
 // kernel: 2 instead of 3 (128 x 64 tile) resp. 4 (128 x 128) fragment splits per K16 step.  Both directions use this
@@ -628,7 +625,19 @@ __global__ __launch_bounds__(256, NST <= 3 ? 3 : (NST <= 4 ? 2 : 1)) void igemm_
 // igemm_dma_kernel.  Measured bound of the idea (diagnostic build, B splits skipped): 27.8 -> 26.6 ms per step.
 // (Round 3 also had a variant that folded the GroupNorm in front of the conv into the A fragments -- bit-identical to launch +
 // conv, measured neutral-to-negative in the step at every threshold, never on by default; removed in round 4.)
-template <int TN, int NST>
+//
+// KXK = false: 1x1 convs (stride 1, no padding).  A slot's source row is fixed: GEMM row m is row m of the A tensor.
+// KXK = true: k x k convs (stride, padding, dilation; both directions).  The pack holds one 1x1-style image per tap, tap t at
+// K16 steps [t * CK / 16, (t + 1) * CK / 16) of one buffer, so the contraction order is (tap, channel) as in igemm_dma_kernel
+// and a stage's B tile is still one contiguous 6 KB (x TN) block.  The A loader is the implicit-GEMM gather of
+// igemm_dma_kernel: a slot's source row is recomputed when the K loop crosses a tap, rows whose tap lies in the padding (or,
+// in a strided data gradient, between the output pixels) read the zero page, and taps that no row of the tile reaches are
+// skipped.  The live taps are a block-uniform 32-bit mask, reduced once through the first word of the (still empty) ring and
+// walked with scalar bit operations: no LDS beyond the ring.  Ring, waits, MFMA loop, split contraction and epilogue are
+// the same code for both.  (The order of the scalar set-up below -- NBW behind the split range, the 1x1 rows in front of b_step /
+// b_base -- is the one that gives all three instantiations the instruction sequences they had as two kernels:
+// profiles/planes_merge_isa.txt.)
+template <int TN, int NST, bool KXK>
 __global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) void igemm_planes_kernel(const IgemmArgs p,
                                                                                                       const unsigned char* planes,
                                                                                                       int JB, int MT, int NT) {
@@ -638,169 +647,34 @@ __global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) v
   constexpr int TM = 1, TNW = 2 * TN, BM = 128, BN = 64 * TN, BK = 16;
   constexpr int A_BYTES = BM * BK * 4, B_BYTES = TN * 6144, ST_BYTES = A_BYTES + B_BYTES;
   constexpr int NA = A_BYTES / 1024 / 4;                  // A pieces per wave and stage (2)
-  constexpr int NBT = B_BYTES / 1024;                     // B pieces per stage: 6 (waves 0-1 issue 2, waves 2-3 one) or 12 (3 each)
+  // (B pieces per stage, B_BYTES / 1024: 6 -- waves 0-1 issue 2, waves 2-3 one -- or 12, 3 each)
   static_assert(NST * ST_BYTES >= 4 * 32 * STAGE_LD * 4, "epilogue staging must fit the ring");
   __shared__ __attribute__((aligned(16))) unsigned char smem[NST * ST_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const float* zero_page = vr_zero_page;
   asm volatile("" : "+s"(zero_page));
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int GT = 8 * ((MT + 7) >> 3) * NT;
-  const int split = __builtin_amdgcn_readfirstlane(p.ksplit > 1 ? (int)blockIdx.x / GT : 0);
-  const int L = blockIdx.x - split * GT, jj = L >> 3;
-  const int nt = jj % NT, mt = (jj / NT) * 8 + (L & 7);
+  int GT, split, L, mt, nt;
+  igemm_tile_map(MT, NT, p.ksplit, GT, split, L, mt, nt);
   if (mt >= MT) return;
   const int m0 = mt * BM, n0 = nt * BN;
-  const int nsteps_all = p.CK / BK;
-  const int s_begin = p.ksplit > 1 ? (int)((long)split * nsteps_all / p.ksplit) : 0;
-  const int nsteps = (p.ksplit > 1 ? (int)((long)(split + 1) * nsteps_all / p.ksplit) : nsteps_all) - s_begin;
-  const int NBW = TN == 2 ? 3 : (wave < 2 ? 2 : 1);      // this wave's B pieces per stage (wave-uniform)
+  const int nkb = p.CK / BK;                              // K16 steps per tap
 
-  // ---- A loader roles (as igemm_dma_kernel with QPR = 4): slot (row, quad) of a 128 x 16 fp32 image, XOR-swizzled
-  const float* a_run[NA];
-  int a_inc[NA];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    const int sl = (wave * NA + i) * 64 + lane, r = sl >> 2;
-    const int q = (sl & 3) ^ ((r >> 2) & 3);
-    const int m = m0 + r;
-    const bool ok = m < p.M;
-    a_run[i] = ok ? p.a + (long)m * p.lda + 4 * q + (long)s_begin * BK : zero_page;
-    a_inc[i] = ok ? BK : 0;
-  }
-  const long b_step = (long)JB * 6144;
-  const unsigned char* b_src = planes + ((long)(n0 >> 6)) * 6144 + (long)lane * 16 + s_begin * b_step;       // + kb * JB * 6144
-  int ld_buf = 0;
-  // one DMA piece of the stage being issued: 0 .. NA - 1 = A, then this wave's B pieces
-  auto issue_piece = [&](int i) {
-    unsigned char* stage = smem + ld_buf * ST_BYTES;
-    if (i < NA) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)a_run[i],
-                                       (__attribute__((address_space(3))) void*)(stage + (wave * NA + i) * 1024), 16, 0, 0);
-      a_run[i] += a_inc[i];
-    } else if (i - NA < NBW) {
-      const int j = i - NA;
-      const int piece = TN == 2 ? wave * 3 + j : (wave < 2 ? wave * 2 + j : 2 + wave);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src + piece * 1024),
-                                       (__attribute__((address_space(3))) void*)(stage + A_BYTES + piece * 1024), 16, 0, 0);
-    }
-  };
-  auto issue_end = [&]() {
-    b_src += b_step;
-    if (++ld_buf == NST) ld_buf = 0;
-  };
-  constexpr int NPMAX = NA + (TN == 2 ? 3 : 2);
-  auto issue = [&]() {
-#pragma unroll
-    for (int i = 0; i < NPMAX; ++i) issue_piece(i);
-    issue_end();
-  };
-
-  f32x16 acc[TM][TNW];
-#pragma unroll
-  for (int j = 0; j < TNW; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
-  const int h = lane >> 5;
-  const int ra = wave * 32 + (lane & 31);
-  const int a_off = ra * BK * 4, a_swz = (ra >> 2) & 3;
-  int b_off[TNW];
-#pragma unroll
-  for (int i = 0; i < TNW; ++i) {
-    const int rb = 32 * i + (lane & 31);
-    b_off[i] = ((rb >> 6) * 6 + h) * 1024 + (rb & 63) * 16;       // + plane * 2048
-  }
-
-#pragma unroll
-  for (int st = 0; st < NST - 1; ++st)
-    if (st < nsteps) issue();
-  int cur = 0;
-  for (int s = 0; s < nsteps; ++s) {
-    if (NST >= 3 && nsteps - 1 - s >= 1) {       // one younger stage stays in flight
-      if (TN == 2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-      else if (wave < 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    const bool more = s + NST - 1 < nsteps;      // the next stage goes into the slot every wave finished reading before this barrier
-    const unsigned char* As = smem + cur * ST_BYTES;
-    const unsigned char* Bs = As + A_BYTES;
-    vr_bf16x8 a3[3], b3[TNW][3];
-#pragma unroll
-    for (int i = 0; i < TNW; ++i)
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) b3[i][pl] = *reinterpret_cast<const vr_bf16x8*>(Bs + b_off[i] + pl * 2048);
-    {
-      f32x4 lo = *reinterpret_cast<const f32x4*>(As + a_off + 16 * ((2 * h) ^ a_swz));
-      f32x4 hi = *reinterpret_cast<const f32x4*>(As + a_off + 16 * ((2 * h + 1) ^ a_swz));
-      vr_split3(lo, hi, a3);
-    }
-    // each DMA instruction of the next stage goes behind a group of six MFMAs, whose execution hides its issue cost
-#pragma unroll
-    for (int jn = 0; jn < TNW; ++jn) {
-      acc[0][jn] = vr_mfma_x6(a3, b3[jn], acc[0][jn]);
-      if (more) {
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < NPMAX; ++q)
-          if (q % TNW == jn) issue_piece(q);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (more) issue_end();
-    if (++cur == NST) cur = 0;
-  }
-  __syncthreads();
-  if (p.ksplit > 1) igemm_splitk_store<TM, TNW>(p, acc, GT, L, split);
-  else igemm_epilogue<TM, TNW, 4, 1>(p, acc, reinterpret_cast<float*>(smem), m0, n0);
-}
-
-// The same GEMM for k x k convs (stride, padding, dilation; both directions) on pre-split weights: the pack holds one 1x1-style
-// image per tap, tap t at K16 steps [t * CK / 16, (t + 1) * CK / 16) of one buffer, so the contraction order is (tap, channel) as
-// in igemm_dma_kernel and a stage's B tile is still one contiguous 6 KB (x TN) block.  The A loader is the implicit-GEMM gather
-// of igemm_dma_kernel: a slot's source row is recomputed when the K loop crosses a tap, rows whose tap lies in the padding (or,
-// in a strided data gradient, between the output pixels) read the zero page, and taps that no row of the tile reaches are
-// skipped.  The live taps are a block-uniform 32-bit mask, reduced once through the first word of the (still empty) ring and
-// walked with scalar bit operations: no LDS beyond the ring.  Ring, waits, MFMA loop, split contraction and epilogue are those
-// of igemm_planes_kernel.
-template <int TN, int NST>
-__global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) void igemm_planes_kxk_kernel(const IgemmArgs p,
-                                                                                                          const unsigned char* planes,
-                                                                                                          int JB, int MT, int NT) {
-  constexpr int TM = 1, TNW = 2 * TN, BM = 128, BN = 64 * TN, BK = 16;
-  constexpr int A_BYTES = BM * BK * 4, B_BYTES = TN * 6144, ST_BYTES = A_BYTES + B_BYTES;
-  constexpr int NA = A_BYTES / 1024 / 4;
-  static_assert(NST * ST_BYTES >= 4 * 32 * STAGE_LD * 4, "epilogue staging must fit the ring");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[NST * ST_BYTES];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const float* zero_page = vr_zero_page;
-  asm volatile("" : "+s"(zero_page));
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int GT = 8 * ((MT + 7) >> 3) * NT;
-  const int split = __builtin_amdgcn_readfirstlane(p.ksplit > 1 ? (int)blockIdx.x / GT : 0);
-  const int L = blockIdx.x - split * GT, jj = L >> 3;
-  const int nt = jj % NT, mt = (jj / NT) * 8 + (L & 7);
-  if (mt >= MT) return;
-  const int m0 = mt * BM, n0 = nt * BN;
-  const int nkb = p.CK / BK, TAPS = p.kh * p.kw;
-  const int NBW = TN == 2 ? 3 : (wave < 2 ? 2 : 1);
-
-  // ---- A loader roles: slot (row, quad) of the 128 x 16 fp32 image; per row the sample's first source row and the
-  // tap-independent part of the source coordinates (a row beyond M gets a y no tap brings into the image)
+  // ---- k x k gather state: per A slot (row, quad) of the 128 x 16 fp32 image the channel offset, the sample's first source
+  // row and the tap-independent part of the source coordinates (a row beyond M gets a y no tap brings into the image)
   int a_c[NA], a_base[NA], a_py[NA], a_px[NA];
+  if constexpr (KXK) {
 #pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    const int sl = (wave * NA + i) * 64 + lane, r = sl >> 2;
-    a_c[i] = 4 * ((sl & 3) ^ ((r >> 2) & 3));
-    const int m = m0 + r;
-    int b, y, x;
-    igemm_row_to_pixel(p, m < p.M ? m : 0, b, y, x);
-    a_base[i] = b * p.SH * p.SW;
-    a_py[i] = m < p.M ? (p.mode == 0 ? y * p.stride - p.pad : y + p.pad) : -(1 << 24);
-    a_px[i] = p.mode == 0 ? x * p.stride - p.pad : x + p.pad;
+    for (int i = 0; i < NA; ++i) {
+      const int sl = (wave * NA + i) * 64 + lane, r = sl >> 2;
+      a_c[i] = 4 * ((sl & 3) ^ ((r >> 2) & 3));
+      const int m = m0 + r;
+      int b, y, x;
+      igemm_row_to_pixel(p, m < p.M ? m : 0, b, y, x);
+      a_base[i] = b * p.SH * p.SW;
+      a_py[i] = m < p.M ? (p.mode == 0 ? y * p.stride - p.pad : y + p.pad) : -(1 << 24);
+      a_px[i] = p.mode == 0 ? x * p.stride - p.pad : x + p.pad;
+    }
   }
   auto src_row = [&](int i, int ky, int kx) -> int {      // source row of slot i under tap (ky, kx), -1: none
     int sy, sx;
@@ -816,8 +690,9 @@ __global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) v
     if (sy < 0 || sy >= p.SH || sx < 0 || sx >= p.SW) return -1;
     return a_base[i] + sy * p.SW + sx;
   };
-  unsigned live;      // taps that reach the image for at least one row of this tile (TAPS <= 32)
-  {
+  unsigned live = 1u;      // k x k: taps that reach the image for at least one row of this tile (kh * kw <= 32)
+  if constexpr (KXK) {
+    const int TAPS = p.kh * p.kw;
     unsigned mine = 0u;
     for (int t = 0; t < TAPS; ++t) {
       const int ky = t / p.kw, kx = t - ky * p.kw;
@@ -835,17 +710,30 @@ __global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) v
     live = (unsigned)__builtin_amdgcn_readfirstlane((int)*mask_s);
     __syncthreads();      // the word belongs to the ring: every wave has read it before the first DMA is issued
   }
-  const int nsteps_all = __popc(live) * nkb;
-  const int s_begin = p.ksplit > 1 ? (int)((long)split * nsteps_all / p.ksplit) : 0;
-  const int nsteps = (p.ksplit > 1 ? (int)((long)(split + 1) * nsteps_all / p.ksplit) : nsteps_all) - s_begin;
+  int s_begin, nsteps;
+  igemm_split_range(p, split, KXK ? __popc(live) * nkb : nkb, s_begin, nsteps);
+  const int NBW = TN == 2 ? 3 : (wave < 2 ? 2 : 1);       // this wave's B pieces per stage (wave-uniform)
 
+  // ---- A loader roles (as igemm_dma_kernel with QPR = 4): slot (row, quad) of a 128 x 16 fp32 image, XOR-swizzled.  A slot
+  // with no source (row beyond M, tap outside the image) points at the zero page and does not advance.
   const float* a_run[NA];
   int a_inc[NA];
+  if constexpr (!KXK) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int sl = (wave * NA + i) * 64 + lane, r = sl >> 2;
+      const int q = (sl & 3) ^ ((r >> 2) & 3);
+      const int m = m0 + r;
+      const bool ok = m < p.M;
+      a_run[i] = ok ? p.a + (long)m * p.lda + 4 * q + (long)s_begin * BK : zero_page;
+      a_inc[i] = ok ? BK : 0;
+    }
+  }
   const long b_step = (long)JB * 6144;
   const unsigned char* b_base = planes + ((long)(n0 >> 6)) * 6144 + (long)lane * 16;
-  const unsigned char* b_src = b_base;
-  unsigned rem = live;      // live taps not yet set up
-  auto setup_tap = [&]() {
+  const unsigned char* b_src = KXK ? b_base : b_base + s_begin * b_step;      // + K16 step * JB * 6144
+  unsigned rem = live;      // k x k: live taps not yet set up
+  [[maybe_unused]] auto setup_tap = [&]() {
     const int t = rem ? __builtin_ctz(rem) : 0;
     rem &= rem - 1;
     const int ky = t / p.kw, kx = t - ky * p.kw;
@@ -857,17 +745,23 @@ __global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) v
     }
     b_src = b_base + (long)t * nkb * b_step;
   };
-  int ld_kb = s_begin - (s_begin / nkb) * nkb, ld_buf = 0;      // (k block, ring slot) of the NEXT stage to issue
-  for (int i = 0; i < s_begin / nkb; ++i) rem &= rem - 1;
-  if (ld_kb != 0 && nsteps > 0) {      // a split that starts inside a tap
-    setup_tap();
+  [[maybe_unused]] int ld_kb = 0;      // k x k: K16 step within its tap of the NEXT stage to issue
+  int ld_buf = 0;                      // ring slot of the NEXT stage to issue
+  if constexpr (KXK) {
+    ld_kb = s_begin - (s_begin / nkb) * nkb;
+    for (int i = 0; i < s_begin / nkb; ++i) rem &= rem - 1;
+    if (ld_kb != 0 && nsteps > 0) {      // a split that starts inside a tap
+      setup_tap();
 #pragma unroll
-    for (int i = 0; i < NA; ++i) a_run[i] += (long)ld_kb * a_inc[i];
-    b_src += ld_kb * b_step;
+      for (int i = 0; i < NA; ++i) a_run[i] += (long)ld_kb * a_inc[i];
+      b_src += ld_kb * b_step;
+    }
   }
   auto issue_begin = [&]() {
-    if (ld_kb == 0) setup_tap();
+    if constexpr (KXK)
+      if (ld_kb == 0) setup_tap();
   };
+  // one DMA piece of the stage being issued: 0 .. NA - 1 = A, then this wave's B pieces
   auto issue_piece = [&](int i) {
     unsigned char* stage = smem + ld_buf * ST_BYTES;
     if (i < NA) {
@@ -883,7 +777,8 @@ __global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) v
   };
   auto issue_end = [&]() {
     b_src += b_step;
-    if (++ld_kb == nkb) ld_kb = 0;
+    if constexpr (KXK)
+      if (++ld_kb == nkb) ld_kb = 0;
     if (++ld_buf == NST) ld_buf = 0;
   };
   constexpr int NPMAX = NA + (TN == 2 ? 3 : 2);
@@ -937,6 +832,7 @@ __global__ __launch_bounds__(256, (NST * (8192 + TN * 6144) <= 49152) ? 3 : 2) v
       f32x4 hi = *reinterpret_cast<const f32x4*>(As + a_off + 16 * ((2 * h + 1) ^ a_swz));
       vr_split3(lo, hi, a3);
     }
+    // each DMA instruction of the next stage goes behind a group of six MFMAs, whose execution hides its issue cost
 #pragma unroll
     for (int jn = 0; jn < TNW; ++jn) {
       acc[0][jn] = vr_mfma_x6(a3, b3[jn], acc[0][jn]);
@@ -1697,7 +1593,7 @@ static int vr_dma_plan(long M, int CN, long ktot, long ws_bytes, int* S_out) {
   if (S > steps / min_steps) S = steps / min_steps;
   if (S > 8) S = 8;
   if (S < 2 || tiles * S < 192) return 0;
-  const long need = S * (8 * vr_cdiv(mt, 8) * nt21) * 8192 * 4;
+  const long need = S * vr_xcd_tiles(mt, nt21) * 8192 * 4;
   if (need > ws_bytes) return 0;
   *S_out = (int)S;
   return 21;
@@ -1716,7 +1612,7 @@ extern "C" int vrnet_conv2d_dma_plan(long rows, int cols, long ktot, int* splits
 extern "C" long vrnet_conv2d_splitk_workspace(long rows, int cols, long ktot) {
   int S = 1;
   if (vr_dma_plan(rows, cols, ktot, 1L << 40, &S) == 0 || S < 2) return 0;
-  return (long)S * (8 * vr_cdiv(vr_cdiv(rows, 128), 8) * vr_cdiv(cols, 64)) * 8192 * 4;
+  return (long)S * vr_xcd_tiles(vr_cdiv(rows, 128), vr_cdiv(cols, 64)) * 8192 * 4;
 }
 
 /* Which LDS-DMA tile vrnet_conv2d_f32 would use at precision 2 / 3 for B*MH*MW GEMM rows and CN GEMM columns (mode 0:
@@ -1732,7 +1628,7 @@ enum ConvKernel {
   CONV_RING = 1,        // igemm_dma_kernel<mode, 3, 1, 1>: the fp32 LDS-DMA ring, 64 x 64              family 2
   CONV_X6 = 2,          // igemm_dma_kernel<mode, 3, 2, 2 / 1, 6>, tile 22 / 21 (+ the split finish)      family 6
   CONV_BF16_TILE = 3,   // igemm_dma_kernel<mode, 3, 2, 2 / 1, 1>: bf16-rounded operands, tile 22 / 21   family 3
-  CONV_PLANES = 4,      // igemm_planes_kernel<2, 2> / <1, 3>, igemm_planes_kxk_kernel<1, 3> on pre-split weights (+ the split finish)   family 9
+  CONV_PLANES = 4,      // igemm_planes_kernel<2, 2, false> / <1, 3, false> / <1, 3, true> on pre-split weights (+ the split finish)   family 9
   CONV_BF16 = 5,        // igemm_bf16_kernel<mode> (igemm_bf16.hip), 64 x 64                              family 3
   CONV_TINY = 6,        // tinyconv.hip                                                                   family 4
   CONV_NARROW = 7,      // narrowconv.hip                                                                 family 5
@@ -1851,19 +1747,19 @@ static int conv_choose(const ConvQuery& q, ConvChoice* c) {
   // precision 2 (x6): 128 x 128 x 16 ring tiles with 2 x 2 accumulators per wave -- each split fragment feeds two
   // MFMA groups, which is what pays for the split (on 64 x 64 tiles the conversions cost what the faster MFMA saves)
   const bool bf16_tiles = precision == 3 || (precision == 1 && mode == 0);   // (mode 1 at precision 1 brings the transposed pack)
-  // A k x k conv whose caller brings pre-split weights (one pack image per tap) runs on igemm_planes_kxk_kernel, 128 x 64 tiles,
+  // A k x k conv whose caller brings pre-split weights (one pack image per tap) runs on igemm_planes_kernel<1, 3, true>, 128 x 64 tiles,
   // whatever the tile count: the caller has paid for the split and asks for this kernel, the rule that sends a launch with few
   // tiles elsewhere is the caller's to apply (Runtime.planes_kxk of program.py brings planes only where this launch would have
   // run on the x6 tiles anyway).  Not taken: contractions that are no multiple of 16, more than 32 taps (the kernel's tap mask),
   // scalar loaders, two-stream launches, and the shapes vr_dma_plan gives the 128 x 128 tile (the gather's row state would cost
-  // 18 VGPRs over igemm_planes_kernel<2, 2>; no k x k launch of the net has the >= 512 such tiles) -- those run as without planes.
+  // 18 VGPRs over igemm_planes_kernel<2, 2, false>; no k x k launch of the net has the >= 512 such tiles) -- those run as without planes.
   if (precision == 2 && q.planes && kh * kw > 1 && kh * kw <= 32 && use_dma && vec && !pair_rows && CK % 16 == 0 &&
       vr_tune("VRNET_X6_PLANES", 1)) {
     const long k_live = conv_k_live(q, MH, MW, SH, SW, CK);
     int S = 1;
     const int tile = vr_dma_plan(M, CN, k_live, q.ws_bytes, &S);
     if (tile != 22) {
-      const long mt = vr_cdiv(M, 128), nt = vr_cdiv(CN, 64), gt = 8 * vr_cdiv(mt, 8) * nt;
+      const long mt = vr_cdiv(M, 128), nt = vr_cdiv(CN, 64), gt = vr_xcd_tiles(mt, nt);
       if (!tile && q.ws_bytes > 0) {      // no tile by the rule: the split of vr_dma_plan without its floor of 192 workgroups
         S = (int)std::min<long>(std::min<long>(vr_cdiv(512, mt * nt), k_live / 16 / 32), 8);
         if (S < 2 || S * gt * 8192 * 4 > q.ws_bytes) S = 1;
@@ -1887,8 +1783,8 @@ static int conv_choose(const ConvQuery& q, ConvChoice* c) {
     if (tile) {
       const long nt = tile == 22 ? nt22 : nt21;
       c->tile = tile; c->S = S; c->mt = (int)mt; c->nt = (int)nt;
-      c->grid_x = (unsigned)(8 * vr_cdiv(mt, 8) * nt * S); c->grid_y = 1;
-      c->finish_grid = S > 1 ? (unsigned)(8 * vr_cdiv(mt, 8) * nt) : 0;
+      c->grid_x = (unsigned)(vr_xcd_tiles(mt, nt) * S); c->grid_y = 1;
+      c->finish_grid = S > 1 ? (unsigned)vr_xcd_tiles(mt, nt) : 0;
       // pre-split weights (vrnet_conv_planes_pack_f32; in mode 1 the pack holds the transposed weights with kscale folded in)
       if (precision == 2 && q.planes && kh == 1 && kw == 1 && stride == 1 && q.pad == 0 && !pair_rows && CK % 16 == 0 &&
           vr_tune("VRNET_X6_PLANES", 1)) {
@@ -1904,7 +1800,7 @@ static int conv_choose(const ConvQuery& q, ConvChoice* c) {
   if (dma_ok && dma_shape) {
     c->kernel = CONV_RING; c->family = 2; c->tile = 64064;
     c->mt = (int)vr_cdiv(M, 64); c->nt = (int)vr_cdiv(CN, 64);
-    c->grid_x = (unsigned)(8 * vr_cdiv(c->mt, 8) * c->nt); c->grid_y = 1;
+    c->grid_x = (unsigned)vr_xcd_tiles(c->mt, c->nt); c->grid_y = 1;
     return VR_OK;
   }
   // Register-staged tiles: 64 x 64 by default; 128 x 64 for narrow outputs over long contractions; 128 x 32 for <= 32 columns.
@@ -2047,11 +1943,11 @@ extern "C" int vrnet_conv2d_f32(const float* a, long lda, const float* w, const 
       // +0.2 ms in the step: DESIGN 3.1)
       if (c.tile == 22) {
         // 128 x 128 tile: two stages (40 KB, 3 workgroups per CU) measured 0.2 ms per step ahead of three (60 KB, 2 per CU)
-        hipLaunchKernelGGL((igemm_planes_kernel<2, 2>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
+        hipLaunchKernelGGL((igemm_planes_kernel<2, 2, false>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
       } else {
-        // k x k: the gathering sibling; its pack holds kh * kw images of JB x CK / 16 blocks
-        if (kh * kw > 1) hipLaunchKernelGGL((igemm_planes_kxk_kernel<1, 3>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
-        else hipLaunchKernelGGL((igemm_planes_kernel<1, 3>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
+        // k x k: the gathering arm (KXK); its pack holds kh * kw images of JB x CK / 16 blocks
+        if (kh * kw > 1) hipLaunchKernelGGL((igemm_planes_kernel<1, 3, true>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
+        else hipLaunchKernelGGL((igemm_planes_kernel<1, 3, false>), grid, block, 0, st, pq, planes, JB, c.mt, c.nt);
         if (c.S > 1) hipLaunchKernelGGL((igemm_splitk_finish_kernel<1, 2, 4, 1>), finish, block, 0, st, pq, c.mt, c.nt);
       }
       VR_LAUNCH_CHECK("conv2d(x6, pre-split weights)");

@@ -100,6 +100,26 @@ __device__ __forceinline__ long igemm_row_index(const IgemmArgs& p, int m) {
   return ((long)b * p.MH + y) * p.MW + x;
 }
 
+// Workgroup -> (split, tile) of the ring kernels' 1-D grids of ksplit * GT workgroups, GT = vr_xcd_tiles(MT, NT): workgroup L
+// of a split is row tile mt, column tile nt.  The NT column tiles of one row tile are consecutive on ONE XCD (ids b, b + 8, ...
+// share an XCD), so its A rows enter a single L2 once; the row tiles are padded to eights, the caller returns when mt >= MT.
+__device__ __forceinline__ void igemm_tile_map(int MT, int NT, int ksplit, int& GT, int& split, int& L, int& mt, int& nt) {
+  GT = 8 * ((MT + 7) >> 3) * NT;
+  split = __builtin_amdgcn_readfirstlane(ksplit > 1 ? (int)blockIdx.x / GT : 0);
+  L = blockIdx.x - split * GT;
+  const int jj = L >> 3;
+  nt = jj % NT;
+  mt = (jj / NT) * 8 + (L & 7);
+}
+
+// Split contraction: split `split` of p.ksplit runs steps [s_begin, s_begin + nsteps) of the tile's nsteps_all K steps.
+// (Takes the argument block, not ksplit by value: with a by-value ksplit hipcc merges the two branches on it and every ring
+// kernel comes out a few instructions different from the measured code -- profiles/planes_merge_isa.txt.)
+__device__ __forceinline__ void igemm_split_range(const IgemmArgs& p, int split, int nsteps_all, int& s_begin, int& nsteps) {
+  s_begin = p.ksplit > 1 ? (int)((long)split * nsteps_all / p.ksplit) : 0;
+  nsteps = (p.ksplit > 1 ? (int)((long)(split + 1) * nsteps_all / p.ksplit) : nsteps_all) - s_begin;
+}
+
 constexpr int STAGE_LD = 36;                       // epilogue staging tile: 32 rows x 36 floats per wave
 
 // One 32 x 32 accumulator tile whose first output element is (row0, col0); `stage`: this wave's private staging tile of

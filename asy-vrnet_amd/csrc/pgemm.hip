@@ -633,7 +633,7 @@ extern "C" int vrnet_gemm_planes_f32(const void* a, long lda, long a_plane, cons
   }
   PlaneOps o{reinterpret_cast<const unsigned short*>(a), lda, a_plane, reinterpret_cast<const unsigned short*>(b), ldb, b_plane};
   const long mt = vr_cdiv(M, PG_BM), nt = vr_cdiv(N, PG_BN);
-  dim3 grid((unsigned)(8 * vr_cdiv(mt, 8) * nt)), block(512);
+  dim3 grid((unsigned)vr_xcd_tiles(mt, nt)), block(512);
   hipStream_t st = vr_stream(stream);
 #ifdef VR_TUNING
   switch (np == 3 ? vr_tune("VRNET_PGEMM_DBG", 0) : 0) {

@@ -118,7 +118,7 @@ int vrnet_conv2d_dma_plan(long rows, int cols, long ktot, int* splits);
  *   0 family   what vrnet_last_kernel reports after the call
  *   1 kernel   0 igemm_kernel (tile 128032 / 128064 / 64064 = rows x columns per workgroup), 1 the fp32 LDS-DMA ring
  *              igemm_dma_kernel<mode, 3, 1, 1> (64064), 2 the x6 tile kernels (tile 22 = 128 x 128, 21 = 128 x 64), 3 the same
- *              tiles on bf16-rounded operands, 4 igemm_planes_kernel on pre-split weights (22 / 21), 5 igemm_bf16_kernel
+ *              tiles on bf16-rounded operands, 4 igemm_planes_kernel<TN, NST, KXK> on pre-split weights (22 / 21), 5 igemm_bf16_kernel
  *              (64064), 6 the tiny-channel kernels, 7 the narrow-output kernels, 8 the patch data gradient (6-8: the rest is 0)
  *   2 tile     3 S   splits of the contraction (> 1: igemm_splitk_finish_kernel follows)
  *   4 k_live   the contraction length that counts for the split: taps that reach the image for at least one row

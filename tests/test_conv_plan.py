@@ -343,7 +343,7 @@ def variants(geo):
 KERNELS = ([("igemm_kernel", t, m, v) for t in (128032, 128064, 64064) for m in (0, 1) for v in ("vec", "scalar")] +          # 12
            [("igemm_dma_kernel<3,1,1>", 64064, m, "vec") for m in (0, 1)] +                                                # 2
            [(n, t, m, "vec") for n in ("x6 tile", "bf16 tile") for t in (22, 21) for m in (0, 1)] +                         # 4 + 4
-           [("igemm_planes_kernel", 22, m, "vec") for m in (0, 1)] + [("igemm_planes_kernel", 21, m, "vec") for m in (0, 1)] +   # <2,2>, <1,3>
+           [("igemm_planes_kernel", 22, m, "vec") for m in (0, 1)] + [("igemm_planes_kernel", 21, m, "vec") for m in (0, 1)] +   # <2,2,false>, <1,3,false>
            [("igemm_bf16_kernel", 64064, m, "vec") for m in (0, 1)])                                                       # 2
 FINISH = {("igemm_splitk_finish_kernel", "<2,1,2,2>"), ("igemm_splitk_finish_kernel", "<1,2,4,1>")}
 # instantiated by the launcher's macro, out of reach of its rule: 128 x 64 asks for vector loaders
@@ -513,7 +513,7 @@ def test_plan_query_refuses_what_the_launcher_refuses(lib):
 
 def test_cases_reach_every_variant():
     assert len(GEOS) == len(set(GEOS))
-    # the 28 instantiations the launcher names (igemm_planes_kernel<2, 2> and <1, 3> serve both modes: mode is an argument there)
+    # the 28 instantiations the launcher names (igemm_planes_kernel<2, 2, false> and <1, 3, false> serve both modes: mode is an argument there)
     assert len({k[:2] if k[0] == "igemm_planes_kernel" else k for k in KERNELS}) + len(FINISH) == 28 and UNREACHABLE < set(KERNELS)
     reached = set().union(*(variants(g) for g in GEOS))
     assert reached == ALL_VARIANTS, (sorted(map(str, ALL_VARIANTS - reached)), sorted(map(str, reached - ALL_VARIANTS)))

@@ -1,4 +1,4 @@
-"""k x k convolutions at precision 2 on pre-split weights: igemm_planes_kxk_kernel (kernel family 9) behind vrnet_conv2d_f32's
+"""k x k convolutions at precision 2 on pre-split weights: igemm_planes_kernel<1, 3, true> (kernel family 9) behind vrnet_conv2d_f32's
 `w_planes`, forward (mode 0) and data gradient (mode 1), and the per-tap pack image it reads.
 
 The pack of a [Cout][Cin][kh][kw] weight is kh * kw images of the 1x1 pack in one buffer, one table entry of
@@ -80,7 +80,7 @@ def lib():
 
 # ================================================================================================ the rule and the plan
 def eligible(geo, mode):
-    """igemm.hip, conv_choose: a k x k call at precision 2 that brings planes runs on igemm_planes_kxk_kernel (aligned bases and
+    """igemm.hip, conv_choose: a k x k call at precision 2 that brings planes runs on igemm_planes_kernel<1, 3, true> (aligned bases and
     row strides % 4 == 0, as every call of this file has them)."""
     B, H, W, Ci, Co, k, s, p, d = geo
     M, MH, MW, SH, SW, CK, CN = gemm_of(geo, mode)

@@ -1,5 +1,5 @@
 """Times single 1x1-conv GEMM launches alone, back to back (host latency does not enter), interleaved rounds in ONE process:
-the x6 kernel with pre-split weights that splits the activations itself (igemm_planes_kernel, round 3) against the plane
+the x6 kernel with pre-split weights that splits the activations itself (igemm_planes_kernel<TN, NST, false>, round 3) against the plane
 GEMM on operands that already are bf16 planes (pgemm_kernel, round 4; np = 3 fp32 values, np = 1 bf16 tensors).
 usage: python tools/pgemm_probe.py [M N K ...]      (default: the net's shapes at phi = l, bs 8, 512 px)"""
 import importlib
