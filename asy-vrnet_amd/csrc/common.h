@@ -78,6 +78,7 @@ typedef struct vrnet_frame_geom {
 }
 #define VR_FLAG_GEOMETRY 256                    /* a record that had to be clamped; bits 1..128: render / nms / evalacc */
 #define VR_FLAG_BOX_COUNT 512                   /* traintargets.hip: a box count outside [0, max_gt], clamped */
+#define VR_FLAG_POINT_COUNT 1024                /* radarmap.hip: a point count outside [0, max_points], clamped */
 
 __device__ __forceinline__ int vr_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

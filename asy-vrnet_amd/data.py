@@ -791,6 +791,228 @@ def device_radar(radar, normalise=True, device="cuda", out=None):
     return out
 
 
+# ---- the radar map from 4D radar points: host statement of csrc/radarmap.hip ---------------------------------------------
+# The reference's data instructions ask for "the radar map with the spatial size of images" from projected point clouds and
+# ship no code for it; the rule below is this project's definition, as `augment_radar` is.  `radar_map` is the truth the
+# kernels are held to, bit for bit.
+# vrnet_radar_view of include/vrnet_hip.h, one record per image (80 bytes)
+RADAR_VIEW_DTYPE = np.dtype([(n, "<i4") for n in ("ih", "iw", "nw", "nh", "dx", "dy", "flip", "count")] + [("P", "<f4", (12,))])
+RADAR_MAX_RADIUS = 8
+
+
+def check_radar_rule(radius, min_depth, fn="radar_map"):
+    """radius as an int in 0..RADAR_MAX_RADIUS and min_depth as a positive finite float32, or a RuntimeError."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= RADAR_MAX_RADIUS:
+        raise RuntimeError(f"{fn}: radius must be an integer in 0..{RADAR_MAX_RADIUS}, got {radius!r}")
+    try:
+        md = np.float32(min_depth)
+    except (TypeError, ValueError):
+        md = np.float32("nan")
+    if not (md > 0 and np.isfinite(md)):
+        raise RuntimeError(f"{fn}: min_depth must be a positive finite number, got {min_depth!r}")
+    return int(radius), md
+
+
+def check_calib(calib, batch, fn="radar_views"):
+    """calib (3, 4) or (B, 3, 4), any real type -> (B, 3, 4) float32."""
+    try:
+        P = np.asarray(calib.detach().cpu().numpy() if torch.is_tensor(calib) else calib, dtype=np.float32)
+    except (TypeError, ValueError):
+        P = None
+    if P is None or P.shape not in ((3, 4), (batch, 3, 4)):
+        raise RuntimeError(f"{fn}: calib is a (3, 4) projection or one per image ({batch}, 3, 4), got "
+                           f"{None if P is None else P.shape}")
+    return np.ascontiguousarray(np.broadcast_to(P, (batch, 3, 4)))
+
+
+def radar_views(table, calib, counts):
+    """The packed per-image table of `hip.radar_map`: a `frame_geometry` table OR an `augment_params` table (both carry ih, iw,
+    nw, nh, dx, dy; only the latter has flip), calib (3, 4) or (B, 3, 4), counts (B) points per image -> a (B,)
+    RADAR_VIEW_DTYPE array (`radar_view_bytes` of it is what the device takes).  Host only."""
+    table = np.asarray(table)
+    if table.ndim != 1 or table.dtype not in (GEOM_DTYPE, AUG_DTYPE):
+        raise RuntimeError("radar_views: the table is a (B,) array of data.GEOM_DTYPE or data.AUG_DTYPE records")
+    B = len(table)
+    P = check_calib(calib, B)
+    counts = np.asarray(counts.cpu().numpy() if torch.is_tensor(counts) else counts)
+    if counts.shape != (B,) or not np.issubdtype(counts.dtype, np.integer):
+        raise RuntimeError(f"radar_views: counts are {B} integers, got {counts.dtype} {counts.shape}")
+    out = np.zeros(B, RADAR_VIEW_DTYPE)
+    for k in ("ih", "iw", "nw", "nh", "dx", "dy"):
+        out[k] = table[k]
+    if table.dtype == AUG_DTYPE:
+        out["flip"] = table["flip"] != 0
+    out["count"] = counts
+    out["P"] = P.reshape(B, 12)
+    return out
+
+
+def radar_view_bytes(views):
+    """A `radar_views` table as the (B, hip.RADAR_VIEW_BYTES) uint8 host tensor the device takes; it shares the table's memory."""
+    return torch.from_numpy(views.view(np.uint8).reshape(len(views), -1))
+
+
+def pack_points(points, max_points):
+    """B arrays of (n_b, 7) float32 rows x, y, z, f0, f1, f2, f3 (None or empty: no points), or a pair (padded (B, n, 7)
+    float32 array, counts (B) integers) -> the pinned host pair (B, max_points, 7) float32 and (B,) int32 that `hip.radar_map`
+    takes after one non-blocking copy (the counts travel in the view table); unused rows are zero.  Raises RuntimeError naming
+    the image for more than max_points rows, a type other than float32 and a wrong shape -- before anything is written."""
+    max_points = int(max_points)
+    if max_points < 1:
+        raise RuntimeError(f"pack_points: max_points must be positive, got {max_points}")
+
+    def host(a):
+        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    if isinstance(points, tuple) and len(points) == 2 and not isinstance(points[0], (list, tuple)) and \
+            getattr(points[0], "ndim", 0) == 3:
+        padded, cnt = host(points[0]), host(points[1])
+        if padded.dtype != np.float32 or padded.shape[2] != 7:
+            raise RuntimeError(f"pack_points: a padded buffer is float32 of shape (B, n, 7), got {padded.dtype} {padded.shape}")
+        if cnt.shape != (padded.shape[0],) or not np.issubdtype(cnt.dtype, np.integer):
+            raise RuntimeError(f"pack_points: counts are {padded.shape[0]} integers, got {cnt.dtype} {cnt.shape}")
+        for b, n in enumerate(cnt.tolist()):
+            if not 0 <= n <= padded.shape[1]:
+                raise RuntimeError(f"pack_points: image {b}: counts says {n} points, the padded buffer holds {padded.shape[1]}")
+        points = [padded[b, :n] for b, n in enumerate(cnt.tolist())]
+    elif not isinstance(points, (list, tuple)):
+        raise RuntimeError("pack_points: expected a list of (n, 7) float32 arrays, or a pair (padded (B, n, 7) array, counts)")
+    rows = []
+    for b, a in enumerate(points):
+        if a is None:
+            rows.append(None)
+            continue
+        a = host(a)
+        if a.size == 0:
+            rows.append(None)
+            continue
+        if a.dtype != np.float32:
+            raise RuntimeError(f"pack_points: image {b}: points are float32 rows x, y, z, f0, f1, f2, f3, got {a.dtype}")
+        if a.ndim != 2 or a.shape[1] != 7:
+            raise RuntimeError(f"pack_points: image {b}: expected (n, 7) rows x, y, z, f0, f1, f2, f3, got {a.shape}")
+        if a.shape[0] > max_points:
+            raise RuntimeError(f"pack_points: image {b} has {a.shape[0]} points, above max_points = {max_points}")
+        rows.append(a)
+    B = len(rows)
+    out = torch.zeros((B, max_points, 7), dtype=torch.float32)
+    counts = torch.zeros(B, dtype=torch.int32)
+    if torch.cuda.is_available():
+        out, counts = out.pin_memory(), counts.pin_memory()
+    for b, a in enumerate(rows):
+        if a is not None:
+            out[b, :len(a)] = torch.from_numpy(np.ascontiguousarray(a))
+            counts[b] = len(a)
+    return out, counts
+
+
+def radar_project(points, P, size, window, min_depth=0.1):
+    """The per-point half of `radar_map`, in float32: (kept (n) bool, ix (n) int64, iy (n) int64, hw (n) float32) -- the window
+    pixel of every point and its depth; ix, iy are 0 where a point is not kept."""
+    f32 = np.float32
+    md = check_radar_rule(0, min_depth)[1]
+    pts, P = np.asarray(points), np.asarray(P)
+    if pts.ndim != 2 or pts.shape[1] != 7 or pts.dtype != np.float32:
+        raise RuntimeError(f"radar_map: points are (n, 7) float32 rows x, y, z, f0, f1, f2, f3, got {pts.dtype} {pts.shape}")
+    if P.shape != (3, 4) or P.dtype != np.float32:
+        raise RuntimeError(f"radar_map: P is a (3, 4) float32 projection, got {P.dtype} {P.shape}")
+    ih, iw = (int(v) for v in size)
+    nw, nh = int(window[0]), int(window[1])
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    with np.errstate(all="ignore"):
+        hu, hv, hw = (((P[r, 0] * x + P[r, 1] * y) + P[r, 2] * z) + P[r, 3] for r in range(3))
+        ok = (hw >= md) & np.isfinite(hw) & np.isfinite(hu) & np.isfinite(hv)
+        den = np.where(ok, hw, f32(1))
+        fx = ((hu / den) * f32(nw)) / f32(iw)
+        fy = ((hv / den) * f32(nh)) / f32(ih)
+        assert hw.dtype == f32 and fx.dtype == f32 and fy.dtype == f32
+        ok &= (fx >= 0) & (fx < f32(nw)) & (fy >= 0) & (fy < f32(nh))
+    ix = np.where(ok, np.floor(fx), 0).astype(np.int64)
+    iy = np.where(ok, np.floor(fy), 0).astype(np.int64)
+    return ok, ix, iy, hw
+
+
+def radar_map(points, P, size, input_shape, window, flip=False, radius=0, min_depth=0.1):
+    """The network's radar input (4, H, W) float32 of ONE image from its radar points -- this project's own definition, the
+    reference has none.  points (n, 7) float32 rows x, y, z, f0, f1, f2, f3: the position in the radar's frame and the four
+    features in the order of the map's channels (the reference names range, velocity, elevation and power).  P (3, 4)
+    float32 maps (x, y, z, 1) to homogeneous CONTINUOUS pixel coordinates of the original frame of size = (ih, iw), source
+    pixel (i, j) covering [i, i + 1) x [j, j + 1); a calibration in OpenCV's convention (pixel centres on integers) adds half
+    of row 2 to rows 0 and 1 first.  window = (nw, nh, dx, dy) on the input_shape = (H, W) canvas is the one the frame went
+    through: `letterbox_geometry`'s, (W, H, 0, 0) for letterbox_image=False, or the nw, nh, dx, dy and flip of an augmentation
+    record (larger than the canvas and negative offsets included).  Everything in float32, every operation rounded on its
+    own, in this order:
+        hu = ((P00 x + P01 y) + P02 z) + P03, hv and hw likewise from rows 1 and 2
+        kept when hw >= min_depth and hw, hu, hv are finite (a NaN anywhere rejects)
+        u = hu / hw, v = hv / hw; fx = (u float(nw)) / float(iw), fy = (v float(nh)) / float(ih)
+        kept when 0 <= fx < nw and 0 <= fy < nh; ix = floor(fx), iy = floor(fy)
+        X = W - 1 - dx - ix when flip, else dx + ix; Y = dy + iy        (the whole canvas is mirrored, as `augment_radar` does)
+    A kept point covers the pixels (X + ox, Y + oy), |ox|, |oy| <= radius (0..8), inside the canvas and inside the window's
+    extent on the canvas (mirrored under flip): nothing is written outside the window.  Of the points covering a pixel the
+    one with the smallest hw wins, the lowest index among equal hw; out[c, Y, X] = f_c of the winner, copied bit for bit, 0
+    where no point lands.  The min-max normalisation of the prediction scripts stays `device_radar(normalise=True)`."""
+    radius = check_radar_rule(radius, min_depth)[0]
+    H, W = (int(v) for v in input_shape)
+    ih, iw = (int(v) for v in size)
+    nw, nh, dx, dy = (int(v) for v in window)
+    pts = np.ascontiguousarray(points)
+    out = np.zeros((4, H, W), np.uint32)
+    if min(ih, iw, nw, nh) <= 0:
+        return out.view(np.float32)
+    ok, ix, iy, hw = radar_project(pts, P, (ih, iw), (nw, nh), min_depth)
+    bits = np.ascontiguousarray(pts[:, 3:7]).view(np.uint32)
+    depth = hw.view(np.uint32)
+    best = np.full((H, W), np.iinfo(np.uint64).max, np.uint64)
+    for i in np.flatnonzero(ok).tolist():
+        cx, cy = dx + int(ix[i]), dy + int(iy[i])
+        x0, x1 = max(cx - radius, 0, dx), min(cx + radius, W - 1, dx + nw - 1)
+        y0, y1 = max(cy - radius, 0, dy), min(cy + radius, H - 1, dy + nh - 1)
+        if x0 > x1 or y0 > y1:
+            continue
+        key = np.uint64((int(depth[i]) << 32) | i)
+        xs = slice(W - 1 - x1, W - x0) if flip else slice(x0, x1 + 1)
+        won = best[y0:y1 + 1, xs] > key              # hw > 0 and finite: its bits order as an integer; the index breaks ties
+        best[y0:y1 + 1, xs][won] = key
+        for c in range(4):
+            out[c, y0:y1 + 1, xs][won] = bits[i, c]
+    return out.view(np.float32)
+
+
+def device_radar_map(points, sizes, input_shape, calib, letterbox_image=True, radius=0, min_depth=0.1, max_points=None,
+                     views=None, device="cuda", out=None, flag=None):
+    """`radar_map` for a batch ON THE DEVICE (vrnet_radar_map_f32, three launches): points as `pack_points` takes them, sizes
+    (B, 2) = (ih, iw) of the original frames, calib (3, 4) or (B, 3, 4) -> (B, 4, H, W) float32 on the device, bit for bit what
+    `radar_map` gives per image under the letterbox window of its frame (the whole canvas with letterbox_image=False).
+    max_points: the capacity of the point buffer (default: the largest count).  views: a `radar_views` table to use instead
+    (an augmentation's windows; its counts are replaced by the points' own); sizes and calib are then not read.  flag: an int32
+    device word that receives hip.FLAG_GEOMETRY / hip.FLAG_POINT_COUNT (never, for a table this function built).  The
+    points and the table are copied non_blocking; no host synchronisation."""
+    from . import hip
+    fn = "device_radar_map"
+    radius, md = check_radar_rule(radius, min_depth, fn)
+    H, W = (int(v) for v in input_shape)
+    if max_points is None:
+        if isinstance(points, tuple) and len(points) == 2 and getattr(points[0], "ndim", 0) == 3:
+            max_points = max(int(points[0].shape[1]), 1)
+        else:
+            max_points = max([1] + [0 if a is None else len(a) for a in points])
+    packed, counts = pack_points(points, max_points)
+    B = len(counts)
+    if views is None:
+        table = frame_geometry(frame_sizes(sizes, B, fn), (H, W), letterbox_image, fn=fn)
+        views = radar_views(table, calib, counts.numpy())
+    else:
+        views = np.array(views, copy=True)
+        if views.dtype != RADAR_VIEW_DTYPE or views.shape != (B,):
+            raise RuntimeError(f"{fn}: views is a ({B},) array of data.RADAR_VIEW_DTYPE records")
+        views["count"] = counts.numpy()
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((B, 4, H, W), dtype=torch.float32, device=dev)
+        hip.radar_map(packed.to(dev, non_blocking=True), radar_view_bytes(views).to(dev, non_blocking=True), H, W, radius,
+                      float(md), out, flag=flag)
+    return out
+
+
 def make_sample(image, box, radar, png, num_classes_seg):
     """YoloDataset.__getitem__ after augmentation (dataloader.py:88-107): (image CHW float64, boxes cxcywh, radar,
     png, one-hot)."""

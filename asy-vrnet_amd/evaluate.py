@@ -169,11 +169,13 @@ class EvalPipeline(infer.FramePipeline):
 
     ragged=True (with max_taps, as `infer.FramePipeline`): frame_shape is the capacity, every image has its own size, and
     `add` takes frames and label maps as lists of arrays (or padded buffers with sizes).  labels_u8 is filled with 255
-    outside each image, which the confusion matrix skips, so only an image's own pixels are counted."""
+    outside each image, which the confusion matrix skips, so only an image's own pixels are counted.
+
+    radar_points / radar_radius / radar_min_depth / calib: as `infer.FramePipeline`; `add` then takes radar points."""
 
     def __init__(self, model, frame_shape, input_shape, class_names, num_seg_classes, batch=1, capacity=None, max_boxes=100,
                  max_gt=64, conf_thres=0.05, nms_thres=0.5, letterbox_image=True, max_candidates=1024, normalise_radar=False,
-                 graph=True, ragged=False, max_taps=None):
+                 graph=True, ragged=False, max_taps=None, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None):
         infer.validate_config(model, frame_shape, input_shape, batch, max_candidates)
         self.class_names, self.num_seg_classes, self.capacity, self.max_boxes, self.max_gt = validate_eval_config(
             class_names, num_seg_classes, batch, capacity, max_boxes, max_gt, conf_thres)
@@ -194,7 +196,8 @@ class EvalPipeline(infer.FramePipeline):
         self.hist = torch.zeros((self.num_seg_classes, self.num_seg_classes), dtype=torch.int64, device=dev)
         super().__init__(model, frame_shape, input_shape, batch=batch, conf_thres=conf_thres, nms_thres=nms_thres,
                          letterbox_image=letterbox_image, max_candidates=max_candidates, normalise_radar=normalise_radar,
-                         render=False, graph=graph, ragged=ragged, max_taps=max_taps)
+                         render=False, graph=graph, ragged=ragged, max_taps=max_taps, radar_points=radar_points,
+                         radar_radius=radar_radius, radar_min_depth=radar_min_depth, calib=calib)
 
     def _tail(self, result):
         from . import hip, metrics
@@ -216,21 +219,26 @@ class EvalPipeline(infer.FramePipeline):
             t.zero_()
         self.image_ids = []
 
-    def add(self, image_ids, frames_u8, radar, label_maps, gt_boxes, sizes=None):
+    def add(self, image_ids, frames_u8, radar, label_maps, gt_boxes, sizes=None, calib=None):
         """One batch: image_ids, a list of B strings (a duplicate raises); frames_u8 (B, ih, iw, 3) uint8 RGB and radar
         (B, 4, H, W), as `FramePipeline.run`; label_maps (B, ih, iw) uint8; gt_boxes, a list of B integer (n, 5) arrays x1,
         y1, x2, y2, class as `data.parse_annotation_line` returns.  Validates on the host, copies into the static buffers
         (non_blocking) and replays the graph (graph=False: runs the chain); no host synchronisation.  Returns the
         `infer.FrameResult` of the batch.  A ragged pipeline takes frames_u8 and label_maps as `FramePipeline.run` takes its
-        frames (lists of arrays of their own sizes, or padded buffers with sizes)."""
+        frames (lists of arrays of their own sizes, or padded buffers with sizes).  A pipeline built with radar_points takes
+        radar POINTS and calib as `FramePipeline.run` does."""
         table = None
+        if calib is not None and self.radar_points is None:
+            raise RuntimeError("EvalPipeline: calib belongs to a pipeline built with radar_points")
         if self.ragged:
             f, r, sizes, table = infer.validate_ragged_inputs(frames_u8, radar, sizes, self.batch, self.frame_shape,
-                                                              self.input_shape, self.letterbox_image, self.max_taps)
+                                                              self.input_shape, self.letterbox_image, self.max_taps,
+                                                              self.radar_points, calib)
         else:
             if sizes is not None:
                 raise RuntimeError("EvalPipeline: sizes belong to a ragged pipeline (ragged=True)")
-            f, r = infer.validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape)
+            f, r = infer.validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape, self.radar_points,
+                                         calib, self.letterbox_image)
         ids, labels, packed = validate_add(image_ids, set(self.image_ids), label_maps, gt_boxes, self.batch, self.frame_shape,
                                            len(self.class_names), self.max_gt, sizes)
         if len(self.image_ids) + self.batch > self.capacity:

@@ -217,6 +217,19 @@ class TrainStep(GraphedStep):
     caller's own sampler; the step's generator is then not advanced).  The table is validated on the host with the rest,
     before anything is enqueued.  max_taps defaults to `data.default_aug_max_taps`.  augment without from_frames raises.
 
+    With from_frames=True and radar_points=max_points the step takes radar POINTS where it took maps:
+
+        step = TrainStep(..., from_frames=True, capacity=(ihm, iwm), radar_points=4096, radar_radius=0, radar_min_depth=0.1, calib=P)
+        res = step(frames, points, boxes, labels, sizes=None, aug=None, calib=None)
+
+    points: B arrays of (n_b, 7) float32 rows x, y, z, f0..f3, or a pair (padded array, counts) (`data.pack_points`); calib: the
+    (3, 4) or (B, 3, 4) projection of `data.radar_map`, per call or from the constructor.  vrnet_radar_map_f32 (three launches)
+    writes the radar input inside graph 0 by the rule of `data.radar_map`: without augment under the window of the geometry
+    table, with augment under the window and flip of that call's augmentation table, in place of vrnet_augment_radar_f32 --
+    every point moves exactly once, where the gather of a finished map duplicates or drops points.  Points and the view
+    table go up through fresh pinned staging tensors; the kernel's bits (hip.FLAG_GEOMETRY, hip.FLAG_POINT_COUNT) join the
+    step's flag word.  radar_points without from_frames raises.
+
     Two kinds of graph.  The forward / backward graph(s) are GraphedStep's (three segments under data parallelism, the
     all-reduces between them); the loss closure is `losses.training_loss_packed` on the static buffers, followed by the
     f-score (f_score=True) and the addition of the step's values to a running fp64 sum.  The UPDATE graph is always its own:
@@ -242,8 +255,16 @@ class TrainStep(GraphedStep):
 
     def __init__(self, net, yolo_loss, optimizer, ema, batch, size, num_seg_classes, max_gt=64, cls_weights=None,
                  focal_loss=True, dice_loss=True, f_score=False, from_bytes=False, device="cuda", warmup=2, segments=None,
-                 from_frames=False, capacity=None, max_taps=None, letterbox_image=True, augment=None, aug_seed=None):
+                 from_frames=False, capacity=None, max_taps=None, letterbox_image=True, augment=None, aug_seed=None,
+                 radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None):
         optimizer._uniform("lr")
+        if radar_points is not None and not from_frames:
+            raise RuntimeError("TrainStep: radar_points needs from_frames=True (the points are projected into the frame's window)")
+        if radar_points is None and (calib is not None or radar_radius != 0 or radar_min_depth != 0.1):
+            raise RuntimeError("TrainStep: calib, radar_radius and radar_min_depth belong to radar_points=max_points")
+        from .infer import RadarPoints
+        self.radar_points = None if radar_points is None else RadarPoints(radar_points, radar_radius, radar_min_depth, calib,
+                                                                          int(batch), "TrainStep")
         if augment is not None and augment is not False and not from_frames:
             raise RuntimeError("TrainStep: augment needs from_frames=True (the augmentation starts from the raw frames)")
         if augment is not None and augment is not False and not letterbox_image:
@@ -299,7 +320,11 @@ class TrainStep(GraphedStep):
             rec = data.aug_record(self.capacity, self.hw, *data.letterbox_geometry(iwm, ihm, w, h))
             self.aug_table = data.check_aug_table(np.stack([rec] * B), self.hw, self.capacity, self.max_taps, "TrainStep")
             self.aug = data.augment_bytes(self.aug_table).to(dev)
-            self.radar_in = torch.zeros((B, 4, h, w), dtype=torch.float32, device=dev)
+            if self.radar_points is None:
+                self.radar_in = torch.zeros((B, 4, h, w), dtype=torch.float32, device=dev)
+        if self.radar_points is not None:    # no points in the warm-up and the capture
+            self.points, self.views = self.radar_points.buffers(table if self.augment is None else self.aug_table, dev)
+            self._radar_ws = self.radar_points.workspace(self.hw, dev)
         self.frames_u8 = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
         self.frame_labels_u8 = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
         self.boxes = torch.zeros((B, max(self.max_gt, 1), 5), dtype=torch.int32, device=dev)
@@ -318,7 +343,8 @@ class TrainStep(GraphedStep):
                                     flag=self.flag)
             hip.augment_box_targets(self.boxes, self.box_counts, self.aug, self.capacity, h, w, targets=self.labels,
                                     counts_out=self.counts, flag=self.flag)
-            hip.augment_radar(self.radar_in, self.aug, self.capacity, out=self.r, flag=self.flag)
+            if self.radar_points is None:
+                hip.augment_radar(self.radar_in, self.aug, self.capacity, out=self.r, flag=self.flag)
         elif self.from_frames:
             h, w = self.hw
             hip.letterbox_ragged(self.frames_u8, None, self.geom, h, w, self.max_taps, images=self.x, flag=self.flag,
@@ -327,6 +353,10 @@ class TrainStep(GraphedStep):
                                    flag=self.flag)
             hip.box_targets_ragged(self.boxes, self.box_counts, self.geom, self.capacity, h, w, targets=self.labels,
                                    counts_out=self.counts, flag=self.flag)
+        if self.radar_points is not None:    # the points of each image under the window (and flip) its frame just went through
+            h, w = self.hw
+            hip.radar_map(self.points, self.views, h, w, self.radar_points.radius, float(self.radar_points.min_depth), self.r,
+                          flag=self.flag, ws=self._radar_ws)
 
     def _loss(self, det, seg):
         total, ldet, lseg = losses.training_loss_packed(self.yolo_loss, det, seg, self.labels, self.counts, self.max_gt, self.png,
@@ -398,7 +428,7 @@ class TrainStep(GraphedStep):
         packed, counts = losses.pack_targets(targets, self.max_gt)        # raises, naming the image, above max_gt
         return images, radar, pngs, seg_labels, packed, counts
 
-    def _validate_frames(self, frames, radar, boxes, labels, sizes, aug=None):
+    def _validate_frames(self, frames, radar, boxes, labels, sizes, aug=None, calib=None):
         """The host checks of a from_frames call, which need no device; returns what the copies take, the geometry table
         (with augment: the augmentation table, drawn here unless the caller brought one) among it."""
         B, (h, w), fn = self.batch, self.hw, "TrainStep"
@@ -415,9 +445,14 @@ class TrainStep(GraphedStep):
             table = data.check_aug_params(aug, own, self.hw, self.capacity, self.max_taps, fn)
         else:
             table = None                     # drawn last, below: a call that raises for another reason draws nothing
-        radar = self._tensor(radar)
-        if tuple(radar.shape) != (B, 4, h, w) or radar.dtype != torch.float32:
-            raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(B, 4, h, w)}, got {radar.dtype} {tuple(radar.shape)}")
+        if calib is not None and self.radar_points is None:
+            raise RuntimeError(f"{fn}: calib belongs to a step built with radar_points")
+        if self.radar_points is None:
+            radar = self._tensor(radar)
+            if tuple(radar.shape) != (B, 4, h, w) or radar.dtype != torch.float32:
+                raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(B, 4, h, w)}, got {radar.dtype} {tuple(radar.shape)}")
+        else:                                # the views follow the table, which may yet be drawn
+            radar = self.radar_points.validate(radar, None, calib)
         if len(boxes) != B:
             raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
         packed, counts = data.pack_boxes(boxes, self.max_gt)              # raises, naming the image
@@ -426,17 +461,19 @@ class TrainStep(GraphedStep):
             # draws anew
             table = data.augment_params(own, self.hw, self._aug_rng, capacity=self.capacity, max_taps=self.max_taps, fn=fn,
                                         **self.augment)
+        if self.radar_points is not None:
+            radar = radar[0], self.radar_points.views(table, radar[1])
         return items, labs, own, table, radar, packed, counts
 
-    def __call__(self, images, radar, targets, pngs, seg_labels=None, sizes=None, aug=None):
+    def __call__(self, images, radar, targets, pngs, seg_labels=None, sizes=None, aug=None, calib=None):
         if self.from_frames:                 # step(frames, radar, boxes, labels, sizes=None, aug=None)
             if seg_labels is not None and sizes is not None:
                 raise RuntimeError("TrainStep: from_frames=True takes (frames, radar, boxes, labels, sizes)")
             items, labs, own, table, radar, packed, counts = self._validate_frames(
-                images, radar, targets, pngs, seg_labels if sizes is None else sizes, aug)
+                images, radar, targets, pngs, seg_labels if sizes is None else sizes, aug, calib)
         else:
-            if sizes is not None or aug is not None:
-                raise RuntimeError("TrainStep: sizes and aug belong to from_frames=True")
+            if sizes is not None or aug is not None or calib is not None:
+                raise RuntimeError("TrainStep: sizes, aug and calib belong to from_frames=True")
             images, radar, pngs, seg_labels, packed, counts = self._validate(images, radar, targets, pngs, seg_labels)
         opt, ema = self.optimizer, self.ema
         lr = float(opt._uniform("lr"))
@@ -469,7 +506,12 @@ class TrainStep(GraphedStep):
                 if seg_labels is not None:
                     self.onehot.copy_(seg_labels, non_blocking=True)
             # with augment the radar maps go through vrnet_augment_radar_f32, which writes self.r inside graph 0
-            (self.r if self.augment is None else self.radar_in).copy_(radar, non_blocking=True)
+            # and radar points through vrnet_radar_map_f32, likewise
+            if self.radar_points is not None:
+                self.points.copy_(radar[0], non_blocking=True)
+                self.views.copy_(radar[1].pin_memory(), non_blocking=True)
+            else:
+                (self.r if self.augment is None else self.radar_in).copy_(radar, non_blocking=True)
             if not self.from_frames:
                 self.labels.copy_(packed, non_blocking=True)
                 self.counts.copy_(counts, non_blocking=True)

@@ -153,6 +153,8 @@ _SIGS = {
     "vrnet_augment_seg_targets_u8": ([P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_augment_box_targets_f32": ([P, P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_augment_radar_f32": ([P, P, I, I, I, I, I, P, P, P], I),
+    "vrnet_radar_map_workspace": ([I, I, I], L),
+    "vrnet_radar_map_f32": ([P, I, P, I, I, I, I, F, P, P, P, L, P], I),
     "vrnet_heatmap_workspace": ([I, I, I], L),
     "vrnet_heatmap_f32": ([P, P, P] + [I] * 11 + [P, P, F, P, P, P, P, L, P], I),
     "vrnet_heatmap_ragged_workspace": ([I, I, I], L),
@@ -1512,4 +1514,45 @@ def augment_radar(radar, aug, capacity, out=None, flag=None):
     _tensors("augment_radar", ((radar, (B, 4, H, W), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
     _check(_lib.vrnet_augment_radar_f32(ptr(radar), _aug(aug, B, "augment_radar"), B, int(capacity[0]), int(capacity[1]), H, W,
                                         ptr(out), ptr(flag), stream()), "augment_radar")
+    return out
+
+
+# ---- the radar map from 4D radar points (include/vrnet_hip.h "the radar map from 4D radar points") -------------------------
+RADAR_VIEW_BYTES = 80    # sizeof(vrnet_radar_view)
+FLAG_POINT_COUNT = 1024  # VR_FLAG_POINT_COUNT of csrc/common.h: radar_map clamped a count outside [0, max_points]
+RADAR_MAX_RADIUS = 8
+
+
+def _views(views, B, fn):
+    """The table: a contiguous uint8 GPU tensor (B, RADAR_VIEW_BYTES), 8-byte aligned (`data.radar_views` packs it)."""
+    if views is None or views.dtype != torch.uint8 or tuple(views.shape) != (B, RADAR_VIEW_BYTES) or not views.is_contiguous() or \
+            not views.is_cuda or views.data_ptr() % 8:
+        raise RuntimeError(f"{fn}: the view table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape ({B}, {RADAR_VIEW_BYTES})")
+    return ptr(views)
+
+
+def radar_map_workspace_bytes(B, H, W):
+    return _lib.vrnet_radar_map_workspace(B, H, W)
+
+
+def radar_map(points, views, H, W, radius, min_depth, out, flag=None, ws=None):
+    """Radar points -> the network's radar input (vrnet_radar_map_f32): points (B, max_points, 7) f32 rows x, y, z, f0..f3,
+    views the (B, RADAR_VIEW_BYTES) table -> out (B, 4, H, W) f32, what `data.radar_map` gives per image, bit for bit; radius
+    0..8, min_depth > 0; flag (1) int32 or None: FLAG_GEOMETRY for a record without pixels, FLAG_POINT_COUNT for a clamped
+    count; ws: radar_map_workspace_bytes(B, H, W) bytes.  Three launches.  Returns out."""
+    if points is None or points.dim() != 3 or points.shape[2] != 7 or points.shape[1] < 1:
+        raise RuntimeError("radar_map: expected points (B, max_points, 7)")
+    B, max_points = points.shape[:2]
+    H, W = int(H), int(W)
+    _tensors("radar_map", ((points, (B, max_points, 7), torch.float32), (out, (B, 4, H, W), torch.float32),
+                           (flag, (1,), torch.int32)))
+    if out is None:
+        raise RuntimeError("radar_map: out is required")
+    need = _lib.vrnet_radar_map_workspace(B, H, W)
+    if ws is None:
+        ws = _ws.get(need, points.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"radar_map: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    _check(_lib.vrnet_radar_map_f32(ptr(points), max_points, _views(views, B, "radar_map"), B, H, W, int(radius), float(min_depth),
+                                    ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), "radar_map")
     return out

@@ -29,6 +29,7 @@ from . import render as rendering
 
 FLAG_CANDIDATES, FLAG_DET_CLASS = 8, 16          # NMS_FLAG_* of csrc/nms.hip, above render.FLAG_*
 FLAG_GEOMETRY = 256                              # VR_FLAG_GEOMETRY of csrc/common.h, above evaluate.FLAG_EVAL_*
+FLAG_POINT_COUNT = 1024                          # VR_FLAG_POINT_COUNT of csrc/common.h (a pipeline built with radar_points)
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -52,13 +53,18 @@ def validate_config(model, frame_shape, input_shape, batch, max_candidates):
     return (ih, iw), (H, W), int(batch), int(max_candidates)
 
 
-def validate_inputs(frames_u8, radar, batch, frame_shape, input_shape):
+def validate_inputs(frames_u8, radar, batch, frame_shape, input_shape, radar_points=None, calib=None, letterbox_image=True):
     """frames (B, ih, iw, 3) uint8 and radar (B, 4, H, W) float32 / float64, numpy arrays or tensors, of exactly the
-    shapes the pipeline was built for (with batch 1 the leading axis may be missing); returns them as tensors."""
+    shapes the pipeline was built for (with batch 1 the leading axis may be missing); returns them as tensors.
+    radar_points (a `RadarPoints`): radar holds points, and the pair `RadarPoints.validate` gives is returned for it."""
     f = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
     if f.dtype != torch.uint8:
         raise RuntimeError(f"FramePipeline: expected uint8 frames, got {f.dtype}")
-    r = validate_radar(radar, batch, input_shape)
+    if radar_points is not None:
+        r = radar_points.validate(radar, data.frame_geometry([tuple(frame_shape)] * batch, input_shape, letterbox_image,
+                                                             fn="FramePipeline"), calib)
+    else:
+        r = validate_radar(radar, batch, input_shape)
     f = f[None] if batch == 1 and f.dim() == 3 else f
     want_f = (batch,) + tuple(frame_shape) + (3,)
     if tuple(f.shape) != want_f:
@@ -78,18 +84,67 @@ def validate_radar(radar, batch, input_shape):
     return r
 
 
-def validate_ragged_inputs(frames, radar, sizes, batch, capacity, input_shape, letterbox_image=True, max_taps=None):
+class RadarPoints:
+    """The radar half of a pipeline built with radar_points: what every call brings in place of finished maps.  max_points is
+    the capacity of the static point buffer, radius / min_depth the rule of `data.radar_map`, calib the default (3, 4) or
+    (B, 3, 4) projection (a call may bring its own).  Host only, but for `buffers` and `workspace`."""
+
+    def __init__(self, max_points, radius=0, min_depth=0.1, calib=None, batch=1, fn="FramePipeline"):
+        if isinstance(max_points, bool) or not isinstance(max_points, (int, np.integer)) or not 1 <= int(max_points) <= 1 << 24:
+            raise RuntimeError(f"{fn}: radar_points is the capacity of the point buffer, an integer in 1..{1 << 24}, got {max_points!r}")
+        self.max_points, self.batch, self.fn = int(max_points), int(batch), fn
+        self.radius, self.min_depth = data.check_radar_rule(radius, min_depth, fn)
+        self.calib = None if calib is None else data.check_calib(calib, self.batch, fn)
+
+    def validate(self, points, table, calib=None):
+        """points as `data.pack_points` takes them, the geometry or augmentation table of the call -> (the pinned (B,
+        max_points, 7) tensor, the (B, hip.RADAR_VIEW_BYTES) uint8 view table).  table=None: a table that does not exist yet."""
+        if (torch.is_tensor(points) or isinstance(points, np.ndarray)) and points.ndim == 4:
+            raise RuntimeError(f"{self.fn}: built with radar_points: a call brings radar POINTS, B arrays of (n, 7) float32 rows, "
+                               "not finished maps")
+        P = self.calib if calib is None else data.check_calib(calib, self.batch, self.fn)
+        if P is None:
+            raise RuntimeError(f"{self.fn}: radar points need a projection: calib=(3, 4) or (B, 3, 4), here or at construction")
+        packed, counts = data.pack_points(points, self.max_points)
+        if len(counts) != self.batch:
+            raise RuntimeError(f"{self.fn}: {len(counts)} point sets for a batch of {self.batch}")
+        if table is None:                    # the caller's table follows: `views` finishes the pair
+            return packed, (P, counts)
+        return packed, self.views(table, (P, counts))
+
+    @staticmethod
+    def views(table, checked):
+        """The view table from what `validate(points, None)` returned beside the points."""
+        return data.radar_view_bytes(data.radar_views(table, checked[0], checked[1].numpy()))
+
+    def buffers(self, table, device):
+        """The static device buffers (points, views) of a pipeline, on a table without points."""
+        B = self.batch
+        P = self.calib if self.calib is not None else np.zeros((B, 3, 4), np.float32)
+        views = data.radar_view_bytes(data.radar_views(table, P, np.zeros(B, np.int32))).to(device)
+        return torch.zeros((B, self.max_points, 7), dtype=torch.float32, device=device), views
+
+    def workspace(self, input_shape, device):
+        from . import hip
+        return torch.empty(hip.radar_map_workspace_bytes(self.batch, *input_shape), dtype=torch.uint8, device=device)
+
+
+def validate_ragged_inputs(frames, radar, sizes, batch, capacity, input_shape, letterbox_image=True, max_taps=None,
+                           radar_points=None, calib=None):
     """The host checks of a ragged `run`, which need no device: frames as a list of `batch` uint8 arrays (ih_b, iw_b, 3) of
     their own sizes (sizes optional, checked when given) or a padded (batch, ihp, iwp, 3) buffer with sizes (batch, 2);
     every size inside the capacity, with a non-empty window and within the tap capacity (`data.frame_geometry`: each
     error names the image index).  Returns (frames as `data.ragged_items` gives them, radar tensor, sizes (B, 2) int64,
-    the geometry table)."""
+    the geometry table).  radar_points (a `RadarPoints`): radar holds points, and the radar tensor returned is the pair
+    `RadarPoints.validate` gives."""
     fn = "FramePipeline"
     items, own = data.ragged_items(frames, sizes, batch, (3,), "frames", fn)
     if torch.is_tensor(items) and (items.shape[1] > capacity[0] or items.shape[2] > capacity[1]):
         raise RuntimeError(f"{fn}: the padded buffer {tuple(items.shape[1:3])} is above the capacity {tuple(capacity)}")
     max_taps = data.default_max_taps(capacity, input_shape) if max_taps is None else max_taps
     table = data.frame_geometry(own, input_shape, letterbox_image, capacity, max_taps, fn)
+    if radar_points is not None:
+        return items, radar_points.validate(radar, table, calib), own, table
     return items, validate_radar(radar, batch, input_shape), own, table
 
 
@@ -168,14 +223,30 @@ class FramePipeline:
     (inside the capacity, non-empty window, taps within max_taps: `data.default_max_taps`), each frame is copied into the
     corner of its slot of `frames_u8` and the geometry table into `geom`, all non_blocking, and the ONE graph is replayed:
     no recapture, no host synchronisation, no per-size cache.  The results are padded (see `FrameResult`).  The radar stays
-    (B, 4, H, W)."""
+    (B, 4, H, W).
+
+    radar_points=max_points: run(frames, points, sizes=None, calib=None) takes radar POINTS where it took maps -- per image
+    (n_b, 7) float32 rows x, y, z, f0, f1, f2, f3 with n_b <= max_points (`data.pack_points`) -- and calib, a (3, 4) or (B, 3, 4)
+    projection from the radar's frame to continuous pixel coordinates of the original frame (here, or per call).
+    vrnet_radar_map_f32, the first radar node of the chain, writes `radar` by the rule of `data.radar_map` under the window
+    each frame goes through (its letterbox window, or the whole input with letterbox_image=False), radar_radius 0..8 the half
+    width of a point's square footprint, radar_min_depth the nearest depth kept; normalise_radar still follows.  Fixed-size
+    and ragged pipelines alike; the static inputs are then `points` (B, max_points, 7) and `views` (B, 80).  FLAG_POINT_COUNT
+    (a count outside the buffer, which the host checks rule out) joins the bits of `flag`."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
-                 heat_alpha=0.5):
+                 heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
+        self.radar_points = None
+        if radar_points is not None:
+            if radar_dtype != torch.float32:
+                raise RuntimeError("FramePipeline: radar_points writes float32 maps; radar_dtype must be float32")
+            self.radar_points = RadarPoints(radar_points, radar_radius, radar_min_depth, calib, self.batch)
+        elif calib is not None or radar_radius != 0 or radar_min_depth != 0.1:
+            raise RuntimeError("FramePipeline: calib, radar_radius and radar_min_depth belong to radar_points=max_points")
         if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
             raise RuntimeError(f"FramePipeline: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
         if not 0.0 <= float(heat_alpha) <= 1.0:
@@ -208,6 +279,10 @@ class FramePipeline:
             table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, self.frame_shape,
                                         self.max_taps, "FramePipeline")
             self.geom = data.geometry_bytes(table).to(dev)
+        if self.radar_points is not None:     # the warm-up and the capture run on no points
+            table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, fn="FramePipeline")
+            self.points, self.views = self.radar_points.buffers(table, dev)
+            self._radar_ws = self.radar_points.workspace(self.input_shape, dev)
         self.cap = None                       # the NMS buffers follow the anchor count of the first (warm-up) pass
         self.graph = self.result = None
         if graph:
@@ -240,6 +315,9 @@ class FramePipeline:
             hip.letterbox_ragged(self.frames_u8, None, self.geom, H, W, self.max_taps, images=images, flag=self.flag)
         else:
             images, _ = data.device_letterbox(self.frames_u8, (H, W), letterbox_image=self.letterbox_image, device=dev)
+        if self.radar_points is not None:     # the first radar node: points -> self.radar under each frame's window
+            hip.radar_map(self.points, self.views, H, W, self.radar_points.radius, float(self.radar_points.min_depth), self.radar,
+                          flag=self.flag, ws=self._radar_ws)
         radar = data.device_radar(self.radar, True, dev) if self.normalise_radar else self.radar
         det, seg = self.model(images, radar)
         pred = decode.decode_outputs(det, (H, W))
@@ -311,19 +389,26 @@ class FramePipeline:
         with collector_held_off(), torch.no_grad(), torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
             self.result = self._chain()
 
-    def run(self, frames_u8, radar, sizes=None):
+    def run(self, frames_u8, radar, sizes=None, calib=None):
         """frames_u8 (B, ih, iw, 3) uint8 RGB and radar (B, 4, H, W) float32 / float64: numpy arrays or tensors, pageable,
         pinned or on the device -> FrameResult.  The inputs are copied into the static buffers (non_blocking), then the graph
         is replayed (graph=False: the chain is run); no host synchronisation.  A ragged pipeline takes frames_u8 as a list
-        of B arrays of their own sizes, or as a padded buffer with sizes (B, 2) = (ih_b, iw_b); the result carries `sizes`."""
+        of B arrays of their own sizes, or as a padded buffer with sizes (B, 2) = (ih_b, iw_b); the result carries `sizes`.
+        A pipeline built with radar_points takes radar POINTS where it took maps -- B arrays of (n_b, 7) float32 rows x, y, z,
+        f0..f3, or a pair (padded array, counts), as `data.pack_points` takes them -- and calib, the (3, 4) or (B, 3, 4)
+        projection of this call (default: the constructor's).  Points and the view table go up through fresh pinned staging
+        tensors, and vrnet_radar_map_f32, inside the graph, writes `radar` under the window of each frame."""
+        if calib is not None and self.radar_points is None:
+            raise RuntimeError("FramePipeline: calib belongs to a pipeline built with radar_points")
         if not self.ragged:
             if sizes is not None:
                 raise RuntimeError("FramePipeline: sizes belong to a ragged pipeline (ragged=True); this one is tied to frames of "
                                    f"{self.frame_shape[0]} x {self.frame_shape[1]}")
-            f, r = validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape)
+            f, r = validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape, self.radar_points, calib,
+                                   self.letterbox_image)
             return self._launch(f, r)
         return self._launch(*validate_ragged_inputs(frames_u8, radar, sizes, self.batch, self.frame_shape, self.input_shape,
-                                                    self.letterbox_image, self.max_taps))
+                                                    self.letterbox_image, self.max_taps, self.radar_points, calib))
 
     def _launch(self, f, r, sizes=None, table=None):
         """The copies and the replay of `run`, on inputs that `validate_inputs` / `validate_ragged_inputs` returned."""
@@ -334,7 +419,11 @@ class FramePipeline:
                 self.sizes = sizes
             else:
                 self.frames_u8.copy_(f, non_blocking=True)
-            self.radar.copy_(r, non_blocking=True)
+            if self.radar_points is not None:
+                self.points.copy_(r[0], non_blocking=True)
+                self.views.copy_(r[1].pin_memory(), non_blocking=True)
+            else:
+                self.radar.copy_(r, non_blocking=True)
             if self.graph is not None:
                 self.graph.replay()
             else:
@@ -347,7 +436,8 @@ class FramePipeline:
 def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     """predict.py's `dir_predict` mode on a ragged pipeline: every picture of the folder dir_origin_path whose name ends in
     one of IMAGE_EXTENSIONS (the reference's filter, lower case), in sorted order, with its radar maps
-    radar_root/<frame id>.npz (`data.load_radar` by `data.frame_id` of the file name), in batches of pipeline.batch.  A
+    radar_root/<frame id>.npz (`data.load_radar` by `data.frame_id` of the file name; for a pipeline built with radar_points
+    `arr_0` of that file holds the image's (n, 7) point rows instead), in batches of pipeline.batch.  A
     final partial batch is filled by repeating the last picture; the repeats are dropped here.  Returns a list of
     (file name, (N, 7) detections) in that order; with dir_save_path the rendered frame of every picture, sliced to its own
     size, is saved there as <stem>.png through Pillow (the reference renames .jpg to .png; here every picture is a PNG), and
@@ -374,7 +464,10 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         frames = [np.array(Image.open(os.path.join(dir_origin_path, n)).convert("RGB"), dtype=np.uint8) for n in chunk]
         radar = [np.asarray(data.load_radar(radar_root, data.frame_id(n)), dtype=np.float32) for n in chunk]
         fill = B - len(chunk)
-        result = pipeline.run(frames + frames[-1:] * fill, np.stack(radar + radar[-1:] * fill))
+        if getattr(pipeline, "radar_points", None) is not None:        # arr_0 holds the (n, 7) point rows
+            result = pipeline.run(frames + frames[-1:] * fill, radar + radar[-1:] * fill)
+        else:
+            result = pipeline.run(frames + frames[-1:] * fill, np.stack(radar + radar[-1:] * fill))
         dets = result.detections()
         rendered = None if dir_save_path is None or result.rendered is None else result.rendered.cpu().numpy()
         heat = None if dir_save_path is None else getattr(result, "heat_picture", None)

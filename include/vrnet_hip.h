@@ -1112,6 +1112,45 @@ int vrnet_augment_box_targets_f32(const int* boxes, const int* counts, const vrn
 int vrnet_augment_radar_f32(const float* radar, const vrnet_aug_rec* aug, int B, int ihm, int iwm, int H, int W, float* out,
                             int* flag, void* stream);
 
+/* ---- the radar map from 4D radar points (csrc/radarmap.hip) ---------------------------------------------------------------
+ * Added within ABI 11: new symbols and one new record layout (vrnet_radar_view) only, no existing signature, layout or kernel
+ * behaviour changed; hip.py binds every declared symbol at import.
+ * The step the reference's data instructions describe and ship no code for: "project 3D point clouds into 2D image plane,
+ * then make a numpy matrix with 4 x 512 x 512".  The rule is this project's definition (host statement: data.radar_map), and
+ * the kernels equal it bit for bit.  points (B, max_points, 7) fp32 rows x, y, z, f0, f1, f2, f3 -- the position in the radar's
+ * frame and the four features in the order of the map's channels; rows at or past the record's count are never read.
+ * views: one record per image.  P maps (x, y, z, 1) to homogeneous CONTINUOUS pixel coordinates of the original (ih, iw)
+ * frame, source pixel (i, j) covering [i, i + 1) x [j, j + 1) (a calibration with pixel centres on integers adds half of row
+ * 2 to rows 0 and 1).  The window nw x nh at (dx, dy) on the (H, W) canvas is the one the frame went through: the letterbox
+ * window, the whole canvas, or the window of an augmentation record, which may be larger than the canvas and start at
+ * negative offsets; flip mirrors the finished canvas.
+ * Per point, in float32, every operation rounded on its own in this order, nothing contracted:
+ *   hu = ((P00 x + P01 y) + P02 z) + P03, hv and hw likewise from rows 1 and 2
+ *   kept when hw >= min_depth and hw, hu, hv are finite (a NaN anywhere rejects)
+ *   u = hu / hw, v = hv / hw (correctly rounded); fx = (u float(nw)) / float(iw), fy = (v float(nh)) / float(ih)
+ *   kept when 0 <= fx < nw and 0 <= fy < nh; ix = floor(fx), iy = floor(fy)
+ *   X = flip ? W - 1 - dx - ix : dx + ix, Y = dy + iy
+ * A kept point covers the pixels (X + ox, Y + oy), |ox|, |oy| <= radius (0..8), that lie inside the canvas and inside the
+ * window's extent on the canvas (mirrored under flip); nothing is written outside the window.  Of the points covering a
+ * pixel the one with the smallest hw wins, the lowest index among equal hw; out[b][c][Y][X] = f_c of the winner, copied bit
+ * for bit, and 0 where no point lands.  out (B, 4, H, W) fp32.  The optional min-max normalisation of the prediction
+ * scripts stays vrnet_radar_normalise, chained behind.
+ * Three launches: keys (B, H, W) uint64 = ~0; one thread per point, a 64-bit atomic minimum of (bits(hw) << 32 | index) per
+ * covered pixel; one thread per pixel resolving the key to the winner's features.  Integer atomics only: the same bytes on
+ * every run; every call initialises its keys, so nothing carries over between calls.  No host synchronisation, no
+ * allocation, no memset; capturable.  workspace: vrnet_radar_map_workspace(B, H, W) bytes, 8-byte aligned.
+ * A record with ih, iw, nw or nh <= 0 gives a zero map for its image and sets bit 256 of *flag (VR_FLAG_GEOMETRY); a count
+ * outside [0, max_points] is clamped and sets bit 1024 (VR_FLAG_POINT_COUNT).  flag may be NULL. */
+typedef struct vrnet_radar_view {
+  int ih, iw;                        /* the original frame the projection is calibrated for */
+  int nw, nh, dx, dy;                /* the frame's window in the canvas; may leave the canvas on every side */
+  int flip, count;                   /* != 0: mirror the canvas left-right; the image's points */
+  float P[12];                       /* the (3, 4) projection, row-major */
+} vrnet_radar_view;                  /* 80 bytes; the table must be 8-byte aligned */
+long vrnet_radar_map_workspace(int B, int H, int W);
+int vrnet_radar_map_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W, int radius,
+                        float min_depth, float* out, int* flag, void* workspace, long workspace_bytes, void* stream);
+
 
 #ifdef __cplusplus
 }
