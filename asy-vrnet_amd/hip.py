@@ -155,6 +155,9 @@ _SIGS = {
     "vrnet_augment_radar_f32": ([P, P, I, I, I, I, I, P, P, P], I),
     "vrnet_radar_map_workspace": ([I, I, I], L),
     "vrnet_radar_map_f32": ([P, I, P, I, I, I, I, F, P, P, P, L, P], I),
+    "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
+    "vrnet_render_labels_u8": ([P, I, I, I, P, P, I, P, I, I, P, P, L, P, I, I, I, P, P], I),
+    "vrnet_render_labels_ragged_u8": ([P, P, P, I, I, I, P, P, I, P, I, P, P, L, P, I, I, P, P], I),
     "vrnet_heatmap_workspace": ([I, I, I], L),
     "vrnet_heatmap_f32": ([P, P, P] + [I] * 11 + [P, P, F, P, P, P, P, L, P], I),
     "vrnet_heatmap_ragged_workspace": ([I, I, I], L),
@@ -1556,3 +1559,72 @@ def radar_map(points, views, H, W, radius, min_depth, out, flag=None, ws=None):
     _check(_lib.vrnet_radar_map_f32(ptr(points), max_points, _views(views, B, "radar_map"), B, H, W, int(radius), float(min_depth),
                                     ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), "radar_map")
     return out
+
+
+# ---- class names and scores on the rendered detections (csrc/labels.hip) ---------------------------------------------------
+FLAG_LABEL_SCORE = 2048  # LB_FLAG_SCORE of csrc/labels.hip: a score that is NaN or outside [0, 1], clamped
+LABEL_SCORES = 101       # the strings 0.00 .. 1.00
+LABEL_RECORD = 8         # int32 per atlas record
+
+
+def label_index(rows, kept, offsets, num_classes, label_idx, flag=None):
+    """The kept rows (B, cap, 7) `detect_finish[_ragged]` wrote, with kept (B) and offsets (B + 1) -> label_idx (N) int32,
+    class * 101 + k at offsets[b] + r for every kept row (vrnet_label_index_f32); flag (1) int32 or None."""
+    if rows is None or rows.dim() != 3:
+        raise RuntimeError("label_index: expected rows of shape (B, cap, 7)")
+    B, cap = rows.shape[:2]
+    if label_idx is None or label_idx.dim() != 1:
+        raise RuntimeError("label_index: label_idx must be a 1-D int32 tensor")
+    _tensors("label_index", ((rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32), (offsets, (B + 1,), torch.int32),
+                             (label_idx, (label_idx.shape[0],), torch.int32), (flag, (1,), torch.int32)))
+    if kept is None or offsets is None:
+        raise RuntimeError("label_index: kept and offsets are required")
+    _check(_lib.vrnet_label_index_f32(ptr(rows), ptr(kept), ptr(offsets), B, cap, int(num_classes), ptr(label_idx),
+                                      label_idx.shape[0], ptr(flag), stream()), "label_index")
+
+
+def _label_args(fn, picture, boxes, box_offsets, box_palette, label_idx, blob, records):
+    """The checks both label renderers share; returns (B, h, w, n_rows, num_classes, n_sizes)."""
+    if picture is None or picture.dim() != 4 or picture.shape[-1] != 3:
+        raise RuntimeError(f"{fn}: expected a contiguous uint8 picture of shape (B, ih, iw, 3)")
+    B, ih, iw = picture.shape[:3]
+    if boxes is None or box_offsets is None or box_palette is None or label_idx is None or blob is None or records is None:
+        raise RuntimeError(f"{fn}: boxes, box_offsets, box_palette, label_idx and the atlas blob and records are required")
+    n_rows = boxes.shape[0]
+    if records.dim() != 3 or records.shape[0] < 1 or records.shape[1] < LABEL_SCORES or records.shape[1] % LABEL_SCORES:
+        raise RuntimeError(f"{fn}: the atlas records must have shape (sizes, num_classes * {LABEL_SCORES}, {LABEL_RECORD}), got "
+                           f"{tuple(records.shape)}")
+    _tensors(fn, ((picture, (B, ih, iw, 3), torch.uint8), (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32),
+                  (box_palette, (box_palette.shape[0], 3), torch.uint8), (label_idx, (n_rows,), torch.int32),
+                  (blob, (blob.shape[0],), torch.uint8),
+                  (records, (records.shape[0], records.shape[1], LABEL_RECORD), torch.int32)))
+    return B, ih, iw, n_rows, records.shape[1] // LABEL_SCORES, records.shape[0]
+
+
+def render_labels(picture, boxes, box_offsets, box_palette, thickness, label_idx, blob, records, size_index, flag=None):
+    """Tags and label text over the picture `render` finished, in place (vrnet_render_labels_u8): picture (B,ih,iw,3) uint8,
+    boxes (N,5) / box_offsets (B+1) / box_palette (m,3) / thickness as `render` took them, label_idx (N) int32 = class * 101
+    + k, blob (bytes) uint8 and records (sizes, num_classes * 101, 8) int32 of a `render.LabelAtlas`, size_index its font size."""
+    fn = "render_labels"
+    B, ih, iw, n_rows, nc, n_sizes = _label_args(fn, picture, boxes, box_offsets, box_palette, label_idx, blob, records)
+    _tensors(fn, ((flag, (1,), torch.int32),))
+    if n_rows == 0:                           # nothing to draw (and an empty tensor has no address to pass)
+        return
+    _check(_lib.vrnet_render_labels_u8(ptr(picture), B, ih, iw, ptr(boxes), ptr(box_offsets), n_rows, ptr(box_palette),
+                                       box_palette.shape[0], int(thickness), ptr(label_idx), ptr(blob), blob.shape[0],
+                                       ptr(records), nc, n_sizes, int(size_index), ptr(flag), stream()), fn)
+
+
+def render_labels_ragged(picture, geom, size_index, boxes, box_offsets, box_palette, label_idx, blob, records, flag=None):
+    """`render_labels` on padded slots (vrnet_render_labels_ragged_u8): ih, iw and the thickness of image b from geom[b], its
+    font size from size_index (B) int32, -1 for an image without labels."""
+    fn = "render_labels_ragged"
+    B, ih, iw, n_rows, nc, n_sizes = _label_args(fn, picture, boxes, box_offsets, box_palette, label_idx, blob, records)
+    _tensors(fn, ((flag, (1,), torch.int32), (size_index, (B,), torch.int32)))
+    if size_index is None:
+        raise RuntimeError(f"{fn}: the per-image size-index table is required")
+    if n_rows == 0:
+        return
+    _check(_lib.vrnet_render_labels_ragged_u8(ptr(picture), _geom(geom, B, fn), ptr(size_index), B, ih, iw, ptr(boxes),
+                                              ptr(box_offsets), n_rows, ptr(box_palette), box_palette.shape[0], ptr(label_idx),
+                                              ptr(blob), blob.shape[0], ptr(records), nc, n_sizes, ptr(flag), stream()), fn)

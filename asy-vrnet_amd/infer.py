@@ -30,6 +30,7 @@ from . import render as rendering
 FLAG_CANDIDATES, FLAG_DET_CLASS = 8, 16          # NMS_FLAG_* of csrc/nms.hip, above render.FLAG_*
 FLAG_GEOMETRY = 256                              # VR_FLAG_GEOMETRY of csrc/common.h, above evaluate.FLAG_EVAL_*
 FLAG_POINT_COUNT = 1024                          # VR_FLAG_POINT_COUNT of csrc/common.h (a pipeline built with radar_points)
+FLAG_LABEL_SCORE = rendering.FLAG_LABEL_SCORE    # 2048, csrc/labels.hip (a pipeline built with labels): a score outside [0, 1]
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -232,12 +233,22 @@ class FramePipeline:
     each frame goes through (its letterbox window, or the whole input with letterbox_image=False), radar_radius 0..8 the half
     width of a point's square footprint, radar_min_depth the nearest depth kept; normalise_radar still follows.  Fixed-size
     and ragged pipelines alike; the static inputs are then `points` (B, max_points, 7) and `views` (B, 80).  FLAG_POINT_COUNT
-    (a count outside the buffer, which the host checks rule out) joins the bits of `flag`."""
+    (a count outside the buffer, which the host checks rule out) joins the bits of `flag`.
+
+    labels: None (the default: the chain, the graph and every byte as before), a `render.LabelAtlas`, or True together with
+    class_names= (one per detection class) and optionally font= (`render.LabelAtlas`: a TrueType path, a callable, or
+    None = Pillow's built-in face) -- the tag and '<class name> <score:.2f>' of yolo.py:210-224 on every rendered box.  Two
+    launches behind the render node: hip.label_index (the kept rows -> class * 101 + k) and the label renderer.  A fixed-size
+    pipeline builds the one font size `render.label_font_size(ih)` (0, below 17 rows: no labels); a ragged one builds every
+    size from 1 to label_font_size(ihm), or the sizes label_sizes= names, and sends the per-image size table up with the
+    geometry table; a frame whose size was not built raises in the host validation of `run`, before anything is enqueued.
+    FLAG_LABEL_SCORE joins the bits of `flag`.  labels needs render=True."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
-                 heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None):
+                 heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
+                 font=None, label_sizes=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
         self.radar_points = None
@@ -283,12 +294,57 @@ class FramePipeline:
             table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, fn="FramePipeline")
             self.points, self.views = self.radar_points.buffers(table, dev)
             self._radar_ws = self.radar_points.workspace(self.input_shape, dev)
+        self.labels = self._label_atlas(labels, class_names, font, label_sizes)
         self.cap = None                       # the NMS buffers follow the anchor count of the first (warm-up) pass
         self.graph = self.result = None
         if graph:
             self._capture()
         else:
             self._warm_up(1)
+
+    def _label_atlas(self, labels, class_names, font, label_sizes):
+        """The atlas of the constructor's labels / class_names / font / label_sizes (None without labels), and the static
+        size tables: `label_size_index` of a fixed-size pipeline (None: font size 0), `label_size_tab` (B) of a ragged one."""
+        fn = "FramePipeline"
+        if labels is None or labels is False:
+            if class_names is not None or font is not None or label_sizes is not None:
+                raise RuntimeError(f"{fn}: class_names, font and label_sizes belong to labels=")
+            return None
+        if not self.render:
+            raise RuntimeError(f"{fn}: labels are drawn on the rendered frame; they need render=True")
+        size = rendering.label_font_size(self.frame_shape[0])
+        if labels is True:
+            if class_names is None or len(class_names) != self.num_classes:
+                raise RuntimeError(f"{fn}: labels=True needs class_names, one per detection class ({self.num_classes})")
+            if label_sizes is None:
+                label_sizes = tuple(range(1, size + 1)) if self.ragged else (size,)
+            elif not self.ragged:
+                raise RuntimeError(f"{fn}: label_sizes belongs to a ragged pipeline; a fixed-size one builds font size {size}")
+            if not self.ragged and size == 0:
+                atlas = None                  # frames lower than 17 rows: the outlines alone
+            else:
+                if not len(tuple(label_sizes)):
+                    raise RuntimeError(f"{fn}: a capacity of {self.frame_shape[0]} rows has no font size >= 1 to build")
+                atlas = rendering.LabelAtlas(class_names, font, label_sizes)
+        elif isinstance(labels, rendering.LabelAtlas):
+            if class_names is not None or font is not None or label_sizes is not None:
+                raise RuntimeError(f"{fn}: class_names, font and label_sizes belong to labels=True; an atlas brings its own")
+            atlas = labels
+            if atlas.num_classes != self.num_classes:
+                raise RuntimeError(f"{fn}: the atlas has {atlas.num_classes} classes, the model {self.num_classes}")
+        else:
+            raise RuntimeError(f"{fn}: labels is None, True or a render.LabelAtlas, got {type(labels).__name__}")
+        if self.box_palette.shape[0] != self.num_classes:
+            raise RuntimeError(f"{fn}: labels need a box palette of one colour per class ({self.num_classes}), got "
+                               f"{self.box_palette.shape[0]}")
+        if self.ragged:                       # the warm-up and the capture run on frames that fill their slots
+            tab = np.full(self.batch, atlas.size_index(size) if size in atlas.sizes else -1, np.int32)
+            self.label_size_tab = torch.from_numpy(tab).to(self.device)
+        else:
+            self.label_size_index = None if size == 0 else atlas.size_index(size)
+            if self.label_size_index is None:
+                return None
+        return atlas
 
     def _allocate(self, anchors):
         from . import hip
@@ -303,6 +359,8 @@ class FramePipeline:
         self._kept_rows, self._rows = torch.empty((B, cap, 7), device=dev), torch.empty((B, cap, 7), device=dev)
         self._draw_rows, self._offsets = torch.empty((B * cap, 5), **i32), torch.empty(B + 1, **i32)
         self._det_counts = torch.empty((B, self.num_classes), dtype=torch.int64, device=dev)
+        if self.labels is not None:
+            self._label_idx = torch.zeros(B * cap, **i32)
 
     def _chain(self):
         """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
@@ -344,6 +402,12 @@ class FramePipeline:
             picture = dict(palette=self.seg_palette, mix_type=self.mix_type, alpha=self.alpha, count=True,
                            box_palette=self.box_palette, flag=self.flag)
             boxes = (self._draw_rows, self._offsets)
+            if self.labels is not None:       # the two label launches sit behind the render node
+                hip.label_index(self._rows, self._kept, self._offsets, self.num_classes, self._label_idx, self.flag)
+                boxes += (self._label_idx,)
+                picture["labels"] = self.labels
+                if self.ragged:
+                    picture["label_sizes"] = self.label_size_tab
             if self.ragged:
                 rendered, seg_counts = rendering.render_frame_ragged(self.frames_u8, self.geom, class_map, boxes, **picture)
             else:
@@ -407,15 +471,21 @@ class FramePipeline:
             f, r = validate_inputs(frames_u8, radar, self.batch, self.frame_shape, self.input_shape, self.radar_points, calib,
                                    self.letterbox_image)
             return self._launch(f, r)
-        return self._launch(*validate_ragged_inputs(frames_u8, radar, sizes, self.batch, self.frame_shape, self.input_shape,
-                                                    self.letterbox_image, self.max_taps, self.radar_points, calib))
+        checked = validate_ragged_inputs(frames_u8, radar, sizes, self.batch, self.frame_shape, self.input_shape,
+                                         self.letterbox_image, self.max_taps, self.radar_points, calib)
+        label_tab = None
+        if self.labels is not None:           # a frame whose font size was not built raises here, before anything is enqueued
+            label_tab = self.labels.size_table([int(s[0]) for s in checked[2]], "FramePipeline")
+        return self._launch(*checked, label_tab=label_tab)
 
-    def _launch(self, f, r, sizes=None, table=None):
+    def _launch(self, f, r, sizes=None, table=None, label_tab=None):
         """The copies and the replay of `run`, on inputs that `validate_inputs` / `validate_ragged_inputs` returned."""
         with torch.cuda.device(self.device):
             if self.ragged:
                 data.fill_slots(self.frames_u8, f, sizes)
                 self.geom.copy_(data.geometry_bytes(table), non_blocking=True)
+                if label_tab is not None:
+                    self.label_size_tab.copy_(torch.from_numpy(label_tab).pin_memory(), non_blocking=True)
                 self.sizes = sizes
             else:
                 self.frames_u8.copy_(f, non_blocking=True)

@@ -487,6 +487,37 @@ def _(frames_u8, class_map, palette, mix_type, alpha, boxes, box_offsets, box_pa
             frames_u8.new_empty((frames_u8.shape[0], palette.shape[0]), dtype=torch.int64))
 
 
+@torch.library.custom_op("vrnet::label_index", mutates_args=(), device_types="cuda")
+def label_index(rows: torch.Tensor, kept: torch.Tensor, offsets: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """The kept rows (B,cap,7) fp32 of `detect_finish` with kept (B) and offsets (B+1) int32 -> (B*cap) int32, class * 101 + k
+    of every kept row at offsets[b] + r (k: the score obj * class_conf formatted with .2f, yolo.py:210), 0 elsewhere."""
+    idx = torch.zeros(rows.shape[0] * rows.shape[1], dtype=torch.int32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        hip.label_index(rows, kept, offsets, num_classes, idx)
+    return idx
+
+
+@label_index.register_fake
+def _(rows, kept, offsets, num_classes):
+    return rows.new_empty((rows.shape[0] * rows.shape[1],), dtype=torch.int32)
+
+
+@torch.library.custom_op("vrnet::render_labels", mutates_args=(), device_types="cuda")
+def render_labels(picture: torch.Tensor, boxes: torch.Tensor, box_offsets: torch.Tensor, box_palette: torch.Tensor, thickness: int,
+                  label_idx: torch.Tensor, blob: torch.Tensor, records: torch.Tensor, size_index: int) -> torch.Tensor:
+    """The picture (B,ih,iw,3) uint8 `render` made of these boxes -> a copy with the tag and the text of every box on it
+    (yolo.py:210-224): label_idx (N) int32 = class * 101 + k, blob / records of a `render.LabelAtlas`, size_index its font size."""
+    out = picture.contiguous().clone()
+    with torch.cuda.device(picture.device):
+        hip.render_labels(out, boxes, box_offsets, box_palette, thickness, label_idx, blob, records, size_index)
+    return out
+
+
+@render_labels.register_fake
+def _(picture, boxes, box_offsets, box_palette, thickness, label_idx, blob, records, size_index):
+    return torch.empty_like(picture, memory_format=torch.contiguous_format)
+
+
 # ---- ShuffleAttention (backbone/attention_modules/shuffle_attention.py:48-72) --------------------------------------------
 @torch.library.custom_op("vrnet::shuffle_attention", mutates_args=(), device_types="cuda")
 def shuffle_attention(x: torch.Tensor, cweight: torch.Tensor, cbias: torch.Tensor, sweight: torch.Tensor, sbias: torch.Tensor,

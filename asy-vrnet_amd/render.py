@@ -25,8 +25,25 @@ ValueError for x1 < x0 where this module paints nothing.
   which is this project's own definition (see csrc/heatmap.hip).
 * `jet_lut`: matplotlib's "jet" as 256 x 3 bytes, from its segment data; matplotlib itself is not imported.
 
-Out of scope: the label text and its filled background (they need the reference's font file), crop saving and video I/O."""
+* `LabelAtlas` / `draw_labels` / `labels=` of `draw_boxes`, `render_frame`, `render_frame_ragged`: yolo.py:198-224, the filled
+  tag in the class colour and '{} {:.2f}'.format(class name, score) in black on it (csrc/labels.hip).  A score in [0, 1] formats
+  to one of 101 strings, so an atlas holds all num_classes x 101 labels of each font size, rasterised ONCE on the host by Pillow
+  itself with the caller's font -- exactly the "L" mask and offset `ImageDraw.text` would paste (`font.getmask2`) -- and the
+  device looks masks up and blends them: Pillow's bytes for any font, layout engine or script.  The font is the caller's: the
+  reference's model_data/simhei.ttf is not shipped (pass its path to get the reference's pictures); the default is Pillow's
+  built-in face, `ImageFont.load_default(size)`.  label_size is (bbox right, bbox bottom) = `font.getbbox(label)[2:4]` =
+  `draw.textbbox((0, 0), label, font)[2:4]`: what the `draw.textsize` the reference calls returned in the Pillow 9 line
+  (Pillow 12 has no textsize).  Memory: sum over sizes, classes and k of mask width x height, plus 32 bytes per label
+  (`atlas.nbytes`; 7 classes at font size 32 are a few MB).
+  The rule (`draw_labels_host` states it in numpy, the kernels equal it byte for byte): the rows of an image are drawn in
+  order; row i paints (a) its rings, (b) the rectangle [ox, oy] .. [ox + size_w, oy + size_h], inclusive, clipped, in its
+  colour, (ox, oy) = (left, top - size_h) if top - size_h >= 0 else (left, top + 1), (c) its mask at (ox + mask_off_x, oy +
+  mask_off_y) in black, clipped: per byte v = DIV255(v * (255 - m)), DIV255(a) = ((a + 128) + ((a + 128) >> 8)) >> 8.  Font
+  size `label_font_size(ih)` = floor(3e-2 ih + 0.5) (yolo.py:163); size 0 (frames lower than 17 rows) draws no labels.
+
+Out of scope: crop saving and video I/O."""
 import colorsys
+import os
 
 import numpy as np
 import torch
@@ -34,6 +51,8 @@ import torch
 MAX_COLORS = 256          # RN_MAXCOL of csrc/render.hip
 MAX_BOXES = 1024          # RN_MAXBOX: box rows of one image
 FLAG_CLASS, FLAG_BOX_COLOUR, FLAG_BOX_ROWS = 1, 2, 4     # bits of the optional `flag` word
+FLAG_LABEL_SCORE = 2048   # LB_FLAG_SCORE of csrc/labels.hip: a label score that is NaN or outside [0, 1], clamped
+LABEL_SCORES = 101        # the strings 0.00 .. 1.00 a score in [0, 1] formats to
 
 _device_palettes = {}
 
@@ -141,7 +160,8 @@ def box_rows(results, image_shape, class_names_or_n, input_shape=None):
 
 
 def render_frame(frames_u8, class_map=None, results=None, input_shape=None, palette=None, mix_type=0, alpha=0.7,
-                 count=False, box_palette=None, thickness=None, out=None, flag=None, device="cuda"):
+                 count=False, box_palette=None, thickness=None, out=None, flag=None, device="cuda", labels=None,
+                 font_size=None):
     """The overlay of `seg_render` and the outlines of `draw_boxes` in ONE launch (vrnet_render_u8), boxes over the
     overlay.  frames_u8 (B,ih,iw,3) uint8 RGB original frames (a single (ih,iw,3) frame counts as B = 1), class_map
     (B,ih,iw) uint8 or None, numpy arrays or tensors.  results: None, the list `non_max_suppression` returns (packed by
@@ -152,8 +172,10 @@ def render_frame(frames_u8, class_map=None, results=None, input_shape=None, pale
     themselves (boxes drawn in place).  flag: a zeroed int32 device tensor of one element that receives the data-error
     bits (FLAG_CLASS: a class id >= len(palette), which takes the last colour and is not counted; FLAG_BOX_COLOUR: a colour
     index outside the box palette, clamped; FLAG_BOX_ROWS: more than MAX_BOXES rows in one image) -- read it when you next
-    synchronise.  Returns out, or (out, counts) with counts (B, len(palette)) int64 when count=True.  No host
-    synchronisation."""
+    synchronise.  labels: a `LabelAtlas` -- the class names and scores of yolo.py:210-224 are drawn over the finished
+    picture by `draw_labels` (font_size: default `label_font_size(ih)`); device results are then the triple (rows, offsets,
+    label_idx (N) int32 = class * 101 + k, as `hip.label_index` writes it).  With labels=None nothing about the call changes.
+    Returns out, or (out, counts) with counts (B, len(palette)) int64 when count=True.  No host synchronisation."""
     from . import hip
     fn = "render"
     img = _as_u8(frames_u8, "frames", 4, fn)
@@ -177,7 +199,15 @@ def render_frame(frames_u8, class_map=None, results=None, input_shape=None, pale
             raise RuntimeError(f"{fn}: out must be a contiguous uint8 tensor of shape {tuple(img.shape)}")
         if cmap is not None and (_overlap(out, img) or _overlap(out, cmap)):
             raise RuntimeError(f"{fn}: out must not alias the frames or the class map when a class map is given")
-    rows = offsets = bpal = None
+    rows = offsets = bpal = label_idx = None
+    if labels is not None:
+        if results is None:
+            raise RuntimeError(f"{fn}: labels need results")
+        font_size = _label_setup(labels, font_size, ih, fn)
+        if isinstance(results, tuple) and all(torch.is_tensor(t) for t in results):
+            if len(results) != 3:
+                raise RuntimeError(f"{fn}: with labels, device results are the triple (rows, offsets, label_idx)")
+            label_idx, results = results[2], results[:2]
     if results is not None:
         if isinstance(results, tuple) and len(results) == 2 and all(torch.is_tensor(t) for t in results):
             rows, offsets = results
@@ -199,18 +229,29 @@ def render_frame(frames_u8, class_map=None, results=None, input_shape=None, pale
             thickness = int(max((iw + ih) // np.mean(input_shape), 1))
         if int(thickness) < 1:
             raise RuntimeError(f"{fn}: thickness must be at least 1, got {thickness!r}")
-        bpal = _palette(box_palette, det_palette(4), fn)
+        bpal = _palette(box_palette, det_palette(4) if labels is None else det_palette(labels.num_classes), fn)
+        if labels is not None:
+            _label_palette(labels, bpal, fn)
+            if host_rows is not None:
+                host_idx, score_bits = _host_label_idx(results, host_rows, labels)
     img = img.to(device, non_blocking=True).contiguous()
     dev = img.device
     cmap = None if cmap is None else cmap.to(dev, non_blocking=True).contiguous()
     with torch.cuda.device(dev):
         if results is not None and host_rows is not None:
             # offsets and rows in one pinned buffer: a single non-blocking copy
-            packed = torch.empty(B + 1 + host_rows.size, dtype=torch.int32).pin_memory()
+            nidx = 0 if labels is None else host_idx.size
+            packed = torch.empty(B + 1 + host_rows.size + nidx, dtype=torch.int32).pin_memory()
             packed[:B + 1] = torch.from_numpy(host_offsets)
-            packed[B + 1:] = torch.from_numpy(host_rows.reshape(-1))
+            packed[B + 1:B + 1 + host_rows.size] = torch.from_numpy(host_rows.reshape(-1))
+            if labels is not None:
+                packed[B + 1 + host_rows.size:] = torch.from_numpy(host_idx)
             packed = packed.to(dev, non_blocking=True)
-            offsets, rows = packed[:B + 1], packed[B + 1:].view(-1, 5)
+            offsets, rows = packed[:B + 1], packed[B + 1:B + 1 + host_rows.size].view(-1, 5)
+            if labels is not None:
+                label_idx = packed[B + 1 + host_rows.size:]
+                if score_bits and flag is not None:
+                    flag.bitwise_or_(score_bits)
         elif results is not None:
             rows, offsets = rows.to(dev).contiguous(), offsets.to(dev).contiguous()
         if out is None:
@@ -219,18 +260,24 @@ def render_frame(frames_u8, class_map=None, results=None, input_shape=None, pale
         hip.render(img, cmap, out, palette=None if pal is None else _palette_on(pal, dev), mix_type=mix_type, alpha=alpha,
                    boxes=rows, box_offsets=offsets, box_palette=None if bpal is None else _palette_on(bpal, dev),
                    thickness=1 if thickness is None else int(thickness), counts=counts, flag=flag)
+        if labels is not None and font_size > 0:
+            blob, records = labels.on(dev)
+            hip.render_labels(out, rows, offsets, _palette_on(bpal, dev), int(thickness), label_idx.to(dev).contiguous(), blob,
+                              records, labels.size_index(font_size), flag=flag)
     return (out, counts) if count else out
 
 
 def render_frame_ragged(frames_u8, geom, class_map=None, results=None, palette=None, mix_type=0, alpha=0.7, count=False,
-                        box_palette=None, out=None, flag=None):
+                        box_palette=None, out=None, flag=None, labels=None, label_sizes=None):
     """`render_frame` for a batch of images of their own sizes (vrnet_render_ragged_u8).  frames_u8 (B, ihm, iwm, 3) and
     class_map (B, ihm, iwm) (or None) are padded uint8 DEVICE tensors with image b in the top-left corner of slot b; geom is
     the (B, hip.GEOM_BYTES) device table of `data.frame_geometry`, which gives every image its size and its outline
     thickness.  results: None or a pair (rows (N, 5) int32, offsets (B + 1) int32) of device tensors, as
     `hip.detect_finish_ragged` leaves them.  Returns out (B, ihm, iwm, 3), or (out, counts) with count=True: image b is
     `out[b, :ih_b, :iw_b]`, equal to `render_frame` on that image alone; every pixel outside it is 0 and is not counted.
-    out must not be the frames.  flag also receives hip.FLAG_GEOMETRY.  No host synchronisation."""
+    out must not be the frames.  flag also receives hip.FLAG_GEOMETRY.  labels: a `LabelAtlas`; results are then the triple
+    (rows, offsets, label_idx) and label_sizes the (B) int32 device table of `atlas.size_table`: the font size of each image
+    as an index into the atlas, -1 for an image without labels.  No host synchronisation."""
     from . import hip
     fn = "render_ragged"
     img = frames_u8
@@ -246,9 +293,17 @@ def render_frame_ragged(frames_u8, geom, class_map=None, results=None, palette=N
         raise RuntimeError(f"{fn}: count=True needs a class map")
     pal = None if class_map is None else _palette(palette, seg_palette(21), fn)
     rows = offsets = bpal = None
+    label_idx = None
+    if labels is not None:
+        if results is None or len(results) != 3 or label_sizes is None:
+            raise RuntimeError(f"{fn}: labels need the device triple (rows, offsets, label_idx) and label_sizes")
+        _label_setup(labels, 0, ih, fn)
+        label_idx, results = results[2], results[:2]
     if results is not None:
         rows, offsets = results
-        bpal = _palette(box_palette, det_palette(4), fn)
+        bpal = _palette(box_palette, det_palette(4) if labels is None else det_palette(labels.num_classes), fn)
+        if labels is not None:
+            _label_palette(labels, bpal, fn)
     dev = img.device
     with torch.cuda.device(dev):
         if out is None:
@@ -258,6 +313,10 @@ def render_frame_ragged(frames_u8, geom, class_map=None, results=None, palette=N
                           palette=None if pal is None else _palette_on(pal, dev), mix_type=mix_type, alpha=alpha, boxes=rows,
                           box_offsets=offsets, box_palette=None if bpal is None else _palette_on(bpal, dev), counts=counts,
                           flag=flag)
+        if labels is not None:
+            blob, records = labels.on(dev)
+            hip.render_labels_ragged(out, geom, label_sizes, rows, offsets, _palette_on(bpal, dev), label_idx, blob, records,
+                                     flag=flag)
     return (out, counts) if count else out
 
 
@@ -440,11 +499,315 @@ def seg_render(frames_u8, class_map, palette=None, mix_type=0, alpha=0.7, count=
     return render_frame(frames_u8, class_map, None, None, palette, mix_type, alpha, count, out=out, flag=flag, device=device)
 
 
-def draw_boxes(frames_u8, results, input_shape, palette=None, thickness=None, out=None, flag=None, device="cuda"):
-    """yolo.py:164-222 without the label text: `box_rows` of the list `non_max_suppression` returns plus the kernel --
-    `thickness` nested outlines per box in palette[class] (default `det_palette(4)`), later boxes over earlier ones.
-    out may be the frames tensor itself (drawn in place).  One non-blocking host-to-device copy of the packed rows."""
+def draw_boxes(frames_u8, results, input_shape, palette=None, thickness=None, out=None, flag=None, device="cuda", labels=None):
+    """yolo.py:164-222: `box_rows` of the list `non_max_suppression` returns plus the kernel -- `thickness` nested outlines
+    per box in palette[class] (default `det_palette(4)`), later boxes over earlier ones; with labels=a `LabelAtlas` also the
+    tag and the text of every box (yolo.py:210-224), without it the outlines alone.  out may be the frames tensor itself
+    (drawn in place).  One non-blocking host-to-device copy of the packed rows."""
     if results is None:
         raise RuntimeError("render: draw_boxes needs the results of non_max_suppression")
     return render_frame(frames_u8, None, results, input_shape, box_palette=palette, thickness=thickness, out=out, flag=flag,
-                        device=device)
+                        device=device, labels=labels)
+
+
+# ---- class names and scores (csrc/labels.hip) --------------------------------------------------------------------------------
+def label_font_size(ih):
+    """The font size of yolo.py:163 for a frame of ih rows: int(floor(3e-2 * ih + 0.5)); 0 below 17 rows (no labels)."""
+    return int(np.floor(3e-2 * int(ih) + 0.5))
+
+
+def score_index(scores, return_flag=False):
+    """k = int('{:.2f}'.format(float(s)).replace('.', '')) for float32 scores in [0, 1], as an int32 array of the same shape:
+    the exact value of the float32 times 100, rounded to nearest with ties to even (0.125 -> 12, 0.375 -> 38), in integer
+    arithmetic on the bits -- never score * 100 in floating point.  NaN or a score outside [0, 1] is clamped into 0..100 (NaN
+    and negatives to 0, above 1 to 100); return_flag=True returns (k, bits) with bits = FLAG_LABEL_SCORE if any score was."""
+    s = np.asarray(scores)
+    if s.dtype != np.float32:
+        raise RuntimeError(f"score_index: expected float32 scores, got {s.dtype}")
+    s = np.ascontiguousarray(s)
+    bits = s.view(np.uint32).astype(np.uint64)
+    e = (bits >> np.uint64(23)) & np.uint64(255)
+    m = (bits & np.uint64(0x7FFFFF)) | np.where(e > 0, np.uint64(0x800000), np.uint64(0))
+    sh = 150 - np.maximum(e.astype(np.int64), 1)                       # s = m 2^-sh; sh >= 23 for s <= 1
+    shc = np.clip(sh, 1, 63).astype(np.uint64)
+    N = np.uint64(100) * m
+    q, rem, half = N >> shc, N & ((np.uint64(1) << shc) - np.uint64(1)), np.uint64(1) << (shc - np.uint64(1))
+    k = (q + ((rem > half) | ((rem == half) & ((q & np.uint64(1)) == 1))).astype(np.uint64)).astype(np.int64)
+    k = np.where(sh >= 32, 0, k)                                       # 100 m < 2^31: below half a unit
+    with np.errstate(invalid="ignore"):
+        bad = ~((s >= 0) & (s <= 1))
+        k = np.where(bad, np.where(s > 1, 100, 0), k).astype(np.int32)
+    return (k, FLAG_LABEL_SCORE if bool(bad.any()) else 0) if return_flag else k
+
+
+class LabelAtlas:
+    """Every label an image can show, rasterised once on the host by Pillow: for each font size in `sizes` (each >= 1), each
+    class c and each k in 0..100 the label f"{name} {k / 100:.2f}" as `ImageDraw.text` would paste it -- the "L" mask and
+    its offset, `font.getmask2(label, "L")` with a fractional start of 0 (origins are integers) -- and label_size =
+    `font.getbbox(label)[2:4]` (module docstring).  font: the path of a TrueType file, a callable size -> PIL.ImageFont, or
+    None = `ImageFont.load_default(size)`.  Pillow is imported here and only here; without it this raises.
+    blob: all masks as one uint8 array; records (len(sizes), num_classes * 101, 8) int32 = blob offset, mask width, mask
+    height, mask offset x, mask offset y, label_size width, label_size height, 0, indexed [size index][c * 101 + k]; both go
+    to a device once (`on`) and are kept, as the palettes are.  nbytes: their size; a blob of 2 GiB or more raises."""
+
+    def __init__(self, class_names, font=None, sizes=(32,)):
+        names, sizes = self._check(class_names, sizes)
+        try:
+            from PIL import ImageFont
+        except ImportError:
+            raise RuntimeError("LabelAtlas: rasterising labels needs Pillow (pip install pillow); everything else in this "
+                               "module works without it") from None
+        if font is None:
+            make = ImageFont.load_default
+        elif callable(font):
+            make = font
+        else:
+            make = lambda size: ImageFont.truetype(os.fspath(font), size)      # noqa: E731
+        masks, total = [], 0
+        records = np.zeros((len(sizes), len(names) * LABEL_SCORES, 8), np.int32)
+        for si, size in enumerate(sizes):
+            f = make(size)
+            for c, name in enumerate(names):
+                for k in range(LABEL_SCORES):
+                    label = f"{name} {k / 100:.2f}"
+                    mask, (mw, mh), off = _label_mask(f, label)
+                    bbox = f.getbbox(label)
+                    if total + mask.size >= 1 << 31:
+                        raise RuntimeError("LabelAtlas: the masks need 2 GiB or more; build fewer sizes or classes")
+                    records[si, c * LABEL_SCORES + k, :7] = (total, mw, mh, int(off[0]), int(off[1]), int(bbox[2]), int(bbox[3]))
+                    masks.append(mask)
+                    total += mask.size
+        self._set(names, sizes, np.concatenate(masks) if total else np.zeros(0, np.uint8), records)
+
+    @staticmethod
+    def _check(class_names, sizes):
+        names = [str(n) for n in class_names]
+        if not 1 <= len(names) <= MAX_COLORS:
+            raise RuntimeError(f"LabelAtlas: 1..{MAX_COLORS} class names, got {len(names)}")
+        try:
+            sizes = tuple(int(v) for v in sizes)
+        except (TypeError, ValueError):
+            raise RuntimeError(f"LabelAtlas: sizes is a sequence of font sizes, got {sizes!r}") from None
+        if not sizes or min(sizes) < 1 or len(set(sizes)) != len(sizes):
+            raise RuntimeError(f"LabelAtlas: sizes must be distinct font sizes >= 1, got {sizes!r}")
+        return names, sizes
+
+    def _set(self, names, sizes, blob, records):
+        if blob.dtype != np.uint8 or blob.ndim != 1 or records.dtype != np.int32 or \
+                records.shape != (len(sizes), len(names) * LABEL_SCORES, 8):
+            raise RuntimeError("LabelAtlas: expected a 1-D uint8 blob and int32 records of shape (sizes, classes * 101, 8)")
+        if blob.size >= 1 << 31:
+            raise RuntimeError("LabelAtlas: the masks need 2 GiB or more; build fewer sizes or classes")
+        r = records.astype(np.int64)
+        if (r[..., :3] < 0).any() or (r[..., 5:7] < 0).any() or (r[..., 0] + r[..., 1] * r[..., 2] > blob.size).any():
+            raise RuntimeError("LabelAtlas: a record points outside the blob")
+        self.class_names, self.sizes = tuple(names), tuple(sizes)
+        self.blob, self.records = np.ascontiguousarray(blob), np.ascontiguousarray(records)
+        self._index = {s: i for i, s in enumerate(self.sizes)}
+        self._device = {}
+
+    @classmethod
+    def from_arrays(cls, class_names, sizes, blob, records):
+        """An atlas from the arrays of another one (`save` / `load`): no font and no Pillow needed."""
+        self = cls.__new__(cls)
+        names, sizes = cls._check(class_names, sizes)
+        self._set(names, sizes, np.asarray(blob), np.asarray(records))
+        return self
+
+    def save(self, path):
+        np.savez_compressed(path, class_names=np.array(self.class_names), sizes=np.array(self.sizes, np.int32), blob=self.blob,
+                            records=self.records)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls.from_arrays([str(n) for n in z["class_names"]], z["sizes"], z["blob"], z["records"])
+
+    @property
+    def num_classes(self):
+        return len(self.class_names)
+
+    @property
+    def nbytes(self):
+        return int(self.blob.nbytes + self.records.nbytes)
+
+    def size_index(self, font_size):
+        """The row of `records` that holds font_size; raises for a size that was not built."""
+        i = self._index.get(int(font_size))
+        if i is None:
+            raise RuntimeError(f"LabelAtlas: font size {int(font_size)} was not built (sizes: {self.sizes})")
+        return i
+
+    def size_table(self, heights, fn="LabelAtlas"):
+        """The (B) int32 table of `render_frame_ragged` for images of these heights: the size index of
+        `label_font_size(ih)`, -1 where that is 0; raises, naming the image, for a size that was not built."""
+        tab = np.empty(len(heights), np.int32)
+        for b, ih in enumerate(heights):
+            size = label_font_size(ih)
+            if size > 0 and size not in self._index:
+                raise RuntimeError(f"{fn}: image {b} of {int(ih)} rows needs font size {size}, which the atlas was not built "
+                                   f"for (sizes: {self.sizes})")
+            tab[b] = self._index[size] if size > 0 else -1
+        return tab
+
+    def record(self, font_size, c, k):
+        """(mask (h, w) uint8, (mask offset x, y), (label_size w, h)) of class c at score index k."""
+        off, mw, mh, mox, moy, lw, lh, _ = (int(v) for v in self.records[self.size_index(font_size), c * LABEL_SCORES + k])
+        return self.blob[off:off + mw * mh].reshape(mh, mw), (mox, moy), (lw, lh)
+
+    def on(self, device):
+        """(blob, records) as tensors on the device; copied once per device and kept."""
+        key = str(torch.device(device))
+        t = self._device.get(key)
+        if t is None:
+            t = self._device[key] = (torch.from_numpy(self.blob).to(device), torch.from_numpy(self.records).to(device))
+        return t
+
+
+def _label_mask(font, label):
+    """What `ImageDraw.text((x, y), label, font=font)` pastes on an RGB image at integer (x, y): (mask bytes, (w, h), offset)."""
+    from PIL import Image
+    try:
+        mask, off = font.getmask2(label, "L")
+    except AttributeError:                    # a bitmap font: ImageDraw.text falls back to getmask, offset 0
+        mask, off = font.getmask(label, "L"), (0, 0)
+    w, h = mask.size
+    if w <= 0 or h <= 0:
+        return np.zeros(0, np.uint8), (0, 0), off
+    return np.frombuffer(Image.Image()._new(mask).tobytes(), np.uint8), (w, h), off
+
+
+def _label_setup(atlas, font_size, ih, fn):
+    if not isinstance(atlas, LabelAtlas):
+        raise RuntimeError(f"{fn}: labels must be a render.LabelAtlas, got {type(atlas).__name__}")
+    font_size = label_font_size(ih) if font_size is None else int(font_size)
+    if font_size < 0:
+        raise RuntimeError(f"{fn}: font_size must not be negative, got {font_size}")
+    if font_size > 0:
+        atlas.size_index(font_size)
+    return font_size
+
+
+def _label_palette(atlas, bpal, fn):
+    if bpal.shape[0] != atlas.num_classes:
+        raise RuntimeError(f"{fn}: the atlas has {atlas.num_classes} classes, the box palette {bpal.shape[0]} colours")
+
+
+def _host_label_idx(results, host_rows, atlas):
+    """class * 101 + k per packed draw row of the list `non_max_suppression` returns, and the score flag bits: the score is
+    np.float32(obj) * np.float32(class_conf), one float32 multiply (yolo.py:157); the class is clamped as the colour is."""
+    parts = [np.zeros((0, 7), np.float32) if d is None else np.asarray(d) for d in results]
+    det = np.concatenate(parts) if parts else np.zeros((0, 7), np.float32)
+    k, bits = score_index(det[:, 4].astype(np.float32) * det[:, 5].astype(np.float32), True)
+    cls = np.clip(host_rows[:, 4].astype(np.int64), 0, atlas.num_classes - 1)
+    return (cls * LABEL_SCORES + k).astype(np.int32), bits
+
+
+def _div255(a):
+    a = a + 128
+    return (a + (a >> 8)) >> 8
+
+
+def draw_labels_host(picture, rows, scores, atlas, font_size, thickness, box_palette=None):
+    """The rule of the module docstring in numpy, for ONE image: picture (ih, iw, 3) uint8 (with or without the outlines
+    already on it: they are painted again), rows (n, 5) int32 = left, top, right, bottom, class as `box_rows` gives them,
+    scores (n) float32 = obj * class_conf.  The rows are drawn in order -- rings, tag, text -- as yolo.py:198-224 draws
+    them; rows past MAX_BOXES are ignored.  Returns the new picture; font_size 0 draws the rings only.  This is the statement
+    the kernels of csrc/labels.hip are tested against; tests/test_labels_host.py pins it to live Pillow."""
+    fn = "draw_labels_host"
+    pic, rows, scores = np.asarray(picture), np.asarray(rows), np.asarray(scores)
+    if pic.dtype != np.uint8 or pic.ndim != 3 or pic.shape[2] != 3:
+        raise RuntimeError(f"{fn}: expected a uint8 picture (ih, iw, 3), got {pic.dtype} {pic.shape}")
+    if rows.dtype != np.int32 or rows.ndim != 2 or rows.shape[1] != 5:
+        raise RuntimeError(f"{fn}: expected int32 rows (n, 5), got {rows.dtype} {rows.shape}")
+    if scores.dtype != np.float32 or scores.shape != (len(rows),):
+        raise RuntimeError(f"{fn}: expected float32 scores ({len(rows)},), got {scores.dtype} {scores.shape}")
+    if int(thickness) < 1:
+        raise RuntimeError(f"{fn}: thickness must be at least 1, got {thickness!r}")
+    font_size = _label_setup(atlas, font_size, pic.shape[0], fn)
+    pal = _palette(box_palette, det_palette(atlas.num_classes), fn)
+    pal = pal.cpu().numpy() if torch.is_tensor(pal) else pal
+    _label_palette(atlas, pal, fn)
+    out = pic.copy()
+    ih, iw = out.shape[:2]
+    ks = score_index(scores)
+
+    def fill(x0, y0, x1, y1, colour):             # the inclusive rectangle, clipped
+        x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, iw - 1), min(y1, ih - 1)
+        if x0 <= x1 and y0 <= y1:
+            out[y0:y1 + 1, x0:x1 + 1] = colour
+
+    for (left, top, right, bottom, cls), k in zip(rows[:MAX_BOXES].tolist(), ks[:MAX_BOXES].tolist()):
+        c = min(max(cls, 0), atlas.num_classes - 1)
+        colour = pal[c]
+        for i in range(int(thickness)):           # (a) the perimeter of each ring
+            l, t, r, b = left + i, top + i, right - i, bottom - i
+            if l > r or t > b:
+                break
+            fill(l, t, r, t, colour)
+            fill(l, b, r, b, colour)
+            fill(l, t, l, b, colour)
+            fill(r, t, r, b, colour)
+        if font_size == 0:
+            continue
+        mask, (mox, moy), (lw, lh) = atlas.record(font_size, c, k)
+        ox, oy = (left, top - lh) if top - lh >= 0 else (left, top + 1)
+        fill(ox, oy, ox + lw, oy + lh, colour)    # (b) the tag
+        tx, ty = ox + mox, oy + moy               # (c) the text, black through the mask
+        x0, y0, x1, y1 = max(tx, 0), max(ty, 0), min(tx + mask.shape[1], iw), min(ty + mask.shape[0], ih)
+        if x0 < x1 and y0 < y1:
+            m = mask[y0 - ty:y1 - ty, x0 - tx:x1 - tx].astype(np.int64)[..., None]
+            out[y0:y1, x0:x1] = _div255(out[y0:y1, x0:x1].astype(np.int64) * (255 - m)).astype(np.uint8)
+    return out
+
+
+def draw_labels(picture, results, atlas, input_shape=None, thickness=None, font_size=None, box_palette=None, flag=None):
+    """yolo.py:210-224 on the device, in place on the (B, ih, iw, 3) uint8 DEVICE picture `render_frame` / `draw_boxes`
+    finished with the same results, palette and thickness (vrnet_render_labels_u8).  results: the list `non_max_suppression`
+    returns -- the host packs the rows, the float32-product scores' indices and the offsets and sends them in one
+    non-blocking copy -- or a device triple (rows (N, 5), offsets (B + 1), label_idx (N)) of int32 tensors.  thickness:
+    default yolo.py:164 from input_shape; font_size: default `label_font_size(ih)`, 0 draws nothing; box_palette: default
+    `det_palette(atlas.num_classes)`; flag: as in `render_frame`, plus FLAG_LABEL_SCORE.  Returns the picture.  No host
+    synchronisation."""
+    from . import hip
+    fn = "draw_labels"
+    if not (torch.is_tensor(picture) and picture.is_cuda and picture.dtype == torch.uint8 and picture.dim() == 4 and
+            picture.shape[-1] == 3 and picture.is_contiguous()):
+        raise RuntimeError(f"{fn}: expected a contiguous uint8 picture (B, ih, iw, 3) on a GPU")
+    B, ih, iw = picture.shape[:3]
+    font_size = _label_setup(atlas, font_size, ih, fn)
+    bpal = _palette(box_palette, det_palette(atlas.num_classes), fn)
+    _label_palette(atlas, bpal, fn)
+    if thickness is None:
+        if input_shape is None:
+            raise RuntimeError(f"{fn}: labels need a thickness or the input_shape it follows from")
+        thickness = int(max((iw + ih) // np.mean(input_shape), 1))
+    if int(thickness) < 1:
+        raise RuntimeError(f"{fn}: thickness must be at least 1, got {thickness!r}")
+    dev = picture.device
+    with torch.cuda.device(dev):
+        if isinstance(results, tuple) and all(torch.is_tensor(t) for t in results):
+            if len(results) != 3:
+                raise RuntimeError(f"{fn}: device results are the triple (rows, offsets, label_idx)")
+            rows, offsets, label_idx = (t.to(dev).contiguous() for t in results)
+        else:
+            if results is None or len(results) != B:
+                raise RuntimeError(f"{fn}: {0 if results is None else len(results)} result entries for {B} frames")
+            host_rows, host_offsets, _, _ = box_rows(results, (ih, iw), MAX_COLORS)
+            if int(np.diff(host_offsets).max(initial=0)) > MAX_BOXES:
+                raise RuntimeError(f"{fn}: more than {MAX_BOXES} boxes in one image")
+            host_idx, bits = _host_label_idx(results, host_rows, atlas)
+            packed = torch.empty(B + 1 + host_rows.size + host_idx.size, dtype=torch.int32).pin_memory()
+            packed[:B + 1] = torch.from_numpy(host_offsets)
+            packed[B + 1:B + 1 + host_rows.size] = torch.from_numpy(host_rows.reshape(-1))
+            packed[B + 1 + host_rows.size:] = torch.from_numpy(host_idx)
+            packed = packed.to(dev, non_blocking=True)
+            offsets, rows = packed[:B + 1], packed[B + 1:B + 1 + host_rows.size].view(-1, 5)
+            label_idx = packed[B + 1 + host_rows.size:]
+            if bits and flag is not None:
+                flag.bitwise_or_(bits)
+        if font_size > 0:
+            blob, records = atlas.on(dev)
+            hip.render_labels(picture, rows, offsets, _palette_on(bpal, dev), int(thickness), label_idx, blob, records,
+                              atlas.size_index(font_size), flag=flag)
+    return picture

@@ -1151,6 +1151,54 @@ long vrnet_radar_map_workspace(int B, int H, int W);
 int vrnet_radar_map_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W, int radius,
                         float min_depth, float* out, int* flag, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- class names and scores on the rendered detections (csrc/labels.hip) -----------------------------------------------
+ * Added within ABI 11: new symbols only, no existing signature, layout or kernel behaviour changed; hip.py binds every
+ * declared symbol at import.
+ * yolo.py:198-224: every detection gets its rings (vrnet_render_u8), a filled tag in the class colour and
+ * '{} {:.2f}'.format(class name, score) in black on it.  A score in [0, 1] formats to one of 101 strings, so the host
+ * rasterises all num_classes x 101 labels once with Pillow (render.LabelAtlas) and the device looks masks up.
+ * ATLAS.  blob: the uint8 "L" masks ImageDraw.text would paste (font.getmask2), row-major, back to back, below 2 GiB.
+ *   records (n_sizes, num_classes * 101, 8) int32, one per font size and label class * 101 + k: blob offset, mask width,
+ *   mask height, mask offset x, mask offset y, label_size width, label_size height, 0.  label_size is (bbox right, bbox
+ *   bottom) = font.getbbox(label)[2:4], what draw.textsize (yolo.py:212) returned in the Pillow 9 line.  The kernels do not
+ *   trust the tables: a label index is clamped into the records, sides and offsets to 2^14, and a record whose mask does
+ *   not lie inside the blob draws its tag without text.
+ * vrnet_label_index_f32, yolo.py:157 + 210: rows (B, cap, 7) / kept (B) / offsets (B + 1) = rows_out, kept and offsets of
+ *   vrnet_detect_finish[_ragged]_f32 -> label_idx[offsets[b] + r] = class * 101 + k for the kept rows (n_out: the length
+ *   of label_idx; nothing else is written).  score = obj * class_conf, one fp32 multiply; k = int('{:.2f}'.format(score)
+ *   without its point): the exact value of the fp32 times 100 rounded to nearest, ties to even (0.125 -> 12, 0.375 -> 38),
+ *   in integer arithmetic on the bits.  NaN or a score outside [0, 1] is clamped (NaN and negatives to 0, above 1 to 100)
+ *   and sets bit 2048 of *flag; a class outside [0, num_classes) takes the clamped class, as the outline colour does,
+ *   and sets bit 16 as vrnet_detect_finish_f32 does.  flag may be NULL.
+ * vrnet_render_labels_u8: in place on the (B, ih, iw, 3) picture vrnet_render_u8 finished with the same boxes, box_offsets,
+ *   box_palette and thickness.  The rows of an image are drawn in order; row i paints (a) its rings, (b) the rectangle
+ *   [ox, oy] .. [ox + size_w, oy + size_h], inclusive, clipped, in its colour, with (ox, oy) = (left, top - size_h) if
+ *   top - size_h >= 0, else (left, top + 1) (yolo.py:216-223), (c) its mask at (ox + mask offset x, oy + mask offset y) in
+ *   black, clipped: per byte v = DIV255(v * (255 - m)), DIV255(a) = ((a + 128) + ((a + 128) >> 8)) >> 8 (Pillow's
+ *   fill_mask_L with ink 0).  Per pixel: i* = the highest row whose ring or fill covers it; the base is the colour of i*
+ *   for a fill, the byte that is there for a ring or without an i*; then the masks of the rows j >= i* (all rows without
+ *   an i*) that cover it with m > 0 apply in ascending j.  Pixels no fill and no text touch keep their bytes.
+ *   Grid (pixel blocks, row, image) over each row's rectangle (the bounding box of fill and mask): work follows the label
+ *   area.  One thread owns a pixel -- that of the highest row whose rectangle covers it -- and computes its whole final
+ *   value from the image's rows in LDS: no racing stores, no floating point, no atomics on pixels, the same bytes on every
+ *   run.  At most 1024 rows per image; later rows are ignored and set bit 2, as in vrnet_render_u8.  size_index: the font
+ *   size, a row of records.
+ * vrnet_render_labels_ragged_u8: the same on padded (B, ihm, iwm, 3) slots with ih, iw and thickness of image b from
+ *   geom[b] and its font size from size_index[b] (int32, B entries; -1: no labels for that image; >= n_sizes: none, and
+ *   bit 256).  Nothing outside an image is written: the padding stays 0.
+ * All three: no allocation, no memset, no host synchronisation; one kernel each, capturable in a graph. */
+int vrnet_label_index_f32(const float* rows, const int* kept, const int* offsets, int B, int cap, int num_classes,
+                          int* label_idx, int n_out, int* flag, void* stream);
+int vrnet_render_labels_u8(unsigned char* picture, int B, int ih, int iw, const int* boxes, const int* box_offsets, int n_rows,
+                           const unsigned char* box_palette, int n_box_colors, int thickness, const int* label_idx,
+                           const unsigned char* blob, long blob_bytes, const int* records, int num_classes, int n_sizes,
+                           int size_index, int* flag, void* stream);
+int vrnet_render_labels_ragged_u8(unsigned char* picture, const vrnet_frame_geom* geom, const int* size_index, int B, int ihm,
+                                  int iwm, const int* boxes, const int* box_offsets, int n_rows,
+                                  const unsigned char* box_palette, int n_box_colors, const int* label_idx,
+                                  const unsigned char* blob, long blob_bytes, const int* records, int num_classes, int n_sizes,
+                                  int* flag, void* stream);
+
 
 #ifdef __cplusplus
 }

@@ -32,11 +32,17 @@ in a hipGraph of its own and replayed --steps times between two device events (d
 alternating rounds, next to a plain device copy of the same frame bytes measured the same way (the bound of a byte-bound
 pass: the heat map reads 3 and writes 1 + 3 bytes per pixel, the copy reads 3 and writes 3); and the replay of
 infer.FramePipeline with and without heatmap=True (without it: the chain as it was before the option existed).
+With --labels HxW[,HxW...] it times the replay of infer.FramePipeline(graph=True) without labels (the chain as it was before
+the option existed) and with labels=True (Pillow's built-in face) on the same seeded frames of each original size H x W, in
+alternating rounds, once per --nms pair (default 0.5/0.4), with the kept counts and the atlas bytes; and, on the rows of that
+run, the device time of the two label launches alone (hip.label_index + render.draw_labels, captured and replayed) at the
+frame's own font size, at half that size (a quarter of the label area on the same frame) and on the first half of every
+image's rows.
 
     python tools/bench_infer.py [--phi l] [--size 512] [--batches 1,8,32] [--dtype f32|bf16] [--nms 0.05/0.5,0.3/0.5]
                                 [--seg 1080x1920,480x640] [--letterbox 1080x1920,480x640] [--render 1080x1920,480x640]
                                 [--pipeline 1080x1920] [--evaluate 1080x1920] [--ragged 1080x1920]
-                                [--heatmap 1080x1920,480x640]
+                                [--heatmap 1080x1920,480x640] [--labels 1080x1920,540x960]
 """
 import argparse
 import os
@@ -62,6 +68,7 @@ def main():
     ap.add_argument("--evaluate", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920)")
     ap.add_argument("--ragged", default="", help="comma list of capacities HxW (e.g. 1080x1920)")
     ap.add_argument("--heatmap", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,480x640)")
+    ap.add_argument("--labels", default="", help="comma list of original frame sizes HxW (e.g. 1080x1920,540x960)")
     args = ap.parse_args()
     import asy_vrnet_amd as A
     from asy_vrnet_amd.data import device_letterbox, resize_image
@@ -77,6 +84,7 @@ def main():
     evaluate_sizes = [tuple(int(v) for v in p.split("x")) for p in args.evaluate.split(",") if p]
     ragged_sizes = [tuple(int(v) for v in p.split("x")) for p in args.ragged.split(",") if p]
     heat_sizes = [tuple(int(v) for v in p.split("x")) for p in args.heatmap.split(",") if p]
+    label_sizes = [tuple(int(v) for v in p.split("x")) for p in args.labels.split(",") if p]
 
     def timed(fn):
         for _ in range(3):
@@ -317,6 +325,60 @@ def main():
                   f"{min(rounds[False]):.3f}..{max(rounds[False]):.3f}), with heatmap=True {med[True]:.3f} ms/batch (rounds "
                   f"{min(rounds[True]):.3f}..{max(rounds[True]):.3f}): +{med[True] - med[False]:.3f} ms; heat range "
                   f"{b.heat_range.tolist()}; other fields equal: {same}")
+
+        for ih, iw in label_sizes:
+            import statistics
+            from asy_vrnet_amd import hip, render as rendering
+            gen = torch.Generator().manual_seed(bs)
+            frames = torch.randint(0, 256, (bs, ih, iw, 3), generator=gen, dtype=torch.uint8).to(dev)
+            names = [f"class {c}" for c in range(model.num_classes)]
+            size = rendering.label_font_size(ih)
+            atlas = rendering.LabelAtlas(names, None, sorted({size, max(size // 2, 1)}))
+            for conf, iou in pairs or [(0.5, 0.4)]:
+                pipes = {lab: FramePipeline(model, (ih, iw), S, batch=bs, conf_thres=conf, nms_thres=iou, labels=lab)
+                         for lab in (None, atlas)}
+                rounds = {lab: [] for lab in pipes}
+                for _ in range(5):                   # alternating rounds, so that a drift of the clock hits them alike
+                    for lab, pipe in pipes.items():
+                        rounds[lab].append(timed(lambda: pipe.run(frames, r)))
+                med = {lab: statistics.median(v) for lab, v in rounds.items()}
+                a, b = pipes[None].run(frames, r), pipes[atlas].run(frames, r)
+                same = all(torch.equal(getattr(a, k), getattr(b, k)) for k in ("rows", "kept", "det_counts", "class_map", "seg_counts"))
+                kept = b.kept.tolist()
+                print(f"  + labels {ih}x{iw}, font size {size}, conf {conf} iou {iou}, bs={bs}: FramePipeline replay without labels "
+                      f"{med[None]:.3f} ms/batch (rounds {min(rounds[None]):.3f}..{max(rounds[None]):.3f}), with labels "
+                      f"{med[atlas]:.3f} ms/batch (rounds {min(rounds[atlas]):.3f}..{max(rounds[atlas]):.3f}): "
+                      f"{(med[atlas] - med[None]) / bs * 1e3:+.1f} us/frame; kept {kept}, flag {int(b.flag)}; atlas {atlas.nbytes} bytes "
+                      f"for sizes {atlas.sizes}; other fields equal: {same}; picture changed: {not torch.equal(a.rendered, b.rendered)}")
+                # the two label launches alone, on the rows of that run
+                p = pipes[atlas]
+                rows, offsets, idx = p._draw_rows.clone(), p._offsets.clone(), torch.zeros_like(p._label_idx)
+                keptrows, kept_t, picture = p._rows.clone(), p._kept.clone(), a.rendered.clone()
+                hip.label_index(keptrows, kept_t, offsets, model.num_classes, idx)
+                o = offsets.tolist()
+                firsts = [(o[i + 1] - o[i] + 1) // 2 for i in range(bs)]             # image b keeps the first half of its rows
+                sel = torch.cat([torch.arange(o[i], o[i] + firsts[i]) for i in range(bs)]).to(dev)
+                half = (rows[sel].contiguous(), torch.tensor([sum(firsts[:i]) for i in range(bs + 1)], dtype=torch.int32).to(dev),
+                        idx[sel].contiguous())
+
+                def alone(font, triple):
+                    hip.label_index(keptrows, kept_t, offsets, model.num_classes, idx)
+                    return rendering.draw_labels(picture, triple, atlas, thickness=p.thickness, font_size=font)
+
+                variants = {"own size": replayed(lambda: alone(size, (rows, offsets, idx))),
+                            "half size": replayed(lambda: alone(max(size // 2, 1), (rows, offsets, idx))),
+                            "half the rows": replayed(lambda: alone(size, half))}
+                rounds = {k: [] for k in variants}
+                for _ in range(5):
+                    for k, fn in variants.items():
+                        rounds[k].append(fn())
+                us = {k: statistics.median(v) * 1e3 for k, v in rounds.items()}
+                area = {f: sum(int(atlas.records[atlas.size_index(f), i, 5] + 1) * int(atlas.records[atlas.size_index(f), i, 6] + 1)
+                               for i in idx[:int(offsets[-1])].tolist()) for f in {size, max(size // 2, 1)}}
+                print(f"  + labels {ih}x{iw}, bs={bs}, device time of label_index + render_labels per captured replay (median of 5 "
+                      f"rounds of {args.steps}): font {size} {us['own size']:.1f} us (tags {area[size]} px of {bs * ih * iw} px); "
+                      f"font {max(size // 2, 1)} {us['half size']:.1f} us (tags {area[max(size // 2, 1)]} px); font {size}, first half "
+                      f"of every image's rows {us['half the rows']:.1f} us")
 
         for ih, iw in ragged_sizes:
             import statistics
