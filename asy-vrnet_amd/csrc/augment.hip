@@ -21,7 +21,7 @@
 //   seg         seg_targets_ragged_kernel's body with the visible-index tables and the flip
 //   boxes       box_targets_ragged_kernel's arithmetic with the record's window and the flip before the clip
 //   radar       an integer gather of the stored map, (B, 4, H, W) -> (B, 4, H, W)
-#include "resample.h"
+#include "augment.h"
 
 #pragma clang fp contract(off)
 
@@ -150,49 +150,6 @@ __global__ __launch_bounds__(256) void augment_horizontal_kernel(const AugFrames
   dst[2] = clip8(a2);
 }
 
-// ---- the colour stage: data.hsv_jitter for one pixel ---------------------------------------------------------------------
-constexpr int HSV_SHIFT = 12;
-
-struct ColorLds {
-  int sdiv[256], hdiv[256];          // rint((255 << 12) / i), rint((180 << 12) / (6 i)); 0 at i = 0
-  unsigned char lut[3][256];
-};
-
-__device__ __forceinline__ void hsv_jitter_pixel(const ColorLds& c, unsigned char* px) {
-  const int r = px[0], g = px[1], b = px[2];
-  const int v = max(r, max(g, b)), vmin = min(r, min(g, b)), d = v - vmin;
-  const int s = (d * c.sdiv[v] + (1 << (HSV_SHIFT - 1))) >> HSV_SHIFT;
-  const int h0 = v == r ? g - b : (v == g ? b - r + 2 * d : r - g + 4 * d);
-  int h = (h0 * c.hdiv[d] + (1 << (HSV_SHIFT - 1))) >> HSV_SHIFT;          // arithmetic shift
-  if (h < 0) h += 180;
-  const int h8 = c.lut[0][h & 255], s8 = c.lut[1][s > 255 ? 255 : s], v8 = c.lut[2][v];
-  const float fv = (float)v8 * (1.f / 255.f);
-  float fb = fv, fg = fv, fr = fv;
-  if (s8 != 0) {
-    const float fs = (float)s8 * (1.f / 255.f);
-    float fh = (float)h8 * (6.f / 180.f);
-    if (fh >= 6.f) fh -= 6.f;                      // a table value >= 180: the hue wraps (exact: 6 <= fh < 12)
-    const float fl = floorf(fh);
-    const int sector = (int)fl;                    // 0 .. 5
-    const float f = fh - fl;
-    // sector -> the tab entries of (b, g, r): {1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}, two bits per sector; picked by
-    // selects, so tab stays in registers
-    const unsigned ib = 0x835u >> (2 * sector) & 3u;            // 1,1,3,0,0,2
-    const unsigned ig = 0x583u >> (2 * sector) & 3u;            // 3,0,0,2,1,1
-    const unsigned ir = 0x358u >> (2 * sector) & 3u;            // 0,2,1,1,3,0
-    const float t0 = fv, t1 = fv * (1.f - fs), t2 = fv * (1.f - fs * f), t3 = fv * (1.f - fs * (1.f - f));
-    fb = ib == 0 ? t0 : (ib == 1 ? t1 : (ib == 2 ? t2 : t3));
-    fg = ig == 0 ? t0 : (ig == 1 ? t1 : (ig == 2 ? t2 : t3));
-    fr = ir == 0 ? t0 : (ir == 1 ? t1 : (ir == 2 ? t2 : t3));
-  }
-  const float o[3] = {fr, fg, fb};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int q = (int)__builtin_rintf(o[k] * 255.f);
-    px[k] = (unsigned char)(q < 0 ? 0 : (q > 255 ? 255 : q));
-  }
-}
-
 __global__ __launch_bounds__(256) void augment_vertical_paste_kernel(const AugFramesArgs p) {
   __shared__ ColorLds c;
   const long HW = (long)p.H * p.W;
@@ -200,13 +157,8 @@ __global__ __launch_bounds__(256) void augment_vertical_paste_kernel(const AugFr
   bool bad;
   const AugRec g = aug_load(p.tab, (int)b, p.ihm, p.iwm, p.H, p.W, bad);
   if (g.color) {                     // block-uniform
-    const int i = threadIdx.x;
-    c.sdiv[i] = i ? (int)rint((double)(255 << HSV_SHIFT) / (double)i) : 0;
-    c.hdiv[i] = i ? (int)rint((double)(180 << HSV_SHIFT) / (6.0 * (double)i)) : 0;
     // the 768 table bytes sit at byte 48 of the 816-byte record: 4-byte aligned words
-    const unsigned* lut = reinterpret_cast<const unsigned*>(reinterpret_cast<const int*>(p.tab + b) + AUG_HEAD_INTS);
-    if (i < 192) reinterpret_cast<unsigned*>(&c.lut[0][0])[i] = lut[i];
-    __syncthreads();
+    color_lds_fill(c, reinterpret_cast<const unsigned*>(reinterpret_cast<const int*>(p.tab + b) + AUG_HEAD_INTS));
   }
   if (r >= HW) return;
   const AugTables s = aug_tables(p, (int)b);
@@ -252,9 +204,6 @@ __global__ __launch_bounds__(256) void augment_vertical_paste_kernel(const AugFr
 }
 
 // ---- the segmentation targets: seg_targets_ragged_kernel (csrc/traintargets.hip) under the record's window and flip ------
-constexpr int ST_ROWS = 16;                       // canvas rows of one workgroup
-constexpr long ST_LDS_MAX = 64 * 1024;
-
 struct AugSegArgs {
   const unsigned char* label;        // (B, ihm, iwm)
   const vrnet_aug_rec* tab;          // (B)
@@ -301,27 +250,7 @@ __global__ __launch_bounds__(256) void augment_seg_targets_kernel(const AugSegAr
   }
   __syncthreads();
   float* oh = p.onehot + ((long)b * p.H + y0) * p.W * n1;
-  const int total = npix * n1;
-  if (p.vec4) {
-    for (int q = threadIdx.x; q < total / 4; q += 256) {
-      int px = (q * 4) / n1, c = q * 4 - px * n1, lab = cls[px];
-      f32x4 v;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[j] = c == lab ? 1.f : 0.f;
-        if (++c == n1 && j < 3) {
-          c = 0;
-          lab = cls[++px];
-        }
-      }
-      *reinterpret_cast<f32x4*>(oh + q * 4) = v;
-    }
-  } else {
-    for (int f = threadIdx.x; f < total; f += 256) {
-      const int px = f / n1;
-      oh[f] = f - px * n1 == cls[px] ? 1.f : 0.f;
-    }
-  }
+  st_store_onehot(cls, oh, npix, n1, p.vec4);
 }
 
 // ---- the box targets: box_targets_ragged_kernel under the record's window, with the flip before the clip --------------------
@@ -334,15 +263,6 @@ struct AugBoxArgs {
   int* counts_out;                   // (B)
   int* flag;                         // or null
 };
-
-// out[:, k] * n / i + d assigned back into the integer array (dataloader.py:239-240): numpy multiplies in int64, divides
-// in double (true_divide), adds the offset in double and truncates toward zero on the store
-__device__ __forceinline__ long long map_coord(int v, int n, int i, int d) {
-  double t = (double)((long long)v * (long long)n);
-  t /= (double)i;
-  t += (double)d;
-  return (long long)t;
-}
 
 __global__ __launch_bounds__(256) void augment_box_targets_kernel(const AugBoxArgs p) {
   __shared__ int s_wave[4];

@@ -1,6 +1,6 @@
-// Pillow's 8-bit resample arithmetic (Resample.c) and the stores behind it, shared by the letterbox (csrc/letterbox.hip) and
-// the training augmentation (csrc/augment.hip): both must produce Pillow's bytes, so both use these functions and nothing
-// of their own.  Every double / float operation rounds once (contract off), as the C code Pillow compiles to does.
+// Pillow's 8-bit resample arithmetic (Resample.c) and the stores behind it, shared by the letterbox (csrc/letterbox.hip), the
+// training augmentation (csrc/augment.hip) and the Mosaic (csrc/mosaic.hip): all must produce Pillow's bytes, so all use
+// these functions and nothing of their own.  Every double / float operation rounds once (contract off), as the C code Pillow compiles to does.
 #pragma once
 #include "common.h"
 

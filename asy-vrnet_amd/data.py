@@ -487,24 +487,30 @@ def check_aug_table(table, input_shape, capacity=None, max_taps=None, fn="augmen
     if table.dtype != AUG_DTYPE or table.ndim != 1:
         raise RuntimeError(f"{fn}: the augmentation table is a (B,) array of data.AUG_DTYPE records")
     for b, t in enumerate(table):
-        ih, iw, nw, nh, dx, dy = (int(t[k]) for k in ("ih", "iw", "nw", "nh", "dx", "dy"))
-        if ih <= 0 or iw <= 0:
-            raise RuntimeError(f"{fn}: image {b}: bad size {ih} x {iw}")
-        if capacity is not None and (ih > capacity[0] or iw > capacity[1]):
-            raise RuntimeError(f"{fn}: image {b}: {ih} x {iw} is above the capacity {capacity[0]} x {capacity[1]}")
-        if nw <= 0 or nh <= 0:
-            raise RuntimeError(f"{fn}: image {b}: the draw leaves an empty window ({nh} x {nw}) for {ih} x {iw} in a {H} x {W} input")
-        if max(nw, nh) > 2 * max(W, H) or not (-nw <= dx <= W and -nh <= dy <= H):
-            raise RuntimeError(f"{fn}: image {b}: the window {nh} x {nw} at ({dy}, {dx}) is out of range for a {H} x {W} input "
-                               f"(at most {2 * max(W, H)} pixels, touching the canvas)")
-        if tuple(int(t[k]) for k in ("lb_nw", "lb_nh", "lb_dx", "lb_dy")) != letterbox_geometry(iw, ih, W, H) or \
-                min(int(t["lb_nw"]), int(t["lb_nh"])) <= 0:
-            raise RuntimeError(f"{fn}: image {b}: the record's letterbox window is not that of {ih} x {iw} in a {H} x {W} input")
-        need = max(resample_ksize(iw, nw) if nw != iw else 0, resample_ksize(ih, nh) if nh != ih else 0)
-        if max_taps is not None and need > max_taps:
-            raise RuntimeError(f"{fn}: image {b}: resizing {ih} x {iw} to {nh} x {nw} takes {need} taps, above the tap capacity "
-                               f"{max_taps} (a sliver: raise max_taps)")
+        check_window(t, (H, W), capacity, max_taps, f"image {b}", fn)
     return table
+
+
+def check_window(t, input_shape, capacity, max_taps, where, fn):
+    """`check_aug_table`'s checks for one record or one Mosaic tile t (fields ih, iw, nw, nh, dx, dy, lb_*); where names it."""
+    H, W = input_shape
+    ih, iw, nw, nh, dx, dy = (int(t[k]) for k in ("ih", "iw", "nw", "nh", "dx", "dy"))
+    if ih <= 0 or iw <= 0:
+        raise RuntimeError(f"{fn}: {where}: bad size {ih} x {iw}")
+    if capacity is not None and (ih > capacity[0] or iw > capacity[1]):
+        raise RuntimeError(f"{fn}: {where}: {ih} x {iw} is above the capacity {capacity[0]} x {capacity[1]}")
+    if nw <= 0 or nh <= 0:
+        raise RuntimeError(f"{fn}: {where}: the draw leaves an empty window ({nh} x {nw}) for {ih} x {iw} in a {H} x {W} input")
+    if max(nw, nh) > 2 * max(W, H) or not (-nw <= dx <= W and -nh <= dy <= H):
+        raise RuntimeError(f"{fn}: {where}: the window {nh} x {nw} at ({dy}, {dx}) is out of range for a {H} x {W} input "
+                           f"(at most {2 * max(W, H)} pixels, touching the canvas)")
+    if tuple(int(t[k]) for k in ("lb_nw", "lb_nh", "lb_dx", "lb_dy")) != letterbox_geometry(iw, ih, W, H) or \
+            min(int(t["lb_nw"]), int(t["lb_nh"])) <= 0:
+        raise RuntimeError(f"{fn}: {where}: the record's letterbox window is not that of {ih} x {iw} in a {H} x {W} input")
+    need = max(resample_ksize(iw, nw) if nw != iw else 0, resample_ksize(ih, nh) if nh != ih else 0)
+    if max_taps is not None and need > max_taps:
+        raise RuntimeError(f"{fn}: {where}: resizing {ih} x {iw} to {nh} x {nw} takes {need} taps, above the tap capacity "
+                           f"{max_taps} (a sliver: raise max_taps)")
 
 
 def augment_params(sizes, input_shape, rng, jitter=.3, hue=.1, sat=.7, val=.4, scale=(.25, 2), flip=.5, color=True,
@@ -728,6 +734,314 @@ def check_aug_params(params, sizes, input_shape, capacity, max_taps, fn):
         if (int(tab[b]["ih"]), int(tab[b]["iw"])) != (ih, iw):
             raise RuntimeError(f"{fn}: image {b}: the record is for {int(tab[b]['ih'])} x {int(tab[b]['iw'])}, the frame is {ih} x {iw}")
     return check_aug_table(tab, input_shape, capacity, max_taps, fn)
+
+
+# ---- Mosaic (utils/dataloader.py:251-426: get_random_data_with_Mosaic, merge_bboxes), host side ----------------------------
+# One output image is made from up to four source frames ("tiles"), each resized and pasted as the single-image augmentation
+# does and shown only inside its quadrant of the canvas, which is cut at (cutx, cuty): tile 0 x < cutx, y < cuty; tile 1
+# x < cutx, y >= cuty; tile 2 x >= cutx, y >= cuty; tile 3 x >= cutx, y < cuty (:393-397).  The reference never reaches this code
+# (__getitem__ does not call it) and moves neither the label map nor the radar map; here one record per output image drives
+# all four parts, and the functions below are the truth the kernels of csrc/mosaic.hip are held to.  Two deliberate
+# departures from the reference:
+#   it flips a tile only when the tile has boxes (:329), an accident of its box code; here the flip applies to every tile,
+#     because the label map and the radar map need it whether or not there are boxes
+#   it keeps boxes that the cut has reduced to zero or one pixel; here a second w > 1 and h > 1 test drops them: such a
+#     target costs a row of max_gt and enters SimOTA with no valid centre
+# Its in-place np.random.shuffle of the boxes (:372) is left out, as in `augment_boxes`.
+# vrnet_mosaic_tile / vrnet_mosaic_rec of include/vrnet_hip.h: 48 bytes per tile, one record per OUTPUT image (976 bytes)
+MOSAIC_TILE_DTYPE = np.dtype([(n, "<i4") for n in ("src", "ih", "iw", "nw", "nh", "dx", "dy", "flip", "lb_nw", "lb_nh", "lb_dx",
+                                                   "lb_dy")])
+MOSAIC_DTYPE = np.dtype([(n, "<i4") for n in ("cutx", "cuty", "color", "reserved")] + [("tile", MOSAIC_TILE_DTYPE, (4,)),
+                                                                                       ("lut", "u1", (3, 256))])
+
+
+def mosaic_record(input_shape, cut, tiles, color=False, gains=(1.0, 1.0, 1.0)):
+    """One MOSAIC_DTYPE record written out by hand: cut = (cutx, cuty); tiles: four entries in the reference's tile order, each
+    None (no tile: src = -1) or (src, (ih, iw), nw, nh, dx, dy[, flip]) -- the source slot, that source's own size, the resized
+    window and where it is pasted, and whether the SOURCE is mirrored left-right before the resize; the letterbox window of
+    each source is filled in; the tables are `aug_luts(gains)`.  Not validated: `check_mosaic_table` does that."""
+    H, W = (int(v) for v in input_shape)
+    rec = np.zeros((), MOSAIC_DTYPE)
+    rec["cutx"], rec["cuty"], rec["color"] = int(cut[0]), int(cut[1]), int(bool(color))
+    rec["tile"]["src"] = -1
+    if len(tiles) != 4:
+        raise RuntimeError(f"mosaic_record: four tiles (None: no tile), got {len(tiles)}")
+    for t, tile in enumerate(tiles):
+        if tile is None:
+            continue
+        src, (ih, iw), nw, nh, dx, dy = tile[:6]
+        lb = letterbox_geometry(max(int(iw), 1), max(int(ih), 1), W, H)
+        rec["tile"][t] = (int(src), int(ih), int(iw), int(nw), int(nh), int(dx), int(dy), int(bool(tile[6])) if len(tile) > 6 else 0) + lb
+    rec["lut"] = aug_luts(gains)
+    return rec
+
+
+def mosaic_bytes(table):
+    """A MOSAIC_DTYPE table as the (B, hip.MOSAIC_BYTES) uint8 host tensor the device takes; it shares the table's memory."""
+    return torch.from_numpy(table.view(np.uint8).reshape(len(table), -1))
+
+
+def check_mosaic_table(table, input_shape, sizes, capacity=None, max_taps=None, fn="mosaic_params"):
+    """Raises RuntimeError naming the output image, and the tile where one is at fault, for a record the kernels would have
+    to clamp: a cut outside 0 <= cutx <= W, 0 <= cuty <= H, a src outside -1 .. S - 1 (sizes (S, 2) = (ih, iw) of the sources),
+    a tile whose ih, iw are not its source's own, and per present tile what `check_aug_table` checks.  A tile with src = -1
+    is no tile and the rest of its head is not looked at.  Host only.  Returns the table as a contiguous array."""
+    H, W = (int(v) for v in input_shape)
+    own = frame_sizes(sizes, fn=fn)
+    table = np.ascontiguousarray(table)
+    if table.dtype != MOSAIC_DTYPE or table.ndim != 1:
+        raise RuntimeError(f"{fn}: the Mosaic table is a (B,) array of data.MOSAIC_DTYPE records")
+    for b, rec in enumerate(table):
+        cutx, cuty = int(rec["cutx"]), int(rec["cuty"])
+        if not (0 <= cutx <= W and 0 <= cuty <= H):
+            raise RuntimeError(f"{fn}: image {b}: the cut ({cutx}, {cuty}) is outside a {H} x {W} input")
+        for t, tile in enumerate(rec["tile"]):
+            src = int(tile["src"])
+            if src == -1:
+                continue
+            where = f"image {b}, tile {t}"
+            if not 0 <= src < len(own):
+                raise RuntimeError(f"{fn}: {where}: source {src} of {len(own)} sources")
+            if (int(tile["ih"]), int(tile["iw"])) != tuple(own[src].tolist()):
+                raise RuntimeError(f"{fn}: {where}: the record is for {int(tile['ih'])} x {int(tile['iw'])}, source {src} is "
+                                   f"{own[src][0]} x {own[src][1]}")
+            check_window(tile, (H, W), capacity, max_taps, where, fn)
+    return table
+
+
+def merge_boxes(box_lists, cutx, cuty):
+    """`merge_bboxes` of utils/dataloader.py:251-295 verbatim, with its asymmetric > and >= tests: box_lists, four arrays of
+    rows x1, y1, x2, y2, cls on the canvas, one per tile -> the rows each tile keeps, cut at (cutx, cuty), tile by tile."""
+    merged = []
+    for i in range(len(box_lists)):
+        for box in box_lists[i]:
+            x1, y1, x2, y2 = box[0], box[1], box[2], box[3]
+            if i == 0:
+                if y1 > cuty or x1 > cutx:
+                    continue
+                if y2 >= cuty and y1 <= cuty:
+                    y2 = cuty
+                if x2 >= cutx and x1 <= cutx:
+                    x2 = cutx
+            if i == 1:
+                if y2 < cuty or x1 > cutx:
+                    continue
+                if y2 >= cuty and y1 <= cuty:
+                    y1 = cuty
+                if x2 >= cutx and x1 <= cutx:
+                    x2 = cutx
+            if i == 2:
+                if y2 < cuty or x2 < cutx:
+                    continue
+                if y2 >= cuty and y1 <= cuty:
+                    y1 = cuty
+                if x2 >= cutx and x1 <= cutx:
+                    x1 = cutx
+            if i == 3:
+                if y1 > cuty or x2 < cutx:
+                    continue
+                if y2 >= cuty and y1 <= cuty:
+                    y2 = cuty
+                if x2 >= cutx and x1 <= cutx:
+                    x1 = cutx
+            merged.append([x1, y1, x2, y2, box[-1]])
+    return np.array(merged, dtype=np.float64).reshape(-1, 5)
+
+
+def mosaic_boxes(box_lists, sizes, input_shape, rec):
+    """The boxes of one Mosaic image: box_lists and sizes are those of the S SOURCES, indexed by the tiles' src.  Tile by tile
+    in order 0..3, the source's rows in their order: integer storage as `augment_boxes`; x1, x2 = iw - x2, iw - x1 when the
+    tile flips (:331); x = x * nw / iw + dx, y = y * nh / ih + dy truncated toward zero; the clip to the canvas; kept when w > 1 and
+    h > 1 (:371-382, minus the in-place shuffle); then `merge_boxes` at the record's cut; then a second w > 1 and h > 1 test
+    (this project's: the reference keeps what the cut reduced to a line).  Returns (n, 5) float64 rows x1, y1, x2, y2, cls."""
+    h, w = (int(v) for v in input_shape)
+    per_tile = []
+    for tile in rec["tile"]:
+        src = int(tile["src"])
+        out = np.zeros((0, 5), np.int64)
+        if src >= 0 and box_lists[src] is not None:
+            out = np.array(box_lists[src], dtype=np.int64).reshape(-1, 5)
+        if out.shape[0]:
+            ih, iw = (int(v) for v in sizes[src])
+            nw, nh, dx, dy = (int(tile[k]) for k in ("nw", "nh", "dx", "dy"))
+            if int(tile["flip"]):
+                out[:, [0, 2]] = iw - out[:, [2, 0]]
+            out[:, [0, 2]] = out[:, [0, 2]] * nw / iw + dx
+            out[:, [1, 3]] = out[:, [1, 3]] * nh / ih + dy
+            out[:, 0:2][out[:, 0:2] < 0] = 0
+            out[:, 2][out[:, 2] > w] = w
+            out[:, 3][out[:, 3] > h] = h
+            out = out[((out[:, 2] - out[:, 0]) > 1) & ((out[:, 3] - out[:, 1]) > 1)]
+        per_tile.append(out.astype(np.float64))
+    merged = merge_boxes(per_tile, int(rec["cutx"]), int(rec["cuty"]))
+    return merged[((merged[:, 2] - merged[:, 0]) > 1) & ((merged[:, 3] - merged[:, 1]) > 1)]
+
+
+def mosaic_sample(images, labels, boxes, radars, input_shape, rec):
+    """One Mosaic dataset item under the record rec (`mosaic_params`), on PIL images and numpy arrays; images, labels, boxes
+    and radars are those of the S SOURCES, indexed by the tiles' src; returns (canvas, boxes, label canvas, radar).  Per
+    tile, inside its quadrant: the image is (source, FLIP_LEFT_RIGHT when the tile flips).resize((nw, nh), BICUBIC) pasted
+    at (dx, dy) on grey (128); the label the same with NEAREST on 0 -- flip first, then resize, the reference's order
+    (:328-344), which matters: Pillow's NEAREST recurrence is not mirror-symmetric; the radar (each map (4, H, W) aligned with
+    the letterbox window of its source) is `augment_radar`'s integer gather per tile, this project's definition: with wx = x -
+    dx, wy = y - dy and wx' = nw - 1 - wx when the tile flips, radar[c, lb_dy + ((2 wy + 1) lb_nh) // (2 nh), lb_dx + ((2 wx' + 1)
+    lb_nw) // (2 nw)] inside the window, 0 outside.  `hsv_jitter` then runs over the whole canvas when the record's colour
+    stage is on (:404-419).  Boxes: `mosaic_boxes`.  Unlike the reference (:329) the flip does not depend on the tile having
+    boxes."""
+    from PIL import Image
+    h, w = (int(v) for v in input_shape)
+    cutx, cuty = int(rec["cutx"]), int(rec["cuty"])
+    canvas = np.full((h, w, 3), 128, np.uint8)
+    label = np.zeros((h, w), np.uint8)
+    radar = np.zeros((4, h, w), np.asarray(radars[0]).dtype)
+    for t, tile in enumerate(rec["tile"]):
+        src = int(tile["src"])
+        if src < 0:
+            continue
+        ys = slice(cuty, h) if t in (1, 2) else slice(0, cuty)
+        xs = slice(cutx, w) if t in (2, 3) else slice(0, cutx)
+        nw, nh, dx, dy, lnw, lnh, ldx, ldy = (int(tile[k]) for k in ("nw", "nh", "dx", "dy", "lb_nw", "lb_nh", "lb_dx", "lb_dy"))
+        image, lab = images[src].convert("RGB"), Image.fromarray(np.array(labels[src]))
+        if int(tile["flip"]):
+            image, lab = image.transpose(Image.FLIP_LEFT_RIGHT), lab.transpose(Image.FLIP_LEFT_RIGHT)
+        new_image = Image.new("RGB", [w, h], (128, 128, 128))
+        new_image.paste(image.resize((nw, nh), Image.BICUBIC), (dx, dy))
+        new_label = Image.new("L", [w, h], (0))
+        new_label.paste(lab.resize((nw, nh), Image.NEAREST), (dx, dy))
+        canvas[ys, xs] = np.array(new_image)[ys, xs]
+        label[ys, xs] = np.array(new_label)[ys, xs]
+        wx, wy = np.arange(w, dtype=np.int64) - dx, np.arange(h, dtype=np.int64) - dy
+        okx, oky = (wx >= 0) & (wx < nw), (wy >= 0) & (wy < nh)
+        if int(tile["flip"]):
+            wx = nw - 1 - wx
+        sx = ldx + ((2 * np.where(okx, wx, 0) + 1) * lnw) // (2 * nw)
+        sy = ldy + ((2 * np.where(oky, wy, 0) + 1) * lnh) // (2 * nh)
+        stored = np.asarray(radars[src])
+        moved = np.where((oky[:, None] & okx[None, :])[None], stored[:, sy[:, None], sx[None, :]], np.zeros((), stored.dtype))
+        radar[:, ys, xs] = moved[:, ys, xs]
+    if int(rec["color"]):
+        canvas = hsv_jitter(canvas, rec["lut"])
+    sizes = [(im.size[1], im.size[0]) for im in images]
+    return Image.fromarray(canvas), mosaic_boxes(boxes, sizes, input_shape, rec), Image.fromarray(label), radar
+
+
+def default_mosaic_max_taps(capacity, input_shape, jitter=.3, scale=(.4, 1), prob=1.0, plain=None):
+    """The tap capacity a Mosaic pipeline reserves per table entry: `default_aug_max_taps` at the Mosaic draw's scale[0] = .4
+    (a tile is never enlarged, and never shrunk below .4 of the canvas on its leading axis), or with prob < 1 the larger of
+    that and what the plain draw (keywords plain) needs."""
+    taps = default_aug_max_taps(capacity, input_shape, jitter, scale)
+    if prob < 1:
+        taps = max(taps, default_aug_max_taps(capacity, input_shape, **{k: v for k, v in (plain or {}).items() if k in ("jitter", "scale")}))
+    return taps
+
+
+def mosaic_params(sizes, input_shape, rng, batch, prob=1.0, jitter=.3, hue=.1, sat=.7, val=.4, scale=(.4, 1), cut=(.3, .7), flip=.5,
+                  color=True, plain=None, capacity=None, max_taps=None, fn="mosaic_params"):
+    """The random draw of Mosaic, one MOSAIC_DTYPE record per OUTPUT image (`mosaic_bytes` of the table is what the device
+    takes): sizes (4 * batch, 2) = (ih, iw) per source, output image b uses sources 4 b .. 4 b + 3; rng a numpy.random.RandomState
+    or a seed.  Per output image one rand() for mosaic = rand() < prob -- always drawn, so the stream does not depend on prob
+    (train.py:108-112: `mosaic_prob`; the `special_aug_ratio` policy is the caller's choice of prob per epoch).
+    If mosaic, in the order of utils/dataloader.py:299-360 and :404: min_offset_x, then min_offset_y = rand(cut[0], cut[1]); per
+    tile the flip (rand() < flip), the two rand() of new_ar = iw / ih * rand(1 - jitter, 1 + jitter) / rand(1 - jitter, 1 + jitter),
+    then scale = rand(scale[0], scale[1]), nh = int(scale * h), nw = int(nh * new_ar) when new_ar < 1, else nw = int(scale * w), nh =
+    int(nw / new_ar); with cutx = int(w * min_offset_x), cuty = int(h * min_offset_y) the placement (dx, dy) = (cutx - nw, cuty -
+    nh), (cutx - nw, cuty), (cutx, cuty), (cutx, cuty - nh) for tiles 0..3; then uniform(-1, 1, 3) * [hue, sat, val] + 1 for the gains
+    (drawn with color=False too).
+    If not mosaic, the `augment_params` draw runs for source 4 b with the keywords in plain and is written as a record with
+    cut = (w, h), tile 0 only and src = -1 for tiles 1-3; a flipping draw mirrors the SOURCE, as every Mosaic tile does, and its
+    window goes to dx' = w - dx - nw, which is where a mirror of the canvas puts it.  The three unused sources of such an image
+    still cost their copies into the slots: the batch layout is fixed at four sources per output image.
+    Host only.  Raises RuntimeError naming the image (and tile) for what `check_mosaic_table` checks."""
+    arr = frame_sizes(sizes, 4 * int(batch), fn)
+    H, W = (int(v) for v in input_shape)
+    rs = rng if isinstance(rng, np.random.RandomState) else np.random.RandomState(rng)
+
+    def rand(a=0.0, b=1.0):
+        return rs.rand() * (b - a) + a
+    for s, (ih, iw) in enumerate(arr.tolist()):            # what no draw can mend is raised before the generator moves
+        if ih <= 0 or iw <= 0:
+            raise RuntimeError(f"{fn}: image {s // 4}, tile {s % 4}: bad size {ih} x {iw}")
+        if capacity is not None and (ih > capacity[0] or iw > capacity[1]):
+            raise RuntimeError(f"{fn}: image {s // 4}, tile {s % 4}: {ih} x {iw} is above the capacity {capacity[0]} x {capacity[1]}")
+    tab = np.zeros(int(batch), MOSAIC_DTYPE)
+    for b in range(int(batch)):
+        if rand() < prob:
+            cutx, cuty = int(W * rand(cut[0], cut[1])), int(H * rand(cut[0], cut[1]))
+            tiles = []
+            for t in range(4):
+                ih, iw = arr[4 * b + t].tolist()
+                flipped = rand() < flip
+                new_ar = iw / ih * rand(1 - jitter, 1 + jitter) / rand(1 - jitter, 1 + jitter)
+                sc = rand(scale[0], scale[1])
+                if new_ar < 1:
+                    nh = int(sc * H)
+                    nw = int(nh * new_ar)
+                else:
+                    nw = int(sc * W)
+                    nh = int(nw / new_ar)
+                dx = cutx - nw if t < 2 else cutx
+                dy = cuty - nh if t in (0, 3) else cuty
+                tiles.append((4 * b + t, (ih, iw), nw, nh, dx, dy, flipped))
+            gains = rs.uniform(-1, 1, 3) * [hue, sat, val] + 1
+            tab[b] = mosaic_record((H, W), (cutx, cuty), tiles, color, gains)
+        else:
+            a = augment_params(arr[4 * b:4 * b + 1], (H, W), rs, capacity=capacity, max_taps=max_taps, fn=fn, **(plain or {}))[0]
+            nw, dx = int(a["nw"]), int(a["dx"])
+            tile = (4 * b, (int(a["ih"]), int(a["iw"])), nw, int(a["nh"]), W - dx - nw if int(a["flip"]) else dx, int(a["dy"]),
+                    int(a["flip"]))
+            tab[b] = mosaic_record((H, W), (W, H), [tile, None, None, None], int(a["color"]))
+            tab[b]["lut"] = a["lut"]
+    return check_mosaic_table(tab, (H, W), arr, capacity, max_taps, fn)
+
+
+def device_mosaic_batch_ragged(frames, sizes, input_shape, labels, boxes, radar, num_classes_seg, params, max_gt=64,
+                               capacity=None, max_taps=None, flag=None, device="cuda"):
+    """`device_augment_batch_ragged` under Mosaic: the dataset item `mosaic_sample` builds per OUTPUT image from S raw source
+    frames of different sizes, ON THE DEVICE -- vrnet_mosaic_frames_u8 (three launches: the float images),
+    vrnet_mosaic_seg_targets_u8, vrnet_mosaic_box_targets_f32 and vrnet_mosaic_radar_f32.  frames / labels / sizes / boxes /
+    capacity: those of the S sources, as `device_augment_batch_ragged` takes them; radar (S, 4, H, W) float32, each map aligned
+    with the letterbox window of its source; params: a (B,) MOSAIC_DTYPE table (`mosaic_params`, or `mosaic_record`s written by
+    hand), validated here (`check_mosaic_table`); max_taps: `default_mosaic_max_taps` with prob < 1.  Returns (images (B,3,H,W)
+    f32, png (B,H,W) int64, onehot (B,H,W,ns+1) f32, targets (B,max_gt,5) f32, counts (B) int32, radar (B,4,H,W) f32), bit for
+    bit what the host functions give per output image -- as long as every image keeps at most max_gt boxes; of more, the
+    first max_gt stay and flag receives hip.FLAG_BOX_COUNT."""
+    from . import hip
+    fn = "device_mosaic_batch_ragged"
+    items, own = ragged_items(frames, sizes, None, (3,), "frames", fn)
+    S = len(own)
+    if labels is None:
+        raise RuntimeError(f"{fn}: the label maps are required")
+    labs = ragged_items(labels, own, S, (), "label maps", fn)[0]
+    if len(boxes) != S:
+        raise RuntimeError(f"{fn}: {len(boxes)} box lists for {S} sources")
+    if capacity is None:
+        capacity = tuple(items.shape[1:3]) if torch.is_tensor(items) else (int(own[:, 0].max()), int(own[:, 1].max()))
+    ihm, iwm = (int(v) for v in capacity)
+    for t in (items, labs):
+        if torch.is_tensor(t) and (t.shape[1] > ihm or t.shape[2] > iwm):
+            raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {(ihm, iwm)}")
+    H, W = (int(v) for v in input_shape)
+    ns = int(num_classes_seg)
+    max_taps = default_mosaic_max_taps((ihm, iwm), (H, W), prob=0.0) if max_taps is None else int(max_taps)
+    tab = check_mosaic_table(params, (H, W), own, (ihm, iwm), max_taps, fn)
+    rad = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
+    if tuple(rad.shape) != (S, 4, H, W) or rad.dtype != torch.float32:
+        raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(S, 4, H, W)}, got {rad.dtype} {tuple(rad.shape)}")
+    packed, counts = pack_boxes(boxes, max_gt)
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        mos = mosaic_bytes(tab).to(dev, non_blocking=True)
+        img = torch.zeros((S, ihm, iwm, 3), dtype=torch.uint8, device=dev)
+        fill_slots(img, items, own)
+        lab = torch.zeros((S, ihm, iwm), dtype=torch.uint8, device=dev)
+        fill_slots(lab, labs, own)
+        images = torch.empty((len(tab), 3, H, W), dtype=torch.float32, device=dev)
+        hip.mosaic_frames(img, mos, H, W, max_taps, images=images, flag=flag)
+        png, onehot = hip.mosaic_seg_targets(lab, mos, H, W, ns, flag=flag)
+        targets, counts_out = hip.mosaic_box_targets(packed.to(dev, non_blocking=True), counts.to(dev, non_blocking=True), mos,
+                                                     (ihm, iwm), H, W, flag=flag)
+        radar_out = hip.mosaic_radar(rad.to(dev, non_blocking=True).contiguous(), mos, (ihm, iwm), flag=flag)
+    return images, png, onehot, targets, counts_out, radar_out
 
 
 class FrameDataset(torch.utils.data.Dataset):

@@ -217,6 +217,26 @@ class TrainStep(GraphedStep):
     caller's own sampler; the step's generator is then not advanced).  The table is validated on the host with the rest,
     before anything is enqueued.  max_taps defaults to `data.default_aug_max_taps`.  augment without from_frames raises.
 
+    With from_frames=True and mosaic set -- True, or a dict of `data.mosaic_params`' keywords (prob, jitter, hue, sat, val, scale,
+    cut, flip, color) -- the prologue is Mosaic (utils/dataloader.py:251-426; train.py:108-112 `mosaic`, `mosaic_prob`): every
+    output image is cut from four source frames, and one record per output image drives the frames, the label maps, the boxes
+    and the radar maps alike (`data.mosaic_sample` is the rule, with its two departures from the reference):
+
+        step = TrainStep(..., from_frames=True, capacity=(ihm, iwm), mosaic=True, augment=None | True | {...}, aug_seed=0)
+        res = step(frames, radar, boxes, labels, sizes=None, aug=None)
+
+    frames, labels and boxes are those of 4 B SOURCES, radar is (4 B, 4, H, W); output image b uses sources 4 b .. 4 b + 3.  Six
+    launches -- vrnet_mosaic_frames_u8 (three), vrnet_mosaic_seg_targets_u8, vrnet_mosaic_box_targets_f32, vrnet_mosaic_radar_f32
+    -- stand where the six of augment stood.  Every call draws its table from the step's RandomState(aug_seed)
+    (`data.mosaic_params`); `step.mosaic_prob` (the `prob` keyword, default 1) is read at every call, so the `special_aug_ratio`
+    policy -- Mosaic for the first share of the epochs -- is one assignment by the caller and needs no new capture; an image
+    that is not mosaicked gets the single-image draw with the keywords of augment.  aug= hands in an explicit
+    `data.MOSAIC_DTYPE` table instead (any tile may name any of the 4 B sources; the generator is then not advanced);
+    `aug_table` keeps the last table.  Host validation as before, with one more rule: the sources of an output image together
+    bring at most max_gt boxes -- conservative, since the cut may drop some, but known before anything is enqueued.  mosaic
+    without from_frames, with radar_points (a tile needs a clip rectangle the view record does not carry: a follow-up) or
+    with letterbox_image=False raises at construction.
+
     With from_frames=True and radar_points=max_points the step takes radar POINTS where it took maps:
 
         step = TrainStep(..., from_frames=True, capacity=(ihm, iwm), radar_points=4096, radar_radius=0, radar_min_depth=0.1, calib=P)
@@ -256,8 +276,16 @@ class TrainStep(GraphedStep):
     def __init__(self, net, yolo_loss, optimizer, ema, batch, size, num_seg_classes, max_gt=64, cls_weights=None,
                  focal_loss=True, dice_loss=True, f_score=False, from_bytes=False, device="cuda", warmup=2, segments=None,
                  from_frames=False, capacity=None, max_taps=None, letterbox_image=True, augment=None, aug_seed=None,
-                 radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None):
+                 radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, mosaic=None):
         optimizer._uniform("lr")
+        if mosaic is not None and mosaic is not False:
+            if not from_frames:
+                raise RuntimeError("TrainStep: mosaic needs from_frames=True (the tiles are cut from the raw frames)")
+            if radar_points is not None:
+                raise RuntimeError("TrainStep: mosaic with radar_points is not built: a tile needs a clip rectangle that "
+                                   "vrnet_radar_view does not carry (a follow-up); give radar maps")
+            if not letterbox_image:
+                raise RuntimeError("TrainStep: mosaic places the tiles itself; letterbox_image=False does not apply")
         if radar_points is not None and not from_frames:
             raise RuntimeError("TrainStep: radar_points needs from_frames=True (the points are projected into the frame's window)")
         if radar_points is None and (calib is not None or radar_radius != 0 or radar_min_depth != 0.1):
@@ -281,6 +309,10 @@ class TrainStep(GraphedStep):
         self.focal_loss, self.dice_loss, self.f_score, self.from_bytes = bool(focal_loss), bool(dice_loss), bool(f_score), bool(from_bytes)
         self.from_frames = bool(from_frames)
         self.augment = None if augment is None or augment is False else ({} if augment is True else dict(augment))
+        self.mosaic = None if mosaic is None or mosaic is False else ({} if mosaic is True else dict(mosaic))
+        if self.mosaic is not None:
+            self.mosaic_prob = float(self.mosaic.pop("prob", 1.0))      # read at every call: the caller may assign it
+        self.sources = int(batch) * (4 if self.mosaic is not None else 1)
         self.names = ("total", "loss_det", "loss_seg") + (("f_score",) if self.f_score else ())
         with torch.cuda.device(dev):
             self.labels = torch.zeros((batch, max(self.max_gt, 1), 5), dtype=torch.float32, device=dev)
@@ -309,7 +341,20 @@ class TrainStep(GraphedStep):
         (h, w), B = self.hw, batch
         self.capacity = ihm, iwm = tuple(int(v) for v in capacity)
         self.letterbox_image = bool(letterbox_image)
-        if self.augment is None:
+        S = self.sources
+        if self.mosaic is not None:
+            # mosaic_prob may change from call to call: the capacity serves the Mosaic draw and the plain one
+            kw = {k: self.mosaic[k] for k in ("jitter", "scale") if k in self.mosaic}
+            self.max_taps = data.default_mosaic_max_taps(self.capacity, self.hw, prob=0.0, plain=self.augment, **kw) \
+                if max_taps is None else int(max_taps)
+            self._aug_rng = np.random.RandomState(aug_seed)
+            lb = data.letterbox_geometry(iwm, ihm, w, h)
+            recs = [data.mosaic_record(self.hw, (w, h), [(4 * b, self.capacity) + lb, None, None, None]) for b in range(B)]
+            self.aug_table = data.check_mosaic_table(np.stack(recs), self.hw, [self.capacity] * S, self.capacity, self.max_taps,
+                                                     "TrainStep")
+            self.aug = data.mosaic_bytes(self.aug_table).to(dev)
+            self.radar_in = torch.zeros((S, 4, h, w), dtype=torch.float32, device=dev)
+        elif self.augment is None:
             self.max_taps = data.default_max_taps(self.capacity, self.hw) if max_taps is None else int(max_taps)
             table = data.frame_geometry([self.capacity] * B, self.hw, self.letterbox_image, self.capacity, self.max_taps, "TrainStep")
             self.geom = data.geometry_bytes(table).to(dev)
@@ -325,17 +370,25 @@ class TrainStep(GraphedStep):
         if self.radar_points is not None:    # no points in the warm-up and the capture
             self.points, self.views = self.radar_points.buffers(table if self.augment is None else self.aug_table, dev)
             self._radar_ws = self.radar_points.workspace(self.hw, dev)
-        self.frames_u8 = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
-        self.frame_labels_u8 = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
-        self.boxes = torch.zeros((B, max(self.max_gt, 1), 5), dtype=torch.int32, device=dev)
-        self.box_counts = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.frames_u8 = torch.zeros((S, ihm, iwm, 3), dtype=torch.uint8, device=dev)
+        self.frame_labels_u8 = torch.zeros((S, ihm, iwm), dtype=torch.uint8, device=dev)
+        self.boxes = torch.zeros((S, max(self.max_gt, 1), 5), dtype=torch.int32, device=dev)
+        self.box_counts = torch.zeros(S, dtype=torch.int32, device=dev)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._lb_ws = torch.empty(hip.letterbox_ragged_workspace_bytes(B, ihm, iwm, h, w, self.max_taps), dtype=torch.uint8,
-                                  device=dev)
+        ws_bytes = hip.mosaic_workspace_bytes if self.mosaic is not None else hip.letterbox_ragged_workspace_bytes
+        self._lb_ws = torch.empty(ws_bytes(B, ihm, iwm, h, w, self.max_taps), dtype=torch.uint8, device=dev)
 
     def _prologue(self):
         if self.from_bytes:
             hip.batch_formats(self.images_u8, self.labels_u8, self.ns, images=self.x, png_out=self.png, onehot=self.onehot)
+        elif self.from_frames and self.mosaic is not None:
+            h, w = self.hw
+            hip.mosaic_frames(self.frames_u8, self.aug, h, w, self.max_taps, images=self.x, flag=self.flag, ws=self._lb_ws)
+            hip.mosaic_seg_targets(self.frame_labels_u8, self.aug, h, w, self.ns, png_out=self.png, onehot=self.onehot,
+                                   flag=self.flag)
+            hip.mosaic_box_targets(self.boxes, self.box_counts, self.aug, self.capacity, h, w, targets=self.labels,
+                                   counts_out=self.counts, flag=self.flag)
+            hip.mosaic_radar(self.radar_in, self.aug, self.capacity, out=self.r, flag=self.flag)
         elif self.from_frames and self.augment is not None:
             h, w = self.hw
             hip.augment_frames(self.frames_u8, self.aug, h, w, self.max_taps, images=self.x, flag=self.flag, ws=self._lb_ws)
@@ -431,13 +484,19 @@ class TrainStep(GraphedStep):
     def _validate_frames(self, frames, radar, boxes, labels, sizes, aug=None, calib=None):
         """The host checks of a from_frames call, which need no device; returns what the copies take, the geometry table
         (with augment: the augmentation table, drawn here unless the caller brought one) among it."""
-        B, (h, w), fn = self.batch, self.hw, "TrainStep"
+        B, (h, w), fn = self.sources, self.hw, "TrainStep"          # with mosaic: the 4 B sources
         items, own = data.ragged_items(frames, sizes, B, (3,), "frames", fn)
         labs = data.ragged_items(labels, own, B, (), "label maps", fn)[0]
         for t in (items, labs):
             if torch.is_tensor(t) and (t.shape[1] > self.capacity[0] or t.shape[2] > self.capacity[1]):
                 raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {self.capacity}")
-        if self.augment is None:
+        if self.mosaic is not None:
+            table = None
+            if aug is not None:
+                if len(np.asarray(aug)) != self.batch:
+                    raise RuntimeError(f"{fn}: the Mosaic table is a ({self.batch},) array of data.MOSAIC_DTYPE records")
+                table = data.check_mosaic_table(aug, self.hw, own, self.capacity, self.max_taps, fn)
+        elif self.augment is None:
             if aug is not None:
                 raise RuntimeError(f"{fn}: an aug table belongs to a step built with augment")
             table = data.frame_geometry(own, self.hw, self.letterbox_image, self.capacity, self.max_taps, fn)
@@ -456,6 +515,17 @@ class TrainStep(GraphedStep):
         if len(boxes) != B:
             raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
         packed, counts = data.pack_boxes(boxes, self.max_gt)              # raises, naming the image
+        if self.mosaic is not None:
+            # conservative: the sources of an output image TOGETHER bring at most max_gt boxes, whatever the cut would drop
+            # (the kernel would keep the first max_gt of more and report FLAG_BOX_COUNT); a drawn table uses sources 4 b .. 4 b + 3
+            for b in range(self.batch):
+                srcs = range(4 * b, 4 * b + 4) if table is None else [int(s) for s in table[b]["tile"]["src"] if s >= 0]
+                total = sum(int(counts[s]) for s in srcs)
+                if total > self.max_gt:
+                    raise RuntimeError(f"{fn}: image {b}: its sources bring {total} boxes together, above max_gt = {self.max_gt}")
+            if table is None:
+                table = data.mosaic_params(own, self.hw, self._aug_rng, self.batch, prob=float(self.mosaic_prob), plain=self.augment,
+                                           capacity=self.capacity, max_taps=self.max_taps, fn=fn, **self.mosaic)
         if table is None:
             # a draw that fails its own checks (an empty window, a sliver's taps) has advanced the generator: the next call
             # draws anew
@@ -490,7 +560,10 @@ class TrainStep(GraphedStep):
                 data.fill_slots(self.frames_u8, items, own)
                 data.fill_slots(self.frame_labels_u8, labs, own)
                 # fresh pinned staging tensors (`pack_boxes` makes its own), as for the step record below
-                if self.augment is None:
+                if self.mosaic is not None:
+                    self.aug_table = table
+                    self.aug.copy_(data.mosaic_bytes(table).pin_memory(), non_blocking=True)
+                elif self.augment is None:
                     self.geom.copy_(data.geometry_bytes(table).pin_memory(), non_blocking=True)
                 else:
                     self.aug_table = table
@@ -511,7 +584,7 @@ class TrainStep(GraphedStep):
                 self.points.copy_(radar[0], non_blocking=True)
                 self.views.copy_(radar[1].pin_memory(), non_blocking=True)
             else:
-                (self.r if self.augment is None else self.radar_in).copy_(radar, non_blocking=True)
+                (self.r if self.augment is None and self.mosaic is None else self.radar_in).copy_(radar, non_blocking=True)
             if not self.from_frames:
                 self.labels.copy_(packed, non_blocking=True)
                 self.counts.copy_(counts, non_blocking=True)

@@ -153,6 +153,11 @@ _SIGS = {
     "vrnet_augment_seg_targets_u8": ([P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_augment_box_targets_f32": ([P, P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_augment_radar_f32": ([P, P, I, I, I, I, I, P, P, P], I),
+    "vrnet_mosaic_workspace_bytes": ([I] * 6, L),
+    "vrnet_mosaic_frames_u8": ([P, I, P] + [I] * 6 + [P, P, P, P, L, P], I),
+    "vrnet_mosaic_seg_targets_u8": ([P, I, P, I, I, I, I, I, I, P, P, P, P], I),
+    "vrnet_mosaic_box_targets_f32": ([P, P, I, P, I, I, I, I, I, I, P, P, P, P], I),
+    "vrnet_mosaic_radar_f32": ([P, I, P, I, I, I, I, I, P, P, P], I),
     "vrnet_radar_map_workspace": ([I, I, I], L),
     "vrnet_radar_map_f32": ([P, I, P, I, I, I, I, F, P, P, P, L, P], I),
     "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
@@ -1517,6 +1522,100 @@ def augment_radar(radar, aug, capacity, out=None, flag=None):
     _tensors("augment_radar", ((radar, (B, 4, H, W), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
     _check(_lib.vrnet_augment_radar_f32(ptr(radar), _aug(aug, B, "augment_radar"), B, int(capacity[0]), int(capacity[1]), H, W,
                                         ptr(out), ptr(flag), stream()), "augment_radar")
+    return out
+
+
+# ---- Mosaic (include/vrnet_hip.h "Mosaic on the device"): one record per OUTPUT image, S source slots --------------------------
+MOSAIC_BYTES = 976       # sizeof(vrnet_mosaic_rec)
+
+
+def _mosaic(mosaic, fn):
+    """The table: a contiguous uint8 GPU tensor (B, MOSAIC_BYTES), 8-byte aligned (`data.mosaic_bytes` packs it); returns
+    (pointer, B)."""
+    if mosaic is None or mosaic.dtype != torch.uint8 or mosaic.dim() != 2 or mosaic.shape[1] != MOSAIC_BYTES or \
+            not mosaic.is_contiguous() or not mosaic.is_cuda or mosaic.data_ptr() % 8:
+        raise RuntimeError(f"{fn}: the Mosaic table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape (B, {MOSAIC_BYTES})")
+    return ptr(mosaic), mosaic.shape[0]
+
+
+def mosaic_workspace_bytes(B, ihm, iwm, H, W, max_taps):
+    return _lib.vrnet_mosaic_workspace_bytes(B, ihm, iwm, H, W, max_taps)
+
+
+def mosaic_frames(img_u8, mosaic, H, W, max_taps, canvas=None, images=None, flag=None, ws=None):
+    """S raw source frames -> B Mosaic canvases (vrnet_mosaic_frames_u8): img_u8 (S,ihm,iwm,3) padded slots, mosaic the
+    (B, MOSAIC_BYTES) table -> canvas (B,H,W,3) uint8 and / or images (B,3,H,W) f32, what `data.mosaic_sample` and
+    `device_batch` give per output image; max_taps: the tap capacity of a table entry; flag (1) int32 or None; ws:
+    mosaic_workspace_bytes(B, ihm, iwm, H, W, max_taps) bytes.  No host validation: `data.check_mosaic_table` is the
+    caller's."""
+    if img_u8 is None or img_u8.dim() != 4:
+        raise RuntimeError("mosaic_frames: expected frames (S, ihm, iwm, 3)")
+    S, ihm, iwm = img_u8.shape[:3]
+    H, W = int(H), int(W)
+    tab, B = _mosaic(mosaic, "mosaic_frames")
+    _tensors("mosaic_frames", ((img_u8, (S, ihm, iwm, 3), torch.uint8), (canvas, (B, H, W, 3), torch.uint8),
+                               (images, (B, 3, H, W), torch.float32), (flag, (1,), torch.int32)))
+    need = _lib.vrnet_mosaic_workspace_bytes(B, ihm, iwm, H, W, int(max_taps))
+    if ws is None:
+        ws = _ws.get(need, img_u8.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"mosaic_frames: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    _check(_lib.vrnet_mosaic_frames_u8(ptr(img_u8), S, tab, B, ihm, iwm, H, W, int(max_taps), ptr(canvas), ptr(images), ptr(flag),
+                                       ptr(ws), ws.numel(), stream()), "mosaic_frames")
+
+
+def mosaic_seg_targets(label_u8, mosaic, H, W, num_classes_seg, png_out=None, onehot=None, flag=None):
+    """`augment_seg_targets` under Mosaic records (vrnet_mosaic_seg_targets_u8): label_u8 (S,ihm,iwm) padded slots -> png_out
+    (B,H,W) int64 and onehot (B,H,W,ns+1) f32 of the Mosaic label canvas.  Returns (png_out, onehot)."""
+    if label_u8 is None or label_u8.dim() != 3:
+        raise RuntimeError("mosaic_seg_targets: expected label maps (S, ihm, iwm)")
+    S, ihm, iwm = label_u8.shape
+    H, W, ns = int(H), int(W), int(num_classes_seg)
+    tab, B = _mosaic(mosaic, "mosaic_seg_targets")
+    if png_out is None:
+        png_out = torch.empty((B, H, W), dtype=torch.int64, device=label_u8.device)
+    if onehot is None:
+        onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=label_u8.device)
+    _tensors("mosaic_seg_targets", ((label_u8, (S, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
+                                    (onehot, (B, H, W, ns + 1), torch.float32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_mosaic_seg_targets_u8(ptr(label_u8), S, tab, B, ihm, iwm, H, W, ns, ptr(png_out), ptr(onehot), ptr(flag),
+                                            stream()), "mosaic_seg_targets")
+    return png_out, onehot
+
+
+def mosaic_box_targets(boxes, counts, mosaic, capacity, H, W, targets=None, counts_out=None, flag=None):
+    """The boxes of S sources -> the packed targets of B Mosaic images (vrnet_mosaic_box_targets_f32): what
+    `data.mosaic_boxes` and `data.boxes_xyxy_to_cxcywh` give per output image, in tile-then-row order; of more than max_gt
+    kept rows the first max_gt stay and flag receives FLAG_BOX_COUNT.  Returns (targets, counts_out)."""
+    if boxes is None or boxes.dim() != 3:
+        raise RuntimeError("mosaic_box_targets: expected boxes (S, max_gt, 5)")
+    S, max_gt = boxes.shape[:2]
+    tab, B = _mosaic(mosaic, "mosaic_box_targets")
+    if targets is None:
+        targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
+    if counts_out is None:
+        counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
+    _tensors("mosaic_box_targets", ((boxes, (S, max_gt, 5), torch.int32), (counts, (S,), torch.int32),
+                                    (targets, (B, max_gt, 5), torch.float32), (counts_out, (B,), torch.int32),
+                                    (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_mosaic_box_targets_f32(ptr(boxes), ptr(counts), S, tab, B, max_gt, int(capacity[0]), int(capacity[1]), int(H),
+                                             int(W), ptr(targets), ptr(counts_out), ptr(flag), stream()), "mosaic_box_targets")
+    return targets, counts_out
+
+
+def mosaic_radar(radar, mosaic, capacity, out=None, flag=None):
+    """The radar maps of S sources under Mosaic records (vrnet_mosaic_radar_f32): radar (S,4,H,W) f32, each aligned with the
+    letterbox window of its source -> out (B,4,H,W) f32, the integer gather of `data.mosaic_sample`; out is not radar;
+    capacity = (ihm, iwm) of the frames' slots, by which the records are judged."""
+    if radar is None or radar.dim() != 4 or radar.shape[1] != 4:
+        raise RuntimeError("mosaic_radar: expected radar maps (S, 4, H, W)")
+    S, _, H, W = radar.shape
+    tab, B = _mosaic(mosaic, "mosaic_radar")
+    if out is None:
+        out = torch.empty((B, 4, H, W), dtype=torch.float32, device=radar.device)
+    _tensors("mosaic_radar", ((radar, (S, 4, H, W), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_mosaic_radar_f32(ptr(radar), S, tab, B, int(capacity[0]), int(capacity[1]), H, W, ptr(out), ptr(flag),
+                                       stream()), "mosaic_radar")
     return out
 
 

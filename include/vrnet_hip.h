@@ -1112,6 +1112,66 @@ int vrnet_augment_box_targets_f32(const int* boxes, const int* counts, const vrn
 int vrnet_augment_radar_f32(const float* radar, const vrnet_aug_rec* aug, int B, int ihm, int iwm, int H, int W, float* out,
                             int* flag, void* stream);
 
+/* ---- Mosaic on the device (csrc/mosaic.hip) ----------------------------------------------------------------------------------
+ * Added within ABI 11: new symbols and one new record layout (vrnet_mosaic_rec, with its vrnet_mosaic_tile) only, no existing
+ * signature, layout or kernel behaviour changed; hip.py binds every declared symbol at import.
+ * The four-tiles-into-one-canvas augmentation of utils/dataloader.py:251-426 (get_random_data_with_Mosaic, merge_bboxes),
+ * applied consistently to the frames, the label maps, the boxes and the radar maps.  Nothing here draws a random number: the
+ * host draws one record per OUTPUT image (data.mosaic_params) and the kernels apply it; they equal the host functions
+ * data.mosaic_sample / mosaic_boxes / merge_boxes / hsv_jitter bit for bit.  Inputs are S source slots (padded (S, ihm, iwm)
+ * frames and label maps, (S, max_gt, 5) boxes, (S, 4, H, W) radar maps), outputs B images; a tile names its source slot, and
+ * several tiles, of one output image or of several, may name the same one.  Output image on grid y; its record is read and
+ * clamped on the device, tile by tile as a vrnet_aug_rec is (src in -1 .. S - 1, 0 <= cutx <= W, 0 <= cuty <= H besides), and if
+ * ANYTHING of it had to be clamped, or a size or window of a present tile is not positive, bit 256 of *flag
+ * (VR_FLAG_GEOMETRY; flag may be NULL) is set and that output image is what an empty record gives in every output (grey
+ * canvas without the colour stage, label 0, no boxes, radar 0); the other images are unaffected.  A resize that needs more
+ * taps than max_taps sets the bit as well.  No host synchronisation; capturable.
+ * Quadrants (dataloader.py:393-397): canvas pixel (x, y) belongs to tile 0 when x < cutx and y < cuty, tile 1 when x < cutx and
+ * y >= cuty, tile 2 when x >= cutx and y >= cuty, tile 3 when x >= cutx and y < cuty.  With wx = x - dx, wy = y - dy of that tile
+ * the pixel is inside when the tile is present (src >= 0) and 0 <= wx < nw, 0 <= wy < nh.  flip mirrors the SOURCE left-right
+ * before the resize (:328-344) -- for every tile, where the reference flips only tiles that have boxes.
+ * vrnet_mosaic_frames_u8: img (S, ihm, iwm, 3) -> canvas (B, H, W, 3) uint8 and / or images (B, 3, H, W) fp32 normalised as
+ *   vrnet_batch_formats_u8 does: inside, Pillow's BICUBIC bytes of the (mirrored) source resized to nw x nh (a pass whose
+ *   size does not change is skipped), grey (128) elsewhere; then -- color != 0 -- the colour stage of
+ *   vrnet_augment_frames_u8 over the whole canvas (:404-419).  Three launches.  workspace:
+ *   vrnet_mosaic_workspace_bytes(B, ihm, iwm, H, W, max_taps) bytes, twice vrnet_letterbox_ragged_workspace's: tables and the
+ *   horizontal result are indexed by canvas column / row, one set for the top and one for the bottom half of the canvas
+ *   (columns), one for the left and one for the right side (rows).
+ * vrnet_mosaic_seg_targets_u8: label (S, ihm, iwm) -> png_out (B, H, W) int64 and onehot (B, H, W, ns + 1) fp32 as
+ *   vrnet_seg_targets_ragged_u8 writes them: inside, Pillow's NEAREST pick of the (mirrored) source, 0 elsewhere.
+ * vrnet_mosaic_box_targets_f32: boxes (S, max_gt, 5) int32 with counts (S) -> targets (B, max_gt, 5) rows [cx, cy, w, h, cls]
+ *   and counts_out (B).  Tile by tile, the source's rows in their order: x1, x2 = iw - x2, iw - x1 when flip; x = x nw / iw +
+ *   dx, y = y nh / ih + dy truncated toward zero (vrnet_augment_box_targets_f32's arithmetic); the clip to the canvas; kept
+ *   when w > 1 and h > 1 (:371-382); merge_bboxes (:251-295) verbatim at the cut; kept when w > 1 and h > 1 again, which the
+ *   reference does not ask.  Kept rows are compacted in that order; of more than max_gt the first max_gt stay and bit 512
+ *   (VR_FLAG_BOX_COUNT) is set, as for a source count outside [0, max_gt] (clamped).
+ * vrnet_mosaic_radar_f32: radar (S, 4, H, W), each aligned with the letterbox window (lb_*) of its source -> out (B, 4, H, W):
+ *   inside, with wx' = flip ? nw - 1 - wx : wx, radar[src][c][lb_dy + ((2 wy + 1) lb_nh) / (2 nh)][lb_dx + ((2 wx' + 1) lb_nw) /
+ *   (2 nw)] (integer division), 0 elsewhere.  out != radar; ihm, iwm only judge the record as the other three do. */
+typedef struct vrnet_mosaic_tile {
+  int src;                           /* the source slot, 0 .. S - 1; -1: no tile (the rest is then not looked at) */
+  int ih, iw;                        /* that source's own size inside its (ihm, iwm) slot */
+  int nw, nh, dx, dy;                /* the resized tile and where it is pasted; may leave the canvas on every side */
+  int flip;                          /* != 0: mirror the SOURCE left-right before the resize */
+  int lb_nw, lb_nh, lb_dx, lb_dy;    /* data.letterbox_geometry of the source: the window its stored radar map is aligned with */
+} vrnet_mosaic_tile;                 /* 48 bytes */
+typedef struct vrnet_mosaic_rec {
+  int cutx, cuty;                    /* the cut: 0 <= cutx <= W, 0 <= cuty <= H */
+  int color, reserved;               /* != 0: run the colour stage; 0 */
+  vrnet_mosaic_tile tile[4];         /* in the reference's tile order (index of :349-360) */
+  unsigned char lut[3][256];         /* hue, saturation, value tables of the colour stage */
+} vrnet_mosaic_rec;                  /* 976 bytes; the table must be 8-byte aligned */
+long vrnet_mosaic_workspace_bytes(int B, int ihm, int iwm, int H, int W, int max_taps);
+int vrnet_mosaic_frames_u8(const unsigned char* img, int S, const vrnet_mosaic_rec* mosaic, int B, int ihm, int iwm, int H, int W,
+                           int max_taps, unsigned char* canvas, float* images, int* flag, void* workspace,
+                           long workspace_bytes, void* stream);
+int vrnet_mosaic_seg_targets_u8(const unsigned char* label, int S, const vrnet_mosaic_rec* mosaic, int B, int ihm, int iwm, int H,
+                                int W, int num_classes_seg, long long* png_out, float* onehot, int* flag, void* stream);
+int vrnet_mosaic_box_targets_f32(const int* boxes, const int* counts, int S, const vrnet_mosaic_rec* mosaic, int B, int max_gt,
+                                 int ihm, int iwm, int H, int W, float* targets, int* counts_out, int* flag, void* stream);
+int vrnet_mosaic_radar_f32(const float* radar, int S, const vrnet_mosaic_rec* mosaic, int B, int ihm, int iwm, int H, int W,
+                           float* out, int* flag, void* stream);
+
 /* ---- the radar map from 4D radar points (csrc/radarmap.hip) ---------------------------------------------------------------
  * Added within ABI 11: new symbols and one new record layout (vrnet_radar_view) only, no existing signature, layout or kernel
  * behaviour changed; hip.py binds every declared symbol at import.

@@ -29,6 +29,12 @@ augment=True) on their own (eager launches of `_prologue()` between HIP events, 
 (copies and the host's draw of the table included).  The last line is one JSON record.
 
     python tools/bench_train_step.py --augment --frames 1080x1920 [--phi l]
+
+--mosaic (with --frames) times Mosaic against that augmentation the same way: the six-launch prologue of
+TrainStep(from_frames=True, augment=True) on B frames and the six-launch prologue of TrainStep(from_frames=True, mosaic=True)
+on 4 B frames, on their own and inside the whole step (copies and the host's draw included).
+
+    python tools/bench_train_step.py --mosaic --frames 1080x1920 [--phi l]
 """
 import argparse
 import math
@@ -237,6 +243,74 @@ def augmented(a):
     print(json.dumps(rec))
 
 
+def mosaicked(a):
+    import json
+    from asy_vrnet_amd.graph import TrainStep
+    dev = torch.device("cuda:0")
+    B, S, NC, NS = a.batch, a.size, 4, 9
+    ih, iw = (int(v) for v in a.frames.lower().split("x"))
+    raw_frames, raw_maps, boxes, _ = synthetic_frames(4 * B, ih, iw, S, NC, NS)
+    boxes = [bx[:8] for bx in boxes]                        # four sources of an image bring at most max_gt = 32 together
+    r = torch.cat([A.synthetic_inputs(B, S, 1 + k, dev)[1] for k in range(4)])
+    pin = lambda t: t.cpu().contiguous().pin_memory()
+    hraw, hmaps, hr = pin(raw_frames), pin(raw_maps), pin(r)
+    batch = {1: (hraw[:B], hr[:B], boxes[:B], hmaps[:B], [(ih, iw)] * B), 4: (hraw, hr, boxes, hmaps, [(ih, iw)] * 4 * B)}
+
+    def trainer():
+        model = A.EfficientVRNet(NC, NS, a.phi, img_size=(S, S)).to(dev).train()
+        A.randomize_state_dict(model.state_dict(), seed=0)
+        return (model, losses.YOLOLoss(NC).to(dev), optim.build_optimizer(model, "sgd", 1.25e-3, 0.937, 5e-4),
+                optim.ModelEMA(model))
+    t1, t2 = trainer(), trainer()
+    kw = dict(max_gt=32, from_frames=True, capacity=(ih, iw), device=dev, aug_seed=0)
+    step_a = TrainStep(t1[0], t1[1], t1[2], t1[3], B, S, NS, augment=True, **kw)
+    step_m = TrainStep(t2[0], t2[1], t2[2], t2[3], B, S, NS, mosaic=True, **kw)
+
+    def step_window(step, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            last = step(*batch[step.sources // B])["total"]
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, float(last)
+
+    def prologue_window(step, n):
+        """The prologue alone on the slots, tables and boxes the last step left: device time between two events."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        step._prologue()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            step._prologue()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+    names = ("prologue augment (6 launches)", "prologue mosaic (6 launches)", "step augment", "step mosaic")
+    for step in (step_a, step_m):
+        step_window(step, 3)
+    ms, _ = step_window(step_a, 3)
+    n_steps = max(a.steps, int(math.ceil(500.0 / ms)))
+    per, last = {n: [] for n in names}, {}
+    for _ in range(a.rounds):                               # alternating: a drift of the box hits every contender alike
+        per[names[0]].append(prologue_window(step_a, 50))
+        per[names[1]].append(prologue_window(step_m, 50))
+        for name, step in ((names[2], step_a), (names[3], step_m)):
+            ms, last[name] = step_window(step, n_steps)
+            per[name].append(ms)
+    print(f"phi={a.phi} bs={B} {S}x{S} frames {ih}x{iw} sgd+ema, real loss: ms, median of {a.rounds} alternating rounds "
+          f"(min .. max); augment: {B} frames per step, mosaic: {4 * B}; device {torch.cuda.get_device_name(dev)}")
+    rec = {"tool": "bench_train_step --mosaic", "phi": a.phi, "batch": B, "size": S, "frames": [ih, iw], "rounds": a.rounds,
+           "steps_per_round": n_steps, "max_taps": [step_a.max_taps, step_m.max_taps],
+           "workspace_bytes": [step_a._lb_ws.numel(), step_m._lb_ws.numel()],
+           "flag": [step_a.stats()["flag"], step_m.stats()["flag"]]}
+    for name in names:
+        v = sorted(per[name])
+        print(f"  {name:36s} {float(np.median(v)):9.3f}  ({v[0]:.3f} .. {v[-1]:.3f})" +
+              (f"  last total loss {last[name]:.4f}" if name in last else ""))
+        rec[name] = {"median_ms": round(float(np.median(v)), 4), "min_ms": round(v[0], 4), "max_ms": round(v[-1], 4)}
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--phi", default="l")
@@ -249,7 +323,13 @@ def main():
                     help="with --captured: raw frames of this size; adds the host-letterbox and the from_frames contenders")
     ap.add_argument("--augment", action="store_true",
                     help="with --frames: the augmented prologue and step against the plain frame path, alternating rounds")
+    ap.add_argument("--mosaic", action="store_true",
+                    help="with --frames: the Mosaic prologue and step against the augmented frame path, alternating rounds")
     a = ap.parse_args()
+    if a.mosaic:
+        if not a.frames:
+            ap.error("--mosaic needs --frames IHxIW")
+        return mosaicked(a)
     if a.augment:
         if not a.frames:
             ap.error("--augment needs --frames IHxIW")
