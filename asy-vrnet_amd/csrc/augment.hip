@@ -21,6 +21,7 @@
 //   seg         seg_targets_ragged_kernel's body with the visible-index tables and the flip
 //   boxes       box_targets_ragged_kernel's arithmetic with the record's window and the flip before the clip
 //   radar       an integer gather of the stored map, (B, 4, H, W) -> (B, 4, H, W)
+// The tap sum is resample.h's; the paste epilogue, the one-hot store, the box rules and the radar pick are augment.h's.
 #include "augment.h"
 
 #pragma clang fp contract(off)
@@ -136,18 +137,7 @@ __global__ __launch_bounds__(256) void augment_horizontal_kernel(const AugFrames
   const AugTables s = aug_tables(p, b);
   const int xmin = s.hb[2 * v], n = s.hb[2 * v + 1];            // xmin + n <= iw: inside the slot's row
   const unsigned char* src = p.img + (((long)b * p.ihm + row) * p.iwm + xmin) * 3;
-  const int* k = s.hk + v;
-  int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-  for (int t = 0; t < n; ++t) {
-    const int w = k[(long)t * p.W];
-    a0 += w * src[3 * t];
-    a1 += w * src[3 * t + 1];
-    a2 += w * src[3 * t + 2];
-  }
-  unsigned char* dst = p.mid + (((long)b * p.ihm + row) * p.W + v) * 3;
-  dst[0] = clip8(a0);
-  dst[1] = clip8(a1);
-  dst[2] = clip8(a2);
+  resample_taps3(src, 3, s.hk + v, p.W, n, p.mid + (((long)b * p.ihm + row) * p.W + v) * 3);
 }
 
 __global__ __launch_bounds__(256) void augment_vertical_paste_kernel(const AugFramesArgs p) {
@@ -162,7 +152,6 @@ __global__ __launch_bounds__(256) void augment_vertical_paste_kernel(const AugFr
   }
   if (r >= HW) return;
   const AugTables s = aug_tables(p, (int)b);
-  const long e = b * HW + r;
   const int y = (int)(r / p.W), x = (int)(r - (long)y * p.W);
   const int wx = (g.flip ? p.W - 1 - x : x) - g.dx, wy = y - g.dy;
   const bool inside = !g.empty && wx >= 0 && wx < g.nw && wy >= 0 && wy < g.nh;
@@ -175,18 +164,7 @@ __global__ __launch_bounds__(256) void augment_vertical_paste_kernel(const AugFr
     if (g.nh != g.ih) {
       const int vy = wy - g.y0;
       const int ymin = s.vb[2 * vy], n = s.vb[2 * vy + 1];
-      const int* k = s.vk + vy;
-      src += ymin * rs;
-      int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-      for (int t = 0; t < n; ++t) {
-        const int w = k[(long)t * p.H];
-        a0 += w * src[t * rs];
-        a1 += w * src[t * rs + 1];
-        a2 += w * src[t * rs + 2];
-      }
-      v[0] = clip8(a0);
-      v[1] = clip8(a1);
-      v[2] = clip8(a2);
+      resample_taps3(src + ymin * rs, rs, s.vk + vy, p.H, n, v);
     } else {
       src += wy * rs;
       v[0] = src[0];
@@ -194,13 +172,7 @@ __global__ __launch_bounds__(256) void augment_vertical_paste_kernel(const AugFr
       v[2] = src[2];
     }
   }
-  if (g.color) hsv_jitter_pixel(c, v);             // the whole canvas, its padding included, as the reference
-  if (p.canvas) {
-    p.canvas[e * 3] = v[0];
-    p.canvas[e * 3 + 1] = v[1];
-    p.canvas[e * 3 + 2] = v[2];
-  }
-  if (p.images) normalise_store(p.images, b, HW, r, v);
+  paste_store(c, g.color, v, p.canvas, p.images, b, HW, r);
 }
 
 // ---- the segmentation targets: seg_targets_ragged_kernel (csrc/traintargets.hip) under the record's window and flip ------
@@ -213,8 +185,6 @@ struct AugSegArgs {
   float* onehot;                     // (B, H, W, ns + 1)
   int* flag;                         // or null
 };
-
-__host__ __device__ inline long st_lds_bytes(int H, int W) { return ((long)W + H) * (long)sizeof(int) + (long)ST_ROWS * W; }
 
 __global__ __launch_bounds__(256) void augment_seg_targets_kernel(const AugSegArgs p) {
   extern __shared__ int st_lds[];
@@ -266,7 +236,7 @@ struct AugBoxArgs {
 
 __global__ __launch_bounds__(256) void augment_box_targets_kernel(const AugBoxArgs p) {
   __shared__ int s_wave[4];
-  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y;
   bool bad;
   const AugRec g = aug_load(p.tab, b, p.ihm, p.iwm, p.H, p.W, bad);
   const int given = p.counts[b];
@@ -295,31 +265,18 @@ __global__ __launch_bounds__(256) void augment_box_targets_kernel(const AugBoxAr
         x2 = p.W - x1;
         x1 = t;
       }
+      // box_clip_keep (augment.h), written out: the call gave this kernel another instruction schedule
       if (x1 < 0) x1 = 0;
       if (y1 < 0) y1 = 0;
       if (x2 > p.W) x2 = p.W;
       if (y2 > p.H) y2 = p.H;
       keep = x2 - x1 > 1 && y2 - y1 > 1;
     }
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) s_wave[wave] = __popcll(mask);
-    __syncthreads();
-    int at = base;
-    for (int w = 0; w < wave; ++w) at += s_wave[w];
-    at += __popcll(mask & ((1ull << lane) - 1ull));
-    base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    if (keep) {                      // at <= i < max_gt: compaction never moves a row up
-      const double w = (double)(x2 - x1), h = (double)(y2 - y1);
-      float* o = out + (long)at * 5;
-      o[0] = (float)((double)x1 + w / 2);
-      o[1] = (float)((double)y1 + h / 2);
-      o[2] = (float)w;
-      o[3] = (float)h;
-      o[4] = (float)c;
-    }
+    const int at = box_compact_slot(keep, base, s_wave);
+    if (keep) box_store_cxcywh(out + (long)at * 5, x1, y1, x2, y2, c);      // at <= i < max_gt: compaction never moves a row up
     __syncthreads();                 // s_wave is rewritten by the next chunk
   }
-  for (int i = base * 5 + threadIdx.x; i < p.max_gt * 5; i += 256) out[i] = 0.f;
+  box_zero_tail(base, p.max_gt, out);
   if (threadIdx.x == 0) p.counts_out[b] = base;
 }
 
@@ -342,12 +299,7 @@ __global__ __launch_bounds__(256) void augment_radar_kernel(const AugRadarArgs p
   const int y = (int)(r / p.W), x = (int)(r - (long)y * p.W);
   const int wx = (g.flip ? p.W - 1 - x : x) - g.dx, wy = y - g.dy;
   const bool inside = !g.empty && g.lb_nw > 0 && g.lb_nh > 0 && wx >= 0 && wx < g.nw && wy >= 0 && wy < g.nh;
-  long at = 0;
-  if (inside) {                      // (2 w + 1) lb / (2 n) < lb: inside the letterbox window, which is inside the canvas
-    const int sy = g.lb_dy + (int)(((2LL * wy + 1) * g.lb_nh) / (2LL * g.nh));
-    const int sx = g.lb_dx + (int)(((2LL * wx + 1) * g.lb_nw) / (2LL * g.nw));
-    at = (long)sy * p.W + sx;
-  }
+  const long at = inside ? radar_pick(0, wx, wy, g.nw, g.nh, g.lb_nw, g.lb_nh, g.lb_dx, g.lb_dy, p.W) : 0;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const long plane = (b * 4 + c) * HW;
@@ -367,18 +319,12 @@ extern "C" int vrnet_augment_frames_u8(const unsigned char* img, const vrnet_aug
   VR_CHECK_ARG((long)B * ihm * iwm < (1L << 31) && (long)B * H * W < (1L << 31) && (long)B * ihm * W < (1L << 31) &&
                    (long)B * lb_ragged_slot_ints(H, W, max_taps) < (1L << 31) && H < (1 << 24) && W < (1 << 24),
                "augment_frames: batch too large");
-  const long tables = lb_align(B * lb_ragged_slot_ints(H, W, max_taps) * (long)sizeof(int));
-  const long need = tables + lb_align((long)B * ihm * W * 3);      // == vrnet_letterbox_ragged_workspace
-  if (!workspace || workspace_bytes < need) {
-    vr_set_error("augment_frames: workspace %ld < %ld bytes", workspace ? workspace_bytes : 0L, need);
-    return VR_ERR_WORKSPACE;
-  }
   AugFramesArgs p{};
+  // one table set and one horizontal result per image: vrnet_letterbox_ragged_workspace's bytes
+  if (!fm_split_workspace("augment_frames", workspace, workspace_bytes, B, ihm, H, W, max_taps, p.tables, p.mid)) return VR_ERR_WORKSPACE;
   p.img = img; p.tab = aug;
   p.B = B; p.ihm = ihm; p.iwm = iwm; p.H = H; p.W = W; p.cap = max_taps;
   p.slot = lb_ragged_slot_ints(H, W, max_taps);
-  p.tables = static_cast<int*>(workspace);
-  p.mid = static_cast<unsigned char*>(workspace) + tables;
   p.canvas = canvas; p.images = images; p.flag = flag;
   hipStream_t st = vr_stream(stream);
   hipLaunchKernelGGL(augment_tables_kernel, dim3((unsigned)vr_cdiv((long)W + H, 256), B), dim3(256), 0, st, p);
@@ -392,8 +338,7 @@ extern "C" int vrnet_augment_seg_targets_u8(const unsigned char* label, const vr
                                             int W, int num_classes_seg, long long* png_out, float* onehot, int* flag,
                                             void* stream) {
   VR_CHECK_ARG(label && aug && png_out && onehot, "augment_seg_targets: label, aug, png_out and onehot are required");
-  VR_CHECK_ARG(B > 0 && B < 65536 && ihm > 0 && iwm > 0 && H > 0 && W > 0 && H < (1 << 24) && W < (1 << 24),
-               "augment_seg_targets: bad shape (B %d, slots %d x %d, canvas %d x %d)", B, ihm, iwm, H, W);
+  VR_CHECK_ARG(fm_shape_ok(B, ihm, iwm, H, W), "augment_seg_targets: bad shape (B %d, slots %d x %d, canvas %d x %d)", B, ihm, iwm, H, W);
   VR_CHECK_ARG(num_classes_seg > 0 && num_classes_seg < 255, "augment_seg_targets: 0 < num_classes_seg < 255, got %d",
                num_classes_seg);
   VR_CHECK_ARG(st_lds_bytes(H, W) <= ST_LDS_MAX, "augment_seg_targets: a %d x %d canvas needs %ld bytes of LDS, above %ld", H, W,
@@ -417,8 +362,7 @@ extern "C" int vrnet_augment_box_targets_f32(const int* boxes, const int* counts
                                              void* stream) {
   VR_CHECK_ARG(boxes && counts && aug && targets && counts_out,
                "augment_box_targets: boxes, counts, aug, targets and counts_out are required");
-  VR_CHECK_ARG(B > 0 && B < 65536 && max_gt > 0 && max_gt <= (1 << 20) && ihm > 0 && iwm > 0 && H > 0 && W > 0 &&
-                   H < (1 << 24) && W < (1 << 24),
+  VR_CHECK_ARG(fm_shape_ok(B, ihm, iwm, H, W) && max_gt > 0 && max_gt <= (1 << 20),
                "augment_box_targets: bad shape (B %d, max_gt %d, slots %d x %d, canvas %d x %d)", B, max_gt, ihm, iwm, H, W);
   AugBoxArgs p{};
   p.boxes = boxes; p.counts = counts; p.tab = aug;
@@ -432,9 +376,7 @@ extern "C" int vrnet_augment_box_targets_f32(const int* boxes, const int* counts
 extern "C" int vrnet_augment_radar_f32(const float* radar, const vrnet_aug_rec* aug, int B, int ihm, int iwm, int H, int W,
                                        float* out, int* flag, void* stream) {
   VR_CHECK_ARG(radar && aug && out && radar != out, "augment_radar: radar, aug and out are required, and out is not the input");
-  VR_CHECK_ARG(B > 0 && B < 65536 && ihm > 0 && iwm > 0 && H > 0 && W > 0 && H < (1 << 24) && W < (1 << 24) &&
-                   (long)B * 4 * H * W < (1L << 40),
-               "augment_radar: bad shape (B %d, slots %d x %d, canvas %d x %d)", B, ihm, iwm, H, W);
+  VR_CHECK_ARG(fm_shape_ok(B, ihm, iwm, H, W) && (long)B * 4 * H * W < (1L << 40), "augment_radar: bad shape (B %d, slots %d x %d, canvas %d x %d)", B, ihm, iwm, H, W);
   AugRadarArgs p{};
   p.radar = radar; p.tab = aug;
   p.B = B; p.ihm = ihm; p.iwm = iwm; p.H = H; p.W = W;

@@ -16,7 +16,7 @@
 //               stores -- canvas rows, CHW planes and the label canvas, each coalesced over a wave's consecutive x
 // The accumulator is int32 as Pillow's: the taps of a row are normalised to sum 1 with negative lobes, sum |k| < 1.4 * 2^22
 // for the bicubic kernel at any scale, so |2^21 + sum k * v| < 2^21 + 255 * 1.4 * 2^22 < 1.5e9 < 2^31.
-#include "resample.h"               // bicubic_taps, clip8, normalise_store, lb_ksize: shared with csrc/augment.hip
+#include "resample.h"               // bicubic_taps, resample_taps3, normalise_store, lb_ksize: shared with augment.hip, mosaic.hip
 
 #pragma clang fp contract(off)
 
@@ -56,18 +56,7 @@ __global__ __launch_bounds__(256) void letterbox_horizontal_kernel(const Letterb
   const int xx = (int)(e - row * p.nw);
   const int xmin = p.hb[2 * xx], n = p.hb[2 * xx + 1];
   const unsigned char* src = p.img + (row * p.iw + xmin) * 3;
-  const int* k = p.hk + xx;
-  int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-  for (int t = 0; t < n; ++t) {
-    const int w = k[(long)t * p.nw];
-    a0 += w * src[3 * t];
-    a1 += w * src[3 * t + 1];
-    a2 += w * src[3 * t + 2];
-  }
-  unsigned char* dst = p.mid + e * 3;
-  dst[0] = clip8(a0);
-  dst[1] = clip8(a1);
-  dst[2] = clip8(a2);
+  resample_taps3(src, 3, p.hk + xx, p.nw, n, p.mid + e * 3);
 }
 
 __global__ __launch_bounds__(256) void letterbox_vertical_paste_kernel(const LetterboxArgs p) {
@@ -85,18 +74,7 @@ __global__ __launch_bounds__(256) void letterbox_vertical_paste_kernel(const Let
     const long rs = (long)p.nw * 3;
     if (p.nh != p.ih) {
       const int ymin = p.vb[2 * wy], n = p.vb[2 * wy + 1];
-      const int* k = p.vk + wy;
-      src += ymin * rs;
-      int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-      for (int t = 0; t < n; ++t) {
-        const int w = k[(long)t * p.nh];
-        a0 += w * src[t * rs];
-        a1 += w * src[t * rs + 1];
-        a2 += w * src[t * rs + 2];
-      }
-      v[0] = clip8(a0);
-      v[1] = clip8(a1);
-      v[2] = clip8(a2);
+      resample_taps3(src + ymin * rs, rs, p.vk + wy, p.nh, n, v);
     } else {
       src += wy * rs;
       v[0] = src[0];
@@ -198,18 +176,7 @@ __global__ __launch_bounds__(256) void letterbox_ragged_horizontal_kernel(const 
   const RaggedTables s = ragged_tables(p, b);
   const int xmin = s.hb[2 * xx], n = s.hb[2 * xx + 1];
   const unsigned char* src = p.img + (((long)b * p.ihm + row) * p.iwm + xmin) * 3;
-  const int* k = s.hk + xx;
-  int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-  for (int t = 0; t < n; ++t) {
-    const int w = k[(long)t * g.nw];
-    a0 += w * src[3 * t];
-    a1 += w * src[3 * t + 1];
-    a2 += w * src[3 * t + 2];
-  }
-  unsigned char* dst = p.mid + (((long)b * p.ihm + row) * p.W + xx) * 3;
-  dst[0] = clip8(a0);
-  dst[1] = clip8(a1);
-  dst[2] = clip8(a2);
+  resample_taps3(src, 3, s.hk + xx, g.nw, n, p.mid + (((long)b * p.ihm + row) * p.W + xx) * 3);
 }
 
 __global__ __launch_bounds__(256) void letterbox_ragged_vertical_paste_kernel(const RaggedLetterboxArgs p) {
@@ -231,18 +198,7 @@ __global__ __launch_bounds__(256) void letterbox_ragged_vertical_paste_kernel(co
     const long rs = (resized ? (long)p.W : (long)p.iwm) * 3;
     if (g.nh != g.ih) {
       const int ymin = s.vb[2 * wy], n = s.vb[2 * wy + 1];
-      const int* k = s.vk + wy;
-      src += ymin * rs;
-      int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-      for (int t = 0; t < n; ++t) {
-        const int w = k[(long)t * g.nh];
-        a0 += w * src[t * rs];
-        a1 += w * src[t * rs + 1];
-        a2 += w * src[t * rs + 2];
-      }
-      v[0] = clip8(a0);
-      v[1] = clip8(a1);
-      v[2] = clip8(a2);
+      resample_taps3(src + ymin * rs, rs, s.vk + wy, g.nh, n, v);
     } else {
       src += wy * rs;
       v[0] = src[0];

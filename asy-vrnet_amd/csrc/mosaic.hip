@@ -202,21 +202,9 @@ __global__ __launch_bounds__(256) void mosaic_horizontal_kernel(const MosFramesA
   const MosTables m = mos_tables(p, b, half);
   const int xmin = m.hb[2 * x], n = m.hb[2 * x + 1];            // xmin + n <= iw: inside the slot's row
   const unsigned char* src = p.img + ((long)t.v[T_SRC] * p.ihm + row) * p.iwm * 3;
-  const int* k = m.hk + x;
   // the flipped source: column c of it is column iw - 1 - c of the slot
   const int first = t.v[T_FLIP] ? t.v[T_IW] - 1 - xmin : xmin, step = t.v[T_FLIP] ? -3 : 3;
-  src += (long)first * 3;
-  int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-  for (int j = 0; j < n; ++j) {
-    const int w = k[(long)j * p.W];
-    a0 += w * src[j * step];
-    a1 += w * src[j * step + 1];
-    a2 += w * src[j * step + 2];
-  }
-  unsigned char* dst = p.mid + ((((long)b * 2 + half) * p.ihm + row) * p.W + x) * 3;
-  dst[0] = clip8(a0);
-  dst[1] = clip8(a1);
-  dst[2] = clip8(a2);
+  resample_taps3(src + (long)first * 3, step, m.hk + x, p.W, n, p.mid + ((((long)b * 2 + half) * p.ihm + row) * p.W + x) * 3);
 }
 
 __global__ __launch_bounds__(256) void mosaic_vertical_paste_kernel(const MosFramesArgs p) {
@@ -228,7 +216,6 @@ __global__ __launch_bounds__(256) void mosaic_vertical_paste_kernel(const MosFra
   if (g.color)                       // block-uniform
     color_lds_fill(c, reinterpret_cast<const unsigned*>(reinterpret_cast<const int*>(p.tab + b) + MOS_LUT_INTS));
   if (r >= HW) return;
-  const long e = b * HW + r;
   const int y = (int)(r / p.W), x = (int)(r - (long)y * p.W);
   const int side = x >= g.cutx, half = y >= g.cuty;
   const MosTile t = mos_pick(g, mos_tile_of(side, half));
@@ -243,18 +230,7 @@ __global__ __launch_bounds__(256) void mosaic_vertical_paste_kernel(const MosFra
     if (t.v[T_NH] != t.v[T_IH]) {
       const MosTables m = mos_tables(p, (int)b, side);
       const int ymin = m.vb[2 * y], n = m.vb[2 * y + 1];
-      const int* k = m.vk + y;
-      src += ymin * rs;
-      int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-      for (int j = 0; j < n; ++j) {
-        const int w = k[(long)j * p.H];
-        a0 += w * src[j * rs];
-        a1 += w * src[j * rs + 1];
-        a2 += w * src[j * rs + 2];
-      }
-      v[0] = clip8(a0);
-      v[1] = clip8(a1);
-      v[2] = clip8(a2);
+      resample_taps3(src + ymin * rs, rs, m.vk + y, p.H, n, v);
     } else {
       src += wy * rs;
       v[0] = src[0];
@@ -262,13 +238,7 @@ __global__ __launch_bounds__(256) void mosaic_vertical_paste_kernel(const MosFra
       v[2] = src[2];
     }
   }
-  if (g.color) hsv_jitter_pixel(c, v);             // the whole canvas, its padding included, as the reference
-  if (p.canvas) {
-    p.canvas[e * 3] = v[0];
-    p.canvas[e * 3 + 1] = v[1];
-    p.canvas[e * 3 + 2] = v[2];
-  }
-  if (p.images) normalise_store(p.images, b, HW, r, v);
+  paste_store(c, g.color, v, p.canvas, p.images, b, HW, r);
 }
 
 // ---- the segmentation targets ------------------------------------------------------------------------------------------------
@@ -364,7 +334,7 @@ __device__ __forceinline__ bool mos_merge(int t, long long& x1, long long& y1, l
 
 __global__ __launch_bounds__(256) void mosaic_box_targets_kernel(const MosBoxArgs p) {
   __shared__ int s_wave[4];
-  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y;
   bool bad;
   const MosRec g = mos_load(p.tab, b, p.S, p.ihm, p.iwm, p.H, p.W, bad);
   float* out = p.targets + (long)b * p.max_gt * 5;
@@ -396,22 +366,14 @@ __global__ __launch_bounds__(256) void mosaic_box_targets_kernel(const MosBoxArg
         y1 = map_coord(r[1], v[T_NH], v[T_IH], v[T_DY]);
         x2 = map_coord(x2, v[T_NW], v[T_IW], v[T_DX]);
         y2 = map_coord(r[3], v[T_NH], v[T_IH], v[T_DY]);
-        if (x1 < 0) x1 = 0;
-        if (y1 < 0) y1 = 0;
-        if (x2 > p.W) x2 = p.W;
-        if (y2 > p.H) y2 = p.H;
-        keep = x2 - x1 > 1 && y2 - y1 > 1;
+        keep = box_clip_keep(x1, y1, x2, y2, p.W, p.H);
         keep = keep && mos_merge(t, x1, y1, x2, y2, g.cutx, g.cuty);
         keep = keep && x2 - x1 > 1 && y2 - y1 > 1;           // what the cut reduced to a line or less is dropped
       }
-      const unsigned long long mask = __ballot(keep);
-      if (lane == 0) s_wave[wave] = __popcll(mask);
-      __syncthreads();
-      int at = base;
-      for (int w = 0; w < wave; ++w) at += s_wave[w];
-      at += __popcll(mask & ((1ull << lane) - 1ull));
-      base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-      if (keep && at < p.max_gt) {   // four sources can keep more than max_gt rows between them: the first max_gt stay
+      const int at = box_compact_slot(keep, base, s_wave);
+      // four sources can keep more than max_gt rows between them: the first max_gt stay.  box_store_cxcywh (augment.h),
+      // written out: the call gave this kernel other registers and another instruction schedule
+      if (keep && at < p.max_gt) {
         const double w = (double)(x2 - x1), h = (double)(y2 - y1);
         float* o = out + (long)at * 5;
         o[0] = (float)((double)x1 + w / 2);
@@ -427,7 +389,7 @@ __global__ __launch_bounds__(256) void mosaic_box_targets_kernel(const MosBoxArg
     bits |= VR_FLAG_BOX_COUNT;
     base = p.max_gt;
   }
-  for (int i = base * 5 + threadIdx.x; i < p.max_gt * 5; i += 256) out[i] = 0.f;
+  box_zero_tail(base, p.max_gt, out);
   if (threadIdx.x == 0) {
     p.counts_out[b] = base;
     if (bits && p.flag) atomicOr(p.flag, bits);
@@ -454,28 +416,25 @@ __global__ __launch_bounds__(256) void mosaic_radar_kernel(const MosRadarArgs p)
   const MosTile t = mos_pick(g, mos_tile_of(x >= g.cutx, y >= g.cuty));
   const bool inside = mos_shows(t, x, y);
   long at = 0;
-  if (inside) {                      // (2 w + 1) lb / (2 n) < lb: inside the letterbox window, which is inside the canvas
+  if (inside) {
     const int wy = y - t.v[T_DY], wx = t.v[T_FLIP] ? t.v[T_NW] - 1 - (x - t.v[T_DX]) : x - t.v[T_DX];
-    const int sy = t.v[T_LDY] + (int)(((2LL * wy + 1) * t.v[T_LNH]) / (2LL * t.v[T_NH]));
-    const int sx = t.v[T_LDX] + (int)(((2LL * wx + 1) * t.v[T_LNW]) / (2LL * t.v[T_NW]));
-    at = (long)t.v[T_SRC] * 4 * HW + (long)sy * p.W + sx;
+    at = radar_pick((long)t.v[T_SRC] * 4 * HW, wx, wy, t.v[T_NW], t.v[T_NH], t.v[T_LNW], t.v[T_LNH], t.v[T_LDX], t.v[T_LDY], p.W);
   }
 #pragma unroll
   for (int c = 0; c < 4; ++c) p.out[(b * 4 + c) * HW + r] = inside ? p.radar[at + c * HW] : 0.f;
 }
 
 bool mos_shape_ok(int S, int B, int ihm, int iwm, int H, int W) {
-  return S > 0 && S < (1 << 20) && B > 0 && B < 65536 && ihm > 0 && iwm > 0 && H > 0 && W > 0 && H < (1 << 24) && W < (1 << 24) &&
-         (long)S * ihm * iwm < (1L << 31) && (long)B * H * W < (1L << 31);
+  return S > 0 && S < (1 << 20) && fm_shape_ok(B, ihm, iwm, H, W) && (long)S * ihm * iwm < (1L << 31) &&
+         (long)B * H * W < (1L << 31);
 }
-
-long mos_tables_bytes(int B, int H, int W, int cap) { return lb_align(2L * B * lb_ragged_slot_ints(H, W, cap) * (long)sizeof(int)); }
 
 }  // namespace
 
+// two table sets and two horizontal results per output image
 extern "C" long vrnet_mosaic_workspace_bytes(int B, int ihm, int iwm, int H, int W, int max_taps) {
   (void)iwm;
-  return mos_tables_bytes(B, H, W, max_taps) + lb_align(2L * B * ihm * W * 3);
+  return fm_workspace_bytes(2L * B, ihm, H, W, max_taps);
 }
 
 extern "C" int vrnet_mosaic_frames_u8(const unsigned char* img, int S, const vrnet_mosaic_rec* mosaic, int B, int ihm, int iwm,
@@ -487,18 +446,11 @@ extern "C" int vrnet_mosaic_frames_u8(const unsigned char* img, int S, const vrn
   VR_CHECK_ARG((reinterpret_cast<uintptr_t>(mosaic) & 7) == 0, "mosaic_frames: the record table must be 8-byte aligned");
   VR_CHECK_ARG(2L * B * ihm * W < (1L << 31) && 2L * B * lb_ragged_slot_ints(H, W, max_taps) < (1L << 31),
                "mosaic_frames: batch too large");
-  const long tables = mos_tables_bytes(B, H, W, max_taps);
-  const long need = vrnet_mosaic_workspace_bytes(B, ihm, iwm, H, W, max_taps);
-  if (!workspace || workspace_bytes < need) {
-    vr_set_error("mosaic_frames: workspace %ld < %ld bytes", workspace ? workspace_bytes : 0L, need);
-    return VR_ERR_WORKSPACE;
-  }
   MosFramesArgs p{};
+  if (!fm_split_workspace("mosaic_frames", workspace, workspace_bytes, 2L * B, ihm, H, W, max_taps, p.tables, p.mid)) return VR_ERR_WORKSPACE;
   p.img = img; p.tab = mosaic;
   p.S = S; p.B = B; p.ihm = ihm; p.iwm = iwm; p.H = H; p.W = W; p.cap = max_taps;
   p.slot = lb_ragged_slot_ints(H, W, max_taps);
-  p.tables = static_cast<int*>(workspace);
-  p.mid = static_cast<unsigned char*>(workspace) + tables;
   p.canvas = canvas; p.images = images; p.flag = flag;
   hipStream_t st = vr_stream(stream);
   hipLaunchKernelGGL(mosaic_tables_kernel, dim3((unsigned)vr_cdiv(2L * (W + H), 256), B), dim3(256), 0, st, p);

@@ -54,6 +54,24 @@ __device__ __forceinline__ unsigned char clip8(int acc) {
   return (unsigned char)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
 }
 
+// ImagingResampleHorizontal_8bpc / Vertical_8bpc for the three channels of one output pixel: tap t reads src[t * step + c]
+// with weight k[t * kstride]; v receives the rounded, clipped bytes.  step is 3 along a row, -3 along a mirrored row, a
+// row's bytes down a column; Step is the caller's own index type (int or long), so its address arithmetic stays as it was
+template <typename Step>
+__device__ __forceinline__ void resample_taps3(const unsigned char* src, Step step, const int* k, int kstride, int n,
+                                               unsigned char* v) {
+  int a0 = 1 << (LB_PRECISION_BITS - 1), a1 = a0, a2 = a0;
+  for (int t = 0; t < n; ++t) {
+    const int w = k[(long)t * kstride];
+    a0 += w * src[t * step];
+    a1 += w * src[t * step + 1];
+    a2 += w * src[t * step + 2];
+  }
+  v[0] = clip8(a0);
+  v[1] = clip8(a1);
+  v[2] = clip8(a2);
+}
+
 // batch_formats_kernel's arithmetic: ((v / 255) - mean) / std in double, rounded once; pixel r of image b's CHW planes
 __device__ __forceinline__ void normalise_store(float* images, long b, long HW, long r, const unsigned char* v) {
   const double mean[3] = {0.485, 0.456, 0.406}, sd[3] = {0.229, 0.224, 0.225};

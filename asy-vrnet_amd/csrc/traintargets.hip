@@ -15,14 +15,13 @@
 //                the canvas: data.adjust_boxes (int64 product, IEEE double division, + offset, truncation toward zero; clip;
 //                rows thinner than 2 px dropped) and data.boxes_xyxy_to_cxcywh.  One workgroup per image; the kept rows are
 //                compacted in input order by a ballot prefix count; rows behind the count are zeroed.
-#include "common.h"
+// The row block, the one-hot store, the coordinate map, the clip and keep test and the compaction are augment.h's: the
+// augmentation and the Mosaic apply the same rules under their own records.
+#include "augment.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int ST_ROWS = 16;                       // canvas rows of one workgroup
-constexpr long ST_LDS_MAX = 64 * 1024;
 
 struct SegTargetsArgs {
   const unsigned char* label;        // (B, ihm, iwm)
@@ -33,8 +32,6 @@ struct SegTargetsArgs {
   float* onehot;                     // (B, H, W, ns + 1)
   int* flag;                         // or null
 };
-
-__host__ __device__ inline long st_lds_bytes(int H, int W) { return ((long)W + H) * (long)sizeof(int) + (long)ST_ROWS * W; }
 
 __global__ __launch_bounds__(256) void seg_targets_ragged_kernel(const SegTargetsArgs p) {
   extern __shared__ int st_lds[];
@@ -70,28 +67,7 @@ __global__ __launch_bounds__(256) void seg_targets_ragged_kernel(const SegTarget
     png[i] = lab;
   }
   __syncthreads();
-  float* oh = p.onehot + ((long)b * p.H + y0) * p.W * n1;
-  const int total = npix * n1;
-  if (p.vec4) {
-    for (int q = threadIdx.x; q < total / 4; q += 256) {
-      int px = (q * 4) / n1, c = q * 4 - px * n1, lab = cls[px];
-      f32x4 v;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[j] = c == lab ? 1.f : 0.f;
-        if (++c == n1 && j < 3) {
-          c = 0;
-          lab = cls[++px];
-        }
-      }
-      *reinterpret_cast<f32x4*>(oh + q * 4) = v;
-    }
-  } else {
-    for (int f = threadIdx.x; f < total; f += 256) {
-      const int px = f / n1;
-      oh[f] = f - px * n1 == cls[px] ? 1.f : 0.f;
-    }
-  }
+  st_store_onehot(cls, p.onehot + ((long)b * p.H + y0) * p.W * n1, npix, n1, p.vec4);
 }
 
 struct BoxTargetsArgs {
@@ -104,18 +80,9 @@ struct BoxTargetsArgs {
   int* flag;                         // or null
 };
 
-// out[:, k] * n / i + d assigned back into the integer array (dataloader.py:170-171): numpy multiplies in int64, divides
-// in double (true_divide), adds the offset in double and truncates toward zero on the store
-__device__ __forceinline__ long long map_coord(int v, int n, int i, int d) {
-  double t = (double)((long long)v * (long long)n);
-  t /= (double)i;
-  t += (double)d;
-  return (long long)t;
-}
-
 __global__ __launch_bounds__(256) void box_targets_ragged_kernel(const BoxTargetsArgs p) {
   __shared__ int s_wave[4];
-  const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y;
   bool bad;
   const vrnet_frame_geom g = vr_geom_load(p.tab, b, p.ihm, p.iwm, p.H, p.W, bad);
   const bool empty = g.ih <= 0 || g.iw <= 0 || g.nw <= 0 || g.nh <= 0;
@@ -140,31 +107,13 @@ __global__ __launch_bounds__(256) void box_targets_ragged_kernel(const BoxTarget
       x2 = map_coord(r[2], g.nw, g.iw, g.dx);
       y2 = map_coord(r[3], g.nh, g.ih, g.dy);
       c = r[4];
-      if (x1 < 0) x1 = 0;
-      if (y1 < 0) y1 = 0;
-      if (x2 > p.W) x2 = p.W;
-      if (y2 > p.H) y2 = p.H;
-      keep = x2 - x1 > 1 && y2 - y1 > 1;
+      keep = box_clip_keep(x1, y1, x2, y2, p.W, p.H);
     }
-    const unsigned long long mask = __ballot(keep);
-    if (lane == 0) s_wave[wave] = __popcll(mask);
-    __syncthreads();
-    int at = base;
-    for (int w = 0; w < wave; ++w) at += s_wave[w];
-    at += __popcll(mask & ((1ull << lane) - 1ull));
-    base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    if (keep) {                      // at <= i < max_gt: compaction never moves a row up
-      const double w = (double)(x2 - x1), h = (double)(y2 - y1);
-      float* o = out + (long)at * 5;
-      o[0] = (float)((double)x1 + w / 2);
-      o[1] = (float)((double)y1 + h / 2);
-      o[2] = (float)w;
-      o[3] = (float)h;
-      o[4] = (float)c;
-    }
+    const int at = box_compact_slot(keep, base, s_wave);
+    if (keep) box_store_cxcywh(out + (long)at * 5, x1, y1, x2, y2, c);      // at <= i < max_gt: compaction never moves a row up
     __syncthreads();                 // s_wave is rewritten by the next chunk
   }
-  for (int i = base * 5 + threadIdx.x; i < p.max_gt * 5; i += 256) out[i] = 0.f;
+  box_zero_tail(base, p.max_gt, out);
   if (threadIdx.x == 0) p.counts_out[b] = base;
 }
 

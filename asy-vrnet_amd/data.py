@@ -389,6 +389,53 @@ def pack_boxes(boxes, max_gt):
     return out, counts
 
 
+def _device_batch_ragged(fn, frames, sizes, input_shape, labels, boxes, radar, num_classes_seg, max_gt, capacity, max_taps, flag,
+                         device, default_taps, table, ops, per="a batch of {}"):
+    """What `device_train_batch_ragged`, `device_augment_batch_ragged` and `device_mosaic_batch_ragged` share; fn is the
+    caller's name in the messages.  default_taps(capacity, input_shape): its tap capacity; table(sizes, input_shape, capacity,
+    max_taps): its validated table as the bytes the device takes, one record per output image; ops: its hip functions for
+    the frames, the segmentation targets, the boxes and the radar maps (None: no radar, and none is returned)."""
+    frames_op, seg_op, box_op, radar_op = ops
+    items, own = ragged_items(frames, sizes, None, (3,), "frames", fn)
+    n = len(own)
+    if labels is None:
+        raise RuntimeError(f"{fn}: the label maps are required")
+    labs = ragged_items(labels, own, n, (), "label maps", fn)[0]
+    if len(boxes) != n:
+        raise RuntimeError(f"{fn}: {len(boxes)} box lists for {per.format(n)}")
+    if capacity is None:
+        capacity = tuple(items.shape[1:3]) if torch.is_tensor(items) else (int(own[:, 0].max()), int(own[:, 1].max()))
+    ihm, iwm = (int(v) for v in capacity)
+    for t in (items, labs):
+        if torch.is_tensor(t) and (t.shape[1] > ihm or t.shape[2] > iwm):
+            raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {(ihm, iwm)}")
+    H, W = (int(v) for v in input_shape)
+    ns = int(num_classes_seg)
+    max_taps = default_taps((ihm, iwm), (H, W)) if max_taps is None else int(max_taps)
+    tab = table(own, (H, W), (ihm, iwm), max_taps)
+    if radar_op is not None:
+        rad = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
+        if tuple(rad.shape) != (n, 4, H, W) or rad.dtype != torch.float32:
+            raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(n, 4, H, W)}, got {rad.dtype} {tuple(rad.shape)}")
+    packed, counts = pack_boxes(boxes, max_gt)
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        tab = tab.to(dev, non_blocking=True)
+        img = torch.zeros((n, ihm, iwm, 3), dtype=torch.uint8, device=dev)
+        fill_slots(img, items, own)
+        lab = torch.zeros((n, ihm, iwm), dtype=torch.uint8, device=dev)
+        fill_slots(lab, labs, own)
+        images = torch.empty((len(tab), 3, H, W), dtype=torch.float32, device=dev)
+        frames_op(img, tab, H, W, max_taps, images=images, flag=flag)
+        png, onehot = seg_op(lab, tab, H, W, ns, flag=flag)
+        targets, counts_out = box_op(packed.to(dev, non_blocking=True), counts.to(dev, non_blocking=True), tab, (ihm, iwm), H, W,
+                                     flag=flag)
+        out = (images, png, onehot, targets, counts_out)
+        if radar_op is not None:
+            out += (radar_op(rad.to(dev, non_blocking=True).contiguous(), tab, (ihm, iwm), flag=flag),)
+    return out
+
+
 def device_train_batch_ragged(frames, sizes, input_shape, labels, boxes, num_classes_seg, max_gt=64, letterbox_image=True,
                               capacity=None, max_taps=None, flag=None, device="cuda"):
     """The dataset item of the reference's training path (`random=False`: `letterbox_sample`, `boxes_xyxy_to_cxcywh`,
@@ -400,37 +447,10 @@ def device_train_batch_ragged(frames, sizes, input_shape, labels, boxes, num_cla
     int32): what `losses.training_loss_packed` reads, bit for bit what the host functions give per image."""
     from . import hip
     fn = "device_train_batch_ragged"
-    items, own = ragged_items(frames, sizes, None, (3,), "frames", fn)
-    B = len(own)
-    if labels is None:
-        raise RuntimeError(f"{fn}: the label maps are required")
-    labs = ragged_items(labels, own, B, (), "label maps", fn)[0]
-    if len(boxes) != B:
-        raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
-    if capacity is None:
-        capacity = tuple(items.shape[1:3]) if torch.is_tensor(items) else (int(own[:, 0].max()), int(own[:, 1].max()))
-    ihm, iwm = (int(v) for v in capacity)
-    for t in (items, labs):
-        if torch.is_tensor(t) and (t.shape[1] > ihm or t.shape[2] > iwm):
-            raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {(ihm, iwm)}")
-    H, W = (int(v) for v in input_shape)
-    ns = int(num_classes_seg)
-    max_taps = default_max_taps((ihm, iwm), (H, W)) if max_taps is None else int(max_taps)
-    tab = frame_geometry(own, (H, W), letterbox_image, (ihm, iwm), max_taps, fn)
-    packed, counts = pack_boxes(boxes, max_gt)
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        geom = geometry_bytes(tab).to(dev, non_blocking=True)
-        img = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
-        fill_slots(img, items, own)
-        lab = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
-        fill_slots(lab, labs, own)
-        images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        hip.letterbox_ragged(img, None, geom, H, W, max_taps, images=images, flag=flag)
-        png, onehot = hip.seg_targets_ragged(lab, geom, H, W, ns, flag=flag)
-        targets, counts_out = hip.box_targets_ragged(packed.to(dev, non_blocking=True), counts.to(dev, non_blocking=True), geom,
-                                                     (ihm, iwm), H, W, flag=flag)
-    return images, png, onehot, targets, counts_out
+    return _device_batch_ragged(
+        fn, frames, sizes, input_shape, labels, boxes, None, num_classes_seg, max_gt, capacity, max_taps, flag, device, default_max_taps,
+        lambda own, shape, cap, taps: geometry_bytes(frame_geometry(own, shape, letterbox_image, cap, taps, fn)),
+        (lambda img, *a, **k: hip.letterbox_ragged(img, None, *a, **k), hip.seg_targets_ragged, hip.box_targets_ragged, None))
 
 
 # ---- the random training augmentation (utils/dataloader.py:187-247, utils_seg/dataloader.py:79-111), host side ----------
@@ -687,41 +707,10 @@ def device_augment_batch_ragged(frames, sizes, input_shape, labels, boxes, radar
     give per image."""
     from . import hip
     fn = "device_augment_batch_ragged"
-    items, own = ragged_items(frames, sizes, None, (3,), "frames", fn)
-    B = len(own)
-    if labels is None:
-        raise RuntimeError(f"{fn}: the label maps are required")
-    labs = ragged_items(labels, own, B, (), "label maps", fn)[0]
-    if len(boxes) != B:
-        raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
-    if capacity is None:
-        capacity = tuple(items.shape[1:3]) if torch.is_tensor(items) else (int(own[:, 0].max()), int(own[:, 1].max()))
-    ihm, iwm = (int(v) for v in capacity)
-    for t in (items, labs):
-        if torch.is_tensor(t) and (t.shape[1] > ihm or t.shape[2] > iwm):
-            raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {(ihm, iwm)}")
-    H, W = (int(v) for v in input_shape)
-    ns = int(num_classes_seg)
-    max_taps = default_aug_max_taps((ihm, iwm), (H, W)) if max_taps is None else int(max_taps)
-    tab = check_aug_params(params, own, (H, W), (ihm, iwm), max_taps, fn)
-    rad = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
-    if tuple(rad.shape) != (B, 4, H, W) or rad.dtype != torch.float32:
-        raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(B, 4, H, W)}, got {rad.dtype} {tuple(rad.shape)}")
-    packed, counts = pack_boxes(boxes, max_gt)
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        aug = augment_bytes(tab).to(dev, non_blocking=True)
-        img = torch.zeros((B, ihm, iwm, 3), dtype=torch.uint8, device=dev)
-        fill_slots(img, items, own)
-        lab = torch.zeros((B, ihm, iwm), dtype=torch.uint8, device=dev)
-        fill_slots(lab, labs, own)
-        images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        hip.augment_frames(img, aug, H, W, max_taps, images=images, flag=flag)
-        png, onehot = hip.augment_seg_targets(lab, aug, H, W, ns, flag=flag)
-        targets, counts_out = hip.augment_box_targets(packed.to(dev, non_blocking=True), counts.to(dev, non_blocking=True), aug,
-                                                      (ihm, iwm), H, W, flag=flag)
-        radar_out = hip.augment_radar(rad.to(dev, non_blocking=True).contiguous(), aug, (ihm, iwm), flag=flag)
-    return images, png, onehot, targets, counts_out, radar_out
+    return _device_batch_ragged(
+        fn, frames, sizes, input_shape, labels, boxes, radar, num_classes_seg, max_gt, capacity, max_taps, flag, device,
+        default_aug_max_taps, lambda own, shape, cap, taps: augment_bytes(check_aug_params(params, own, shape, cap, taps, fn)),
+        (hip.augment_frames, hip.augment_seg_targets, hip.augment_box_targets, hip.augment_radar))
 
 
 def check_aug_params(params, sizes, input_shape, capacity, max_taps, fn):
@@ -1007,41 +996,11 @@ def device_mosaic_batch_ragged(frames, sizes, input_shape, labels, boxes, radar,
     first max_gt stay and flag receives hip.FLAG_BOX_COUNT."""
     from . import hip
     fn = "device_mosaic_batch_ragged"
-    items, own = ragged_items(frames, sizes, None, (3,), "frames", fn)
-    S = len(own)
-    if labels is None:
-        raise RuntimeError(f"{fn}: the label maps are required")
-    labs = ragged_items(labels, own, S, (), "label maps", fn)[0]
-    if len(boxes) != S:
-        raise RuntimeError(f"{fn}: {len(boxes)} box lists for {S} sources")
-    if capacity is None:
-        capacity = tuple(items.shape[1:3]) if torch.is_tensor(items) else (int(own[:, 0].max()), int(own[:, 1].max()))
-    ihm, iwm = (int(v) for v in capacity)
-    for t in (items, labs):
-        if torch.is_tensor(t) and (t.shape[1] > ihm or t.shape[2] > iwm):
-            raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {(ihm, iwm)}")
-    H, W = (int(v) for v in input_shape)
-    ns = int(num_classes_seg)
-    max_taps = default_mosaic_max_taps((ihm, iwm), (H, W), prob=0.0) if max_taps is None else int(max_taps)
-    tab = check_mosaic_table(params, (H, W), own, (ihm, iwm), max_taps, fn)
-    rad = radar if torch.is_tensor(radar) else torch.from_numpy(np.ascontiguousarray(radar))
-    if tuple(rad.shape) != (S, 4, H, W) or rad.dtype != torch.float32:
-        raise RuntimeError(f"{fn}: radar must be torch.float32 of shape {(S, 4, H, W)}, got {rad.dtype} {tuple(rad.shape)}")
-    packed, counts = pack_boxes(boxes, max_gt)
-    dev = torch.device(device)
-    with torch.cuda.device(dev):
-        mos = mosaic_bytes(tab).to(dev, non_blocking=True)
-        img = torch.zeros((S, ihm, iwm, 3), dtype=torch.uint8, device=dev)
-        fill_slots(img, items, own)
-        lab = torch.zeros((S, ihm, iwm), dtype=torch.uint8, device=dev)
-        fill_slots(lab, labs, own)
-        images = torch.empty((len(tab), 3, H, W), dtype=torch.float32, device=dev)
-        hip.mosaic_frames(img, mos, H, W, max_taps, images=images, flag=flag)
-        png, onehot = hip.mosaic_seg_targets(lab, mos, H, W, ns, flag=flag)
-        targets, counts_out = hip.mosaic_box_targets(packed.to(dev, non_blocking=True), counts.to(dev, non_blocking=True), mos,
-                                                     (ihm, iwm), H, W, flag=flag)
-        radar_out = hip.mosaic_radar(rad.to(dev, non_blocking=True).contiguous(), mos, (ihm, iwm), flag=flag)
-    return images, png, onehot, targets, counts_out, radar_out
+    return _device_batch_ragged(
+        fn, frames, sizes, input_shape, labels, boxes, radar, num_classes_seg, max_gt, capacity, max_taps, flag, device,
+        lambda cap, shape: default_mosaic_max_taps(cap, shape, prob=0.0),
+        lambda own, shape, cap, taps: mosaic_bytes(check_mosaic_table(params, shape, own, cap, taps, fn)),
+        (hip.mosaic_frames, hip.mosaic_seg_targets, hip.mosaic_box_targets, hip.mosaic_radar), per="{} sources")
 
 
 class FrameDataset(torch.utils.data.Dataset):

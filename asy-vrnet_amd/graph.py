@@ -168,6 +168,126 @@ class GraphedStep:
         return self.loss
 
 
+class _PlainFrames:
+    """The frame mode of `TrainStep(from_frames=True)`: what the prologue does to the raw frames.  This one is the plain
+    letterbox; `_AugmentFrames` and `_MosaicFrames` answer the same questions for the augmentation and for Mosaic.
+    TrainStep picks one in its constructor and asks it wherever the three differ, so it branches nowhere itself; a
+    further mode is a further subclass and one more line where the constructor picks."""
+    per_image = 1                            # source slots per output image
+    table_attr, keeps_table = "geom", False  # the step's device table; keeps_table: drawn per call, aug_table keeps the host copy
+    ops = ("letterbox_ragged", "seg_targets_ragged", "box_targets_ragged", None)   # hip's frames, seg, boxes and radar calls
+    workspace = "letterbox_ragged_workspace_bytes"
+    to_bytes = staticmethod(data.geometry_bytes)
+
+    def default_max_taps(self, step):
+        return data.default_max_taps(step.capacity, step.hw)
+
+    def warmup_table(self, step):
+        """The table of the warm-up and the capture: frames that fill their slots."""
+        return data.frame_geometry([step.capacity] * step.batch, step.hw, step.letterbox_image, step.capacity, step.max_taps, "TrainStep")
+
+    def check(self, step, aug, own):
+        """The table of a call from the caller's aug and the frames' own sizes, checked; None: `finish` draws it."""
+        if aug is not None:
+            raise RuntimeError("TrainStep: an aug table belongs to a step built with augment")
+        return data.frame_geometry(own, step.hw, step.letterbox_image, step.capacity, step.max_taps, "TrainStep")
+
+    def finish(self, step, own, table, counts):
+        """The last host check of a call, after everything else has passed: what needs the box counts, then the draw from
+        the step's generator where `check` left the table open.  A call that raises for another reason draws nothing."""
+        return table
+
+    def radar_dst(self, step):
+        """Where a call's radar maps are copied to."""
+        return step.r
+
+    def frames(self, step, table, **kw):
+        hip.letterbox_ragged(step.frames_u8, None, table, *step.hw, step.max_taps, **kw)
+
+    def launch(self, step):
+        """The prologue's launches: frames, segmentation targets, boxes, radar maps."""
+        (h, w), table = step.hw, getattr(step, self.table_attr)
+        self.frames(step, table, images=step.x, flag=step.flag, ws=step._lb_ws)
+        getattr(hip, self.ops[1])(step.frame_labels_u8, table, h, w, step.ns, png_out=step.png, onehot=step.onehot, flag=step.flag)
+        getattr(hip, self.ops[2])(step.boxes, step.box_counts, table, step.capacity, h, w, targets=step.labels, counts_out=step.counts,
+                                  flag=step.flag)
+        if self.ops[3] and step.radar_points is None:        # radar points: vrnet_radar_map_f32 writes step.r instead
+            getattr(hip, self.ops[3])(step.radar_in, table, step.capacity, out=step.r, flag=step.flag)
+
+
+class _AugmentFrames(_PlainFrames):
+    """The single-image training augmentation: one `data.AUG_DTYPE` record per image, drawn per call."""
+    table_attr, keeps_table = "aug", True
+    ops = ("augment_frames", "augment_seg_targets", "augment_box_targets", "augment_radar")
+    to_bytes = staticmethod(data.augment_bytes)
+
+    def default_max_taps(self, step):
+        kw = {k: step.augment[k] for k in ("jitter", "scale") if k in step.augment}
+        return data.default_aug_max_taps(step.capacity, step.hw, **kw)
+
+    def warmup_table(self, step):
+        """... under the letterbox window of such a frame."""
+        (ihm, iwm), (h, w) = step.capacity, step.hw
+        rec = data.aug_record(step.capacity, step.hw, *data.letterbox_geometry(iwm, ihm, w, h))
+        return data.check_aug_table(np.stack([rec] * step.batch), step.hw, step.capacity, step.max_taps, "TrainStep")
+
+    def check(self, step, aug, own):
+        return None if aug is None else data.check_aug_params(aug, own, step.hw, step.capacity, step.max_taps, "TrainStep")
+
+    def finish(self, step, own, table, counts):
+        if table is None:
+            # a draw that fails its own checks (an empty window, a sliver's taps) has advanced the generator: the next call
+            # draws anew
+            table = data.augment_params(own, step.hw, step._aug_rng, capacity=step.capacity, max_taps=step.max_taps, fn="TrainStep",
+                                        **step.augment)
+        return table
+
+    def radar_dst(self, step):
+        return step.radar_in
+
+    def frames(self, step, table, **kw):
+        getattr(hip, self.ops[0])(step.frames_u8, table, *step.hw, step.max_taps, **kw)
+
+
+class _MosaicFrames(_AugmentFrames):
+    """Mosaic: one `data.MOSAIC_DTYPE` record per output image over four source slots each, drawn per call."""
+    per_image = 4
+    ops = ("mosaic_frames", "mosaic_seg_targets", "mosaic_box_targets", "mosaic_radar")
+    workspace = "mosaic_workspace_bytes"
+    to_bytes = staticmethod(data.mosaic_bytes)
+
+    def default_max_taps(self, step):
+        # mosaic_prob may change from call to call: the capacity serves the Mosaic draw and the plain one
+        kw = {k: step.mosaic[k] for k in ("jitter", "scale") if k in step.mosaic}
+        return data.default_mosaic_max_taps(step.capacity, step.hw, prob=0.0, plain=step.augment, **kw)
+
+    def warmup_table(self, step):
+        (ihm, iwm), (h, w) = step.capacity, step.hw
+        lb = data.letterbox_geometry(iwm, ihm, w, h)
+        recs = [data.mosaic_record(step.hw, (w, h), [(4 * b, step.capacity) + lb, None, None, None]) for b in range(step.batch)]
+        return data.check_mosaic_table(np.stack(recs), step.hw, [step.capacity] * step.sources, step.capacity, step.max_taps, "TrainStep")
+
+    def check(self, step, aug, own):
+        if aug is None:
+            return None
+        if len(np.asarray(aug)) != step.batch:
+            raise RuntimeError(f"TrainStep: the Mosaic table is a ({step.batch},) array of data.MOSAIC_DTYPE records")
+        return data.check_mosaic_table(aug, step.hw, own, step.capacity, step.max_taps, "TrainStep")
+
+    def finish(self, step, own, table, counts):
+        # conservative: the sources of an output image TOGETHER bring at most max_gt boxes, whatever the cut would drop
+        # (the kernel would keep the first max_gt of more and report FLAG_BOX_COUNT); a drawn table uses sources 4 b .. 4 b + 3
+        for b in range(step.batch):
+            srcs = range(4 * b, 4 * b + 4) if table is None else [int(s) for s in table[b]["tile"]["src"] if s >= 0]
+            total = sum(int(counts[s]) for s in srcs)
+            if total > step.max_gt:
+                raise RuntimeError(f"TrainStep: image {b}: its sources bring {total} boxes together, above max_gt = {step.max_gt}")
+        if table is None:
+            table = data.mosaic_params(own, step.hw, step._aug_rng, step.batch, prob=float(step.mosaic_prob), plain=step.augment,
+                                       capacity=step.capacity, max_taps=step.max_taps, fn="TrainStep", **step.mosaic)
+        return table
+
+
 class TrainStep(GraphedStep):
     """One captured training step: forward, the reference's loss (`losses.training_loss`: SimOTA YOLO loss, focal or CE,
     dice, det + 5 seg; utils_fit.py:96-106), backward, optimizer step and EMA update, replayed without a host sync.
@@ -312,7 +432,8 @@ class TrainStep(GraphedStep):
         self.mosaic = None if mosaic is None or mosaic is False else ({} if mosaic is True else dict(mosaic))
         if self.mosaic is not None:
             self.mosaic_prob = float(self.mosaic.pop("prob", 1.0))      # read at every call: the caller may assign it
-        self.sources = int(batch) * (4 if self.mosaic is not None else 1)
+        self.mode = _MosaicFrames() if self.mosaic is not None else _AugmentFrames() if self.augment is not None else _PlainFrames()
+        self.sources = int(batch) * self.mode.per_image
         self.names = ("total", "loss_det", "loss_seg") + (("f_score",) if self.f_score else ())
         with torch.cuda.device(dev):
             self.labels = torch.zeros((batch, max(self.max_gt, 1), 5), dtype=torch.float32, device=dev)
@@ -341,71 +462,30 @@ class TrainStep(GraphedStep):
         (h, w), B = self.hw, batch
         self.capacity = ihm, iwm = tuple(int(v) for v in capacity)
         self.letterbox_image = bool(letterbox_image)
-        S = self.sources
-        if self.mosaic is not None:
-            # mosaic_prob may change from call to call: the capacity serves the Mosaic draw and the plain one
-            kw = {k: self.mosaic[k] for k in ("jitter", "scale") if k in self.mosaic}
-            self.max_taps = data.default_mosaic_max_taps(self.capacity, self.hw, prob=0.0, plain=self.augment, **kw) \
-                if max_taps is None else int(max_taps)
+        S, mode = self.sources, self.mode
+        self.max_taps = mode.default_max_taps(self) if max_taps is None else int(max_taps)
+        table = mode.warmup_table(self)
+        if mode.keeps_table:
             self._aug_rng = np.random.RandomState(aug_seed)
-            lb = data.letterbox_geometry(iwm, ihm, w, h)
-            recs = [data.mosaic_record(self.hw, (w, h), [(4 * b, self.capacity) + lb, None, None, None]) for b in range(B)]
-            self.aug_table = data.check_mosaic_table(np.stack(recs), self.hw, [self.capacity] * S, self.capacity, self.max_taps,
-                                                     "TrainStep")
-            self.aug = data.mosaic_bytes(self.aug_table).to(dev)
-            self.radar_in = torch.zeros((S, 4, h, w), dtype=torch.float32, device=dev)
-        elif self.augment is None:
-            self.max_taps = data.default_max_taps(self.capacity, self.hw) if max_taps is None else int(max_taps)
-            table = data.frame_geometry([self.capacity] * B, self.hw, self.letterbox_image, self.capacity, self.max_taps, "TrainStep")
-            self.geom = data.geometry_bytes(table).to(dev)
-        else:
-            kw = {k: self.augment[k] for k in ("jitter", "scale") if k in self.augment}
-            self.max_taps = data.default_aug_max_taps(self.capacity, self.hw, **kw) if max_taps is None else int(max_taps)
-            self._aug_rng = np.random.RandomState(aug_seed)
-            rec = data.aug_record(self.capacity, self.hw, *data.letterbox_geometry(iwm, ihm, w, h))
-            self.aug_table = data.check_aug_table(np.stack([rec] * B), self.hw, self.capacity, self.max_taps, "TrainStep")
-            self.aug = data.augment_bytes(self.aug_table).to(dev)
-            if self.radar_points is None:
-                self.radar_in = torch.zeros((B, 4, h, w), dtype=torch.float32, device=dev)
+            self.aug_table = table
+        setattr(self, mode.table_attr, mode.to_bytes(table).to(dev))
         if self.radar_points is not None:    # no points in the warm-up and the capture
-            self.points, self.views = self.radar_points.buffers(table if self.augment is None else self.aug_table, dev)
+            self.points, self.views = self.radar_points.buffers(table, dev)
             self._radar_ws = self.radar_points.workspace(self.hw, dev)
+        elif mode.ops[3]:                    # the prologue moves the radar maps: a call copies them here (mode.radar_dst)
+            self.radar_in = torch.zeros((S, 4, h, w), dtype=torch.float32, device=dev)
         self.frames_u8 = torch.zeros((S, ihm, iwm, 3), dtype=torch.uint8, device=dev)
         self.frame_labels_u8 = torch.zeros((S, ihm, iwm), dtype=torch.uint8, device=dev)
         self.boxes = torch.zeros((S, max(self.max_gt, 1), 5), dtype=torch.int32, device=dev)
         self.box_counts = torch.zeros(S, dtype=torch.int32, device=dev)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        ws_bytes = hip.mosaic_workspace_bytes if self.mosaic is not None else hip.letterbox_ragged_workspace_bytes
-        self._lb_ws = torch.empty(ws_bytes(B, ihm, iwm, h, w, self.max_taps), dtype=torch.uint8, device=dev)
+        self._lb_ws = torch.empty(getattr(hip, mode.workspace)(B, ihm, iwm, h, w, self.max_taps), dtype=torch.uint8, device=dev)
 
     def _prologue(self):
         if self.from_bytes:
             hip.batch_formats(self.images_u8, self.labels_u8, self.ns, images=self.x, png_out=self.png, onehot=self.onehot)
-        elif self.from_frames and self.mosaic is not None:
-            h, w = self.hw
-            hip.mosaic_frames(self.frames_u8, self.aug, h, w, self.max_taps, images=self.x, flag=self.flag, ws=self._lb_ws)
-            hip.mosaic_seg_targets(self.frame_labels_u8, self.aug, h, w, self.ns, png_out=self.png, onehot=self.onehot,
-                                   flag=self.flag)
-            hip.mosaic_box_targets(self.boxes, self.box_counts, self.aug, self.capacity, h, w, targets=self.labels,
-                                   counts_out=self.counts, flag=self.flag)
-            hip.mosaic_radar(self.radar_in, self.aug, self.capacity, out=self.r, flag=self.flag)
-        elif self.from_frames and self.augment is not None:
-            h, w = self.hw
-            hip.augment_frames(self.frames_u8, self.aug, h, w, self.max_taps, images=self.x, flag=self.flag, ws=self._lb_ws)
-            hip.augment_seg_targets(self.frame_labels_u8, self.aug, h, w, self.ns, png_out=self.png, onehot=self.onehot,
-                                    flag=self.flag)
-            hip.augment_box_targets(self.boxes, self.box_counts, self.aug, self.capacity, h, w, targets=self.labels,
-                                    counts_out=self.counts, flag=self.flag)
-            if self.radar_points is None:
-                hip.augment_radar(self.radar_in, self.aug, self.capacity, out=self.r, flag=self.flag)
         elif self.from_frames:
-            h, w = self.hw
-            hip.letterbox_ragged(self.frames_u8, None, self.geom, h, w, self.max_taps, images=self.x, flag=self.flag,
-                                 ws=self._lb_ws)
-            hip.seg_targets_ragged(self.frame_labels_u8, self.geom, h, w, self.ns, png_out=self.png, onehot=self.onehot,
-                                   flag=self.flag)
-            hip.box_targets_ragged(self.boxes, self.box_counts, self.geom, self.capacity, h, w, targets=self.labels,
-                                   counts_out=self.counts, flag=self.flag)
+            self.mode.launch(self)
         if self.radar_points is not None:    # the points of each image under the window (and flip) its frame just went through
             h, w = self.hw
             hip.radar_map(self.points, self.views, h, w, self.radar_points.radius, float(self.radar_points.min_depth), self.r,
@@ -490,20 +570,7 @@ class TrainStep(GraphedStep):
         for t in (items, labs):
             if torch.is_tensor(t) and (t.shape[1] > self.capacity[0] or t.shape[2] > self.capacity[1]):
                 raise RuntimeError(f"{fn}: the padded buffer {tuple(t.shape[1:3])} is above the capacity {self.capacity}")
-        if self.mosaic is not None:
-            table = None
-            if aug is not None:
-                if len(np.asarray(aug)) != self.batch:
-                    raise RuntimeError(f"{fn}: the Mosaic table is a ({self.batch},) array of data.MOSAIC_DTYPE records")
-                table = data.check_mosaic_table(aug, self.hw, own, self.capacity, self.max_taps, fn)
-        elif self.augment is None:
-            if aug is not None:
-                raise RuntimeError(f"{fn}: an aug table belongs to a step built with augment")
-            table = data.frame_geometry(own, self.hw, self.letterbox_image, self.capacity, self.max_taps, fn)
-        elif aug is not None:
-            table = data.check_aug_params(aug, own, self.hw, self.capacity, self.max_taps, fn)
-        else:
-            table = None                     # drawn last, below: a call that raises for another reason draws nothing
+        table = self.mode.check(self, aug, own)          # None: drawn last, below: a call that raises for another reason draws nothing
         if calib is not None and self.radar_points is None:
             raise RuntimeError(f"{fn}: calib belongs to a step built with radar_points")
         if self.radar_points is None:
@@ -515,22 +582,7 @@ class TrainStep(GraphedStep):
         if len(boxes) != B:
             raise RuntimeError(f"{fn}: {len(boxes)} box lists for a batch of {B}")
         packed, counts = data.pack_boxes(boxes, self.max_gt)              # raises, naming the image
-        if self.mosaic is not None:
-            # conservative: the sources of an output image TOGETHER bring at most max_gt boxes, whatever the cut would drop
-            # (the kernel would keep the first max_gt of more and report FLAG_BOX_COUNT); a drawn table uses sources 4 b .. 4 b + 3
-            for b in range(self.batch):
-                srcs = range(4 * b, 4 * b + 4) if table is None else [int(s) for s in table[b]["tile"]["src"] if s >= 0]
-                total = sum(int(counts[s]) for s in srcs)
-                if total > self.max_gt:
-                    raise RuntimeError(f"{fn}: image {b}: its sources bring {total} boxes together, above max_gt = {self.max_gt}")
-            if table is None:
-                table = data.mosaic_params(own, self.hw, self._aug_rng, self.batch, prob=float(self.mosaic_prob), plain=self.augment,
-                                           capacity=self.capacity, max_taps=self.max_taps, fn=fn, **self.mosaic)
-        if table is None:
-            # a draw that fails its own checks (an empty window, a sliver's taps) has advanced the generator: the next call
-            # draws anew
-            table = data.augment_params(own, self.hw, self._aug_rng, capacity=self.capacity, max_taps=self.max_taps, fn=fn,
-                                        **self.augment)
+        table = self.mode.finish(self, own, table, counts)
         if self.radar_points is not None:
             radar = radar[0], self.radar_points.views(table, radar[1])
         return items, labs, own, table, radar, packed, counts
@@ -560,14 +612,9 @@ class TrainStep(GraphedStep):
                 data.fill_slots(self.frames_u8, items, own)
                 data.fill_slots(self.frame_labels_u8, labs, own)
                 # fresh pinned staging tensors (`pack_boxes` makes its own), as for the step record below
-                if self.mosaic is not None:
+                if self.mode.keeps_table:
                     self.aug_table = table
-                    self.aug.copy_(data.mosaic_bytes(table).pin_memory(), non_blocking=True)
-                elif self.augment is None:
-                    self.geom.copy_(data.geometry_bytes(table).pin_memory(), non_blocking=True)
-                else:
-                    self.aug_table = table
-                    self.aug.copy_(data.augment_bytes(table).pin_memory(), non_blocking=True)
+                getattr(self, self.mode.table_attr).copy_(self.mode.to_bytes(table).pin_memory(), non_blocking=True)
                 self.boxes.copy_(packed, non_blocking=True)
                 self.box_counts.copy_(counts, non_blocking=True)
             elif self.from_bytes:
@@ -584,7 +631,7 @@ class TrainStep(GraphedStep):
                 self.points.copy_(radar[0], non_blocking=True)
                 self.views.copy_(radar[1].pin_memory(), non_blocking=True)
             else:
-                (self.r if self.augment is None and self.mosaic is None else self.radar_in).copy_(radar, non_blocking=True)
+                self.mode.radar_dst(self).copy_(radar, non_blocking=True)
             if not self.from_frames:
                 self.labels.copy_(packed, non_blocking=True)
                 self.counts.copy_(counts, non_blocking=True)

@@ -1298,12 +1298,39 @@ FLAG_GEOMETRY = 256      # VR_FLAG_GEOMETRY of csrc/common.h
 FLAG_BOX_COUNT = 512     # VR_FLAG_BOX_COUNT of csrc/common.h: box_targets_ragged clamped a count outside [0, max_gt]
 
 
+AUG_BYTES = 816          # sizeof(vrnet_aug_rec)
+MOSAIC_BYTES = 976       # sizeof(vrnet_mosaic_rec)
+
+
+class _TableKind:
+    """One kind of per-image device table: `what` it is called in messages, its record bytes, the wrapper names it gives
+    ("{}_ragged", "augment_{}", "mosaic_{}" -- the C entry points are vrnet_<name>_<type>), the workspace function of its
+    frames call, and `sources`: the table has one record per OUTPUT image over S source slots, so the batch size comes from
+    the table and the C calls take S in front of it (Mosaic).  Otherwise there is one record per input."""
+
+    def __init__(self, what, nbytes, name, workspace, sources=False):
+        self.what, self.nbytes, self.name, self.workspace, self.sources = what, nbytes, name, workspace, sources
+        self.n = "S" if sources else "B"                  # the inputs' leading dimension, in messages
+
+
+_GEOM = _TableKind("geometry", GEOM_BYTES, "{}_ragged", "vrnet_letterbox_ragged_workspace")
+_AUG = _TableKind("augmentation", AUG_BYTES, "augment_{}", "vrnet_letterbox_ragged_workspace")
+_MOSAIC = _TableKind("Mosaic", MOSAIC_BYTES, "mosaic_{}", "vrnet_mosaic_workspace_bytes", sources=True)
+
+
+def _table(kind, t, n_in, fn):
+    """The table: a contiguous uint8 GPU tensor (B, kind.nbytes), 8-byte aligned (`data.frame_geometry`, `data.augment_bytes`
+    and `data.mosaic_bytes` pack them); B is n_in, the inputs' count, unless the kind has sources.  Returns the leading
+    arguments of the C call after the inputs: (table, B), or (S, table, B)."""
+    if t is None or t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != kind.nbytes or not (kind.sources or t.shape[0] == n_in) or \
+            not t.is_contiguous() or not t.is_cuda or t.data_ptr() % 8:
+        raise RuntimeError(f"{fn}: the {kind.what} table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape "
+                           f"({'B' if kind.sources else n_in}, {kind.nbytes})")
+    return (n_in, ptr(t), t.shape[0]) if kind.sources else (ptr(t), n_in)
+
+
 def _geom(geom, B, fn):
-    """The table: a contiguous uint8 GPU tensor (B, GEOM_BYTES), 8-byte aligned (`data.frame_geometry` packs it)."""
-    if geom is None or geom.dtype != torch.uint8 or tuple(geom.shape) != (B, GEOM_BYTES) or not geom.is_contiguous() or \
-            not geom.is_cuda or geom.data_ptr() % 8:
-        raise RuntimeError(f"{fn}: the geometry table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape ({B}, {GEOM_BYTES})")
-    return ptr(geom)
+    return _table(_GEOM, geom, B, fn)[0]
 
 
 def letterbox_ragged_workspace_bytes(B, ihm, iwm, H, W, max_taps):
@@ -1380,24 +1407,79 @@ def render_ragged(frames, class_map, geom, out, palette=None, mix_type=0, alpha=
                                        ptr(counts), ptr(flag), stream()), "render_ragged")
 
 
+# ---- the frame modes of training: the plain letterbox, the augmentation and the Mosaic run the same four operations ----
+# under their own table kind; one body per operation, and the public wrappers below are one call each
+def _seg_targets(kind, label_u8, tab, H, W, num_classes_seg, png_out, onehot, flag):
+    fn = kind.name.format("seg_targets")
+    if label_u8 is None or label_u8.dim() != 3:
+        raise RuntimeError(f"{fn}: expected label maps ({kind.n}, ihm, iwm)")
+    n, ihm, iwm = label_u8.shape
+    H, W, ns = int(H), int(W), int(num_classes_seg)
+    B = _table(kind, tab, n, fn)[-1] if kind.sources else n
+    if png_out is None:
+        png_out = torch.empty((B, H, W), dtype=torch.int64, device=label_u8.device)
+    if onehot is None:
+        onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=label_u8.device)
+    _tensors(fn, ((label_u8, (n, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
+                  (onehot, (B, H, W, ns + 1), torch.float32), (flag, (1,), torch.int32)))
+    _check(getattr(_lib, f"vrnet_{fn}_u8")(ptr(label_u8), *_table(kind, tab, n, fn), ihm, iwm, H, W, ns, ptr(png_out), ptr(onehot), ptr(flag), stream()), fn)
+    return png_out, onehot
+
+
+def _box_targets(kind, boxes, counts, tab, capacity, H, W, targets, counts_out, flag):
+    fn = kind.name.format("box_targets")
+    if boxes is None or boxes.dim() != 3:
+        raise RuntimeError(f"{fn}: expected boxes ({kind.n}, max_gt, 5)")
+    n, max_gt = boxes.shape[:2]
+    B = _table(kind, tab, n, fn)[-1] if kind.sources else n
+    if targets is None:
+        targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
+    if counts_out is None:
+        counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
+    _tensors(fn, ((boxes, (n, max_gt, 5), torch.int32), (counts, (n,), torch.int32), (targets, (B, max_gt, 5), torch.float32),
+                  (counts_out, (B,), torch.int32), (flag, (1,), torch.int32)))
+    _check(getattr(_lib, f"vrnet_{fn}_f32")(ptr(boxes), ptr(counts), *_table(kind, tab, n, fn), max_gt, int(capacity[0]), int(capacity[1]), int(H), int(W),
+                                            ptr(targets), ptr(counts_out), ptr(flag), stream()), fn)
+    return targets, counts_out
+
+
+def _frames(kind, img_u8, tab, H, W, max_taps, canvas, images, flag, ws):
+    fn = kind.name.format("frames")
+    if img_u8 is None or img_u8.dim() != 4:
+        raise RuntimeError(f"{fn}: expected frames ({kind.n}, ihm, iwm, 3)")
+    n, ihm, iwm = img_u8.shape[:3]
+    H, W = int(H), int(W)
+    B = _table(kind, tab, n, fn)[-1] if kind.sources else n
+    _tensors(fn, ((img_u8, (n, ihm, iwm, 3), torch.uint8), (canvas, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
+                  (flag, (1,), torch.int32)))
+    need = getattr(_lib, kind.workspace)(B, ihm, iwm, H, W, int(max_taps))
+    if ws is None:
+        ws = _ws.get(need, img_u8.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"{fn}: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    _check(getattr(_lib, f"vrnet_{fn}_u8")(ptr(img_u8), *_table(kind, tab, n, fn), ihm, iwm, H, W, int(max_taps), ptr(canvas), ptr(images), ptr(flag),
+                                           ptr(ws), ws.numel(), stream()), fn)
+
+
+def _radar(kind, radar, tab, capacity, out, flag):
+    fn = kind.name.format("radar")
+    if radar is None or radar.dim() != 4 or radar.shape[1] != 4:
+        raise RuntimeError(f"{fn}: expected radar maps ({kind.n}, 4, H, W)")
+    n, _, H, W = radar.shape
+    B = _table(kind, tab, n, fn)[-1] if kind.sources else n
+    if out is None:
+        out = torch.empty((B, 4, H, W), dtype=torch.float32, device=radar.device)
+    _tensors(fn, ((radar, (n, 4, H, W), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
+    _check(getattr(_lib, f"vrnet_{fn}_f32")(ptr(radar), *_table(kind, tab, n, fn), int(capacity[0]), int(capacity[1]), H, W, ptr(out), ptr(flag), stream()), fn)
+    return out
+
+
 def seg_targets_ragged(label_u8, geom, H, W, num_classes_seg, png_out=None, onehot=None, flag=None):
     """Raw label maps of their own sizes -> the segmentation targets of the letterboxed batch (vrnet_seg_targets_ragged_u8):
     label_u8 (B,ihm,iwm) padded slots, geom the (B, GEOM_BYTES) table -> png_out (B,H,W) int64 (Pillow's NEAREST pick in the
     window, 0 outside, labels >= ns clamped to ns) and onehot (B,H,W,ns+1) f32, as `batch_formats` writes them; flag (1)
     int32 or None.  Returns (png_out, onehot)."""
-    if label_u8 is None or label_u8.dim() != 3:
-        raise RuntimeError("seg_targets_ragged: expected label maps (B, ihm, iwm)")
-    B, ihm, iwm = label_u8.shape
-    H, W, ns = int(H), int(W), int(num_classes_seg)
-    if png_out is None:
-        png_out = torch.empty((B, H, W), dtype=torch.int64, device=label_u8.device)
-    if onehot is None:
-        onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=label_u8.device)
-    _tensors("seg_targets_ragged", ((label_u8, (B, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
-                                         (onehot, (B, H, W, ns + 1), torch.float32), (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_seg_targets_ragged_u8(ptr(label_u8), _geom(geom, B, "seg_targets_ragged"), B, ihm, iwm, H, W, ns,
-                                            ptr(png_out), ptr(onehot), ptr(flag), stream()), "seg_targets_ragged")
-    return png_out, onehot
+    return _seg_targets(_GEOM, label_u8, geom, H, W, num_classes_seg, png_out, onehot, flag)
 
 
 def box_targets_ragged(boxes, counts, geom, capacity, H, W, targets=None, counts_out=None, flag=None):
@@ -1406,20 +1488,7 @@ def box_targets_ragged(boxes, counts, geom, capacity, H, W, targets=None, counts
     (ihm, iwm) -> targets (B,max_gt,5) f32 rows [cx, cy, w, h, cls] and counts_out (B) int32, what `data.adjust_boxes` and
     `data.boxes_xyxy_to_cxcywh` give per image, kept rows in input order, the rows behind them 0.  flag (1) int32 or None:
     receives FLAG_BOX_COUNT for a count outside [0, max_gt] (clamped).  Returns (targets, counts_out)."""
-    if boxes is None or boxes.dim() != 3:
-        raise RuntimeError("box_targets_ragged: expected boxes (B, max_gt, 5)")
-    B, max_gt = boxes.shape[:2]
-    if targets is None:
-        targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
-    if counts_out is None:
-        counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
-    _tensors("box_targets_ragged", ((boxes, (B, max_gt, 5), torch.int32), (counts, (B,), torch.int32),
-                                         (targets, (B, max_gt, 5), torch.float32), (counts_out, (B,), torch.int32),
-                                         (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_box_targets_ragged_f32(ptr(boxes), ptr(counts), _geom(geom, B, "box_targets_ragged"), B, max_gt,
-                                             int(capacity[0]), int(capacity[1]), int(H), int(W), ptr(targets), ptr(counts_out),
-                                             ptr(flag), stream()), "box_targets_ragged")
-    return targets, counts_out
+    return _box_targets(_GEOM, boxes, counts, geom, capacity, H, W, targets, counts_out, flag)
 
 
 def heatmap_ragged_workspace_bytes(B, H, W):
@@ -1442,102 +1511,34 @@ def heatmap_ragged(levels, geom, H, W, mask, minmax, ws, window=1, frames=None, 
 
 
 # ---- training augmentation (include/vrnet_hip.h "training augmentation"): per-image records from a device table ----------
-AUG_BYTES = 816          # sizeof(vrnet_aug_rec)
-
-
-def _aug(aug, B, fn):
-    """The table: a contiguous uint8 GPU tensor (B, AUG_BYTES), 8-byte aligned (`data.augment_params` packs it)."""
-    if aug is None or aug.dtype != torch.uint8 or tuple(aug.shape) != (B, AUG_BYTES) or not aug.is_contiguous() or \
-            not aug.is_cuda or aug.data_ptr() % 8:
-        raise RuntimeError(f"{fn}: the augmentation table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape ({B}, {AUG_BYTES})")
-    return ptr(aug)
-
-
 def augment_frames(img_u8, aug, H, W, max_taps, canvas=None, images=None, flag=None, ws=None):
     """Raw frames of their own sizes -> the augmented canvas (vrnet_augment_frames_u8): img_u8 (B,ihm,iwm,3) padded slots, aug
     the (B, AUG_BYTES) table -> canvas (B,H,W,3) uint8 and / or images (B,3,H,W) f32, what `data.augment_sample` and
     `device_batch` give per image; max_taps: the tap capacity of a table entry; flag (1) int32 or None; ws:
     letterbox_ragged_workspace_bytes(B, ihm, iwm, H, W, max_taps) bytes."""
-    if img_u8 is None or img_u8.dim() != 4:
-        raise RuntimeError("augment_frames: expected frames (B, ihm, iwm, 3)")
-    B, ihm, iwm = img_u8.shape[:3]
-    H, W = int(H), int(W)
-    _tensors("augment_frames", ((img_u8, (B, ihm, iwm, 3), torch.uint8), (canvas, (B, H, W, 3), torch.uint8),
-                                (images, (B, 3, H, W), torch.float32), (flag, (1,), torch.int32)))
-    need = _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, int(max_taps))
-    if ws is None:
-        ws = _ws.get(need, img_u8.device)
-    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise RuntimeError(f"augment_frames: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
-    _check(_lib.vrnet_augment_frames_u8(ptr(img_u8), _aug(aug, B, "augment_frames"), B, ihm, iwm, H, W, int(max_taps), ptr(canvas),
-                                        ptr(images), ptr(flag), ptr(ws), ws.numel(), stream()), "augment_frames")
+    _frames(_AUG, img_u8, aug, H, W, max_taps, canvas, images, flag, ws)
 
 
 def augment_seg_targets(label_u8, aug, H, W, num_classes_seg, png_out=None, onehot=None, flag=None):
     """`seg_targets_ragged` under the augmentation records (vrnet_augment_seg_targets_u8): label_u8 (B,ihm,iwm) padded slots
     -> png_out (B,H,W) int64 and onehot (B,H,W,ns+1) f32 of the augmented label canvas.  Returns (png_out, onehot)."""
-    if label_u8 is None or label_u8.dim() != 3:
-        raise RuntimeError("augment_seg_targets: expected label maps (B, ihm, iwm)")
-    B, ihm, iwm = label_u8.shape
-    H, W, ns = int(H), int(W), int(num_classes_seg)
-    if png_out is None:
-        png_out = torch.empty((B, H, W), dtype=torch.int64, device=label_u8.device)
-    if onehot is None:
-        onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=label_u8.device)
-    _tensors("augment_seg_targets", ((label_u8, (B, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
-                                     (onehot, (B, H, W, ns + 1), torch.float32), (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_augment_seg_targets_u8(ptr(label_u8), _aug(aug, B, "augment_seg_targets"), B, ihm, iwm, H, W, ns,
-                                             ptr(png_out), ptr(onehot), ptr(flag), stream()), "augment_seg_targets")
-    return png_out, onehot
+    return _seg_targets(_AUG, label_u8, aug, H, W, num_classes_seg, png_out, onehot, flag)
 
 
 def augment_box_targets(boxes, counts, aug, capacity, H, W, targets=None, counts_out=None, flag=None):
     """`box_targets_ragged` under the augmentation records (vrnet_augment_box_targets_f32): what `data.augment_boxes` and
     `data.boxes_xyxy_to_cxcywh` give per image.  Returns (targets, counts_out)."""
-    if boxes is None or boxes.dim() != 3:
-        raise RuntimeError("augment_box_targets: expected boxes (B, max_gt, 5)")
-    B, max_gt = boxes.shape[:2]
-    if targets is None:
-        targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
-    if counts_out is None:
-        counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
-    _tensors("augment_box_targets", ((boxes, (B, max_gt, 5), torch.int32), (counts, (B,), torch.int32),
-                                     (targets, (B, max_gt, 5), torch.float32), (counts_out, (B,), torch.int32),
-                                     (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_augment_box_targets_f32(ptr(boxes), ptr(counts), _aug(aug, B, "augment_box_targets"), B, max_gt,
-                                              int(capacity[0]), int(capacity[1]), int(H), int(W), ptr(targets), ptr(counts_out),
-                                              ptr(flag), stream()), "augment_box_targets")
-    return targets, counts_out
+    return _box_targets(_AUG, boxes, counts, aug, capacity, H, W, targets, counts_out, flag)
 
 
 def augment_radar(radar, aug, capacity, out=None, flag=None):
     """The radar maps under the augmentation records (vrnet_augment_radar_f32): radar (B,4,H,W) f32, aligned with the
     letterbox window of its frame -> out (B,4,H,W) f32, the integer gather of `data.augment_radar`; out is not radar;
     capacity = (ihm, iwm) of the frames' slots, by which the records are judged."""
-    if radar is None or radar.dim() != 4 or radar.shape[1] != 4:
-        raise RuntimeError("augment_radar: expected radar maps (B, 4, H, W)")
-    B, _, H, W = radar.shape
-    if out is None:
-        out = torch.empty((B, 4, H, W), dtype=torch.float32, device=radar.device)
-    _tensors("augment_radar", ((radar, (B, 4, H, W), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_augment_radar_f32(ptr(radar), _aug(aug, B, "augment_radar"), B, int(capacity[0]), int(capacity[1]), H, W,
-                                        ptr(out), ptr(flag), stream()), "augment_radar")
-    return out
+    return _radar(_AUG, radar, aug, capacity, out, flag)
 
 
 # ---- Mosaic (include/vrnet_hip.h "Mosaic on the device"): one record per OUTPUT image, S source slots --------------------------
-MOSAIC_BYTES = 976       # sizeof(vrnet_mosaic_rec)
-
-
-def _mosaic(mosaic, fn):
-    """The table: a contiguous uint8 GPU tensor (B, MOSAIC_BYTES), 8-byte aligned (`data.mosaic_bytes` packs it); returns
-    (pointer, B)."""
-    if mosaic is None or mosaic.dtype != torch.uint8 or mosaic.dim() != 2 or mosaic.shape[1] != MOSAIC_BYTES or \
-            not mosaic.is_contiguous() or not mosaic.is_cuda or mosaic.data_ptr() % 8:
-        raise RuntimeError(f"{fn}: the Mosaic table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape (B, {MOSAIC_BYTES})")
-    return ptr(mosaic), mosaic.shape[0]
-
-
 def mosaic_workspace_bytes(B, ihm, iwm, H, W, max_taps):
     return _lib.vrnet_mosaic_workspace_bytes(B, ihm, iwm, H, W, max_taps)
 
@@ -1548,75 +1549,27 @@ def mosaic_frames(img_u8, mosaic, H, W, max_taps, canvas=None, images=None, flag
     `device_batch` give per output image; max_taps: the tap capacity of a table entry; flag (1) int32 or None; ws:
     mosaic_workspace_bytes(B, ihm, iwm, H, W, max_taps) bytes.  No host validation: `data.check_mosaic_table` is the
     caller's."""
-    if img_u8 is None or img_u8.dim() != 4:
-        raise RuntimeError("mosaic_frames: expected frames (S, ihm, iwm, 3)")
-    S, ihm, iwm = img_u8.shape[:3]
-    H, W = int(H), int(W)
-    tab, B = _mosaic(mosaic, "mosaic_frames")
-    _tensors("mosaic_frames", ((img_u8, (S, ihm, iwm, 3), torch.uint8), (canvas, (B, H, W, 3), torch.uint8),
-                               (images, (B, 3, H, W), torch.float32), (flag, (1,), torch.int32)))
-    need = _lib.vrnet_mosaic_workspace_bytes(B, ihm, iwm, H, W, int(max_taps))
-    if ws is None:
-        ws = _ws.get(need, img_u8.device)
-    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise RuntimeError(f"mosaic_frames: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
-    _check(_lib.vrnet_mosaic_frames_u8(ptr(img_u8), S, tab, B, ihm, iwm, H, W, int(max_taps), ptr(canvas), ptr(images), ptr(flag),
-                                       ptr(ws), ws.numel(), stream()), "mosaic_frames")
+    _frames(_MOSAIC, img_u8, mosaic, H, W, max_taps, canvas, images, flag, ws)
 
 
 def mosaic_seg_targets(label_u8, mosaic, H, W, num_classes_seg, png_out=None, onehot=None, flag=None):
     """`augment_seg_targets` under Mosaic records (vrnet_mosaic_seg_targets_u8): label_u8 (S,ihm,iwm) padded slots -> png_out
     (B,H,W) int64 and onehot (B,H,W,ns+1) f32 of the Mosaic label canvas.  Returns (png_out, onehot)."""
-    if label_u8 is None or label_u8.dim() != 3:
-        raise RuntimeError("mosaic_seg_targets: expected label maps (S, ihm, iwm)")
-    S, ihm, iwm = label_u8.shape
-    H, W, ns = int(H), int(W), int(num_classes_seg)
-    tab, B = _mosaic(mosaic, "mosaic_seg_targets")
-    if png_out is None:
-        png_out = torch.empty((B, H, W), dtype=torch.int64, device=label_u8.device)
-    if onehot is None:
-        onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=label_u8.device)
-    _tensors("mosaic_seg_targets", ((label_u8, (S, ihm, iwm), torch.uint8), (png_out, (B, H, W), torch.int64),
-                                    (onehot, (B, H, W, ns + 1), torch.float32), (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_mosaic_seg_targets_u8(ptr(label_u8), S, tab, B, ihm, iwm, H, W, ns, ptr(png_out), ptr(onehot), ptr(flag),
-                                            stream()), "mosaic_seg_targets")
-    return png_out, onehot
+    return _seg_targets(_MOSAIC, label_u8, mosaic, H, W, num_classes_seg, png_out, onehot, flag)
 
 
 def mosaic_box_targets(boxes, counts, mosaic, capacity, H, W, targets=None, counts_out=None, flag=None):
     """The boxes of S sources -> the packed targets of B Mosaic images (vrnet_mosaic_box_targets_f32): what
     `data.mosaic_boxes` and `data.boxes_xyxy_to_cxcywh` give per output image, in tile-then-row order; of more than max_gt
     kept rows the first max_gt stay and flag receives FLAG_BOX_COUNT.  Returns (targets, counts_out)."""
-    if boxes is None or boxes.dim() != 3:
-        raise RuntimeError("mosaic_box_targets: expected boxes (S, max_gt, 5)")
-    S, max_gt = boxes.shape[:2]
-    tab, B = _mosaic(mosaic, "mosaic_box_targets")
-    if targets is None:
-        targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
-    if counts_out is None:
-        counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
-    _tensors("mosaic_box_targets", ((boxes, (S, max_gt, 5), torch.int32), (counts, (S,), torch.int32),
-                                    (targets, (B, max_gt, 5), torch.float32), (counts_out, (B,), torch.int32),
-                                    (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_mosaic_box_targets_f32(ptr(boxes), ptr(counts), S, tab, B, max_gt, int(capacity[0]), int(capacity[1]), int(H),
-                                             int(W), ptr(targets), ptr(counts_out), ptr(flag), stream()), "mosaic_box_targets")
-    return targets, counts_out
+    return _box_targets(_MOSAIC, boxes, counts, mosaic, capacity, H, W, targets, counts_out, flag)
 
 
 def mosaic_radar(radar, mosaic, capacity, out=None, flag=None):
     """The radar maps of S sources under Mosaic records (vrnet_mosaic_radar_f32): radar (S,4,H,W) f32, each aligned with the
     letterbox window of its source -> out (B,4,H,W) f32, the integer gather of `data.mosaic_sample`; out is not radar;
     capacity = (ihm, iwm) of the frames' slots, by which the records are judged."""
-    if radar is None or radar.dim() != 4 or radar.shape[1] != 4:
-        raise RuntimeError("mosaic_radar: expected radar maps (S, 4, H, W)")
-    S, _, H, W = radar.shape
-    tab, B = _mosaic(mosaic, "mosaic_radar")
-    if out is None:
-        out = torch.empty((B, 4, H, W), dtype=torch.float32, device=radar.device)
-    _tensors("mosaic_radar", ((radar, (S, 4, H, W), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_mosaic_radar_f32(ptr(radar), S, tab, B, int(capacity[0]), int(capacity[1]), H, W, ptr(out), ptr(flag),
-                                       stream()), "mosaic_radar")
-    return out
+    return _radar(_MOSAIC, radar, mosaic, capacity, out, flag)
 
 
 # ---- the radar map from 4D radar points (include/vrnet_hip.h "the radar map from 4D radar points") -------------------------
