@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
@@ -79,6 +80,19 @@ typedef struct vrnet_frame_geom {
 #define VR_FLAG_GEOMETRY 256                    /* a record that had to be clamped; bits 1..128: render / nms / evalacc */
 #define VR_FLAG_BOX_COUNT 512                   /* traintargets.hip: a box count outside [0, max_gt], clamped */
 #define VR_FLAG_POINT_COUNT 1024                /* radarmap.hip: a point count outside [0, max_points], clamped */
+/* 2048: LB_FLAG_SCORE of labels.hip, which shares the pipeline's flag word */
+#define VR_FLAG_CROP_ARENA 4096                 /* crops.hip: a crop that did not fit into the arena, dropped */
+extern "C" {
+/* include/vrnet_hip.h: one record per draw row of vrnet_crop_boxes_u8. */
+typedef struct vrnet_crop_rec {
+  int offset;                                   /* the crop's first pixel in the arena; 0 if empty, -1 if dropped */
+  int w, h;                                     /* 0, 0: an empty crop */
+  int image;                                    /* the image the row belongs to; -1 behind the last row */
+} vrnet_crop_rec;
+}
+static_assert(sizeof(vrnet_crop_rec) == 16 && offsetof(vrnet_crop_rec, offset) == 0 && offsetof(vrnet_crop_rec, w) == 4 &&
+                  offsetof(vrnet_crop_rec, h) == 8 && offsetof(vrnet_crop_rec, image) == 12,
+              "vrnet_crop_rec is four int32: render.CROP_RECORD mirrors it");
 
 __device__ __forceinline__ int vr_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

@@ -171,11 +171,13 @@ class EvalPipeline(infer.FramePipeline):
     `add` takes frames and label maps as lists of arrays (or padded buffers with sizes).  labels_u8 is filled with 255
     outside each image, which the confusion matrix skips, so only an image's own pixels are counted.
 
-    radar_points / radar_radius / radar_min_depth / calib: as `infer.FramePipeline`; `add` then takes radar points."""
+    radar_points / radar_radius / radar_min_depth / calib: as `infer.FramePipeline`; `add` then takes radar points.
+    crops: forwarded to `infer.FramePipeline` (the crops of the last batch are `self.result.crops`); nothing here reads them."""
 
     def __init__(self, model, frame_shape, input_shape, class_names, num_seg_classes, batch=1, capacity=None, max_boxes=100,
                  max_gt=64, conf_thres=0.05, nms_thres=0.5, letterbox_image=True, max_candidates=1024, normalise_radar=False,
-                 graph=True, ragged=False, max_taps=None, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None):
+                 graph=True, ragged=False, max_taps=None, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None,
+                 crops=None):
         infer.validate_config(model, frame_shape, input_shape, batch, max_candidates)
         self.class_names, self.num_seg_classes, self.capacity, self.max_boxes, self.max_gt = validate_eval_config(
             class_names, num_seg_classes, batch, capacity, max_boxes, max_gt, conf_thres)
@@ -197,7 +199,7 @@ class EvalPipeline(infer.FramePipeline):
         super().__init__(model, frame_shape, input_shape, batch=batch, conf_thres=conf_thres, nms_thres=nms_thres,
                          letterbox_image=letterbox_image, max_candidates=max_candidates, normalise_radar=normalise_radar,
                          render=False, graph=graph, ragged=ragged, max_taps=max_taps, radar_points=radar_points,
-                         radar_radius=radar_radius, radar_min_depth=radar_min_depth, calib=calib)
+                         radar_radius=radar_radius, radar_min_depth=radar_min_depth, calib=calib, crops=crops)
 
     def _tail(self, result):
         from . import hip, metrics

@@ -163,6 +163,7 @@ _SIGS = {
     "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
     "vrnet_render_labels_u8": ([P, I, I, I, P, P, I, P, I, I, P, P, L, P, I, I, I, P, P], I),
     "vrnet_render_labels_ragged_u8": ([P, P, P, I, I, I, P, P, I, P, I, P, P, L, P, I, I, P, P], I),
+    "vrnet_crop_boxes_u8": ([P, I, I, I, P, P, P, I, P, L, P, P, P, P], I),
     "vrnet_heatmap_workspace": ([I, I, I], L),
     "vrnet_heatmap_f32": ([P, P, P] + [I] * 11 + [P, P, F, P, P, P, P, L, P], I),
     "vrnet_heatmap_ragged_workspace": ([I, I, I], L),
@@ -1680,3 +1681,30 @@ def render_labels_ragged(picture, geom, size_index, boxes, box_offsets, box_pale
     _check(_lib.vrnet_render_labels_ragged_u8(ptr(picture), _geom(geom, B, fn), ptr(size_index), B, ih, iw, ptr(boxes),
                                               ptr(box_offsets), n_rows, ptr(box_palette), box_palette.shape[0], ptr(label_idx),
                                               ptr(blob), blob.shape[0], ptr(records), nc, n_sizes, ptr(flag), stream()), fn)
+
+
+# ---- detection crops (csrc/crops.hip) ----------------------------------------------------------------------------------------
+FLAG_CROP_ARENA = 4096   # VR_FLAG_CROP_ARENA of csrc/common.h: a crop that did not fit into the arena, dropped
+CROP_RECORD = 4          # int32 per vrnet_crop_rec: offset, w, h, image
+
+
+def crop_boxes(frames, rows, offsets, arena, table, summary, geom=None, flag=None):
+    """The crops of yolo.py:180-193 into one packed arena (vrnet_crop_boxes_u8): frames (B, ihm, iwm, 3) uint8, rows (n_cap, 5)
+    / offsets (B + 1) int32 as `detect_finish[_ragged]` leave them -> arena (3 * capacity) uint8, table (n_cap, 4) int32 records
+    offset, w, h, image and summary (2) int32 = (rows, pixels in use), by the rule of `render.crop_layout`; geom: the
+    (B, GEOM_BYTES) table of a ragged batch, None: every image fills its slot; flag (1) int32 or None: FLAG_CROP_ARENA for a
+    dropped crop, FLAG_GEOMETRY for a clamped record.  Two launches."""
+    fn = "crop_boxes"
+    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError(f"{fn}: expected contiguous uint8 frames of shape (B, ihm, iwm, 3)")
+    B, ihm, iwm = frames.shape[:3]
+    if rows is None or rows.dim() != 2 or rows.shape[0] < 1 or offsets is None or arena is None or table is None or summary is None:
+        raise RuntimeError(f"{fn}: rows (n_cap >= 1, 5), offsets, arena, table and summary are required")
+    n_cap = rows.shape[0]
+    if arena.dim() != 1 or arena.shape[0] < 3 or arena.shape[0] % 3:
+        raise RuntimeError(f"{fn}: the arena must be a 1-D uint8 tensor of 3 * capacity bytes, got shape {tuple(arena.shape)}")
+    _tensors(fn, ((frames, (B, ihm, iwm, 3), torch.uint8), (rows, (n_cap, 5), torch.int32), (offsets, (B + 1,), torch.int32),
+                  (arena, (arena.shape[0],), torch.uint8), (table, (n_cap, CROP_RECORD), torch.int32),
+                  (summary, (2,), torch.int32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_crop_boxes_u8(ptr(frames), B, ihm, iwm, None if geom is None else _geom(geom, B, fn), ptr(rows), ptr(offsets),
+                                    n_cap, ptr(arena), arena.shape[0] // 3, ptr(table), ptr(summary), ptr(flag), stream()), fn)

@@ -14,7 +14,8 @@ Bits of `FrameResult.flag` (an int32 word, zeroed by every run; read it when you
 FLAG_BOX_COLOUR, FLAG_BOX_ROWS (see render.render_frame), FLAG_CANDIDATES -- an image had more candidates than the
 capacity, so only its `cap` best-scored ones were considered -- and FLAG_DET_CLASS -- a kept row with a class id
 outside [0, num_classes), which is not counted -- and, in a ragged pipeline, FLAG_GEOMETRY -- a record of the geometry
-table had to be clamped by a kernel, which the host checks of `run` rule out.
+table had to be clamped by a kernel, which the host checks of `run` rule out.  A pipeline built with crops= adds
+hip.crop_boxes behind hip.detect_finish and FLAG_CROP_ARENA, a crop that did not fit into the arena.
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
@@ -31,6 +32,7 @@ FLAG_CANDIDATES, FLAG_DET_CLASS = 8, 16          # NMS_FLAG_* of csrc/nms.hip, a
 FLAG_GEOMETRY = 256                              # VR_FLAG_GEOMETRY of csrc/common.h, above evaluate.FLAG_EVAL_*
 FLAG_POINT_COUNT = 1024                          # VR_FLAG_POINT_COUNT of csrc/common.h (a pipeline built with radar_points)
 FLAG_LABEL_SCORE = rendering.FLAG_LABEL_SCORE    # 2048, csrc/labels.hip (a pipeline built with labels): a score outside [0, 1]
+FLAG_CROP_ARENA = rendering.FLAG_CROP_ARENA      # 4096, csrc/crops.hip (a pipeline built with crops): a crop that did not fit
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -149,6 +151,18 @@ def validate_ragged_inputs(frames, radar, sizes, batch, capacity, input_shape, l
     return items, validate_radar(radar, batch, input_shape), own, table
 
 
+def crop_capacity(crops, batch, frame_shape):
+    """The pixels of a pipeline's crop arena from its crops= keyword: None (no crops), True (2 * batch * ihm * iwm, at most
+    2^30) or the number itself, 1..2^30."""
+    if crops is None or crops is False:
+        return None
+    if crops is True:
+        return min(2 * int(batch) * int(frame_shape[0]) * int(frame_shape[1]), 1 << 30)
+    if not isinstance(crops, (int, np.integer)) or not 1 <= int(crops) <= 1 << 30:
+        raise RuntimeError(f"FramePipeline: crops is None, True or the capacity of the crop arena, 1..2^30 pixels, got {crops!r}")
+    return int(crops)
+
+
 def unmap_scalars(input_shape, image_shape, letterbox_image):
     """(offset, scale): the (y, x) float64 pairs with which decode.yolo_correct_boxes maps a centre, (c - offset) * scale, and a
     size, s * scale -- its own expressions, np.round included; (0, 0), (1, 1) without a letterbox."""
@@ -173,15 +187,17 @@ class FrameResult:
     fixed-size pipeline).
     From a pipeline with heatmap=True (None otherwise): heat_mask (B, ih, iw) uint8, heat_picture (B, ih, iw, 3) uint8 and
     heat_range (B, 2) int32 = each mask's (min, max), what `render.heatmap` returns for the frames and the raw detection
-    maps of the run; padded like class_map / rendered from a ragged pipeline."""
+    maps of the run; padded like class_map / rendered from a ragged pipeline.
+    From a pipeline built with crops (None otherwise): crops, the `render.Crops` of the run -- every kept detection cut out
+    of the original frame, `crops.images()[b][i]` being row i of image b."""
     __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
-                 "heat_picture", "heat_range")
+                 "heat_picture", "heat_range", "crops")
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
-                 heat_picture=None, heat_range=None):
+                 heat_picture=None, heat_range=None, crops=None):
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
-        self.heat_mask, self.heat_picture, self.heat_range = heat_mask, heat_picture, heat_range
+        self.heat_mask, self.heat_picture, self.heat_range, self.crops = heat_mask, heat_picture, heat_range, crops
 
     def detections(self):
         """The list `decode.non_max_suppression` returns: per image an (N_b, 7) float32 numpy array in the same order,
@@ -242,15 +258,24 @@ class FramePipeline:
     pipeline builds the one font size `render.label_font_size(ih)` (0, below 17 rows: no labels); a ragged one builds every
     size from 1 to label_font_size(ihm), or the sizes label_sizes= names, and sends the per-image size table up with the
     geometry table; a frame whose size was not built raises in the host validation of `run`, before anything is enqueued.
-    FLAG_LABEL_SCORE joins the bits of `flag`.  labels needs render=True."""
+    FLAG_LABEL_SCORE joins the bits of `flag`.  labels needs render=True.
+
+    crops: None (the default: the chain, the graph and the result as before), True or the capacity of the crop arena in
+    pixels -- the `crop` switch of yolo.py:180-193: every kept detection is cut out of the ORIGINAL frame into a packed arena
+    on the device (`render.crop_boxes`; fixed-size and ragged pipelines alike) and `FrameResult.crops` is its `render.Crops`.
+    The arena, the table and the summary are allocated before the capture; the two launches of hip.crop_boxes sit right
+    behind the detect_finish node.  True means 2 * batch * ihm * iwm pixels: a cap the caller may change, not a measured
+    number -- 6 bytes per frame pixel, about 100 MB at batch 8 and 1080 x 1920.  Crops beyond the arena are dropped, a
+    prefix is kept, and FLAG_CROP_ARENA joins the bits of `flag`."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
-                 font=None, label_sizes=None):
+                 font=None, label_sizes=None, crops=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
+        self.crop_capacity = crop_capacity(crops, self.batch, self.frame_shape)
         self.radar_points = None
         if radar_points is not None:
             if radar_dtype != torch.float32:
@@ -361,6 +386,9 @@ class FramePipeline:
         self._det_counts = torch.empty((B, self.num_classes), dtype=torch.int64, device=dev)
         if self.labels is not None:
             self._label_idx = torch.zeros(B * cap, **i32)
+        self._crops = None
+        if self.crop_capacity is not None:
+            self._crops = rendering.crop_buffers(B * cap, self.crop_capacity, B, self.flag, dev)
 
     def _chain(self):
         """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
@@ -388,15 +416,19 @@ class FramePipeline:
         finished = (self._rows, self._draw_rows, self._offsets, self._det_counts, self.flag)
         if self.ragged:
             hip.detect_finish_ragged(self._kept_rows, self._kept, self.geom, self.num_classes, F, *finished)
-            class_map = decode.seg_predict_ragged(seg, self.geom, F, self.flag)
         else:
             hip.detect_finish(self._kept_rows, self._kept, self.num_classes, F, self.offset, self.scale, *finished)
-            if self.letterbox_image:
-                class_map = decode.seg_predict(seg, (H, W), F)
-            else:                             # the frame was stretched over the whole input: the window is the input
-                class_map = torch.empty((B,) + F, dtype=torch.uint8, device=dev)
-                ws = torch.empty(hip.seg_predict_workspace_bytes(B, seg.shape[1], H, W), dtype=torch.uint8, device=dev)
-                hip.seg_predict(seg.contiguous().float(), 0, 0, H, W, class_map, ws)
+        if self._crops is not None:           # right behind the finish node: from the original frames, which nothing draws on
+            hip.crop_boxes(self.frames_u8, self._draw_rows, self._offsets, self._crops.arena, self._crops.table,
+                           self._crops.summary, geom=self.geom if self.ragged else None, flag=self.flag)
+        if self.ragged:
+            class_map = decode.seg_predict_ragged(seg, self.geom, F, self.flag)
+        elif self.letterbox_image:
+            class_map = decode.seg_predict(seg, (H, W), F)
+        else:                                 # the frame was stretched over the whole input: the window is the input
+            class_map = torch.empty((B,) + F, dtype=torch.uint8, device=dev)
+            ws = torch.empty(hip.seg_predict_workspace_bytes(B, seg.shape[1], H, W), dtype=torch.uint8, device=dev)
+            hip.seg_predict(seg.contiguous().float(), 0, 0, H, W, class_map, ws)
         rendered = seg_counts = None
         if self.render:
             picture = dict(palette=self.seg_palette, mix_type=self.mix_type, alpha=self.alpha, count=True,
@@ -413,7 +445,7 @@ class FramePipeline:
             else:
                 rendered, seg_counts = rendering.render_frame(self.frames_u8, class_map, boxes, thickness=self.thickness,
                                                               device=dev, **picture)
-        result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag)
+        result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops)
         if self.heatmap:
             if self.ragged:
                 heat = rendering.heatmap_ragged(self.frames_u8, det, self.geom, (H, W), window=self.letterbox_image,
@@ -511,7 +543,11 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     final partial batch is filled by repeating the last picture; the repeats are dropped here.  Returns a list of
     (file name, (N, 7) detections) in that order; with dir_save_path the rendered frame of every picture, sliced to its own
     size, is saved there as <stem>.png through Pillow (the reference renames .jpg to .png; here every picture is a PNG), and
-    from a pipeline with heatmap=True its heat picture as <stem>_heat.png beside it.  Two pictures that would share one
+    from a pipeline with heatmap=True its heat picture as <stem>_heat.png beside it.  From a pipeline built with crops every
+    non-empty crop the arena kept is saved as dir_save_path/img_crop/<stem>_crop_<i>.png, i being the row's index within its
+    picture (the `i` of yolo.py:180-193); the crops of the repeated fill pictures are dropped with the repeats.  The reference
+    writes img_crop/crop_<i>.png and so overwrites the crops of one picture with those of the next: the stem in the name is a
+    deliberate departure.  Two pictures that would share one
     output file (names that differ only in their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on): with
     dir_save_path that raises before anything runs."""
     from PIL import Image
@@ -542,6 +578,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         rendered = None if dir_save_path is None or result.rendered is None else result.rendered.cpu().numpy()
         heat = None if dir_save_path is None else getattr(result, "heat_picture", None)
         heat = None if heat is None else heat.cpu().numpy()
+        crops = None if dir_save_path is None else getattr(result, "crops", None)
+        crops = None if crops is None else crops.images()
         for b, n in enumerate(chunk):
             out.append((n, dets[b]))
             ih, iw = (int(v) for v in result.sizes[b])
@@ -549,4 +587,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
                 Image.fromarray(rendered[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + ".png"))
             if heat is not None:
                 Image.fromarray(heat[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_heat.png"))
+            for i, crop in enumerate(crops[b] if crops is not None else ()):
+                if crop is not None and crop.size:
+                    os.makedirs(os.path.join(dir_save_path, "img_crop"), exist_ok=True)
+                    Image.fromarray(crop).save(os.path.join(dir_save_path, "img_crop", f"{os.path.splitext(n)[0]}_crop_{i}.png"))
     return out

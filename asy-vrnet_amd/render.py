@@ -41,7 +41,16 @@ ValueError for x1 < x0 where this module paints nothing.
   mask_off_y) in black, clipped: per byte v = DIV255(v * (255 - m)), DIV255(a) = ((a + 128) + ((a + 128) >> 8)) >> 8.  Font
   size `label_font_size(ih)` = floor(3e-2 ih + 0.5) (yolo.py:163); size 0 (frames lower than 17 rows) draws no labels.
 
-Out of scope: crop saving and video I/O."""
+* `crop_boxes` / `Crops` / `crop_boxes_host` / `crop_layout`: yolo.py:180-193, the `crop` switch of detect_image -- every
+  detection cut out of the ORIGINAL frame (the reference crops before it draws), all crops of a batch in one packed arena on
+  the device (csrc/crops.hip).  The rule: a row left, top, right, bottom of an image (ih, iw) is clamped again, l = max(left,
+  0), t = max(top, 0), r = min(right, iw), bt = min(bottom, ih), w = r - l, h = bt - t, so no read leaves the frame whatever
+  the row holds; rows that `box_rows` or the finish kernel made are unchanged by it.  w <= 0 or h <= 0 is an EMPTY crop (Pillow
+  gives a zero-size image for w == 0 or h == 0 and raises ValueError for right < left; the reference would crash on saving
+  either, so the empty entry is this project's definition); otherwise the crop is frame[t:bt, l:r, :], bit for bit
+  np.array(image.crop([left, top, right, bottom])).  The arena's layout is `crop_layout`'s.
+
+Out of scope: crops resized to one size, image encoding and video I/O."""
 import colorsys
 import os
 
@@ -53,6 +62,8 @@ MAX_BOXES = 1024          # RN_MAXBOX: box rows of one image
 FLAG_CLASS, FLAG_BOX_COLOUR, FLAG_BOX_ROWS = 1, 2, 4     # bits of the optional `flag` word
 FLAG_LABEL_SCORE = 2048   # LB_FLAG_SCORE of csrc/labels.hip: a label score that is NaN or outside [0, 1], clamped
 LABEL_SCORES = 101        # the strings 0.00 .. 1.00 a score in [0, 1] formats to
+FLAG_CROP_ARENA = 4096    # VR_FLAG_CROP_ARENA of csrc/common.h: a crop that did not fit into the arena, dropped
+CROP_RECORD = np.dtype([("offset", "<i4"), ("w", "<i4"), ("h", "<i4"), ("image", "<i4")])      # vrnet_crop_rec, 16 bytes
 
 _device_palettes = {}
 
@@ -811,3 +822,153 @@ def draw_labels(picture, results, atlas, input_shape=None, thickness=None, font_
             hip.render_labels(picture, rows, offsets, _palette_on(bpal, dev), int(thickness), label_idx, blob, records,
                               atlas.size_index(font_size), flag=flag)
     return picture
+
+
+# ---- detection crops (csrc/crops.hip) ------------------------------------------------------------------------------------------
+def _crop_rows(rows, fn):
+    rows = np.asarray(rows)
+    if rows.dtype != np.int32 or rows.ndim != 2 or rows.shape[1] != 5:
+        raise RuntimeError(f"{fn}: expected int32 rows (n, 5), got {rows.dtype} {rows.shape}")
+    return rows.astype(np.int64)
+
+
+def _crop_windows(rows, ih, iw):
+    """The clamp of the module docstring for (n, 5) int64 rows and per-row (or scalar) image sizes: l, t, w, h with
+    w = h = 0 for an empty crop."""
+    l, t = np.maximum(rows[:, 0], 0), np.maximum(rows[:, 1], 0)
+    w, h = np.minimum(rows[:, 2], iw) - l, np.minimum(rows[:, 3], ih) - t
+    empty = (w <= 0) | (h <= 0)
+    return l, t, np.where(empty, 0, w), np.where(empty, 0, h)
+
+
+def crop_boxes_host(frame, rows):
+    """The crops of yolo.py:180-193 for ONE image in numpy: frame (ih, iw, 3) uint8, the ORIGINAL picture, and rows (n, 5)
+    int32 = left, top, right, bottom, class as `box_rows` gives them.  Returns a list of n uint8 arrays: frame[t:bt, l:r]
+    under the clamp of the module docstring -- bit for bit np.array(image.crop([left, top, right, bottom])) for the rows
+    `box_rows` makes -- and an array of shape (0, 0, 3) for an empty crop (w <= 0 or h <= 0, where Pillow gives a zero-size
+    image or raises).  This is the statement the kernels of csrc/crops.hip are tested against; tests/test_crops_host.py pins
+    it to live Pillow."""
+    fn = "crop_boxes_host"
+    pic = np.asarray(frame)
+    if pic.dtype != np.uint8 or pic.ndim != 3 or pic.shape[2] != 3:
+        raise RuntimeError(f"{fn}: expected a uint8 frame (ih, iw, 3), got {pic.dtype} {pic.shape}")
+    l, t, w, h = _crop_windows(_crop_rows(rows, fn), pic.shape[0], pic.shape[1])
+    return [pic[t[n]:t[n] + h[n], l[n]:l[n] + w[n]].copy() if w[n] else np.zeros((0, 0, 3), np.uint8) for n in range(len(l))]
+
+
+def crop_layout(rows, offsets, sizes, capacity):
+    """Where `crop_boxes` puts every crop: rows (N, 5) int32 in the packed order of `box_rows`, offsets (B + 1) int32, sizes
+    = (ih, iw) of all images or a (B, 2) array of each one's, capacity in pixels.  Returns (table, summary, flag): table (N)
+    records of CROP_RECORD -- offset, w, h, image --, summary = (N, used) and flag = FLAG_CROP_ARENA if a crop was dropped,
+    else 0.  Row n needs a = w * h rounded up to a multiple of 4 pixels (0 if empty); its offset is the sum of a over ALL
+    earlier rows, in pixels.  An empty row has w = h = 0 and offset 0; a non-empty row with offset + a > capacity is dropped:
+    it keeps w, h and gets offset -1, and since the sum runs over all rows, so does every later non-empty row.  used: the
+    sum of a over the kept rows.  The image of a row: offsets made monotone, c[0] = 0, c[i] = min(N, max(0, offsets[0..i])),
+    N = offsets[B] clamped to [0, len(rows)]; row n belongs to the image b with c[b] <= n < c[b + 1]."""
+    fn = "crop_layout"
+    rows = _crop_rows(rows, fn)
+    offsets = np.asarray(offsets)
+    if offsets.dtype != np.int32 or offsets.ndim != 1 or offsets.size < 2:
+        raise RuntimeError(f"{fn}: expected int32 offsets (B + 1), got {offsets.dtype} {offsets.shape}")
+    B = offsets.size - 1
+    sizes = np.asarray(sizes, np.int64)
+    sizes = np.broadcast_to(sizes, (B, 2)) if sizes.shape == (2,) else sizes
+    if sizes.shape != (B, 2) or int(capacity) < 1:
+        raise RuntimeError(f"{fn}: sizes is (ih, iw) or a ({B}, 2) array and the capacity at least one pixel")
+    N = int(np.clip(offsets[B], 0, len(rows)))
+    c = np.minimum(N, np.maximum.accumulate(np.maximum(offsets.astype(np.int64), 0)))
+    image = np.minimum(np.searchsorted(c[1:], np.arange(N), side="right"), B - 1)
+    _, _, w, h = _crop_windows(rows[:N], sizes[image, 0], sizes[image, 1])
+    a = (w * h + 3) // 4 * 4
+    off = np.cumsum(a) - a
+    kept = (a > 0) & (off + a <= int(capacity))
+    table = np.zeros(N, CROP_RECORD)
+    table["offset"] = np.where(a == 0, 0, np.where(kept, off, -1))
+    table["w"], table["h"], table["image"] = w, h, image
+    return table, (N, int(a[kept].sum())), FLAG_CROP_ARENA if bool(((a > 0) & ~kept).any()) else 0
+
+
+class Crops:
+    """What `crop_boxes` leaves on the device: arena (3 * capacity) uint8, the crops back to back, crop n one contiguous
+    (h, w, 3) block at arena[3 * offset:]; table (n_cap, 4) int32, one CROP_RECORD -- offset, w, h, image -- per draw row
+    (offset -1: the arena was full and the crop was dropped; w = h = 0: an empty crop; image -1: behind the last row);
+    summary (2) int32 = (rows, pixels in use); flag (1) int32.  A second stage that stays on the device reads arena and
+    table directly.  From a pipeline these are its own buffers: the next run overwrites them."""
+    __slots__ = ("arena", "table", "summary", "flag", "batch", "_packed")
+
+    def __init__(self, arena, table, summary, flag, batch, packed=None):
+        self.arena, self.table, self.summary, self.flag, self.batch, self._packed = arena, table, summary, flag, int(batch), packed
+
+    def images(self):
+        """The read-back: one list per image of its crops in row order as (h, w, 3) uint8 arrays -- shape (0, 0, 3) for an
+        empty crop, None for one the arena dropped.  Two device-to-host copies: the table with the summary (which waits for
+        the device), then arena[:3 * used]."""
+        packed = self._packed if self._packed is not None else torch.cat([self.table.reshape(-1), self.summary])
+        packed = packed.cpu().numpy()
+        (N, used), table = (int(v) for v in packed[-2:]), packed[:-2].view(CROP_RECORD)
+        arena = self.arena[:3 * used].cpu().numpy()
+        out = [[] for _ in range(self.batch)]
+        for off, w, h, b in table[:N].tolist():
+            if off < 0:
+                crop = None
+            elif w <= 0 or h <= 0:
+                crop = np.zeros((0, 0, 3), np.uint8)
+            else:
+                crop = arena[3 * off:3 * (off + w * h)].reshape(h, w, 3).copy()
+            out[b].append(crop)
+        return out
+
+
+def crop_buffers(n_cap, capacity, batch, flag, device):
+    """The device buffers of one `hip.crop_boxes` call as a `Crops`: table and summary share one int32 tensor, so the
+    read-back fetches both in one copy."""
+    capacity = int(capacity)
+    if not 1 <= capacity <= 1 << 30:
+        raise RuntimeError(f"crop_boxes: the capacity must lie in 1..2^30 pixels, got {capacity}")
+    packed = torch.empty(n_cap * 4 + 2, dtype=torch.int32, device=device)
+    arena = torch.empty(3 * capacity, dtype=torch.uint8, device=device)
+    return Crops(arena, packed[:n_cap * 4].view(n_cap, 4), packed[n_cap * 4:], flag, batch, packed)
+
+
+def crop_boxes(frames_u8, results, capacity=None, geom=None, flag=None, device="cuda"):
+    """yolo.py:180-193 on the device: every detection cut out of the ORIGINAL frames (crop before you draw, as the reference
+    does) into one packed arena, by the rule of `crop_boxes_host` and `crop_layout` (vrnet_crop_boxes_u8, two launches).
+    frames_u8 (B, ih, iw, 3) uint8 RGB, numpy or tensor (a single (ih, iw, 3) frame counts as B = 1).  results: the list
+    `non_max_suppression` returns -- packed by `box_rows` and sent in one pinned non-blocking copy -- or a pair (rows (n_cap,
+    5) int32, offsets (B + 1) int32) of device tensors, exactly as `render_frame` accepts them.  geom: the (B,
+    hip.GEOM_BYTES) device table of `data.frame_geometry` for padded ragged frames (image b in the top-left corner of slot
+    b); no crop then holds a byte of the padding.  capacity: the arena in pixels, default 2 * B * ih * iw.  flag: a zeroed
+    int32 device tensor of one element (a fresh one by default) that receives FLAG_CROP_ARENA -- a crop that did not fit,
+    dropped with every non-empty one behind it -- and hip.FLAG_GEOMETRY.  Returns a `Crops`.  No host synchronisation."""
+    from . import hip
+    fn = "crop_boxes"
+    img = _as_u8(frames_u8, "frames", 4, fn)
+    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
+        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    B, ih, iw = img.shape[:3]
+    if results is None:
+        raise RuntimeError(f"{fn}: needs the results of non_max_suppression or a device pair (rows, offsets)")
+    host = None
+    if isinstance(results, tuple) and len(results) == 2 and all(torch.is_tensor(t) for t in results):
+        rows, offsets = results
+    else:
+        if len(results) != B:
+            raise RuntimeError(f"{fn}: {len(results)} result entries for {B} frames")
+        host = box_rows(results, (ih, iw), MAX_COLORS)[:2]
+    img = img.to(device, non_blocking=True).contiguous()
+    dev = img.device
+    with torch.cuda.device(dev):
+        if host is not None:                  # offsets and rows in one pinned buffer; at least one row, so it has an address
+            n = max(len(host[0]), 1)
+            packed = torch.zeros(B + 1 + 5 * n, dtype=torch.int32).pin_memory()
+            packed[:B + 1] = torch.from_numpy(host[1])
+            packed[B + 1:B + 1 + host[0].size] = torch.from_numpy(host[0].reshape(-1))
+            packed = packed.to(dev, non_blocking=True)
+            offsets, rows = packed[:B + 1], packed[B + 1:].view(n, 5)
+        else:
+            rows, offsets = rows.to(dev).contiguous(), offsets.to(dev).contiguous()
+        if flag is None:
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        crops = crop_buffers(rows.shape[0], min(2 * B * ih * iw, 1 << 30) if capacity is None else capacity, B, flag, dev)
+        hip.crop_boxes(img, rows, offsets, crops.arena, crops.table, crops.summary, geom=geom, flag=flag)
+    return crops

@@ -1259,6 +1259,42 @@ int vrnet_render_labels_ragged_u8(unsigned char* picture, const vrnet_frame_geom
                                   const unsigned char* blob, long blob_bytes, const int* records, int num_classes, int n_sizes,
                                   int* flag, void* stream);
 
+/* ---- detection crops (csrc/crops.hip) -----------------------------------------------------------------------------------
+ * Added within ABI 11: a new symbol and one new record layout (vrnet_crop_rec) only, no existing signature, layout or kernel
+ * behaviour changed; hip.py binds every declared symbol at import.
+ * yolo.py:180-193, the `crop` switch of detect_image: every kept detection is cut out of the ORIGINAL frame (the reference
+ * crops before it draws) and saved.  Here the crops of a batch go into one packed arena on the device; the host statement
+ * is render.crop_boxes_host / render.crop_layout, and the kernels equal it bit for bit.
+ * vrnet_crop_boxes_u8: frames (B, ihm, iwm, 3) u8 slots with image b in the top-left corner of slot b, of size geom[b].ih x
+ *   geom[b].iw (clamped to the slot; a clamped or empty record sets bit 256) or ihm x iwm with geom == NULL; rows (n_cap, 5)
+ *   int32 = left, top, right, bottom, class and offsets (B + 1) as vrnet_detect_finish[_ragged]_f32 leave them.  N =
+ *   offsets[B] clamped to [0, n_cap]; the offsets are made monotone (c[0] = 0, c[i] = min(N, max(0, offsets[0..i]))) and row n
+ *   belongs to the image b with c[b] <= n < c[b + 1], so a hostile table indexes nothing outside.
+ *   Row n is clamped again, l = max(left, 0), t = max(top, 0), r = min(right, iw), bt = min(bottom, ih), w = r - l, h = bt - t.
+ *   w <= 0 or h <= 0: an EMPTY crop, table[n] = {0, 0, 0, b}, nothing copied (Pillow gives a zero-size image for w == 0 or
+ *   h == 0 and raises for right < left; the reference would crash on saving either).  Otherwise the crop is
+ *   frame[t:bt, l:r, :], bit for bit np.array(image.crop([left, top, right, bottom])), one contiguous (h, w, 3) block at
+ *   arena + 3 offset, offset = the sum of a over ALL earlier rows, a = w h rounded up to a multiple of 4 (0 for an empty
+ *   row), in 64 bits: every crop starts on a 4-byte boundary, and the up to 3 pad pixels behind it are zero bytes, so the
+ *   used prefix of the arena is the same bytes on every run.  A non-empty row with offset + a > capacity_px is DROPPED:
+ *   table[n] = {-1, w, h, b} and bit 4096 of *flag (VR_FLAG_CROP_ARENA) is set; the sum runs over all rows, so every later
+ *   non-empty row is dropped too: what is kept is a prefix.  table[n] = {0, 0, 0, -1} for N <= n < n_cap.  summary = (N, used),
+ *   used = the pixels in use (the sum of a over the kept rows); arena bytes at or beyond 3 used are not written.
+ *   Two launches: the layout (one workgroup, chunked prefix sums with a running 64-bit base) and the copy (a fixed number of
+ *   workgroups per row of the table; one that finds its row empty or dropped leaves at once, the others store each aligned
+ *   dword of the crop's block once, its four bytes gathered from the frame: work follows the crop area).  The grid depends
+ *   on n_cap alone.  No allocation, no memset, no host synchronisation; capturable in a graph.
+ *   0 < B < 65536, 0 < n_cap <= 2^20, 0 < capacity_px <= 2^30, ihm iwm < 2^31; arena (3 capacity_px bytes) and table 4-byte
+ *   aligned; flag may be NULL. */
+typedef struct vrnet_crop_rec {
+  int offset;                        /* the crop's first pixel in the arena; 0 if empty, -1 if dropped */
+  int w, h;                          /* 0, 0: an empty crop */
+  int image;                         /* the image the row belongs to; -1 behind the last row */
+} vrnet_crop_rec;                    /* 16 bytes */
+int vrnet_crop_boxes_u8(const unsigned char* frames, int B, int ihm, int iwm, const vrnet_frame_geom* geom, const int* rows,
+                        const int* offsets, int n_cap, unsigned char* arena, long capacity_px, vrnet_crop_rec* table,
+                        int* summary, int* flag, void* stream);
+
 
 #ifdef __cplusplus
 }
