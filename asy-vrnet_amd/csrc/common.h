@@ -82,6 +82,7 @@ typedef struct vrnet_frame_geom {
 #define VR_FLAG_POINT_COUNT 1024                /* radarmap.hip: a point count outside [0, max_points], clamped */
 /* 2048: LB_FLAG_SCORE of labels.hip, which shares the pipeline's flag word */
 #define VR_FLAG_CROP_ARENA 4096                 /* crops.hip: a crop that did not fit into the arena, dropped */
+#define VR_FLAG_DEHAZE 8192                     /* dehaze.hip: a degenerate image, returned unchanged */
 extern "C" {
 /* include/vrnet_hip.h: one record per draw row of vrnet_crop_boxes_u8. */
 typedef struct vrnet_crop_rec {

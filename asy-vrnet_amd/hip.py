@@ -164,6 +164,8 @@ _SIGS = {
     "vrnet_render_labels_u8": ([P, I, I, I, P, P, I, P, I, I, P, P, L, P, I, I, I, P, P], I),
     "vrnet_render_labels_ragged_u8": ([P, P, P, I, I, I, P, P, I, P, I, P, P, L, P, I, I, P, P], I),
     "vrnet_crop_boxes_u8": ([P, I, I, I, P, P, P, I, P, L, P, P, P, P], I),
+    "vrnet_dehaze_workspace_bytes": ([I, I, I], L),
+    "vrnet_dehaze_u8": ([P, P, I, I, I, I, I, D, D, D, P, P, P, P, L, P], I),
     "vrnet_heatmap_workspace": ([I, I, I], L),
     "vrnet_heatmap_f32": ([P, P, P] + [I] * 11 + [P, P, F, P, P, P, P, L, P], I),
     "vrnet_heatmap_ragged_workspace": ([I, I, I], L),
@@ -1708,3 +1710,34 @@ def crop_boxes(frames, rows, offsets, arena, table, summary, geom=None, flag=Non
                   (summary, (2,), torch.int32), (flag, (1,), torch.int32)))
     _check(_lib.vrnet_crop_boxes_u8(ptr(frames), B, ihm, iwm, None if geom is None else _geom(geom, B, fn), ptr(rows), ptr(offsets),
                                     n_cap, ptr(arena), arena.shape[0] // 3, ptr(table), ptr(summary), ptr(flag), stream()), fn)
+
+
+# ---- dark-channel dehazing (csrc/dehaze.hip) ---------------------------------------------------------------------------------
+FLAG_DEHAZE = 8192       # VR_FLAG_DEHAZE of csrc/common.h: a degenerate image, returned unchanged
+
+
+def dehaze_workspace_bytes(B, ihm, iwm):
+    n = _lib.vrnet_dehaze_workspace_bytes(B, ihm, iwm)
+    if n < 0:
+        raise RuntimeError(f"dehaze: bad shape (B {B}, slots of {ihm} x {iwm}; 1..65535 images, sides up to 2^17, at most 2^26 "
+                           "pixels each and 2^31 in all)")
+    return n
+
+
+def dehaze(frames, out, ws, geom=None, sz=15, r=60, eps=1e-4, omega=0.95, tx=0.1, transmission=None, flag=None):
+    """Dark-channel-prior dehazing by the rule of `render.dehaze_host` (vrnet_dehaze_u8): frames (B, ihm, iwm, 3) uint8 ->
+    out, another tensor of the same shape; transmission (B, ihm, iwm) float64 or None; ws: uint8, at least
+    dehaze_workspace_bytes(B, ihm, iwm) bytes -- its first 32 B bytes hold (A_r, A_g, A_b, degenerate) as float64 per image
+    afterwards; geom: the (B, GEOM_BYTES) table of a ragged batch, None: every image fills its slot; flag (1) int32 or
+    None: FLAG_DEHAZE for a degenerate image (returned unchanged, t = 1), FLAG_GEOMETRY for a bad record (a zero image).
+    Eleven launches, no host synchronisation."""
+    fn = "dehaze"
+    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError(f"{fn}: expected contiguous uint8 frames of shape (B, ihm, iwm, 3)")
+    B, ihm, iwm = frames.shape[:3]
+    if out is None or ws is None or out.data_ptr() == frames.data_ptr():
+        raise RuntimeError(f"{fn}: out (a tensor other than frames) and the workspace are required")
+    _tensors(fn, ((frames, (B, ihm, iwm, 3), torch.uint8), (out, (B, ihm, iwm, 3), torch.uint8),
+                  (transmission, (B, ihm, iwm), torch.float64), (flag, (1,), torch.int32), (ws, (ws.numel(),), torch.uint8)))
+    _check(_lib.vrnet_dehaze_u8(ptr(frames), None if geom is None else _geom(geom, B, fn), B, ihm, iwm, int(sz), int(r), float(eps),
+                                float(omega), float(tx), ptr(out), ptr(transmission), ptr(flag), ptr(ws), ws.numel(), stream()), fn)

@@ -15,7 +15,9 @@ FLAG_BOX_COLOUR, FLAG_BOX_ROWS (see render.render_frame), FLAG_CANDIDATES -- an 
 capacity, so only its `cap` best-scored ones were considered -- and FLAG_DET_CLASS -- a kept row with a class id
 outside [0, num_classes), which is not counted -- and, in a ragged pipeline, FLAG_GEOMETRY -- a record of the geometry
 table had to be clamped by a kernel, which the host checks of `run` rule out.  A pipeline built with crops= adds
-hip.crop_boxes behind hip.detect_finish and FLAG_CROP_ARENA, a crop that did not fit into the arena.
+hip.crop_boxes behind hip.detect_finish and FLAG_CROP_ARENA, a crop that did not fit into the arena.  A pipeline built with
+dehaze= puts hip.dehaze in front of the letterbox, so that everything downstream reads the dehazed frames, and adds
+FLAG_DEHAZE, a degenerate image that went on unchanged.
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
@@ -33,6 +35,7 @@ FLAG_GEOMETRY = 256                              # VR_FLAG_GEOMETRY of csrc/comm
 FLAG_POINT_COUNT = 1024                          # VR_FLAG_POINT_COUNT of csrc/common.h (a pipeline built with radar_points)
 FLAG_LABEL_SCORE = rendering.FLAG_LABEL_SCORE    # 2048, csrc/labels.hip (a pipeline built with labels): a score outside [0, 1]
 FLAG_CROP_ARENA = rendering.FLAG_CROP_ARENA      # 4096, csrc/crops.hip (a pipeline built with crops): a crop that did not fit
+FLAG_DEHAZE = rendering.FLAG_DEHAZE              # 8192, csrc/dehaze.hip (a pipeline built with dehaze): a degenerate image, unchanged
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -163,6 +166,18 @@ def crop_capacity(crops, batch, frame_shape):
     return int(crops)
 
 
+def dehaze_config(dehaze):
+    """The parameters of a pipeline's dehazing stage from its dehaze= keyword: None (no stage), True (the defaults of
+    `render.dehaze_host`) or a dict of its keywords sz, r, eps, omega, tx; checked by `render.dehaze_params`."""
+    if dehaze is None or dehaze is False:
+        return None
+    if dehaze is True:
+        dehaze = {}
+    if not isinstance(dehaze, dict) or set(dehaze) - {"sz", "r", "eps", "omega", "tx"}:
+        raise RuntimeError(f"FramePipeline: dehaze is None, True or a dict of sz, r, eps, omega, tx, got {dehaze!r}")
+    return rendering.dehaze_params(fn="FramePipeline", **dehaze)
+
+
 def unmap_scalars(input_shape, image_shape, letterbox_image):
     """(offset, scale): the (y, x) float64 pairs with which decode.yolo_correct_boxes maps a centre, (c - offset) * scale, and a
     size, s * scale -- its own expressions, np.round included; (0, 0), (1, 1) without a letterbox."""
@@ -189,15 +204,18 @@ class FrameResult:
     heat_range (B, 2) int32 = each mask's (min, max), what `render.heatmap` returns for the frames and the raw detection
     maps of the run; padded like class_map / rendered from a ragged pipeline.
     From a pipeline built with crops (None otherwise): crops, the `render.Crops` of the run -- every kept detection cut out
-    of the original frame, `crops.images()[b][i]` being row i of image b."""
+    of the original frame, `crops.images()[b][i]` being row i of image b.
+    From a pipeline built with dehaze (None otherwise): dehazed (B, ih, iw, 3) uint8, the frames everything else of the
+    result was computed from; padded like rendered from a ragged pipeline."""
     __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
-                 "heat_picture", "heat_range", "crops")
+                 "heat_picture", "heat_range", "crops", "dehazed")
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
-                 heat_picture=None, heat_range=None, crops=None):
+                 heat_picture=None, heat_range=None, crops=None, dehazed=None):
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
         self.heat_mask, self.heat_picture, self.heat_range, self.crops = heat_mask, heat_picture, heat_range, crops
+        self.dehazed = dehazed
 
     def detections(self):
         """The list `decode.non_max_suppression` returns: per image an (N_b, 7) float32 numpy array in the same order,
@@ -266,16 +284,29 @@ class FramePipeline:
     The arena, the table and the summary are allocated before the capture; the two launches of hip.crop_boxes sit right
     behind the detect_finish node.  True means 2 * batch * ihm * iwm pixels: a cap the caller may change, not a measured
     number -- 6 bytes per frame pixel, about 100 MB at batch 8 and 1080 x 1920.  Crops beyond the arena are dropped, a
-    prefix is kept, and FLAG_CROP_ARENA joins the bits of `flag`."""
+    prefix is kept, and FLAG_CROP_ARENA joins the bits of `flag`.
+
+    dehaze: None (the default: exactly the calls issued without it), True or a dict of the keywords sz, r, eps, omega, tx of
+    `render.dehaze_host` -- dark-channel-prior dehazing of the raw frames (`render.dehaze`, csrc/dehaze.hip) as the first
+    stage: the eleven launches of hip.dehaze sit in front of the letterbox node, and the letterbox, `render_frame`, the heat
+    map, the labels and the crops all read the dehazed frames, which are `FrameResult.dehazed`.  The workspace (seven
+    float64 planes of batch * ihm * iwm, `hip.dehaze_workspace_bytes`) and the second frame buffer are allocated before the
+    capture.  Fixed-size and ragged pipelines alike; a frame too small for the box (r // 2 > min(ih, iw) - 1) raises on the
+    host, in the constructor or in the validation of `run`; an image without atmospheric light (a black one, or one below
+    2000 pixels) goes on unchanged and FLAG_DEHAZE joins the bits of `flag`."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
-                 font=None, label_sizes=None, crops=None):
+                 font=None, label_sizes=None, crops=None, dehaze=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
         self.crop_capacity = crop_capacity(crops, self.batch, self.frame_shape)
+        self.dehaze = dehaze_config(dehaze)
+        if self.dehaze is not None and not rendering.dehaze_size_ok(*self.frame_shape, self.dehaze["r"]):
+            raise RuntimeError(f"FramePipeline: frames of {self.frame_shape[0]} x {self.frame_shape[1]} allow no single reflection "
+                               f"of the dehazing box r = {self.dehaze['r']}")
         self.radar_points = None
         if radar_points is not None:
             if radar_dtype != torch.float32:
@@ -320,6 +351,10 @@ class FramePipeline:
             self.points, self.views = self.radar_points.buffers(table, dev)
             self._radar_ws = self.radar_points.workspace(self.input_shape, dev)
         self.labels = self._label_atlas(labels, class_names, font, label_sizes)
+        if self.dehaze is not None:           # before the capture: the second frame buffer and the workspace
+            from . import hip
+            self._dehazed = torch.zeros_like(self.frames_u8)
+            self._dehaze_ws = torch.empty(hip.dehaze_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
         self.cap = None                       # the NMS buffers follow the anchor count of the first (warm-up) pass
         self.graph = self.result = None
         if graph:
@@ -396,11 +431,16 @@ class FramePipeline:
         from . import decode, hip            # the library loads with the first pass, not with the package
         (H, W), F, B, dev = self.input_shape, self.frame_shape, self.batch, self.device
         self.flag.zero_()                     # first: the ragged letterbox may raise FLAG_GEOMETRY
+        frames = self.frames_u8
+        if self.dehaze is not None:           # in front of the letterbox: everything below reads the dehazed frames
+            frames = self._dehazed
+            hip.dehaze(self.frames_u8, frames, self._dehaze_ws, geom=self.geom if self.ragged else None, flag=self.flag,
+                       **self.dehaze)
         if self.ragged:
             images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-            hip.letterbox_ragged(self.frames_u8, None, self.geom, H, W, self.max_taps, images=images, flag=self.flag)
+            hip.letterbox_ragged(frames, None, self.geom, H, W, self.max_taps, images=images, flag=self.flag)
         else:
-            images, _ = data.device_letterbox(self.frames_u8, (H, W), letterbox_image=self.letterbox_image, device=dev)
+            images, _ = data.device_letterbox(frames, (H, W), letterbox_image=self.letterbox_image, device=dev)
         if self.radar_points is not None:     # the first radar node: points -> self.radar under each frame's window
             hip.radar_map(self.points, self.views, H, W, self.radar_points.radius, float(self.radar_points.min_depth), self.radar,
                           flag=self.flag, ws=self._radar_ws)
@@ -419,7 +459,7 @@ class FramePipeline:
         else:
             hip.detect_finish(self._kept_rows, self._kept, self.num_classes, F, self.offset, self.scale, *finished)
         if self._crops is not None:           # right behind the finish node: from the original frames, which nothing draws on
-            hip.crop_boxes(self.frames_u8, self._draw_rows, self._offsets, self._crops.arena, self._crops.table,
+            hip.crop_boxes(frames, self._draw_rows, self._offsets, self._crops.arena, self._crops.table,
                            self._crops.summary, geom=self.geom if self.ragged else None, flag=self.flag)
         if self.ragged:
             class_map = decode.seg_predict_ragged(seg, self.geom, F, self.flag)
@@ -441,17 +481,18 @@ class FramePipeline:
                 if self.ragged:
                     picture["label_sizes"] = self.label_size_tab
             if self.ragged:
-                rendered, seg_counts = rendering.render_frame_ragged(self.frames_u8, self.geom, class_map, boxes, **picture)
+                rendered, seg_counts = rendering.render_frame_ragged(frames, self.geom, class_map, boxes, **picture)
             else:
-                rendered, seg_counts = rendering.render_frame(self.frames_u8, class_map, boxes, thickness=self.thickness,
+                rendered, seg_counts = rendering.render_frame(frames, class_map, boxes, thickness=self.thickness,
                                                               device=dev, **picture)
-        result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops)
+        result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops,
+                             dehazed=frames if self.dehaze is not None else None)
         if self.heatmap:
             if self.ragged:
-                heat = rendering.heatmap_ragged(self.frames_u8, det, self.geom, (H, W), window=self.letterbox_image,
+                heat = rendering.heatmap_ragged(frames, det, self.geom, (H, W), window=self.letterbox_image,
                                                 alpha=self.heat_alpha, flag=self.flag)
             else:
-                heat = rendering.heatmap(self.frames_u8, det, (H, W), letterbox_image=self.letterbox_image, alpha=self.heat_alpha)
+                heat = rendering.heatmap(frames, det, (H, W), letterbox_image=self.letterbox_image, alpha=self.heat_alpha)
             result.heat_picture, result.heat_mask, result.heat_range = heat
         self._tail(result)
         return result
@@ -505,6 +546,11 @@ class FramePipeline:
             return self._launch(f, r)
         checked = validate_ragged_inputs(frames_u8, radar, sizes, self.batch, self.frame_shape, self.input_shape,
                                          self.letterbox_image, self.max_taps, self.radar_points, calib)
+        if self.dehaze is not None:           # a frame too small for the box raises here, before anything is enqueued
+            for b, (h, w) in enumerate(np.asarray(checked[2]).tolist()):
+                if not rendering.dehaze_size_ok(h, w, self.dehaze["r"]):
+                    raise RuntimeError(f"FramePipeline: image {b}: {h} x {w} allows no single reflection of the dehazing box "
+                                       f"r = {self.dehaze['r']}")
         label_tab = None
         if self.labels is not None:           # a frame whose font size was not built raises here, before anything is enqueued
             label_tab = self.labels.size_table([int(s[0]) for s in checked[2]], "FramePipeline")
@@ -547,9 +593,9 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     non-empty crop the arena kept is saved as dir_save_path/img_crop/<stem>_crop_<i>.png, i being the row's index within its
     picture (the `i` of yolo.py:180-193); the crops of the repeated fill pictures are dropped with the repeats.  The reference
     writes img_crop/crop_<i>.png and so overwrites the crops of one picture with those of the next: the stem in the name is a
-    deliberate departure.  Two pictures that would share one
-    output file (names that differ only in their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on): with
-    dir_save_path that raises before anything runs."""
+    deliberate departure.  From a pipeline built with dehaze the dehazed frame is saved as <stem>_dehaze.png.  Two pictures
+    that would share one output file (names that differ only in their extension, or `a_heat.jpg` next to `a.jpg` with heat
+    maps on, or `a_dehaze.jpg` with dehazing on): with dir_save_path that raises before anything runs."""
     from PIL import Image
     if not getattr(pipeline, "ragged", False):
         raise RuntimeError("predict_dir: needs a ragged pipeline (FramePipeline(..., ragged=True)): a folder holds pictures of any size")
@@ -558,7 +604,9 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         stems = {}
         for n in names:
             stem = os.path.splitext(n)[0]
-            for target in (stem, stem + "_heat") if getattr(pipeline, "heatmap", False) else (stem,):
+            targets = (stem,) + ((stem + "_heat",) if getattr(pipeline, "heatmap", False) else ()) + \
+                ((stem + "_dehaze",) if getattr(pipeline, "dehaze", None) is not None else ())
+            for target in targets:
                 other = stems.setdefault(target, n)
                 if other != n:
                     raise RuntimeError(f"predict_dir: {other} and {n} would both be saved as {target}.png")
@@ -578,6 +626,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         rendered = None if dir_save_path is None or result.rendered is None else result.rendered.cpu().numpy()
         heat = None if dir_save_path is None else getattr(result, "heat_picture", None)
         heat = None if heat is None else heat.cpu().numpy()
+        dehazed = None if dir_save_path is None else getattr(result, "dehazed", None)
+        dehazed = None if dehazed is None else dehazed.cpu().numpy()
         crops = None if dir_save_path is None else getattr(result, "crops", None)
         crops = None if crops is None else crops.images()
         for b, n in enumerate(chunk):
@@ -587,6 +637,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
                 Image.fromarray(rendered[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + ".png"))
             if heat is not None:
                 Image.fromarray(heat[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_heat.png"))
+            if dehazed is not None:
+                Image.fromarray(dehazed[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_dehaze.png"))
             for i, crop in enumerate(crops[b] if crops is not None else ()):
                 if crop is not None and crop.size:
                     os.makedirs(os.path.join(dir_save_path, "img_crop"), exist_ok=True)

@@ -50,6 +50,10 @@ ValueError for x1 < x0 where this module paints nothing.
   either, so the empty entry is this project's definition); otherwise the crop is frame[t:bt, l:r, :], bit for bit
   np.array(image.crop([left, top, right, bottom])).  The arena's layout is `crop_layout`'s.
 
+* `dehaze` / `dehaze_host`: He et al.'s dark-channel-prior dehazing, the reference's image_augmentation_test/dark_channel.py,
+  on the raw frames (csrc/dehaze.hip).  `dehaze_host` states the rule in numpy float64, one rounding per operation; the
+  kernels equal it bit for bit.
+
 Out of scope: crops resized to one size, image encoding and video I/O."""
 import colorsys
 import os
@@ -64,6 +68,8 @@ FLAG_LABEL_SCORE = 2048   # LB_FLAG_SCORE of csrc/labels.hip: a label score that
 LABEL_SCORES = 101        # the strings 0.00 .. 1.00 a score in [0, 1] formats to
 FLAG_CROP_ARENA = 4096    # VR_FLAG_CROP_ARENA of csrc/common.h: a crop that did not fit into the arena, dropped
 CROP_RECORD = np.dtype([("offset", "<i4"), ("w", "<i4"), ("h", "<i4"), ("image", "<i4")])      # vrnet_crop_rec, 16 bytes
+FLAG_DEHAZE = 8192        # VR_FLAG_DEHAZE of csrc/common.h: a degenerate image, returned unchanged by `dehaze`
+DEHAZE_MAX_SZ, DEHAZE_MAX_R = 31, 128
 
 _device_palettes = {}
 
@@ -972,3 +978,161 @@ def crop_boxes(frames_u8, results, capacity=None, geom=None, flag=None, device="
         crops = crop_buffers(rows.shape[0], min(2 * B * ih * iw, 1 << 30) if capacity is None else capacity, B, flag, dev)
         hip.crop_boxes(img, rows, offsets, crops.arena, crops.table, crops.summary, geom=geom, flag=flag)
     return crops
+
+
+# ---- dark-channel dehazing (csrc/dehaze.hip) -----------------------------------------------------------------------------------
+def dehaze_params(sz=15, r=60, eps=1e-4, omega=0.95, tx=0.1, fn="dehaze"):
+    """The parameters of the dehazing rule, checked: sz odd in 1..31, 2 <= r <= 128, eps > 0 (finite), 0 < omega <= 1,
+    0 < tx <= 1.  Returns them as a dict of Python numbers."""
+    ints = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (sz, r))
+    if not ints or not 1 <= sz <= DEHAZE_MAX_SZ or sz % 2 == 0 or not 2 <= r <= DEHAZE_MAX_R:
+        raise RuntimeError(f"{fn}: sz must be an odd integer in 1..{DEHAZE_MAX_SZ} and r an integer in 2..{DEHAZE_MAX_R}, got sz "
+                           f"{sz!r}, r {r!r}")
+    try:
+        eps, omega, tx = float(eps), float(omega), float(tx)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{fn}: eps, omega and tx are numbers, got {eps!r}, {omega!r}, {tx!r}") from None
+    if not (0.0 < eps < np.inf and 0.0 < omega <= 1.0 and 0.0 < tx <= 1.0):
+        raise RuntimeError(f"{fn}: eps must be positive and finite, omega and tx in (0, 1], got eps {eps}, omega {omega}, tx {tx}")
+    return dict(sz=int(sz), r=int(r), eps=eps, omega=omega, tx=tx)
+
+
+def dehaze_size_ok(ih, iw, r):
+    """Whether an (ih, iw) image allows the single reflection of an r x r box: r // 2 <= min(ih, iw) - 1."""
+    return int(r) // 2 <= min(int(ih), int(iw)) - 1
+
+
+def _erode_host(a, sz, fill):
+    """The minimum over the sz x sz window centred on each pixel, positions outside the image ignored."""
+    h = sz // 2
+    ih, iw = a.shape
+    p = np.full((ih + 2 * h, iw + 2 * h), fill, a.dtype)
+    p[h:h + ih, h:h + iw] = a
+    rows = p[:, 0:iw].copy()
+    for j in range(1, sz):
+        np.minimum(rows, p[:, j:j + iw], out=rows)
+    out = rows[0:ih].copy()
+    for j in range(1, sz):
+        np.minimum(out, rows[j:j + ih], out=out)
+    return out
+
+
+def _refl_host(i, n):
+    i = np.abs(i)
+    return np.where(i < n, i, 2 * (n - 1) - i)
+
+
+def box_filter_host(p, r):
+    """cv2.boxFilter(p, CV_64F, (r, r)) restated: normalised, anchor r // 2, BORDER_REFLECT_101, the r taps of each pass added
+    one after the other from the leftmost (topmost) on -- r shifted adds per pass, then one division by float(r * r)."""
+    p = np.asarray(p, np.float64)
+    ih, iw = p.shape
+    o = r // 2
+    if o > min(ih, iw) - 1:
+        raise RuntimeError(f"box_filter_host: a {ih} x {iw} plane allows no single reflection of a box of {r}")
+    q = p[:, _refl_host(np.arange(-o, iw - o + r - 1), iw)]
+    h = q[:, 0:iw].copy()
+    for j in range(1, r):
+        h += q[:, j:j + iw]
+    q = h[_refl_host(np.arange(-o, ih - o + r - 1), ih)]
+    v = q[0:ih].copy()
+    for j in range(1, r):
+        v += q[j:j + ih]
+    return v / float(r * r)
+
+
+def gray_host(rgb):
+    """OpenCV's 8-bit RGB -> gray: (4899 R + 9617 G + 1868 B + 8192) >> 14, uint8."""
+    c = np.asarray(rgb).astype(np.int64)
+    return ((4899 * c[..., 0] + 9617 * c[..., 1] + 1868 * c[..., 2] + 8192) >> 14).astype(np.uint8)
+
+
+def atmospheric_light_host(rgb, dark8):
+    """A of the rule: numpx = max(ih * iw // 1000, 1); the pixels in ascending (dark8, flat index) order, the last numpx
+    without the first of those; A_c = (float(integer sum of byte_c) / 255.0) / float(numpx)."""
+    n = dark8.size
+    numpx = max(n // 1000, 1)
+    idx = np.argsort(dark8.reshape(-1), kind="stable")[n - numpx:][1:]
+    S = rgb.reshape(n, 3)[idx].astype(np.int64).sum(0)
+    return (S.astype(np.float64) / 255.0) / float(numpx)
+
+
+def saturate_host(v):
+    """clip(rint(v), 0, 255) as uint8, half to even: the saturate_cast of a float64 picture."""
+    return np.clip(np.rint(v), 0.0, 255.0).astype(np.uint8)
+
+
+def dehaze_host(rgb, sz=15, r=60, eps=1e-4, omega=0.95, tx=0.1):
+    """He et al.'s dark-channel-prior dehazing of ONE (ih, iw, 3) uint8 RGB frame in numpy float64, every operation rounded
+    on its own in the order of the header's statement (include/vrnet_hip.h, vrnet_dehaze_u8): dark channel, atmospheric
+    light from the brightest 0.1 % of it, transmission estimate, guided filter with an r x r box, recovery.  Returns
+    (bytes (ih, iw, 3) uint8, t (ih, iw) float64, A (3) float64).  A degenerate image -- any A_c == 0 (which includes
+    ih * iw < 2000, where nothing is summed) or r // 2 > min(ih, iw) - 1 -- comes back unchanged with t = 1.  This is the
+    statement the kernels of csrc/dehaze.hip are tested against.  The OpenCV semantics in it (erode's border, BGR2GRAY's
+    integers, boxFilter's anchor and border, saturate_cast) are restated from OpenCV's published behaviour and have never
+    been run against cv2."""
+    fn = "dehaze_host"
+    q = dehaze_params(sz, r, eps, omega, tx, fn)
+    sz, r, eps, omega, tx = q["sz"], q["r"], q["eps"], q["omega"], q["tx"]
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or min(rgb.shape) <= 0:
+        raise RuntimeError(f"{fn}: expected a uint8 frame (ih, iw, 3), got {rgb.dtype} {rgb.shape}")
+    ih, iw = rgb.shape[:2]
+    dark8 = _erode_host(rgb.min(2), sz, np.uint8(255))
+    A = atmospheric_light_host(rgb, dark8)
+    if bool((A == 0.0).any()) or not dehaze_size_ok(ih, iw, r):
+        return rgb.copy(), np.ones((ih, iw), np.float64), A
+    I = rgb.astype(np.float64) / 255.0
+    te = 1.0 - omega * _erode_host((I / A).min(2), sz, np.inf)
+    g = gray_host(rgb).astype(np.float64) / 255.0
+    mI, mp, mIp, mII = box_filter_host(g, r), box_filter_host(te, r), box_filter_host(g * te, r), box_filter_host(g * g, r)
+    a = (mIp - mI * mp) / ((mII - mI * mI) + eps)
+    b = mp - a * mI
+    t = box_filter_host(a, r) * g + box_filter_host(b, r)
+    v = ((I - A) / np.maximum(t, tx)[..., None] + A) * 255.0
+    return saturate_host(v), t, A
+
+
+def dehaze(frames_u8, sizes=None, geom=None, sz=15, r=60, eps=1e-4, omega=0.95, tx=0.1, transmission=False, flag=None,
+           device="cuda"):
+    """`dehaze_host` on the device (vrnet_dehaze_u8, eleven launches, no host synchronisation): frames_u8 (B, ih, iw, 3) uint8
+    RGB, numpy or tensor (a single (ih, iw, 3) frame counts as B = 1).  sizes: (B, 2) host integers (ih_b, iw_b) when the
+    frames are padded slots with image b in the top-left corner of slot b -- a table is built from them --, or geom: the
+    (B, hip.GEOM_BYTES) device table of `data.frame_geometry`; neither: every image fills its slot.  Outside an image's
+    corner the results are 0.  Returns (out (B, ih, iw, 3) uint8, t (B, ih, iw) float64 or None without transmission=True,
+    A (B, 3) float64), all on the device.  flag: a zeroed int32 device tensor of one element, or None: it receives
+    FLAG_DEHAZE for a degenerate image, which comes back unchanged with t = 1, and hip.FLAG_GEOMETRY for a bad record of
+    the table, which gives a zero image.  A size known on the host (no table, or sizes) that
+    allows no single reflection of the box, r // 2 > min(ih, iw) - 1, raises before anything is enqueued."""
+    from . import data, hip
+    fn = "dehaze"
+    q = dehaze_params(sz, r, eps, omega, tx, fn)
+    img = _as_u8(frames_u8, "frames", 4, fn)
+    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
+        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    B, ih, iw = img.shape[:3]
+    if sizes is not None and geom is not None:
+        raise RuntimeError(f"{fn}: give sizes or a geometry table, not both")
+    table = None
+    if sizes is not None:
+        arr = data.frame_sizes(sizes, B, fn)
+        for b, (h, w) in enumerate(arr.tolist()):
+            if h <= 0 or w <= 0 or h > ih or w > iw:
+                raise RuntimeError(f"{fn}: image {b}: bad size {h} x {w} in a slot of {ih} x {iw}")
+            if not dehaze_size_ok(h, w, q["r"]):
+                raise RuntimeError(f"{fn}: image {b}: {h} x {w} allows no single reflection of a box of r = {q['r']}")
+        table = np.zeros(B, data.GEOM_DTYPE)
+        table["ih"], table["iw"], table["thickness"] = arr[:, 0], arr[:, 1], 1
+    elif geom is None and not dehaze_size_ok(ih, iw, q["r"]):
+        raise RuntimeError(f"{fn}: frames of {ih} x {iw} allow no single reflection of a box of r = {q['r']}")
+    img = img.to(device, non_blocking=True).contiguous()
+    dev = img.device
+    with torch.cuda.device(dev):
+        if table is not None:
+            geom = data.geometry_bytes(table).pin_memory().to(dev, non_blocking=True)
+        out = torch.empty_like(img)
+        t = torch.empty((B, ih, iw), dtype=torch.float64, device=dev) if transmission else None
+        ws = torch.empty(hip.dehaze_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
+        hip.dehaze(img, out, ws, geom=geom, transmission=t, flag=flag, **q)
+        A = ws[:32 * B].view(torch.float64).view(B, 4)[:, :3].clone()
+    return out, t, A

@@ -1295,6 +1295,51 @@ int vrnet_crop_boxes_u8(const unsigned char* frames, int B, int ihm, int iwm, co
                         const int* offsets, int n_cap, unsigned char* arena, long capacity_px, vrnet_crop_rec* table,
                         int* summary, int* flag, void* stream);
 
+/* ---- dark-channel dehazing (csrc/dehaze.hip) ------------------------------------------------------------------------------
+ * Added within ABI 11: two new symbols only, no existing signature, layout or kernel behaviour changed.
+ * He et al.'s dark-channel-prior dehazing, the reference's image_augmentation_test/dark_channel.py restated; the host
+ * statement is render.dehaze_host and the kernels equal it bit for bit.  THE RULE for one (ih, iw, 3) uint8 RGB image; every
+ * float64 operation is rounded on its own in the order written, nothing is contracted, divisions are IEEE:
+ *   I_c   = double(byte_c) / 255.0.
+ *   d8    = min over c of byte_c; dark8 = the minimum of d8 over the sz x sz window centred on the pixel (sz odd), positions
+ *           outside the image ignored (cv2.erode's default border); uint8 (the reference's d8 / 255 orders identically).
+ *   numpx = max(ih iw / 1000, 1) in integers.  The pixels in ascending order of (dark8, flat index y iw + x) -- a stable
+ *           ascending argsort, one valid outcome of the reference's unordered ties --: the last numpx of them without the first
+ *           of those (the reference's range(1, numpx)); S_c = the INTEGER sum of byte_c over these numpx - 1 pixels (the
+ *           reference adds floats sequentially: rounding only, and this is order-free); A_c = (double(S_c) / 255.0) / double(numpx).
+ *   m     = min over c of (I_c / A_c);  te = 1.0 - omega * (the same windowed minimum of m).
+ *   g8    = (4899 R + 9617 G + 1868 B + 8192) >> 14 (OpenCV's 8-bit BGR2GRAY);  g = double(g8) / 255.0.
+ *   box(p): cv2.boxFilter(p, CV_64F, (r, r)), normalised, anchor o = r / 2, REFLECT_101: refl(i, n) = |i| if |i| < n, else
+ *           2 (n - 1) - |i|;  h(y, x) = p(y, refl(x - o, iw)), then += p(y, refl(x - o + j, iw)) for j = 1 .. r - 1 in that
+ *           order; the same over the rows of h; then / double(r r).  The fixed tap order makes it reproducible.
+ *   mI = box(g), mp = box(te), mIp = box(g * te), mII = box(g * g);  a = (mIp - mI * mp) / ((mII - mI * mI) + eps);
+ *   b = mp - a * mI;  t = box(a) * g + box(b).
+ *   J_c = (I_c - A_c) / max(t, tx) + A_c;  v = J_c * 255.0;  byte = clip(rint(v), 0, 255), half to even (the saturate_cast
+ *   cv2.imwrite applies).
+ *   DEGENERATE: any A_c == 0 (numpx == 1 included, where nothing is summed), or r / 2 > min(ih, iw) - 1 (the size allows no
+ *   single reflection).  A degenerate image comes back UNCHANGED with t = 1 and sets bit 8192 of *flag (VR_FLAG_DEHAZE); the
+ *   other images of the batch are unaffected.
+ * The OpenCV semantics above are restated from its published behaviour and have never been run against cv2.
+ * vrnet_dehaze_u8: frames (B, ihm, iwm, 3) u8; out the same shape, a different buffer (frames is not modified);
+ *   transmission (B, ihm, iwm) f64 or NULL; flag may be NULL; geom the per-image table of the ragged batches, or NULL when
+ *   every image fills its slot.  With a table image b is the geom[b].ih x geom[b].iw top-left corner of its slot and
+ *   everything outside the corner is written 0 in out and transmission; a record with ih, iw <= 0 or above the slot sets
+ *   bit 256 (VR_FLAG_GEOMETRY) and gives a zero image.  One kernel body for both cases.
+ *   sz odd in 1..31, 2 <= r <= 128, eps > 0 (finite), 0 < omega <= 1, 0 < tx <= 1; 0 < B < 65536, ihm, iwm <= 2^17,
+ *   ihm iwm <= 2^26, B ihm iwm <= 2^31; workspace and transmission 8-byte aligned.
+ *   Eleven launches (init, dark channel + histogram, threshold bin, per-chunk counts of the bin, ranked integer sums, A and
+ *   the degenerate decision, transmission estimate, box rows of g / te / g te / g g, box columns fused with a and b, box rows
+ *   of a and b, box columns fused with t, the recovery and the byte store).  Every call initialises what it accumulates
+ *   into; integer atomics only (the histogram and the sums): the same bytes on every run.  No allocation, no memset node,
+ *   no host synchronisation; capturable in a graph.
+ * vrnet_dehaze_workspace_bytes: the bytes of `workspace` (-1 for a shape outside the limits): seven float64 planes of
+ *   B ihm iwm, one byte plane and small tables.  After the call its first 32 B bytes hold, per image, the doubles
+ *   A_r, A_g, A_b and 1.0 for a degenerate or bad image (else 0.0). */
+long vrnet_dehaze_workspace_bytes(int B, int ihm, int iwm);
+int vrnet_dehaze_u8(const unsigned char* frames, const vrnet_frame_geom* geom, int B, int ihm, int iwm, int sz, int r, double eps,
+                    double omega, double tx, unsigned char* out, double* transmission, int* flag, void* workspace,
+                    long workspace_bytes, void* stream);
+
 
 #ifdef __cplusplus
 }
