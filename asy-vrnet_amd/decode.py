@@ -119,58 +119,53 @@ def seg_window(input_shape, image_shape):
     return (H - nh) // 2, (W - nw) // 2, nh, nw
 
 
-def seg_predict(outputs_seg, input_shape, image_shape):
+def seg_predict(outputs_seg, input_shape, image_shape=None, geom=None, capacity=None, flag=None, fn="seg_predict"):
     """get_miou_png / detect_image (utils_seg/callbacks.py:140-157, deeplab.py:141-167) for a batch of images of one
     original size: outputs_seg (B, C, H, W) seg logits of a letterboxed input of input_shape = (H, W), image_shape =
     (ih, iw).  Returns the (B, ih, iw) uint8 class map on the logits' device: per output pixel the arg-max over classes of
     the OpenCV INTER_LINEAR resize of the letterbox window's softmax (softmax, crop, resize, arg-max: the reference's
     order), equal values going to the lower class as numpy argmax.  No host synchronisation; fp16 / bf16 logits are
-    computed in fp32."""
+    computed in fp32.
+    geom: the (B, hip.GEOM_BYTES) device table of `data.frame_geometry` for a batch of images of their own sizes
+    (vrnet_seg_predict_ragged_f32), with capacity = (ihm, iwm) in place of image_shape.  The class map is then the padded
+    (B, ihm, iwm): image b is `[b, :ih_b, :iw_b]`, equal to the call without a table on that image alone, and every pixel
+    outside it is 0.  flag: an int32 device word for hip.FLAG_GEOMETRY, or None."""
+    table = hip._table_call(fn, geom, (("image_shape", image_shape, None),), (("capacity", capacity, None),))
     if not (torch.is_tensor(outputs_seg) and outputs_seg.dim() == 4):
-        raise RuntimeError("seg_predict: expects (B, C, H, W) seg logits")
+        raise RuntimeError(f"{fn}: expects (B, C, H, W) seg logits")
     B, C, H, W = outputs_seg.shape
     if not 0 < C <= SEG_MAX_CLASSES:
-        raise RuntimeError(f"seg_predict: {C} classes (1..{SEG_MAX_CLASSES} supported)")
-    if (H, W) != (int(input_shape[0]), int(input_shape[1])):
-        raise RuntimeError(f"seg_predict: logits are {H} x {W}, input_shape is {tuple(input_shape)}")
-    ih, iw = int(image_shape[0]), int(image_shape[1])
-    if ih <= 0 or iw <= 0:
-        raise RuntimeError(f"seg_predict: bad image_shape {tuple(image_shape)}")
-    top, left, nh, nw = seg_window(input_shape, image_shape)
-    if nh <= 0 or nw <= 0:
-        raise RuntimeError(f"seg_predict: image {ih} x {iw} leaves an empty window in {H} x {W}")
-    if not outputs_seg.is_cuda:
-        raise RuntimeError("seg_predict: the logits must be on a GPU (there is no CPU fallback)")
+        raise RuntimeError(f"{fn}: {C} classes (1..{SEG_MAX_CLASSES} supported)")
+    if input_shape is not None and (H, W) != (int(input_shape[0]), int(input_shape[1])):
+        raise RuntimeError(f"{fn}: logits are {H} x {W}, input_shape is {tuple(input_shape)}")
+    if table:
+        oh, ow = int(capacity[0]), int(capacity[1])
+        if not outputs_seg.is_cuda:
+            raise RuntimeError(f"{fn}: the logits must be on a GPU (there is no CPU fallback)")
+        if oh <= 0 or ow <= 0 or B == 0:
+            raise RuntimeError(f"{fn}: bad capacity {tuple(capacity)} or an empty batch")
+    else:
+        oh, ow = int(image_shape[0]), int(image_shape[1])
+        if oh <= 0 or ow <= 0:
+            raise RuntimeError(f"{fn}: bad image_shape {tuple(image_shape)}")
+        top, left, nh, nw = seg_window(input_shape, image_shape)
+        if nh <= 0 or nw <= 0:
+            raise RuntimeError(f"{fn}: image {oh} x {ow} leaves an empty window in {H} x {W}")
+        if not outputs_seg.is_cuda:
+            raise RuntimeError(f"{fn}: the logits must be on a GPU (there is no CPU fallback)")
     x = outputs_seg.detach()
     x = x if (x.is_contiguous() and x.dtype == torch.float32) else x.contiguous().float()
-    out = torch.empty((B, ih, iw), dtype=torch.uint8, device=x.device)
-    if B == 0:
-        return out
-    ws = torch.empty(hip.seg_predict_workspace_bytes(B, C, nh, nw), dtype=torch.uint8, device=x.device)
-    hip.seg_predict(x, top, left, nh, nw, out, ws)
+    with torch.cuda.device(x.device):
+        out = torch.empty((B, oh, ow), dtype=torch.uint8, device=x.device)
+        if table:
+            ws = torch.empty(hip.seg_predict_ragged_workspace_bytes(B, C, H, W), dtype=torch.uint8, device=x.device)
+            hip.seg_predict(x, None, None, None, None, out, ws, geom=geom, flag=flag, fn=fn)
+        elif B:
+            ws = torch.empty(hip.seg_predict_workspace_bytes(B, C, nh, nw), dtype=torch.uint8, device=x.device)
+            hip.seg_predict(x, top, left, nh, nw, out, ws)
     return out
 
 
 def seg_predict_ragged(outputs_seg, geom, capacity, flag=None):
-    """`seg_predict` for a batch of images of their own sizes (vrnet_seg_predict_ragged_f32): outputs_seg (B, C, H, W) seg
-    logits, geom the (B, hip.GEOM_BYTES) device table of `data.frame_geometry` (window and size of image b), capacity =
-    (ihm, iwm).  Returns the padded (B, ihm, iwm) uint8 class map: image b is `[b, :ih_b, :iw_b]`, equal to `seg_predict` on
-    that image alone, and every pixel outside it is 0.  flag: an int32 device word for hip.FLAG_GEOMETRY, or None.  No host
-    synchronisation."""
-    if not (torch.is_tensor(outputs_seg) and outputs_seg.dim() == 4):
-        raise RuntimeError("seg_predict_ragged: expects (B, C, H, W) seg logits")
-    B, C, H, W = outputs_seg.shape
-    if not 0 < C <= SEG_MAX_CLASSES:
-        raise RuntimeError(f"seg_predict_ragged: {C} classes (1..{SEG_MAX_CLASSES} supported)")
-    if not outputs_seg.is_cuda:
-        raise RuntimeError("seg_predict_ragged: the logits must be on a GPU (there is no CPU fallback)")
-    ihm, iwm = int(capacity[0]), int(capacity[1])
-    if ihm <= 0 or iwm <= 0 or B == 0:
-        raise RuntimeError(f"seg_predict_ragged: bad capacity {tuple(capacity)} or an empty batch")
-    x = outputs_seg.detach()
-    x = x if (x.is_contiguous() and x.dtype == torch.float32) else x.contiguous().float()
-    with torch.cuda.device(x.device):
-        out = torch.empty((B, ihm, iwm), dtype=torch.uint8, device=x.device)
-        ws = torch.empty(hip.seg_predict_ragged_workspace_bytes(B, C, H, W), dtype=torch.uint8, device=x.device)
-        hip.seg_predict_ragged(x, geom, out, ws, flag)
-    return out
+    """`seg_predict` with a geometry table, under its earlier name."""
+    return seg_predict(outputs_seg, None, None, geom, capacity, flag, "seg_predict_ragged")

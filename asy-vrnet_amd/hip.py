@@ -269,6 +269,21 @@ def _tensors(fn, specs):
             raise RuntimeError(f"{fn}: expected a contiguous {dt} GPU tensor of shape {sh}, got {t.dtype} {tuple(t.shape)}")
 
 
+def _table_call(fn, geom, replaced=(), table_only=()):
+    """Whether this call of a frame op has a geometry table.  The inference-side frame ops are one body each: without geom
+    every image fills its slot and the launch arguments carry the geometry; with geom, the (B, GEOM_BYTES) device table of
+    `data.frame_geometry`, every image has its own, the `_ragged` entry point runs and flag receives FLAG_GEOMETRY.  The
+    `_ragged` names forward to the body, which needs the table then.  replaced: (name, value, default) of the arguments the
+    table replaces, absent (at their default) beside a table; table_only: those only a table call has."""
+    if geom is None and fn.endswith("_ragged"):
+        raise RuntimeError(f"{fn}: the geometry table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape (B, {GEOM_BYTES})")
+    clash = [n for n, v, d in (table_only if geom is None else replaced) if not (v is d or (not torch.is_tensor(v) and v == d))]
+    if clash:
+        raise RuntimeError(f"{fn}: {', '.join(clash)}: " + ("only a call with a geometry table (geom=) takes that" if geom is None else
+                                                             "the geometry table holds that for every image; pass it or geom, not both"))
+    return geom is not None
+
+
 def stream():
     return torch.cuda.current_stream().cuda_stream
 
@@ -993,18 +1008,26 @@ def nms_capped(rows, scores, classes, ids, counts, segments, stride, cap, iou_th
                                      ptr(rows_out), ptr(flag), stream()), "nms_capped")
 
 
-def detect_finish(rows, kept, num_classes, image_shape, offset, scale, rows_out, draw_rows, offsets, det_counts, flag):
+def detect_finish(rows, kept, num_classes, image_shape, offset, scale, rows_out, draw_rows, offsets, det_counts, flag, geom=None,
+                  capacity=None, fn="detect_finish"):
     """The kept rows (B, cap, 7) of nms_capped -> rows in pixels of the original image, the renderer's box rows with
     their offsets and the class counts (vrnet_detect_finish_f32).  offset / scale: the (y, x) float64 pairs of
-    yolo_correct_boxes; image_shape = (ih, iw)."""
+    yolo_correct_boxes; image_shape = (ih, iw).  With geom (`_table_call`) all three are None: the shape and the un-map
+    scalars of image b come from geom[b], and capacity = (ihm, iwm) (vrnet_detect_finish_ragged_f32)."""
+    table = _table_call(fn, geom, (("image_shape", image_shape, None), ("offset", offset, None), ("scale", scale, None)),
+                       (("capacity", capacity, None),))
     B, cap = rows.shape[:2]
-    _tensors("detect_finish", ((rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32),
-                               (rows_out, (B, cap, 7), torch.float32), (draw_rows, (B * cap, 5), torch.int32),
-                               (offsets, (B + 1,), torch.int32), (det_counts, (B, num_classes), torch.int64),
-                               (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_detect_finish_f32(ptr(rows), ptr(kept), B, cap, int(num_classes), int(image_shape[0]), int(image_shape[1]),
-                                        float(offset[0]), float(offset[1]), float(scale[0]), float(scale[1]), ptr(rows_out),
-                                        ptr(draw_rows), ptr(offsets), ptr(det_counts), ptr(flag), stream()), "detect_finish")
+    _tensors(fn, ((rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32), (rows_out, (B, cap, 7), torch.float32),
+                  (draw_rows, (B * cap, 5), torch.int32), (offsets, (B + 1,), torch.int32),
+                  (det_counts, (B, num_classes), torch.int64), (flag, (1,), torch.int32)))
+    outs = (rows_out, draw_rows, offsets, det_counts, flag)
+    if table:
+        _check(_lib.vrnet_detect_finish_ragged_f32(ptr(rows), ptr(kept), _geom(geom, B, fn), B, cap, int(num_classes), int(capacity[0]),
+                                                   int(capacity[1]), *map(ptr, outs), stream()), fn)
+    else:
+        _check(_lib.vrnet_detect_finish_f32(ptr(rows), ptr(kept), B, cap, int(num_classes), int(image_shape[0]), int(image_shape[1]),
+                                            float(offset[0]), float(offset[1]), float(scale[0]), float(scale[1]), *map(ptr, outs),
+                                            stream()), fn)
 
 
 def eval_append(rows, kept, gt, gt_count, cursor, arena, flag):
@@ -1071,47 +1094,67 @@ def letterbox_workspace_bytes(B, ih, iw, nh, nw):
     return _lib.vrnet_letterbox_workspace(B, ih, iw, nh, nw)
 
 
-def letterbox(img_u8, label_u8, H, W, nw, nh, dx, dy, canvas=None, images=None, label_out=None, ws=None):
+def letterbox(img_u8, label_u8, H, W, nw=None, nh=None, dx=None, dy=None, canvas=None, images=None, label_out=None, ws=None,
+              geom=None, max_taps=None, flag=None, fn="letterbox"):
     """Raw frames -> the letterboxed batch, Pillow's bytes (vrnet_letterbox_u8): img_u8 (B,ih,iw,3) uint8 RGB, label_u8
     (B,ih,iw) uint8 or None; the window nw x nh at column dx, row dy of the W x H canvas.  Outputs (None = not wanted):
     canvas (B,H,W,3) uint8, images (B,3,H,W) f32 normalised as batch_formats does, label_out (B,H,W) uint8.  ws: a uint8
-    tensor of letterbox_workspace_bytes(B, ih, iw, nh, nw) bytes (default: this stream's scratch arena)."""
+    tensor of letterbox_workspace_bytes(B, ih, iw, nh, nw) bytes (default: this stream's scratch arena).  With geom
+    (`_table_call`) the inputs are padded slots (B,ihm,iwm,..), the window of image b comes from geom[b] in place of nw, nh, dx,
+    dy, max_taps is the tap capacity of a table entry and ws has letterbox_ragged_workspace_bytes (vrnet_letterbox_ragged_u8)."""
+    table = _table_call(fn, geom, (("nw", nw, None), ("nh", nh, None), ("dx", dx, None), ("dy", dy, None)),
+                       (("max_taps", max_taps, None),))
+    m = "m" if table else ""
     src = img_u8 if img_u8 is not None else label_u8
     if src is None or src.dim() < 3:
-        raise RuntimeError("letterbox: expected frames (B, ih, iw, 3) and / or label maps (B, ih, iw)")
+        raise RuntimeError(f"{fn}: expected frames (B, ih{m}, iw{m}, 3) and / or label maps (B, ih{m}, iw{m})")
     B, ih, iw = src.shape[:3]
-    _tensors("letterbox", ((img_u8, (B, ih, iw, 3), torch.uint8), (label_u8, (B, ih, iw), torch.uint8),
-                           (canvas, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
-                           (label_out, (B, H, W), torch.uint8)))
+    _tensors(fn, ((img_u8, (B, ih, iw, 3), torch.uint8), (label_u8, (B, ih, iw), torch.uint8), (canvas, (B, H, W, 3), torch.uint8),
+                  (images, (B, 3, H, W), torch.float32), (label_out, (B, H, W), torch.uint8), (flag, (1,), torch.int32)))
+    # a table call asks for its size even when the caller brings a workspace
+    need = _lib.vrnet_letterbox_ragged_workspace(B, ih, iw, int(H), int(W), int(max_taps)) if table else None
     if ws is None:
-        ws = _ws.get(_lib.vrnet_letterbox_workspace(B, ih, iw, nh, nw), src.device)
+        ws = _ws.get(need if table else _lib.vrnet_letterbox_workspace(B, ih, iw, nh, nw), src.device)
     elif ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise RuntimeError(f"letterbox: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
-    _check(_lib.vrnet_letterbox_u8(ptr(img_u8), ptr(label_u8), B, ih, iw, int(H), int(W), int(nw), int(nh), int(dx), int(dy),
-                                   ptr(canvas), ptr(images), ptr(label_out), ptr(ws), ws.numel(), stream()), "letterbox")
+        raise RuntimeError(f"{fn}: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    if table:
+        _check(_lib.vrnet_letterbox_ragged_u8(ptr(img_u8), ptr(label_u8), _geom(geom, B, fn), B, ih, iw, int(H), int(W), int(max_taps),
+                                              ptr(canvas), ptr(images), ptr(label_out), ptr(flag), ptr(ws), ws.numel(), stream()), fn)
+    else:
+        _check(_lib.vrnet_letterbox_u8(ptr(img_u8), ptr(label_u8), B, ih, iw, int(H), int(W), int(nw), int(nh), int(dx), int(dy),
+                                       ptr(canvas), ptr(images), ptr(label_out), ptr(ws), ws.numel(), stream()), fn)
 
 
 def render(frames, class_map, out, palette=None, mix_type=0, alpha=0.7, boxes=None, box_offsets=None, box_palette=None,
-           thickness=1, counts=None, flag=None):
+           thickness=1, counts=None, flag=None, geom=None, fn="render"):
     """The rendered frames (vrnet_render_u8): frames / out (B,ih,iw,3) uint8, class_map (B,ih,iw) uint8 or None, palette
     (n,3) uint8, boxes (N,5) int32 with box_offsets (B+1) int32 and box_palette (m,3) uint8, counts (B,n) int64 (overwritten;
     n = counts.shape[1] when there is no palette), flag (1) int32 (data-error bits, OR-ed in).  out may be frames when there
-    is no class map."""
-    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8 or not frames.is_contiguous():
-        raise RuntimeError("render: expected contiguous uint8 frames of shape (B, ih, iw, 3)")
+    is no class map.  With geom (`_table_call`) frames / out / class_map are padded slots, ih, iw and the thickness of image b
+    come from geom[b] and out must not be the frames (vrnet_render_ragged_u8)."""
+    table = _table_call(fn, geom, (("thickness", thickness, 1),))
+    m = "m" if table else ""
+    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3 or \
+            not (table or (frames.dtype == torch.uint8 and frames.is_contiguous())):
+        raise RuntimeError(f"{fn}: expected contiguous uint8 frames of shape (B, ih{m}, iw{m}, 3)")
     B, ih, iw = frames.shape[:3]
     n_colors = palette.shape[0] if palette is not None else (counts.shape[1] if counts is not None else 0)
     n_rows = 0 if boxes is None else boxes.shape[0]
-    _tensors("render", (
-        (out, (B, ih, iw, 3), torch.uint8), (class_map, (B, ih, iw), torch.uint8), (palette, (n_colors, 3), torch.uint8),
-        (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32), (counts, (B, n_colors), torch.int64),
-        (flag, (1,), torch.int32), (box_palette, (0 if box_palette is None else box_palette.shape[0], 3), torch.uint8)))
+    n_box_colors = 0 if box_palette is None else box_palette.shape[0]
+    _tensors(fn, (
+        (frames, (B, ih, iw, 3), torch.uint8), (out, (B, ih, iw, 3), torch.uint8), (class_map, (B, ih, iw), torch.uint8),
+        (palette, (n_colors, 3), torch.uint8), (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32),
+        (counts, (B, n_colors), torch.int64), (flag, (1,), torch.int32), (box_palette, (n_box_colors, 3), torch.uint8)))
     if out is None or (n_rows and (box_offsets is None or box_palette is None)):
-        raise RuntimeError("render: out is required, and box rows need box_offsets and a box_palette")
-    _check(_lib.vrnet_render_u8(ptr(frames), ptr(class_map), B, ih, iw, ptr(palette), n_colors, int(mix_type), float(alpha),
-                                ptr(boxes) if n_rows else None, ptr(box_offsets), n_rows, ptr(box_palette),
-                                0 if box_palette is None else box_palette.shape[0], int(thickness), ptr(out), ptr(counts),
-                                ptr(flag), stream()), "render")
+        raise RuntimeError(f"{fn}: out is required, and box rows need box_offsets and a box_palette")
+    picture = (ptr(palette), n_colors, int(mix_type), float(alpha), ptr(boxes) if n_rows else None, ptr(box_offsets), n_rows,
+               ptr(box_palette), n_box_colors)
+    if table:
+        _check(_lib.vrnet_render_ragged_u8(ptr(frames), ptr(class_map), _geom(geom, B, fn), B, ih, iw, *picture, ptr(out),
+                                           ptr(counts), ptr(flag), stream()), fn)
+    else:
+        _check(_lib.vrnet_render_u8(ptr(frames), ptr(class_map), B, ih, iw, *picture, int(thickness), ptr(out), ptr(counts),
+                                    ptr(flag), stream()), fn)
 
 
 def _heat_levels(fn, levels, H, W):
@@ -1127,20 +1170,29 @@ def heatmap_workspace_bytes(B, H, W):
     return _lib.vrnet_heatmap_workspace(B, H, W)
 
 
-def heatmap(levels, H, W, mask, minmax, ws, window=0, dx=0, dy=0, nw=0, nh=0, frames=None, cmap=None, alpha=0.5, out=None):
+def heatmap(levels, H, W, mask, minmax, ws, window=0, dx=0, dy=0, nw=0, nh=0, frames=None, cmap=None, alpha=0.5, out=None,
+            geom=None, flag=None, fn="heatmap"):
     """yolo.py:288-351 on the device (vrnet_heatmap_f32): levels the three raw detection maps of an (H, W) input -> mask
     (B, ih, iw) uint8 and minmax (B, 2) int32; with out (B, ih, iw, 3) uint8 also the blend of cmap (256, 3) uint8 over
     frames (B, ih, iw, 3) uint8.  window = 1 maps the pixels through the letterbox window (dx, dy, nw, nh).  ws:
-    heatmap_workspace_bytes(B, H, W) bytes."""
-    B, nc = _heat_levels("heatmap", levels, int(H), int(W))
+    heatmap_workspace_bytes(B, H, W) bytes.  With geom (`_table_call`) mask, frames and out are padded slots, ih, iw and the
+    window of image b come from geom[b], 0 outside the image, and ws has heatmap_ragged_workspace_bytes
+    (vrnet_heatmap_ragged_f32)."""
+    table = _table_call(fn, geom, (("dx", dx, 0), ("dy", dy, 0), ("nw", nw, 0), ("nh", nh, 0)))
+    m = "m" if table else ""
+    B, nc = _heat_levels(fn, levels, int(H), int(W))
     if mask is None or mask.dim() != 3:
-        raise RuntimeError("heatmap: mask (B, ih, iw) is required")
+        raise RuntimeError(f"{fn}: mask (B, ih{m}, iw{m}) is required")
     ih, iw = mask.shape[1:]
-    _tensors("heatmap", ((mask, (B, ih, iw), torch.uint8), (minmax, (B, 2), torch.int32), (frames, (B, ih, iw, 3), torch.uint8),
-                         (out, (B, ih, iw, 3), torch.uint8), (cmap, (256, 3), torch.uint8)))
-    _check(_lib.vrnet_heatmap_f32(ptr(levels[0]), ptr(levels[1]), ptr(levels[2]), B, nc, int(H), int(W), ih, iw, int(window),
-                                  int(dx), int(dy), int(nw), int(nh), ptr(frames), ptr(cmap), float(alpha), ptr(mask), ptr(out),
-                                  ptr(minmax), ptr(ws), ws.numel(), stream()), "heatmap")
+    _tensors(fn, ((mask, (B, ih, iw), torch.uint8), (minmax, (B, 2), torch.int32), (frames, (B, ih, iw, 3), torch.uint8),
+                  (out, (B, ih, iw, 3), torch.uint8), (cmap, (256, 3), torch.uint8), (flag, (1,), torch.int32)))
+    lv, picture = [ptr(t) for t in levels], (ptr(frames), ptr(cmap), float(alpha), ptr(mask), ptr(out), ptr(minmax))
+    if table:
+        _check(_lib.vrnet_heatmap_ragged_f32(*lv, _geom(geom, B, fn), B, nc, int(H), int(W), ih, iw, int(window), *picture, ptr(flag),
+                                             ptr(ws), ws.numel(), stream()), fn)
+    else:
+        _check(_lib.vrnet_heatmap_f32(*lv, B, nc, int(H), int(W), ih, iw, int(window), int(dx), int(dy), int(nw), int(nh), *picture,
+                                      ptr(ws), ws.numel(), stream()), fn)
 
 
 def yolo_loss(levels, grads, strides, labels, counts, max_gt, grad_scale, out, fg=None, matched=None, piou=None):
@@ -1179,12 +1231,19 @@ def seg_predict_workspace_bytes(B, C, nh, nw):
     return _lib.vrnet_seg_predict_workspace(B, C, nh, nw)
 
 
-def seg_predict(x, top, left, nh, nw, out, ws):
+def seg_predict(x, top, left, nh, nw, out, ws, geom=None, flag=None, fn="seg_predict"):
     """x (B, C, H, W) fp32 -> out (B, oh, ow) uint8: arg-max of the bilinear resize of the window's softmax
-    (vrnet_seg_predict_f32); ws: seg_predict_workspace_bytes(B, C, nh, nw) bytes."""
+    (vrnet_seg_predict_f32); ws: seg_predict_workspace_bytes(B, C, nh, nw) bytes.  With geom (`_table_call`) top, left, nh and
+    nw are None: out is (B, ihm, iwm), the window and size of image b come from geom[b], 0 outside the image, and ws has
+    seg_predict_ragged_workspace_bytes(B, C, H, W) bytes (vrnet_seg_predict_ragged_f32)."""
     B, C, H, W = x.shape
-    _check(_lib.vrnet_seg_predict_f32(ptr(x), B, C, H, W, top, left, nh, nw, out.shape[1], out.shape[2], ptr(out), ptr(ws),
-                                      ws.numel(), stream()), "seg_predict")
+    if _table_call(fn, geom, (("top", top, None), ("left", left, None), ("nh", nh, None), ("nw", nw, None))):
+        _tensors(fn, ((x, (B, C, H, W), torch.float32), (out, (B,) + tuple(out.shape[1:3]), torch.uint8), (flag, (1,), torch.int32)))
+        _check(_lib.vrnet_seg_predict_ragged_f32(ptr(x), _geom(geom, B, fn), B, C, H, W, out.shape[1], out.shape[2], ptr(out),
+                                                 ptr(flag), ptr(ws), ws.numel(), stream()), fn)
+    else:
+        _check(_lib.vrnet_seg_predict_f32(ptr(x), B, C, H, W, top, left, nh, nw, out.shape[1], out.shape[2], ptr(out), ptr(ws),
+                                          ws.numel(), stream()), fn)
 
 
 def confusion_hist(label, pred, n, hist):
@@ -1336,78 +1395,35 @@ def _geom(geom, B, fn):
     return _table(_GEOM, geom, B, fn)[0]
 
 
-def letterbox_ragged_workspace_bytes(B, ihm, iwm, H, W, max_taps):
-    return _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, max_taps)
-
-
+# the `_ragged` names of the inference-side frame ops: each is the fixed-name body with the table (`_table_call`)
 def letterbox_ragged(img_u8, label_u8, geom, H, W, max_taps, canvas=None, images=None, label_out=None, flag=None, ws=None):
-    """`letterbox` for frames of their own sizes (vrnet_letterbox_ragged_u8): img_u8 (B,ihm,iwm,3) / label_u8 (B,ihm,iwm)
-    padded slots, geom the (B, GEOM_BYTES) table; max_taps: the tap capacity of a table entry; flag (1) int32 or None."""
-    src = img_u8 if img_u8 is not None else label_u8
-    if src is None or src.dim() < 3:
-        raise RuntimeError("letterbox_ragged: expected frames (B, ihm, iwm, 3) and / or label maps (B, ihm, iwm)")
-    B, ihm, iwm = src.shape[:3]
-    _tensors("letterbox_ragged", ((img_u8, (B, ihm, iwm, 3), torch.uint8), (label_u8, (B, ihm, iwm), torch.uint8),
-                                       (canvas, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
-                                       (label_out, (B, H, W), torch.uint8), (flag, (1,), torch.int32)))
-    need = _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, int(H), int(W), int(max_taps))
-    if ws is None:
-        ws = _ws.get(need, src.device)
-    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise RuntimeError(f"letterbox_ragged: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
-    _check(_lib.vrnet_letterbox_ragged_u8(ptr(img_u8), ptr(label_u8), _geom(geom, B, "letterbox_ragged"), B, ihm, iwm, int(H),
-                                          int(W), int(max_taps), ptr(canvas), ptr(images), ptr(label_out), ptr(flag), ptr(ws),
-                                          ws.numel(), stream()), "letterbox_ragged")
+    letterbox(img_u8, label_u8, H, W, None, None, None, None, canvas, images, label_out, ws, geom, max_taps, flag, "letterbox_ragged")
 
 
 def detect_finish_ragged(rows, kept, geom, num_classes, capacity, rows_out, draw_rows, offsets, det_counts, flag):
-    """`detect_finish` with the image shape and the un-map scalars of image b from geom[b]
-    (vrnet_detect_finish_ragged_f32); capacity = (ihm, iwm)."""
-    B, cap = rows.shape[:2]
-    _tensors("detect_finish_ragged", (
-        (rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32), (rows_out, (B, cap, 7), torch.float32),
-        (draw_rows, (B * cap, 5), torch.int32), (offsets, (B + 1,), torch.int32), (det_counts, (B, num_classes), torch.int64),
-        (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_detect_finish_ragged_f32(ptr(rows), ptr(kept), _geom(geom, B, "detect_finish_ragged"), B, cap,
-                                               int(num_classes), int(capacity[0]), int(capacity[1]), ptr(rows_out),
-                                               ptr(draw_rows), ptr(offsets), ptr(det_counts), ptr(flag), stream()),
-           "detect_finish_ragged")
-
-
-def seg_predict_ragged_workspace_bytes(B, C, H, W):
-    return _lib.vrnet_seg_predict_ragged_workspace(B, C, H, W)
+    detect_finish(rows, kept, num_classes, None, None, None, rows_out, draw_rows, offsets, det_counts, flag, geom, capacity,
+                  "detect_finish_ragged")
 
 
 def seg_predict_ragged(x, geom, out, ws, flag=None):
-    """x (B, C, H, W) fp32 -> out (B, ihm, iwm) uint8, the window and size of image b from geom[b], 0 outside the image
-    (vrnet_seg_predict_ragged_f32); ws: seg_predict_ragged_workspace_bytes(B, C, H, W) bytes."""
-    B, C, H, W = x.shape
-    _tensors("seg_predict_ragged", ((x, (B, C, H, W), torch.float32), (out, (B,) + tuple(out.shape[1:3]), torch.uint8),
-                                         (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_seg_predict_ragged_f32(ptr(x), _geom(geom, B, "seg_predict_ragged"), B, C, H, W, out.shape[1], out.shape[2],
-                                             ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), "seg_predict_ragged")
+    seg_predict(x, None, None, None, None, out, ws, geom, flag, "seg_predict_ragged")
 
 
 def render_ragged(frames, class_map, geom, out, palette=None, mix_type=0, alpha=0.7, boxes=None, box_offsets=None,
                   box_palette=None, counts=None, flag=None):
-    """`render` on padded slots (vrnet_render_ragged_u8): frames / out (B,ihm,iwm,3), class_map (B,ihm,iwm); ih, iw and the
-    thickness of image b from geom[b]; out must not be the frames."""
-    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3:
-        raise RuntimeError("render_ragged: expected contiguous uint8 frames of shape (B, ihm, iwm, 3)")
-    B, ih, iw = frames.shape[:3]
-    n_colors = palette.shape[0] if palette is not None else (counts.shape[1] if counts is not None else 0)
-    n_rows = 0 if boxes is None else boxes.shape[0]
-    _tensors("render_ragged", (
-        (frames, (B, ih, iw, 3), torch.uint8), (out, (B, ih, iw, 3), torch.uint8), (class_map, (B, ih, iw), torch.uint8),
-        (palette, (n_colors, 3), torch.uint8), (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32),
-        (counts, (B, n_colors), torch.int64), (flag, (1,), torch.int32),
-        (box_palette, (0 if box_palette is None else box_palette.shape[0], 3), torch.uint8)))
-    if out is None or (n_rows and (box_offsets is None or box_palette is None)):
-        raise RuntimeError("render_ragged: out is required, and box rows need box_offsets and a box_palette")
-    _check(_lib.vrnet_render_ragged_u8(ptr(frames), ptr(class_map), _geom(geom, B, "render_ragged"), B, ih, iw, ptr(palette),
-                                       n_colors, int(mix_type), float(alpha), ptr(boxes) if n_rows else None, ptr(box_offsets),
-                                       n_rows, ptr(box_palette), 0 if box_palette is None else box_palette.shape[0], ptr(out),
-                                       ptr(counts), ptr(flag), stream()), "render_ragged")
+    render(frames, class_map, out, palette, mix_type, alpha, boxes, box_offsets, box_palette, 1, counts, flag, geom, "render_ragged")
+
+
+def heatmap_ragged(levels, geom, H, W, mask, minmax, ws, window=1, frames=None, cmap=None, alpha=0.5, out=None, flag=None):
+    heatmap(levels, H, W, mask, minmax, ws, window, 0, 0, 0, 0, frames, cmap, alpha, out, geom, flag, "heatmap_ragged")
+
+
+def letterbox_ragged_workspace_bytes(B, ihm, iwm, H, W, max_taps):
+    return _lib.vrnet_letterbox_ragged_workspace(B, ihm, iwm, H, W, max_taps)
+
+
+def seg_predict_ragged_workspace_bytes(B, C, H, W):
+    return _lib.vrnet_seg_predict_ragged_workspace(B, C, H, W)
 
 
 # ---- the frame modes of training: the plain letterbox, the augmentation and the Mosaic run the same four operations ----
@@ -1496,21 +1512,6 @@ def box_targets_ragged(boxes, counts, geom, capacity, H, W, targets=None, counts
 
 def heatmap_ragged_workspace_bytes(B, H, W):
     return _lib.vrnet_heatmap_ragged_workspace(B, H, W)
-
-
-def heatmap_ragged(levels, geom, H, W, mask, minmax, ws, window=1, frames=None, cmap=None, alpha=0.5, out=None, flag=None):
-    """`heatmap` on padded slots (vrnet_heatmap_ragged_f32): mask (B, ihm, iwm), frames / out (B, ihm, iwm, 3); ih, iw and
-    the window of image b from geom[b]; 0 outside the image.  ws: heatmap_ragged_workspace_bytes(B, H, W) bytes."""
-    B, nc = _heat_levels("heatmap_ragged", levels, int(H), int(W))
-    if mask is None or mask.dim() != 3:
-        raise RuntimeError("heatmap_ragged: mask (B, ihm, iwm) is required")
-    ihm, iwm = mask.shape[1:]
-    _tensors("heatmap_ragged", ((mask, (B, ihm, iwm), torch.uint8), (minmax, (B, 2), torch.int32),
-                                (frames, (B, ihm, iwm, 3), torch.uint8), (out, (B, ihm, iwm, 3), torch.uint8),
-                                (cmap, (256, 3), torch.uint8), (flag, (1,), torch.int32)))
-    _check(_lib.vrnet_heatmap_ragged_f32(ptr(levels[0]), ptr(levels[1]), ptr(levels[2]), _geom(geom, B, "heatmap_ragged"), B, nc,
-                                         int(H), int(W), ihm, iwm, int(window), ptr(frames), ptr(cmap), float(alpha), ptr(mask),
-                                         ptr(out), ptr(minmax), ptr(flag), ptr(ws), ws.numel(), stream()), "heatmap_ragged")
 
 
 # ---- training augmentation (include/vrnet_hip.h "training augmentation"): per-image records from a device table ----------
@@ -1638,51 +1639,43 @@ def label_index(rows, kept, offsets, num_classes, label_idx, flag=None):
                                       label_idx.shape[0], ptr(flag), stream()), "label_index")
 
 
-def _label_args(fn, picture, boxes, box_offsets, box_palette, label_idx, blob, records):
-    """The checks both label renderers share; returns (B, h, w, n_rows, num_classes, n_sizes)."""
+def render_labels(picture, boxes, box_offsets, box_palette, thickness, label_idx, blob, records, size_index, flag=None, geom=None,
+                  fn="render_labels"):
+    """Tags and label text over the picture `render` finished, in place (vrnet_render_labels_u8): picture (B,ih,iw,3) uint8,
+    boxes (N,5) / box_offsets (B+1) / box_palette (m,3) / thickness as `render` took them, label_idx (N) int32 = class * 101
+    + k, blob (bytes) uint8 and records (sizes, num_classes * 101, 8) int32 of a `render.LabelAtlas`, size_index its font size.
+    With geom (`_table_call`) thickness is None: ih, iw and the thickness of image b come from geom[b], and size_index is the
+    (B) int32 device table of each image's font size, -1 for an image without labels (vrnet_render_labels_ragged_u8)."""
+    table = _table_call(fn, geom, (("thickness", thickness, None),))
     if picture is None or picture.dim() != 4 or picture.shape[-1] != 3:
         raise RuntimeError(f"{fn}: expected a contiguous uint8 picture of shape (B, ih, iw, 3)")
     B, ih, iw = picture.shape[:3]
     if boxes is None or box_offsets is None or box_palette is None or label_idx is None or blob is None or records is None:
         raise RuntimeError(f"{fn}: boxes, box_offsets, box_palette, label_idx and the atlas blob and records are required")
-    n_rows = boxes.shape[0]
     if records.dim() != 3 or records.shape[0] < 1 or records.shape[1] < LABEL_SCORES or records.shape[1] % LABEL_SCORES:
         raise RuntimeError(f"{fn}: the atlas records must have shape (sizes, num_classes * {LABEL_SCORES}, {LABEL_RECORD}), got "
                            f"{tuple(records.shape)}")
+    n_rows, n_sizes = boxes.shape[0], records.shape[0]
     _tensors(fn, ((picture, (B, ih, iw, 3), torch.uint8), (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32),
                   (box_palette, (box_palette.shape[0], 3), torch.uint8), (label_idx, (n_rows,), torch.int32),
-                  (blob, (blob.shape[0],), torch.uint8),
-                  (records, (records.shape[0], records.shape[1], LABEL_RECORD), torch.int32)))
-    return B, ih, iw, n_rows, records.shape[1] // LABEL_SCORES, records.shape[0]
-
-
-def render_labels(picture, boxes, box_offsets, box_palette, thickness, label_idx, blob, records, size_index, flag=None):
-    """Tags and label text over the picture `render` finished, in place (vrnet_render_labels_u8): picture (B,ih,iw,3) uint8,
-    boxes (N,5) / box_offsets (B+1) / box_palette (m,3) / thickness as `render` took them, label_idx (N) int32 = class * 101
-    + k, blob (bytes) uint8 and records (sizes, num_classes * 101, 8) int32 of a `render.LabelAtlas`, size_index its font size."""
-    fn = "render_labels"
-    B, ih, iw, n_rows, nc, n_sizes = _label_args(fn, picture, boxes, box_offsets, box_palette, label_idx, blob, records)
-    _tensors(fn, ((flag, (1,), torch.int32),))
+                  (blob, (blob.shape[0],), torch.uint8), (records, (n_sizes, records.shape[1], LABEL_RECORD), torch.int32),
+                  (flag, (1,), torch.int32), (size_index if table else None, (B,), torch.int32)))
+    if table and size_index is None:
+        raise RuntimeError(f"{fn}: the per-image size-index table is required")
     if n_rows == 0:                           # nothing to draw (and an empty tensor has no address to pass)
         return
-    _check(_lib.vrnet_render_labels_u8(ptr(picture), B, ih, iw, ptr(boxes), ptr(box_offsets), n_rows, ptr(box_palette),
-                                       box_palette.shape[0], int(thickness), ptr(label_idx), ptr(blob), blob.shape[0],
-                                       ptr(records), nc, n_sizes, int(size_index), ptr(flag), stream()), fn)
+    rows = (ptr(boxes), ptr(box_offsets), n_rows, ptr(box_palette), box_palette.shape[0])
+    atlas = (ptr(label_idx), ptr(blob), blob.shape[0], ptr(records), records.shape[1] // LABEL_SCORES, n_sizes)
+    if table:
+        _check(_lib.vrnet_render_labels_ragged_u8(ptr(picture), _geom(geom, B, fn), ptr(size_index), B, ih, iw, *rows, *atlas, ptr(flag),
+                                                  stream()), fn)
+    else:
+        _check(_lib.vrnet_render_labels_u8(ptr(picture), B, ih, iw, *rows, int(thickness), *atlas, int(size_index), ptr(flag),
+                                           stream()), fn)
 
 
 def render_labels_ragged(picture, geom, size_index, boxes, box_offsets, box_palette, label_idx, blob, records, flag=None):
-    """`render_labels` on padded slots (vrnet_render_labels_ragged_u8): ih, iw and the thickness of image b from geom[b], its
-    font size from size_index (B) int32, -1 for an image without labels."""
-    fn = "render_labels_ragged"
-    B, ih, iw, n_rows, nc, n_sizes = _label_args(fn, picture, boxes, box_offsets, box_palette, label_idx, blob, records)
-    _tensors(fn, ((flag, (1,), torch.int32), (size_index, (B,), torch.int32)))
-    if size_index is None:
-        raise RuntimeError(f"{fn}: the per-image size-index table is required")
-    if n_rows == 0:
-        return
-    _check(_lib.vrnet_render_labels_ragged_u8(ptr(picture), _geom(geom, B, fn), ptr(size_index), B, ih, iw, ptr(boxes),
-                                              ptr(box_offsets), n_rows, ptr(box_palette), box_palette.shape[0], ptr(label_idx),
-                                              ptr(blob), blob.shape[0], ptr(records), nc, n_sizes, ptr(flag), stream()), fn)
+    render_labels(picture, boxes, box_offsets, box_palette, None, label_idx, blob, records, size_index, flag, geom, "render_labels_ragged")
 
 
 # ---- detection crops (csrc/crops.hip) ----------------------------------------------------------------------------------------

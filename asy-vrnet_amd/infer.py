@@ -330,8 +330,6 @@ class FramePipeline:
         self.device = dev = p.device
         (ih, iw), (H, W), B = self.frame_shape, self.input_shape, self.batch
         self.num_classes = int(model.num_classes)
-        self.thickness = int(max((iw + ih) // np.mean(self.input_shape), 1))                    # yolo.py:164
-        self.offset, self.scale = unmap_scalars(self.input_shape, self.frame_shape, self.letterbox_image)
         pal = rendering.seg_palette(int(model.num_seg_classes)) if seg_palette is None else seg_palette
         bpal = rendering.det_palette(self.num_classes) if box_palette is None else box_palette
         self.seg_palette, self.box_palette = (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
@@ -340,12 +338,19 @@ class FramePipeline:
         self.frames_u8 = torch.zeros((B, ih, iw, 3), dtype=torch.uint8, device=dev)
         self.radar = torch.zeros((B, 4, H, W), dtype=radar_dtype, device=dev)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ragged, self.sizes = bool(ragged), None
+        self.ragged, self.sizes, self.label_size_tab = bool(ragged), None, None
         if self.ragged:                       # the warm-up and the capture run on a table of frames that fill their slots
             self.max_taps = data.default_max_taps(self.frame_shape, self.input_shape) if max_taps is None else int(max_taps)
             table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, self.frame_shape,
                                         self.max_taps, "FramePipeline")
             self.geom = data.geometry_bytes(table).to(dev)
+            # the table holds every image's shape, un-map scalars, thickness and window: the frame ops get the slots' capacity
+            self.image_shape = self.offset = self.scale = self.thickness = None
+            self._slots, self._heat_window = self.frame_shape, dict(window=self.letterbox_image)
+        else:                                 # the same for all images: launch arguments of the frame ops
+            self.image_shape, self._slots, self._heat_window = self.frame_shape, None, dict(letterbox_image=self.letterbox_image)
+            self.thickness = int(max((iw + ih) // np.mean(self.input_shape), 1))                # yolo.py:164
+            self.offset, self.scale = unmap_scalars(self.input_shape, self.frame_shape, self.letterbox_image)
         if self.radar_points is not None:     # the warm-up and the capture run on no points
             table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, fn="FramePipeline")
             self.points, self.views = self.radar_points.buffers(table, dev)
@@ -427,18 +432,20 @@ class FramePipeline:
 
     def _chain(self):
         """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
-        device where a fixed one passes it in the launch arguments: the four frame ops differ, nothing else."""
+        device where a fixed one passes it in the launch arguments: every frame op takes either (`hip._table_call`), so the two
+        chains are one but for the letterbox, which a fixed pipeline runs through `data.device_letterbox`, and for the
+        stretched frame of a fixed pipeline without a letterbox, whose seg window is the whole input."""
         from . import decode, hip            # the library loads with the first pass, not with the package
         (H, W), F, B, dev = self.input_shape, self.frame_shape, self.batch, self.device
+        geom = self.geom if self.ragged else None
         self.flag.zero_()                     # first: the ragged letterbox may raise FLAG_GEOMETRY
         frames = self.frames_u8
         if self.dehaze is not None:           # in front of the letterbox: everything below reads the dehazed frames
             frames = self._dehazed
-            hip.dehaze(self.frames_u8, frames, self._dehaze_ws, geom=self.geom if self.ragged else None, flag=self.flag,
-                       **self.dehaze)
+            hip.dehaze(self.frames_u8, frames, self._dehaze_ws, geom=geom, flag=self.flag, **self.dehaze)
         if self.ragged:
             images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-            hip.letterbox_ragged(frames, None, self.geom, H, W, self.max_taps, images=images, flag=self.flag)
+            hip.letterbox(frames, None, H, W, images=images, geom=geom, max_taps=self.max_taps, flag=self.flag)
         else:
             images, _ = data.device_letterbox(frames, (H, W), letterbox_image=self.letterbox_image, device=dev)
         if self.radar_points is not None:     # the first radar node: points -> self.radar under each frame's window
@@ -453,47 +460,32 @@ class FramePipeline:
         hip.detect_select(pred, self.num_classes, self.conf_thres, rows, scores, classes, ids, counts)
         hip.nms_capped(rows, scores, classes, ids, counts, B, pred.shape[1], self.cap, self.nms_thres, self._nms_ws,
                        self._keep, self._kept, self._kept_rows, self.flag)
-        finished = (self._rows, self._draw_rows, self._offsets, self._det_counts, self.flag)
-        if self.ragged:
-            hip.detect_finish_ragged(self._kept_rows, self._kept, self.geom, self.num_classes, F, *finished)
-        else:
-            hip.detect_finish(self._kept_rows, self._kept, self.num_classes, F, self.offset, self.scale, *finished)
+        hip.detect_finish(self._kept_rows, self._kept, self.num_classes, self.image_shape, self.offset, self.scale, self._rows,
+                          self._draw_rows, self._offsets, self._det_counts, self.flag, geom=geom, capacity=self._slots)
         if self._crops is not None:           # right behind the finish node: from the original frames, which nothing draws on
             hip.crop_boxes(frames, self._draw_rows, self._offsets, self._crops.arena, self._crops.table,
-                           self._crops.summary, geom=self.geom if self.ragged else None, flag=self.flag)
-        if self.ragged:
-            class_map = decode.seg_predict_ragged(seg, self.geom, F, self.flag)
-        elif self.letterbox_image:
-            class_map = decode.seg_predict(seg, (H, W), F)
+                           self._crops.summary, geom=geom, flag=self.flag)
+        if self.ragged or self.letterbox_image:
+            class_map = decode.seg_predict(seg, (H, W), self.image_shape, geom=geom, capacity=self._slots, flag=self.flag)
         else:                                 # the frame was stretched over the whole input: the window is the input
             class_map = torch.empty((B,) + F, dtype=torch.uint8, device=dev)
             ws = torch.empty(hip.seg_predict_workspace_bytes(B, seg.shape[1], H, W), dtype=torch.uint8, device=dev)
             hip.seg_predict(seg.contiguous().float(), 0, 0, H, W, class_map, ws)
         rendered = seg_counts = None
         if self.render:
-            picture = dict(palette=self.seg_palette, mix_type=self.mix_type, alpha=self.alpha, count=True,
-                           box_palette=self.box_palette, flag=self.flag)
             boxes = (self._draw_rows, self._offsets)
             if self.labels is not None:       # the two label launches sit behind the render node
                 hip.label_index(self._rows, self._kept, self._offsets, self.num_classes, self._label_idx, self.flag)
                 boxes += (self._label_idx,)
-                picture["labels"] = self.labels
-                if self.ragged:
-                    picture["label_sizes"] = self.label_size_tab
-            if self.ragged:
-                rendered, seg_counts = rendering.render_frame_ragged(frames, self.geom, class_map, boxes, **picture)
-            else:
-                rendered, seg_counts = rendering.render_frame(frames, class_map, boxes, thickness=self.thickness,
-                                                              device=dev, **picture)
+            rendered, seg_counts = rendering.render_frame(
+                frames, class_map, boxes, palette=self.seg_palette, mix_type=self.mix_type, alpha=self.alpha, count=True,
+                box_palette=self.box_palette, thickness=self.thickness, flag=self.flag, device=dev, labels=self.labels, geom=geom,
+                label_sizes=self.label_size_tab)
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops,
                              dehazed=frames if self.dehaze is not None else None)
         if self.heatmap:
-            if self.ragged:
-                heat = rendering.heatmap_ragged(frames, det, self.geom, (H, W), window=self.letterbox_image,
-                                                alpha=self.heat_alpha, flag=self.flag)
-            else:
-                heat = rendering.heatmap(frames, det, (H, W), letterbox_image=self.letterbox_image, alpha=self.heat_alpha)
-            result.heat_picture, result.heat_mask, result.heat_range = heat
+            result.heat_picture, result.heat_mask, result.heat_range = rendering.heatmap(
+                frames, det, (H, W), alpha=self.heat_alpha, geom=geom, flag=self.flag, **self._heat_window)
         self._tail(result)
         return result
 

@@ -176,9 +176,48 @@ def box_rows(results, image_shape, class_names_or_n, input_shape=None):
     return rows, np.array(offsets, np.int32), thickness, counts
 
 
+def _results(fn, results, B, ih, iw, atlas=None, host=True):
+    """The host half of handing results to a kernel: the checks, and send(dev, flag) -> (rows (N, 5), offsets (B + 1),
+    label_idx (N) or None), int32 tensors on dev.  From the list `non_max_suppression` returns: the rows of `box_rows`, with
+    an atlas the label indices of the float32-product scores (their FLAG_LABEL_SCORE bits OR-ed into flag), packed behind
+    the offsets into one pinned buffer and sent in a single non-blocking copy.  Or from a device pair (rows, offsets) or
+    triple (rows, offsets, label_idx), label_idx (N) int32 = class * 101 + k as `hip.label_index` writes it; an atlas needs
+    the triple.  host=False: device tensors only."""
+    if isinstance(results, tuple) and len(results) in (2, 3) and all(torch.is_tensor(t) for t in results):
+        if atlas is not None and len(results) != 3:
+            raise RuntimeError(f"{fn}: with labels, device results are the triple (rows, offsets, label_idx)")
+        rows, offsets = results[:2]
+        if rows.dtype != torch.int32 or offsets.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 5 or \
+                tuple(offsets.shape) != (B + 1,):
+            raise RuntimeError(f"{fn}: expected int32 rows (N, 5) and offsets ({B + 1},), got {tuple(rows.shape)} "
+                               f"{rows.dtype} and {tuple(offsets.shape)} {offsets.dtype}")
+        keep = results if atlas is not None else (rows, offsets, None)
+        return lambda dev, flag: tuple(None if t is None else t.to(dev).contiguous() for t in keep)
+    if not host:
+        raise RuntimeError(f"{fn}: with a geometry table the results are device tensors (rows, offsets[, label_idx])")
+    if results is None or len(results) != B:
+        raise RuntimeError(f"{fn}: {0 if results is None else len(results)} result entries for {B} frames")
+    host_rows, host_offsets, _, _ = box_rows(results, (ih, iw), MAX_COLORS)
+    if int(np.diff(host_offsets).max(initial=0)) > MAX_BOXES:
+        raise RuntimeError(f"{fn}: more than {MAX_BOXES} boxes in one image")
+    parts, bits, n = [host_offsets, host_rows.reshape(-1)], 0, host_rows.size
+    if atlas is not None:
+        host_idx, bits = _host_label_idx(results, host_rows, atlas)
+        parts.append(host_idx)
+
+    def send(dev, flag):
+        packed = torch.empty(sum(p.size for p in parts), dtype=torch.int32).pin_memory()
+        torch.cat([torch.from_numpy(p) for p in parts], out=packed)
+        packed = packed.to(dev, non_blocking=True)
+        if bits and flag is not None:
+            flag.bitwise_or_(bits)
+        return packed[B + 1:B + 1 + n].view(-1, 5), packed[:B + 1], packed[B + 1 + n:] if atlas is not None else None
+    return send
+
+
 def render_frame(frames_u8, class_map=None, results=None, input_shape=None, palette=None, mix_type=0, alpha=0.7,
                  count=False, box_palette=None, thickness=None, out=None, flag=None, device="cuda", labels=None,
-                 font_size=None):
+                 font_size=None, geom=None, label_sizes=None, fn="render"):
     """The overlay of `seg_render` and the outlines of `draw_boxes` in ONE launch (vrnet_render_u8), boxes over the
     overlay.  frames_u8 (B,ih,iw,3) uint8 RGB original frames (a single (ih,iw,3) frame counts as B = 1), class_map
     (B,ih,iw) uint8 or None, numpy arrays or tensors.  results: None, the list `non_max_suppression` returns (packed by
@@ -192,9 +231,20 @@ def render_frame(frames_u8, class_map=None, results=None, input_shape=None, pale
     synchronise.  labels: a `LabelAtlas` -- the class names and scores of yolo.py:210-224 are drawn over the finished
     picture by `draw_labels` (font_size: default `label_font_size(ih)`); device results are then the triple (rows, offsets,
     label_idx (N) int32 = class * 101 + k, as `hip.label_index` writes it).  With labels=None nothing about the call changes.
-    Returns out, or (out, counts) with counts (B, len(palette)) int64 when count=True.  No host synchronisation."""
+    Returns out, or (out, counts) with counts (B, len(palette)) int64 when count=True.  No host synchronisation.
+    geom: the (B, hip.GEOM_BYTES) device table of `data.frame_geometry` for a batch of images of their own sizes
+    (vrnet_render_ragged_u8).  frames_u8 (B, ihm, iwm, 3) and class_map (B, ihm, iwm) are then padded uint8 DEVICE tensors with
+    image b in the top-left corner of slot b, results device tensors as `hip.detect_finish` leaves them, and the table gives
+    every image its size, its outline thickness and its font size: input_shape, thickness and font_size stay away, and
+    labels need label_sizes, the (B) int32 device table of `atlas.size_table` (the font size of each image as an index into
+    the atlas, -1 for an image without labels).  Image b of the result is `out[b, :ih_b, :iw_b]`, equal to the call without a
+    table on that image alone; every pixel outside it is 0 and is not counted.  out must not be the frames.  flag also
+    receives hip.FLAG_GEOMETRY."""
     from . import hip
-    fn = "render"
+    table = hip._table_call(fn, geom, (("input_shape", input_shape, None), ("thickness", thickness, None),
+                                      ("font_size", font_size, None)), (("label_sizes", label_sizes, None),))
+    if table and not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4):
+        raise RuntimeError(f"{fn}: expected padded uint8 frames (B, ihm, iwm, 3) on a GPU")
     img = _as_u8(frames_u8, "frames", 4, fn)
     if img.dim() != 4 or img.shape[-1] != 3:
         raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
@@ -216,125 +266,48 @@ def render_frame(frames_u8, class_map=None, results=None, input_shape=None, pale
             raise RuntimeError(f"{fn}: out must be a contiguous uint8 tensor of shape {tuple(img.shape)}")
         if cmap is not None and (_overlap(out, img) or _overlap(out, cmap)):
             raise RuntimeError(f"{fn}: out must not alias the frames or the class map when a class map is given")
-    rows = offsets = bpal = label_idx = None
+    bpal = None
     if labels is not None:
         if results is None:
             raise RuntimeError(f"{fn}: labels need results")
-        font_size = _label_setup(labels, font_size, ih, fn)
-        if isinstance(results, tuple) and all(torch.is_tensor(t) for t in results):
-            if len(results) != 3:
-                raise RuntimeError(f"{fn}: with labels, device results are the triple (rows, offsets, label_idx)")
-            label_idx, results = results[2], results[:2]
+        if table and label_sizes is None:
+            raise RuntimeError(f"{fn}: labels need the device triple (rows, offsets, label_idx) and label_sizes")
+        font_size = _label_setup(labels, 0 if table else font_size, ih, fn)
     if results is not None:
-        if isinstance(results, tuple) and len(results) == 2 and all(torch.is_tensor(t) for t in results):
-            rows, offsets = results
-            if rows.dtype != torch.int32 or offsets.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 5 or \
-                    tuple(offsets.shape) != (B + 1,):
-                raise RuntimeError(f"{fn}: expected int32 rows (N, 5) and offsets ({B + 1},), got {tuple(rows.shape)} "
-                                   f"{rows.dtype} and {tuple(offsets.shape)} {offsets.dtype}")
-            host_rows = None
-        else:
-            if len(results) != B:
-                raise RuntimeError(f"{fn}: {len(results)} result entries for {B} frames")
-            host_rows, host_offsets, auto, _ = box_rows(results, (ih, iw), MAX_COLORS, input_shape)
-            if int(np.diff(host_offsets).max(initial=0)) > MAX_BOXES:
-                raise RuntimeError(f"{fn}: more than {MAX_BOXES} boxes in one image")
-            thickness = auto if thickness is None else thickness
-        if thickness is None:
+        if thickness is None and not table:
             if input_shape is None:
                 raise RuntimeError(f"{fn}: boxes need a thickness or the input_shape it follows from")
             thickness = int(max((iw + ih) // np.mean(input_shape), 1))
-        if int(thickness) < 1:
+        if not table and int(thickness) < 1:
             raise RuntimeError(f"{fn}: thickness must be at least 1, got {thickness!r}")
         bpal = _palette(box_palette, det_palette(4) if labels is None else det_palette(labels.num_classes), fn)
         if labels is not None:
             _label_palette(labels, bpal, fn)
-            if host_rows is not None:
-                host_idx, score_bits = _host_label_idx(results, host_rows, labels)
-    img = img.to(device, non_blocking=True).contiguous()
+        send = _results(fn, results, B, ih, iw, labels, host=not table)
+    img = img.to(img.device if table else device, non_blocking=True).contiguous()
     dev = img.device
     cmap = None if cmap is None else cmap.to(dev, non_blocking=True).contiguous()
     with torch.cuda.device(dev):
-        if results is not None and host_rows is not None:
-            # offsets and rows in one pinned buffer: a single non-blocking copy
-            nidx = 0 if labels is None else host_idx.size
-            packed = torch.empty(B + 1 + host_rows.size + nidx, dtype=torch.int32).pin_memory()
-            packed[:B + 1] = torch.from_numpy(host_offsets)
-            packed[B + 1:B + 1 + host_rows.size] = torch.from_numpy(host_rows.reshape(-1))
-            if labels is not None:
-                packed[B + 1 + host_rows.size:] = torch.from_numpy(host_idx)
-            packed = packed.to(dev, non_blocking=True)
-            offsets, rows = packed[:B + 1], packed[B + 1:B + 1 + host_rows.size].view(-1, 5)
-            if labels is not None:
-                label_idx = packed[B + 1 + host_rows.size:]
-                if score_bits and flag is not None:
-                    flag.bitwise_or_(score_bits)
-        elif results is not None:
-            rows, offsets = rows.to(dev).contiguous(), offsets.to(dev).contiguous()
+        rows, offsets, label_idx = (None, None, None) if results is None else send(dev, flag)
         if out is None:
             out = torch.empty((B, ih, iw, 3), dtype=torch.uint8, device=dev)
         counts = torch.empty((B, pal.shape[0]), dtype=torch.int64, device=dev) if count else None
         hip.render(img, cmap, out, palette=None if pal is None else _palette_on(pal, dev), mix_type=mix_type, alpha=alpha,
                    boxes=rows, box_offsets=offsets, box_palette=None if bpal is None else _palette_on(bpal, dev),
-                   thickness=1 if thickness is None else int(thickness), counts=counts, flag=flag)
-        if labels is not None and font_size > 0:
+                   thickness=1 if thickness is None else int(thickness), counts=counts, flag=flag, geom=geom, fn=fn)
+        if labels is not None and (table or font_size > 0):
             blob, records = labels.on(dev)
-            hip.render_labels(out, rows, offsets, _palette_on(bpal, dev), int(thickness), label_idx.to(dev).contiguous(), blob,
-                              records, labels.size_index(font_size), flag=flag)
+            hip.render_labels(out, rows, offsets, _palette_on(bpal, dev), None if table else int(thickness), label_idx, blob, records,
+                              label_sizes if table else labels.size_index(font_size), flag=flag, geom=geom,
+                              fn=fn.replace("render", "render_labels"))
     return (out, counts) if count else out
 
 
 def render_frame_ragged(frames_u8, geom, class_map=None, results=None, palette=None, mix_type=0, alpha=0.7, count=False,
                         box_palette=None, out=None, flag=None, labels=None, label_sizes=None):
-    """`render_frame` for a batch of images of their own sizes (vrnet_render_ragged_u8).  frames_u8 (B, ihm, iwm, 3) and
-    class_map (B, ihm, iwm) (or None) are padded uint8 DEVICE tensors with image b in the top-left corner of slot b; geom is
-    the (B, hip.GEOM_BYTES) device table of `data.frame_geometry`, which gives every image its size and its outline
-    thickness.  results: None or a pair (rows (N, 5) int32, offsets (B + 1) int32) of device tensors, as
-    `hip.detect_finish_ragged` leaves them.  Returns out (B, ihm, iwm, 3), or (out, counts) with count=True: image b is
-    `out[b, :ih_b, :iw_b]`, equal to `render_frame` on that image alone; every pixel outside it is 0 and is not counted.
-    out must not be the frames.  flag also receives hip.FLAG_GEOMETRY.  labels: a `LabelAtlas`; results are then the triple
-    (rows, offsets, label_idx) and label_sizes the (B) int32 device table of `atlas.size_table`: the font size of each image
-    as an index into the atlas, -1 for an image without labels.  No host synchronisation."""
-    from . import hip
-    fn = "render_ragged"
-    img = frames_u8
-    if not (torch.is_tensor(img) and img.is_cuda and img.dtype == torch.uint8 and img.dim() == 4 and img.shape[-1] == 3):
-        raise RuntimeError(f"{fn}: expected padded uint8 frames (B, ihm, iwm, 3) on a GPU")
-    B, ih, iw = img.shape[:3]
-    if class_map is not None and not (torch.is_tensor(class_map) and class_map.dtype == torch.uint8 and
-                                      tuple(class_map.shape) == (B, ih, iw)):
-        raise RuntimeError(f"{fn}: the class map must be a uint8 tensor of shape {(B, ih, iw)}")
-    if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
-        raise RuntimeError(f"{fn}: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
-    if count and class_map is None:
-        raise RuntimeError(f"{fn}: count=True needs a class map")
-    pal = None if class_map is None else _palette(palette, seg_palette(21), fn)
-    rows = offsets = bpal = None
-    label_idx = None
-    if labels is not None:
-        if results is None or len(results) != 3 or label_sizes is None:
-            raise RuntimeError(f"{fn}: labels need the device triple (rows, offsets, label_idx) and label_sizes")
-        _label_setup(labels, 0, ih, fn)
-        label_idx, results = results[2], results[:2]
-    if results is not None:
-        rows, offsets = results
-        bpal = _palette(box_palette, det_palette(4) if labels is None else det_palette(labels.num_classes), fn)
-        if labels is not None:
-            _label_palette(labels, bpal, fn)
-    dev = img.device
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty((B, ih, iw, 3), dtype=torch.uint8, device=dev)
-        counts = torch.empty((B, pal.shape[0]), dtype=torch.int64, device=dev) if count else None
-        hip.render_ragged(img.contiguous(), None if class_map is None else class_map.contiguous(), geom, out,
-                          palette=None if pal is None else _palette_on(pal, dev), mix_type=mix_type, alpha=alpha, boxes=rows,
-                          box_offsets=offsets, box_palette=None if bpal is None else _palette_on(bpal, dev), counts=counts,
-                          flag=flag)
-        if labels is not None:
-            blob, records = labels.on(dev)
-            hip.render_labels_ragged(out, geom, label_sizes, rows, offsets, _palette_on(bpal, dev), label_idx, blob, records,
-                                     flag=flag)
-    return (out, counts) if count else out
+    """`render_frame` with a geometry table, under its earlier name."""
+    return render_frame(frames_u8, class_map, results, None, palette, mix_type, alpha, count, box_palette, out=out, flag=flag,
+                        labels=labels, geom=geom, label_sizes=label_sizes, fn="render_ragged")
 
 
 # matplotlib's "jet" (_cm.py `_jet_data`): per channel the (x, y) break points of a piecewise-linear map
@@ -403,7 +376,7 @@ def _heat_device(outputs, fn):
 
 
 def _heat_window(input_shape, image_shape, letterbox_image):
-    """(window, dx, dy, nw, nh) of the fixed-size call."""
+    """(window, dx, dy, nw, nh) of a call without a geometry table."""
     if not letterbox_image:
         return 0, 0, 0, 0, 0
     from . import decode
@@ -417,22 +390,9 @@ def heatmap_mask(outputs, image_shape, input_shape, letterbox_image=False):
     """Steps :336-342 of yolo.py `detect_heatmap` for a batch: outputs = the three raw detection maps (B, 5 + nc, H/8, W/8),
     (.., H/16, W/16), (.., H/32, W/32) of a network input of input_shape = (H, W), image_shape = (ih, iw) of the original
     frames.  Returns the (B, ih, iw) uint8 mask on the outputs' device.  letterbox_image=False: the reference's resize of the
-    whole level map; True: through the window of `decode.seg_window` (module docstring).  No host synchronisation."""
-    from . import hip
-    fn = "heatmap"
-    B, (H, W) = _heat_levels(outputs, input_shape, fn)
-    ih, iw = int(image_shape[0]), int(image_shape[1])
-    if ih <= 0 or iw <= 0:
-        raise RuntimeError(f"{fn}: bad image_shape {tuple(image_shape)}")
-    window = _heat_window((H, W), (ih, iw), letterbox_image)
-    levels = _heat_device(outputs, fn)
-    dev = levels[0].device
-    with torch.cuda.device(dev):
-        mask = torch.empty((B, ih, iw), dtype=torch.uint8, device=dev)
-        minmax = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        ws = torch.empty(hip.heatmap_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
-        hip.heatmap(levels, H, W, mask, minmax, ws, *window)
-    return mask
+    whole level map; True: through the window of `decode.seg_window` (module docstring).  No host synchronisation.  This is
+    `heatmap` without the picture."""
+    return heatmap(None, outputs, input_shape, letterbox_image, image_shape=image_shape)[1]
 
 
 def _heat_frames(frames_u8, batched, out, fn):
@@ -448,62 +408,52 @@ def _heat_frames(frames_u8, batched, out, fn):
     return img
 
 
-def heatmap(frames_u8, outputs, input_shape, letterbox_image=False, alpha=0.5, cmap=None, out=None):
+def heatmap(frames_u8, outputs, input_shape, letterbox_image=False, alpha=0.5, cmap=None, out=None, geom=None, window=True,
+            flag=None, image_shape=None, fn="heatmap"):
     """yolo.py:288-351 `detect_heatmap` on the device: frames_u8 (B, ih, iw, 3) uint8 RGB original frames (numpy or tensor; a
     single (ih, iw, 3) frame counts as B = 1) and outputs as in `heatmap_mask`.  Returns (picture, mask, minmax): picture
     (B, ih, iw, 3) uint8 = Image.blend(frame, cmap[index(mask)], alpha) with matplotlib's default normalisation per image
     (module docstring), mask (B, ih, iw) uint8, minmax (B, 2) int32 = each mask's (min, max).  cmap: a (256, 3) uint8 table,
     default `jet_lut()`.  out: the device tensor to write the picture into; it must not alias the frames.  No host
-    synchronisation."""
+    synchronisation.  frames_u8=None with image_shape = (ih, iw): no picture (None), the mask and its range alone.
+    geom: the (B, hip.GEOM_BYTES) device table of `data.frame_geometry` for a batch of images of their own sizes
+    (vrnet_heatmap_ragged_f32): frames_u8 (B, ihm, iwm, 3) are then padded uint8 DEVICE slots with image b in the top-left
+    corner.  window=True maps the pixels of image b through its letterbox window (dx, dy, nw, nh) of the table (the whole
+    input for a table made with letterbox_image=False), window=False is the reference's whole-map resize: window says with a
+    table what letterbox_image says without one.  Image b of the results is `[b, :ih_b, :iw_b]`, equal to the call without a
+    table on that image alone; every pixel outside it is 0 and minmax[b] covers the image's own pixels.  flag: an int32
+    device word for hip.FLAG_GEOMETRY, or None."""
     from . import hip
-    fn = "heatmap"
+    table = hip._table_call(fn, geom, (("letterbox_image", letterbox_image, False),), (("window", window, True),))
     B, (H, W) = _heat_levels(outputs, input_shape, fn)
-    img = _heat_frames(frames_u8, True, out, fn)
-    if img.shape[0] != B:
-        raise RuntimeError(f"{fn}: {img.shape[0]} frames for outputs of {B} images")
-    ih, iw = img.shape[1:3]
-    lut = _heat_common(alpha, cmap, fn)
-    window = _heat_window((H, W), (ih, iw), letterbox_image)
+    img = lut = None
+    if frames_u8 is not None:
+        img = _heat_frames(frames_u8, not table, out, fn)
+        if img.shape[0] != B:
+            raise RuntimeError(f"{fn}: {img.shape[0]} frame{' slot' * table}s for outputs of {B} images")
+        image_shape, lut = img.shape[1:3], _heat_common(alpha, cmap, fn)
+    ih, iw = int(image_shape[0]), int(image_shape[1])
+    if ih <= 0 or iw <= 0:
+        raise RuntimeError(f"{fn}: bad image_shape {tuple(image_shape)}")
+    scalars = (1 if window else 0,) if table else _heat_window((H, W), (ih, iw), letterbox_image)
     levels = _heat_device(outputs, fn)
     dev = levels[0].device
-    img = img.to(dev, non_blocking=True).contiguous()
+    if table and img is not None and img.device != dev:
+        raise RuntimeError(f"{fn}: the frames must be on the outputs' device {dev}")
+    img = None if img is None else img.to(dev, non_blocking=True).contiguous()
     with torch.cuda.device(dev):
-        picture = torch.empty((B, ih, iw, 3), dtype=torch.uint8, device=dev) if out is None else out
+        picture = out if out is not None or img is None else torch.empty((B, ih, iw, 3), dtype=torch.uint8, device=dev)
         mask = torch.empty((B, ih, iw), dtype=torch.uint8, device=dev)
         minmax = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        ws = torch.empty(hip.heatmap_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
-        hip.heatmap(levels, H, W, mask, minmax, ws, *window, frames=img, cmap=_palette_on(lut, dev), alpha=alpha, out=picture)
+        need = (hip.heatmap_ragged_workspace_bytes if table else hip.heatmap_workspace_bytes)(B, H, W)
+        hip.heatmap(levels, H, W, mask, minmax, torch.empty(need, dtype=torch.uint8, device=dev), *scalars, frames=img,
+                    cmap=None if lut is None else _palette_on(lut, dev), alpha=alpha, out=picture, geom=geom, flag=flag, fn=fn)
     return picture, mask, minmax
 
 
 def heatmap_ragged(frames_u8, outputs, geom, input_shape, window=True, alpha=0.5, cmap=None, out=None, flag=None):
-    """`heatmap` for a batch of images of their own sizes (vrnet_heatmap_ragged_f32): frames_u8 (B, ihm, iwm, 3) padded uint8
-    DEVICE slots with image b in the top-left corner, geom the (B, hip.GEOM_BYTES) device table of `data.frame_geometry`.
-    window=True maps the pixels of image b through its letterbox window (dx, dy, nw, nh) of the table (the whole input for
-    a table made with letterbox_image=False); window=False is the reference's whole-map resize.  Returns (picture
-    (B, ihm, iwm, 3), mask (B, ihm, iwm), minmax (B, 2)): image b is `[b, :ih_b, :iw_b]`, equal to `heatmap` on that image
-    alone; every pixel outside it is 0 and minmax[b] covers the image's own pixels.  flag: an int32 device word for
-    hip.FLAG_GEOMETRY, or None.  No host synchronisation."""
-    from . import hip
-    fn = "heatmap_ragged"
-    B, (H, W) = _heat_levels(outputs, input_shape, fn)
-    img = _heat_frames(frames_u8, False, out, fn)
-    if img.shape[0] != B:
-        raise RuntimeError(f"{fn}: {img.shape[0]} frame slots for outputs of {B} images")
-    lut = _heat_common(alpha, cmap, fn)
-    levels = _heat_device(outputs, fn)
-    dev = levels[0].device
-    if img.device != dev:
-        raise RuntimeError(f"{fn}: the frames must be on the outputs' device {dev}")
-    ihm, iwm = img.shape[1:3]
-    with torch.cuda.device(dev):
-        picture = torch.empty((B, ihm, iwm, 3), dtype=torch.uint8, device=dev) if out is None else out
-        mask = torch.empty((B, ihm, iwm), dtype=torch.uint8, device=dev)
-        minmax = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        ws = torch.empty(hip.heatmap_ragged_workspace_bytes(B, H, W), dtype=torch.uint8, device=dev)
-        hip.heatmap_ragged(levels, geom, H, W, mask, minmax, ws, window=1 if window else 0, frames=img.contiguous(),
-                           cmap=_palette_on(lut, dev), alpha=alpha, out=picture, flag=flag)
-    return picture, mask, minmax
+    """`heatmap` with a geometry table, under its earlier name."""
+    return heatmap(frames_u8, outputs, input_shape, False, alpha, cmap, out, geom, window, flag, fn="heatmap_ragged")
 
 
 def seg_render(frames_u8, class_map, palette=None, mix_type=0, alpha=0.7, count=False, out=None, flag=None, device="cuda"):
@@ -801,28 +751,9 @@ def draw_labels(picture, results, atlas, input_shape=None, thickness=None, font_
         thickness = int(max((iw + ih) // np.mean(input_shape), 1))
     if int(thickness) < 1:
         raise RuntimeError(f"{fn}: thickness must be at least 1, got {thickness!r}")
-    dev = picture.device
+    send, dev = _results(fn, results, B, ih, iw, atlas), picture.device
     with torch.cuda.device(dev):
-        if isinstance(results, tuple) and all(torch.is_tensor(t) for t in results):
-            if len(results) != 3:
-                raise RuntimeError(f"{fn}: device results are the triple (rows, offsets, label_idx)")
-            rows, offsets, label_idx = (t.to(dev).contiguous() for t in results)
-        else:
-            if results is None or len(results) != B:
-                raise RuntimeError(f"{fn}: {0 if results is None else len(results)} result entries for {B} frames")
-            host_rows, host_offsets, _, _ = box_rows(results, (ih, iw), MAX_COLORS)
-            if int(np.diff(host_offsets).max(initial=0)) > MAX_BOXES:
-                raise RuntimeError(f"{fn}: more than {MAX_BOXES} boxes in one image")
-            host_idx, bits = _host_label_idx(results, host_rows, atlas)
-            packed = torch.empty(B + 1 + host_rows.size + host_idx.size, dtype=torch.int32).pin_memory()
-            packed[:B + 1] = torch.from_numpy(host_offsets)
-            packed[B + 1:B + 1 + host_rows.size] = torch.from_numpy(host_rows.reshape(-1))
-            packed[B + 1 + host_rows.size:] = torch.from_numpy(host_idx)
-            packed = packed.to(dev, non_blocking=True)
-            offsets, rows = packed[:B + 1], packed[B + 1:B + 1 + host_rows.size].view(-1, 5)
-            label_idx = packed[B + 1 + host_rows.size:]
-            if bits and flag is not None:
-                flag.bitwise_or_(bits)
+        rows, offsets, label_idx = send(dev, flag)
         if font_size > 0:
             blob, records = atlas.on(dev)
             hip.render_labels(picture, rows, offsets, _palette_on(bpal, dev), int(thickness), label_idx, blob, records,
