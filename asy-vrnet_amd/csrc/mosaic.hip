@@ -23,7 +23,10 @@
 //   seg         the NEAREST pick per tile, on the mirrored source column when flipped
 //   boxes       per tile and row: flip, map, clip, keep, merge_bboxes at the cut, keep again; compacted across the sources
 //   radar       an integer gather of the tile's stored map
+//   radar points (init, points, resolve)  the radar input from the POINTS of the sources instead: every point of a tile's
+//               source is projected into the tile's window once and competes for the pixels of the tile's quadrant
 #include "augment.h"
+#include "radarpoint.h"
 
 #pragma clang fp contract(off)
 
@@ -42,7 +45,13 @@ typedef struct vrnet_mosaic_rec {
   vrnet_mosaic_tile tile[4];         /* in the reference's tile order */
   unsigned char lut[3][256];         /* hue, saturation, value tables of the colour stage */
 } vrnet_mosaic_rec;
+/* include/vrnet_hip.h: what vrnet_mosaic_radar_points_f32 knows of a source beside the Mosaic record (56 bytes). */
+typedef struct vrnet_radar_source {
+  int count, reserved;               /* the source's points; 0 */
+  float P[12];                       /* (3, 4) row-major: (x, y, z, 1) -> homogeneous continuous pixel coordinates of the source */
+} vrnet_radar_source;
 }
+static_assert(sizeof(vrnet_radar_source) == 56 && alignof(vrnet_radar_source) == 4, "vrnet_radar_source layout");
 static_assert(sizeof(vrnet_mosaic_tile) == 48 && sizeof(vrnet_mosaic_rec) == 976 && alignof(vrnet_mosaic_rec) == 4,
               "vrnet_mosaic_rec layout");
 
@@ -424,6 +433,86 @@ __global__ __launch_bounds__(256) void mosaic_radar_kernel(const MosRadarArgs p)
   for (int c = 0; c < 4; ++c) p.out[(b * 4 + c) * HW + r] = inside ? p.radar[at + c * HW] : 0.f;
 }
 
+// ---- the radar map from the sources' points --------------------------------------------------------------------------------
+// data.mosaic_radar_map: tile t of output image b is data.radar_map of its source's points under the tile's window, cut to
+// the tile's quadrant.  A mirrored tile puts window pixel ix at canvas column dx + nw - 1 - ix (the SOURCE is mirrored, the
+// window stays where it is).  [xa, xb) x [ya, yb) of mos_load is the window cut by the quadrant, which lies inside the canvas:
+// the footprint of a point is clipped to it, so a key plane only ever holds candidates of the tile that owns the pixel and
+// the resolve pass reads the winner's features from that tile's source.
+struct MosPointsArgs {
+  const float* points;               // (S, max_points, 7)
+  const vrnet_radar_source* src;     // (S)
+  const vrnet_mosaic_rec* tab;       // (B)
+  int S, B, max_points, ihm, iwm, H, W, radius;
+  float min_depth;
+  unsigned long long* keys;          // (B, H, W)
+  float* out;                        // (B, 4, H, W)
+  int* flag;                         // or null
+};
+
+__global__ __launch_bounds__(256) void mosaic_radar_points_init_kernel(unsigned long long* keys, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) keys[i] = RM_EMPTY;
+}
+
+// grid (point chunks, 4 tiles, B output images): the record, the tile and the source's entry are the same in every lane
+__global__ __launch_bounds__(256) void mosaic_radar_points_kernel(const MosPointsArgs p) {
+  const int b = blockIdx.z, q = blockIdx.y;
+  bool bad;
+  const MosRec g = mos_load(p.tab, b, p.S, p.ihm, p.iwm, p.H, p.W, bad);
+  const MosTile t = mos_pick(g, q);
+  const int src = t.v[T_SRC];                                   // -1 .. S - 1 (mos_load); -1 for every tile of a bad record
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (first && q == 0 && bad && p.flag) atomicOr(p.flag, VR_FLAG_GEOMETRY);
+  if (src < 0) return;
+  const vrnet_radar_source* s = p.src + src;
+  const int given = s->count, count = vr_clampi(given, 0, p.max_points);
+  if (first && count != given && p.flag) atomicOr(p.flag, VR_FLAG_POINT_COUNT);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= count || t.v[T_XA] >= t.v[T_XB] || t.v[T_YA] >= t.v[T_YB]) return;
+  int ix, iy;
+  float hw;
+  if (!rm_project(s->P, p.points + ((long)src * p.max_points + i) * RM_POINT_FLOATS, p.min_depth, t.v[T_IH], t.v[T_IW], t.v[T_NW],
+                  t.v[T_NH], ix, iy, hw))
+    return;
+  // the centre on the canvas, 64-bit as in radarmap.hip; the covered pixels are inside [xa, xb) x [ya, yb), hence the canvas
+  const long long cx = (long long)t.v[T_DX] + (t.v[T_FLIP] ? t.v[T_NW] - 1 - ix : ix), cy = (long long)t.v[T_DY] + iy;
+  long long x0 = cx - p.radius, x1 = cx + p.radius, y0 = cy - p.radius, y1 = cy + p.radius;
+  x0 = x0 < t.v[T_XA] ? t.v[T_XA] : x0;
+  y0 = y0 < t.v[T_YA] ? t.v[T_YA] : y0;
+  x1 = x1 > t.v[T_XB] - 1 ? t.v[T_XB] - 1 : x1;
+  y1 = y1 > t.v[T_YB] - 1 ? t.v[T_YB] - 1 : y1;
+  if (x0 > x1 || y0 > y1) return;
+  const unsigned long long key = rm_key(hw, i);
+  unsigned long long* plane = p.keys + (long)b * p.H * p.W;
+  for (int yy = (int)y0; yy <= (int)y1; ++yy)
+    for (int xx = (int)x0; xx <= (int)x1; ++xx) atomicMin(plane + (long)yy * p.W + xx, key);
+}
+
+__global__ __launch_bounds__(256) void mosaic_radar_points_resolve_kernel(const MosPointsArgs p) {
+  const long HW = (long)p.H * p.W;
+  const long b = blockIdx.y, r = (long)blockIdx.x * 256 + threadIdx.x;
+  bool bad;
+  const MosRec g = mos_load(p.tab, (int)b, p.S, p.ihm, p.iwm, p.H, p.W, bad);
+  if (r >= HW) return;
+  const int y = (int)(r / p.W), x = (int)(r - (long)y * p.W);
+  const MosTile t = mos_pick(g, mos_tile_of(x >= g.cutx, y >= g.cuty));
+  const unsigned long long key = p.keys[b * HW + r];
+  const unsigned idx = (unsigned)key;
+  unsigned f[4] = {0u, 0u, 0u, 0u};
+  // a key is only ever written inside what its tile shows, by a point below its source's count
+  if (key != RM_EMPTY && idx < (unsigned)p.max_points && mos_shows(t, x, y)) {
+    const unsigned* q = reinterpret_cast<const unsigned*>(p.points) + ((long)t.v[T_SRC] * p.max_points + idx) * RM_POINT_FLOATS + 3;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) f[c] = q[c];
+  }
+  unsigned* out = reinterpret_cast<unsigned*>(p.out);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) out[(b * 4 + c) * HW + r] = f[c];
+}
+
+long mos_points_bytes(int B, int H, int W) { return (((long)B * H * W * 8) + 255) & ~255L; }
+
 bool mos_shape_ok(int S, int B, int ihm, int iwm, int H, int W) {
   return S > 0 && S < (1 << 20) && fm_shape_ok(B, ihm, iwm, H, W) && (long)S * ihm * iwm < (1L << 31) &&
          (long)B * H * W < (1L << 31);
@@ -510,5 +599,43 @@ extern "C" int vrnet_mosaic_radar_f32(const float* radar, int S, const vrnet_mos
   p.out = out; p.flag = flag;
   hipLaunchKernelGGL(mosaic_radar_kernel, dim3((unsigned)vr_cdiv((long)H * W, 256), B), dim3(256), 0, vr_stream(stream), p);
   VR_LAUNCH_CHECK("mosaic_radar");
+  return VR_OK;
+}
+
+extern "C" long vrnet_mosaic_radar_points_workspace(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0 || (long)B * H * W >= (1L << 31)) return -1;
+  return mos_points_bytes(B, H, W);
+}
+
+extern "C" int vrnet_mosaic_radar_points_f32(const float* points, int max_points, int S, const vrnet_radar_source* sources,
+                                             const vrnet_mosaic_rec* mosaic, int B, int ihm, int iwm, int H, int W, int radius,
+                                             float min_depth, float* out, int* flag, void* workspace, long workspace_bytes,
+                                             void* stream) {
+  VR_CHECK_ARG(points && sources && mosaic && out, "mosaic_radar_points: points, sources, mosaic and out are required");
+  VR_CHECK_ARG(mos_shape_ok(S, B, ihm, iwm, H, W) && max_points > 0 && max_points <= (1 << 24) && (long)S * max_points < (1L << 31),
+               "mosaic_radar_points: bad shape (S %d, max_points %d, B %d, slots %d x %d, canvas %d x %d)", S, max_points, B, ihm, iwm, H,
+               W);
+  VR_CHECK_ARG(radius >= 0 && radius <= 8, "mosaic_radar_points: 0 <= radius <= 8, got %d", radius);
+  VR_CHECK_ARG(min_depth > 0.f && min_depth < INFINITY, "mosaic_radar_points: min_depth must be positive and finite, got %g",
+               (double)min_depth);
+  VR_CHECK_ARG((reinterpret_cast<uintptr_t>(mosaic) & 7) == 0 && (reinterpret_cast<uintptr_t>(sources) & 7) == 0,
+               "mosaic_radar_points: the record table and the source table must be 8-byte aligned");
+  const long need = mos_points_bytes(B, H, W);
+  if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7)) {
+    vr_set_error("mosaic_radar_points: workspace %ld < %ld bytes, or not 8-byte aligned", workspace ? workspace_bytes : 0L, need);
+    return VR_ERR_WORKSPACE;
+  }
+  MosPointsArgs p{};
+  p.points = points; p.src = sources; p.tab = mosaic;
+  p.S = S; p.B = B; p.max_points = max_points; p.ihm = ihm; p.iwm = iwm; p.H = H; p.W = W; p.radius = radius;
+  p.min_depth = min_depth;
+  p.keys = static_cast<unsigned long long*>(workspace);
+  p.out = out; p.flag = flag;
+  hipStream_t st = vr_stream(stream);
+  const long n = (long)B * H * W;
+  hipLaunchKernelGGL(mosaic_radar_points_init_kernel, dim3((unsigned)vr_cdiv(n, 256)), dim3(256), 0, st, p.keys, n);
+  hipLaunchKernelGGL(mosaic_radar_points_kernel, dim3((unsigned)vr_cdiv(max_points, 256), 4, B), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(mosaic_radar_points_resolve_kernel, dim3((unsigned)vr_cdiv((long)H * W, 256), B), dim3(256), 0, st, p);
+  VR_LAUNCH_CHECK("mosaic_radar_points");
   return VR_OK;
 }

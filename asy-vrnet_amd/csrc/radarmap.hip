@@ -20,7 +20,7 @@
 //   resolve  one thread per pixel: the key's low word names the winner; its four features go to the four planes as BITS
 //            (NaN payloads survive), 0 where the key is still ~0; consecutive lanes store consecutive x
 // Integer atomics only, and a minimum does not depend on the arrival order: the same bytes on every run.
-#include "common.h"
+#include "radarpoint.h"
 
 #pragma clang fp contract(off)
 
@@ -36,9 +36,6 @@ typedef struct vrnet_radar_view {
 static_assert(sizeof(vrnet_radar_view) == 80 && alignof(vrnet_radar_view) == 4, "vrnet_radar_view layout");
 
 namespace {
-
-constexpr unsigned long long RM_EMPTY = ~0ULL;
-constexpr int RM_POINT_FLOATS = 7;
 
 struct RadarMapArgs {
   const float* points;               // (B, max_points, 7)
@@ -67,17 +64,11 @@ __global__ __launch_bounds__(256) void radar_map_points_kernel(const RadarMapArg
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (bad || i >= count) return;
   const float* q = p.points + ((long)b * p.max_points + i) * RM_POINT_FLOATS;
-  const float x = q[0], y = q[1], z = q[2];
-  const float hu = ((g.P[0] * x + g.P[1] * y) + g.P[2] * z) + g.P[3];
-  const float hv = ((g.P[4] * x + g.P[5] * y) + g.P[6] * z) + g.P[7];
-  const float hw = ((g.P[8] * x + g.P[9] * y) + g.P[10] * z) + g.P[11];
-  // a NaN fails every comparison; |h| < Inf rejects the infinities
-  if (!(hw >= p.min_depth) || !(fabsf(hw) < INFINITY) || !(fabsf(hu) < INFINITY) || !(fabsf(hv) < INFINITY)) return;
-  const float u = hu / hw, v = hv / hw;
-  const float fx = (u * (float)g.nw) / (float)g.iw, fy = (v * (float)g.nh) / (float)g.ih;
-  if (!(fx >= 0.f && fx < (float)g.nw && fy >= 0.f && fy < (float)g.nh)) return;
+  int ix, iy;
+  float hw;
+  if (!rm_project(g.P, q, p.min_depth, g.ih, g.iw, g.nw, g.nh, ix, iy, hw)) return;      // radarpoint.h
   // the centre in canvas coordinates before the flip; 64-bit: a hostile dx + ix must not wrap
-  const long long cx = (long long)g.dx + (long long)floorf(fx), cy = (long long)g.dy + (long long)floorf(fy);
+  const long long cx = (long long)g.dx + ix, cy = (long long)g.dy + iy;
   // covered = the footprint cut by the canvas and by the window; every bound below is inside [0, W) x [0, H)
   const long long wx1 = (long long)g.dx + g.nw - 1, wy1 = (long long)g.dy + g.nh - 1;
   long long x0 = cx - p.radius, x1 = cx + p.radius, y0 = cy - p.radius, y1 = cy + p.radius;
@@ -86,7 +77,7 @@ __global__ __launch_bounds__(256) void radar_map_points_kernel(const RadarMapArg
   x1 = x1 > p.W - 1 ? p.W - 1 : x1;  x1 = x1 > wx1 ? wx1 : x1;
   y1 = y1 > p.H - 1 ? p.H - 1 : y1;  y1 = y1 > wy1 ? wy1 : y1;
   if (x0 > x1 || y0 > y1) return;
-  const unsigned long long key = ((unsigned long long)__float_as_uint(hw) << 32) | (unsigned)i;
+  const unsigned long long key = rm_key(hw, i);
   unsigned long long* plane = p.keys + (long)b * p.H * p.W;
   for (int yy = (int)y0; yy <= (int)y1; ++yy)
     for (int xx = (int)x0; xx <= (int)x1; ++xx)

@@ -1125,11 +1125,13 @@ def radar_view_bytes(views):
     return torch.from_numpy(views.view(np.uint8).reshape(len(views), -1))
 
 
-def pack_points(points, max_points):
+def pack_points(points, max_points, where=None):
     """B arrays of (n_b, 7) float32 rows x, y, z, f0, f1, f2, f3 (None or empty: no points), or a pair (padded (B, n, 7)
     float32 array, counts (B) integers) -> the pinned host pair (B, max_points, 7) float32 and (B,) int32 that `hip.radar_map`
     takes after one non-blocking copy (the counts travel in the view table); unused rows are zero.  Raises RuntimeError naming
-    the image for more than max_points rows, a type other than float32 and a wrong shape -- before anything is written."""
+    the image for more than max_points rows, a type other than float32 and a wrong shape -- before anything is written.
+    where: index -> the name of that point set in a message (default "image b"; the sources of a Mosaic are "image b, tile t")."""
+    where = where or (lambda b: f"image {b}")
     max_points = int(max_points)
     if max_points < 1:
         raise RuntimeError(f"pack_points: max_points must be positive, got {max_points}")
@@ -1145,7 +1147,7 @@ def pack_points(points, max_points):
             raise RuntimeError(f"pack_points: counts are {padded.shape[0]} integers, got {cnt.dtype} {cnt.shape}")
         for b, n in enumerate(cnt.tolist()):
             if not 0 <= n <= padded.shape[1]:
-                raise RuntimeError(f"pack_points: image {b}: counts says {n} points, the padded buffer holds {padded.shape[1]}")
+                raise RuntimeError(f"pack_points: {where(b)}: counts says {n} points, the padded buffer holds {padded.shape[1]}")
         points = [padded[b, :n] for b, n in enumerate(cnt.tolist())]
     elif not isinstance(points, (list, tuple)):
         raise RuntimeError("pack_points: expected a list of (n, 7) float32 arrays, or a pair (padded (B, n, 7) array, counts)")
@@ -1159,11 +1161,11 @@ def pack_points(points, max_points):
             rows.append(None)
             continue
         if a.dtype != np.float32:
-            raise RuntimeError(f"pack_points: image {b}: points are float32 rows x, y, z, f0, f1, f2, f3, got {a.dtype}")
+            raise RuntimeError(f"pack_points: {where(b)}: points are float32 rows x, y, z, f0, f1, f2, f3, got {a.dtype}")
         if a.ndim != 2 or a.shape[1] != 7:
-            raise RuntimeError(f"pack_points: image {b}: expected (n, 7) rows x, y, z, f0, f1, f2, f3, got {a.shape}")
+            raise RuntimeError(f"pack_points: {where(b)}: expected (n, 7) rows x, y, z, f0, f1, f2, f3, got {a.shape}")
         if a.shape[0] > max_points:
-            raise RuntimeError(f"pack_points: image {b} has {a.shape[0]} points, above max_points = {max_points}")
+            raise RuntimeError(f"pack_points: {where(b)} has {a.shape[0]} points, above max_points = {max_points}")
         rows.append(a)
     B = len(rows)
     out = torch.zeros((B, max_points, 7), dtype=torch.float32)
@@ -1283,6 +1285,104 @@ def device_radar_map(points, sizes, input_shape, calib, letterbox_image=True, ra
             out = torch.empty((B, 4, H, W), dtype=torch.float32, device=dev)
         hip.radar_map(packed.to(dev, non_blocking=True), radar_view_bytes(views).to(dev, non_blocking=True), H, W, radius,
                       float(md), out, flag=flag)
+    return out
+
+
+# ---- radar points under Mosaic: host statement of the radar-points kernels of csrc/mosaic.hip ----------------------------------
+# vrnet_radar_source of include/vrnet_hip.h, one record per SOURCE (56 bytes): what the kernel needs beside the Mosaic record
+RADAR_SOURCE_DTYPE = np.dtype([("count", "<i4"), ("reserved", "<i4"), ("P", "<f4", (12,))])
+
+
+def radar_sources(calib, counts):
+    """The packed per-source table of `hip.mosaic_radar_points`: calib (3, 4) or (S, 3, 4), counts (S) points per source -> an
+    (S,) RADAR_SOURCE_DTYPE array (`radar_source_bytes` of it is what the device takes).  Host only."""
+    counts = np.asarray(counts.cpu().numpy() if torch.is_tensor(counts) else counts)
+    if counts.ndim != 1 or len(counts) == 0 or not np.issubdtype(counts.dtype, np.integer):
+        raise RuntimeError(f"radar_sources: counts are S integers, one per source, got {counts.dtype} {counts.shape}")
+    S = len(counts)
+    out = np.zeros(S, RADAR_SOURCE_DTYPE)
+    out["count"] = counts
+    out["P"] = check_calib(calib, S, "radar_sources").reshape(S, 12)
+    return out
+
+
+def radar_source_bytes(sources):
+    """A `radar_sources` table as the (S, hip.RADAR_SOURCE_BYTES) uint8 host tensor the device takes; it shares the table's memory."""
+    return torch.from_numpy(sources.view(np.uint8).reshape(len(sources), -1))
+
+
+def mosaic_radar_map(points, calib, sizes, input_shape, rec, radius=0, min_depth=0.1):
+    """The radar input (4, H, W) float32 of ONE Mosaic image from the radar POINTS of its sources, where `mosaic_sample` gathers
+    from finished maps -- this project's own definition, stated through `radar_map` and nothing else.  points: S arrays of
+    (n, 7) float32 rows, indexed by the tiles' src (None or empty: no points); calib (3, 4) or (S, 3, 4), the projection of each
+    source's own frame; sizes (S, 2) = (ih, iw) of the sources; rec: one MOSAIC_DTYPE record.  For every tile t with src >= 0:
+        window = (nw, nh, W - dx - nw if tile.flip else dx, dy)
+        m = radar_map(points[src], P[src], (tile.ih, tile.iw), (H, W), window, flip=bool(tile.flip), radius, min_depth)
+        out[:, ys, xs] = m[:, ys, xs]
+    with ys, xs the tile's quadrant as in `mosaic_sample` (tile 0: x < cutx, y < cuty; 1: x < cutx, y >= cuty; 2: x >= cutx, y >=
+    cuty; 3: x >= cutx, y < cuty), and 0 elsewhere.  The shifted window puts a mirrored source at X = dx + nw - 1 - ix: that is
+    the tile flip of `mosaic_sample` (wx' = nw - 1 - wx, the SOURCE is mirrored), not a mirror of the canvas, and the window's
+    extent stays [dx, dx + nw - 1].  What follows from the rule:
+        a kept point whose centre lies outside its quadrant still covers the quadrant's pixels within radius;
+        each pixel receives candidates from one source only, its quadrant's tile's;
+        the winner is the smallest hw, then the lowest index within that source;
+        a non-mosaicked record (cut (W, H), tile 0 only) is `radar_map` under tile 0's window.
+    Every point moves exactly once, where the gather of a map rasterised under the source's letterbox window drops points of
+    a shrunk tile and duplicates those of an enlarged one.  The record is taken as it is: `check_mosaic_table` validates."""
+    H, W = (int(v) for v in input_shape)
+    own = frame_sizes(sizes, fn="mosaic_radar_map")
+    S = len(own)
+    P = check_calib(calib, S, "mosaic_radar_map")
+    if len(points) != S:
+        raise RuntimeError(f"mosaic_radar_map: {len(points)} point sets for {S} sources")
+    cutx, cuty = int(rec["cutx"]), int(rec["cuty"])
+    out = np.zeros((4, H, W), np.float32)
+    for t, tile in enumerate(rec["tile"]):
+        src = int(tile["src"])
+        if src < 0:
+            continue
+        ys = slice(cuty, H) if t in (1, 2) else slice(0, cuty)
+        xs = slice(cutx, W) if t in (2, 3) else slice(0, cutx)
+        nw, nh, dx, dy, flip = (int(tile[k]) for k in ("nw", "nh", "dx", "dy", "flip"))
+        pts = points[src]
+        pts = np.zeros((0, 7), np.float32) if pts is None or len(pts) == 0 else np.asarray(pts)
+        m = radar_map(pts, P[src], (int(tile["ih"]), int(tile["iw"])), (H, W), (nw, nh, W - dx - nw if flip else dx, dy), bool(flip),
+                      radius, min_depth)
+        out[:, ys, xs] = m[:, ys, xs]
+    return out
+
+
+def device_mosaic_radar_map(points, sizes, input_shape, calib, params, radius=0, min_depth=0.1, max_points=None, capacity=None,
+                            device="cuda", out=None, flag=None):
+    """`mosaic_radar_map` for a batch ON THE DEVICE (vrnet_mosaic_radar_points_f32, three launches): points of the S sources
+    as `pack_points` takes them, sizes (S, 2) = (ih, iw) of the sources, calib (3, 4) or (S, 3, 4), params a (B,) MOSAIC_DTYPE
+    table (`mosaic_params`, or `mosaic_record`s written by hand), validated here (`check_mosaic_table`) -> (B, 4, H, W) float32
+    on the device, bit for bit what `mosaic_radar_map` gives per output image.  max_points: the capacity of the point buffer
+    (default: the largest count); capacity: (ihm, iwm) by which the records are judged (default: the largest source).  flag: an
+    int32 device word that receives hip.FLAG_GEOMETRY / hip.FLAG_POINT_COUNT (never, for inputs that passed the checks here).
+    The points and the tables are copied non_blocking; no host synchronisation."""
+    from . import hip
+    fn = "device_mosaic_radar_map"
+    radius, md = check_radar_rule(radius, min_depth, fn)
+    H, W = (int(v) for v in input_shape)
+    if max_points is None:
+        if isinstance(points, tuple) and len(points) == 2 and getattr(points[0], "ndim", 0) == 3:
+            max_points = max(int(points[0].shape[1]), 1)
+        else:
+            max_points = max([1] + [0 if a is None else len(a) for a in points])
+    packed, counts = pack_points(points, max_points)
+    S = len(counts)
+    own = frame_sizes(sizes, S, fn)
+    if capacity is None:
+        capacity = (int(own[:, 0].max()), int(own[:, 1].max()))
+    table = check_mosaic_table(params, (H, W), own, capacity, None, fn)
+    sources = radar_sources(check_calib(calib, S, fn), counts.numpy())
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty((len(table), 4, H, W), dtype=torch.float32, device=dev)
+        hip.mosaic_radar_points(packed.to(dev, non_blocking=True), radar_source_bytes(sources).to(dev, non_blocking=True),
+                                mosaic_bytes(table).to(dev, non_blocking=True), capacity, H, W, radius, float(md), out, flag=flag)
     return out
 
 

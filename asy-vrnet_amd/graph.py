@@ -211,8 +211,25 @@ class _PlainFrames:
         getattr(hip, self.ops[1])(step.frame_labels_u8, table, h, w, step.ns, png_out=step.png, onehot=step.onehot, flag=step.flag)
         getattr(hip, self.ops[2])(step.boxes, step.box_counts, table, step.capacity, h, w, targets=step.labels, counts_out=step.counts,
                                   flag=step.flag)
-        if self.ops[3] and step.radar_points is None:        # radar points: vrnet_radar_map_f32 writes step.r instead
+        if step.radar_points is not None:                    # radar points: projected into step.r, no finished maps to move
+            self.points(step, table)
+        elif self.ops[3]:
             getattr(hip, self.ops[3])(step.radar_in, table, step.capacity, out=step.r, flag=step.flag)
+
+    # radar points (step.radar_points, an `infer.RadarPoints` over the step's sources): the per-call device table beside the
+    # points, the key workspace and the launch
+    def point_table(self, step, table, checked):
+        """The uint8 host table `points` reads beside the points, from the call's table and the (projection, counts) pair
+        `RadarPoints.validate(points, None)` returned: one view record per image, under the window its frame goes through."""
+        return step.radar_points.views(table, checked)
+
+    def point_workspace_bytes(self, step):
+        return hip.radar_map_workspace_bytes(step.batch, *step.hw)
+
+    def points(self, step, table):
+        """vrnet_radar_map_f32: the points of each image under the window (and flip) its frame just went through."""
+        rp = step.radar_points
+        hip.radar_map(step.points, step.views, *step.hw, rp.radius, float(rp.min_depth), step.r, flag=step.flag, ws=step._radar_ws)
 
 
 class _AugmentFrames(_PlainFrames):
@@ -287,6 +304,20 @@ class _MosaicFrames(_AugmentFrames):
                                        capacity=step.capacity, max_taps=step.max_taps, fn="TrainStep", **step.mosaic)
         return table
 
+    # radar points: the windows are the Mosaic table's own, which the kernel reads where the other Mosaic kernels do; the
+    # table beside the points carries only what a SOURCE adds, its count and its projection
+    def point_table(self, step, table, checked):
+        return data.radar_source_bytes(data.radar_sources(checked[0], checked[1].numpy()))
+
+    def point_workspace_bytes(self, step):
+        return hip.mosaic_radar_points_workspace_bytes(step.batch, *step.hw)
+
+    def points(self, step, table):
+        """vrnet_mosaic_radar_points_f32: the points of every tile's source under the tile's window, inside its quadrant."""
+        rp = step.radar_points
+        hip.mosaic_radar_points(step.points, step.views, table, step.capacity, *step.hw, rp.radius, float(rp.min_depth), step.r,
+                                flag=step.flag, ws=step._radar_ws)
+
 
 class TrainStep(GraphedStep):
     """One captured training step: forward, the reference's loss (`losses.training_loss`: SimOTA YOLO loss, focal or CE,
@@ -354,8 +385,7 @@ class TrainStep(GraphedStep):
     `data.MOSAIC_DTYPE` table instead (any tile may name any of the 4 B sources; the generator is then not advanced);
     `aug_table` keeps the last table.  Host validation as before, with one more rule: the sources of an output image together
     bring at most max_gt boxes -- conservative, since the cut may drop some, but known before anything is enqueued.  mosaic
-    without from_frames, with radar_points (a tile needs a clip rectangle the view record does not carry: a follow-up) or
-    with letterbox_image=False raises at construction.
+    without from_frames or with letterbox_image=False raises at construction.
 
     With from_frames=True and radar_points=max_points the step takes radar POINTS where it took maps:
 
@@ -369,6 +399,21 @@ class TrainStep(GraphedStep):
     every point moves exactly once, where the gather of a finished map duplicates or drops points.  Points and the view
     table go up through fresh pinned staging tensors; the kernel's bits (hip.FLAG_GEOMETRY, hip.FLAG_POINT_COUNT) join the
     step's flag word.  radar_points without from_frames raises.
+
+    With mosaic AND radar_points the points are those of the 4 B SOURCES and every tile's points are projected into the tile's
+    own window (`data.mosaic_radar_map` is the rule):
+
+        step = TrainStep(..., from_frames=True, capacity=(ihm, iwm), mosaic=True, radar_points=4096, calib=P)
+        res = step(frames, points, boxes, labels, sizes=None, aug=None, calib=None)
+
+    points: 4 B point sets, one per source; calib: (3, 4) or (4 B, 3, 4), one projection per SOURCE.  The static buffers are the
+    (4 B, max_points, 7) points, the (4 B, hip.RADAR_SOURCE_BYTES) table of counts and projections and the key workspace; no
+    (4 B, 4, H, W) maps exist or cross PCIe.  vrnet_mosaic_radar_points_f32 (three launches) stands where vrnet_mosaic_radar_f32
+    stood and reads the step's Mosaic table (`step.aug`) as the other Mosaic kernels do, so drawn tables, aug= tables and
+    `mosaic_prob` behave as with maps.  An error that names a point set names its source as "image b, tile t".  The one
+    asymmetry against the plain and the augment mode: here the projection is REQUIRED at construction (a per-call calib still
+    overrides it).  `TrainStep(mosaic=True, radar_points=N)` without one has always been refused at construction and stays
+    refused: such a step could otherwise only fail at its first call, after the warm-up and the capture were paid for.
 
     Two kinds of graph.  The forward / backward graph(s) are GraphedStep's (three segments under data parallelism, the
     all-reduces between them); the loss closure is `losses.training_loss_packed` on the static buffers, followed by the
@@ -401,18 +446,24 @@ class TrainStep(GraphedStep):
         if mosaic is not None and mosaic is not False:
             if not from_frames:
                 raise RuntimeError("TrainStep: mosaic needs from_frames=True (the tiles are cut from the raw frames)")
-            if radar_points is not None:
-                raise RuntimeError("TrainStep: mosaic with radar_points is not built: a tile needs a clip rectangle that "
-                                   "vrnet_radar_view does not carry (a follow-up); give radar maps")
+            if radar_points is not None and calib is None:
+                raise RuntimeError("TrainStep: mosaic with radar_points needs calib= at construction: one (3, 4) projection, or "
+                                   "(4 * batch, 3, 4), one per SOURCE (a call may still bring its own)")
             if not letterbox_image:
                 raise RuntimeError("TrainStep: mosaic places the tiles itself; letterbox_image=False does not apply")
         if radar_points is not None and not from_frames:
             raise RuntimeError("TrainStep: radar_points needs from_frames=True (the points are projected into the frame's window)")
         if radar_points is None and (calib is not None or radar_radius != 0 or radar_min_depth != 0.1):
             raise RuntimeError("TrainStep: calib, radar_radius and radar_min_depth belong to radar_points=max_points")
-        from .infer import RadarPoints
+        self.augment = None if augment is None or augment is False else ({} if augment is True else dict(augment))
+        self.mosaic = None if mosaic is None or mosaic is False else ({} if mosaic is True else dict(mosaic))
+        if self.mosaic is not None:
+            self.mosaic_prob = float(self.mosaic.pop("prob", 1.0))      # read at every call: the caller may assign it
+        self.mode = _MosaicFrames() if self.mosaic is not None else _AugmentFrames() if self.augment is not None else _PlainFrames()
+        self.sources = int(batch) * self.mode.per_image
+        from .infer import RadarPoints                   # one point set and one projection per SOURCE
         self.radar_points = None if radar_points is None else RadarPoints(radar_points, radar_radius, radar_min_depth, calib,
-                                                                          int(batch), "TrainStep")
+                                                                          self.sources, "TrainStep", self.mode.per_image)
         if augment is not None and augment is not False and not from_frames:
             raise RuntimeError("TrainStep: augment needs from_frames=True (the augmentation starts from the raw frames)")
         if augment is not None and augment is not False and not letterbox_image:
@@ -428,12 +479,6 @@ class TrainStep(GraphedStep):
         self.batch, self.hw, self.ns, self.max_gt = int(batch), (h, w), ns, int(max_gt)
         self.focal_loss, self.dice_loss, self.f_score, self.from_bytes = bool(focal_loss), bool(dice_loss), bool(f_score), bool(from_bytes)
         self.from_frames = bool(from_frames)
-        self.augment = None if augment is None or augment is False else ({} if augment is True else dict(augment))
-        self.mosaic = None if mosaic is None or mosaic is False else ({} if mosaic is True else dict(mosaic))
-        if self.mosaic is not None:
-            self.mosaic_prob = float(self.mosaic.pop("prob", 1.0))      # read at every call: the caller may assign it
-        self.mode = _MosaicFrames() if self.mosaic is not None else _AugmentFrames() if self.augment is not None else _PlainFrames()
-        self.sources = int(batch) * self.mode.per_image
         self.names = ("total", "loss_det", "loss_seg") + (("f_score",) if self.f_score else ())
         with torch.cuda.device(dev):
             self.labels = torch.zeros((batch, max(self.max_gt, 1), 5), dtype=torch.float32, device=dev)
@@ -469,9 +514,12 @@ class TrainStep(GraphedStep):
             self._aug_rng = np.random.RandomState(aug_seed)
             self.aug_table = table
         setattr(self, mode.table_attr, mode.to_bytes(table).to(dev))
-        if self.radar_points is not None:    # no points in the warm-up and the capture
-            self.points, self.views = self.radar_points.buffers(table, dev)
-            self._radar_ws = self.radar_points.workspace(self.hw, dev)
+        if self.radar_points is not None:    # no points in the warm-up and the capture: every count is 0
+            rp = self.radar_points
+            P = rp.calib if rp.calib is not None else np.zeros((S, 3, 4), np.float32)
+            self.points = torch.zeros((S, rp.max_points, 7), dtype=torch.float32, device=dev)
+            self.views = mode.point_table(self, table, (P, torch.zeros(S, dtype=torch.int32))).to(dev)
+            self._radar_ws = torch.empty(mode.point_workspace_bytes(self), dtype=torch.uint8, device=dev)
         elif mode.ops[3]:                    # the prologue moves the radar maps: a call copies them here (mode.radar_dst)
             self.radar_in = torch.zeros((S, 4, h, w), dtype=torch.float32, device=dev)
         self.frames_u8 = torch.zeros((S, ihm, iwm, 3), dtype=torch.uint8, device=dev)
@@ -486,10 +534,6 @@ class TrainStep(GraphedStep):
             hip.batch_formats(self.images_u8, self.labels_u8, self.ns, images=self.x, png_out=self.png, onehot=self.onehot)
         elif self.from_frames:
             self.mode.launch(self)
-        if self.radar_points is not None:    # the points of each image under the window (and flip) its frame just went through
-            h, w = self.hw
-            hip.radar_map(self.points, self.views, h, w, self.radar_points.radius, float(self.radar_points.min_depth), self.r,
-                          flag=self.flag, ws=self._radar_ws)
 
     def _loss(self, det, seg):
         total, ldet, lseg = losses.training_loss_packed(self.yolo_loss, det, seg, self.labels, self.counts, self.max_gt, self.png,
@@ -584,7 +628,7 @@ class TrainStep(GraphedStep):
         packed, counts = data.pack_boxes(boxes, self.max_gt)              # raises, naming the image
         table = self.mode.finish(self, own, table, counts)
         if self.radar_points is not None:
-            radar = radar[0], self.radar_points.views(table, radar[1])
+            radar = radar[0], self.mode.point_table(self, table, radar[1])
         return items, labs, own, table, radar, packed, counts
 
     def __call__(self, images, radar, targets, pngs, seg_labels=None, sizes=None, aug=None, calib=None):

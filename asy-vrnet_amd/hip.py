@@ -160,6 +160,8 @@ _SIGS = {
     "vrnet_mosaic_radar_f32": ([P, I, P, I, I, I, I, I, P, P, P], I),
     "vrnet_radar_map_workspace": ([I, I, I], L),
     "vrnet_radar_map_f32": ([P, I, P, I, I, I, I, F, P, P, P, L, P], I),
+    "vrnet_mosaic_radar_points_workspace": ([I, I, I], L),
+    "vrnet_mosaic_radar_points_f32": ([P, I, I, P, P, I, I, I, I, I, I, F, P, P, P, L, P], I),
     "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
     "vrnet_render_labels_u8": ([P, I, I, I, P, P, I, P, I, I, P, P, L, P, I, I, I, P, P], I),
     "vrnet_render_labels_ragged_u8": ([P, P, P, I, I, I, P, P, I, P, I, P, P, L, P, I, I, P, P], I),
@@ -1614,6 +1616,44 @@ def radar_map(points, views, H, W, radius, min_depth, out, flag=None, ws=None):
         raise RuntimeError(f"radar_map: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
     _check(_lib.vrnet_radar_map_f32(ptr(points), max_points, _views(views, B, "radar_map"), B, H, W, int(radius), float(min_depth),
                                     ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), "radar_map")
+    return out
+
+
+# ---- radar points under Mosaic (include/vrnet_hip.h "radar points under Mosaic") ----------------------------------------------
+RADAR_SOURCE_BYTES = 56  # sizeof(vrnet_radar_source)
+
+
+def mosaic_radar_points_workspace_bytes(B, H, W):
+    return _lib.vrnet_mosaic_radar_points_workspace(B, H, W)
+
+
+def mosaic_radar_points(points, sources, table, capacity, H, W, radius, min_depth, out, flag=None, ws=None):
+    """The radar points of S sources -> the radar input of B Mosaic images (vrnet_mosaic_radar_points_f32): points
+    (S, max_points, 7) f32 rows x, y, z, f0..f3, sources the (S, RADAR_SOURCE_BYTES) table of counts and projections
+    (`data.radar_sources` packs it), table the (B, MOSAIC_BYTES) Mosaic table the other Mosaic calls take, capacity = (ihm, iwm)
+    of the frames' slots, by which the records are judged -> out (B, 4, H, W) f32, what `data.mosaic_radar_map` gives per output
+    image, bit for bit; radius 0..8, min_depth > 0; flag (1) int32 or None: FLAG_GEOMETRY for a record that had to be clamped
+    (its whole image is 0), FLAG_POINT_COUNT for a clamped count; ws: mosaic_radar_points_workspace_bytes(B, H, W) bytes.
+    Three launches.  Returns out."""
+    fn = "mosaic_radar_points"
+    if points is None or points.dim() != 3 or points.shape[2] != 7 or points.shape[1] < 1:
+        raise RuntimeError(f"{fn}: expected points (S, max_points, 7)")
+    S, max_points = points.shape[:2]
+    H, W = int(H), int(W)
+    if sources is None or sources.dtype != torch.uint8 or tuple(sources.shape) != (S, RADAR_SOURCE_BYTES) or \
+            not sources.is_contiguous() or not sources.is_cuda or sources.data_ptr() % 8:
+        raise RuntimeError(f"{fn}: the source table must be a contiguous, 8-byte aligned uint8 GPU tensor of shape ({S}, {RADAR_SOURCE_BYTES})")
+    _, tab, B = _table(_MOSAIC, table, S, fn)
+    if out is None:
+        raise RuntimeError(f"{fn}: out is required")
+    _tensors(fn, ((points, (S, max_points, 7), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
+    need = _lib.vrnet_mosaic_radar_points_workspace(B, H, W)
+    if ws is None:
+        ws = _ws.get(need, points.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"{fn}: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    _check(_lib.vrnet_mosaic_radar_points_f32(ptr(points), max_points, S, ptr(sources), tab, B, int(capacity[0]), int(capacity[1]), H, W,
+                                              int(radius), float(min_depth), ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), fn)
     return out
 
 

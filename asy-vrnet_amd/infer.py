@@ -93,12 +93,15 @@ def validate_radar(radar, batch, input_shape):
 class RadarPoints:
     """The radar half of a pipeline built with radar_points: what every call brings in place of finished maps.  max_points is
     the capacity of the static point buffer, radius / min_depth the rule of `data.radar_map`, calib the default (3, 4) or
-    (B, 3, 4) projection (a call may bring its own).  Host only, but for `buffers` and `workspace`."""
+    (B, 3, 4) projection (a call may bring its own).  per_image > 1: the batch is that many SOURCES per output image (Mosaic),
+    and a message names point set s as "image s // per_image, tile s % per_image".  Host only, but for `buffers` and
+    `workspace`."""
 
-    def __init__(self, max_points, radius=0, min_depth=0.1, calib=None, batch=1, fn="FramePipeline"):
+    def __init__(self, max_points, radius=0, min_depth=0.1, calib=None, batch=1, fn="FramePipeline", per_image=1):
         if isinstance(max_points, bool) or not isinstance(max_points, (int, np.integer)) or not 1 <= int(max_points) <= 1 << 24:
             raise RuntimeError(f"{fn}: radar_points is the capacity of the point buffer, an integer in 1..{1 << 24}, got {max_points!r}")
         self.max_points, self.batch, self.fn = int(max_points), int(batch), fn
+        self.where = None if per_image == 1 else (lambda s: f"image {s // per_image}, tile {s % per_image}")
         self.radius, self.min_depth = data.check_radar_rule(radius, min_depth, fn)
         self.calib = None if calib is None else data.check_calib(calib, self.batch, fn)
 
@@ -111,7 +114,7 @@ class RadarPoints:
         P = self.calib if calib is None else data.check_calib(calib, self.batch, self.fn)
         if P is None:
             raise RuntimeError(f"{self.fn}: radar points need a projection: calib=(3, 4) or (B, 3, 4), here or at construction")
-        packed, counts = data.pack_points(points, self.max_points)
+        packed, counts = data.pack_points(points, self.max_points, self.where)
         if len(counts) != self.batch:
             raise RuntimeError(f"{self.fn}: {len(counts)} point sets for a batch of {self.batch}")
         if table is None:                    # the caller's table follows: `views` finishes the pair

@@ -1211,6 +1211,36 @@ long vrnet_radar_map_workspace(int B, int H, int W);
 int vrnet_radar_map_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W, int radius,
                         float min_depth, float* out, int* flag, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- radar points under Mosaic (csrc/mosaic.hip; the projection of a point: csrc/radarpoint.h) ---------------------------------
+ * Added within ABI 11: new symbols and one new record layout (vrnet_radar_source) only, no existing signature, layout or kernel
+ * behaviour changed; hip.py binds every declared symbol at import.
+ * The radar input of B Mosaic images from the POINTS of their S sources (host statement: data.mosaic_radar_map), in place of
+ * vrnet_mosaic_radar_f32's gather from finished maps.  points (S, max_points, 7) fp32 rows as vrnet_radar_map_f32 takes them;
+ * sources: count and projection per source; mosaic: the (B) record table the other Mosaic kernels read, judged by the same
+ * rule with the same S, ihm, iwm, H, W (a record that had to be clamped gives a zero map for its WHOLE output image and sets
+ * bit 256, VR_FLAG_GEOMETRY).  For tile t of output image b with src >= 0, every point i < count[src] is projected by
+ * vrnet_radar_map_f32's arithmetic with the source's P, the tile's (ih, iw) and its window (nw, nh) to the window pixel
+ * (ix, iy); its centre is canvas pixel (dx + (flip ? nw - 1 - ix : ix), dy + iy) -- the SOURCE is mirrored, the window stays --
+ * and it covers the pixels within `radius` of the centre that lie inside the window AND inside the tile's quadrant (hence
+ * inside the canvas).  A kept point centred outside its quadrant still covers the quadrant's pixels within radius.  Per pixel
+ * the covering point with the smallest hw wins, the lowest index among equals; all candidates of a pixel come from the one
+ * tile that owns it.  out (B, 4, H, W) receives the winner's four features as bits, 0 where no point lands, where the tile
+ * is absent (src = -1) and outside the tile's window.
+ * Three launches as vrnet_radar_map_f32: keys (B, H, W) uint64 = ~0; one thread per (output image, tile, point), a 64-bit
+ * atomic minimum per covered pixel; one thread per pixel resolving its key through its quadrant's tile.  Integer atomics
+ * only: the same bytes on every run; nothing carries over between calls.  No host synchronisation, no allocation;
+ * capturable.  workspace: vrnet_mosaic_radar_points_workspace(B, H, W) bytes, 8-byte aligned.  A count outside
+ * [0, max_points] of a source that a present tile names is clamped and sets bit 1024 (VR_FLAG_POINT_COUNT); the count of a
+ * source no tile names is not read.  radius 0..8, min_depth positive and finite.  flag may be NULL. */
+typedef struct vrnet_radar_source {
+  int count, reserved;               /* the source's points; 0 */
+  float P[12];                       /* the (3, 4) projection of the source's own (ih, iw) frame, row-major */
+} vrnet_radar_source;                /* 56 bytes; the table must be 8-byte aligned */
+long vrnet_mosaic_radar_points_workspace(int B, int H, int W);
+int vrnet_mosaic_radar_points_f32(const float* points, int max_points, int S, const vrnet_radar_source* sources,
+                                  const vrnet_mosaic_rec* mosaic, int B, int ihm, int iwm, int H, int W, int radius,
+                                  float min_depth, float* out, int* flag, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- class names and scores on the rendered detections (csrc/labels.hip) -----------------------------------------------
  * Added within ABI 11: new symbols only, no existing signature, layout or kernel behaviour changed; hip.py binds every
  * declared symbol at import.

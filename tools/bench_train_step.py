@@ -35,6 +35,12 @@ TrainStep(from_frames=True, augment=True) on B frames and the six-launch prologu
 on 4 B frames, on their own and inside the whole step (copies and the host's draw included).
 
     python tools/bench_train_step.py --mosaic --frames 1080x1920 [--phi l]
+
+--mosaic-points N (with --frames) times the two radar inputs of the Mosaic step against each other the same way: finished maps
+(4 B maps of (4, S, S) floats a step, vrnet_mosaic_radar_f32) and radar POINTS (4 B clouds of N points, vrnet_mosaic_radar_points_f32,
+radius --radius), the prologues on their own and the whole steps, copies, the host's draw and the packing of the points included.
+
+    python tools/bench_train_step.py --mosaic-points 4096 --frames 1080x1920 [--phi l]
 """
 import argparse
 import math
@@ -311,6 +317,93 @@ def mosaicked(a):
     print(json.dumps(rec))
 
 
+def mosaic_points(a):
+    import json
+    from asy_vrnet_amd.graph import TrainStep
+    dev = torch.device("cuda:0")
+    B, S, NC, NS, N = a.batch, a.size, 4, 9, a.mosaic_points
+    ih, iw = (int(v) for v in a.frames.lower().split("x"))
+    raw_frames, raw_maps, boxes, _ = synthetic_frames(4 * B, ih, iw, S, NC, NS)
+    boxes = [bx[:8] for bx in boxes]                        # four sources of an image bring at most max_gt = 32 together
+    r = torch.cat([A.synthetic_inputs(B, S, 1 + k, dev)[1] for k in range(4)])
+    pin = lambda t: t.cpu().contiguous().pin_memory()
+    hraw, hmaps, hr, sizes = pin(raw_frames), pin(raw_maps), pin(r), [(ih, iw)] * 4 * B
+    # a pinhole with the principal point in the middle of the frame; N points per source spread over the frame and a margin
+    P = np.array([[1000.0, 0, iw / 2, 0], [0, 1000.0, ih / 2, 0], [0, 0, 1, 0]], np.float32)
+    rng = np.random.default_rng(1)
+    z = rng.uniform(2, 120, (4 * B, N))
+    clouds = np.zeros((4 * B, N, 7), np.float32)
+    clouds[..., 0] = (rng.uniform(-0.05 * iw, 1.05 * iw, (4 * B, N)) - iw / 2) * z / 1000.0
+    clouds[..., 1] = (rng.uniform(-0.05 * ih, 1.05 * ih, (4 * B, N)) - ih / 2) * z / 1000.0
+    clouds[..., 2] = z
+    clouds[..., 3:] = rng.standard_normal((4 * B, N, 4))
+    points = (clouds, np.full(4 * B, N, np.int64))          # the padded form of data.pack_points
+
+    def trainer():
+        model = A.EfficientVRNet(NC, NS, a.phi, img_size=(S, S)).to(dev).train()
+        A.randomize_state_dict(model.state_dict(), seed=0)
+        return (model, losses.YOLOLoss(NC).to(dev), optim.build_optimizer(model, "sgd", 1.25e-3, 0.937, 5e-4),
+                optim.ModelEMA(model))
+    t1, t2 = trainer(), trainer()
+    kw = dict(max_gt=32, from_frames=True, capacity=(ih, iw), device=dev, aug_seed=0, mosaic=True)
+    step_m = TrainStep(t1[0], t1[1], t1[2], t1[3], B, S, NS, **kw)
+    step_p = TrainStep(t2[0], t2[1], t2[2], t2[3], B, S, NS, radar_points=N, radar_radius=a.radius, calib=P, **kw)
+    radar = {id(step_m): hr, id(step_p): points}
+
+    def step_window(step, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            last = step(hraw, radar[id(step)], boxes, hmaps, sizes)["total"]
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3, float(last)
+
+    def prologue_window(step, n):
+        """The prologue alone on the slots, tables, boxes and radar inputs the last step left: device time between two events."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        step._prologue()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            step._prologue()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def pack_window(n):
+        """The host's share of the points path alone: validation and packing into the pinned staging tensor."""
+        t0 = time.perf_counter()
+        for _ in range(n):
+            step_p.radar_points.validate(points, None)
+        return (time.perf_counter() - t0) / n * 1e3
+    names = ("prologue mosaic, maps (6 launches)", "prologue mosaic, points (8 launches)", "step mosaic, maps", "step mosaic, points",
+             "host packing of the points")
+    for step in (step_m, step_p):
+        step_window(step, 3)
+    ms, _ = step_window(step_m, 3)
+    n_steps = max(a.steps, int(math.ceil(500.0 / ms)))
+    per, last = {n: [] for n in names}, {}
+    for _ in range(a.rounds):                               # alternating: a drift of the box hits every contender alike
+        per[names[0]].append(prologue_window(step_m, 50))
+        per[names[1]].append(prologue_window(step_p, 50))
+        for name, step in ((names[2], step_m), (names[3], step_p)):
+            ms, last[name] = step_window(step, n_steps)
+            per[name].append(ms)
+        per[names[4]].append(pack_window(10))
+    lit = int((step_p.r != 0).any(dim=1).sum())
+    print(f"phi={a.phi} bs={B} {S}x{S} frames {ih}x{iw} sgd+ema, real loss: ms, median of {a.rounds} alternating rounds "
+          f"(min .. max); {4 * B} sources per step, {N} points per source, radius {a.radius}; device {torch.cuda.get_device_name(dev)}")
+    rec = {"tool": "bench_train_step --mosaic-points", "phi": a.phi, "batch": B, "size": S, "frames": [ih, iw], "rounds": a.rounds,
+           "steps_per_round": n_steps, "points": N, "radius": a.radius, "radar_bytes_per_step": [hr.numel() * 4, clouds.nbytes + 4 * B * 56],
+           "lit_pixels_last_step": lit, "flag": [step_m.stats()["flag"], step_p.stats()["flag"]]}
+    for name in names:
+        v = sorted(per[name])
+        print(f"  {name:40s} {float(np.median(v)):9.3f}  ({v[0]:.3f} .. {v[-1]:.3f})" +
+              (f"  last total loss {last[name]:.4f}" if name in last else ""))
+        rec[name] = {"median_ms": round(float(np.median(v)), 4), "min_ms": round(v[0], 4), "max_ms": round(v[-1], 4)}
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--phi", default="l")
@@ -325,7 +418,14 @@ def main():
                     help="with --frames: the augmented prologue and step against the plain frame path, alternating rounds")
     ap.add_argument("--mosaic", action="store_true",
                     help="with --frames: the Mosaic prologue and step against the augmented frame path, alternating rounds")
+    ap.add_argument("--mosaic-points", type=int, default=None, metavar="N",
+                    help="with --frames: the Mosaic step fed N radar points per source against the one fed finished maps")
+    ap.add_argument("--radius", type=int, default=0, help="with --mosaic-points: the footprint radius of a point")
     a = ap.parse_args()
+    if a.mosaic_points:
+        if not a.frames:
+            ap.error("--mosaic-points needs --frames IHxIW")
+        return mosaic_points(a)
     if a.mosaic:
         if not a.frames:
             ap.error("--mosaic needs --frames IHxIW")
