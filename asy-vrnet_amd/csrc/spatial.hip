@@ -951,6 +951,12 @@ struct SaParams {
   const float *cw, *cb, *sw, *sb, *gnw, *gnb;
 };
 __device__ __forceinline__ int sa_dst(int q, int C) { return q < C / 2 ? 2 * q : 2 * (q - C / 2) + 1; }
+// dz = dy x sig'(z) of both backward kernels: every product rounded, none fused into what follows -- sa_bwd_apply_kernel subtracts
+// the mean of the values sa_bwd_reduce_kernel added and needs their bits
+__device__ __forceinline__ float sa_dz(float g, float xv, float sg) {
+#pragma clang fp contract(off)
+  return g * xv * sg * (1.f - sg);
+}
 
 __global__ void sa_coef_fwd_kernel(const double* mom, SaParams sp, int B, long HW, int C, int G, float* P, float* Q,
                                    float* Mn) {
@@ -1004,7 +1010,7 @@ __global__ __launch_bounds__(256) void sa_bwd_reduce_kernel(const float* dy, lon
     for (long r = r0 + ty; r < r1; r += RP) {
       const float xv = x[(b * HW + r) * ldx + q];
       const float sg = vr_sigmoid(pq * (xv - mq) + qq);
-      const double dz = (double)(dy[(b * HW + r) * lddy + dq] * xv * sg * (1.f - sg));
+      const double dz = (double)sa_dz(dy[(b * HW + r) * lddy + dq], xv, sg);
       t1 += dz;
       t2 += dz * (double)xv;
     }
@@ -1061,9 +1067,9 @@ __global__ __launch_bounds__(256) void sa_coef_bwd_kernel(const double* T, const
       if (var < 0) var = 0;
       const double r = 1.0 / sqrt(var + 1e-5);
       const double k = (double)sp.sw[i] * sp.gnw[i];
-      const double m1 = k * t1 / (double)HW, m2 = k * r * (t2 - mean * t1) / (double)HW;
-      E[e] = (float)(-r * r * m2);           // dx = dy * (...) + E * (x - Mn) + F
-      F[e] = (float)(-r * m1);
+      const double m2 = k * r * (t2 - mean * t1) / (double)HW;
+      E[e] = (float)(-r * r * m2);           // dx = dy * sig + P * (dz - F) + E * (x - Mn): F is the mean of dz (sa_bwd_apply_kernel)
+      F[e] = (float)(t1 / (double)HW);
     }
   } else {
     // one workgroup per parameter index i: the B * G (sample, group) terms are spread over the threads and added in a
@@ -1112,7 +1118,7 @@ __global__ __launch_bounds__(256) void sa_coef_bwd_kernel(const double* T, const
 
 __global__ __launch_bounds__(256) void sa_bwd_apply_kernel(const float* dy, long lddy, const float* x, long ldx,
                                                            const float* P, const float* Q, const float* Mn, const float* E,
-                                                           const float* F, float* dx, long lddx, long HW, int C,
+                                                           const float* F, float* dx, long lddx, long HW, int C, int cp,
                                                            int accumulate) {
   const long b = blockIdx.y;
   const long total = HW * C;
@@ -1120,10 +1126,14 @@ __global__ __launch_bounds__(256) void sa_bwd_apply_kernel(const float* dy, long
     const long r = e / C;
     const int q = e - r * C;
     const float xv = x[(b * HW + r) * ldx + q];
-    const float pq = P[b * C + q], mq = Mn[b * C + q];
+    const float pq = P[b * C + q], mq = Mn[b * C + q], fq = F[b * C + q];
     const float sg = vr_sigmoid(pq * (xv - mq) + Q[b * C + q]);
     const float g = dy[(b * HW + r) * lddy + sa_dst(q, C)];
-    const float v = g * (sg + xv * sg * (1.f - sg) * pq) + E[b * C + q] * (xv - mq) + F[b * C + q];
+    // Normalised half: P dz and -P mean(dz) are each 1 / sqrt(var + eps) times the size of their sum where the variance is small
+    // (HW = 1: 316 times, and the sum is 0), so dz -- the product of sa_bwd_reduce_kernel, in its order -- meets its mean F BEFORE
+    // the scaling by P: rounded to fp32 one by one, the two terms left 2^-13 of dx at HW = 1.  Gate half: P = E = 0, F the term.
+    const float dz = sa_dz(g, xv, sg);
+    const float v = g * sg + (q % (2 * cp) >= cp ? pq * (dz - fq) : fq) + E[b * C + q] * (xv - mq);
     float* d = dx + (b * HW + r) * lddx + q;
     *d = accumulate ? *d + v : v;
   }
@@ -1474,7 +1484,7 @@ extern "C" int vrnet_sa_bwd_f32(const float* dy, long lddy, const float* x, long
                      dsw, dsb, dgnw, dgnb, accumulate_params);
   VR_LAUNCH_CHECK("sa_coef_bwd");
   hipLaunchKernelGGL(sa_bwd_apply_kernel, dim3(grid_for(HW * C), B), dim3(256), 0, st, dy, lddy, x, ldx, P, Q, Mn, E, F, dx,
-                     lddx, HW, C, accumulate_dx);
+                     lddx, HW, C, C / (2 * G), accumulate_dx);
   VR_LAUNCH_CHECK("sa_bwd_apply");
   return VR_OK;
 }
