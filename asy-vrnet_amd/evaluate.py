@@ -32,7 +32,8 @@ from . import data, infer
 FLAG_EVAL_CAPACITY, FLAG_EVAL_GT, FLAG_EVAL_BOX = 32, 64, 128     # EVAL_FLAG_* of csrc/evalacc.hip, above infer.FLAG_*
 MIN_CONF = 1e-4
 _FLAG_NAMES = {1: "render.FLAG_CLASS", 2: "render.FLAG_BOX_COLOUR", 4: "render.FLAG_BOX_ROWS", 8: "FLAG_CANDIDATES",
-               16: "FLAG_DET_CLASS", 32: "FLAG_EVAL_CAPACITY", 64: "FLAG_EVAL_GT", 128: "FLAG_EVAL_BOX", 8192: "FLAG_DEHAZE"}
+               16: "FLAG_DET_CLASS", 32: "FLAG_EVAL_CAPACITY", 64: "FLAG_EVAL_GT", 128: "FLAG_EVAL_BOX", 8192: "FLAG_DEHAZE",
+               16384: "FLAG_ACE"}
 
 
 def score6(x):
@@ -173,12 +174,13 @@ class EvalPipeline(infer.FramePipeline):
 
     radar_points / radar_radius / radar_min_depth / calib: as `infer.FramePipeline`; `add` then takes radar points.
     crops: forwarded to `infer.FramePipeline` (the crops of the last batch are `self.result.crops`); nothing here reads them.
-    dehaze: forwarded to `infer.FramePipeline`: the validation pass then scores the network on the dehazed frames."""
+    dehaze: forwarded to `infer.FramePipeline`: the validation pass then scores the network on the dehazed frames.
+    ace: forwarded likewise: the validation pass scores the network on the ACE-enhanced frames."""
 
     def __init__(self, model, frame_shape, input_shape, class_names, num_seg_classes, batch=1, capacity=None, max_boxes=100,
                  max_gt=64, conf_thres=0.05, nms_thres=0.5, letterbox_image=True, max_candidates=1024, normalise_radar=False,
                  graph=True, ragged=False, max_taps=None, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None,
-                 crops=None, dehaze=None):
+                 crops=None, dehaze=None, ace=None):
         infer.validate_config(model, frame_shape, input_shape, batch, max_candidates)
         self.class_names, self.num_seg_classes, self.capacity, self.max_boxes, self.max_gt = validate_eval_config(
             class_names, num_seg_classes, batch, capacity, max_boxes, max_gt, conf_thres)
@@ -201,7 +203,7 @@ class EvalPipeline(infer.FramePipeline):
                          letterbox_image=letterbox_image, max_candidates=max_candidates, normalise_radar=normalise_radar,
                          render=False, graph=graph, ragged=ragged, max_taps=max_taps, radar_points=radar_points,
                          radar_radius=radar_radius, radar_min_depth=radar_min_depth, calib=calib, crops=crops,
-                         dehaze=dehaze)
+                         dehaze=dehaze, ace=ace)
 
     def _tail(self, result):
         from . import hip, metrics

@@ -168,6 +168,8 @@ _SIGS = {
     "vrnet_crop_boxes_u8": ([P, I, I, I, P, P, P, I, P, L, P, P, P, P], I),
     "vrnet_dehaze_workspace_bytes": ([I, I, I], L),
     "vrnet_dehaze_u8": ([P, P, I, I, I, I, I, D, D, D, P, P, P, P, L, P], I),
+    "vrnet_ace_workspace_bytes": ([I, I, I], L),
+    "vrnet_ace_u8": ([P, P, I, I, I, I, D, D, I, P, P, P, P, L, P], I),
     "vrnet_heatmap_workspace": ([I, I, I], L),
     "vrnet_heatmap_f32": ([P, P, P] + [I] * 11 + [P, P, F, P, P, P, P, L, P], I),
     "vrnet_heatmap_ragged_workspace": ([I, I, I], L),
@@ -1774,3 +1776,35 @@ def dehaze(frames, out, ws, geom=None, sz=15, r=60, eps=1e-4, omega=0.95, tx=0.1
                   (transmission, (B, ihm, iwm), torch.float64), (flag, (1,), torch.int32), (ws, (ws.numel(),), torch.uint8)))
     _check(_lib.vrnet_dehaze_u8(ptr(frames), None if geom is None else _geom(geom, B, fn), B, ihm, iwm, int(sz), int(r), float(eps),
                                 float(omega), float(tx), ptr(out), ptr(transmission), ptr(flag), ptr(ws), ws.numel(), stream()), fn)
+
+
+# ---- ACE de-rain enhancement (csrc/ace.hip) ------------------------------------------------------------------------------------
+FLAG_ACE = 16384         # VR_FLAG_ACE of csrc/common.h: a degenerate image, returned unchanged
+
+
+def ace_workspace_bytes(B, ihm, iwm):
+    n = _lib.vrnet_ace_workspace_bytes(B, ihm, iwm)
+    if n < 0:
+        raise RuntimeError(f"ace: bad shape (B {B}, slots of {ihm} x {iwm}; 1..65535 images, sides up to 2^17, at most 2^26 "
+                           "pixels each and 2^31 in all)")
+    return n
+
+
+def ace(frames, out, ws, weights, geom=None, ratio=4.0, radius=3, s=0.005, bins=2000, flag=None):
+    """Automatic Colour Equalisation by the rule of `render.ace_host` (vrnet_ace_u8): frames (B, ihm, iwm, 3) uint8 -> out,
+    another tensor of the same shape; ws: uint8, at least ace_workspace_bytes(B, ihm, iwm) bytes; weights: the
+    (2 radius + 1, 2 radius + 1) float64 table of `render.ace_weights` on the device; geom: the (B, GEOM_BYTES) table of a
+    ragged batch, None: every image fills its slot; flag (1) int32 or None: FLAG_ACE for a degenerate image (returned
+    unchanged), FLAG_GEOMETRY for a bad record (a zero image).  2 N + 4 launches for a slot with N pyramid levels above its
+    bottom, no host synchronisation."""
+    fn = "ace"
+    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError(f"{fn}: expected contiguous uint8 frames of shape (B, ihm, iwm, 3)")
+    B, ihm, iwm = frames.shape[:3]
+    if out is None or ws is None or weights is None or out.data_ptr() == frames.data_ptr():
+        raise RuntimeError(f"{fn}: out (a tensor other than frames), the weights and the workspace are required")
+    n = 2 * int(radius) + 1
+    _tensors(fn, ((frames, (B, ihm, iwm, 3), torch.uint8), (out, (B, ihm, iwm, 3), torch.uint8), (weights, (n, n), torch.float64),
+                  (flag, (1,), torch.int32), (ws, (ws.numel(),), torch.uint8)))
+    _check(_lib.vrnet_ace_u8(ptr(frames), None if geom is None else _geom(geom, B, fn), B, ihm, iwm, int(radius), float(ratio),
+                             float(s), int(bins), ptr(weights), ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), fn)

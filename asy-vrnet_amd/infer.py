@@ -17,7 +17,8 @@ outside [0, num_classes), which is not counted -- and, in a ragged pipeline, FLA
 table had to be clamped by a kernel, which the host checks of `run` rule out.  A pipeline built with crops= adds
 hip.crop_boxes behind hip.detect_finish and FLAG_CROP_ARENA, a crop that did not fit into the arena.  A pipeline built with
 dehaze= puts hip.dehaze in front of the letterbox, so that everything downstream reads the dehazed frames, and adds
-FLAG_DEHAZE, a degenerate image that went on unchanged.
+FLAG_DEHAZE, a degenerate image that went on unchanged.  A pipeline built with ace= puts hip.ace there too, behind hip.dehaze
+when both are on, and adds FLAG_ACE for its degenerate images.
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
@@ -36,6 +37,7 @@ FLAG_POINT_COUNT = 1024                          # VR_FLAG_POINT_COUNT of csrc/c
 FLAG_LABEL_SCORE = rendering.FLAG_LABEL_SCORE    # 2048, csrc/labels.hip (a pipeline built with labels): a score outside [0, 1]
 FLAG_CROP_ARENA = rendering.FLAG_CROP_ARENA      # 4096, csrc/crops.hip (a pipeline built with crops): a crop that did not fit
 FLAG_DEHAZE = rendering.FLAG_DEHAZE              # 8192, csrc/dehaze.hip (a pipeline built with dehaze): a degenerate image, unchanged
+FLAG_ACE = rendering.FLAG_ACE                    # 16384, csrc/ace.hip (a pipeline built with ace): a degenerate image, unchanged
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -181,6 +183,18 @@ def dehaze_config(dehaze):
     return rendering.dehaze_params(fn="FramePipeline", **dehaze)
 
 
+def ace_config(ace):
+    """The parameters of a pipeline's ACE stage from its ace= keyword: None (no stage), True (the defaults of
+    `render.ace_host`) or a dict of its keywords ratio, radius, s, bins; checked by `render.ace_params`."""
+    if ace is None or ace is False:
+        return None
+    if ace is True:
+        ace = {}
+    if not isinstance(ace, dict) or set(ace) - {"ratio", "radius", "s", "bins"}:
+        raise RuntimeError(f"FramePipeline: ace is None, True or a dict of ratio, radius, s, bins, got {ace!r}")
+    return rendering.ace_params(fn="FramePipeline", **ace)
+
+
 def unmap_scalars(input_shape, image_shape, letterbox_image):
     """(offset, scale): the (y, x) float64 pairs with which decode.yolo_correct_boxes maps a centre, (c - offset) * scale, and a
     size, s * scale -- its own expressions, np.round included; (0, 0), (1, 1) without a letterbox."""
@@ -209,16 +223,18 @@ class FrameResult:
     From a pipeline built with crops (None otherwise): crops, the `render.Crops` of the run -- every kept detection cut out
     of the original frame, `crops.images()[b][i]` being row i of image b.
     From a pipeline built with dehaze (None otherwise): dehazed (B, ih, iw, 3) uint8, the frames everything else of the
-    result was computed from; padded like rendered from a ragged pipeline."""
+    result was computed from; padded like rendered from a ragged pipeline.
+    From a pipeline built with ace (None otherwise): enhanced (B, ih, iw, 3) uint8, the output of the ACE stage, which then
+    is what everything else of the result was computed from (the stage reads the dehazed frames when both are on)."""
     __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
-                 "heat_picture", "heat_range", "crops", "dehazed")
+                 "heat_picture", "heat_range", "crops", "dehazed", "enhanced")
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
-                 heat_picture=None, heat_range=None, crops=None, dehazed=None):
+                 heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None):
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
         self.heat_mask, self.heat_picture, self.heat_range, self.crops = heat_mask, heat_picture, heat_range, crops
-        self.dehazed = dehazed
+        self.dehazed, self.enhanced = dehazed, enhanced
 
     def detections(self):
         """The list `decode.non_max_suppression` returns: per image an (N_b, 7) float32 numpy array in the same order,
@@ -296,13 +312,21 @@ class FramePipeline:
     float64 planes of batch * ihm * iwm, `hip.dehaze_workspace_bytes`) and the second frame buffer are allocated before the
     capture.  Fixed-size and ragged pipelines alike; a frame too small for the box (r // 2 > min(ih, iw) - 1) raises on the
     host, in the constructor or in the validation of `run`; an image without atmospheric light (a black one, or one below
-    2000 pixels) goes on unchanged and FLAG_DEHAZE joins the bits of `flag`."""
+    2000 pixels) goes on unchanged and FLAG_DEHAZE joins the bits of `flag`.
+
+    ace: None (the default: exactly the calls issued without it), True or a dict of the keywords ratio, radius, s, bins of
+    `render.ace_host` -- the fast Automatic Colour Equalisation of the reference's sharpen.py, its de-rain enhancement
+    (`render.ace`, csrc/ace.hip): the launches of hip.ace sit in front of the letterbox node, behind those of hip.dehaze when
+    both are on (ACE then reads the dehazed frames), and everything downstream reads its output, `FrameResult.enhanced`.  The
+    buffer, the weights table and the workspace (`hip.ace_workspace_bytes`, about 40 bytes per frame pixel) are allocated
+    before the capture.  Fixed-size and ragged pipelines alike; a degenerate image (min(ih, iw) <= 2, or a constant R_0)
+    goes on unchanged and FLAG_ACE joins the bits of `flag`."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
-                 font=None, label_sizes=None, crops=None, dehaze=None):
+                 font=None, label_sizes=None, crops=None, dehaze=None, ace=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
         self.crop_capacity = crop_capacity(crops, self.batch, self.frame_shape)
@@ -310,6 +334,7 @@ class FramePipeline:
         if self.dehaze is not None and not rendering.dehaze_size_ok(*self.frame_shape, self.dehaze["r"]):
             raise RuntimeError(f"FramePipeline: frames of {self.frame_shape[0]} x {self.frame_shape[1]} allow no single reflection "
                                f"of the dehazing box r = {self.dehaze['r']}")
+        self.ace = ace_config(ace)
         self.radar_points = None
         if radar_points is not None:
             if radar_dtype != torch.float32:
@@ -363,6 +388,11 @@ class FramePipeline:
             from . import hip
             self._dehazed = torch.zeros_like(self.frames_u8)
             self._dehaze_ws = torch.empty(hip.dehaze_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
+        if self.ace is not None:              # before the capture: the stage's output, its weights table and its workspace
+            from . import hip
+            self._enhanced = torch.zeros_like(self.frames_u8)
+            self._ace_weights = torch.from_numpy(rendering.ace_weights(self.ace["radius"])).to(dev)
+            self._ace_ws = torch.empty(hip.ace_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
         self.cap = None                       # the NMS buffers follow the anchor count of the first (warm-up) pass
         self.graph = self.result = None
         if graph:
@@ -446,6 +476,10 @@ class FramePipeline:
         if self.dehaze is not None:           # in front of the letterbox: everything below reads the dehazed frames
             frames = self._dehazed
             hip.dehaze(self.frames_u8, frames, self._dehaze_ws, geom=geom, flag=self.flag, **self.dehaze)
+        dehazed = frames if self.dehaze is not None else None
+        if self.ace is not None:              # behind the dehazing, in front of the letterbox
+            hip.ace(frames, self._enhanced, self._ace_ws, self._ace_weights, geom=geom, flag=self.flag, **self.ace)
+            frames = self._enhanced
         if self.ragged:
             images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
             hip.letterbox(frames, None, H, W, images=images, geom=geom, max_taps=self.max_taps, flag=self.flag)
@@ -485,7 +519,7 @@ class FramePipeline:
                 box_palette=self.box_palette, thickness=self.thickness, flag=self.flag, device=dev, labels=self.labels, geom=geom,
                 label_sizes=self.label_size_tab)
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops,
-                             dehazed=frames if self.dehaze is not None else None)
+                             dehazed=dehazed, enhanced=frames if self.ace is not None else None)
         if self.heatmap:
             result.heat_picture, result.heat_mask, result.heat_range = rendering.heatmap(
                 frames, det, (H, W), alpha=self.heat_alpha, geom=geom, flag=self.flag, **self._heat_window)
@@ -588,9 +622,10 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     non-empty crop the arena kept is saved as dir_save_path/img_crop/<stem>_crop_<i>.png, i being the row's index within its
     picture (the `i` of yolo.py:180-193); the crops of the repeated fill pictures are dropped with the repeats.  The reference
     writes img_crop/crop_<i>.png and so overwrites the crops of one picture with those of the next: the stem in the name is a
-    deliberate departure.  From a pipeline built with dehaze the dehazed frame is saved as <stem>_dehaze.png.  Two pictures
-    that would share one output file (names that differ only in their extension, or `a_heat.jpg` next to `a.jpg` with heat
-    maps on, or `a_dehaze.jpg` with dehazing on): with dir_save_path that raises before anything runs."""
+    deliberate departure.  From a pipeline built with dehaze the dehazed frame is saved as <stem>_dehaze.png, from one built
+    with ace the enhanced frame as <stem>_ace.png.  Two pictures that would share one output file (names that differ only in
+    their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on, or `a_dehaze.jpg` with dehazing on, or `a_ace.jpg`
+    with ACE on): with dir_save_path that raises before anything runs."""
     from PIL import Image
     if not getattr(pipeline, "ragged", False):
         raise RuntimeError("predict_dir: needs a ragged pipeline (FramePipeline(..., ragged=True)): a folder holds pictures of any size")
@@ -600,7 +635,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         for n in names:
             stem = os.path.splitext(n)[0]
             targets = (stem,) + ((stem + "_heat",) if getattr(pipeline, "heatmap", False) else ()) + \
-                ((stem + "_dehaze",) if getattr(pipeline, "dehaze", None) is not None else ())
+                ((stem + "_dehaze",) if getattr(pipeline, "dehaze", None) is not None else ()) + \
+                ((stem + "_ace",) if getattr(pipeline, "ace", None) is not None else ())
             for target in targets:
                 other = stems.setdefault(target, n)
                 if other != n:
@@ -623,6 +659,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         heat = None if heat is None else heat.cpu().numpy()
         dehazed = None if dir_save_path is None else getattr(result, "dehazed", None)
         dehazed = None if dehazed is None else dehazed.cpu().numpy()
+        enhanced = None if dir_save_path is None else getattr(result, "enhanced", None)
+        enhanced = None if enhanced is None else enhanced.cpu().numpy()
         crops = None if dir_save_path is None else getattr(result, "crops", None)
         crops = None if crops is None else crops.images()
         for b, n in enumerate(chunk):
@@ -634,6 +672,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
                 Image.fromarray(heat[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_heat.png"))
             if dehazed is not None:
                 Image.fromarray(dehazed[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_dehaze.png"))
+            if enhanced is not None:
+                Image.fromarray(enhanced[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_ace.png"))
             for i, crop in enumerate(crops[b] if crops is not None else ()):
                 if crop is not None and crop.size:
                     os.makedirs(os.path.join(dir_save_path, "img_crop"), exist_ok=True)

@@ -54,6 +54,10 @@ ValueError for x1 < x0 where this module paints nothing.
   on the raw frames (csrc/dehaze.hip).  `dehaze_host` states the rule in numpy float64, one rounding per operation; the
   kernels equal it bit for bit.
 
+* `ace` / `ace_host`: the fast Automatic Colour Equalisation of the reference's image_augmentation_test/sharpen.py (its
+  de-rain enhancement) on the raw frames (csrc/ace.hip).  `ace_host` states the rule in numpy float64, one rounding per
+  operation; the kernels equal it byte for byte.
+
 Out of scope: crops resized to one size, image encoding and video I/O."""
 import colorsys
 import os
@@ -70,6 +74,8 @@ FLAG_CROP_ARENA = 4096    # VR_FLAG_CROP_ARENA of csrc/common.h: a crop that did
 CROP_RECORD = np.dtype([("offset", "<i4"), ("w", "<i4"), ("h", "<i4"), ("image", "<i4")])      # vrnet_crop_rec, 16 bytes
 FLAG_DEHAZE = 8192        # VR_FLAG_DEHAZE of csrc/common.h: a degenerate image, returned unchanged by `dehaze`
 DEHAZE_MAX_SZ, DEHAZE_MAX_R = 31, 128
+FLAG_ACE = 16384          # VR_FLAG_ACE of csrc/common.h: a degenerate image, returned unchanged by `ace`
+ACE_MAX_RADIUS, ACE_MAX_BINS = 8, 4096
 
 _device_palettes = {}
 
@@ -1067,3 +1073,188 @@ def dehaze(frames_u8, sizes=None, geom=None, sz=15, r=60, eps=1e-4, omega=0.95, 
         hip.dehaze(img, out, ws, geom=geom, transmission=t, flag=flag, **q)
         A = ws[:32 * B].view(torch.float64).view(B, 4)[:, :3].clone()
     return out, t, A
+
+
+# ---- ACE de-rain enhancement (csrc/ace.hip) ------------------------------------------------------------------------------------
+def ace_params(ratio=4.0, radius=3, s=0.005, bins=2000, fn="ace"):
+    """The parameters of the ACE rule, checked: ratio > 0 (finite), radius an integer in 1..8, 0 <= s < 0.5, bins an integer
+    in 2..4096.  Returns them as a dict of Python numbers."""
+    ints = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (radius, bins))
+    if not ints or not 1 <= radius <= ACE_MAX_RADIUS or not 2 <= bins <= ACE_MAX_BINS:
+        raise RuntimeError(f"{fn}: radius must be an integer in 1..{ACE_MAX_RADIUS} and bins an integer in 2..{ACE_MAX_BINS}, got "
+                           f"radius {radius!r}, bins {bins!r}")
+    try:
+        ratio, s = float(ratio), float(s)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{fn}: ratio and s are numbers, got {ratio!r}, {s!r}") from None
+    if not (0.0 < ratio < np.inf and 0.0 <= s < 0.5):
+        raise RuntimeError(f"{fn}: ratio must be positive and finite and s in [0, 0.5), got ratio {ratio}, s {s}")
+    return dict(ratio=ratio, radius=int(radius), s=s, bins=int(bins))
+
+
+def ace_weights(radius):
+    """The tap weights of the rule, (2 radius + 1, 2 radius + 1) float64: m[dy, dx] = 1.0 / sqrt(dy^2 + dx^2) with the centre
+    0, then m /= m.sum() in numpy's own summation.  The device receives this table as data."""
+    radius = ace_params(radius=radius, fn="ace_weights")["radius"]
+    d = np.arange(-radius, radius + 1, dtype=np.float64)
+    q = d[:, None] * d[:, None] + d[None, :] * d[None, :]
+    m = np.zeros_like(q)
+    m[q > 0.0] = 1.0 / np.sqrt(q[q > 0.0])
+    m /= m.sum()
+    return m
+
+
+def _ace_taps_host(n, k):
+    """cv2's INTER_LINEAR taps of one axis, source length n -> destination length k: (s0, s1, a0, a1)."""
+    scale = float(n) / float(k)
+    f = ((np.arange(k, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s0 = np.floor(f)
+    f = f - s0
+    s0 = s0.astype(np.int64)
+    f[s0 < 0] = 0.0
+    s0[s0 < 0] = 0
+    f[s0 >= n - 1] = 0.0
+    s0[s0 >= n - 1] = n - 1
+    s1 = np.minimum(s0 + 1, n - 1)
+    return s0, s1, (np.float32(1.0) - f).astype(np.float64), f.astype(np.float64)
+
+
+def ace_resize_host(S, h, w):
+    """cv2.resize(S, (w, h)) with its default INTER_LINEAR on a float64 plane, restated.  A source of exactly (2 h, 2 w) takes
+    OpenCV's exact-halving switch to the area path: (((S00 + S01) + S10) + S11) * 0.25 over each 2 x 2 block.  Otherwise two
+    taps per axis at the half-pixel-centre position, the fraction held in float32 and clamped taps weighted (1, 0): columns
+    first, H = S[:, x0] * a0 + S[:, x1] * a1, then rows, H[y0] * b0 + H[y1] * b1, every operation rounded on its own."""
+    S = np.asarray(S, np.float64)
+    h, w = int(h), int(w)
+    if S.ndim != 2 or min(S.shape) <= 0 or h <= 0 or w <= 0:
+        raise RuntimeError(f"ace_resize_host: expected a plane (n, m) and a size h, w >= 1, got {S.shape} -> {h} x {w}")
+    if S.shape == (2 * h, 2 * w):
+        return (((S[0::2, 0::2] + S[0::2, 1::2]) + S[1::2, 0::2]) + S[1::2, 1::2]) * 0.25
+    x0, x1, a0, a1 = _ace_taps_host(S.shape[1], w)
+    y0, y1, b0, b1 = _ace_taps_host(S.shape[0], h)
+    H = S[:, x0] * a0 + S[:, x1] * a1
+    return H[y0] * b0[:, None] + H[y1] * b1[:, None]
+
+
+def ace_ice_host(P, ratio, weights):
+    """The tap sum of the rule over one plane: res = 0.0, then for dy, and inside it dx, from -radius to radius without the
+    centre, res += m[dy, dx] * clip((P(y, x) - P(cy, cx)) * ratio, -1, 1), (cy, cx) clamped to the plane."""
+    h, w = P.shape
+    radius = weights.shape[0] // 2
+    ys, xs = np.arange(h), np.arange(w)
+    res = np.zeros((h, w), np.float64)
+    for dy in range(-radius, radius + 1):
+        rows = P[np.clip(ys + dy, 0, h - 1)]
+        for dx in range(-radius, radius + 1):
+            if dy == 0 and dx == 0:
+                continue
+            res += weights[dy + radius, dx + radius] * np.clip((P - rows[:, np.clip(xs + dx, 0, w - 1)]) * ratio, -1.0, 1.0)
+    return res
+
+
+def ace_bins_host(x, bins):
+    """numpy's uniform-bin rule restated as the device applies it: (counts (bins) int64, edges (bins + 1) float64) equal to
+    np.histogram(x, bins).  first, last = min, max of x (widened by 0.5 each way when equal); step = (last - first) / bins;
+    edge(i) = i * step + first, edge(bins) = last; idx = int(((v - first) / (last - first)) * bins), minus 1 at idx == bins,
+    minus 1 where v < edge(idx), plus 1 where v >= edge(idx + 1) and idx != bins - 1."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    bins = int(bins)
+    first, last = float(x.min()), float(x.max())
+    if first == last:
+        first, last = first - 0.5, last + 0.5
+    step = (last - first) / bins
+    edges = np.arange(bins + 1, dtype=np.float64) * step + first
+    edges[bins] = last
+    idx = (((x - first) / (last - first)) * bins).astype(np.int64)
+    idx[idx == bins] -= 1
+    idx[x < edges[idx]] -= 1
+    idx[(x >= edges[idx + 1]) & (idx != bins - 1)] += 1
+    return np.bincount(idx, minlength=bins).astype(np.int64), edges
+
+
+def ace_levels(ih, iw):
+    """The pyramid's level sizes [(h_0, w_0), ...]: halved upwards, (n + 1) // 2, down to the first with min(h, w) <= 2."""
+    sizes = [(int(ih), int(iw))]
+    while min(sizes[-1]) > 2:
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    return sizes
+
+
+def ace_host(rgb, ratio=4.0, radius=3, s=0.005, bins=2000):
+    """The fast Automatic Colour Equalisation of ONE (ih, iw, 3) uint8 RGB frame in numpy float64, each channel on its own and
+    every operation rounded on its own in the order of the header's statement (include/vrnet_hip.h, vrnet_ace_u8):
+    I_0 = byte / 255.0; the pyramid I_{L+1} = resize(I_L, (h_L + 1) // 2, (w_L + 1) // 2) down to the first level with
+    min(h, w) <= 2, where R = 0.5; above it R_L = (resize(R_{L+1}) + ice(I_L)) - ice(resize(I_{L+1})), both resized to
+    (h_L, w_L); then the stretch of R_0 between the edges of np.histogram(R_0, bins) at which the cumulative share reaches s
+    and last stays at or below 1.0 - s, clipped to [0, 1], times 255.0 and `saturate_host`.  Returns (bytes (ih, iw, 3) uint8,
+    degenerate): an image with min(ih, iw) <= 2, or with lmax <= lmin in any channel (a constant frame), is degenerate and
+    comes back unchanged in all three channels.  This is the statement the kernels of csrc/ace.hip are tested against.  The
+    OpenCV semantics in it (INTER_LINEAR's float32 fraction and clamped taps, the exact-halving switch to the area path) are
+    restated from OpenCV's published behaviour and have never been run against cv2."""
+    fn = "ace_host"
+    q = ace_params(ratio, radius, s, bins, fn)
+    ratio, radius, s, bins = q["ratio"], q["radius"], q["s"], q["bins"]
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or min(rgb.shape) <= 0:
+        raise RuntimeError(f"{fn}: expected a uint8 frame (ih, iw, 3), got {rgb.dtype} {rgb.shape}")
+    ih, iw = rgb.shape[:2]
+    sizes = ace_levels(ih, iw)
+    if len(sizes) == 1:
+        return rgb.copy(), True
+    m = ace_weights(radius)
+    out = np.empty_like(rgb)
+    for c in range(3):
+        planes = [rgb[..., c].astype(np.float64) / 255.0]
+        for h, w in sizes[1:]:
+            planes.append(ace_resize_host(planes[-1], h, w))
+        R = np.full(sizes[-1], 0.5, np.float64)
+        for L in range(len(sizes) - 2, -1, -1):
+            h, w = sizes[L]
+            R = (ace_resize_host(R, h, w) + ace_ice_host(planes[L], ratio, m)) - ace_ice_host(ace_resize_host(planes[L + 1], h, w), ratio, m)
+        hist, edges = np.histogram(R, bins)
+        d = np.cumsum(hist).astype(np.float64) / float(ih * iw)
+        lmin = int(np.flatnonzero(d >= s)[0])
+        below = np.flatnonzero(d <= 1.0 - s)
+        lmax = int(below[-1]) if len(below) else -1
+        if lmax <= lmin:
+            return rgb.copy(), True
+        v = np.clip((R - edges[lmin]) / (edges[lmax] - edges[lmin]), 0.0, 1.0)
+        out[..., c] = saturate_host(v * 255.0)
+    return out, False
+
+
+def ace(frames_u8, sizes=None, geom=None, ratio=4.0, radius=3, s=0.005, bins=2000, flag=None, device="cuda"):
+    """`ace_host` on the device (vrnet_ace_u8, two launches per pyramid level plus four, no host synchronisation): frames_u8
+    (B, ih, iw, 3) uint8 RGB, numpy or tensor (a single (ih, iw, 3) frame counts as B = 1).  sizes: (B, 2) host integers
+    (ih_b, iw_b) when the frames are padded slots with image b in the top-left corner of slot b -- a table is built from
+    them --, or geom: the (B, hip.GEOM_BYTES) device table of `data.frame_geometry`; neither: every image fills its slot.
+    Outside an image's corner the result is 0.  Returns out (B, ih, iw, 3) uint8 on the device.  flag: a zeroed int32 device
+    tensor of one element, or None: it receives FLAG_ACE for a degenerate image (min(ih, iw) <= 2, or a constant R_0), which
+    comes back unchanged, and hip.FLAG_GEOMETRY for a bad record of the table, which gives a zero image."""
+    from . import data, hip
+    fn = "ace"
+    q = ace_params(ratio, radius, s, bins, fn)
+    img = _as_u8(frames_u8, "frames", 4, fn)
+    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
+        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    B, ih, iw = img.shape[:3]
+    if sizes is not None and geom is not None:
+        raise RuntimeError(f"{fn}: give sizes or a geometry table, not both")
+    table = None
+    if sizes is not None:
+        arr = data.frame_sizes(sizes, B, fn)
+        for b, (h, w) in enumerate(arr.tolist()):
+            if h <= 0 or w <= 0 or h > ih or w > iw:
+                raise RuntimeError(f"{fn}: image {b}: bad size {h} x {w} in a slot of {ih} x {iw}")
+        table = np.zeros(B, data.GEOM_DTYPE)
+        table["ih"], table["iw"], table["thickness"] = arr[:, 0], arr[:, 1], 1
+    img = img.to(device, non_blocking=True).contiguous()
+    dev = img.device
+    with torch.cuda.device(dev):
+        if table is not None:
+            geom = data.geometry_bytes(table).pin_memory().to(dev, non_blocking=True)
+        weights = torch.from_numpy(ace_weights(q["radius"])).to(dev)
+        out = torch.empty_like(img)
+        ws = torch.empty(hip.ace_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
+        hip.ace(img, out, ws, weights, geom=geom, flag=flag, **q)
+    return out

@@ -1370,6 +1370,63 @@ int vrnet_dehaze_u8(const unsigned char* frames, const vrnet_frame_geom* geom, i
                     double omega, double tx, unsigned char* out, double* transmission, int* flag, void* workspace,
                     long workspace_bytes, void* stream);
 
+/* ---- ACE de-rain enhancement (csrc/ace.hip) -------------------------------------------------------------------------------
+ * Added within ABI 11: two new symbols only, no existing signature, layout or kernel behaviour changed.
+ * The fast Automatic Colour Equalisation of the reference's image_augmentation_test/sharpen.py restated; the host statement is
+ * render.ace_host and the kernels equal it byte for byte.  THE RULE for one (ih, iw, 3) uint8 image, each channel on its own;
+ * every float64 operation is rounded on its own in the order written, nothing is contracted, divisions are IEEE.
+ * Parameters: ratio (4.0), radius (3), s (0.005), bins (2000).
+ *   I0 = double(byte) / 255.0.
+ *   weights: computed on the host and passed as data, (2 radius + 1)^2 doubles: m[dy, dx] = 1.0 / sqrt(dy^2 + dx^2), the
+ *     centre 0, then m /= m.sum() in numpy's own summation (render.ace_weights).
+ *   ice(P), P of (h, w): res = 0.0; for dy = -radius .. radius and, inside it, dx = -radius .. radius, skipping the centre:
+ *     res += m[dy, dx] * clip((P(y, x) - P(cy, cx)) * ratio, -1, 1), cy = clamp(y + dy, 0, h - 1), cx clamped likewise: edge
+ *     replication of P itself.
+ *   resize(S, h, w): cv2's default INTER_LINEAR resize on float64.
+ *     Halving case: the source is exactly (2 h, 2 w) -- OpenCV's exact-halving switch to the fast area path:
+ *       out = (((S00 + S01) + S10) + S11) * 0.25 over each 2 x 2 block.
+ *     Two-tap case, otherwise; per axis, destination index d, source length n, destination length k:
+ *       scale = double(n) / double(k);  f = float((d + 0.5) * scale - 0.5), computed in double and rounded to float once;
+ *       s0 = floor(f), then f -= s0 in float;  s0 < 0: s0 = 0, f = 0;  s0 >= n - 1: s0 = n - 1, f = 0;
+ *       s1 = min(s0 + 1, n - 1);  the weights a0 = double(1.f - f), a1 = double(f).
+ *       Columns first: H(y, x) = S(y, x0) * a0 + S(y, x1) * a1;  then rows: out = H(y0, x) * b0 + H(y1, x) * b1.
+ *   The pyramid: I_0 = I0;  I_{L+1} = resize(I_L, (h_L + 1) / 2, (w_L + 1) / 2) while min(h_L, w_L) > 2.  At the first level
+ *     with min <= 2, R = 0.5 everywhere.  Above it R_L = (resize(R_{L+1}, h_L, w_L) + ice(I_L)) - ice(resize(I_{L+1}, h_L, w_L)).
+ *     The up-resized constant bottom goes through the resize formula like any plane (0.5 a0 + 0.5 a1 is not always 0.5).
+ *   The stretch (the reference's stretchImage): first, last = the minimum and maximum of R_0, widened by 0.5 each way when
+ *     equal;  step = (last - first) / bins;  edge(i) = i * step + first, edge(bins) = last.  The bin of a value v:
+ *     idx = int(((v - first) / (last - first)) * bins);  idx == bins: idx -= 1;  v < edge(idx): idx -= 1;
+ *     v >= edge(idx + 1) and idx != bins - 1: idx += 1 -- numpy's uniform-bin rule, np.histogram(R_0, bins).
+ *     d(i) = double(cumulative count) / double(ih iw);  lmin = the first i with d(i) >= s;  lmax = the last i with
+ *     d(i) <= 1.0 - s, or -1 if there is none;  out = clip((R_0 - edge(lmin)) / (edge(lmax) - edge(lmin)), 0, 1);
+ *     byte = clip(rint(out * 255.0), 0, 255), half to even.
+ *   DEGENERATE: min(ih, iw) <= 2, or lmax <= lmin in any channel (a constant frame whose R_0 is exactly 0.5: lmin = 1000,
+ *     lmax = 999 at the defaults; the reference would write a black picture).  All three channels of a degenerate image come
+ *     back UNCHANGED and bit 16384 of *flag (VR_FLAG_ACE) is set; the other images of the batch are unaffected.  A constant
+ *     frame of a size whose up-resize fractions are not exact in float32 has an R_0 that differs from 0.5 in its last bits;
+ *     by the rule it is not degenerate, and the stretch spreads those bits over the byte range.
+ * The OpenCV resize semantics above are restated from its published behaviour and have never been run against cv2.
+ * vrnet_ace_u8: frames (B, ihm, iwm, 3) u8; out the same shape, a different buffer (frames is not modified); weights the
+ *   (2 radius + 1)^2 doubles above in DEVICE memory, 8-byte aligned; flag may be NULL; geom the per-image table of the ragged
+ *   batches, or NULL when every image fills its slot.  With a table image b is the geom[b].ih x geom[b].iw top-left corner
+ *   of its slot and everything outside the corner is written 0; a record with ih, iw <= 0 or above the slot sets bit 256
+ *   (VR_FLAG_GEOMETRY) and gives a zero image.  One kernel body for both cases: the grids follow (B, ihm, iwm) alone, every
+ *   image derives its level sizes from its own record, workgroups beyond an image's level or at its bottom leave at once.
+ *   radius in 1..8, ratio > 0 (finite), 0 <= s < 0.5, bins in 2..4096; the shape limits of vrnet_dehaze_u8.
+ *   2 N + 4 launches, N being the levels above the bottom of the SLOT's pyramid (N = 10 at 1080 x 1920: 24 launches): init,
+ *   N down-resizes, N level launches (per 32 x 32 tile and channel the tiles of I_L and of resize(I_{L+1}) with a halo of
+ *   radius in LDS, both tap sums from LDS with the weights through the scalar cache, resize(R_{L+1}) at the pixel, no
+ *   full-size plane of either up-resized operand; one instance per radius; level 0 also the minimum and maximum of R_0 through
+ *   an order-preserving 64-bit integer key and integer atomics), the histogram, the cumulative scan with both thresholds,
+ *   the stretch with the byte store.  Every call initialises what it accumulates into; integer atomics only: the same bytes
+ *   on every run.  No allocation, no memset node, no host synchronisation; capturable in a graph.
+ * vrnet_ace_workspace_bytes: the bytes of `workspace` (-1 for a shape outside the limits): R_0 and, for every deeper level of
+ *   the slot's pyramid, I_L and R_L as float64 (about 5 / 3 x 24 B ihm iwm bytes), and 48 KB of histogram bins per image. */
+long vrnet_ace_workspace_bytes(int B, int ihm, int iwm);
+int vrnet_ace_u8(const unsigned char* frames, const vrnet_frame_geom* geom, int B, int ihm, int iwm, int radius, double ratio,
+                 double s, int bins, const double* weights, unsigned char* out, int* flag, void* workspace, long workspace_bytes,
+                 void* stream);
+
 
 #ifdef __cplusplus
 }
