@@ -11,6 +11,7 @@ batch -- image normalisation + CHW, label clamp, one-hot -- from bytes.  Pins: t
 `YoloDataset.__getitem__` (train=False) + `yolo_dataset_collate`, importable once cv2 / albumentations are stubbed (the
 evaluation path touches neither), produced tests/golden/dataset_small.npz (tools/make_golden_dataset.py) -- parsing,
 letterbox, box mapping, clamp, one-hot and collate are held to it bit for bit (tests/test_data.py)."""
+import math
 import os
 import re
 
@@ -633,10 +634,234 @@ def hsv_jitter(canvas_u8, luts):
     return hsv_to_rgb_u8(np.stack([luts[k][hsv[..., k]] for k in range(3)], -1))
 
 
-def augment_boxes(box, iw, ih, w, h, rec):
+# ---- the blur and the rotation behind the paste (utils_seg/dataloader.py:113-131), host side ---------------------------------
+# The segmentation loader blurs (cv2.GaussianBlur(image, (5, 5), 0)) and rotates (cv2.warpAffine about the canvas centre by a
+# whole angle in [-10, 10]: INTER_CUBIC and a grey border for the image, INTER_NEAREST and a 0 border for the label map) each
+# item with probability 0.25 each, between the flip and the colour stage.  The functions below restate OpenCV's 8-bit
+# fixed-point paths from its public sources and are the truth the vrnet_augment_post_* kernels of csrc/augment.hip are held
+# to, bit for bit; cv2 is not a dependency of this project and agreement with cv2's own bytes is UNMEASURED.
+# vrnet_aug_post_rec of include/vrnet_hip.h, one record per image (112 bytes)
+AUG_POST_DTYPE = np.dtype([(n, "<i4") for n in ("blur", "rotate", "angle", "reserved")] + [("inv", "<f8", (6,)), ("fwd", "<f8", (6,))])
+AUG_POST_MIN_SIDE = 8                            # the smallest canvas side the entry points of the post stage take
+AUG_POST_MAX_ANGLE = 45                          # the largest max_angle they take
+
+
+def reflect_101(i, n):
+    """OpenCV's BORDER_REFLECT_101 for indices -n < i < 2 n - 1 of an axis of n: -1 -> 1, -2 -> 2, n -> n - 2, n + 1 -> n - 3."""
+    i = np.asarray(i)
+    i = np.where(i < 0, -i, i)
+    return np.where(i >= n, 2 * n - 2 - i, i)
+
+
+def gaussian_blur5_u8(canvas):
+    """cv2.GaussianBlur(canvas, (5, 5), 0) on (H, W, 3) uint8 restated, integers only: with w = [1, 4, 6, 4, 1] on both axes
+    and BORDER_REFLECT_101, S = sum_j sum_i w[j] w[i] p[y + j - 2, x + i - 2]; the output is (S + 128) >> 8.  That is what
+    OpenCV's 8-bit fixed-point path gives for the ksize = 5, sigma = 0 kernel {1, 4, 6, 4, 1} / 16: every weight is exact in
+    8.8 fixed point, and its final rounding is this one.  Restated from OpenCV's published behaviour; agreement with cv2's own
+    bytes is UNMEASURED.  H, W >= 3 (the reflection); the device entry points ask for 8."""
+    a = np.asarray(canvas)
+    if a.ndim != 3 or a.dtype != np.uint8 or min(a.shape[:2]) < 3:
+        raise RuntimeError(f"gaussian_blur5_u8: expected (H, W, C) uint8 with H, W >= 3, got {a.dtype} {a.shape}")
+    a = a.astype(np.int64)
+    H, W = a.shape[:2]
+    w = (1, 4, 6, 4, 1)
+    ix, iy = reflect_101(np.arange(-2, W + 2), W), reflect_101(np.arange(-2, H + 2), H)
+    h = sum(w[i] * a[:, ix[i:i + W]] for i in range(5))
+    s = sum(w[j] * h[iy[j:j + H]] for j in range(5))
+    return ((s + 128) >> 8).astype(np.uint8)
+
+
+def rotation_matrices(input_shape, angle):
+    """(fwd, inv), six float64 each, of the reference's rotation by `angle` (its `rotation`, an int; it passes -rotation to
+    cv2.getRotationMatrix2D) about c = (W // 2, H // 2): a = -angle * pi / 180, alpha = cos a, beta = sin a, fwd = [[alpha, beta,
+    (1 - alpha) cx - beta cy], [-beta, alpha, beta cx + (1 - alpha) cy]]; inv is its inverse by warpAffine's own sequence: D =
+    1 / (m0 m4 - m1 m3), A11 = m4 D, A22 = m0 D, m1 *= -D, m3 *= -D, b1 = -A11 m2 - m1 m5, b2 = -m3 m2 - A22 m5.  Host only:
+    the device receives the twelve doubles."""
+    H, W = (int(v) for v in input_shape)
+    cx, cy = float(W // 2), float(H // 2)
+    a = -int(angle) * math.pi / 180
+    alpha, beta = math.cos(a), math.sin(a)
+    m = [alpha, beta, (1 - alpha) * cx - beta * cy, -beta, alpha, beta * cx + (1 - alpha) * cy]
+    fwd = np.array(m, np.float64)
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = m[4] * D, m[0] * D
+    m[0], m[4] = A11, A22
+    m[1] *= -D
+    m[3] *= -D
+    b1 = -m[0] * m[2] - m[1] * m[5]
+    b2 = -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    return fwd, np.array(m, np.float64)
+
+
+def _sat_i32(v):
+    return np.clip(np.rint(v), -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
+
+
+def _wrap_i32(v):
+    return ((v + 2 ** 31) % 2 ** 32) - 2 ** 31
+
+
+def warp_coords(inv, H, W, nearest):
+    """warpAffine's fixed-point coordinate walk (AB_BITS = 10) for the (H, W) output under the inverse map inv: adelta[x] =
+    rint(inv[0] x 1024), bdelta[x] = rint(inv[3] x 1024); per row X0 = rint((inv[1] y + inv[2]) 1024) + rd, Y0 = rint((inv[4] y +
+    inv[5]) 1024) + rd with rd = 512 for nearest and 16 otherwise; rint rounds half to even, one IEEE rounding per operation.
+    nearest: returns (sx, sy) = ((X0 + adelta[x]) >> 10, (Y0 + bdelta[x]) >> 10).  Otherwise (sx, sy, ax, ay): X = (X0 +
+    adelta[x]) >> 5, sx = X >> 5, ax = X & 31, the same for Y.  All shifts are arithmetic, on 32-bit integers; (H, W) int64."""
+    inv = np.asarray(inv, np.float64).reshape(6)
+    x, y = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
+    rd = 512 if nearest else 16
+    adelta, bdelta = _sat_i32(inv[0] * x * 1024.0), _sat_i32(inv[3] * x * 1024.0)
+    X0 = _wrap_i32(_sat_i32((inv[1] * y + inv[2]) * 1024.0) + rd)
+    Y0 = _wrap_i32(_sat_i32((inv[4] * y + inv[5]) * 1024.0) + rd)
+    X, Y = _wrap_i32(X0[:, None] + adelta[None, :]), _wrap_i32(Y0[:, None] + bdelta[None, :])
+    if nearest:
+        return X >> 10, Y >> 10
+    X, Y = X >> 5, Y >> 5
+    return X >> 5, Y >> 5, X & 31, Y & 31
+
+
+def cubic_coeffs(a):
+    """The four float32 bicubic coefficients (A = -0.75) at t = a / 32, a in 0 .. 31, one rounding per operation, evaluated left
+    to right as written in `cubic_weights`; (..., 4) float32."""
+    f32 = np.float32
+    t = np.asarray(a).astype(f32) * f32(1 / 32)
+    A, one = f32(-0.75), f32(1)
+    u, v = t + one, one - t
+    c0 = ((A * u - f32(5) * A) * u + f32(8) * A) * u - f32(4) * A
+    c1 = ((A + f32(2)) * t - (A + f32(3))) * t * t + one
+    c2 = ((A + f32(2)) * v - (A + f32(3))) * v * v + one
+    c3 = one - c0 - c1 - c2
+    out = np.stack([c0, c1, c2, c3], -1)
+    assert out.dtype == np.float32
+    return out
+
+
+def cubic_weights(ay, ax):
+    """The 4 x 4 fixed-point weights of warpAffine's INTER_CUBIC for the fractions ay, ax in 0 .. 31 (1 / 32 pixel): with t =
+    a / 32 in float32 and A = -0.75f, c0 = ((A (t + 1) - 5 A)(t + 1) + 8 A)(t + 1) - 4 A, c1 = ((A + 2) t - (A + 3)) t t + 1, c2 =
+    ((A + 2)(1 - t) - (A + 3))(1 - t)(1 - t) + 1, c3 = 1 - c0 - c1 - c2; weight [k1][k2] = rint(float32(cy[k1] cx[k2]) 32768f) as
+    int32.  If the sixteen do not sum to 32768 the difference is taken from one of the four central weights (k1, k2 in {1, 2}):
+    from the largest when the sum is short, from the smallest when it is long, the first in row-major order on a tie.  So
+    every set sums to exactly 32768 and ay = ax = 0 is the identity.  OpenCV keeps these weights in int16; whether its bytes
+    differ where a weight reaches 32768 is part of what is UNMEASURED.  Returns (..., 4, 4) int32."""
+    f32 = np.float32
+    cy, cx = np.broadcast_arrays(cubic_coeffs(ay), cubic_coeffs(ax))
+    wt = np.rint((cy[..., :, None] * cx[..., None, :]).astype(f32) * f32(32768)).astype(np.int32)
+    diff = 32768 - wt.reshape(wt.shape[:-2] + (16,)).sum(-1)
+    mid = wt[..., 1:3, 1:3].reshape(wt.shape[:-2] + (4,))
+    pick = np.where(diff > 0, mid.argmax(-1), mid.argmin(-1))               # argmax / argmin: the first on a tie
+    add = np.zeros(mid.shape, np.int32)
+    np.put_along_axis(add, pick[..., None], diff[..., None].astype(np.int32), -1)
+    wt = wt.copy()
+    wt[..., 1:3, 1:3] += add.reshape(add.shape[:-1] + (2, 2))
+    return wt
+
+
+def rotate_canvas_u8(canvas, inv):
+    """cv2.warpAffine(canvas, M, (W, H), flags=INTER_CUBIC, borderValue=(128, 128, 128)) on (H, W, 3) uint8 restated, with inv the
+    inverse of M (`rotation_matrices`): (sx, sy, ax, ay) = `warp_coords`, wt = `cubic_weights(ay, ax)`; each channel of output
+    (x, y) is clip((sum_{k1, k2} wt[k1][k2] src[sy - 1 + k1, sx - 1 + k2] + 16384) >> 15, 0, 255); a tap outside the canvas
+    reads 128.  Agreement with cv2's own bytes is UNMEASURED."""
+    a = np.asarray(canvas)
+    H, W = a.shape[:2]
+    sx, sy, ax, ay = warp_coords(inv, H, W, False)
+    wt = cubic_weights(ay, ax).astype(np.int64)
+    acc = np.zeros(a.shape, np.int64)
+    for k1 in range(4):
+        for k2 in range(4):
+            yy, xx = sy - 1 + k1, sx - 1 + k2
+            ok = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+            v = np.where(ok[..., None], a[np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)], 128).astype(np.int64)
+            acc += wt[..., k1, k2, None] * v
+    return np.clip((acc + 16384) >> 15, 0, 255).astype(np.uint8)
+
+
+def rotate_nearest(plane, inv, fill):
+    """cv2.warpAffine(plane, M, (W, H), flags=INTER_NEAREST, borderValue=fill) on an (H, W) array of any type: output (x, y) is
+    plane[sy, sx] of the nearest walk of `warp_coords`, or fill outside.  The label canvas takes fill 0, before the
+    >= num_classes clamp and the one-hot; each radar channel takes fill 0.0 -- this project's definition: the reference
+    rotates no radar map."""
+    a = np.asarray(plane)
+    H, W = a.shape
+    sx, sy = warp_coords(inv, H, W, True)
+    ok = (sy >= 0) & (sy < H) & (sx >= 0) & (sx < W)
+    return np.where(ok, a[np.clip(sy, 0, H - 1), np.clip(sx, 0, W - 1)], np.asarray(fill, a.dtype)).astype(a.dtype)
+
+
+def rotate_boxes(box, fwd, w, h):
+    """The boxes under the rotation -- this project's definition, the segmentation loader has none.  box: the int64 rows [x1,
+    y1, x2, y2, cls] of `augment_boxes` before its clip, changed in place and returned: the four corners go through fwd in
+    float64, x' = fwd[0] x + fwd[1] y + fwd[2], y' = fwd[3] x + fwd[4] y + fwd[5], evaluated left to right; the min and max per
+    axis are stored back into the integer array, which truncates toward zero as every other box stage does.  The clip to the
+    (w, h) canvas and the keep test follow in `augment_boxes`."""
+    fwd = np.asarray(fwd, np.float64).reshape(6)
+    if len(box):
+        xs = box[:, [0, 2, 0, 2]].astype(np.float64)
+        ys = box[:, [1, 1, 3, 3]].astype(np.float64)
+        rx = fwd[0] * xs + fwd[1] * ys + fwd[2]
+        ry = fwd[3] * xs + fwd[4] * ys + fwd[5]
+        box[:, 0], box[:, 2] = rx.min(1), rx.max(1)
+        box[:, 1], box[:, 3] = ry.min(1), ry.max(1)
+    return box
+
+
+def aug_post_record(input_shape, blur, angle):
+    """One AUG_POST_DTYPE record written out by hand: blur on or off, the rotation by `angle` (the reference's `rotation`; 0:
+    no rotation, the warp is then the identity and is skipped) with both matrices of `rotation_matrices`."""
+    rec = np.zeros((), AUG_POST_DTYPE)
+    rec["blur"], rec["rotate"], rec["angle"] = int(bool(blur)), int(int(angle) != 0), int(angle)
+    rec["fwd"], rec["inv"] = rotation_matrices(input_shape, int(angle))
+    return rec
+
+
+def check_aug_post_table(table, input_shape, max_angle=None, batch=None, fn="augment_post_params"):
+    """Raises RuntimeError naming the image index for a post record the kernels would have to clamp: a matrix entry that is
+    not finite, or |angle| above max_angle, the capacity the LDS budget of vrnet_augment_post_frames_u8 was sized for.  Host
+    only.  Returns the table as a contiguous array."""
+    H, W = (int(v) for v in input_shape)
+    table = np.ascontiguousarray(table)
+    if table.dtype != AUG_POST_DTYPE or table.ndim != 1 or (batch is not None and len(table) != batch):
+        raise RuntimeError(f"{fn}: the post table is a ({'B' if batch is None else batch},) array of data.AUG_POST_DTYPE records")
+    if max_angle is not None and not 0 <= int(max_angle) <= AUG_POST_MAX_ANGLE:
+        raise RuntimeError(f"{fn}: 0 <= max_angle <= {AUG_POST_MAX_ANGLE}, got {max_angle}")
+    if min(H, W) < AUG_POST_MIN_SIDE:
+        raise RuntimeError(f"{fn}: blur and rotation need a canvas of at least {AUG_POST_MIN_SIDE} x {AUG_POST_MIN_SIDE}, got {H} x {W}")
+    for b, t in enumerate(table):
+        if not (np.isfinite(t["inv"]).all() and np.isfinite(t["fwd"]).all()):
+            raise RuntimeError(f"{fn}: image {b}: the post record's matrices are not finite")
+        if max_angle is not None and abs(int(t["angle"])) > int(max_angle):
+            raise RuntimeError(f"{fn}: image {b}: the angle {int(t['angle'])} is above max_angle = {int(max_angle)}")
+    return table
+
+
+def augment_post_params(n, input_shape, rng, blur=.25, rotate=.25, max_angle=10):
+    """The random draw of the blur and the rotation, one AUG_POST_DTYPE record per image (`aug_post_bytes` of the table is what
+    the device takes).  Per image, as utils_seg/dataloader.py:113-131: rand() < blur, rand() < rotate, randint(-max_angle,
+    max_angle + 1); all three are always drawn, for the whole batch AFTER `augment_params` has drawn its table from the same
+    RandomState -- and only when blur > 0 or rotate > 0: with both at 0 the generator is not touched, so every seeded result
+    from before this stage existed stays what it was.  rotate is stored as 0 when the drawn angle is 0.  Host only."""
+    rs = rng if isinstance(rng, np.random.RandomState) else np.random.RandomState(rng)
+    tab = np.stack([aug_post_record(input_shape, False, 0)] * int(n)) if n else np.zeros(0, AUG_POST_DTYPE)
+    if blur > 0 or rotate > 0:
+        for b in range(int(n)):
+            blurred, rotated = rs.rand() < blur, rs.rand() < rotate
+            angle = int(rs.randint(-int(max_angle), int(max_angle) + 1))
+            tab[b] = aug_post_record(input_shape, blurred, angle if rotated else 0)
+    return check_aug_post_table(tab, input_shape, max_angle)
+
+
+def aug_post_bytes(table):
+    """An AUG_POST_DTYPE table as the (B, hip.AUG_POST_BYTES) uint8 host tensor the device takes; it shares the table's memory."""
+    return torch.from_numpy(table.view(np.uint8).reshape(len(table), -1))
+
+
+def augment_boxes(box, iw, ih, w, h, rec, post=None):
     """`adjust_boxes` with the window of the record instead of the letterbox's, and box[:, [0, 2]] = w - box[:, [2, 0]] when
     the record flips, before the clip (dataloader.py:237-247, minus its in-place shuffle): integer storage, so every
-    mapped coordinate is truncated toward zero.  With the letterbox window and no flip it equals `adjust_boxes`."""
+    mapped coordinate is truncated toward zero.  With the letterbox window and no flip it equals `adjust_boxes`.  post: an
+    AUG_POST_DTYPE record; when it rotates, `rotate_boxes` runs behind the flip, and the clip follows once."""
     nw, nh, dx, dy = (int(rec[k]) for k in ("nw", "nh", "dx", "dy"))
     out = np.array(box, dtype=np.int64).reshape(-1, 5)
     if out.shape[0] == 0:
@@ -645,6 +870,8 @@ def augment_boxes(box, iw, ih, w, h, rec):
     out[:, [1, 3]] = out[:, [1, 3]] * nh / ih + dy
     if int(rec["flip"]):
         out[:, [0, 2]] = w - out[:, [2, 0]]
+    if post is not None and int(post["rotate"]):
+        rotate_boxes(out, post["fwd"], w, h)
     out[:, 0:2][out[:, 0:2] < 0] = 0
     out[:, 2][out[:, 2] > w] = w
     out[:, 3][out[:, 3] > h] = h
@@ -673,12 +900,15 @@ def augment_radar(radar, input_shape, rec):
     return np.where((oky[:, None] & okx[None, :])[None], out, np.zeros((), radar.dtype)).astype(radar.dtype)
 
 
-def augment_sample(image, seg_label, box, radar, input_shape, rec):
+def augment_sample(image, seg_label, box, radar, input_shape, rec, post=None):
     """One dataset item under the augmentation record rec (`augment_params`), on PIL images and numpy arrays; returns
     (canvas, boxes, label canvas, radar).  Image: resize((nw, nh), BICUBIC) pasted at (dx, dy) on a grey (128) canvas --
     Pillow crops what falls outside -- then FLIP_LEFT_RIGHT of the whole canvas when the record flips, then `hsv_jitter`
     when its colour stage is on (the order of dataloader.py:195-232).  Label: resize((nw, nh), NEAREST) pasted on a 0 canvas
-    and flipped with it (utils_seg/dataloader.py:91-111), no colour stage.  Boxes: `augment_boxes`.  Radar: `augment_radar`."""
+    and flipped with it (utils_seg/dataloader.py:91-111), no colour stage.  Boxes: `augment_boxes`.  Radar: `augment_radar`.
+    post: an AUG_POST_DTYPE record (`augment_post_params`) or None.  Between the flip and the colour stage, in the order of
+    utils_seg/dataloader.py:113-131: `gaussian_blur5_u8` of the canvas when it blurs; when it rotates, `rotate_canvas_u8` of
+    the canvas, `rotate_nearest` of the label canvas (fill 0) and of each radar channel (fill 0.0), `rotate_boxes`."""
     from PIL import Image
     iw, ih = image.size
     h, w = input_shape
@@ -690,13 +920,21 @@ def augment_sample(image, seg_label, box, radar, input_shape, rec):
     if int(rec["flip"]):
         new_image = new_image.transpose(Image.FLIP_LEFT_RIGHT)
         new_label = new_label.transpose(Image.FLIP_LEFT_RIGHT)
+    new_radar = augment_radar(radar, input_shape, rec)
+    if post is not None:                 # utils_seg/dataloader.py:113-131: the blur, then the rotation, before the colour stage
+        if int(post["blur"]):
+            new_image = Image.fromarray(gaussian_blur5_u8(np.array(new_image, np.uint8)))
+        if int(post["rotate"]):
+            new_image = Image.fromarray(rotate_canvas_u8(np.array(new_image, np.uint8), post["inv"]))
+            new_label = Image.fromarray(rotate_nearest(np.array(new_label, np.uint8), post["inv"], 0))
+            new_radar = np.stack([rotate_nearest(ch, post["inv"], 0.0) for ch in new_radar])
     if int(rec["color"]):
         new_image = Image.fromarray(hsv_jitter(np.array(new_image, np.uint8), rec["lut"]))
-    return new_image, augment_boxes(box, iw, ih, w, h, rec), new_label, augment_radar(radar, input_shape, rec)
+    return new_image, augment_boxes(box, iw, ih, w, h, rec, post), new_label, new_radar
 
 
 def device_augment_batch_ragged(frames, sizes, input_shape, labels, boxes, radar, num_classes_seg, params, max_gt=64,
-                                capacity=None, max_taps=None, flag=None, device="cuda"):
+                                capacity=None, max_taps=None, flag=None, device="cuda", post=None, max_angle=10):
     """`device_train_batch_ragged` under the training augmentation: the dataset item `augment_sample` builds per image, for a
     batch of RAW frames of different sizes, ON THE DEVICE -- vrnet_augment_frames_u8 (three launches: the float images),
     vrnet_augment_seg_targets_u8, vrnet_augment_box_targets_f32 and vrnet_augment_radar_f32.  frames / labels / sizes / boxes /
@@ -704,13 +942,50 @@ def device_augment_batch_ragged(frames, sizes, input_shape, labels, boxes, radar
     of its frame; params: an AUG_DTYPE table (`augment_params`, or `aug_record`s written by hand), validated here
     (`check_aug_table`); max_taps: `default_aug_max_taps`.  Returns (images (B,3,H,W) f32, png (B,H,W) int64, onehot
     (B,H,W,ns+1) f32, targets (B,max_gt,5) f32, counts (B) int32, radar (B,4,H,W) f32), bit for bit what the host functions
-    give per image."""
+    give per image.  post: an AUG_POST_DTYPE table (`augment_post_params`, or `aug_post_record`s written by hand; validated
+    here, `check_aug_post_table`) adds the blur and the rotation as `augment_sample(..., post=...)` applies them: the frames
+    go through vrnet_augment_frames_u8 with the colour stage off and vrnet_augment_post_frames_u8, the labels and the radar
+    maps through a nearest gather behind their kernels, the boxes through vrnet_augment_post_box_targets_f32; max_angle: the
+    capacity of the rotation, at least the largest |angle| of the table."""
     from . import hip
     fn = "device_augment_batch_ragged"
+    ops = (hip.augment_frames, hip.augment_seg_targets, hip.augment_box_targets, hip.augment_radar)
+    if post is not None:
+        ops = _post_ops(check_aug_post_table(post, input_shape, max_angle, len(boxes), fn), int(max_angle), device)
     return _device_batch_ragged(
         fn, frames, sizes, input_shape, labels, boxes, radar, num_classes_seg, max_gt, capacity, max_taps, flag, device,
-        default_aug_max_taps, lambda own, shape, cap, taps: augment_bytes(check_aug_params(params, own, shape, cap, taps, fn)),
-        (hip.augment_frames, hip.augment_seg_targets, hip.augment_box_targets, hip.augment_radar))
+        default_aug_max_taps, lambda own, shape, cap, taps: augment_bytes(check_aug_params(params, own, shape, cap, taps, fn)), ops)
+
+
+def aug_without_color(aug):
+    """A copy of the (B, hip.AUG_BYTES) device table with the colour stage of every record off: what vrnet_augment_frames_u8
+    runs on when the post stage follows, which applies the colour behind the rotation."""
+    out = aug.clone()
+    out[:, 28:32] = 0                    # vrnet_aug_rec.color
+    return out
+
+
+def _post_ops(post, max_angle, device):
+    """The four eager operations of `device_augment_batch_ragged` with a post table, in the call shapes of
+    `_device_batch_ragged`'s ops."""
+    from . import hip
+    ptab = aug_post_bytes(post).to(torch.device(device))
+
+    def frames_op(img, tab, H, W, max_taps, images, flag):
+        canvas = torch.empty((len(tab), H, W, 3), dtype=torch.uint8, device=img.device)
+        hip.augment_frames(img, aug_without_color(tab), H, W, max_taps, canvas=canvas, flag=flag)
+        hip.augment_post_frames(canvas, tab, ptab, tuple(img.shape[1:3]), max_angle, images=images, flag=flag)
+
+    def seg_op(lab, tab, H, W, ns, flag):
+        png, onehot = hip.augment_seg_targets(lab, tab, H, W, ns, flag=flag)
+        return hip.augment_post_seg_targets(png, ptab, ns, max_angle, onehot=onehot, flag=flag)
+
+    def box_op(packed, counts, tab, capacity, H, W, flag):
+        return hip.augment_post_box_targets(packed, counts, tab, ptab, capacity, H, W, max_angle, flag=flag)
+
+    def radar_op(rad, tab, capacity, flag):
+        return hip.augment_post_radar(hip.augment_radar(rad, tab, capacity, flag=flag), ptab, max_angle, flag=flag)
+    return frames_op, seg_op, box_op, radar_op
 
 
 def check_aug_params(params, sizes, input_shape, capacity, max_taps, fn):

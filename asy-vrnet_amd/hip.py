@@ -153,6 +153,10 @@ _SIGS = {
     "vrnet_augment_seg_targets_u8": ([P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_augment_box_targets_f32": ([P, P, P, I, I, I, I, I, I, P, P, P, P], I),
     "vrnet_augment_radar_f32": ([P, P, I, I, I, I, I, P, P, P], I),
+    "vrnet_augment_post_frames_u8": ([P, P, P] + [I] * 6 + [P, P, P, P], I),
+    "vrnet_augment_post_seg_targets_i64": ([P, P, I, I, I, I, I, P, P, P, P], I),
+    "vrnet_augment_post_box_targets_f32": ([P, P, P, P] + [I] * 7 + [P, P, P, P], I),
+    "vrnet_augment_post_radar_f32": ([P, P, I, I, I, I, P, P, P], I),
     "vrnet_mosaic_workspace_bytes": ([I] * 6, L),
     "vrnet_mosaic_frames_u8": ([P, I, P] + [I] * 6 + [P, P, P, P, L, P], I),
     "vrnet_mosaic_seg_targets_u8": ([P, I, P, I, I, I, I, I, I, P, P, P, P], I),
@@ -1365,6 +1369,7 @@ FLAG_BOX_COUNT = 512     # VR_FLAG_BOX_COUNT of csrc/common.h: box_targets_ragge
 
 
 AUG_BYTES = 816          # sizeof(vrnet_aug_rec)
+AUG_POST_BYTES = 112     # sizeof(vrnet_aug_post_rec)
 MOSAIC_BYTES = 976       # sizeof(vrnet_mosaic_rec)
 
 
@@ -1381,6 +1386,7 @@ class _TableKind:
 
 _GEOM = _TableKind("geometry", GEOM_BYTES, "{}_ragged", "vrnet_letterbox_ragged_workspace")
 _AUG = _TableKind("augmentation", AUG_BYTES, "augment_{}", "vrnet_letterbox_ragged_workspace")
+_AUG_POST = _TableKind("post", AUG_POST_BYTES, "augment_post_{}", None)
 _MOSAIC = _TableKind("Mosaic", MOSAIC_BYTES, "mosaic_{}", "vrnet_mosaic_workspace_bytes", sources=True)
 
 
@@ -1544,6 +1550,79 @@ def augment_radar(radar, aug, capacity, out=None, flag=None):
     letterbox window of its frame -> out (B,4,H,W) f32, the integer gather of `data.augment_radar`; out is not radar;
     capacity = (ihm, iwm) of the frames' slots, by which the records are judged."""
     return _radar(_AUG, radar, aug, capacity, out, flag)
+
+
+# ---- the blur and the rotation behind the augmentation (include/vrnet_hip.h "the blur and the rotation") ------------------------
+def augment_post_frames(canvas_u8, aug, post, capacity, max_angle, images=None, canvas_out=None, flag=None):
+    """The blur, the rotation and the colour stage behind `augment_frames` (vrnet_augment_post_frames_u8, one launch): canvas_u8
+    (B,H,W,3), what `augment_frames` wrote with the colour stage of every record off; aug the (B, AUG_BYTES) table (its color
+    and tables are applied here); post the (B, AUG_POST_BYTES) table (`data.aug_post_bytes`); capacity = (ihm, iwm) of the
+    frames' slots, by which the aug records are judged; max_angle: the capacity of the rotation -> images (B,3,H,W) f32 and /
+    or canvas_out (B,H,W,3) uint8, not canvas_u8: what `data.augment_sample(..., post=...)` and `device_batch` give per image."""
+    fn = "augment_post_frames"
+    if canvas_u8 is None or canvas_u8.dim() != 4:
+        raise RuntimeError(f"{fn}: expected canvases (B, H, W, 3)")
+    B, H, W = canvas_u8.shape[:3]
+    _tensors(fn, ((canvas_u8, (B, H, W, 3), torch.uint8), (canvas_out, (B, H, W, 3), torch.uint8), (images, (B, 3, H, W), torch.float32),
+                  (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_augment_post_frames_u8(ptr(canvas_u8), _table(_AUG, aug, B, fn)[0], _table(_AUG_POST, post, B, fn)[0], B,
+                                             int(capacity[0]), int(capacity[1]), H, W, int(max_angle), ptr(canvas_out), ptr(images),
+                                             ptr(flag), stream()), fn)
+
+
+def augment_post_seg_targets(png, post, num_classes_seg, max_angle, png_out=None, onehot=None, flag=None):
+    """The label canvas under the rotation (vrnet_augment_post_seg_targets_i64): png (B,H,W) int64, what `augment_seg_targets`
+    wrote -> png_out (B,H,W) int64, not png, and onehot (B,H,W,ns+1) f32: `data.rotate_nearest` with fill 0.  Returns
+    (png_out, onehot)."""
+    fn = "augment_post_seg_targets"
+    if png is None or png.dim() != 3:
+        raise RuntimeError(f"{fn}: expected label canvases (B, H, W)")
+    B, H, W = png.shape
+    ns = int(num_classes_seg)
+    if png_out is None:
+        png_out = torch.empty_like(png)
+    if onehot is None:
+        onehot = torch.empty((B, H, W, ns + 1), dtype=torch.float32, device=png.device)
+    _tensors(fn, ((png, (B, H, W), torch.int64), (png_out, (B, H, W), torch.int64), (onehot, (B, H, W, ns + 1), torch.float32),
+                  (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_augment_post_seg_targets_i64(ptr(png), _table(_AUG_POST, post, B, fn)[0], B, H, W, ns, int(max_angle), ptr(png_out),
+                                                   ptr(onehot), ptr(flag), stream()), fn)
+    return png_out, onehot
+
+
+def augment_post_box_targets(boxes, counts, aug, post, capacity, H, W, max_angle, targets=None, counts_out=None, flag=None):
+    """`augment_box_targets` with the rotation of the post records between the flip and the clip
+    (vrnet_augment_post_box_targets_f32): what `data.augment_boxes(..., post=...)` and `data.boxes_xyxy_to_cxcywh` give per image.
+    Returns (targets, counts_out)."""
+    fn = "augment_post_box_targets"
+    if boxes is None or boxes.dim() != 3:
+        raise RuntimeError(f"{fn}: expected boxes (B, max_gt, 5)")
+    B, max_gt = boxes.shape[:2]
+    if targets is None:
+        targets = torch.empty((B, max_gt, 5), dtype=torch.float32, device=boxes.device)
+    if counts_out is None:
+        counts_out = torch.empty(B, dtype=torch.int32, device=boxes.device)
+    _tensors(fn, ((boxes, (B, max_gt, 5), torch.int32), (counts, (B,), torch.int32), (targets, (B, max_gt, 5), torch.float32),
+                  (counts_out, (B,), torch.int32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_augment_post_box_targets_f32(ptr(boxes), ptr(counts), _table(_AUG, aug, B, fn)[0], _table(_AUG_POST, post, B, fn)[0],
+                                                   B, max_gt, int(capacity[0]), int(capacity[1]), int(H), int(W), int(max_angle),
+                                                   ptr(targets), ptr(counts_out), ptr(flag), stream()), fn)
+    return targets, counts_out
+
+
+def augment_post_radar(radar, post, max_angle, out=None, flag=None):
+    """A finished radar input under the rotation (vrnet_augment_post_radar_f32): radar (B,4,H,W) f32, what `augment_radar` or
+    `radar_map` wrote -> out (B,4,H,W) f32, not radar: `data.rotate_nearest` per channel with fill 0.0."""
+    fn = "augment_post_radar"
+    if radar is None or radar.dim() != 4 or radar.shape[1] != 4:
+        raise RuntimeError(f"{fn}: expected radar maps (B, 4, H, W)")
+    B, _, H, W = radar.shape
+    if out is None:
+        out = torch.empty_like(radar)
+    _tensors(fn, ((radar, (B, 4, H, W), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_augment_post_radar_f32(ptr(radar), _table(_AUG_POST, post, B, fn)[0], B, H, W, int(max_angle), ptr(out), ptr(flag),
+                                             stream()), fn)
+    return out
 
 
 # ---- Mosaic (include/vrnet_hip.h "Mosaic on the device"): one record per OUTPUT image, S source slots --------------------------

@@ -1112,6 +1112,48 @@ int vrnet_augment_box_targets_f32(const int* boxes, const int* counts, const vrn
 int vrnet_augment_radar_f32(const float* radar, const vrnet_aug_rec* aug, int B, int ihm, int iwm, int H, int W, float* out,
                             int* flag, void* stream);
 
+/* ---- the blur and the rotation behind the augmentation (csrc/augment.hip) ---------------------------------------------------
+ * Added within ABI 11: new symbols and one new record layout (vrnet_aug_post_rec) only; the four entry points above are
+ * unchanged in signature and bytes; hip.py binds every declared symbol at import.
+ * utils_seg/dataloader.py:113-131: cv2.GaussianBlur(image, (5, 5), 0) (:113-115) and a rotation about the canvas centre by a
+ * whole angle in [-10, 10] (:117-131: cv2.warpAffine, INTER_CUBIC with a grey (128) border for the image, INTER_NEAREST with a 0
+ * border for the label map), each with probability 0.25, between the flip and the colour stage.  The host draws one
+ * vrnet_aug_post_rec per image (data.augment_post_params) and computes both matrices (data.rotation_matrices); the kernels walk
+ * warpAffine's fixed-point coordinates (AB_BITS = 10, rint in double) from the twelve doubles and equal data.gaussian_blur5_u8,
+ * rotate_canvas_u8, rotate_nearest and rotate_boxes bit for bit.  Those functions restate OpenCV's 8-bit paths from its public
+ * sources; agreement with cv2's own bytes is UNMEASURED.  A record with a matrix entry that is not finite or with |angle| >
+ * max_angle neither blurs nor rotates and sets bit 256 of *flag (VR_FLAG_GEOMETRY; flag may be NULL).  H, W >= 8; 0 <=
+ * max_angle <= 45; the post table must be 8-byte aligned.  One launch each; no host synchronisation; capturable.
+ * vrnet_augment_post_frames_u8: canvas (B, H, W, 3), what vrnet_augment_frames_u8 wrote with the colour stage OFF (the colour
+ *   moves behind the rotation) -> images (B, 3, H, W) fp32 normalised and / or canvas_out (B, H, W, 3), canvas_out != canvas:
+ *   the blur (weights {1, 4, 6, 4, 1} on both axes, BORDER_REFLECT_101, (S + 128) >> 8), the bicubic rotation (4 x 4 taps with
+ *   int32 weights that sum to 32768, a tap outside the canvas reads 128, (sum + 16384) >> 15 clipped), then -- color != 0 in the
+ *   image's vrnet_aug_rec -- the colour stage with its tables.  A workgroup owns a 32 x 8 output tile and stages the bounding
+ *   box of its source pixels in LDS; the box is sized for max_angle (a tile whose box is larger reads grey beyond it and sets
+ *   bit 256).  ihm, iwm only judge the vrnet_aug_rec as the entry points above do.
+ * vrnet_augment_post_seg_targets_i64: png (B, H, W) int64, what vrnet_augment_seg_targets_u8 wrote -> png_out (B, H, W) int64,
+ *   png_out != png, and onehot (B, H, W, ns + 1) fp32 of the rotated label canvas: the nearest walk, 0 outside.
+ * vrnet_augment_post_box_targets_f32: vrnet_augment_box_targets_f32 with the rotation between the flip and the clip: the four
+ *   corners through fwd in double, min and max per axis, truncated toward zero (this project's definition).
+ * vrnet_augment_post_radar_f32: radar (B, 4, H, W), a finished radar input -> out (B, 4, H, W), out != radar: the nearest walk,
+ *   0.0 outside (this project's definition). */
+typedef struct vrnet_aug_post_rec {
+  int blur, rotate;                  /* != 0: blur the canvas; rotate canvas, label map, radar map and boxes */
+  int angle, reserved;               /* the reference's `rotation` in degrees, judged against max_angle */
+  double inv[6], fwd[6];             /* data.rotation_matrices: the map warpAffine walks, and the one the boxes take */
+} vrnet_aug_post_rec;                /* 112 bytes; the table must be 8-byte aligned */
+int vrnet_augment_post_frames_u8(const unsigned char* canvas, const vrnet_aug_rec* aug, const vrnet_aug_post_rec* post, int B,
+                                 int ihm, int iwm, int H, int W, int max_angle, unsigned char* canvas_out, float* images,
+                                 int* flag, void* stream);
+int vrnet_augment_post_seg_targets_i64(const long long* png, const vrnet_aug_post_rec* post, int B, int H, int W,
+                                       int num_classes_seg, int max_angle, long long* png_out, float* onehot, int* flag,
+                                       void* stream);
+int vrnet_augment_post_box_targets_f32(const int* boxes, const int* counts, const vrnet_aug_rec* aug,
+                                       const vrnet_aug_post_rec* post, int B, int max_gt, int ihm, int iwm, int H, int W,
+                                       int max_angle, float* targets, int* counts_out, int* flag, void* stream);
+int vrnet_augment_post_radar_f32(const float* radar, const vrnet_aug_post_rec* post, int B, int H, int W, int max_angle,
+                                 float* out, int* flag, void* stream);
+
 /* ---- Mosaic on the device (csrc/mosaic.hip) ----------------------------------------------------------------------------------
  * Added within ABI 11: new symbols and one new record layout (vrnet_mosaic_rec, with its vrnet_mosaic_tile) only, no existing
  * signature, layout or kernel behaviour changed; hip.py binds every declared symbol at import.
