@@ -25,6 +25,7 @@
 // below them: a frames kernel that reads the uncoloured canvas, and the label, radar and box kernels of the rotation.
 // The tap sum is resample.h's; the paste epilogue, the one-hot store, the box rules and the radar pick are augment.h's.
 #include "augment.h"
+#include "postrec.h"
 
 #pragma clang fp contract(off)
 
@@ -37,15 +38,8 @@ typedef struct vrnet_aug_rec {
   int lb_nw, lb_nh, lb_dx, lb_dy;    /* data.letterbox_geometry: the window the stored radar map is aligned with */
   unsigned char lut[3][256];         /* hue, saturation, value tables of the colour stage */
 } vrnet_aug_rec;
-/* include/vrnet_hip.h: the per-image record of the blur and the rotation (112 bytes). */
-typedef struct vrnet_aug_post_rec {
-  int blur, rotate;                  /* != 0: blur the canvas; rotate canvas, label map, radar map and boxes */
-  int angle, reserved;               /* the reference's `rotation` in degrees, judged against max_angle */
-  double inv[6], fwd[6];             /* data.rotation_matrices: the map warpAffine walks, and the one the boxes take */
-} vrnet_aug_post_rec;
 }
 static_assert(sizeof(vrnet_aug_rec) == 816 && alignof(vrnet_aug_rec) == 4, "vrnet_aug_rec layout");
-static_assert(sizeof(vrnet_aug_post_rec) == 112 && alignof(vrnet_aug_post_rec) == 8, "vrnet_aug_post_rec layout");
 
 namespace {
 
@@ -321,30 +315,6 @@ __global__ __launch_bounds__(256) void augment_radar_kernel(const AugRadarArgs p
 // warpAffine's fixed-point coordinates from them (data.warp_coords) and equal data.gaussian_blur5_u8, rotate_canvas_u8,
 // rotate_nearest and rotate_boxes bit for bit.  The frames kernel reads the UNCOLOURED canvas vrnet_augment_frames_u8 wrote and
 // runs the colour stage behind the rotation; the label map, the radar map and the boxes follow their own kernels above.
-struct PostRec {
-  int blur, rotate;
-  double inv[6], fwd[6];
-};
-
-// Record b, judged: a matrix entry that is not finite, or |angle| above the capacity the caller sized the LDS region for, is
-// `bad`: the record then neither blurs nor rotates (and is reported).  b is block-uniform, so the loads are wave-uniform.
-__device__ __forceinline__ PostRec post_load(const vrnet_aug_post_rec* tab, int b, int max_angle, bool& bad) {
-  const vrnet_aug_post_rec* t = tab + b;
-  PostRec q;
-  bool finite = true;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    q.inv[k] = t->inv[k];
-    q.fwd[k] = t->fwd[k];
-    finite = finite && isfinite(q.inv[k]) && isfinite(q.fwd[k]);
-  }
-  const long angle = t->angle;
-  bad = !finite || angle > max_angle || angle < -(long)max_angle;
-  q.blur = !bad && t->blur != 0;
-  q.rotate = !bad && t->rotate != 0;
-  return q;
-}
-
 // saturate_cast<int>(rint(v)): what cvRound gives the walk for every value a rotation of the canvas can produce
 __device__ __forceinline__ int post_round(double v) {
   const double r = rint(v);
@@ -731,8 +701,8 @@ inline bool post_args_ok(const char* who, const void* post, int B, int H, int W,
     vr_set_error("%s: bad shape (B %d, canvas %d x %d; the blur and the rotation need at least 8 x 8)", who, B, H, W);
     return false;
   }
-  if (max_angle < 0 || max_angle > 45) {
-    vr_set_error("%s: 0 <= max_angle <= 45, got %d", who, max_angle);
+  if (max_angle < 0 || max_angle > POST_MAX_ANGLE) {
+    vr_set_error("%s: 0 <= max_angle <= %d, got %d", who, POST_MAX_ANGLE, max_angle);
     return false;
   }
   return true;

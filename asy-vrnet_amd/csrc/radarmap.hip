@@ -20,6 +20,17 @@
 //   resolve  one thread per pixel: the key's low word names the winner; its four features go to the four planes as BITS
 //            (NaN payloads survive), 0 where the key is still ~0; consecutive lanes store consecutive x
 // Integer atomics only, and a minimum does not depend on the arrival order: the same bytes on every run.
+//
+// Under a rotation (vrnet_radar_map_post_f32: one vrnet_aug_post_rec per image beside the view record) the point pass moves
+// the CENTRE of a kept point through the record's forward matrix -- data.radar_map(..., post=) is the rule -- so the "exactly
+// once" above holds there too, where the nearest gather of a finished map (augment.hip: post radar) drops and duplicates
+// isolated points.  In float64, every operation rounded on its own, left to right as the boxes take fwd:
+//   rx = (fwd[0] X + fwd[1] Y) + fwd[2], ry = (fwd[3] X + fwd[4] Y) + fwd[5]; X' = floor(rx + 0.5), Y' = floor(ry + 0.5)
+//   dropped when (X', Y') is outside the canvas; else the rectangle the point would cover without the rotation (cut to the
+//   canvas and the window, mirrored under flip) is translated by (X' - X, Y' - Y) and cut to the canvas once more
+// The square is not rotated and neither is the window's border.  The same three launches, key plane and resolve kernel; the
+// point kernel is one body, the rotation a compile-time branch of it.
+#include "postrec.h"
 #include "radarpoint.h"
 
 #pragma clang fp contract(off)
@@ -45,6 +56,8 @@ struct RadarMapArgs {
   unsigned long long* keys;          // (B, H, W)
   float* out;                        // (B, 4, H, W)
   int* flag;                         // or null
+  const vrnet_aug_post_rec* post;    // (B); the POST kernel only
+  int max_angle;
 };
 
 __global__ __launch_bounds__(256) void radar_map_init_kernel(unsigned long long* keys, long n) {
@@ -52,21 +65,27 @@ __global__ __launch_bounds__(256) void radar_map_init_kernel(unsigned long long*
   if (i < n) keys[i] = RM_EMPTY;
 }
 
+// POST: the image's post record is judged as the post kernels of augment.hip judge it, and a record that rotates moves the
+// footprint of every kept point; !POST is the point pass of vrnet_radar_map_f32
+template <bool POST>
 __global__ __launch_bounds__(256) void radar_map_points_kernel(const RadarMapArgs p) {
   const int b = blockIdx.y;
   const vrnet_radar_view g = p.views[b];
   const bool bad = g.ih <= 0 || g.iw <= 0 || g.nw <= 0 || g.nh <= 0;
   const int count = vr_clampi(g.count, 0, p.max_points);
+  bool qbad = false;
+  PostRec q;
+  if constexpr (POST) q = post_load(p.post, b, p.max_angle, qbad);
   if (blockIdx.x == 0 && threadIdx.x == 0 && p.flag) {
-    const int bits = (bad ? VR_FLAG_GEOMETRY : 0) | (count != g.count ? VR_FLAG_POINT_COUNT : 0);
+    const int bits = (bad || qbad ? VR_FLAG_GEOMETRY : 0) | (count != g.count ? VR_FLAG_POINT_COUNT : 0);
     if (bits) atomicOr(p.flag, bits);
   }
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (bad || i >= count) return;
-  const float* q = p.points + ((long)b * p.max_points + i) * RM_POINT_FLOATS;
+  const float* pt = p.points + ((long)b * p.max_points + i) * RM_POINT_FLOATS;
   int ix, iy;
   float hw;
-  if (!rm_project(g.P, q, p.min_depth, g.ih, g.iw, g.nw, g.nh, ix, iy, hw)) return;      // radarpoint.h
+  if (!rm_project(g.P, pt, p.min_depth, g.ih, g.iw, g.nw, g.nh, ix, iy, hw)) return;     // radarpoint.h
   // the centre in canvas coordinates before the flip; 64-bit: a hostile dx + ix must not wrap
   const long long cx = (long long)g.dx + ix, cy = (long long)g.dy + iy;
   // covered = the footprint cut by the canvas and by the window; every bound below is inside [0, W) x [0, H)
@@ -77,11 +96,29 @@ __global__ __launch_bounds__(256) void radar_map_points_kernel(const RadarMapArg
   x1 = x1 > p.W - 1 ? p.W - 1 : x1;  x1 = x1 > wx1 ? wx1 : x1;
   y1 = y1 > p.H - 1 ? p.H - 1 : y1;  y1 = y1 > wy1 ? wy1 : y1;
   if (x0 > x1 || y0 > y1) return;
+  if (g.flip) {                        // the columns of the finished canvas: still inside [0, W)
+    const long long t = p.W - 1 - x1;
+    x1 = p.W - 1 - x0;
+    x0 = t;
+  }
+  if constexpr (POST) {
+    if (q.rotate) {
+      const long long X = g.flip ? p.W - 1 - cx : cx;          // |X| < 2^33: exact as a double
+      const double rx = (q.fwd[0] * (double)X + q.fwd[1] * (double)cy) + q.fwd[2];
+      const double ry = (q.fwd[3] * (double)X + q.fwd[4] * (double)cy) + q.fwd[5];
+      const double fx = floor(rx + 0.5), fy = floor(ry + 0.5);
+      if (!(fx >= 0.0 && fx < (double)p.W && fy >= 0.0 && fy < (double)p.H)) return;      // a NaN fails here too
+      const long long tx = (int)fx - X, ty = (int)fy - cy;      // 0 <= fx < W, 0 <= fy < H
+      x0 += tx;  x1 += tx;  y0 += ty;  y1 += ty;               // the cut rectangle follows its centre, then the canvas cuts it
+      x0 = x0 < 0 ? 0 : x0;  x1 = x1 > p.W - 1 ? p.W - 1 : x1;
+      y0 = y0 < 0 ? 0 : y0;  y1 = y1 > p.H - 1 ? p.H - 1 : y1;
+      if (x0 > x1 || y0 > y1) return;
+    }
+  }
   const unsigned long long key = rm_key(hw, i);
   unsigned long long* plane = p.keys + (long)b * p.H * p.W;
   for (int yy = (int)y0; yy <= (int)y1; ++yy)
-    for (int xx = (int)x0; xx <= (int)x1; ++xx)
-      atomicMin(plane + (long)yy * p.W + (g.flip ? p.W - 1 - xx : xx), key);
+    for (int xx = (int)x0; xx <= (int)x1; ++xx) atomicMin(plane + (long)yy * p.W + xx, key);
 }
 
 __global__ __launch_bounds__(256) void radar_map_resolve_kernel(const RadarMapArgs p) {
@@ -110,20 +147,26 @@ extern "C" long vrnet_radar_map_workspace(int B, int H, int W) {
   return radar_map_bytes(B, H, W);
 }
 
-extern "C" int vrnet_radar_map_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W,
-                                   int radius, float min_depth, float* out, int* flag, void* workspace, long workspace_bytes,
-                                   void* stream) {
-  VR_CHECK_ARG(points && views && out, "radar_map: points, views and out are required");
+namespace {
+
+// both entry points: post == nullptr is vrnet_radar_map_f32
+int radar_map_run(const char* who, const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W,
+                  int radius, float min_depth, const vrnet_aug_post_rec* post, int max_angle, float* out, int* flag,
+                  void* workspace, long workspace_bytes, void* stream) {
+  VR_CHECK_ARG(points && views && out, "%s: points, views and out are required", who);
   VR_CHECK_ARG(B > 0 && B < 65536 && max_points > 0 && max_points <= (1 << 24) && H > 0 && W > 0 && H < (1 << 24) &&
                    W < (1 << 24) && (long)B * 4 * H * W < (1L << 40),
-               "radar_map: bad shape (B %d, max_points %d, canvas %d x %d)", B, max_points, H, W);
-  VR_CHECK_ARG(radius >= 0 && radius <= 8, "radar_map: 0 <= radius <= 8, got %d", radius);
-  VR_CHECK_ARG(min_depth > 0.f && min_depth < INFINITY, "radar_map: min_depth must be positive and finite, got %g",
+               "%s: bad shape (B %d, max_points %d, canvas %d x %d)", who, B, max_points, H, W);
+  VR_CHECK_ARG(radius >= 0 && radius <= 8, "%s: 0 <= radius <= 8, got %d", who, radius);
+  VR_CHECK_ARG(min_depth > 0.f && min_depth < INFINITY, "%s: min_depth must be positive and finite, got %g", who,
                (double)min_depth);
-  VR_CHECK_ARG((reinterpret_cast<uintptr_t>(views) & 7) == 0, "radar_map: the view table must be 8-byte aligned");
+  VR_CHECK_ARG((reinterpret_cast<uintptr_t>(views) & 7) == 0, "%s: the view table must be 8-byte aligned", who);
+  VR_CHECK_ARG(!post || (reinterpret_cast<uintptr_t>(post) & 7) == 0, "%s: the post table must be 8-byte aligned", who);
+  VR_CHECK_ARG(!post || (max_angle >= 0 && max_angle <= POST_MAX_ANGLE), "%s: 0 <= max_angle <= %d, got %d", who, POST_MAX_ANGLE,
+               max_angle);
   const long need = radar_map_bytes(B, H, W);
   if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7)) {
-    vr_set_error("radar_map: workspace %ld < %ld bytes, or not 8-byte aligned", workspace ? workspace_bytes : 0L, need);
+    vr_set_error("%s: workspace %ld < %ld bytes, or not 8-byte aligned", who, workspace ? workspace_bytes : 0L, need);
     return VR_ERR_WORKSPACE;
   }
   RadarMapArgs p{};
@@ -132,11 +175,32 @@ extern "C" int vrnet_radar_map_f32(const float* points, int max_points, const vr
   p.min_depth = min_depth;
   p.keys = static_cast<unsigned long long*>(workspace);
   p.out = out; p.flag = flag;
+  p.post = post; p.max_angle = max_angle;
   hipStream_t st = vr_stream(stream);
   const long n = (long)B * H * W;
+  const dim3 pgrid((unsigned)vr_cdiv(max_points, 256), B);
   hipLaunchKernelGGL(radar_map_init_kernel, dim3((unsigned)vr_cdiv(n, 256)), dim3(256), 0, st, p.keys, n);
-  hipLaunchKernelGGL(radar_map_points_kernel, dim3((unsigned)vr_cdiv(max_points, 256), B), dim3(256), 0, st, p);
+  if (post)
+    hipLaunchKernelGGL(radar_map_points_kernel<true>, pgrid, dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL(radar_map_points_kernel<false>, pgrid, dim3(256), 0, st, p);
   hipLaunchKernelGGL(radar_map_resolve_kernel, dim3((unsigned)vr_cdiv((long)H * W, 256), B), dim3(256), 0, st, p);
-  VR_LAUNCH_CHECK("radar_map");
+  VR_LAUNCH_CHECK(who);
   return VR_OK;
+}
+
+}  // namespace
+
+extern "C" int vrnet_radar_map_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W,
+                                   int radius, float min_depth, float* out, int* flag, void* workspace, long workspace_bytes,
+                                   void* stream) {
+  return radar_map_run("radar_map", points, max_points, views, B, H, W, radius, min_depth, nullptr, 0, out, flag, workspace,
+                       workspace_bytes, stream);
+}
+
+extern "C" int vrnet_radar_map_post_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W,
+                                        int radius, float min_depth, const vrnet_aug_post_rec* post, int max_angle, float* out,
+                                        int* flag, void* workspace, long workspace_bytes, void* stream) {
+  return radar_map_run(post ? "radar_map_post" : "radar_map", points, max_points, views, B, H, W, radius, min_depth, post, max_angle,
+                       out, flag, workspace, workspace_bytes, stream);
 }

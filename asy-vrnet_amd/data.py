@@ -1480,7 +1480,7 @@ def radar_project(points, P, size, window, min_depth=0.1):
     return ok, ix, iy, hw
 
 
-def radar_map(points, P, size, input_shape, window, flip=False, radius=0, min_depth=0.1):
+def radar_map(points, P, size, input_shape, window, flip=False, radius=0, min_depth=0.1, post=None):
     """The network's radar input (4, H, W) float32 of ONE image from its radar points -- this project's own definition, the
     reference has none.  points (n, 7) float32 rows x, y, z, f0, f1, f2, f3: the position in the radar's frame and the four
     features in the order of the map's channels (the reference names range, velocity, elevation and power).  P (3, 4)
@@ -1498,8 +1498,19 @@ def radar_map(points, P, size, input_shape, window, flip=False, radius=0, min_de
     A kept point covers the pixels (X + ox, Y + oy), |ox|, |oy| <= radius (0..8), inside the canvas and inside the window's
     extent on the canvas (mirrored under flip): nothing is written outside the window.  Of the points covering a pixel the
     one with the smallest hw wins, the lowest index among equal hw; out[c, Y, X] = f_c of the winner, copied bit for bit, 0
-    where no point lands.  The min-max normalisation of the prediction scripts stays `device_radar(normalise=True)`."""
+    where no point lands.  The min-max normalisation of the prediction scripts stays `device_radar(normalise=True)`.
+    post: one AUG_POST_DTYPE record (`augment_post_params`, `aug_post_record`) or None.  Only its rotation is looked at; None
+    or rotate == 0 changes nothing above.  When it rotates, the CENTRE (X, Y) of a kept point goes through fwd in float64,
+    every operation rounded on its own, left to right as `rotate_boxes` does:
+        rx = (fwd[0] X + fwd[1] Y) + fwd[2], ry = (fwd[3] X + fwd[4] Y) + fwd[5]
+        X' = floor(rx + 0.5), Y' = floor(ry + 0.5)      (pixel centres on integers, the rounding of `warp_coords`' nearest walk)
+    A point whose (X', Y') is outside the canvas is dropped.  Otherwise the rectangle the point covers WITHOUT the rotation --
+    already cut to the canvas and to the window's extent, mirrored under flip -- is translated by (X' - X, Y' - Y) and cut to
+    the canvas once more.  The square is not rotated and neither is the window's border; the winner of a pixel is chosen as
+    above.  Every point moves exactly once: `rotate_nearest` of a finished map drops some isolated pixels and doubles others.
+    The record is taken as it is (the host check is `check_aug_post_table`, the caller's)."""
     radius = check_radar_rule(radius, min_depth)[0]
+    fwd = [float(v) for v in np.asarray(post["fwd"]).reshape(6)] if post is not None and int(post["rotate"]) else None
     H, W = (int(v) for v in input_shape)
     ih, iw = (int(v) for v in size)
     nw, nh, dx, dy = (int(v) for v in window)
@@ -1518,7 +1529,20 @@ def radar_map(points, P, size, input_shape, window, flip=False, radius=0, min_de
         if x0 > x1 or y0 > y1:
             continue
         key = np.uint64((int(depth[i]) << 32) | i)
-        xs = slice(W - 1 - x1, W - x0) if flip else slice(x0, x1 + 1)
+        if flip:                                 # the columns of the finished canvas
+            x0, x1 = W - 1 - x1, W - 1 - x0
+        if fwd is not None:
+            X, Y = W - 1 - cx if flip else cx, cy
+            rx = (fwd[0] * float(X) + fwd[1] * float(Y)) + fwd[2]
+            ry = (fwd[3] * float(X) + fwd[4] * float(Y)) + fwd[5]
+            fx, fy = np.floor(rx + 0.5), np.floor(ry + 0.5)
+            if not (0 <= fx < W and 0 <= fy < H):        # a NaN fails here too
+                continue
+            tx, ty = int(fx) - X, int(fy) - Y
+            x0, x1, y0, y1 = max(x0 + tx, 0), min(x1 + tx, W - 1), max(y0 + ty, 0), min(y1 + ty, H - 1)
+            if x0 > x1 or y0 > y1:
+                continue
+        xs = slice(x0, x1 + 1)
         won = best[y0:y1 + 1, xs] > key              # hw > 0 and finite: its bits order as an integer; the index breaks ties
         best[y0:y1 + 1, xs][won] = key
         for c in range(4):
@@ -1527,14 +1551,16 @@ def radar_map(points, P, size, input_shape, window, flip=False, radius=0, min_de
 
 
 def device_radar_map(points, sizes, input_shape, calib, letterbox_image=True, radius=0, min_depth=0.1, max_points=None,
-                     views=None, device="cuda", out=None, flag=None):
+                     views=None, device="cuda", out=None, flag=None, post=None, max_angle=10):
     """`radar_map` for a batch ON THE DEVICE (vrnet_radar_map_f32, three launches): points as `pack_points` takes them, sizes
     (B, 2) = (ih, iw) of the original frames, calib (3, 4) or (B, 3, 4) -> (B, 4, H, W) float32 on the device, bit for bit what
     `radar_map` gives per image under the letterbox window of its frame (the whole canvas with letterbox_image=False).
     max_points: the capacity of the point buffer (default: the largest count).  views: a `radar_views` table to use instead
     (an augmentation's windows; its counts are replaced by the points' own); sizes and calib are then not read.  flag: an int32
     device word that receives hip.FLAG_GEOMETRY / hip.FLAG_POINT_COUNT (never, for a table this function built).  The
-    points and the table are copied non_blocking; no host synchronisation."""
+    points and the table are copied non_blocking; no host synchronisation.  post: an AUG_POST_DTYPE table, one record per
+    image (validated here, `check_aug_post_table`, which names the image): the rotation of `radar_map(..., post=)` inside the
+    point pass (vrnet_radar_map_post_f32, the same three launches); max_angle: at least the largest |angle| of the table."""
     from . import hip
     fn = "device_radar_map"
     radius, md = check_radar_rule(radius, min_depth, fn)
@@ -1554,12 +1580,18 @@ def device_radar_map(points, sizes, input_shape, calib, letterbox_image=True, ra
         if views.dtype != RADAR_VIEW_DTYPE or views.shape != (B,):
             raise RuntimeError(f"{fn}: views is a ({B},) array of data.RADAR_VIEW_DTYPE records")
         views["count"] = counts.numpy()
+    if post is not None:
+        post = check_aug_post_table(post, (H, W), max_angle, B, fn)
     dev = torch.device(device)
     with torch.cuda.device(dev):
         if out is None:
             out = torch.empty((B, 4, H, W), dtype=torch.float32, device=dev)
-        hip.radar_map(packed.to(dev, non_blocking=True), radar_view_bytes(views).to(dev, non_blocking=True), H, W, radius,
-                      float(md), out, flag=flag)
+        pts, vw = packed.to(dev, non_blocking=True), radar_view_bytes(views).to(dev, non_blocking=True)
+        if post is None:
+            hip.radar_map(pts, vw, H, W, radius, float(md), out, flag=flag)
+        else:
+            hip.radar_map_post(pts, vw, aug_post_bytes(post).to(dev, non_blocking=True), H, W, radius, float(md), int(max_angle), out,
+                               flag=flag)
     return out
 
 

@@ -164,6 +164,7 @@ _SIGS = {
     "vrnet_mosaic_radar_f32": ([P, I, P, I, I, I, I, I, P, P, P], I),
     "vrnet_radar_map_workspace": ([I, I, I], L),
     "vrnet_radar_map_f32": ([P, I, P, I, I, I, I, F, P, P, P, L, P], I),
+    "vrnet_radar_map_post_f32": ([P, I, P, I, I, I, I, F, P, I, P, P, P, L, P], I),
     "vrnet_mosaic_radar_points_workspace": ([I, I, I], L),
     "vrnet_mosaic_radar_points_f32": ([P, I, I, P, P, I, I, I, I, I, I, F, P, P, P, L, P], I),
     "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
@@ -1677,27 +1678,46 @@ def radar_map_workspace_bytes(B, H, W):
     return _lib.vrnet_radar_map_workspace(B, H, W)
 
 
+def _radar_map(fn, points, views, H, W, radius, min_depth, out, flag, ws, post=None, max_angle=0):
+    """`radar_map` and `radar_map_post`: one body, the post table optional."""
+    if points is None or points.dim() != 3 or points.shape[2] != 7 or points.shape[1] < 1:
+        raise RuntimeError(f"{fn}: expected points (B, max_points, 7)")
+    B, max_points = points.shape[:2]
+    H, W = int(H), int(W)
+    _tensors(fn, ((points, (B, max_points, 7), torch.float32), (out, (B, 4, H, W), torch.float32), (flag, (1,), torch.int32)))
+    if out is None:
+        raise RuntimeError(f"{fn}: out is required")
+    need = _lib.vrnet_radar_map_workspace(B, H, W)
+    if ws is None:
+        ws = _ws.get(need, points.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"{fn}: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    head = (ptr(points), max_points, _views(views, B, fn), B, H, W, int(radius), float(min_depth))
+    tail = (ptr(out), ptr(flag), ptr(ws), ws.numel(), stream())
+    if post is None:
+        _check(_lib.vrnet_radar_map_f32(*head, *tail), fn)
+    else:
+        _check(_lib.vrnet_radar_map_post_f32(*head, _table(_AUG_POST, post, B, fn)[0], int(max_angle), *tail), fn)
+    return out
+
+
 def radar_map(points, views, H, W, radius, min_depth, out, flag=None, ws=None):
     """Radar points -> the network's radar input (vrnet_radar_map_f32): points (B, max_points, 7) f32 rows x, y, z, f0..f3,
     views the (B, RADAR_VIEW_BYTES) table -> out (B, 4, H, W) f32, what `data.radar_map` gives per image, bit for bit; radius
     0..8, min_depth > 0; flag (1) int32 or None: FLAG_GEOMETRY for a record without pixels, FLAG_POINT_COUNT for a clamped
     count; ws: radar_map_workspace_bytes(B, H, W) bytes.  Three launches.  Returns out."""
-    if points is None or points.dim() != 3 or points.shape[2] != 7 or points.shape[1] < 1:
-        raise RuntimeError("radar_map: expected points (B, max_points, 7)")
-    B, max_points = points.shape[:2]
-    H, W = int(H), int(W)
-    _tensors("radar_map", ((points, (B, max_points, 7), torch.float32), (out, (B, 4, H, W), torch.float32),
-                           (flag, (1,), torch.int32)))
-    if out is None:
-        raise RuntimeError("radar_map: out is required")
-    need = _lib.vrnet_radar_map_workspace(B, H, W)
-    if ws is None:
-        ws = _ws.get(need, points.device)
-    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
-        raise RuntimeError(f"radar_map: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
-    _check(_lib.vrnet_radar_map_f32(ptr(points), max_points, _views(views, B, "radar_map"), B, H, W, int(radius), float(min_depth),
-                                    ptr(out), ptr(flag), ptr(ws), ws.numel(), stream()), "radar_map")
-    return out
+    return _radar_map("radar_map", points, views, H, W, radius, min_depth, out, flag, ws)
+
+
+def radar_map_post(points, views, post, H, W, radius, min_depth, max_angle, out, flag=None, ws=None):
+    """`radar_map` under the rotation of the post stage (vrnet_radar_map_post_f32): post the (B, AUG_POST_BYTES) table
+    (`data.aug_post_bytes`), max_angle the capacity its records are judged by -> out (B, 4, H, W) f32, what
+    `data.radar_map(..., post=)` gives per image, bit for bit: the centre of every kept point goes through the record's
+    forward matrix once, its cut footprint follows it.  flag receives FLAG_GEOMETRY also for a post record that is not finite
+    or above max_angle (that image is then not rotated).  The same three launches and workspace.  Returns out."""
+    if post is None:
+        raise RuntimeError("radar_map_post: the post table is required (radar_map is the call without one)")
+    return _radar_map("radar_map_post", points, views, H, W, radius, min_depth, out, flag, ws, post, max_angle)
 
 
 # ---- radar points under Mosaic (include/vrnet_hip.h "radar points under Mosaic") ----------------------------------------------

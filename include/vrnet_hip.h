@@ -1253,6 +1253,30 @@ long vrnet_radar_map_workspace(int B, int H, int W);
 int vrnet_radar_map_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W, int radius,
                         float min_depth, float* out, int* flag, void* workspace, long workspace_bytes, void* stream);
 
+/* ---- the radar map from points under a rotation (csrc/radarmap.hip; the record and its judgement: csrc/postrec.h) ----------------
+ * Added within ABI 11: one new symbol only, no existing signature, layout or kernel behaviour changed -- vrnet_radar_map_f32
+ * writes the bytes it wrote before; hip.py binds every declared symbol at import.
+ * vrnet_radar_map_f32 with the rotation of the post stage inside the point pass (host statement: data.radar_map(..., post=)):
+ * post is the (B) table of vrnet_aug_post_rec the vrnet_augment_post_* entry points read, 8-byte aligned, 0 <= max_angle <= 45.
+ * Only the ROTATION of a record is looked at (a blur does not move a point), and only its forward matrix is applied.  For a
+ * record that rotates, after the canvas pixel (X, Y) of a kept point has been computed as above, flip included -- in
+ * float64, every operation rounded on its own, left to right as vrnet_augment_post_box_targets_f32 takes fwd, nothing contracted:
+ *   rx = (fwd[0] X + fwd[1] Y) + fwd[2], ry = (fwd[3] X + fwd[4] Y) + fwd[5]
+ *   X' = floor(rx + 0.5), Y' = floor(ry + 0.5)     (pixel centres on integers, the rounding of the nearest walk)
+ *   the point is dropped when (X', Y') is outside the canvas (a NaN counts as outside)
+ *   else the rectangle it would cover without the rotation -- already cut to the canvas and to the window's extent, mirrored
+ *   under flip -- is translated by (X' - X, Y' - Y) and cut to the canvas once more
+ * The square is NOT rotated and neither is the window's border: a translated footprint may cross the rotated image of the
+ * border by the footprint's own size.  The winner of a pixel is chosen as before.  Every point moves exactly once, where
+ * vrnet_augment_post_radar_f32, the nearest gather of a FINISHED map, drops some isolated one-pixel points and duplicates others.
+ * A record with a matrix entry that is not finite or with |angle| > max_angle does not rotate its image and sets bit 256 of
+ * *flag (VR_FLAG_GEOMETRY), as in the other post entry points; the view record's own rules hold as above.  post == NULL is
+ * vrnet_radar_map_f32.  The same three launches, workspace, key plane and resolve kernel; the point kernel is the same body with
+ * the rotation compiled in.  64-bit integer atomic minimum only; no allocation, no memset, no host synchronisation; capturable. */
+int vrnet_radar_map_post_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, int H, int W, int radius,
+                             float min_depth, const vrnet_aug_post_rec* post, int max_angle, float* out, int* flag,
+                             void* workspace, long workspace_bytes, void* stream);
+
 /* ---- radar points under Mosaic (csrc/mosaic.hip; the projection of a point: csrc/radarpoint.h) ---------------------------------
  * Added within ABI 11: new symbols and one new record layout (vrnet_radar_source) only, no existing signature, layout or kernel
  * behaviour changed; hip.py binds every declared symbol at import.

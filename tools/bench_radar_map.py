@@ -8,6 +8,13 @@
      synchronise, rounds alternating between the two pipelines.
 
     python tools/bench_radar_map.py --batch 8 --size 512 --points 4096 --radii 0,2 --frame 480x640
+
+--post times the radar map under the rotation of the post stage instead (vrnet_radar_map_post_f32), the same way (1): per radius,
+in alternating rounds, a captured replay of vrnet_radar_map_f32, of vrnet_radar_map_post_f32 with no record rotating, of the same
+with every record rotating by +-10 degrees, and of what a finished map needs instead: vrnet_radar_map_f32 followed by the nearest
+gather vrnet_augment_post_radar_f32 on those records.  The last line is one JSON record.
+
+    python tools/bench_radar_map.py --post --batch 8 --size 512 --points 4096 --radii 0,2 --frame 480x640 --steps 1000
 """
 import argparse
 import os
@@ -59,6 +66,63 @@ def summary(rounds):
     return f"{statistics.median(rounds):.4f} ms (rounds {min(rounds):.4f}..{max(rounds):.4f})"
 
 
+def post_main(args):
+    import json
+    B, S, N = args.batch, args.size, args.points
+    frame = tuple(int(v) for v in args.frame.split("x"))
+    radii = [int(r) for r in args.radii.split(",")]
+    P = camera(frame)
+    pts = [cloud(b, N) for b in range(B)]
+    table = data.frame_geometry([frame] * B, (S, S))
+    packed, counts = data.pack_points(pts, N)
+    points_d = packed.cuda()
+    views_d = data.radar_view_bytes(data.radar_views(table, P, counts.numpy())).cuda()
+    off = np.stack([data.aug_post_record((S, S), False, 0)] * B)
+    on = np.stack([data.aug_post_record((S, S), False, 10 if b % 2 else -10) for b in range(B)])
+    tabs = {"off": data.aug_post_bytes(off).cuda(), "on": data.aug_post_bytes(on).cuda()}
+    out, mid = torch.empty((B, 4, S, S), device="cuda"), torch.empty((B, 4, S, S), device="cuda")
+    ws = torch.empty(hip.radar_map_workspace_bytes(B, S, S), dtype=torch.uint8, device="cuda")
+    calls = {"vrnet_radar_map_f32": lambda r: hip.radar_map(points_d, views_d, S, S, r, 0.1, out, ws=ws),
+             "vrnet_radar_map_post_f32, no record rotates": lambda r: hip.radar_map_post(points_d, views_d, tabs["off"], S, S, r, 0.1, 10, out, ws=ws),
+             "vrnet_radar_map_post_f32, every record +-10": lambda r: hip.radar_map_post(points_d, views_d, tabs["on"], S, S, r, 0.1, 10, out, ws=ws),
+             "vrnet_radar_map_f32 + vrnet_augment_post_radar_f32, +-10": lambda r: (
+                 hip.radar_map(points_d, views_d, S, S, r, 0.1, mid, ws=ws), hip.augment_post_radar(mid, tabs["on"], 10, out=out))}
+    stream = torch.cuda.Stream()
+    graphs, lit = {}, {}
+    with torch.cuda.stream(stream):
+        for r in radii:
+            for name, fn in calls.items():
+                for _ in range(2):
+                    fn(r)
+                torch.cuda.synchronize()
+                graphs[name, r] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[name, r], stream=stream):
+                    fn(r)
+                graphs[name, r].replay()
+                torch.cuda.synchronize()
+                lit[name, r] = int((out != 0).any(1).sum())
+        # image 0 at the first radius against the host rule, bit for bit
+        graphs["vrnet_radar_map_post_f32, every record +-10", radii[0]].replay()
+        torch.cuda.synchronize()
+        want = data.radar_map(pts[0], P, frame, (S, S), data.letterbox_geometry(frame[1], frame[0], S, S), False, radii[0], 0.1, post=on[0])
+        same = bool(np.array_equal(out[0].cpu().numpy().view(np.uint32), want.view(np.uint32)))
+        times = {k: [] for k in graphs}
+        for _ in range(args.rounds):                        # alternating: a drift of the box hits every contender alike
+            for k in graphs:
+                times[k].append(device_ms(graphs[k].replay, args.steps))
+    torch.cuda.synchronize()
+    print(f"radar map from points under a rotation, bs={B}, {S}x{S}, {N} points per frame, frames {frame[0]}x{frame[1]}; image 0 at radius "
+          f"{radii[0]} equals data.radar_map(..., post=): {same}; device time per captured replay, median of {args.rounds} alternating "
+          f"rounds of {args.steps}; device {torch.cuda.get_device_name(0)}")
+    rec = {"tool": "bench_radar_map --post", "batch": B, "size": S, "points": N, "frame": list(frame), "rounds": args.rounds,
+           "steps": args.steps, "equals_host": same}
+    for (name, r), v in times.items():
+        print(f"  radius {r}  {name:58s} {summary(v)}  {lit[name, r]} pixels lit")
+        rec[f"radius {r}: {name}"] = {"median_ms": round(statistics.median(v), 5), "min_ms": round(min(v), 5), "max_ms": round(max(v), 5),
+                                      "lit": lit[name, r]}
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -69,9 +133,12 @@ def main():
     ap.add_argument("--phi", default="nano")
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--post", action="store_true", help="the map under the rotation of the post stage against the plain map and the gather")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_radar_map: needs a GPU; nothing is measured without one")
+    if args.post:
+        return post_main(args)
     B, S, N = args.batch, args.size, args.points
     frame = tuple(int(v) for v in args.frame.split("x"))
     radii = [int(r) for r in args.radii.split(",")]
