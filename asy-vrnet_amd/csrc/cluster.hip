@@ -902,6 +902,17 @@ extern "C" long vrnet_cluster_state_floats(int B, int H, int W, int E, int fold)
   return (long)B * E * fold * fold * CL_STATE;
 }
 
+/* What a launch on regions of N points in `blocks` = B * E * fold^2 workgroups runs (host only; bwd != 0: the backward):
+ * *T = threads per workgroup of the register kernel, *npt = its points per lane group (the template argument); *T = 0,
+ * *npt = 0: the streaming kernel.  Answered by the cluster_plan the launchers call; refuses what cluster_check refuses of
+ * (N, blocks). */
+extern "C" int vrnet_cluster_plan(int N, long blocks, int bwd, int* T, int* npt) {
+  VR_CHECK_ARG(T && npt, "cluster_plan: null output");
+  VR_CHECK_ARG(N > 0 && blocks > 0, "cluster_plan: bad shape");
+  VR_CHECK_ARG(cluster_plan(N, blocks, T, npt, bwd ? 1 : 0) == 0, "cluster_plan: unsupported region of %d points", N);
+  return VR_OK;
+}
+
 /* The same forward with the hard assignment GIVEN (idx is read, not written): every point goes to the centre idx names,
  * with that centre's similarity.  For parity work: two arithmetic paths can only be compared to rounding level when the
  * numerically tied points of the arg-max (vr_coc.py:173-176) are decided the same way in both. */

@@ -95,6 +95,7 @@ _SIGS = {
     "vrnet_fill_f32": ([P, F, L, P], I),
     "vrnet_cluster_fwd_f32": ([P, P, L, P, P, P, L, P, P, I, I, I, I, I, I, P, P, P], I),
     "vrnet_cluster_fwd_forced_f32": ([P, P, L, P, P, P, L, P, P, I, I, I, I, I, I, P, P, P], I),
+    "vrnet_cluster_plan": ([I, L, I, P, P], I),
     "vrnet_cluster_bwd_workspace": ([I, I, I], L),
     "vrnet_cluster_bwd_workspace2": ([I, I, I, I, I], L),
     "vrnet_cluster_bwd_f32": ([P, P, L, P, P, P, P, L, P, P, L, P, P, I, I, I, I, I, I, I, P, P, P, P, P, L, P], I),
@@ -753,6 +754,14 @@ def fill_(dst, value):
 def cluster_state_floats(B, H, W, E, fold):
     """Floats of per-region forward state for regions of more than 256 points (0: none needed)."""
     return _lib.vrnet_cluster_state_floats(B, H, W, E, fold)
+
+
+def cluster_plan(N, blocks, bwd):
+    """(T, NPT) of the register kernel a Cluster launch on regions of N points in `blocks` = B * E * fold^2 workgroups runs,
+    (0, 0) for the streaming kernel (vrnet_cluster_plan in include/vrnet_hip.h; a host call).  Raises where the launch is refused."""
+    T, npt = ctypes.c_int(-1), ctypes.c_int(-1)
+    _check(_lib.vrnet_cluster_plan(N, blocks, int(bool(bwd)), ctypes.byref(T), ctypes.byref(npt)), "cluster_plan")
+    return T.value, npt.value
 
 
 def cluster_fwd(f, v, ld, alpha, beta, out, ldo, idx, wgt, B, H, W, E, Dh, fold, alpha2=None, beta2=None, forced=False,

@@ -278,6 +278,8 @@ int vrnet_pack_weight_t_f32(const float* w_oihw, const float* kscale, float* w_t
  * = size of ONE direction's planes.
  * forward:  u = x w1^T + b1 (stored to upre when non-NULL: the backward pass needs it);  y = res + res_scale * (gelu(u) w2^T
  *   + b2)  (exact-erf GELU; res / res_scale / b1 / b2 optional);  stats as in vrnet_conv2d_f32 ([M/32][C/32][2] fp64).
+ *   res_scale scales the Mlp's output only on its way onto a residual: given WITHOUT res it is ignored, y = gelu(u) w2^T + b2
+ *   (pinned by tests/test_cluster_edges.py).
  * backward: given dy and the stored u:  du = gelu'(u) * ((dy * dy_scale) w2);  dx = du w1;  h = gelu(u) is recomputed.
  *   du and h are written once (operands of the two weight gradients, vrnet_conv2d_wgrad_f32), dx is the data gradient.
  * precision 4 (round 4): precision 1 with the hidden-sized tensors in bf16 -- `upre` (forward: written, backward: read), `h` and
@@ -474,6 +476,10 @@ int vrnet_cluster_fwd_f32(const float* f, const float* v, long ld, const float* 
 int vrnet_cluster_fwd_forced_f32(const float* f, const float* v, long ld, const float* alpha, const float* beta,
                                  float* out, long ldo, const unsigned char* idx, float* wgt, int B, int H, int W, int E, int D,
                                  int fold, const float* alpha2, const float* beta2, void* stream);
+/* What a launch on regions of N = (H / fold) (W / fold) points in blocks = B * E * fold^2 workgroups runs (host only; ABI 11;
+ * bwd != 0: the backward): *T threads per workgroup and *npt points per lane group of the register kernel, or *T = 0, *npt = 0:
+ * the streaming kernel.  Answered by the function the launchers dispatch on; an error code where they would refuse (N, blocks). */
+int vrnet_cluster_plan(int N, long blocks, int bwd, int* T, int* npt);
 long vrnet_cluster_bwd_workspace(int B, int E, int fold);                          /* regions of <= 256 points */
 long vrnet_cluster_bwd_workspace2(int B, int H, int W, int E, int fold);            /* any region size */
 /* Recomputes the forward from f, v with the saved assignment idx; df, dv share row stride lddf.
