@@ -1595,6 +1595,109 @@ def device_radar_map(points, sizes, input_shape, calib, letterbox_image=True, ra
     return out
 
 
+# ---- the radar readout of the detections: host statement of csrc/boxradar.hip ---------------------------------------------------
+def check_box_shrink(shrink, fn="box_radar"):
+    """shrink as a float32 in (0, 1], or a RuntimeError."""
+    try:
+        s = np.float32(shrink)
+    except (TypeError, ValueError):
+        s = np.float32("nan")
+    if isinstance(shrink, bool) or not (s > 0 and s <= 1):
+        raise RuntimeError(f"{fn}: shrink must lie in (0, 1], got {shrink!r}")
+    return s
+
+
+def box_radar(points, P, size, rows, min_depth=0.1, shrink=1.0):
+    """What the radar says about every detection of ONE image -- this project's own definition, the reference has none:
+    (count (m) int32, readout (m, 2, 5) float32).  points (n, 7) float32 rows x, y, z, f0, f1, f2, f3 and P (3, 4) float32 as
+    `radar_map` takes them, size = (ih, iw) of the original frame, rows (m, >= 4) float32 whose first four columns are top,
+    left, bottom, right in pixels of that frame (`FrameResult.rows`).  Boxes and projected points both live in the original
+    frame, so no window takes part.  Everything in float32, every operation rounded on its own, in this order.  Per point i
+    (the first three lines are `radar_project`'s):
+        hu = ((P00 x + P01 y) + P02 z) + P03, hv and hw likewise from rows 1 and 2
+        kept when hw >= min_depth and hw, hu, hv are finite (a NaN anywhere rejects)
+        u = hu / hw, v = hv / hw; in view when 0 <= u < float(iw) and 0 <= v < float(ih)
+    Per box (t, l, b, rt) = rows[r, 0:4]:
+        shrink == 1: y0 = t, y1 = b, x0 = l, x1 = rt                       (the row's own numbers, exactly)
+        otherwise    cy = (t + b) * 0.5, cx = (l + rt) * 0.5, hy = ((b - t) * 0.5) * shrink, hx = ((rt - l) * 0.5) * shrink
+                     y0 = cy - hy, y1 = cy + hy, x0 = cx - hx, x1 = cx + hx
+        inside when x0 <= u < x1 and y0 <= v < y1                          (a NaN edge contains nothing)
+    The candidates of a box are the points kept, in view and inside it -- a point inside several boxes is a candidate of each
+    -- ordered by the key bits(hw) << 32 | i: hw is positive and finite, so its bits order as an unsigned integer, and equal
+    depths go to the lower index.  count[r] is their number, readout[r, 0] = (hw, f0, f1, f2, f3) of the smallest key, the
+    NEAREST point, readout[r, 1] the same of the candidate of rank (count - 1) // 2 in ascending order, the LOWER MEDIAN by
+    depth: the value to trust when water clutter in front of a hull makes the nearest point unrepresentative.  Feature bits
+    are copied (NaN payloads survive); with count == 0 all ten numbers are +0.0.  shrink in (0, 1] keeps the box's centre and
+    scales its sides; min_depth as `check_radar_rule` has it.  Bad shapes or types raise RuntimeError."""
+    f32 = np.float32
+    md = check_radar_rule(0, min_depth, "box_radar")[1]
+    s = check_box_shrink(shrink)
+    pts, P, rows = np.asarray(points), np.asarray(P), np.asarray(rows)
+    if pts.ndim != 2 or pts.shape[1] != 7 or pts.dtype != np.float32:
+        raise RuntimeError(f"box_radar: points are (n, 7) float32 rows x, y, z, f0, f1, f2, f3, got {pts.dtype} {pts.shape}")
+    if P.shape != (3, 4) or P.dtype != np.float32:
+        raise RuntimeError(f"box_radar: P is a (3, 4) float32 projection, got {P.dtype} {P.shape}")
+    if rows.ndim != 2 or rows.shape[1] < 4 or rows.dtype != np.float32:
+        raise RuntimeError(f"box_radar: rows are (m, >= 4) float32 with top, left, bottom, right in front, got {rows.dtype} {rows.shape}")
+    ih, iw = (int(v) for v in size)
+    m = rows.shape[0]
+    count, readout = np.zeros(m, np.int32), np.zeros((m, 2, 5), np.uint32)
+    if min(ih, iw) <= 0 or not len(pts) or not m:
+        return count, readout.view(f32)
+    pts = np.ascontiguousarray(pts)
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    with np.errstate(all="ignore"):
+        hu, hv, hw = (((P[r, 0] * x + P[r, 1] * y) + P[r, 2] * z) + P[r, 3] for r in range(3))
+        ok = (hw >= md) & np.isfinite(hw) & np.isfinite(hu) & np.isfinite(hv)
+        den = np.where(ok, hw, f32(1))
+        u, v = hu / den, hv / den
+        assert hw.dtype == f32 and u.dtype == f32 and v.dtype == f32
+        ok &= (u >= 0) & (u < f32(iw)) & (v >= 0) & (v < f32(ih))
+        t, l, b, rt = (rows[:, k].astype(f32) for k in range(4))
+        if s == 1:
+            y0, y1, x0, x1 = t, b, l, rt
+        else:
+            cy, cx = (t + b) * f32(0.5), (l + rt) * f32(0.5)
+            hy, hx = ((b - t) * f32(0.5)) * s, ((rt - l) * f32(0.5)) * s
+            y0, y1, x0, x1 = cy - hy, cy + hy, cx - hx, cx + hx
+        assert y0.dtype == f32 and x1.dtype == f32
+        idx = np.flatnonzero(ok)
+        keys = (hw[idx].view(np.uint32).astype(np.uint64) << np.uint64(32)) | idx.astype(np.uint64)
+        order = np.argsort(keys, kind="stable")
+        idx, uu, vv = idx[order], u[idx][order], v[idx][order]           # the candidates of any box, in ascending key order
+        inside = (x0[:, None] <= uu) & (uu < x1[:, None]) & (y0[:, None] <= vv) & (vv < y1[:, None])
+    bits = pts.view(np.uint32)
+    depth = hw.view(np.uint32)
+    for r in range(m):
+        mine = idx[inside[r]]
+        count[r] = len(mine)
+        if len(mine):
+            for k, i in enumerate((mine[0], mine[(len(mine) - 1) // 2])):
+                readout[r, k, 0] = depth[i]
+                readout[r, k, 1:] = bits[i, 3:7]
+    return count, readout.view(f32)
+
+
+def device_box_radar(points, views, rows, kept, min_depth=0.1, shrink=1.0, flag=None, ws=None):
+    """`box_radar` for a batch ON THE DEVICE (vrnet_box_radar_f32, two launches), the eager call outside a pipeline: points
+    (B, max_points, 7) float32 and views, the (B, hip.RADAR_VIEW_BYTES) uint8 table (`radar_view_bytes(radar_views(...))`; ih,
+    iw, count and P are read), rows (B, cap, 7) float32 and kept (B) int32 as `FrameResult` holds them, all on the device ->
+    (counts (B, cap) int32, readout (B, cap, 2, 5) float32) on the device: per image what `box_radar` gives on rows[:kept], bit
+    for bit, zeros behind.  flag: an int32 device word that receives hip.FLAG_GEOMETRY / FLAG_POINT_COUNT / FLAG_BOX_COUNT.
+    No host synchronisation."""
+    from . import hip
+    fn = "device_box_radar"
+    md = check_radar_rule(0, min_depth, fn)[1]
+    s = check_box_shrink(shrink, fn)
+    if not torch.is_tensor(rows) or rows.dim() != 3 or not rows.is_cuda:
+        raise RuntimeError(f"{fn}: rows is a (B, cap, 7) float32 tensor on the device")
+    B, cap = rows.shape[:2]
+    with torch.cuda.device(rows.device):
+        counts = torch.empty((B, cap), dtype=torch.int32, device=rows.device)
+        readout = torch.empty((B, cap, 2, 5), dtype=torch.float32, device=rows.device)
+        return hip.box_radar(points, views, rows, kept, float(md), float(s), counts, readout, flag=flag, ws=ws)
+
+
 # ---- radar points under Mosaic: host statement of the radar-points kernels of csrc/mosaic.hip ----------------------------------
 # vrnet_radar_source of include/vrnet_hip.h, one record per SOURCE (56 bytes): what the kernel needs beside the Mosaic record
 RADAR_SOURCE_DTYPE = np.dtype([("count", "<i4"), ("reserved", "<i4"), ("P", "<f4", (12,))])

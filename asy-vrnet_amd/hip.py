@@ -166,6 +166,8 @@ _SIGS = {
     "vrnet_radar_map_workspace": ([I, I, I], L),
     "vrnet_radar_map_f32": ([P, I, P, I, I, I, I, F, P, P, P, L, P], I),
     "vrnet_radar_map_post_f32": ([P, I, P, I, I, I, I, F, P, I, P, P, P, L, P], I),
+    "vrnet_box_radar_workspace": ([I, I], L),
+    "vrnet_box_radar_f32": ([P, I, P, I, P, P, I, F, F, P, P, P, P, L, P], I),
     "vrnet_mosaic_radar_points_workspace": ([I, I, I], L),
     "vrnet_mosaic_radar_points_f32": ([P, I, I, P, P, I, I, I, I, I, I, F, P, P, P, L, P], I),
     "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
@@ -1727,6 +1729,42 @@ def radar_map_post(points, views, post, H, W, radius, min_depth, max_angle, out,
     if post is None:
         raise RuntimeError("radar_map_post: the post table is required (radar_map is the call without one)")
     return _radar_map("radar_map_post", points, views, H, W, radius, min_depth, out, flag, ws, post, max_angle)
+
+
+# ---- the radar readout of the detections (include/vrnet_hip.h "the radar readout of the detections") -------------------------
+def box_radar_workspace_bytes(B, max_points):
+    return _lib.vrnet_box_radar_workspace(B, max_points)
+
+
+def box_radar(points, views, rows, kept, min_depth, shrink, counts, readout, flag=None, ws=None):
+    """Radar points and kept detections -> the readout of every box (vrnet_box_radar_f32): points (B, max_points, 7) f32 and
+    views (B, RADAR_VIEW_BYTES) as `radar_map` takes them (ih, iw, count and P are read), rows (B, cap, 7) f32 with top, left,
+    bottom, right in pixels of the original frame in front, kept (B) int32 -> counts (B, cap) int32 and readout (B, cap, 2, 5)
+    f32, what `data.box_radar` gives per image on rows[:kept], bit for bit, and zeros from row kept[b] on: every element is
+    written.  min_depth > 0, 0 < shrink <= 1; flag (1) int32 or None: FLAG_GEOMETRY for ih or iw <= 0 (zeros for that image),
+    FLAG_POINT_COUNT / FLAG_BOX_COUNT for a clamped count / kept; ws: box_radar_workspace_bytes(B, max_points) bytes.  Two
+    launches.  Returns (counts, readout)."""
+    fn = "box_radar"
+    if points is None or points.dim() != 3 or points.shape[2] != 7 or points.shape[1] < 1:
+        raise RuntimeError(f"{fn}: expected points (B, max_points, 7)")
+    B, max_points = points.shape[:2]
+    if rows is None or rows.dim() != 3 or rows.shape[0] != B or rows.shape[1] < 1 or rows.shape[2] != 7:
+        raise RuntimeError(f"{fn}: expected rows ({B}, cap, 7)")
+    cap = rows.shape[1]
+    if counts is None or readout is None:
+        raise RuntimeError(f"{fn}: counts and readout are required")
+    _tensors(fn, ((points, (B, max_points, 7), torch.float32), (rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32),
+                  (counts, (B, cap), torch.int32), (readout, (B, cap, 2, 5), torch.float32), (flag, (1,), torch.int32)))
+    if kept is None:
+        raise RuntimeError(f"{fn}: kept is required")
+    need = _lib.vrnet_box_radar_workspace(B, max_points)
+    if ws is None:
+        ws = _ws.get(need, points.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise RuntimeError(f"{fn}: the workspace must be a contiguous uint8 tensor, got {ws.dtype}")
+    _check(_lib.vrnet_box_radar_f32(ptr(points), max_points, _views(views, B, fn), B, ptr(rows), ptr(kept), cap, float(min_depth),
+                                    float(shrink), ptr(counts), ptr(readout), ptr(flag), ptr(ws), ws.numel(), stream()), fn)
+    return counts, readout
 
 
 # ---- radar points under Mosaic (include/vrnet_hip.h "radar points under Mosaic") ----------------------------------------------

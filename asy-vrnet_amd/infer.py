@@ -18,7 +18,9 @@ table had to be clamped by a kernel, which the host checks of `run` rule out.  A
 hip.crop_boxes behind hip.detect_finish and FLAG_CROP_ARENA, a crop that did not fit into the arena.  A pipeline built with
 dehaze= puts hip.dehaze in front of the letterbox, so that everything downstream reads the dehazed frames, and adds
 FLAG_DEHAZE, a degenerate image that went on unchanged.  A pipeline built with ace= puts hip.ace there too, behind hip.dehaze
-when both are on, and adds FLAG_ACE for its degenerate images.
+when both are on, and adds FLAG_ACE for its degenerate images.  A pipeline built with radar_points and box_radar= adds
+hip.box_radar behind the finish node (behind the crops): the radar readout of every kept detection; FLAG_BOX_COUNT, a kept count
+outside the row buffer, is ruled out by the NMS that writes it.
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
@@ -33,6 +35,7 @@ from . import render as rendering
 
 FLAG_CANDIDATES, FLAG_DET_CLASS = 8, 16          # NMS_FLAG_* of csrc/nms.hip, above render.FLAG_*
 FLAG_GEOMETRY = 256                              # VR_FLAG_GEOMETRY of csrc/common.h, above evaluate.FLAG_EVAL_*
+FLAG_BOX_COUNT = 512                             # VR_FLAG_BOX_COUNT of csrc/common.h (a pipeline built with box_radar): kept outside [0, cap]
 FLAG_POINT_COUNT = 1024                          # VR_FLAG_POINT_COUNT of csrc/common.h (a pipeline built with radar_points)
 FLAG_LABEL_SCORE = rendering.FLAG_LABEL_SCORE    # 2048, csrc/labels.hip (a pipeline built with labels): a score outside [0, 1]
 FLAG_CROP_ARENA = rendering.FLAG_CROP_ARENA      # 4096, csrc/crops.hip (a pipeline built with crops): a crop that did not fit
@@ -225,16 +228,20 @@ class FrameResult:
     From a pipeline built with dehaze (None otherwise): dehazed (B, ih, iw, 3) uint8, the frames everything else of the
     result was computed from; padded like rendered from a ragged pipeline.
     From a pipeline built with ace (None otherwise): enhanced (B, ih, iw, 3) uint8, the output of the ACE stage, which then
-    is what everything else of the result was computed from (the stage reads the dehazed frames when both are on)."""
+    is what everything else of the result was computed from (the stage reads the dehazed frames when both are on).
+    From a pipeline built with box_radar (None otherwise): box_points (B, cap) int32, the radar points inside each kept box,
+    and box_radar (B, cap, 2, 5) float32, (depth, f0, f1, f2, f3) of the nearest of them and of their lower median by depth
+    (`data.box_radar` is the rule), both zero from row kept[b] on; `radar_readout` brings them to the host."""
     __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
-                 "heat_picture", "heat_range", "crops", "dehazed", "enhanced")
+                 "heat_picture", "heat_range", "crops", "dehazed", "enhanced", "box_points", "box_radar")
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
-                 heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None):
+                 heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None, box_points=None, box_radar=None):
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
         self.heat_mask, self.heat_picture, self.heat_range, self.crops = heat_mask, heat_picture, heat_range, crops
         self.dehazed, self.enhanced = dehazed, enhanced
+        self.box_points, self.box_radar = box_points, box_radar
 
     def detections(self):
         """The list `decode.non_max_suppression` returns: per image an (N_b, 7) float32 numpy array in the same order,
@@ -245,6 +252,21 @@ class FrameResult:
         kept = packed[-B:].view(np.int32)
         rows = packed[:-B].reshape(B, -1, 7)
         return [rows[b, :kept[b]].copy() for b in range(B)]
+
+    def radar_readout(self):
+        """The radar readout of a pipeline built with box_radar, beside `detections()` and in its row order: per image a
+        (N_b, 11) float32 numpy array -- the points inside the box (a count, exact as a float32: at most 2^24), then depth, f0,
+        f1, f2, f3 of the nearest point and the same five of the lower median by depth; (0, 11) for an image without
+        detections.  One device-to-host copy (counts, readout and kept packed into one tensor), which waits for the frame."""
+        if self.box_points is None or self.box_radar is None:
+            raise RuntimeError("FrameResult.radar_readout: the pipeline was not built with box_radar")
+        B, cap = self.box_points.shape
+        packed = torch.cat([self.box_points.reshape(-1).view(torch.float32), self.box_radar.reshape(-1),
+                            self.kept.view(torch.float32)]).cpu().numpy()
+        counts = packed[:B * cap].view(np.int32).reshape(B, cap)
+        readout = packed[B * cap:B * cap * 11].reshape(B, cap, 10)
+        kept = packed[B * cap * 11:].view(np.int32)
+        return [np.concatenate([counts[b, :kept[b], None].astype(np.float32), readout[b, :kept[b]]], axis=1) for b in range(B)]
 
 
 class FramePipeline:
@@ -320,13 +342,22 @@ class FramePipeline:
     both are on (ACE then reads the dehazed frames), and everything downstream reads its output, `FrameResult.enhanced`.  The
     buffer, the weights table and the workspace (`hip.ace_workspace_bytes`, about 40 bytes per frame pixel) are allocated
     before the capture.  Fixed-size and ragged pipelines alike; a degenerate image (min(ih, iw) <= 2, or a constant R_0)
-    goes on unchanged and FLAG_ACE joins the bits of `flag`."""
+    goes on unchanged and FLAG_ACE joins the bits of `flag`.
+
+    box_radar: None (the default: exactly the calls issued without it) or True, in a pipeline built with radar_points -- the
+    radar readout of every kept detection (`data.box_radar`, csrc/boxradar.hip): how many of the image's radar points lie in
+    the box, and depth and features of the nearest of them and of their lower median by depth, as `FrameResult.box_points`
+    and `FrameResult.box_radar`.  The two launches of hip.box_radar sit behind the detect_finish node (behind the crop
+    launches when crops is on) and read the static `points` and `views` and the rows of the result, with radar_min_depth;
+    box_shrink in (0, 1] scales every box about its centre first.  Outputs and workspace are allocated before the capture.
+    Fixed-size and ragged pipelines alike, with and without letterbox_image: rows and projected points both live in the
+    original frame."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
-                 font=None, label_sizes=None, crops=None, dehaze=None, ace=None):
+                 font=None, label_sizes=None, crops=None, dehaze=None, ace=None, box_radar=None, box_shrink=1.0):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
         self.crop_capacity = crop_capacity(crops, self.batch, self.frame_shape)
@@ -342,6 +373,14 @@ class FramePipeline:
             self.radar_points = RadarPoints(radar_points, radar_radius, radar_min_depth, calib, self.batch)
         elif calib is not None or radar_radius != 0 or radar_min_depth != 0.1:
             raise RuntimeError("FramePipeline: calib, radar_radius and radar_min_depth belong to radar_points=max_points")
+        self.box_radar = bool(box_radar)
+        if self.box_radar:
+            if self.radar_points is None:
+                raise RuntimeError("FramePipeline: box_radar reads the radar POINTS of a pipeline built with radar_points=max_points; "
+                                   "this one takes finished maps")
+            self.box_shrink = float(data.check_box_shrink(box_shrink, "FramePipeline"))
+        elif isinstance(box_shrink, bool) or box_shrink != 1.0:
+            raise RuntimeError("FramePipeline: box_shrink belongs to box_radar=True")
         if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
             raise RuntimeError(f"FramePipeline: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
         if not 0.0 <= float(heat_alpha) <= 1.0:
@@ -462,6 +501,10 @@ class FramePipeline:
         self._crops = None
         if self.crop_capacity is not None:
             self._crops = rendering.crop_buffers(B * cap, self.crop_capacity, B, self.flag, dev)
+        self._box_points = self._box_radar = None
+        if self.box_radar:                    # before the capture: the two outputs and the projected points
+            self._box_points, self._box_radar = torch.zeros((B, cap), **i32), torch.zeros((B, cap, 2, 5), device=dev)
+            self._box_ws = torch.empty(hip.box_radar_workspace_bytes(B, self.radar_points.max_points), dtype=torch.uint8, device=dev)
 
     def _chain(self):
         """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
@@ -502,6 +545,9 @@ class FramePipeline:
         if self._crops is not None:           # right behind the finish node: from the original frames, which nothing draws on
             hip.crop_boxes(frames, self._draw_rows, self._offsets, self._crops.arena, self._crops.table,
                            self._crops.summary, geom=geom, flag=self.flag)
+        if self.box_radar:                    # behind the finish node (and the crops): rows and points share the original frame
+            hip.box_radar(self.points, self.views, self._rows, self._kept, float(self.radar_points.min_depth), self.box_shrink,
+                          self._box_points, self._box_radar, flag=self.flag, ws=self._box_ws)
         if self.ragged or self.letterbox_image:
             class_map = decode.seg_predict(seg, (H, W), self.image_shape, geom=geom, capacity=self._slots, flag=self.flag)
         else:                                 # the frame was stretched over the whole input: the window is the input
@@ -519,7 +565,8 @@ class FramePipeline:
                 box_palette=self.box_palette, thickness=self.thickness, flag=self.flag, device=dev, labels=self.labels, geom=geom,
                 label_sizes=self.label_size_tab)
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops,
-                             dehazed=dehazed, enhanced=frames if self.ace is not None else None)
+                             dehazed=dehazed, enhanced=frames if self.ace is not None else None, box_points=self._box_points,
+                             box_radar=self._box_radar)
         if self.heatmap:
             result.heat_picture, result.heat_mask, result.heat_range = rendering.heatmap(
                 frames, det, (H, W), alpha=self.heat_alpha, geom=geom, flag=self.flag, **self._heat_window)
@@ -610,6 +657,23 @@ class FramePipeline:
         return self.result
 
 
+def radar_text(detections, readout):
+    """The <stem>_radar.txt of `predict_dir` for one picture: detections (N, 7) as `FrameResult.detections` gives them and
+    readout (N, 11) as `FrameResult.radar_readout` does -> one line per detection, space-separated: the class as an integer,
+    the score obj * class_conf (the float32 product), left top right bottom, the points inside the box as an integer, then
+    depth f0 f1 f2 f3 of the nearest point and of the lower median; every float as %.9g, which names a float32 exactly."""
+    detections, readout = np.asarray(detections, np.float32), np.asarray(readout, np.float32)
+    if detections.ndim != 2 or detections.shape[1] != 7 or readout.shape != (len(detections), 11):
+        raise RuntimeError(f"radar_text: expected (N, 7) detections and (N, 11) readout rows, got {detections.shape} and {readout.shape}")
+    lines = []
+    for d, r in zip(detections, readout):
+        top, left, bottom, right = d[:4]
+        floats = [d[4] * d[5], left, top, right, bottom]
+        lines.append(" ".join([str(int(d[6]))] + ["%.9g" % float(v) for v in floats] + [str(int(r[0]))] +
+                              ["%.9g" % float(v) for v in r[1:]]) + "\n")
+    return "".join(lines)
+
+
 def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     """predict.py's `dir_predict` mode on a ragged pipeline: every picture of the folder dir_origin_path whose name ends in
     one of IMAGE_EXTENSIONS (the reference's filter, lower case), in sorted order, with its radar maps
@@ -623,9 +687,10 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     picture (the `i` of yolo.py:180-193); the crops of the repeated fill pictures are dropped with the repeats.  The reference
     writes img_crop/crop_<i>.png and so overwrites the crops of one picture with those of the next: the stem in the name is a
     deliberate departure.  From a pipeline built with dehaze the dehazed frame is saved as <stem>_dehaze.png, from one built
-    with ace the enhanced frame as <stem>_ace.png.  Two pictures that would share one output file (names that differ only in
+    with ace the enhanced frame as <stem>_ace.png, from one built with box_radar the radar readout of the picture's
+    detections as <stem>_radar.txt (`radar_text`).  Two pictures that would share one output name (names that differ only in
     their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on, or `a_dehaze.jpg` with dehazing on, or `a_ace.jpg`
-    with ACE on): with dir_save_path that raises before anything runs."""
+    with ACE on, or `a_radar.jpg` with the readout on): with dir_save_path that raises before anything runs."""
     from PIL import Image
     if not getattr(pipeline, "ragged", False):
         raise RuntimeError("predict_dir: needs a ragged pipeline (FramePipeline(..., ragged=True)): a folder holds pictures of any size")
@@ -636,7 +701,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
             stem = os.path.splitext(n)[0]
             targets = (stem,) + ((stem + "_heat",) if getattr(pipeline, "heatmap", False) else ()) + \
                 ((stem + "_dehaze",) if getattr(pipeline, "dehaze", None) is not None else ()) + \
-                ((stem + "_ace",) if getattr(pipeline, "ace", None) is not None else ())
+                ((stem + "_ace",) if getattr(pipeline, "ace", None) is not None else ()) + \
+                ((stem + "_radar",) if getattr(pipeline, "box_radar", False) else ())
             for target in targets:
                 other = stems.setdefault(target, n)
                 if other != n:
@@ -663,9 +729,13 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         enhanced = None if enhanced is None else enhanced.cpu().numpy()
         crops = None if dir_save_path is None else getattr(result, "crops", None)
         crops = None if crops is None else crops.images()
+        readout = None if dir_save_path is None or getattr(result, "box_radar", None) is None else result.radar_readout()
         for b, n in enumerate(chunk):
             out.append((n, dets[b]))
             ih, iw = (int(v) for v in result.sizes[b])
+            if readout is not None:
+                with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_radar.txt"), "w") as f:
+                    f.write(radar_text(dets[b], readout[b]))
             if rendered is not None:
                 Image.fromarray(rendered[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + ".png"))
             if heat is not None:

@@ -1283,6 +1283,46 @@ int vrnet_radar_map_post_f32(const float* points, int max_points, const vrnet_ra
                              float min_depth, const vrnet_aug_post_rec* post, int max_angle, float* out, int* flag,
                              void* workspace, long workspace_bytes, void* stream);
 
+/* ---- the radar readout of the detections (csrc/boxradar.hip; the projection of a point: csrc/radarpoint.h) -------------------
+ * Added within ABI 11: two new symbols only, no existing signature, layout or kernel behaviour changed; hip.py binds every
+ * declared symbol at import.
+ * Per kept detection: the number of radar points inside its box, the nearest of them and their lower median by depth.  The
+ * reference has no code for it; the rule is this project's definition (host statement: data.box_radar) and the kernels equal
+ * it bit for bit.  points and views as vrnet_radar_map_f32 takes them; of a view record only ih, iw, count and P are read.
+ * rows (B, cap, 7) fp32, the first four numbers of a row being top, left, bottom, right in pixels of the ORIGINAL frame (the
+ * rows vrnet_detect_finish_f32 writes); kept (B) int32, the rows of each image that count.  Boxes and projected points both
+ * live in the original frame, so no window takes part.
+ * THE RULE, in float32, every operation rounded on its own in this order, nothing contracted.  Per point i:
+ *   hu = ((P00 x + P01 y) + P02 z) + P03, hv and hw likewise from rows 1 and 2
+ *   kept when hw >= min_depth and hw, hu, hv are finite (a NaN anywhere rejects)
+ *   u = hu / hw, v = hv / hw (correctly rounded); in view when 0 <= u < float(iw) and 0 <= v < float(ih)
+ * Per box (t, l, b, rt):
+ *   shrink == 1: y0 = t, y1 = b, x0 = l, x1 = rt, the row's own numbers
+ *   otherwise:   cy = (t + b) 0.5, cx = (l + rt) 0.5, hy = ((b - t) 0.5) shrink, hx = ((rt - l) 0.5) shrink,
+ *                y0 = cy - hy, y1 = cy + hy, x0 = cx - hx, x1 = cx + hx
+ *   inside when x0 <= u < x1 and y0 <= v < y1 (a NaN edge contains nothing)
+ * The candidates of a box -- kept, in view, inside; a point inside several boxes is a candidate of each -- are ordered by
+ * key = bits(hw) << 32 | i: hw is positive and finite, so its bits order as an unsigned integer; equal depths go to the lower
+ * index.  counts_out[b][r] = their number; readout_out[b][r][0] = (hw, f0, f1, f2, f3) of the smallest key (the NEAREST),
+ * readout_out[b][r][1] = the same of the key of rank (count - 1) / 2 in ascending order (the LOWER MEDIAN by depth).  Feature
+ * bits are copied, NaN payloads included; without a candidate all ten numbers are +0.0.  0 < shrink <= 1, min_depth > 0.
+ * counts_out (B, cap) int32 and readout_out (B, cap, 2, 5) fp32: EVERY element is written by every call, zeros from row
+ * kept[b] on, so no memset is needed and no call depends on an earlier one.
+ * Two launches: one thread per point writes (u, v, hw) into three planes of the workspace (12 bytes a point; hw = +0.0 marks
+ * a point that is not a candidate of any box); one workgroup of 256 per (row, image) counts the candidates and takes their
+ * minimum key (wave shuffles, then LDS), and from three candidates on selects the median exactly by an MSB-first radix select
+ * on the 64-bit key, 8 bits a pass with a 256-bin LDS histogram, re-reading the planes: there is no list of candidates, so no
+ * capacity at which the answer changes.  Integer atomics only (LDS histogram; the OR into *flag is the one global atomic):
+ * the same bytes on every run.  No allocation, no memset, no host synchronisation; capturable.
+ * A record with ih or iw <= 0 gives zeros for its image and sets bit 256 of *flag (VR_FLAG_GEOMETRY); a point count outside
+ * [0, max_points] is clamped and sets bit 1024 (VR_FLAG_POINT_COUNT); kept[b] outside [0, cap] is clamped and sets bit 512
+ * (VR_FLAG_BOX_COUNT).  flag may be NULL.  B < 65536, max_points <= 2^24, cap <= 2^20.
+ * workspace: vrnet_box_radar_workspace(B, max_points) bytes (-1 for a shape outside the limits), 8-byte aligned. */
+long vrnet_box_radar_workspace(int B, int max_points);
+int vrnet_box_radar_f32(const float* points, int max_points, const vrnet_radar_view* views, int B, const float* rows,
+                        const int* kept, int cap, float min_depth, float shrink, int* counts_out, float* readout_out, int* flag,
+                        void* workspace, long workspace_bytes, void* stream);
+
 /* ---- radar points under Mosaic (csrc/mosaic.hip; the projection of a point: csrc/radarpoint.h) ---------------------------------
  * Added within ABI 11: new symbols and one new record layout (vrnet_radar_source) only, no existing signature, layout or kernel
  * behaviour changed; hip.py binds every declared symbol at import.
