@@ -711,6 +711,15 @@ extern "C" int vrnet_wgrad_planes_ok(long M, int Cin, int Cout) {
   return (M >= 256 && Cin >= min_c && Cout >= min_c && Cin % 8 == 0 && Cout % 8 == 0) ? 1 : 0;
 }
 
+/* The row split and tiling of vrnet_wgrad_planes_f32 (host only; include/vrnet_hip.h): what the launcher itself uses. */
+extern "C" int vrnet_wgrad_planes_plan(long M, int Cin, int Cout, int np, int* n_tiles, int* c_tiles, int* splits,
+                                       int* rows_per_split) {
+  VR_CHECK_ARG(n_tiles && c_tiles && splits && rows_per_split && M > 0 && M < (1L << 31) && Cin > 0 && Cout > 0 && (np == 1 || np == 3),
+               "wgrad_planes_plan: bad arguments");
+  pwgrad_plan(M, Cin, Cout, np, n_tiles, c_tiles, splits, rows_per_split);
+  return VR_OK;
+}
+
 extern "C" long vrnet_wgrad_planes_workspace(long M, int Cin, int Cout) {
   int nt, ct, S, rows;
   pwgrad_plan(M, Cin, Cout, 1, &nt, &ct, &S, &rows);      // (the np = 1 plan has the most splits)

@@ -41,6 +41,7 @@ _SIGS = {
     "vrnet_planes_from_f32": ([P, L, L, L, P, L, L, I, P], I),
     "vrnet_wgrad_planes_ok": ([L, I, I], I),
     "vrnet_wgrad_planes_workspace": ([L, I, I], L),
+    "vrnet_wgrad_planes_plan": ([L, I, I, I, P, P, P, P], I),
     "vrnet_wgrad_planes_f32": ([P, L, L, P, L, L, I, L, I, I, P, P, P, I, P, P, P, P, L, P], I),
     "vrnet_conv2d_dma_tile": ([L, I], I),
     "vrnet_conv2d_wgrad_workspace": ([I] * 8, L),
@@ -433,12 +434,30 @@ def wgrad_planes_ok(M, Cin, Cout):
     return bool(_lib.vrnet_wgrad_planes_ok(M, Cin, Cout))
 
 
-def wgrad_planes(x, dy, M, Cin, Cout, dw, dbias=None, row_scale=None, accumulate=0, w=None, bias=None, dls=None):
-    """dw (+ dbias, + dls) of a 1x1 conv from plane operands x (M x Cin) and dy (M x Cout) (vrnet_wgrad_planes_f32)."""
+def wgrad_planes_plan(M, Cin, Cout, np_):
+    """(n_tiles, c_tiles, splits, rows_per_split) of wgrad_planes at np_ = 3 or 1 (vrnet_wgrad_planes_plan; a host call)."""
+    out = [ctypes.c_int() for _ in range(4)]
+    _check(_lib.vrnet_wgrad_planes_plan(M, Cin, Cout, np_, *(ctypes.byref(o) for o in out)), "wgrad_planes_plan")
+    return tuple(o.value for o in out)
+
+
+def wgrad_planes_workspace(M, Cin, Cout):
+    """Bytes of workspace wgrad_planes needs (either np)."""
+    return _lib.vrnet_wgrad_planes_workspace(M, Cin, Cout)
+
+
+def wgrad_planes(x, dy, M, Cin, Cout, dw, dbias=None, row_scale=None, accumulate=0, w=None, bias=None, dls=None, ws=None,
+                 ws_bytes=None):
+    """dw (+ dbias, + dls) of a 1x1 conv from plane operands x (M x Cin) and dy (M x Cout) (vrnet_wgrad_planes_f32).
+    ws (a tensor): the workspace of the call instead of this stream's scratch arena; ws_bytes: how much of it the call may use
+    (default: all of it)."""
     assert x.np == dy.np
-    ws = _ws.get(_lib.vrnet_wgrad_planes_workspace(M, Cin, Cout), dw.device)
+    if ws is None:
+        ws = _ws.get(_lib.vrnet_wgrad_planes_workspace(M, Cin, Cout), dw.device)
+    if ws_bytes is None:
+        ws_bytes = ws.numel() * ws.element_size()
     _check(_lib.vrnet_wgrad_planes_f32(ptr(x.t), x.ld, x.plane, ptr(dy.t), dy.ld, dy.plane, x.np, M, Cin, Cout, ptr(dw), ptr(dbias),
-                                       ptr(row_scale), accumulate, ptr(w), ptr(bias), ptr(dls), ptr(ws), ws.numel(), stream()),
+                                       ptr(row_scale), accumulate, ptr(w), ptr(bias), ptr(dls), ptr(ws), ws_bytes, stream()),
            "wgrad_planes")
 
 

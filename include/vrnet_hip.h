@@ -222,6 +222,11 @@ int vrnet_cluster_bwd_planes_f32(const void* f, const void* v, long ld, int in_b
                                  long workspace_bytes, void* stream);
 int vrnet_wgrad_planes_ok(long M, int Cin, int Cout);
 long vrnet_wgrad_planes_workspace(long M, int Cin, int Cout);
+/* What vrnet_wgrad_planes_f32 launches for M contraction rows at np = 3 or 1; a host-only query over the function the launcher
+ * itself plans with.  n_tiles x c_tiles tiles of 128 (Cout) x 128 (Cin) channels, `splits` row splits of rows_per_split rows (a
+ * multiple of 32; the last split may be shorter), one fp32 slab per split; the grid is 8 * ceil(splits / 8) * n_tiles * c_tiles
+ * workgroups.  Returns non-zero on bad arguments. */
+int vrnet_wgrad_planes_plan(long M, int Cin, int Cout, int np, int* n_tiles, int* c_tiles, int* splits, int* rows_per_split);
 int vrnet_wgrad_planes_f32(const void* x, long ldx, long x_plane, const void* dy, long lddy, long dy_plane, int np, long M, int Cin,
                            int Cout, float* dw, float* dbias, const float* row_scale, int accumulate, const float* w,
                            const float* bias, float* dls, void* workspace, long workspace_bytes, void* stream);

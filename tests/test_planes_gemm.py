@@ -234,7 +234,7 @@ WGRAD_CASES = [
     (8192, 256, 320),        # proj
     (2048, 512, 2048),       # stage 3
     (1000, 136, 104),        # ragged rows and channel counts (multiples of 8)
-    (288, 96, 128),          # one split of 9 stages
+    (288, 96, 128),          # three splits of 96 rows, 3 stages each (tests/test_planes_plan.py asserts the plan)
     (32768, 128, 256),
 ]
 
