@@ -1491,7 +1491,7 @@ extern "C" int vrnet_ls_coef_bwd(const double* mom2, const float* ls, int B, int
 }
 
 extern "C" int vrnet_moments_to_float(const double* mom, float* out, long n, double scale, int which, void* stream) {
-  VR_CHECK_ARG(mom && out && (which == 0 || which == 1), "moments_to_float: bad arguments");
+  VR_CHECK_ARG(mom && out && n > 0 && (which == 0 || which == 1), "moments_to_float: bad arguments");
   hipLaunchKernelGGL(moments_to_float_kernel, dim3(vr_cdiv(n, 256)), dim3(256), 0, vr_stream(stream), mom, out, n, scale,
                      which);
   VR_LAUNCH_CHECK("moments_to_float");
@@ -1546,7 +1546,7 @@ extern "C" int vrnet_cat2_f32(float* a, long lda, int Ca, float* b, long ldb, in
 }
 
 extern "C" int vrnet_nchw_to_nhwc_f32(const float* src, float* dst, long ldd, int B, int C, long HW, void* stream) {
-  VR_CHECK_ARG(src && dst && ldd >= C, "nchw_to_nhwc: bad arguments");
+  VR_CHECK_ARG(src && dst && B > 0 && B < 65536 && C > 0 && HW > 0 && ldd >= C, "nchw_to_nhwc: bad arguments");
   if ((C == 3 || C == 4) && HW >= 4096) {
     long pb = vr_cdiv(HW, 256);
     if (pb > 4096) pb = 4096;
@@ -1564,7 +1564,7 @@ extern "C" int vrnet_nchw_to_nhwc_f32(const float* src, float* dst, long ldd, in
 
 extern "C" int vrnet_nhwc_to_nchw_f32(const float* src, long lds, float* dst, int B, int C, long HW, int accumulate,
                                       void* stream) {
-  VR_CHECK_ARG(src && dst && lds >= C, "nhwc_to_nchw: bad arguments");
+  VR_CHECK_ARG(src && dst && B > 0 && B < 65536 && C > 0 && HW > 0 && lds >= C, "nhwc_to_nchw: bad arguments");
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(vr_cdiv(HW, 32), vr_cdiv(C, 32), B), dim3(32, 8), 0, vr_stream(stream),
                      src, lds, dst, C, HW, accumulate);
   VR_LAUNCH_CHECK("nhwc_to_nchw");
@@ -1573,7 +1573,7 @@ extern "C" int vrnet_nhwc_to_nchw_f32(const float* src, long lds, float* dst, in
 
 extern "C" int vrnet_add_f32(float* dst, const float* src, long n, void* stream) {
   if (vr_ablated("misc")) return VR_OK;
-  VR_CHECK_ARG(dst && src && n >= 0, "add: bad arguments");
+  VR_CHECK_ARG(n >= 0 && (n == 0 || (dst && src)), "add: bad arguments");      // an empty tensor has no address
   if (n == 0) return VR_OK;
   long blocks = vr_cdiv(n, 1024);
   if (blocks > 8192) blocks = 8192;
@@ -1583,7 +1583,7 @@ extern "C" int vrnet_add_f32(float* dst, const float* src, long n, void* stream)
 }
 
 extern "C" int vrnet_fill_f32(float* dst, float value, long n, void* stream) {
-  VR_CHECK_ARG(dst && n >= 0, "fill: bad arguments");
+  VR_CHECK_ARG(n >= 0 && (n == 0 || dst), "fill: bad arguments");
   if (n == 0) return VR_OK;
   long blocks = vr_cdiv(n, 1024);
   if (blocks > 8192) blocks = 8192;
