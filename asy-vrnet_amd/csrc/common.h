@@ -84,6 +84,7 @@ typedef struct vrnet_frame_geom {
 #define VR_FLAG_CROP_ARENA 4096                 /* crops.hip: a crop that did not fit into the arena, dropped */
 #define VR_FLAG_DEHAZE 8192                     /* dehaze.hip: a degenerate image, returned unchanged */
 #define VR_FLAG_ACE 16384                       /* ace.hip: a degenerate image, returned unchanged */
+#define VR_FLAG_TRACK_FULL 32768                /* track.hip: a valid row found no free slot in the track table, id 0 */
 extern "C" {
 /* include/vrnet_hip.h: one record per draw row of vrnet_crop_boxes_u8. */
 typedef struct vrnet_crop_rec {

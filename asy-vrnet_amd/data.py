@@ -1698,6 +1698,256 @@ def device_box_radar(points, views, rows, kept, min_depth=0.1, shrink=1.0, flag=
         return hip.box_radar(points, views, rows, kept, float(md), float(s), counts, readout, flag=flag, ws=ws)
 
 
+# ---- multi-object tracking of the detections: host statement of csrc/track.hip ----------------------------------------------------
+# vrnet_track of include/vrnet_hip.h: one track, 64 bytes; a free slot is all zeros, so zeroed memory is the reset state
+TRACK_DTYPE = np.dtype([("id", "<i4"), ("cls", "<i4"), ("hits", "<i4"), ("misses", "<i4"), ("row", "<i4"), ("range_age", "<i4"),
+                        ("x", "<f4", (5,)), ("v", "<f4", (5,))])
+assert TRACK_DTYPE.itemsize == 64
+TRACK_HEAD = 4                       # per stream, int32: ids handed out so far, live tracks, calls so far, births of this call
+TRACK_MAX_TRACKS, TRACK_MAX_ROWS = 256, 1024
+FLAG_TRACK_FULL = 32768              # VR_FLAG_TRACK_FULL of csrc/common.h: a valid row found no free slot and got id 0
+_TRACK_DEFAULTS = dict(max_tracks=64, iou=0.3, max_age=5, gain=(0.5, 0.25), range_gain=(0.5, 0.25))
+_INT_MAX = 2 ** 31 - 1
+
+
+def check_track_params(track=True, fn="track_update"):
+    """The tracker's parameters from True / None (the defaults) or a dict that overrides some of max_tracks = 64 (1..256),
+    iou = 0.3 (the match threshold, in (0, 1]), max_age = 5 (a track is freed after more than that many calls in a row
+    without a match; 0..2^20), gain = (0.5, 0.25) and range_gain = (0.5, 0.25) (position and rate gain of the box filter and
+    of the range filter, each finite and in [0, 2]) -> a dict with all five, the floats as float32.  Anything else raises
+    RuntimeError."""
+    if track is None or track is True:
+        track = {}
+    if not isinstance(track, dict):
+        raise RuntimeError(f"{fn}: track is None, True or a dict of parameters, got {type(track).__name__}")
+    unknown = sorted(set(track) - set(_TRACK_DEFAULTS))
+    if unknown:
+        raise RuntimeError(f"{fn}: unknown track parameters {unknown}; known: {sorted(_TRACK_DEFAULTS)}")
+    p = dict(_TRACK_DEFAULTS, **track)
+
+    def whole(name, lo, hi):
+        v = p[name]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise RuntimeError(f"{fn}: {name} must be an integer in [{lo}, {hi}], got {v!r}")
+        return int(v)
+
+    def real(name, v):
+        try:
+            f = np.float32(v)
+        except (TypeError, ValueError):
+            f = np.float32("nan")
+        if isinstance(v, bool) or not np.isfinite(f):
+            raise RuntimeError(f"{fn}: {name} must be a finite number, got {v!r}")
+        return f
+
+    out = dict(max_tracks=whole("max_tracks", 1, TRACK_MAX_TRACKS), max_age=whole("max_age", 0, 1 << 20))
+    out["iou"] = real("iou", p["iou"])
+    if not (out["iou"] > 0 and out["iou"] <= 1):
+        raise RuntimeError(f"{fn}: iou must lie in (0, 1], got {p['iou']!r}")
+    for name in ("gain", "range_gain"):
+        try:
+            pair = tuple(p[name])
+        except TypeError:
+            pair = ()
+        if len(pair) != 2:
+            raise RuntimeError(f"{fn}: {name} is a (position, rate) pair, got {p[name]!r}")
+        out[name] = tuple(real(name, v) for v in pair)
+        if not all(0 <= g <= 2 for g in out[name]):
+            raise RuntimeError(f"{fn}: {name} must lie in [0, 2], got {p[name]!r}")
+    return out
+
+
+def track_key(iou, slot, row):
+    """The 64-bit key of a candidate pair: bits(iou) << 32 | (65535 - slot) << 16 | (65535 - row).  iou is positive, so its
+    bits order as an unsigned integer; the LARGEST key is the pair to take: the largest IoU, then the lowest slot, then the
+    lowest row.  No two pairs share a key, and 0 is no pair.  Arrays or scalars -> uint64."""
+    bits = np.asarray(iou, np.float32).view(np.uint32).astype(np.uint64)
+    return (bits << np.uint64(32)) | ((np.uint64(65535) - np.asarray(slot).astype(np.uint64)) << np.uint64(16)) | \
+        (np.uint64(65535) - np.asarray(row).astype(np.uint64))
+
+
+def track_iou(tracks, boxes):
+    """IoU of every (track box, detection box) pair, (T, 4) and (n, 4) float32 of top, left, bottom, right, all FINITE ->
+    (T, n) float32, every operation rounded on its own in this order:
+        ih = min(b1, b2) - max(t1, t2), iw = min(r1, r2) - max(l1, l2)           (min(a, b) = a if a < b else b; max likewise)
+        ih > 0 and iw > 0: inter = ih * iw, union = ((b1 - t1) * (r1 - l1) + (b2 - t2) * (r2 - l2)) - inter, iou = inter / union
+        otherwise 0
+    An overflowing area can make the quotient NaN; a NaN is no candidate."""
+    f32 = np.float32
+    a, z = np.asarray(tracks, f32)[:, None, :], np.asarray(boxes, f32)[None, :, :]
+    with np.errstate(all="ignore"):
+        lo = lambda p, q: np.where(p < q, p, q)
+        hi = lambda p, q: np.where(p > q, p, q)
+        ih = lo(a[..., 2], z[..., 2]) - hi(a[..., 0], z[..., 0])
+        iw = lo(a[..., 3], z[..., 3]) - hi(a[..., 1], z[..., 1])
+        inter = ih * iw
+        a1 = (a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1])
+        a2 = (z[..., 2] - z[..., 0]) * (z[..., 3] - z[..., 1])
+        union = (a1 + a2) - inter
+        iou = np.where((ih > 0) & (iw > 0), inter / union, f32(0))
+    assert iou.dtype == f32
+    return iou
+
+
+def track_class(value):
+    """The class of a detection row as the tracker reads it: the float32 truncated toward zero when it lies in
+    [-2^31, 2^31), -1 otherwise (NaN included).  Array -> int32."""
+    v = np.asarray(value, np.float32)
+    ok = (v >= np.float32(-2147483648.0)) & (v < np.float32(2147483648.0))
+    return np.where(ok, np.where(ok, v, 0).astype(np.int64), -1).astype(np.int32)
+
+
+def _track_range(rec, depth_ok, depth, gains):
+    """Step 3's range update of one record."""
+    f32 = np.float32
+    if not depth_ok:
+        return
+    if rec["range_age"] < 0:
+        rec["x"][4], rec["v"][4] = depth, f32(0)
+    else:
+        r = f32(depth - rec["x"][4])
+        rec["x"][4] = f32(rec["x"][4] + f32(gains[0] * r))
+        rec["v"][4] = f32(rec["v"][4] + f32(gains[1] * r))
+    rec["range_age"] = 0
+
+
+def track_update(table, head, rows, kept, box_points=None, box_radar=None, params=None):
+    """One call of the tracker on every stream -- this project's own definition, the reference has no tracker:
+    (table, head, ids, flag), new arrays.  table (B, T) TRACK_DTYPE and head (B, 4) int32 are the state BEFORE the call (zeros:
+    the reset state), rows (B, cap, >= 7) float32 and kept (B) int32 as `FrameResult` holds them (top, left, bottom, right in
+    pixels of the original frame, the class in column 6), box_points (B, cap) int32 and box_radar (B, cap, 2, 5) float32 the
+    radar readout of the rows (`box_radar`; both or neither), params from `check_track_params` (max_tracks is not read: T is
+    the table's).  ids (B, cap) int32: the id of the track each row matched or started, 0 for an invalid row, for a row that
+    found no slot and from row kept[b] on.  flag: FLAG_BOX_COUNT when a kept[b] outside [0, cap] was clamped,
+    FLAG_TRACK_FULL when a valid row found no free slot.  Everything in float32, every operation rounded on its own.
+    Per stream, with n = kept[b] clamped:
+      1 predict  every live slot (id != 0): x[k] = x[k] + v[k], k < 4; with range_age >= 0 the same for x[4], and range_age
+                 += 1 (saturating).  A slot whose predicted box is not finite is freed (all 16 words zero)
+      2 match    a row is VALID when its four coordinates are finite, bottom > top and right > left.  A live slot and a valid
+                 row of its class (`track_class` of column 6) are a candidate pair iff `track_iou` >= iou (equality matches).
+                 Greedy: repeatedly take the candidate of the largest `track_key` among unmatched slots and unmatched rows
+      3 update   a matched (slot, row i), per box component: r = z - x, x = x + g_pos r, v = v + g_vel r; hits += 1
+                 (saturating), misses = 0, row = i.  Range, when box_points[b, i] > 0 and depth = box_radar[b, i, 1, 0] (the
+                 lower median) is finite: range_age < 0: x[4] = depth, v[4] = 0; otherwise the same filter with range_gain;
+                 then range_age = 0
+      4 coast    an unmatched live slot: misses += 1, row = -1; freed when misses > max_age
+      5 births   valid unmatched rows in ascending order take the free slots in ascending order, those freed in 1 and 4
+                 included: id = ++head[0], cls, hits = 1, misses = 0, row = i, x[0:4] = z, v = 0, range_age = -1, then the
+                 range as in 3.  Without a free slot: id 0 and FLAG_TRACK_FULL
+      6 header   head[1] = live tracks, head[3] = births of this call, head[2] += 1"""
+    f32, fn = np.float32, "track_update"
+    p = check_track_params(params, fn)
+    table, head, rows, kept = np.array(table), np.array(head), np.asarray(rows), np.asarray(kept)
+    if table.dtype != TRACK_DTYPE or table.ndim != 2 or not 1 <= table.shape[1] <= TRACK_MAX_TRACKS:
+        raise RuntimeError(f"{fn}: table is (B, T) TRACK_DTYPE with T in [1, {TRACK_MAX_TRACKS}], got {table.dtype} {table.shape}")
+    B, T = table.shape
+    if head.shape != (B, TRACK_HEAD) or head.dtype != np.int32:
+        raise RuntimeError(f"{fn}: head is ({B}, {TRACK_HEAD}) int32, got {head.dtype} {head.shape}")
+    if rows.ndim != 3 or rows.shape[0] != B or rows.shape[2] < 7 or rows.dtype != np.float32 or not 1 <= rows.shape[1] <= TRACK_MAX_ROWS:
+        raise RuntimeError(f"{fn}: rows are ({B}, cap, >= 7) float32 with cap in [1, {TRACK_MAX_ROWS}], got {rows.dtype} {rows.shape}")
+    cap = rows.shape[1]
+    if kept.shape != (B,) or kept.dtype != np.int32:
+        raise RuntimeError(f"{fn}: kept is ({B}) int32, got {kept.dtype} {kept.shape}")
+    if (box_points is None) != (box_radar is None):
+        raise RuntimeError(f"{fn}: box_points and box_radar come together or not at all")
+    if box_points is not None:
+        box_points, box_radar = np.asarray(box_points), np.asarray(box_radar)
+        if box_points.shape != (B, cap) or box_points.dtype != np.int32 or box_radar.shape != (B, cap, 2, 5) or box_radar.dtype != f32:
+            raise RuntimeError(f"{fn}: box_points is ({B}, {cap}) int32 and box_radar ({B}, {cap}, 2, 5) float32, got "
+                               f"{box_points.dtype} {box_points.shape} and {box_radar.dtype} {box_radar.shape}")
+    thr, max_age, (gp, gv), rg = p["iou"], p["max_age"], p["gain"], p["range_gain"]
+    ids, flag = np.zeros((B, cap), np.int32), 0
+    slots = np.arange(T)
+    for b in range(B):
+        tab, n = table[b], min(max(int(kept[b]), 0), cap)
+        if n != int(kept[b]):
+            flag |= 512
+        with np.errstate(all="ignore"):
+            # 1 predict
+            live = tab["id"] != 0
+            tab["x"][:, :4] = np.where(live[:, None], tab["x"][:, :4] + tab["v"][:, :4], tab["x"][:, :4])
+            ranged = live & (tab["range_age"] >= 0)
+            tab["x"][:, 4] = np.where(ranged, tab["x"][:, 4] + tab["v"][:, 4], tab["x"][:, 4])
+            tab["range_age"] = np.where(ranged & (tab["range_age"] < _INT_MAX), tab["range_age"] + 1, tab["range_age"])
+            lost = live & ~np.isfinite(tab["x"][:, :4]).all(1)
+            tab[lost] = np.zeros((), TRACK_DTYPE)
+            live &= ~lost
+            # 2 match
+            z = np.ascontiguousarray(rows[b, :n, :4])
+            cls = track_class(rows[b, :n, 6])
+            valid = np.isfinite(z).all(1) & (z[:, 2] > z[:, 0]) & (z[:, 3] > z[:, 1])
+            iou = track_iou(np.where(live[:, None], tab["x"][:, :4], f32(0)), np.where(valid[:, None], z, f32(0)))
+            cand = live[:, None] & valid[None, :] & (tab["cls"][:, None] == cls[None, :]) & (iou >= thr)
+        cs, ci = np.nonzero(cand)
+        keys = track_key(iou[cs, ci], cs, ci)
+        slot_row, row_slot = np.full(T, -1), np.full(n, -1)
+        open_ = np.ones(len(keys), bool)
+        while open_.any():                   # the plain way: one pair at a time
+            k = int(np.argmax(np.where(open_, keys, np.uint64(0))))
+            s, i = int(cs[k]), int(ci[k])
+            slot_row[s], row_slot[i] = i, s
+            open_ &= (cs != s) & (ci != i)
+        # 3 update, 4 coast
+        for s in slots[live]:
+            rec, i = tab[s], slot_row[s]
+            if i < 0:
+                rec["misses"] += 1
+                rec["row"] = -1
+                if rec["misses"] > max_age:
+                    tab[s] = np.zeros((), TRACK_DTYPE)
+                continue
+            for k in range(4):
+                r = f32(z[i, k] - rec["x"][k])
+                rec["x"][k] = f32(rec["x"][k] + f32(gp * r))
+                rec["v"][k] = f32(rec["v"][k] + f32(gv * r))
+            rec["hits"] = min(int(rec["hits"]) + 1, _INT_MAX)
+            rec["misses"], rec["row"] = 0, i
+            ids[b, i] = rec["id"]
+            if box_points is not None:
+                depth = box_radar[b, i, 1, 0]
+                _track_range(rec, box_points[b, i] > 0 and np.isfinite(depth), depth, rg)
+        # 5 births
+        free = [int(s) for s in slots[tab["id"] == 0]]
+        births = 0
+        for i in np.flatnonzero(valid & (row_slot < 0)):
+            if births == len(free):
+                flag |= FLAG_TRACK_FULL
+                break
+            rec = tab[free[births]]
+            births += 1
+            rec["id"] = ids[b, i] = ids_wrap(int(head[b, 0]) + births)
+            rec["cls"], rec["hits"], rec["misses"], rec["row"], rec["range_age"] = cls[i], 1, 0, i, -1
+            rec["x"][:4], rec["x"][4], rec["v"][:] = z[i], 0, 0
+            if box_points is not None:
+                depth = box_radar[b, i, 1, 0]
+                _track_range(rec, box_points[b, i] > 0 and np.isfinite(depth), depth, rg)
+        # 6 header
+        head[b, 0] = ids_wrap(int(head[b, 0]) + births)
+        head[b, 1], head[b, 3] = int((tab["id"] != 0).sum()), births
+        head[b, 2] = ids_wrap(int(head[b, 2]) + 1)
+    return table, head, ids, flag
+
+
+def ids_wrap(v):
+    """An int32 counter after 2^31 - 1: it wraps, as the device's does (2^31 births or calls of one stream are not reached)."""
+    return np.int32(((int(v) + 2 ** 31) % 2 ** 32) - 2 ** 31)
+
+
+def track_text(tracks):
+    """The <stem>_tracks.txt of `predict_dir` for one picture: tracks, a TRACK_DTYPE array (free slots are skipped) -> one line
+    per live track in slot order, space-separated: id class hits misses top left bottom right range rate -- the four integers,
+    then x[0:4], and x[4], v[4] of the range filter (0 0 before the first radar update); every float as %.9g, which names a
+    float32 exactly."""
+    tracks = np.asarray(tracks)
+    if tracks.dtype != TRACK_DTYPE or tracks.ndim != 1:
+        raise RuntimeError(f"track_text: expected a one-dimensional TRACK_DTYPE array, got {tracks.dtype} {tracks.shape}")
+    lines = []
+    for t in tracks[tracks["id"] != 0]:
+        floats = list(t["x"][:4]) + [t["x"][4], t["v"][4]]
+        lines.append(" ".join([str(int(t[k])) for k in ("id", "cls", "hits", "misses")] + ["%.9g" % float(v) for v in floats]) + "\n")
+    return "".join(lines)
+
+
 # ---- radar points under Mosaic: host statement of the radar-points kernels of csrc/mosaic.hip ----------------------------------
 # vrnet_radar_source of include/vrnet_hip.h, one record per SOURCE (56 bytes): what the kernel needs beside the Mosaic record
 RADAR_SOURCE_DTYPE = np.dtype([("count", "<i4"), ("reserved", "<i4"), ("P", "<f4", (12,))])

@@ -169,6 +169,7 @@ _SIGS = {
     "vrnet_radar_map_post_f32": ([P, I, P, I, I, I, I, F, P, I, P, P, P, L, P], I),
     "vrnet_box_radar_workspace": ([I, I], L),
     "vrnet_box_radar_f32": ([P, I, P, I, P, P, I, F, F, P, P, P, P, L, P], I),
+    "vrnet_track_update_f32": ([P, P, I, I, P, I, P, P, P, P, F, I, F, F, F, F, P, P], I),
     "vrnet_mosaic_radar_points_workspace": ([I, I, I], L),
     "vrnet_mosaic_radar_points_f32": ([P, I, I, P, P, I, I, I, I, I, I, F, P, P, P, L, P], I),
     "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
@@ -1784,6 +1785,43 @@ def box_radar(points, views, rows, kept, min_depth, shrink, counts, readout, fla
     _check(_lib.vrnet_box_radar_f32(ptr(points), max_points, _views(views, B, fn), B, ptr(rows), ptr(kept), cap, float(min_depth),
                                     float(shrink), ptr(counts), ptr(readout), ptr(flag), ptr(ws), ws.numel(), stream()), fn)
     return counts, readout
+
+
+# ---- multi-object tracking of the detections (include/vrnet_hip.h "multi-object tracking of the detections") -----------------
+TRACK_WORDS, TRACK_HEAD = 16, 4  # sizeof(vrnet_track) / 4; the int32 words of a stream's header
+
+
+def track_update(rows, kept, table, head, ids, params, box_points=None, box_radar=None, flag=None):
+    """One call of the tracker on every stream (vrnet_track_update_f32, one launch): rows (B, cap, 7) f32 and kept (B) int32 as
+    `detect_finish` writes them, cap <= 1024; table (B, T, 16) int32, the (B, T) vrnet_track records of `data.TRACK_DTYPE` as
+    words, T in [1, 256], and head (B, 4) int32: the state, updated in place (zeros: the reset state); ids (B, cap) int32, the
+    track id of every row, every element written; params: the dict of `data.check_track_params` (iou, max_age, gain,
+    range_gain; max_tracks is the table's T).  box_points (B, cap) int32 and box_radar (B, cap, 2, 5) f32: the outputs of
+    `box_radar` for these rows, both or neither.  flag (1) int32 or None: FLAG_BOX_COUNT for a clamped kept, 32768
+    (data.FLAG_TRACK_FULL) for a valid row that found no free slot.  What `data.track_update` gives, bit for bit.  Returns
+    (table, head, ids)."""
+    fn = "track_update"
+    if rows is None or rows.dim() != 3 or rows.shape[1] < 1 or rows.shape[2] != 7:
+        raise RuntimeError(f"{fn}: expected rows (B, cap, 7)")
+    B, cap = rows.shape[:2]
+    if table is None or table.dim() != 3 or table.shape[0] != B or table.shape[1] < 1 or table.shape[2] != TRACK_WORDS:
+        raise RuntimeError(f"{fn}: expected table ({B}, max_tracks, {TRACK_WORDS}) int32, the records as words")
+    T = table.shape[1]
+    if kept is None or head is None or ids is None:
+        raise RuntimeError(f"{fn}: kept, head and ids are required")
+    if (box_points is None) != (box_radar is None):
+        raise RuntimeError(f"{fn}: box_points and box_radar come together or not at all")
+    _tensors(fn, ((rows, (B, cap, 7), torch.float32), (kept, (B,), torch.int32), (table, (B, T, TRACK_WORDS), torch.int32),
+                  (head, (B, TRACK_HEAD), torch.int32), (ids, (B, cap), torch.int32), (box_points, (B, cap), torch.int32),
+                  (box_radar, (B, cap, 2, 5), torch.float32), (flag, (1,), torch.int32)))
+    try:
+        iou, max_age, (gp, gv), (rp, rv) = params["iou"], params["max_age"], params["gain"], params["range_gain"]
+    except (TypeError, KeyError, ValueError):
+        raise RuntimeError(f"{fn}: params is the dict of data.check_track_params") from None
+    _check(_lib.vrnet_track_update_f32(ptr(rows), ptr(kept), B, cap, ptr(table), T, ptr(head), ptr(ids), ptr(box_points),
+                                       ptr(box_radar), float(iou), int(max_age), float(gp), float(gv), float(rp), float(rv),
+                                       ptr(flag), stream()), fn)
+    return table, head, ids
 
 
 # ---- radar points under Mosaic (include/vrnet_hip.h "radar points under Mosaic") ----------------------------------------------

@@ -20,7 +20,10 @@ dehaze= puts hip.dehaze in front of the letterbox, so that everything downstream
 FLAG_DEHAZE, a degenerate image that went on unchanged.  A pipeline built with ace= puts hip.ace there too, behind hip.dehaze
 when both are on, and adds FLAG_ACE for its degenerate images.  A pipeline built with radar_points and box_radar= adds
 hip.box_radar behind the finish node (behind the crops): the radar readout of every kept detection; FLAG_BOX_COUNT, a kept count
-outside the row buffer, is ruled out by the NMS that writes it.
+outside the row buffer, is ruled out by the NMS that writes it.  A pipeline built with track= adds hip.track_update behind
+that (behind the crops or the finish node without box_radar) and in front of decode.seg_predict: every batch slot becomes a
+stream whose track table lives on the device across runs, and FLAG_TRACK_FULL says that a valid row found no free slot in it
+and got track id 0.
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
@@ -41,6 +44,7 @@ FLAG_LABEL_SCORE = rendering.FLAG_LABEL_SCORE    # 2048, csrc/labels.hip (a pipe
 FLAG_CROP_ARENA = rendering.FLAG_CROP_ARENA      # 4096, csrc/crops.hip (a pipeline built with crops): a crop that did not fit
 FLAG_DEHAZE = rendering.FLAG_DEHAZE              # 8192, csrc/dehaze.hip (a pipeline built with dehaze): a degenerate image, unchanged
 FLAG_ACE = rendering.FLAG_ACE                    # 16384, csrc/ace.hip (a pipeline built with ace): a degenerate image, unchanged
+FLAG_TRACK_FULL = data.FLAG_TRACK_FULL           # 32768, VR_FLAG_TRACK_FULL of csrc/common.h (a pipeline built with track): the table was full
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -231,12 +235,19 @@ class FrameResult:
     is what everything else of the result was computed from (the stage reads the dehazed frames when both are on).
     From a pipeline built with box_radar (None otherwise): box_points (B, cap) int32, the radar points inside each kept box,
     and box_radar (B, cap, 2, 5) float32, (depth, f0, f1, f2, f3) of the nearest of them and of their lower median by depth
-    (`data.box_radar` is the rule), both zero from row kept[b] on; `radar_readout` brings them to the host."""
+    (`data.box_radar` is the rule), both zero from row kept[b] on; `radar_readout` brings them to the host.
+    From a pipeline built with track (None otherwise): track_ids (B, cap) int32, the id of the track each row matched or
+    started (0: none, and from row kept[b] on), track_table (B, T, 16) int32, the pipeline's own table of `data.TRACK_DTYPE`
+    records as words, and track_head (B, 4) int32 (ids handed out, live tracks, calls, births of this call) -- the state after
+    this run, which the next run updates in place; `tracks` brings them to the host."""
     __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
-                 "heat_picture", "heat_range", "crops", "dehazed", "enhanced", "box_points", "box_radar")
+                 "heat_picture", "heat_range", "crops", "dehazed", "enhanced", "box_points", "box_radar", "track_ids",
+                 "track_table", "track_head")
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
-                 heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None, box_points=None, box_radar=None):
+                 heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None, box_points=None, box_radar=None,
+                 track_ids=None, track_table=None, track_head=None):
+        self.track_ids, self.track_table, self.track_head = track_ids, track_table, track_head
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
         self.heat_mask, self.heat_picture, self.heat_range, self.crops = heat_mask, heat_picture, heat_range, crops
@@ -267,6 +278,20 @@ class FrameResult:
         readout = packed[B * cap:B * cap * 11].reshape(B, cap, 10)
         kept = packed[B * cap * 11:].view(np.int32)
         return [np.concatenate([counts[b, :kept[b], None].astype(np.float32), readout[b, :kept[b]]], axis=1) for b in range(B)]
+
+    def tracks(self):
+        """The tracks of a pipeline built with track, after this run: per stream a pair (the live records as a
+        `data.TRACK_DTYPE` array in slot order, the track ids of the kept rows as an (N_b) int32 array in the order of
+        `detections()`).  One device-to-host copy (table, ids and kept packed into one tensor), which waits for the frame."""
+        if self.track_table is None or self.track_ids is None:
+            raise RuntimeError("FrameResult.tracks: the pipeline was not built with track")
+        B, T = self.track_table.shape[:2]
+        cap = self.track_ids.shape[1]
+        packed = torch.cat([self.track_table.reshape(-1), self.track_ids.reshape(-1), self.kept]).cpu().numpy()
+        table = packed[:B * T * 16].view(data.TRACK_DTYPE).reshape(B, T)
+        ids = packed[B * T * 16:B * T * 16 + B * cap].reshape(B, cap)
+        kept = packed[B * T * 16 + B * cap:]
+        return [(table[b][table[b]["id"] != 0].copy(), ids[b, :kept[b]].copy()) for b in range(B)]
 
 
 class FramePipeline:
@@ -351,15 +376,26 @@ class FramePipeline:
     launches when crops is on) and read the static `points` and `views` and the rows of the result, with radar_min_depth;
     box_shrink in (0, 1] scales every box about its centre first.  Outputs and workspace are allocated before the capture.
     Fixed-size and ragged pipelines alike, with and without letterbox_image: rows and projected points both live in the
-    original frame."""
+    original frame.
+
+    track: None (the default: exactly the calls issued without it), True or a dict of `data.check_track_params` (max_tracks,
+    iou, max_age, gain, range_gain) -- multi-object tracking of the kept detections on the device (`data.track_update`,
+    csrc/track.hip).  Every batch slot b becomes a STREAM: successive runs bring successive frames of camera b.  A table of
+    max_tracks tracks per stream lives in device memory across the runs (and the replays of the graph); the one launch of
+    hip.track_update behind hip.box_radar -- behind the crops or the finish node without it -- and in front of the seg node
+    predicts, matches greedily by IoU within a class, filters box and rates, and with box_radar the range and its rate from
+    the lower-median depth of the readout, coasts, frees and starts tracks, and writes `FrameResult.track_ids`.  Table, header
+    and ids are allocated before the capture and zeroed after the warm-up, which runs the chain; `reset_tracks` zeroes them
+    again.  Rates are per call: a stream must be fed at a constant frame rate.  Fixed-size and ragged pipelines alike."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
-                 font=None, label_sizes=None, crops=None, dehaze=None, ace=None, box_radar=None, box_shrink=1.0):
+                 font=None, label_sizes=None, crops=None, dehaze=None, ace=None, box_radar=None, box_shrink=1.0, track=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
+        self.track = None if track is None or track is False else data.check_track_params(track, "FramePipeline")
         self.crop_capacity = crop_capacity(crops, self.batch, self.frame_shape)
         self.dehaze = dehaze_config(dehaze)
         if self.dehaze is not None and not rendering.dehaze_size_ok(*self.frame_shape, self.dehaze["r"]):
@@ -438,6 +474,8 @@ class FramePipeline:
             self._capture()
         else:
             self._warm_up(1)
+        if self.track is not None:            # the warm-up and the capture ran the chain on zero input: back to the reset state
+            self.reset_tracks()
 
     def _label_atlas(self, labels, class_names, font, label_sizes):
         """The atlas of the constructor's labels / class_names / font / label_sizes (None without labels), and the static
@@ -505,6 +543,12 @@ class FramePipeline:
         if self.box_radar:                    # before the capture: the two outputs and the projected points
             self._box_points, self._box_radar = torch.zeros((B, cap), **i32), torch.zeros((B, cap, 2, 5), device=dev)
             self._box_ws = torch.empty(hip.box_radar_workspace_bytes(B, self.radar_points.max_points), dtype=torch.uint8, device=dev)
+        self._track_table = self._track_head = self._track_ids = None
+        if self.track is not None:            # before the capture: the state of every stream and the ids of the rows
+            if cap > data.TRACK_MAX_ROWS:
+                raise RuntimeError(f"FramePipeline: track takes at most {data.TRACK_MAX_ROWS} rows an image, max_candidates gives {cap}")
+            self._track_table = torch.zeros((B, self.track["max_tracks"], hip.TRACK_WORDS), **i32)
+            self._track_head, self._track_ids = torch.zeros((B, hip.TRACK_HEAD), **i32), torch.zeros((B, cap), **i32)
 
     def _chain(self):
         """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
@@ -548,6 +592,9 @@ class FramePipeline:
         if self.box_radar:                    # behind the finish node (and the crops): rows and points share the original frame
             hip.box_radar(self.points, self.views, self._rows, self._kept, float(self.radar_points.min_depth), self.box_shrink,
                           self._box_points, self._box_radar, flag=self.flag, ws=self._box_ws)
+        if self.track is not None:            # behind the readout, in front of the seg node: the state is updated in place
+            hip.track_update(self._rows, self._kept, self._track_table, self._track_head, self._track_ids, self.track,
+                             box_points=self._box_points, box_radar=self._box_radar, flag=self.flag)
         if self.ragged or self.letterbox_image:
             class_map = decode.seg_predict(seg, (H, W), self.image_shape, geom=geom, capacity=self._slots, flag=self.flag)
         else:                                 # the frame was stretched over the whole input: the window is the input
@@ -566,7 +613,8 @@ class FramePipeline:
                 label_sizes=self.label_size_tab)
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops,
                              dehazed=dehazed, enhanced=frames if self.ace is not None else None, box_points=self._box_points,
-                             box_radar=self._box_radar)
+                             box_radar=self._box_radar, track_ids=self._track_ids, track_table=self._track_table,
+                             track_head=self._track_head)
         if self.heatmap:
             result.heat_picture, result.heat_mask, result.heat_range = rendering.heatmap(
                 frames, det, (H, W), alpha=self.heat_alpha, geom=geom, flag=self.flag, **self._heat_window)
@@ -601,6 +649,22 @@ class FramePipeline:
         from .graph import collector_held_off
         with collector_held_off(), torch.no_grad(), torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
             self.result = self._chain()
+
+    def reset_tracks(self, streams=None):
+        """Zeroes the track state of the named streams (batch slots), or of all: table, header and ids, on the current
+        stream, without a host synchronisation.  A stream that starts a new sequence is reset; ids start again at 1."""
+        if self.track is None:
+            raise RuntimeError("FramePipeline.reset_tracks: the pipeline was not built with track")
+        if streams is None:
+            streams = range(self.batch)
+        streams = [int(b) for b in streams]
+        if any(not 0 <= b < self.batch for b in streams):
+            raise RuntimeError(f"FramePipeline.reset_tracks: streams are batch slots in [0, {self.batch}), got {streams}")
+        with torch.cuda.device(self.device):
+            for b in streams:
+                self._track_table[b].zero_()
+                self._track_head[b].zero_()
+                self._track_ids[b].zero_()
 
     def run(self, frames_u8, radar, sizes=None, calib=None):
         """frames_u8 (B, ih, iw, 3) uint8 RGB and radar (B, 4, H, W) float32 / float64: numpy arrays or tensors, pageable,
@@ -690,10 +754,18 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     with ace the enhanced frame as <stem>_ace.png, from one built with box_radar the radar readout of the picture's
     detections as <stem>_radar.txt (`radar_text`).  Two pictures that would share one output name (names that differ only in
     their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on, or `a_dehaze.jpg` with dehazing on, or `a_ace.jpg`
-    with ACE on, or `a_radar.jpg` with the readout on): with dir_save_path that raises before anything runs."""
+    with ACE on, or `a_radar.jpg` with the readout on, or `a_tracks.jpg` with tracking on): with dir_save_path that raises
+    before anything runs.  A pipeline built with track must have batch 1 -- the folder then is ONE sequence in its sorted
+    order, fed to stream 0 of the pipeline as it stands (call `reset_tracks` first for a fresh sequence), and the live tracks
+    after every picture are saved as <stem>_tracks.txt (`data.track_text`); with batch > 1 neighbouring files would land in
+    different streams, which raises before anything runs."""
     from PIL import Image
     if not getattr(pipeline, "ragged", False):
         raise RuntimeError("predict_dir: needs a ragged pipeline (FramePipeline(..., ragged=True)): a folder holds pictures of any size")
+    tracking = getattr(pipeline, "track", None) is not None
+    if tracking and pipeline.batch != 1:
+        raise RuntimeError(f"predict_dir: a tracking pipeline reads the folder as one sequence and needs batch 1, got batch "
+                           f"{pipeline.batch}: neighbouring pictures would land in different streams")
     names = sorted(n for n in os.listdir(dir_origin_path) if n.lower().endswith(IMAGE_EXTENSIONS))
     if dir_save_path is not None:
         stems = {}
@@ -702,7 +774,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
             targets = (stem,) + ((stem + "_heat",) if getattr(pipeline, "heatmap", False) else ()) + \
                 ((stem + "_dehaze",) if getattr(pipeline, "dehaze", None) is not None else ()) + \
                 ((stem + "_ace",) if getattr(pipeline, "ace", None) is not None else ()) + \
-                ((stem + "_radar",) if getattr(pipeline, "box_radar", False) else ())
+                ((stem + "_radar",) if getattr(pipeline, "box_radar", False) else ()) + \
+                ((stem + "_tracks",) if tracking else ())
             for target in targets:
                 other = stems.setdefault(target, n)
                 if other != n:
@@ -730,9 +803,13 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         crops = None if dir_save_path is None else getattr(result, "crops", None)
         crops = None if crops is None else crops.images()
         readout = None if dir_save_path is None or getattr(result, "box_radar", None) is None else result.radar_readout()
+        tracks = None if dir_save_path is None or not tracking else result.tracks()
         for b, n in enumerate(chunk):
             out.append((n, dets[b]))
             ih, iw = (int(v) for v in result.sizes[b])
+            if tracks is not None:
+                with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_tracks.txt"), "w") as f:
+                    f.write(data.track_text(tracks[b][0]))
             if readout is not None:
                 with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_radar.txt"), "w") as f:
                     f.write(radar_text(dets[b], readout[b]))

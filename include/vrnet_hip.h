@@ -1328,6 +1328,59 @@ int vrnet_box_radar_f32(const float* points, int max_points, const vrnet_radar_v
                         const int* kept, int cap, float min_depth, float shrink, int* counts_out, float* readout_out, int* flag,
                         void* workspace, long workspace_bytes, void* stream);
 
+/* ---- multi-object tracking of the detections (csrc/track.hip) ------------------------------------------------------------------
+ * Added within ABI 11: one new symbol and one new record layout (vrnet_track) only, no existing signature, layout or kernel
+ * behaviour changed; hip.py binds every declared symbol at import.
+ * Every batch slot b is a STREAM: successive calls bring successive frames of camera b, and a table of max_tracks tracks per
+ * stream persists in device memory between the calls.  The reference has no tracker; the rule is this project's definition
+ * (host statement: data.track_update) and the kernel equals it bit for bit.
+ * table (B, max_tracks) records of 64 bytes, max_tracks in [1, 256]; a free slot is all zeros, so zeroed memory is the reset
+ * state.  head (B, 4) int32 per stream: ids handed out so far, live tracks, calls so far, births of this call; zeros at reset.
+ * rows (B, cap, 7) fp32 and kept (B) int32 as vrnet_detect_finish_f32 writes them (top, left, bottom, right in pixels of the
+ * original frame in front, the class in column 6), cap <= 1024.  box_points (B, cap) int32 and box_radar (B, cap, 2, 5) fp32:
+ * the outputs of vrnet_box_radar_f32 for the same rows, both or both NULL.
+ * THE RULE, in float32, every operation rounded on its own, nothing contracted.  Per stream, n = kept[b] clamped to [0, cap]:
+ *   1 predict  every live slot (id != 0): x[k] = x[k] + v[k], k < 4; with range_age >= 0 the same for x[4] and range_age += 1
+ *              (saturating).  A slot whose predicted box is not finite is freed
+ *   2 match    a row is VALID when its four coordinates are finite, bottom > top and right > left; its class is column 6
+ *              truncated toward zero when inside [-2^31, 2^31), -1 otherwise.  For a live slot and a valid row of its class:
+ *              ih = min(b1, b2) - max(t1, t2), iw = min(r1, r2) - max(l1, l2) (min(a, b) = a < b ? a : b, max likewise);
+ *              ih > 0 and iw > 0: inter = ih iw, union = ((b1 - t1)(r1 - l1) + (b2 - t2)(r2 - l2)) - inter,
+ *              iou = inter / union (correctly rounded); otherwise 0.  A candidate iff iou >= the threshold (equality matches,
+ *              a NaN does not).  key = bits(iou) << 32 | (65535 - slot) << 16 | (65535 - row).  Greedy: repeatedly the
+ *              candidate of the LARGEST key among unmatched slots and unmatched rows -- the largest IoU, then the lowest slot,
+ *              then the lowest row
+ *   3 update   a matched (slot, row i), per box component: r = z - x, x = x + gain_pos r, v = v + gain_vel r; hits += 1
+ *              (saturating), misses = 0, row = i.  Range, with the radar pair, box_points[b][i] > 0 and a finite
+ *              depth = box_radar[b][i][1][0] (the lower median): range_age < 0: x[4] = depth, v[4] = 0; otherwise the same
+ *              filter with the range gains; then range_age = 0
+ *   4 coast    an unmatched live slot: misses += 1, row = -1; freed (16 zero words) when misses > max_age
+ *   5 births   valid unmatched rows in ascending order take the free slots in ascending order, those freed in 1 and 4
+ *              included: id = ++head[0], cls, hits = 1, misses = 0, row = i, x[0..3] = z, v = 0, range_age = -1, then the
+ *              range as in 3.  A row without a free slot gets id 0 and sets bit 32768 of *flag (VR_FLAG_TRACK_FULL)
+ *   6 header   head[1] = live tracks, head[3] = births of this call, head[2] += 1
+ * ids_out (B, cap) int32: the id of the track each row matched or started; 0 for an invalid row, a row without a slot and
+ * from row kept[b] on: EVERY element is written by every call.  kept[b] outside [0, cap] is clamped and sets bit 512
+ * (VR_FLAG_BOX_COUNT).  flag may be NULL.  0 < iou <= 1, 0 <= max_age <= 2^20, every gain in [0, 2].  B < 65536.
+ * One launch, grid (B), one workgroup of 256 per stream: slot s in the registers of thread s, the boxes in LDS (about 43 KB),
+ * the matching as rounds of mutually-best pairs (the same result: keys are unique) -- per round a sweep of the open pairs,
+ * the best key of a slot by wave shuffles, the best key of a row by an integer LDS atomic maximum -- and two exclusive block
+ * scans for the births.  No workspace, no IoU matrix in memory, no float atomics (the OR into *flag is the one global
+ * atomic): the same bytes on every run.  No allocation, no memset, no host synchronisation; capturable. */
+typedef struct vrnet_track {
+  int id;              /* 0: a free slot */
+  int cls;             /* the class of the track */
+  int hits;            /* calls matched since birth, the birth counting 1 */
+  int misses;          /* consecutive calls without a match */
+  int row;             /* the detection row matched in this call; -1 when coasting */
+  int range_age;       /* calls since the last radar update; -1: never */
+  float x[5];          /* top, left, bottom, right, range */
+  float v[5];          /* their rates, per call */
+} vrnet_track;
+int vrnet_track_update_f32(const float* rows, const int* kept, int B, int cap, vrnet_track* table, int max_tracks, int* head,
+                           int* ids_out, const int* box_points, const float* box_radar, float iou, int max_age, float gain_pos,
+                           float gain_vel, float range_gain_pos, float range_gain_vel, int* flag, void* stream);
+
 /* ---- radar points under Mosaic (csrc/mosaic.hip; the projection of a point: csrc/radarpoint.h) ---------------------------------
  * Added within ABI 11: new symbols and one new record layout (vrnet_radar_source) only, no existing signature, layout or kernel
  * behaviour changed; hip.py binds every declared symbol at import.
