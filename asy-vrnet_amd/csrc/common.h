@@ -85,6 +85,7 @@ typedef struct vrnet_frame_geom {
 #define VR_FLAG_DEHAZE 8192                     /* dehaze.hip: a degenerate image, returned unchanged */
 #define VR_FLAG_ACE 16384                       /* ace.hip: a degenerate image, returned unchanged */
 #define VR_FLAG_TRACK_FULL 32768                /* track.hip: a valid row found no free slot in the track table, id 0 */
+#define VR_FLAG_CAPTION 65536                   /* captions.hip: a range or a speed that cannot be drawn, left out of its caption */
 extern "C" {
 /* include/vrnet_hip.h: one record per draw row of vrnet_crop_boxes_u8. */
 typedef struct vrnet_crop_rec {

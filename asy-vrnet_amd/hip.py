@@ -175,6 +175,9 @@ _SIGS = {
     "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
     "vrnet_render_labels_u8": ([P, I, I, I, P, P, I, P, I, I, P, P, L, P, I, I, I, P, P], I),
     "vrnet_render_labels_ragged_u8": ([P, P, P, I, I, I, P, P, I, P, I, P, P, L, P, I, I, P, P], I),
+    "vrnet_caption_text_f32": ([P, P, P, I, I, P, I, P, P, F, P, I, P, P], I),
+    "vrnet_render_captions_u8": ([P, I, I, I, P, P, I, P, I, P, P, L, P, I, I, P, P], I),
+    "vrnet_render_captions_ragged_u8": ([P, P, P, I, I, I, P, P, I, P, I, P, P, L, P, I, P, P], I),
     "vrnet_crop_boxes_u8": ([P, I, I, I, P, P, P, I, P, L, P, P, P, P], I),
     "vrnet_dehaze_workspace_bytes": ([I, I, I], L),
     "vrnet_dehaze_u8": ([P, P, I, I, I, I, I, D, D, D, P, P, P, P, L, P], I),
@@ -1921,6 +1924,78 @@ def render_labels(picture, boxes, box_offsets, box_palette, thickness, label_idx
 
 def render_labels_ragged(picture, geom, size_index, boxes, box_offsets, box_palette, label_idx, blob, records, flag=None):
     render_labels(picture, boxes, box_offsets, box_palette, None, label_idx, blob, records, size_index, flag, geom, "render_labels_ragged")
+
+
+# ---- track ids, radar range and closing speed under the rendered detections (csrc/captions.hip) ------------------------------
+FLAG_CAPTION = 65536     # VR_FLAG_CAPTION of csrc/common.h: a range or a speed that cannot be drawn, left out of its caption
+CAPTION_WORDS = 12       # int32 per caption record: 32 codes as bytes, their count, three zeros
+CAPTION_GLYPHS = 18      # "0123456789.-+#m/s "
+GLYPH_RECORD = 4         # int32 per glyph record: blob offset, cell width, cell height, 0
+
+
+def caption_text(kept, offsets, captions, ids=None, table=None, box_points=None, box_radar=None, rate_scale=0.0, flag=None):
+    """The caption of every kept row, composed on the device (vrnet_caption_text_f32, one launch): kept (B) and offsets (B + 1)
+    int32 as `detect_finish` writes them -> captions (N, 12) int32 records at offsets[b] + r, nothing else written.  ids (B, cap)
+    int32 and table (B, T, 16) int32 of `track_update`, box_points (B, cap) int32 and box_radar (B, cap, 2, 5) f32 of
+    `box_radar`: each optional, table needs ids, at least one of ids and the readout.  rate_scale: the frame rate that turns the
+    tracker's per-call range rate into the closing speed, 0 for no speed field.  flag (1) int32 or None: FLAG_CAPTION for a
+    field left out, FLAG_BOX_COUNT for a clamped kept.  What `render.caption_strings` gives, code for code.  Returns captions."""
+    fn = "caption_text"
+    if kept is None or offsets is None or captions is None:
+        raise RuntimeError(f"{fn}: kept, offsets and captions are required")
+    if (box_points is None) != (box_radar is None):
+        raise RuntimeError(f"{fn}: box_points and box_radar come together or not at all")
+    shaped = ids if ids is not None else box_points
+    if shaped is None or shaped.dim() != 2:
+        raise RuntimeError(f"{fn}: needs track ids (B, cap) or the radar readout")
+    if table is not None and (ids is None or table.dim() != 3 or table.shape[2] != TRACK_WORDS):
+        raise RuntimeError(f"{fn}: a track table (B, max_tracks, {TRACK_WORDS}) int32 needs the track ids")
+    if captions.dim() != 2:
+        raise RuntimeError(f"{fn}: captions must have shape (N, {CAPTION_WORDS})")
+    B, cap = shaped.shape
+    T = table.shape[1] if table is not None else 0
+    _tensors(fn, ((ids, (B, cap), torch.int32), (kept, (B,), torch.int32), (offsets, (B + 1,), torch.int32),
+                  (table, (B, T, TRACK_WORDS), torch.int32), (box_points, (B, cap), torch.int32),
+                  (box_radar, (B, cap, 2, 5), torch.float32), (captions, (captions.shape[0], CAPTION_WORDS), torch.int32),
+                  (flag, (1,), torch.int32)))
+    if captions.shape[0] == 0:                # nothing to write (and an empty tensor has no address to pass)
+        return captions
+    _check(_lib.vrnet_caption_text_f32(ptr(ids), ptr(kept), ptr(offsets), B, cap, ptr(table), T, ptr(box_points), ptr(box_radar),
+                                       float(rate_scale), ptr(captions), captions.shape[0], ptr(flag), stream()), fn)
+    return captions
+
+
+def render_captions(picture, boxes, box_offsets, box_palette, captions, blob, records, size_index, flag=None, geom=None,
+                    fn="render_captions"):
+    """Caption tags and text over the finished picture, in place (vrnet_render_captions_u8): picture (B,ih,iw,3) uint8, boxes
+    (N,5) / box_offsets (B+1) / box_palette (m,3) as `render` took them, captions (N, 12) int32 as `caption_text` writes them,
+    blob (bytes) uint8 and records (sizes, 18, 4) int32 of a `render.GlyphAtlas`, size_index its font size.  With geom
+    (`_table_call`) ih and iw of image b come from geom[b], and size_index is the (B) int32 device table of each image's font
+    size, -1 for an image without captions (vrnet_render_captions_ragged_u8)."""
+    table = _table_call(fn, geom)
+    if picture is None or picture.dim() != 4 or picture.shape[-1] != 3:
+        raise RuntimeError(f"{fn}: expected a contiguous uint8 picture of shape (B, ih, iw, 3)")
+    B, ih, iw = picture.shape[:3]
+    if boxes is None or box_offsets is None or box_palette is None or captions is None or blob is None or records is None:
+        raise RuntimeError(f"{fn}: boxes, box_offsets, box_palette, captions and the atlas blob and records are required")
+    if records.dim() != 3 or records.shape[0] < 1:
+        raise RuntimeError(f"{fn}: the atlas records must have shape (sizes, {CAPTION_GLYPHS}, {GLYPH_RECORD}), got {tuple(records.shape)}")
+    if torch.is_tensor(size_index) != table:
+        raise RuntimeError(f"{fn}: size_index is one font size of the atlas, or beside a geometry table the (B) int32 table of them")
+    n_rows, n_sizes = boxes.shape[0], records.shape[0]
+    _tensors(fn, ((picture, (B, ih, iw, 3), torch.uint8), (boxes, (n_rows, 5), torch.int32), (box_offsets, (B + 1,), torch.int32),
+                  (box_palette, (box_palette.shape[0], 3), torch.uint8), (captions, (n_rows, CAPTION_WORDS), torch.int32),
+                  (blob, (blob.shape[0],), torch.uint8), (records, (n_sizes, CAPTION_GLYPHS, GLYPH_RECORD), torch.int32),
+                  (flag, (1,), torch.int32), (size_index if table else None, (B,), torch.int32)))
+    if n_rows == 0:                           # nothing to draw (and an empty tensor has no address to pass)
+        return
+    rows = (ptr(boxes), ptr(box_offsets), n_rows, ptr(box_palette), box_palette.shape[0])
+    atlas = (ptr(captions), ptr(blob), blob.shape[0], ptr(records), n_sizes)
+    if table:
+        _check(_lib.vrnet_render_captions_ragged_u8(ptr(picture), _geom(geom, B, fn), ptr(size_index), B, ih, iw, *rows, *atlas,
+                                                    ptr(flag), stream()), fn)
+    else:
+        _check(_lib.vrnet_render_captions_u8(ptr(picture), B, ih, iw, *rows, *atlas, int(size_index), ptr(flag), stream()), fn)
 
 
 # ---- detection crops (csrc/crops.hip) ----------------------------------------------------------------------------------------

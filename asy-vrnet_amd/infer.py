@@ -23,7 +23,9 @@ hip.box_radar behind the finish node (behind the crops): the radar readout of ev
 outside the row buffer, is ruled out by the NMS that writes it.  A pipeline built with track= adds hip.track_update behind
 that (behind the crops or the finish node without box_radar) and in front of decode.seg_predict: every batch slot becomes a
 stream whose track table lives on the device across runs, and FLAG_TRACK_FULL says that a valid row found no free slot in it
-and got track id 0.
+and got track id 0.  A pipeline built with captions= adds hip.caption_text behind that (behind hip.box_radar without a tracker) and
+hip.render_captions behind the label launches (behind the render node without labels): '#<track id> <range>m <speed>m/s'
+under every rendered box; FLAG_CAPTION says that a range or a speed could not be drawn and was left out.
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
@@ -45,6 +47,7 @@ FLAG_CROP_ARENA = rendering.FLAG_CROP_ARENA      # 4096, csrc/crops.hip (a pipel
 FLAG_DEHAZE = rendering.FLAG_DEHAZE              # 8192, csrc/dehaze.hip (a pipeline built with dehaze): a degenerate image, unchanged
 FLAG_ACE = rendering.FLAG_ACE                    # 16384, csrc/ace.hip (a pipeline built with ace): a degenerate image, unchanged
 FLAG_TRACK_FULL = data.FLAG_TRACK_FULL           # 32768, VR_FLAG_TRACK_FULL of csrc/common.h (a pipeline built with track): the table was full
+FLAG_CAPTION = rendering.FLAG_CAPTION            # 65536, VR_FLAG_CAPTION of csrc/common.h (a pipeline built with captions): a field left out
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -202,6 +205,53 @@ def ace_config(ace):
     return rendering.ace_params(fn="FramePipeline", **ace)
 
 
+def caption_config(captions, render, track, box_radar, ragged, ih):
+    """The captions= keyword of a pipeline, checked on the host: None (no captions), True, a `render.GlyphAtlas` or a dict of
+    atlas, fps, font, sizes -> (composing, fps, size index); composing is the atlas, or True where a fixed-size pipeline of
+    frames lower than 17 rows composes the text and draws nothing; the size index is that of a fixed-size pipeline's one
+    font size (None: nothing is drawn, or a ragged pipeline, whose table follows each call).  Names what is missing."""
+    fn = "FramePipeline"
+    if captions is None or captions is False:
+        return None, 0.0, None
+    if captions is True:
+        captions = {}
+    elif isinstance(captions, rendering.GlyphAtlas):
+        captions = {"atlas": captions}
+    if not isinstance(captions, dict) or set(captions) - {"atlas", "fps", "font", "sizes"}:
+        raise RuntimeError(f"{fn}: captions is None, True, a render.GlyphAtlas or a dict of atlas, fps, font, sizes, got {captions!r}")
+    if not render:
+        raise RuntimeError(f"{fn}: captions are drawn on the rendered frame; they need render=True")
+    if not (track or box_radar):
+        raise RuntimeError(f"{fn}: captions show track ids and radar ranges; they need track= or box_radar=True (or both), and this "
+                           "pipeline has neither")
+    fps = captions.get("fps", 0.0)
+    if isinstance(fps, bool) or not isinstance(fps, (int, float, np.integer, np.floating)) or not 0.0 <= float(fps) <= 1e6:
+        raise RuntimeError(f"{fn}: captions: fps is the frame rate of the streams, a number in [0, 1e6], got {fps!r}")
+    if float(fps) > 0 and not (track and box_radar):
+        raise RuntimeError(f"{fn}: captions: fps draws the closing speed, the rate of the tracker's filtered radar range; it needs "
+                           f"track= together with box_radar=True, and this pipeline lacks {'box_radar=True' if track else 'track='}")
+    atlas, size = captions.get("atlas"), rendering.label_font_size(ih)
+    if atlas is not None:
+        if not isinstance(atlas, rendering.GlyphAtlas) or captions.get("font") is not None or captions.get("sizes") is not None:
+            raise RuntimeError(f"{fn}: captions: atlas is a render.GlyphAtlas, which brings its own font and sizes")
+    elif not ragged and size == 0:
+        if captions.get("sizes") is not None:
+            raise RuntimeError(f"{fn}: captions: sizes belongs to a ragged pipeline; a fixed-size one builds font size {size}")
+        return True, float(fps), None
+    else:
+        sizes = captions.get("sizes")
+        if sizes is None:
+            sizes = tuple(range(1, size + 1)) if ragged else (size,)
+        elif not ragged:
+            raise RuntimeError(f"{fn}: captions: sizes belongs to a ragged pipeline; a fixed-size one builds font size {size}")
+        if not len(tuple(sizes)):
+            raise RuntimeError(f"{fn}: captions: a capacity of {ih} rows has no font size >= 1 to build")
+        atlas = rendering.GlyphAtlas(captions.get("font"), sizes)
+    if ragged:
+        return atlas, float(fps), None
+    return atlas, float(fps), None if size == 0 else atlas.size_index(size)
+
+
 def unmap_scalars(input_shape, image_shape, letterbox_image):
     """(offset, scale): the (y, x) float64 pairs with which decode.yolo_correct_boxes maps a centre, (c - offset) * scale, and a
     size, s * scale -- its own expressions, np.round included; (0, 0), (1, 1) without a letterbox."""
@@ -239,15 +289,17 @@ class FrameResult:
     From a pipeline built with track (None otherwise): track_ids (B, cap) int32, the id of the track each row matched or
     started (0: none, and from row kept[b] on), track_table (B, T, 16) int32, the pipeline's own table of `data.TRACK_DTYPE`
     records as words, and track_head (B, 4) int32 (ids handed out, live tracks, calls, births of this call) -- the state after
-    this run, which the next run updates in place; `tracks` brings them to the host."""
+    this run, which the next run updates in place; `tracks` brings them to the host.
+    From a pipeline built with captions (None otherwise): captions (B * cap, 12) int32, the caption records of the kept rows,
+    image b's from row `kept[:b].sum()` on (`render.caption_decode`); `caption_strings` brings them to the host."""
     __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
                  "heat_picture", "heat_range", "crops", "dehazed", "enhanced", "box_points", "box_radar", "track_ids",
-                 "track_table", "track_head")
+                 "track_table", "track_head", "captions")
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
                  heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None, box_points=None, box_radar=None,
-                 track_ids=None, track_table=None, track_head=None):
-        self.track_ids, self.track_table, self.track_head = track_ids, track_table, track_head
+                 track_ids=None, track_table=None, track_head=None, captions=None):
+        self.track_ids, self.track_table, self.track_head, self.captions = track_ids, track_table, track_head, captions
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
         self.heat_mask, self.heat_picture, self.heat_range, self.crops = heat_mask, heat_picture, heat_range, crops
@@ -292,6 +344,17 @@ class FrameResult:
         ids = packed[B * T * 16:B * T * 16 + B * cap].reshape(B, cap)
         kept = packed[B * T * 16 + B * cap:]
         return [(table[b][table[b]["id"] != 0].copy(), ids[b, :kept[b]].copy()) for b in range(B)]
+
+    def caption_strings(self):
+        """The captions of a pipeline built with captions, as drawn: per image the list of its kept rows' strings, in the order
+        of `detections()`.  One device-to-host copy (records and kept packed into one tensor), which waits for the frame."""
+        if self.captions is None:
+            raise RuntimeError("FrameResult.caption_strings: the pipeline was not built with captions")
+        B = self.kept.shape[0]
+        packed = torch.cat([self.captions.reshape(-1), self.kept]).cpu().numpy()
+        ends = np.cumsum(packed[-B:])
+        text = rendering.caption_decode(packed[:-B].reshape(-1, rendering.CAPTION_WORDS)[:ends[-1]])
+        return [text[e - k:e] for e, k in zip(ends.tolist(), packed[-B:].tolist())]
 
 
 class FramePipeline:
@@ -386,13 +449,27 @@ class FramePipeline:
     predicts, matches greedily by IoU within a class, filters box and rates, and with box_radar the range and its rate from
     the lower-median depth of the readout, coasts, frees and starts tracks, and writes `FrameResult.track_ids`.  Table, header
     and ids are allocated before the capture and zeroed after the warm-up, which runs the chain; `reset_tracks` zeroes them
-    again.  Rates are per call: a stream must be fed at a constant frame rate.  Fixed-size and ragged pipelines alike."""
+    again.  Rates are per call: a stream must be fed at a constant frame rate.  Fixed-size and ragged pipelines alike.
+
+    captions: None (the default: exactly the calls issued without it), True, a `render.GlyphAtlas`, or a dict of atlas, fps,
+    font and sizes -- a second tag UNDER every rendered box, '#<track id> <range>m <closing speed>m/s' such as
+    '#17 42.5m -1.2m/s' (`render.caption_strings` and `render.draw_captions_host` are the rule, csrc/captions.hip the
+    kernels).  It needs render=True and at least one of track and box_radar: the id comes from the tracker, the range from the
+    track's filtered range (with a tracker) or the lower-median depth of the readout (without one).  fps (default 0: no
+    speed field) is the frame rate the streams are fed at, which turns the tracker's per-call range rate into metres per
+    second; it needs track with box_radar.  font: as `render.GlyphAtlas` takes it.  A fixed-size pipeline builds the one font
+    size `render.label_font_size(ih)` (0, below 17 rows: the text is composed, nothing is drawn); a ragged one builds every
+    size from 1 to label_font_size(ihm), or those sizes= names, and a frame whose size was not built raises in the host
+    validation of `run`, before anything is enqueued.  Two launches: hip.caption_text behind hip.track_update (behind
+    hip.box_radar without a tracker) and hip.render_captions behind the label launches (behind the render node without
+    labels); the records, `FrameResult.captions`, are allocated before the capture.  FLAG_CAPTION joins the bits of `flag`."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
-                 font=None, label_sizes=None, crops=None, dehaze=None, ace=None, box_radar=None, box_shrink=1.0, track=None):
+                 font=None, label_sizes=None, crops=None, dehaze=None, ace=None, box_radar=None, box_shrink=1.0, track=None,
+                 captions=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
         self.track = None if track is None or track is False else data.check_track_params(track, "FramePipeline")
@@ -417,6 +494,9 @@ class FramePipeline:
             self.box_shrink = float(data.check_box_shrink(box_shrink, "FramePipeline"))
         elif isinstance(box_shrink, bool) or box_shrink != 1.0:
             raise RuntimeError("FramePipeline: box_shrink belongs to box_radar=True")
+        self.captions, self.caption_fps, self.caption_size_index = caption_config(
+            captions, bool(render), self.track is not None, self.box_radar, bool(ragged), self.frame_shape[0])
+        self.caption_size_tab = None
         if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
             raise RuntimeError(f"FramePipeline: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
         if not 0.0 <= float(heat_alpha) <= 1.0:
@@ -459,6 +539,10 @@ class FramePipeline:
             self.points, self.views = self.radar_points.buffers(table, dev)
             self._radar_ws = self.radar_points.workspace(self.input_shape, dev)
         self.labels = self._label_atlas(labels, class_names, font, label_sizes)
+        if self.captions is not None and self.ragged:      # the warm-up and the capture run on frames that fill their slots
+            size = rendering.label_font_size(ih)
+            tab = np.full(B, self.captions.size_index(size) if size in self.captions.sizes else -1, np.int32)
+            self.caption_size_tab = torch.from_numpy(tab).to(dev)
         if self.dehaze is not None:           # before the capture: the second frame buffer and the workspace
             from . import hip
             self._dehazed = torch.zeros_like(self.frames_u8)
@@ -549,6 +633,9 @@ class FramePipeline:
                 raise RuntimeError(f"FramePipeline: track takes at most {data.TRACK_MAX_ROWS} rows an image, max_candidates gives {cap}")
             self._track_table = torch.zeros((B, self.track["max_tracks"], hip.TRACK_WORDS), **i32)
             self._track_head, self._track_ids = torch.zeros((B, hip.TRACK_HEAD), **i32), torch.zeros((B, cap), **i32)
+        self._captions = None
+        if self.captions is not None:         # before the capture: one record per draw row
+            self._captions = torch.zeros((B * cap, hip.CAPTION_WORDS), **i32)
 
     def _chain(self):
         """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
@@ -595,6 +682,9 @@ class FramePipeline:
         if self.track is not None:            # behind the readout, in front of the seg node: the state is updated in place
             hip.track_update(self._rows, self._kept, self._track_table, self._track_head, self._track_ids, self.track,
                              box_points=self._box_points, box_radar=self._box_radar, flag=self.flag)
+        if self.captions is not None:         # behind the tracker (or the readout): the text of every kept row
+            hip.caption_text(self._kept, self._offsets, self._captions, ids=self._track_ids, table=self._track_table,
+                             box_points=self._box_points, box_radar=self._box_radar, rate_scale=self.caption_fps, flag=self.flag)
         if self.ragged or self.letterbox_image:
             class_map = decode.seg_predict(seg, (H, W), self.image_shape, geom=geom, capacity=self._slots, flag=self.flag)
         else:                                 # the frame was stretched over the whole input: the window is the input
@@ -611,10 +701,14 @@ class FramePipeline:
                 frames, class_map, boxes, palette=self.seg_palette, mix_type=self.mix_type, alpha=self.alpha, count=True,
                 box_palette=self.box_palette, thickness=self.thickness, flag=self.flag, device=dev, labels=self.labels, geom=geom,
                 label_sizes=self.label_size_tab)
+            size = self.caption_size_tab if self.ragged else self.caption_size_index
+            if self.captions is not None and size is not None:      # behind the label launches: a pass over the finished picture
+                hip.render_captions(rendered, self._draw_rows, self._offsets, self.box_palette, self._captions,
+                                    *self.captions.on(dev), size, flag=self.flag, geom=geom)
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops,
                              dehazed=dehazed, enhanced=frames if self.ace is not None else None, box_points=self._box_points,
                              box_radar=self._box_radar, track_ids=self._track_ids, track_table=self._track_table,
-                             track_head=self._track_head)
+                             track_head=self._track_head, captions=self._captions)
         if self.heatmap:
             result.heat_picture, result.heat_mask, result.heat_range = rendering.heatmap(
                 frames, det, (H, W), alpha=self.heat_alpha, geom=geom, flag=self.flag, **self._heat_window)
@@ -694,9 +788,12 @@ class FramePipeline:
         label_tab = None
         if self.labels is not None:           # a frame whose font size was not built raises here, before anything is enqueued
             label_tab = self.labels.size_table([int(s[0]) for s in checked[2]], "FramePipeline")
-        return self._launch(*checked, label_tab=label_tab)
+        caption_tab = None
+        if self.captions is not None:         # the same for the glyph sizes
+            caption_tab = self.captions.size_table([int(s[0]) for s in checked[2]], "FramePipeline")
+        return self._launch(*checked, label_tab=label_tab, caption_tab=caption_tab)
 
-    def _launch(self, f, r, sizes=None, table=None, label_tab=None):
+    def _launch(self, f, r, sizes=None, table=None, label_tab=None, caption_tab=None):
         """The copies and the replay of `run`, on inputs that `validate_inputs` / `validate_ragged_inputs` returned."""
         with torch.cuda.device(self.device):
             if self.ragged:
@@ -704,6 +801,8 @@ class FramePipeline:
                 self.geom.copy_(data.geometry_bytes(table), non_blocking=True)
                 if label_tab is not None:
                     self.label_size_tab.copy_(torch.from_numpy(label_tab).pin_memory(), non_blocking=True)
+                if caption_tab is not None:
+                    self.caption_size_tab.copy_(torch.from_numpy(caption_tab).pin_memory(), non_blocking=True)
                 self.sizes = sizes
             else:
                 self.frames_u8.copy_(f, non_blocking=True)

@@ -41,6 +41,14 @@ ValueError for x1 < x0 where this module paints nothing.
   mask_off_y) in black, clipped: per byte v = DIV255(v * (255 - m)), DIV255(a) = ((a + 128) + ((a + 128) >> 8)) >> 8.  Font
   size `label_font_size(ih)` = floor(3e-2 ih + 0.5) (yolo.py:163); size 0 (frames lower than 17 rows) draws no labels.
 
+* `GlyphAtlas` / `caption_strings` / `draw_captions` / `draw_captions_host`: a second tag UNDER every box with what the
+  label atlas cannot hold -- '#<track id> <range>m <closing speed>m/s', e.g. '#17 42.5m -1.2m/s' -- composed on the device
+  from the track table and the radar readout (csrc/captions.hip).  The reference has nothing like it: the rule is this
+  project's, stated by `caption_strings` (the text; `fixed_tenths` is the integer statement of its '{:.1f}') and
+  `draw_captions_host` (the pixels), and the kernels equal both byte for byte.  A caption is the atlas's glyph cells side by
+  side with integer widths, NOT Pillow's layout of the whole string: kerning and fractional advances are lost, every single
+  glyph is Pillow's bytes.
+
 * `crop_boxes` / `Crops` / `crop_boxes_host` / `crop_layout`: yolo.py:180-193, the `crop` switch of detect_image -- every
   detection cut out of the ORIGINAL frame (the reference crops before it draws), all crops of a batch in one packed arena on
   the device (csrc/crops.hip).  The rule: a row left, top, right, bottom of an image (ih, iw) is clamped again, l = max(left,
@@ -76,6 +84,13 @@ FLAG_DEHAZE = 8192        # VR_FLAG_DEHAZE of csrc/common.h: a degenerate image,
 DEHAZE_MAX_SZ, DEHAZE_MAX_R = 31, 128
 FLAG_ACE = 16384          # VR_FLAG_ACE of csrc/common.h: a degenerate image, returned unchanged by `ace`
 ACE_MAX_RADIUS, ACE_MAX_BINS = 8, 4096
+FLAG_BOX_COUNT = 512      # VR_FLAG_BOX_COUNT of csrc/common.h: a kept count outside [0, cap], clamped (`caption_strings`)
+FLAG_CAPTION = 65536      # VR_FLAG_CAPTION of csrc/common.h: a range or a speed that cannot be drawn, left out of its caption
+CAPTION_ALPHABET = "0123456789.-+#m/s "          # a glyph code is the index into it
+CAPTION_GLYPHS = len(CAPTION_ALPHABET)           # 18
+CAPTION_MAX, CAPTION_WORDS = 32, 12              # glyph codes and int32 words of one caption record
+CAPTION_MAX_SIDE = 1 << 14                       # CP_MAXDIM of csrc/captions.hip: a cell side is clamped to this
+CAPTION_SATURATED = (1 << 31) - 1                # what `fixed_tenths` gives from 2^31 - 1 on, for an infinity and for a NaN
 
 _device_palettes = {}
 
@@ -764,6 +779,349 @@ def draw_labels(picture, results, atlas, input_shape=None, thickness=None, font_
             blob, records = atlas.on(dev)
             hip.render_labels(picture, rows, offsets, _palette_on(bpal, dev), int(thickness), label_idx, blob, records,
                               atlas.size_index(font_size), flag=flag)
+    return picture
+
+
+# ---- track ids, radar range and closing speed under the detections (csrc/captions.hip) ---------------------------------------
+def fixed_tenths(values):
+    """(k, negative) of float32 values, arrays of the same shape: k int32 = the exact value of |x| times 10, rounded to nearest
+    with ties to even on the exact binary value (0.25 -> 2, 0.75 -> 8), in integer arithmetic on the bits -- `score_index`
+    with one decimal and no range limit -- saturated at 2^31 - 1, which is also what an infinity or a NaN gives; negative bool =
+    the sign bit.  So '{:.1f}'.format(float(x)) is ('-' if negative else '') + f'{k // 10}.{k % 10}' wherever k is below
+    the saturation, -0.04 -> '-0.0' included.  csrc/captions.hip mirrors this line by line."""
+    s = np.asarray(values)
+    if s.dtype != np.float32:
+        raise RuntimeError(f"fixed_tenths: expected float32 values, got {s.dtype}")
+    bits = np.ascontiguousarray(s).view(np.uint32).astype(np.uint64)
+    e = ((bits >> np.uint64(23)) & np.uint64(255)).astype(np.int64)
+    m = (bits & np.uint64(0x7FFFFF)) | np.where(e > 0, np.uint64(0x800000), np.uint64(0))
+    sh = 150 - np.maximum(e, 1)                                        # |x| = m 2^-sh
+    N = np.uint64(10) * m                                              # below 2^28
+    shr = np.clip(sh, 1, 63).astype(np.uint64)
+    q, rem, half = N >> shr, N & ((np.uint64(1) << shr) - np.uint64(1)), np.uint64(1) << (shr - np.uint64(1))
+    down = (q + ((rem > half) | ((rem == half) & ((q & np.uint64(1)) == 1))).astype(np.uint64)).astype(np.int64)
+    up = np.minimum(N << np.clip(-sh, 0, 31).astype(np.uint64), np.uint64(CAPTION_SATURATED)).astype(np.int64)
+    k = np.where(sh >= 1, down, np.where(sh < -31, CAPTION_SATURATED, up))
+    k = np.where(e == 255, CAPTION_SATURATED, k).astype(np.int32)
+    return k.reshape(s.shape), (bits >> np.uint64(31)).astype(bool).reshape(s.shape)
+
+
+class GlyphAtlas:
+    """The 18 glyphs of CAPTION_ALPHABET, rasterised once on the host by Pillow, for each font size in `sizes` (each >= 1).
+    font: as `LabelAtlas` takes it -- the path of a TrueType file, a callable size -> PIL.ImageFont, or None =
+    `ImageFont.load_default(size)`.  Pillow is imported here and only here; without it this raises.
+    A glyph's mask and offset (mox, moy) are `_label_mask(font, ch)`'s, what `ImageDraw.text` would paste, and adv =
+    ceil(font.getlength(ch)).  Its CELL is the union of the advance box [0, adv) and the mask's extent [mox, mox + mw): width
+    max(adv, mox + mw) - min(mox, 0), at least 1, the mask pasted into the zeroed cell at column mox - min(mox, 0), so nothing
+    of a glyph is clipped (the built-in face has mox = -1 for '/', '3' and 's' at some sizes).  All cells of a size share the
+    height cell_h = max(moy + mh) - min(0, min moy) over the alphabet; a mask sits at row moy - min(0, min moy).
+    A caption is cells side by side with integer widths -- NOT Pillow's layout of the whole string: kerning and fractional
+    advances are lost; every single glyph is Pillow's bytes.
+    blob: the cells as uint8, row-major, back to back; records (len(sizes), 18, 4) int32 = blob offset, cell width, cell
+    height, 0; both go to a device once (`on`) and are kept.  nbytes: their size."""
+
+    def __init__(self, font=None, sizes=(32,)):
+        sizes = self._check(sizes)
+        try:
+            from PIL import ImageFont
+        except ImportError:
+            raise RuntimeError("GlyphAtlas: rasterising glyphs needs Pillow (pip install pillow); everything else in this "
+                               "module works without it") from None
+        if font is None:
+            make = ImageFont.load_default
+        elif callable(font):
+            make = font
+        else:
+            make = lambda size: ImageFont.truetype(os.fspath(font), size)      # noqa: E731
+        cells, total = [], 0
+        records = np.zeros((len(sizes), CAPTION_GLYPHS, 4), np.int32)
+        for si, size in enumerate(sizes):
+            f = make(size)
+            glyphs = []
+            for ch in CAPTION_ALPHABET:
+                mask, (mw, mh), off = _label_mask(f, ch)
+                glyphs.append((mask.reshape(mh, mw), int(off[0]), int(off[1]), int(np.ceil(f.getlength(ch)))))
+            up = -min(0, min(moy for _, _, moy, _ in glyphs))
+            cell_h = max(moy + m.shape[0] for m, _, moy, _ in glyphs) + up
+            for c, (m, mox, moy, adv) in enumerate(glyphs):
+                left = -min(mox, 0)
+                cw = max(max(adv, mox + m.shape[1]) + left, 1)
+                cell = np.zeros((cell_h, cw), np.uint8)
+                cell[moy + up:moy + up + m.shape[0], mox + left:mox + left + m.shape[1]] = m
+                records[si, c, :3] = (total, cw, cell_h)
+                cells.append(cell.reshape(-1))
+                total += cell.size
+        self._set(sizes, np.concatenate(cells), records)
+
+    @staticmethod
+    def _check(sizes):
+        try:
+            sizes = tuple(int(v) for v in sizes)
+        except (TypeError, ValueError):
+            raise RuntimeError(f"GlyphAtlas: sizes is a sequence of font sizes, got {sizes!r}") from None
+        if not sizes or min(sizes) < 1 or len(set(sizes)) != len(sizes):
+            raise RuntimeError(f"GlyphAtlas: sizes must be distinct font sizes >= 1, got {sizes!r}")
+        return sizes
+
+    def _set(self, sizes, blob, records):
+        if blob.dtype != np.uint8 or blob.ndim != 1 or records.dtype != np.int32 or records.shape != (len(sizes), CAPTION_GLYPHS, 4):
+            raise RuntimeError(f"GlyphAtlas: expected a 1-D uint8 blob and int32 records of shape (sizes, {CAPTION_GLYPHS}, 4)")
+        r = records.astype(np.int64)
+        if blob.size >= 1 << 31 or (r[..., 0] < 0).any() or (r[..., 1] < 1).any() or (r[..., 2] < 0).any() or \
+                (r[..., 1:3] > CAPTION_MAX_SIDE).any() or (r[..., 0] + r[..., 1] * r[..., 2] > blob.size).any():
+            raise RuntimeError(f"GlyphAtlas: a record points outside the blob, or a cell side outside [1, {CAPTION_MAX_SIDE}]")
+        if (r[..., 2] != r[:, :1, 2]).any():
+            raise RuntimeError("GlyphAtlas: the cells of one font size share one height")
+        self.sizes = tuple(sizes)
+        self.blob, self.records = np.ascontiguousarray(blob), np.ascontiguousarray(records)
+        self._index = {s: i for i, s in enumerate(self.sizes)}
+        self._device = {}
+
+    @classmethod
+    def from_arrays(cls, sizes, blob, records):
+        """An atlas from the arrays of another one (`save` / `load`): no font and no Pillow needed."""
+        self = cls.__new__(cls)
+        self._set(cls._check(sizes), np.asarray(blob), np.asarray(records))
+        return self
+
+    def save(self, path):
+        np.savez_compressed(path, sizes=np.array(self.sizes, np.int32), blob=self.blob, records=self.records)
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            return cls.from_arrays(z["sizes"], z["blob"], z["records"])
+
+    @property
+    def nbytes(self):
+        return int(self.blob.nbytes + self.records.nbytes)
+
+    def size_index(self, font_size):
+        """The row of `records` that holds font_size; raises for a size that was not built."""
+        i = self._index.get(int(font_size))
+        if i is None:
+            raise RuntimeError(f"GlyphAtlas: font size {int(font_size)} was not built (sizes: {self.sizes})")
+        return i
+
+    def size_table(self, heights, fn="GlyphAtlas"):
+        """The (B) int32 table of a ragged `draw_captions` for images of these heights: the size index of
+        `label_font_size(ih)`, -1 where that is 0; raises, naming the image, for a size that was not built."""
+        tab = np.empty(len(heights), np.int32)
+        for b, ih in enumerate(heights):
+            size = label_font_size(ih)
+            if size > 0 and size not in self._index:
+                raise RuntimeError(f"{fn}: image {b} of {int(ih)} rows needs font size {size}, which the glyph atlas was not "
+                                   f"built for (sizes: {self.sizes})")
+            tab[b] = self._index[size] if size > 0 else -1
+        return tab
+
+    def cell(self, font_size, code):
+        """The (cell_h, width) uint8 cell of glyph `code` at font_size."""
+        off, cw, ch, _ = (int(v) for v in self.records[self.size_index(font_size), code])
+        return self.blob[off:off + cw * ch].reshape(ch, cw)
+
+    def on(self, device):
+        """(blob, records) as tensors on the device; copied once per device and kept."""
+        key = str(torch.device(device))
+        t = self._device.get(key)
+        if t is None:
+            t = self._device[key] = (torch.from_numpy(self.blob).to(device), torch.from_numpy(self.records).to(device))
+        return t
+
+
+def caption_strings(ids, kept, table=None, box_points=None, box_radar=None, rate_scale=0.0):
+    """The caption of every kept row, on the host: (strings, bits) with strings[b][r] the caption of row r < kept[b] of image b
+    and bits the flag bits.  ids (B, cap) int32 track ids or None; kept (B) integers, clamped into [0, cap] with FLAG_BOX_COUNT;
+    table (B, T) `data.TRACK_DTYPE` or None (needs ids); box_points (B, cap) int32 and box_radar (B, cap, 2, 5) float32, the
+    radar readout, both or neither; at least one of ids and the readout.  Up to three fields joined by one space:
+      '#<id>'      with ids, for ids[b][r] > 0;
+      the range    '{:.1f}'.format(rng) + 'm'.  With a table: the lowest slot s with table[b][s].id == ids[b][r], id != 0 and
+                   row == r; drawn when its range_age >= 0, rng = x[4], the filtered range (also while the radar coasts).
+                   Without a table: box_points[b][r] > 0 and rng = box_radar[b][r][1][0], the lower median.  Valid when rng is
+                   not NaN, its sign bit is clear and `fixed_tenths` gives k <= 99999; otherwise left out, with FLAG_CAPTION;
+      the speed    '{:+.1f}'.format(rate) + 'm/s', only with a table, a drawn range and rate_scale > 0: rate = v[4] *
+                   rate_scale, one float32 multiply (rate_scale is the caller's frame rate: the tracker's rates are per call).
+                   Valid when the rate is finite and k <= 9999; otherwise left out, with FLAG_CAPTION.
+    A row without a field has the empty caption.  The longest caption is '#2147483647 9999.9m -999.9m/s', 29 characters."""
+    fn = "caption_strings"
+    if (box_points is None) != (box_radar is None):
+        raise RuntimeError(f"{fn}: box_points and box_radar come together or not at all")
+    if ids is None and box_points is None:
+        raise RuntimeError(f"{fn}: needs track ids or the radar readout")
+    if table is not None and ids is None:
+        raise RuntimeError(f"{fn}: a track table needs the track ids")
+    kept = np.asarray(kept).astype(np.int64).reshape(-1)
+    B = len(kept)
+    ids = None if ids is None else np.asarray(ids).reshape(B, -1)
+    cap = ids.shape[1] if ids is not None else np.asarray(box_points).reshape(B, -1).shape[1]
+    if box_points is not None:
+        box_points = np.asarray(box_points).reshape(B, cap)
+        box_radar = np.asarray(box_radar, np.float32).reshape(B, cap, 2, 5)
+    if table is not None:
+        table = np.asarray(table).reshape(B, -1)
+    scale = np.float32(rate_scale)
+    if table is not None:                     # the range and the rate of every slot; the rate is one float32 multiply
+        rng_of, age_of = np.ascontiguousarray(table["x"][..., 4], np.float32), table["range_age"].tolist()
+        with np.errstate(invalid="ignore", over="ignore"):
+            rate_of = np.ascontiguousarray(table["v"][..., 4], np.float32) * scale
+        rate_ok = (np.isfinite(rate_of) & (fixed_tenths(rate_of)[0] <= 9999)).tolist()
+        rate_of, slot_id, slot_row = rate_of.tolist(), table["id"].tolist(), table["row"].tolist()
+    else:
+        rng_of = box_radar[:, :, 1, 0] if box_points is not None else np.zeros((B, 0), np.float32)
+        have = None if box_points is None else (box_points > 0).tolist()
+    k, neg = fixed_tenths(np.ascontiguousarray(rng_of, np.float32))
+    rng_ok, rng_of = (~np.isnan(rng_of) & ~neg & (k <= 99999)).tolist(), rng_of.tolist()
+    id_of = None if ids is None else ids.tolist()
+    strings, bits = [], 0
+    for b in range(B):
+        n = int(min(max(kept[b], 0), cap))
+        if n != kept[b]:
+            bits |= FLAG_BOX_COUNT
+        slot_of = {}
+        if table is not None:                 # the lowest slot that names a row and carries that row's id
+            for s in range(table.shape[1] - 1, -1, -1):
+                r = slot_row[b][s]
+                if slot_id[b][s] != 0 and 0 <= r < n and id_of[b][r] == slot_id[b][s]:
+                    slot_of[r] = s
+        out = []
+        for r in range(n):
+            fields, at = [], None             # at: where this row's range stands, if it has one
+            if id_of is not None and id_of[b][r] > 0:
+                fields.append(f"#{id_of[b][r]}")
+            if table is not None:
+                s = slot_of.get(r)
+                if s is not None and age_of[b][s] >= 0:
+                    at = s
+            elif have is not None and have[b][r]:
+                at = r
+            if at is not None and not rng_ok[b][at]:
+                bits |= FLAG_CAPTION
+            elif at is not None:
+                fields.append("{:.1f}".format(rng_of[b][at]) + "m")
+                if table is not None and scale > 0:
+                    if rate_ok[b][at]:
+                        fields.append("{:+.1f}".format(rate_of[b][at]) + "m/s")
+                    else:
+                        bits |= FLAG_CAPTION
+            out.append(" ".join(fields))
+        strings.append(out)
+    return strings, bits
+
+
+def caption_records(strings):
+    """Host captions -> the (n, 12) int32 records of csrc/captions.hip: words 0..7 the 32 glyph codes as bytes (code i is byte
+    i, little-endian), word 8 the count, words 9..11 zero.  strings: a list of strings, or of per-image lists of them (taken in
+    order); every character from CAPTION_ALPHABET, at most 32 of them."""
+    flat = []
+    for s in strings:
+        flat += [s] if isinstance(s, str) else list(s)
+    for s in flat:
+        if len(s) > CAPTION_MAX or not set(s) <= set(CAPTION_ALPHABET):
+            raise RuntimeError(f"caption_records: {s!r} has more than {CAPTION_MAX} characters or one outside {CAPTION_ALPHABET!r}")
+    code = bytes(max(CAPTION_ALPHABET.find(chr(c)), 0) for c in range(256))
+    packed = b"".join(s.encode("ascii").translate(code).ljust(CAPTION_MAX, b"\0") for s in flat)
+    rec = np.zeros((len(flat), CAPTION_WORDS), np.int32)
+    rec.view(np.uint8).reshape(len(flat), 4 * CAPTION_WORDS)[:, :CAPTION_MAX] = np.frombuffer(packed, np.uint8).reshape(len(flat), CAPTION_MAX)
+    rec[:, 8] = [len(s) for s in flat]
+    return rec
+
+
+def caption_decode(records):
+    """(n, 12) int32 records -> the list of their strings, as the draw kernel reads them: a count outside [0, 32] is clamped, a
+    code above 17 reads as 17 (the space)."""
+    rec = np.ascontiguousarray(np.asarray(records))
+    if rec.dtype != np.int32 or rec.ndim != 2 or rec.shape[1] != CAPTION_WORDS:
+        raise RuntimeError(f"caption_decode: expected int32 records (n, {CAPTION_WORDS}), got {rec.dtype} {rec.shape}")
+    glyph = bytes(ord(CAPTION_ALPHABET[min(c, CAPTION_GLYPHS - 1)]) for c in range(256))
+    text, step = rec.tobytes().translate(glyph).decode("ascii"), 4 * CAPTION_WORDS
+    return [text[i * step:i * step + n] for i, n in enumerate(np.clip(rec[:, 8], 0, CAPTION_MAX).tolist())]
+
+
+def _caption_setup(atlas, font_size, ih, fn):
+    if not isinstance(atlas, GlyphAtlas):
+        raise RuntimeError(f"{fn}: the atlas must be a render.GlyphAtlas, got {type(atlas).__name__}")
+    font_size = label_font_size(ih) if font_size is None else int(font_size)
+    if font_size < 0:
+        raise RuntimeError(f"{fn}: font_size must not be negative, got {font_size}")
+    if font_size > 0:
+        atlas.size_index(font_size)
+    return font_size
+
+
+def draw_captions_host(picture, rows, strings, atlas, font_size, box_palette=None):
+    """The caption rule in numpy, for ONE image: picture (ih, iw, 3) uint8, finished (outlines and labels are on it), rows
+    (n, 5) int32 = left, top, right, bottom, class as `box_rows` gives them, strings the n captions (`caption_strings`).
+    Captions are a pass of their own over the finished picture; the rows are drawn in order, rows past MAX_BOXES are ignored.
+    Row i with a caption of n > 0 glyphs at this font size, W the sum of its cell widths and ch the cell height: (ox, oy) =
+    (left, bottom + 1) if bottom + ch <= ih - 1, else (left, bottom - ch), left and bottom clamped to +-2^29; it paints the
+    rectangle [ox, ox + W - 1] x [oy, oy + ch - 1], clipped to the image, in palette[class] (the class clamped into the
+    palette; default `det_palette(4)`), then its cells left to right in black: v = DIV255(v * (255 - m)).  Text never leaves
+    its own tag, so a pixel's final value follows from the HIGHEST row whose tag covers it; pixels no tag covers keep their
+    bytes.  font_size None: `label_font_size(ih)`; 0 draws nothing.  Returns the new picture.  This is the statement the
+    kernels of csrc/captions.hip are tested against."""
+    fn = "draw_captions_host"
+    pic, rows = np.asarray(picture), np.asarray(rows)
+    if pic.dtype != np.uint8 or pic.ndim != 3 or pic.shape[2] != 3:
+        raise RuntimeError(f"{fn}: expected a uint8 picture (ih, iw, 3), got {pic.dtype} {pic.shape}")
+    if rows.dtype != np.int32 or rows.ndim != 2 or rows.shape[1] != 5 or len(strings) != len(rows):
+        raise RuntimeError(f"{fn}: expected int32 rows (n, 5) and n captions, got {rows.dtype} {rows.shape} and {len(strings)}")
+    ih, iw = pic.shape[:2]
+    font_size = _caption_setup(atlas, font_size, ih, fn)
+    pal = _palette(box_palette, det_palette(4), fn)
+    pal = pal.cpu().numpy() if torch.is_tensor(pal) else pal
+    out = pic.copy()
+    if font_size == 0:
+        return out
+    limit = 1 << 29
+    for (left, _, _, bottom, cls), text in zip(rows[:MAX_BOXES].tolist(), list(strings)[:MAX_BOXES]):
+        if not text:
+            continue
+        cells = [atlas.cell(font_size, CAPTION_ALPHABET.index(ch)) for ch in text]
+        tag = np.concatenate(cells, axis=1).astype(np.int64)
+        ch, W = tag.shape
+        left, bottom = min(max(left, -limit), limit), min(max(bottom, -limit), limit)
+        ox, oy = (left, bottom + 1) if bottom + ch <= ih - 1 else (left, bottom - ch)
+        x0, y0, x1, y1 = max(ox, 0), max(oy, 0), min(ox + W, iw), min(oy + ch, ih)
+        if x0 < x1 and y0 < y1:
+            colour = pal[min(max(cls, 0), len(pal) - 1)].astype(np.int64)
+            m = tag[y0 - oy:y1 - oy, x0 - ox:x1 - ox, None]
+            out[y0:y1, x0:x1] = _div255(colour * (255 - m)).astype(np.uint8)
+    return out
+
+
+def draw_captions(picture, results, captions, atlas, font_size=None, box_palette=None, geom=None, flag=None):
+    """The captions on the device, in place on the finished (B, ih, iw, 3) uint8 DEVICE picture (vrnet_render_captions_u8):
+    results as `draw_labels` takes them -- the list `non_max_suppression` returns, or a device pair / triple (rows (N, 5),
+    offsets (B + 1)[, label_idx]) of int32 tensors; captions: the (N, 12) int32 device records `hip.caption_text` wrote, or
+    host strings (`caption_records` packs them, one non-blocking copy).  font_size: default `label_font_size(ih)`, 0 draws
+    nothing; box_palette: default `det_palette(4)`; flag: FLAG_BOX_ROWS for more than 1024 rows in an image.  With geom, the
+    device table of `data.frame_geometry`, the picture is (B, ihm, iwm, 3) padded slots, results are device tensors and
+    font_size is the (B) int32 device table `GlyphAtlas.size_table` gives, -1 for an image without captions
+    (vrnet_render_captions_ragged_u8).  Returns the picture.  No host synchronisation."""
+    from . import hip
+    fn = "draw_captions"
+    if not (torch.is_tensor(picture) and picture.is_cuda and picture.dtype == torch.uint8 and picture.dim() == 4 and
+            picture.shape[-1] == 3 and picture.is_contiguous()):
+        raise RuntimeError(f"{fn}: expected a contiguous uint8 picture (B, ih, iw, 3) on a GPU")
+    B, ih, iw = picture.shape[:3]
+    if geom is None:
+        font_size = _caption_setup(atlas, font_size, ih, fn)
+        size = atlas.size_index(font_size) if font_size > 0 else None
+    else:
+        if not isinstance(atlas, GlyphAtlas):
+            raise RuntimeError(f"{fn}: the atlas must be a render.GlyphAtlas, got {type(atlas).__name__}")
+        if not torch.is_tensor(font_size):
+            raise RuntimeError(f"{fn}: with a geometry table font_size is the (B) int32 device table of GlyphAtlas.size_table")
+        size = font_size
+    bpal = _palette(box_palette, det_palette(4), fn)
+    send, dev = _results(fn, results, B, ih, iw, host=geom is None), picture.device
+    with torch.cuda.device(dev):
+        rows, offsets, _ = send(dev, flag)
+        if not torch.is_tensor(captions):
+            captions = torch.from_numpy(caption_records(captions)).pin_memory().to(dev, non_blocking=True)
+        if size is not None:
+            blob, records = atlas.on(dev)
+            hip.render_captions(picture, rows, offsets, _palette_on(bpal, dev), captions, blob, records, size, flag=flag, geom=geom)
     return picture
 
 

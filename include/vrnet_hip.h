@@ -1459,6 +1459,67 @@ int vrnet_render_labels_ragged_u8(unsigned char* picture, const vrnet_frame_geom
                                   const unsigned char* blob, long blob_bytes, const int* records, int num_classes, int n_sizes,
                                   int* flag, void* stream);
 
+/* ---- track ids, radar range and closing speed under the rendered detections (csrc/captions.hip) ------------------------
+ * Added within ABI 11: new symbols only, no existing signature, layout or kernel behaviour changed; hip.py binds every
+ * declared symbol at import.
+ * A second tag UNDER every box with what the label atlas cannot hold: '#<track id> <range>m <closing speed>m/s', e.g.
+ * '#17 42.5m -1.2m/s', composed on the device from the track table (vrnet_track_update_f32) and the radar readout
+ * (vrnet_box_radar_f32).  The reference has nothing like it; the rule is this project's definition (host statements:
+ * render.caption_strings, render.fixed_tenths, render.draw_captions_host) and the kernels equal it byte for byte.
+ * ALPHABET.  "0123456789.-+#m/s ", 18 glyphs; a glyph code is the index into it.
+ * CAPTION RECORD.  12 int32: words 0..7 hold 32 codes as bytes (code i is byte i), word 8 their count n, words 9..11 are 0.
+ * GLYPH ATLAS (render.GlyphAtlas).  blob: the uint8 cells, row-major, back to back, below 2 GiB; records (n_sizes, 18, 4)
+ *   int32 per font size and code: blob offset, cell width, cell height, 0.  A cell is Pillow's mask of the single glyph in
+ *   the union of its advance box and the mask's extent; all cells of a size share one height.  A caption is cells side by
+ *   side with integer widths, not Pillow's layout of the whole string (no kerning, no fractional advances).  The kernels do
+ *   not trust the tables: n is clamped to 32, a code to 17, a cell side to 2^14, the tag height is that of code 0, and a
+ *   record whose cell leaves the blob draws as an empty cell.
+ * vrnet_caption_text_f32: ids (B, cap) int32 / kept (B) / offsets (B + 1) as vrnet_track_update_f32 and
+ *   vrnet_detect_finish[_ragged]_f32 write them, table (B, max_tracks) vrnet_track, box_points (B, cap) / box_radar
+ *   (B, cap, 2, 5) of vrnet_box_radar_f32 -> captions_out[offsets[b] + r] for the kept rows r < kept[b] (n_out: the records
+ *   of captions_out; nothing else is written).  ids, table and the readout pair are each optional (NULL); table needs ids;
+ *   at least one of ids and the readout.  cap <= 1024, max_tracks <= 256.  Up to three fields, joined by one space:
+ *     '#<id>'    with ids, for ids[b][r] > 0, in decimal;
+ *     the range  '{:.1f}'.format(rng) + 'm'.  With a table: the lowest slot s of stream b with id == ids[b][r], id != 0 and
+ *                row == r; drawn when its range_age >= 0, rng = x[4], the filtered range (also while the radar coasts).
+ *                Without a table: box_points[b][r] > 0 and rng = box_radar[b][r][1][0], the lower median.  Valid when rng is
+ *                not NaN, its sign bit is clear and k <= 99999; otherwise left out, and bit 65536 of *flag (VR_FLAG_CAPTION);
+ *     the speed  '{:+.1f}'.format(rate) + 'm/s', only with a table, a drawn range and rate_scale > 0 (in [0, 1e6]): rate =
+ *                v[4] * rate_scale, one fp32 multiply -- rate_scale is the caller's frame rate, the tracker's rates being
+ *                per call -- the sign from the sign bit.  Valid when finite and k <= 9999; otherwise left out, bit 65536.
+ *   k: the exact value of the fp32 times 10, rounded to nearest with ties to even on the exact binary value, in integer
+ *   arithmetic on the bits (what Python's format prints: 0.25 -> 0.2, 0.75 -> 0.8, -0.04 -> -0.0); decimal digits by integer
+ *   division.  The longest caption, '#2147483647 9999.9m -999.9m/s', has 29 codes; a row without a field has n = 0.
+ *   kept[b] outside [0, cap] is clamped and sets bit 512 (VR_FLAG_BOX_COUNT).  flag may be NULL.
+ *   One workgroup of 256 per image: thread s publishes row -> s of its slot into an LDS array with an integer atomic
+ *   minimum, so a corrupt table still gives one answer; behind a barrier the threads stride over the rows and format.
+ * vrnet_render_captions_u8: in place on the finished (B, ih, iw, 3) picture (outlines, labels), with the boxes, box_offsets
+ *   and box_palette vrnet_render_u8 took and captions (n_rows, 12).  The rows of an image are drawn in order.  Row i with
+ *   n > 0 codes, W the sum of its cell widths at font size size_index and ch the cell height: (ox, oy) = (left, bottom + 1)
+ *   if bottom + ch <= ih - 1, else (left, bottom - ch), left and bottom clamped to +-2^29; it paints [ox, ox + W - 1] x
+ *   [oy, oy + ch - 1], clipped, in its class colour (the class clamped into the palette), then its cells left to right in
+ *   black: v = DIV255(v * (255 - m)), as vrnet_render_labels_u8 blends.  Text never leaves its own tag, so a pixel's final
+ *   value follows from the HIGHEST row whose tag covers it; pixels no tag covers keep their bytes.
+ *   Grid (pixel blocks, row, image) over each row's clipped tag: work follows the caption area.  A workgroup stages the tag
+ *   rectangles of the image's rows in LDS (16 KiB) and the pen positions of its own row; a thread leaves a pixel a higher
+ *   row's tag covers, otherwise it writes the pixel once.  No racing stores, no floating point, no atomics on pixels.  At
+ *   most 1024 rows per image; later rows are ignored and set bit 4, as in vrnet_render_u8.
+ * vrnet_render_captions_ragged_u8: the same on padded (B, ihm, iwm, 3) slots with ih, iw of image b from geom[b] and its
+ *   font size from size_index[b] (int32, B entries; -1: no captions for that image; >= n_sizes: none, and bit 256).
+ *   Nothing outside an image is written.
+ * All three: no allocation, no memset, no host synchronisation; one kernel each, capturable in a graph. */
+int vrnet_caption_text_f32(const int* ids, const int* kept, const int* offsets, int B, int cap, const vrnet_track* table,
+                           int max_tracks, const int* box_points, const float* box_radar, float rate_scale, int* captions_out,
+                           int n_out, int* flag, void* stream);
+int vrnet_render_captions_u8(unsigned char* picture, int B, int ih, int iw, const int* boxes, const int* box_offsets, int n_rows,
+                             const unsigned char* box_palette, int n_box_colors, const int* captions, const unsigned char* blob,
+                             long blob_bytes, const int* records, int n_sizes, int size_index, int* flag, void* stream);
+int vrnet_render_captions_ragged_u8(unsigned char* picture, const vrnet_frame_geom* geom, const int* size_index, int B, int ihm,
+                                    int iwm, const int* boxes, const int* box_offsets, int n_rows,
+                                    const unsigned char* box_palette, int n_box_colors, const int* captions,
+                                    const unsigned char* blob, long blob_bytes, const int* records, int n_sizes, int* flag,
+                                    void* stream);
+
 /* ---- detection crops (csrc/crops.hip) -----------------------------------------------------------------------------------
  * Added within ABI 11: a new symbol and one new record layout (vrnet_crop_rec) only, no existing signature, layout or kernel
  * behaviour changed; hip.py binds every declared symbol at import.
