@@ -86,6 +86,20 @@ typedef struct vrnet_frame_geom {
 #define VR_FLAG_ACE 16384                       /* ace.hip: a degenerate image, returned unchanged */
 #define VR_FLAG_TRACK_FULL 32768                /* track.hip: a valid row found no free slot in the track table, id 0 */
 #define VR_FLAG_CAPTION 65536                   /* captions.hip: a range or a speed that cannot be drawn, left out of its caption */
+#define VR_FLAG_REGIONS 131072                  /* regions.hip: more regions than the table holds; labels and head are complete */
+extern "C" {
+/* include/vrnet_hip.h: one record per region of vrnet_seg_regions_u8. */
+typedef struct vrnet_region {
+  int cls, area;                                /* the class of the region's pixels and their number */
+  int left, top, right, bottom;                 /* the bounding box, right and bottom exclusive */
+  int first;                                    /* y iw + x of the first pixel in raster order */
+  int det;                                      /* the linked row of the image, -1: none */
+  long long sum_x, sum_y;                       /* exact sums of the pixel coordinates: the centroid is sum / area */
+} vrnet_region;
+}
+static_assert(sizeof(vrnet_region) == 48 && offsetof(vrnet_region, first) == 24 && offsetof(vrnet_region, det) == 28 &&
+                  offsetof(vrnet_region, sum_x) == 32 && offsetof(vrnet_region, sum_y) == 40,
+              "vrnet_region is 48 bytes: decode.REGION_DTYPE mirrors it");
 extern "C" {
 /* include/vrnet_hip.h: one record per draw row of vrnet_crop_boxes_u8. */
 typedef struct vrnet_crop_rec {

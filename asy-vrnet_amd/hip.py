@@ -170,6 +170,8 @@ _SIGS = {
     "vrnet_box_radar_workspace": ([I, I], L),
     "vrnet_box_radar_f32": ([P, I, P, I, P, P, I, F, F, P, P, P, P, L, P], I),
     "vrnet_track_update_f32": ([P, P, I, I, P, I, P, P, P, P, F, I, F, F, F, F, P, P], I),
+    "vrnet_seg_regions_workspace_bytes": ([I, I, I], L),
+    "vrnet_seg_regions_u8": ([P, I, I, I, P, I, I, P, P, I, I, I, I, I, I, P, I, P, P, P, P, P, P, L, P], I),
     "vrnet_mosaic_radar_points_workspace": ([I, I, I], L),
     "vrnet_mosaic_radar_points_f32": ([P, I, I, P, P, I, I, I, I, I, I, F, P, P, P, L, P], I),
     "vrnet_label_index_f32": ([P, P, P, I, I, I, P, I, P, P], I),
@@ -2023,6 +2025,55 @@ def crop_boxes(frames, rows, offsets, arena, table, summary, geom=None, flag=Non
                   (summary, (2,), torch.int32), (flag, (1,), torch.int32)))
     _check(_lib.vrnet_crop_boxes_u8(ptr(frames), B, ihm, iwm, None if geom is None else _geom(geom, B, fn), ptr(rows), ptr(offsets),
                                     n_cap, ptr(arena), arena.shape[0] // 3, ptr(table), ptr(summary), ptr(flag), stream()), fn)
+
+
+# ---- connected regions of the class map (csrc/regions.hip) ---------------------------------------------------------------------
+FLAG_REGIONS = 131072    # VR_FLAG_REGIONS of csrc/common.h: more regions than the table holds; labels and head are complete
+REGION_WORDS = 12        # int32 per vrnet_region: cls, area, left, top, right, bottom, first, det, then sum_x and sum_y as int64
+REGION_HEAD = 4          # int32 per image: regions, records in the table, pixels in kept regions, pixels dropped by min_area
+
+
+def seg_regions_workspace_bytes(B, ihm, iwm):
+    n = _lib.vrnet_seg_regions_workspace_bytes(B, ihm, iwm)
+    if n < 0:
+        raise RuntimeError(f"seg_regions: bad shape (B {B}, slots of {ihm} x {iwm}; 1..65535 images, sides up to 2^17, below 2^31 "
+                           "pixels each)")
+    return n
+
+
+def seg_regions(class_map, rows, offsets, labels, table, head, box_regions, ws, connectivity=8, background=0, min_area=1,
+                det_to_seg=None, geom=None, flag=None, fn="seg_regions"):
+    """The connected regions of the class map by the rule of `decode.seg_regions_host` (vrnet_seg_regions_u8): class_map
+    (B, ihm, iwm) uint8; rows (n_cap >= 1, 5) / offsets (B + 1) int32 as `detect_finish[_ragged]` leave them -> labels
+    (B, ihm, iwm) int32, table (B, max_regions, 12) int32 -- the vrnet_region records of `decode.REGION_DTYPE` as words,
+    max_regions in [1, 4096] --, head (B, 4) int32 and box_regions (B, cap) int32, every element written; ws: uint8, at least
+    seg_regions_workspace_bytes(B, ihm, iwm) bytes; det_to_seg: (n) int32 on the device, one seg class per detection class, or
+    None; geom (`_table_call`): the (B, GEOM_BYTES) table of a ragged batch, None: every image fills its slot; flag (1) int32
+    or None: FLAG_REGIONS for more regions than max_regions, FLAG_GEOMETRY for a bad record (an image without regions).  Seven
+    launches, no host synchronisation."""
+    table_call = _table_call(fn, geom)
+    if class_map is None or class_map.dim() != 3:
+        raise RuntimeError(f"{fn}: expected a contiguous uint8 class map of shape (B, ihm, iwm)")
+    B, ihm, iwm = class_map.shape
+    if ihm * iwm >= 1 << 31:
+        raise RuntimeError(f"{fn}: a slot of {ihm} x {iwm} has 2^31 pixels or more")
+    if rows is None or rows.dim() != 2 or rows.shape[0] < 1 or offsets is None or labels is None or head is None or ws is None:
+        raise RuntimeError(f"{fn}: rows (n_cap >= 1, 5), offsets, labels, table, head, box_regions and the workspace are required")
+    if table is None or table.dim() != 3 or table.shape[1] < 1 or table.shape[2] != REGION_WORDS:
+        raise RuntimeError(f"{fn}: expected table ({B}, max_regions, {REGION_WORDS}) int32, the records as words")
+    if box_regions is None or box_regions.dim() != 2 or box_regions.shape[1] < 1:
+        raise RuntimeError(f"{fn}: expected box_regions ({B}, cap >= 1) int32")
+    n_cap, R, cap = rows.shape[0], table.shape[1], box_regions.shape[1]
+    n_det = 0 if det_to_seg is None else det_to_seg.numel()
+    _tensors(fn, ((class_map, (B, ihm, iwm), torch.uint8), (rows, (n_cap, 5), torch.int32), (offsets, (B + 1,), torch.int32),
+                  (labels, (B, ihm, iwm), torch.int32), (table, (B, R, REGION_WORDS), torch.int32),
+                  (head, (B, REGION_HEAD), torch.int32), (box_regions, (B, cap), torch.int32), (det_to_seg, (n_det,), torch.int32),
+                  (flag, (1,), torch.int32), (ws, (ws.numel(),), torch.uint8)))
+    _check(_lib.vrnet_seg_regions_u8(ptr(class_map), B, ihm, iwm, _geom(geom, B, fn) if table_call else None, ihm, iwm, ptr(rows),
+                                     ptr(offsets), n_cap, cap, int(connectivity), int(background), int(min_area), R,
+                                     ptr(det_to_seg), n_det, ptr(labels), ptr(table), ptr(head), ptr(box_regions), ptr(flag),
+                                     ptr(ws), ws.numel(), stream()), fn)
+    return labels, table, head, box_regions
 
 
 # ---- dark-channel dehazing (csrc/dehaze.hip) ---------------------------------------------------------------------------------

@@ -25,7 +25,9 @@ that (behind the crops or the finish node without box_radar) and in front of dec
 stream whose track table lives on the device across runs, and FLAG_TRACK_FULL says that a valid row found no free slot in it
 and got track id 0.  A pipeline built with captions= adds hip.caption_text behind that (behind hip.box_radar without a tracker) and
 hip.render_captions behind the label launches (behind the render node without labels): '#<track id> <range>m <speed>m/s'
-under every rendered box; FLAG_CAPTION says that a range or a speed could not be drawn and was left out.
+under every rendered box; FLAG_CAPTION says that a range or a speed could not be drawn and was left out.  A pipeline built
+with regions= adds hip.seg_regions directly behind decode.seg_predict and in front of the render node: the connected regions
+of the class map, linked both ways with the kept rows; FLAG_REGIONS says that an image had more regions than the table holds.
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
@@ -48,6 +50,7 @@ FLAG_DEHAZE = rendering.FLAG_DEHAZE              # 8192, csrc/dehaze.hip (a pipe
 FLAG_ACE = rendering.FLAG_ACE                    # 16384, csrc/ace.hip (a pipeline built with ace): a degenerate image, unchanged
 FLAG_TRACK_FULL = data.FLAG_TRACK_FULL           # 32768, VR_FLAG_TRACK_FULL of csrc/common.h (a pipeline built with track): the table was full
 FLAG_CAPTION = rendering.FLAG_CAPTION            # 65536, VR_FLAG_CAPTION of csrc/common.h (a pipeline built with captions): a field left out
+FLAG_REGIONS = 131072                            # VR_FLAG_REGIONS of csrc/common.h (a pipeline built with regions): more regions than the table
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -291,14 +294,21 @@ class FrameResult:
     records as words, and track_head (B, 4) int32 (ids handed out, live tracks, calls, births of this call) -- the state after
     this run, which the next run updates in place; `tracks` brings them to the host.
     From a pipeline built with captions (None otherwise): captions (B * cap, 12) int32, the caption records of the kept rows,
-    image b's from row `kept[:b].sum()` on (`render.caption_decode`); `caption_strings` brings them to the host."""
+    image b's from row `kept[:b].sum()` on (`render.caption_decode`); `caption_strings` brings them to the host.
+    From a pipeline built with regions (None otherwise): region_labels (B, ih, iw) int32, the id of the connected region of
+    every pixel of the class map (0: none; padded like class_map from a ragged pipeline), region_table (B, max_regions, 12)
+    int32, the records of `decode.REGION_DTYPE` as words, region_head (B, 4) int32 (regions, records in the table, pixels in
+    regions, pixels dropped by min_area) and box_regions (B, cap) int32, the region linked to each kept row (0: none, and from
+    row kept[b] on) -- `decode.seg_regions_host` is the rule; `regions` brings them to the host."""
     __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
                  "heat_picture", "heat_range", "crops", "dehazed", "enhanced", "box_points", "box_radar", "track_ids",
-                 "track_table", "track_head", "captions")
+                 "track_table", "track_head", "captions", "region_labels", "region_table", "region_head", "box_regions")
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
                  heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None, box_points=None, box_radar=None,
-                 track_ids=None, track_table=None, track_head=None, captions=None):
+                 track_ids=None, track_table=None, track_head=None, captions=None, region_labels=None, region_table=None,
+                 region_head=None, box_regions=None):
+        self.region_labels, self.region_table, self.region_head, self.box_regions = region_labels, region_table, region_head, box_regions
         self.track_ids, self.track_table, self.track_head, self.captions = track_ids, track_table, track_head, captions
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
@@ -344,6 +354,27 @@ class FrameResult:
         ids = packed[B * T * 16:B * T * 16 + B * cap].reshape(B, cap)
         kept = packed[B * T * 16 + B * cap:]
         return [(table[b][table[b]["id"] != 0].copy(), ids[b, :kept[b]].copy()) for b in range(B)]
+
+    def regions(self):
+        """The regions of a pipeline built with regions: per image a triple (the records as a `decode.REGION_DTYPE` array cut
+        to their count, the (ih_b, iw_b) int32 label map cut to the image, the region ids of the kept rows as an (N_b) int32
+        array in the order of `detections()`).  Two device-to-host copies: table, header, links and kept packed into one
+        tensor, which waits for the frame, and the label maps."""
+        if self.region_table is None or self.region_labels is None:
+            raise RuntimeError("FrameResult.regions: the pipeline was not built with regions")
+        from . import decode
+        B, R = self.region_table.shape[:2]
+        cap = self.box_regions.shape[1]
+        packed = torch.cat([self.region_table.reshape(-1), self.region_head.reshape(-1), self.box_regions.reshape(-1),
+                            self.kept]).cpu().numpy()
+        table = packed[:B * R * 12].view(decode.REGION_DTYPE).reshape(B, R)
+        head = packed[B * R * 12:B * R * 12 + 4 * B].reshape(B, 4)
+        links = packed[B * R * 12 + 4 * B:B * R * 12 + 4 * B + B * cap].reshape(B, cap)
+        kept = packed[B * R * 12 + 4 * B + B * cap:]
+        labels = self.region_labels.cpu().numpy()
+        sizes = [labels.shape[1:]] * B if self.sizes is None else [(int(h), int(w)) for h, w in self.sizes]
+        return [(table[b, :head[b, 1]].copy(), labels[b, :sizes[b][0], :sizes[b][1]].copy(), links[b, :kept[b]].copy())
+                for b in range(B)]
 
     def caption_strings(self):
         """The captions of a pipeline built with captions, as drawn: per image the list of its kept rows' strings, in the order
@@ -462,16 +493,29 @@ class FramePipeline:
     size from 1 to label_font_size(ihm), or those sizes= names, and a frame whose size was not built raises in the host
     validation of `run`, before anything is enqueued.  Two launches: hip.caption_text behind hip.track_update (behind
     hip.box_radar without a tracker) and hip.render_captions behind the label launches (behind the render node without
-    labels); the records, `FrameResult.captions`, are allocated before the capture.  FLAG_CAPTION joins the bits of `flag`."""
+    labels); the records, `FrameResult.captions`, are allocated before the capture.  FLAG_CAPTION joins the bits of `flag`.
+
+    regions: None (the default: exactly the calls issued without it), True or a dict of `decode.check_region_params`
+    (connectivity, background, min_area, max_regions, det_to_seg -- one seg class per detection class of the model) -- the
+    connected regions of the class map (`decode.seg_regions_host`, csrc/regions.hip): how many separate vessels or piers the
+    class map holds, each one's class, area, bounding box and exact coordinate sums, and which kept row belongs to which of
+    them, as `FrameResult.region_labels`, `region_table`, `region_head` and `box_regions`.  The seven launches of
+    hip.seg_regions sit directly behind the seg node and in front of the render node and read the class map and the draw rows
+    of the result.  Outputs and workspace (8 bytes per pixel of the batch) are allocated before the capture.  Fixed-size and
+    ragged pipelines alike, with and without letterbox_image.  FLAG_REGIONS joins the bits of `flag`."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
                  font=None, label_sizes=None, crops=None, dehaze=None, ace=None, box_radar=None, box_shrink=1.0, track=None,
-                 captions=None):
+                 captions=None, regions=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
+        self.regions = None
+        if regions is not None and regions is not False:
+            from .decode import check_region_params
+            self.regions = check_region_params(regions, "FramePipeline", num_classes=int(model.num_classes))
         self.track = None if track is None or track is False else data.check_track_params(track, "FramePipeline")
         self.crop_capacity = crop_capacity(crops, self.batch, self.frame_shape)
         self.dehaze = dehaze_config(dehaze)
@@ -636,6 +680,15 @@ class FramePipeline:
         self._captions = None
         if self.captions is not None:         # before the capture: one record per draw row
             self._captions = torch.zeros((B * cap, hip.CAPTION_WORDS), **i32)
+        self._region_labels = self._region_table = self._region_head = self._box_regions = None
+        if self.regions is not None:          # before the capture: the four outputs, the gate and the workspace
+            ih, iw = self.frame_shape
+            self._region_labels = torch.zeros((B, ih, iw), **i32)
+            self._region_table = torch.zeros((B, self.regions["max_regions"], hip.REGION_WORDS), **i32)
+            self._region_head, self._box_regions = torch.zeros((B, hip.REGION_HEAD), **i32), torch.zeros((B, cap), **i32)
+            gate = self.regions["det_to_seg"]
+            self._region_gate = None if gate is None else torch.tensor(gate, **i32)
+            self._region_ws = torch.empty(hip.seg_regions_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
 
     def _chain(self):
         """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
@@ -691,6 +744,10 @@ class FramePipeline:
             class_map = torch.empty((B,) + F, dtype=torch.uint8, device=dev)
             ws = torch.empty(hip.seg_predict_workspace_bytes(B, seg.shape[1], H, W), dtype=torch.uint8, device=dev)
             hip.seg_predict(seg.contiguous().float(), 0, 0, H, W, class_map, ws)
+        if self.regions is not None:          # directly behind the seg node, in front of the render node
+            hip.seg_regions(class_map, self._draw_rows, self._offsets, self._region_labels, self._region_table, self._region_head,
+                            self._box_regions, self._region_ws, self.regions["connectivity"], self.regions["background"],
+                            self.regions["min_area"], det_to_seg=self._region_gate, geom=geom, flag=self.flag)
         rendered = seg_counts = None
         if self.render:
             boxes = (self._draw_rows, self._offsets)
@@ -708,7 +765,8 @@ class FramePipeline:
         result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops,
                              dehazed=dehazed, enhanced=frames if self.ace is not None else None, box_points=self._box_points,
                              box_radar=self._box_radar, track_ids=self._track_ids, track_table=self._track_table,
-                             track_head=self._track_head, captions=self._captions)
+                             track_head=self._track_head, captions=self._captions, region_labels=self._region_labels,
+                             region_table=self._region_table, region_head=self._region_head, box_regions=self._box_regions)
         if self.heatmap:
             result.heat_picture, result.heat_mask, result.heat_range = rendering.heatmap(
                 frames, det, (H, W), alpha=self.heat_alpha, geom=geom, flag=self.flag, **self._heat_window)
@@ -853,8 +911,9 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     with ace the enhanced frame as <stem>_ace.png, from one built with box_radar the radar readout of the picture's
     detections as <stem>_radar.txt (`radar_text`).  Two pictures that would share one output name (names that differ only in
     their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on, or `a_dehaze.jpg` with dehazing on, or `a_ace.jpg`
-    with ACE on, or `a_radar.jpg` with the readout on, or `a_tracks.jpg` with tracking on): with dir_save_path that raises
-    before anything runs.  A pipeline built with track must have batch 1 -- the folder then is ONE sequence in its sorted
+    with ACE on, or `a_radar.jpg` with the readout on, or `a_tracks.jpg` with tracking on, or `a_regions.jpg` with regions
+    on): with dir_save_path that raises before anything runs.  From a pipeline built with regions the records of the picture's
+    connected regions are saved as <stem>_regions.txt (`decode.region_text`).  A pipeline built with track must have batch 1 -- the folder then is ONE sequence in its sorted
     order, fed to stream 0 of the pipeline as it stands (call `reset_tracks` first for a fresh sequence), and the live tracks
     after every picture are saved as <stem>_tracks.txt (`data.track_text`); with batch > 1 neighbouring files would land in
     different streams, which raises before anything runs."""
@@ -874,7 +933,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
                 ((stem + "_dehaze",) if getattr(pipeline, "dehaze", None) is not None else ()) + \
                 ((stem + "_ace",) if getattr(pipeline, "ace", None) is not None else ()) + \
                 ((stem + "_radar",) if getattr(pipeline, "box_radar", False) else ()) + \
-                ((stem + "_tracks",) if tracking else ())
+                ((stem + "_tracks",) if tracking else ()) + \
+                ((stem + "_regions",) if getattr(pipeline, "regions", None) is not None else ())
             for target in targets:
                 other = stems.setdefault(target, n)
                 if other != n:
@@ -903,12 +963,17 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         crops = None if crops is None else crops.images()
         readout = None if dir_save_path is None or getattr(result, "box_radar", None) is None else result.radar_readout()
         tracks = None if dir_save_path is None or not tracking else result.tracks()
+        regions = None if dir_save_path is None or getattr(result, "region_table", None) is None else result.regions()
         for b, n in enumerate(chunk):
             out.append((n, dets[b]))
             ih, iw = (int(v) for v in result.sizes[b])
             if tracks is not None:
                 with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_tracks.txt"), "w") as f:
                     f.write(data.track_text(tracks[b][0]))
+            if regions is not None:
+                from .decode import region_text
+                with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_regions.txt"), "w") as f:
+                    f.write(region_text(regions[b][0]))
             if readout is not None:
                 with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_radar.txt"), "w") as f:
                     f.write(radar_text(dets[b], readout[b]))

@@ -1556,6 +1556,62 @@ int vrnet_crop_boxes_u8(const unsigned char* frames, int B, int ihm, int iwm, co
                         const int* offsets, int n_cap, unsigned char* arena, long capacity_px, vrnet_crop_rec* table,
                         int* summary, int* flag, void* stream);
 
+/* ---- connected regions of the class map (csrc/regions.hip) -----------------------------------------------------------------
+ * Added within ABI 11: two new symbols, one new record layout (vrnet_region) and one new flag bit only, no existing signature,
+ * layout or kernel behaviour changed; hip.py binds every declared symbol at import.
+ * The reference stops at the class map and the boxes; this is the join between them -- how many separate vessels or piers the
+ * class map holds, where each lies, how large it is, and which detection row belongs to which of them.  The rule is this
+ * project's definition; the host statement is decode.seg_regions_host and the kernels equal it bit for bit.  THE RULE for one
+ * image of size (ih, iw):
+ *   Pixels of class `background` are unlabelled (background = -1: every class is labelled).  A region is a maximal set of
+ *   pixels of ONE class connected under `connectivity`, 4 or 8.  A region of fewer than min_area pixels is dropped and its
+ *   pixels get label 0.  The remaining n regions get the ids 1..n in the order of their first pixel in raster order, the
+ *   smallest y iw + x.
+ *   labels: the id of every kept region at each of its pixels, ids beyond max_regions included: no capacity changes it.
+ *   table: the record of id k at table[k - 1] for k = 1..min(n, max_regions), zeros behind.  right and bottom are exclusive,
+ *   first = y iw + x of the first pixel, sum_x and sum_y the exact integer sums of the pixel coordinates.
+ *   head = (n, min(n, max_regions), the pixels in kept regions, the non-background pixels dropped by min_area).
+ *   n > max_regions sets bit 131072 of *flag (VR_FLAG_REGIONS).
+ *   The link, over the records of the table and the rows of the image: a row left, top, right, bottom is clamped to the image
+ *   (each coordinate to [0, iw] or [0, ih], as vrnet_crop_boxes_u8 clamps it) and is EMPTY with right <= left or bottom <=
+ *   top; an empty row links to nothing.  A row and a record's bounding box have the integer intersection I and union U; the
+ *   best partner is the one with the largest I / U, compared as I1 U2 against I2 U1 in 64 bits (both below 2^63 after the
+ *   clamp), I > 0 required, ties to the lowest index.  det of a record: the index of its best row within the image, or -1.
+ *   box_regions of a row: the id of its best record, or 0.  With det_to_seg (n_det entries, one seg class per detection class)
+ *   a row of class c links only with records of class det_to_seg[c] and the other records ignore it; c outside [0, n_det)
+ *   links to nothing.
+ * vrnet_seg_regions_u8: class_map (B, ihm, iwm) u8 slots with image b in the top-left corner of slot b, of size geom[b].ih x
+ *   geom[b].iw (clamped to the slot; a clamped or empty record sets bit 256 and an empty image has no region) or ih x iw with
+ *   geom == NULL (ih <= ihm, iw <= iwm); rows (n_cap, 5) int32 and offsets (B + 1) as vrnet_detect_finish[_ragged]_f32 leave
+ *   them, made monotone as vrnet_crop_boxes_u8 does; of the rows of an image the first `cap` take part.  labels (B, ihm, iwm)
+ *   int32, 0 outside the image; table (B, max_regions) vrnet_region, 8-byte aligned; head (B, 4) int32; box_regions (B, cap)
+ *   int32, 0 from the image's row count on; det_to_seg (n_det) int32 in device memory or NULL with n_det = 0; flag may be NULL.
+ *   Every element of every output is written on every call.
+ *   Seven launches (six for a slot of one tile): a 64 x 16 tile labelled in LDS by union-find with the integer atomic minimum,
+ *   one union per pair of touching runs, which also initialises everything the call accumulates into; the lock-free
+ *   atomicMin union across tile edges and corners on an int32 parent plane, whose `find` reads with relaxed agent-scope
+ *   atomic loads (the root is the smallest index of the component, so the result does not depend on the order of arrival);
+ *   the roots and the areas; the kept roots per chunk of 2048 pixels; their ranks; the labels and the statistics, gathered per
+ *   run of a wave and per tile in LDS before one integer atomic per id, tile and field; the link and the header, eight
+ *   workgroups per image.  No workgroup waits for another.  Integer atomics only: the same bytes on every run.  No
+ *   allocation, no memset node, no host synchronisation; capturable in a graph.
+ *   connectivity 4 or 8, background in [-1, 255], min_area >= 1, 1 <= max_regions <= 4096, 0 <= n_det <= 256; 0 < B < 65536,
+ *   ihm, iwm <= 2^17, ihm iwm < 2^31; 0 < n_cap, cap <= 2^20.
+ * vrnet_seg_regions_workspace_bytes: the bytes of `workspace` (-1 for a shape outside the limits): two int32 planes of
+ *   B ihm iwm and four int32 per chunk of 2048 pixels. */
+typedef struct vrnet_region {
+  int cls, area;                     /* the class of the region's pixels and their number */
+  int left, top, right, bottom;      /* the bounding box, right and bottom exclusive */
+  int first;                         /* y iw + x of the first pixel in raster order */
+  int det;                           /* the linked row of the image, -1: none */
+  long long sum_x, sum_y;            /* exact sums of the pixel coordinates: the centroid is sum / area */
+} vrnet_region;                      /* 48 bytes */
+long vrnet_seg_regions_workspace_bytes(int B, int ihm, int iwm);
+int vrnet_seg_regions_u8(const unsigned char* class_map, int B, int ihm, int iwm, const vrnet_frame_geom* geom, int ih, int iw,
+                         const int* rows, const int* offsets, int n_cap, int cap, int connectivity, int background, int min_area,
+                         int max_regions, const int* det_to_seg, int n_det, int* labels, vrnet_region* table, int* head,
+                         int* box_regions, int* flag, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- dark-channel dehazing (csrc/dehaze.hip) ------------------------------------------------------------------------------
  * Added within ABI 11: two new symbols only, no existing signature, layout or kernel behaviour changed.
  * He et al.'s dark-channel-prior dehazing, the reference's image_augmentation_test/dark_channel.py restated; the host
