@@ -111,6 +111,18 @@ typedef struct vrnet_crop_rec {
 static_assert(sizeof(vrnet_crop_rec) == 16 && offsetof(vrnet_crop_rec, offset) == 0 && offsetof(vrnet_crop_rec, w) == 4 &&
                   offsetof(vrnet_crop_rec, h) == 8 && offsetof(vrnet_crop_rec, image) == 12,
               "vrnet_crop_rec is four int32: render.CROP_RECORD mirrors it");
+extern "C" {
+/* include/vrnet_hip.h: one record per draw row of vrnet_chip_boxes_u8. */
+typedef struct vrnet_chip_rec {
+  int image;                                    /* the image the row belongs to; -1 behind the last row */
+  int w, h;                                     /* the clamped crop; 0, 0: an empty crop */
+  int nw, nh, dx, dy;                           /* the resized crop and where it is pasted in the chip */
+  int state;                                    /* 1 resized, 2 empty (a grey chip), 0 behind the last row (not written) */
+} vrnet_chip_rec;
+}
+static_assert(sizeof(vrnet_chip_rec) == 32 && offsetof(vrnet_chip_rec, image) == 0 && offsetof(vrnet_chip_rec, nw) == 12 &&
+                  offsetof(vrnet_chip_rec, state) == 28,
+              "vrnet_chip_rec is eight int32: render.CHIP_RECORD mirrors it");
 
 __device__ __forceinline__ int vr_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

@@ -181,6 +181,8 @@ _SIGS = {
     "vrnet_render_captions_u8": ([P, I, I, I, P, P, I, P, I, P, P, L, P, I, I, P, P], I),
     "vrnet_render_captions_ragged_u8": ([P, P, P, I, I, I, P, P, I, P, I, P, P, L, P, I, P, P], I),
     "vrnet_crop_boxes_u8": ([P, I, I, I, P, P, P, I, P, L, P, P, P, P], I),
+    "vrnet_chip_workspace": ([I, I, I], L),
+    "vrnet_chip_boxes_u8": ([P, I, I, I, P, P, P, I, I, I, I, P, P, P, P, P, P, P], I),
     "vrnet_dehaze_workspace_bytes": ([I, I, I], L),
     "vrnet_dehaze_u8": ([P, P, I, I, I, I, I, D, D, D, P, P, P, P, L, P], I),
     "vrnet_ace_workspace_bytes": ([I, I, I], L),
@@ -2025,6 +2027,49 @@ def crop_boxes(frames, rows, offsets, arena, table, summary, geom=None, flag=Non
                   (summary, (2,), torch.int32), (flag, (1,), torch.int32)))
     _check(_lib.vrnet_crop_boxes_u8(ptr(frames), B, ihm, iwm, None if geom is None else _geom(geom, B, fn), ptr(rows), ptr(offsets),
                                     n_cap, ptr(arena), arena.shape[0] // 3, ptr(table), ptr(summary), ptr(flag), stream()), fn)
+
+
+# ---- fixed-size detection chips (csrc/chips.hip) -----------------------------------------------------------------------------
+CHIP_RECORD = 8          # int32 per vrnet_chip_rec: image, w, h, nw, nh, dx, dy, state
+CHIP_MAX = 256           # the largest side of a chip
+
+
+def chip_workspace_bytes(n_cap, sh, sw):
+    n = _lib.vrnet_chip_workspace(n_cap, sh, sw)
+    if n < 0:
+        raise RuntimeError(f"chip_boxes: bad shape ({n_cap} rows, chips of {sh} x {sw}; 1..2^20 rows, sides in 1..{CHIP_MAX})")
+    return n
+
+
+def chip_boxes(frames, rows, offsets, chips, table, summary, ws, letterbox=False, chips_f32=None, geom=None, flag=None):
+    """The crops of `crop_boxes` brought to one size (vrnet_chip_boxes_u8): frames (B, ihm, iwm, 3) uint8, rows (n_cap, 5) /
+    offsets (B + 1) int32 as `detect_finish[_ragged]` leave them -> chips (n_cap, sh, sw, 3) uint8, chip n of row n, by the rule
+    of `render.chip_boxes_host` (Pillow's BICUBIC on the crop; letterbox: resize_image's window on grey 128); chips_f32
+    (n_cap, 3, sh, sw) float32 or None: the normalised form; table (n_cap, 8) int32 records image, w, h, nw, nh, dx, dy, state
+    and summary (1) int32 = rows; ws: uint8, at least `chip_workspace_bytes(n_cap, sh, sw)`; geom: the (B, GEOM_BYTES) table of
+    a ragged batch, None: every image fills its slot; flag (1) int32 or None: FLAG_GEOMETRY for a clamped record.  Chips behind
+    the last row are not written.  Two launches."""
+    fn = "chip_boxes"
+    if frames is None or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError(f"{fn}: expected contiguous uint8 frames of shape (B, ihm, iwm, 3)")
+    B, ihm, iwm = frames.shape[:3]
+    if rows is None or rows.dim() != 2 or rows.shape[0] < 1 or offsets is None or chips is None or table is None or summary is None:
+        raise RuntimeError(f"{fn}: rows (n_cap >= 1, 5), offsets, chips, table and summary are required")
+    n_cap = rows.shape[0]
+    if chips.dim() != 4 or chips.shape[0] != n_cap or chips.shape[3] != 3 or not (1 <= chips.shape[1] <= CHIP_MAX and
+                                                                                  1 <= chips.shape[2] <= CHIP_MAX):
+        raise RuntimeError(f"{fn}: the chips must be a uint8 tensor ({n_cap}, sh, sw, 3) with sides in 1..{CHIP_MAX}, got shape "
+                           f"{tuple(chips.shape)}")
+    sh, sw = chips.shape[1:3]
+    need = chip_workspace_bytes(n_cap, sh, sw)
+    if ws is None or ws.dtype != torch.uint8 or ws.dim() != 1 or ws.shape[0] < need or not ws.is_contiguous():
+        raise RuntimeError(f"{fn}: the workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    _tensors(fn, ((frames, (B, ihm, iwm, 3), torch.uint8), (rows, (n_cap, 5), torch.int32), (offsets, (B + 1,), torch.int32),
+                  (chips, (n_cap, sh, sw, 3), torch.uint8), (chips_f32, (n_cap, 3, sh, sw), torch.float32),
+                  (table, (n_cap, CHIP_RECORD), torch.int32), (summary, (1,), torch.int32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_chip_boxes_u8(ptr(frames), B, ihm, iwm, None if geom is None else _geom(geom, B, fn), ptr(rows), ptr(offsets),
+                                    n_cap, sh, sw, int(bool(letterbox)), ptr(chips), ptr(chips_f32), ptr(table), ptr(summary),
+                                    ptr(ws), ptr(flag), stream()), fn)
 
 
 # ---- connected regions of the class map (csrc/regions.hip) ---------------------------------------------------------------------

@@ -16,7 +16,8 @@ capacity, so only its `cap` best-scored ones were considered -- and FLAG_DET_CLA
 outside [0, num_classes), which is not counted -- and, in a ragged pipeline, FLAG_GEOMETRY -- a record of the geometry
 table had to be clamped by a kernel, which the host checks of `run` rule out.  A pipeline built with crops= adds
 hip.crop_boxes behind hip.detect_finish and FLAG_CROP_ARENA, a crop that did not fit into the arena.  A pipeline built with
-dehaze= puts hip.dehaze in front of the letterbox, so that everything downstream reads the dehazed frames, and adds
+chips= adds hip.chip_boxes behind that (behind hip.detect_finish without crops): the same crops at one size; no new bit.  A
+pipeline built with dehaze= puts hip.dehaze in front of the letterbox, so that everything downstream reads the dehazed frames, and adds
 FLAG_DEHAZE, a degenerate image that went on unchanged.  A pipeline built with ace= puts hip.ace there too, behind hip.dehaze
 when both are on, and adds FLAG_ACE for its degenerate images.  A pipeline built with radar_points and box_radar= adds
 hip.box_radar behind the finish node (behind the crops): the radar readout of every kept detection; FLAG_BOX_COUNT, a kept count
@@ -184,6 +185,18 @@ def crop_capacity(crops, batch, frame_shape):
     return int(crops)
 
 
+def chip_config(chips):
+    """The fixed-size chips of a pipeline from its chips= keyword: None (no chips), a size (sh, sw), or a dict of size,
+    letterbox and normalised.  Returns None or a dict of all three, the size checked (sides in 1..render.CHIP_MAX)."""
+    if chips is None or chips is False:
+        return None
+    cfg = dict(chips) if isinstance(chips, dict) else {"size": chips}
+    if "size" not in cfg or set(cfg) - {"size", "letterbox", "normalised"}:
+        raise RuntimeError(f"FramePipeline: chips is None, a size (sh, sw) or a dict of size, letterbox, normalised, got {chips!r}")
+    return dict(size=rendering._chip_size(cfg["size"], "FramePipeline: chips"), letterbox=bool(cfg.get("letterbox", False)),
+                normalised=bool(cfg.get("normalised", False)))
+
+
 def dehaze_config(dehaze):
     """The parameters of a pipeline's dehazing stage from its dehaze= keyword: None (no stage), True (the defaults of
     `render.dehaze_host`) or a dict of its keywords sz, r, eps, omega, tx; checked by `render.dehaze_params`."""
@@ -282,6 +295,8 @@ class FrameResult:
     maps of the run; padded like class_map / rendered from a ragged pipeline.
     From a pipeline built with crops (None otherwise): crops, the `render.Crops` of the run -- every kept detection cut out
     of the original frame, `crops.images()[b][i]` being row i of image b.
+    From a pipeline built with chips (None otherwise): chips, the `render.Chips` of the run -- the same crops brought to one
+    size, `chips.chips[n]` (and `chips.chips_f32[n]`) being draw row n and `chips.images()[b][i]` row i of image b.
     From a pipeline built with dehaze (None otherwise): dehazed (B, ih, iw, 3) uint8, the frames everything else of the
     result was computed from; padded like rendered from a ragged pipeline.
     From a pipeline built with ace (None otherwise): enhanced (B, ih, iw, 3) uint8, the output of the ACE stage, which then
@@ -302,12 +317,13 @@ class FrameResult:
     row kept[b] on) -- `decode.seg_regions_host` is the rule; `regions` brings them to the host."""
     __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
                  "heat_picture", "heat_range", "crops", "dehazed", "enhanced", "box_points", "box_radar", "track_ids",
-                 "track_table", "track_head", "captions", "region_labels", "region_table", "region_head", "box_regions")
+                 "track_table", "track_head", "captions", "region_labels", "region_table", "region_head", "box_regions", "chips")
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
                  heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None, box_points=None, box_radar=None,
                  track_ids=None, track_table=None, track_head=None, captions=None, region_labels=None, region_table=None,
-                 region_head=None, box_regions=None):
+                 region_head=None, box_regions=None, chips=None):
+        self.chips = chips
         self.region_labels, self.region_table, self.region_head, self.box_regions = region_labels, region_table, region_head, box_regions
         self.track_ids, self.track_table, self.track_head, self.captions = track_ids, track_table, track_head, captions
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
@@ -446,6 +462,16 @@ class FramePipeline:
     number -- 6 bytes per frame pixel, about 100 MB at batch 8 and 1080 x 1920.  Crops beyond the arena are dropped, a
     prefix is kept, and FLAG_CROP_ARENA joins the bits of `flag`.
 
+    chips: None (the default: exactly the calls issued without it), a size (sh, sw) or a dict of size, letterbox and
+    normalised -- every kept detection cut out of the ORIGINAL frame and brought to one size with Pillow's BICUBIC
+    (`render.chip_boxes`, csrc/chips.hip; `render.chip_boxes_host` is the rule): one (batch * cap, sh, sw, 3) uint8 tensor of
+    equal-sized pictures for a second stage, chip n of draw row n, and with normalised its (batch * cap, 3, sh, sw) float
+    form; letterbox keeps the crop's aspect ratio on grey 128.  `FrameResult.chips` is its `render.Chips`.  Chips, table,
+    summary and workspace are allocated with the NMS buffers, before the capture; the two launches of hip.chip_boxes sit
+    directly behind the crop launches (behind the detect_finish node without crops), in front of hip.box_radar, and read the
+    frames the crops read -- the dehazed or ACE frames when those stages are on.  Chips behind the last row are not written.
+    Fixed-size and ragged pipelines alike; no new flag bit.
+
     dehaze: None (the default: exactly the calls issued without it), True or a dict of the keywords sz, r, eps, omega, tx of
     `render.dehaze_host` -- dark-channel-prior dehazing of the raw frames (`render.dehaze`, csrc/dehaze.hip) as the first
     stage: the eleven launches of hip.dehaze sit in front of the letterbox node, and the letterbox, `render_frame`, the heat
@@ -509,9 +535,10 @@ class FramePipeline:
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
                  font=None, label_sizes=None, crops=None, dehaze=None, ace=None, box_radar=None, box_shrink=1.0, track=None,
-                 captions=None, regions=None):
+                 captions=None, regions=None, chips=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
+        self.chips = chip_config(chips)
         self.regions = None
         if regions is not None and regions is not False:
             from .decode import check_region_params
@@ -667,6 +694,10 @@ class FramePipeline:
         self._crops = None
         if self.crop_capacity is not None:
             self._crops = rendering.crop_buffers(B * cap, self.crop_capacity, B, self.flag, dev)
+        self._chips = None
+        if self.chips is not None:            # before the capture: chips, table, summary and the tap tables
+            self._chips = rendering.chip_buffers(B * cap, self.chips["size"], B, self.chips["letterbox"],
+                                                 self.chips["normalised"], self.flag, dev)
         self._box_points = self._box_radar = None
         if self.box_radar:                    # before the capture: the two outputs and the projected points
             self._box_points, self._box_radar = torch.zeros((B, cap), **i32), torch.zeros((B, cap, 2, 5), device=dev)
@@ -729,6 +760,10 @@ class FramePipeline:
         if self._crops is not None:           # right behind the finish node: from the original frames, which nothing draws on
             hip.crop_boxes(frames, self._draw_rows, self._offsets, self._crops.arena, self._crops.table,
                            self._crops.summary, geom=geom, flag=self.flag)
+        if self._chips is not None:           # directly behind the crops: the same rows of the same frames, at one size
+            hip.chip_boxes(frames, self._draw_rows, self._offsets, self._chips.chips, self._chips.table, self._chips.summary,
+                           self._chips.workspace, letterbox=self._chips.letterbox, chips_f32=self._chips.chips_f32, geom=geom,
+                           flag=self.flag)
         if self.box_radar:                    # behind the finish node (and the crops): rows and points share the original frame
             hip.box_radar(self.points, self.views, self._rows, self._kept, float(self.radar_points.min_depth), self.box_shrink,
                           self._box_points, self._box_radar, flag=self.flag, ws=self._box_ws)
@@ -766,7 +801,8 @@ class FramePipeline:
                              dehazed=dehazed, enhanced=frames if self.ace is not None else None, box_points=self._box_points,
                              box_radar=self._box_radar, track_ids=self._track_ids, track_table=self._track_table,
                              track_head=self._track_head, captions=self._captions, region_labels=self._region_labels,
-                             region_table=self._region_table, region_head=self._region_head, box_regions=self._box_regions)
+                             region_table=self._region_table, region_head=self._region_head, box_regions=self._box_regions,
+                             chips=self._chips)
         if self.heatmap:
             result.heat_picture, result.heat_mask, result.heat_range = rendering.heatmap(
                 frames, det, (H, W), alpha=self.heat_alpha, geom=geom, flag=self.flag, **self._heat_window)
@@ -907,7 +943,9 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     non-empty crop the arena kept is saved as dir_save_path/img_crop/<stem>_crop_<i>.png, i being the row's index within its
     picture (the `i` of yolo.py:180-193); the crops of the repeated fill pictures are dropped with the repeats.  The reference
     writes img_crop/crop_<i>.png and so overwrites the crops of one picture with those of the next: the stem in the name is a
-    deliberate departure.  From a pipeline built with dehaze the dehazed frame is saved as <stem>_dehaze.png, from one built
+    deliberate departure.  From a pipeline built with chips every chip is saved as dir_save_path/img_chip/<stem>_chip_<i>.png,
+    with the same i (the grey chip of an empty crop included, so that i stays the row's index).  From a pipeline built with
+    dehaze the dehazed frame is saved as <stem>_dehaze.png, from one built
     with ace the enhanced frame as <stem>_ace.png, from one built with box_radar the radar readout of the picture's
     detections as <stem>_radar.txt (`radar_text`).  Two pictures that would share one output name (names that differ only in
     their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on, or `a_dehaze.jpg` with dehazing on, or `a_ace.jpg`
@@ -961,6 +999,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         enhanced = None if enhanced is None else enhanced.cpu().numpy()
         crops = None if dir_save_path is None else getattr(result, "crops", None)
         crops = None if crops is None else crops.images()
+        chips = None if dir_save_path is None else getattr(result, "chips", None)
+        chips = None if chips is None else chips.images()
         readout = None if dir_save_path is None or getattr(result, "box_radar", None) is None else result.radar_readout()
         tracks = None if dir_save_path is None or not tracking else result.tracks()
         regions = None if dir_save_path is None or getattr(result, "region_table", None) is None else result.regions()
@@ -989,4 +1029,7 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
                 if crop is not None and crop.size:
                     os.makedirs(os.path.join(dir_save_path, "img_crop"), exist_ok=True)
                     Image.fromarray(crop).save(os.path.join(dir_save_path, "img_crop", f"{os.path.splitext(n)[0]}_crop_{i}.png"))
+            for i, chip in enumerate(chips[b] if chips is not None else ()):
+                os.makedirs(os.path.join(dir_save_path, "img_chip"), exist_ok=True)
+                Image.fromarray(chip).save(os.path.join(dir_save_path, "img_chip", f"{os.path.splitext(n)[0]}_chip_{i}.png"))
     return out

@@ -58,6 +58,12 @@ ValueError for x1 < x0 where this module paints nothing.
   either, so the empty entry is this project's definition); otherwise the crop is frame[t:bt, l:r, :], bit for bit
   np.array(image.crop([left, top, right, bottom])).  The arena's layout is `crop_layout`'s.
 
+* `chip_boxes` / `Chips` / `chip_boxes_host` / `chip_geometry` / `chip_resample_host`: the same crops brought to ONE size, the
+  way the reference brings any picture to a fixed size (resize_image, utils/utils.py:19-32) -- one (n, sh, sw, 3) tensor of
+  equal-sized pictures, and optionally its normalised (n, 3, sh, sw) float form, for a second stage (csrc/chips.hip).
+  `chip_boxes_host` states the rule with Pillow itself (crop, THEN resize with BICUBIC; letterbox: resize_image's window on
+  grey 128 with nw, nh >= 1), `chip_resample_host` the integer arithmetic the kernels run; both equal Pillow byte for byte.
+
 * `dehaze` / `dehaze_host`: He et al.'s dark-channel-prior dehazing, the reference's image_augmentation_test/dark_channel.py,
   on the raw frames (csrc/dehaze.hip).  `dehaze_host` states the rule in numpy float64, one rounding per operation; the
   kernels equal it bit for bit.
@@ -66,7 +72,7 @@ ValueError for x1 < x0 where this module paints nothing.
   de-rain enhancement) on the raw frames (csrc/ace.hip).  `ace_host` states the rule in numpy float64, one rounding per
   operation; the kernels equal it byte for byte.
 
-Out of scope: crops resized to one size, image encoding and video I/O."""
+Out of scope: any resize filter but BICUBIC for the chips, image encoding and video I/O."""
 import colorsys
 import os
 
@@ -80,6 +86,8 @@ FLAG_LABEL_SCORE = 2048   # LB_FLAG_SCORE of csrc/labels.hip: a label score that
 LABEL_SCORES = 101        # the strings 0.00 .. 1.00 a score in [0, 1] formats to
 FLAG_CROP_ARENA = 4096    # VR_FLAG_CROP_ARENA of csrc/common.h: a crop that did not fit into the arena, dropped
 CROP_RECORD = np.dtype([("offset", "<i4"), ("w", "<i4"), ("h", "<i4"), ("image", "<i4")])      # vrnet_crop_rec, 16 bytes
+CHIP_RECORD = np.dtype([(k, "<i4") for k in ("image", "w", "h", "nw", "nh", "dx", "dy", "state")])      # vrnet_chip_rec, 32 bytes
+CHIP_MAX = 256            # CH_MAX of csrc/chips.hip: the largest side of a chip
 FLAG_DEHAZE = 8192        # VR_FLAG_DEHAZE of csrc/common.h: a degenerate image, returned unchanged by `dehaze`
 DEHAZE_MAX_SZ, DEHAZE_MAX_R = 31, 128
 FLAG_ACE = 16384          # VR_FLAG_ACE of csrc/common.h: a degenerate image, returned unchanged by `ace`
@@ -1273,6 +1281,242 @@ def crop_boxes(frames_u8, results, capacity=None, geom=None, flag=None, device="
         crops = crop_buffers(rows.shape[0], min(2 * B * ih * iw, 1 << 30) if capacity is None else capacity, B, flag, dev)
         hip.crop_boxes(img, rows, offsets, crops.arena, crops.table, crops.summary, geom=geom, flag=flag)
     return crops
+
+
+# ---- fixed-size detection chips (csrc/chips.hip) -------------------------------------------------------------------------------
+def _chip_size(size, fn):
+    try:
+        sh, sw = (int(v) if isinstance(v, (int, np.integer)) and not isinstance(v, bool) else 0 for v in size)
+    except (TypeError, ValueError):
+        sh = sw = 0
+    if not (1 <= sh <= CHIP_MAX and 1 <= sw <= CHIP_MAX):
+        raise RuntimeError(f"{fn}: size is (sh, sw) with both sides integers in 1..{CHIP_MAX}, got {size!r}")
+    return sh, sw
+
+
+def chip_geometry(w, h, size, letterbox):
+    """The integers of the chip rule for a clamped crop of w x h pixels and size = (sh, sw): (nw, nh, dx, dy), the size the
+    crop is resized to and where it is pasted in the chip.  An empty crop (w <= 0 or h <= 0): (0, 0, 0, 0), an all-grey chip.
+    letterbox False: (sw, sh, 0, 0).  letterbox True: resize_image's rule (utils/utils.py:19-32) on the crop in Python
+    doubles, scale = min(sw / w, sh / h), nw = max(int(w * scale), 1), nh = max(int(h * scale), 1), pasted at ((sw - nw) //
+    2, (sh - nh) // 2).  The max(.., 1) is a deliberate departure from the reference: a 1000 x 3 crop into 64 x 64 gives
+    nh = 0 there, and Pillow raises on it; here the strip keeps one row."""
+    sh, sw = _chip_size(size, "chip_geometry")
+    w, h = int(w), int(h)
+    if w <= 0 or h <= 0:
+        return 0, 0, 0, 0
+    if not letterbox:
+        return sw, sh, 0, 0
+    scale = min(sw / w, sh / h)
+    nw, nh = max(int(w * scale), 1), max(int(h * scale), 1)
+    return nw, nh, (sw - nw) // 2, (sh - nh) // 2
+
+
+def chip_boxes_host(frame, rows, size, letterbox=False):
+    """THE RULE of the fixed-size chips for ONE image, with Pillow itself: frame (ih, iw, 3) uint8, the ORIGINAL picture, rows
+    (n, 5) int32 = left, top, right, bottom, class, size = (sh, sw).  Returns a list of n (sh, sw, 3) uint8 arrays.  The crop
+    of a row is the one `crop_boxes_host` takes (each coordinate clamped to the image, w = r - l, h = bt - t).  letterbox
+    False: image.crop((l, t, r, bt)).resize((sw, sh), BICUBIC) -- crop THEN resize: the taps stop at the crop's edge
+    (resize(box=...) reads beyond it and gives other bytes).  letterbox True: the crop resized to `chip_geometry`'s (nw, nh)
+    and pasted at its (dx, dy) on grey 128, resize_image's rule with nw, nh >= 1 (the departure `chip_geometry` states).  An
+    empty crop (w <= 0 or h <= 0) is an all-grey chip in both modes.  A pass whose size does not change is the identity, as
+    it is in Pillow.  The kernels of csrc/chips.hip are tested against this function, bit for bit."""
+    from PIL import Image
+    fn = "chip_boxes_host"
+    pic = np.asarray(frame)
+    if pic.dtype != np.uint8 or pic.ndim != 3 or pic.shape[2] != 3:
+        raise RuntimeError(f"{fn}: expected a uint8 frame (ih, iw, 3), got {pic.dtype} {pic.shape}")
+    sh, sw = _chip_size(size, fn)
+    l, t, w, h = _crop_windows(_crop_rows(rows, fn), pic.shape[0], pic.shape[1])
+    image = Image.fromarray(np.ascontiguousarray(pic))
+    out = []
+    for n in range(len(l)):
+        chip = np.full((sh, sw, 3), 128, np.uint8)
+        if w[n] > 0:
+            nw, nh, dx, dy = chip_geometry(w[n], h[n], (sh, sw), letterbox)
+            crop = image.crop((int(l[n]), int(t[n]), int(l[n] + w[n]), int(t[n] + h[n])))
+            chip[dy:dy + nh, dx:dx + nw] = np.asarray(crop.resize((nw, nh), Image.BICUBIC))
+        out.append(chip)
+    return out
+
+
+def _bicubic(x):
+    """Resample.c bicubic_filter, a = -0.5, in Python doubles (one rounding per operation, as the C code)."""
+    a = -0.5
+    x = -x if x < 0.0 else x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _chip_axis(n_in, n_out):
+    """Per output index of an axis resized n_in -> n_out: (xmin, n, ww) of Resample.c precompute_coeffs -- the window and the
+    sum of its bicubic values in the order x = 0 .. n - 1 -- and the integer weights recomputed from them alone, as the
+    kernel recomputes them (normalize_coeffs_8bpc: 22 bits, rounded half away from zero)."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support, ss = 2.0 * fs, 1.0 / fs
+    table = []
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), n_in) - xmin
+        ww = 0.0
+        for x in range(n):
+            ww += _bicubic((x + xmin - center + 0.5) * ss)
+        k = np.zeros(n, np.int32)
+        for x in range(n):                    # from (xmin, n, ww) alone
+            wt = _bicubic((x + xmin - center + 0.5) * ss)
+            if ww != 0.0:
+                wt /= ww
+            k[x] = int(-0.5 + wt * (1 << 22)) if wt < 0 else int(0.5 + wt * (1 << 22))
+        table.append((xmin, n, ww, k))
+    return table
+
+
+def chip_resample_host(crop, nh, nw):
+    """The arithmetic the kernels of csrc/chips.hip run, in numpy, without Pillow: crop (h, w, 3) uint8 -> (nh, nw, 3) uint8,
+    byte for byte image.resize((nw, nh), BICUBIC).  Per axis a table of (xmin, n, ww) per output index (`_chip_axis`), every
+    integer weight recomputed from its entry; each pass sums weight * byte in int32 on top of 1 << 21, shifts by 22 and clips;
+    the horizontal pass is rounded to bytes before the vertical one, the only ordering Pillow imposes -- integer addition is
+    associative, so the kernel may add the taps of the vertical pass in chunks of source rows.  A pass whose size does not
+    change has the weights (0, 1, 0, 0) exactly and is the identity.  Kept so that the kernel's arithmetic is pinned to Pillow
+    without a GPU (tests/test_chips_host.py)."""
+    fn = "chip_resample_host"
+    src = np.asarray(crop)
+    if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3 or min(src.shape) < 1:
+        raise RuntimeError(f"{fn}: expected a non-empty uint8 crop (h, w, 3), got {src.dtype} {src.shape}")
+    nh, nw = int(nh), int(nw)
+    if nh < 1 or nw < 1:
+        raise RuntimeError(f"{fn}: the new size must be at least 1 x 1, got {nh} x {nw}")
+    h, w = src.shape[:2]
+
+    def clip8(acc):
+        return np.clip(acc >> 22, 0, 255).astype(np.uint8)
+
+    mid = np.empty((h, nw, 3), np.uint8)
+    for xx, (xmin, n, _, k) in enumerate(_chip_axis(w, nw)):
+        acc = np.full((h, 3), 1 << 21, np.int32)
+        for x in range(n):
+            acc += k[x] * src[:, xmin + x, :].astype(np.int32)
+        mid[:, xx] = clip8(acc)
+    out = np.empty((nh, nw, 3), np.uint8)
+    for yy, (ymin, n, _, k) in enumerate(_chip_axis(h, nh)):
+        acc = np.full((nw, 3), 1 << 21, np.int32)
+        for y in range(n):
+            acc += k[y] * mid[ymin + y].astype(np.int32)
+        out[yy] = clip8(acc)
+    return out
+
+
+def chip_table(rows, offsets, sizes, size, letterbox=False):
+    """The records `chip_boxes` leaves for its rows: rows (N, 5) int32, offsets (B + 1) int32, sizes = (ih, iw) of all images
+    or a (B, 2) array of each one's.  Returns (table, N): N = offsets[B] clamped to [0, len(rows)] records of CHIP_RECORD --
+    image, w, h, nw, nh, dx, dy, state (1 resized, 2 empty) -- with the image of a row as `crop_layout` finds it."""
+    fn = "chip_table"
+    rows = _crop_rows(rows, fn)
+    offsets = np.asarray(offsets)
+    if offsets.dtype != np.int32 or offsets.ndim != 1 or offsets.size < 2:
+        raise RuntimeError(f"{fn}: expected int32 offsets (B + 1), got {offsets.dtype} {offsets.shape}")
+    B = offsets.size - 1
+    sizes = np.asarray(sizes, np.int64)
+    sizes = np.broadcast_to(sizes, (B, 2)) if sizes.shape == (2,) else sizes
+    if sizes.shape != (B, 2):
+        raise RuntimeError(f"{fn}: sizes is (ih, iw) or a ({B}, 2) array")
+    N = int(np.clip(offsets[B], 0, len(rows)))
+    c = np.minimum(N, np.maximum.accumulate(np.maximum(offsets.astype(np.int64), 0)))
+    image = np.minimum(np.searchsorted(c[1:], np.arange(N), side="right"), B - 1)
+    _, _, w, h = _crop_windows(rows[:N], sizes[image, 0], sizes[image, 1])
+    table = np.zeros(N, CHIP_RECORD)
+    for n in range(N):
+        table[n] = (image[n], w[n], h[n]) + chip_geometry(w[n], h[n], size, letterbox) + (1 if w[n] > 0 else 2,)
+    return table, N
+
+
+class Chips:
+    """What `chip_boxes` leaves on the device: chips (n_cap, sh, sw, 3) uint8, chip n of draw row n; chips_f32 (n_cap, 3, sh,
+    sw) float32, the same bytes normalised as the network's input is (None unless asked for); table (n_cap, 8) int32, one
+    CHIP_RECORD -- image, w, h, nw, nh, dx, dy, state -- per draw row (state 1: resized, 2: an empty crop, a grey chip, 0
+    with image -1: behind the last row, whose chips are NOT written and hold what the buffer held); summary (1) int32 =
+    rows; flag (1) int32.  A second stage that stays on the device reads chips_f32[:rows].  From a pipeline these are its
+    own buffers: the next run overwrites them."""
+    __slots__ = ("chips", "chips_f32", "table", "summary", "flag", "batch", "size", "letterbox", "workspace", "_packed")
+
+    def __init__(self, chips, chips_f32, table, summary, flag, batch, size, letterbox, workspace, packed):
+        self.chips, self.chips_f32, self.table, self.summary, self.flag = chips, chips_f32, table, summary, flag
+        self.batch, self.size, self.letterbox, self.workspace, self._packed = int(batch), tuple(size), bool(letterbox), workspace, packed
+
+    def images(self):
+        """The read-back: one list per image of its chips in row order as (sh, sw, 3) uint8 arrays.  ONE device-to-host copy
+        (table, summary and chips share a buffer), which waits for the device."""
+        packed = self._packed.cpu().numpy()
+        n_cap, (sh, sw) = self.table.shape[0], self.size
+        table = packed[:32 * n_cap].view(CHIP_RECORD)
+        N = int(packed[32 * n_cap:32 * n_cap + 4].view(np.int32)[0])
+        chips = packed[32 * n_cap + 16:].reshape(n_cap, sh, sw, 3)
+        out = [[] for _ in range(self.batch)]
+        for n in range(min(max(N, 0), n_cap)):
+            out[int(table["image"][n])].append(chips[n].copy())
+        return out
+
+
+def chip_buffers(n_cap, size, batch, letterbox, normalised, flag, device):
+    """The device buffers of one `hip.chip_boxes` call as a `Chips`: table, summary and chips share one uint8 tensor (the
+    table first, the summary in 16 bytes of its own, then the chips), so the read-back is one copy."""
+    from . import hip
+    sh, sw = _chip_size(size, "chip_boxes")
+    packed = torch.zeros(32 * n_cap + 16 + n_cap * sh * sw * 3, dtype=torch.uint8, device=device)
+    table = packed[:32 * n_cap].view(torch.int32).view(n_cap, 8)
+    summary = packed[32 * n_cap:32 * n_cap + 4].view(torch.int32)
+    chips = packed[32 * n_cap + 16:].view(n_cap, sh, sw, 3)
+    f32 = torch.zeros((n_cap, 3, sh, sw), dtype=torch.float32, device=device) if normalised else None
+    ws = torch.empty(hip.chip_workspace_bytes(n_cap, sh, sw), dtype=torch.uint8, device=device)
+    return Chips(chips, f32, table, summary, flag, batch, (sh, sw), letterbox, ws, packed)
+
+
+def chip_boxes(frames_u8, results, size, letterbox=False, normalised=False, geom=None, flag=None, device="cuda"):
+    """Every detection cut out of the ORIGINAL frames and brought to size = (sh, sw) on the device, by the rule of
+    `chip_boxes_host` (vrnet_chip_boxes_u8, two launches): one tensor of equal-sized pictures, what a second-stage
+    classifier, an appearance descriptor or a thumbnail strip takes.  frames_u8, results, geom and flag as `crop_boxes` takes
+    them; letterbox: keep the crop's aspect ratio on grey 128 (resize_image's rule) instead of stretching it; normalised:
+    also write `Chips.chips_f32`, the chips as the network's input is normalised.  flag receives hip.FLAG_GEOMETRY alone.
+    Returns a `Chips`.  No host synchronisation."""
+    from . import hip
+    fn = "chip_boxes"
+    size = _chip_size(size, fn)
+    img = _as_u8(frames_u8, "frames", 4, fn)
+    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
+        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    B, ih, iw = img.shape[:3]
+    if results is None:
+        raise RuntimeError(f"{fn}: needs the results of non_max_suppression or a device pair (rows, offsets)")
+    host = None
+    if isinstance(results, tuple) and len(results) == 2 and all(torch.is_tensor(t) for t in results):
+        rows, offsets = results
+    else:
+        if len(results) != B:
+            raise RuntimeError(f"{fn}: {len(results)} result entries for {B} frames")
+        host = box_rows(results, (ih, iw), MAX_COLORS)[:2]
+    img = img.to(device, non_blocking=True).contiguous()
+    dev = img.device
+    with torch.cuda.device(dev):
+        if host is not None:                  # offsets and rows in one pinned buffer; at least one row, so it has an address
+            n = max(len(host[0]), 1)
+            packed = torch.zeros(B + 1 + 5 * n, dtype=torch.int32).pin_memory()
+            packed[:B + 1] = torch.from_numpy(host[1])
+            packed[B + 1:B + 1 + host[0].size] = torch.from_numpy(host[0].reshape(-1))
+            packed = packed.to(dev, non_blocking=True)
+            offsets, rows = packed[:B + 1], packed[B + 1:].view(n, 5)
+        else:
+            rows, offsets = rows.to(dev).contiguous(), offsets.to(dev).contiguous()
+        if flag is None:
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        chips = chip_buffers(rows.shape[0], size, B, letterbox, normalised, flag, dev)
+        hip.chip_boxes(img, rows, offsets, chips.chips, chips.table, chips.summary, chips.workspace, letterbox=letterbox,
+                       chips_f32=chips.chips_f32, geom=geom, flag=flag)
+    return chips
 
 
 # ---- dark-channel dehazing (csrc/dehaze.hip) -----------------------------------------------------------------------------------

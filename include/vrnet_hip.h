@@ -1556,6 +1556,43 @@ int vrnet_crop_boxes_u8(const unsigned char* frames, int B, int ihm, int iwm, co
                         const int* offsets, int n_cap, unsigned char* arena, long capacity_px, vrnet_crop_rec* table,
                         int* summary, int* flag, void* stream);
 
+/* ---- fixed-size detection chips (csrc/chips.hip) ---------------------------------------------------------------------------
+ * Added within ABI 11: two new symbols and one new record layout (vrnet_chip_rec) only, no existing signature, layout, flag
+ * bit or kernel behaviour changed; hip.py binds every declared symbol at import.
+ * resize_image, utils/utils.py:19-32, the reference's way to bring any picture to a fixed size, applied to every crop of
+ * yolo.py:180-193: one tensor of equal-sized pictures for a second stage.  The host statement, with Pillow itself, is
+ * render.chip_boxes_host / render.chip_geometry, and the kernels equal it bit for bit.
+ * vrnet_chip_boxes_u8: frames, geom, rows, offsets, n_cap, N, the image of a row and its clamp l, t, w, h exactly as
+ *   vrnet_crop_boxes_u8 takes and makes them (a clamped or empty geom record sets bit 256 of *flag; no other bit is set).
+ *   Chip n belongs to row n.  w <= 0 or h <= 0: the chip is all grey 128, table[n] = {b, 0, 0, 0, 0, 0, 0, 2}.  Otherwise
+ *   letterbox == 0: the chip is image.crop((l, t, r, bt)).resize((sw, sh), BICUBIC) -- crop THEN resize, the taps stop at the
+ *   crop's edge -- and nw, nh, dx, dy = sw, sh, 0, 0.  letterbox != 0: scale = min(sw / w, sh / h) in doubles, nw =
+ *   max(int(w scale), 1), nh = max(int(h scale), 1) (the max is a departure: the reference lets Pillow raise on nh = 0), the
+ *   crop resized to (nw, nh) and pasted at dx, dy = (sw - nw) / 2, (sh - nh) / 2 on grey 128.  table[n] = {b, w, h, nw, nh,
+ *   dx, dy, 1}.  The bytes are Pillow's: Resample.c's windows and 22-bit weights, the horizontal pass rounded to bytes before
+ *   the vertical one; a pass whose size does not change is the identity.
+ *   chips (n_cap, sh, sw, 3) u8; chips_f32 (n_cap, 3, sh, sw) or NULL: the same bytes as ((v / 255) - mean) / std in double,
+ *   rounded once, the network's input.  table[n] = {-1, 0, 0, 0, 0, 0, 0, 0} for N <= n < n_cap, and chips and float chips
+ *   of those rows are NOT written: the work follows the row count.  summary (1) = N.
+ *   workspace: vrnet_chip_workspace(n_cap, sh, sw) bytes (16 (sh + sw) a row: per output index of each axis the window and
+ *   the sum of its bicubic values, from which every thread recomputes any integer weight; no tap capacity, no intermediate
+ *   picture), 8-byte aligned; -1 for sizes outside the limits.
+ *   Two launches whose grids depend on n_cap, sh and sw alone: the tables (one workgroup per row) and the resample (one
+ *   workgroup per row and band of 8 chip rows, which streams the band's source rows in chunks of at most 16 through LDS; one behind
+ *   the last row leaves at once).  No allocation, no memset, no host synchronisation; capturable in a graph.
+ *   0 < B < 65536, 0 < n_cap <= 2^20, 1 <= sh, sw <= 256, ihm iwm < 2^31; table and chips_f32 4-byte aligned; flag may be
+ *   NULL. */
+typedef struct vrnet_chip_rec {
+  int image;                         /* the image the row belongs to; -1 behind the last row */
+  int w, h;                          /* the clamped crop; 0, 0: an empty crop */
+  int nw, nh, dx, dy;                /* the resized crop and where it is pasted in the chip */
+  int state;                         /* 1 resized, 2 empty (a grey chip), 0 behind the last row (not written) */
+} vrnet_chip_rec;                    /* 32 bytes */
+long vrnet_chip_workspace(int n_cap, int sh, int sw);
+int vrnet_chip_boxes_u8(const unsigned char* frames, int B, int ihm, int iwm, const vrnet_frame_geom* geom, const int* rows,
+                        const int* offsets, int n_cap, int sh, int sw, int letterbox, unsigned char* chips, float* chips_f32,
+                        vrnet_chip_rec* table, int* summary, void* workspace, int* flag, void* stream);
+
 /* ---- connected regions of the class map (csrc/regions.hip) -----------------------------------------------------------------
  * Added within ABI 11: two new symbols, one new record layout (vrnet_region) and one new flag bit only, no existing signature,
  * layout or kernel behaviour changed; hip.py binds every declared symbol at import.
