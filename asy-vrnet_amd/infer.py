@@ -14,32 +14,35 @@ Bits of `FrameResult.flag` (an int32 word, zeroed by every run; read it when you
 FLAG_BOX_COLOUR, FLAG_BOX_ROWS (see render.render_frame), FLAG_CANDIDATES -- an image had more candidates than the
 capacity, so only its `cap` best-scored ones were considered -- and FLAG_DET_CLASS -- a kept row with a class id
 outside [0, num_classes), which is not counted -- and, in a ragged pipeline, FLAG_GEOMETRY -- a record of the geometry
-table had to be clamped by a kernel, which the host checks of `run` rule out.  A pipeline built with crops= adds
-hip.crop_boxes behind hip.detect_finish and FLAG_CROP_ARENA, a crop that did not fit into the arena.  A pipeline built with
-chips= adds hip.chip_boxes behind that (behind hip.detect_finish without crops): the same crops at one size; no new bit.  A
-pipeline built with dehaze= puts hip.dehaze in front of the letterbox, so that everything downstream reads the dehazed frames, and adds
-FLAG_DEHAZE, a degenerate image that went on unchanged.  A pipeline built with ace= puts hip.ace there too, behind hip.dehaze
-when both are on, and adds FLAG_ACE for its degenerate images.  A pipeline built with radar_points and box_radar= adds
-hip.box_radar behind the finish node (behind the crops): the radar readout of every kept detection; FLAG_BOX_COUNT, a kept count
-outside the row buffer, is ruled out by the NMS that writes it.  A pipeline built with track= adds hip.track_update behind
-that (behind the crops or the finish node without box_radar) and in front of decode.seg_predict: every batch slot becomes a
-stream whose track table lives on the device across runs, and FLAG_TRACK_FULL says that a valid row found no free slot in it
-and got track id 0.  A pipeline built with captions= adds hip.caption_text behind that (behind hip.box_radar without a tracker) and
-hip.render_captions behind the label launches (behind the render node without labels): '#<track id> <range>m <speed>m/s'
-under every rendered box; FLAG_CAPTION says that a range or a speed could not be drawn and was left out.  A pipeline built
-with regions= adds hip.seg_regions directly behind decode.seg_predict and in front of the render node: the connected regions
-of the class map, linked both ways with the kept rows; FLAG_REGIONS says that an image had more regions than the table holds.
+table had to be clamped by a kernel, which the host checks of `run` rule out.  The optional stages add their own: FLAG_POINT_COUNT
+(radar_points), FLAG_LABEL_SCORE, FLAG_CROP_ARENA, FLAG_DEHAZE, FLAG_ACE, FLAG_BOX_COUNT, FLAG_TRACK_FULL, FLAG_CAPTION and
+FLAG_REGIONS, each described with its stage.
+
+Everything else a pipeline can do is an optional STAGE, one class of `stages.py` each, which holds the stage's keyword,
+buffers, launches, result fields and documentation.  `stages.STAGES` is their order; a pipeline keeps those that are on, in
+that order, as `stages`, and the chain calls them at four hook points, within a hook point in that order:
+
+    frames      in front of the letterbox; each may replace the frames everything later reads     dehaze, ace
+    rows        behind hip.detect_finish, in front of the seg node                                  crops, chips, box_radar, track,
+                                                                                                    captions (hip.caption_text)
+    class_map   behind the seg node, in front of the render node                                    regions, labels (hip.label_index;
+                                                                                                    the render node draws them)
+    picture     behind the render node, in front of `_tail`                                         captions (hip.render_captions),
+                                                                                                    heatmap
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
 arguments, so ONE captured graph serves any mix of sizes.  `predict_dir` is predict.py's `dir_predict` mode on top of it."""
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import data
 from . import render as rendering
+from .stages import (STAGES, ace_config, caption_config, chip_config, crop_capacity, dehaze_config,    # noqa: F401
+                     radar_text)
 
 FLAG_CANDIDATES, FLAG_DET_CLASS = 8, 16          # NMS_FLAG_* of csrc/nms.hip, above render.FLAG_*
 FLAG_GEOMETRY = 256                              # VR_FLAG_GEOMETRY of csrc/common.h, above evaluate.FLAG_EVAL_*
@@ -173,101 +176,6 @@ def validate_ragged_inputs(frames, radar, sizes, batch, capacity, input_shape, l
     return items, validate_radar(radar, batch, input_shape), own, table
 
 
-def crop_capacity(crops, batch, frame_shape):
-    """The pixels of a pipeline's crop arena from its crops= keyword: None (no crops), True (2 * batch * ihm * iwm, at most
-    2^30) or the number itself, 1..2^30."""
-    if crops is None or crops is False:
-        return None
-    if crops is True:
-        return min(2 * int(batch) * int(frame_shape[0]) * int(frame_shape[1]), 1 << 30)
-    if not isinstance(crops, (int, np.integer)) or not 1 <= int(crops) <= 1 << 30:
-        raise RuntimeError(f"FramePipeline: crops is None, True or the capacity of the crop arena, 1..2^30 pixels, got {crops!r}")
-    return int(crops)
-
-
-def chip_config(chips):
-    """The fixed-size chips of a pipeline from its chips= keyword: None (no chips), a size (sh, sw), or a dict of size,
-    letterbox and normalised.  Returns None or a dict of all three, the size checked (sides in 1..render.CHIP_MAX)."""
-    if chips is None or chips is False:
-        return None
-    cfg = dict(chips) if isinstance(chips, dict) else {"size": chips}
-    if "size" not in cfg or set(cfg) - {"size", "letterbox", "normalised"}:
-        raise RuntimeError(f"FramePipeline: chips is None, a size (sh, sw) or a dict of size, letterbox, normalised, got {chips!r}")
-    return dict(size=rendering._chip_size(cfg["size"], "FramePipeline: chips"), letterbox=bool(cfg.get("letterbox", False)),
-                normalised=bool(cfg.get("normalised", False)))
-
-
-def dehaze_config(dehaze):
-    """The parameters of a pipeline's dehazing stage from its dehaze= keyword: None (no stage), True (the defaults of
-    `render.dehaze_host`) or a dict of its keywords sz, r, eps, omega, tx; checked by `render.dehaze_params`."""
-    if dehaze is None or dehaze is False:
-        return None
-    if dehaze is True:
-        dehaze = {}
-    if not isinstance(dehaze, dict) or set(dehaze) - {"sz", "r", "eps", "omega", "tx"}:
-        raise RuntimeError(f"FramePipeline: dehaze is None, True or a dict of sz, r, eps, omega, tx, got {dehaze!r}")
-    return rendering.dehaze_params(fn="FramePipeline", **dehaze)
-
-
-def ace_config(ace):
-    """The parameters of a pipeline's ACE stage from its ace= keyword: None (no stage), True (the defaults of
-    `render.ace_host`) or a dict of its keywords ratio, radius, s, bins; checked by `render.ace_params`."""
-    if ace is None or ace is False:
-        return None
-    if ace is True:
-        ace = {}
-    if not isinstance(ace, dict) or set(ace) - {"ratio", "radius", "s", "bins"}:
-        raise RuntimeError(f"FramePipeline: ace is None, True or a dict of ratio, radius, s, bins, got {ace!r}")
-    return rendering.ace_params(fn="FramePipeline", **ace)
-
-
-def caption_config(captions, render, track, box_radar, ragged, ih):
-    """The captions= keyword of a pipeline, checked on the host: None (no captions), True, a `render.GlyphAtlas` or a dict of
-    atlas, fps, font, sizes -> (composing, fps, size index); composing is the atlas, or True where a fixed-size pipeline of
-    frames lower than 17 rows composes the text and draws nothing; the size index is that of a fixed-size pipeline's one
-    font size (None: nothing is drawn, or a ragged pipeline, whose table follows each call).  Names what is missing."""
-    fn = "FramePipeline"
-    if captions is None or captions is False:
-        return None, 0.0, None
-    if captions is True:
-        captions = {}
-    elif isinstance(captions, rendering.GlyphAtlas):
-        captions = {"atlas": captions}
-    if not isinstance(captions, dict) or set(captions) - {"atlas", "fps", "font", "sizes"}:
-        raise RuntimeError(f"{fn}: captions is None, True, a render.GlyphAtlas or a dict of atlas, fps, font, sizes, got {captions!r}")
-    if not render:
-        raise RuntimeError(f"{fn}: captions are drawn on the rendered frame; they need render=True")
-    if not (track or box_radar):
-        raise RuntimeError(f"{fn}: captions show track ids and radar ranges; they need track= or box_radar=True (or both), and this "
-                           "pipeline has neither")
-    fps = captions.get("fps", 0.0)
-    if isinstance(fps, bool) or not isinstance(fps, (int, float, np.integer, np.floating)) or not 0.0 <= float(fps) <= 1e6:
-        raise RuntimeError(f"{fn}: captions: fps is the frame rate of the streams, a number in [0, 1e6], got {fps!r}")
-    if float(fps) > 0 and not (track and box_radar):
-        raise RuntimeError(f"{fn}: captions: fps draws the closing speed, the rate of the tracker's filtered radar range; it needs "
-                           f"track= together with box_radar=True, and this pipeline lacks {'box_radar=True' if track else 'track='}")
-    atlas, size = captions.get("atlas"), rendering.label_font_size(ih)
-    if atlas is not None:
-        if not isinstance(atlas, rendering.GlyphAtlas) or captions.get("font") is not None or captions.get("sizes") is not None:
-            raise RuntimeError(f"{fn}: captions: atlas is a render.GlyphAtlas, which brings its own font and sizes")
-    elif not ragged and size == 0:
-        if captions.get("sizes") is not None:
-            raise RuntimeError(f"{fn}: captions: sizes belongs to a ragged pipeline; a fixed-size one builds font size {size}")
-        return True, float(fps), None
-    else:
-        sizes = captions.get("sizes")
-        if sizes is None:
-            sizes = tuple(range(1, size + 1)) if ragged else (size,)
-        elif not ragged:
-            raise RuntimeError(f"{fn}: captions: sizes belongs to a ragged pipeline; a fixed-size one builds font size {size}")
-        if not len(tuple(sizes)):
-            raise RuntimeError(f"{fn}: captions: a capacity of {ih} rows has no font size >= 1 to build")
-        atlas = rendering.GlyphAtlas(captions.get("font"), sizes)
-    if ragged:
-        return atlas, float(fps), None
-    return atlas, float(fps), None if size == 0 else atlas.size_index(size)
-
-
 def unmap_scalars(input_shape, image_shape, letterbox_image):
     """(offset, scale): the (y, x) float64 pairs with which decode.yolo_correct_boxes maps a centre, (c - offset) * scale, and a
     size, s * scale -- its own expressions, np.round included; (0, 0), (1, 1) without a letterbox."""
@@ -290,47 +198,24 @@ class FrameResult:
     is `class_map[b, :ih_b, :iw_b]` / `rendered[b, :ih_b, :iw_b]` with (ih_b, iw_b) = sizes[b], everything outside it is 0,
     and seg_counts[b] counts the image's own pixels only.  sizes: the (B, 2) host integers of that run (None from a
     fixed-size pipeline).
-    From a pipeline with heatmap=True (None otherwise): heat_mask (B, ih, iw) uint8, heat_picture (B, ih, iw, 3) uint8 and
-    heat_range (B, 2) int32 = each mask's (min, max), what `render.heatmap` returns for the frames and the raw detection
-    maps of the run; padded like class_map / rendered from a ragged pipeline.
-    From a pipeline built with crops (None otherwise): crops, the `render.Crops` of the run -- every kept detection cut out
-    of the original frame, `crops.images()[b][i]` being row i of image b.
-    From a pipeline built with chips (None otherwise): chips, the `render.Chips` of the run -- the same crops brought to one
-    size, `chips.chips[n]` (and `chips.chips_f32[n]`) being draw row n and `chips.images()[b][i]` row i of image b.
-    From a pipeline built with dehaze (None otherwise): dehazed (B, ih, iw, 3) uint8, the frames everything else of the
-    result was computed from; padded like rendered from a ragged pipeline.
-    From a pipeline built with ace (None otherwise): enhanced (B, ih, iw, 3) uint8, the output of the ACE stage, which then
-    is what everything else of the result was computed from (the stage reads the dehazed frames when both are on).
-    From a pipeline built with box_radar (None otherwise): box_points (B, cap) int32, the radar points inside each kept box,
-    and box_radar (B, cap, 2, 5) float32, (depth, f0, f1, f2, f3) of the nearest of them and of their lower median by depth
-    (`data.box_radar` is the rule), both zero from row kept[b] on; `radar_readout` brings them to the host.
-    From a pipeline built with track (None otherwise): track_ids (B, cap) int32, the id of the track each row matched or
-    started (0: none, and from row kept[b] on), track_table (B, T, 16) int32, the pipeline's own table of `data.TRACK_DTYPE`
-    records as words, and track_head (B, 4) int32 (ids handed out, live tracks, calls, births of this call) -- the state after
-    this run, which the next run updates in place; `tracks` brings them to the host.
-    From a pipeline built with captions (None otherwise): captions (B * cap, 12) int32, the caption records of the kept rows,
-    image b's from row `kept[:b].sum()` on (`render.caption_decode`); `caption_strings` brings them to the host.
-    From a pipeline built with regions (None otherwise): region_labels (B, ih, iw) int32, the id of the connected region of
-    every pixel of the class map (0: none; padded like class_map from a ragged pipeline), region_table (B, max_regions, 12)
-    int32, the records of `decode.REGION_DTYPE` as words, region_head (B, 4) int32 (regions, records in the table, pixels in
-    regions, pixels dropped by min_area) and box_regions (B, cap) int32, the region linked to each kept row (0: none, and from
-    row kept[b] on) -- `decode.seg_regions_host` is the rule; `regions` brings them to the host."""
-    __slots__ = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes", "heat_mask",
-                 "heat_picture", "heat_range", "crops", "dehazed", "enhanced", "box_points", "box_radar", "track_ids",
-                 "track_table", "track_head", "captions", "region_labels", "region_table", "region_head", "box_regions", "chips")
+    The optional fields, each None unless its stage is on (the stage class of `stages.py` says the rest): dehazed and enhanced
+    (B, ih, iw, 3) uint8, the frames everything else was computed from (`stages.Dehaze`, `stages.Ace`); crops, a
+    `render.Crops` (`stages.Crops`); chips, a `render.Chips` (`stages.Chips`); box_points (B, cap) int32 and box_radar (B, cap,
+    2, 5) float32 (`stages.BoxRadar`; `radar_readout`); track_ids (B, cap), track_table (B, T, 16) and track_head (B, 4) int32
+    (`stages.Track`; `tracks`); captions (B * cap, 12) int32 (`stages.Captions`; `caption_strings`); region_labels (B, ih, iw),
+    region_table (B, max_regions, 12), region_head (B, 4) and box_regions (B, cap) int32 (`stages.Regions`; `regions`);
+    heat_mask (B, ih, iw) uint8, heat_picture (B, ih, iw, 3) uint8 and heat_range (B, 2) int32 (`stages.Heatmap`).  The
+    constructor takes them as keywords."""
+    CORE = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes")
+    __slots__ = CORE + tuple(f for stage in STAGES for f in stage.fields)
 
-    def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, heat_mask=None,
-                 heat_picture=None, heat_range=None, crops=None, dehazed=None, enhanced=None, box_points=None, box_radar=None,
-                 track_ids=None, track_table=None, track_head=None, captions=None, region_labels=None, region_table=None,
-                 region_head=None, box_regions=None, chips=None):
-        self.chips = chips
-        self.region_labels, self.region_table, self.region_head, self.box_regions = region_labels, region_table, region_head, box_regions
-        self.track_ids, self.track_table, self.track_head, self.captions = track_ids, track_table, track_head, captions
+    def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, **fields):
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
         self.seg_counts, self.rendered, self.flag, self.sizes = seg_counts, rendered, flag, sizes
-        self.heat_mask, self.heat_picture, self.heat_range, self.crops = heat_mask, heat_picture, heat_range, crops
-        self.dehazed, self.enhanced = dehazed, enhanced
-        self.box_points, self.box_radar = box_points, box_radar
+        for name in self.__slots__[len(self.CORE):]:
+            setattr(self, name, fields.pop(name, None))
+        if fields:
+            raise TypeError(f"FrameResult: no such fields: {', '.join(sorted(fields))}")
 
     def detections(self):
         """The list `decode.non_max_suppression` returns: per image an (N_b, 7) float32 numpy array in the same order,
@@ -418,10 +303,7 @@ class FramePipeline:
     the host.  radar_dtype: the type of the static radar buffer; float64 maps are normalised in float64, as the reference
     normalises a float64 .npz, only in a float64 buffer.  render / mix_type / alpha / seg_palette / box_palette: the
     `render.render_frame` picture (seg overlay, box outlines of thickness yolo.py:164) and the per-class pixel counts;
-    default palettes `render.seg_palette(num_seg_classes)` and `render.det_palette(num_classes)`.  heatmap=True adds the
-    detection heat map of yolo.py:288-351 (`render.heatmap` on the raw detection maps and the frames, jet blended at
-    heat_alpha; aligned through the letterbox window when letterbox_image is set) to the chain and the result; with the
-    default nothing about the chain, the result or the graph changes.
+    default palettes `render.seg_palette(num_seg_classes)` and `render.det_palette(num_classes)`.
 
     graph=True warms the chain up (twice, on a side stream: workspaces and caches exist before the capture; the model's
     buffers are restored afterwards) and captures it as one hipGraph; run() then copies the inputs into the static
@@ -445,90 +327,11 @@ class FramePipeline:
     and ragged pipelines alike; the static inputs are then `points` (B, max_points, 7) and `views` (B, 80).  FLAG_POINT_COUNT
     (a count outside the buffer, which the host checks rule out) joins the bits of `flag`.
 
-    labels: None (the default: the chain, the graph and every byte as before), a `render.LabelAtlas`, or True together with
-    class_names= (one per detection class) and optionally font= (`render.LabelAtlas`: a TrueType path, a callable, or
-    None = Pillow's built-in face) -- the tag and '<class name> <score:.2f>' of yolo.py:210-224 on every rendered box.  Two
-    launches behind the render node: hip.label_index (the kept rows -> class * 101 + k) and the label renderer.  A fixed-size
-    pipeline builds the one font size `render.label_font_size(ih)` (0, below 17 rows: no labels); a ragged one builds every
-    size from 1 to label_font_size(ihm), or the sizes label_sizes= names, and sends the per-image size table up with the
-    geometry table; a frame whose size was not built raises in the host validation of `run`, before anything is enqueued.
-    FLAG_LABEL_SCORE joins the bits of `flag`.  labels needs render=True.
-
-    crops: None (the default: the chain, the graph and the result as before), True or the capacity of the crop arena in
-    pixels -- the `crop` switch of yolo.py:180-193: every kept detection is cut out of the ORIGINAL frame into a packed arena
-    on the device (`render.crop_boxes`; fixed-size and ragged pipelines alike) and `FrameResult.crops` is its `render.Crops`.
-    The arena, the table and the summary are allocated before the capture; the two launches of hip.crop_boxes sit right
-    behind the detect_finish node.  True means 2 * batch * ihm * iwm pixels: a cap the caller may change, not a measured
-    number -- 6 bytes per frame pixel, about 100 MB at batch 8 and 1080 x 1920.  Crops beyond the arena are dropped, a
-    prefix is kept, and FLAG_CROP_ARENA joins the bits of `flag`.
-
-    chips: None (the default: exactly the calls issued without it), a size (sh, sw) or a dict of size, letterbox and
-    normalised -- every kept detection cut out of the ORIGINAL frame and brought to one size with Pillow's BICUBIC
-    (`render.chip_boxes`, csrc/chips.hip; `render.chip_boxes_host` is the rule): one (batch * cap, sh, sw, 3) uint8 tensor of
-    equal-sized pictures for a second stage, chip n of draw row n, and with normalised its (batch * cap, 3, sh, sw) float
-    form; letterbox keeps the crop's aspect ratio on grey 128.  `FrameResult.chips` is its `render.Chips`.  Chips, table,
-    summary and workspace are allocated with the NMS buffers, before the capture; the two launches of hip.chip_boxes sit
-    directly behind the crop launches (behind the detect_finish node without crops), in front of hip.box_radar, and read the
-    frames the crops read -- the dehazed or ACE frames when those stages are on.  Chips behind the last row are not written.
-    Fixed-size and ragged pipelines alike; no new flag bit.
-
-    dehaze: None (the default: exactly the calls issued without it), True or a dict of the keywords sz, r, eps, omega, tx of
-    `render.dehaze_host` -- dark-channel-prior dehazing of the raw frames (`render.dehaze`, csrc/dehaze.hip) as the first
-    stage: the eleven launches of hip.dehaze sit in front of the letterbox node, and the letterbox, `render_frame`, the heat
-    map, the labels and the crops all read the dehazed frames, which are `FrameResult.dehazed`.  The workspace (seven
-    float64 planes of batch * ihm * iwm, `hip.dehaze_workspace_bytes`) and the second frame buffer are allocated before the
-    capture.  Fixed-size and ragged pipelines alike; a frame too small for the box (r // 2 > min(ih, iw) - 1) raises on the
-    host, in the constructor or in the validation of `run`; an image without atmospheric light (a black one, or one below
-    2000 pixels) goes on unchanged and FLAG_DEHAZE joins the bits of `flag`.
-
-    ace: None (the default: exactly the calls issued without it), True or a dict of the keywords ratio, radius, s, bins of
-    `render.ace_host` -- the fast Automatic Colour Equalisation of the reference's sharpen.py, its de-rain enhancement
-    (`render.ace`, csrc/ace.hip): the launches of hip.ace sit in front of the letterbox node, behind those of hip.dehaze when
-    both are on (ACE then reads the dehazed frames), and everything downstream reads its output, `FrameResult.enhanced`.  The
-    buffer, the weights table and the workspace (`hip.ace_workspace_bytes`, about 40 bytes per frame pixel) are allocated
-    before the capture.  Fixed-size and ragged pipelines alike; a degenerate image (min(ih, iw) <= 2, or a constant R_0)
-    goes on unchanged and FLAG_ACE joins the bits of `flag`.
-
-    box_radar: None (the default: exactly the calls issued without it) or True, in a pipeline built with radar_points -- the
-    radar readout of every kept detection (`data.box_radar`, csrc/boxradar.hip): how many of the image's radar points lie in
-    the box, and depth and features of the nearest of them and of their lower median by depth, as `FrameResult.box_points`
-    and `FrameResult.box_radar`.  The two launches of hip.box_radar sit behind the detect_finish node (behind the crop
-    launches when crops is on) and read the static `points` and `views` and the rows of the result, with radar_min_depth;
-    box_shrink in (0, 1] scales every box about its centre first.  Outputs and workspace are allocated before the capture.
-    Fixed-size and ragged pipelines alike, with and without letterbox_image: rows and projected points both live in the
-    original frame.
-
-    track: None (the default: exactly the calls issued without it), True or a dict of `data.check_track_params` (max_tracks,
-    iou, max_age, gain, range_gain) -- multi-object tracking of the kept detections on the device (`data.track_update`,
-    csrc/track.hip).  Every batch slot b becomes a STREAM: successive runs bring successive frames of camera b.  A table of
-    max_tracks tracks per stream lives in device memory across the runs (and the replays of the graph); the one launch of
-    hip.track_update behind hip.box_radar -- behind the crops or the finish node without it -- and in front of the seg node
-    predicts, matches greedily by IoU within a class, filters box and rates, and with box_radar the range and its rate from
-    the lower-median depth of the readout, coasts, frees and starts tracks, and writes `FrameResult.track_ids`.  Table, header
-    and ids are allocated before the capture and zeroed after the warm-up, which runs the chain; `reset_tracks` zeroes them
-    again.  Rates are per call: a stream must be fed at a constant frame rate.  Fixed-size and ragged pipelines alike.
-
-    captions: None (the default: exactly the calls issued without it), True, a `render.GlyphAtlas`, or a dict of atlas, fps,
-    font and sizes -- a second tag UNDER every rendered box, '#<track id> <range>m <closing speed>m/s' such as
-    '#17 42.5m -1.2m/s' (`render.caption_strings` and `render.draw_captions_host` are the rule, csrc/captions.hip the
-    kernels).  It needs render=True and at least one of track and box_radar: the id comes from the tracker, the range from the
-    track's filtered range (with a tracker) or the lower-median depth of the readout (without one).  fps (default 0: no
-    speed field) is the frame rate the streams are fed at, which turns the tracker's per-call range rate into metres per
-    second; it needs track with box_radar.  font: as `render.GlyphAtlas` takes it.  A fixed-size pipeline builds the one font
-    size `render.label_font_size(ih)` (0, below 17 rows: the text is composed, nothing is drawn); a ragged one builds every
-    size from 1 to label_font_size(ihm), or those sizes= names, and a frame whose size was not built raises in the host
-    validation of `run`, before anything is enqueued.  Two launches: hip.caption_text behind hip.track_update (behind
-    hip.box_radar without a tracker) and hip.render_captions behind the label launches (behind the render node without
-    labels); the records, `FrameResult.captions`, are allocated before the capture.  FLAG_CAPTION joins the bits of `flag`.
-
-    regions: None (the default: exactly the calls issued without it), True or a dict of `decode.check_region_params`
-    (connectivity, background, min_area, max_regions, det_to_seg -- one seg class per detection class of the model) -- the
-    connected regions of the class map (`decode.seg_regions_host`, csrc/regions.hip): how many separate vessels or piers the
-    class map holds, each one's class, area, bounding box and exact coordinate sums, and which kept row belongs to which of
-    them, as `FrameResult.region_labels`, `region_table`, `region_head` and `box_regions`.  The seven launches of
-    hip.seg_regions sit directly behind the seg node and in front of the render node and read the class map and the draw rows
-    of the result.  Outputs and workspace (8 bytes per pixel of the batch) are allocated before the capture.  Fixed-size and
-    ragged pipelines alike, with and without letterbox_image.  FLAG_REGIONS joins the bits of `flag`."""
+    The optional stages, each documented on its class of `stages.py`, in launch order: dehaze= (`stages.Dehaze`), ace=
+    (`Ace`), crops= (`Crops`), chips= (`Chips`), box_radar= / box_shrink= (`BoxRadar`), track= (`Track`), captions=
+    (`Captions`), regions= (`Regions`), labels= / class_names= / font= / label_sizes= (`Labels`), heatmap= / heat_alpha=
+    (`Heatmap`).  With its default a stage changes nothing about the chain, the graph or the result.  `stages` holds those
+    that are on; the attribute of each keyword's name holds its checked parameters (`crop_capacity` for crops=)."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
                  max_candidates=1024, normalise_radar=False, render=True, mix_type=0, alpha=0.7, seg_palette=None,
@@ -538,18 +341,7 @@ class FramePipeline:
                  captions=None, regions=None, chips=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
-        self.chips = chip_config(chips)
-        self.regions = None
-        if regions is not None and regions is not False:
-            from .decode import check_region_params
-            self.regions = check_region_params(regions, "FramePipeline", num_classes=int(model.num_classes))
-        self.track = None if track is None or track is False else data.check_track_params(track, "FramePipeline")
-        self.crop_capacity = crop_capacity(crops, self.batch, self.frame_shape)
-        self.dehaze = dehaze_config(dehaze)
-        if self.dehaze is not None and not rendering.dehaze_size_ok(*self.frame_shape, self.dehaze["r"]):
-            raise RuntimeError(f"FramePipeline: frames of {self.frame_shape[0]} x {self.frame_shape[1]} allow no single reflection "
-                               f"of the dehazing box r = {self.dehaze['r']}")
-        self.ace = ace_config(ace)
+        self.model, self.render, self.ragged = model, bool(render), bool(ragged)
         self.radar_points = None
         if radar_points is not None:
             if radar_dtype != torch.float32:
@@ -557,27 +349,16 @@ class FramePipeline:
             self.radar_points = RadarPoints(radar_points, radar_radius, radar_min_depth, calib, self.batch)
         elif calib is not None or radar_radius != 0 or radar_min_depth != 0.1:
             raise RuntimeError("FramePipeline: calib, radar_radius and radar_min_depth belong to radar_points=max_points")
-        self.box_radar = bool(box_radar)
-        if self.box_radar:
-            if self.radar_points is None:
-                raise RuntimeError("FramePipeline: box_radar reads the radar POINTS of a pipeline built with radar_points=max_points; "
-                                   "this one takes finished maps")
-            self.box_shrink = float(data.check_box_shrink(box_shrink, "FramePipeline"))
-        elif isinstance(box_shrink, bool) or box_shrink != 1.0:
-            raise RuntimeError("FramePipeline: box_shrink belongs to box_radar=True")
-        self.captions, self.caption_fps, self.caption_size_index = caption_config(
-            captions, bool(render), self.track is not None, self.box_radar, bool(ragged), self.frame_shape[0])
-        self.caption_size_tab = None
+        kw = dict(dehaze=dehaze, ace=ace, crops=crops, chips=chips, box_radar=box_radar, box_shrink=box_shrink, track=track,
+                  captions=captions, regions=regions, labels=labels, class_names=class_names, font=font, label_sizes=label_sizes,
+                  heatmap=heatmap, heat_alpha=heat_alpha)
+        self.stages = self._parse(kw, early=True)         # the keyword checks that need no device
         if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
             raise RuntimeError(f"FramePipeline: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
-        if not 0.0 <= float(heat_alpha) <= 1.0:
-            raise RuntimeError(f"FramePipeline: heat_alpha must lie in [0, 1], got {heat_alpha!r}")
-        self.heatmap, self.heat_alpha = bool(heatmap), float(heat_alpha)
         if radar_dtype not in (torch.float32, torch.float64) or (radar_dtype == torch.float64 and not normalise_radar):
             raise RuntimeError("FramePipeline: radar_dtype is float32, or float64 together with normalise_radar")
-        self.model = model
         self.conf_thres, self.nms_thres, self.letterbox_image = float(conf_thres), float(nms_thres), bool(letterbox_image)
-        self.normalise_radar, self.render, self.mix_type, self.alpha = bool(normalise_radar), bool(render), mix_type, float(alpha)
+        self.normalise_radar, self.mix_type, self.alpha = bool(normalise_radar), mix_type, float(alpha)
         p = next(model.parameters(), None)
         if p is None or not p.is_cuda:
             raise RuntimeError("FramePipeline: the model must be on a HIP device (there is no CPU fallback)")
@@ -592,7 +373,7 @@ class FramePipeline:
         self.frames_u8 = torch.zeros((B, ih, iw, 3), dtype=torch.uint8, device=dev)
         self.radar = torch.zeros((B, 4, H, W), dtype=radar_dtype, device=dev)
         self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.ragged, self.sizes, self.label_size_tab = bool(ragged), None, None
+        self.sizes = None
         if self.ragged:                       # the warm-up and the capture run on a table of frames that fill their slots
             self.max_taps = data.default_max_taps(self.frame_shape, self.input_shape) if max_taps is None else int(max_taps)
             table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, self.frame_shape,
@@ -609,72 +390,23 @@ class FramePipeline:
             table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, fn="FramePipeline")
             self.points, self.views = self.radar_points.buffers(table, dev)
             self._radar_ws = self.radar_points.workspace(self.input_shape, dev)
-        self.labels = self._label_atlas(labels, class_names, font, label_sizes)
-        if self.captions is not None and self.ragged:      # the warm-up and the capture run on frames that fill their slots
-            size = rendering.label_font_size(ih)
-            tab = np.full(B, self.captions.size_index(size) if size in self.captions.sizes else -1, np.int32)
-            self.caption_size_tab = torch.from_numpy(tab).to(dev)
-        if self.dehaze is not None:           # before the capture: the second frame buffer and the workspace
-            from . import hip
-            self._dehazed = torch.zeros_like(self.frames_u8)
-            self._dehaze_ws = torch.empty(hip.dehaze_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
-        if self.ace is not None:              # before the capture: the stage's output, its weights table and its workspace
-            from . import hip
-            self._enhanced = torch.zeros_like(self.frames_u8)
-            self._ace_weights = torch.from_numpy(rendering.ace_weights(self.ace["radius"])).to(dev)
-            self._ace_ws = torch.empty(hip.ace_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
+        self.stages = sorted(self.stages + self._parse(kw, early=False), key=lambda s: STAGES.index(type(s)))
+        from . import hip
+        for s in self.stages:                 # before the capture: what follows from the frame shape alone
+            s.static(self, hip)
         self.cap = None                       # the NMS buffers follow the anchor count of the first (warm-up) pass
         self.graph = self.result = None
         if graph:
             self._capture()
         else:
             self._warm_up(1)
-        if self.track is not None:            # the warm-up and the capture ran the chain on zero input: back to the reset state
-            self.reset_tracks()
+        for s in self.stages:                 # the warm-up and the capture ran the chain on zero input
+            s.ready(self)
 
-    def _label_atlas(self, labels, class_names, font, label_sizes):
-        """The atlas of the constructor's labels / class_names / font / label_sizes (None without labels), and the static
-        size tables: `label_size_index` of a fixed-size pipeline (None: font size 0), `label_size_tab` (B) of a ragged one."""
-        fn = "FramePipeline"
-        if labels is None or labels is False:
-            if class_names is not None or font is not None or label_sizes is not None:
-                raise RuntimeError(f"{fn}: class_names, font and label_sizes belong to labels=")
-            return None
-        if not self.render:
-            raise RuntimeError(f"{fn}: labels are drawn on the rendered frame; they need render=True")
-        size = rendering.label_font_size(self.frame_shape[0])
-        if labels is True:
-            if class_names is None or len(class_names) != self.num_classes:
-                raise RuntimeError(f"{fn}: labels=True needs class_names, one per detection class ({self.num_classes})")
-            if label_sizes is None:
-                label_sizes = tuple(range(1, size + 1)) if self.ragged else (size,)
-            elif not self.ragged:
-                raise RuntimeError(f"{fn}: label_sizes belongs to a ragged pipeline; a fixed-size one builds font size {size}")
-            if not self.ragged and size == 0:
-                atlas = None                  # frames lower than 17 rows: the outlines alone
-            else:
-                if not len(tuple(label_sizes)):
-                    raise RuntimeError(f"{fn}: a capacity of {self.frame_shape[0]} rows has no font size >= 1 to build")
-                atlas = rendering.LabelAtlas(class_names, font, label_sizes)
-        elif isinstance(labels, rendering.LabelAtlas):
-            if class_names is not None or font is not None or label_sizes is not None:
-                raise RuntimeError(f"{fn}: class_names, font and label_sizes belong to labels=True; an atlas brings its own")
-            atlas = labels
-            if atlas.num_classes != self.num_classes:
-                raise RuntimeError(f"{fn}: the atlas has {atlas.num_classes} classes, the model {self.num_classes}")
-        else:
-            raise RuntimeError(f"{fn}: labels is None, True or a render.LabelAtlas, got {type(labels).__name__}")
-        if self.box_palette.shape[0] != self.num_classes:
-            raise RuntimeError(f"{fn}: labels need a box palette of one colour per class ({self.num_classes}), got "
-                               f"{self.box_palette.shape[0]}")
-        if self.ragged:                       # the warm-up and the capture run on frames that fill their slots
-            tab = np.full(self.batch, atlas.size_index(size) if size in atlas.sizes else -1, np.int32)
-            self.label_size_tab = torch.from_numpy(tab).to(self.device)
-        else:
-            self.label_size_index = None if size == 0 else atlas.size_index(size)
-            if self.label_size_index is None:
-                return None
-        return atlas
+    def _parse(self, kw, early):
+        """The stages of STAGES whose keyword checks run in front of (early) or behind the device check, those that are on."""
+        found = [cls.parse(self, kw) for cls in STAGES if cls.early == early]
+        return [s for s in found if s is not None]
 
     def _allocate(self, anchors):
         from . import hip
@@ -689,66 +421,37 @@ class FramePipeline:
         self._kept_rows, self._rows = torch.empty((B, cap, 7), device=dev), torch.empty((B, cap, 7), device=dev)
         self._draw_rows, self._offsets = torch.empty((B * cap, 5), **i32), torch.empty(B + 1, **i32)
         self._det_counts = torch.empty((B, self.num_classes), dtype=torch.int64, device=dev)
-        if self.labels is not None:
-            self._label_idx = torch.zeros(B * cap, **i32)
-        self._crops = None
-        if self.crop_capacity is not None:
-            self._crops = rendering.crop_buffers(B * cap, self.crop_capacity, B, self.flag, dev)
-        self._chips = None
-        if self.chips is not None:            # before the capture: chips, table, summary and the tap tables
-            self._chips = rendering.chip_buffers(B * cap, self.chips["size"], B, self.chips["letterbox"],
-                                                 self.chips["normalised"], self.flag, dev)
-        self._box_points = self._box_radar = None
-        if self.box_radar:                    # before the capture: the two outputs and the projected points
-            self._box_points, self._box_radar = torch.zeros((B, cap), **i32), torch.zeros((B, cap, 2, 5), device=dev)
-            self._box_ws = torch.empty(hip.box_radar_workspace_bytes(B, self.radar_points.max_points), dtype=torch.uint8, device=dev)
-        self._track_table = self._track_head = self._track_ids = None
-        if self.track is not None:            # before the capture: the state of every stream and the ids of the rows
-            if cap > data.TRACK_MAX_ROWS:
-                raise RuntimeError(f"FramePipeline: track takes at most {data.TRACK_MAX_ROWS} rows an image, max_candidates gives {cap}")
-            self._track_table = torch.zeros((B, self.track["max_tracks"], hip.TRACK_WORDS), **i32)
-            self._track_head, self._track_ids = torch.zeros((B, hip.TRACK_HEAD), **i32), torch.zeros((B, cap), **i32)
-        self._captions = None
-        if self.captions is not None:         # before the capture: one record per draw row
-            self._captions = torch.zeros((B * cap, hip.CAPTION_WORDS), **i32)
-        self._region_labels = self._region_table = self._region_head = self._box_regions = None
-        if self.regions is not None:          # before the capture: the four outputs, the gate and the workspace
-            ih, iw = self.frame_shape
-            self._region_labels = torch.zeros((B, ih, iw), **i32)
-            self._region_table = torch.zeros((B, self.regions["max_regions"], hip.REGION_WORDS), **i32)
-            self._region_head, self._box_regions = torch.zeros((B, hip.REGION_HEAD), **i32), torch.zeros((B, cap), **i32)
-            gate = self.regions["det_to_seg"]
-            self._region_gate = None if gate is None else torch.tensor(gate, **i32)
-            self._region_ws = torch.empty(hip.seg_regions_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
+        for s in self.stages:                 # before the capture: what the stages keep per row
+            s.allocate(self, hip, cap)
+
+    def _at(self, point, c):
+        """The launches of the stages at one hook point of the chain, in the order of STAGES."""
+        for s in self.stages:
+            getattr(s, point)(self, c)
 
     def _chain(self):
         """The chain of the module docstring.  A ragged pipeline reads the geometry of every image from `self.geom` on the
         device where a fixed one passes it in the launch arguments: every frame op takes either (`hip._table_call`), so the two
         chains are one but for the letterbox, which a fixed pipeline runs through `data.device_letterbox`, and for the
-        stretched frame of a fixed pipeline without a letterbox, whose seg window is the whole input."""
+        stretched frame of a fixed pipeline without a letterbox, whose seg window is the whole input.  c is the context the
+        stages' hooks read and write (`stages.Stage`)."""
         from . import decode, hip            # the library loads with the first pass, not with the package
         (H, W), F, B, dev = self.input_shape, self.frame_shape, self.batch, self.device
-        geom = self.geom if self.ragged else None
+        c = SimpleNamespace(hip=hip, geom=self.geom if self.ragged else None, frames=self.frames_u8, out={}, labels=None,
+                            label_sizes=None, rendered=None)
         self.flag.zero_()                     # first: the ragged letterbox may raise FLAG_GEOMETRY
-        frames = self.frames_u8
-        if self.dehaze is not None:           # in front of the letterbox: everything below reads the dehazed frames
-            frames = self._dehazed
-            hip.dehaze(self.frames_u8, frames, self._dehaze_ws, geom=geom, flag=self.flag, **self.dehaze)
-        dehazed = frames if self.dehaze is not None else None
-        if self.ace is not None:              # behind the dehazing, in front of the letterbox
-            hip.ace(frames, self._enhanced, self._ace_ws, self._ace_weights, geom=geom, flag=self.flag, **self.ace)
-            frames = self._enhanced
+        self._at("frames", c)
         if self.ragged:
             images = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-            hip.letterbox(frames, None, H, W, images=images, geom=geom, max_taps=self.max_taps, flag=self.flag)
+            hip.letterbox(c.frames, None, H, W, images=images, geom=c.geom, max_taps=self.max_taps, flag=self.flag)
         else:
-            images, _ = data.device_letterbox(frames, (H, W), letterbox_image=self.letterbox_image, device=dev)
+            images, _ = data.device_letterbox(c.frames, (H, W), letterbox_image=self.letterbox_image, device=dev)
         if self.radar_points is not None:     # the first radar node: points -> self.radar under each frame's window
             hip.radar_map(self.points, self.views, H, W, self.radar_points.radius, float(self.radar_points.min_depth), self.radar,
                           flag=self.flag, ws=self._radar_ws)
         radar = data.device_radar(self.radar, True, dev) if self.normalise_radar else self.radar
-        det, seg = self.model(images, radar)
-        pred = decode.decode_outputs(det, (H, W))
+        c.det, seg = self.model(images, radar)
+        pred = decode.decode_outputs(c.det, (H, W))
         if self.cap is None:
             self._allocate(pred.shape[1])
         rows, scores, classes, ids, counts = self._cand
@@ -756,56 +459,24 @@ class FramePipeline:
         hip.nms_capped(rows, scores, classes, ids, counts, B, pred.shape[1], self.cap, self.nms_thres, self._nms_ws,
                        self._keep, self._kept, self._kept_rows, self.flag)
         hip.detect_finish(self._kept_rows, self._kept, self.num_classes, self.image_shape, self.offset, self.scale, self._rows,
-                          self._draw_rows, self._offsets, self._det_counts, self.flag, geom=geom, capacity=self._slots)
-        if self._crops is not None:           # right behind the finish node: from the original frames, which nothing draws on
-            hip.crop_boxes(frames, self._draw_rows, self._offsets, self._crops.arena, self._crops.table,
-                           self._crops.summary, geom=geom, flag=self.flag)
-        if self._chips is not None:           # directly behind the crops: the same rows of the same frames, at one size
-            hip.chip_boxes(frames, self._draw_rows, self._offsets, self._chips.chips, self._chips.table, self._chips.summary,
-                           self._chips.workspace, letterbox=self._chips.letterbox, chips_f32=self._chips.chips_f32, geom=geom,
-                           flag=self.flag)
-        if self.box_radar:                    # behind the finish node (and the crops): rows and points share the original frame
-            hip.box_radar(self.points, self.views, self._rows, self._kept, float(self.radar_points.min_depth), self.box_shrink,
-                          self._box_points, self._box_radar, flag=self.flag, ws=self._box_ws)
-        if self.track is not None:            # behind the readout, in front of the seg node: the state is updated in place
-            hip.track_update(self._rows, self._kept, self._track_table, self._track_head, self._track_ids, self.track,
-                             box_points=self._box_points, box_radar=self._box_radar, flag=self.flag)
-        if self.captions is not None:         # behind the tracker (or the readout): the text of every kept row
-            hip.caption_text(self._kept, self._offsets, self._captions, ids=self._track_ids, table=self._track_table,
-                             box_points=self._box_points, box_radar=self._box_radar, rate_scale=self.caption_fps, flag=self.flag)
+                          self._draw_rows, self._offsets, self._det_counts, self.flag, geom=c.geom, capacity=self._slots)
+        self._at("rows", c)
         if self.ragged or self.letterbox_image:
-            class_map = decode.seg_predict(seg, (H, W), self.image_shape, geom=geom, capacity=self._slots, flag=self.flag)
+            c.class_map = decode.seg_predict(seg, (H, W), self.image_shape, geom=c.geom, capacity=self._slots, flag=self.flag)
         else:                                 # the frame was stretched over the whole input: the window is the input
-            class_map = torch.empty((B,) + F, dtype=torch.uint8, device=dev)
+            c.class_map = torch.empty((B,) + F, dtype=torch.uint8, device=dev)
             ws = torch.empty(hip.seg_predict_workspace_bytes(B, seg.shape[1], H, W), dtype=torch.uint8, device=dev)
-            hip.seg_predict(seg.contiguous().float(), 0, 0, H, W, class_map, ws)
-        if self.regions is not None:          # directly behind the seg node, in front of the render node
-            hip.seg_regions(class_map, self._draw_rows, self._offsets, self._region_labels, self._region_table, self._region_head,
-                            self._box_regions, self._region_ws, self.regions["connectivity"], self.regions["background"],
-                            self.regions["min_area"], det_to_seg=self._region_gate, geom=geom, flag=self.flag)
-        rendered = seg_counts = None
+            hip.seg_predict(seg.contiguous().float(), 0, 0, H, W, c.class_map, ws)
+        c.boxes = (self._draw_rows, self._offsets)
+        self._at("class_map", c)
+        seg_counts = None
         if self.render:
-            boxes = (self._draw_rows, self._offsets)
-            if self.labels is not None:       # the two label launches sit behind the render node
-                hip.label_index(self._rows, self._kept, self._offsets, self.num_classes, self._label_idx, self.flag)
-                boxes += (self._label_idx,)
-            rendered, seg_counts = rendering.render_frame(
-                frames, class_map, boxes, palette=self.seg_palette, mix_type=self.mix_type, alpha=self.alpha, count=True,
-                box_palette=self.box_palette, thickness=self.thickness, flag=self.flag, device=dev, labels=self.labels, geom=geom,
-                label_sizes=self.label_size_tab)
-            size = self.caption_size_tab if self.ragged else self.caption_size_index
-            if self.captions is not None and size is not None:      # behind the label launches: a pass over the finished picture
-                hip.render_captions(rendered, self._draw_rows, self._offsets, self.box_palette, self._captions,
-                                    *self.captions.on(dev), size, flag=self.flag, geom=geom)
-        result = FrameResult(self._rows, self._kept, self._det_counts, class_map, seg_counts, rendered, self.flag, crops=self._crops,
-                             dehazed=dehazed, enhanced=frames if self.ace is not None else None, box_points=self._box_points,
-                             box_radar=self._box_radar, track_ids=self._track_ids, track_table=self._track_table,
-                             track_head=self._track_head, captions=self._captions, region_labels=self._region_labels,
-                             region_table=self._region_table, region_head=self._region_head, box_regions=self._box_regions,
-                             chips=self._chips)
-        if self.heatmap:
-            result.heat_picture, result.heat_mask, result.heat_range = rendering.heatmap(
-                frames, det, (H, W), alpha=self.heat_alpha, geom=geom, flag=self.flag, **self._heat_window)
+            c.rendered, seg_counts = rendering.render_frame(
+                c.frames, c.class_map, c.boxes, palette=self.seg_palette, mix_type=self.mix_type, alpha=self.alpha, count=True,
+                box_palette=self.box_palette, thickness=self.thickness, flag=self.flag, device=dev, labels=c.labels, geom=c.geom,
+                label_sizes=c.label_sizes)
+        self._at("picture", c)
+        result = FrameResult(self._rows, self._kept, self._det_counts, c.class_map, seg_counts, c.rendered, self.flag, **c.out)
         self._tail(result)
         return result
 
@@ -874,29 +545,19 @@ class FramePipeline:
             return self._launch(f, r)
         checked = validate_ragged_inputs(frames_u8, radar, sizes, self.batch, self.frame_shape, self.input_shape,
                                          self.letterbox_image, self.max_taps, self.radar_points, calib)
-        if self.dehaze is not None:           # a frame too small for the box raises here, before anything is enqueued
-            for b, (h, w) in enumerate(np.asarray(checked[2]).tolist()):
-                if not rendering.dehaze_size_ok(h, w, self.dehaze["r"]):
-                    raise RuntimeError(f"FramePipeline: image {b}: {h} x {w} allows no single reflection of the dehazing box "
-                                       f"r = {self.dehaze['r']}")
-        label_tab = None
-        if self.labels is not None:           # a frame whose font size was not built raises here, before anything is enqueued
-            label_tab = self.labels.size_table([int(s[0]) for s in checked[2]], "FramePipeline")
-        caption_tab = None
-        if self.captions is not None:         # the same for the glyph sizes
-            caption_tab = self.captions.size_table([int(s[0]) for s in checked[2]], "FramePipeline")
-        return self._launch(*checked, label_tab=label_tab, caption_tab=caption_tab)
+        # a frame a stage cannot take raises here, before anything is enqueued; the stages' per-image tables follow the geometry
+        tables = [pair for s in self.stages for pair in s.check(self, checked[2])]
+        return self._launch(*checked, tables=tables)
 
-    def _launch(self, f, r, sizes=None, table=None, label_tab=None, caption_tab=None):
-        """The copies and the replay of `run`, on inputs that `validate_inputs` / `validate_ragged_inputs` returned."""
+    def _launch(self, f, r, sizes=None, table=None, tables=()):
+        """The copies and the replay of `run`, on inputs that `validate_inputs` / `validate_ragged_inputs` returned; tables: the
+        (device table, host array) pairs of the stages' `check`."""
         with torch.cuda.device(self.device):
             if self.ragged:
                 data.fill_slots(self.frames_u8, f, sizes)
                 self.geom.copy_(data.geometry_bytes(table), non_blocking=True)
-                if label_tab is not None:
-                    self.label_size_tab.copy_(torch.from_numpy(label_tab).pin_memory(), non_blocking=True)
-                if caption_tab is not None:
-                    self.caption_size_tab.copy_(torch.from_numpy(caption_tab).pin_memory(), non_blocking=True)
+                for dst, host in tables:
+                    dst.copy_(torch.from_numpy(host).pin_memory(), non_blocking=True)
                 self.sizes = sizes
             else:
                 self.frames_u8.copy_(f, non_blocking=True)
@@ -914,23 +575,6 @@ class FramePipeline:
         return self.result
 
 
-def radar_text(detections, readout):
-    """The <stem>_radar.txt of `predict_dir` for one picture: detections (N, 7) as `FrameResult.detections` gives them and
-    readout (N, 11) as `FrameResult.radar_readout` does -> one line per detection, space-separated: the class as an integer,
-    the score obj * class_conf (the float32 product), left top right bottom, the points inside the box as an integer, then
-    depth f0 f1 f2 f3 of the nearest point and of the lower median; every float as %.9g, which names a float32 exactly."""
-    detections, readout = np.asarray(detections, np.float32), np.asarray(readout, np.float32)
-    if detections.ndim != 2 or detections.shape[1] != 7 or readout.shape != (len(detections), 11):
-        raise RuntimeError(f"radar_text: expected (N, 7) detections and (N, 11) readout rows, got {detections.shape} and {readout.shape}")
-    lines = []
-    for d, r in zip(detections, readout):
-        top, left, bottom, right = d[:4]
-        floats = [d[4] * d[5], left, top, right, bottom]
-        lines.append(" ".join([str(int(d[6]))] + ["%.9g" % float(v) for v in floats] + [str(int(r[0]))] +
-                              ["%.9g" % float(v) for v in r[1:]]) + "\n")
-    return "".join(lines)
-
-
 def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     """predict.py's `dir_predict` mode on a ragged pipeline: every picture of the folder dir_origin_path whose name ends in
     one of IMAGE_EXTENSIONS (the reference's filter, lower case), in sorted order, with its radar maps
@@ -939,47 +583,30 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     final partial batch is filled by repeating the last picture; the repeats are dropped here.  Returns a list of
     (file name, (N, 7) detections) in that order; with dir_save_path the rendered frame of every picture, sliced to its own
     size, is saved there as <stem>.png through Pillow (the reference renames .jpg to .png; here every picture is a PNG), and
-    from a pipeline with heatmap=True its heat picture as <stem>_heat.png beside it.  From a pipeline built with crops every
-    non-empty crop the arena kept is saved as dir_save_path/img_crop/<stem>_crop_<i>.png, i being the row's index within its
-    picture (the `i` of yolo.py:180-193); the crops of the repeated fill pictures are dropped with the repeats.  The reference
-    writes img_crop/crop_<i>.png and so overwrites the crops of one picture with those of the next: the stem in the name is a
-    deliberate departure.  From a pipeline built with chips every chip is saved as dir_save_path/img_chip/<stem>_chip_<i>.png,
-    with the same i (the grey chip of an empty crop included, so that i stays the row's index).  From a pipeline built with
-    dehaze the dehazed frame is saved as <stem>_dehaze.png, from one built
-    with ace the enhanced frame as <stem>_ace.png, from one built with box_radar the radar readout of the picture's
-    detections as <stem>_radar.txt (`radar_text`).  Two pictures that would share one output name (names that differ only in
-    their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on, or `a_dehaze.jpg` with dehazing on, or `a_ace.jpg`
-    with ACE on, or `a_radar.jpg` with the readout on, or `a_tracks.jpg` with tracking on, or `a_regions.jpg` with regions
-    on): with dir_save_path that raises before anything runs.  From a pipeline built with regions the records of the picture's
-    connected regions are saved as <stem>_regions.txt (`decode.region_text`).  A pipeline built with track must have batch 1 -- the folder then is ONE sequence in its sorted
-    order, fed to stream 0 of the pipeline as it stands (call `reset_tracks` first for a fresh sequence), and the live tracks
-    after every picture are saved as <stem>_tracks.txt (`data.track_text`); with batch > 1 neighbouring files would land in
-    different streams, which raises before anything runs."""
+    every stage of the pipeline saves its own beside it -- <stem>_heat.png, <stem>_dehaze.png, <stem>_ace.png,
+    <stem>_radar.txt, <stem>_tracks.txt, <stem>_regions.txt, img_crop/<stem>_crop_<i>.png, img_chip/<stem>_chip_<i>.png: see
+    the stage classes of `stages.py`; what belongs to the repeated fill pictures is dropped with the repeats.  Each stage
+    reads its part of a batch back once, and nothing is read back without dir_save_path.  Two pictures that would share one
+    output name (names that differ only in their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on, and so for
+    every suffix a stage claims): with dir_save_path that raises before anything runs.  A pipeline built with track must
+    have batch 1 (`stages.Track`), which raises before anything runs too.  A pipeline without `stages` has none."""
     from PIL import Image
     if not getattr(pipeline, "ragged", False):
         raise RuntimeError("predict_dir: needs a ragged pipeline (FramePipeline(..., ragged=True)): a folder holds pictures of any size")
-    tracking = getattr(pipeline, "track", None) is not None
-    if tracking and pipeline.batch != 1:
-        raise RuntimeError(f"predict_dir: a tracking pipeline reads the folder as one sequence and needs batch 1, got batch "
-                           f"{pipeline.batch}: neighbouring pictures would land in different streams")
+    stages = getattr(pipeline, "stages", ())
+    for s in stages:
+        s.folder(pipeline)
     names = sorted(n for n in os.listdir(dir_origin_path) if n.lower().endswith(IMAGE_EXTENSIONS))
     if dir_save_path is not None:
-        stems = {}
+        owner = {}
         for n in names:
             stem = os.path.splitext(n)[0]
-            targets = (stem,) + ((stem + "_heat",) if getattr(pipeline, "heatmap", False) else ()) + \
-                ((stem + "_dehaze",) if getattr(pipeline, "dehaze", None) is not None else ()) + \
-                ((stem + "_ace",) if getattr(pipeline, "ace", None) is not None else ()) + \
-                ((stem + "_radar",) if getattr(pipeline, "box_radar", False) else ()) + \
-                ((stem + "_tracks",) if tracking else ()) + \
-                ((stem + "_regions",) if getattr(pipeline, "regions", None) is not None else ())
-            for target in targets:
-                other = stems.setdefault(target, n)
+            for target in [stem] + [stem + suffix for s in stages for suffix in s.claims]:
+                other = owner.setdefault(target, n)
                 if other != n:
                     raise RuntimeError(f"predict_dir: {other} and {n} would both be saved as {target}.png")
-    B, out = pipeline.batch, []
-    if dir_save_path is not None:
         os.makedirs(dir_save_path, exist_ok=True)
+    B, out = pipeline.batch, []
     for k in range(0, len(names), B):
         chunk = names[k:k + B]
         frames = [np.array(Image.open(os.path.join(dir_origin_path, n)).convert("RGB"), dtype=np.uint8) for n in chunk]
@@ -990,46 +617,16 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
         else:
             result = pipeline.run(frames + frames[-1:] * fill, np.stack(radar + radar[-1:] * fill))
         dets = result.detections()
-        rendered = None if dir_save_path is None or result.rendered is None else result.rendered.cpu().numpy()
-        heat = None if dir_save_path is None else getattr(result, "heat_picture", None)
-        heat = None if heat is None else heat.cpu().numpy()
-        dehazed = None if dir_save_path is None else getattr(result, "dehazed", None)
-        dehazed = None if dehazed is None else dehazed.cpu().numpy()
-        enhanced = None if dir_save_path is None else getattr(result, "enhanced", None)
-        enhanced = None if enhanced is None else enhanced.cpu().numpy()
-        crops = None if dir_save_path is None else getattr(result, "crops", None)
-        crops = None if crops is None else crops.images()
-        chips = None if dir_save_path is None else getattr(result, "chips", None)
-        chips = None if chips is None else chips.images()
-        readout = None if dir_save_path is None or getattr(result, "box_radar", None) is None else result.radar_readout()
-        tracks = None if dir_save_path is None or not tracking else result.tracks()
-        regions = None if dir_save_path is None or getattr(result, "region_table", None) is None else result.regions()
+        out.extend(zip(chunk, dets))
+        if dir_save_path is None:
+            continue
+        rendered = None if result.rendered is None else result.rendered.cpu().numpy()
+        host = [(s, s.read(result)) for s in stages]
         for b, n in enumerate(chunk):
-            out.append((n, dets[b]))
-            ih, iw = (int(v) for v in result.sizes[b])
-            if tracks is not None:
-                with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_tracks.txt"), "w") as f:
-                    f.write(data.track_text(tracks[b][0]))
-            if regions is not None:
-                from .decode import region_text
-                with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_regions.txt"), "w") as f:
-                    f.write(region_text(regions[b][0]))
-            if readout is not None:
-                with open(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_radar.txt"), "w") as f:
-                    f.write(radar_text(dets[b], readout[b]))
+            stem, (ih, iw) = os.path.splitext(n)[0], (int(v) for v in result.sizes[b])
             if rendered is not None:
-                Image.fromarray(rendered[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + ".png"))
-            if heat is not None:
-                Image.fromarray(heat[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_heat.png"))
-            if dehazed is not None:
-                Image.fromarray(dehazed[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_dehaze.png"))
-            if enhanced is not None:
-                Image.fromarray(enhanced[b, :ih, :iw]).save(os.path.join(dir_save_path, os.path.splitext(n)[0] + "_ace.png"))
-            for i, crop in enumerate(crops[b] if crops is not None else ()):
-                if crop is not None and crop.size:
-                    os.makedirs(os.path.join(dir_save_path, "img_crop"), exist_ok=True)
-                    Image.fromarray(crop).save(os.path.join(dir_save_path, "img_crop", f"{os.path.splitext(n)[0]}_crop_{i}.png"))
-            for i, chip in enumerate(chips[b] if chips is not None else ()):
-                os.makedirs(os.path.join(dir_save_path, "img_chip"), exist_ok=True)
-                Image.fromarray(chip).save(os.path.join(dir_save_path, "img_chip", f"{os.path.splitext(n)[0]}_chip_{i}.png"))
+                Image.fromarray(rendered[b, :ih, :iw]).save(os.path.join(dir_save_path, stem + ".png"))
+            for s, part in host:
+                if part is not None:
+                    s.save(part, b, stem, (ih, iw), dets[b], dir_save_path)
     return out

@@ -330,11 +330,8 @@ def test_chips_keyword_checks(model, fixed):
     assert infer.chip_config((5, 7)) == dict(size=(5, 7), letterbox=False, normalised=False)
 
 
-def test_without_chips_the_chain_issues_the_calls_it_issued_before(model, fixed, monkeypatch):
-    """Every wrapper of hip.py the chain calls, in order: chips=None never reaches chip_boxes and issues the calls of a
-    pipeline built without the keyword, and chips=(8, 8) adds exactly that one call, right behind detect_finish (behind
-    crop_boxes with crops)."""
-    import asy_vrnet_amd as A
+def recorded_calls(monkeypatch):
+    """A list that every public wrapper of hip.py appends its name to when it is called, in call order."""
     import asy_vrnet_amd.hip as hip
     calls = []
     quiet = ("ptr", "stream", "empty", "tuning_build", "kernel_launches", "last_kernel")
@@ -346,6 +343,15 @@ def test_without_chips_the_chain_issues_the_calls_it_issued_before(model, fixed,
             calls.append(_n)
             return _f(*a, **k)
         monkeypatch.setattr(hip, name, counted)
+    return calls
+
+
+def test_without_chips_the_chain_issues_the_calls_it_issued_before(model, fixed, monkeypatch):
+    """Every wrapper of hip.py the chain calls, in order: chips=None never reaches chip_boxes and issues the calls of a
+    pipeline built without the keyword, and chips=(8, 8) adds exactly that one call, right behind detect_finish (behind
+    crop_boxes with crops)."""
+    import asy_vrnet_amd as A
+    calls = recorded_calls(monkeypatch)
 
     def chain(**extra):
         pipe = A.FramePipeline(model, F, S, graph=False, **extra, **fixed["kw"])
@@ -361,6 +367,41 @@ def test_without_chips_the_chain_issues_the_calls_it_issued_before(model, fixed,
     both, crops = chain(chips=(8, 8), crops=True), chain(crops=True)
     at = both.index("chip_boxes")
     assert both[at - 1] == "crop_boxes" and both[at - 2] == "detect_finish" and both[:at] + both[at + 1:] == crops
+
+
+ALL_STAGES = dict(dehaze=True, ace=True, crops=True, chips=(8, 8), radar_points=16, calib=np.array(
+    [[40.0, 0, 28, 0], [0, 40.0, 20, 0], [0, 0, 1, 0]], np.float32), box_radar=True, track=True, captions=dict(fps=25.0),
+    regions=True, labels=True, class_names=("a", "b", "c", "d"), heatmap=True, graph=False)
+# recorded on the commit in front of the stage objects, where `_chain` named every stage in an `if` of its own
+ALL_STAGES_CALLS = {
+    "fixed": ["dehaze", "ace", "letterbox", "radar_map", ("forward", 677), "decode_outputs", "detect_select", "nms_capped",
+              "detect_finish", "crop_boxes", "chip_boxes", "box_radar", "track_update", "caption_text", "seg_predict",
+              "seg_regions", "label_index", "render", "render_labels", "render_captions", "heatmap"],
+    "ragged": ["dehaze", "ace", "letterbox", "radar_map", ("forward", 677), "decode_outputs", "detect_select", "nms_capped",
+               "detect_finish", "crop_boxes", "chip_boxes", "box_radar", "track_update", "caption_text", "seg_predict",
+               "seg_regions", "label_index", "render", "render_labels", "render_captions", "heatmap"]}
+
+
+@pytest.mark.parametrize("kind", ["fixed", "ragged"])
+def test_with_every_stage_on_the_chain_issues_the_calls_it_issued_before(kind, model, request, monkeypatch):
+    """The launch order of the ten optional stages, pinned: one pass of the chain with all of them on issues exactly the
+    calls, in the order, that it issued when every stage was a block of `_chain`.  The several hundred calls of the model's
+    forward, which the chain issues as one, stand in the list as ("forward", their number)."""
+    import asy_vrnet_amd as A
+    kw = request.getfixturevalue(kind)["kw"]
+    pipe = A.FramePipeline(model, (48, 64) if kind == "fixed" else RAGGED_CAP, S, **ALL_STAGES, **kw)
+    calls, forward = recorded_calls(monkeypatch), []
+    hooks = [model.register_forward_pre_hook(lambda *a: forward.append(len(calls))),
+             model.register_forward_hook(lambda *a: forward.append(len(calls)))]
+    with torch.no_grad():
+        pipe._chain()
+    torch.cuda.synchronize()
+    for h in hooks:
+        h.remove()
+    start, end = forward
+    calls = calls[:start] + [("forward", end - start)] + calls[end:]
+    print(kind, calls)
+    assert calls == ALL_STAGES_CALLS[kind]
 
 
 def test_predict_dir_saves_the_chips_of_every_picture(ragged, tmp_path):

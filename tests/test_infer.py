@@ -319,6 +319,23 @@ def test_pipeline_argument_errors():
         infer.validate_inputs(frames.astype(np.float32), radar, 2, F, S)
 
 
+def test_the_stage_list_names_the_ten_stages_their_fields_and_their_output_names():
+    """The launch order of the optional stages is `infer.STAGES`; every field a stage declares is a field of FrameResult
+    that defaults to None and is taken as a keyword; the output names `predict_dir` keeps apart are the stages' claims."""
+    assert [s.name for s in infer.STAGES] == ["dehaze", "ace", "crops", "chips", "box_radar", "track", "captions", "regions",
+                                              "labels", "heatmap"]
+    bare = infer.FrameResult(1, 2, 3, 4, 5, 6, 7)
+    fields = [f for s in infer.STAGES for f in s.fields]
+    assert len(fields) == len(set(fields)) == 17 and all(getattr(bare, f) is None for f in fields)
+    full = infer.FrameResult(1, 2, 3, 4, 5, 6, 7, **{f: i for i, f in enumerate(fields)})
+    assert [getattr(full, f) for f in fields] == list(range(17)) and (full.rows, full.flag, full.sizes) == (1, 7, None)
+    with pytest.raises(TypeError, match="heat_map"):
+        infer.FrameResult(1, 2, 3, 4, 5, 6, 7, heat_map=8)
+    claims = {s.name: tuple(s.claims) for s in infer.STAGES}
+    assert claims == dict(dehaze=("_dehaze",), ace=("_ace",), crops=(), chips=(), box_radar=("_radar",), track=("_tracks",),
+                          captions=(), regions=("_regions",), labels=(), heatmap=("_heat",))
+
+
 def test_unmap_scalars_are_those_of_yolo_correct_boxes():
     """(c - offset) * scale and s * scale with the scalars of unmap_scalars are yolo_correct_boxes' own operations."""
     rng = np.random.default_rng(77)
