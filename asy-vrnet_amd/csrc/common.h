@@ -87,6 +87,7 @@ typedef struct vrnet_frame_geom {
 #define VR_FLAG_TRACK_FULL 32768                /* track.hip: a valid row found no free slot in the track table, id 0 */
 #define VR_FLAG_CAPTION 65536                   /* captions.hip: a range or a speed that cannot be drawn, left out of its caption */
 #define VR_FLAG_REGIONS 131072                  /* regions.hip: more regions than the table holds; labels and head are complete */
+#define VR_FLAG_JPEG_ARENA 262144               /* jpeg.hip: a file that did not fit its slot of the arena, length 0 */
 extern "C" {
 /* include/vrnet_hip.h: one record per region of vrnet_seg_regions_u8. */
 typedef struct vrnet_region {

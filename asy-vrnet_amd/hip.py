@@ -183,6 +183,8 @@ _SIGS = {
     "vrnet_crop_boxes_u8": ([P, I, I, I, P, P, P, I, P, L, P, P, P, P], I),
     "vrnet_chip_workspace": ([I, I, I], L),
     "vrnet_chip_boxes_u8": ([P, I, I, I, P, P, P, I, I, I, I, P, P, P, P, P, P, P], I),
+    "vrnet_jpeg_workspace_bytes": ([I, I, I, I, L], L),
+    "vrnet_jpeg_encode_u8": ([P, I, I, I, P, P, I, P, P, L, P, P, P, L, P], I),
     "vrnet_dehaze_workspace_bytes": ([I, I, I], L),
     "vrnet_dehaze_u8": ([P, P, I, I, I, I, I, D, D, D, P, P, P, P, L, P], I),
     "vrnet_ace_workspace_bytes": ([I, I, I], L),
@@ -2070,6 +2072,47 @@ def chip_boxes(frames, rows, offsets, chips, table, summary, ws, letterbox=False
     _check(_lib.vrnet_chip_boxes_u8(ptr(frames), B, ihm, iwm, None if geom is None else _geom(geom, B, fn), ptr(rows), ptr(offsets),
                                     n_cap, sh, sw, int(bool(letterbox)), ptr(chips), ptr(chips_f32), ptr(table), ptr(summary),
                                     ptr(ws), ptr(flag), stream()), fn)
+
+
+# ---- baseline JPEG (csrc/jpeg.hip) ---------------------------------------------------------------------------------------------
+FLAG_JPEG_ARENA = 262144     # VR_FLAG_JPEG_ARENA of csrc/common.h: a file that did not fit its slot of the arena, length 0
+JPEG_HEADER = 623            # bytes in front of the scan data
+JPEG_MAX_BLOCKS = 1 << 20    # JP_MAX_BLOCKS of csrc/jpeg.hip: the blocks of one slot, so that bit offsets fit 32 bits
+
+
+def jpeg_workspace_bytes(B, H, W, subsampling, capacity):
+    n = _lib.vrnet_jpeg_workspace_bytes(B, H, W, int(subsampling), int(capacity))
+    if n < 0:
+        raise RuntimeError(f"jpeg_encode: bad shape (B {B}, slots of {H} x {W}, subsampling {subsampling}, capacity {capacity}; "
+                           f"1..65535 images, sides up to 65535, at most {JPEG_MAX_BLOCKS} blocks an image, subsampling 0 or 2, a "
+                           f"capacity from {JPEG_HEADER + 2} bytes to below 2^31)")
+    return n
+
+
+def jpeg_encode(images, header, arena, record, ws, subsampling=0, sizes=None, geom=None, flag=None):
+    """Baseline JPEG files by the rule of `render.jpeg_encode_host` (vrnet_jpeg_encode_u8): images (B, H, W, 3) uint8 -> arena
+    (B, capacity) uint8, slot b a complete file in its first record[b, 0] bytes, and record (B, 2) int32 = (length, state):
+    state 1 a file, 2 it did not fit the capacity (length 0, FLAG_JPEG_ARENA), 3 an image without pixels (length 0).  Bytes of
+    a slot behind its length are not defined.  header: the (623) uint8 template of `render.jpeg_header` on the device, which
+    holds the quantisation tables; height and width are patched per image.  sizes: a (B, 2) int32 device table (h, w) of the
+    images in the corners of their slots, or geom (`_table_call`): the (B, GEOM_BYTES) table of a ragged batch; neither: every
+    image fills its slot.  ws: uint8, at least jpeg_workspace_bytes(B, H, W, subsampling, capacity) bytes; flag (1) int32 or
+    None: FLAG_JPEG_ARENA, and FLAG_GEOMETRY for a size that had to be clamped.  Eight launches, no host synchronisation."""
+    fn = "jpeg_encode"
+    table_call = _table_call(fn, geom, (("sizes", sizes, None),))
+    if images is None or images.dim() != 4 or images.shape[-1] != 3:
+        raise RuntimeError(f"{fn}: expected contiguous uint8 images of shape (B, H, W, 3)")
+    B, H, W = images.shape[:3]
+    if arena is None or arena.dim() != 2 or header is None or record is None or ws is None:
+        raise RuntimeError(f"{fn}: header, arena (B, capacity), record and the workspace are required")
+    capacity = arena.shape[1]
+    need = jpeg_workspace_bytes(B, H, W, subsampling, capacity)
+    if ws.dtype != torch.uint8 or ws.dim() != 1 or ws.shape[0] < need or not ws.is_contiguous():
+        raise RuntimeError(f"{fn}: the workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    _tensors(fn, ((images, (B, H, W, 3), torch.uint8), (header, (JPEG_HEADER,), torch.uint8), (arena, (B, capacity), torch.uint8),
+                  (record, (B, 2), torch.int32), (sizes, (B, 2), torch.int32), (flag, (1,), torch.int32)))
+    _check(_lib.vrnet_jpeg_encode_u8(ptr(images), B, H, W, _geom(geom, B, fn) if table_call else None, ptr(sizes), int(subsampling),
+                                     ptr(header), ptr(arena), capacity, ptr(record), ptr(flag), ptr(ws), ws.numel(), stream()), fn)
 
 
 # ---- connected regions of the class map (csrc/regions.hip) ---------------------------------------------------------------------

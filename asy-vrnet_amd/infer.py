@@ -16,11 +16,11 @@ capacity, so only its `cap` best-scored ones were considered -- and FLAG_DET_CLA
 outside [0, num_classes), which is not counted -- and, in a ragged pipeline, FLAG_GEOMETRY -- a record of the geometry
 table had to be clamped by a kernel, which the host checks of `run` rule out.  The optional stages add their own: FLAG_POINT_COUNT
 (radar_points), FLAG_LABEL_SCORE, FLAG_CROP_ARENA, FLAG_DEHAZE, FLAG_ACE, FLAG_BOX_COUNT, FLAG_TRACK_FULL, FLAG_CAPTION and
-FLAG_REGIONS, each described with its stage.
+FLAG_REGIONS and FLAG_JPEG_ARENA, each described with its stage.
 
 Everything else a pipeline can do is an optional STAGE, one class of `stages.py` each, which holds the stage's keyword,
 buffers, launches, result fields and documentation.  `stages.STAGES` is their order; a pipeline keeps those that are on, in
-that order, as `stages`, and the chain calls them at four hook points, within a hook point in that order:
+that order, as `stages`, and the chain calls them at five hook points, within a hook point in that order:
 
     frames      in front of the letterbox; each may replace the frames everything later reads     dehaze, ace
     rows        behind hip.detect_finish, in front of the seg node                                  crops, chips, box_radar, track,
@@ -29,6 +29,8 @@ that order, as `stages`, and the chain calls them at four hook points, within a 
                                                                                                     the render node draws them)
     picture     behind the render node, in front of `_tail`                                         captions (hip.render_captions),
                                                                                                     heatmap
+    output      behind every picture, in front of `_tail`: what leaves the device in its final form  jpeg (`stages.OUTPUTS`,
+                                                                                                    kept behind the ten)
 
 ragged=True lifts the one-size limit: the pipeline is built for a CAPACITY (ihm, iwm), every frame of a call has its own
 size inside it, and the per-image geometry travels in a small device table (`data.frame_geometry`) instead of the launch
@@ -41,8 +43,8 @@ import torch
 
 from . import data
 from . import render as rendering
-from .stages import (STAGES, ace_config, caption_config, chip_config, crop_capacity, dehaze_config,    # noqa: F401
-                     radar_text)
+from .stages import (OUTPUTS, STAGES, ace_config, caption_config, chip_config, crop_capacity, dehaze_config,    # noqa: F401
+                     jpeg_config, radar_text)
 
 FLAG_CANDIDATES, FLAG_DET_CLASS = 8, 16          # NMS_FLAG_* of csrc/nms.hip, above render.FLAG_*
 FLAG_GEOMETRY = 256                              # VR_FLAG_GEOMETRY of csrc/common.h, above evaluate.FLAG_EVAL_*
@@ -55,6 +57,7 @@ FLAG_ACE = rendering.FLAG_ACE                    # 16384, csrc/ace.hip (a pipeli
 FLAG_TRACK_FULL = data.FLAG_TRACK_FULL           # 32768, VR_FLAG_TRACK_FULL of csrc/common.h (a pipeline built with track): the table was full
 FLAG_CAPTION = rendering.FLAG_CAPTION            # 65536, VR_FLAG_CAPTION of csrc/common.h (a pipeline built with captions): a field left out
 FLAG_REGIONS = 131072                            # VR_FLAG_REGIONS of csrc/common.h (a pipeline built with regions): more regions than the table
+FLAG_JPEG_ARENA = rendering.FLAG_JPEG_ARENA      # 262144, VR_FLAG_JPEG_ARENA of csrc/common.h (a pipeline built with jpeg): a file that did not fit
 # the picture formats predict.py's dir_predict mode accepts, matched against the lower-cased file name
 IMAGE_EXTENSIONS = tuple("." + e for e in "bmp dib jpeg jpg pbm pgm png ppm tif tiff".split())
 
@@ -204,10 +207,10 @@ class FrameResult:
     2, 5) float32 (`stages.BoxRadar`; `radar_readout`); track_ids (B, cap), track_table (B, T, 16) and track_head (B, 4) int32
     (`stages.Track`; `tracks`); captions (B * cap, 12) int32 (`stages.Captions`; `caption_strings`); region_labels (B, ih, iw),
     region_table (B, max_regions, 12), region_head (B, 4) and box_regions (B, cap) int32 (`stages.Regions`; `regions`);
-    heat_mask (B, ih, iw) uint8, heat_picture (B, ih, iw, 3) uint8 and heat_range (B, 2) int32 (`stages.Heatmap`).  The
-    constructor takes them as keywords."""
+    heat_mask (B, ih, iw) uint8, heat_picture (B, ih, iw, 3) uint8 and heat_range (B, 2) int32 (`stages.Heatmap`); jpeg, a
+    `render.Jpegs` (`stages.Jpeg`, the one entry of `stages.OUTPUTS`).  The constructor takes them as keywords."""
     CORE = ("rows", "kept", "det_counts", "class_map", "seg_counts", "rendered", "flag", "sizes")
-    __slots__ = CORE + tuple(f for stage in STAGES for f in stage.fields)
+    __slots__ = CORE + tuple(f for stage in STAGES + OUTPUTS for f in stage.fields)
 
     def __init__(self, rows, kept, det_counts, class_map, seg_counts, rendered, flag, sizes=None, **fields):
         self.rows, self.kept, self.det_counts, self.class_map = rows, kept, det_counts, class_map
@@ -330,7 +333,8 @@ class FramePipeline:
     The optional stages, each documented on its class of `stages.py`, in launch order: dehaze= (`stages.Dehaze`), ace=
     (`Ace`), crops= (`Crops`), chips= (`Chips`), box_radar= / box_shrink= (`BoxRadar`), track= (`Track`), captions=
     (`Captions`), regions= (`Regions`), labels= / class_names= / font= / label_sizes= (`Labels`), heatmap= / heat_alpha=
-    (`Heatmap`).  With its default a stage changes nothing about the chain, the graph or the result.  `stages` holds those
+    (`Heatmap`), and behind them the outputs of `stages.OUTPUTS`: jpeg= (`Jpeg`).  With its default a stage changes nothing
+    about the chain, the graph or the result.  `stages` holds those
     that are on; the attribute of each keyword's name holds its checked parameters (`crop_capacity` for crops=)."""
 
     def __init__(self, model, frame_shape, input_shape, batch=1, conf_thres=0.5, nms_thres=0.4, letterbox_image=True,
@@ -338,7 +342,7 @@ class FramePipeline:
                  box_palette=None, graph=True, radar_dtype=torch.float32, ragged=False, max_taps=None, heatmap=False,
                  heat_alpha=0.5, radar_points=None, radar_radius=0, radar_min_depth=0.1, calib=None, labels=None, class_names=None,
                  font=None, label_sizes=None, crops=None, dehaze=None, ace=None, box_radar=None, box_shrink=1.0, track=None,
-                 captions=None, regions=None, chips=None):
+                 captions=None, regions=None, chips=None, jpeg=None):
         self.frame_shape, self.input_shape, self.batch, self.max_candidates = validate_config(
             model, frame_shape, input_shape, batch, max_candidates)
         self.model, self.render, self.ragged = model, bool(render), bool(ragged)
@@ -351,8 +355,9 @@ class FramePipeline:
             raise RuntimeError("FramePipeline: calib, radar_radius and radar_min_depth belong to radar_points=max_points")
         kw = dict(dehaze=dehaze, ace=ace, crops=crops, chips=chips, box_radar=box_radar, box_shrink=box_shrink, track=track,
                   captions=captions, regions=regions, labels=labels, class_names=class_names, font=font, label_sizes=label_sizes,
-                  heatmap=heatmap, heat_alpha=heat_alpha)
+                  heatmap=heatmap, heat_alpha=heat_alpha, jpeg=jpeg)
         self.stages = self._parse(kw, early=True)         # the keyword checks that need no device
+        outputs = [s for s in (cls.parse(self, kw) for cls in OUTPUTS) if s is not None]
         if mix_type not in (0, 1, 2) or not 0.0 <= float(alpha) <= 1.0:
             raise RuntimeError(f"FramePipeline: mix_type must be 0, 1 or 2 and alpha in [0, 1], got {mix_type!r}, {alpha!r}")
         if radar_dtype not in (torch.float32, torch.float64) or (radar_dtype == torch.float64 and not normalise_radar):
@@ -390,7 +395,7 @@ class FramePipeline:
             table = data.frame_geometry([self.frame_shape] * B, self.input_shape, self.letterbox_image, fn="FramePipeline")
             self.points, self.views = self.radar_points.buffers(table, dev)
             self._radar_ws = self.radar_points.workspace(self.input_shape, dev)
-        self.stages = sorted(self.stages + self._parse(kw, early=False), key=lambda s: STAGES.index(type(s)))
+        self.stages = sorted(self.stages + self._parse(kw, early=False), key=lambda s: STAGES.index(type(s))) + outputs
         from . import hip
         for s in self.stages:                 # before the capture: what follows from the frame shape alone
             s.static(self, hip)
@@ -476,6 +481,7 @@ class FramePipeline:
                 box_palette=self.box_palette, thickness=self.thickness, flag=self.flag, device=dev, labels=c.labels, geom=c.geom,
                 label_sizes=c.label_sizes)
         self._at("picture", c)
+        self._at("output", c)
         result = FrameResult(self._rows, self._kept, self._det_counts, c.class_map, seg_counts, c.rendered, self.flag, **c.out)
         self._tail(result)
         return result
@@ -584,7 +590,8 @@ def predict_dir(pipeline, dir_origin_path, radar_root, dir_save_path=None):
     (file name, (N, 7) detections) in that order; with dir_save_path the rendered frame of every picture, sliced to its own
     size, is saved there as <stem>.png through Pillow (the reference renames .jpg to .png; here every picture is a PNG), and
     every stage of the pipeline saves its own beside it -- <stem>_heat.png, <stem>_dehaze.png, <stem>_ace.png,
-    <stem>_radar.txt, <stem>_tracks.txt, <stem>_regions.txt, img_crop/<stem>_crop_<i>.png, img_chip/<stem>_chip_<i>.png: see
+    <stem>_radar.txt, <stem>_tracks.txt, <stem>_regions.txt, img_crop/<stem>_crop_<i>.png, img_chip/<stem>_chip_<i>.png, and
+    <stem>.jpg, the device-encoded file of a pipeline built with jpeg=, written as it is, without Pillow: see
     the stage classes of `stages.py`; what belongs to the repeated fill pictures is dropped with the repeats.  Each stage
     reads its part of a batch back once, and nothing is read back without dir_save_path.  Two pictures that would share one
     output name (names that differ only in their extension, or `a_heat.jpg` next to `a.jpg` with heat maps on, and so for

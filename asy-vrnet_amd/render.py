@@ -58,6 +58,11 @@ ValueError for x1 < x0 where this module paints nothing.
   either, so the empty entry is this project's definition); otherwise the crop is frame[t:bt, l:r, :], bit for bit
   np.array(image.crop([left, top, right, bottom])).  The arena's layout is `crop_layout`'s.
 
+* `jpeg_encode` / `Jpegs` / `jpeg_encode_host` / `jpeg_header` / `jpeg_tables`: the `r_image.save(..., quality=95, subsampling=0)`
+  of predict.py -- every picture of a batch as a finished baseline JPEG file in a byte arena on the device (csrc/jpeg.hip),
+  every byte the one Pillow (libjpeg-turbo) writes at that quality and subsampling (0: 4:4:4, 2: 4:2:0).  `jpeg_encode_host`
+  states the rule in numpy, in integers from end to end, and is pinned to live Pillow without a GPU (tests/test_jpeg_host.py).
+
 * `chip_boxes` / `Chips` / `chip_boxes_host` / `chip_geometry` / `chip_resample_host`: the same crops brought to ONE size, the
   way the reference brings any picture to a fixed size (resize_image, utils/utils.py:19-32) -- one (n, sh, sw, 3) tensor of
   equal-sized pictures, and optionally its normalised (n, 3, sh, sw) float form, for a second stage (csrc/chips.hip).
@@ -1859,4 +1864,328 @@ def ace(frames_u8, sizes=None, geom=None, ratio=4.0, radius=3, s=0.005, bins=200
         out = torch.empty_like(img)
         ws = torch.empty(hip.ace_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
         hip.ace(img, out, ws, weights, geom=geom, flag=flag, **q)
+    return out
+
+
+# ---- baseline JPEG (csrc/jpeg.hip) ---------------------------------------------------------------------------------------------
+FLAG_JPEG_ARENA = 262144     # VR_FLAG_JPEG_ARENA of csrc/common.h: a file that did not fit its slot of the arena, length 0
+JPEG_HEADER = 623            # bytes in front of the scan data, the same in both modes
+JPEG_MAX_BLOCKS = 1 << 20    # blocks of one image: 1658 bits a block at the most, so every bit offset fits 32 bits
+# the natural (row-major) index of the coefficient at each zigzag position
+JPEG_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                        35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47,
+                        55, 62, 63])
+# ITU-T T.81 Annex K.1: the luminance and chrominance quantisation tables at quality 50, row-major
+_JPEG_BASE = np.array([[16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51,
+                        87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101,
+                        72, 92, 95, 98, 112, 100, 103, 99],
+                       [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99,
+                        99, 99, 99] + [99] * 32])
+# Annex K.3: (code lengths 1..16, values) of the DC luminance, AC luminance, DC chrominance and AC chrominance tables
+_JPEG_HUFF = tuple((bytes.fromhex(b), bytes.fromhex(v)) for b, v in (
+    ("00010501010101010100000000000000", "000102030405060708090a0b"),
+    ("0002010303020403050504040000017d",
+     "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a43444546"
+     "4748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8"
+     "b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"),
+    ("00030101010101010101010000000000", "000102030405060708090a0b"),
+    ("00020102040403040705040400010277",
+     "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445"
+     "464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6"
+     "b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")))
+
+
+def _jpeg_params(quality, subsampling, fn):
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise RuntimeError(f"{fn}: quality is an integer in 1..100, got {quality!r}")
+    if isinstance(subsampling, bool) or subsampling not in (0, 2):
+        raise RuntimeError(f"{fn}: subsampling is 0 (4:4:4) or 2 (4:2:0), got {subsampling!r}")
+    return int(quality), int(subsampling)
+
+
+def jpeg_tables(quality=95):
+    """The two quantisation tables of a quality in 1..100, libjpeg's rule: scale = 5000 // q below 50, else 200 - 2 q, and
+    t = clip((base * scale + 50) // 100, 1, 255) on the Annex K tables -> (2, 64) int64, luminance then chrominance, ROW-MAJOR
+    (the header and the kernels hold them in zigzag order: `tables[:, JPEG_ZIGZAG]`)."""
+    quality, _ = _jpeg_params(quality, 0, "jpeg_tables")
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return np.clip((_JPEG_BASE * scale + 50) // 100, 1, 255)
+
+
+def jpeg_huffman():
+    """The four Annex K Huffman tables as (code, length) pairs by symbol: a (4, 256, 2) int64 array, DC luminance, AC
+    luminance, DC chrominance, AC chrominance; length 0: the table has no such symbol.  Codes are assigned as T.81 Annex C
+    does: in order of length, counting up."""
+    out = np.zeros((4, 256, 2), np.int64)
+    for t, (bits, vals) in enumerate(_JPEG_HUFF):
+        code, k = 0, 0
+        for length in range(1, 17):
+            for _ in range(bits[length - 1]):
+                out[t, vals[k]] = code, length
+                code, k = code + 1, k + 1
+            code <<= 1
+    return out
+
+
+def jpeg_header(height, width, quality=95, subsampling=0):
+    """The 623 bytes in front of the scan data, as libjpeg writes them for Pillow's `save(format="JPEG", quality=,
+    subsampling=)`: SOI, the JFIF 1.01 segment (no units, density 1 x 1), the two quantisation tables in zigzag order, SOF0
+    (components 1, 2, 3; sampling 0x11 each for 4:4:4, 0x22, 0x11, 0x11 for 4:2:0; tables 0, 1, 1), the four Annex K Huffman
+    tables and the scan header.  Height and width are bytes 163..166, big-endian: the device patches them per image."""
+    quality, subsampling = _jpeg_params(quality, subsampling, "jpeg_header")
+    if not (0 <= int(height) <= 65535 and 0 <= int(width) <= 65535):
+        raise RuntimeError(f"jpeg_header: a JPEG's sides are at most 65535, got {height} x {width}")
+    seg = lambda marker, body: bytes([0xFF, marker]) + (len(body) + 2).to_bytes(2, "big") + body
+    out = b"\xff\xd8" + seg(0xE0, b"JFIF\0" + bytes([1, 1, 0, 0, 1, 0, 1, 0, 0]))
+    for i, t in enumerate(jpeg_tables(quality)):
+        out += seg(0xDB, bytes([i]) + bytes(t[JPEG_ZIGZAG].tolist()))
+    out += seg(0xC0, bytes([8]) + int(height).to_bytes(2, "big") + int(width).to_bytes(2, "big") +
+               bytes([3, 1, 0x22 if subsampling else 0x11, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for (bits, vals), ident in zip(_JPEG_HUFF, (0x00, 0x10, 0x01, 0x11)):
+        out += seg(0xC4, bytes([ident]) + bits + vals)
+    out += seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+    assert len(out) == JPEG_HEADER
+    return out
+
+
+def _jpeg_fdct(blocks):
+    """libjpeg's jfdctint (CONST_BITS 13, PASS1_BITS 2) on (N, 8, 8) int64 samples minus 128: rows, then columns."""
+    def descale(x, n):
+        return (x + (1 << (n - 1))) >> n
+
+    def one(d, first):
+        t0, t7, t1, t6 = d[..., 0] + d[..., 7], d[..., 0] - d[..., 7], d[..., 1] + d[..., 6], d[..., 1] - d[..., 6]
+        t2, t5, t3, t4 = d[..., 2] + d[..., 5], d[..., 2] - d[..., 5], d[..., 3] + d[..., 4], d[..., 3] - d[..., 4]
+        t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+        n = 11 if first else 15
+        out = np.empty_like(d)
+        out[..., 0] = (t10 + t11) << 2 if first else descale(t10 + t11, 2)
+        out[..., 4] = (t10 - t11) << 2 if first else descale(t10 - t11, 2)
+        z1 = (t12 + t13) * 4433
+        out[..., 2], out[..., 6] = descale(z1 + t13 * 6270, n), descale(z1 - t12 * 15137, n)
+        z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+        z5 = (z3 + z4) * 9633
+        t4, t5, t6, t7 = t4 * 2446, t5 * 16819, t6 * 25172, t7 * 12299
+        z1, z2, z3, z4 = z1 * -7373, z2 * -20995, z3 * -16069 + z5, z4 * -3196 + z5
+        out[..., 7], out[..., 5] = descale(t4 + z1 + z3, n), descale(t5 + z2 + z4, n)
+        out[..., 3], out[..., 1] = descale(t6 + z2 + z3, n), descale(t7 + z1 + z4, n)
+        return out
+
+    rows = one(blocks, True)
+    return one(rows.transpose(0, 2, 1), False).transpose(0, 2, 1)
+
+
+def _jpeg_pad(plane, h, w):
+    """plane replicated at its right and lower edge to (h, w)."""
+    return np.pad(plane, ((0, h - plane.shape[0]), (0, w - plane.shape[1])), mode="edge")
+
+
+def jpeg_blocks_host(image_u8, quality=95, subsampling=0):
+    """The quantised coefficients of an (h, w, 3) uint8 RGB image in scan order -> (coefficients (N, 64) int64 in zigzag order,
+    component (N) of each block: 0, 1, 2, dummy (N) bool).  A dummy block (a Y block of a 4:2:0 MCU beyond ceil(h / 8) block
+    rows or ceil(w / 8) block columns) has no AC and the DC of the block in front of it."""
+    fn = "jpeg_encode_host"
+    quality, subsampling = _jpeg_params(quality, subsampling, fn)
+    a = np.asarray(image_u8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or min(a.shape) < 1 or max(a.shape[:2]) > 65535:
+        raise RuntimeError(f"{fn}: expected an (h, w, 3) uint8 image with sides in 1..65535, got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    F = lambda x: int(x * 65536 + 0.5)
+    R, G, B = (a[..., c].astype(np.int64) for c in range(3))
+    Y = (F(.299) * R + F(.587) * G + F(.114) * B + 32768) >> 16
+    Cb = (-F(.16874) * R - F(.33126) * G + F(.5) * B + (128 << 16) + 32767) >> 16
+    Cr = (F(.5) * R - F(.41869) * G - F(.08131) * B + (128 << 16) + 32767) >> 16
+    split = lambda p: p.reshape(p.shape[0] // 8, 8, p.shape[1] // 8, 8).transpose(0, 2, 1, 3)      # (block rows, block cols, 8, 8)
+    if subsampling == 0:
+        MH, MW = -(-h // 8), -(-w // 8)
+        units = np.stack([split(_jpeg_pad(p, 8 * MH, 8 * MW)) for p in (Y, Cb, Cr)], axis=2)      # (MH, MW, 3, 8, 8)
+        comp, dummy = np.tile(np.arange(3), MH * MW), np.zeros(3 * MH * MW, bool)
+    else:
+        MH, MW = -(-h // 16), -(-w // 16)
+        yb = split(_jpeg_pad(Y, 16 * MH, 16 * MW)).reshape(MH, 2, MW, 2, 8, 8).transpose(0, 2, 1, 3, 4, 5).reshape(MH, MW, 4, 8, 8)
+        by, bx = np.meshgrid(np.arange(2 * MH), np.arange(2 * MW), indexing="ij")
+        dm = ((by >= -(-h // 8)) | (bx >= -(-w // 8))).reshape(MH, 2, MW, 2).transpose(0, 2, 1, 3).reshape(MH, MW, 4)
+        bias = np.tile(np.array([1, 2]), 4 * MW)
+        small = []
+        for p in (Cb, Cr):
+            p = _jpeg_pad(p, h + (h & 1), 16 * MW)
+            p = (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + bias) >> 2
+            small.append(split(_jpeg_pad(p, 8 * MH, 8 * MW))[:, :, None])
+        units = np.concatenate([yb] + small, axis=2)                                               # (MH, MW, 6, 8, 8)
+        comp = np.tile(np.array([0, 0, 0, 0, 1, 2]), MH * MW)
+        dummy = np.concatenate([dm, np.zeros((MH, MW, 2), bool)], axis=2).reshape(-1)
+    if len(comp) > JPEG_MAX_BLOCKS:
+        raise RuntimeError(f"{fn}: {len(comp)} blocks; at most {JPEG_MAX_BLOCKS} an image")
+    c = _jpeg_fdct(units.reshape(-1, 8, 8) - 128).reshape(-1, 64)[:, JPEG_ZIGZAG]
+    d = 8 * jpeg_tables(quality)[:, JPEG_ZIGZAG][np.minimum(comp, 1)]
+    q = np.sign(c) * ((np.abs(c) + (d >> 1)) // d)
+    for k in np.flatnonzero(dummy):           # in order: a dummy may follow a dummy
+        q[k, 0], q[k, 1:] = q[k - 1, 0], 0
+    return q, comp, dummy
+
+
+def _jpeg_bits(values, lengths):
+    """The bits of (value, length <= 63) items, most significant first, as one uint8 array of 0 / 1."""
+    lengths = np.asarray(lengths, np.int64)
+    ends = np.cumsum(lengths)
+    j = np.arange(int(ends[-1]) if len(ends) else 0) - np.repeat(ends - lengths, lengths)      # the bit's index in its item
+    return ((np.repeat(np.asarray(values, np.uint64), lengths) >> (np.repeat(lengths, lengths) - 1 - j).astype(np.uint64)) & 1).astype(np.uint8)
+
+
+def jpeg_scan_host(q, comp):
+    """The entropy-coded scan of `jpeg_blocks_host`'s blocks, byte-stuffed, without EOI: one DC predictor per component from
+    0 on, never reset; category bit_length(|v|), value bits the low s bits of v (of v - 1 when v < 0); AC as (run << 4) | s in
+    zigzag order, 0xF0 for each full run of 16 zeros in front of a non-zero and 0x00 where the block ends in zeros; bits MSB
+    first, the last byte padded with ones, every 0xFF byte followed by 0x00.  Returns (bytes, ZRL symbols coded)."""
+    huff = jpeg_huffman()
+    N = len(q)
+    diff = q[:, 0].copy()
+    for c in range(3):
+        k = np.flatnonzero(comp == c)
+        diff[k] = np.diff(q[k, 0], prepend=0)
+    cat = lambda v: np.where(v == 0, 0, np.floor(np.log2(np.maximum(np.abs(v), 1))).astype(np.int64) + 1)   # exact below 2^52
+    extra = lambda v, s: (np.where(v < 0, v - 1, v) & ((1 << s) - 1))
+    chroma = np.minimum(comp, 1)
+    s = cat(diff)
+    code = huff[2 * chroma, s]
+    items = [(np.arange(N) * 65, (code[:, 0] << s) | extra(diff, s), code[:, 1] + s)]           # key, value, length
+    blk, pos = np.nonzero(q[:, 1:])
+    pos = pos + 1
+    first = np.ones(len(blk), bool)
+    first[1:] = blk[1:] != blk[:-1]
+    run = pos - np.where(first, 0, np.concatenate([[0], pos[:-1]])) - 1
+    v = q[blk, pos]
+    s = cat(v)
+    tab = 2 * chroma[blk] + 1
+    sym, zrl = huff[tab, ((run & 15) << 4) | s], huff[tab, 0xF0]
+    val, length = (sym[:, 0] << s) | extra(v, s), sym[:, 1] + s
+    for n in range(1, 4):                     # a run of up to 62 zeros: at most three ZRL in front of the symbol
+        more = (run >> 4) >= n
+        val, length = np.where(more, (zrl[:, 0] << length) | val, val), np.where(more, length + zrl[:, 1], length)
+    items.append((blk * 65 + pos, val, length))
+    eob = np.flatnonzero(q[:, 63] == 0)
+    e = huff[2 * chroma[eob] + 1, 0]
+    items.append((eob * 65 + 64, e[:, 0], e[:, 1]))
+    key, val, length = (np.concatenate([it[i] for it in items]) for i in range(3))
+    order = np.argsort(key, kind="stable")
+    bits = _jpeg_bits(val[order], length[order])
+    bits = np.concatenate([bits, np.ones(-len(bits) % 8, np.uint8)])
+    raw = np.packbits(bits)
+    at = np.flatnonzero(raw == 0xFF)
+    return bytes(np.insert(raw, at + 1, 0).tolist()), int((run >> 4).sum())
+
+
+def jpeg_encode_host(image_u8, quality=95, subsampling=0):
+    """The rule of `jpeg_encode` in numpy: the baseline JPEG file of an (h, w, 3) uint8 RGB image, every byte the one Pillow
+    (libjpeg-turbo) writes for `Image.save(format="JPEG", quality=quality, subsampling=subsampling)` -- `jpeg_header`, the
+    scan of `jpeg_blocks_host` / `jpeg_scan_host` (integer colour conversion, edge replication, the 4:2:0 box reduction with
+    its alternating bias, jfdctint, rounding quantisation, the Annex K Huffman tables, byte stuffing) and EOI.  Everything is
+    integer arithmetic.  subsampling: 0 (4:4:4) or 2 (4:2:0)."""
+    q, comp, _ = jpeg_blocks_host(image_u8, quality, subsampling)
+    h, w = np.asarray(image_u8).shape[:2]
+    return jpeg_header(h, w, quality, subsampling) + jpeg_scan_host(q, comp)[0] + b"\xff\xd9"
+
+
+class Jpegs:
+    """What `jpeg_encode` leaves on the device: arena (B, capacity) uint8, slot b a complete JPEG file in its first
+    record[b, 0] bytes; record (B, 2) int32 = (length, state) -- state 1: a file; 2: the file did not fit the capacity, length
+    0 and FLAG_JPEG_ARENA in flag; 3: an image without pixels --; flag (1) int32.  Bytes of a slot behind its length are not
+    defined.  From a pipeline these are its own buffers: the next run overwrites them."""
+    __slots__ = ("arena", "record", "flag", "quality", "subsampling", "header", "workspace")
+
+    def __init__(self, arena, record, flag, quality, subsampling, header, workspace):
+        self.arena, self.record, self.flag, self.quality, self.subsampling = arena, record, flag, int(quality), int(subsampling)
+        self.header, self.workspace = header, workspace
+
+    @property
+    def capacity(self):
+        return self.arena.shape[1]
+
+    def bytes(self):
+        """The files as a list of `bytes`, b"" for an image whose file did not fit: the record is read back first (which waits
+        for the device), then only the used bytes of every slot, gathered into one copy."""
+        lengths = np.clip(self.record.cpu().numpy()[:, 0].astype(np.int64), 0, self.capacity)
+        if not lengths.sum():
+            return [b""] * len(lengths)
+        used = torch.cat([self.arena[b, :int(n)] for b, n in enumerate(lengths) if n]).cpu().numpy().tobytes()
+        ends = np.cumsum(lengths)
+        return [used[e - n:e] for e, n in zip(ends.tolist(), lengths.tolist())]
+
+    def save(self, paths):
+        """Writes file b to paths[b] (None, or an image without a file: nothing is written).  Returns the files of `bytes`."""
+        files = self.bytes()
+        if len(paths) != len(files):
+            raise RuntimeError(f"Jpegs.save: {len(paths)} paths for {len(files)} images")
+        for path, data in zip(paths, files):
+            if path is not None and data:
+                with open(path, "wb") as f:
+                    f.write(data)
+        return files
+
+
+def jpeg_capacity(h, w):
+    """The default bytes of a slot of the arena: the header plus 3 h w.  A cap the caller may change, not a bound: noise at
+    quality 100 exceeds it."""
+    return JPEG_HEADER + 3 * int(h) * int(w)
+
+
+def jpeg_shape(h, w, subsampling, fn="jpeg_encode"):
+    """The host check that bounds an image so that the kernels' 32-bit bit offsets suffice: sides in 1..65535 and at most
+    JPEG_MAX_BLOCKS blocks (a block codes to at most 1658 bits).  Returns the blocks of an (h, w) image."""
+    blocks = 6 * (-(-h // 16)) * (-(-w // 16)) if subsampling else 3 * (-(-h // 8)) * (-(-w // 8))
+    if not (1 <= h <= 65535 and 1 <= w <= 65535) or blocks > JPEG_MAX_BLOCKS:
+        raise RuntimeError(f"{fn}: images of {h} x {w}: sides are 1..65535 and an image has at most {JPEG_MAX_BLOCKS} blocks "
+                           f"(bit offsets are 32-bit), this one {blocks}")
+    return blocks
+
+
+def jpeg_buffers(batch, h, w, quality=95, subsampling=0, capacity=None, flag=None, device="cuda", fn="jpeg_encode"):
+    """The device buffers of one `hip.jpeg_encode` call on (batch, h, w, 3) slots as a `Jpegs`: arena, record, the header
+    template and the workspace.  The keywords are checked here, on the host."""
+    from . import hip
+    quality, subsampling = _jpeg_params(quality, subsampling, fn)
+    if capacity is None:
+        capacity = jpeg_capacity(h, w)
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not JPEG_HEADER + 2 <= int(capacity) < (1 << 31) - 64:
+        raise RuntimeError(f"{fn}: capacity is the bytes of one slot of the arena, {JPEG_HEADER + 2}..2^31 - 65, got {capacity!r}")
+    jpeg_shape(h, w, subsampling, fn)
+    ws = torch.empty(hip.jpeg_workspace_bytes(batch, h, w, subsampling, int(capacity)), dtype=torch.uint8, device=device)
+    header = torch.from_numpy(np.frombuffer(jpeg_header(0, 0, quality, subsampling), np.uint8).copy()).to(device)
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=device)
+    return Jpegs(torch.empty((batch, int(capacity)), dtype=torch.uint8, device=device),
+                 torch.zeros((batch, 2), dtype=torch.int32, device=device), flag, quality, subsampling, header, ws)
+
+
+def jpeg_encode(images_u8, quality=95, subsampling=0, sizes=None, geom=None, capacity=None, flag=None, device="cuda"):
+    """Baseline JPEG files on the device by the rule of `jpeg_encode_host` (vrnet_jpeg_encode_u8, eight launches, no host
+    synchronisation): images_u8 (N, h, w, 3) uint8 RGB, numpy or tensor (a single (h, w, 3) image counts as N = 1) -- frames,
+    rendered pictures, heat maps, the chips tensor of a `Chips`.  quality 1..100 and subsampling 0 (4:4:4) or 2 (4:2:0) as
+    Pillow's `save`.  sizes: (N, 2) host integers (h_b, w_b) when the images are padded slots with image b in the top-left
+    corner of slot b, or geom: the (N, hip.GEOM_BYTES) device table of `data.frame_geometry`; neither: every image fills its
+    slot.  capacity: the bytes of one slot of the arena, default `jpeg_capacity(h, w)`; a file that does not fit gets length
+    0 and FLAG_JPEG_ARENA in flag (a zeroed int32 device tensor of one element; None: one is made), the others are
+    unaffected.  Returns a `Jpegs`."""
+    from . import data, hip
+    fn = "jpeg_encode"
+    img = _as_u8(images_u8, "images", 4, fn)
+    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
+        raise RuntimeError(f"{fn}: expected images of shape (N, h, w, 3) or (h, w, 3), got {tuple(img.shape)}")
+    B, h, w = img.shape[:3]
+    if sizes is not None and geom is not None:
+        raise RuntimeError(f"{fn}: give sizes or a geometry table, not both")
+    table = None
+    if sizes is not None:
+        table = data.frame_sizes(sizes, B, fn)
+        for b, (ih, iw) in enumerate(table.tolist()):
+            if ih <= 0 or iw <= 0 or ih > h or iw > w:
+                raise RuntimeError(f"{fn}: image {b}: bad size {ih} x {iw} in a slot of {h} x {w}")
+    _jpeg_params(quality, subsampling, fn)    # before anything is enqueued
+    img = img.to(device, non_blocking=True).contiguous()
+    dev = img.device
+    with torch.cuda.device(dev):
+        out = jpeg_buffers(B, h, w, quality, subsampling, capacity, flag, dev, fn)
+        if table is not None:
+            table = torch.from_numpy(np.ascontiguousarray(table, np.int32)).pin_memory().to(dev, non_blocking=True)
+        hip.jpeg_encode(img, out.header, out.arena, out.record, out.workspace, out.subsampling, sizes=table, geom=geom, flag=out.flag)
     return out

@@ -1,7 +1,9 @@
 """The optional stages of `infer.FramePipeline`, one class each, and STAGES, their launch order.  A class holds everything
 its feature needs of the pipeline: the keyword and its checks, the buffers, the launches, the result fields, the ragged
 per-call check and its part of `infer.predict_dir`; its docstring is the feature's documentation.  `FramePipeline` parses
-STAGES in order, keeps the stages that are on as `pipeline.stages` and calls their hooks where `infer`'s docstring says."""
+STAGES in order, keeps the stages that are on as `pipeline.stages` and calls their hooks where `infer`'s docstring says.
+OUTPUTS, at the end of the file, holds the stages that turn a finished picture into what leaves the device (`Jpeg`): they are
+parsed behind STAGES, kept behind them in `pipeline.stages` and run at the `output` hook point."""
 import os
 
 import numpy as np
@@ -35,7 +37,7 @@ class Stage:
     the "must be on a HIP device" check; `early = False` moves a stage's parse behind it, where the palettes exist.
     static(p, hip): the buffers that follow from the frame shape alone; allocate(p, hip, cap): those that need `cap`.  Both
     run before the capture.  ready(p): after the warm-up and the capture, which ran the chain on zero input.
-    frames / rows / class_map / picture (p, c): the launches at that hook point of the chain.  c is the context of one pass:
+    frames / rows / class_map / picture / output (p, c): the launches at that hook point of the chain.  c is the context of one pass:
     hip, geom (the geometry table of a ragged pipeline, or None), frames (what everything later reads: a stage may replace
     it), det, class_map, boxes / labels / label_sizes (arguments of the render node), rendered, and out, the dict of the
     optional result fields -- a stage writes those it names in `fields` and may read those of the stages in front of it.
@@ -58,6 +60,7 @@ class Stage:
     def rows(self, p, c): pass
     def class_map(self, p, c): pass
     def picture(self, p, c): pass
+    def output(self, p, c): pass
     def folder(self, p): pass
 
     def check(self, p, sizes):
@@ -598,3 +601,70 @@ class Heatmap(Stage):
 
 # the launch order: within a hook point of the chain the stages run in this order (the table of infer's docstring)
 STAGES = (Dehaze, Ace, Crops, Chips, BoxRadar, Track, Captions, Regions, Labels, Heatmap)
+
+
+def jpeg_config(jpeg, render):
+    """The encoder of a pipeline from its jpeg= keyword: None (no files), True (quality 95, 4:4:4, the rendered frame, the
+    default capacity) or a dict of quality, subsampling, source and capacity.  Returns None or a dict of all four, checked:
+    source is "rendered" (it needs render=True) or "frames"."""
+    if _off(jpeg):
+        return None
+    cfg = {} if jpeg is True else jpeg
+    if not isinstance(cfg, dict) or set(cfg) - {"quality", "subsampling", "source", "capacity"}:
+        raise RuntimeError(f"{FN}: jpeg is None, True or a dict of quality, subsampling, source, capacity, got {jpeg!r}")
+    quality, subsampling = rendering._jpeg_params(cfg.get("quality", 95), cfg.get("subsampling", 0), f"{FN}: jpeg")
+    source, capacity = cfg.get("source", "rendered"), cfg.get("capacity")
+    if source not in ("rendered", "frames"):
+        raise RuntimeError(f"{FN}: jpeg: source is 'rendered' or 'frames', got {source!r}")
+    if source == "rendered" and not render:
+        raise RuntimeError(f"{FN}: jpeg: source='rendered' encodes the rendered frame; it needs render=True (or source='frames')")
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or
+                                 not rendering.JPEG_HEADER + 2 <= int(capacity) < (1 << 31) - 64):
+        raise RuntimeError(f"{FN}: jpeg: capacity is the bytes of one slot of the arena, {rendering.JPEG_HEADER + 2}..2^31 - 65, "
+                           f"got {capacity!r}")
+    return dict(quality=quality, subsampling=subsampling, source=source, capacity=None if capacity is None else int(capacity))
+
+
+class Jpeg(Stage):
+    """jpeg: None (the default: exactly the calls issued without it), True or a dict of quality (95), subsampling (0: 4:4:4, or
+    2: 4:2:0), source and capacity -- every picture of the batch leaves the device as a finished baseline JPEG file
+    (`render.jpeg_encode`, csrc/jpeg.hip; `render.jpeg_encode_host` is the rule: the bytes Pillow's `save(format="JPEG",
+    quality=, subsampling=)` writes).  source: "rendered" (the default; it needs render=True) or "frames", what the renderer
+    reads -- the dehazed or enhanced frame when those stages are on.  `FrameResult.jpeg` is its `render.Jpegs`:
+    `jpeg.bytes()[b]` is the file of picture b, of its own size from a ragged pipeline (SOF0 carries (ih_b, iw_b) of the
+    geometry table).  Arena, record, header template and workspace are allocated before the capture; the eight launches of
+    hip.jpeg_encode are the last of the chain, at the `output` hook point behind `picture`.  capacity: the bytes of a slot
+    of the arena, default `render.jpeg_capacity(ih, iw)` = 623 + 3 ih iw; a file that does not fit gets length 0 and
+    FLAG_JPEG_ARENA joins the bits of `flag`.  Not an entry of STAGES, whose ten names are pinned: an OUTPUT, parsed from
+    OUTPUTS and kept behind the ten in `pipeline.stages`.  `predict_dir` writes <stem>.jpg straight from the bytes, beside
+    <stem>.png."""
+    name, fields = "jpeg", ("jpeg",)
+
+    @classmethod
+    def parse(cls, p, kw):
+        p.jpeg = jpeg_config(kw["jpeg"], p.render)
+        if p.jpeg is None:
+            return None
+        rendering.jpeg_shape(*p.frame_shape, p.jpeg["subsampling"], f"{FN}: jpeg")
+        return cls()
+
+    def static(self, p, hip):
+        self.buffers = rendering.jpeg_buffers(p.batch, *p.frame_shape, p.jpeg["quality"], p.jpeg["subsampling"],
+                                              p.jpeg["capacity"], p.flag, p.device, f"{FN}: jpeg")
+
+    def output(self, p, c):
+        b = c.out["jpeg"] = self.buffers
+        c.hip.jpeg_encode(c.rendered if p.jpeg["source"] == "rendered" else c.frames, b.header, b.arena, b.record, b.workspace,
+                          b.subsampling, geom=c.geom, flag=p.flag)
+
+    def read(self, result):
+        return result.jpeg.bytes()
+
+    def save(self, host, b, stem, size, det, dst):
+        if host[b]:
+            with open(os.path.join(dst, stem + ".jpg"), "wb") as f:
+                f.write(host[b])
+
+
+# what leaves the device in its final form: parsed behind STAGES and kept behind them in `pipeline.stages`
+OUTPUTS = (Jpeg,)

@@ -1593,6 +1593,32 @@ int vrnet_chip_boxes_u8(const unsigned char* frames, int B, int ihm, int iwm, co
                         const int* offsets, int n_cap, int sh, int sw, int letterbox, unsigned char* chips, float* chips_f32,
                         vrnet_chip_rec* table, int* summary, void* workspace, int* flag, void* stream);
 
+/* ---- baseline JPEG (csrc/jpeg.hip) ------------------------------------------------------------------------------------------
+ * Added within ABI 11: two new symbols and one new flag bit only, no existing signature, layout or kernel behaviour changed.
+ * Every image of a batch to a complete baseline JFIF file, every byte the one Pillow (libjpeg-turbo) writes for
+ * Image.save(format="JPEG", quality=q, subsampling=0 or 2).  The rule is stated on the host by render.jpeg_encode_host (integer
+ * colour conversion, edge replication, the 4:2:0 box reduction with its alternating bias and its dummy blocks, jfdctint,
+ * rounding quantisation, the Annex K Huffman tables, one DC predictor per component, byte stuffing) and at the top of
+ * csrc/jpeg.hip, and the kernels equal it byte for byte.
+ * vrnet_jpeg_encode_u8: images (B, H, W, 3) u8 RGB.  The size (h, w) of image b, in the top-left corner of its slot, is
+ *   geom[b].ih, iw, or sizes[2 b], sizes[2 b + 1] ((B, 2) int32), or H, W when both are NULL (at most one of the two may be
+ *   given); it is clamped to the slot, which sets bit 256 of *flag (VR_FLAG_GEOMETRY), and an image without pixels gets the
+ *   record (0, 3).  subsampling: 0 (4:4:4) or 2 (4:2:0).  header: the 623 bytes in front of the scan data on the device
+ *   (render.jpeg_header), whose two DQT segments are the quantisation tables the kernels use; height and width (bytes
+ *   163..166) are written per image.  arena (B, capacity) u8: slot b holds the file in its first record[2 b] bytes; bytes
+ *   behind that are not defined.  record (B, 2) int32 = (length, state): state 1 a complete file; 2 the file did not fit
+ *   capacity: length 0, bit 262144 of *flag (VR_FLAG_JPEG_ARENA), the other images unaffected; 3 no pixels.
+ *   workspace: vrnet_jpeg_workspace_bytes(B, H, W, subsampling, capacity) bytes, 16-byte aligned (-1: a bad shape): the int16
+ *   coefficients in scan and zigzag order (128 bytes a block), a bit offset per block, and the unstuffed bit stream
+ *   (capacity bytes an image).  Eight launches (blocks, lengths, scan, zero, emit, count, scan, pack), no host
+ *   synchronisation, no allocation, integer atomics only: the same bytes on every run.  Bit offsets are 32-bit, which the
+ *   limit of 2^20 blocks a slot (at most 1658 bits each) guarantees.
+ *   0 < B < 65536, 1 <= H, W <= 65535, 625 <= capacity < 2^31 - 64; flag may be NULL. */
+long vrnet_jpeg_workspace_bytes(int B, int H, int W, int subsampling, long capacity);
+int vrnet_jpeg_encode_u8(const unsigned char* images, int B, int H, int W, const vrnet_frame_geom* geom, const int* sizes,
+                         int subsampling, const unsigned char* header, unsigned char* arena, long capacity, int* record, int* flag,
+                         void* workspace, long workspace_bytes, void* stream);
+
 /* ---- connected regions of the class map (csrc/regions.hip) -----------------------------------------------------------------
  * Added within ABI 11: two new symbols, one new record layout (vrnet_region) and one new flag bit only, no existing signature,
  * layout or kernel behaviour changed; hip.py binds every declared symbol at import.
