@@ -143,14 +143,9 @@ __global__ __launch_bounds__(256) void ace_init_kernel(const AceArgs p) {
   }
   if (tid < 8) p.recd[b * 8 + tid] = 0.0;
   if (tid == 0) {
-    int ih = p.ihm, iw = p.iwm;
-    bool bad = false;
-    if (p.geom) {
-      const int gh = p.geom[b].ih, gw = p.geom[b].iw;
-      ih = vr_clampi(gh, 0, p.ihm);
-      iw = vr_clampi(gw, 0, p.iwm);
-      bad = gh <= 0 || gw <= 0 || ih != gh || iw != gw;
-    }
+    int ih, iw;
+    bool bad;
+    vr_image_size(p.geom, b, p.ihm, p.iwm, p.ihm, p.iwm, ih, iw, bad);
     int state = 0, nl = 0;
     if (bad) {
       state = ACE_BAD;
@@ -469,8 +464,6 @@ __global__ __launch_bounds__(256) void ace_store_kernel(const AceArgs p, const A
   dst[2] = (unsigned char)q[2];
 }
 
-inline long ace_align(long v) { return (v + 255) & ~255L; }
-
 struct AceLayout {
   long rec, keys, recd, hist, total;
   long I[ACE_MAXLEVELS], R[ACE_MAXLEVELS];
@@ -480,10 +473,10 @@ struct AceLayout {
 AceLayout ace_layout(int B, int ihm, int iwm) {
   AceLayout l;
   l.rec = 0;
-  l.keys = ace_align(l.rec + (long)sizeof(AceRec) * B);
-  l.recd = ace_align(l.keys + 48L * B);
-  l.hist = ace_align(l.recd + 64L * B);
-  long at = ace_align(l.hist + 12L * ACE_MAXBINS * B);
+  l.keys = vr_align256(l.rec + (long)sizeof(AceRec) * B);
+  l.recd = vr_align256(l.keys + 48L * B);
+  l.hist = vr_align256(l.recd + 64L * B);
+  long at = vr_align256(l.hist + 12L * ACE_MAXBINS * B);
   l.nl = 0;
   l.hm[0] = ihm;
   l.wm[0] = iwm;
@@ -493,7 +486,7 @@ AceLayout ace_layout(int B, int ihm, int iwm) {
     ++l.nl;
   }
   for (int L = 0; L <= l.nl; ++L) {
-    const long plane = ace_align(24L * B * l.hm[L] * l.wm[L]);
+    const long plane = vr_align256(24L * B * l.hm[L] * l.wm[L]);
     l.I[L] = -1;
     if (L > 0) {
       l.I[L] = at;

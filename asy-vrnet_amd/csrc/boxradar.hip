@@ -29,6 +29,7 @@
 //            features are gathered from `points` by index at the end.
 // Integer atomics only (the one global atomic is the OR into *flag), counts and exact selections: the same bytes on every run.
 #include "radarpoint.h"
+#include "wgscan.h"
 
 #pragma clang fp contract(off)
 
@@ -86,11 +87,6 @@ __global__ __launch_bounds__(256) void box_radar_project_kernel(const BoxRadarAr
   p.hw[at] = hw;
 }
 
-__device__ __forceinline__ unsigned long long br_shfl_xor(unsigned long long k, int o) {
-  const unsigned lo = __shfl_xor((unsigned)k, o, 64), hi = __shfl_xor((unsigned)(k >> 32), o, 64);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 // the candidates of this box among the image's n projected points whose key equals `prefix` on the bits of `mask`: their
 // number and their smallest key, the same in every thread.  red_n / red_k: four slots each; ends behind a barrier
 __device__ __forceinline__ void br_sweep(const float* pu, const float* pv, const float* ph, int n, float x0, float x1, float y0,
@@ -110,17 +106,12 @@ __device__ __forceinline__ void br_sweep(const float* pu, const float* pv, const
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    c += __shfl_xor(c, o, 64);
-    const unsigned long long t = br_shfl_xor(k, o);
+    const unsigned long long t = vr_shfl_xor64(k, o);
     k = t < k ? t : k;
   }
   __syncthreads();                     // the slots may still be read from the sweep before
-  if ((threadIdx.x & 63) == 0) {
-    red_n[threadIdx.x >> 6] = c;
-    red_k[threadIdx.x >> 6] = k;
-  }
-  __syncthreads();
-  count = (red_n[0] + red_n[1]) + (red_n[2] + red_n[3]);
+  if ((threadIdx.x & 63) == 0) red_k[threadIdx.x >> 6] = k;
+  count = vr_block_sum(c, red_n);      // its barrier stands behind the keys too
   best = red_k[0];
 #pragma unroll
   for (int w = 1; w < 4; ++w) best = red_k[w] < best ? red_k[w] : best;
@@ -172,12 +163,7 @@ __global__ __launch_bounds__(256) void box_radar_select_kernel(const BoxRadarArg
 #pragma unroll
           for (int j = 0; j < 4; ++j) h4[j] = hist[4 * tid + j];
           const unsigned own = (h4[0] + h4[1]) + (h4[2] + h4[3]);
-          unsigned incl = own;
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) {
-            const unsigned up = __shfl_up(incl, o, 64);
-            if (tid >= o) incl += up;
-          }
+          const unsigned incl = vr_wave_scan_incl(own);
           unsigned before = incl - own, sel = h4[0];
           if ((unsigned)rank >= before && (unsigned)rank < incl) {
             int j = 0;
@@ -221,7 +207,7 @@ __global__ __launch_bounds__(256) void box_radar_select_kernel(const BoxRadarArg
   }
 }
 
-long box_radar_bytes(int B, int max_points) { return (((long)B * max_points * 12) + 255) & ~255L; }
+long box_radar_bytes(int B, int max_points) { return vr_align256((long)B * max_points * 12); }
 
 }  // namespace
 

@@ -253,8 +253,8 @@ __global__ __launch_bounds__(CP_THREADS) void captions_kernel(const DrawArgs p) 
     ih = g.ih; iw = g.iw;
     if (sidx < 0 || sidx >= p.n_sizes) return;        // no captions for this image
   }
-  const int start = vr_clampi(p.offsets[b], 0, p.n_rows);
-  int n = vr_clampi(p.offsets[b + 1], start, p.n_rows) - start;
+  int start, n;
+  vr_row_range(p.offsets, b, p.n_rows, start, n);
   if (n > CP_MAXROWS) {
     if (first && p.flag) atomicOr(p.flag, CP_FLAG_BOX_ROWS);
     n = CP_MAXROWS;

@@ -58,16 +58,6 @@ struct ChipArgs {
   int B, ihm, iwm, n_cap, sh, sw, letterbox;
 };
 
-// the size of image b: the table's, clamped to the slot (crop_image_size of crops.hip)
-__device__ __forceinline__ void chip_image_size(const ChipArgs& p, int b, int& ih, int& iw, bool& bad) {
-  ih = p.ihm; iw = p.iwm; bad = false;
-  if (p.geom) {
-    const int gh = p.geom[b].ih, gw = p.geom[b].iw;
-    ih = vr_clampi(gh, 0, p.ihm); iw = vr_clampi(gw, 0, p.iwm);
-    bad = gh <= 0 || gw <= 0 || ih != gh || iw != gw;
-  }
-}
-
 // the clamp of a row to its image (crop_window of crops.hip): x, y = l, t; z, w = w, h (both 0 for an empty crop)
 __device__ __forceinline__ int4 chip_window(const int* row, int ih, int iw) {
   const int l = vr_clampi(row[0], 0, iw), t = vr_clampi(row[1], 0, ih);
@@ -149,7 +139,7 @@ __global__ __launch_bounds__(256) void chip_tables_kernel(const ChipArgs p) {
   const int b = s_image;
   int ih, iw;
   bool bad;
-  chip_image_size(p, b, ih, iw, bad);
+  vr_image_size(p.geom, b, p.ihm, p.iwm, p.ihm, p.iwm, ih, iw, bad);
   const int4 q = chip_window(p.rows + 5L * n, ih, iw);
   if (tid == 0 && bad && p.flag) atomicOr(p.flag, VR_FLAG_GEOMETRY);
   if (q.z == 0) {
@@ -174,7 +164,7 @@ __global__ __launch_bounds__(256) void chip_resample_kernel(const ChipArgs p, in
   if (rec.state == 0 || rec.image < 0 || rec.image >= p.B) return;          // behind the last row: nothing is written
   int ih, iw;
   bool bad;
-  chip_image_size(p, rec.image, ih, iw, bad);
+  vr_image_size(p.geom, rec.image, p.ihm, p.iwm, p.ihm, p.iwm, ih, iw, bad);
   const int4 q = chip_window(p.rows + 5L * n, ih, iw);
   const int w = q.z, h = q.w, sh = p.sh, sw = p.sw;
   const int4 g = w > 0 ? chip_geometry(w, h, sh, sw, p.letterbox) : make_int4(0, 0, 0, 0);

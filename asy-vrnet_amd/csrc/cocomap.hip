@@ -371,8 +371,6 @@ __global__ __launch_bounds__(CM_SUM_BLOCK) void cm_summarise_kernel(const CocoAr
   if (tid == 0) p.stats[s] = scnt[0] ? ssum[0] / (double)scnt[0] : -1.0;
 }
 
-long cm_align(long n) { return (n + 255) & ~255L; }
-
 }  // namespace
 
 extern "C" long vrnet_coco_map_group_bytes(int n_det, int n_gt) {
@@ -382,7 +380,7 @@ extern "C" long vrnet_coco_map_group_bytes(int n_det, int n_gt) {
 
 extern "C" long vrnet_coco_map_workspace_bytes(int D, long slice_bytes) {
   if (D < 0 || slice_bytes < 0) return 0;
-  return 256 + cm_align((long)CM_CH * D) + cm_align(slice_bytes);
+  return 256 + vr_align256((long)CM_CH * D) + vr_align256(slice_bytes);
 }
 
 extern "C" int vrnet_coco_map_f64(const double* det_box, const int* order, const int* rank, const int* class_slot,
@@ -417,7 +415,7 @@ extern "C" int vrnet_coco_map_f64(const double* det_box, const int* order, const
   p.thr = iou_thrs; p.rec = rec_thrs;
   p.match = dt_match; p.code = dt_code; p.n_gt = n_gt; p.precision = precision; p.recall = recall; p.stats = stats;
   char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-  p.pack = reinterpret_cast<unsigned char*>(w);   w += cm_align((long)CM_CH * D);
+  p.pack = reinterpret_cast<unsigned char*>(w);   w += vr_align256((long)CM_CH * D);
   p.slices = reinterpret_cast<unsigned char*>(w);
   p.slice_bytes = slice_bytes;
   const hipStream_t st = vr_stream(stream);

@@ -47,6 +47,8 @@ static inline hipStream_t vr_stream(void* s) { return reinterpret_cast<hipStream
 static inline long vr_cdiv(long a, long b) { return (a + b - 1) / b; }
 // Workgroups of the XCD-aware tile map for mt x nt tiles: the row tiles are padded to whole eights (one per XCD).
 static inline long vr_xcd_tiles(long mt, long nt) { return 8 * vr_cdiv(mt, 8) * nt; }
+// workspace parts begin on 256-byte boundaries
+static inline long vr_align256(long n) { return (n + 255) & ~255L; }
 static inline bool vr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // stream_ops.hip: the work split of the moments kernel on 16-byte accesses (C % 4 == 0), and the launch that finishes its
@@ -152,6 +154,26 @@ __device__ __forceinline__ vrnet_frame_geom vr_geom_load(const vrnet_frame_geom*
           g.seg_left != t.seg_left || g.seg_top != t.seg_top;
   }
   return g;
+}
+
+// The size rule of vr_geom_load alone, for the stages that read nothing else of a record: (gh, gw) clamped to the slot.
+// bad: something was clamped, or a side is not positive.
+__device__ __forceinline__ void vr_size_clamp(int gh, int gw, int ihm, int iwm, int& ih, int& iw, bool& bad) {
+  ih = vr_clampi(gh, 0, ihm);
+  iw = vr_clampi(gw, 0, iwm);
+  bad = gh <= 0 || gw <= 0 || ih != gh || iw != gw;
+}
+// The size of image b inside its (ihm, iwm) slot: the table's under that rule; (ih0, iw0) without a table.
+__device__ __forceinline__ void vr_image_size(const vrnet_frame_geom* geom, int b, int ihm, int iwm, int ih0, int iw0, int& ih,
+                                              int& iw, bool& bad) {
+  ih = ih0; iw = iw0; bad = false;
+  if (geom) vr_size_clamp(geom[b].ih, geom[b].iw, ihm, iwm, ih, iw, bad);
+}
+
+// The draw rows of image b in a table of n_rows: offsets[b] .. offsets[b + 1], clamped so that no row lies outside it.
+__device__ __forceinline__ void vr_row_range(const int* offsets, int b, int n_rows, int& start, int& n) {
+  start = vr_clampi(offsets[b], 0, n_rows);
+  n = vr_clampi(offsets[b + 1], start, n_rows) - start;
 }
 
 // Pillow's nearest resize of an axis in -> out (Geometry.c ImagingScaleAffine): the source index of each output index, a

@@ -22,6 +22,7 @@
 // crop's block; every dword is stored once, by one lane, with its four bytes gathered from the frame.  It trusts the record
 // for the offset alone, and checks that: l, t, w, h are derived again from the row.
 #include "common.h"
+#include "wgscan.h"
 
 #include <climits>
 
@@ -42,51 +43,12 @@ struct CropArgs {
   int B, ihm, iwm, n_cap;
 };
 
-// the size of image b: the table's, clamped to the slot
-__device__ __forceinline__ void crop_image_size(const CropArgs& p, int b, int& ih, int& iw, bool& bad) {
-  ih = p.ihm; iw = p.iwm; bad = false;
-  if (p.geom) {
-    const int gh = p.geom[b].ih, gw = p.geom[b].iw;
-    ih = vr_clampi(gh, 0, p.ihm); iw = vr_clampi(gw, 0, p.iwm);
-    bad = gh <= 0 || gw <= 0 || ih != gh || iw != gw;
-  }
-}
-
 // the clamp of a row to its image: x, y = l, t; z, w = w, h (both 0 for an empty crop)
 __device__ __forceinline__ int4 crop_window(const int* row, int ih, int iw) {
   const int l = vr_clampi(row[0], 0, iw), t = vr_clampi(row[1], 0, ih);      // clamped to both ends: l > iw is empty either
   const int r = vr_clampi(row[2], 0, iw), bt = vr_clampi(row[3], 0, ih);     // way, and no difference can overflow
   const int w = r - l, h = bt - t;
   return (w <= 0 || h <= 0) ? make_int4(l, t, 0, 0) : make_int4(l, t, w, h);
-}
-
-// inclusive scans of one value per thread over the workgroup of 256, thread order; s_wave[4] is rewritten by the next call,
-// so the caller synchronises in between
-__device__ __forceinline__ long long block_prefix_sum(long long v, long long* s_wave, long long& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) v += s_wave[w];
-  total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-  return v;
-}
-__device__ __forceinline__ int block_prefix_max(int v, int* s_wave, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v = max(v, u);
-  }
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) v = max(v, s_wave[w]);
-  total = max(max(s_wave[0], s_wave[1]), max(s_wave[2], s_wave[3]));
-  return v;
 }
 
 __global__ __launch_bounds__(256) void crop_layout_kernel(const CropArgs p) {
@@ -104,7 +66,7 @@ __global__ __launch_bounds__(256) void crop_layout_kernel(const CropArgs p) {
   for (int i0 = 0; i0 < p.B; i0 += 256) {
     const int nimg = min(256, p.B - i0);
     int chunk_max;
-    const int mine = block_prefix_max(tid < nimg ? p.offsets[i0 + tid + 1] : INT_MIN, s_maxw, chunk_max);
+    const int mine = vr_block_scan_incl<vr_op_max>(tid < nimg ? p.offsets[i0 + tid + 1] : INT_MIN, s_maxw, chunk_max);
     s_end[tid] = min(N, max(run, mine));              // threads past nimg: the chunk's end
     run = max(run, chunk_max);
     __syncthreads();
@@ -123,13 +85,13 @@ __global__ __launch_bounds__(256) void crop_layout_kernel(const CropArgs p) {
         b = i0 + lo;
         int ih, iw;
         bool bad;
-        crop_image_size(p, b, ih, iw, bad);
+        vr_image_size(p.geom, b, p.ihm, p.iwm, p.ihm, p.iwm, ih, iw, bad);
         badgeom |= bad;
         q = crop_window(p.rows + 5L * n, ih, iw);
       }
       const long long a = ((long long)q.z * q.w + 3) & ~3LL;
       long long total;
-      const long long off = base + block_prefix_sum(a, s_sumw, total) - a;
+      const long long off = base + vr_block_scan_incl<vr_op_sum>(a, s_sumw, total) - a;
       base += total;
       if (valid) {
         vrnet_crop_rec rec{0, q.z, q.w, b};
@@ -168,7 +130,7 @@ __global__ __launch_bounds__(256) void crop_copy_kernel(const CropArgs p, int xb
   if (rec.offset < 0 || rec.w <= 0 || rec.h <= 0 || rec.image < 0 || rec.image >= p.B) return;
   int ih, iw;
   bool bad;
-  crop_image_size(p, rec.image, ih, iw, bad);
+  vr_image_size(p.geom, rec.image, p.ihm, p.iwm, p.ihm, p.iwm, ih, iw, bad);
   const int4 q = crop_window(p.rows + 5L * n, ih, iw);
   const long long a = ((long long)q.z * q.w + 3) & ~3LL;
   if (a == 0 || (long long)rec.offset + a > p.capacity) return;          // a record that is not this row's: nothing is written

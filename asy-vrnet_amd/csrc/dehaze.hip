@@ -45,6 +45,7 @@
 // its start -- the caller may read A there --, then the integer records, histograms, sums and chunk counts, dark8, and seven
 // float64 planes of B ihm iwm: te, four horizontal sums (the first two reused for a and b's), a, b.
 #include "common.h"
+#include "wgscan.h"
 
 #include <climits>
 
@@ -101,14 +102,9 @@ __global__ __launch_bounds__(256) void dh_init_kernel(const DhArgs p) {
   p.hist[b * 256 + tid] = 0;
   if (tid < 4) p.sums[b * 4 + tid] = 0ull;
   if (tid == 0) {
-    int ih = p.ihm, iw = p.iwm;
-    bool bad = false;
-    if (p.geom) {
-      const int gh = p.geom[b].ih, gw = p.geom[b].iw;
-      ih = vr_clampi(gh, 0, p.ihm);
-      iw = vr_clampi(gw, 0, p.iwm);
-      bad = gh <= 0 || gw <= 0 || ih != gh || iw != gw;
-    }
+    int ih, iw;
+    bool bad;
+    vr_image_size(p.geom, b, p.ihm, p.iwm, p.ihm, p.iwm, ih, iw, bad);
     int state = 0;
     if (bad) {
       state = DH_BAD;
@@ -239,18 +235,15 @@ __global__ __launch_bounds__(256) void dh_count_kernel(const DhArgs p) {
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((tid & 63) == 0) s_wave[tid >> 6] = c;
-  __syncthreads();
-  if (tid == 0) p.cnt[(long)b * p.nchunks + blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  c = vr_block_sum(c, s_wave);
+  if (tid == 0) p.cnt[(long)b * p.nchunks + blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(256) void dh_sum_kernel(const DhArgs p) {
   __shared__ int s_wave[4];
   __shared__ int s_scan[4];
   __shared__ unsigned int s_sum[3];
-  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, tid = threadIdx.x;
   const DhRec rec = p.rec[b];
   if (rec.state & DH_BAD) return;
   const long n = (long)rec.ih * rec.iw, c0 = (long)blockIdx.x * DH_CHUNK;
@@ -258,12 +251,8 @@ __global__ __launch_bounds__(256) void dh_sum_kernel(const DhArgs p) {
   // the bin-T pixels of the earlier chunks
   int before = 0;
   for (int i = tid; i < (int)blockIdx.x; i += 256) before += p.cnt[(long)b * p.nchunks + i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-  if (lane == 0) s_wave[wave] = before;
   if (tid < 3) s_sum[tid] = 0u;
-  __syncthreads();
-  before = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  before = vr_block_sum(before, s_wave);            // its barrier also stands behind the zeros of s_sum
   const long f0 = c0 + (long)tid * DH_PER_THREAD;
   const unsigned char* dark = p.dark + (long)b * p.ihm * p.iwm;
   const unsigned char* frame = p.frames + 3L * b * p.ihm * p.iwm;
@@ -280,16 +269,8 @@ __global__ __launch_bounds__(256) void dh_sum_kernel(const DhArgs p) {
       }
     }
   }
-  int incl = mine;                                  // the inclusive prefix over the workgroup, thread order
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += u;
-  }
-  if (lane == 63) s_scan[wave] = incl;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) incl += s_scan[w];
-  int rank = before + incl - mine;                  // of this thread's first bin-T pixel
+  int total;                                        // the inclusive prefix over the workgroup, thread order
+  int rank = before + vr_block_scan_incl<vr_op_sum>(mine, s_scan, total) - mine;      // of this thread's first bin-T pixel
   unsigned int s0 = 0, s1 = 0, s2 = 0;
   if (f0 < n) {
     for (int k = 0; k < DH_PER_THREAD && f0 + k < n; ++k) {
@@ -491,8 +472,6 @@ __global__ __launch_bounds__(256) void dh_box_v_kernel(const DhArgs p) {
   }
 }
 
-inline long dh_align(long v) { return (v + 255) & ~255L; }
-
 struct DhLayout {
   long recd, rec, hist, sums, cnt, dark, planes, plane, total;
   int nchunks;
@@ -502,13 +481,13 @@ DhLayout dh_layout(int B, int ihm, int iwm) {
   const long px = (long)ihm * iwm;
   l.nchunks = (int)vr_cdiv(px, DH_CHUNK);
   l.recd = 0;
-  l.rec = dh_align(l.recd + 32L * B);
-  l.hist = dh_align(l.rec + (long)sizeof(DhRec) * B);
-  l.sums = dh_align(l.hist + 1024L * B);
-  l.cnt = dh_align(l.sums + 32L * B);
-  l.dark = dh_align(l.cnt + 4L * B * l.nchunks);
-  l.planes = dh_align(l.dark + (long)B * px);
-  l.plane = dh_align(8L * B * px);
+  l.rec = vr_align256(l.recd + 32L * B);
+  l.hist = vr_align256(l.rec + (long)sizeof(DhRec) * B);
+  l.sums = vr_align256(l.hist + 1024L * B);
+  l.cnt = vr_align256(l.sums + 32L * B);
+  l.dark = vr_align256(l.cnt + 4L * B * l.nchunks);
+  l.planes = vr_align256(l.dark + (long)B * px);
+  l.plane = vr_align256(8L * B * px);
   l.total = l.planes + 7 * l.plane;
   return l;
 }

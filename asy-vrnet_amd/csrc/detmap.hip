@@ -292,13 +292,11 @@ __global__ void dm_mean_kernel(const DetMapArgs p) {
   p.map[t] = cnt ? sum / (double)cnt : 0.0;
 }
 
-long dm_align(long n) { return (n + 255) & ~255L; }
-
 }  // namespace
 
 extern "C" long vrnet_det_map_workspace_bytes(int D, int G, int T) {
   if (D < 0 || G < 0 || T <= 0) return 0;
-  return 256 + dm_align(4L * T * G) + 2 * dm_align(4L * T * D);
+  return 256 + vr_align256(4L * T * G) + 2 * vr_align256(4L * T * D);
 }
 
 extern "C" int vrnet_det_map_f64(const int* det_image, const int* det_label, const double* det_score, const double* det_box,
@@ -335,8 +333,8 @@ extern "C" int vrnet_det_map_f64(const int* det_image, const int* det_label, con
   p.n_gt = n_gt; p.n_img = n_img; p.n_tp = n_tp;
   p.ap = ap; p.f1 = f1; p.recall = recall; p.precision = precision; p.lamr = lamr; p.map = map;
   char* w = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-  p.first = reinterpret_cast<int*>(w);   w += dm_align(4L * T * G);
-  p.ctp = reinterpret_cast<int*>(w);     w += dm_align(4L * T * D);
+  p.first = reinterpret_cast<int*>(w);   w += vr_align256(4L * T * G);
+  p.ctp = reinterpret_cast<int*>(w);     w += vr_align256(4L * T * D);
   p.cfp = reinterpret_cast<int*>(w);
   const hipStream_t st = vr_stream(stream);
   // first = 0x7f7f7f7f: above every rank (D <= 2^24)

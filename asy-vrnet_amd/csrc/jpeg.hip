@@ -39,6 +39,7 @@
 // An image whose file does not fit `capacity` gets the record (0, 2) and nothing of its slot is written by the pack kernel;
 // a size record that had to be clamped sets VR_FLAG_GEOMETRY, one without pixels gives the record (0, 3).
 #include "common.h"
+#include "wgscan.h"
 
 namespace {
 
@@ -124,17 +125,8 @@ struct JpegArgs {
 
 // the size of image b (clamped to its slot; bad: it had to be) and its blocks
 __device__ __forceinline__ void jpeg_size(const JpegArgs& p, int b, int& h, int& w, bool& bad) {
-  int gh = p.H, gw = p.W;
-  if (p.geom) {
-    gh = p.geom[b].ih;
-    gw = p.geom[b].iw;
-  } else if (p.sizes) {
-    gh = p.sizes[2 * b];
-    gw = p.sizes[2 * b + 1];
-  }
-  h = vr_clampi(gh, 0, p.H);
-  w = vr_clampi(gw, 0, p.W);
-  bad = h != gh || w != gw || h <= 0 || w <= 0;
+  if (p.sizes && !p.geom) vr_size_clamp(p.sizes[2 * b], p.sizes[2 * b + 1], p.H, p.W, h, w, bad);
+  else vr_image_size(p.geom, b, p.H, p.W, p.H, p.W, h, w, bad);
   if (h <= 0 || w <= 0) h = w = 0;
 }
 __device__ __forceinline__ int jpeg_block_count(int h, int w, int sub) {
@@ -317,31 +309,6 @@ __device__ __forceinline__ unsigned long long jpeg_item(const short* coef, int k
   return 0ull;
 }
 
-__device__ __forceinline__ unsigned int jpeg_wave_sum(unsigned int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// the inclusive prefix over the lanes of a wave
-__device__ __forceinline__ unsigned int jpeg_wave_scan(unsigned int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-// the inclusive prefix over the 256 threads of a workgroup and their sum; s_wave[4] is rewritten by the next call
-__device__ __forceinline__ unsigned int jpeg_block_scan(unsigned int v, unsigned int* s_wave, unsigned int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = jpeg_wave_scan(v, lane);
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  for (int i = 0; i < wave; ++i) v += s_wave[i];
-  total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-  return v;
-}
-
 __global__ __launch_bounds__(256) void jpeg_length_kernel(const JpegArgs p) {
   __shared__ unsigned int s_wave[4];
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -358,11 +325,11 @@ __global__ __launch_bounds__(256) void jpeg_length_kernel(const JpegArgs p) {
     if (k >= nb) break;
     int len;
     jpeg_item(coef, k, h, w, p.sub, lane, len);
-    const unsigned int bits = jpeg_wave_sum((unsigned int)len);
+    const unsigned int bits = vr_wave_sum((unsigned int)len);
     if (lane == i) mine = bits;
   }
   unsigned int total;
-  const unsigned int incl = jpeg_block_scan(mine, s_wave, total);
+  const unsigned int incl = vr_block_scan_incl<vr_op_sum>(mine, s_wave, total);
   const int k = k0 + threadIdx.x;
   if (k < nb) p.bitoff[(long)b * p.nbmax + k] = incl - mine;
   if (threadIdx.x == 0) p.chunk[(long)b * p.nchunk + blockIdx.x] = total;
@@ -381,7 +348,7 @@ __global__ __launch_bounds__(256) void jpeg_scan_kernel(const JpegArgs p) {
     const int c = c0 + tid;
     const unsigned int v = c < nc ? chunk[c] : 0u;
     unsigned int total;
-    const unsigned int incl = jpeg_block_scan(v, s_wave, total);
+    const unsigned int incl = vr_block_scan_incl<vr_op_sum>(v, s_wave, total);
     if (c < nc) chunk[c] = base + incl - v;
     base += total;
     __syncthreads();
@@ -424,7 +391,7 @@ __global__ __launch_bounds__(256) void jpeg_emit_kernel(const JpegArgs p) {
     if (k >= nb) break;
     int len;
     const unsigned long long val = jpeg_item(coef, k, h, w, p.sub, lane, len);
-    const unsigned int pos = first + bitoff[k] + jpeg_wave_scan((unsigned int)len, lane) - (unsigned int)len;
+    const unsigned int pos = first + bitoff[k] + vr_wave_scan_incl((unsigned int)len) - (unsigned int)len;
     if (len > 0) {
       const unsigned int word = pos >> 5, off = pos & 31u;
       const unsigned long long X = val << (64 - len);                     // left-aligned; len <= 59
@@ -464,8 +431,7 @@ __global__ __launch_bounds__(256) void jpeg_ffcount_kernel(const JpegArgs p) {
   const long left = raw - 4 * idx;
   unsigned int c = 0;
   if (left > 0) c = jpeg_ff_bytes(jpeg_stream_word(p.words + (long)b * p.slotwords, idx, bits), (int)min(left, 4L));
-  unsigned int total;
-  jpeg_block_scan(c, s_wave, total);
+  const unsigned int total = vr_block_sum(c, s_wave);
   if (threadIdx.x == 0) p.ffc[(long)b * p.nstuff + blockIdx.x] = total;
 }
 
@@ -484,7 +450,7 @@ __global__ __launch_bounds__(256) void jpeg_ffscan_kernel(const JpegArgs p) {
     const int c = c0 + tid;
     const unsigned int v = c < nc ? ffc[c] : 0u;
     unsigned int total;
-    const unsigned int incl = jpeg_block_scan(v, s_wave, total);
+    const unsigned int incl = vr_block_scan_incl<vr_op_sum>(v, s_wave, total);
     if (c < nc) ffc[c] = base + incl - v;
     base += total;
     __syncthreads();
@@ -529,7 +495,7 @@ __global__ __launch_bounds__(256) void jpeg_pack_kernel(const JpegArgs p) {
   const unsigned int v = n ? jpeg_stream_word(p.words + (long)b * p.slotwords, idx, bits) : 0u;
   const unsigned int c = jpeg_ff_bytes(v, n);
   unsigned int total;
-  const unsigned int before = jpeg_block_scan(c, s_wave, total) - c + p.ffc[(long)b * p.nstuff + blockIdx.x];
+  const unsigned int before = vr_block_scan_incl<vr_op_sum>(c, s_wave, total) - c + p.ffc[(long)b * p.nstuff + blockIdx.x];
   unsigned char* dst = out + JP_HEADER + 4 * idx + before;
   for (int j = 0; j < n; ++j) {
     const unsigned char byte = (unsigned char)(v >> (24 - 8 * j));
@@ -551,14 +517,13 @@ bool jpeg_plan(int B, int H, int W, int sub, long capacity, JpegPlan& q) {
   q.nchunk = (int)vr_cdiv(nb, JP_SCAN_CHUNK);
   q.slotwords = (int)(vr_cdiv(capacity, 4) + 2);
   q.nstuff = (int)vr_cdiv(q.slotwords, JP_STUFF_CHUNK / 4);
-  auto up = [](long v) { return (v + 255) & ~255L; };
   long at = 0;
-  q.coef = at; at += up(2L * 64 * nb * B);
-  q.bitoff = at; at += up(4L * nb * B);
-  q.chunk = at; at += up(4L * q.nchunk * B);
-  q.head = at; at += up(16L * B);
-  q.words = at; at += up(4L * q.slotwords * B);
-  q.ffc = at; at += up(4L * q.nstuff * B);
+  q.coef = at; at += vr_align256(2L * 64 * nb * B);
+  q.bitoff = at; at += vr_align256(4L * nb * B);
+  q.chunk = at; at += vr_align256(4L * q.nchunk * B);
+  q.head = at; at += vr_align256(16L * B);
+  q.words = at; at += vr_align256(4L * q.slotwords * B);
+  q.ffc = at; at += vr_align256(4L * q.nstuff * B);
   q.total = at;
   return true;
 }

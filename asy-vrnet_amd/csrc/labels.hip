@@ -51,8 +51,6 @@ struct LabelArgs {
   int B, ih, iw, n_rows, n_box_colors, n_labels, n_sizes, size_index, thickness;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ __forceinline__ unsigned int div255(unsigned int a) {
   a += 128u;
   return (a + (a >> 8)) >> 8;
@@ -91,8 +89,8 @@ __global__ __launch_bounds__(256) void labels_kernel(const LabelArgs p) {
     ih = g.ih; iw = g.iw; thickness = g.thickness;
     if (sidx < 0 || sidx >= p.n_sizes) return;        // no labels for this image
   }
-  const int start = clampi(p.offsets[b], 0, p.n_rows);
-  int n = clampi(p.offsets[b + 1], start, p.n_rows) - start;
+  int start, n;
+  vr_row_range(p.offsets, b, p.n_rows, start, n);
   if (n > RN_MAXBOX) {
     if (first && p.flag) atomicOr(p.flag, RN_FLAG_BOX_ROWS);
     n = RN_MAXBOX;
@@ -101,14 +99,14 @@ __global__ __launch_bounds__(256) void labels_kernel(const LabelArgs p) {
   const int* recs = p.recs + (long)sidx * p.n_labels * LB_REC;
   for (int k = tid; k < n; k += 256) {
     const int* row = p.boxes + 5L * (start + k);
-    const int left = clampi(row[0], -RN_COORD, RN_COORD), top = clampi(row[1], -RN_COORD, RN_COORD);
-    s_box[k] = make_int4(left, top, clampi(row[2], -RN_COORD, RN_COORD), clampi(row[3], -RN_COORD, RN_COORD));
-    s_col[k] = (unsigned char)clampi(row[4], 0, p.n_box_colors - 1);
-    const int* rec = recs + (long)clampi(p.label_idx[start + k], 0, p.n_labels - 1) * LB_REC;
+    const int left = vr_clampi(row[0], -RN_COORD, RN_COORD), top = vr_clampi(row[1], -RN_COORD, RN_COORD);
+    s_box[k] = make_int4(left, top, vr_clampi(row[2], -RN_COORD, RN_COORD), vr_clampi(row[3], -RN_COORD, RN_COORD));
+    s_col[k] = (unsigned char)vr_clampi(row[4], 0, p.n_box_colors - 1);
+    const int* rec = recs + (long)vr_clampi(p.label_idx[start + k], 0, p.n_labels - 1) * LB_REC;
     const int off = rec[0];
-    int mw = clampi(rec[1], 0, LB_MAXDIM), mh = clampi(rec[2], 0, LB_MAXDIM);
-    const int mox = clampi(rec[3], -LB_MAXDIM, LB_MAXDIM), moy = clampi(rec[4], -LB_MAXDIM, LB_MAXDIM);
-    const int lw = clampi(rec[5], 0, LB_MAXDIM), lh = clampi(rec[6], 0, LB_MAXDIM);
+    int mw = vr_clampi(rec[1], 0, LB_MAXDIM), mh = vr_clampi(rec[2], 0, LB_MAXDIM);
+    const int mox = vr_clampi(rec[3], -LB_MAXDIM, LB_MAXDIM), moy = vr_clampi(rec[4], -LB_MAXDIM, LB_MAXDIM);
+    const int lw = vr_clampi(rec[5], 0, LB_MAXDIM), lh = vr_clampi(rec[6], 0, LB_MAXDIM);
     if (off < 0 || (long)off + (long)mw * mh > p.blob_bytes) mw = mh = 0;      // a mask outside the blob: no text
     const int ox = left, oy = top - lh >= 0 ? top - lh : top + 1;
     s_fill[k] = make_int4(ox, oy, ox + lw, oy + lh);
@@ -227,7 +225,7 @@ __global__ __launch_bounds__(256) void label_index_kernel(const IndexArgs p) {
   if (bad && p.flag) atomicOr(p.flag, LB_FLAG_SCORE);
   const int label = (int)r[6];
   if ((label < 0 || label >= p.nc) && p.flag) atomicOr(p.flag, NMS_FLAG_DET_CLASS);
-  p.out[pos] = clampi(label, 0, p.nc - 1) * LB_SCORES + idx;
+  p.out[pos] = vr_clampi(label, 0, p.nc - 1) * LB_SCORES + idx;
 }
 
 int labels_check(const char* fn, const LabelArgs& p, int num_classes) {

@@ -37,6 +37,7 @@
 //      pass through LDS; a wave per row over the records, reduced by shuffles), head, box_regions and the flag.
 // `left` of every record starts as INT_MAX, the neutral element of its integer minimum; the last launch zeroes it behind the count.
 #include "common.h"
+#include "wgscan.h"
 
 #include <climits>
 
@@ -62,15 +63,6 @@ struct RegionArgs {
   long npix;                               // ihm iwm
   int B, ihm, iwm, ih, iw, n_cap, cap, connectivity, background, min_area, max_regions, n_det, nchunks;
 };
-
-__device__ __forceinline__ void rg_size(const RegionArgs& p, int b, int& ih, int& iw, bool& bad) {
-  ih = p.ih; iw = p.iw; bad = false;
-  if (p.geom) {
-    const int gh = p.geom[b].ih, gw = p.geom[b].iw;
-    ih = vr_clampi(gh, 0, p.ihm); iw = vr_clampi(gw, 0, p.iwm);
-    bad = gh <= 0 || gw <= 0 || ih != gh || iw != gw;
-  }
-}
 
 // ---- union-find in LDS ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int rg_find_lds(volatile int* lab, int x) {
@@ -127,12 +119,8 @@ __device__ __forceinline__ bool rg_run(int key, int& length) {
 }
 
 __device__ __forceinline__ int rg_block_sum(int v, int* s_wave) {      // the sum over the 256 threads, in every thread
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   __syncthreads();                                                      // s_wave may still be read from the call before
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+  return vr_block_sum(v, s_wave);
 }
 
 __device__ __forceinline__ int rg_wave_before(const int* cnt, int wave) {      // the counts of the waves in front of this one
@@ -155,7 +143,7 @@ __global__ __launch_bounds__(256) void rg_tile_kernel(const RegionArgs p) {
   }
   int ih, iw;
   bool bad;
-  rg_size(p, b, ih, iw, bad);
+  vr_image_size(p.geom, b, p.ihm, p.iwm, p.ih, p.iw, ih, iw, bad);
   const unsigned char* src = p.cls + (long)b * p.npix;
   const int x = x0 + lx;
   int c[4];
@@ -211,7 +199,7 @@ __global__ __launch_bounds__(256) void rg_merge_kernel(const RegionArgs p, int n
   long t = (long)blockIdx.x * 256 + threadIdx.x;
   int ih, iw;
   bool bad;
-  rg_size(p, b, ih, iw, bad);
+  vr_image_size(p.geom, b, p.ihm, p.iwm, p.ih, p.iw, ih, iw, bad);
   const unsigned char* src = p.cls + (long)b * p.npix;
   int* par = p.parent + (long)b * p.npix;
   const bool eight = p.connectivity == 8;
@@ -267,7 +255,7 @@ __global__ __launch_bounds__(256) void rg_flatten_kernel(const RegionArgs p) {
   const int b = blockIdx.z, x = blockIdx.x * RG_TW + (threadIdx.x & 63), ly0 = threadIdx.x >> 6;
   int ih, iw;
   bool bad;
-  rg_size(p, b, ih, iw, bad);
+  vr_image_size(p.geom, b, p.ihm, p.iwm, p.ih, p.iw, ih, iw, bad);
   int* par = p.parent + (long)b * p.npix;
   int* area = p.area + (long)b * p.npix;
   if (threadIdx.x < RG_SLOTS) s_key[threadIdx.x] = s_area[threadIdx.x] = 0;
@@ -387,7 +375,7 @@ __global__ __launch_bounds__(256) void rg_label_kernel(const RegionArgs p) {
   const int b = blockIdx.z, x = blockIdx.x * RG_TW + (threadIdx.x & 63), ly0 = threadIdx.x >> 6;
   int ih, iw;
   bool bad;
-  rg_size(p, b, ih, iw, bad);
+  vr_image_size(p.geom, b, p.ihm, p.iwm, p.ih, p.iw, ih, iw, bad);
   const long off = (long)b * p.npix;
   vrnet_region* table = p.table + (long)b * p.max_regions;
   if (threadIdx.x < RG_SLOTS) {
@@ -471,7 +459,7 @@ __global__ __launch_bounds__(256) void rg_link_kernel(const RegionArgs p) {
   const int b = blockIdx.y, g = blockIdx.x, tid = threadIdx.x;
   int ih, iw;
   bool bad;
-  rg_size(p, b, ih, iw, bad);
+  vr_image_size(p.geom, b, p.ihm, p.iwm, p.ih, p.iw, ih, iw, bad);
   const int* part = p.partial + (long)b * p.nchunks * 4;
   int n = 0, kept = 0, dropped = 0;
   for (int c = tid; c < p.nchunks; c += 256) {

@@ -56,12 +56,10 @@ struct RenderArgs {
   float alpha;
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ __forceinline__ int4 load_row(const int* row, int& colour) {
   colour = row[4];
-  return make_int4(clampi(row[0], -RN_COORD, RN_COORD), clampi(row[1], -RN_COORD, RN_COORD),
-                   clampi(row[2], -RN_COORD, RN_COORD), clampi(row[3], -RN_COORD, RN_COORD));
+  return make_int4(vr_clampi(row[0], -RN_COORD, RN_COORD), vr_clampi(row[1], -RN_COORD, RN_COORD),
+                   vr_clampi(row[2], -RN_COORD, RN_COORD), vr_clampi(row[3], -RN_COORD, RN_COORD));
 }
 
 // first and one-past-last row of image b, kept inside the rows array whatever the offsets hold
@@ -69,8 +67,7 @@ __device__ __forceinline__ void row_range(const RenderArgs& p, int b, int& start
   start = 0;
   n = 0;
   if (!p.boxes) return;
-  start = clampi(p.offsets[b], 0, p.n_rows);
-  n = clampi(p.offsets[b + 1], start, p.n_rows) - start;
+  vr_row_range(p.offsets, b, p.n_rows, start, n);
 }
 
 __device__ __forceinline__ void raise_flag(const RenderArgs& p, int bit) {
@@ -125,7 +122,7 @@ __device__ void render_pixel(const RenderArgs& p, const unsigned int* s_pal, con
     int ci;
     const int4 q = load_row(p.boxes + 5L * (start + k), ci);
     if (on_rings(x, y, q, p.thickness)) {
-      v = s_bpal[clampi(ci, 0, p.n_box_colors - 1)];
+      v = s_bpal[vr_clampi(ci, 0, p.n_box_colors - 1)];
       painted = true;
       break;
     }
@@ -170,7 +167,7 @@ __global__ __launch_bounds__(256) void render_kernel(const RenderArgs p) {
         int ci;
         s_rows[k] = load_row(p.boxes + 5L * (start + k), ci);
         if (ci < 0 || ci >= p.n_box_colors) raise_flag(p, RN_FLAG_BOX_COLOUR);
-        s_rcol[k] = (unsigned char)clampi(ci, 0, p.n_box_colors - 1);
+        s_rcol[k] = (unsigned char)vr_clampi(ci, 0, p.n_box_colors - 1);
       }
       cur_b = pb;
       __syncthreads();
@@ -323,7 +320,7 @@ __global__ __launch_bounds__(256) void render_ragged_kernel(const RaggedRenderAr
     int ci;
     s_rows[k] = load_row(p.boxes + 5L * (start + k), ci);
     if (ci < 0 || ci >= p.n_box_colors) raise_flag(p, RN_FLAG_BOX_COLOUR);
-    s_rcol[k] = (unsigned char)clampi(ci, 0, p.n_box_colors - 1);
+    s_rcol[k] = (unsigned char)vr_clampi(ci, 0, p.n_box_colors - 1);
   }
   __syncthreads();
   const int slot = p.ih * p.iw, ngroups = (slot + 3) / 4;

@@ -18,6 +18,7 @@
 // such row with the k-th free slot.  Integer atomics only (LDS; the one global atomic is the OR into *flag); every word of
 // table, head and ids is a pure function of the inputs: the same bytes on every run.
 #include "common.h"
+#include "wgscan.h"
 
 #pragma clang fp contract(off)
 
@@ -35,6 +36,7 @@ static_assert(sizeof(vrnet_track) == 64 && alignof(vrnet_track) == 4 && offsetof
 namespace {
 
 constexpr int TK_THREADS = 256, TK_WAVES = 4;
+static_assert(TK_THREADS == VR_WG_THREADS && TK_WAVES == VR_WG_WAVES, "tk_scan is the 256-thread scan of wgscan.h over part[TK_WAVES]");
 constexpr int TK_MAX_TRACKS = 256, TK_MAX_ROWS = 1024;
 constexpr int TK_ROW_FLOATS = 7;     // top, left, bottom, right, obj, class_conf, class
 constexpr int TK_HEAD = 4;           // ids handed out, live tracks, calls, births of this call
@@ -57,11 +59,6 @@ struct TrackArgs {
 
 __device__ __forceinline__ bool tk_finite(float a) { return fabsf(a) < INFINITY; }
 
-__device__ __forceinline__ unsigned long long tk_shfl_xor(unsigned long long k, int o) {
-  const unsigned lo = __shfl_xor((unsigned)k, o, 64), hi = __shfl_xor((unsigned)(k >> 32), o, 64);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 // data.track_iou of one pair
 __device__ __forceinline__ float tk_iou(float t1, float l1, float b1, float r1, float t2, float l2, float b2, float r2) {
   const float ih = (b1 < b2 ? b1 : b2) - (t1 > t2 ? t1 : t2);
@@ -75,24 +72,8 @@ __device__ __forceinline__ float tk_iou(float t1, float l1, float b1, float r1, 
 
 // exclusive scan of one 0 / 1 value per thread over the 256 threads; tot: the sum.  part: four slots; ends behind a barrier
 __device__ __forceinline__ int tk_scan(int own, int* part, int& tot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = own;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += up;
-  }
   __syncthreads();                     // the slots may still be read from the scan before
-  if (lane == 63) part[wave] = incl;
-  __syncthreads();
-  int before = 0;
-  tot = 0;
-#pragma unroll
-  for (int w = 0; w < TK_WAVES; ++w) {
-    if (w < wave) before += part[w];
-    tot += part[w];
-  }
-  return before + incl - own;
+  return vr_block_scan_incl<vr_op_sum>(own, part, tot) - own;
 }
 
 // step 3's range update of one record from row i of the readout
@@ -188,7 +169,7 @@ __global__ __launch_bounds__(TK_THREADS) void track_update_kernel(const TrackArg
       if (__any(best != 0ULL)) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long other = tk_shfl_xor(best, o);
+          const unsigned long long other = vr_shfl_xor64(best, o);
           best = other > best ? other : best;
         }
       }

@@ -142,6 +142,42 @@ def _as_u8(a, what, batched, fn):
     return t[None] if t.dim() == batched - 1 else t
 
 
+def _as_frames(a, what, shapes, fn, empty_ok=False):
+    """`_as_u8` of a batch of pictures, (B, ih, iw, 3) with a single picture as B = 1: `what` and `shapes` word the error."""
+    img = _as_u8(a, what, 4, fn)
+    if img.dim() != 4 or img.shape[-1] != 3 or (min(img.shape) <= 0 and not empty_ok):
+        raise RuntimeError(f"{fn}: expected {what} of shape {shapes}, got {tuple(img.shape)}")
+    return img
+
+
+_FRAMES = "(B, ih, iw, 3) or (ih, iw, 3)"
+
+
+def _host_sizes(sizes, geom, B, ih, iw, fn, also=None):
+    """The sizes of B images in slots of (ih, iw), given on the host or in a device table, not in both: the checked (B, 2)
+    array of `sizes`, or None without them.  also(b, h, w): the caller's own check of image b, behind the slot check."""
+    from . import data
+    if sizes is not None and geom is not None:
+        raise RuntimeError(f"{fn}: give sizes or a geometry table, not both")
+    if sizes is None:
+        return None
+    arr = data.frame_sizes(sizes, B, fn)
+    for b, (h, w) in enumerate(arr.tolist()):
+        if h <= 0 or w <= 0 or h > ih or w > iw:
+            raise RuntimeError(f"{fn}: image {b}: bad size {h} x {w} in a slot of {ih} x {iw}")
+        if also is not None:
+            also(b, h, w)
+    return arr
+
+
+def _sizes_geom(arr, dev):
+    """The device geometry table of host sizes: ih, iw and a thickness of 1, nothing else."""
+    from . import data
+    table = np.zeros(len(arr), data.GEOM_DTYPE)
+    table["ih"], table["iw"], table["thickness"] = arr[:, 0], arr[:, 1], 1
+    return data.geometry_bytes(table).pin_memory().to(dev, non_blocking=True)
+
+
 def _palette(pal, default, fn):
     """(n, 3) uint8 numpy from None (the default), a class count or an array of colours."""
     if pal is None:
@@ -279,9 +315,7 @@ def render_frame(frames_u8, class_map=None, results=None, input_shape=None, pale
                                       ("font_size", font_size, None)), (("label_sizes", label_sizes, None),))
     if table and not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4):
         raise RuntimeError(f"{fn}: expected padded uint8 frames (B, ihm, iwm, 3) on a GPU")
-    img = _as_u8(frames_u8, "frames", 4, fn)
-    if img.dim() != 4 or img.shape[-1] != 3:
-        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    img = _as_frames(frames_u8, "frames", _FRAMES, fn, empty_ok=True)
     B, ih, iw = img.shape[:3]
     if min(B, ih, iw) <= 0:
         raise RuntimeError(f"{fn}: empty frames {tuple(img.shape)}")
@@ -1256,9 +1290,7 @@ def crop_boxes(frames_u8, results, capacity=None, geom=None, flag=None, device="
     dropped with every non-empty one behind it -- and hip.FLAG_GEOMETRY.  Returns a `Crops`.  No host synchronisation."""
     from . import hip
     fn = "crop_boxes"
-    img = _as_u8(frames_u8, "frames", 4, fn)
-    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
-        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    img = _as_frames(frames_u8, "frames", _FRAMES, fn)
     B, ih, iw = img.shape[:3]
     if results is None:
         raise RuntimeError(f"{fn}: needs the results of non_max_suppression or a device pair (rows, offsets)")
@@ -1491,9 +1523,7 @@ def chip_boxes(frames_u8, results, size, letterbox=False, normalised=False, geom
     from . import hip
     fn = "chip_boxes"
     size = _chip_size(size, fn)
-    img = _as_u8(frames_u8, "frames", 4, fn)
-    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
-        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    img = _as_frames(frames_u8, "frames", _FRAMES, fn)
     B, ih, iw = img.shape[:3]
     if results is None:
         raise RuntimeError(f"{fn}: needs the results of non_max_suppression or a device pair (rows, offsets)")
@@ -1648,32 +1678,24 @@ def dehaze(frames_u8, sizes=None, geom=None, sz=15, r=60, eps=1e-4, omega=0.95, 
     FLAG_DEHAZE for a degenerate image, which comes back unchanged with t = 1, and hip.FLAG_GEOMETRY for a bad record of
     the table, which gives a zero image.  A size known on the host (no table, or sizes) that
     allows no single reflection of the box, r // 2 > min(ih, iw) - 1, raises before anything is enqueued."""
-    from . import data, hip
+    from . import hip
     fn = "dehaze"
     q = dehaze_params(sz, r, eps, omega, tx, fn)
-    img = _as_u8(frames_u8, "frames", 4, fn)
-    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
-        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    img = _as_frames(frames_u8, "frames", _FRAMES, fn)
     B, ih, iw = img.shape[:3]
-    if sizes is not None and geom is not None:
-        raise RuntimeError(f"{fn}: give sizes or a geometry table, not both")
-    table = None
-    if sizes is not None:
-        arr = data.frame_sizes(sizes, B, fn)
-        for b, (h, w) in enumerate(arr.tolist()):
-            if h <= 0 or w <= 0 or h > ih or w > iw:
-                raise RuntimeError(f"{fn}: image {b}: bad size {h} x {w} in a slot of {ih} x {iw}")
-            if not dehaze_size_ok(h, w, q["r"]):
-                raise RuntimeError(f"{fn}: image {b}: {h} x {w} allows no single reflection of a box of r = {q['r']}")
-        table = np.zeros(B, data.GEOM_DTYPE)
-        table["ih"], table["iw"], table["thickness"] = arr[:, 0], arr[:, 1], 1
-    elif geom is None and not dehaze_size_ok(ih, iw, q["r"]):
+
+    def box_fits(b, h, w):                    # run per image behind its slot check, so the errors come in the order they did
+        if not dehaze_size_ok(h, w, q["r"]):
+            raise RuntimeError(f"{fn}: image {b}: {h} x {w} allows no single reflection of a box of r = {q['r']}")
+
+    arr =_host_sizes(sizes, geom, B, ih, iw, fn, also=box_fits)
+    if arr is None and geom is None and not dehaze_size_ok(ih, iw, q["r"]):
         raise RuntimeError(f"{fn}: frames of {ih} x {iw} allow no single reflection of a box of r = {q['r']}")
     img = img.to(device, non_blocking=True).contiguous()
     dev = img.device
     with torch.cuda.device(dev):
-        if table is not None:
-            geom = data.geometry_bytes(table).pin_memory().to(dev, non_blocking=True)
+        if arr is not None:
+            geom = _sizes_geom(arr, dev)
         out = torch.empty_like(img)
         t = torch.empty((B, ih, iw), dtype=torch.float64, device=dev) if transmission else None
         ws = torch.empty(hip.dehaze_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
@@ -1838,28 +1860,17 @@ def ace(frames_u8, sizes=None, geom=None, ratio=4.0, radius=3, s=0.005, bins=200
     Outside an image's corner the result is 0.  Returns out (B, ih, iw, 3) uint8 on the device.  flag: a zeroed int32 device
     tensor of one element, or None: it receives FLAG_ACE for a degenerate image (min(ih, iw) <= 2, or a constant R_0), which
     comes back unchanged, and hip.FLAG_GEOMETRY for a bad record of the table, which gives a zero image."""
-    from . import data, hip
+    from . import hip
     fn = "ace"
     q = ace_params(ratio, radius, s, bins, fn)
-    img = _as_u8(frames_u8, "frames", 4, fn)
-    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
-        raise RuntimeError(f"{fn}: expected frames of shape (B, ih, iw, 3) or (ih, iw, 3), got {tuple(img.shape)}")
+    img = _as_frames(frames_u8, "frames", _FRAMES, fn)
     B, ih, iw = img.shape[:3]
-    if sizes is not None and geom is not None:
-        raise RuntimeError(f"{fn}: give sizes or a geometry table, not both")
-    table = None
-    if sizes is not None:
-        arr = data.frame_sizes(sizes, B, fn)
-        for b, (h, w) in enumerate(arr.tolist()):
-            if h <= 0 or w <= 0 or h > ih or w > iw:
-                raise RuntimeError(f"{fn}: image {b}: bad size {h} x {w} in a slot of {ih} x {iw}")
-        table = np.zeros(B, data.GEOM_DTYPE)
-        table["ih"], table["iw"], table["thickness"] = arr[:, 0], arr[:, 1], 1
+    arr = _host_sizes(sizes, geom, B, ih, iw, fn)
     img = img.to(device, non_blocking=True).contiguous()
     dev = img.device
     with torch.cuda.device(dev):
-        if table is not None:
-            geom = data.geometry_bytes(table).pin_memory().to(dev, non_blocking=True)
+        if arr is not None:
+            geom = _sizes_geom(arr, dev)
         weights = torch.from_numpy(ace_weights(q["radius"])).to(dev)
         out = torch.empty_like(img)
         ws = torch.empty(hip.ace_workspace_bytes(B, ih, iw), dtype=torch.uint8, device=dev)
@@ -2166,20 +2177,11 @@ def jpeg_encode(images_u8, quality=95, subsampling=0, sizes=None, geom=None, cap
     slot.  capacity: the bytes of one slot of the arena, default `jpeg_capacity(h, w)`; a file that does not fit gets length
     0 and FLAG_JPEG_ARENA in flag (a zeroed int32 device tensor of one element; None: one is made), the others are
     unaffected.  Returns a `Jpegs`."""
-    from . import data, hip
+    from . import hip
     fn = "jpeg_encode"
-    img = _as_u8(images_u8, "images", 4, fn)
-    if img.dim() != 4 or img.shape[-1] != 3 or min(img.shape) <= 0:
-        raise RuntimeError(f"{fn}: expected images of shape (N, h, w, 3) or (h, w, 3), got {tuple(img.shape)}")
+    img = _as_frames(images_u8, "images", "(N, h, w, 3) or (h, w, 3)", fn)
     B, h, w = img.shape[:3]
-    if sizes is not None and geom is not None:
-        raise RuntimeError(f"{fn}: give sizes or a geometry table, not both")
-    table = None
-    if sizes is not None:
-        table = data.frame_sizes(sizes, B, fn)
-        for b, (ih, iw) in enumerate(table.tolist()):
-            if ih <= 0 or iw <= 0 or ih > h or iw > w:
-                raise RuntimeError(f"{fn}: image {b}: bad size {ih} x {iw} in a slot of {h} x {w}")
+    table = _host_sizes(sizes, geom, B, h, w, fn)
     _jpeg_params(quality, subsampling, fn)    # before anything is enqueued
     img = img.to(device, non_blocking=True).contiguous()
     dev = img.device

@@ -157,6 +157,17 @@ def test_degenerate_images_and_a_bad_record_inside_a_batch():
         assert np.array_equal(got[0][1], slots[1])
 
 
+def test_a_record_above_its_slot_and_an_empty_one():
+    """Image 1's record is no image, ih = 25 in a slot of 16 rows as much as ih = 0: a zero image and FLAG_GEOMETRY.  Image 0
+    as ever."""
+    import asy_vrnet_amd.hip as hip
+    slots = np.stack([rainy(61, 16, 24), rainy(62, 16, 24)])
+    for ih in (25, 0):
+        got = launch(slots, [(11, 17), (ih, 20)])
+        assert got[1] == hip.FLAG_GEOMETRY == 256 and not got[0][1].any()
+        same(got, 0, np.ascontiguousarray(slots[0, :11, :17]))
+
+
 def test_no_state_between_calls():
     import asy_vrnet_amd.hip as hip
     one = np.stack([rainy(61, 37, 53), rainy(62, 37, 53)])

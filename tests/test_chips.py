@@ -161,6 +161,31 @@ def test_ragged_chips_hold_no_padding_and_a_clamped_record_sets_the_flag():
     check(frames, rows, offsets, (8, 8), False, [(cap[0], 31), sizes[1]], hostile, want_flag=256)
 
 
+def test_a_record_above_its_slot_and_an_empty_one():
+    """Image 1's record is no image.  ih = 25 in a slot of 16 rows is clamped to the slot, so its rows are cut as in a 16 x 20
+    image; ih = 0 leaves it no pixel, so both its rows are empty crops: grey chips.  Either way FLAG_GEOMETRY, and image 0 as
+    ever."""
+    import asy_vrnet_amd.hip as hip
+    cap, good = (16, 24), (11, 17)
+    frames = frames_of(20, 2, *cap)
+    rows = np.array([[2, 1, 9, 8, 0],                 # image 0: 7 x 7
+                     [10, 5, 30, 30, 1],              # hostile: 7 x 6 after the clamp to 17 x 11
+                     [3, 2, 8, 14, 2],                # image 1: 5 x 12
+                     [0, 10, 24, 40, 3]], np.int32)   # 20 x 6 of 16 x 20
+    offsets = np.array([0, 2, 4], np.int32)
+    geom = data.geometry_bytes(data.frame_geometry([good, (16, 20)], (64, 64), True, cap)).cuda()
+    images = [frames[0, :11, :17], frames[1, :16, :20]]
+    for ih, records in ((25, [(1, 5, 12, 8, 8, 0, 0, 1), (1, 20, 6, 8, 8, 0, 0, 1)]), (0, [(1, 0, 0, 0, 0, 0, 0, 2)] * 2)):
+        hostile = geom.clone()
+        hostile.view(torch.int32).view(2, -1)[1, 0] = ih
+        chips, raw, table, summary, flag = launch(frames, rows, offsets, (8, 8), False, geom=hostile)
+        assert flag == hip.FLAG_GEOMETRY == 256 and summary == [4]
+        assert table[:4].tolist() == [(0, 7, 7, 8, 8, 0, 0, 1), (0, 7, 6, 8, 8, 0, 0, 1)] + records
+        for n in range(4):
+            want = render.chip_boxes_host(images[n // 2], rows[n:n + 1], (8, 8), False)[0] if ih or n < 2 else np.full((8, 8, 3), 128)
+            assert np.array_equal(chips[n], want) and np.array_equal(raw[n].view(np.float32), normalised(want).reshape(-1)), n
+
+
 def test_argument_checks():
     import asy_vrnet_amd.hip as hip
     frames, rows, offsets = cuda(frames_of(12, 2)), cuda(EDGE_ROWS), cuda(np.array([0, 0, len(EDGE_ROWS)], np.int32))

@@ -151,6 +151,28 @@ def test_ragged_crops_hold_no_padding():
     assert (arena[:3 * used] != 255).all()
 
 
+def test_a_record_above_its_slot_and_an_empty_one():
+    """Image 1's record is no image.  ih = 25 in a slot of 16 rows is clamped to the slot, so its rows are cut as in a 16 x 20
+    image; ih = 0 leaves it no pixel, so both its rows are empty records.  Either way FLAG_GEOMETRY, and image 0 as ever."""
+    import asy_vrnet_amd.hip as hip
+    cap, good = (16, 24), (11, 17)
+    frames = frames_of(20, 2, *cap)
+    rows = np.array([[2, 1, 9, 8, 0],                 # image 0: 7 x 7, 52 pixels of the arena
+                     [10, 5, 30, 30, 1],              # hostile: 7 x 6 after the clamp to 17 x 11, 44 pixels
+                     [3, 2, 8, 14, 2],                # image 1: 5 x 12
+                     [0, 10, 24, 40, 3]], np.int32)   # 20 x 6 of 16 x 20
+    offsets = np.array([0, 2, 4], np.int32)
+    geom = data.geometry_bytes(data.frame_geometry([good, (16, 20)], (64, 64), True, cap)).cuda()
+    for ih, records, used in ((25, [(96, 5, 12, 1), (156, 20, 6, 1)], 276), (0, [(0, 0, 0, 1), (0, 0, 0, 1)], 96)):
+        hostile = geom.clone()
+        hostile.view(torch.int32).view(2, -1)[1, 0] = ih
+        arena, table, summary, flag = launch(frames, rows, offsets, 2048, geom=hostile)
+        assert flag == hip.FLAG_GEOMETRY == 256 and summary == [4, used]
+        assert table[:4].tolist() == [(0, 7, 7, 0), (52, 7, 6, 0)] + records
+        want = expected_arena([frames[0, :11, :17], frames[1, :16, :20]], rows, table[:4], used)
+        assert np.array_equal(arena[:3 * used], want) and (arena[3 * used:] == FILL).all()
+
+
 def test_the_same_call_twice_gives_the_same_bytes():
     frames, rows = frames_of(10, 3), tiny_rows(300, 11)
     offsets = np.array([0, 100, 180, 300], np.int32)

@@ -192,6 +192,21 @@ def test_degenerate_images_and_a_bad_record_inside_a_batch():
         same(got, 5, last, sz=5, r=12)
 
 
+def test_a_record_above_its_slot_and_an_empty_one():
+    """Image 1's record is no image, ih = 25 in a slot of 16 rows as much as ih = 0: a zero image, t = 0, A = 0, the state
+    1.0 and FLAG_GEOMETRY.  Image 0 as ever: at 11 x 17 nothing is summed into A, so the rule returns it unchanged (FLAG_DEHAZE)."""
+    import asy_vrnet_amd.hip as hip
+    slots = np.stack([hazy(61, 16, 24), hazy(62, 16, 24)])
+    good = np.ascontiguousarray(slots[0, :11, :17])
+    for ih in (25, 0):
+        got = launch(slots, [(11, 17), (ih, 20)], sz=5, r=12)
+        out, t, A, degenerate, flag = got
+        assert flag == hip.FLAG_GEOMETRY | hip.FLAG_DEHAZE and degenerate.tolist() == [1, 1]
+        same(got, 0, good, sz=5, r=12)
+        assert np.array_equal(out[0, :11, :17], good)
+        assert not out[1].any() and not t[1].any() and not bits(A[1]).any()
+
+
 def test_no_state_between_calls():
     import asy_vrnet_amd.hip as hip
     one = np.stack([hazy(61, 48, 64), hazy(62, 48, 64)])

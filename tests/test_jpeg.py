@@ -126,6 +126,23 @@ def test_a_file_that_does_not_fit_its_slot():
         assert (files[0] == want[1]) == fits and (int(out.flag) == 0) == fits
 
 
+def test_a_record_above_its_slot_and_an_empty_one():
+    """Image 1's record is no image.  ih = 25 in a slot of 16 rows is clamped to the slot: the file of the 16 x 20 picture;
+    ih = 0 leaves it no pixel: no file, record (0, 3).  Either way FLAG_GEOMETRY, and image 0 as ever."""
+    import asy_vrnet_amd.hip as hip
+    slots = np.random.default_rng(12).integers(0, 256, (2, 16, 24, 3), dtype=np.uint8)
+    geom = data.geometry_bytes(data.frame_geometry([(11, 17), (16, 20)], S, True, (16, 24))).cuda()
+    good, clamped = (render.jpeg_encode_host(slots[0, :11, :17], 90, 0), render.jpeg_encode_host(slots[1, :16, :20], 90, 0))
+    for ih, record, file in ((25, [len(clamped), 1], clamped), (0, [0, 3], b"")):
+        hostile = geom.clone()
+        hostile.view(torch.int32).view(2, -1)[1, 0] = ih
+        out, files = encode(slots, 90, 0, geom=hostile, capacity=1 << 14)
+        assert int(out.flag) == hip.FLAG_GEOMETRY == 256
+        assert out.record.cpu().numpy().tolist() == [[len(good), 1], record]
+        same(files[0], good, "image 0")
+        same(files[1], file, "image 1")
+
+
 def test_two_calls_give_the_same_bytes():
     a = np.stack([natural(72, 104, 1), pictures(72, 104)["noise"]])
     for subsampling in (0, 2):

@@ -174,6 +174,33 @@ def test_ragged_slots(A):
     assert [h.tolist() for h in heads] == [[1, 1, s[0] * s[1], 0] for s in sizes]
 
 
+def test_a_record_above_its_slot_and_an_empty_one(A):
+    """Image 1's record is no image.  ih = 25 in a slot of 16 rows is clamped to the slot: the regions of a 16 x 20 image;
+    ih = 0 leaves it no pixel: no label, no record, no link, a head of zeros.  Either way FLAG_GEOMETRY, and image 0 as ever."""
+    slot, good = (16, 24), (11, 17)
+    p = A.decode.check_region_params(dict(connectivity=8, background=-1), "test")
+    maps = np.full((2,) + slot, 3, np.uint8)
+    maps[0, :11, :17] = np.random.RandomState(70).randint(0, 3, good)
+    maps[1, :16, :20] = np.random.RandomState(71).randint(0, 3, (16, 20))
+    per_image = [random_rows(60, 3, good), random_rows(61, 3, (16, 20))]
+    rows, offsets, cap = packed_rows(per_image)
+    buf = Buffers(A, 2, slot[0], slot[1], p["max_regions"], cap)
+    geom = A.data.geometry_bytes(A.data.frame_geometry([good, (16, 20)], (64, 64), True, slot)).cuda()
+    for ih, seen in ((25, [good, (16, 20)]), (0, [good])):
+        hostile = geom.clone()
+        hostile.view(torch.int32).view(2, -1)[1, 0] = ih
+        labels, table, head, links, flag = buf.call(A, cuda(maps), rows, offsets, p, hostile)
+        assert flag == A.hip.FLAG_GEOMETRY == 256
+        for b, (h, w) in enumerate(seen):
+            wl, wt, wh, wb, wf = A.decode.seg_regions_host(maps[b, :h, :w], per_image[b], **p)
+            assert wf == 0 and wh[0] > 3
+            assert np.array_equal(labels[b, :h, :w], wl) and not labels[b, h:].any() and not labels[b, :, w:].any()
+            assert np.array_equal(head[b], wh) and np.array_equal(words(table[b]), words(wt))
+            assert np.array_equal(links[b], np.concatenate([wb, np.zeros(cap - len(wb), np.int32)]))
+        if ih == 0:
+            assert not labels[1].any() and head[1].tolist() == [0, 0, 0, 0] and not words(table[1]).any() and not links[1].any()
+
+
 def test_the_eager_call(A):
     images = np.stack([blobs(), noise(0.5, 2, BIG)])
     dets = [np.array([[10.5, 20.2, 90.9, 200.0, 0.9, 0.8, 1], [0, 0, 150, 260, 0.9, 0.9, 2]], np.float32), None]
